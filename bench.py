@@ -115,6 +115,8 @@ def parse_args():
     ap.add_argument("--heuristic-cpu-worker", type=int, default=0, help=argparse.SUPPRESS)  # child of the batched heuristic entry
     ap.add_argument("--create-rate-worker", default=None, help=argparse.SUPPRESS)   # "r/n": child of the create_rate entry, bound to the CPU slice of rank r of n
     ap.add_argument("--no-affinity", action="store_true", help="do not bind a rank's host threads to the CPU slice of its GPU (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed back (cost, index path, partitioning, superreads of every table) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -195,6 +197,40 @@ def solution_tuple(table):
     a0, a1, q, tv, sid = table.super_reads()
     idx, tv2 = table.index_path()
     return (int(table.optimal_score()), idx.tolist(), tv.tolist(), tv2.tolist(), table.partitioning().tolist(), a0.tolist(), a1.tolist(), q.tolist(), sid.tolist())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def table_outputs(table):
+    """What the caller of a solve receives from one table (the drop-in class's getters), as named arrays."""
+    a0, a1, q, tv, sid = table.super_reads()
+    idx, path_tv = table.index_path()
+    return {"optimal_cost": [table.optimal_score()], "index_path": idx, "path_transmission": path_tv, "partitioning": table.partitioning(),
+            "superread_allele0": a0, "superread_allele1": a1, "superread_quality": q, "superread_transmission": tv, "superread_sample_ids": sid}
+
+
+def write_outputs(out_dir, outputs, limit=DUMP_LIMIT_BYTES):
+    """`outputs`: {table name: table_outputs(...)} -> out_dir/<table name>_<output>.npy (just <output>.npy for one unnamed table), float64
+    (every output is an integer below 2^53).  Past `limit` bytes in all, each large array keeps a fixed seeded sample of its elements (sorted positions)."""
+    import numpy as np
+
+    arrays = {}
+    for table, outs in outputs.items():
+        for key, value in outs.items():
+            arrays[f"{table}_{key}" if table else key] = np.asarray(value, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = 0.95 * limit / total   # (room for the small arrays kept whole and the .npy headers)
+        for name, a in arrays.items():
+            if a.size > 1024:
+                pick = np.sort(np.random.default_rng(12345).choice(a.size, max(1024, int(a.size * keep)), replace=False))
+                arrays[name] = a.reshape(-1)[pick]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} output arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB{', sampled' if total > limit else ''}) written to {out_dir}",
+          file=sys.stderr, flush=True)
 
 
 def reference_seconds(args, seed, n_columns, want_solution=False):
@@ -1000,6 +1036,10 @@ def main():
     if args.workload:
         for key, value in WORKLOADS[args.workload].items():
             setattr(args, key, value)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.dump_outputs and (args.genotype or args.heuristic or args.shim):
+        raise SystemExit("--dump-outputs writes the phasing tables' outputs: not available with --genotype / --heuristic / --shim")
     import __graft_entry__ as entry
 
     if not os.path.exists(os.path.join(ROOT, "whatshap_amd", "libwhatshap_amd.so")):
@@ -1158,7 +1198,8 @@ def main():
             host_shapes += [(first[0], first[1], (whole + 1) // 2), (first[0], first[1], (whole + 2) // 3), (first[0], first[1], (whole + 1) // 2, 2)]
     host_shapes = list(dict.fromkeys(tuple(h) + (1,) * (4 - len(h)) for h in host_shapes))   # (workers, threads per create, tables per window, windows on the device)
 
-    def fresh_step(shape):
+    def fresh_step(shape, keep=None):
+        # keep: a dict that receives what the step's tables hand back (--dump-outputs), read out before their destroy and NOT timed
         ta = time.perf_counter()
         if len(problems) == 1:
             t = _native.NativeTable(problems[0], device=device, path=native_path, solve=False, options=option_dict(args))
@@ -1168,17 +1209,24 @@ def main():
             tc = time.perf_counter()
             st = t.stats()
             checksum = int(t.optimal_score())
+            if keep is not None:
+                keep.update(outputs_of([t]))
+            tk = time.perf_counter()
             t.close()
             td = time.perf_counter()
-            return {"wall_ms": (td - ta) * 1e3, "create_ms": (tb - ta) * 1e3, "solve_ms": (tc - tb) * 1e3, "close_ms": (td - tc) * 1e3,
-                    "device_ms": st["total_ms"], "superreads_ms": st["host_finish_ms"], "flatten_ms": st.get("host_flatten_ms"), "checksum": checksum}
+            return {"wall_ms": (td - tk + tc - ta) * 1e3, "create_ms": (tb - ta) * 1e3, "solve_ms": (tc - tb) * 1e3, "close_ms": (td - tk) * 1e3,
+                    "device_ms": st["total_ms"], "superreads_ms": st["host_finish_ms"], "flatten_ms": st.get("host_flatten_ms"), "checksum": checksum,
+                    "untimed_ms": (tk - tc) * 1e3}
         trace = []
         solved = solve_blocks(problems, device=device, path=native_path, max_in_flight=shape[2], release=True,
                               create_threads=shape[0], host_threads_per_create=shape[1], windows_on_device=shape[3], trace=trace)
         tc = time.perf_counter()
         checksum = int(sum(t.optimal_score() for t in solved))
+        if keep is not None:
+            keep.update(outputs_of(solved))
+        tk = time.perf_counter()
         close_tables(solved)     # (on a few threads: 7 ms for 96 tables one after the other)
-        td = time.perf_counter()
+        td = time.perf_counter() - (tk - tc)
         # the submitting thread's time line: waiting for a window's creates (not hidden under a solve) / enqueue + device + result extraction
         create_wait = solve_ms = 0.0
         last = 0.0
@@ -1191,7 +1239,7 @@ def main():
                 solve_ms += ms - last
             last = ms
         return {"wall_ms": (td - ta) * 1e3, "create_ms": create_wait, "solve_ms": solve_ms, "close_ms": (td - tc) * 1e3, "checksum": checksum,
-                "other_ms": (tc - ta) * 1e3 - create_wait - solve_ms}   # (the work queue's own tail: device releases on the pool's threads, the pool's shutdown)
+                "other_ms": (tc - ta) * 1e3 - create_wait - solve_ms, "untimed_ms": (tk - tc) * 1e3}   # (the work queue's own tail: device releases on the pool's threads, the pool's shutdown)
 
     tried = []
     shape = host_shapes[0]
@@ -1209,13 +1257,22 @@ def main():
         shape = (best["create_threads"], best["host_threads_per_create"], best["tables_per_window"], best["windows_on_device"])
     for _ in range(max(0, args.warmup - 1 - len(host_shapes))):
         fresh_step(shape)
+    def outputs_of(step_tables):
+        # the tables of a step come back in the order of `problems` (this rank's blocks); one block: plain names
+        if len(blocks) == 1:
+            return {"": table_outputs(t) for t in step_tables}
+        return {f"block{blocks[b][0]}": table_outputs(t) for b, t in zip(mine, step_tables)}
+
+    dumped = {}
     sync()
     t0 = time.perf_counter()
     fresh = []
-    for _ in range(args.steps):
-        fresh.append(fresh_step(shape))
+    for i in range(args.steps):
+        fresh.append(fresh_step(shape, keep=dumped if (args.dump_outputs and i == args.steps - 1) else None))
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - sum(r.get("untimed_ms", 0.0) for r in fresh) * 1e-3
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, dumped, limit=DUMP_LIMIT_BYTES // world)
     step_s = [r["wall_ms"] * 1e-3 for r in fresh]
     if any(r["checksum"] != int(totals[2]) for r in fresh):
         raise SystemExit(f"rank {rank}: a fresh solve's cost checksum {[r['checksum'] for r in fresh]} differs from the resident tables' {int(totals[2])}")

@@ -11,7 +11,7 @@ import os, re, subprocess, sys
 src = sys.argv[1] if len(sys.argv) > 1 else "dp_device.hip"
 filt = sys.argv[2] if len(sys.argv) > 2 else "."
 root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "whatshap_amd", "csrc")
-out = "/tmp/whamd_isa"; os.makedirs(out, exist_ok=True)
+out = os.path.join(root, "build", "isa"); os.makedirs(out, exist_ok=True)   # inside the checkout (git-ignored): no file shared with other users
 asm = os.path.join(out, src.replace(".hip", ".s"))
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", src, "-o", asm], cwd=root, check=True, stderr=subprocess.DEVNULL)
 name, body, kernels = None, [], {}

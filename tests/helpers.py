@@ -146,3 +146,132 @@ def wmec_cost_of_partitioning(problem, partitioning):
     s = np.bincount(inv, weights=q * disagree, minlength=uniq.size)
     w = np.bincount(inv, weights=q, minlength=uniq.size)
     return int(np.minimum(s, w - s).sum())
+
+
+# ---- the compiled reference's PedMecHeuristic, live (oracle/_ref) or as recorded from it (tests/golden/reference_heuristic.npz)
+# oracle/_ref is built only where the reference sources are; everywhere else the tests compare against what it returned for the
+# same inputs.  To (re)record: build oracle/_ref, then run the heuristic tests with WHAMD_RECORD_REFERENCE=1 set on an MI355X
+# (python -m pytest tests/test_heuristic.py tests/test_gpu_heuristic.py): every live answer is added to the file at exit.
+REFERENCE_HEURISTIC_RECORD = os.path.join(GOLDEN_DIR, "reference_heuristic.npz")
+_HEURISTIC_FIELDS = ("score", "bipartition", "transmission", "haplotypes", "mutated")
+_recorded = None
+_to_record = {}
+
+
+def problem_digest(problem, *extra):
+    """sha256 of every input array of a ProblemArrays (and `extra`): the key of a recorded reference answer."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for name in ("read_ptr", "var_position", "var_allele", "var_quality", "read_sample_id", "individual_id", "triple_ids", "genotype",
+                 "genotype_likelihoods", "recombcost", "positions"):
+        a = getattr(problem, name)
+        h.update(name.encode())
+        if a is not None:
+            h.update(str(a.dtype).encode() + str(a.shape).encode() + np.ascontiguousarray(a).tobytes())
+    h.update(repr((problem.distrust_genotypes, problem.n_variants) + tuple(extra)).encode())
+    return h.hexdigest()[:32]
+
+
+class RecordedHeuristic:
+    """The getters of oracle.ReferenceHeuristic, answered from the record."""
+
+    def __init__(self, fields):
+        self._f = fields
+
+    def score(self):
+        return float(self._f["score"][0])
+
+    def bipartition(self):
+        return self._f["bipartition"]
+
+    def transmission(self):
+        return self._f["transmission"]
+
+    def haplotypes(self):
+        return self._f["haplotypes"], self._f["mutated"]
+
+
+def _save_record():
+    old = dict(np.load(REFERENCE_HEURISTIC_RECORD)) if os.path.exists(REFERENCE_HEURISTIC_RECORD) else {}
+    old.update(_to_record)
+    np.savez_compressed(REFERENCE_HEURISTIC_RECORD, **old)
+
+
+def reference_heuristic(problem, row_limit):
+    """oracle.ReferenceHeuristic(problem, row_limit) where oracle/_ref is built, else its recorded answer for this very input."""
+    global _recorded
+    import oracle
+
+    key = problem_digest(problem, "heuristic", int(row_limit))
+    if oracle.have_reference():
+        ref = oracle.ReferenceHeuristic(problem, row_limit=row_limit)
+        if os.environ.get("WHAMD_RECORD_REFERENCE"):
+            if not _to_record:
+                import atexit
+
+                atexit.register(_save_record)
+            haps, mut = ref.haplotypes()
+            values = (np.array([ref.score()], dtype=np.float32), ref.bipartition(), ref.transmission(), haps, mut)
+            _to_record.update({f"{key}/{f}": v for f, v in zip(_HEURISTIC_FIELDS, values)})
+        return ref
+    if _recorded is None:
+        _recorded = np.load(REFERENCE_HEURISTIC_RECORD) if os.path.exists(REFERENCE_HEURISTIC_RECORD) else {}
+    if f"{key}/score" not in _recorded:
+        raise AssertionError(f"no recorded reference answer for this input ({key}, row limit {row_limit}) in {REFERENCE_HEURISTIC_RECORD}, "
+                             "and oracle/_ref is not built: re-record (see tests/helpers.py)")
+    return RecordedHeuristic({f: _recorded[f"{key}/{f}"] for f in _HEURISTIC_FIELDS})
+
+
+# ---- the compiled reference's PedigreeDPTable, live or as recorded from it (tests/golden/reference_tables.json.gz); recorded the same
+# way: WHAMD_RECORD_REFERENCE=1 python -m pytest tests/test_oracle.py with oracle/_ref built
+REFERENCE_TABLE_RECORD = os.path.join(GOLDEN_DIR, "reference_tables.json.gz")
+_recorded_tables = None
+_tables_to_record = {}
+
+
+def _save_table_record():
+    import gzip
+
+    old = {}
+    if os.path.exists(REFERENCE_TABLE_RECORD):
+        with gzip.open(REFERENCE_TABLE_RECORD, "rt") as f:
+            old = json.load(f)
+    old.update(_tables_to_record)
+    with gzip.GzipFile(REFERENCE_TABLE_RECORD, "wb", mtime=0) as f:
+        f.write(json.dumps(old, sort_keys=True, separators=(",", ":")).encode())
+
+
+def reference_solution(problem):
+    """table_solution(oracle.ReferenceTable(problem)) where oracle/_ref is built, else its recorded answer for this very input;
+    raises oracle.OracleError with the reference's message where the reference refused the input."""
+    global _recorded_tables
+    import gzip
+
+    import oracle
+
+    key = problem_digest(problem, "table")
+    if oracle.have_reference():
+        try:
+            rec = {"solution": table_solution(oracle.ReferenceTable(problem)), "error": None}
+        except oracle.OracleError as e:
+            rec = {"solution": None, "error": str(e)}
+        if os.environ.get("WHAMD_RECORD_REFERENCE"):
+            if not _tables_to_record:
+                import atexit
+
+                atexit.register(_save_table_record)
+            _tables_to_record[key] = rec
+    else:
+        if _recorded_tables is None:
+            _recorded_tables = {}
+            if os.path.exists(REFERENCE_TABLE_RECORD):
+                with gzip.open(REFERENCE_TABLE_RECORD, "rt") as f:
+                    _recorded_tables = json.load(f)
+        if key not in _recorded_tables:
+            raise AssertionError(f"no recorded reference answer for this input ({key}) in {REFERENCE_TABLE_RECORD}, and oracle/_ref is not built: "
+                                 "re-record (see tests/helpers.py)")
+        rec = _recorded_tables[key]
+    if rec["error"] is not None:
+        raise oracle.OracleError(rec["error"])
+    return rec["solution"]

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import load_golden, problem_from_json
+from helpers import load_golden, problem_from_json, reference_heuristic
 from heuristic_cases import random_cases, result_tuple, synthetic_cases
 from whatshap_amd import _native
 from whatshap_amd.synthetic import synthetic_block
@@ -20,14 +20,14 @@ def device(problem, row_limit):
 
 def test_random_instances_vs_the_compiled_reference():
     for name, problem, row_limit in random_cases(815, 50):
-        want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(problem, row_limit=row_limit))
+        want = oracle.heuristic_tuple(reference_heuristic(problem, row_limit))
         assert result_tuple(device(problem, row_limit)) == want, name
 
 
 @pytest.mark.parametrize("case", synthetic_cases(), ids=lambda c: c[0])
 def test_synthetic_blocks_vs_the_compiled_reference(case):
     name, problem, row_limit = case
-    want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(problem, row_limit=row_limit))
+    want = oracle.heuristic_tuple(reference_heuristic(problem, row_limit))
     got = device(problem, row_limit)
     assert result_tuple(got) == want, name
     host = _native.pedmec_heuristic(problem, row_limit=row_limit, host_diagnostic=True)
@@ -46,7 +46,7 @@ def test_golden_vectors():
 def test_coverages_the_exact_dp_cannot_afford(kw, row_limit):
     """Thousands of columns at coverage 18 - 40 (the exact table stops at 25 reads per column): the use the solver exists for."""
     p = synthetic_block(**kw)
-    want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(p, row_limit=row_limit))
+    want = oracle.heuristic_tuple(reference_heuristic(p, row_limit))
     got = device(p, row_limit)
     assert result_tuple(got) == want
     assert got["stats"]["max_solutions"] >= min(row_limit, 16)
@@ -55,7 +55,7 @@ def test_coverages_the_exact_dp_cannot_afford(kw, row_limit):
 def test_fewer_threads_than_solutions(monkeypatch):
     """One wavefront for a beam of hundreds of solutions (WHAMD_HEURISTIC_THREADS): every phase loops over the beam in rounds."""
     p = synthetic_block(n_variants=800, coverage=26, seed=16, trio=True)
-    want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(p, row_limit=128))
+    want = oracle.heuristic_tuple(reference_heuristic(p, 128))
     monkeypatch.setenv("WHAMD_HEURISTIC_THREADS", "64")
     assert result_tuple(device(p, 128)) == want
 
@@ -82,7 +82,7 @@ def test_drop_in_class_and_shim():
         rs.add(read)
     recomb = [int(x) for x in p.recombcost]
     solver = PedMecHeuristic(rs, recomb, ped, 64, distrust_genotypes=False, positions=[int(x) for x in p.positions], allow_mutations=True, verbosity=0)
-    want = oracle.ReferenceHeuristic(p, row_limit=64)
+    want = reference_heuristic(p, 64)
     superreads, transmission = solver.get_super_reads()
     haps, mut = want.haplotypes()
     assert transmission == want.transmission().tolist() and solver.get_optimal_cost() == 0
@@ -118,7 +118,7 @@ def test_32_tables_in_one_launch_equal_single_solves_and_the_reference():
         assert len(got) == 32
         for i, (p, g) in enumerate(zip(problems, got)):
             if i % 4 == 0 or row_limit == 64:
-                want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(p, row_limit=row_limit))
+                want = oracle.heuristic_tuple(reference_heuristic(p, row_limit))
                 assert result_tuple(g) == want, (row_limit, specs[i])
             if i % 8 == 1:
                 assert result_tuple(g) == result_tuple(device(p, row_limit)), (row_limit, specs[i])

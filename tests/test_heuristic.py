@@ -6,7 +6,7 @@ vectors.  Everything the reference's getters return is compared: bipartition, tr
 import pytest
 
 import oracle
-from helpers import load_golden, problem_from_json
+from helpers import load_golden, problem_from_json, reference_heuristic
 from heuristic_cases import random_cases, result_tuple, synthetic_cases
 from whatshap_amd import _native
 
@@ -15,18 +15,16 @@ def host(problem, row_limit):
     return result_tuple(_native.pedmec_heuristic(problem, row_limit=row_limit, host_diagnostic=True))
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 def test_random_instances_vs_the_compiled_reference():
     for name, problem, row_limit in random_cases(4711, 60):
-        want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(problem, row_limit=row_limit))
+        want = oracle.heuristic_tuple(reference_heuristic(problem, row_limit))
         assert host(problem, row_limit) == want, name
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 @pytest.mark.parametrize("case", synthetic_cases(), ids=lambda c: c[0])
 def test_synthetic_blocks_vs_the_compiled_reference(case):
     name, problem, row_limit = case
-    want = oracle.heuristic_tuple(oracle.ReferenceHeuristic(problem, row_limit=row_limit))
+    want = oracle.heuristic_tuple(reference_heuristic(problem, row_limit))
     got = _native.pedmec_heuristic(problem, row_limit=row_limit, host_diagnostic=True)
     assert result_tuple(got) == want, name
     assert 1 <= got["stats"]["max_solutions"] and got["stats"]["n_columns"] == problem.n_variants

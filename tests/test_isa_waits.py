@@ -39,10 +39,10 @@ def test_the_genotyping_combine_requests_everything_before_it_waits():
 # ---- round 5: the X runs (kernels_slots.h, slot_runx) -- the column trip as it is MEANT to be issued, pinned on the cross-compiled assembly
 def _device_asm():
     """dp_device.hip compiled to gfx950 assembly (once per test session: ~1 min)."""
-    out = "/tmp/whamd_isa"
+    src_dir = os.path.join(ROOT, "whatshap_amd", "csrc")
+    out = os.path.join(src_dir, "build", "isa")   # this checkout's own (git-ignored) build directory, as scripts/isa_wait_audit.py uses
     os.makedirs(out, exist_ok=True)
     asm = os.path.join(out, "dp_device_xrun.s")
-    src_dir = os.path.join(ROOT, "whatshap_amd", "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, n)) for n in os.listdir(src_dir) if n.endswith((".h", ".hip")))
     if not os.path.exists(asm) or os.path.getmtime(asm) < newest:
         subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "dp_device.hip", "-o", asm], cwd=src_dir, check=True,

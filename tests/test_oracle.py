@@ -7,7 +7,7 @@ import random
 import pytest
 
 import oracle
-from helpers import first_difference, load_golden, problem_from_json, table_solution
+from helpers import first_difference, load_golden, problem_from_json, reference_solution, table_solution
 from reference_cases import all_cases
 from whatshap_amd.core import problem_from_objects
 from whatshap_amd.synthetic import random_small_instance, synthetic_block
@@ -79,14 +79,13 @@ def test_reference_known_answers(case):
             assert got == tuple(sorted(expected)), (case.name, ind)
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 def test_oracle_vs_compiled_reference_random():
     rng = random.Random(4242)
     for i in range(300):
         p = random_small_instance(rng)
         want, werr = None, None
         try:
-            want = table_solution(oracle.ReferenceTable(p))
+            want = reference_solution(p)
         except oracle.OracleError as e:
             werr = str(e)
         got, gerr = oracle_outcome(p)
@@ -94,19 +93,16 @@ def test_oracle_vs_compiled_reference_random():
         assert got == want, f"{i}: {first_difference(want, got)}"
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 @pytest.mark.parametrize("mode", ["three_children", "three_trios", "big_family"])
 def test_oracle_vs_compiled_reference_larger_pedigrees(mode):
     """Three trios (T = 64) and a seven-individual family: the restatement is general in T and in the number of individuals,
     like the reference (src/pedigreepartitions.cpp:7-42); pinned against the compiled reference before the device path is."""
-    if not oracle.have_reference():
-        pytest.skip("compiled reference not built")
     rng = random.Random({"three_children": 91, "three_trios": 92, "big_family": 93}[mode])
     compared = 0
     for _ in range(60):
         p = random_small_instance(rng, mode=mode, max_variants=7, max_reads=6)
         try:
-            want = table_solution(oracle.ReferenceTable(p))
+            want = reference_solution(p)
         except oracle.OracleError as e:
             with pytest.raises(oracle.OracleError, match=str(e)):
                 oracle.OracleTable(p)
@@ -116,12 +112,11 @@ def test_oracle_vs_compiled_reference_larger_pedigrees(mode):
     assert compared > 40
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 @pytest.mark.parametrize("kw", [dict(n_variants=300, coverage=10, seed=31), dict(n_variants=150, coverage=9, seed=32, trio=True),
                                 dict(n_variants=3000, coverage=14, seed=33, n_columns_limit=40)], ids=str)
 def test_oracle_vs_compiled_reference_synthetic(kw):
     p = synthetic_block(**kw)
-    assert table_solution(oracle.OracleTable(p)) == table_solution(oracle.ReferenceTable(p))
+    assert table_solution(oracle.OracleTable(p)) == reference_solution(p)
 
 
 def _with_blank_alleles(p, rng):
@@ -141,7 +136,6 @@ def _with_blank_alleles(p, rng):
                                  p.distrust_genotypes, n_variants=p.n_variants)
 
 
-@pytest.mark.skipif(not oracle.have_reference(), reason="oracle/_ref not built (no reference tree here)")
 def test_blank_alleles_inside_reads_vs_compiled_reference():
     """Entry::BLANK (2) as the allele of a read's own variant is legal input for the reference: set/update_partitioning
     skip it (src/pedigreecolumncostcomputer.cpp:69-70, 93-94).  The restatement must treat it the same way (its phred
@@ -154,7 +148,7 @@ def test_blank_alleles_inside_reads_vs_compiled_reference():
     for i in range(120):
         p = _with_blank_alleles(random_small_instance(rng, allow_conflict=False, max_variants=9, max_reads=7), rng)
         n_with_blank += int((p.var_allele == 2).any())
-        want = table_solution(oracle.ReferenceTable(p))
+        want = reference_solution(p)
         got, err = oracle_outcome(p)
         assert err is None and got == want, f"{i}: {first_difference(want, got)}"
     assert n_with_blank > 40
