@@ -374,6 +374,100 @@ void whamd_release_caches(void);
  * the reference frees everything with the table. */
 uint64_t whamd_host_pool_idle_bytes(void);
 
+/* ---- Allele detection by re-alignment (ReadSetReader.detect_alleles_by_alignment, whatshap/variants.py:685-912) ----------------
+ * For every (alignment, variant) pair that _iterate_cigar (whatshap/_variants.pyx:10-81) yields, ReadSetReader.realign cuts a window of
+ * the read, builds one padded window per allele and keeps the allele whose edit distance to the read window is strictly smallest
+ * (unit costs: edit_distance, quality 30; affine: edit_distance_affine_gap, quality d0 - d1, whatshap/align.pyx:16-196).  Here the
+ * CIGAR walk and the windows are computed on the host (csrc/realign.cpp, several threads), the distances and the decision on the
+ * device (csrc/realign_device.hip); only the per-job result comes back.  Views carry no pysam object; every pointer is borrowed for
+ * the duration of the call.
+ * Errors (WHAMD_ERR_INVALID, nothing launched) carry the reference's exception as a prefix of the message:
+ *   "ValueError: Unsupported CIGAR operation: N"         (_iterate_cigar)
+ *   "AssertionError: ..."                                (cigar_prefix_length, the window asserts of realign, unsorted variants,
+ *                                                         affine costs without their parameters)
+ *   "IndexError: list index out of range"                (an allowed allele set that keeps no allele)
+ *   "TypeError: ..."                                     (a job on an alignment without query sequence)
+ * When several alignments fail, the first one in alignment order is reported. */
+typedef struct whamd_realign_alignments_view {
+	uint64_t n_alignments;
+	const int64_t* reference_start;  /* [n] AlignedSegment.reference_start */
+	const uint64_t* first_variant;   /* [n] the `j` of detect_alleles_by_alignment, or NULL (0 for every alignment) */
+	const uint64_t* cigar_ptr;       /* [n + 1] ops of alignment a: cigar_ptr[a] .. cigar_ptr[a+1]-1 */
+	const uint32_t* cigar_op;        /* MIDNSHP=X as 0 .. 8 (anything else: ValueError when reached) */
+	const uint32_t* cigar_len;
+	const uint64_t* seq_ptr;         /* [n + 1] query_sequence bytes of alignment a: seq[seq_ptr[a] .. seq_ptr[a+1]-1] */
+	const uint8_t* seq;
+	const uint8_t* seq_present;      /* [n] 0: query_sequence is None; NULL: every alignment has one */
+} whamd_realign_alignments_view;
+
+typedef struct whamd_realign_variants_view {
+	uint64_t n_variants;             /* in the order of the caller's list (the walk asserts what the reference asserts about it) */
+	const int64_t* position;         /* [n] VcfVariant.position (0-based) */
+	const uint64_t* ref_ptr;         /* [n + 1] reference_allele bytes */
+	const uint8_t* ref_bytes;
+	const uint64_t* alt_ptr;         /* [n + 1] alt alleles of variant v: alt_ptr[v] .. alt_ptr[v+1]-1 (allele index 1 ..) */
+	const uint64_t* alt_byte_ptr;    /* [n_alts + 1] bytes of every alt allele */
+	const uint8_t* alt_bytes;
+	const uint64_t* restrict_ptr;    /* [n + 1] Genotype.as_vector() of restricted_genotypes[v], or NULL: no restriction at all */
+	const int64_t* restrict_alleles;
+	const uint8_t* restrict_present; /* [n] 0: no restriction for this variant; NULL: every variant has its list */
+} whamd_realign_variants_view;
+
+/* The reference as the bytes of one slice: bytes[k] is chromosome position offset + k.  chromosome_length is len(reference) (what
+ * realign asserts against); the slice must cover every window (the span the alignments touch plus the overhang) or the call fails. */
+typedef struct whamd_realign_reference_view {
+	const uint8_t* bytes;
+	uint64_t offset;
+	uint64_t length;
+	uint64_t chromosome_length;
+} whamd_realign_reference_view;
+
+/* overhang, use_affine, gap_start, gap_extend, default_mismatch of detect_alleles_by_alignment.  gap_start / gap_extend are what
+ * the Cython int parameters hold (the binding truncates toward zero), default_mismatch is rounded to f32 as the float table is.
+ * affine_unset = 1: use_affine with one of the three left as None -- the first job realign computes distances for fails with
+ * "AssertionError: ..." where the reference asserts them (after slicing the query, before the distances); no job, no error. */
+typedef struct whamd_realign_params {
+	int64_t overhang;
+	int32_t use_affine;
+	int32_t gap_start;
+	int32_t gap_extend;
+	float default_mismatch;
+	int32_t affine_unset;
+} whamd_realign_params;
+
+typedef struct whamd_realign_stats {
+	uint64_t n_alignments;
+	uint64_t n_jobs;                 /* (alignment, variant) pairs realign computed distances for (symbolic alleles make none) */
+	uint64_t n_pairs;                /* (job, allele) distances */
+	uint64_t n_results;              /* jobs with a decision (what the generator yields) */
+	double host_walk_ms;             /* wall: CIGAR walk, windows, descriptors into the pinned staging buffer */
+	double upload_ms;                /* HIP events: reference slice, variant tables, descriptors, query windows */
+	double kernel_ms;                /* HIP events: distances + decision */
+	double download_ms;              /* HIP events: the per-job results */
+	double host_finish_ms;           /* wall: per-alignment result lists */
+	double total_ms;                 /* wall of the whole call */
+} whamd_realign_stats;
+
+typedef struct whamd_realign whamd_realign; /* opaque */
+
+/* One call for a batch of alignments against one variant list and one reference (a chromosome x sample of _alignments_to_reads). */
+whamd_status_t whamd_realign_detect(const whamd_realign_alignments_view* alignments, const whamd_realign_variants_view* variants,
+                                    const whamd_realign_reference_view* reference, const whamd_realign_params* params, int device,
+                                    whamd_realign** out);
+/* Results in the order detect_alleles_by_alignment yields them, alignment after alignment: (variant index, allele, quality) of
+ * alignment a are entries ptr[a] .. ptr[a+1]-1.  ptr_out: [n_alignments + 1]; the others [whamd_realign_result_count].  NULL skips. */
+uint64_t whamd_realign_result_count(const whamd_realign* r);
+whamd_status_t whamd_realign_get(const whamd_realign* r, uint64_t* ptr_out, uint64_t* variant_out, int32_t* allele_out, int64_t* quality_out);
+whamd_status_t whamd_realign_get_stats(const whamd_realign* r, whamd_realign_stats* stats_out);
+void whamd_realign_destroy(whamd_realign* r);
+
+/* Raw distances for a batch of (query, target) pairs: edit_distance(query, target) (unbanded, whatshap/align.pyx:16-97) or
+ * edit_distance_affine_gap(query, target, mismatch_cost, gap_start, gap_extend) (:103-196) with one f32 mismatch cost per query
+ * byte (mismatch_cost is laid out like `query`; NULL for unit costs).  distance_out: [n_pairs]. */
+whamd_status_t whamd_edit_distance_batch(uint64_t n_pairs, const uint64_t* query_ptr, const uint8_t* query, const uint64_t* target_ptr,
+                                         const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start,
+                                         int32_t gap_extend, int device, int64_t* distance_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,17 @@ whamd_status_t whamd_debug_pedmec_heuristic_create_host(const whamd_readset_view
                                                         const uint32_t* positions, size_t n_positions, uint32_t row_limit, int allow_mutations,
                                                         whamd_heuristic** out);
 
+/* HOST-ONLY DIAGNOSTIC of allele detection (csrc/realign.cpp): the same CIGAR walk as whamd_realign_detect, then both distances and the
+ * decision restated on one CPU thread -- the cross-check the CPU test-suite compares with the reference's recorded yields; never what
+ * the product calls.  The handle is read with the whamd_realign_* getters of the debug library. */
+whamd_status_t whamd_debug_realign_detect_host(const whamd_realign_alignments_view* alignments, const whamd_realign_variants_view* variants,
+                                               const whamd_realign_reference_view* reference, const whamd_realign_params* params,
+                                               whamd_realign** out);
+/* whamd_edit_distance_batch on the host (same restatement as above). */
+whamd_status_t whamd_debug_edit_distance_host(uint64_t n_pairs, const uint64_t* query_ptr, const uint8_t* query, const uint64_t* target_ptr,
+                                              const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start,
+                                              int32_t gap_extend, int64_t* distance_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,35 @@ class HeuristicJob(C.Structure):
                 ("n_positions", C.c_size_t), ("row_limit", C.c_uint32), ("allow_mutations", C.c_int)]
 
 
+class RealignAlignmentsView(C.Structure):
+    _fields_ = [("n_alignments", C.c_uint64), ("reference_start", C.POINTER(C.c_int64)), ("first_variant", C.POINTER(C.c_uint64)),
+                ("cigar_ptr", C.POINTER(C.c_uint64)), ("cigar_op", C.POINTER(C.c_uint32)), ("cigar_len", C.POINTER(C.c_uint32)),
+                ("seq_ptr", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint8)), ("seq_present", C.POINTER(C.c_uint8))]
+
+
+class RealignVariantsView(C.Structure):
+    _fields_ = [("n_variants", C.c_uint64), ("position", C.POINTER(C.c_int64)), ("ref_ptr", C.POINTER(C.c_uint64)), ("ref_bytes", C.POINTER(C.c_uint8)),
+                ("alt_ptr", C.POINTER(C.c_uint64)), ("alt_byte_ptr", C.POINTER(C.c_uint64)), ("alt_bytes", C.POINTER(C.c_uint8)),
+                ("restrict_ptr", C.POINTER(C.c_uint64)), ("restrict_alleles", C.POINTER(C.c_int64)), ("restrict_present", C.POINTER(C.c_uint8))]
+
+
+class RealignReferenceView(C.Structure):
+    _fields_ = [("bytes", C.POINTER(C.c_uint8)), ("offset", C.c_uint64), ("length", C.c_uint64), ("chromosome_length", C.c_uint64)]
+
+
+class RealignParams(C.Structure):
+    _fields_ = [("overhang", C.c_int64), ("use_affine", C.c_int32), ("gap_start", C.c_int32), ("gap_extend", C.c_int32), ("default_mismatch", C.c_float),
+                ("affine_unset", C.c_int32)]
+
+
+class RealignStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_alignments", "n_jobs", "n_pairs", "n_results")] + [
+        (name, C.c_double) for name in ("host_walk_ms", "upload_ms", "kernel_ms", "download_ms", "host_finish_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -271,6 +300,12 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_pedmec_heuristic_create_host.restype = C.c_int
     L.whamd_debug_pedmec_heuristic_create_host.argtypes = [C.POINTER(ReadSetView), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(PedigreeView), C.c_int,
                                                            C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_debug_realign_detect_host.restype = C.c_int
+    L.whamd_debug_realign_detect_host.argtypes = [C.POINTER(RealignAlignmentsView), C.POINTER(RealignVariantsView), C.POINTER(RealignReferenceView),
+                                                  C.POINTER(RealignParams), C.POINTER(C.c_void_p)]
+    L.whamd_debug_edit_distance_host.restype = C.c_int
+    L.whamd_debug_edit_distance_host.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
+                                                 C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     _debug_lib = L
     return L
 
@@ -370,6 +405,20 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
         C.POINTER(ReadSetView), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t, C.c_uint32, C.c_int,
         C.POINTER(C.c_uint8), C.POINTER(C.c_uint64),
     ]
+    L.whamd_realign_detect.restype = C.c_int
+    L.whamd_realign_detect.argtypes = [C.POINTER(RealignAlignmentsView), C.POINTER(RealignVariantsView), C.POINTER(RealignReferenceView),
+                                       C.POINTER(RealignParams), C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_realign_result_count.restype = C.c_uint64
+    L.whamd_realign_result_count.argtypes = [C.c_void_p]
+    L.whamd_realign_get.restype = C.c_int
+    L.whamd_realign_get.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.whamd_realign_get_stats.restype = C.c_int
+    L.whamd_realign_get_stats.argtypes = [C.c_void_p, C.POINTER(RealignStats)]
+    L.whamd_realign_destroy.restype = None
+    L.whamd_realign_destroy.argtypes = [C.c_void_p]
+    L.whamd_edit_distance_batch.restype = C.c_int
+    L.whamd_edit_distance_batch.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
+                                            C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_int64)]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -388,6 +437,8 @@ EXPORTED_SYMBOLS = [
     "whamd_pedmec_heuristic_column_count", "whamd_pedmec_heuristic_sample_count", "whamd_pedmec_heuristic_read_count",
     "whamd_pedmec_heuristic_get", "whamd_pedmec_heuristic_get_stats", "whamd_pedmec_heuristic_destroy",
     "whamd_readselection", "whamd_genotype_likelihoods", "whamd_release_caches", "whamd_host_pool_idle_bytes",
+    "whamd_realign_detect", "whamd_realign_result_count", "whamd_realign_get", "whamd_realign_get_stats", "whamd_realign_destroy",
+    "whamd_edit_distance_batch",
 ]
 
 

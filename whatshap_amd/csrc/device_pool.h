@@ -14,5 +14,8 @@ hipError_t devpool_take(int device, size_t bytes, void** out, size_t* got);
 // The caller has made sure nothing on the device still uses the block (stream synchronised).
 void devpool_give(int device, void* ptr, size_t bytes);
 void devpool_release();
+// The pinned host blocks of the same module (the solve's download buffers): kept between calls, at most 1 GiB idle, freed by whamd_release_caches().
+hipError_t pinned_block_take(size_t bytes, void** out, size_t* got);
+void pinned_block_give(void* ptr, size_t bytes);
 
 }  // namespace whamd

@@ -402,6 +402,9 @@ struct StageSession {
 
 }  // namespace
 
+hipError_t pinned_block_take(size_t bytes, void** out, size_t* got) { return pinned_take(bytes, out, got); }
+void pinned_block_give(void* ptr, size_t bytes) { pinned_give(ptr, bytes); }
+
 hipError_t devpool_take(int device, size_t bytes, void** out, size_t* got) {
 	const size_t want = pool_class(bytes);
 	*got = want;

@@ -1,0 +1,555 @@
+// realign_device.hip -- gfx950 kernels of allele detection by re-alignment (realign.h) and of the raw distance batch.
+//
+//   unit costs    edit_distance (whatshap/align.pyx:16-97): global Levenshtein distance, exact.  One lane per job; the lane runs its job's
+//                 alleles one after the other and decides.  Common prefix and suffix are stripped first (they do not change a unit edit
+//                 distance, and an SNV window of 21 bases keeps one or two columns), then bit-parallel Myers / Hyyro with 64-bit words: the
+//                 query in words of 64 rows, one word after the other over the whole target, the horizontal deltas between two words kept
+//                 as bit planes in a per-lane scratch row (queries longer than 64 only).  Match masks for A / C / G / T are built once per
+//                 word; any other target byte (N, lower case, ...) scans the word's query bytes -- every comparison is byte-exact.
+//   affine costs  edit_distance_affine_gap (:103-196): Gotoh restated operation by operation in f32 (no multiply in the recurrence, no
+//                 fast-math: the sums are the reference's).  One wave per job, lane = query row, anti-diagonal sweep: at step s lane i
+//                 computes column s - i from its own previous column, the value lane i-1 handed over (__shfl_up) and the one it handed
+//                 over a step earlier (the diagonal).  Queries longer than 64 rows run in strips; the last row of a strip is kept for the
+//                 first lane of the next one, in LDS when it fits (targets up to 5 460 bytes), else in a global scratch row of the wave.
+//   long jobs     only jobs whose query is longer than 64 need a scratch row (Myers carry, Gotoh strip boundary).  They run in a launch of
+//                 their own, whose rows are sized by their longest allele window and whose grid is capped by the scratch budget; the
+//                 launch over all other jobs needs no scratch at all.
+//   decision      realign (variants.py:866-891): distances of the allowed alleles in index order, stable order by distance, the first
+//                 allele iff it is alone or strictly best; quality 30 (unit) or d0 - d1 / d0 (affine).
+// Only the per-job result (allele or -1, and the quality in affine mode) goes back to the host.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "device_pool.h"
+#include "realign.h"
+
+namespace whamd {
+namespace {
+
+// ---------------------------------------------------------------------------------------------- unit cost: Myers / Hyyro
+constexpr uint64_t WORD_ONES = ~0ull;
+
+template <class Q, class T>
+__device__ __forceinline__ uint64_t match_scan(const Q& q, uint32_t q0, uint32_t rows, uint8_t c) {
+	uint64_t eq = 0;
+	for (uint32_t r = 0; r < rows; ++r) eq |= (uint64_t)(q(q0 + r) == c) << r;
+	return eq;
+}
+
+// Levenshtein distance of q[qb, qb + m) and t[tb, tb + n); carry: 2 * ceil(n / 64) words of this lane (used when m > 64 after stripping)
+template <class Q, class T>
+__device__ int64_t unit_distance(const Q& q, uint32_t qb, uint32_t m, const T& t, uint32_t tb, uint32_t n, uint64_t* carry) {
+	while (m > 0 && n > 0 && q(qb) == t(tb)) { ++qb; ++tb; --m; --n; }
+	while (m > 0 && n > 0 && q(qb + m - 1) == t(tb + n - 1)) { --m; --n; }
+	if (m == 0) return n;
+	if (n == 0) return m;
+	int64_t score = m;
+	const uint32_t words = (m + 63) / 64;
+	for (uint32_t w = 0; w < words; ++w) {
+		const uint32_t q0 = qb + 64 * w, rows = min(64u, m - 64 * w);
+		uint64_t pa = 0, pc = 0, pg = 0, pt = 0;
+		for (uint32_t r = 0; r < rows; ++r) {
+			const uint8_t c = q(q0 + r);
+			const uint64_t bit = 1ull << r;
+			pa |= c == 'A' ? bit : 0;
+			pc |= c == 'C' ? bit : 0;
+			pg |= c == 'G' ? bit : 0;
+			pt |= c == 'T' ? bit : 0;
+		}
+		const uint64_t high = 1ull << (rows - 1);
+		const bool last_word = w + 1 == words;
+		uint64_t pv = WORD_ONES, mv = 0, in_p = 0, in_m = 0, out_p = 0, out_m = 0;
+		for (uint32_t j = 0; j < n; ++j) {
+			const uint32_t bit = j & 63;
+			if (w > 0 && bit == 0) { in_p = carry[2 * (j >> 6)]; in_m = carry[2 * (j >> 6) + 1]; }
+			const int hin = w == 0 ? 1 : ((in_p >> bit) & 1) ? 1 : ((in_m >> bit) & 1) ? -1 : 0;   // row 0 of the matrix: D[0][j] = j
+			const uint8_t c = t(tb + j);
+			uint64_t eq = c == 'A' ? pa : c == 'C' ? pc : c == 'G' ? pg : c == 'T' ? pt : match_scan<Q, T>(q, q0, rows, c);
+			const uint64_t xv = eq | mv;
+			if (hin < 0) eq |= 1;
+			const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
+			uint64_t ph = mv | ~(xh | pv);
+			uint64_t mh = pv & xh;
+			const int hout = (ph & high) ? 1 : (mh & high) ? -1 : 0;
+			ph <<= 1;
+			mh <<= 1;
+			if (hin < 0) mh |= 1;
+			else if (hin > 0) ph |= 1;
+			pv = mh | ~(xv | ph);
+			mv = ph & xv;
+			if (last_word) {
+				score += hout;
+			} else {
+				out_p |= (uint64_t)(hout > 0) << bit;
+				out_m |= (uint64_t)(hout < 0) << bit;
+				if (bit == 63 || j + 1 == n) { carry[2 * (j >> 6)] = out_p; carry[2 * (j >> 6) + 1] = out_m; out_p = out_m = 0; }
+			}
+		}
+	}
+	return score;
+}
+
+// ---------------------------------------------------------------------------------------------- affine cost: Gotoh, one wave
+__device__ __forceinline__ float min2(float x, float y) { return y < x ? y : x; }
+__device__ __forceinline__ float min3(float x, float y, float z) { return min2(min2(x, y), z); }
+
+// edit_distance_affine_gap(q[qb, qb + m), t[tb, tb + n), cost, gap_start, gap_extend); cost(k) = mismatch_cost[k] of the unstripped query.
+// Every lane of the wave calls it with the same arguments; bnd: 3 (n + 1) floats of this wave, in LDS or global memory (strips of more than 64 rows).
+template <class Q, class T, class C>
+__device__ int64_t affine_distance(const Q& q, uint32_t qb, uint32_t m, const T& t, uint32_t tb, uint32_t n, const C& cost, int32_t gs,
+                                   int32_t ge, float* bnd, bool global_row) {
+	const uint32_t lane = threadIdx.x & 63;
+	uint32_t len_p = 0;
+	while (m > 0 && n > 0 && q(qb + len_p) == t(tb + len_p)) { ++len_p; --m; --n; }
+	while (m > 0 && n > 0 && q(qb + len_p + m - 1) == t(tb + len_p + n - 1)) { --m; --n; }
+	if (m == 0 && n == 0) return 0;
+	if (m == 0 || n == 0) return (int64_t)min2(affine_gap_f(m ? m : n, gs, ge), AFFINE_INF);   // min(INT_MAX, f(len), INT_MAX)
+	const float fgs = (float)gs, fge = (float)ge;
+	float result = 0.0f;
+	for (uint32_t s0 = 0; s0 < m; s0 += 64) {
+		const uint32_t rows = min(64u, m - s0);
+		const uint32_t i = s0 + lane + 1;   // this lane's row
+		const bool active = lane < rows;
+		const bool last_strip = s0 + 64 >= m;
+		const uint8_t qc = active ? q(qb + len_p + i - 1) : 0;
+		const float mc = active ? cost(len_p + i - 1) : 0.0f;
+		float ca = AFFINE_INF, cb = affine_gap_f(i, gs, ge), cc = AFFINE_INF;   // row i, column 0
+		float ua = 0.0f, ub = 0.0f, uc = 0.0f;                                  // row i - 1, one column to the left (the diagonal)
+		for (uint32_t step = 0; step < n + rows; ++step) {
+			float na = __shfl_up(ca, 1, 64), nb = __shfl_up(cb, 1, 64), nc = __shfl_up(cc, 1, 64);   // row i - 1, this step's column
+			const int j = (int)step - (int)lane;
+			if (lane == 0 && j >= 0 && j <= (int)n) {
+				if (s0 == 0) {
+					if (j == 0) { na = 0.0f; nb = 0.0f; nc = 0.0f; }
+					else { na = AFFINE_INF; nb = AFFINE_INF; nc = affine_gap_f(j, gs, ge); }
+				} else {
+					na = bnd[3 * j]; nb = bnd[3 * j + 1]; nc = bnd[3 * j + 2];
+				}
+			}
+			if (active && j >= 1 && j <= (int)n) {
+				const float m_c = qc == t(tb + len_p + j - 1) ? 0.0f : mc;
+				const float c_a = min3(ua, ub, uc) + m_c;
+				const float c_b = min3(na + fgs, nb + fge, nc + fgs);
+				const float c_c = min3(ca + fgs, cb + fgs, cc + fge);
+				ca = c_a;
+				cb = c_b;
+				cc = c_c;
+			}
+			ua = na;
+			ub = nb;
+			uc = nc;
+			if (!last_strip && lane == 63 && j >= 0 && j <= (int)n) { bnd[3 * j] = ca; bnd[3 * j + 1] = cb; bnd[3 * j + 2] = cc; }
+		}
+		// the next strip's lane 0 reads what lane 63 wrote: in LDS that is program order, in a global scratch row the stores must be complete and
+		// no earlier load of the row may be served from a cache line read before them (only between strips: one-strip queries pay nothing)
+		if (!last_strip) {
+			if (global_row) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+			else __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+		}
+		__builtin_amdgcn_wave_barrier();
+		if (last_strip) result = __shfl(min3(ca, cb, cc), rows - 1, 64);
+	}
+	return (int64_t)result;   // int(...): toward zero
+}
+
+// ---------------------------------------------------------------------------------------------- realign: distances + decision
+struct RealignArgs {
+	const RealignJob* jobs;
+	const RealignVariant* vars;
+	const uint32_t* allow;
+	const uint64_t* alt_off;
+	const uint8_t* alt_bytes;
+	const uint8_t* ref;
+	const uint8_t* qbuf;
+	const uint32_t* subset;    // the jobs of this launch (NULL: 0 .. n_items - 1)
+	uint32_t n_items;
+	uint32_t skip_long;        // 1: leave jobs with a query longer than 64 to the launch over `subset`
+	uint64_t* carry;           // unit: carry_words per lane
+	float* bnd;                // affine: rows_floats per wave in global memory, or NULL (rows in LDS)
+	uint32_t carry_words, row_floats;
+	int32_t gap_start, gap_extend;
+	float mismatch;
+	int32_t* allele_out;
+	int64_t* quality_out;
+};
+
+struct BytesAt {
+	const uint8_t* p;
+	__device__ uint8_t operator()(uint32_t k) const { return p[k]; }
+};
+struct TargetAt {
+	Target t;
+	__device__ uint8_t operator()(uint32_t k) const { return t.at(k); }
+};
+struct ConstCost {
+	float c;
+	__device__ float operator()(uint32_t) const { return c; }
+};
+struct CostAt {
+	const float* p;
+	__device__ float operator()(uint32_t k) const { return p[k]; }
+};
+
+// the strip boundary row of wave `wave` of this block
+__device__ __forceinline__ float* boundary_row(float* global_rows, uint32_t row_floats, float* lds) {
+	const uint32_t wave = threadIdx.x >> 6;
+	if (global_rows) return global_rows + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * row_floats;
+	return lds + (size_t)wave * row_floats;
+}
+
+__global__ void __launch_bounds__(256) realign_unit_kernel(RealignArgs a) {
+	const uint32_t stride = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x;
+	uint64_t* carry = a.carry ? a.carry + (uint64_t)tid * a.carry_words : nullptr;
+	for (uint32_t k = tid; k < a.n_items; k += stride) {
+		const uint32_t x = a.subset ? a.subset[k] : k;
+		const RealignJob job = a.jobs[x];
+		if (a.skip_long && job.q_len > 64) continue;
+		const RealignVariant v = a.vars[job.variant];
+		const BytesAt q{a.qbuf + job.q_off};
+		int64_t d0 = INT64_MAX, d1 = INT64_MAX;
+		int32_t best = -1;
+		for (uint32_t i = 0; i < v.allow_n; ++i) {
+			const uint32_t allele = a.allow[v.allow_off + i];
+			const TargetAt t{allele_target(job, v, allele, a.ref, a.alt_off, a.alt_bytes)};
+			const int64_t d = unit_distance(q, 0, job.q_len, t, 0, t.t.len(), carry);
+			if (d < d0) { d1 = d0; d0 = d; best = (int32_t)allele; }
+			else if (d < d1) d1 = d;
+		}
+		a.allele_out[x] = (v.allow_n == 1 || d0 < d1) ? best : -1;
+	}
+}
+
+__global__ void __launch_bounds__(256) realign_affine_kernel(RealignArgs a) {
+	extern __shared__ float lds[];
+	const uint32_t waves = blockDim.x >> 6, lane = threadIdx.x & 63;
+	float* bnd = boundary_row(a.bnd, a.row_floats, lds);
+	for (uint32_t k = blockIdx.x * waves + (threadIdx.x >> 6); k < a.n_items; k += gridDim.x * waves) {
+		const uint32_t x = a.subset ? a.subset[k] : k;
+		const RealignJob job = a.jobs[x];
+		if (a.skip_long && job.q_len > 64) continue;
+		const RealignVariant v = a.vars[job.variant];
+		const BytesAt q{a.qbuf + job.q_off};
+		int64_t d0 = INT64_MAX, d1 = INT64_MAX;
+		int32_t best = -1;
+		for (uint32_t i = 0; i < v.allow_n; ++i) {
+			const uint32_t allele = a.allow[v.allow_off + i];
+			const TargetAt t{allele_target(job, v, allele, a.ref, a.alt_off, a.alt_bytes)};
+			const int64_t d = affine_distance(q, 0, job.q_len, t, 0, t.t.len(), ConstCost{a.mismatch}, a.gap_start, a.gap_extend, bnd, a.bnd != nullptr);
+			if (d < d0) { d1 = d0; d0 = d; best = (int32_t)allele; }
+			else if (d < d1) d1 = d;
+		}
+		if (lane == 0) {
+			a.allele_out[x] = (v.allow_n == 1 || d0 < d1) ? best : -1;
+			a.quality_out[x] = v.allow_n > 1 ? d0 - d1 : d0;
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------- raw distance batch
+struct PairArgs {
+	const uint64_t* qptr;
+	const uint8_t* q;
+	const uint64_t* tptr;
+	const uint8_t* t;
+	const float* cost;
+	const uint32_t* subset;
+	uint32_t n_items;
+	uint32_t skip_long;
+	uint64_t* carry;
+	float* bnd;
+	uint32_t carry_words, row_floats;
+	int32_t gap_start, gap_extend;
+	int64_t* out;
+};
+
+__global__ void __launch_bounds__(256) distance_unit_kernel(PairArgs a) {
+	const uint32_t stride = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x;
+	uint64_t* carry = a.carry ? a.carry + (uint64_t)tid * a.carry_words : nullptr;
+	for (uint32_t k = tid; k < a.n_items; k += stride) {
+		const uint32_t x = a.subset ? a.subset[k] : k;
+		const uint64_t q0 = a.qptr[x], t0 = a.tptr[x];
+		const uint32_t m = (uint32_t)(a.qptr[x + 1] - q0);
+		if (a.skip_long && m > 64) continue;
+		a.out[x] = unit_distance(BytesAt{a.q + q0}, 0, m, BytesAt{a.t + t0}, 0, (uint32_t)(a.tptr[x + 1] - t0), carry);
+	}
+}
+
+__global__ void __launch_bounds__(256) distance_affine_kernel(PairArgs a) {
+	extern __shared__ float lds[];
+	const uint32_t waves = blockDim.x >> 6, lane = threadIdx.x & 63;
+	float* bnd = boundary_row(a.bnd, a.row_floats, lds);
+	for (uint32_t k = blockIdx.x * waves + (threadIdx.x >> 6); k < a.n_items; k += gridDim.x * waves) {
+		const uint32_t x = a.subset ? a.subset[k] : k;
+		const uint64_t q0 = a.qptr[x], t0 = a.tptr[x];
+		const uint32_t m = (uint32_t)(a.qptr[x + 1] - q0);
+		if (a.skip_long && m > 64) continue;
+		const int64_t d = affine_distance(BytesAt{a.q + q0}, 0, m, BytesAt{a.t + t0}, 0, (uint32_t)(a.tptr[x + 1] - t0), CostAt{a.cost + q0},
+		                                  a.gap_start, a.gap_extend, bnd, a.bnd != nullptr);
+		if (lane == 0) a.out[x] = d;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------- host driver
+#define RA_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { msg = std::string(#expr) + " failed: " + hipGetErrorString(e_); return WHAMD_ERR_DEVICE; } } while (0)
+
+constexpr uint32_t BLOCK = 256, MAX_BLOCKS = 8192, MAX_LONG_BLOCKS = 1024;
+constexpr size_t LDS_LIMIT = 64 << 10;
+constexpr size_t SCRATCH_BUDGET = (size_t)512 << 20;   // scratch rows of the long-job launch: the grid shrinks to stay within this (at least one block)
+
+// What a call holds on the device and in pinned memory; given back on every way out.
+struct Session {
+	int device = -1;
+	hipStream_t stream = nullptr;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	std::vector<std::pair<void*, size_t>> dev, pinned;
+	~Session() {
+		if (stream) (void)hipStreamSynchronize(stream);
+		for (auto& b : dev) devpool_give(device, b.first, b.second);
+		for (auto& b : pinned) pinned_block_give(b.first, b.second);
+		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+		if (stream) (void)hipStreamDestroy(stream);
+	}
+	whamd_status_t open(int dev_index, std::string& msg) {
+		int ndev = 0;
+		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+			(void)hipGetLastError();
+			msg = "no HIP device visible: the whatshap_amd device path needs an MI355X (gfx950); there is no CPU fallback";
+			return WHAMD_ERR_DEVICE;
+		}
+		if (dev_index < 0 || dev_index >= ndev) { msg = "device index " + std::to_string(dev_index) + " out of range (" + std::to_string(ndev) + " visible)"; return WHAMD_ERR_DEVICE; }
+		device = dev_index;
+		RA_TRY(hipSetDevice(device));
+		RA_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+		for (hipEvent_t& e : ev) RA_TRY(hipEventCreate(&e));
+		return WHAMD_OK;
+	}
+	whamd_status_t device_block(size_t bytes, void** out, std::string& msg) {
+		size_t got = 0;
+		RA_TRY(devpool_take(device, std::max<size_t>(bytes, 256), out, &got));
+		dev.emplace_back(*out, got);
+		return WHAMD_OK;
+	}
+	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg) {
+		size_t got = 0;
+		RA_TRY(pinned_block_take(std::max<size_t>(bytes, 256), out, &got));
+		pinned.emplace_back(*out, got);
+		return WHAMD_OK;
+	}
+	double ms(int a, int b) const {
+		float t = 0.0f;
+		return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
+	}
+};
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Launch shape of the jobs with a query longer than 64 whose longest allele window is `max_target` bytes.
+struct LongShape {
+	uint32_t blocks = 0, block = 64;
+	size_t lds = 0;           // dynamic LDS per block (affine rows in LDS)
+	size_t scratch = 0;       // bytes of global scratch (unit carry rows, or affine rows that do not fit in LDS)
+	uint32_t carry_words = 0, row_floats = 0;
+	bool global_rows = false;
+};
+LongShape long_shape(bool affine, uint64_t n_long, uint32_t max_target) {
+	LongShape s;
+	if (n_long == 0) return s;   // no second launch
+	if (affine) {
+		s.row_floats = 3 * (max_target + 1);
+		const size_t row = (size_t)s.row_floats * 4;
+		s.block = row * 4 <= LDS_LIMIT ? 256 : 64;
+		s.global_rows = row > LDS_LIMIT;
+		const uint64_t waves = s.block / 64;
+		uint64_t blocks = std::min<uint64_t>((n_long + waves - 1) / waves, MAX_LONG_BLOCKS);
+		if (s.global_rows) blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, SCRATCH_BUDGET / row));
+		s.blocks = (uint32_t)blocks;
+		s.lds = s.global_rows ? 0 : row * waves;
+		s.scratch = s.global_rows ? row * blocks : 0;
+	} else {
+		s.carry_words = 2 * ((std::max(max_target, 1u) + 63) / 64);
+		const size_t per_block = (size_t)s.block * s.carry_words * 8;
+		s.blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((n_long + s.block - 1) / s.block, MAX_LONG_BLOCKS),
+		                                                              SCRATCH_BUDGET / per_block));
+		s.scratch = per_block * s.blocks;
+	}
+	return s;
+}
+
+}  // namespace
+
+whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, double* upload_ms, double* kernel_ms,
+                              double* download_ms, std::string& msg) {
+	Session s;
+	whamd_status_t st = s.open(device, msg);
+	if (st != WHAMD_OK) return st;
+	const bool affine = b.params.use_affine != 0;
+	// one staging image, one device block: jobs | query windows | long jobs | variants | allowed alleles | alt offsets | alt bytes | reference slice
+	const size_t o_jobs = 0, o_q = align_up(o_jobs + b.n_jobs * sizeof(RealignJob)), o_long = align_up(o_q + b.n_query_bytes);
+	const size_t o_var = align_up(o_long + b.n_long * 4);
+	const size_t o_allow = align_up(o_var + b.variants.size() * sizeof(RealignVariant)), o_alt = align_up(o_allow + b.allow.size() * 4);
+	const size_t o_altb = align_up(o_alt + b.alt_off.size() * 8), o_ref = align_up(o_altb + b.n_alt_bytes), total = align_up(o_ref + b.ref_len);
+	char* stage = nullptr;
+	char* base = nullptr;
+	if ((st = s.pinned_block(total, (void**)&stage, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(total, (void**)&base, msg)) != WHAMD_OK) return st;
+	const uint32_t n_ranges = (uint32_t)b.range_jobs.size();
+	parallel_ranges(n_ranges + 1, host_threads(n_ranges + 1, 1), [&](uint64_t begin, uint64_t end, uint32_t) {
+		for (uint64_t r = begin; r < end; ++r) {
+			if (r == n_ranges) {   // the small tables and the reference slice
+				if (!b.variants.empty()) std::memcpy(stage + o_var, b.variants.data(), b.variants.size() * sizeof(RealignVariant));
+				if (!b.allow.empty()) std::memcpy(stage + o_allow, b.allow.data(), b.allow.size() * 4);
+				std::memcpy(stage + o_alt, b.alt_off.data(), b.alt_off.size() * 8);
+				if (b.n_alt_bytes) std::memcpy(stage + o_altb, b.alt_bytes, b.n_alt_bytes);
+				if (b.ref_len) std::memcpy(stage + o_ref, b.ref, b.ref_len);
+				continue;
+			}
+			RealignJob* dst = (RealignJob*)(stage + o_jobs) + b.range_job_base[r];
+			const uint64_t qbase = b.range_query_base[r];
+			for (const RealignJob& j : b.range_jobs[r]) {
+				RealignJob k = j;
+				k.q_off += qbase;
+				*dst++ = k;
+			}
+			if (!b.range_query[r].empty()) std::memcpy(stage + o_q + qbase, b.range_query[r].data(), b.range_query[r].size());
+			uint32_t* ldst = (uint32_t*)(stage + o_long) + b.range_long_base[r];
+			for (uint32_t x : b.range_long[r]) *ldst++ = (uint32_t)(b.range_job_base[r] + x);
+		}
+	});
+	// results: alleles | qualities
+	const size_t r_q = align_up(b.n_jobs * 4), r_total = r_q + (affine ? b.n_jobs * 8 : 0);
+	char* res = nullptr;
+	char* hres = nullptr;
+	if ((st = s.device_block(r_total, (void**)&res, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(r_total, (void**)&hres, msg)) != WHAMD_OK) return st;
+	RealignArgs a{};
+	a.jobs = (const RealignJob*)(base + o_jobs);
+	a.qbuf = (const uint8_t*)(base + o_q);
+	a.vars = (const RealignVariant*)(base + o_var);
+	a.allow = (const uint32_t*)(base + o_allow);
+	a.alt_off = (const uint64_t*)(base + o_alt);
+	a.alt_bytes = (const uint8_t*)(base + o_altb);
+	a.ref = (const uint8_t*)(base + o_ref);
+	a.gap_start = b.params.gap_start;
+	a.gap_extend = b.params.gap_extend;
+	a.mismatch = b.params.default_mismatch;
+	a.allele_out = (int32_t*)res;
+	a.quality_out = affine ? (int64_t*)(res + r_q) : nullptr;
+	// the launch over every job with a query of at most 64 (no scratch), then the one over the long jobs
+	RealignArgs shortj = a;
+	shortj.n_items = (uint32_t)b.n_jobs;
+	shortj.skip_long = b.n_long > 0;
+	const uint32_t short_blocks = (uint32_t)std::min<uint64_t>(affine ? (b.n_jobs + BLOCK / 64 - 1) / (BLOCK / 64) : (b.n_jobs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
+	RealignArgs longj = a;
+	const LongShape ls = long_shape(affine, b.n_long, b.max_target_long);
+	if (b.n_long) {
+		longj.subset = (const uint32_t*)(base + o_long);
+		longj.n_items = (uint32_t)b.n_long;
+		longj.carry_words = ls.carry_words;
+		longj.row_floats = ls.row_floats;
+		if (ls.scratch) {
+			void* c = nullptr;
+			if ((st = s.device_block(ls.scratch, &c, msg)) != WHAMD_OK) return st;
+			if (affine) longj.bnd = (float*)c;
+			else longj.carry = (uint64_t*)c;
+		}
+	}
+	RA_TRY(hipEventRecord(s.ev[0], s.stream));
+	RA_TRY(hipMemcpyAsync(base, stage, total, hipMemcpyHostToDevice, s.stream));
+	RA_TRY(hipEventRecord(s.ev[1], s.stream));
+	if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
+	else hipLaunchKernelGGL(realign_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
+	RA_TRY(hipGetLastError());
+	if (b.n_long) {
+		if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longj);
+		else hipLaunchKernelGGL(realign_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longj);
+		RA_TRY(hipGetLastError());
+	}
+	RA_TRY(hipEventRecord(s.ev[2], s.stream));
+	RA_TRY(hipMemcpyAsync(hres, res, r_total, hipMemcpyDeviceToHost, s.stream));
+	RA_TRY(hipEventRecord(s.ev[3], s.stream));
+	RA_TRY(hipStreamSynchronize(s.stream));
+	*upload_ms = s.ms(0, 1);
+	*kernel_ms = s.ms(1, 2);
+	*download_ms = s.ms(2, 3);
+	std::memcpy(allele_out, hres, b.n_jobs * 4);
+	if (affine) std::memcpy(quality_out, hres + r_q, b.n_jobs * 8);
+	return WHAMD_OK;
+}
+
+whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr, const uint8_t* query, const uint64_t* target_ptr,
+                                    const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start, int32_t gap_extend,
+                                    int device, int64_t* distance_out, std::string& msg) {
+	if (n_pairs >= UINT32_MAX) { msg = "too many pairs for one call"; return WHAMD_ERR_INVALID; }
+	uint32_t max_t_long = 0;
+	std::vector<uint32_t> long_pairs;
+	for (uint64_t p = 0; p < n_pairs; ++p) {
+		if (query_ptr[p + 1] < query_ptr[p] || target_ptr[p + 1] < target_ptr[p]) { msg = "query_ptr / target_ptr must not decrease"; return WHAMD_ERR_INVALID; }
+		if (target_ptr[p + 1] - target_ptr[p] >= UINT32_MAX || query_ptr[p + 1] - query_ptr[p] >= UINT32_MAX) { msg = "sequence too long"; return WHAMD_ERR_INVALID; }
+		if (query_ptr[p + 1] - query_ptr[p] > 64) {
+			long_pairs.push_back((uint32_t)p);
+			max_t_long = (uint32_t)std::max<uint64_t>(max_t_long, target_ptr[p + 1] - target_ptr[p]);
+		}
+	}
+	Session s;
+	whamd_status_t st = s.open(device, msg);
+	if (st != WHAMD_OK) return st;
+	const uint64_t nq = query_ptr[n_pairs], nt = target_ptr[n_pairs], n_long = long_pairs.size();
+	const size_t o_qp = 0, o_tp = align_up((n_pairs + 1) * 8), o_q = align_up(o_tp + (n_pairs + 1) * 8), o_t = align_up(o_q + nq);
+	const size_t o_c = align_up(o_t + nt), o_long = align_up(o_c + (use_affine ? nq * 4 : 0)), o_out = align_up(o_long + n_long * 4);
+	const size_t total = align_up(o_out + n_pairs * 8);
+	char* stage = nullptr;
+	char* base = nullptr;
+	if ((st = s.pinned_block(total, (void**)&stage, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(total, (void**)&base, msg)) != WHAMD_OK) return st;
+	std::memcpy(stage + o_qp, query_ptr, (n_pairs + 1) * 8);
+	std::memcpy(stage + o_tp, target_ptr, (n_pairs + 1) * 8);
+	if (nq) std::memcpy(stage + o_q, query, nq);
+	if (nt) std::memcpy(stage + o_t, target, nt);
+	if (use_affine && nq) std::memcpy(stage + o_c, mismatch_cost, nq * 4);
+	if (n_long) std::memcpy(stage + o_long, long_pairs.data(), n_long * 4);
+	PairArgs a{};
+	a.qptr = (const uint64_t*)(base + o_qp);
+	a.tptr = (const uint64_t*)(base + o_tp);
+	a.q = (const uint8_t*)(base + o_q);
+	a.t = (const uint8_t*)(base + o_t);
+	a.cost = (const float*)(base + o_c);
+	a.gap_start = gap_start;
+	a.gap_extend = gap_extend;
+	a.out = (int64_t*)(base + o_out);
+	PairArgs shortp = a;
+	shortp.n_items = (uint32_t)n_pairs;
+	shortp.skip_long = n_long > 0;
+	const uint32_t short_blocks = (uint32_t)std::min<uint64_t>(use_affine ? (n_pairs + BLOCK / 64 - 1) / (BLOCK / 64) : (n_pairs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
+	PairArgs longp = a;
+	const LongShape ls = long_shape(use_affine != 0, n_long, max_t_long);
+	if (n_long) {
+		longp.subset = (const uint32_t*)(base + o_long);
+		longp.n_items = (uint32_t)n_long;
+		longp.carry_words = ls.carry_words;
+		longp.row_floats = ls.row_floats;
+		if (ls.scratch) {
+			void* c = nullptr;
+			if ((st = s.device_block(ls.scratch, &c, msg)) != WHAMD_OK) return st;
+			if (use_affine) longp.bnd = (float*)c;
+			else longp.carry = (uint64_t*)c;
+		}
+	}
+	RA_TRY(hipMemcpyAsync(base, stage, o_out, hipMemcpyHostToDevice, s.stream));
+	if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
+	else hipLaunchKernelGGL(distance_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
+	RA_TRY(hipGetLastError());
+	if (n_long) {
+		if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longp);
+		else hipLaunchKernelGGL(distance_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longp);
+		RA_TRY(hipGetLastError());
+	}
+	RA_TRY(hipMemcpyAsync(stage + o_out, base + o_out, n_pairs * 8, hipMemcpyDeviceToHost, s.stream));
+	RA_TRY(hipStreamSynchronize(s.stream));
+	std::memcpy(distance_out, stage + o_out, n_pairs * 8);
+	return WHAMD_OK;
+}
+
+}  // namespace whamd

@@ -270,3 +270,75 @@ def random_small_instance(rng: random.Random, mode: Optional[str] = None, max_va
     return ProblemArrays(read_ptr, pos, alle, qual, samples, np.arange(n_ind, dtype=np.uint32),
                          np.asarray(triples, dtype=np.uint32), genotype, gl, recomb,
                          np.asarray(positions, dtype=np.uint32), distrust, n_variants=n_cols)
+
+
+class _RealignVariant:
+    __slots__ = ("position", "reference_allele", "_alts")
+
+    def __init__(self, position, ref, alts):
+        self.position, self.reference_allele, self._alts = position, ref, alts
+
+    def get_alt_allele_list(self):
+        return self._alts
+
+
+class _RealignRead:
+    __slots__ = ("reference_start", "cigartuples", "query_sequence")
+
+    def __init__(self, start, cigar, seq):
+        self.reference_start, self.cigartuples, self.query_sequence = start, cigar, seq
+
+
+def realign_workload(n_variants=200_000, genome=20_000_000, coverage=20, read_len=(10_000, 20_000), error=0.01, seed=1):
+    """A seeded input of allele detection by re-alignment (scripts/gpu_realign_bench.py, tests/test_gpu_realign.py): a random reference,
+    variants (90 % SNV, 8 % indels of 1 - 20 bp, 2 % multi-allelic), reads drawn from the reference with `error` substitutions and small
+    indels (as CIGAR I / D).  Returns (reference bytes, variants, reads) -- duck-typed like VcfVariant / AlignedSegment."""
+    rng = np.random.default_rng(seed)
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)
+    ref = bases[rng.integers(0, 4, genome)]
+    pos = np.sort(rng.choice(np.arange(100, genome - 100), n_variants, replace=False))
+    kind = rng.random(n_variants)
+    variants = []
+    refb = ref.tobytes()
+    for p, k in zip(pos.tolist(), kind.tolist()):
+        r = refb[p:p + 1].decode()
+        alt = "ACGT"[("ACGT".index(r) + 1 + int(k * 1000) % 3) % 4]
+        if k < 0.9:
+            variants.append(_RealignVariant(p, r, [alt]))
+        elif k < 0.98:
+            n = 1 + int(k * 10000) % 20
+            if int(k * 100000) % 2:
+                variants.append(_RealignVariant(p, refb[p:p + n + 1].decode(), [r]))
+            else:
+                variants.append(_RealignVariant(p, r, [r + bases[rng.integers(0, 4, n)].tobytes().decode()]))
+        else:
+            variants.append(_RealignVariant(p, r, [alt, "ACGT"[("ACGT".index(alt) + 1) % 4] if "ACGT"[("ACGT".index(alt) + 1) % 4] != r else "N"]))
+    reads = []
+    total = 0
+    while total < coverage * genome:
+        n = int(rng.integers(read_len[0], read_len[1] + 1))
+        start = int(rng.integers(0, genome - n - 100))
+        seg = ref[start:start + n].copy()
+        sub = rng.random(n) < error * 0.6
+        seg[sub] = bases[rng.integers(0, 4, int(sub.sum()))]
+        events = np.sort(rng.choice(np.arange(20, n - 20), max(1, int(n * error * 0.4)), replace=False))
+        cigar, pieces, last = [], [], 0
+        for e in events.tolist():
+            if e <= last:
+                continue
+            cigar.append((0, e - last))
+            pieces.append(seg[last:e])
+            ln = 1 + int(rng.integers(0, 3))
+            if rng.random() < 0.5:
+                cigar.append((1, ln))
+                pieces.append(bases[rng.integers(0, 4, ln)])
+                last = e
+            else:
+                cigar.append((2, ln))
+                last = e + ln
+        cigar.append((0, n - last))
+        pieces.append(seg[last:])
+        reads.append(_RealignRead(start, cigar, np.concatenate(pieces).tobytes().decode()))
+        total += n
+    reads.sort(key=lambda r: r.reference_start)
+    return refb, variants, reads
