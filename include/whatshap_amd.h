@@ -468,6 +468,62 @@ whamd_status_t whamd_edit_distance_batch(uint64_t n_pairs, const uint64_t* query
                                          const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start,
                                          int32_t gap_extend, int device, int64_t* distance_out);
 
+/* ---- Polyphase read scoring (ReadScoring::scoreReadset, src/polyphase/readscoring.cpp:17-84) ----------------------------------------
+ * For every pair of reads of an AlleleMatrix (src/polyphase/allelematrix.cpp:59-91) that share at least min_overlap positions, the sum
+ * over the shared positions of log(P(same haplotype) / P(different haplotypes)), from genotype likelihoods of the allele depths.  Here
+ * the matrix, the likelihoods (readscoring.cpp:123-191), the allele-pair tables (:193-225) and one float term per (position, allele,
+ * allele) are computed on the host (csrc/polyscore.cpp); the pair loop runs on the device (csrc/polyscore_device.hip) and its results
+ * are bit-identical to the host restatement of the debug library.  The reference sums the genotypes of a position in the iteration order
+ * of an unordered_map; this library sums them in increasing genotype index, which can move a term by one float ulp.
+ * A matrix is a CSR list of reads: read r lists (position, allele) entries read_ptr[r] .. read_ptr[r+1]-1, positions in genome
+ * coordinates as Read::getPosition gives them, as AlleleMatrix(ReadSet*) takes them (:59-91): the first and last LISTED entry are the
+ * read's first / last position, a position listed twice keeps the allele listed last and counts twice in the depths.  An empty read
+ * has first position UINT32_MAX and last 0 (the readList constructor's convention, :45-47).
+ * Errors (WHAMD_ERR_INVALID, nothing launched): a negative allele (undefined in the reference), an allele above 15 or a ploidy above 15
+ * (Genotype's limits, src/genotype.h), a position outside [0, 2^32).  ploidy < 2 gives an empty result, as in the reference.
+ * Results: per matrix, (i, j, score) with i > j in original read ids, sorted by the triangular index i*(i-1)/2 + j
+ * (TriangleSparseMatrix::getIndices, trianglesparsematrix.cpp:66-73); scores that are exactly 0 are not stored, NaN scores are counted. */
+typedef struct whamd_poly_matrix_view {
+	uint64_t n_reads;
+	const uint64_t* read_ptr;        /* [n_reads + 1] */
+	const int64_t* position;         /* [read_ptr[n_reads]] */
+	const int8_t* allele;            /* [read_ptr[n_reads]] */
+} whamd_poly_matrix_view;
+
+typedef struct whamd_poly_score_stats {
+	double err;                      /* the allele error rate used: the caller's, or estimateAlleleErrorRate's when the caller passed 0 */
+	uint64_t n_reads;
+	uint64_t n_positions;
+	uint64_t n_candidates;           /* pairs the reference's loop visits (readscoring.cpp:67-78; ties in first position by read id) */
+	uint64_t n_overlapping;          /* candidate pairs that share at least min_overlap positions */
+	uint64_t n_entries;              /* stored scores */
+	uint64_t n_nan;                  /* NaN scores (counted, not stored: the reference's warning) */
+	uint64_t n_pair_positions;       /* shared positions summed over the candidate pairs (the pair loop's table lookups) */
+	uint32_t launches;               /* device steps of the whole call: pair loop, scan, compaction, sort (0: nothing touched the device) */
+	double host_ms;                  /* wall, whole call: matrices, likelihoods, term tables, windows */
+	double upload_ms;                /* HIP events, whole call */
+	double kernel_ms;                /* HIP events, whole call: pair loop, compaction, sort */
+	double download_ms;              /* HIP events, whole call */
+	double total_ms;                 /* wall, whole call */
+} whamd_poly_score_stats;
+
+typedef struct whamd_poly_scores whamd_poly_scores; /* opaque: the result of one whamd_poly_score call */
+
+/* One call for a batch of n_matrices matrices (polyphase scores one block at a time: small blocks share one launch sequence).  err == 0
+ * estimates the error rate per matrix (readscoring.cpp:33-34). */
+whamd_status_t whamd_poly_score(const whamd_poly_matrix_view* matrices, uint64_t n_matrices, uint32_t min_overlap, uint32_t ploidy, double err,
+                                int device, whamd_poly_scores** out);
+uint64_t whamd_poly_score_matrix_count(const whamd_poly_scores* s);
+/* Entries of matrix m; i_out / j_out / score_out: [whamd_poly_score_count(s, m)], NULL skips. */
+uint64_t whamd_poly_score_count(const whamd_poly_scores* s, uint64_t m);
+whamd_status_t whamd_poly_score_get(const whamd_poly_scores* s, uint64_t m, uint32_t* i_out, uint32_t* j_out, float* score_out);
+/* Counts and err of matrix m; the times are those of the whole call. */
+whamd_status_t whamd_poly_score_get_stats(const whamd_poly_scores* s, uint64_t m, whamd_poly_score_stats* stats_out);
+void whamd_poly_score_destroy(whamd_poly_scores* s);
+/* ReadScoring::estimateAlleleErrorRate (readscoring.cpp:86-107): the err in 0.01, 0.02, ... (the reference's accumulating loop) whose
+ * genotype likelihoods explain the depths best; host only, nothing printed. */
+whamd_status_t whamd_poly_estimate_error_rate(const whamd_poly_matrix_view* matrix, uint32_t ploidy, double* err_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,12 @@ whamd_status_t whamd_debug_edit_distance_host(uint64_t n_pairs, const uint64_t* 
                                               const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start,
                                               int32_t gap_extend, int64_t* distance_out);
 
+/* HOST-ONLY DIAGNOSTIC of polyphase read scoring (csrc/polyscore.cpp): the same matrices, term tables and windows as whamd_poly_score,
+ * then the pair loop on one CPU thread with the device's arithmetic -- the device's bit-exact reference and what the CPU test-suite
+ * compares with the recorded reference; never what the product calls.  Read with the whamd_poly_score_* getters of the debug library. */
+whamd_status_t whamd_debug_poly_score_host(const whamd_poly_matrix_view* matrices, uint64_t n_matrices, uint32_t min_overlap, uint32_t ploidy,
+                                           double err, whamd_poly_scores** out);
+
 #ifdef __cplusplus
 }
 #endif

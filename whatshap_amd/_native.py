@@ -161,6 +161,18 @@ class RealignStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PolyMatrixView(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("position", C.POINTER(C.c_int64)), ("allele", C.POINTER(C.c_int8))]
+
+
+class PolyScoreStats(C.Structure):
+    _fields_ = [("err", C.c_double)] + [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_candidates", "n_overlapping", "n_entries", "n_nan", "n_pair_positions")] + [
+        ("launches", C.c_uint32)] + [(name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -306,6 +318,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_edit_distance_host.restype = C.c_int
     L.whamd_debug_edit_distance_host.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
                                                  C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    L.whamd_debug_poly_score_host.restype = C.c_int
+    L.whamd_debug_poly_score_host.argtypes = [C.POINTER(PolyMatrixView), C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]
     _debug_lib = L
     return L
 
@@ -419,6 +433,20 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_edit_distance_batch.restype = C.c_int
     L.whamd_edit_distance_batch.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
                                             C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int, C.POINTER(C.c_int64)]
+    L.whamd_poly_score.restype = C.c_int
+    L.whamd_poly_score.argtypes = [C.POINTER(PolyMatrixView), C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_poly_score_matrix_count.restype = C.c_uint64
+    L.whamd_poly_score_matrix_count.argtypes = [C.c_void_p]
+    L.whamd_poly_score_count.restype = C.c_uint64
+    L.whamd_poly_score_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_poly_score_get.restype = C.c_int
+    L.whamd_poly_score_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.whamd_poly_score_get_stats.restype = C.c_int
+    L.whamd_poly_score_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PolyScoreStats)]
+    L.whamd_poly_score_destroy.restype = None
+    L.whamd_poly_score_destroy.argtypes = [C.c_void_p]
+    L.whamd_poly_estimate_error_rate.restype = C.c_int
+    L.whamd_poly_estimate_error_rate.argtypes = [C.POINTER(PolyMatrixView), C.c_uint32, C.POINTER(C.c_double)]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -439,6 +467,8 @@ EXPORTED_SYMBOLS = [
     "whamd_readselection", "whamd_genotype_likelihoods", "whamd_release_caches", "whamd_host_pool_idle_bytes",
     "whamd_realign_detect", "whamd_realign_result_count", "whamd_realign_get", "whamd_realign_get_stats", "whamd_realign_destroy",
     "whamd_edit_distance_batch",
+    "whamd_poly_score", "whamd_poly_score_matrix_count", "whamd_poly_score_count", "whamd_poly_score_get", "whamd_poly_score_get_stats",
+    "whamd_poly_score_destroy", "whamd_poly_estimate_error_rate",
 ]
 
 
