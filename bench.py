@@ -15,13 +15,18 @@ Workloads (BASELINE.json `configs`):
 `python bench.py --gpus N` starts its N ranks itself (one process per GPU through torch.distributed.run on
 127.0.0.1) when it was not already launched by torchrun, and fails loudly when fewer than N devices are visible.
 
-At N = 1 with no workload flags the line also carries `configs`: the other single-GPU workloads of BASELINE.json
+A plain run does what the headline needs and nothing else: it builds the inputs, creates and solves the tables once (their
+columns and cost checksum are the reference of every fresh step), warms up, times the --steps steps, writes --dump-outputs
+and prints the line.  Everything else below -- value_resident, roofline and counters, cpu_baseline, end_to_end,
+value_8d_strict, create_rate, `configs` -- is measured by `bench.py --full` only.
+
+With --full at N = 1 and no workload flags the line also carries `configs`: the other single-GPU workloads of BASELINE.json
 (configs[1] 50 000 x coverage 15, configs[3] trio, three configs[4] blocks in flight) plus an irregular read layout
 (Poisson starts, geometric lengths: the planner's typical case rather than its best) and a quartet, each measured by a child
 `bench.py --workload NAME --sub` with its own value / ms_per_step / steps / roofline.frac / cpu_baseline sample.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline      counter-based: the fraction of the chip's VALU issue slots the dominant kernel uses (the binding roof of
+Prints ONE JSON line (rank 0) with the driver's contract fields plus, with --full,
+  roofline     counter-based: the fraction of the chip's VALU issue slots the dominant kernel uses (the binding roof of
                 this integer min-plus path; no MFMA), next to the LDS-pipe and MEASURED HBM fractions.  The counters
                 come from rocprofv3 --pmc passes that bench.py itself runs after the timed region (separate passes,
                 only with --kernel-trace) on a short slice of the same workload; `hbm_model_ratio` keeps SURVEY.md
@@ -95,18 +100,20 @@ def parse_args():
     ap.add_argument("--heuristic", action="store_true", help="the PedMecHeuristic row: beam search at a coverage the exact DP cannot afford (row limit 256)")
     ap.add_argument("--shim", action="store_true", help="enter through whatshap_amd.shim with the reference's own ReadSet / Pedigree objects (the compiled whatshap.core of oracle/_ref/cy as the container types)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="a named workload (sets the flags above)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: resident tables, counters and roofline, CPU baselines, end to end, create rate, `configs`")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="append the other single-GPU workloads as `configs` (auto: N=1 and no workload flags)")
+                    help="with --full: append the other single-GPU workloads as `configs` (auto: N=1 and no workload flags)")
     ap.add_argument("--sub", action="store_true", help=argparse.SUPPRESS)   # child of the `configs` array: short counters, short CPU sample, no torch
     ap.add_argument("--oversubscribe", action="store_true", help="allow more ranks than devices (rank r uses device r %% visible; tests)")
     ap.add_argument("--path", default="auto")
     ap.add_argument("--option", action="append", default=[], help="key=value passed to whamd_dptable_set_option")
     ap.add_argument("--cpu-baseline-columns", type=int, default=-1,
-                    help="steady-state columns of the same ReadSet timed on the compiled reference (default: ~15 s worth; 0 = skip)")
+                    help="with --full: steady-state columns of the same ReadSet timed on the compiled reference (default: ~15 s worth; 0 = skip)")
     ap.add_argument("--cpu-baseline-procs", type=int, default=0,
-                    help="also time P concurrent single-thread reference processes on independent blocks (BASELINE.md 3.5; -1 = nproc)")
+                    help="with --full: also time P concurrent single-thread reference processes on independent blocks (BASELINE.md 3.5; -1 = nproc)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "on", "off"],
-                    help="run the rocprofv3 counter passes after the timed region (auto: N=1 and rocprofv3 present)")
+                    help="with --full: run the rocprofv3 counter passes after the timed region (auto: N=1 and rocprofv3 present)")
     ap.add_argument("--pmc-variants", type=int, default=8000)
     ap.add_argument("--pmc-keep", default=os.path.join(ROOT, "gpurun_out", "pmc_live"), help="where the filtered counter CSVs are kept")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"), help="where the full record (every entry, every counter) is written")
@@ -539,7 +546,7 @@ def genotype_main(args):
     kernel = "geno_slot_run" if stats["slot_runs"] else "geno_forward"
     avg_launch_us = stats["backward_ms"] * 1e3 / max(stats["slot_runs"], 1) if stats["slot_runs"] else stats["total_ms"] * 1e3 / max(stats["launches"], 1)
     pmc, pmc_note = None, "skipped"
-    if args.pmc in ("on", "auto"):
+    if args.full and args.pmc in ("on", "auto"):
         _native.release_caches()
         try:
             pmc, pmc_note = run_pmc_passes(args, kernel, args.pmc_keep)
@@ -551,7 +558,7 @@ def genotype_main(args):
     roof["pmc_note"] = pmc_note
     roof["launch_time_note"] = "chain time / runs per chain (the two chains run side by side on two streams: a launch's own duration is at most this)"
     out["roofline"] = roof
-    if args.cpu_baseline_columns != 0:
+    if args.full and args.cpu_baseline_columns != 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from genotype_cases import reference_likelihoods
         from oracle import build_cython_ref
@@ -633,7 +640,7 @@ def heuristic_main(args):
         "end_to_end": {"value": cols / wall_s, "unit": "variant-columns/s", "what": "plans + upload + kernel + phasing of every table from host arrays, wall"},
     }
     pmc, pmc_note = None, "skipped"
-    if args.pmc in ("on", "auto"):
+    if args.full and args.pmc in ("on", "auto"):
         try:
             pmc, pmc_note = run_pmc_passes(args, "heuristic_kernel", args.pmc_keep)
         except Exception as exc:  # noqa: BLE001
@@ -645,7 +652,7 @@ def heuristic_main(args):
     roof["shape_note"] = (f"{n_tables} persistent workgroup(s), one per table (a chain over columns and reads; the beam is the only parallelism inside a table): "
                           f"the chip-wide fraction is bounded by {n_tables} / 256 CUs")
     out["roofline"] = roof
-    if args.cpu_baseline_columns != 0:
+    if args.full and args.cpu_baseline_columns != 0:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle
         from heuristic_cases import result_tuple
@@ -770,7 +777,7 @@ def shim_main(args):
     roof.pop("hbm_model_ratio", None)
     roof["pmc_note"] = "the device work is the headline's (config2) / config3's: counters there"
     out["roofline"] = roof
-    if args.cpu_baseline_columns != 0:
+    if args.full and args.cpu_baseline_columns != 0:
         # the reference CLASS on a prefix of the same objects' data: the CPU rate of the step, and the parity bit -- objects compared with objects
         ramp = 2 * args.coverage
         times = {}
@@ -972,7 +979,7 @@ def run_extra_configs(args):
     """The other single-GPU workloads, one child process each (own tables, own counters, own CPU sample)."""
     out = []
     for name in EXTRA_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--sub", "--steps", "6", "--warmup", "2",
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--sub", "--full", "--steps", "6", "--warmup", "2",
                "--configs", "off", "--pmc", args.pmc, "--pmc-keep", os.path.join(args.pmc_keep, name)]
         if args.cpu_baseline_columns == 0:
             cmd += ["--cpu-baseline-columns", "0"]
@@ -1038,6 +1045,8 @@ def main():
             setattr(args, key, value)
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full and (args.configs == "on" or args.pmc == "on" or args.cpu_baseline_columns > 0 or args.cpu_baseline_procs != 0):
+        raise SystemExit("--configs on / --pmc on / --cpu-baseline-columns N / --cpu-baseline-procs P are measured by a --full run only")
     if args.dump_outputs and (args.genotype or args.heuristic or args.shim):
         raise SystemExit("--dump-outputs writes the phasing tables' outputs: not available with --genotype / --heuristic / --shim")
     import __graft_entry__ as entry
@@ -1129,8 +1138,11 @@ def main():
         if torch is not None:
             torch.cuda.synchronize()
 
-    # ---------------------------------------------------------------- region 1: tables RESIDENT (created before the clock) -> value_resident, roofline
-    for _ in range(args.warmup):
+    # ---------------------------------------------------------------- region 1: tables RESIDENT (created before the clock).  A plain run solves them once: their
+    # columns and costs are the headline's, their cost checksum the one every fresh step must reproduce.  --full: --warmup steps, then --steps timed ones
+    # -> value_resident, roofline
+    resident = args.full or args.pmc_inner
+    for _ in range(args.warmup if resident else 0):
         step()
     if args.pmc_inner:
         step()
@@ -1141,7 +1153,7 @@ def main():
     launches = 0
     step_s = []
     grouped = False
-    for _ in range(args.steps):
+    for _ in range(args.steps if resident else 1):
         ts = time.perf_counter()
         step()
         step_s.append(time.perf_counter() - ts)
@@ -1282,14 +1294,16 @@ def main():
         return vals[len(vals) // 2] if vals else None
 
     per_rank = {"rank": rank, "device": device, "tables": len(problems), "create_ms": med("create_ms"), "solve_ms": med("solve_ms"), "close_ms": med("close_ms"), "other_ms": med("other_ms"),
-                "step_ms": med("wall_ms"), "resident_step_ms": sorted(resident_step_s)[len(resident_step_s) // 2] * 1e3,
+                "step_ms": med("wall_ms"),
                 "cpus": (cpu_binding or {}).get("n_cpus", n_cpus), "cpu_quota": quota, "cpu_budget": budget, "numa_node": (cpu_binding or {}).get("node"), "cpu_source": (cpu_binding or {}).get("source", "unbound"),
                 "create_threads": shape[0], "host_threads_per_create": shape[1], "tables_per_window": shape[2], "windows_on_device": shape[3]}
+    if args.full:
+        per_rank["resident_step_ms"] = sorted(resident_step_s)[len(resident_step_s) // 2] * 1e3
     per_rank_checksums = [int(totals[2])]
     # what a SCALE record can be audited with: which rank ran which blocks on which device, and for how long
     print(f"[bench rank {rank}/{world}] device {device}, blocks {[blocks[b][0] for b in mine]} (seeds), {len(mine)} table(s), fresh: {elapsed:.3f} s for {args.steps} step(s) "
-          f"(create {per_rank['create_ms']:.1f} ms + solve {per_rank['solve_ms']:.1f} ms + close {per_rank['close_ms']:.1f} ms per step), resident: {elapsed_resident:.3f} s, "
-          f"cpus {per_rank['cpus']} ({per_rank['cpu_source']}, node {per_rank['numa_node']}), cost checksum {int(totals[2])}", file=sys.stderr, flush=True)
+          f"(create {per_rank['create_ms']:.1f} ms + solve {per_rank['solve_ms']:.1f} ms + close {per_rank['close_ms']:.1f} ms per step), "
+          + (f"resident: {elapsed_resident:.3f} s, " if args.full else "") + f"cpus {per_rank['cpus']} ({per_rank['cpu_source']}, node {per_rank['numa_node']}), cost checksum {int(totals[2])}", file=sys.stderr, flush=True)
     per_rank_all = [per_rank]
     if dist is not None:
         import torch as _torch
@@ -1349,148 +1363,150 @@ def main():
                 "optimal_cost_checksum_per_rank": per_rank_checksums,
                 "rendezvous": "gloo (barrier, max-over-ranks time, checksums; no collective on the data path)" if dist is not None else "none",
             },
-            "rank0": {"forward_ms_per_step": fwd_ms / args.steps, "backtrace_ms_per_step": bt_ms / args.steps,
-                      "forward_launches_per_step": launches / args.steps},
             "value_is": "FRESH tables: every timed step runs whamd_dptable_create (columns, indexing schemes, cost terms, plan, upload) from the flattened host arrays, the "
                         "solve (forward, backtrace, path download, superread assembly) and the destroy of every table of the rank -- SURVEY.md 8(d)'s clock starts at the "
                         "constructor; several tables go through the host-side work queue (next window created under the current solve)",
-            "value_resident": {"value": cols_job * args.steps / elapsed_resident, "ms_per_step": elapsed_resident / args.steps * 1e3,
-                               "ms_per_step_min": min(resident_step_s) * 1e3, "ms_per_step_median": sorted(resident_step_s)[len(resident_step_s) // 2] * 1e3,
-                               "bipartition_costs_per_s": costs_job * args.steps / elapsed_resident,
-                               "what": "the same steps on tables created BEFORE the clock (plan and operand tables resident in HBM): forward + backtrace + result extraction only -- what "
-                                       "rounds 1-5 reported as `value`; the roofline's launch time is measured here"},
             "per_rank": per_rank_all,
             "host_shapes_tried": tried,
         }
+        if args.full:
+            out["rank0"] = {"forward_ms_per_step": fwd_ms / args.steps, "backtrace_ms_per_step": bt_ms / args.steps,
+                            "forward_launches_per_step": launches / args.steps}
+            out["value_resident"] = {"value": cols_job * args.steps / elapsed_resident, "ms_per_step": elapsed_resident / args.steps * 1e3,
+                                     "ms_per_step_min": min(resident_step_s) * 1e3, "ms_per_step_median": sorted(resident_step_s)[len(resident_step_s) // 2] * 1e3,
+                                     "bipartition_costs_per_s": costs_job * args.steps / elapsed_resident,
+                                     "what": "the same steps on tables created BEFORE the clock (plan and operand tables resident in HBM): forward + backtrace + result extraction only -- what "
+                                             "rounds 1-5 reported as `value`; the roofline's launch time is measured here"}
         out["config"]["cpu_binding"] = (f"rank r bound to the CPUs of its GPU's NUMA node, shared evenly between the ranks of that node (whatshap_amd.blocks.bind_rank_to_device_cpus): "
                                         f"{(cpu_binding or {}).get('n_cpus')} CPUs, {(cpu_binding or {}).get('source')}") if cpu_binding is not None else "none (--no-affinity)"
-        # ---- fresh tables end to end (host-inclusive): create + solve + getters
-        if world == 1 and len(blocks) == 1:
-            seed, v = blocks[mine[0]]
-            problem = build_block(args, seed, v)
+        if args.full:   # what the headline does not need: each of these is a run of its own
+            # ---- fresh tables end to end (host-inclusive): create + solve + getters
+            if world == 1 and len(blocks) == 1:
+                seed, v = blocks[mine[0]]
+                problem = build_block(args, seed, v)
 
-            def fresh_table():
+                def fresh_table():
+                    te0 = time.perf_counter()
+                    fresh = _native.NativeTable(problem, device=device, path=None if args.path == "auto" else args.path, solve=False)
+                    apply_options(fresh, args)
+                    te1 = time.perf_counter()
+                    fresh.solve()
+                    fresh.optimal_score(), fresh.super_reads(), fresh.partitioning()
+                    te2 = time.perf_counter()
+                    fresh_stats.update(fresh.stats())
+                    fresh.close()
+                    return (te1 - te0) * 1e3, (te2 - te1) * 1e3
+
+                fresh_stats = {}
+                fresh_table()   # (the first create of a process also sizes the pinned staging area)
+                create_ms, rest_ms = fresh_table()
+                # "from entering the constructor to index_path complete, excluding ReadSet flattening and superread assembly".  The
+                # constructor of the reference (src/pedigreedptable.cpp:15-37) walks the columns, builds the indexing schemes and runs compute_table;
+                # here that is ALL of whamd_dptable_create (columns + indexing scheme + cost terms, plan, upload: its input is the flattened CSR view)
+                # plus the device's forward pass, backtrace and path download; whamd_dptable_wait's superread assembly (host_finish_ms) stays outside.
+                strict_ms = create_ms + fresh_stats["total_ms"]
+                out["value_8d_strict"] = {"value": v / (strict_ms * 1e-3), "unit": "variant-columns/s", "ms": strict_ms, "create_ms": create_ms,
+                                          "flatten_ms": fresh_stats.get("host_flatten_ms"),
+                                          "terms_plan_upload_ms": (create_ms - fresh_stats["host_flatten_ms"]) if fresh_stats.get("host_flatten_ms") is not None else None,
+                                          "device_ms": fresh_stats["total_ms"], "superreads_ms_excluded": fresh_stats["host_finish_ms"],
+                                          "what": "SURVEY 8(d) to the letter for ONE fresh table: whamd_dptable_create (flatten_ms = ColumnIterator's columns; the rest = indexing scheme, cost terms, plan, upload) + forward + backtrace + path download; superread assembly and destroy excluded (`value` includes both)"}
+                out["end_to_end"] = {"value": v / ((create_ms + rest_ms) * 1e-3), "unit": "variant-columns/s", "create_ms": create_ms,
+                                     "solve_and_getters_ms": rest_ms, "host_threads": min(os.cpu_count() or 1, 32),
+                                     "fraction_of_device_only": (v / ((create_ms + rest_ms) * 1e-3)) / out["value_resident"]["value"],
+                                     "what": "whamd_dptable_create (flatten + plan + upload) + solve + 3 getters of ONE fresh table from host arrays"}
+                if not args.sub:
+                    # the same with the create path held to 8 host threads (WHAMD_PLAN_THREADS; the default is min(hardware threads, 32))
+                    saved = os.environ.get("WHAMD_PLAN_THREADS")
+                    os.environ["WHAMD_PLAN_THREADS"] = "8"
+                    try:
+                        create8, rest8 = fresh_table()
+                    finally:
+                        if saved is None:
+                            del os.environ["WHAMD_PLAN_THREADS"]
+                        else:
+                            os.environ["WHAMD_PLAN_THREADS"] = saved
+                    out["end_to_end"]["create_ms_8_threads"] = create8
+                    out["end_to_end"]["value_8_threads"] = v / ((create8 + rest8) * 1e-3)
+            elif world == 1:
+                # several tables: `value` already is the host-side work queue from host arrays (region 2); end to end adds the three getters of every table
                 te0 = time.perf_counter()
-                fresh = _native.NativeTable(problem, device=device, path=None if args.path == "auto" else args.path, solve=False)
-                apply_options(fresh, args)
-                te1 = time.perf_counter()
-                fresh.solve()
-                fresh.optimal_score(), fresh.super_reads(), fresh.partitioning()
-                te2 = time.perf_counter()
-                fresh_stats.update(fresh.stats())
-                fresh.close()
-                return (te1 - te0) * 1e3, (te2 - te1) * 1e3
-
-            fresh_stats = {}
-            fresh_table()   # (the first create of a process also sizes the pinned staging area)
-            create_ms, rest_ms = fresh_table()
-            # "from entering the constructor to index_path complete, excluding ReadSet flattening and superread assembly".  The
-            # constructor of the reference (src/pedigreedptable.cpp:15-37) walks the columns, builds the indexing schemes and runs compute_table;
-            # here that is ALL of whamd_dptable_create (columns + indexing scheme + cost terms, plan, upload: its input is the flattened CSR view)
-            # plus the device's forward pass, backtrace and path download; whamd_dptable_wait's superread assembly (host_finish_ms) stays outside.
-            strict_ms = create_ms + fresh_stats["total_ms"]
-            out["value_8d_strict"] = {"value": v / (strict_ms * 1e-3), "unit": "variant-columns/s", "ms": strict_ms, "create_ms": create_ms,
-                                      "flatten_ms": fresh_stats.get("host_flatten_ms"),
-                                      "terms_plan_upload_ms": (create_ms - fresh_stats["host_flatten_ms"]) if fresh_stats.get("host_flatten_ms") is not None else None,
-                                      "device_ms": fresh_stats["total_ms"], "superreads_ms_excluded": fresh_stats["host_finish_ms"],
-                                      "what": "SURVEY 8(d) to the letter for ONE fresh table: whamd_dptable_create (flatten_ms = ColumnIterator's columns; the rest = indexing scheme, cost terms, plan, upload) + forward + backtrace + path download; superread assembly and destroy excluded (`value` includes both)"}
-            out["end_to_end"] = {"value": v / ((create_ms + rest_ms) * 1e-3), "unit": "variant-columns/s", "create_ms": create_ms,
-                                 "solve_and_getters_ms": rest_ms, "host_threads": min(os.cpu_count() or 1, 32),
-                                 "fraction_of_device_only": (v / ((create_ms + rest_ms) * 1e-3)) / out["value_resident"]["value"],
-                                 "what": "whamd_dptable_create (flatten + plan + upload) + solve + 3 getters of ONE fresh table from host arrays"}
-            if not args.sub:
-                # the same with the create path held to 8 host threads (WHAMD_PLAN_THREADS; the default is min(hardware threads, 32))
-                saved = os.environ.get("WHAMD_PLAN_THREADS")
-                os.environ["WHAMD_PLAN_THREADS"] = "8"
+                solved = solve_blocks(problems, device=device, path=native_path, max_in_flight=shape[2], release=True, create_threads=shape[0], host_threads_per_create=shape[1], windows_on_device=shape[3])
+                checksum = 0
+                for t in solved:
+                    checksum += t.optimal_score()
+                    t.super_reads(), t.partitioning()
+                wall = time.perf_counter() - te0
+                for t in solved:
+                    t.close()
+                if checksum != int(totals[2]):
+                    raise SystemExit(f"end_to_end: cost checksum {checksum} of the pipelined solve differs from {int(totals[2])}")
+                out["end_to_end"] = {"value": cols_job / wall, "unit": "variant-columns/s", "wall_ms": wall * 1e3, "tables_per_window": shape[2], "create_threads": shape[0],
+                                     "host_threads_per_create": shape[1], "fraction_of_device_only": (cols_job / wall) / out["value_resident"]["value"], "tried": tried,
+                                     "what": f"{len(problems)} fresh tables from host arrays through blocks.solve_blocks (create of the next window on `create_threads` host workers x "
+                                             f"`host_threads_per_create` threads under the device solve of the current one, enqueue_many / wait_many per window) + 3 getters per table"}
+                # ---- how many fresh tables per second ONE RANK'S SHARE of this host hands to its device (one node's host feeds eight GPUs): creates only, in a child process
+                # bound to the CPU slice rank 0 of 8 would get (bind_rank_to_device_cpus), against the rate at which one device solves such tables with its tables resident
+                device_tables_per_s = len(problems) * args.steps / elapsed_resident
+                rate = {"device_tables_per_s": device_tables_per_s, "host_nproc": os.cpu_count()}
                 try:
-                    create8, rest8 = fresh_table()
-                finally:
-                    if saved is None:
-                        del os.environ["WHAMD_PLAN_THREADS"]
+                    _native.release_caches()   # (the child sizes its arenas by the device's FREE memory: this process's kept arenas and pools go back first -- eight trio tables are 127 GB)
+                    cmd = [sys.executable, os.path.abspath(__file__), "--create-rate-worker", "0/8", "--coverage", str(args.coverage), "--variants", str(blocks[0][1]),
+                           "--blocks", str(len(problems)), "--path", args.path] + workload_flags(args)
+                    for kv in args.option:
+                        cmd += ["--option", kv]
+                    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+                    line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+                    if res.returncode == 0 and line:
+                        rate.update(json.loads(line[-1]))
+                        rate["host_over_8_devices"] = rate["tables_per_s"] / device_tables_per_s
+                        rate["what"] = (f"{len(problems)} whamd_dptable_create calls (flatten + plan + upload, no solve) in a process held to the CPUs rank 0 of 8 gets "
+                                        f"({rate.get('cpus')} of {os.cpu_count()}: the NUMA node of its GPU shared evenly), best of the host shapes tried; against the tables per second ONE device "
+                                        f"solves with its tables resident: below 1.0 an 8-GPU node is bound by its host.  (Rounds 4-5 divided the WHOLE host's single-process rate by 8.)")
                     else:
-                        os.environ["WHAMD_PLAN_THREADS"] = saved
-                out["end_to_end"]["create_ms_8_threads"] = create8
-                out["end_to_end"]["value_8_threads"] = v / ((create8 + rest8) * 1e-3)
-        elif world == 1:
-            # several tables: `value` already is the host-side work queue from host arrays (region 2); end to end adds the three getters of every table
-            te0 = time.perf_counter()
-            solved = solve_blocks(problems, device=device, path=native_path, max_in_flight=shape[2], release=True, create_threads=shape[0], host_threads_per_create=shape[1], windows_on_device=shape[3])
-            checksum = 0
-            for t in solved:
-                checksum += t.optimal_score()
-                t.super_reads(), t.partitioning()
-            wall = time.perf_counter() - te0
-            for t in solved:
-                t.close()
-            if checksum != int(totals[2]):
-                raise SystemExit(f"end_to_end: cost checksum {checksum} of the pipelined solve differs from {int(totals[2])}")
-            out["end_to_end"] = {"value": cols_job / wall, "unit": "variant-columns/s", "wall_ms": wall * 1e3, "tables_per_window": shape[2], "create_threads": shape[0],
-                                 "host_threads_per_create": shape[1], "fraction_of_device_only": (cols_job / wall) / out["value_resident"]["value"], "tried": tried,
-                                 "what": f"{len(problems)} fresh tables from host arrays through blocks.solve_blocks (create of the next window on `create_threads` host workers x "
-                                         f"`host_threads_per_create` threads under the device solve of the current one, enqueue_many / wait_many per window) + 3 getters per table"}
-            # ---- how many fresh tables per second ONE RANK'S SHARE of this host hands to its device (one node's host feeds eight GPUs): creates only, in a child process
-            # bound to the CPU slice rank 0 of 8 would get (bind_rank_to_device_cpus), against the rate at which one device solves such tables with its tables resident
-            device_tables_per_s = len(problems) * args.steps / elapsed_resident
-            rate = {"device_tables_per_s": device_tables_per_s, "host_nproc": os.cpu_count()}
-            try:
-                _native.release_caches()   # (the child sizes its arenas by the device's FREE memory: this process's kept arenas and pools go back first -- eight trio tables are 127 GB)
-                cmd = [sys.executable, os.path.abspath(__file__), "--create-rate-worker", "0/8", "--coverage", str(args.coverage), "--variants", str(blocks[0][1]),
-                       "--blocks", str(len(problems)), "--path", args.path] + workload_flags(args)
-                for kv in args.option:
-                    cmd += ["--option", kv]
-                res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-                line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
-                if res.returncode == 0 and line:
-                    rate.update(json.loads(line[-1]))
-                    rate["host_over_8_devices"] = rate["tables_per_s"] / device_tables_per_s
-                    rate["what"] = (f"{len(problems)} whamd_dptable_create calls (flatten + plan + upload, no solve) in a process held to the CPUs rank 0 of 8 gets "
-                                    f"({rate.get('cpus')} of {os.cpu_count()}: the NUMA node of its GPU shared evenly), best of the host shapes tried; against the tables per second ONE device "
-                                    f"solves with its tables resident: below 1.0 an 8-GPU node is bound by its host.  (Rounds 4-5 divided the WHOLE host's single-process rate by 8.)")
-                else:
-                    rate["error"] = f"rc={res.returncode} {res.stderr[-200:]}"
-            except Exception as exc:  # noqa: BLE001 -- never costs the line
-                rate["error"] = repr(exc)
-            out["create_rate"] = rate
-        # ---- counters of the dominant kernel
-        pmc, pmc_note = None, "skipped"
-        want_pmc = args.pmc == "on" or (args.pmc == "auto" and world == 1 and not column_path)
-        if want_pmc:
-            for t in tables:
-                t.release_device()
-            try:
-                pmc, pmc_note = run_pmc_passes(args, kernel, args.pmc_keep)
-            except Exception as exc:  # noqa: BLE001 -- the bench line must come out whatever the profiler does
-                pmc_note = repr(exc)
-        out["roofline"] = roofline_from_counters(pmc, avg_launch_us, kernel, bytes_per_launch, args)
-        out["roofline"]["pmc_note"] = pmc_note
-        # work-based bound: the fewest VALU lane-operations the algorithm needs per evaluated (cell, transmission value) of a
-        # column -- single individual: A, K - A, min3, accumulate + ending reads = 5, half of the cells by symmetry; trio (NF = 2): 2 adds + min,
-        # 2 x 6 butterfly, accumulate, ending reads = 19; quartet 31 -- issued at the chip's 512 wave-instructions per cycle, over the forward time
-        ops = {1: 5.0, 4: 19.0, 16: 31.0}[T]
-        if T == 1 and args.path == "auto" and not args.distrust:
-            # Y-form runs: one absolute-difference-accumulate per evaluated cell-column, a quarter of the add that forms the thread's
-            # operand, and per ending read (0.5 per column) compare, shift-in and maximum on each pair: 1 + 0.25 + 1.5 = 2.75
-            ops = 2.75
-        evaluated = costs_job / world * (0.5 if T == 1 else 1.0)
-        out["roofline"]["work_bound_frac"] = (evaluated * ops / 64.0 / (N_SIMD / 2.0) / (CLOCK_GHZ * 1e9)) / max(fwd_ms / args.steps * 1e-3, 1e-12)
-        out["roofline"]["work_bound_note"] = f"{ops:g} VALU lane-operations per evaluated cell-value of a column at 512 wave-instructions/cycle, over the forward time of a step"
-        # ---- CPU baseline (rank 0, N = 1 only)
-        args.variants_for_cpu = blocks[0][1]
-        args.device_for_parity = device
-        if world == 1 and args.cpu_baseline_columns != 0:
-            out["cpu_baseline"] = cpu_baseline(args, blocks[0][0])
-            out["identical_to_reference"] = out["cpu_baseline"].pop("identical_to_reference")
-            out["identical_what"] = out["cpu_baseline"].pop("identical_what")
-            out["speedup_vs_cpu_baseline_device_only"] = out["value_resident"]["value"] / out["cpu_baseline"]["value"]
-            out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        procs = args.cpu_baseline_procs if args.cpu_baseline_procs >= 0 else (os.cpu_count() or 1)
-        if world == 1 and procs > 0:
-            out["cpu_baseline_all_cores"] = cpu_baseline_procs(args, procs)
-        # ---- the other single-GPU workloads of BASELINE.json (+ an irregular layout, + a quartet)
-        if args.configs == "on" or (args.configs == "auto" and world == 1 and not explicit and not args.sub):
-            for t in tables:
-                t.release_device()
-            out["configs"] = run_extra_configs(args)
+                        rate["error"] = f"rc={res.returncode} {res.stderr[-200:]}"
+                except Exception as exc:  # noqa: BLE001 -- never costs the line
+                    rate["error"] = repr(exc)
+                out["create_rate"] = rate
+            # ---- counters of the dominant kernel
+            pmc, pmc_note = None, "skipped"
+            want_pmc = args.pmc == "on" or (args.pmc == "auto" and world == 1 and not column_path)
+            if want_pmc:
+                for t in tables:
+                    t.release_device()
+                try:
+                    pmc, pmc_note = run_pmc_passes(args, kernel, args.pmc_keep)
+                except Exception as exc:  # noqa: BLE001 -- the bench line must come out whatever the profiler does
+                    pmc_note = repr(exc)
+            out["roofline"] = roofline_from_counters(pmc, avg_launch_us, kernel, bytes_per_launch, args)
+            out["roofline"]["pmc_note"] = pmc_note
+            # work-based bound: the fewest VALU lane-operations the algorithm needs per evaluated (cell, transmission value) of a
+            # column -- single individual: A, K - A, min3, accumulate + ending reads = 5, half of the cells by symmetry; trio (NF = 2): 2 adds + min,
+            # 2 x 6 butterfly, accumulate, ending reads = 19; quartet 31 -- issued at the chip's 512 wave-instructions per cycle, over the forward time
+            ops = {1: 5.0, 4: 19.0, 16: 31.0}[T]
+            if T == 1 and args.path == "auto" and not args.distrust:
+                # Y-form runs: one absolute-difference-accumulate per evaluated cell-column, a quarter of the add that forms the thread's
+                # operand, and per ending read (0.5 per column) compare, shift-in and maximum on each pair: 1 + 0.25 + 1.5 = 2.75
+                ops = 2.75
+            evaluated = costs_job / world * (0.5 if T == 1 else 1.0)
+            out["roofline"]["work_bound_frac"] = (evaluated * ops / 64.0 / (N_SIMD / 2.0) / (CLOCK_GHZ * 1e9)) / max(fwd_ms / args.steps * 1e-3, 1e-12)
+            out["roofline"]["work_bound_note"] = f"{ops:g} VALU lane-operations per evaluated cell-value of a column at 512 wave-instructions/cycle, over the forward time of a step"
+            # ---- CPU baseline (rank 0, N = 1 only)
+            args.variants_for_cpu = blocks[0][1]
+            args.device_for_parity = device
+            if world == 1 and args.cpu_baseline_columns != 0:
+                out["cpu_baseline"] = cpu_baseline(args, blocks[0][0])
+                out["identical_to_reference"] = out["cpu_baseline"].pop("identical_to_reference")
+                out["identical_what"] = out["cpu_baseline"].pop("identical_what")
+                out["speedup_vs_cpu_baseline_device_only"] = out["value_resident"]["value"] / out["cpu_baseline"]["value"]
+                out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
+            procs = args.cpu_baseline_procs if args.cpu_baseline_procs >= 0 else (os.cpu_count() or 1)
+            if world == 1 and procs > 0:
+                out["cpu_baseline_all_cores"] = cpu_baseline_procs(args, procs)
+            # ---- the other single-GPU workloads of BASELINE.json (+ an irregular layout, + a quartet)
+            if args.configs == "on" or (args.configs == "auto" and world == 1 and not explicit and not args.sub):
+                for t in tables:
+                    t.release_device()
+                out["configs"] = run_extra_configs(args)
         emit(out, args)
         parity = [out.get("identical_to_reference")] + [c.get("identical_to_reference") for c in out.get("configs", [])]
         if any(x is False for x in parity):

@@ -76,6 +76,13 @@ def test_gpus_without_devices_is_refused():
     assert "refusing to run fewer ranks" in (res.stdout + res.stderr) or "no HIP device" in (res.stdout + res.stderr)
 
 
+def test_measurements_of_a_full_run_are_refused_without_full():
+    """Counters, CPU baselines and `configs` are measured by `bench.py --full` only: asking a plain run for them is an error, not a silent no-op."""
+    for extra in (["--configs", "on"], ["--pmc", "on"], ["--cpu-baseline-columns", "100"], ["--cpu-baseline-procs", "4"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120)
+        assert res.returncode != 0 and "--full run only" in res.stderr, (extra, res.stderr[-500:])
+
+
 def test_roofline_fractions_from_counters():
     b = _bench()
     pmc = {"SQ_INSTS_VALU": 2.74e6, "FETCH_SIZE": 1254.1, "WRITE_SIZE": 4833.6, "SQ_LDS_IDX_ACTIVE": 1.62e6,

@@ -679,7 +679,7 @@ def test_bench_with_two_ranks_on_one_device_matches_a_single_rank():
     import json, os, subprocess, sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--variants", "4000", "--blocks", "6", "--coverage", "14", "--steps", "1", "--warmup", "1", "--pmc", "off", "--cpu-baseline-columns", "0"]
+    common = ["--full", "--variants", "4000", "--blocks", "6", "--coverage", "14", "--steps", "1", "--warmup", "1", "--pmc", "off", "--cpu-baseline-columns", "0"]
     lines = []
     for gpus in (1, 2):
         res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--oversubscribe"] + common,
@@ -702,6 +702,33 @@ def test_bench_with_two_ranks_on_one_device_matches_a_single_rank():
     # per-rank checksums against single-rank solves of exactly those blocks
     for seeds, checksum in zip(two["config"]["block_seeds_per_rank"], two["config"]["optimal_cost_checksum_per_rank"]):
         assert checksum == sum(_native.NativeTable(synthetic_block(4000, 14, seed=s)).optimal_score() for s in seeds)
+
+
+def test_plain_bench_run_reports_the_headline_only_and_dumps_what_a_full_run_dumps(tmp_path):
+    """A plain `bench.py` run carries the contract's fields and none of the figures that take runs of their own (those are
+    --full's); the outputs it dumps with --dump-outputs are those of a --full run of the same workload."""
+    import json, os, subprocess, sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--variants", "4000", "--coverage", "14", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--pmc", "off", "--cpu-baseline-columns", "0"])):
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common + extra
+                             + ["--dump-outputs", str(tmp_path / mode), "--detail-file", str(tmp_path / f"{mode}_detail.json")],
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[mode] = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup"):
+        assert plain[key] == full[key], key
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["config"]["optimal_cost_checksum"] == full["config"]["optimal_cost_checksum"]
+    assert not {"value_resident", "roofline", "cpu_baseline", "end_to_end", "value_8d_strict", "create_rate", "configs"} & set(plain)
+    assert {"value_resident", "roofline", "end_to_end", "value_8d_strict"} <= set(full)
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)), name
 
 
 def test_shim_with_compiled_ingestion_on_plain_reference_objects():
