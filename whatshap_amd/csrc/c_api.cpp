@@ -13,6 +13,7 @@
 #ifdef WHAMD_DEBUG_BUILD
 #include "../../include/whatshap_amd_debug.h"
 #endif
+#include "device_runtime.h"
 #include "device_table.h"
 #include "genotype.h"
 #include "heuristic.h"
@@ -1027,9 +1028,7 @@ whamd_status_t whamd_genotype_likelihoods(const whamd_readset_view* readset, con
 uint64_t whamd_host_pool_idle_bytes(void) { return (uint64_t)whamd::host_pool_idle_bytes(); }
 
 void whamd_release_caches(void) {
-	genotype_release_cache();
-	whamd::heuristic_release_cache();
-	whamd::dptable_release_caches();
+	whamd::device_release_caches();
 	whamd::host_pool_release();   // the host side's kept blocks (host_memory.cpp)
 }
 

@@ -1,0 +1,120 @@
+// device_runtime.h -- what every device layer shares on the host side (device_runtime.cpp; no kernels): the pools that keep device
+// buffers, pinned blocks, streams with their events and backtrace arenas between calls (per process, every device), the upload streams
+// and pinned staging areas of the create path, and the per-call Session.  whamd_release_caches() empties the pools through
+// device_release_caches().
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/whatshap_amd.h"
+
+// `msg` (std::string&) is in scope; the enclosing function returns whamd_status_t.
+#define HIP_TRY(expr)                                                                                 \
+	do {                                                                                              \
+		hipError_t err_ = (expr);                                                                     \
+		if (err_ != hipSuccess) {                                                                     \
+			msg = std::string(#expr) + " failed: " + hipGetErrorString(err_);                         \
+			return WHAMD_ERR_DEVICE;                                                                  \
+		}                                                                                             \
+	} while (0)
+
+namespace whamd {
+
+// Makes `device` current; the two messages of a call without a usable device are written here and nowhere else.
+whamd_status_t open_device(int device, std::string& msg);
+
+// ---------------------------------------------------------------------------------------------- device pool
+// A create / solve used to hipMalloc 20 - 30 arrays and hipFree them again, each a driver round trip behind one driver lock (tables
+// created on several host threads at once waited for each other there).  Blocks are taken from and given back to a pool, rounded to
+// size classes (eight per power of two: at most 12.5 % over) so that the tables of one run reuse each other's.
+// *got = the block's real size (the class): give exactly that back.
+hipError_t devpool_take(int device, size_t bytes, void** out, size_t* got);
+// The caller has made sure nothing on the device still uses the block (stream synchronised).
+void devpool_give(int device, void* ptr, size_t bytes);
+void devpool_release();
+// The pinned host blocks (the solves' download buffers, the calls' staging blocks): same size classes, at most 1 GiB kept idle.
+hipError_t pinned_take(size_t bytes, void** out, size_t* got);
+void pinned_give(void* ptr, size_t bytes);
+
+// A table's stream and events come from a pool as well: creating and destroying them per table (a stream, five events, hipHostMalloc /
+// hipHostFree of the path buffer) was as expensive as the whole create of a coverage-15 table (24 tables: create 103 ms on 8 threads,
+// close 110 ms).  ev[0 .. 3] record times, ev[4] and ev[5] do not.
+struct StreamSet { hipStream_t stream = nullptr; hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int device = -1; };
+bool streamset_take(int device, StreamSet& out);
+void streamset_give(const StreamSet& ss);   // (the stream is idle: the caller synchronised it)
+
+// One of the streams the UPLOADS of all tables of `device` go through (shared, used for nothing else); nullptr if none could be made.
+hipStream_t upload_stream_of(int device);
+
+// ---------------------------------------------------------------------------------------------- arenas kept between tables
+// nullptr: nothing suitable.  `make_room`: the caller is about to hipMalloc `need` bytes -- blocks that do not fit are freed first.
+void* arena_take(int device, size_t need, size_t& got, bool make_room = true);
+void arena_give(int device, void* ptr, size_t bytes);   // called with `device` current
+size_t arena_idle_bytes(int device);
+void arena_release();   // every idle arena goes back to the driver (a call that finds the device more than half full does this first)
+
+// Everything above and the idle staging areas, and the genotyper's column store (genotype.h): whamd_release_caches.
+void device_release_caches();
+
+// ---------------------------------------------------------------------------------------------- pinned staging of the create path
+constexpr size_t STAGE_MAX = (size_t)1 << 30;
+// One upload()'s hold on a pinned staging area (device_runtime.cpp, UploadStage) and the copies it sends from there on `stream`.
+struct StageSession {
+	hipStream_t stream;
+	size_t used = 0, total = 0;
+	bool pending = false;
+	const bool enabled;
+	int slot = -1;          // the area this session owns, -1: none (pageable copies)
+	char* base = nullptr;
+	size_t cap = 0;
+	// One image of everything a table uploads (DeviceTable::upload): the area holds `bytes` and copy() leaves it alone (pieces that do not fit the image go
+	// out as copies of their own, straight from the caller's memory).
+	bool image = false;
+	explicit StageSession(hipStream_t s);
+	~StageSession();
+	// The table's create returns without waiting for the copies (DeviceTable::upload): the area stays reserved -- for the NEXT session -- behind an event.
+	bool park();
+	bool ensure(size_t bytes);   // area empty (nothing pending): make it hold `bytes`, or everything the largest table so far staged
+	hipError_t copy(void* dst, const void* src, size_t bytes);
+	bool begin_image(size_t bytes);
+	void expect(size_t bytes);   // before the first copy: one allocation
+	void finish() {              // after the caller synchronised the stream
+		pending = false;
+		used = 0;
+	}
+};
+
+// ---------------------------------------------------------------------------------------------- one call on one device
+// What a call holds on the device and in pinned memory; given back on every way out.
+struct Session {
+	int device = -1;
+	hipStream_t stream = nullptr;
+	std::vector<hipEvent_t> ev;              // [0, n_events) of open() record times (ms); sync_event() appends
+	std::vector<hipStream_t> streams;        // add_stream()
+	std::vector<std::pair<void*, size_t>> dev, pinned;   // (pointer, size class) of the pools
+	std::vector<void*> fresh;                // fresh_block()
+	Session() = default;
+	Session(const Session&) = delete;
+	Session& operator=(const Session&) = delete;
+	~Session() { close(); }
+	// open_device(), a stream of the call's own and `n_events` events that record times.
+	whamd_status_t open(int dev_index, int n_events, std::string& msg);
+	// Waits for the stream, gives the blocks back, destroys events and streams.  (The destructor; a caller that times it calls it itself.)
+	void close();
+	whamd_status_t device_block(size_t bytes, void** out, std::string& msg);
+	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg);
+	// Not from the pool: hipMalloc -- after devpool_release() once more if the first fails -- and hipFree when the session ends.
+	hipError_t fresh_block(void** out, size_t bytes);
+	hipError_t add_stream(hipStream_t* out);
+	hipError_t sync_event(hipEvent_t* out);   // hipEventDisableTiming: orders streams, records no time
+	double ms(int a, int b) const {
+		float t = 0.0f;
+		return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
+	}
+};
+
+}  // namespace whamd

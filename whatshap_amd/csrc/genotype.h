@@ -42,11 +42,8 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, int device, std::vector<double>& gl_out, GenotypeStats& st,
                                     bool& used, std::string& msg);
 
-// Frees the device memory genotype_solve_device keeps between calls (one column store per device).
+// Frees the device memory genotype_solve_device keeps between calls (one column store per device); device_release_caches() calls it.
 void genotype_release_cache();
-// The phasing tables' counterpart (dp_device.hip): one backtrace arena kept between tables; a genotyping call that finds the device
-// more than half full gives it back first.
-void dptable_release_arena_cache();
 // The column store kept between calls (mapping tens of GB of fresh device memory took seconds in one call out of four):
 // acquire returns the cached block of `device` grown to `bytes` and marks it in use, or nullptr (in use by another call,
 // allocation failed, caching disabled) -- the caller then allocates its own.  release marks it idle again; a block larger than
@@ -54,5 +51,11 @@ void dptable_release_arena_cache();
 void* genotype_slab_acquire(int device, size_t bytes);
 void genotype_slab_release(int device);
 size_t genotype_slab_idle_bytes(int device);
+// A call's hold on the acquired block (`device` >= 0): released on every way out.  Declared before the call's Session, so that the
+// session has waited for its stream by then.
+struct GenotypeSlabHold {
+	int device = -1;
+	~GenotypeSlabHold() { if (device >= 0) genotype_slab_release(device); }
+};
 
 }  // namespace whamd

@@ -29,17 +29,8 @@
 #include <mutex>
 
 #include "debug_build.h"
-#include "device_pool.h"
+#include "device_runtime.h"
 #include "genotype.h"
-
-#define GENO_TRY(expr)                                                                                   \
-	do {                                                                                                 \
-		hipError_t e_ = (expr);                                                                          \
-		if (e_ != hipSuccess) {                                                                          \
-			msg = std::string(#expr) + " failed: " + hipGetErrorString(e_);                              \
-			return WHAMD_ERR_DEVICE;                                                                     \
-		}                                                                                                \
-	} while (0)
 
 namespace whamd {
 
@@ -555,17 +546,9 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	st.n_columns = n;
 	st.transmissions = T;
 	if (n == 0) return WHAMD_OK;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-		msg = "no HIP device visible: the whatshap_amd device path needs an MI355X (gfx950); there is no CPU fallback";
-		return WHAMD_ERR_DEVICE;
-	}
-	if (device < 0 || device >= ndev) {
-		msg = "device index " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)";
-		return WHAMD_ERR_DEVICE;
-	}
+	const whamd_status_t opened = open_device(device, msg);
+	if (opened != WHAMD_OK) return opened;
 	if (T != 1 && T != 4 && T != 16) { msg = "unsupported number of transmission values"; return WHAMD_ERR_UNSUPPORTED; }
-	GENO_TRY(hipSetDevice(device));
 	// the run-fused path wherever it applies (no forced window, every column in a run, stores fit in HBM)
 	if (!window_hint && !debug_env("WHAMD_GENOTYPE_COLUMNS")) {
 		bool used = false;
@@ -588,10 +571,10 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	const uint32_t max_blocks = (uint32_t)(((((size_t)1 << max_k) * T) + GENO_BLOCK - 1) / GENO_BLOCK);
 	const uint32_t n_gl = 1 + 3 * ni;
 	size_t free_b = 0, total_b = 0;
-	GENO_TRY(hipMemGetInfo(&free_b, &total_b));
+	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	if (free_b < total_b / 2) {   // a phasing table of this process may have left its arena in the cache (dp_device.hip)
-		dptable_release_arena_cache();
-		GENO_TRY(hipMemGetInfo(&free_b, &total_b));
+		arena_release();
+		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	}
 	free_b += genotype_slab_idle_bytes(device);   // the block kept from an earlier call is available to this one
 	// Window = how many backward columns are kept at once.  If all of them fit in a quarter of the free memory there is one
@@ -614,35 +597,12 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	}
 	const auto t_phase0 = std::chrono::steady_clock::now();
 	auto phase_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase0).count(); };
-	hipStream_t stream = nullptr;
-	GENO_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-	std::vector<void*> allocations;
-	std::vector<hipStream_t> extra_streams;   // the second chain's stream and every event: owned by cleanup(), whichever way the call ends
-	std::vector<hipEvent_t> all_events;
-	bool slab_from_cache = false;
-	auto cleanup = [&]() {
-		for (hipEvent_t e : all_events) (void)hipEventDestroy(e);
-		for (hipStream_t s2 : extra_streams) (void)hipStreamDestroy(s2);
-		for (void* a : allocations) (void)hipFree(a);
-		if (slab_from_cache) genotype_slab_release(device);
-		if (stream) (void)hipStreamDestroy(stream);
-	};
-	auto fail = [&](hipError_t e, const char* what) {
-		msg = std::string(what) + " failed: " + hipGetErrorString(e);
-		cleanup();
-		return WHAMD_ERR_DEVICE;
-	};
-#define GENO_DEV(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(e_, #expr); } while (0)
-	auto alloc = [&](void** dptr, size_t bytes) -> hipError_t {
-		hipError_t e = hipMalloc(dptr, std::max<size_t>(bytes, 16));
-		if (e != hipSuccess) {   // idle blocks of the phasing / heuristic pool may hold the memory: give them back, try once more
-			(void)hipGetLastError();
-			devpool_release();
-			e = hipMalloc(dptr, std::max<size_t>(bytes, 16));
-		}
-		if (e == hipSuccess) allocations.push_back(*dptr);
-		return e;
-	};
+	GenotypeSlabHold slab;
+	Session ses;   // the second chain's stream, every event and every block: the session's, whichever way the call ends
+	const whamd_status_t session_open = ses.open(device, 3, msg);
+	if (session_open != WHAMD_OK) return session_open;
+	const hipStream_t stream = ses.stream;
+	auto alloc = [&](void** dptr, size_t bytes) { return ses.fresh_block(dptr, bytes); };
 	auto up = [&](void** dptr, const void* src, size_t bytes) -> hipError_t {
 		hipError_t e = alloc(dptr, bytes);
 		if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, stream);
@@ -658,19 +618,19 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	}
 	GenoDev G{};
 	void *d_col_ptr, *d_ind, *d_allele, *d_pe, *d_k, *d_b, *d_f, *d_fmask, *d_bern, *d_prior, *d_gidx, *d_h2p, *d_fwb;
-	GENO_DEV(up(&d_col_ptr, p.col_ptr.data(), p.col_ptr.size() * 8));
-	GENO_DEV(up(&d_ind, ent_ind.data(), ent_ind.size()));
-	GENO_DEV(up(&d_allele, ent_allele.data(), ent_allele.size()));
-	GENO_DEV(up(&d_pe, m.error_prob.data(), m.error_prob.size() * 8));
-	GENO_DEV(up(&d_k, p.k.data(), n));
-	GENO_DEV(up(&d_b, p.b.data(), n));
-	GENO_DEV(up(&d_f, p.f.data(), n));
-	GENO_DEV(up(&d_fmask, p.fwd_mask.data(), (size_t)n * 4));
-	GENO_DEV(up(&d_bern, m.transition_bern.data(), m.transition_bern.size() * 8));
-	GENO_DEV(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
-	GENO_DEV(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
-	GENO_DEV(up(&d_h2p, p.h2p.data(), p.h2p.size()));
-	GENO_DEV(up(&d_fwb, fw_blocks.data(), (size_t)n * 4));
+	HIP_TRY(up(&d_col_ptr, p.col_ptr.data(), p.col_ptr.size() * 8));
+	HIP_TRY(up(&d_ind, ent_ind.data(), ent_ind.size()));
+	HIP_TRY(up(&d_allele, ent_allele.data(), ent_allele.size()));
+	HIP_TRY(up(&d_pe, m.error_prob.data(), m.error_prob.size() * 8));
+	HIP_TRY(up(&d_k, p.k.data(), n));
+	HIP_TRY(up(&d_b, p.b.data(), n));
+	HIP_TRY(up(&d_f, p.f.data(), n));
+	HIP_TRY(up(&d_fmask, p.fwd_mask.data(), (size_t)n * 4));
+	HIP_TRY(up(&d_bern, m.transition_bern.data(), m.transition_bern.size() * 8));
+	HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
+	HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
+	HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
+	HIP_TRY(up(&d_fwb, fw_blocks.data(), (size_t)n * 4));
 	G.col_ptr = (const uint64_t*)d_col_ptr; G.ent_ind = (const uint8_t*)d_ind; G.ent_allele = (const uint8_t*)d_allele; G.ent_pe = (const double*)d_pe;
 	G.k = (const uint8_t*)d_k; G.b = (const uint8_t*)d_b; G.f = (const uint8_t*)d_f; G.fwd_mask = (const uint32_t*)d_fmask;
 	G.bern = (const double*)d_bern; G.prior = (const double*)d_prior; G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p;
@@ -685,7 +645,7 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 				G.slot_of[2 * s] = (uint8_t)p.h2p[(size_t)s * 2];
 				G.slot_of[2 * s + 1] = (uint8_t)p.h2p[(size_t)s * 2 + 1];
 			} else {
-				if (p.P != 4 || child_slots + 2 > 4) { cleanup(); msg = "unsupported pedigree shape for device genotyping"; return WHAMD_ERR_UNSUPPORTED; }
+				if (p.P != 4 || child_slots + 2 > 4) { msg = "unsupported pedigree shape for device genotyping"; return WHAMD_ERR_UNSUPPORTED; }
 				for (uint32_t h = 0; h < 2; ++h) {
 					G.slot_of[2 * s + h] = (uint8_t)(p.P + child_slots + h);
 					for (uint32_t i = 0; i < T; ++i) G.child_part[i][child_slots + h] = (uint8_t)p.h2p[((size_t)i * ni + s) * 2 + h];
@@ -699,11 +659,10 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	const uint32_t max_groups = (max_k + GENO_GROUP_BITS - 1) / GENO_GROUP_BITS;
 	G.table_stride = std::max(1u, max_groups) * GENO_GROUP * 4 * ni;
 	double* d_tables = nullptr;
-	GENO_DEV(alloc((void**)&d_tables, (size_t)n * G.table_stride * sizeof(double)));
+	HIP_TRY(alloc((void**)&d_tables, (size_t)n * G.table_stride * sizeof(double)));
 	G.tables = d_tables;
 	const size_t table_bytes = (size_t)G.table_stride * sizeof(double);   // the step kernels copy their column's tables into LDS
 	if (table_bytes + sizeof(GenoShared) > 160 * 1024) {   // (a quartet beyond coverage ~35: never reached below the 25-read limit, but never a bare launch failure)
-		cleanup();
 		msg = "lookup tables of " + std::to_string(table_bytes >> 10) + " KiB per column do not fit in LDS";
 		return WHAMD_ERR_UNSUPPORTED;
 	}
@@ -712,7 +671,7 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		                     (const void*)geno_forward<1, 0>, (const void*)geno_forward<1, 1>, (const void*)geno_forward<1, 2>,
 		                     (const void*)geno_forward<4, 0>, (const void*)geno_forward<4, 1>, (const void*)geno_forward<4, 2>,
 		                     (const void*)geno_forward<16, 0>, (const void*)geno_forward<16, 1>, (const void*)geno_forward<16, 2>};
-		for (const void* fn : fns) GENO_DEV(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(GenoShared)));
+		for (const void* fn : fns) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(GenoShared)));
 	}
 	// ---- buffers: every column buffer carries its per-block sums
 	struct Buf { double* v = nullptr; double* partials = nullptr; uint32_t blocks = 0; };
@@ -723,9 +682,9 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		const size_t count = 4 + (size_t)n_windows + wstore.size() + astore.size();
 		double *slab_v = nullptr, *slab_p = nullptr;
 		slab_v = (double*)genotype_slab_acquire(device, count * buf_doubles * 8);
-		slab_from_cache = slab_v != nullptr;
-		if (!slab_v) GENO_DEV(alloc((void**)&slab_v, count * buf_doubles * 8));
-		GENO_DEV(alloc((void**)&slab_p, count * (size_t)max_blocks * 8));
+		if (slab_v) slab.device = device;
+		if (!slab_v) HIP_TRY(alloc((void**)&slab_v, count * buf_doubles * 8));
+		HIP_TRY(alloc((void**)&slab_p, count * (size_t)max_blocks * 8));
 		size_t next = 0;
 		auto take = [&](Buf& bf) { bf.v = slab_v + next * buf_doubles; bf.partials = slab_p + next * max_blocks; ++next; };
 		for (Buf& bf : alpha) take(bf);
@@ -735,10 +694,9 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		for (Buf& bf : astore) take(bf);
 	}
 	double *d_glpart = nullptr, *d_gl = nullptr;
-	GENO_DEV(alloc((void**)&d_glpart, (size_t)std::min<uint32_t>(K, n_windows == 1 ? 1024u : K) * max_blocks * n_gl * 8));
-	GENO_DEV(alloc((void**)&d_gl, gl_out.size() * 8));
-	hipEvent_t ev[3];
-	for (hipEvent_t& e : ev) { GENO_DEV(hipEventCreate(&e)); all_events.push_back(e); }
+	HIP_TRY(alloc((void**)&d_glpart, (size_t)std::min<uint32_t>(K, n_windows == 1 ? 1024u : K) * max_blocks * n_gl * 8));
+	HIP_TRY(alloc((void**)&d_gl, gl_out.size() * 8));
+	const hipEvent_t ev[3] = {ses.ev[0], ses.ev[1], ses.ev[2]};
 	uint64_t launches = 0;
 	// one backward step: column c, B_c in `in` (null: last column) -> B_{c-1} in `out`
 	auto backward = [&](uint32_t c, const Buf* in, Buf& out, hipStream_t on = nullptr) -> hipError_t {
@@ -759,11 +717,11 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 	};
 	const double ms_allocated = phase_ms();
 	const auto t_enqueue0 = std::chrono::steady_clock::now();
-	GENO_DEV(hipEventRecord(ev[0], stream));
+	HIP_TRY(hipEventRecord(ev[0], stream));
 	if (max_groups) {
 		hipLaunchKernelGGL(geno_tables, dim3((max_groups * GENO_GROUP + GENO_BLOCK - 1) / GENO_BLOCK, n), dim3(GENO_BLOCK), 0, stream, G, d_tables);
 		++launches;
-		GENO_DEV(hipGetLastError());
+		HIP_TRY(hipGetLastError());
 	}
 	// ---- pass 1: B_{c-1} for c = n-1 .. 1, kept where c - 1 is the last column of a window (nothing to keep with one window)
 	if (n_windows > 1) {
@@ -772,12 +730,12 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		for (uint32_t c = n - 1; c >= 1; --c) {
 			const bool keep = (c - 1) % K == K - 1;
 			Buf& out = keep ? ckpt[(c - 1) / K] : pp[flip];
-			GENO_DEV(backward(c, in, out));
+			HIP_TRY(backward(c, in, out));
 			in = &out;
 			if (!keep) flip ^= 1u;
 		}
 	}
-	GENO_DEV(hipEventRecord(ev[1], stream));
+	HIP_TRY(hipEventRecord(ev[1], stream));
 	auto fwd_args = [&](uint32_t c, const Buf* prev_alpha, const Buf* beta, Buf* out, double* glp) {
 		const bool last = c + 1 == n;
 		const uint32_t fc = last ? 0u : p.f[c], fm = last ? 0u : p.fwd_mask[c];
@@ -806,37 +764,34 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		// ---- everything fits: the backward chain (this stream) and the forward chain of the A columns (a second stream) run side
 		// by side -- they meet only in the likelihood sums, which one batched launch per 1024 columns computes afterwards
 		hipStream_t stream2 = nullptr;
-		GENO_DEV(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-		extra_streams.push_back(stream2);
+		HIP_TRY(ses.add_stream(&stream2));
 		hipEvent_t ev_start, ev_fwd;
-		GENO_DEV(hipEventCreateWithFlags(&ev_start, hipEventDisableTiming));
-		all_events.push_back(ev_start);
-		GENO_DEV(hipEventCreateWithFlags(&ev_fwd, hipEventDisableTiming));
-		all_events.push_back(ev_fwd);
-		GENO_DEV(hipEventRecord(ev_start, stream));
-		GENO_DEV(hipStreamWaitEvent(stream2, ev_start, 0));   // (uploads happened on `stream`)
+		HIP_TRY(ses.sync_event(&ev_start));
+		HIP_TRY(ses.sync_event(&ev_fwd));
+		HIP_TRY(hipEventRecord(ev_start, stream));
+		HIP_TRY(hipStreamWaitEvent(stream2, ev_start, 0));   // (uploads happened on `stream`)
 		// interleave the submissions so that neither hardware queue runs dry
 		uint32_t cb = n - 1, cf = 0;
 		while (cb >= 1 || cf + 1 < n) {
 			if (cb >= 1) {
-				GENO_DEV(backward(cb, cb == n - 1 ? nullptr : &wstore[cb], wstore[cb - 1]));
+				HIP_TRY(backward(cb, cb == n - 1 ? nullptr : &wstore[cb], wstore[cb - 1]));
 				--cb;
 			}
 			if (cf + 1 < n) {
 				astore[cf].blocks = fw_blocks[cf];
-				GENO_DEV(launch_forward(fwd_args(cf, cf ? &astore[cf - 1] : nullptr, nullptr, &astore[cf], nullptr), 1, stream2));
+				HIP_TRY(launch_forward(fwd_args(cf, cf ? &astore[cf - 1] : nullptr, nullptr, &astore[cf], nullptr), 1, stream2));
 				++cf;
 			}
 		}
-		GENO_DEV(hipEventRecord(ev_fwd, stream2));
-		GENO_DEV(hipStreamWaitEvent(stream, ev_fwd, 0));
-		GENO_DEV(hipEventRecord(ev[1], stream));
+		HIP_TRY(hipEventRecord(ev_fwd, stream2));
+		HIP_TRY(hipStreamWaitEvent(stream, ev_fwd, 0));
+		HIP_TRY(hipEventRecord(ev[1], stream));
 		constexpr uint32_t BATCH = 1024;
 		std::vector<GenoFwdArgs> batch(n);
 		for (uint32_t c = 0; c < n; ++c)
 			batch[c] = fwd_args(c, c ? &astore[c - 1] : nullptr, c + 1 < n ? &wstore[c] : nullptr, nullptr, d_glpart + (size_t)(c % BATCH) * max_blocks * n_gl);
 		void* d_batch = nullptr;
-		GENO_DEV(up(&d_batch, batch.data(), batch.size() * sizeof(GenoFwdArgs)));
+		HIP_TRY(up(&d_batch, batch.data(), batch.size() * sizeof(GenoFwdArgs)));
 		for (uint32_t c0 = 0; c0 < n; c0 += BATCH) {
 			const uint32_t cols = std::min(BATCH, n - c0);
 			uint32_t gx = 1;
@@ -848,25 +803,23 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 			else if (T == 4) hipLaunchKernelGGL((geno_forward<4, 2>), grid, block, table_bytes, stream, G, none, bp);
 			else hipLaunchKernelGGL((geno_forward<16, 2>), grid, block, table_bytes, stream, G, none, bp);
 			++launches;
-			GENO_DEV(hipGetLastError());
+			HIP_TRY(hipGetLastError());
 			hipLaunchKernelGGL(geno_finish, dim3(cols), dim3(64), 0, stream, d_glpart, (const uint32_t*)d_fwb, c0, max_blocks, ni, n, d_gl);
 			++launches;
-			GENO_DEV(hipGetLastError());
+			HIP_TRY(hipGetLastError());
 		}
-		GENO_DEV(hipStreamSynchronize(stream));
+		HIP_TRY(hipStreamSynchronize(stream));
 	} else {
 	// ---- windows: the backward columns of window w + 1 are recomputed on a second stream (into the other half of the window
 	// store) while the forward pass runs through window w
 	hipStream_t stream2 = nullptr;
-	GENO_DEV(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-	extra_streams.push_back(stream2);
+	HIP_TRY(ses.add_stream(&stream2));
 	hipEvent_t ev_back[2], ev_fwd[2], ev_pass1;
-	for (hipEvent_t& e : ev_back) { GENO_DEV(hipEventCreateWithFlags(&e, hipEventDisableTiming)); all_events.push_back(e); }
-	for (hipEvent_t& e : ev_fwd) { GENO_DEV(hipEventCreateWithFlags(&e, hipEventDisableTiming)); all_events.push_back(e); }
-	GENO_DEV(hipEventCreateWithFlags(&ev_pass1, hipEventDisableTiming));
-	all_events.push_back(ev_pass1);
-	GENO_DEV(hipEventRecord(ev_pass1, stream));
-	GENO_DEV(hipStreamWaitEvent(stream2, ev_pass1, 0));   // the kept columns (and the uploads) are complete
+	for (hipEvent_t& e : ev_back) HIP_TRY(ses.sync_event(&e));
+	for (hipEvent_t& e : ev_fwd) HIP_TRY(ses.sync_event(&e));
+	HIP_TRY(ses.sync_event(&ev_pass1));
+	HIP_TRY(hipEventRecord(ev_pass1, stream));
+	HIP_TRY(hipStreamWaitEvent(stream2, ev_pass1, 0));   // the kept columns (and the uploads) are complete
 	auto recompute = [&](uint32_t w) -> hipError_t {      // B_c for the columns of window w but its last, on stream2
 		const uint32_t lo = w * K, hi = std::min(n, lo + K);
 		Buf* half = wstore.data() + (size_t)(w & 1u) * K;
@@ -878,57 +831,56 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		}
 		return hipEventRecord(ev_back[w & 1u], stream2);
 	};
-	GENO_DEV(recompute(0));
+	HIP_TRY(recompute(0));
 	uint32_t aflip = 0;
 	const Buf* prev_alpha = nullptr;
 	for (uint32_t w = 0; w < n_windows; ++w) {
 		const uint32_t lo = w * K, hi = std::min(n, lo + K);
 		const Buf* half = wstore.data() + (size_t)(w & 1u) * K;
 		const Buf* last_beta = hi == n ? nullptr : &ckpt[w];
-		GENO_DEV(hipStreamWaitEvent(stream, ev_back[w & 1u], 0));
+		HIP_TRY(hipStreamWaitEvent(stream, ev_back[w & 1u], 0));
 		if (w + 1 < n_windows) {
-			if (w >= 1) GENO_DEV(hipStreamWaitEvent(stream2, ev_fwd[(w - 1) & 1u], 0));   // the forward pass of window w - 1 is done with that half
-			GENO_DEV(recompute(w + 1));
+			if (w >= 1) HIP_TRY(hipStreamWaitEvent(stream2, ev_fwd[(w - 1) & 1u], 0));   // the forward pass of window w - 1 is done with that half
+			HIP_TRY(recompute(w + 1));
 		}
 		for (uint32_t c = lo; c < hi; ++c) {
 			const Buf* beta = c == hi - 1 ? last_beta : &half[c - lo];
 			Buf& out = alpha[aflip];
 			out.blocks = fw_blocks[c];
-			GENO_DEV(launch_forward(fwd_args(c, prev_alpha, beta, &out, d_glpart + (size_t)(c - lo) * max_blocks * n_gl), 0, stream));
+			HIP_TRY(launch_forward(fwd_args(c, prev_alpha, beta, &out, d_glpart + (size_t)(c - lo) * max_blocks * n_gl), 0, stream));
 			prev_alpha = &out;
 			aflip ^= 1u;
 		}
 		hipLaunchKernelGGL(geno_finish, dim3(hi - lo), dim3(64), 0, stream, d_glpart, (const uint32_t*)d_fwb, lo, max_blocks, ni, n, d_gl);
 		++launches;
-		GENO_DEV(hipGetLastError());
-		GENO_DEV(hipEventRecord(ev_fwd[w & 1u], stream));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ev_fwd[w & 1u], stream));
 	}
-	GENO_DEV(hipStreamSynchronize(stream));
-	GENO_DEV(hipStreamSynchronize(stream2));
+	HIP_TRY(hipStreamSynchronize(stream));
+	HIP_TRY(hipStreamSynchronize(stream2));
 	}
-	GENO_DEV(hipEventRecord(ev[2], stream));
+	HIP_TRY(hipEventRecord(ev[2], stream));
 	if (getenv("WHAMD_DEBUG_TIMING")) {
 		const double enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
-		GENO_DEV(hipStreamSynchronize(stream));
+		HIP_TRY(hipStreamSynchronize(stream));
 		const double all = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
 		fprintf(stderr, "[whamd timing] genotype: %llu launches submitted in %.1f ms (host), stream drained after %.1f ms\n", (unsigned long long)launches, enq, all);
 	}
-	GENO_DEV(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, stream));
-	GENO_DEV(hipStreamSynchronize(stream));
+	HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
 	float ms01 = 0, ms12 = 0, ms02 = 0;
-	GENO_DEV(hipEventElapsedTime(&ms01, ev[0], ev[1]));
-	GENO_DEV(hipEventElapsedTime(&ms12, ev[1], ev[2]));
-	GENO_DEV(hipEventElapsedTime(&ms02, ev[0], ev[2]));
+	HIP_TRY(hipEventElapsedTime(&ms01, ev[0], ev[1]));
+	HIP_TRY(hipEventElapsedTime(&ms12, ev[1], ev[2]));
+	HIP_TRY(hipEventElapsedTime(&ms02, ev[0], ev[2]));
 	st.backward_ms = ms01;
 	st.forward_ms = ms12;
 	st.total_ms = ms02;
 	st.launches = launches;
 	const double ms_done = phase_ms();
-	cleanup();
+	ses.close();   // (here, not at the return: the line below times it)
 	if (getenv("WHAMD_DEBUG_TIMING"))
 		fprintf(stderr, "[whamd timing] genotype phases (wall): allocations + uploads %.1f ms, submission + device %.1f ms, freeing %.1f ms\n",
 		        ms_allocated, ms_done - ms_allocated, phase_ms() - ms_done);
-#undef GENO_DEV
 	return WHAMD_OK;
 }
 

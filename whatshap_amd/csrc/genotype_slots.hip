@@ -27,7 +27,7 @@
 #include <cstring>
 
 #include "debug_build.h"
-#include "device_pool.h"
+#include "device_runtime.h"
 #include "genotype.h"
 #include "slots.h"
 
@@ -587,19 +587,6 @@ __global__ __launch_bounds__(256) void geno_slot_finish(GsDev G, const double* _
 	}
 }
 
-struct Cleanup {
-	std::vector<void*> allocations;
-	std::vector<hipStream_t> streams;
-	std::vector<hipEvent_t> events;
-	int slab_device = -1;
-	~Cleanup() {
-		if (slab_device >= 0) genotype_slab_release(slab_device);
-		for (hipEvent_t e : events) (void)hipEventDestroy(e);
-		for (hipStream_t s : streams) (void)hipStreamDestroy(s);
-		for (void* a : allocations) (void)hipFree(a);
-	}
-};
-
 }  // namespace
 
 // Returns WHAMD_OK with `used` = false when the table is not eligible (the caller takes the per-column kernels): a pedigree the
@@ -615,8 +602,7 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	if (!plan_forward_slots(p, l_pref > 0 ? -l_pref : 0, 0, plan, 0, /*genotype_mode=*/true)) return WHAMD_OK;
 	for (const Step& s : plan.steps) if (s.kind != 2) return WHAMD_OK;   // a column no run can take
 	const uint32_t tb = T == 1 ? 0u : (T == 4 ? 2u : 4u), E = 2u * p.P, A = m.A;
-#define GS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { msg = std::string(#expr) + " failed: " + hipGetErrorString(e_); return WHAMD_ERR_DEVICE; } } while (0)
-	GS_TRY(hipSetDevice(device));
+	HIP_TRY(hipSetDevice(device));
 	const size_t n_runs = plan.runs.size();
 	// ---- host descriptors
 	std::vector<GsCol> cols(n);
@@ -690,10 +676,10 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		}
 	}
 	size_t free_b = 0, total_b = 0;
-	GS_TRY(hipMemGetInfo(&free_b, &total_b));
+	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	if (free_b < total_b / 2) {   // a phasing table of this process may have left its arena in the cache (dp_device.hip)
-		dptable_release_arena_cache();
-		GS_TRY(hipMemGetInfo(&free_b, &total_b));
+		arena_release();
+		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	}
 	free_b += genotype_slab_idle_bytes(device);   // the column store kept from an earlier call is available to this one
 	constexpr uint32_t BATCH = 512;
@@ -746,21 +732,14 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	st.transmissions = T;
 	st.window = n_windows > 1 ? windows[0].c1 - windows[0].c0 : n;
 	for (uint32_t c = 0; c < n; ++c) { st.n_cells += 1ull << p.k[c]; st.max_coverage = std::max<uint32_t>(st.max_coverage, p.k[c]); }
-	Cleanup keep;
-	hipStream_t sf = nullptr, sb = nullptr, sc = nullptr;
-	GS_TRY(hipStreamCreateWithFlags(&sf, hipStreamNonBlocking)); keep.streams.push_back(sf);
-	GS_TRY(hipStreamCreateWithFlags(&sb, hipStreamNonBlocking)); keep.streams.push_back(sb);
-	if (n_windows > 1 || debug_env("WHAMD_GENO_PIECES")) { GS_TRY(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking)); keep.streams.push_back(sc); }   // (likelihood sums beside the chains)
-	auto alloc = [&](void** dptr, size_t bytes) -> hipError_t {
-		hipError_t e = hipMalloc(dptr, std::max<size_t>(bytes, 16));
-		if (e != hipSuccess) {   // idle blocks of the phasing / heuristic pool may hold the memory: give them back, try once more
-			(void)hipGetLastError();
-			devpool_release();
-			e = hipMalloc(dptr, std::max<size_t>(bytes, 16));
-		}
-		if (e == hipSuccess) keep.allocations.push_back(*dptr);
-		return e;
-	};
+	GenotypeSlabHold slab;
+	Session keep;   // its own stream carries the forward chain; four events for the times
+	const whamd_status_t opened = keep.open(device, 4, msg);
+	if (opened != WHAMD_OK) return opened;
+	hipStream_t sf = keep.stream, sb = nullptr, sc = nullptr;
+	HIP_TRY(keep.add_stream(&sb));
+	if (n_windows > 1 || debug_env("WHAMD_GENO_PIECES")) HIP_TRY(keep.add_stream(&sc));   // (likelihood sums beside the chains)
+	auto alloc = [&](void** dptr, size_t bytes) { return keep.fresh_block(dptr, bytes); };
 	auto up = [&](void** dptr, const void* src, size_t bytes) -> hipError_t {
 		hipError_t e = alloc(dptr, bytes);
 		if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, sf);
@@ -772,44 +751,43 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	GsDev G{};
 	void *d_cols, *d_rows, *d_prior, *d_rho, *d_gidx, *d_h2p, *d_runs, *d_ccols, *d_tab, *d_fs, *d_bs, *d_part, *d_glpart, *d_gl;
 	double* d_x[4];
-	GS_TRY(up(&d_cols, cols.data(), cols.size() * sizeof(GsCol)));
-	GS_TRY(up(&d_rows, rows.data(), rows.size() * sizeof(GsRow)));
-	GS_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
-	GS_TRY(up(&d_rho, rho.data(), rho.size() * 8));
-	GS_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
-	GS_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
-	GS_TRY(up(&d_runs, runs.data(), runs.size() * sizeof(GsRun)));
-	GS_TRY(up(&d_ccols, ccols.data(), ccols.size() * sizeof(GsCombineCol)));
-	GS_TRY(alloc(&d_tab, (size_t)tab_words * 8));
+	HIP_TRY(up(&d_cols, cols.data(), cols.size() * sizeof(GsCol)));
+	HIP_TRY(up(&d_rows, rows.data(), rows.size() * sizeof(GsRow)));
+	HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
+	HIP_TRY(up(&d_rho, rho.data(), rho.size() * 8));
+	HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
+	HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
+	HIP_TRY(up(&d_runs, runs.data(), runs.size() * sizeof(GsRun)));
+	HIP_TRY(up(&d_ccols, ccols.data(), ccols.size() * sizeof(GsCombineCol)));
+	HIP_TRY(alloc(&d_tab, (size_t)tab_words * 8));
 	d_fs = genotype_slab_acquire(device, 2 * n_sets * (size_t)window_words * 8);   // the column stores in the block kept between calls
-	if (d_fs) keep.slab_device = device;
-	else GS_TRY(alloc(&d_fs, 2 * n_sets * (size_t)window_words * 8));
+	if (d_fs) slab.device = device;
+	else HIP_TRY(alloc(&d_fs, 2 * n_sets * (size_t)window_words * 8));
 	d_bs = (double*)d_fs + n_sets * window_words;
 	void* d_check = nullptr;   // the forward exchange column entering every window but the first
 	const size_t check_bytes = ((size_t)1 << max_f) * T * 8;
-	if (n_windows > 1) GS_TRY(alloc(&d_check, (n_windows - 1) * check_bytes));
-	GS_TRY(alloc(&d_part, (size_t)n_partials * 8));
-	GS_TRY(alloc(&d_glpart, (size_t)BATCH * max_blocks * T * A * 8));
-	GS_TRY(alloc(&d_gl, gl_out.size() * 8));
-	for (double*& x : d_x) GS_TRY(alloc((void**)&x, ((size_t)1 << max_f) * T * 8));
+	if (n_windows > 1) HIP_TRY(alloc(&d_check, (n_windows - 1) * check_bytes));
+	HIP_TRY(alloc(&d_part, (size_t)n_partials * 8));
+	HIP_TRY(alloc(&d_glpart, (size_t)BATCH * max_blocks * T * A * 8));
+	HIP_TRY(alloc(&d_gl, gl_out.size() * 8));
+	for (double*& x : d_x) HIP_TRY(alloc((void**)&x, ((size_t)1 << max_f) * T * 8));
 	G.cols = (const GsCol*)d_cols; G.rows = (const GsRow*)d_rows; G.prior = (const double*)d_prior; G.rho = (const double*)d_rho;
 	G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p; G.tab = (double*)d_tab; G.fstore = (double*)d_fs; G.bstore = (double*)d_bs;
 	G.dbg = nullptr;
 #ifdef WHAMD_GENO_STAMPS
-	{ void* d_dbg = nullptr; GS_TRY(alloc(&d_dbg, 128)); GS_TRY(hipMemset(d_dbg, 0, 128)); G.dbg = (unsigned long long*)d_dbg; }
+	{ void* d_dbg = nullptr; HIP_TRY(alloc(&d_dbg, 128)); HIP_TRY(hipMemset(d_dbg, 0, 128)); G.dbg = (unsigned long long*)d_dbg; }
 #endif
 	G.partials = (double*)d_part; G.T = T; G.A = A; G.P = p.P; G.n_ind = ni; G.n_cols = n;
-	hipEvent_t ev[4];
-	for (hipEvent_t& e : ev) { GS_TRY(hipEventCreate(&e)); keep.events.push_back(e); }
+	const hipEvent_t ev[4] = {keep.ev[0], keep.ev[1], keep.ev[2], keep.ev[3]};
 	using RunFn = void (*)(GsDev, GsRun, const double*, double*);
 	RunFn fwd = nullptr, bwd = nullptr;
 	if (tb == 0) { fwd = geno_slot_run<0, 2, 0>; bwd = geno_slot_run<0, 2, 1>; }
 	else if (tb == 2) { fwd = geno_slot_run<2, 4, 0>; bwd = geno_slot_run<2, 4, 1>; }
 	else { fwd = geno_slot_run<4, 4, 0>; bwd = geno_slot_run<4, 4, 1>; }
-	GS_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-	GS_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	uint64_t launches = 0;
-	GS_TRY(hipEventRecord(ev[0], sf));
+	HIP_TRY(hipEventRecord(ev[0], sf));
 	{
 		uint32_t most = 0;
 		for (const GsRun& r : runs) most = std::max<uint32_t>(most, ((r.ncols * T) << r.g) + ((r.ncols * T) << r.lw) + r.ncols * 64u);
@@ -819,10 +797,10 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 			hipLaunchKernelGGL(geno_slot_tables, dim3(bx, ny), dim3(256), 0, sf, G, (const GsRun*)d_runs + r0);
 			++launches;
 		}
-		GS_TRY(hipGetLastError());
+		HIP_TRY(hipGetLastError());
 	}
-	GS_TRY(hipEventRecord(ev[1], sf));
-	GS_TRY(hipStreamWaitEvent(sb, ev[1], 0));   // uploads and tables are complete
+	HIP_TRY(hipEventRecord(ev[1], sf));
+	HIP_TRY(hipStreamWaitEvent(sb, ev[1], 0));   // uploads and tables are complete
 	auto lds_of = [&](const GsRun& r) {
 		const size_t waves = r.threads >> 6;
 		return ((size_t)2 * r.threads + waves * r.ncols * T * E + (size_t)r.ncols * T * A + ((r.ncols + 1) & ~1u) + 16) * 8 + (size_t)r.ncols * sizeof(GsCol);
@@ -867,22 +845,22 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		auto piece_lo = [&](size_t k) { return n_runs * k / n_pieces; };
 		std::vector<hipEvent_t> pf(n_pieces), pb(n_pieces);
 		for (size_t k = 0; k < n_pieces; ++k)
-			for (hipEvent_t* e : {&pf[k], &pb[k]}) { GS_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming)); keep.events.push_back(*e); }
+			for (hipEvent_t* e : {&pf[k], &pb[k]}) HIP_TRY(keep.sync_event(e));
 		size_t rf = 0, rb = n_runs, kf = 0, kb = n_pieces;
 		while (rf < n_runs || rb > 0) {
 			if (rf < n_runs) {
 				launch_fwd(rf++, g);
-				if (rf == piece_lo(kf + 1)) { GS_TRY(hipEventRecord(pf[kf], sf)); ++kf; }
+				if (rf == piece_lo(kf + 1)) { HIP_TRY(hipEventRecord(pf[kf], sf)); ++kf; }
 			}
 			if (rb > 0) {
 				launch_bwd(--rb, g);
-				if (rb == piece_lo(kb - 1)) { --kb; GS_TRY(hipEventRecord(pb[kb], sb)); }
+				if (rb == piece_lo(kb - 1)) { --kb; HIP_TRY(hipEventRecord(pb[kb], sb)); }
 			}
 		}
-		GS_TRY(hipGetLastError());
-		GS_TRY(hipEventRecord(ev[2], sb));
-		GS_TRY(hipStreamWaitEvent(sf, ev[2], 0));
-		GS_TRY(hipEventRecord(ev[2], sf));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ev[2], sb));
+		HIP_TRY(hipStreamWaitEvent(sf, ev[2], 0));
+		HIP_TRY(hipEventRecord(ev[2], sf));
 		// pieces in the order both chains have passed them: from the middle outwards
 		std::vector<size_t> order;
 		for (size_t d = 0; order.size() < n_pieces; ++d) {
@@ -895,8 +873,8 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		const hipStream_t cs = third_stream ? sc : sf;
 		for (size_t k : order) {
 			if (third_stream) {
-				GS_TRY(hipStreamWaitEvent(sc, pf[k], 0));
-				GS_TRY(hipStreamWaitEvent(sc, pb[k], 0));
+				HIP_TRY(hipStreamWaitEvent(sc, pf[k], 0));
+				HIP_TRY(hipStreamWaitEvent(sc, pb[k], 0));
 			}
 			const size_t r0 = piece_lo(k), r1 = piece_lo(k + 1);
 			GsWindow piece{r0, r1, 0, plan.runs[r0].c0, plan.runs[r1 - 1].c0 + plan.runs[r1 - 1].ncols};
@@ -904,9 +882,9 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		}
 		if (third_stream) {
 			hipEvent_t done = nullptr;
-			GS_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming)); keep.events.push_back(done);
-			GS_TRY(hipEventRecord(done, sc));
-			GS_TRY(hipStreamWaitEvent(sf, done, 0));
+			HIP_TRY(keep.sync_event(&done));
+			HIP_TRY(hipEventRecord(done, sc));
+			HIP_TRY(hipStreamWaitEvent(sf, done, 0));
 		}
 	} else {
 		// pass 1: the whole forward chain; the exchange column entering every window is kept.  Every window writes its columns into its set and
@@ -915,48 +893,48 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		const size_t last = n_windows - 1;
 		std::vector<hipEvent_t> ef(n_windows), eb(n_windows), ec(n_windows);
 		for (size_t w = 0; w < n_windows; ++w)
-			for (hipEvent_t* e : {&ef[w], &eb[w], &ec[w]}) { GS_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming)); keep.events.push_back(*e); }
+			for (hipEvent_t* e : {&ef[w], &eb[w], &ec[w]}) HIP_TRY(keep.sync_event(e));
 		for (size_t w = 0; w < n_windows; ++w) {
 			const GsWindow& wdw = windows[w];
-			if (w > 0) GS_TRY(hipMemcpyAsync((char*)d_check + (w - 1) * check_bytes, d_x[wdw.r0 & 1], check_bytes, hipMemcpyDeviceToDevice, sf));
+			if (w > 0) HIP_TRY(hipMemcpyAsync((char*)d_check + (w - 1) * check_bytes, d_x[wdw.r0 & 1], check_bytes, hipMemcpyDeviceToDevice, sf));
 			const GsDev g = with_stores(w % 2);
 			for (size_t ri = wdw.r0; ri < wdw.r1; ++ri) launch_fwd(ri, g);
 		}
-		GS_TRY(hipGetLastError());
-		GS_TRY(hipEventRecord(ef[last], sf));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ef[last], sf));
 		// newest window first: (recompute the forward columns,) backward chain, likelihoods -- forward of window w - 1 beside backward / combine of w
 		for (size_t w = n_windows; w-- > 0;) {
 			const GsWindow& wdw = windows[w];
 			const GsDev g = with_stores(w % 2);
 			if (w != last) {
-				if (w + 2 < n_windows) GS_TRY(hipStreamWaitEvent(sf, ec[w + 2], 0));   // the stores of this set are free again
-				if (w > 0) GS_TRY(hipMemcpyAsync(d_x[wdw.r0 & 1], (char*)d_check + (w - 1) * check_bytes, check_bytes, hipMemcpyDeviceToDevice, sf));
+				if (w + 2 < n_windows) HIP_TRY(hipStreamWaitEvent(sf, ec[w + 2], 0));   // the stores of this set are free again
+				if (w > 0) HIP_TRY(hipMemcpyAsync(d_x[wdw.r0 & 1], (char*)d_check + (w - 1) * check_bytes, check_bytes, hipMemcpyDeviceToDevice, sf));
 				for (size_t ri = wdw.r0; ri < wdw.r1; ++ri) launch_fwd(ri, g);
-				GS_TRY(hipEventRecord(ef[w], sf));
+				HIP_TRY(hipEventRecord(ef[w], sf));
 			}
-			GS_TRY(hipStreamWaitEvent(sb, ef[w], 0));
-			if (w + 2 < n_windows) GS_TRY(hipStreamWaitEvent(sb, ec[w + 2], 0));
+			HIP_TRY(hipStreamWaitEvent(sb, ef[w], 0));
+			if (w + 2 < n_windows) HIP_TRY(hipStreamWaitEvent(sb, ec[w + 2], 0));
 			for (size_t ri = wdw.r1; ri-- > wdw.r0;) launch_bwd(ri, g);
-			GS_TRY(hipEventRecord(eb[w], sb));
-			GS_TRY(hipStreamWaitEvent(sc, eb[w], 0));
+			HIP_TRY(hipEventRecord(eb[w], sb));
+			HIP_TRY(hipStreamWaitEvent(sc, eb[w], 0));
 			launch_combine(wdw, g, sc);
-			GS_TRY(hipEventRecord(ec[w], sc));
-			GS_TRY(hipGetLastError());
+			HIP_TRY(hipEventRecord(ec[w], sc));
+			HIP_TRY(hipGetLastError());
 		}
-		GS_TRY(hipEventRecord(ev[2], sb));
-		GS_TRY(hipStreamWaitEvent(sf, ec[0], 0));
-		GS_TRY(hipStreamWaitEvent(sf, ec[n_windows > 1 ? 1 : 0], 0));
+		HIP_TRY(hipEventRecord(ev[2], sb));
+		HIP_TRY(hipStreamWaitEvent(sf, ec[0], 0));
+		HIP_TRY(hipStreamWaitEvent(sf, ec[n_windows > 1 ? 1 : 0], 0));
 	}
-	GS_TRY(hipGetLastError());
-	GS_TRY(hipEventRecord(ev[3], sf));
-	GS_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, sf));
-	GS_TRY(hipStreamSynchronize(sf));
-	GS_TRY(hipStreamSynchronize(sb));
-	if (sc) GS_TRY(hipStreamSynchronize(sc));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(ev[3], sf));
+	HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, sf));
+	HIP_TRY(hipStreamSynchronize(sf));
+	HIP_TRY(hipStreamSynchronize(sb));
+	if (sc) HIP_TRY(hipStreamSynchronize(sc));
 #ifdef WHAMD_GENO_STAMPS
 	{
 		unsigned long long d[16];
-		GS_TRY(hipMemcpy(d, G.dbg, sizeof d, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(d, G.dbg, sizeof d, hipMemcpyDeviceToHost));
 		for (int dir = 0; dir < 2; ++dir) {
 			const double runs = (double)std::max<unsigned long long>(d[dir * 8 + 6], 1);
 			fprintf(stderr, "[whamd geno stamps] %s: %llu runs, %.1f columns each; cycles since kernel start (wave 0 / workgroup 0): staged %.0f, entered + reduced %.0f, loop done %.0f, exit %.0f\n",
@@ -965,9 +943,9 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	}
 #endif
 	float t_tab = 0, t_chain = 0, t_all = 0;
-	GS_TRY(hipEventElapsedTime(&t_tab, ev[0], ev[1]));
-	GS_TRY(hipEventElapsedTime(&t_chain, ev[1], ev[2]));
-	GS_TRY(hipEventElapsedTime(&t_all, ev[0], ev[3]));
+	HIP_TRY(hipEventElapsedTime(&t_tab, ev[0], ev[1]));
+	HIP_TRY(hipEventElapsedTime(&t_chain, ev[1], ev[2]));
+	HIP_TRY(hipEventElapsedTime(&t_all, ev[0], ev[3]));
 	st.backward_ms = t_chain;              // the two chains side by side
 	st.forward_ms = t_all - t_chain;       // tables + combine
 	st.total_ms = t_all;
@@ -976,7 +954,6 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	if (getenv("WHAMD_DEBUG_TIMING"))
 		fprintf(stderr, "[whamd timing] genotype slot runs: %zu runs (%.1f columns per run), %zu window(s), tables %.2f ms, chains %.2f ms, combine %.2f ms; tables %.1f MB, stores %zu x %.1f MB\n",
 		        n_runs, (double)n / n_runs, n_windows, t_tab, t_chain, t_all - t_chain - t_tab, tab_words * 8e-6, 2 * n_sets, window_words * 8e-6);
-#undef GS_TRY
 	return WHAMD_OK;
 }
 

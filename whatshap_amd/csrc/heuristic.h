@@ -93,8 +93,6 @@ public:
 private:
 	Impl* impl_;
 };
-// gives the device buffers kept between solves back to the driver (whamd_release_caches)
-void heuristic_release_cache();
 whamd_status_t heuristic_solve_host(const HeurPlan& plan, HeurResult& out, std::string& msg);
 // allele votes of the final bipartition and the optimal phasing per column (host, src/pedmecheuristic.cpp:361-406)
 void heuristic_finish(const HeurPlan& plan, HeurResult& out);

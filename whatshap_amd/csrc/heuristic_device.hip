@@ -16,7 +16,7 @@
 #include <utility>
 #include <vector>
 
-#include "device_pool.h"
+#include "device_runtime.h"
 #include "heuristic.h"
 
 #define HEUR_FN __device__
@@ -85,17 +85,12 @@ __global__ __launch_bounds__(MAXT) void heuristic_kernel_many(const HeurDev* __r
 
 }  // namespace
 
-void heuristic_release_cache() { devpool_release(); }
-
 // Several tables in flight: everything between "plans built" and "bipartitions on the host".
 struct HeurBatch::Impl {
-	int device = 0;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	Session s;   // the stream, two events, every block but the jobs' arenas
 	struct Job {
 		const HeurPlan* plan = nullptr;
 		HeurDev D{};
-		std::vector<std::pair<void*, size_t>> blocks;   // pool blocks (pointer, class size)
 		void* arena = nullptr; size_t arena_bytes = 0;
 		unsigned long long arena_words = 0;
 		uint64_t cap = 0;
@@ -104,26 +99,17 @@ struct HeurBatch::Impl {
 		unsigned long long stats[32] = {0};
 	};
 	std::vector<Job> jobs;
-	HeurDev* d_tables = nullptr; size_t d_tables_bytes = 0;
+	HeurDev* d_tables = nullptr;
 	bool launched = false;
-	~Impl() {
-		(void)hipSetDevice(device);
-		if (stream) (void)hipStreamSynchronize(stream);
-		for (Job& j : jobs) {
-			for (auto& b : j.blocks) devpool_give(device, b.first, b.second);
-			devpool_give(device, j.arena, j.arena_bytes);
-		}
-		devpool_give(device, d_tables, d_tables_bytes);
-		if (ev0) (void)hipEventDestroy(ev0);
-		if (ev1) (void)hipEventDestroy(ev1);
-		if (stream) (void)hipStreamDestroy(stream);
+	~Impl() {   // (a job's arena is given back and taken again between launches: the job's, not the session's)
+		if (s.device >= 0) (void)hipSetDevice(s.device);
+		if (s.stream) (void)hipStreamSynchronize(s.stream);
+		for (Job& j : jobs) devpool_give(s.device, j.arena, j.arena_bytes);
 	}
 };
 
 HeurBatch::HeurBatch() : impl_(new Impl()) {}
 HeurBatch::~HeurBatch() { delete impl_; }
-
-#define HEUR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { msg = std::string(#expr) + " failed: " + hipGetErrorString(e_); return WHAMD_ERR_DEVICE; } } while (0)
 
 // Launches every job that is not done yet: one launch per workgroup size (the kernel is compiled for 512 and for 1024 threads).
 static whamd_status_t heur_launch_pending(HeurBatch::Impl& m, std::string& msg) {
@@ -137,44 +123,31 @@ static whamd_status_t heur_launch_pending(HeurBatch::Impl& m, std::string& msg) 
 			if (!m.jobs[i].done && m.jobs[i].block == block) { host.push_back(m.jobs[i].D); which.push_back(i); }
 		if (host.empty()) continue;
 		if (host.size() == 1) {   // a single table: descriptor by value (kernel arguments)
-			if (block <= 512u) hipLaunchKernelGGL(heuristic_kernel<512>, dim3(1), dim3(block), 0, m.stream, host[0]);
-			else hipLaunchKernelGGL(heuristic_kernel<1024>, dim3(1), dim3(block), 0, m.stream, host[0]);
+			if (block <= 512u) hipLaunchKernelGGL(heuristic_kernel<512>, dim3(1), dim3(block), 0, m.s.stream, host[0]);
+			else hipLaunchKernelGGL(heuristic_kernel<1024>, dim3(1), dim3(block), 0, m.s.stream, host[0]);
 			continue;
 		}
 		HeurDev* dst = m.d_tables + written;
 		written += host.size();
-		HEUR_TRY(hipMemcpyAsync(dst, host.data(), host.size() * sizeof(HeurDev), hipMemcpyHostToDevice, m.stream));
-		HEUR_TRY(hipStreamSynchronize(m.stream));   // (`host` is pageable and dies with this scope)
-		if (block <= 512u) hipLaunchKernelGGL(heuristic_kernel_many<512>, dim3((uint32_t)host.size()), dim3(block), 0, m.stream, dst);
-		else hipLaunchKernelGGL(heuristic_kernel_many<1024>, dim3((uint32_t)host.size()), dim3(block), 0, m.stream, dst);
+		HIP_TRY(hipMemcpyAsync(dst, host.data(), host.size() * sizeof(HeurDev), hipMemcpyHostToDevice, m.s.stream));
+		HIP_TRY(hipStreamSynchronize(m.s.stream));   // (`host` is pageable and dies with this scope)
+		if (block <= 512u) hipLaunchKernelGGL(heuristic_kernel_many<512>, dim3((uint32_t)host.size()), dim3(block), 0, m.s.stream, dst);
+		else hipLaunchKernelGGL(heuristic_kernel_many<1024>, dim3((uint32_t)host.size()), dim3(block), 0, m.s.stream, dst);
 	}
-	HEUR_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	return WHAMD_OK;
 }
 
 whamd_status_t HeurBatch::enqueue(const HeurPlan* const* plans, size_t n, int device, std::string& msg) {
 	Impl& m = *impl_;
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-		msg = "no HIP device visible: the whatshap_amd device path needs an MI355X (gfx950); there is no CPU fallback";
-		return WHAMD_ERR_DEVICE;
-	}
-	if (device < 0 || device >= ndev) { msg = "device index " + std::to_string(device) + " out of range (" + std::to_string(ndev) + " visible)"; return WHAMD_ERR_DEVICE; }
-	m.device = device;
-	HEUR_TRY(hipSetDevice(device));
-	HEUR_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-	HEUR_TRY(hipEventCreate(&m.ev0));
-	HEUR_TRY(hipEventCreate(&m.ev1));
+	const whamd_status_t opened = m.s.open(device, 2, msg);
+	if (opened != WHAMD_OK) return opened;
 	size_t free_b = 0, total_b = 0;
-	HEUR_TRY(hipMemGetInfo(&free_b, &total_b));
+	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	const size_t budget = free_b / 3 / std::max<size_t>(n, 1);   // what one table's pools may take
 	m.jobs.resize(n);
-	{
-		size_t got = 0;
-		void* ptr = nullptr;
-		HEUR_TRY(devpool_take(device, (n + 1) * sizeof(HeurDev), &ptr, &got));
-		m.d_tables = (HeurDev*)ptr; m.d_tables_bytes = got;
-	}
+	const whamd_status_t tables = m.s.device_block((n + 1) * sizeof(HeurDev), (void**)&m.d_tables, msg);
+	if (tables != WHAMD_OK) return tables;
 	for (size_t ji = 0; ji < n; ++ji) {
 		const HeurPlan& pl = *plans[ji];
 		Impl::Job& job = m.jobs[ji];
@@ -196,7 +169,7 @@ whamd_status_t HeurBatch::enqueue(const HeurPlan* const* plans, size_t n, int de
 		auto alloc = [&](void** dptr, size_t bytes) -> hipError_t {
 			size_t got = 0;
 			hipError_t e = devpool_take(device, std::max<size_t>(bytes, 16), dptr, &got);
-			if (e == hipSuccess) job.blocks.emplace_back(*dptr, got);
+			if (e == hipSuccess) m.s.dev.emplace_back(*dptr, got);
 			return e;
 		};
 		// the small read-only arrays of the plan travel as ONE block (one allocation, one copy)
@@ -217,31 +190,31 @@ whamd_status_t HeurBatch::enqueue(const HeurPlan* const* plans, size_t n, int de
 		std::vector<char> staged(std::max<size_t>(total, 16), 0);
 		for (const Piece& pc : pieces) if (pc.bytes) std::memcpy(staged.data() + pc.off, pc.src, pc.bytes);
 		char* base = nullptr;
-		HEUR_TRY(alloc((void**)&base, staged.size()));
-		HEUR_TRY(hipMemcpyAsync(base, staged.data(), staged.size(), hipMemcpyHostToDevice, m.stream));
-		HEUR_TRY(hipStreamSynchronize(m.stream));   // (`staged` is pageable)
+		HIP_TRY(alloc((void**)&base, staged.size()));
+		HIP_TRY(hipMemcpyAsync(base, staged.data(), staged.size(), hipMemcpyHostToDevice, m.s.stream));
+		HIP_TRY(hipStreamSynchronize(m.s.stream));   // (`staged` is pageable)
 		D.trios = (const uint32_t*)(base + o_trios); D.recomb = (const float*)(base + o_recomb); D.mutation = (const float*)(base + o_mut);
 		D.genotype = (const int8_t*)(base + o_geno); D.start_index = (const uint32_t*)(base + o_start); D.col = (const HeurColMeta*)(base + o_col);
 		D.kept = (const uint32_t*)(base + o_kept); D.reads = (const HeurReadMeta*)(base + o_reads); D.new_balance = (const float*)(base + o_bal);
 		D.new_target = (const int32_t*)(base + o_target);
 		D.cap = (uint32_t)cap; D.tsz = tsz;
-		for (int q = 0; q < 2; ++q) HEUR_TRY(alloc((void**)&D.pool_words[q], heur_pool_words(D.cap, pl.nw, pl.n_samples, pl.w_max) * 4));
-		HEUR_TRY(alloc((void**)&D.scratch, heur_scratch_words(D.cap, pl.nw) * 4));
-		HEUR_TRY(alloc((void**)&D.hash, heur_hash_words(tsz) * 4));
+		for (int q = 0; q < 2; ++q) HIP_TRY(alloc((void**)&D.pool_words[q], heur_pool_words(D.cap, pl.nw, pl.n_samples, pl.w_max) * 4));
+		HIP_TRY(alloc((void**)&D.scratch, heur_scratch_words(D.cap, pl.nw) * 4));
+		HIP_TRY(alloc((void**)&D.hash, heur_hash_words(tsz) * 4));
 		// col_off | col_count | opt_trans | opt_bipart | stats: one block
 		const size_t b_off = 0, b_count = (size_t)pl.n_cols * 8, b_trans = b_count + (((size_t)pl.n_cols * 4 + 7) & ~(size_t)7), b_bip = b_trans + (((size_t)pl.n_cols * 4 + 7) & ~(size_t)7);
 		const size_t b_stats = b_bip + ((std::max<size_t>(pl.n_reads, 1) + 255) & ~(size_t)255), b_total = b_stats + 256;
 		char* res = nullptr;
-		HEUR_TRY(alloc((void**)&res, b_total));
+		HIP_TRY(alloc((void**)&res, b_total));
 		D.col_off = (unsigned long long*)(res + b_off); D.col_count = (uint32_t*)(res + b_count); D.opt_trans = (uint32_t*)(res + b_trans);
 		D.opt_bipart = (uint8_t*)(res + b_bip); D.stats = (unsigned long long*)(res + b_stats);
-		HEUR_TRY(hipMemsetAsync(res + b_bip, 0, b_total - b_bip, m.stream));
+		HIP_TRY(hipMemsetAsync(res + b_bip, 0, b_total - b_bip, m.s.stream));
 		// the backtrace arena: sized for 4 x row_limit x 4^trios solutions per column first, regrown on overflow while memory allows
 		unsigned long long stride_sum = 0;
 		for (uint32_t p = 0; p < pl.n_cols; ++p) stride_sum += 2 + ((pl.n_new[p] + 31) >> 5);
 		job.arena_words = stride_sum * std::min<uint64_t>(cap, (uint64_t)pl.row_limit * 4u * T) + 1024;
 		if (job.arena_words * 4 > free_b / 2 / std::max<size_t>(n, 1)) { msg = "PedMecHeuristic: the backtrace records do not fit in device memory"; return WHAMD_ERR_UNSUPPORTED; }
-		HEUR_TRY(devpool_take(device, job.arena_words * 4, &job.arena, &job.arena_bytes));
+		HIP_TRY(devpool_take(device, job.arena_words * 4, &job.arena, &job.arena_bytes));
 		D.arena = (uint32_t*)job.arena; D.arena_words = job.arena_words;
 		// as many threads as the beam usually has solutions (a barrier costs with the number of waves): 2 x row_limit, 128 .. 1024
 		uint32_t block = 128;
@@ -249,10 +222,10 @@ whamd_status_t HeurBatch::enqueue(const HeurPlan* const* plans, size_t n, int de
 		if (const char* e = getenv("WHAMD_HEURISTIC_THREADS")) { block = 128; const uint32_t want = (uint32_t)std::max(64, std::min(1024, atoi(e))); while (block < want) block <<= 1; }
 		job.block = block;
 	}
-	HEUR_TRY(hipEventRecord(m.ev0, m.stream));
+	HIP_TRY(hipEventRecord(m.s.ev[0], m.s.stream));
 	const whamd_status_t st = heur_launch_pending(m, msg);
 	if (st != WHAMD_OK) return st;
-	HEUR_TRY(hipEventRecord(m.ev1, m.stream));
+	HIP_TRY(hipEventRecord(m.s.ev[1], m.s.stream));
 	m.launched = true;
 	return WHAMD_OK;
 }
@@ -260,29 +233,29 @@ whamd_status_t HeurBatch::enqueue(const HeurPlan* const* plans, size_t n, int de
 whamd_status_t HeurBatch::wait(HeurResult* outs, std::string& msg) {
 	Impl& m = *impl_;
 	if (!m.launched) { msg = "the batch was not enqueued"; return WHAMD_ERR_INVALID; }
-	HEUR_TRY(hipSetDevice(m.device));
+	HIP_TRY(hipSetDevice(m.s.device));
 	float ms_total = 0;
 	for (;;) {
-		hipError_t e = hipStreamSynchronize(m.stream);
+		hipError_t e = hipStreamSynchronize(m.s.stream);
 		if (e != hipSuccess) { msg = std::string("heuristic kernel failed: ") + hipGetErrorString(e); return WHAMD_ERR_DEVICE; }
 		float ms = 0;
-		(void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
+		(void)hipEventElapsedTime(&ms, m.s.ev[0], m.s.ev[1]);
 		ms_total += ms;
 		bool again = false;
 		for (Impl::Job& job : m.jobs) {
 			if (job.done) continue;
-			HEUR_TRY(hipMemcpy(job.stats, job.D.stats, sizeof job.stats, hipMemcpyDeviceToHost));
+			HIP_TRY(hipMemcpy(job.stats, job.D.stats, sizeof job.stats, hipMemcpyDeviceToHost));
 			if (job.stats[0] == 2) {   // the records outgrew the arena: four times the room, this table once more
-				devpool_give(m.device, job.arena, job.arena_bytes);
+				devpool_give(m.s.device, job.arena, job.arena_bytes);
 				job.arena = nullptr;
 				job.arena_words *= 4;
 				size_t free_b = 0, total_b = 0;
-				HEUR_TRY(hipMemGetInfo(&free_b, &total_b));
+				HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 				if (job.arena_words * 4 > free_b / 2) { msg = "PedMecHeuristic: the backtrace records do not fit in device memory"; return WHAMD_ERR_UNSUPPORTED; }
-				HEUR_TRY(devpool_take(m.device, job.arena_words * 4, &job.arena, &job.arena_bytes));
+				HIP_TRY(devpool_take(m.s.device, job.arena_words * 4, &job.arena, &job.arena_bytes));
 				job.D.arena = (uint32_t*)job.arena; job.D.arena_words = job.arena_words;
-				HEUR_TRY(hipMemsetAsync(job.D.stats, 0, 256, m.stream));
-				HEUR_TRY(hipMemsetAsync(job.D.opt_bipart, 0, std::max<size_t>(job.plan->n_reads, 1), m.stream));
+				HIP_TRY(hipMemsetAsync(job.D.stats, 0, 256, m.s.stream));
+				HIP_TRY(hipMemsetAsync(job.D.opt_bipart, 0, std::max<size_t>(job.plan->n_reads, 1), m.s.stream));
 				again = true;
 				continue;
 			}
@@ -290,10 +263,10 @@ whamd_status_t HeurBatch::wait(HeurResult* outs, std::string& msg) {
 			job.done = true;
 		}
 		if (!again) break;
-		HEUR_TRY(hipEventRecord(m.ev0, m.stream));
+		HIP_TRY(hipEventRecord(m.s.ev[0], m.s.stream));
 		const whamd_status_t st = heur_launch_pending(m, msg);
 		if (st != WHAMD_OK) return st;
-		HEUR_TRY(hipEventRecord(m.ev1, m.stream));
+		HIP_TRY(hipEventRecord(m.s.ev[1], m.s.stream));
 	}
 #ifdef WHAMD_HEURISTIC_STAMPS
 	for (const Impl::Job& job : m.jobs)
@@ -311,12 +284,11 @@ whamd_status_t HeurBatch::wait(HeurResult* outs, std::string& msg) {
 		out.device_ms = ms_total;   // (the launch all tables of the batch shared)
 		out.max_solutions = job.stats[1];
 		out.total_solutions = job.stats[2];
-		HEUR_TRY(hipMemcpy(out.transmission.data(), job.D.opt_trans, (size_t)pl.n_cols * 4, hipMemcpyDeviceToHost));
-		if (pl.n_reads) HEUR_TRY(hipMemcpy(out.bipartition.data(), job.D.opt_bipart, pl.n_reads, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(out.transmission.data(), job.D.opt_trans, (size_t)pl.n_cols * 4, hipMemcpyDeviceToHost));
+		if (pl.n_reads) HIP_TRY(hipMemcpy(out.bipartition.data(), job.D.opt_bipart, pl.n_reads, hipMemcpyDeviceToHost));
 	}
 	return WHAMD_OK;
 }
-#undef HEUR_TRY
 
 whamd_status_t heuristic_solve_device(const HeurPlan& pl, int device, HeurResult& out, std::string& msg) {
 	HeurBatch batch;

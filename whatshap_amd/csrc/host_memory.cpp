@@ -1,4 +1,4 @@
-// host_memory.cpp -- the host side's large blocks are KEPT between tables (the device side has its pools: device_pool.h).
+// host_memory.cpp -- the host side's large blocks are KEPT between tables (the device side has its pools: device_runtime.h).
 //
 // A table's create path sizes ~100 arrays of 64 KB .. 50 MB (columns, entries, deltas, terms, plan rows, descriptors, solution) and its destroy
 // frees them.  glibc serves such sizes with one mmap each and returns them with munmap: every create faults its pages in again, every destroy

@@ -1,4 +1,4 @@
-// host_parallel.h -- the two helpers of the host create path (problem.cpp, slot_plan.cpp, dp_device.hip): ranges of independent items
+// host_parallel.h -- the two helpers of the host create path (problem.cpp, slot_plan.cpp, dp_device.hip, device_runtime.cpp): ranges of independent items
 // on a few host threads, and vectors that are not zero-filled when they are sized (the range workers touch their own part first, so
 // the page faults of a 30 MB array are spread over the threads as well).
 #pragma once

@@ -17,7 +17,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "device_pool.h"
+#include "device_runtime.h"
 #include "polyscore.h"
 
 namespace whamd {
@@ -127,53 +127,6 @@ __global__ void __launch_bounds__(BLOCK) poly_compact_kernel(CompactArgs a) {
 	}
 }
 
-#define PS_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { msg = std::string(#expr) + " failed: " + hipGetErrorString(e_); return WHAMD_ERR_DEVICE; } } while (0)
-
-// What a call holds on the device and in pinned memory; given back on every way out.
-struct Session {
-	int device = -1;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	std::vector<std::pair<void*, size_t>> dev, pinned;
-	~Session() {
-		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& b : dev) devpool_give(device, b.first, b.second);
-		for (auto& b : pinned) pinned_block_give(b.first, b.second);
-		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-		if (stream) (void)hipStreamDestroy(stream);
-	}
-	whamd_status_t open(int dev_index, std::string& msg) {
-		int ndev = 0;
-		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-			(void)hipGetLastError();
-			msg = "no HIP device visible: the whatshap_amd device path needs an MI355X (gfx950); there is no CPU fallback";
-			return WHAMD_ERR_DEVICE;
-		}
-		if (dev_index < 0 || dev_index >= ndev) { msg = "device index " + std::to_string(dev_index) + " out of range (" + std::to_string(ndev) + " visible)"; return WHAMD_ERR_DEVICE; }
-		device = dev_index;
-		PS_TRY(hipSetDevice(device));
-		PS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		for (hipEvent_t& e : ev) PS_TRY(hipEventCreate(&e));
-		return WHAMD_OK;
-	}
-	whamd_status_t device_block(size_t bytes, void** out, std::string& msg) {
-		size_t got = 0;
-		PS_TRY(devpool_take(device, std::max<size_t>(bytes, 256), out, &got));
-		dev.emplace_back(*out, got);
-		return WHAMD_OK;
-	}
-	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg) {
-		size_t got = 0;
-		PS_TRY(pinned_block_take(std::max<size_t>(bytes, 256), out, &got));
-		pinned.emplace_back(*out, got);
-		return WHAMD_OK;
-	}
-	double ms(int a, int b) const {
-		float t = 0.0f;
-		return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
-	}
-};
-
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -214,7 +167,7 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	const size_t o_counts = o; o = align_up(o + n_mats * 24);
 	const size_t total_in = o;
 	Session s;
-	whamd_status_t st = s.open(device, msg);
+	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
 	char* stage = nullptr;
 	char* base = nullptr;
@@ -263,7 +216,7 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	if ((st = s.device_block(n_pairs * 4, (void**)&keep, msg)) != WHAMD_OK) return st;
 	if ((st = s.device_block(n_pairs * 4, (void**)&slot, msg)) != WHAMD_OK) return st;
 	size_t scan_tmp = 0;
-	PS_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
+	HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
 	void* scan_buf = nullptr;
 	if ((st = s.device_block(scan_tmp, &scan_buf, msg)) != WHAMD_OK) return st;
 	uint32_t* tail = nullptr;   // pinned: keep and slot of the last pair, then the counts
@@ -288,16 +241,16 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	pa.counts = (unsigned long long*)(base + o_counts);
 	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pairs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
 
-	PS_TRY(hipEventRecord(s.ev[0], s.stream));
-	PS_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
-	PS_TRY(hipEventRecord(s.ev[1], s.stream));
+	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+	HIP_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
+	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
 	hipLaunchKernelGGL(poly_pair_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, pa);
-	PS_TRY(hipGetLastError());
-	PS_TRY(rocprim::exclusive_scan(scan_buf, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
-	PS_TRY(hipMemcpyAsync(tail, keep + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
-	PS_TRY(hipMemcpyAsync(tail + 1, slot + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
-	PS_TRY(hipMemcpyAsync(tail + 2, base + o_counts, n_mats * 24, hipMemcpyDeviceToHost, s.stream));
-	PS_TRY(hipStreamSynchronize(s.stream));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(rocprim::exclusive_scan(scan_buf, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
+	HIP_TRY(hipMemcpyAsync(tail, keep + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
+	HIP_TRY(hipMemcpyAsync(tail + 1, slot + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
+	HIP_TRY(hipMemcpyAsync(tail + 2, base + o_counts, n_mats * 24, hipMemcpyDeviceToHost, s.stream));
+	HIP_TRY(hipStreamSynchronize(s.stream));
 	*launches = 2;
 	const uint64_t n_kept = (uint64_t)tail[0] + tail[1];
 	const unsigned long long* counts = (const unsigned long long*)(tail + 2);
@@ -318,20 +271,20 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 		const uint64_t max_key = (uint64_t)N * N;
 		while (end_bit < 64 && (max_key >> end_bit)) ++end_bit;
 		size_t sort_tmp = 0;
-		PS_TRY(rocprim::radix_sort_pairs(nullptr, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
 		void* sort_buf = nullptr;
 		if ((st = s.device_block(sort_tmp, &sort_buf, msg)) != WHAMD_OK) return st;
 		char* res = nullptr;
 		if ((st = s.pinned_block(n_kept * 12, (void**)&res, msg)) != WHAMD_OK) return st;
 		CompactArgs ca{n_pairs, N, pa.pair_prefix, pa.order, score, keep, slot, key, val};
 		hipLaunchKernelGGL(poly_compact_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, ca);
-		PS_TRY(hipGetLastError());
-		PS_TRY(rocprim::radix_sort_pairs(sort_buf, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
-		PS_TRY(hipEventRecord(s.ev[2], s.stream));
-		PS_TRY(hipMemcpyAsync(res, key2, n_kept * 8, hipMemcpyDeviceToHost, s.stream));
-		PS_TRY(hipMemcpyAsync(res + n_kept * 8, val2, n_kept * 4, hipMemcpyDeviceToHost, s.stream));
-		PS_TRY(hipEventRecord(s.ev[3], s.stream));
-		PS_TRY(hipStreamSynchronize(s.stream));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(rocprim::radix_sort_pairs(sort_buf, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
+		HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+		HIP_TRY(hipMemcpyAsync(res, key2, n_kept * 8, hipMemcpyDeviceToHost, s.stream));
+		HIP_TRY(hipMemcpyAsync(res + n_kept * 8, val2, n_kept * 4, hipMemcpyDeviceToHost, s.stream));
+		HIP_TRY(hipEventRecord(s.ev[3], s.stream));
+		HIP_TRY(hipStreamSynchronize(s.stream));
 		*launches = 4;
 		dl_ms = (float)s.ms(2, 3);
 		*kernel_ms = s.ms(1, 2);
@@ -355,8 +308,8 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 			}
 		});
 	} else {
-		PS_TRY(hipEventRecord(s.ev[2], s.stream));
-		PS_TRY(hipStreamSynchronize(s.stream));
+		HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+		HIP_TRY(hipStreamSynchronize(s.stream));
 		*kernel_ms = s.ms(1, 2);
 	}
 	*upload_ms = s.ms(0, 1);

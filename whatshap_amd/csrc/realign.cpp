@@ -11,7 +11,6 @@
 #include <vector>
 
 #include "debug_build.h"
-#include "device_pool.h"
 
 namespace whamd {
 void set_last_error(const std::string& msg);   // c_api.cpp

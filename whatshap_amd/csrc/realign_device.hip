@@ -23,7 +23,7 @@
 #include <cstring>
 #include <string>
 
-#include "device_pool.h"
+#include "device_runtime.h"
 #include "realign.h"
 
 namespace whamd {
@@ -293,56 +293,9 @@ __global__ void __launch_bounds__(256) distance_affine_kernel(PairArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- host driver
-#define RA_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { msg = std::string(#expr) + " failed: " + hipGetErrorString(e_); return WHAMD_ERR_DEVICE; } } while (0)
-
 constexpr uint32_t BLOCK = 256, MAX_BLOCKS = 8192, MAX_LONG_BLOCKS = 1024;
 constexpr size_t LDS_LIMIT = 64 << 10;
 constexpr size_t SCRATCH_BUDGET = (size_t)512 << 20;   // scratch rows of the long-job launch: the grid shrinks to stay within this (at least one block)
-
-// What a call holds on the device and in pinned memory; given back on every way out.
-struct Session {
-	int device = -1;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-	std::vector<std::pair<void*, size_t>> dev, pinned;
-	~Session() {
-		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& b : dev) devpool_give(device, b.first, b.second);
-		for (auto& b : pinned) pinned_block_give(b.first, b.second);
-		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-		if (stream) (void)hipStreamDestroy(stream);
-	}
-	whamd_status_t open(int dev_index, std::string& msg) {
-		int ndev = 0;
-		if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-			(void)hipGetLastError();
-			msg = "no HIP device visible: the whatshap_amd device path needs an MI355X (gfx950); there is no CPU fallback";
-			return WHAMD_ERR_DEVICE;
-		}
-		if (dev_index < 0 || dev_index >= ndev) { msg = "device index " + std::to_string(dev_index) + " out of range (" + std::to_string(ndev) + " visible)"; return WHAMD_ERR_DEVICE; }
-		device = dev_index;
-		RA_TRY(hipSetDevice(device));
-		RA_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		for (hipEvent_t& e : ev) RA_TRY(hipEventCreate(&e));
-		return WHAMD_OK;
-	}
-	whamd_status_t device_block(size_t bytes, void** out, std::string& msg) {
-		size_t got = 0;
-		RA_TRY(devpool_take(device, std::max<size_t>(bytes, 256), out, &got));
-		dev.emplace_back(*out, got);
-		return WHAMD_OK;
-	}
-	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg) {
-		size_t got = 0;
-		RA_TRY(pinned_block_take(std::max<size_t>(bytes, 256), out, &got));
-		pinned.emplace_back(*out, got);
-		return WHAMD_OK;
-	}
-	double ms(int a, int b) const {
-		float t = 0.0f;
-		return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
-	}
-};
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -383,7 +336,7 @@ LongShape long_shape(bool affine, uint64_t n_long, uint32_t max_target) {
 whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, double* upload_ms, double* kernel_ms,
                               double* download_ms, std::string& msg) {
 	Session s;
-	whamd_status_t st = s.open(device, msg);
+	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
 	const bool affine = b.params.use_affine != 0;
 	// one staging image, one device block: jobs | query windows | long jobs | variants | allowed alleles | alt offsets | alt bytes | reference slice
@@ -456,21 +409,21 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 			else longj.carry = (uint64_t*)c;
 		}
 	}
-	RA_TRY(hipEventRecord(s.ev[0], s.stream));
-	RA_TRY(hipMemcpyAsync(base, stage, total, hipMemcpyHostToDevice, s.stream));
-	RA_TRY(hipEventRecord(s.ev[1], s.stream));
+	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+	HIP_TRY(hipMemcpyAsync(base, stage, total, hipMemcpyHostToDevice, s.stream));
+	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
 	if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
 	else hipLaunchKernelGGL(realign_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
-	RA_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	if (b.n_long) {
 		if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longj);
 		else hipLaunchKernelGGL(realign_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longj);
-		RA_TRY(hipGetLastError());
+		HIP_TRY(hipGetLastError());
 	}
-	RA_TRY(hipEventRecord(s.ev[2], s.stream));
-	RA_TRY(hipMemcpyAsync(hres, res, r_total, hipMemcpyDeviceToHost, s.stream));
-	RA_TRY(hipEventRecord(s.ev[3], s.stream));
-	RA_TRY(hipStreamSynchronize(s.stream));
+	HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+	HIP_TRY(hipMemcpyAsync(hres, res, r_total, hipMemcpyDeviceToHost, s.stream));
+	HIP_TRY(hipEventRecord(s.ev[3], s.stream));
+	HIP_TRY(hipStreamSynchronize(s.stream));
 	*upload_ms = s.ms(0, 1);
 	*kernel_ms = s.ms(1, 2);
 	*download_ms = s.ms(2, 3);
@@ -494,7 +447,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 		}
 	}
 	Session s;
-	whamd_status_t st = s.open(device, msg);
+	whamd_status_t st = s.open(device, 0, msg);
 	if (st != WHAMD_OK) return st;
 	const uint64_t nq = query_ptr[n_pairs], nt = target_ptr[n_pairs], n_long = long_pairs.size();
 	const size_t o_qp = 0, o_tp = align_up((n_pairs + 1) * 8), o_q = align_up(o_tp + (n_pairs + 1) * 8), o_t = align_up(o_q + nq);
@@ -537,17 +490,17 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 			else longp.carry = (uint64_t*)c;
 		}
 	}
-	RA_TRY(hipMemcpyAsync(base, stage, o_out, hipMemcpyHostToDevice, s.stream));
+	HIP_TRY(hipMemcpyAsync(base, stage, o_out, hipMemcpyHostToDevice, s.stream));
 	if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
 	else hipLaunchKernelGGL(distance_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
-	RA_TRY(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 	if (n_long) {
 		if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longp);
 		else hipLaunchKernelGGL(distance_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longp);
-		RA_TRY(hipGetLastError());
+		HIP_TRY(hipGetLastError());
 	}
-	RA_TRY(hipMemcpyAsync(stage + o_out, base + o_out, n_pairs * 8, hipMemcpyDeviceToHost, s.stream));
-	RA_TRY(hipStreamSynchronize(s.stream));
+	HIP_TRY(hipMemcpyAsync(stage + o_out, base + o_out, n_pairs * 8, hipMemcpyDeviceToHost, s.stream));
+	HIP_TRY(hipStreamSynchronize(s.stream));
 	std::memcpy(distance_out, stage + o_out, n_pairs * 8);
 	return WHAMD_OK;
 }
