@@ -524,6 +524,68 @@ void whamd_poly_score_destroy(whamd_poly_scores* s);
  * genotype likelihoods explain the depths best; host only, nothing printed. */
 whamd_status_t whamd_poly_estimate_error_rate(const whamd_poly_matrix_view* matrix, uint32_t ploidy, double* err_out);
 
+/* ---- Progeny marker scoring (get_variant_scoring, whatshap/polyphase/offspringscoring.py:143-188) ---------------------------------------
+ * The "scoring" stage of polyphasegenetic: for every marker node i and every partner j = i + s of the stride list of scoring_window,
+ * ProgenyGenotypeLikelihoods::get{SimplexNulliplex,SimplexSimplex,DuplexNulliplex}Score(i, j)
+ * (src/polyphase/progenygenotypelikelihoods.cpp:116-149): log(1 / (ploidy - 1)) plus, over the progeny samples with data at both nodes in
+ * increasing order, log(cooccur / disjoint) of two weighted sums of 4 or 6 likelihood products.  The host (csrc/progeny.cpp) finds the
+ * stored entries and the row each of them reads; one device lane per entry walks the samples in double (csrc/progeny_device.hip).  Products
+ * and sums are rounded one by one as the reference's are, so only log can differ from it (device math library against the host's).
+ * The table is the reference's: float, [position][sample][genotype 0 .. ploidy], a sample without data at a position has a negative
+ * genotype-0 value; a node at or beyond n_positions reads 0.0 everywhere (getGl, :72-76).  Only genotypes 0 .. 2 are read.
+ * Stored entries, as the reference's loop stores them: -inf where both nodes belong to one variant; nothing for an anchor that is not
+ * simplex-nulliplex (alt_count 1, co_alt_count 0); else the score kind follows the partner's variant type, (1, 0), (2, 0) or (1, 1) --
+ * any other type is WHAMD_ERR_INVALID --, and a partner of the same variant as the partner scored before it stores that score again.
+ * Errors (WHAMD_ERR_INVALID, nothing launched): ploidy < 2, scoring_window < 1 -- and scoring_window 1 .. 3, for which the reference's
+ * stride list raises --, a node variant outside the type arrays, (n_positions + 1) * n_samples * (ploidy + 1) >= 2^32 (the reference's
+ * uint32 index).  Results: per problem, (i, j) with i > j sorted by the triangular index i*(i-1)/2 + j, the double score and its float
+ * rounding (TriangleSparseMatrix.set). */
+typedef struct whamd_progeny_view {
+	const float* gl;                 /* [n_positions][n_samples][ploidy + 1] */
+	uint64_t n_positions;            /* numPositions of the reference's constructor */
+	uint32_t n_samples;
+	uint32_t ploidy;
+	uint64_t n_nodes;                /* len(varinfo.get_node_positions()) */
+	const uint32_t* node_variant;    /* [n_nodes] node_to_variant */
+	uint64_t n_variants;
+	const uint32_t* alt_count;       /* [n_variants] */
+	const uint32_t* co_alt_count;    /* [n_variants] */
+	uint32_t scoring_window;
+} whamd_progeny_view;
+
+typedef struct whamd_progeny_score_stats {
+	uint64_t n_nodes;
+	uint64_t n_entries;              /* stored entries */
+	uint64_t n_inf;                  /* of them: set to -inf (both nodes of one variant) */
+	uint64_t n_reused;               /* of them: the score of the partner before, stored again */
+	uint64_t n_sample_terms;         /* (n_entries - n_inf) * n_samples: sample iterations of the pair loop */
+	uint32_t launches;               /* kernel launches of the whole call (0: nothing touched the device) */
+	double host_ms;                  /* wall, whole call: validation, entry lists */
+	double upload_ms;                /* HIP events, whole call */
+	double kernel_ms;                /* HIP events, whole call */
+	double download_ms;              /* HIP events, whole call */
+	double total_ms;                 /* wall, whole call (the repack of the tables included) */
+} whamd_progeny_score_stats;
+
+typedef struct whamd_progeny_scores whamd_progeny_scores; /* opaque: the result of one whamd_progeny_score call */
+
+/* One call for a batch of problems (chromosomes, parents): one upload, one launch, one download. */
+whamd_status_t whamd_progeny_score(const whamd_progeny_view* problems, uint64_t n_problems, int device, whamd_progeny_scores** out);
+uint64_t whamd_progeny_score_problem_count(const whamd_progeny_scores* s);
+/* Entries of problem m; the outputs are [whamd_progeny_score_count(s, m)], NULL skips. */
+uint64_t whamd_progeny_score_count(const whamd_progeny_scores* s, uint64_t m);
+whamd_status_t whamd_progeny_score_get(const whamd_progeny_scores* s, uint64_t m, uint32_t* i_out, uint32_t* j_out, float* score_f32_out,
+                                       double* score_f64_out);
+/* Counts of problem m; the times are those of the whole call. */
+whamd_status_t whamd_progeny_score_get_stats(const whamd_progeny_scores* s, uint64_t m, whamd_progeny_score_stats* stats_out);
+void whamd_progeny_score_destroy(whamd_progeny_scores* s);
+/* get_most_likely_variant_type (offspringscoring.py:191-211) for n_nodes table rows (nodes == NULL: rows 0 .. n_nodes - 1): llh_out
+ * [n_nodes][(ploidy+1)(ploidy+2)/2] holds the llh of every parental type (g0, g1 <= g0) in the reference's loop order, starting at 1.0 as
+ * it does; g0_out / g1_out the first type with a strictly larger llh.  priors: [ploidy+1][ploidy+1][ploidy+1] (compute_gt_likelihood_priors).
+ * One device lane per (row, type). */
+whamd_status_t whamd_progeny_variant_types(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
+                                           const uint32_t* nodes, uint64_t n_nodes, int device, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,21 @@ whamd_status_t whamd_debug_edit_distance_host(uint64_t n_pairs, const uint64_t* 
 whamd_status_t whamd_debug_poly_score_host(const whamd_poly_matrix_view* matrices, uint64_t n_matrices, uint32_t min_overlap, uint32_t ploidy,
                                            double err, whamd_poly_scores** out);
 
+/* HOST-ONLY DIAGNOSTICS of progeny marker scoring (csrc/progeny.cpp): the same entry lists as whamd_progeny_score, then the pair loop on
+ * one CPU thread on the caller's table with the device's inner function -- what the CPU test-suite holds to the recorded reference bit for
+ * bit; never what the product calls.  Read with the whamd_progeny_score_* getters of the debug library. */
+whamd_status_t whamd_debug_progeny_score_host(const whamd_progeny_view* problems, uint64_t n_problems, whamd_progeny_scores** out);
+/* The same for a caller-given list of pairs of one problem (a sample of a large one): stored_out[x] = 1 and score_out[x] where the
+ * reference's loop stores an entry for (i[x], j[x]), else 0. */
+whamd_status_t whamd_debug_progeny_score_entries_host(const whamd_progeny_view* problem, uint64_t n_entries, const uint32_t* i, const uint32_t* j,
+                                                      double* score_out, uint8_t* stored_out);
+/* One pair score of the table: kind 0 getSimplexNulliplexScore, 1 getSimplexSimplexScore, 2 getDuplexNulliplexScore (pos1, pos2). */
+whamd_status_t whamd_debug_progeny_pair_score_host(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, uint64_t pos1,
+                                                   uint64_t pos2, uint32_t kind, double* score_out);
+/* whamd_progeny_variant_types on one CPU thread. */
+whamd_status_t whamd_debug_progeny_variant_types_host(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
+                                                      const uint32_t* nodes, uint64_t n_nodes, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
+
 #ifdef __cplusplus
 }
 #endif

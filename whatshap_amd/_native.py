@@ -173,6 +173,20 @@ class PolyScoreStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class ProgenyView(C.Structure):
+    _fields_ = [("gl", C.POINTER(C.c_float)), ("n_positions", C.c_uint64), ("n_samples", C.c_uint32), ("ploidy", C.c_uint32), ("n_nodes", C.c_uint64),
+                ("node_variant", C.POINTER(C.c_uint32)), ("n_variants", C.c_uint64), ("alt_count", C.POINTER(C.c_uint32)),
+                ("co_alt_count", C.POINTER(C.c_uint32)), ("scoring_window", C.c_uint32)]
+
+
+class ProgenyScoreStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_nodes", "n_entries", "n_inf", "n_reused", "n_sample_terms")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -320,6 +334,17 @@ def debug_lib() -> C.CDLL:
                                                  C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     L.whamd_debug_poly_score_host.restype = C.c_int
     L.whamd_debug_poly_score_host.argtypes = [C.POINTER(PolyMatrixView), C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]
+    L.whamd_debug_progeny_score_host.restype = C.c_int
+    L.whamd_debug_progeny_score_host.argtypes = [C.POINTER(ProgenyView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_progeny_score_entries_host.restype = C.c_int
+    L.whamd_debug_progeny_score_entries_host.argtypes = [C.POINTER(ProgenyView), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                         C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+    L.whamd_debug_progeny_pair_score_host.restype = C.c_int
+    L.whamd_debug_progeny_pair_score_host.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                      C.POINTER(C.c_double)]
+    L.whamd_debug_progeny_variant_types_host.restype = C.c_int
+    L.whamd_debug_progeny_variant_types_host.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                                         C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     _debug_lib = L
     return L
 
@@ -447,6 +472,21 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_poly_score_destroy.argtypes = [C.c_void_p]
     L.whamd_poly_estimate_error_rate.restype = C.c_int
     L.whamd_poly_estimate_error_rate.argtypes = [C.POINTER(PolyMatrixView), C.c_uint32, C.POINTER(C.c_double)]
+    L.whamd_progeny_score.restype = C.c_int
+    L.whamd_progeny_score.argtypes = [C.POINTER(ProgenyView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_progeny_score_problem_count.restype = C.c_uint64
+    L.whamd_progeny_score_problem_count.argtypes = [C.c_void_p]
+    L.whamd_progeny_score_count.restype = C.c_uint64
+    L.whamd_progeny_score_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_progeny_score_get.restype = C.c_int
+    L.whamd_progeny_score_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    L.whamd_progeny_score_get_stats.restype = C.c_int
+    L.whamd_progeny_score_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ProgenyScoreStats)]
+    L.whamd_progeny_score_destroy.restype = None
+    L.whamd_progeny_score_destroy.argtypes = [C.c_void_p]
+    L.whamd_progeny_variant_types.restype = C.c_int
+    L.whamd_progeny_variant_types.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                              C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -469,6 +509,8 @@ EXPORTED_SYMBOLS = [
     "whamd_edit_distance_batch",
     "whamd_poly_score", "whamd_poly_score_matrix_count", "whamd_poly_score_count", "whamd_poly_score_get", "whamd_poly_score_get_stats",
     "whamd_poly_score_destroy", "whamd_poly_estimate_error_rate",
+    "whamd_progeny_score", "whamd_progeny_score_problem_count", "whamd_progeny_score_count", "whamd_progeny_score_get", "whamd_progeny_score_get_stats",
+    "whamd_progeny_score_destroy", "whamd_progeny_variant_types",
 ]
 
 
