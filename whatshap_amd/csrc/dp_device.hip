@@ -69,6 +69,159 @@ bool select_kernels(uint32_t T, uint32_t n_ind, FusedFn& ff, KeysFn& kf) {
 
 }  // namespace
 
+// ================================================================================================ what a create shares between its phases
+
+namespace {
+
+// The laps of a create under WHAMD_DEBUG_TIMING: lap() prints the time since the previous lap; every lap also counts towards one of the four stages of
+// the closing summary line (plan | descriptors + copies | backtrace arena | rest).  Without the switch nothing is measured.
+struct CreateLaps {
+	using Clock = std::chrono::steady_clock;
+	const bool on = getenv("WHAMD_DEBUG_TIMING") != nullptr;
+	Clock::time_point last = Clock::now();
+	double stage_ms[4] = {0.0, 0.0, 0.0, 0.0};
+	int stage = 0;
+	double take() {
+		const auto now = Clock::now();
+		const double ms = std::chrono::duration<double, std::milli>(now - last).count();
+		last = now;
+		stage_ms[stage] += ms;
+		return ms;
+	}
+	void lap(const char* what) {
+		if (on) fprintf(stderr, "[whamd timing]   upload: %s %.2f ms\n", what, take());
+	}
+	void next_stage() {
+		if (!on) return;
+		take();
+		if (stage < 3) ++stage;
+	}
+	void summary(double arena_gb) {
+		if (!on) return;
+		take();
+		fprintf(stderr, "[whamd timing] upload: plan %.1f ms, descriptors + copies %.1f ms, backtrace arena (%.2f GB) %.1f ms, rest %.1f ms\n", stage_ms[0], stage_ms[1], arena_gb, stage_ms[2],
+		        stage_ms[3]);
+	}
+};
+
+// The upload half of a create.  ONE device block and ONE staging image per table: every uploaded array is a piece of the block at the offset it has in the
+// pinned area, and the pieces leave as a few large copies.  (Per-array copies of ~1 MB ran at 25 GB/s -- 96 coverage-15 tables, 28 MB each, spent their
+// creates waiting for the link --; pieces of 32 MB and more reach 56 GB/s: scripts/micro/r6_h2d_rate.py.)  Without an image or a block every array is an
+// allocation and a copy of its own.
+struct TableUploader {
+	const int device;
+	const hipStream_t stream;   // every copy of the create and its table kernels (all tables' images on ONE shared stream instead of sixteen at once was measured: 1 055 - 1 273 against 1 015 - 1 153 creates/s, noise)
+	StageSession stage;
+	std::vector<std::pair<void*, size_t>>& allocations;   // the table's: what alloc() takes, Impl::release() gives back
+	char* d_slab = nullptr;
+	size_t slab_cap = 0, slab_used = 0, slab_flushed = 0;
+	bool unstaged_copies = false;   // a copy whose source is pageable memory of this call: the create must wait for it
+
+	TableUploader(int dev, hipStream_t us, std::vector<std::pair<void*, size_t>>& table_allocations) : device(dev), stream(us), stage(us), allocations(table_allocations) {}
+
+	hipError_t alloc(void** dptr, size_t bytes) {
+		size_t got = 0;
+		hipError_t e = devpool_take(device, std::max<size_t>(bytes, 16), dptr, &got);
+		if (e == hipSuccess) allocations.emplace_back(*dptr, got);
+		return e;
+	}
+	// The staging image and the device block for `upload_bytes` (an upper bound of everything up() will be given); where either is not to be had, up() falls back.
+	void open_block(size_t upload_bytes) {
+		stage.expect(upload_bytes);
+		if (upload_bytes <= STAGE_MAX && !debug_env("WHAMD_NO_UPLOAD_SLAB") && stage.begin_image(upload_bytes)) {
+			void* ptr = nullptr;
+			if (alloc(&ptr, upload_bytes) == hipSuccess) { d_slab = (char*)ptr; slab_cap = upload_bytes; }
+			else { (void)hipGetLastError(); stage.image = false; }
+		}
+	}
+	hipError_t flush() {
+		if (!d_slab || slab_used == slab_flushed) return hipSuccess;
+		// (WHAMD_SKIP_SLAB_COPY=1, debug library, RESULTS INVALID: the image is built but does not travel -- what the creates cost without the link)
+		const hipError_t e = debug_env("WHAMD_SKIP_SLAB_COPY") ? hipSuccess : hipMemcpyAsync(d_slab + slab_flushed, stage.base + slab_flushed, slab_used - slab_flushed, hipMemcpyHostToDevice, stream);
+		stage.pending = true;
+		slab_flushed = slab_used;
+		return e;
+	}
+	hipError_t up(void** dptr, const void* src, size_t bytes) {
+		const size_t padded = (bytes + 255) & ~(size_t)255;
+		if (d_slab && slab_used + padded <= slab_cap) {
+			*dptr = d_slab + slab_used;
+			char* at = stage.base + slab_used;
+			const char* from = (const char*)src;
+			if (bytes >= ((size_t)4 << 20)) parallel_ranges(bytes, host_threads(bytes, (size_t)2 << 20), [at, from](uint64_t b0, uint64_t b1, uint32_t) { std::memcpy(at + b0, from + b0, b1 - b0); });
+			else if (bytes) std::memcpy(at, from, bytes);
+			slab_used += padded;
+			stage.total += padded;
+			return slab_used - slab_flushed >= ((size_t)32 << 20) ? flush() : hipSuccess;
+		}
+		hipError_t e = alloc(dptr, bytes);
+		if (e != hipSuccess) return e;
+		if (bytes) e = stage.copy(*dptr, src, bytes);
+		if (bytes && stage.image) unstaged_copies = true;   // (did not fit the image: copied straight from the caller's memory)
+		return e;
+	}
+	// reserves `bytes` like up(), sends only the byte ranges of `pieces`
+	hipError_t up_pieces(void** dptr, const void* src, size_t bytes, const std::vector<std::pair<size_t, size_t>>& pieces) {
+		const size_t padded = (bytes + 255) & ~(size_t)255;
+		const bool in_slab = d_slab && slab_used + padded <= slab_cap;
+		if (in_slab) {
+			hipError_t e = flush();   // what is staged so far leaves as it is; this array's pieces go out on their own
+			if (e != hipSuccess) return e;
+			*dptr = d_slab + slab_used;
+			slab_used += padded;
+			slab_flushed = slab_used;      // (nothing of this array is in the staging image)
+		} else {
+			hipError_t e = alloc(dptr, bytes);
+			if (e != hipSuccess) return e;
+		}
+		const size_t image_at = slab_used - padded;   // (in_slab: where the array lies in the block AND in the staging image)
+		for (const auto& pc : pieces) {
+			if (pc.second <= pc.first) continue;
+			const char* from = (const char*)src + pc.first;
+			if (in_slab) {   // through the pinned image, like everything else: the copy's source outlives the create
+				std::memcpy(stage.base + image_at + pc.first, from, pc.second - pc.first);
+				from = stage.base + image_at + pc.first;
+				stage.pending = true;
+			} else {
+				unstaged_copies = true;   // (straight from the caller's pageable memory: the create ends with a host wait)
+			}
+			hipError_t e = hipMemcpyAsync((char*)*dptr + pc.first, from, pc.second - pc.first, hipMemcpyHostToDevice, stream);
+			if (e != hipSuccess) return e;
+		}
+		return hipSuccess;
+	}
+};
+
+// What one create passes from phase to phase (DeviceTable::upload); everything that outlives the create is in Impl.
+struct TableBuild {
+	CreateLaps laps;
+	// sizes
+	uint32_t n = 0;              // columns
+	uint32_t tbits = 0;          // transmission bits of an argmin
+	uint32_t ni = 1;             // individuals, at least one
+	size_t free_b = 0;           // free HBM when the create began, idle arenas included
+	uint64_t arena_cap = 0;      // what the backtrace arena may take
+	uint64_t bt = 0;             // bytes of the arena (the largest window's)
+	uint32_t max_f = 0, max_keys_f = 0;   // log2 of the widest exchange column / of the widest column on the key path
+	size_t exchange_bytes = 0;   // one exchange column at max_f: a d_pr buffer of a lane, a kept window boundary
+	// flags
+	bool force_keys = false;     // every per-column step takes the key path
+	bool ped_slots = false;      // pedigree slot runs
+	// host arrays whose copies may still be reading them when their phase returns, or that a later phase reads
+	std::vector<uint32_t> segs;               // deposit segments of the columns outside slot runs (the column backtrace units inline them)
+	RawVec<uint32_t> term_ptr32;
+	std::vector<uint32_t> window_first_col;   // first column of every window after the first
+	RawVec<uint32_t> slot_blob;
+	std::vector<uint32_t> slot_blob_off, slot_blob_words;   // per slot run: its piece of the blob (the slot backtrace units)
+	std::vector<int32_t> delta_fallback;
+	// device arrays only the table kernels read
+	const SlotRun* d_runs = nullptr;
+	const PedSlotExtra* d_pextra = nullptr;
+	const DevTerm* d_fterms = nullptr;
+};
+
+}  // namespace
+
 // ================================================================================================ DeviceTable
 
 struct DeviceTable::Impl {
@@ -198,6 +351,31 @@ struct DeviceTable::Impl {
 	uint32_t* d_bt_state = nullptr;     // (x, transmission) the walk of a window hands to the next older one
 	BtJob* d_window_jobs = nullptr;
 
+	// the phases of a create (DeviceTable::upload), in the order they run
+	whamd_status_t open(int dev, std::string& msg);
+	whamd_status_t choose_plan(Problem& p, TableBuild& b, std::string& msg);
+	void dump_plan(const Problem& p) const;
+	whamd_status_t describe_columns(const Problem& p, TableBuild& b, std::string& msg);
+	whamd_status_t lay_out_arena(const Problem& p, TableBuild& b, std::string& msg);
+	size_t upload_bound(const Problem& p, const TableBuild& b) const;
+	whamd_status_t upload_column_arrays(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
+	void build_slot_blobs(TableBuild& b) const;
+	uint64_t lay_out_slot_tables(const TableBuild& b);
+	whamd_status_t upload_slot_arrays(TableBuild& b, TableUploader& up, std::string& msg);
+	void make_jobs();
+	void make_units(const TableBuild& b);
+	whamd_status_t make_windows(const TableBuild& b, TableUploader& up, std::string& msg);
+	whamd_status_t take_result_block(uint32_t n, TableUploader& up, std::string& msg);
+	whamd_status_t make_chunks(const Problem& p, TableUploader& up, std::string& msg);
+	whamd_status_t take_solve_buffers(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
+	whamd_status_t make_lanes(const TableBuild& b, TableUploader& up, std::string& msg);
+	whamd_status_t make_schedule(const TableBuild& b, std::string& msg);
+	void make_briefs();
+	whamd_status_t upload_entries(TableUploader& up, std::string& msg);
+	whamd_status_t launch_table_kernels(const Problem& p, const TableBuild& b, TableUploader& up, std::string& msg);
+	whamd_status_t arm_debug_stamps(TableUploader& up, std::string& msg);
+	whamd_status_t record_group_backtrace(uint32_t n, TableUploader& up, std::string& msg);
+	// the solve
 	void launch_column_step(const Problem& p, const Step& step, const Lane& lane, const uint32_t* prev, uint32_t* cur, uint64_t& launches);
 	void launch_run(const ResBatchEntry& e, uint32_t step_index, uint64_t& launches);
 	void launch_slot_run(const SlotBatchEntry& e, uint64_t& launches);
@@ -218,6 +396,14 @@ struct DeviceTable::Impl {
 	hipStream_t tail_stream = nullptr;  // where submit_tail put the tail of the solve in flight, and its place in the order of all tails of the process
 	uint64_t tail_seq = 0;
 	bool tail_elsewhere = false;        // the tail (backtrace, downloads) of the solve in flight went onto another table's stream: wait() waits for ev3, not for `stream`
+
+	// the pooled stream and events (device_runtime.h), taken on the first create and given back by release_device
+	void adopt(const StreamSet& ss) { stream = ss.stream; ev0 = ss.ev[0]; ev1 = ss.ev[1]; ev2 = ss.ev[2]; ev3 = ss.ev[3]; ev_group = ss.ev[4]; ev_upload = ss.ev[5]; }
+	StreamSet stream_set() const {
+		StreamSet ss;
+		ss.stream = stream; ss.ev[0] = ev0; ss.ev[1] = ev1; ss.ev[2] = ev2; ss.ev[3] = ev3; ss.ev[4] = ev_group; ss.ev[5] = ev_upload; ss.device = device;
+		return ss;
+	}
 
 	void release_lanes() {
 		max_grid_x = 1;
@@ -267,12 +453,10 @@ void DeviceTable::release_device() {
 	if (m.stream) {
 		if (m.own_stream_used) (void)hipStreamSynchronize(m.stream);   // (13 ms for the 96 tables of a step when every table waited for a stream it had never used)
 		m.own_stream_used = false;
-		StreamSet ss;
-		ss.stream = m.stream; ss.ev[0] = m.ev0; ss.ev[1] = m.ev1; ss.ev[2] = m.ev2; ss.ev[3] = m.ev3; ss.ev[4] = m.ev_group; ss.ev[5] = m.ev_upload; ss.device = m.device;
-		streamset_give(ss);
+		streamset_give(m.stream_set());
 	}
-	m.stream = m.run_stream = nullptr;
-	m.ev0 = m.ev1 = m.ev2 = m.ev3 = m.ev_group = m.ev_upload = nullptr;
+	m.adopt(StreamSet());
+	m.run_stream = nullptr;
 	m.timing_pending = false;
 }
 
@@ -325,19 +509,29 @@ void DeviceTable::set_shared_launches(bool v) { impl_->shared_hint = v; }
 void DeviceTable::set_side_by_side(bool v) { impl_->side_by_side = v; }
 void DeviceTable::set_symmetry(int level) { impl_->symmetry = level < 0 ? 0 : (level > 2 ? 2 : level); }
 
-whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
-	Impl& m = *impl_;
-	m.device = device;
-	const whamd_status_t opened = open_device(device, msg);
+// ================================================================================================ create: the phases of DeviceTable::upload
+// Each phase says in its parameters what it touches: `Problem`, the build object (TableBuild: what later phases read), the uploader (TableUploader: the phase
+// allocates, copies or launches).  Everything else it reads and writes is the table's own state in Impl.  The order of the phases that take an uploader IS the
+// layout of the table's device block and the order of its driver calls.
+
+whamd_status_t DeviceTable::Impl::open(int dev, std::string& msg) {
+	Impl& m = *this;
+	m.device = dev;
+	const whamd_status_t opened = open_device(dev, msg);
 	if (opened != WHAMD_OK) return opened;
 	if (!m.stream) {
 		StreamSet ss;
-		if (!streamset_take(device, ss)) { msg = "could not create the table's stream and events"; return WHAMD_ERR_DEVICE; }
-		m.stream = ss.stream; m.ev0 = ss.ev[0]; m.ev1 = ss.ev[1]; m.ev2 = ss.ev[2]; m.ev3 = ss.ev[3]; m.ev_group = ss.ev[4]; m.ev_upload = ss.ev[5];
+		if (!streamset_take(dev, ss)) { msg = "could not create the table's stream and events"; return WHAMD_ERR_DEVICE; }
+		m.adopt(ss);
 	}
 	m.release();
-	const uint32_t n = p.n_cols;
-	if (n == 0) return WHAMD_OK;
+	return WHAMD_OK;
+}
+
+// The kernels (templated or wide), the forward path (slot runs, LDS-resident runs, per column) and its plan.  Produces b.force_keys and b.free_b, decides where the superreads
+// are made, and fills the problem's lazy term lists where the chosen path reads them.
+whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::string& msg) {
+	Impl& m = *this;
 	// pedigrees beyond the templated kernels (three trios, more than six individuals): the generic per-column kernel, key path only
 	m.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
 	if (m.wide && (p.T > (uint32_t)MAX_T_WIDE || p.n_ind > (uint32_t)MAX_IND_WIDE)) {
@@ -347,9 +541,8 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 	// ... and a column with more allele-assignment terms than the templated kernels stage in LDS (genotypes not trusted, seven and more
 	// individuals): the generic kernel reads them from global memory
 	for (uint32_t c = 0; c < p.n_cols && !m.wide; ++c) m.wide = p.term_end(c, p.T - 1) - p.term_begin(c, 0) > (uint64_t)COL_MAXTERMS;
-	const bool force_keys = m.path == "column_keys" || m.wide;
+	b.force_keys = m.path == "column_keys" || m.wide;
 	const bool want_resident = (m.path == "auto" || m.path == "resident") && !m.wide;
-	const auto tu0 = std::chrono::steady_clock::now();
 	size_t free_b = 0, total_b = 0;
 	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	if (free_b < total_b / 2) {   // a genotyping call of this process may be holding its column store (genotype.h): give it back first
@@ -361,7 +554,8 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 		devpool_release();
 		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	}
-	free_b += arena_idle_bytes(device);   // (taken below, or freed before this table's own arena is allocated)
+	free_b += arena_idle_bytes(m.device);   // (taken by take_solve_buffers, or freed before this table's own arena is allocated)
+	b.free_b = free_b;
 	// A wide single-individual table (coverage >= 18: 128 and more workgroups per launch) that will share its launches with many others
 	// takes EIGHT cells per thread and twelve local slots: half the wavefronts per table and longer runs -- 24 coverage-20 tables
 	// 7.7 M columns/s instead of 6.4 M; alone the same table is slower that way (1.87 M against 2.26 M), and narrow tables gain nothing.
@@ -384,7 +578,7 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 		if (st != WHAMD_OK) return st;
 	}
 	if (m.use_slots) {
-		// the driver below walks plan.steps / plan.component_first_step; slot runs are steps of kind 2
+		// the driver walks plan.steps / plan.component_first_step; slot runs are steps of kind 2
 		m.plan = ResidentPlan();
 		m.plan.steps = m.splan.steps;
 		m.plan.component_first_step = m.splan.component_first_step;
@@ -393,80 +587,48 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 		m.splan = SlotPlan();
 		plan_forward(p, want_resident, m.l_pref, m.fold, m.plan, m.symmetry);
 	}
-	const auto tu1 = std::chrono::steady_clock::now();
-	if (debug_env("WHAMD_DEBUG_PLAN")) {
-		for (const Step& st : m.plan.steps) {
-			if (st.kind == 0) { fprintf(stderr, "[plan] column %u k=%u b=%u f=%u\n", st.index, p.k[st.index], p.b[st.index], p.f[st.index]); continue; }
-			if (st.kind == 2) {
-				const SlotRun& r = m.splan.runs[st.index];
-				fprintf(stderr, "[plan] slot run c0=%u ncols=%u g=%u L=%u half=%u ends=%u has_prev=%u in_identity=%u in_half=%u mirror_pos=%u in_occ=%x out_occ=%x mirror_out=%u\n",
-				        r.c0, r.ncols, r.g, r.L, r.half, r.n_ends, r.has_prev, r.in_identity, r.in_half, r.in_mirror_pos, r.in_occ, r.out_occ, r.mirror_out);
-				if (m.splan.ped) fprintf(stderr, "[plan]   pedigree run: T=%u forms per value=%u table words=%u record words per workgroup=%u\n", 1u << m.splan.pextra[st.index].tb,
-				                         m.splan.pextra[st.index].nf, m.splan.pextra[st.index].s_off + r.ncols * 64u * pslot_ns(m.splan.pextra[st.index].nf), m.splan.pextra[st.index].rec_words);
-				continue;
-			}
-			const ResSegment& sgm = m.plan.segments[st.index];
-			fprintf(stderr, "[plan] run c0=%u ncols=%u g=%u threads=%u max_l=%u stage_words=%u\n", sgm.c0, sgm.ncols, sgm.g, sgm.threads, sgm.max_l, sgm.stage_words);
-			for (uint32_t i = 0; i < sgm.ncols; ++i) {
-				const ResColumn& rc = m.plan.columns[sgm.col_off + i];
-				const ResBacktrace& rb = m.plan.backtrace[sgm.col_off + i];
-				fprintf(stderr, "[plan]   col %u mode=%u nfold=%u Lb=%u Lf=%u ebits=%u epos0=%u nthr=%u stage_off=%u nwords=%u | bt layout=%u n_g=%u n_l=%u\n",
-				        sgm.c0 + i, rc.mode, rc.nfold, rc.Lb, rc.Lf, rc.ebits, rc.epos[0], rc.nthr, rc.stage_off, rc.nwords, rb.layout, rb.n_g, rb.n_l);
-			}
+	// The superreads of a single-individual table with trusted genotypes are made on the device, behind the backtrace (the condition is finish_columns' first branch).
+	m.device_superreads = p.n_ind == 1 && p.T == 1 && p.P == 2 && !p.distrust && p.h2p.size() >= 2 && p.h2p[0] == 0 && p.h2p[1] == 1 && p.genotype.size() >= p.n_cols &&
+	                      !debug_env("WHAMD_HOST_SUPERREADS");
+	return WHAMD_OK;
+}
+
+// WHAMD_DEBUG_PLAN (debug library): the chosen plan, one line per step.
+void DeviceTable::Impl::dump_plan(const Problem& p) const {
+	const Impl& m = *this;
+	for (const Step& st : m.plan.steps) {
+		if (st.kind == 0) { fprintf(stderr, "[plan] column %u k=%u b=%u f=%u\n", st.index, p.k[st.index], p.b[st.index], p.f[st.index]); continue; }
+		if (st.kind == 2) {
+			const SlotRun& r = m.splan.runs[st.index];
+			fprintf(stderr, "[plan] slot run c0=%u ncols=%u g=%u L=%u half=%u ends=%u has_prev=%u in_identity=%u in_half=%u mirror_pos=%u in_occ=%x out_occ=%x mirror_out=%u\n",
+			        r.c0, r.ncols, r.g, r.L, r.half, r.n_ends, r.has_prev, r.in_identity, r.in_half, r.in_mirror_pos, r.in_occ, r.out_occ, r.mirror_out);
+			if (m.splan.ped) fprintf(stderr, "[plan]   pedigree run: T=%u forms per value=%u table words=%u record words per workgroup=%u\n", 1u << m.splan.pextra[st.index].tb,
+			                         m.splan.pextra[st.index].nf, m.splan.pextra[st.index].s_off + r.ncols * 64u * pslot_ns(m.splan.pextra[st.index].nf), m.splan.pextra[st.index].rec_words);
+			continue;
+		}
+		const ResSegment& sgm = m.plan.segments[st.index];
+		fprintf(stderr, "[plan] run c0=%u ncols=%u g=%u threads=%u max_l=%u stage_words=%u\n", sgm.c0, sgm.ncols, sgm.g, sgm.threads, sgm.max_l, sgm.stage_words);
+		for (uint32_t i = 0; i < sgm.ncols; ++i) {
+			const ResColumn& rc = m.plan.columns[sgm.col_off + i];
+			const ResBacktrace& rb = m.plan.backtrace[sgm.col_off + i];
+			fprintf(stderr, "[plan]   col %u mode=%u nfold=%u Lb=%u Lf=%u ebits=%u epos0=%u nthr=%u stage_off=%u nwords=%u | bt layout=%u n_g=%u n_l=%u\n",
+			        sgm.c0 + i, rc.mode, rc.nfold, rc.Lb, rc.Lf, rc.ebits, rc.epos[0], rc.nthr, rc.stage_off, rc.nwords, rb.layout, rb.n_g, rb.n_l);
 		}
 	}
-	const uint32_t tbits = 2 * p.n_triples;
-	const uint32_t ni = std::max<uint32_t>(p.n_ind, 1);
-	const bool timing = getenv("WHAMD_DEBUG_TIMING") != nullptr;
-	auto lap_t = std::chrono::steady_clock::now();
-	auto ulap = [&](const char* what) {
-		if (!timing) return;
-		const auto now = std::chrono::steady_clock::now();
-		fprintf(stderr, "[whamd timing]   upload: %s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - lap_t).count());
-		lap_t = now;
-	};
-	// ---- descriptors
-	m.cols.resize(n);
-	std::vector<uint32_t> segs;
-	RawVec<uint32_t> term_ptr32((size_t)n * (p.T + 1));
-	static_assert(sizeof(CostTerm) == sizeof(DevTerm), "Problem::terms / fterms are uploaded as they are");
-	const RawVec<CostTerm>& terms = p.terms;
+}
+
+// What a column's descriptor holds by itself, and its 32-bit term offsets (b.term_ptr32): a few host threads.  Fails if the problem exceeds 32-bit offsets.  Host only.
+whamd_status_t DeviceTable::Impl::describe_columns(const Problem& p, TableBuild& b, std::string& msg) {
+	Impl& m = *this;
+	const uint32_t n = b.n, ni = b.ni, tbits = b.tbits;
 	if (p.terms.size() >= 0xFFFFFFFFull || (uint64_t)p.col_ptr[n] * ni >= 0xFFFFFFFFull) {
 		msg = "problem too large for 32-bit device offsets";
 		return WHAMD_ERR_UNSUPPORTED;
 	}
-	uint64_t bt = 0, seg_bt = 0;
-	size_t seg_cursor = 0, slot_cursor = 0;
-	uint32_t max_f = 0, max_keys_f = 0;
-	// what the arena may take: free HBM minus the descriptors (~1 KiB per column), exchange buffers, tables and slack
-	const uint64_t reserve = (3ull << 30) + (uint64_t)n * 1024ull + m.table_bytes;
-	const bool ped_slots = m.use_slots && m.splan.ped;
-	auto slot_record_bytes = [&](size_t ri) -> uint64_t {   // record of one slot run: only launched workgroups write
-		const SlotRun& run = m.splan.runs[ri];
-		if (ped_slots) return (uint64_t)m.splan.pextra[ri].rec_words * 4ull << run.g;
-		return (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half));
-	};
-	uint64_t arena_cap = free_b > reserve ? free_b - reserve : 0;
-	if (m.arena_limit) arena_cap = std::min<uint64_t>(arena_cap, m.arena_limit);
-	std::vector<uint32_t> window_first_col;   // first column of every window after the first
-	uint64_t bt_max = 0;
-	auto open_unit = [&](uint32_t c, uint64_t bytes) -> bool {   // a backtrace unit of `bytes` starts at column c
-		if (bytes + 16 > arena_cap) return false;
-		if (bt + bytes + 16 > arena_cap) {
-			bt_max = std::max(bt_max, bt);
-			bt = 0;
-			window_first_col.push_back(c);
-		}
-		return true;
-	};
-	auto unit_too_large = [&](uint32_t c) {
-		msg = "the backtrace record of the unit at column " + std::to_string(c) + " alone does not fit in the arena (" + std::to_string(arena_cap >> 20) +
-		      " MiB of " + std::to_string(free_b >> 20) + " MiB free HBM)";
-		return WHAMD_ERR_UNSUPPORTED;
-	};
-	// what a column's descriptor holds by itself: a few host threads; the offsets that run through the table (segment lists,
-	// backtrace records, windows) follow in column order
-	parallel_ranges(n, host_threads(n, 16384), [&](uint64_t c0, uint64_t c1, uint32_t) {
+	m.cols.resize(n);
+	b.term_ptr32.resize((size_t)n * (p.T + 1));
+	RawVec<uint32_t>& term_ptr32 = b.term_ptr32;
+	parallel_ranges(n, host_threads(n, 16384), [&m, &p, &term_ptr32, n, ni, tbits](uint64_t c0, uint64_t c1, uint32_t) {
 		for (uint32_t c = (uint32_t)c0; c < (uint32_t)c1; ++c) {
 			DevColumn d{};
 			d.k = p.k[c];
@@ -483,6 +645,46 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 			m.cols[c] = d;
 		}
 	});
+	return WHAMD_OK;
+}
+
+// The offsets that run through the table, in column order: segment lists (b.segs), the place of every backtrace unit's record in the arena (DevColumn::bt_off, the
+// runs' rec / bt words), the windows where the arena is smaller than the records (b.window_first_col).  Produces b.arena_cap, b.bt, b.max_f, b.max_keys_f,
+// b.exchange_bytes; fails if a unit or the whole does not fit.  Host only.
+whamd_status_t DeviceTable::Impl::lay_out_arena(const Problem& p, TableBuild& b, std::string& msg) {
+	Impl& m = *this;
+	const uint32_t n = b.n;
+	const bool ped_slots = b.ped_slots;
+	std::vector<uint32_t>& segs = b.segs;
+	uint64_t bt = 0, seg_bt = 0;
+	size_t seg_cursor = 0, slot_cursor = 0;
+	uint32_t max_f = 0, max_keys_f = 0;
+	// what the arena may take: free HBM minus the descriptors (~1 KiB per column), exchange buffers, tables and slack
+	const uint64_t reserve = (3ull << 30) + (uint64_t)n * 1024ull + m.table_bytes;
+	auto slot_record_bytes = [&m, ped_slots](size_t ri) -> uint64_t {   // record of one slot run: only launched workgroups write
+		const SlotRun& run = m.splan.runs[ri];
+		if (ped_slots) return (uint64_t)m.splan.pextra[ri].rec_words * 4ull << run.g;
+		return (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half));
+	};
+	uint64_t arena_cap = b.free_b > reserve ? b.free_b - reserve : 0;
+	if (m.arena_limit) arena_cap = std::min<uint64_t>(arena_cap, m.arena_limit);
+	b.arena_cap = arena_cap;
+	std::vector<uint32_t>& window_first_col = b.window_first_col;
+	uint64_t bt_max = 0;
+	auto open_unit = [&bt, &bt_max, &window_first_col, arena_cap](uint32_t c, uint64_t bytes) -> bool {   // a backtrace unit of `bytes` starts at column c
+		if (bytes + 16 > arena_cap) return false;
+		if (bt + bytes + 16 > arena_cap) {
+			bt_max = std::max(bt_max, bt);
+			bt = 0;
+			window_first_col.push_back(c);
+		}
+		return true;
+	};
+	auto unit_too_large = [&msg, &b](uint32_t c) {
+		msg = "the backtrace record of the unit at column " + std::to_string(c) + " alone does not fit in the arena (" + std::to_string(b.arena_cap >> 20) +
+		      " MiB of " + std::to_string(b.free_b >> 20) + " MiB free HBM)";
+		return WHAMD_ERR_UNSUPPORTED;
+	};
 	for (uint32_t c = 0; c < n; ++c) {
 		DevColumn& d = m.cols[c];
 		const bool in_slot_run = m.use_slots && m.splan.col_to_row[c] >= 0;   // (the run kernels read none of the per-column arrays)
@@ -521,7 +723,7 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 			}
 			d.bt_off = seg_bt;
 		} else {
-			const bool fused_ok = !force_keys && !d.is_last && d.f >= 6 && d.ebits <= (uint32_t)QMAX;
+			const bool fused_ok = !b.force_keys && !d.is_last && d.f >= 6 && d.ebits <= (uint32_t)QMAX;
 			d.mode = fused_ok ? 0u : 1u;
 			const uint64_t bytes = d.mode == 0 ? (uint64_t)d.nplanes * p.T * (1ull << (d.f - 6)) * 8ull : (uint64_t)p.T * (1ull << d.f) * 4ull;
 			if (!open_unit(c, bytes)) return unit_too_large(c);
@@ -532,291 +734,232 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 		bt = (bt + 15ull) & ~15ull;
 		max_f = std::max(max_f, d.f);
 	}
-	ulap("column descriptors (host)");
-	bt = bt_max = std::max(bt_max, bt);
+	b.laps.lap("column descriptors (host)");
+	bt = std::max(bt_max, bt);
+	b.bt = bt;
+	b.max_f = max_f;
+	b.max_keys_f = max_keys_f;
+	b.exchange_bytes = (size_t)(1ull << max_f) * p.T * 4;
 	m.bt_bytes = bt;
 	m.windowed = !window_first_col.empty();
-	m.checkpoint_bytes = (size_t)(1ull << max_f) * p.T * 4;
-	const uint64_t need = bt + (2ull + window_first_col.size()) * (1ull << max_f) * p.T * 4ull + (1ull << max_keys_f) * p.T * 8ull;
-	if (need + (1ull << 30) > free_b) {
-		msg = "backtrace arena of " + std::to_string(need >> 20) + " MiB does not fit in free HBM (" + std::to_string(free_b >> 20) + " MiB)";
+	m.checkpoint_bytes = b.exchange_bytes;
+	const uint64_t need = bt + (2ull + window_first_col.size()) * b.exchange_bytes + (1ull << max_keys_f) * p.T * 8ull;
+	if (need + (1ull << 30) > b.free_b) {
+		msg = "backtrace arena of " + std::to_string(need >> 20) + " MiB does not fit in free HBM (" + std::to_string(b.free_b >> 20) + " MiB)";
 		return WHAMD_ERR_UNSUPPORTED;
 	}
-	// ---- allocate + upload
-	// Everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the solve behind ev_upload.
-	// WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.
-	hipStream_t us = debug_env("WHAMD_UPLOAD_ON_TABLE_STREAM") ? nullptr : upload_stream_of(device);
-	if (!us) us = m.stream;
-	m.upload_stream = us;
-	if (us == m.stream) m.own_stream_used = true;
-	StageSession stage(us);
-	ulap("staging area taken");
-	auto alloc = [&](void** dptr, size_t bytes) -> hipError_t {
-		size_t got = 0;
-		hipError_t e = devpool_take(device, std::max<size_t>(bytes, 16), dptr, &got);
-		if (e == hipSuccess) m.allocations.emplace_back(*dptr, got);
-		return e;
-	};
-	std::vector<int32_t> delta_fallback;
+	return WHAMD_OK;
+}
+
+// An upper bound of what the phases below hand to TableUploader::up (the size of the table's device block and staging image).
+size_t DeviceTable::Impl::upload_bound(const Problem& p, const TableBuild& b) const {
+	const Impl& m = *this;
+	const size_t delta_count = p.n_ind == 0 ? std::max<size_t>(p.col_ptr[b.n], 1) : (size_t)p.col_ptr[b.n] * p.n_ind;
+	const size_t super_upload = m.device_superreads ? ((size_t)b.n + 1) * 8 + b.n + 1024 : 0;
+	return m.cols.size() * sizeof(DevColumn) + delta_count * sizeof(int32_t) + b.term_ptr32.size() * 4 + (p.terms.size() + p.fterms.size()) * sizeof(DevTerm) + b.segs.size() * 4 +
+	       m.plan.columns.size() * (sizeof(ResColumn) + sizeof(ResBacktrace) + sizeof(PedColumn)) + m.plan.ped_terms.size() * sizeof(PedTerm) +
+	       (m.splan.rows.size() + SLOT_ROW_PAD) * sizeof(SlotRow) + m.splan.prows.size() * sizeof(PedSlotRow) + m.splan.bt_cols.size() * (sizeof(SlotBtCol) + 8) +
+	       m.splan.runs.size() * (sizeof(SlotRun) + sizeof(PedSlotExtra) + sizeof(BtUnit) + sizeof(SlotBatchEntry) + 64) + m.plan.segments.size() * (sizeof(ResBatchEntry) + sizeof(BtUnit)) + super_upload + ((size_t)8 << 20);
+}
+
+// The per-column arrays (descriptors, deltas, term offsets, terms -- whole, or only the columns outside slot runs), the superread inputs, segment lists and the
+// descriptors of the LDS-resident runs.
+whamd_status_t DeviceTable::Impl::upload_column_arrays(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	const uint32_t n = b.n;
+	static_assert(sizeof(CostTerm) == sizeof(DevTerm), "Problem::terms / fterms are uploaded as they are");
+	const RawVec<CostTerm>& terms = p.terms;
 	const int32_t* delta_src = p.delta.data();
 	size_t delta_count = (size_t)p.col_ptr[n] * p.n_ind;
-	if (p.n_ind == 0) { delta_fallback.assign(std::max<size_t>(p.col_ptr[n], 1), 0); delta_src = delta_fallback.data(); delta_count = delta_fallback.size(); }
-	void *d_delta, *d_term_ptr, *d_terms, *d_segs, *d_bt, *d_keys, *d_last_keys, *d_rcol, *d_rbt, *d_fterms = nullptr;
-	// The superreads of a single-individual table with trusted genotypes are made on the device, behind the backtrace (the condition is finish_columns' first branch).
-	m.device_superreads = n > 0 && p.n_ind == 1 && p.T == 1 && p.P == 2 && !p.distrust && p.h2p.size() >= 2 && p.h2p[0] == 0 && p.h2p[1] == 1 && p.genotype.size() >= n &&
-	                      !debug_env("WHAMD_HOST_SUPERREADS");
-	const size_t super_upload = m.device_superreads ? ((size_t)n + 1) * 8 + n + 1024 : 0;
-	const size_t upload_bytes = m.cols.size() * sizeof(DevColumn) + delta_count * sizeof(int32_t) + term_ptr32.size() * 4 + (terms.size() + p.fterms.size()) * sizeof(DevTerm) + segs.size() * 4 +
-	             m.plan.columns.size() * (sizeof(ResColumn) + sizeof(ResBacktrace) + sizeof(PedColumn)) + m.plan.ped_terms.size() * sizeof(PedTerm) +
-	             (m.splan.rows.size() + SLOT_ROW_PAD) * sizeof(SlotRow) + m.splan.prows.size() * sizeof(PedSlotRow) + m.splan.bt_cols.size() * (sizeof(SlotBtCol) + 8) +
-	             m.splan.runs.size() * (sizeof(SlotRun) + sizeof(PedSlotExtra) + sizeof(BtUnit) + sizeof(SlotBatchEntry) + 64) + m.plan.segments.size() * (sizeof(ResBatchEntry) + sizeof(BtUnit)) + super_upload + ((size_t)8 << 20);
-	stage.expect(upload_bytes);
-	// ONE device block and ONE staging image per table: every uploaded array is a piece of the block at the offset it has in the pinned area, and the pieces
-	// leave as a few large copies.  (Per-array copies of ~1 MB ran at 25 GB/s -- 96 coverage-15 tables, 28 MB each, spent their creates waiting for the link --;
-	// pieces of 32 MB and more reach 56 GB/s: scripts/micro/r6_h2d_rate.py.)
-	char* d_slab = nullptr;
-	size_t slab_cap = 0, slab_used = 0, slab_flushed = 0;
-	if (upload_bytes <= STAGE_MAX && !debug_env("WHAMD_NO_UPLOAD_SLAB") && stage.begin_image(upload_bytes)) {
-		void* ptr = nullptr;
-		if (alloc(&ptr, upload_bytes) == hipSuccess) { d_slab = (char*)ptr; slab_cap = upload_bytes; }
-		else { (void)hipGetLastError(); stage.image = false; }
-	}
-	ulap("staging image sized, device block taken");
-	bool unstaged_copies = false;   // a copy whose source is pageable memory of this call: the create must wait for it
-	const hipStream_t copy_stream = us;   // (all tables' images on ONE shared stream instead of sixteen at once was measured: 1 055 - 1 273 against 1 015 - 1 153 creates/s, noise)
-	auto flush_slab = [&]() -> hipError_t {
-		if (!d_slab || slab_used == slab_flushed) return hipSuccess;
-		// (WHAMD_SKIP_SLAB_COPY=1, debug library, RESULTS INVALID: the image is built but does not travel -- what the creates cost without the link)
-		const hipError_t e = debug_env("WHAMD_SKIP_SLAB_COPY") ? hipSuccess : hipMemcpyAsync(d_slab + slab_flushed, stage.base + slab_flushed, slab_used - slab_flushed, hipMemcpyHostToDevice, copy_stream);
-		stage.pending = true;
-		slab_flushed = slab_used;
-		return e;
-	};
-	auto up = [&](void** dptr, const void* src, size_t bytes) -> hipError_t {
-		const size_t padded = (bytes + 255) & ~(size_t)255;
-		if (d_slab && slab_used + padded <= slab_cap) {
-			*dptr = d_slab + slab_used;
-			char* at = stage.base + slab_used;
-			const char* from = (const char*)src;
-			if (bytes >= ((size_t)4 << 20)) parallel_ranges(bytes, host_threads(bytes, (size_t)2 << 20), [&](uint64_t b0, uint64_t b1, uint32_t) { std::memcpy(at + b0, from + b0, b1 - b0); });
-			else if (bytes) std::memcpy(at, from, bytes);
-			slab_used += padded;
-			stage.total += padded;
-			return slab_used - slab_flushed >= ((size_t)32 << 20) ? flush_slab() : hipSuccess;
-		}
-		hipError_t e = alloc(dptr, bytes);
-		if (e != hipSuccess) return e;
-		if (bytes) e = stage.copy(*dptr, src, bytes);
-		if (bytes && stage.image) unstaged_copies = true;   // (did not fit the image: copied straight from the caller's memory)
-		return e;
-	};
+	if (p.n_ind == 0) { b.delta_fallback.assign(std::max<size_t>(p.col_ptr[n], 1), 0); delta_src = b.delta_fallback.data(); delta_count = b.delta_fallback.size(); }
 	// A single-individual table on slot runs: no kernel reads the per-column arrays (descriptor, deltas, term offsets, terms) of a column INSIDE a run -- the run
 	// kernels and slot_tables work from the rows, the backtrace from its units -- so only the columns outside runs travel (the coverage ramp, the last column, what an
 	// irregular layout leaves between runs): 96 of a column's 450 bytes, and concurrent creates are bound by bytes through the link.  The arrays keep
 	// their size and indexing on the device; the pieces that are not sent are never read.
-	std::vector<std::pair<uint32_t, uint32_t>> sent;   // [first, last) column ranges that are uploaded
-	const bool sparse_columns = m.use_slots && !ped_slots && p.T == 1 && !m.windowed && !debug_env("WHAMD_DENSE_COLUMN_UPLOAD");
+	const bool sparse_columns = m.use_slots && !b.ped_slots && p.T == 1 && !m.windowed && !debug_env("WHAMD_DENSE_COLUMN_UPLOAD");
 	if (sparse_columns) {
+		std::vector<std::pair<size_t, size_t>> pc_cols, pc_delta, pc_tptr, pc_terms;   // byte ranges of the columns [c, e) outside runs
 		for (uint32_t c = 0; c < n;) {
 			if (m.splan.col_to_row[c] >= 0) { ++c; continue; }
 			uint32_t e = c + 1;
 			while (e < n && m.splan.col_to_row[e] < 0) ++e;
-			sent.emplace_back(c, e);
+			pc_cols.emplace_back((size_t)c * sizeof(DevColumn), (size_t)e * sizeof(DevColumn));
+			pc_delta.emplace_back((size_t)p.col_ptr[c] * p.n_ind * sizeof(int32_t), (size_t)p.col_ptr[e] * p.n_ind * sizeof(int32_t));
+			pc_tptr.emplace_back((size_t)c * (p.T + 1) * sizeof(uint32_t), (size_t)e * (p.T + 1) * sizeof(uint32_t));
+			pc_terms.emplace_back((size_t)p.term_ptr[(size_t)c * p.T] * sizeof(DevTerm), (size_t)p.term_ptr[(size_t)e * p.T] * sizeof(DevTerm));
 			c = e;
 		}
-	}
-	// reserves [count x elem] bytes like `up`, sends only the element ranges of `pieces` (element index = f(column))
-	auto up_pieces = [&](void** dptr, const void* src, size_t bytes, const std::vector<std::pair<size_t, size_t>>& pieces) -> hipError_t {
-		const size_t padded = (bytes + 255) & ~(size_t)255;
-		const bool in_slab = d_slab && slab_used + padded <= slab_cap;
-		if (in_slab) {
-			hipError_t e = flush_slab();   // what is staged so far leaves as it is; this array's pieces go out on their own
-			if (e != hipSuccess) return e;
-			*dptr = d_slab + slab_used;
-			slab_used += padded;
-			slab_flushed = slab_used;      // (nothing of this array is in the staging image)
-		} else {
-			hipError_t e = alloc(dptr, bytes);
-			if (e != hipSuccess) return e;
-		}
-		const size_t image_at = slab_used - padded;   // (in_slab: where the array lies in the block AND in the staging image)
-		for (const auto& pc : pieces) {
-			if (pc.second <= pc.first) continue;
-			const char* from = (const char*)src + pc.first;
-			if (in_slab) {   // through the pinned image, like everything else: the copy's source outlives the create
-				std::memcpy(stage.base + image_at + pc.first, from, pc.second - pc.first);
-				from = stage.base + image_at + pc.first;
-				stage.pending = true;
-			} else {
-				unstaged_copies = true;   // (straight from the caller's pageable memory: upload() ends with a host wait)
-			}
-			hipError_t e = hipMemcpyAsync((char*)*dptr + pc.first, from, pc.second - pc.first, hipMemcpyHostToDevice, us);
-			if (e != hipSuccess) return e;
-		}
-		return hipSuccess;
-	};
-	if (sparse_columns) {
-		std::vector<std::pair<size_t, size_t>> pc_cols, pc_delta, pc_tptr, pc_terms;
-		for (const auto& r : sent) {
-			pc_cols.emplace_back((size_t)r.first * sizeof(DevColumn), (size_t)r.second * sizeof(DevColumn));
-			pc_delta.emplace_back((size_t)p.col_ptr[r.first] * p.n_ind * sizeof(int32_t), (size_t)p.col_ptr[r.second] * p.n_ind * sizeof(int32_t));
-			pc_tptr.emplace_back((size_t)r.first * (p.T + 1) * sizeof(uint32_t), (size_t)r.second * (p.T + 1) * sizeof(uint32_t));
-			pc_terms.emplace_back((size_t)p.term_ptr[(size_t)r.first * p.T] * sizeof(DevTerm), (size_t)p.term_ptr[(size_t)r.second * p.T] * sizeof(DevTerm));
-		}
-		HIP_TRY(up_pieces((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn), pc_cols));
+		HIP_TRY(up.up_pieces((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn), pc_cols));
 		// (the deltas travel whole when the device makes the superreads: superreads_single reads every column's)
-		if (m.device_superreads) HIP_TRY(up(&d_delta, delta_src, delta_count * sizeof(int32_t)));
-		else HIP_TRY(up_pieces(&d_delta, delta_src, delta_count * sizeof(int32_t), pc_delta));
-		HIP_TRY(up_pieces(&d_term_ptr, term_ptr32.data(), term_ptr32.size() * sizeof(uint32_t), pc_tptr));
-		HIP_TRY(up_pieces(&d_terms, terms.data(), terms.size() * sizeof(DevTerm), pc_terms));
+		if (m.device_superreads) HIP_TRY(up.up((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t)));
+		else HIP_TRY(up.up_pieces((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t), pc_delta));
+		HIP_TRY(up.up_pieces((void**)&m.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t), pc_tptr));
+		HIP_TRY(up.up_pieces((void**)&m.dp.terms, terms.data(), terms.size() * sizeof(DevTerm), pc_terms));
 	} else {
-	HIP_TRY(up((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn)));
-	HIP_TRY(up(&d_delta, delta_src, delta_count * sizeof(int32_t)));
-	HIP_TRY(up(&d_term_ptr, term_ptr32.data(), term_ptr32.size() * sizeof(uint32_t)));
-	HIP_TRY(up(&d_terms, terms.data(), terms.size() * sizeof(DevTerm)));
+		HIP_TRY(up.up((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn)));
+		HIP_TRY(up.up((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t)));
+		HIP_TRY(up.up((void**)&m.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t)));
+		HIP_TRY(up.up((void**)&m.dp.terms, terms.data(), terms.size() * sizeof(DevTerm)));
 	}
+	m.dp.cols = m.d_cols;
 	if (m.device_superreads) {
-		void *d_cp = nullptr, *d_geno = nullptr;
-		HIP_TRY(up(&d_cp, p.col_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t)));
-		HIP_TRY(up(&d_geno, p.genotype.data(), (size_t)n));
 		m.super_args = SuperreadArgs{};
-		m.super_args.delta = (const int32_t*)d_delta;
-		m.super_args.col_ptr = (const unsigned long long*)d_cp;
-		m.super_args.genotype = (const uint8_t*)d_geno;
+		HIP_TRY(up.up((void**)&m.super_args.col_ptr, p.col_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t)));
+		HIP_TRY(up.up((void**)&m.super_args.genotype, p.genotype.data(), (size_t)n));
+		m.super_args.delta = m.dp.delta;
 		m.super_args.n_cols = n;
 		m.super_words = (size_t)n + ((size_t)2 * n + 3) / 4;
 	}
-	if (!p.fterms.empty()) HIP_TRY(up(&d_fterms, p.fterms.data(), p.fterms.size() * sizeof(DevTerm)));   // factorised lines (pedslot_tables, PSLOT_FACT)
-	HIP_TRY(up(&d_segs, segs.data(), segs.size() * sizeof(uint32_t)));
-	HIP_TRY(up(&d_rcol, m.plan.columns.data(), m.plan.columns.size() * sizeof(ResColumn)));
-	HIP_TRY(up(&d_rbt, m.plan.backtrace.data(), m.plan.backtrace.size() * sizeof(ResBacktrace)));
-	void *d_pcol = nullptr, *d_pterm = nullptr;
+	b.d_fterms = nullptr;
+	if (!p.fterms.empty()) HIP_TRY(up.up((void**)&b.d_fterms, p.fterms.data(), p.fterms.size() * sizeof(DevTerm)));   // factorised lines (pedslot_tables, PSLOT_FACT)
+	HIP_TRY(up.up((void**)&m.dp.segs, b.segs.data(), b.segs.size() * sizeof(uint32_t)));
+	HIP_TRY(up.up((void**)&m.dp.res_cols, m.plan.columns.data(), m.plan.columns.size() * sizeof(ResColumn)));
+	HIP_TRY(up.up((void**)&m.dp.res_bt, m.plan.backtrace.data(), m.plan.backtrace.size() * sizeof(ResBacktrace)));
 	m.plan.ped_columns.resize(m.plan.ped_columns.empty() ? 0 : m.plan.columns.size());
-	HIP_TRY(up(&d_pcol, m.plan.ped_columns.data(), m.plan.ped_columns.size() * sizeof(PedColumn)));
-	HIP_TRY(up(&d_pterm, m.plan.ped_terms.data(), m.plan.ped_terms.size() * sizeof(PedTerm)));
-	m.dp.ped_cols = (const PedColumn*)d_pcol;
-	m.dp.ped_terms = (const PedTerm*)d_pterm;
-	ulap("column arrays: allocations + copies");
-	// slot runs: per-column descriptors and the backtrace blobs ([ncols] SlotBtCol + ending slots per run)
-	RawVec<uint32_t> slot_blob;
-	std::vector<uint32_t> slot_blob_off(m.splan.runs.size(), 0), slot_blob_words(m.splan.runs.size(), 0);
-	{
-		// offsets first (one pass over the runs), then every run copies its own piece (8 MB for configs[2]: 0.9 ms when it was one growing vector)
-		size_t words = 0;
-		for (size_t ri = 0; ri < m.splan.runs.size(); ++ri) {
+	HIP_TRY(up.up((void**)&m.dp.ped_cols, m.plan.ped_columns.data(), m.plan.ped_columns.size() * sizeof(PedColumn)));
+	HIP_TRY(up.up((void**)&m.dp.ped_terms, m.plan.ped_terms.data(), m.plan.ped_terms.size() * sizeof(PedTerm)));
+	b.laps.lap("column arrays: allocations + copies");
+	return WHAMD_OK;
+}
+
+// Slot runs: the backtrace blob ([ncols] SlotBtCol + ending slots per run) and where every run's piece lies in it (b.slot_blob_off / _words).  Host only.
+void DeviceTable::Impl::build_slot_blobs(TableBuild& b) const {
+	const Impl& m = *this;
+	b.slot_blob_off.assign(m.splan.runs.size(), 0);
+	b.slot_blob_words.assign(m.splan.runs.size(), 0);
+	// offsets first (one pass over the runs), then every run copies its own piece (8 MB for configs[2]: 0.9 ms when it was one growing vector)
+	size_t words = 0;
+	for (size_t ri = 0; ri < m.splan.runs.size(); ++ri) {
+		const SlotRun& run = m.splan.runs[ri];
+		b.slot_blob_off[ri] = (uint32_t)words;
+		b.slot_blob_words[ri] = (uint32_t)((size_t)run.ncols * (sizeof(SlotBtCol) / 4) + (run.n_ends + 3) / 4 + 1);
+		words += b.slot_blob_words[ri];
+	}
+	b.slot_blob.resize(words);
+	uint32_t* blob = b.slot_blob.data();
+	const uint32_t* blob_off = b.slot_blob_off.data();
+	parallel_ranges(m.splan.runs.size(), host_threads(m.splan.runs.size(), 512), [&m, blob, blob_off](uint64_t r0, uint64_t r1, uint32_t) {
+		for (size_t ri = r0; ri < r1; ++ri) {
 			const SlotRun& run = m.splan.runs[ri];
-			slot_blob_off[ri] = (uint32_t)words;
-			slot_blob_words[ri] = (uint32_t)((size_t)run.ncols * (sizeof(SlotBtCol) / 4) + (run.n_ends + 3) / 4 + 1);
-			words += slot_blob_words[ri];
+			uint32_t* dst = blob + blob_off[ri];
+			const size_t col_words = (size_t)run.ncols * (sizeof(SlotBtCol) / 4);
+			std::memcpy(dst, m.splan.bt_cols.data() + run.row_off, col_words * 4);
+			const size_t end_words = (run.n_ends + 3) / 4 + 1;
+			std::memset(dst + col_words, 0, end_words * 4);
+			if (run.n_ends) std::memcpy(dst + col_words, m.splan.end_slots.data() + m.splan.end_off[ri], run.n_ends);
 		}
-		slot_blob.resize(words);
-		parallel_ranges(m.splan.runs.size(), host_threads(m.splan.runs.size(), 512), [&](uint64_t r0, uint64_t r1, uint32_t) {
-			for (size_t ri = r0; ri < r1; ++ri) {
-				const SlotRun& run = m.splan.runs[ri];
-				uint32_t* dst = slot_blob.data() + slot_blob_off[ri];
-				const size_t col_words = (size_t)run.ncols * (sizeof(SlotBtCol) / 4);
-				std::memcpy(dst, m.splan.bt_cols.data() + run.row_off, col_words * 4);
-				const size_t end_words = (run.n_ends + 3) / 4 + 1;
-				std::memset(dst + col_words, 0, end_words * 4);
-				if (run.n_ends) std::memcpy(dst + col_words, m.splan.end_slots.data() + m.splan.end_off[ri], run.n_ends);
-			}
-		});
-	}
-	ulap("slot backtrace blobs (host)");
-	void *d_srows = nullptr, *d_sblob = nullptr;
-	if (!m.splan.rows.empty()) m.splan.rows.resize(m.splan.rows.size() + SLOT_ROW_PAD);   // the kernel's scalar-cache warm-up touches a fixed number of rows
-	HIP_TRY(up(&d_srows, m.splan.rows.data(), m.splan.rows.size() * sizeof(SlotRow)));
-	ulap("slot rows: allocation + copy");
-	HIP_TRY(up(&d_sblob, slot_blob.data(), slot_blob.size() * sizeof(uint32_t)));
-	void* d_sctrl = nullptr;
-	HIP_TRY(up(&d_sctrl, m.splan.ctrl.data(), m.splan.ctrl.size() * sizeof(uint32_t)));
-	m.dp.slot_ctrl = (const uint32_t*)d_sctrl;
-	// single-individual slot runs: the prologue's tables (SlotRun::tab_g / tab_w / tab_sl), built on the device below
-	void *d_sruns = nullptr, *d_stab = nullptr;
+	});
+}
+
+// Single-individual slot runs: where the prologue's tables of every run (SlotRun::tab_g / tab_w / tab_sl, an X run's tab_kr / tab_par) lie in the table block that
+// slot_tables fills; marks the X runs.  Returns the block's size in words.  Host only.
+uint64_t DeviceTable::Impl::lay_out_slot_tables(const TableBuild& b) {
+	Impl& m = *this;
 	uint64_t slot_tab_words = 0;
-	if (m.use_slots && !ped_slots) {
-		for (SlotRun& run : m.splan.runs) {
-			auto pad4 = [](uint64_t v) { return (v + 3ull) & ~3ull; };
-			// X runs (kernels_slots.h, slot_runx_body): a Y-form run with four cells per thread whose columns and ending reads fit the kernel's registers; the
-			// rows of its tables are padded with zero columns to a pair of trips
-			const bool xrun = (run.yflags & 1u) && (run.lr == 2u || (run.lr == 3u && !debug_env("WHAMD_NO_XRUN8"))) && run.ncols <= (uint32_t)SLOT_XCOLS &&
-			                  run.n_ends <= (uint32_t)SLOT_XENDS && !debug_env("WHAMD_NO_XRUN");
-			const uint64_t ncp = xrun ? ((run.ncols + 7u) & ~7u) : run.ncols;
-			run.tab_g = (uint32_t)slot_tab_words;
-			slot_tab_words += pad4(ncp << (run.g - run.half));
-			run.tab_w = (uint32_t)slot_tab_words;
-			slot_tab_words += pad4(ncp * (run.threads >> 6));
-			run.tab_sl = (uint32_t)slot_tab_words;
-			slot_tab_words += ncp * 64u;
-			if (xrun) {
-				run.yflags |= 8u;
-				slot_tab_words = (slot_tab_words + 15u) & ~(uint64_t)15;   // (a trip's sixteen Kr words are ONE 64-byte line of the scalar cache)
-				run.tab_kr = (uint32_t)slot_tab_words;
-				slot_tab_words += pad4((((uint64_t)run.ncols + SLOT_XPAD) << run.lr) + run.ncols + SLOT_XPAD);   // Kr words, then one control word per column
-				run.tab_par = (uint32_t)slot_tab_words;
-				slot_tab_words += pad4((uint64_t)run.threads + (1ull << (run.g - run.half)));
-			}
+	for (SlotRun& run : m.splan.runs) {
+		auto pad4 = [](uint64_t v) { return (v + 3ull) & ~3ull; };
+		// X runs (kernels_slots.h, slot_runx_body): a Y-form run with four cells per thread whose columns and ending reads fit the kernel's registers; the
+		// rows of its tables are padded with zero columns to a pair of trips
+		const bool xrun = (run.yflags & 1u) && (run.lr == 2u || (run.lr == 3u && !debug_env("WHAMD_NO_XRUN8"))) && run.ncols <= (uint32_t)SLOT_XCOLS &&
+		                  run.n_ends <= (uint32_t)SLOT_XENDS && !debug_env("WHAMD_NO_XRUN");
+		const uint64_t ncp = xrun ? ((run.ncols + 7u) & ~7u) : run.ncols;
+		run.tab_g = (uint32_t)slot_tab_words;
+		slot_tab_words += pad4(ncp << (run.g - run.half));
+		run.tab_w = (uint32_t)slot_tab_words;
+		slot_tab_words += pad4(ncp * (run.threads >> 6));
+		run.tab_sl = (uint32_t)slot_tab_words;
+		slot_tab_words += ncp * 64u;
+		if (xrun) {
+			run.yflags |= 8u;
+			slot_tab_words = (slot_tab_words + 15u) & ~(uint64_t)15;   // (a trip's sixteen Kr words are ONE 64-byte line of the scalar cache)
+			run.tab_kr = (uint32_t)slot_tab_words;
+			slot_tab_words += pad4((((uint64_t)run.ncols + SLOT_XPAD) << run.lr) + run.ncols + SLOT_XPAD);   // Kr words, then one control word per column
+			run.tab_par = (uint32_t)slot_tab_words;
+			slot_tab_words += pad4((uint64_t)run.threads + (1ull << (run.g - run.half)));
 		}
-		slot_tab_words += (uint64_t)SLOT_XCOLS * 64u;   // (an X run requests the lane parts of SLOT_XCOLS columns whatever its length)
-		if (getenv("WHAMD_DEBUG_TIMING")) {
-			size_t nx = 0, not_y = 0, not_lr = 0, long_run = 0, many_ends = 0;
-			for (const SlotRun& run : m.splan.runs) {
-				nx += (run.yflags & 8u) != 0;
-				not_y += !(run.yflags & 1u); not_lr += run.lr != 2u && run.lr != 3u; long_run += run.ncols > (uint32_t)SLOT_XCOLS; many_ends += run.n_ends > (uint32_t)SLOT_XENDS;
-			}
-			fprintf(stderr, "[whamd timing]   X runs: %zu of %zu (not Y form %zu, cells per thread %zu, more than %d columns %zu, more than %d ending reads %zu)\n", nx, m.splan.runs.size(), not_y,
-			        not_lr, SLOT_XCOLS, long_run, SLOT_XENDS, many_ends);
+	}
+	slot_tab_words += (uint64_t)SLOT_XCOLS * 64u;   // (an X run requests the lane parts of SLOT_XCOLS columns whatever its length)
+	if (b.laps.on) {
+		size_t nx = 0, not_y = 0, not_lr = 0, long_run = 0, many_ends = 0;
+		for (const SlotRun& run : m.splan.runs) {
+			nx += (run.yflags & 8u) != 0;
+			not_y += !(run.yflags & 1u); not_lr += run.lr != 2u && run.lr != 3u; long_run += run.ncols > (uint32_t)SLOT_XCOLS; many_ends += run.n_ends > (uint32_t)SLOT_XENDS;
 		}
+		fprintf(stderr, "[whamd timing]   X runs: %zu of %zu (not Y form %zu, cells per thread %zu, more than %d columns %zu, more than %d ending reads %zu)\n", nx, m.splan.runs.size(), not_y,
+		        not_lr, SLOT_XCOLS, long_run, SLOT_XENDS, many_ends);
+	}
+	return slot_tab_words;
+}
+
+// What the slot-run kernels read: rows, backtrace blobs, control words, the runs themselves and the block their tables are built in (single individual:
+// slot_tables; pedigree: pedslot_tables, with the pedigree rows and extras).  Produces b.d_runs / b.d_pextra for launch_table_kernels.
+whamd_status_t DeviceTable::Impl::upload_slot_arrays(TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	build_slot_blobs(b);
+	b.laps.lap("slot backtrace blobs (host)");
+	if (!m.splan.rows.empty()) m.splan.rows.resize(m.splan.rows.size() + SLOT_ROW_PAD);   // the kernel's scalar-cache warm-up touches a fixed number of rows
+	HIP_TRY(up.up((void**)&m.dp.slot_rows, m.splan.rows.data(), m.splan.rows.size() * sizeof(SlotRow)));
+	b.laps.lap("slot rows: allocation + copy");
+	HIP_TRY(up.up((void**)&m.dp.slot_blob, b.slot_blob.data(), b.slot_blob.size() * sizeof(uint32_t)));
+	HIP_TRY(up.up((void**)&m.dp.slot_ctrl, m.splan.ctrl.data(), m.splan.ctrl.size() * sizeof(uint32_t)));
+	m.dp.slot_tab = nullptr;
+	b.d_runs = nullptr;
+	if (m.use_slots && !b.ped_slots) {
+		const uint64_t slot_tab_words = lay_out_slot_tables(b);
 		if (slot_tab_words >= 0xFFFFFFFFull) { msg = "slot-run tables exceed 32-bit offsets"; return WHAMD_ERR_UNSUPPORTED; }
-		HIP_TRY(up(&d_sruns, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
-		ulap("slot blobs, control words, runs: allocations + copies");
-		HIP_TRY(alloc(&d_stab, slot_tab_words * 4));
-		ulap("slot tables: allocation");
+		HIP_TRY(up.up((void**)&b.d_runs, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
+		b.laps.lap("slot blobs, control words, runs: allocations + copies");
+		HIP_TRY(up.alloc((void**)&m.dp.slot_tab, slot_tab_words * 4));
+		b.laps.lap("slot tables: allocation");
 	}
-	m.dp.slot_tab = (const uint32_t*)d_stab;
-	void *d_prows = nullptr, *d_pruns = nullptr, *d_pextra = nullptr, *d_ptab = nullptr;
-	if (ped_slots) {
-		HIP_TRY(up(&d_prows, m.splan.prows.data(), m.splan.prows.size() * sizeof(PedSlotRow)));
-		HIP_TRY(up(&d_pruns, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
-		HIP_TRY(up(&d_pextra, m.splan.pextra.data(), m.splan.pextra.size() * sizeof(PedSlotExtra)));
-		HIP_TRY(alloc(&d_ptab, m.table_bytes));
+	m.dp.pslot_rows = nullptr;
+	m.dp.pslot_tab = nullptr;
+	b.d_pextra = nullptr;
+	if (b.ped_slots) {
+		HIP_TRY(up.up((void**)&m.dp.pslot_rows, m.splan.prows.data(), m.splan.prows.size() * sizeof(PedSlotRow)));
+		HIP_TRY(up.up((void**)&b.d_runs, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
+		HIP_TRY(up.up((void**)&b.d_pextra, m.splan.pextra.data(), m.splan.pextra.size() * sizeof(PedSlotExtra)));
+		HIP_TRY(up.alloc((void**)&m.dp.pslot_tab, m.table_bytes));
 	}
-	m.dp.pslot_rows = (const PedSlotRow*)d_prows;
-	m.dp.pslot_tab = (const uint32_t*)d_ptab;
-	m.dp.slot_rows = (const SlotRow*)d_srows;
-	m.dp.slot_blob = (const uint32_t*)d_sblob;
-	ulap("slot rows / blobs / control words: allocations + copies");
-	// ---- jobs (see Impl::Job): connected components made of runs only get their own job
+	b.laps.lap("slot rows / blobs / control words: allocations + copies");
+	return WHAMD_OK;
+}
+
+// Jobs (see Impl::Job): connected components made of runs only get their own job.  Host only.
+void DeviceTable::Impl::make_jobs() {
+	Impl& m = *this;
 	m.release_lanes();
-	{
-		Impl::Job final_job;
-		final_job.final = true;
-		std::vector<Impl::Job> component_jobs;
-		const std::vector<uint32_t>& first = m.plan.component_first_step;
-		// Components as jobs of their own run side by side on lanes -- and walk back one after the other through the SEQUENTIAL backtrace (the chunked one takes a
-		// single job): 16 ms for an irregular coverage-20 table of 200 000 columns whose forward pass is 57 ms, nearly all of it one giant component (a Poisson layout
-		// leaves a gap every few ten thousand columns).  A table whose largest component holds four fifths of its steps or more stays ONE job: the lanes would gain
-		// less than the walk loses ((1 - s) x forward against s x 16 ms).  WHAMD_SPLIT_COMPONENTS=1 (debug library): always split, as before.
-		size_t largest = 0;
-		for (size_t k = 0; k < first.size(); ++k) largest = std::max<size_t>(largest, (k + 1 < first.size() ? first[k + 1] : m.plan.steps.size()) - first[k]);
-		const bool worth_splitting = largest * 5 < m.plan.steps.size() * 4 || debug_env("WHAMD_SPLIT_COMPONENTS");
-		const bool split = m.max_lanes > 1 && first.size() > 1 && worth_splitting && !debug_env("WHAMD_DEBUG_STAMPS") && !m.windowed;
-		if (!split) {
-			for (uint32_t si = 0; si < m.plan.steps.size(); ++si) final_job.steps.push_back(si);
-		} else {
-			for (size_t k = 0; k < first.size(); ++k) {
-				const uint32_t s0 = first[k], s1 = k + 1 < first.size() ? first[k + 1] : (uint32_t)m.plan.steps.size();
-				Impl::Job* job = &final_job;
-				if (k + 1 < first.size()) { component_jobs.emplace_back(); job = &component_jobs.back(); }
-				for (uint32_t si = s0; si < s1; ++si) job->steps.push_back(si);
-			}
+	Impl::Job final_job;
+	final_job.final = true;
+	std::vector<Impl::Job> component_jobs;
+	const std::vector<uint32_t>& first = m.plan.component_first_step;
+	// Components as jobs of their own run side by side on lanes -- and walk back one after the other through the SEQUENTIAL backtrace (the chunked one takes a
+	// single job): 16 ms for an irregular coverage-20 table of 200 000 columns whose forward pass is 57 ms, nearly all of it one giant component (a Poisson layout
+	// leaves a gap every few ten thousand columns).  A table whose largest component holds four fifths of its steps or more stays ONE job: the lanes would gain
+	// less than the walk loses ((1 - s) x forward against s x 16 ms).  WHAMD_SPLIT_COMPONENTS=1 (debug library): always split, as before.
+	size_t largest = 0;
+	for (size_t k = 0; k < first.size(); ++k) largest = std::max<size_t>(largest, (k + 1 < first.size() ? first[k + 1] : m.plan.steps.size()) - first[k]);
+	const bool worth_splitting = largest * 5 < m.plan.steps.size() * 4 || debug_env("WHAMD_SPLIT_COMPONENTS");
+	const bool split = m.max_lanes > 1 && first.size() > 1 && worth_splitting && !debug_env("WHAMD_DEBUG_STAMPS") && !m.windowed;
+	if (!split) {
+		for (uint32_t si = 0; si < m.plan.steps.size(); ++si) final_job.steps.push_back(si);
+	} else {
+		for (size_t k = 0; k < first.size(); ++k) {
+			const uint32_t s0 = first[k], s1 = k + 1 < first.size() ? first[k + 1] : (uint32_t)m.plan.steps.size();
+			Impl::Job* job = &final_job;
+			if (k + 1 < first.size()) { component_jobs.emplace_back(); job = &component_jobs.back(); }
+			for (uint32_t si = s0; si < s1; ++si) job->steps.push_back(si);
 		}
-		m.jobs.push_back(std::move(final_job));
-		for (Impl::Job& j : component_jobs) m.jobs.push_back(std::move(j));
 	}
-	{
-		m.units.clear();
-		for (Impl::Job& job : m.jobs) {
+	m.jobs.push_back(std::move(final_job));
+	for (Impl::Job& j : component_jobs) m.jobs.push_back(std::move(j));
+}
+
+// The backtrace units: every job's steps in reverse order, each with everything the walk needs of it.  Reads b.segs, b.slot_blob_off / _words.  Host only.
+void DeviceTable::Impl::make_units(const TableBuild& b) {
+	Impl& m = *this;
+	m.units.clear();
+	for (Impl::Job& job : m.jobs) {
 		job.unit_off = (uint32_t)m.units.size();
 		for (size_t sj = job.steps.size(); sj-- > 0;) {
 			const Step& st = m.plan.steps[job.steps[sj]];
@@ -833,19 +976,19 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 				const uint32_t nseg = (uint32_t)d.nseg_fwd + d.nseg_end;
 				if (nseg <= (uint32_t)(RES_IOSEG + RES_BT_LRUNS)) {
 					uint32_t* dst = u.wext;  // wext[6] and lext[10] are contiguous: 16 run slots
-					for (uint32_t i = 0; i < nseg; ++i) dst[i] = segs[d.seg_off + i];
+					for (uint32_t i = 0; i < nseg; ++i) dst[i] = b.segs[d.seg_off + i];
 					u.pad1[0] = 1;  // runs are inline
 				}
 			} else if (st.kind == 2) {
 				const SlotRun& run = m.splan.runs[st.index];
 				SlotBtUnit su{};
-				su.kind = ped_slots ? 3 : 2; su.c0 = run.c0; su.ncols = run.ncols; su.blob_off = slot_blob_off[st.index];
+				su.kind = b.ped_slots ? 3 : 2; su.c0 = run.c0; su.ncols = run.ncols; su.blob_off = b.slot_blob_off[st.index];
 				su.g = run.g; su.L = run.L; su.n_ends = run.n_ends; su.threads = run.threads;
-				su.bt_lo = run.rec_lo; su.bt_hi = run.rec_hi; su.half = run.half; su.blob_words = slot_blob_words[st.index];
+				su.bt_lo = run.rec_lo; su.bt_hi = run.rec_hi; su.half = run.half; su.blob_words = b.slot_blob_words[st.index];
 				su.f_exit = m.splan.f_exit[st.index];
 				for (uint32_t j = 0; j < su.f_exit && j < 32; ++j) su.exit_pos[j] = (uint8_t)slot_pos(run.out_pos, m.splan.exit_slot[st.index][j]);
 				su.lr = run.lr;
-				if (ped_slots) { su.n_ends = m.splan.pextra[st.index].rec_words; su.lr = m.splan.pextra[st.index].tb; }   // kind 3: words of one workgroup's record, log2 T
+				if (b.ped_slots) { su.n_ends = m.splan.pextra[st.index].rec_words; su.lr = m.splan.pextra[st.index].tb; }   // kind 3: words of one workgroup's record, log2 T
 				for (uint32_t j = 0; j < su.f_exit && j < 32; ++j) su.exit_slot[j] = m.splan.exit_slot[st.index][j];
 				static_assert(sizeof(SlotBtUnit) == sizeof(BtUnit), "unit headers share one array");
 				std::memcpy(&u, &su, sizeof u);
@@ -861,366 +1004,404 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 			m.units.push_back(u);
 		}
 		job.unit_count = (uint32_t)m.units.size() - job.unit_off;
+	}
+}
+
+// Windows (see Impl::Window): the single job's steps cut where the arena offsets start over (b.window_first_col); their backtrace jobs, the kept boundary columns
+// and the state one window's walk hands to the next.
+whamd_status_t DeviceTable::Impl::make_windows(const TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	m.dp.bt_state = nullptr;
+	if (!m.windowed) return WHAMD_OK;
+	const std::vector<uint32_t>& window_first_col = b.window_first_col;
+	const std::vector<uint32_t>& steps = m.jobs[0].steps;
+	const uint32_t n_steps = (uint32_t)steps.size();
+	auto first_col = [&m, &steps](uint32_t pos) {
+		const Step& st = m.plan.steps[steps[pos]];
+		return st.kind == 0 ? st.index : (st.kind == 2 ? m.splan.runs[st.index].c0 : m.plan.segments[st.index].c0);
+	};
+	Impl::Window w;
+	size_t next = 0;
+	for (uint32_t pos = 0; pos < n_steps; ++pos) {
+		if (next < window_first_col.size() && first_col(pos) == window_first_col[next]) {
+			w.step_hi = pos;
+			m.windows.push_back(w);
+			w = Impl::Window();
+			w.step_lo = pos;
+			++next;
 		}
 	}
-	// ---- windows (see Impl::Window): the single job's steps cut where the arena offsets start over
-	if (m.windowed) {
-		const std::vector<uint32_t>& steps = m.jobs[0].steps;
-		const uint32_t n_steps = (uint32_t)steps.size();
-		auto first_col = [&](uint32_t pos) {
-			const Step& st = m.plan.steps[steps[pos]];
-			return st.kind == 0 ? st.index : (st.kind == 2 ? m.splan.runs[st.index].c0 : m.plan.segments[st.index].c0);
-		};
-		Impl::Window w;
-		size_t next = 0;
-		for (uint32_t pos = 0; pos < n_steps; ++pos) {
-			if (next < window_first_col.size() && first_col(pos) == window_first_col[next]) {
-				w.step_hi = pos;
-				m.windows.push_back(w);
-				w = Impl::Window();
-				w.step_lo = pos;
-				++next;
-			}
-		}
-		w.step_hi = n_steps;
-		m.windows.push_back(w);
-		if (next != window_first_col.size()) { msg = "internal error: a window does not start at a step"; return WHAMD_ERR_DEVICE; }
-		std::vector<BtJob> wjobs;
-		for (size_t wi = 0; wi < m.windows.size(); ++wi) {   // units are the steps in reverse order
-			Impl::Window& win = m.windows[wi];
-			win.unit_off = n_steps - win.step_hi;
-			win.unit_count = win.step_hi - win.step_lo;
-			wjobs.push_back(BtJob{win.unit_off, win.unit_count, wi + 1 == m.windows.size() ? 1u : 2u, 0u});
-		}
-		void* d_wjobs = nullptr;
-		HIP_TRY(up(&d_wjobs, wjobs.data(), wjobs.size() * sizeof(BtJob)));
-		m.d_window_jobs = (BtJob*)d_wjobs;
-		HIP_TRY(alloc((void**)&m.d_checkpoints, (m.windows.size() - 1) * m.checkpoint_bytes));
-		HIP_TRY(alloc((void**)&m.d_bt_state, 16));
-		if (getenv("WHAMD_DEBUG_TIMING")) fprintf(stderr, "[whamd timing] windowed solve: %zu windows, arena %.2f GB\n", m.windows.size(), (double)bt / 1e9);
+	w.step_hi = n_steps;
+	m.windows.push_back(w);
+	if (next != window_first_col.size()) { msg = "internal error: a window does not start at a step"; return WHAMD_ERR_DEVICE; }
+	std::vector<BtJob> wjobs;
+	for (size_t wi = 0; wi < m.windows.size(); ++wi) {   // units are the steps in reverse order
+		Impl::Window& win = m.windows[wi];
+		win.unit_off = n_steps - win.step_hi;
+		win.unit_count = win.step_hi - win.step_lo;
+		wjobs.push_back(BtJob{win.unit_off, win.unit_count, wi + 1 == m.windows.size() ? 1u : 2u, 0u});
 	}
-	// ---- everything a solve hands back lies in ONE device block, laid out like the pinned buffer it is downloaded into: [n] path index, [n] path transmission, the
-	// final job's score with the other jobs' behind it (d_job_scores[0] IS d_score: job 0 is the final one and has no entry of its own), four words of backtrace
-	// counters, the superreads.  Five copies per table -- 4.6 us each as blit kernels, one after the other on a group's stream: 2.6 ms behind a 96-table solve -- are one.
+	HIP_TRY(up.up((void**)&m.d_window_jobs, wjobs.data(), wjobs.size() * sizeof(BtJob)));
+	HIP_TRY(up.alloc((void**)&m.d_checkpoints, (m.windows.size() - 1) * m.checkpoint_bytes));
+	HIP_TRY(up.alloc((void**)&m.d_bt_state, 16));
+	m.dp.bt_state = m.d_bt_state;
+	if (b.laps.on) fprintf(stderr, "[whamd timing] windowed solve: %zu windows, arena %.2f GB\n", m.windows.size(), (double)b.bt / 1e9);
+	return WHAMD_OK;
+}
+
+// Everything a solve hands back lies in ONE device block, laid out like the pinned buffer it is downloaded into: [n] path index, [n] path transmission, the
+// final job's score with the other jobs' behind it (d_job_scores[0] IS d_score: job 0 is the final one and has no entry of its own), four words of backtrace
+// counters, the superreads.  Five copies per table -- 4.6 us each as blit kernels, one after the other on a group's stream: 2.6 ms behind a 96-table solve -- are one.
+whamd_status_t DeviceTable::Impl::take_result_block(uint32_t n, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
 	m.super_off = 2 * (size_t)n + 4 + m.jobs.size();
-	{
-		void* d_res = nullptr;
-		HIP_TRY(alloc(&d_res, (m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t) + 16));
-		uint32_t* res = (uint32_t*)d_res;
-		m.d_path_index = res;
-		m.d_path_trans = res + n;
-		m.d_score = res + 2 * (size_t)n;
-		m.d_job_scores = res + 2 * (size_t)n;
-		m.d_bt_counters = res + 2 * (size_t)n + m.jobs.size();
-		if (m.device_superreads) {
-			m.super_args.out = res + m.super_off;
-			m.super_args.path_index = m.d_path_index;
+	void* d_res = nullptr;
+	HIP_TRY(up.alloc(&d_res, (m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t) + 16));
+	uint32_t* res = (uint32_t*)d_res;
+	m.d_path_index = res;
+	m.d_path_trans = res + n;
+	m.d_score = res + 2 * (size_t)n;
+	m.d_job_scores = res + 2 * (size_t)n;
+	m.d_bt_counters = res + 2 * (size_t)n + m.jobs.size();
+	if (m.device_superreads) {
+		m.super_args.out = res + m.super_off;
+		m.super_args.path_index = m.d_path_index;
+	}
+	return WHAMD_OK;
+}
+
+namespace {
+
+// Orientation generators of the speculative backtrace (BtChunk): per individual the transmission bits its relabelling flips -- a founder those of the
+// trios it is a parent of, a child both of its own trio (exact where genotypes are heterozygous); individuals that are
+// both, or pedigrees with more than BT_GENERATORS individuals, get no generator (still exact, more walked twice).  Pure in the problem.
+struct OrientationGenerators {
+	std::vector<int> of_individual;   // -1: none
+	std::vector<uint32_t> tflip;
+	explicit OrientationGenerators(const Problem& p) : of_individual(std::max<uint32_t>(p.n_ind, 1), -1) {
+		if (p.n_ind < 2 || p.n_ind > BT_GENERATORS) return;
+		for (uint32_t s = 0; s < p.n_ind; ++s) {
+			uint32_t as_parent = 0, as_child = 0;
+			for (uint32_t t3 = 0; t3 < p.n_triples; ++t3) {
+				if (p.triples[t3][0] == s) as_parent |= 1u << (2 * t3);
+				if (p.triples[t3][1] == s) as_parent |= 1u << (2 * t3 + 1);
+				if (p.triples[t3][2] == s) as_child |= 3u << (2 * t3);
+			}
+			if (as_parent && as_child) continue;
+			if (!as_parent && !as_child) continue;   // unrelated individual of a multi-sample table
+			of_individual[s] = (int)tflip.size();
+			tflip.push_back(as_parent | as_child);
 		}
 	}
-	// ---- chunks of the speculative backtrace: a new chunk starts at every BT_CHUNK_RUNS-th slot run (single job only)
+	// the orientations of a chunk that starts from the projection column of column c_last: bit j = j-th forwarded read
+	void orient(const Problem& p, uint32_t c_last, BtChunk& ch) const {
+		ch.n_orient = 1;
+		for (uint32_t q = 0; q < BT_GENERATORS; ++q) ch.flip[q] = 0;
+		if (p.n_triples == 0 && p.n_ind <= 1) {
+			const uint32_t fb = p.f[c_last];
+			ch.flip[0] = fb >= BT_STATE_TSHIFT ? BT_STATE_XMASK : ((1u << fb) - 1u);
+			ch.n_orient = 2;
+			return;
+		}
+		if (tflip.empty()) return;
+		const ColumnEntry* col = p.col_begin(c_last);
+		uint32_t bit = 0;
+		for (uint32_t j = 0; j < p.k[c_last]; ++j) {
+			if (!((p.fwd_mask[c_last] >> j) & 1u)) continue;
+			const int gq = of_individual[col[j].sample];
+			if (gq >= 0) ch.flip[gq] |= 1u << bit;
+			++bit;
+		}
+		for (size_t q = 0; q < tflip.size(); ++q) ch.flip[q] |= tflip[q] << BT_STATE_TSHIFT;
+		ch.n_orient = 1u << tflip.size();
+	}
+};
+
+}  // namespace
+
+// Chunks of the speculative backtrace: a new chunk starts at every BT_CHUNK_RUNS-th run (single job only); the run that leaves a chunk's seed gets its spec id.
+// Produces m.use_chunks, m.chunks, the walk's buffers and m.dp.spec_keys / spec_stride (the schedule's entries carry them).
+whamd_status_t DeviceTable::Impl::make_chunks(const Problem& p, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	const uint32_t n = p.n_cols;
 	m.use_chunks = false;
 	m.chunks.clear();
 	m.n_spec = 0;
 	for (SlotRun& run : m.splan.runs) run.spec_id = 0;
 	const bool trio_runs = !m.use_slots && !m.plan.ped_columns.empty();   // LDS-resident trio runs (kernels_trio.h)
 	if (trio_runs) for (ResSegment& sgm : m.plan.segments) sgm.in_mirror_bit = 0;   // (trio runs have no mirror: the field carries the spec id)
-	if ((m.use_slots || trio_runs) && m.jobs.size() == 1 && !m.windowed && !getenv("WHAMD_BT_SEQUENTIAL") && m.units.size() > 2u * BT_CHUNK_RUNS) {
-		m.use_chunks = true;
-		// orientation generators (BtChunk): per individual the transmission bits its relabelling flips -- a founder those of the
-		// trios it is a parent of, a child both of its own trio (exact where genotypes are heterozygous); individuals that are
-		// both, or pedigrees with more than BT_GENERATORS individuals, get no generator (still exact, more walked twice)
-		std::vector<int> generator_of(std::max<uint32_t>(p.n_ind, 1), -1);
-		std::vector<uint32_t> generator_tflip;
-		if (p.n_ind >= 2 && p.n_ind <= BT_GENERATORS) {
-			for (uint32_t s = 0; s < p.n_ind; ++s) {
-				uint32_t as_parent = 0, as_child = 0;
-				for (uint32_t t3 = 0; t3 < p.n_triples; ++t3) {
-					if (p.triples[t3][0] == s) as_parent |= 1u << (2 * t3);
-					if (p.triples[t3][1] == s) as_parent |= 1u << (2 * t3 + 1);
-					if (p.triples[t3][2] == s) as_child |= 3u << (2 * t3);
-				}
-				if (as_parent && as_child) continue;
-				if (!as_parent && !as_child) continue;   // unrelated individual of a multi-sample table
-				generator_of[s] = (int)generator_tflip.size();
-				generator_tflip.push_back(as_parent | as_child);
-			}
+	m.dp.spec_keys = nullptr;
+	if (!((m.use_slots || trio_runs) && m.jobs.size() == 1 && !m.windowed && !getenv("WHAMD_BT_SEQUENTIAL") && m.units.size() > 2u * BT_CHUNK_RUNS)) return WHAMD_OK;
+	m.use_chunks = true;
+	const OrientationGenerators generators(p);
+	BtChunk cur{};
+	cur.n_orient = 1;   // the newest chunk starts from the table's optimum
+	uint32_t runs_in_chunk = 0;
+	for (uint32_t u = 0; u < m.units.size(); ++u) {
+		const bool is_run = m.units[u].kind == 2 || m.units[u].kind == 3 || (trio_runs && m.units[u].kind == 1);
+		if (is_run && runs_in_chunk >= (uint32_t)BT_CHUNK_RUNS && u > 0) {
+			m.chunks.push_back(cur);
+			cur = BtChunk{};
+			cur.unit_off = u;
+			cur.spec_id = ++m.n_spec;
+			generators.orient(p, m.units[u].c0 + m.units[u].ncols - 1, cur);   // (the last column of unit u's step)
+			runs_in_chunk = 0;
+			// the run of unit u leaves the seed: units are the job's steps in reverse order
+			const Step& st = m.plan.steps[m.jobs[0].steps[m.jobs[0].steps.size() - 1 - u]];
+			if (trio_runs) m.plan.segments[st.index].in_mirror_bit = m.n_spec;
+			else m.splan.runs[st.index].spec_id = m.n_spec;
 		}
-		auto orientations = [&](BtChunk& ch, uint32_t unit) {
-			// the chunk starts from the projection column of the LAST column of unit `unit`'s step: bit j = j-th forwarded read
-			const BtUnit& bu = m.units[unit];
-			const uint32_t c_last = bu.c0 + bu.ncols - 1;
-			ch.n_orient = 1;
-			for (uint32_t q = 0; q < BT_GENERATORS; ++q) ch.flip[q] = 0;
-			if (p.n_triples == 0 && p.n_ind <= 1) {
-				const uint32_t fb = p.f[c_last];
-				ch.flip[0] = fb >= BT_STATE_TSHIFT ? BT_STATE_XMASK : ((1u << fb) - 1u);
-				ch.n_orient = 2;
-				return;
-			}
-			if (generator_tflip.empty()) return;
-			const ColumnEntry* col = p.col_begin(c_last);
-			uint32_t bit = 0;
-			for (uint32_t j = 0; j < p.k[c_last]; ++j) {
-				if (!((p.fwd_mask[c_last] >> j) & 1u)) continue;
-				const int gq = generator_of[col[j].sample];
-				if (gq >= 0) ch.flip[gq] |= 1u << bit;
-				++bit;
-			}
-			for (size_t q = 0; q < generator_tflip.size(); ++q) ch.flip[q] |= generator_tflip[q] << BT_STATE_TSHIFT;
-			ch.n_orient = 1u << generator_tflip.size();
-		};
-		BtChunk cur{};
-		cur.n_orient = 1;   // the newest chunk starts from the table's optimum
-		uint32_t runs_in_chunk = 0;
-		for (uint32_t u = 0; u < m.units.size(); ++u) {
-			const bool is_run = m.units[u].kind == 2 || m.units[u].kind == 3 || (trio_runs && m.units[u].kind == 1);
-			if (is_run && runs_in_chunk >= (uint32_t)BT_CHUNK_RUNS && u > 0) {
-				m.chunks.push_back(cur);
-				cur = BtChunk{};
-				cur.unit_off = u;
-				cur.spec_id = ++m.n_spec;
-				orientations(cur, u);
-				runs_in_chunk = 0;
-				// the run of unit u leaves the seed: units are the job's steps in reverse order
-				const Step& st = m.plan.steps[m.jobs[0].steps[m.jobs[0].steps.size() - 1 - u]];
-				if (trio_runs) m.plan.segments[st.index].in_mirror_bit = m.n_spec;
-				else m.splan.runs[st.index].spec_id = m.n_spec;
-			}
-			runs_in_chunk += is_run;
-			++cur.unit_count;
-		}
-		m.chunks.push_back(cur);
-		void *d_chunks = nullptr;
-		HIP_TRY(up(&d_chunks, m.chunks.data(), m.chunks.size() * sizeof(BtChunk)));
-		m.d_chunks = (BtChunk*)d_chunks;
-		m.n_orient_max = 1;
-		for (const BtChunk& ch : m.chunks) m.n_orient_max = std::max(m.n_orient_max, ch.n_orient);
-		HIP_TRY(alloc((void**)&m.d_unit_x, (size_t)m.n_orient_max * m.units.size() * 4));
-		HIP_TRY(alloc((void**)&m.d_path2, (size_t)m.n_orient_max * n * 4));
-		HIP_TRY(alloc((void**)&m.d_trans2, (size_t)m.n_orient_max * n * 4));
-		HIP_TRY(alloc((void**)&m.d_sel, m.units.size() + 16));
-		HIP_TRY(alloc((void**)&m.d_guess, m.chunks.size() * 4));
-		uint32_t stride = 64;
-		for (const SlotRun& run : m.splan.runs) if (run.spec_id) stride = std::max(stride, (run.threads >> 6) << (run.g - run.half));
-		if (trio_runs) for (const ResSegment& sgm : m.plan.segments) if (sgm.in_mirror_bit) stride = std::max(stride, (sgm.threads >> 6) << sgm.g);
-		m.dp.spec_stride = stride;
-		void* d_spec = nullptr;
-		HIP_TRY(alloc(&d_spec, ((size_t)m.n_spec + 1) * stride * 8));
-		m.dp.spec_keys = (unsigned long long*)d_spec;
-	} else {
-		m.dp.spec_keys = nullptr;
+		runs_in_chunk += is_run;
+		++cur.unit_count;
 	}
-	HIP_TRY(up((void**)&m.d_units, m.units.data(), m.units.size() * sizeof(BtUnit)));
+	m.chunks.push_back(cur);
+	HIP_TRY(up.up((void**)&m.d_chunks, m.chunks.data(), m.chunks.size() * sizeof(BtChunk)));
+	m.n_orient_max = 1;
+	for (const BtChunk& ch : m.chunks) m.n_orient_max = std::max(m.n_orient_max, ch.n_orient);
+	HIP_TRY(up.alloc((void**)&m.d_unit_x, (size_t)m.n_orient_max * m.units.size() * 4));
+	HIP_TRY(up.alloc((void**)&m.d_path2, (size_t)m.n_orient_max * n * 4));
+	HIP_TRY(up.alloc((void**)&m.d_trans2, (size_t)m.n_orient_max * n * 4));
+	HIP_TRY(up.alloc((void**)&m.d_sel, m.units.size() + 16));
+	HIP_TRY(up.alloc((void**)&m.d_guess, m.chunks.size() * 4));
+	uint32_t stride = 64;
+	for (const SlotRun& run : m.splan.runs) if (run.spec_id) stride = std::max(stride, (run.threads >> 6) << (run.g - run.half));
+	if (trio_runs) for (const ResSegment& sgm : m.plan.segments) if (sgm.in_mirror_bit) stride = std::max(stride, (sgm.threads >> 6) << sgm.g);
+	m.dp.spec_stride = stride;
+	HIP_TRY(up.alloc((void**)&m.dp.spec_keys, ((size_t)m.n_spec + 1) * stride * 8));
+	return WHAMD_OK;
+}
+
+// The units' device copy, the LDS sizes of the two backtrace kernels, the runs' table block, the backtrace arena (b.bt bytes: from the arena cache, else from the
+// driver), key scratch, the two exchange buffers of lane 0 and the pinned block a solve downloads into.
+whamd_status_t DeviceTable::Impl::take_solve_buffers(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	HIP_TRY(up.up((void**)&m.d_units, m.units.data(), m.units.size() * sizeof(BtUnit)));
 	{
 		uint32_t max_stage = 0;
 		for (const ResSegment& sgm : m.plan.segments) max_stage = std::max(max_stage, sgm.stage_words);
 		for (size_t ri = 0; ri < m.splan.runs.size(); ++ri)
-			max_stage = std::max(max_stage, ped_slots ? m.splan.pextra[ri].rec_words / 2u : (m.splan.runs[ri].n_ends * m.splan.runs[ri].threads + 7) / 8);
+			max_stage = std::max(max_stage, b.ped_slots ? m.splan.pextra[ri].rec_words / 2u : (m.splan.runs[ri].n_ends * m.splan.runs[ri].threads + 7) / 8);
 		m.bt_lds = (size_t)2 * RES_MAXCOLS * 128 + 512 + 16 + (size_t)BT_CELLS * 4 + (size_t)RES_MAXCOLS * 4 + (size_t)max_stage * 8 + 16;
 		m.chunk_lds = (size_t)(32 + 4 + BT_CELLS + BT_CHUNK_BLOB) * 4 + (size_t)max_stage * 8 + 16;
 	}
 	void* d_rtab = nullptr;
 	const bool ped_plan = !m.plan.ped_columns.empty();
-	HIP_TRY(alloc(&d_rtab, m.plan.columns.size() * (ped_plan ? PED_TABLE : RES_TABLE) * sizeof(int32_t)));
+	HIP_TRY(up.alloc(&d_rtab, m.plan.columns.size() * (ped_plan ? PED_TABLE : RES_TABLE) * sizeof(int32_t)));
 	m.dp.res_tables = ped_plan ? nullptr : (int32_t*)d_rtab;
 	m.dp.ped_tables = ped_plan ? (int32_t*)d_rtab : nullptr;
-	ulap("jobs, backtrace units, schedule");
-	const auto tu2 = std::chrono::steady_clock::now();
+	b.laps.lap("jobs, backtrace units, schedule");
+	b.laps.next_stage();
 	{
 		size_t got = 0;
-		d_bt = arena_take(device, bt, got);
+		void* d_bt = arena_take(m.device, b.bt, got);
 		if (!d_bt) {
-			HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(bt, 16)));
-			got = std::max<size_t>(bt, 16);
+			HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(b.bt, 16)));
+			got = std::max<size_t>(b.bt, 16);
 		}
 		m.d_arena = d_bt;
 		m.arena_bytes = got;
+		m.dp.bt = (uint8_t*)d_bt;
 	}
-	const auto tu3 = std::chrono::steady_clock::now();
-	m.key_entries = (size_t)(1ull << max_keys_f) * p.T;
-	HIP_TRY(alloc(&d_keys, m.key_entries * 8));
-	HIP_TRY(alloc(&d_last_keys, (size_t)MAX_T_WIDE * 8));
-	HIP_TRY(alloc((void**)&m.d_pr[0], (size_t)(1ull << max_f) * p.T * 4));
-	HIP_TRY(alloc((void**)&m.d_pr[1], (size_t)(1ull << max_f) * p.T * 4));
+	b.laps.next_stage();
+	m.key_entries = (size_t)(1ull << b.max_keys_f) * p.T;
+	HIP_TRY(up.alloc((void**)&m.dp.keys, m.key_entries * 8));
+	HIP_TRY(up.alloc((void**)&m.dp.last_keys, (size_t)MAX_T_WIDE * 8));
+	HIP_TRY(up.alloc((void**)&m.d_pr[0], b.exchange_bytes));
+	HIP_TRY(up.alloc((void**)&m.d_pr[1], b.exchange_bytes));
 	HIP_TRY(pinned_take((m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t), (void**)&m.h_pinned, &m.h_pinned_bytes));
-	{   // lanes: longest job first to the least loaded lane; lane 0 always runs the final job
-		// at most 1 GiB of private exchange buffers (coverage 23: 64 MiB per lane)
-		const size_t lane_bytes = 2 * ((size_t)(1ull << max_f) * p.T * 4);
-		const size_t by_memory = std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(lane_bytes, 1));
-		const size_t n_lanes = std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)m.max_lanes, by_memory), m.jobs.size()));
-		m.lanes.assign(n_lanes, Impl::Lane());
-		std::vector<uint64_t> load(n_lanes, 0);
-		std::vector<uint32_t> order;
-		for (uint32_t j = 1; j < m.jobs.size(); ++j) order.push_back(j);
-		std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return m.jobs[a].steps.size() > m.jobs[b].steps.size(); });
-		m.lanes[0].jobs.push_back(0);
-		load[0] = m.jobs[0].steps.size() + 1;
-		for (uint32_t j : order) {
-			const size_t l = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-			m.lanes[l].jobs.push_back(j);
-			load[l] += m.jobs[j].steps.size() + 1;
+	return WHAMD_OK;
+}
+
+// Lanes: longest job first to the least loaded lane; lane 0 always runs the final job.  Every lane but the first gets exchange buffers and key scratch of its own.
+whamd_status_t DeviceTable::Impl::make_lanes(const TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	// at most 1 GiB of private exchange buffers (coverage 23: 64 MiB per lane)
+	const size_t lane_bytes = 2 * b.exchange_bytes;
+	const size_t by_memory = std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(lane_bytes, 1));
+	const size_t n_lanes = std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)m.max_lanes, by_memory), m.jobs.size()));
+	m.lanes.assign(n_lanes, Impl::Lane());
+	std::vector<uint64_t> load(n_lanes, 0);
+	std::vector<uint32_t> order;
+	for (uint32_t j = 1; j < m.jobs.size(); ++j) order.push_back(j);
+	std::stable_sort(order.begin(), order.end(), [&m](uint32_t x, uint32_t y) { return m.jobs[x].steps.size() > m.jobs[y].steps.size(); });
+	m.lanes[0].jobs.push_back(0);
+	load[0] = m.jobs[0].steps.size() + 1;
+	for (uint32_t j : order) {
+		const size_t l = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
+		m.lanes[l].jobs.push_back(j);
+		load[l] += m.jobs[j].steps.size() + 1;
+	}
+	m.lanes[0].d_pr[0] = m.d_pr[0];
+	m.lanes[0].d_pr[1] = m.d_pr[1];
+	m.lanes[0].d_keys = m.dp.keys;
+	for (size_t l = 1; l < n_lanes; ++l) {
+		HIP_TRY(up.alloc((void**)&m.lanes[l].d_pr[0], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.lanes[l].d_pr[1], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.lanes[l].d_keys, m.key_entries * 8));
+	}
+	return WHAMD_OK;
+}
+
+// The schedule: the lanes advance in lockstep; super-step t holds step t of every lane that still has one.  Makes the entries of the batched launches
+// (m.entries / m.slot_entries: they carry the device pointers of everything above) and, windowed, the replay of every older window.  Host only.
+whamd_status_t DeviceTable::Impl::make_schedule(const TableBuild& b, std::string& msg) {
+	Impl& m = *this;
+	const bool ped_slots = b.ped_slots;
+	struct Cursor { size_t job_i = 0, step_i = 0; uint32_t flip = 0; };
+	std::vector<Cursor> cur(m.lanes.size());
+	for (;;) {
+		Impl::SuperStep ss;
+		ss.entry_off = (uint32_t)(m.use_slots ? m.slot_entries.size() : m.entries.size());
+		for (size_t li = 0; li < m.lanes.size(); ++li) {
+			Impl::Lane& lane = m.lanes[li];
+			Cursor& c = cur[li];
+			if (c.job_i == lane.jobs.size()) continue;
+			const uint32_t job_id = lane.jobs[c.job_i];
+			const Impl::Job& job = m.jobs[job_id];
+			const uint32_t si = job.steps[c.step_i];
+			const bool first = c.step_i == 0, last = c.step_i + 1 == job.steps.size();
+			const Step& step = m.plan.steps[si];
+			ss.io[0] = lane.d_pr[c.flip]; ss.io[1] = lane.d_pr[c.flip ^ 1];
+			if (step.kind == 2) {
+				SlotBatchEntry e{};
+				e.run = m.splan.runs[step.index];
+				if (first) e.run.has_prev = 0;  // a job starts from cost 0
+				e.prev = lane.d_pr[c.flip];
+				e.cur = lane.d_pr[c.flip ^ 1];
+				e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
+				if (m.splan.ped) {
+					const PedSlotExtra& pex = m.splan.pextra[step.index];
+					ss.lds = std::max<size_t>(ss.lds, pedslot_lds_bytes(e.run.threads, e.run.ncols, pex));
+				} else
+				ss.lds = std::max<size_t>(ss.lds, slot_run_lds_bytes(e.run.threads, e.run.lr, e.run.ncols));
+				e.pad = step.index;
+				// the owning table's arrays: a group launch (slot_group / pedslot_group) serves runs of several tables
+				if (ped_slots) e.ex = m.splan.pextra[step.index];
+				e.tab = ped_slots ? m.dp.pslot_tab : m.dp.slot_tab;
+				e.rows = ped_slots ? (const void*)m.dp.pslot_rows : (const void*)m.dp.slot_rows;
+				e.ctrl = m.dp.slot_ctrl;
+				e.bt = m.dp.bt;
+				e.spec_keys = m.dp.spec_keys;
+				e.spec_stride = m.dp.spec_stride;
+				if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) e.pad2 = (uint32_t)atoi(skip);   // (timing experiments in a group launch)
+				if (debug_env("WHAMD_NO_WARM")) e.pad2 |= 0x10000u;
+				ss.grid_x = std::max(ss.grid_x, 1u << (e.run.g - e.run.half));
+				ss.threads = std::max(ss.threads, e.run.threads);
+				m.slot_entries.push_back(e);
+				++ss.entry_count;
+			} else if (step.kind == 1) {
+				ResBatchEntry e{};
+				e.sg = m.plan.segments[step.index];
+				e.sg.pad = step.index;
+				if (first) e.sg.has_prev = 0;  // a job starts from cost 0
+				e.prev = lane.d_pr[c.flip];
+				e.cur = lane.d_pr[c.flip ^ 1];
+				e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
+				const size_t lds = e.sg.kind == 1
+					? ((((size_t)e.sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)e.sg.n_terms * 2 + 3) & ~(size_t)3) * 4 + 2 * ((size_t)16 << e.sg.max_l) + (size_t)e.sg.stage_words * 8)
+					: ((size_t)e.sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << e.sg.max_l) + (size_t)e.sg.stage_words * 8);
+				ss.lds = std::max(ss.lds, lds);
+				ss.grid_x = std::max(ss.grid_x, 1u << (e.sg.g - e.sg.half));
+				ss.threads = std::max(ss.threads, e.sg.threads);
+				ss.sym = ss.sym || e.sg.half || e.sg.in_half || e.sg.mirror_out;
+				m.entries.push_back(e);
+				++ss.entry_count;
+			} else {
+				ss.singles.push_back(Impl::Single{(uint32_t)li, si, c.flip, first, (last && !job.final) ? (int32_t)job_id : -1});
+			}
+			c.flip ^= 1;
+			if (last) { ++c.job_i; c.step_i = 0; } else ++c.step_i;
 		}
-		m.lanes[0].d_pr[0] = m.d_pr[0];
-		m.lanes[0].d_pr[1] = m.d_pr[1];
-		m.lanes[0].d_keys = (unsigned long long*)d_keys;
-		for (size_t l = 1; l < n_lanes; ++l) {
-			HIP_TRY(alloc((void**)&m.lanes[l].d_pr[0], (size_t)(1ull << max_f) * p.T * 4));
-			HIP_TRY(alloc((void**)&m.lanes[l].d_pr[1], (size_t)(1ull << max_f) * p.T * 4));
-			HIP_TRY(alloc((void**)&m.lanes[l].d_keys, m.key_entries * 8));
+		if (!ss.entry_count && ss.singles.empty()) break;
+		m.max_grid_x = std::max(m.max_grid_x, ss.grid_x * std::max(1u, ss.entry_count));
+		m.schedule.push_back(std::move(ss));
+	}
+	if (m.windowed) {
+		// one lane, one job: super-step i is step i.  Pass 1 = the schedule as it is, plus the kept columns and the
+		// walk of the newest window; then every older window again, newest first.
+		if (m.schedule.size() != m.jobs[0].steps.size()) { msg = "internal error: windowed schedule"; return WHAMD_ERR_DEVICE; }
+		const size_t nw = m.windows.size();
+		for (size_t wi = 0; wi + 1 < nw; ++wi) m.schedule[m.windows[wi].step_hi - 1].ck_save = (int32_t)wi;
+		m.schedule.back().bt_window = (int32_t)(nw - 1);
+		for (size_t wi = nw - 1; wi-- > 0;) {
+			const Impl::Window& win = m.windows[wi];
+			for (uint32_t pos = win.step_lo; pos < win.step_hi; ++pos) {
+				Impl::SuperStep again = m.schedule[pos];
+				again.ck_save = -1;
+				again.ck_load = (pos == win.step_lo && wi > 0) ? (int32_t)(wi - 1) : -1;
+				again.bt_window = pos + 1 == win.step_hi ? (int32_t)wi : -1;
+				m.schedule.push_back(std::move(again));
+			}
 		}
 	}
-	{   // schedule: the lanes advance in lockstep; super-step t holds step t of every lane that still has one
-		struct Cursor { size_t job_i = 0, step_i = 0; uint32_t flip = 0; };
-		std::vector<Cursor> cur(m.lanes.size());
-		for (;;) {
-			Impl::SuperStep ss;
-			ss.entry_off = (uint32_t)(m.use_slots ? m.slot_entries.size() : m.entries.size());
-			for (size_t li = 0; li < m.lanes.size(); ++li) {
-				Impl::Lane& lane = m.lanes[li];
-				Cursor& c = cur[li];
-				if (c.job_i == lane.jobs.size()) continue;
-				const uint32_t job_id = lane.jobs[c.job_i];
-				const Impl::Job& job = m.jobs[job_id];
-				const uint32_t si = job.steps[c.step_i];
-				const bool first = c.step_i == 0, last = c.step_i + 1 == job.steps.size();
-				const Step& step = m.plan.steps[si];
-				if (step.kind == 2) {
-					SlotBatchEntry e{};
-					e.run = m.splan.runs[step.index];
-					if (first) e.run.has_prev = 0;  // a job starts from cost 0
-					e.prev = lane.d_pr[c.flip];
-					e.cur = lane.d_pr[c.flip ^ 1];
-					e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
-					ss.io[0] = lane.d_pr[c.flip]; ss.io[1] = lane.d_pr[c.flip ^ 1];
-					if (m.splan.ped) {
-						const PedSlotExtra& pex = m.splan.pextra[step.index];
-						ss.lds = std::max<size_t>(ss.lds, pedslot_lds_bytes(e.run.threads, e.run.ncols, pex));
-					} else
-					ss.lds = std::max<size_t>(ss.lds, slot_run_lds_bytes(e.run.threads, e.run.lr, e.run.ncols));
-					e.pad = step.index;
-					// the owning table's arrays: a group launch (slot_group / pedslot_group) serves runs of several tables
-					if (ped_slots) e.ex = m.splan.pextra[step.index];
-					e.tab = ped_slots ? (const uint32_t*)d_ptab : (const uint32_t*)d_stab;
-					e.rows = ped_slots ? (const void*)d_prows : (const void*)d_srows;
-					e.ctrl = (const uint32_t*)d_sctrl;
-					e.bt = (uint8_t*)d_bt;
-					e.spec_keys = m.dp.spec_keys;
-					e.spec_stride = m.dp.spec_stride;
-					if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) e.pad2 = (uint32_t)atoi(skip);   // (timing experiments in a group launch)
-					if (debug_env("WHAMD_NO_WARM")) e.pad2 |= 0x10000u;
-					ss.grid_x = std::max(ss.grid_x, 1u << (e.run.g - e.run.half));
-					ss.threads = std::max(ss.threads, e.run.threads);
-					m.slot_entries.push_back(e);
-					++ss.entry_count;
-				} else if (step.kind == 1) {
-					ResBatchEntry e{};
-					e.sg = m.plan.segments[step.index];
-					e.sg.pad = step.index;
-					if (first) e.sg.has_prev = 0;  // a job starts from cost 0
-					e.prev = lane.d_pr[c.flip];
-					e.cur = lane.d_pr[c.flip ^ 1];
-					e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
-					ss.io[0] = lane.d_pr[c.flip]; ss.io[1] = lane.d_pr[c.flip ^ 1];
-					const size_t lds = e.sg.kind == 1
-						? ((((size_t)e.sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)e.sg.n_terms * 2 + 3) & ~(size_t)3) * 4 + 2 * ((size_t)16 << e.sg.max_l) + (size_t)e.sg.stage_words * 8)
-						: ((size_t)e.sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << e.sg.max_l) + (size_t)e.sg.stage_words * 8);
-					ss.lds = std::max(ss.lds, lds);
-					ss.grid_x = std::max(ss.grid_x, 1u << (e.sg.g - e.sg.half));
-					ss.threads = std::max(ss.threads, e.sg.threads);
-					ss.sym = ss.sym || e.sg.half || e.sg.in_half || e.sg.mirror_out;
-					m.entries.push_back(e);
-					++ss.entry_count;
-				} else {
-					ss.singles.push_back(Impl::Single{(uint32_t)li, si, c.flip, first, (last && !job.final) ? (int32_t)job_id : -1});
-					ss.io[0] = lane.d_pr[c.flip]; ss.io[1] = lane.d_pr[c.flip ^ 1];
-				}
-				c.flip ^= 1;
-				if (last) { ++c.job_i; c.step_i = 0; } else ++c.step_i;
+	return WHAMD_OK;
+}
+
+// What a group submission reads of the schedule (see StepBrief / EntryBrief).  Host only.
+void DeviceTable::Impl::make_briefs() {
+	Impl& m = *this;
+	m.step_brief.clear();
+	m.entry_brief.clear();
+	if (!m.use_slots) return;
+	m.step_brief.reserve(m.schedule.size());
+	m.entry_brief.reserve(m.slot_entries.size());
+	for (const Impl::SuperStep& ss : m.schedule) {
+		m.step_brief.push_back(Impl::StepBrief{(uint32_t)m.entry_brief.size(), (uint32_t)ss.lds, (uint16_t)ss.entry_count, (uint8_t)(ss.singles.empty() ? 0 : 1), 0});
+		for (uint32_t q = 0; q < ss.entry_count; ++q) {
+			const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q];
+			Impl::EntryBrief eb{};
+			eb.grid_x = (uint16_t)(1u << (he.run.g - he.run.half));
+			eb.threads = (uint16_t)he.run.threads;
+			eb.lds_x = (uint32_t)((size_t)2 * he.run.threads * (4u << he.run.lr));
+			// kernel variants of a group launch: 0 single individual (four cells per thread); 1 .. 5 pedigree runs (TB, NF) = (2,2) (2,4) (4,2) (4,4) (2,16); 6 single, eight cells;
+			// 7 trio on factorised lines; 8 / 9 X runs with four / eight cells (slot_groupx); 10 quartet on factorised lines
+			if (m.splan.ped) eb.variant = eb.variant_x = (uint8_t)(he.ex.nf == (uint32_t)PSLOT_FACT4 ? 10 : he.ex.nf == (uint32_t)PSLOT_FACT ? 7 : (he.ex.nf == 16 ? 5 : 1 + (he.ex.tb == 4 ? 2 : 0) + (he.ex.nf == 4 ? 1 : 0)));
+			else {
+				eb.variant = (uint8_t)(he.run.lr == 3 ? 6 : 0);
+				eb.variant_x = (he.run.yflags & 8u) ? (uint8_t)(he.run.lr == 3 ? 9 : 8) : eb.variant;
 			}
-			if (!ss.entry_count && ss.singles.empty()) break;
-			m.max_grid_x = std::max(m.max_grid_x, ss.grid_x * std::max(1u, ss.entry_count));
-			m.schedule.push_back(std::move(ss));
+			m.entry_brief.push_back(eb);
 		}
-		if (m.windowed) {
-			// one lane, one job: super-step i is step i.  Pass 1 = the schedule as it is, plus the kept columns and the
-			// walk of the newest window; then every older window again, newest first.
-			if (m.schedule.size() != m.jobs[0].steps.size()) { msg = "internal error: windowed schedule"; return WHAMD_ERR_DEVICE; }
-			const size_t nw = m.windows.size();
-			for (size_t wi = 0; wi + 1 < nw; ++wi) m.schedule[m.windows[wi].step_hi - 1].ck_save = (int32_t)wi;
-			m.schedule.back().bt_window = (int32_t)(nw - 1);
-			for (size_t wi = nw - 1; wi-- > 0;) {
-				const Impl::Window& win = m.windows[wi];
-				for (uint32_t pos = win.step_lo; pos < win.step_hi; ++pos) {
-					Impl::SuperStep again = m.schedule[pos];
-					again.ck_save = -1;
-					again.ck_load = (pos == win.step_lo && wi > 0) ? (int32_t)(wi - 1) : -1;
-					again.bt_window = pos + 1 == win.step_hi ? (int32_t)wi : -1;
-					m.schedule.push_back(std::move(again));
-				}
-			}
-		}
-		m.step_brief.clear();
-		m.entry_brief.clear();
-		if (m.use_slots) {
-			m.step_brief.reserve(m.schedule.size());
-			m.entry_brief.reserve(m.slot_entries.size());
-			for (const Impl::SuperStep& ss : m.schedule) {
-				m.step_brief.push_back(Impl::StepBrief{(uint32_t)m.entry_brief.size(), (uint32_t)ss.lds, (uint16_t)ss.entry_count, (uint8_t)(ss.singles.empty() ? 0 : 1), 0});
-				for (uint32_t q = 0; q < ss.entry_count; ++q) {
-					const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q];
-					Impl::EntryBrief eb{};
-					eb.grid_x = (uint16_t)(1u << (he.run.g - he.run.half));
-					eb.threads = (uint16_t)he.run.threads;
-					eb.lds_x = (uint32_t)((size_t)2 * he.run.threads * (4u << he.run.lr));
-					// kernel variants of a group launch: 0 single individual (four cells per thread); 1 .. 5 pedigree runs (TB, NF) = (2,2) (2,4) (4,2) (4,4) (2,16); 6 single, eight cells;
-					// 7 trio on factorised lines; 8 / 9 X runs with four / eight cells (slot_groupx); 10 quartet on factorised lines
-					if (m.splan.ped) eb.variant = eb.variant_x = (uint8_t)(he.ex.nf == (uint32_t)PSLOT_FACT4 ? 10 : he.ex.nf == (uint32_t)PSLOT_FACT ? 7 : (he.ex.nf == 16 ? 5 : 1 + (he.ex.tb == 4 ? 2 : 0) + (he.ex.nf == 4 ? 1 : 0)));
-					else {
-						eb.variant = (uint8_t)(he.run.lr == 3 ? 6 : 0);
-						eb.variant_x = (he.run.yflags & 8u) ? (uint8_t)(he.run.lr == 3 ? 9 : 8) : eb.variant;
-					}
-					m.entry_brief.push_back(eb);
-				}
-			}
-		}
-		void* d_entries = nullptr;
-		HIP_TRY(up(&d_entries, m.entries.data(), m.entries.size() * sizeof(ResBatchEntry)));
-		m.d_entries = (ResBatchEntry*)d_entries;
-		void* d_slot_entries = nullptr;
-		m.slot_entries.resize(m.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_core)
-		HIP_TRY(up(&d_slot_entries, m.slot_entries.data(), m.slot_entries.size() * sizeof(SlotBatchEntry)));
-		m.slot_entries.resize(m.slot_entries.size() - 2);
-		m.d_slot_entries = (SlotBatchEntry*)d_slot_entries;
-		std::vector<BtJob> btjobs;
-		for (const Impl::Job& job : m.jobs) btjobs.push_back(BtJob{job.unit_off, job.unit_count, job.final ? 1u : 0u, 0u});
-		void* d_btjobs = nullptr;
-		HIP_TRY(up(&d_btjobs, btjobs.data(), btjobs.size() * sizeof(BtJob)));
-		m.d_btjobs = (BtJob*)d_btjobs;
 	}
-	HIP_TRY(flush_slab());   // (everything is staged; the table kernels below read it)
-	m.dp.cols = m.d_cols;
-	m.dp.term_ptr = (const uint32_t*)d_term_ptr;
-	m.dp.terms = (const DevTerm*)d_terms;
-	if (ped_slots) {
-		// the cost-form tables of every run (slots.h), once per table: blockIdx.y = run
+}
+
+// The entries of the batched launches and the backtrace jobs: the last arrays of the image.
+whamd_status_t DeviceTable::Impl::upload_entries(TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	HIP_TRY(up.up((void**)&m.d_entries, m.entries.data(), m.entries.size() * sizeof(ResBatchEntry)));
+	m.slot_entries.resize(m.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_core)
+	HIP_TRY(up.up((void**)&m.d_slot_entries, m.slot_entries.data(), m.slot_entries.size() * sizeof(SlotBatchEntry)));
+	m.slot_entries.resize(m.slot_entries.size() - 2);
+	std::vector<BtJob> btjobs;
+	for (const Impl::Job& job : m.jobs) btjobs.push_back(BtJob{job.unit_off, job.unit_count, job.final ? 1u : 0u, 0u});
+	HIP_TRY(up.up((void**)&m.d_btjobs, btjobs.data(), btjobs.size() * sizeof(BtJob)));
+	return WHAMD_OK;
+}
+
+// The rest of the image leaves; behind it the kernels that build the slot runs' tables, once per table (blockIdx.y = run); `ev_upload` marks the end of it all.
+whamd_status_t DeviceTable::Impl::launch_table_kernels(const Problem& p, const TableBuild& b, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	const hipStream_t us = up.stream;
+	HIP_TRY(up.flush());   // (everything is staged; the table kernels below read it)
+	if (b.ped_slots) {
+		// the cost-form tables of every run (slots.h)
 		uint32_t most = 0;
 		for (size_t ri = 0; ri < m.splan.runs.size(); ++ri)
 			most = std::max<uint32_t>(most, (m.splan.pextra[ri].fwn << m.splan.runs[ri].g) + (m.splan.pextra[ri].fwn << m.splan.runs[ri].lw) + m.splan.runs[ri].ncols * (64u * pslot_ns(m.splan.pextra[ri].nf) + p.T * pslot_nk(m.splan.pextra[ri].nf)));
 		const uint32_t bx = std::max(1u, std::min(1024u, (most + 255u) / 256u));
 		for (size_t r0 = 0; r0 < m.splan.runs.size(); r0 += 32768) {   // (gridDim.y <= 65535)
 			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.splan.runs.size() - r0);
-			hipLaunchKernelGGL(pedslot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, (const SlotRun*)d_pruns + r0, (const PedSlotExtra*)d_pextra + r0, (uint32_t*)d_ptab,
-			                   (const DevTerm*)d_fterms);
+			hipLaunchKernelGGL(pedslot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, b.d_runs + r0, b.d_pextra + r0, (uint32_t*)m.dp.pslot_tab, b.d_fterms);
 		}
 		HIP_TRY(hipGetLastError());
 	}
-	if (m.use_slots && !ped_slots && !m.splan.runs.empty()) {
+	if (m.use_slots && !b.ped_slots && !m.splan.runs.empty()) {
 		uint32_t most = 0;
 		for (const SlotRun& run : m.splan.runs) most = std::max<uint32_t>(most, ((run.ncols + 8u) << (run.g - run.half)) + (run.ncols + 8u) * ((run.threads >> 6) + 64u));
 		const uint32_t bx = std::max(1u, std::min(64u, (most + 255u) / 256u));
 		for (size_t r0 = 0; r0 < m.splan.runs.size(); r0 += 32768) {
 			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.splan.runs.size() - r0);
-			hipLaunchKernelGGL(slot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, (const SlotRun*)d_sruns + r0, (uint32_t*)d_stab);
+			hipLaunchKernelGGL(slot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, b.d_runs + r0, (uint32_t*)m.dp.slot_tab);
 		}
 		HIP_TRY(hipGetLastError());
 	}
@@ -1229,148 +1410,151 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 	// the queue of the others' copies (half of a create's wall time at 16 workers).  WHAMD_SYNC_UPLOAD=1 (debug library) restores the wait.
 	HIP_TRY(hipEventRecord(m.ev_upload, us));
 	m.upload_pending = true;
-	if (debug_env("WHAMD_SYNC_UPLOAD") || unstaged_copies || !stage.image || !stage.park()) {
+	if (debug_env("WHAMD_SYNC_UPLOAD") || up.unstaged_copies || !up.stage.image || !up.stage.park()) {
 		HIP_TRY(hipStreamSynchronize(us));
-		stage.finish();
+		up.stage.finish();
 	}
-	m.dp.delta = (const int32_t*)d_delta;
-	m.dp.term_ptr = (const uint32_t*)d_term_ptr;
-	m.dp.terms = (const DevTerm*)d_terms;
-	m.dp.segs = (const uint32_t*)d_segs;
-	m.dp.bt = (uint8_t*)d_bt;
-	m.dp.keys = (unsigned long long*)d_keys;
-	m.dp.last_keys = (unsigned long long*)d_last_keys;
-	m.dp.bt_state = m.windowed ? m.d_bt_state : nullptr;
-	m.dp.res_cols = (const ResColumn*)d_rcol;
-	m.dp.res_bt = (const ResBacktrace*)d_rbt;
+	return WHAMD_OK;
+}
+
+// The in-kernel cycle stamps and timing experiments of the debug library (m.dp.dbg, dbg_wg_off, dbg_flags).
+whamd_status_t DeviceTable::Impl::arm_debug_stamps(TableUploader& up, std::string& msg) {
+	Impl& m = *this;
 	m.dp.dbg = nullptr;
-	if (getenv("WHAMD_DEBUG_TIMING")) {
-		auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-		fprintf(stderr, "[whamd timing] upload: plan %.1f ms, descriptors + copies %.1f ms, backtrace arena (%.2f GB) %.1f ms, rest %.1f ms\n",
-		        ms(tu0, tu1), ms(tu1, tu2), (double)bt / 1e9, ms(tu2, tu3), ms(tu3, std::chrono::steady_clock::now()));
-	}
 	if (debug_env("WHAMD_DEBUG_STAMPS") && !m.use_slots) {   // in-kernel cycle stamps of the LDS-resident runs (WHAMD_DEBUG_TIMING: host phases only)
-		void* d_dbg = nullptr;
 		const size_t dbg_bytes = (m.plan.segments.size() + 1) * 64 + 4 * 512 * 16 + 64;
-		HIP_TRY(alloc(&d_dbg, dbg_bytes));
-		HIP_TRY(hipMemset(d_dbg, 0, dbg_bytes));
-		m.dp.dbg = (unsigned long long*)d_dbg;
+		HIP_TRY(up.alloc((void**)&m.dp.dbg, dbg_bytes));
+		HIP_TRY(hipMemset(m.dp.dbg, 0, dbg_bytes));
 		m.dp.dbg_wg_off = (uint32_t)((m.plan.segments.size() + 1) * 8);
 		m.dp.dbg_flags = (uint32_t)atoi(debug_env("WHAMD_DEBUG_STAMPS"));
 	}
 	if (debug_env("WHAMD_SLOT_STAMPS") && m.use_slots) {   // in-kernel cycle stamps of workgroup 0 / wave 0 of every slot run
-		void* d_dbg = nullptr;
 		const size_t dbg_bytes = (m.splan.runs.size() + 1) * 48 * 8 + 4 * 512 * 16 + 128;   // + the backtrace kernel's own stamps
-		HIP_TRY(alloc(&d_dbg, dbg_bytes));
-		HIP_TRY(hipMemset(d_dbg, 0, dbg_bytes));
-		m.dp.dbg = (unsigned long long*)d_dbg;
+		HIP_TRY(up.alloc((void**)&m.dp.dbg, dbg_bytes));
+		HIP_TRY(hipMemset(m.dp.dbg, 0, dbg_bytes));
 		m.dp.dbg_wg_off = (uint32_t)((m.splan.runs.size() + 1) * 48);
 		for (size_t i = 0; i < m.slot_entries.size(); ++i) m.slot_entries[i].run.pad = (uint32_t)i;
 	}
 	if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) m.dp.dbg_flags = (uint32_t)atoi(skip);  // timing experiments (results invalid): 1 no exit
 	                                                                                          // stores, 2 no records, 4 one column per run, 8 no ending reads, 16 no cost update
-	m.dp.n_cols = n;
-	m.dp.T = p.T;
-	m.dp.tbits = tbits;
-	m.dp.n_ind = p.n_ind;
-	// kernels with more than 64 KiB of dynamic LDS need the opt-in on every device they run on -- once per process and device (23 driver calls
-	// per table were a tenth of a coverage-15 create when many tables are built at once)
-	{
-		static std::mutex attr_mu;
-		static unsigned long long attr_done = 0;   // bit = device
-		std::lock_guard<std::mutex> lock(attr_mu);
-		if (device >= 64 || !((attr_done >> device) & 1ull)) {
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_segment<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_segment<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	return WHAMD_OK;
+}
+
+// Kernels with more than 64 KiB of dynamic LDS need the opt-in on every device they run on -- once per process and device (23 driver calls
+// per table were a tenth of a coverage-15 create when many tables are built at once).
+static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
+#define K(...) reinterpret_cast<const void*>((__VA_ARGS__))
+#define WHAMD_RUNX(XC, STAMPS) K(slot_runx<2, XC, STAMPS, false>), K(slot_runx<2, XC, STAMPS, true>)
+#define WHAMD_PSLOT(TBV, NFV) K(pedslot_run<TBV, NFV, false, false>), K(pedslot_run<TBV, NFV, false, true>), K(pedslot_run<TBV, NFV, true, false>), K(pedslot_run<TBV, NFV, true, true>)
+#define WHAMD_PSLOTX(TBV, NFV) K(pedslot_runx<TBV, NFV, 32, false>), K(pedslot_runx<TBV, NFV, 32, true>)
+	// (The compiler emits the instantiations in the order they are first named, here: a reordered table is a reordered code object.  The debug
+	// library's additions -- cycle stamps, pedigree X runs -- stand where it has always named them.)
+	static const void* const kernels[] = {
+		K(resident_segment<false, false>), K(resident_segment<false, true>),
 #ifdef WHAMD_DEBUG_BUILD
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_segment<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		K(resident_segment<true, true>),
 #endif
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_batch<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_batch<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(backtrace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_segment_ped<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		K(resident_batch<false>), K(resident_batch<true>), K(backtrace_kernel), K(resident_segment_ped<false>),
 #ifdef WHAMD_DEBUG_BUILD
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(resident_segment_ped<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		K(resident_segment_ped<true>),
 #endif
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((resident_segment_ped<false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 24, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 24, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 32, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 32, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		K(resident_segment_ped<false, true>),
 		// every instantiation launch_slot_run / enqueue_group may pick: a 9..16-column run of 512 threads needs slotx_lds_bytes(512, 16) = 72 KB, above the
 		// 64 KB a kernel gets without the attribute (XC = 0: streamed operands, 16 KB; XC = 8: 56 KB -- registered all the same, the limit is per function)
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 0, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 0, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 8, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 8, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 16, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 16, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_groupx<2, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_groupx<3, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		WHAMD_RUNX(24, false), WHAMD_RUNX(32, false), WHAMD_RUNX(0, false), WHAMD_RUNX(8, false), WHAMD_RUNX(16, false),
+		K(slot_groupx<2, false>), K(slot_groupx<3, false>),
 #ifdef WHAMD_DEBUG_BUILD
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 24, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 24, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 32, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((slot_runx<2, 32, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		WHAMD_RUNX(24, true), WHAMD_RUNX(32, true),
+		WHAMD_PSLOTX(2, 2), WHAMD_PSLOTX(2, 4), WHAMD_PSLOTX(4, 2), WHAMD_PSLOTX(4, 4), WHAMD_PSLOTX(2, 16), WHAMD_PSLOTX(2, PSLOT_FACT),
 #endif
-#ifdef WHAMD_DEBUG_BUILD
-#define WHAMD_PSLOTX_ATTR(TBV, NFV) \
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_runx<TBV, NFV, 32, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_runx<TBV, NFV, 32, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		WHAMD_PSLOTX_ATTR(2, 2) WHAMD_PSLOTX_ATTR(2, 4) WHAMD_PSLOTX_ATTR(4, 2) WHAMD_PSLOTX_ATTR(4, 4) WHAMD_PSLOTX_ATTR(2, 16) WHAMD_PSLOTX_ATTR(2, PSLOT_FACT)
-#undef WHAMD_PSLOTX_ATTR
-#endif
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 4, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 4, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 4, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 4, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 2, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 2, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 2, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 2, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 4, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 4, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 4, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, 4, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 16, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 16, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 16, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, 16, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<2, 16>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, PSLOT_FACT, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, PSLOT_FACT, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, PSLOT_FACT, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<2, PSLOT_FACT, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<2, PSLOT_FACT>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, PSLOT_FACT4, false, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, PSLOT_FACT4, false, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, PSLOT_FACT4, true, false>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_run<4, PSLOT_FACT4, true, true>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<4, PSLOT_FACT4>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<2, 2>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<2, 4>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<4, 2>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>((pedslot_group<4, 4>)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-			if (device < 64) attr_done |= 1ull << device;
-		}
-	}
-	m.d_bt_entry = nullptr;
-	if (m.use_chunks) {   // (m.dp is complete here)
-		BtGroupEntry& e = m.h_bt_entry;
-		e = BtGroupEntry{};
-		e.P = m.dp;
-		e.units = m.d_units; e.chunks = m.d_chunks;
-		e.n_chunks = (uint32_t)m.chunks.size(); e.n_units = (uint32_t)m.units.size(); e.n_orient_max = m.n_orient_max; e.n_cols = n;
-		e.path2 = m.d_path2; e.trans2 = m.d_trans2; e.out_score = m.d_score; e.unit_x2 = m.d_unit_x; e.guess = m.d_guess; e.sel = m.d_sel; e.counters = m.d_bt_counters;
-		e.path_index = m.d_path_index; e.path_trans = m.d_path_trans;
-		if (m.device_superreads) e.super = m.super_args;
-		void* d_entry = nullptr;
-		HIP_TRY(alloc(&d_entry, sizeof(BtGroupEntry)));
-		HIP_TRY(hipMemcpyAsync(d_entry, &m.h_bt_entry, sizeof(BtGroupEntry), hipMemcpyHostToDevice, us));   // (the source is a member: it outlives the copy)
-		HIP_TRY(hipEventRecord(m.ev_upload, us));
-		m.d_bt_entry = (BtGroupEntry*)d_entry;
-	}
+		WHAMD_PSLOT(2, 4), WHAMD_PSLOT(4, 2), WHAMD_PSLOT(4, 4),
+		WHAMD_PSLOT(2, 16), K(pedslot_group<2, 16>),
+		WHAMD_PSLOT(2, PSLOT_FACT), K(pedslot_group<2, PSLOT_FACT>),
+		WHAMD_PSLOT(4, PSLOT_FACT4), K(pedslot_group<4, PSLOT_FACT4>),
+		K(pedslot_group<2, 2>), K(pedslot_group<2, 4>), K(pedslot_group<4, 2>), K(pedslot_group<4, 4>),
+	};
+#undef K
+#undef WHAMD_RUNX
+#undef WHAMD_PSLOT
+#undef WHAMD_PSLOTX
+	static std::mutex attr_mu;
+	static unsigned long long attr_done = 0;   // bit = device
+	std::lock_guard<std::mutex> lock(attr_mu);
+	if (device < 64 && ((attr_done >> device) & 1ull)) return WHAMD_OK;
+	for (const void* kernel : kernels) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	if (device < 64) attr_done |= 1ull << device;
 	return WHAMD_OK;
+}
+
+// What a batched backtrace launch reads for this table (BtGroupEntry): a copy of the finished m.dp and the walk's buffers, on the device behind `ev_upload`.
+whamd_status_t DeviceTable::Impl::record_group_backtrace(uint32_t n, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	m.d_bt_entry = nullptr;
+	if (!m.use_chunks) return WHAMD_OK;
+	BtGroupEntry& e = m.h_bt_entry;
+	e = BtGroupEntry{};
+	e.P = m.dp;
+	e.units = m.d_units; e.chunks = m.d_chunks;
+	e.n_chunks = (uint32_t)m.chunks.size(); e.n_units = (uint32_t)m.units.size(); e.n_orient_max = m.n_orient_max; e.n_cols = n;
+	e.path2 = m.d_path2; e.trans2 = m.d_trans2; e.out_score = m.d_score; e.unit_x2 = m.d_unit_x; e.guess = m.d_guess; e.sel = m.d_sel; e.counters = m.d_bt_counters;
+	e.path_index = m.d_path_index; e.path_trans = m.d_path_trans;
+	if (m.device_superreads) e.super = m.super_args;
+	void* d_entry = nullptr;
+	HIP_TRY(up.alloc(&d_entry, sizeof(BtGroupEntry)));
+	HIP_TRY(hipMemcpyAsync(d_entry, &m.h_bt_entry, sizeof(BtGroupEntry), hipMemcpyHostToDevice, up.stream));   // (the source is a member: it outlives the copy)
+	HIP_TRY(hipEventRecord(m.ev_upload, up.stream));
+	m.d_bt_entry = (BtGroupEntry*)d_entry;
+	return WHAMD_OK;
+}
+
+// Everything whamd_dptable_create does after the planner, phase by phase (DESIGN.md 6.1 lists what crosses between them).
+whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
+	Impl& m = *impl_;
+	whamd_status_t st = m.open(device, msg);
+	if (st != WHAMD_OK || p.n_cols == 0) return st;
+	TableBuild b;
+	b.n = p.n_cols;
+	b.tbits = 2 * p.n_triples;
+	b.ni = std::max<uint32_t>(p.n_ind, 1);
+	m.dp.n_cols = b.n;
+	m.dp.T = p.T;
+	m.dp.tbits = b.tbits;
+	m.dp.n_ind = p.n_ind;
+	// ---- host: path and plan, column descriptors, the layout of the backtrace arena
+	if ((st = m.choose_plan(p, b, msg)) != WHAMD_OK) return st;
+	b.ped_slots = m.use_slots && m.splan.ped;
+	b.laps.next_stage();
+	if (debug_env("WHAMD_DEBUG_PLAN")) m.dump_plan(p);
+	if ((st = m.describe_columns(p, b, msg)) != WHAMD_OK) return st;
+	if ((st = m.lay_out_arena(p, b, msg)) != WHAMD_OK) return st;
+	// ---- the upload opens: everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the
+	// solve behind ev_upload.  WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.
+	m.upload_stream = debug_env("WHAMD_UPLOAD_ON_TABLE_STREAM") ? nullptr : upload_stream_of(device);
+	if (!m.upload_stream) m.upload_stream = m.stream;
+	if (m.upload_stream == m.stream) m.own_stream_used = true;
+	TableUploader up(device, m.upload_stream, m.allocations);
+	b.laps.lap("staging area taken");
+	up.open_block(m.upload_bound(p, b));
+	b.laps.lap("staging image sized, device block taken");
+	// ---- the device block fills in this order; the image leaves in pieces of 32 MB
+	if ((st = m.upload_column_arrays(p, b, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.upload_slot_arrays(b, up, msg)) != WHAMD_OK) return st;
+	m.make_jobs();
+	m.make_units(b);
+	if ((st = m.make_windows(b, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.take_result_block(b.n, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.make_chunks(p, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.take_solve_buffers(p, b, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.make_lanes(b, up, msg)) != WHAMD_OK) return st;
+	if ((st = m.make_schedule(b, msg)) != WHAMD_OK) return st;
+	m.make_briefs();
+	if ((st = m.upload_entries(up, msg)) != WHAMD_OK) return st;
+	// ---- the image's tail and the table kernels go out; what follows only completes what the solve's launches read
+	if ((st = m.launch_table_kernels(p, b, up, msg)) != WHAMD_OK) return st;
+	b.laps.summary((double)b.bt / 1e9);
+	if ((st = m.arm_debug_stamps(up, msg)) != WHAMD_OK) return st;
+	if ((st = opt_in_large_lds(device, msg)) != WHAMD_OK) return st;
+	return m.record_group_backtrace(b.n, up, msg);
 }
 
 whamd_status_t DeviceTable::solve(const Problem& p, Solution& s, whamd_solve_stats& st, std::string& msg) {
