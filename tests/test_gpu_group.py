@@ -92,6 +92,60 @@ def test_24_different_tables_batched_equal_one_by_one_and_the_oracle(tables_and_
         t.close()
 
 
+def test_250_tables_of_ten_problems_in_one_group(tables_and_alone):
+    """250 tables, ten narrow problems of the_24_tables() in turn -- the 1 800-column single (chunked backtrace), the four shorter singles,
+    an irregular one, a tie-heavy one, two short trios, the 300-column quartet -- each equal to the solve of its problem alone (which the
+    test above compares with the oracle).  More members than one launch's argument block holds (SLOT_GROUP_MAX = BT_GROUP_MAX = 248), but
+    this mix does NOT fill a block: its runs spread over several kernel variants (at most 175 of one in a super-step) and only 50 members
+    walk back in chunks.  The test below is the one that overflows."""
+    cases, alone = tables_and_alone
+    picks = (3, 4, 5, 6, 7, 11, 14, 18, 19, 22)
+    assert [cases[i][0] for i in picks] == ["single"] * 5 + ["irregular", "ties", "trio", "trio", "quartet"]
+    order = [picks[k % len(picks)] for k in range(250)]
+    tables = [_native.NativeTable(cases[i][1], solve=False) for i in order]
+    _native.enqueue_many(tables)
+    _native.wait_many(tables)
+    for k, (t, i) in enumerate(zip(tables, order)):
+        got = table_solution(t)
+        assert got == alone[i], (k, i, cases[i][0], first_difference(alone[i], got))
+    stats = [t.stats() for t in tables]
+    for t in tables:
+        t.close()
+    assert all(s["group_tables"] == 250 for s in stats), "the 250 tables did not share their launches"
+    assert any(s["bt_chunks"] > 0 for s in stats), "no table of the batch went through the chunked backtrace"
+
+
+def test_250_runs_of_one_kernel_overflow_a_group_launch_and_the_batched_backtrace(tables_and_alone):
+    """250 tables of ONE problem, the 900-column single: one component, a run in every super-step but the last and more than 2 x 16 units, so
+    every super-step collects 250 runs of the same kernel variant and 250 members walk back in chunks.  An argument block holds 248
+    (SLOT_GROUP_MAX = BT_GROUP_MAX): each super-step's batch is flushed in its middle (248 runs + 2) and the batched backtrace is cut in two.
+    Every table equals the solve alone, and counts the forward launches it counts in a group of two: a table is in exactly one of the two
+    launches of a super-step, whichever side of the cut it is on."""
+    cases, alone = tables_and_alone
+    problem, want = cases[4][1], alone[4]
+    plan = _native.plan_summary(problem)
+    assert plan["n_components"] == 1 and plan["n_runs"] == plan["n_steps"] - 1 and plan["n_steps"] > 32, plan
+    pair = [_native.NativeTable(problem, solve=False) for _ in range(2)]
+    _native.enqueue_many(pair)
+    _native.wait_many(pair)
+    launches = pair[0].stats()["forward_launches"]
+    assert launches >= plan["n_runs"] and pair[1].stats()["forward_launches"] == launches
+    for t in pair:
+        t.close()
+    tables = [_native.NativeTable(problem, solve=False) for _ in range(250)]
+    _native.enqueue_many(tables)
+    _native.wait_many(tables)
+    for k, t in enumerate(tables):
+        got = table_solution(t)
+        assert got == want, (k, first_difference(want, got))
+    stats = [t.stats() for t in tables]
+    for t in tables:
+        t.close()
+    assert all(s["group_tables"] == 250 for s in stats), "the 250 tables did not share their launches"
+    assert all(s["bt_chunks"] > 0 for s in stats), "a table did not go through the chunked backtrace"
+    assert [s["forward_launches"] for s in stats] == [launches] * 250, "a table on one side of the cut counted another number of launches"
+
+
 def test_batch_with_tables_outside_the_group(tables_and_alone):
     """Per-column and LDS-resident tables keep their own streams next to a group; a table with connected components brings several
     runs per super-step into the group launch."""

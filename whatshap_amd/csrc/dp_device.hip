@@ -67,6 +67,31 @@ bool select_kernels(uint32_t T, uint32_t n_ind, FusedFn& ff, KeysFn& kf) {
 	return false;
 }
 
+// The kernels of the solve, one pointer type per signature.  Which instantiation a run takes is decided by the *_kernel functions of "launch tables of the
+// solve", which stand BELOW opt_in_large_lds: the compiler emits the instantiations in the order they are first named, and that table names most of them first.
+using SegmentFn = void (*)(DevProblem, ResSegment, const uint32_t*, uint32_t*, uint32_t*);
+using PedSegmentFn = void (*)(DevProblem, ResSegment, const uint32_t*, uint32_t*);
+using ResBatchFn = void (*)(DevProblem, const ResBatchEntry*);
+using SlotRunFn = void (*)(DevProblem, SlotRun, const uint32_t*, uint32_t*, uint32_t*);
+using SlotRunXFn = void (*)(DevProblem, SlotRun, const uint32_t*, uint32_t*, uint32_t*, uint32_t);
+using PedSlotRunFn = void (*)(DevProblem, SlotRun, PedSlotExtra, const uint32_t*, uint32_t*);
+using SlotBatchFn = void (*)(DevProblem, const SlotBatchEntry*);
+using GroupFn = void (*)(SlotGroupArgs);
+
+// The kernel variants of a group launch (DESIGN.md 6.2 has the table).  The values are the order of the launches inside a super-step.
+enum GroupVariant : uint8_t { GV_SINGLE4 = 0, GV_PED_2_2, GV_PED_2_4, GV_PED_4_2, GV_PED_4_4, GV_PED_2_16, GV_SINGLE8, GV_TRIO_FACT, GV_X4, GV_X8, GV_QUARTET_FACT, GROUP_VARIANTS };
+struct GroupVariantPair { GroupVariant plain, x; };   // x: the X kernel's variant where the run is eligible (else = plain)
+
+GroupVariantPair group_variants_of(const SlotBatchEntry& he, bool ped) {
+	if (ped) {
+		const GroupVariant v = he.ex.nf == (uint32_t)PSLOT_FACT4 ? GV_QUARTET_FACT : he.ex.nf == (uint32_t)PSLOT_FACT ? GV_TRIO_FACT : he.ex.nf == 16 ? GV_PED_2_16
+		                       : he.ex.tb == 4 ? (he.ex.nf == 4 ? GV_PED_4_4 : GV_PED_4_2) : (he.ex.nf == 4 ? GV_PED_2_4 : GV_PED_2_2);
+		return {v, v};
+	}
+	const GroupVariant v = he.run.lr == 3 ? GV_SINGLE8 : GV_SINGLE4;
+	return {v, (he.run.yflags & 8u) ? (he.run.lr == 3 ? GV_X8 : GV_X4) : v};
+}
+
 }  // namespace
 
 // ================================================================================================ what a create shares between its phases
@@ -227,7 +252,6 @@ struct TableBuild {
 struct DeviceTable::Impl {
 	int device = 0;
 	hipStream_t stream = nullptr;
-	hipStream_t run_stream = nullptr;   // where the forward steps of the solve being submitted go: `stream`, or the stream of the group's first table (enqueue_group)
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	hipEvent_t ev_group = nullptr;      // group solve: "the forward pass of every table of the group is submitted up to here"
 	hipEvent_t ev_upload = nullptr;     // "everything upload() put on `stream` -- the copies, the table kernels -- is done": a solve waits for it ON THE DEVICE (begin_solve)
@@ -254,10 +278,7 @@ struct DeviceTable::Impl {
 	bool fold = true;
 	int symmetry = 1;  // single individual: compute only half of a run, the rest is its mirror image (plan_forward)
 	uint64_t bt_bytes = 0;
-	uint64_t launches = 0;
-	uint32_t group_tables = 1;  // tables that shared the forward launches of the solve in flight (enqueue_group)
 	uint32_t max_grid_x = 1;    // widest launch of the schedule, in workgroups
-	bool enqueue_open = false;  // resumable enqueue (enqueue_some)
 	size_t h_pinned_bytes = 0;
 	uint32_t* h_pinned = nullptr;  // [2 n + jobs + 3]: path index, path transmission, score of the final job, scores of the others, the chunked backtrace's three counters
 	// A job is a sequence of forward steps with its own backtrace.  Job 0 ("final") is the last connected component (it
@@ -299,7 +320,7 @@ struct DeviceTable::Impl {
 	// 320-byte SlotBatchEntry and a SuperStep per table and super-step out of cold memory -- 31 ms of host time for 2 276 super-steps, 13 ms with these
 	// (scripts/gpu_group_submit_ab.py).  Built at create time (where the entries are made, on the create's own threads).
 	struct StepBrief { uint32_t entry_off, lds; uint16_t entry_count; uint8_t has_singles, pad; };
-	struct EntryBrief { uint16_t grid_x, threads; uint32_t lds_x; uint8_t variant, variant_x, pad[2]; };   // variant_x: the X kernel's variant where the run is eligible (else = variant)
+	struct EntryBrief { uint16_t grid_x, threads; uint32_t lds_x; GroupVariantPair variant; uint8_t pad[2]; };
 	std::vector<StepBrief> step_brief;
 	std::vector<EntryBrief> entry_brief;
 	std::vector<ResBatchEntry> entries;
@@ -333,7 +354,6 @@ struct DeviceTable::Impl {
 	bool side_by_side = false;  // this solve's launches run beside other tables' on their own streams: X runs take the streamed variant (16 KB of LDS instead of ~90:
 	                            // three tables on three streams, 3.1 M columns/s with the LDS lines -- one workgroup per CU, the streams take turns -- 5 M without)
 	int max_lanes = 32;
-	size_t next_super = 0;  // cursor of the resumable enqueue
 	// Windowed solve (backtrace arena larger than what HBM can hold): the steps are cut into WINDOWS whose records fit the
 	// arena one at a time.  Pass 1 runs the whole forward pass (records of all windows but the last are written and
 	// dropped) and keeps the exchange column at every window boundary; then, newest window first, the window's steps
@@ -375,13 +395,36 @@ struct DeviceTable::Impl {
 	whamd_status_t launch_table_kernels(const Problem& p, const TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t arm_debug_stamps(TableUploader& up, std::string& msg);
 	whamd_status_t record_group_backtrace(uint32_t n, TableUploader& up, std::string& msg);
-	// the solve
+	// The solve being submitted or awaiting collection.  (own_stream_used and upload_pending below describe the stream and the upload, not a solve.)
+	struct SolveInFlight {
+		hipStream_t run_stream = nullptr;   // where the forward steps go: `stream`, or the stream of the group's lead.  Set where a solve opens (enqueue_some_unguarded,
+		                                    // GroupSubmission::open_members); read by begin_solve, the launch_* functions, submit_super_step, submit_singles
+		uint32_t group_tables = 1;          // tables that shared the forward launches.  Set where a solve opens; read by wait (whamd_solve_stats)
+		bool enqueue_open = false;          // a solve has been opened and its tail is not submitted yet.  Set where a solve opens, cleared by rewind; read by
+		                                    // enqueue_some_unguarded (resume or open) and group_eligible
+		size_t next_super = 0;              // cursor of the resumable enqueue.  Set by begin_solve and rewind, advanced and read by enqueue_some_unguarded only
+		uint64_t launches = 0;              // forward launches so far.  Set by begin_solve, enqueue_some_unguarded and GroupSubmission::submit_tails; read by wait
+		hipStream_t tail_stream = nullptr;  // where the tail (backtrace, downloads) went, and its place in the order of all tails of the process.  Set by submit_tail;
+		uint64_t tail_seq = 0;              // read by wait_last_of_each_stream
+		bool tail_elsewhere = false;        // the tail went onto another table's stream.  Set by submit_tail; read by wait (waits for ev3, not for `stream`),
+		                                    // wait_last_of_each_stream and release
+		bool timing_pending = false;        // wait has collected a solve whose event timings nobody has read yet.  Set by wait, cleared by begin_solve (the events
+		                                    // are the new solve's from there on) and read_timing
+		static inline std::atomic<uint64_t> tails_submitted{0};   // numbers tail_seq
+		// No solve is being submitted: the next enqueue begins with the preamble again, on the table's own stream.
+		void rewind(hipStream_t own) { enqueue_open = false; next_super = 0; run_stream = own; }
+	} inflight;
+	// the solve, step by step
+	struct GroupSubmission;
 	void launch_column_step(const Problem& p, const Step& step, const Lane& lane, const uint32_t* prev, uint32_t* cur, uint64_t& launches);
-	void launch_run(const ResBatchEntry& e, uint32_t step_index, uint64_t& launches);
+	void launch_run(const ResBatchEntry& e, uint64_t& launches);
 	void launch_slot_run(const SlotBatchEntry& e, uint64_t& launches);
 	whamd_status_t begin_solve(const Problem& p, Solution& s, std::string& msg);
+	whamd_status_t submit_super_step(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg);
 	whamd_status_t submit_singles(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg);
-	whamd_status_t submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream = nullptr, bool backtrace_done = false, bool superreads_done = false);
+	whamd_status_t submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream = nullptr, bool walked_by_group = false);
+	whamd_status_t report_slot_stamps(std::string& msg) const;
+	whamd_status_t report_resident_stamps(std::string& msg) const;
 	BtGroupEntry h_bt_entry{};          // what a batched backtrace launch reads for this table (kernels_backtrace.h backtrace_chunks_group), and its device copy
 	BtGroupEntry* d_bt_entry = nullptr;
 	// get_super_reads on the device (kernels_backtrace.h superreads_single): a table with one individual and trusted genotypes
@@ -392,10 +435,6 @@ struct DeviceTable::Impl {
 	                                    // solve and tail are on the lead's stream, its uploads on an upload stream -- release() then has nothing to wait for there)
 	bool upload_pending = false;        // the uploads went through a shared upload stream and no solve has been ordered behind `ev_upload` yet
 	hipStream_t upload_stream = nullptr;
-	bool timing_pending = false;        // wait() has collected a solve whose event timings nobody has read yet (read_timing)
-	hipStream_t tail_stream = nullptr;  // where submit_tail put the tail of the solve in flight, and its place in the order of all tails of the process
-	uint64_t tail_seq = 0;
-	bool tail_elsewhere = false;        // the tail (backtrace, downloads) of the solve in flight went onto another table's stream: wait() waits for ev3, not for `stream`
 
 	// the pooled stream and events (device_runtime.h), taken on the first create and given back by release_device
 	void adopt(const StreamSet& ss) { stream = ss.stream; ev0 = ss.ev[0]; ev1 = ss.ev[1]; ev2 = ss.ev[2]; ev3 = ss.ev[3]; ev_group = ss.ev[4]; ev_upload = ss.ev[5]; }
@@ -416,8 +455,8 @@ struct DeviceTable::Impl {
 	}
 
 	void release() {
-		if (tail_elsewhere && ev3) (void)hipEventSynchronize(ev3);   // (a solve whose tail ran on the group's lead stream: nothing of it may still be reading the buffers)
-		tail_elsewhere = false;
+		if (inflight.tail_elsewhere && ev3) (void)hipEventSynchronize(ev3);   // (a solve whose tail ran on the group's lead stream: nothing of it may still be reading the buffers)
+		inflight.tail_elsewhere = false;
 		if (upload_pending && ev_upload) (void)hipEventSynchronize(ev_upload);   // (a table closed without a solve: its copies may still be on the upload stream)
 		upload_pending = false;
 		release_lanes();
@@ -456,8 +495,8 @@ void DeviceTable::release_device() {
 		streamset_give(m.stream_set());
 	}
 	m.adopt(StreamSet());
-	m.run_stream = nullptr;
-	m.timing_pending = false;
+	m.inflight.run_stream = nullptr;
+	m.inflight.timing_pending = false;
 }
 
 int DeviceTable::device_count() {
@@ -1353,13 +1392,7 @@ void DeviceTable::Impl::make_briefs() {
 			eb.grid_x = (uint16_t)(1u << (he.run.g - he.run.half));
 			eb.threads = (uint16_t)he.run.threads;
 			eb.lds_x = (uint32_t)((size_t)2 * he.run.threads * (4u << he.run.lr));
-			// kernel variants of a group launch: 0 single individual (four cells per thread); 1 .. 5 pedigree runs (TB, NF) = (2,2) (2,4) (4,2) (4,4) (2,16); 6 single, eight cells;
-			// 7 trio on factorised lines; 8 / 9 X runs with four / eight cells (slot_groupx); 10 quartet on factorised lines
-			if (m.splan.ped) eb.variant = eb.variant_x = (uint8_t)(he.ex.nf == (uint32_t)PSLOT_FACT4 ? 10 : he.ex.nf == (uint32_t)PSLOT_FACT ? 7 : (he.ex.nf == 16 ? 5 : 1 + (he.ex.tb == 4 ? 2 : 0) + (he.ex.nf == 4 ? 1 : 0)));
-			else {
-				eb.variant = (uint8_t)(he.run.lr == 3 ? 6 : 0);
-				eb.variant_x = (he.run.yflags & 8u) ? (uint8_t)(he.run.lr == 3 ? 9 : 8) : eb.variant;
-			}
+			eb.variant = group_variants_of(he, m.splan.ped);
 			m.entry_brief.push_back(eb);
 		}
 	}
@@ -1557,6 +1590,106 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 	return m.record_group_backtrace(b.n, up, msg);
 }
 
+// ---------------------------------------------------------------------------------------------- launch tables of the solve
+// Which instantiation a run takes, one function per kernel signature; the launch_* functions and the group's flush compute grid, block and LDS, ask here
+// and launch.  (They stand here, and in this order, because the instantiations are emitted in the order they are first named: see opt_in_large_lds.  The
+// instantiations with cycle stamps and timing switches exist in the debug library only, debug_build.h: `stamps` is false in the product.)
+namespace {
+
+SegmentFn segment_kernel(bool stamps, bool sym) {
+#ifdef WHAMD_DEBUG_BUILD
+	if (stamps) return resident_segment<true, true>;
+#endif
+	return sym ? resident_segment<false, true> : resident_segment<false, false>;
+}
+
+PedSegmentFn ped_segment_kernel(bool stamps, bool spec) {
+#ifdef WHAMD_DEBUG_BUILD
+	if (stamps) return resident_segment_ped<true>;
+#endif
+	return spec ? resident_segment_ped<false, true> : resident_segment_ped<false>;
+}
+
+ResBatchFn resident_batch_kernel(bool sym) { return sym ? resident_batch<true> : resident_batch<false>; }
+
+#ifdef WHAMD_DEBUG_BUILD
+// X run of a pedigree (kernels_pedslots.h pedslot_runx; WHAMD_PED_XRUN=1): the costs of xc = 16 or 32 columns formed in the prologue, scalars through the scalar cache
+PedSlotRunFn pedslot_runx_kernel(uint32_t tb, uint32_t nf, uint32_t xc, bool spec) {
+#define WHAMD_ROW(TB, NF) { pedslot_runx<TB, NF, 16, true>, pedslot_runx<TB, NF, 16, false>, pedslot_runx<TB, NF, 32, true>, pedslot_runx<TB, NF, 32, false> }
+	static const PedSlotRunFn table[6][4] = {WHAMD_ROW(2, PSLOT_FACT), WHAMD_ROW(2, 16), WHAMD_ROW(2, 2), WHAMD_ROW(2, 4), WHAMD_ROW(4, 2), WHAMD_ROW(4, 4)};
+#undef WHAMD_ROW
+	const int row = tb == 2 ? (nf == (uint32_t)PSLOT_FACT ? 0 : nf == 16 ? 1 : nf == 2 ? 2 : 3) : (nf == 2 ? 4 : 5);
+	return table[row][(xc == 16 ? 0 : 2) + (spec ? 0 : 1)];
+}
+#endif
+
+PedSlotRunFn pedslot_run_kernel(uint32_t tb, uint32_t nf, bool spec, bool packed) {
+#define WHAMD_ROW(TB, NF) { pedslot_run<TB, NF, true, true>, pedslot_run<TB, NF, true, false>, pedslot_run<TB, NF, false, true>, pedslot_run<TB, NF, false, false> }
+	static const PedSlotRunFn table[7][4] = {WHAMD_ROW(2, PSLOT_FACT), WHAMD_ROW(4, PSLOT_FACT4), WHAMD_ROW(2, 16), WHAMD_ROW(2, 2), WHAMD_ROW(2, 4), WHAMD_ROW(4, 2), WHAMD_ROW(4, 4)};
+#undef WHAMD_ROW
+	const int row = tb == 2 && nf == (uint32_t)PSLOT_FACT ? 0 : tb == 4 && nf == (uint32_t)PSLOT_FACT4 ? 1 : tb == 2 ? (nf == 16 ? 2 : nf == 2 ? 3 : 4) : (nf == 2 ? 5 : 6);
+	return table[row][(spec ? 0 : 2) + (packed ? 0 : 1)];
+}
+
+// X run of a single individual, four cells per thread; xc: columns whose operands the prologue forms (0: streamed operands, which has no form with stamps)
+SlotRunXFn slot_runx_kernel(uint32_t xc, bool stamps, bool spec) {
+#define WHAMD_PAIR(XC, STAMPS) { slot_runx<2, XC, STAMPS, true>, slot_runx<2, XC, STAMPS, false> }
+#ifdef WHAMD_DEBUG_BUILD
+	static const SlotRunXFn stamped[2][2] = {WHAMD_PAIR(24, true), WHAMD_PAIR(32, true)};
+	if (stamps && xc) return stamped[xc == 24 ? 0 : 1][spec ? 0 : 1];
+#endif
+	static const SlotRunXFn table[5][2] = {WHAMD_PAIR(0, false), WHAMD_PAIR(8, false), WHAMD_PAIR(16, false), WHAMD_PAIR(24, false), WHAMD_PAIR(32, false)};
+#undef WHAMD_PAIR
+	return table[xc / 8][spec ? 0 : 1];
+}
+
+// Slot run of a single individual: 2^lr cells per thread; Y form (slot_plan.cpp): one instruction per cell-column
+SlotRunFn slot_run_kernel(uint32_t lr, bool yform, bool stamps, bool spec) {
+#ifdef WHAMD_DEBUG_BUILD
+#define WHAMD_ROW(LR, YF) { slot_run<LR, true, true, YF>, slot_run<LR, true, false, YF>, slot_run<LR, false, true, YF>, slot_run<LR, false, false, YF> }
+#else
+#define WHAMD_ROW(LR, YF) { nullptr, nullptr, slot_run<LR, false, true, YF>, slot_run<LR, false, false, YF> }
+#endif
+	static const SlotRunFn table[5][4] = {WHAMD_ROW(3, true), WHAMD_ROW(3, false), WHAMD_ROW(1, false), WHAMD_ROW(2, true), WHAMD_ROW(2, false)};
+#undef WHAMD_ROW
+	const int row = lr == 3 ? (yform ? 0 : 1) : lr == 1 ? 2 : (yform ? 3 : 4);
+	return table[row][(stamps ? 0 : 2) + (spec ? 0 : 1)];
+}
+
+SlotBatchFn slot_batch_kernel(int lr) {
+	if (lr == 1) return slot_batch<1>;
+	if (lr == 3) return slot_batch<3>;
+	return slot_batch<2>;
+}
+
+// tight: the variants held to 80 SGPRs (four workgroups per CU); dbg: the lead's timing switches (debug library)
+GroupFn group_kernel(GroupVariant v, bool dbg, bool tight) {
+	switch (v) {
+		case GV_SINGLE4:
+#ifdef WHAMD_DEBUG_BUILD
+			if (dbg) return slot_group<2, true, false>;
+#endif
+			return tight ? slot_group<2, false, true> : slot_group<2, false, false>;
+		case GV_PED_2_2: return pedslot_group<2, 2>;
+		case GV_PED_2_4: return pedslot_group<2, 4>;
+		case GV_PED_4_2: return pedslot_group<4, 2>;
+		case GV_PED_4_4: return pedslot_group<4, 4>;
+		case GV_PED_2_16: return pedslot_group<2, 16>;
+		case GV_SINGLE8: return tight ? slot_group<3, false, true> : slot_group<3, false, false>;
+		case GV_TRIO_FACT: return pedslot_group<2, PSLOT_FACT>;
+		case GV_X4: return slot_groupx<2, false>;
+		case GV_X8: return slot_groupx<3, false>;
+		case GV_QUARTET_FACT: return pedslot_group<4, PSLOT_FACT4>;
+		case GROUP_VARIANTS: break;
+	}
+	return nullptr;
+}
+
+}  // namespace
+
+// ================================================================================================ solve: one table
+// enqueue_some opens the solve (begin_solve), submits super-steps (submit_super_step) and, when none is left, the tail (submit_tail); wait collects.
+// DESIGN.md 6.2 lists the steps and what crosses between them.
 whamd_status_t DeviceTable::solve(const Problem& p, Solution& s, whamd_solve_stats& st, std::string& msg) {
 	whamd_status_t status = enqueue(p, s, msg);
 	if (status != WHAMD_OK) return status;
@@ -1575,6 +1708,7 @@ whamd_status_t DeviceTable::enqueue(const Problem& p, Solution& s, std::string& 
 void DeviceTable::Impl::launch_column_step(const Problem& p, const Step& step, const Lane& lane, const uint32_t* prev, uint32_t* cur,
                                            uint64_t& launches) {
 	Impl& m = *this;
+	const hipStream_t rs = m.inflight.run_stream;
 	DevProblem dp = m.dp;
 	dp.keys = lane.d_keys;
 	const uint32_t c = step.index;
@@ -1582,43 +1716,35 @@ void DeviceTable::Impl::launch_column_step(const Problem& p, const Step& step, c
 	if (d.mode == 0) {
 		const uint32_t threads = 1u << d.f;
 		const uint32_t block = std::min<uint32_t>(256, threads);
-		hipLaunchKernelGGL(m.fused, dim3(threads / block), dim3(block), 0, m.run_stream, dp, c, prev, cur);
+		hipLaunchKernelGGL(m.fused, dim3(threads / block), dim3(block), 0, rs, dp, c, prev, cur);
 		launches += 1;
 	} else {
 		const uint64_t total = (1ull << (d.f + d.ebits - d.eloop)) * (m.wide ? p.T : 1u);
 		const uint32_t block = (uint32_t)std::min<uint64_t>(256, (total + 63) / 64 * 64);
-		if (m.wide) hipLaunchKernelGGL(column_step_wide, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, m.run_stream, dp, c, prev, (uint32_t)total);
-		else hipLaunchKernelGGL(m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, m.run_stream, dp, c, prev, (uint32_t)total);
+		if (m.wide) hipLaunchKernelGGL(column_step_wide, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
+		else hipLaunchKernelGGL(m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
 		const uint32_t entries = (1u << d.f) * p.T;
 		const uint32_t fblock = std::min<uint32_t>(256, (entries + 63) / 64 * 64);
-		hipLaunchKernelGGL(column_finalize, dim3((entries + fblock - 1) / fblock), dim3(fblock), 0, m.run_stream, dp, c, cur, entries);
+		hipLaunchKernelGGL(column_finalize, dim3((entries + fblock - 1) / fblock), dim3(fblock), 0, rs, dp, c, cur, entries);
 		launches += 2;
 	}
 }
 
 // One run as a launch of its own (kernel arguments by value).
-void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint32_t step_index, uint64_t& launches) {
+void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 	Impl& m = *this;
 	const ResSegment& sg = e.sg;
+	const hipStream_t rs = m.inflight.run_stream;
+	const bool stamps = DEBUG_BUILD && m.dp.dbg != nullptr;
 	if (sg.kind == 1) {
 		const size_t words = ((size_t)sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)sg.n_terms * 2 + 3) & ~(size_t)3;
 		const size_t lds_ped = words * 4 + 2 * ((size_t)16 << sg.max_l) + (size_t)sg.stage_words * 8;
-#ifdef WHAMD_DEBUG_BUILD
-		if (m.dp.dbg) hipLaunchKernelGGL(resident_segment_ped<true>, dim3(1u << sg.g), dim3(sg.threads), lds_ped, m.run_stream, m.dp, sg, e.prev, e.cur);
-		else
-#endif
-		if (sg.in_mirror_bit && m.use_chunks) hipLaunchKernelGGL((resident_segment_ped<false, true>), dim3(1u << sg.g), dim3(sg.threads), lds_ped, m.run_stream, m.dp, sg, e.prev, e.cur);
-		else hipLaunchKernelGGL(resident_segment_ped<false>, dim3(1u << sg.g), dim3(sg.threads), lds_ped, m.run_stream, m.dp, sg, e.prev, e.cur);
+		const PedSegmentFn kernel = ped_segment_kernel(stamps, sg.in_mirror_bit && m.use_chunks);
+		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, m.dp, sg, e.prev, e.cur);
 	} else {
 		const size_t lds = (size_t)sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << sg.max_l) + (size_t)sg.stage_words * 8;
-		const bool sym = sg.half || sg.in_half || sg.mirror_out;
-		const dim3 grid(1u << (sg.g - sg.half)), block(sg.threads);
-#ifdef WHAMD_DEBUG_BUILD
-		if (m.dp.dbg) hipLaunchKernelGGL((resident_segment<true, true>), grid, block, lds, m.run_stream, m.dp, sg, e.prev, e.cur, e.score_out);
-		else
-#endif
-		if (sym) hipLaunchKernelGGL((resident_segment<false, true>), grid, block, lds, m.run_stream, m.dp, sg, e.prev, e.cur, e.score_out);
-		else hipLaunchKernelGGL((resident_segment<false, false>), grid, block, lds, m.run_stream, m.dp, sg, e.prev, e.cur, e.score_out);
+		const SegmentFn kernel = segment_kernel(stamps, sg.half || sg.in_half || sg.mirror_out);
+		hipLaunchKernelGGL(kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, m.dp, sg, e.prev, e.cur, e.score_out);
 	}
 	launches += 1;
 }
@@ -1627,43 +1753,24 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint32_t step_index, 
 void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launches) {
 	Impl& m = *this;
 	const SlotRun& run = e.run;
+	const hipStream_t rs = m.inflight.run_stream;
 	const bool spec = run.spec_id != 0 && m.use_chunks && !debug_env("WHAMD_NO_SPEC_KERNEL");
+	const bool stamps = DEBUG_BUILD && (m.dp.dbg != nullptr || m.dp.dbg_flags != 0);
+	launches += 1;
 	if (m.splan.ped) {
 		const PedSlotExtra& ex = m.splan.pextra[e.pad];
-		const size_t lds_ped = pedslot_lds_bytes(run.threads, run.ncols, ex);
-		const dim3 grid(1u << run.g), block(run.threads);
+		size_t lds = pedslot_lds_bytes(run.threads, run.ncols, ex);
+		PedSlotRunFn kernel = pedslot_run_kernel(ex.tb, ex.nf, spec, (run.yflags & 16u) != 0);
 #ifdef WHAMD_DEBUG_BUILD
-		if ((run.yflags & 8u) && !m.side_by_side) {   // X run (kernels_pedslots.h, pedslot_runx; WHAMD_PED_XRUN=1): the costs of every column formed in the prologue, scalars through the scalar cache
-#define WHAMD_PSLOTX_LAUNCH2(TBV, NFV, XCV) do { const size_t lds_x = pedslotx_lds_bytes(run.threads, XCV); \
-		if (spec) hipLaunchKernelGGL((pedslot_runx<TBV, NFV, XCV, true>), grid, block, lds_x, m.run_stream, m.dp, run, ex, e.prev, e.cur); \
-		else hipLaunchKernelGGL((pedslot_runx<TBV, NFV, XCV, false>), grid, block, lds_x, m.run_stream, m.dp, run, ex, e.prev, e.cur); } while (0)
-#define WHAMD_PSLOTX_LAUNCH(TBV, NFV) do { if (run.ncols <= 16u) WHAMD_PSLOTX_LAUNCH2(TBV, NFV, 16); else WHAMD_PSLOTX_LAUNCH2(TBV, NFV, 32); } while (0)
-			if (ex.tb == 2 && ex.nf == (uint32_t)PSLOT_FACT) WHAMD_PSLOTX_LAUNCH(2, PSLOT_FACT);
-			else if (ex.tb == 2 && ex.nf == 16) WHAMD_PSLOTX_LAUNCH(2, 16);
-			else if (ex.tb == 2 && ex.nf == 2) WHAMD_PSLOTX_LAUNCH(2, 2);
-			else if (ex.tb == 2) WHAMD_PSLOTX_LAUNCH(2, 4);
-			else if (ex.nf == 2) WHAMD_PSLOTX_LAUNCH(4, 2);
-			else WHAMD_PSLOTX_LAUNCH(4, 4);
-#undef WHAMD_PSLOTX_LAUNCH
-#undef WHAMD_PSLOTX_LAUNCH2
-			launches += 1;
-			return;
+		if ((run.yflags & 8u) && !m.side_by_side) {   // X run (WHAMD_PED_XRUN=1)
+			const uint32_t xc = run.ncols <= 16u ? 16u : 32u;
+			lds = pedslotx_lds_bytes(run.threads, xc);
+			kernel = pedslot_runx_kernel(ex.tb, ex.nf, xc, spec);
 		}
 #endif
-#define WHAMD_PSLOT_LAUNCH(TBV, NFV, SPECV) do { if (run.yflags & 16u) hipLaunchKernelGGL((pedslot_run<TBV, NFV, SPECV, true>), grid, block, lds_ped, m.run_stream, m.dp, run, ex, e.prev, e.cur); \
-		else hipLaunchKernelGGL((pedslot_run<TBV, NFV, SPECV, false>), grid, block, lds_ped, m.run_stream, m.dp, run, ex, e.prev, e.cur); } while (0)
-		if (ex.tb == 2 && ex.nf == (uint32_t)PSLOT_FACT) { if (spec) WHAMD_PSLOT_LAUNCH(2, PSLOT_FACT, true); else WHAMD_PSLOT_LAUNCH(2, PSLOT_FACT, false); }
-		else if (ex.tb == 4 && ex.nf == (uint32_t)PSLOT_FACT4) { if (spec) WHAMD_PSLOT_LAUNCH(4, PSLOT_FACT4, true); else WHAMD_PSLOT_LAUNCH(4, PSLOT_FACT4, false); }
-		else if (ex.tb == 2 && ex.nf == 16) { if (spec) WHAMD_PSLOT_LAUNCH(2, 16, true); else WHAMD_PSLOT_LAUNCH(2, 16, false); }
-		else if (ex.tb == 2 && ex.nf == 2) { if (spec) WHAMD_PSLOT_LAUNCH(2, 2, true); else WHAMD_PSLOT_LAUNCH(2, 2, false); }
-		else if (ex.tb == 2) { if (spec) WHAMD_PSLOT_LAUNCH(2, 4, true); else WHAMD_PSLOT_LAUNCH(2, 4, false); }
-		else if (ex.nf == 2) { if (spec) WHAMD_PSLOT_LAUNCH(4, 2, true); else WHAMD_PSLOT_LAUNCH(4, 2, false); }
-		else { if (spec) WHAMD_PSLOT_LAUNCH(4, 4, true); else WHAMD_PSLOT_LAUNCH(4, 4, false); }
-#undef WHAMD_PSLOT_LAUNCH
-		launches += 1;
+		hipLaunchKernelGGL(kernel, dim3(1u << run.g), dim3(run.threads), lds, rs, m.dp, run, ex, e.prev, e.cur);
 		return;
 	}
-	const size_t lds = slot_run_lds_bytes(run.threads, run.lr, run.ncols);   // wave-slot exchange + hot lines + per-wave A + lane sums
 	const dim3 grid(1u << (run.g - run.half)), block(run.threads);
 	if ((run.yflags & 8u) && run.lr == 2u) {   // X run with four cells per thread: registers instead of LDS lines (LDS: the wave-slot exchange buffers + the threads' own operand lines)
 		// (no LDS lines: room for other tables' workgroups on the CU -- or, from 1 024 workgroups on, for FOUR of this table's own instead of two:
@@ -1672,51 +1779,15 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 		const size_t lds_x = streamed ? (size_t)2 * run.threads * 16 : slotx_lds_bytes(run.threads, (run.ncols + 7u) & ~7u);
 		// narrow tables: the run's workgroups packed onto one XCD (slot_runx: eight times the grid, every eighth workgroup works)
 		const uint32_t pack = (grid.x <= 32u && !m.side_by_side && !debug_env("WHAMD_NO_XCD_PACK")) ? 1u : 0u;
-		const dim3 xgrid(pack ? grid.x * 8u : grid.x);
-#define WHAMD_SLOTX_LAUNCH(XCV, DBGV, SPECV) hipLaunchKernelGGL((slot_runx<2, XCV, DBGV, SPECV>), xgrid, block, lds_x, m.run_stream, m.dp, run, e.prev, e.cur, e.score_out, pack)
-		if (streamed) {
-			if (spec) WHAMD_SLOTX_LAUNCH(0, false, true); else WHAMD_SLOTX_LAUNCH(0, false, false);
-		} else
-#ifdef WHAMD_DEBUG_BUILD
-		if (m.dp.dbg != nullptr || m.dp.dbg_flags != 0) {
-			if (run.ncols <= 24u) { if (spec) WHAMD_SLOTX_LAUNCH(24, true, true); else WHAMD_SLOTX_LAUNCH(24, true, false); }
-			else { if (spec) WHAMD_SLOTX_LAUNCH(32, true, true); else WHAMD_SLOTX_LAUNCH(32, true, false); }
-		} else
-#endif
-		if (run.ncols <= 8u) { if (spec) WHAMD_SLOTX_LAUNCH(8, false, true); else WHAMD_SLOTX_LAUNCH(8, false, false); }       // (the prologue forms the operands of XC columns:
-		else if (run.ncols <= 16u) { if (spec) WHAMD_SLOTX_LAUNCH(16, false, true); else WHAMD_SLOTX_LAUNCH(16, false, false); }   //  an irregular layout's runs are ~10 columns long)
-		else if (run.ncols <= 24u) { if (spec) WHAMD_SLOTX_LAUNCH(24, false, true); else WHAMD_SLOTX_LAUNCH(24, false, false); }
-		else { if (spec) WHAMD_SLOTX_LAUNCH(32, false, true); else WHAMD_SLOTX_LAUNCH(32, false, false); }
-#undef WHAMD_SLOTX_LAUNCH
-		launches += 1;
+		// the prologue forms the operands of XC columns (an irregular layout's runs are ~10 columns long); with stamps there are the two long forms only
+		const uint32_t xc = streamed ? 0u : (run.ncols <= 8u && !stamps) ? 8u : (run.ncols <= 16u && !stamps) ? 16u : run.ncols <= 24u ? 24u : 32u;
+		const SlotRunXFn kernel = slot_runx_kernel(xc, stamps, spec);
+		hipLaunchKernelGGL(kernel, dim3(pack ? grid.x * 8u : grid.x), block, lds_x, rs, m.dp, run, e.prev, e.cur, e.score_out, pack);
 		return;
 	}
-	// (the instantiations with cycle stamps and timing switches exist in the debug library only: debug_build.h)
-#ifdef WHAMD_DEBUG_BUILD
-	const bool dbg = m.dp.dbg != nullptr || m.dp.dbg_flags != 0;
-#define WHAMD_IF_DBG(stmt) if (dbg) { stmt; } else
-#else
-#define WHAMD_IF_DBG(stmt)
-#endif
-#define WHAMD_SLOT_LAUNCH(LRV, DBGV, SPECV) hipLaunchKernelGGL((slot_run<LRV, DBGV, SPECV>), grid, block, lds, m.run_stream, m.dp, run, e.prev, e.cur, e.score_out)
-	if (run.lr == 3 && (run.yflags & 1u)) {   // Y-form run, eight cells per thread
-#define WHAMD_SLOT_LAUNCH_Y3(DBGV, SPECV) hipLaunchKernelGGL((slot_run<3, DBGV, SPECV, true>), grid, block, lds, m.run_stream, m.dp, run, e.prev, e.cur, e.score_out)
-		WHAMD_IF_DBG(if (spec) WHAMD_SLOT_LAUNCH_Y3(true, true); else WHAMD_SLOT_LAUNCH_Y3(true, false)) { if (spec) WHAMD_SLOT_LAUNCH_Y3(false, true); else WHAMD_SLOT_LAUNCH_Y3(false, false); }
-#undef WHAMD_SLOT_LAUNCH_Y3
-	} else if (run.lr == 3) {
-		WHAMD_IF_DBG(if (spec) WHAMD_SLOT_LAUNCH(3, true, true); else WHAMD_SLOT_LAUNCH(3, true, false)) { if (spec) WHAMD_SLOT_LAUNCH(3, false, true); else WHAMD_SLOT_LAUNCH(3, false, false); }
-	} else if (run.lr == 1) {
-		WHAMD_IF_DBG(if (spec) WHAMD_SLOT_LAUNCH(1, true, true); else WHAMD_SLOT_LAUNCH(1, true, false)) { if (spec) WHAMD_SLOT_LAUNCH(1, false, true); else WHAMD_SLOT_LAUNCH(1, false, false); }
-	} else if (run.yflags & 1u) {   // Y-form run (slot_plan.cpp): one instruction per cell-column
-#define WHAMD_SLOT_LAUNCH_Y(DBGV, SPECV) hipLaunchKernelGGL((slot_run<2, DBGV, SPECV, true>), grid, block, lds, m.run_stream, m.dp, run, e.prev, e.cur, e.score_out)
-		WHAMD_IF_DBG(if (spec) WHAMD_SLOT_LAUNCH_Y(true, true); else WHAMD_SLOT_LAUNCH_Y(true, false)) { if (spec) WHAMD_SLOT_LAUNCH_Y(false, true); else WHAMD_SLOT_LAUNCH_Y(false, false); }
-#undef WHAMD_SLOT_LAUNCH_Y
-	} else {
-		WHAMD_IF_DBG(if (spec) WHAMD_SLOT_LAUNCH(2, true, true); else WHAMD_SLOT_LAUNCH(2, true, false)) { if (spec) WHAMD_SLOT_LAUNCH(2, false, true); else WHAMD_SLOT_LAUNCH(2, false, false); }
-	}
-#undef WHAMD_SLOT_LAUNCH
-#undef WHAMD_IF_DBG
-	launches += 1;
+	const size_t lds = slot_run_lds_bytes(run.threads, run.lr, run.ncols);   // wave-slot exchange + hot lines + per-wave A + lane sums
+	const SlotRunFn kernel = slot_run_kernel(run.lr, (run.yflags & 1u) != 0, stamps, spec);
+	hipLaunchKernelGGL(kernel, grid, block, lds, rs, m.dp, run, e.prev, e.cur, e.score_out);
 }
 
 // Resumable submission: the first call does the preamble, every call submits super-steps until at least `budget`
@@ -1737,66 +1808,89 @@ void DeviceTable::abort_enqueue() {
 		(void)hipStreamSynchronize(m.stream);
 		(void)hipGetLastError();
 	}
-	m.enqueue_open = false;
-	m.next_super = 0;
+	m.inflight.rewind(m.stream);
 }
 
-// The preamble of a solve on m.run_stream: path buffers, key re-arm, the start event, the lookup tables of the LDS-resident paths.
+// The preamble of a solve on its run stream: path buffers, key re-arm, the start event, the lookup tables of the LDS-resident paths.
 whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std::string& msg) {
 	Impl& m = *this;
+	const hipStream_t rs = m.inflight.run_stream;
 	const uint32_t n = p.n_cols;
 	s.path_index.assign(n, 0);
 	s.path_trans.assign(n, 0);
 	s.superreads_done = false;
-	m.launches = 0;
-	m.next_super = 0;
+	m.inflight.launches = 0;
+	m.inflight.next_super = 0;
 	if (n == 0) return WHAMD_OK;
-	if (m.run_stream == m.stream) m.own_stream_used = true;
-	if (m.ev_upload && (m.upload_pending || m.run_stream != m.stream)) HIP_TRY(hipStreamWaitEvent(m.run_stream, m.ev_upload, 0));   // (the uploads went through an upload stream; once a solve has been collected they are known to be there)
-	for (const Impl::Lane& lane : m.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.key_entries * 8, m.run_stream));
-	HIP_TRY(hipMemsetAsync(m.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, m.run_stream));
-	if (m.use_chunks) HIP_TRY(hipMemsetAsync(m.dp.spec_keys, 0xFF, ((size_t)m.n_spec + 1) * m.dp.spec_stride * 8, m.run_stream));
-	if (m.windowed) HIP_TRY(hipMemsetAsync(m.d_path_trans, 0, (size_t)n * 4, m.run_stream));
-	m.timing_pending = false;   // (the events are this solve's from here on)
-	HIP_TRY(hipEventRecord(m.ev0, m.run_stream));
+	if (rs == m.stream) m.own_stream_used = true;
+	if (m.ev_upload && (m.upload_pending || rs != m.stream)) HIP_TRY(hipStreamWaitEvent(rs, m.ev_upload, 0));   // (the uploads went through an upload stream; once a solve has been collected they are known to be there)
+	for (const Impl::Lane& lane : m.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.key_entries * 8, rs));
+	HIP_TRY(hipMemsetAsync(m.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, rs));
+	if (m.use_chunks) HIP_TRY(hipMemsetAsync(m.dp.spec_keys, 0xFF, ((size_t)m.n_spec + 1) * m.dp.spec_stride * 8, rs));
+	if (m.windowed) HIP_TRY(hipMemsetAsync(m.d_path_trans, 0, (size_t)n * 4, rs));
+	m.inflight.timing_pending = false;   // (the events are this solve's from here on)
+	HIP_TRY(hipEventRecord(m.ev0, rs));
 	if (!m.plan.ped_columns.empty()) {
 		const uint32_t entries = (uint32_t)m.plan.ped_columns.size() * PED_TABLE;
-		hipLaunchKernelGGL(ped_tables, dim3((entries + 255) / 256), dim3(256), 0, m.run_stream, m.dp.ped_cols, (uint32_t)m.plan.ped_columns.size(), m.dp.ped_tables);
+		hipLaunchKernelGGL(ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.ped_cols, (uint32_t)m.plan.ped_columns.size(), m.dp.ped_tables);
 	} else if (!m.use_slots && !m.plan.columns.empty()) {
 		const uint32_t entries = (uint32_t)m.plan.columns.size() * RES_TABLE;
-		hipLaunchKernelGGL(resident_tables, dim3((entries + 255) / 256), dim3(256), 0, m.run_stream, m.dp.res_cols, (uint32_t)m.plan.columns.size(), m.dp.res_tables);
+		hipLaunchKernelGGL(resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.res_cols, (uint32_t)m.plan.columns.size(), m.dp.res_tables);
 	}
 	return WHAMD_OK;
 }
 
-// The per-column steps of one super-step (each a launch of its own on m.run_stream).
+// One super-step of a table on its own: the kept column of a window boundary restored, the runs (one batched launch, or the single run as a launch of its
+// own), the per-column steps, the column kept for a later window, the window's walk.
+whamd_status_t DeviceTable::Impl::submit_super_step(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg) {
+	Impl& m = *this;
+	const hipStream_t rs = m.inflight.run_stream;
+	const dim3 grid(ss.grid_x, ss.entry_count), block(ss.threads);
+	if (ss.ck_load >= 0) HIP_TRY(hipMemcpyAsync(ss.io[0], m.d_checkpoints + (size_t)ss.ck_load * m.checkpoint_bytes, m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
+	if (ss.entry_count == 1) {
+		if (m.use_slots) m.launch_slot_run(m.slot_entries[ss.entry_off], launches);
+		else m.launch_run(m.entries[ss.entry_off], launches);
+	} else if (ss.entry_count > 1) {
+		if (m.use_slots) { const SlotBatchFn kernel = slot_batch_kernel(m.slot_lr_used); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_slot_entries + ss.entry_off); }
+		else { const ResBatchFn kernel = resident_batch_kernel(ss.sym); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_entries + ss.entry_off); }
+		launches += 1;
+	}
+	const whamd_status_t st = m.submit_singles(p, ss, launches, msg);
+	if (st != WHAMD_OK) return st;
+	if (ss.ck_save >= 0) HIP_TRY(hipMemcpyAsync(m.d_checkpoints + (size_t)ss.ck_save * m.checkpoint_bytes, ss.io[1], m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
+	if (ss.bt_window >= 0)
+		hipLaunchKernelGGL(backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, rs, m.dp, m.d_units, m.d_window_jobs + ss.bt_window,
+		                   m.d_path_index, m.d_path_trans, m.d_score);
+	return WHAMD_OK;
+}
+
+// The per-column steps of one super-step (each a launch of its own on the run stream).
 whamd_status_t DeviceTable::Impl::submit_singles(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg) {
 	Impl& m = *this;
+	const hipStream_t rs = m.inflight.run_stream;
 	for (const Impl::Single& sg : ss.singles) {
 		const Impl::Lane& lane = m.lanes[sg.lane];
-		if (sg.zero_prev) HIP_TRY(hipMemsetAsync(lane.d_pr[sg.flip], 0, 4 * (size_t)p.T, m.run_stream));
+		if (sg.zero_prev) HIP_TRY(hipMemsetAsync(lane.d_pr[sg.flip], 0, 4 * (size_t)p.T, rs));
 		m.launch_column_step(p, m.plan.steps[sg.step], lane, lane.d_pr[sg.flip], lane.d_pr[sg.flip ^ 1], launches);
 		if (sg.score_job >= 0)
-			HIP_TRY(hipMemcpyAsync(m.d_job_scores + sg.score_job, lane.d_pr[sg.flip ^ 1], 4, hipMemcpyDeviceToDevice, m.run_stream));
+			HIP_TRY(hipMemcpyAsync(m.d_job_scores + sg.score_job, lane.d_pr[sg.flip ^ 1], 4, hipMemcpyDeviceToDevice, rs));
 	}
 	return WHAMD_OK;
 }
 
-// Everything after the forward pass, on the table's OWN stream: backtrace, downloads, events.
-whamd_status_t DeviceTable::Impl::submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream, bool backtrace_done, bool superreads_done) {
+// Everything after the forward pass, on `tail_stream` (default: the table's OWN stream): backtrace, downloads, events.  walked_by_group: a batched launch
+// has walked this table and made its superreads with the rest of its group; ev1 was recorded in front of it.
+whamd_status_t DeviceTable::Impl::submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream, bool walked_by_group) {
 	Impl& m = *this;
 	const hipStream_t ts = tail_stream ? tail_stream : m.stream;
-	m.tail_elsewhere = ts != m.stream;
+	m.inflight.tail_elsewhere = ts != m.stream;
 	if (ts == m.stream) m.own_stream_used = true;
-	m.tail_stream = ts;
-	{
-		static std::atomic<uint64_t> seq{0};
-		m.tail_seq = ++seq;
-	}
+	m.inflight.tail_stream = ts;
+	m.inflight.tail_seq = ++Impl::SolveInFlight::tails_submitted;
 	const uint32_t n = p.n_cols;
 	HIP_TRY(hipGetLastError());
-	if (!backtrace_done) HIP_TRY(hipEventRecord(m.ev1, ts));   // (backtrace_done: a batched launch walked this table with the rest of its group; ev1 was recorded in front of it)
-	if (backtrace_done) {
+	if (!walked_by_group) HIP_TRY(hipEventRecord(m.ev1, ts));
+	if (walked_by_group) {
 	} else if (m.use_chunks) {
 		hipLaunchKernelGGL(backtrace_chunks, dim3(m.n_orient_max * (uint32_t)m.chunks.size()), dim3(256), m.chunk_lds, ts, m.dp, m.d_units, m.d_chunks,
 		                   (uint32_t)m.chunks.size(), (uint32_t)m.units.size(), 0u, m.n_orient_max, m.d_path2, m.d_trans2, m.d_score, m.d_unit_x, m.d_guess, m.d_sel, m.d_bt_counters);
@@ -1809,11 +1903,9 @@ whamd_status_t DeviceTable::Impl::submit_tail(const Problem& p, std::string& msg
 	                   m.d_path_index, m.d_path_trans, m.d_score);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(m.ev2, ts));
-	if (m.device_superreads) {
-		if (!superreads_done) {
-			hipLaunchKernelGGL(superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, m.super_args);
-			HIP_TRY(hipGetLastError());
-		}
+	if (m.device_superreads && !walked_by_group) {
+		hipLaunchKernelGGL(superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, m.super_args);
+		HIP_TRY(hipGetLastError());
 	}
 	// ONE download per table (the device block has the pinned buffer's layout, upload()); pinned: a copy into pageable memory would block this call until the stream drains
 	HIP_TRY(hipMemcpyAsync(m.h_pinned, m.d_path_index, (m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t), hipMemcpyDeviceToHost, ts));
@@ -1826,55 +1918,34 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 	const uint32_t n = p.n_cols;
 	done = false;
 	if (n) HIP_TRY(hipSetDevice(m.device));
-	if (!m.enqueue_open) {
-		m.enqueue_open = true;
-		m.run_stream = m.stream;
-		m.group_tables = 1;
+	if (!m.inflight.enqueue_open) {
+		m.inflight.enqueue_open = true;
+		m.inflight.run_stream = m.stream;
+		m.inflight.group_tables = 1;
 		const whamd_status_t st = m.begin_solve(p, s, msg);
 		if (st != WHAMD_OK) return st;
 		if (n == 0) {  // src/pedigreedptable.cpp:88-92
 			s.optimal_score = 0;
-			m.enqueue_open = false;
+			m.inflight.enqueue_open = false;
 			done = true;
 			return WHAMD_OK;
 		}
 	}
 	uint64_t launches = 0;
-	while (m.next_super < m.schedule.size() && launches < budget) {
-		const Impl::SuperStep& ss = m.schedule[m.next_super++];
-		if (ss.ck_load >= 0) HIP_TRY(hipMemcpyAsync(ss.io[0], m.d_checkpoints + (size_t)ss.ck_load * m.checkpoint_bytes, m.checkpoint_bytes, hipMemcpyDeviceToDevice, m.stream));
-		if (m.use_slots) {
-			if (ss.entry_count == 1) m.launch_slot_run(m.slot_entries[ss.entry_off], launches);
-			else if (ss.entry_count > 1) {
-				if (m.slot_lr_used == 1) hipLaunchKernelGGL(slot_batch<1>, dim3(ss.grid_x, ss.entry_count), dim3(ss.threads), ss.lds, m.stream, m.dp, m.d_slot_entries + ss.entry_off);
-				else if (m.slot_lr_used == 3) hipLaunchKernelGGL(slot_batch<3>, dim3(ss.grid_x, ss.entry_count), dim3(ss.threads), ss.lds, m.stream, m.dp, m.d_slot_entries + ss.entry_off);
-				else hipLaunchKernelGGL(slot_batch<2>, dim3(ss.grid_x, ss.entry_count), dim3(ss.threads), ss.lds, m.stream, m.dp, m.d_slot_entries + ss.entry_off);
-				launches += 1;
-			}
-		} else if (ss.entry_count == 1) {
-			m.launch_run(m.entries[ss.entry_off], 0, launches);
-		} else if (ss.entry_count > 1) {
-			if (ss.sym) hipLaunchKernelGGL(resident_batch<true>, dim3(ss.grid_x, ss.entry_count), dim3(ss.threads), ss.lds, m.stream, m.dp, m.d_entries + ss.entry_off);
-			else hipLaunchKernelGGL(resident_batch<false>, dim3(ss.grid_x, ss.entry_count), dim3(ss.threads), ss.lds, m.stream, m.dp, m.d_entries + ss.entry_off);
-			launches += 1;
-		}
-		const whamd_status_t st = m.submit_singles(p, ss, launches, msg);
+	while (m.inflight.next_super < m.schedule.size() && launches < budget) {
+		const whamd_status_t st = m.submit_super_step(p, m.schedule[m.inflight.next_super++], launches, msg);
 		if (st != WHAMD_OK) return st;
-		if (ss.ck_save >= 0) HIP_TRY(hipMemcpyAsync(m.d_checkpoints + (size_t)ss.ck_save * m.checkpoint_bytes, ss.io[1], m.checkpoint_bytes, hipMemcpyDeviceToDevice, m.stream));
-		if (ss.bt_window >= 0)
-			hipLaunchKernelGGL(backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, m.stream, m.dp, m.d_units, m.d_window_jobs + ss.bt_window,
-			                   m.d_path_index, m.d_path_trans, m.d_score);
 	}
-	m.launches += launches;
-	if (m.next_super < m.schedule.size()) return WHAMD_OK;
+	m.inflight.launches += launches;
+	if (m.inflight.next_super < m.schedule.size()) return WHAMD_OK;
 	const whamd_status_t st = m.submit_tail(p, msg);
 	if (st != WHAMD_OK) return st;
-	m.enqueue_open = false;
+	m.inflight.enqueue_open = false;
 	done = true;
 	return WHAMD_OK;
 }
 
-// ---------------------------------------------------------------------------------------------- group solve
+// ================================================================================================ solve: a group
 // Several independent tables as ONE sequence of launches (whamd_dptable_enqueue_many): super-step k of the group = step k of every
 // member that still has one; the runs of all members go out as one slot_group / pedslot_group launch per kernel variant
 // (blockIdx.y = member), on the stream of the group's first table; per-column steps follow as launches of their own.  When the
@@ -1882,7 +1953,7 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 // those overlap across the members -- so whamd_dptable_wait works per table as before.
 bool DeviceTable::group_eligible(const Problem& p) const {
 	const Impl& m = *impl_;
-	if (p.n_cols == 0 || !m.use_slots || m.windowed || m.enqueue_open || m.dp.dbg || (m.dp.dbg_flags && m.splan.ped)) return false;
+	if (p.n_cols == 0 || !m.use_slots || m.windowed || m.inflight.enqueue_open || m.dp.dbg || (m.dp.dbg_flags && m.splan.ped)) return false;
 	if (!m.splan.ped && m.slot_lr_used != 2 && m.slot_lr_used != 3) return false;   // (group kernels: four or eight cells per thread)
 	return debug_env("WHAMD_NO_GROUP") == nullptr;
 }
@@ -1890,200 +1961,205 @@ bool DeviceTable::group_eligible(const Problem& p) const {
 int DeviceTable::device_index() const { return impl_->device; }
 uint32_t DeviceTable::widest_launch() const { return impl_->max_grid_x; }
 
-whamd_status_t DeviceTable::enqueue_group(DeviceTable* const* tables, const Problem* const* problems, Solution* const* solutions, size_t n_tables, std::string& msg) {
-	if (n_tables == 0) return WHAMD_OK;
-	HIP_TRY(hipSetDevice(tables[0]->impl_->device));
-	// ---- parts.  Tables that advance in lockstep are all in the same phase at the same time: every workgroup waits in its prologue
-	// together, then they all compete for the issue slots together -- three full-width tables in ONE launch per super-step take 17 us
-	// where three tables on their own streams, drifting against each other, take 11 (whamd_dptable_enqueue_many therefore keeps up to
-	// four full-width tables on their own streams).  A group can be cut into PARTS, each a group of its own on the stream of its first
-	// table, submitted round robin; measured on 24 full-width tables that is no gain over one part (6.30 M columns/s with 1 part,
-	// 6.23 / 6.15 / 5.75 / 6.06 / 5.98 with 2 / 3 / 4 / 6 / 8: profiles/r04/), so one part is the default and WHAMD_GROUP_PARTS the experiment.
-	uint64_t width = 0;
-	for (size_t i = 0; i < n_tables; ++i) width += tables[i]->impl_->max_grid_x;
-	size_t n_parts = 1;
-	if (const char* e = debug_env("WHAMD_GROUP_PARTS")) n_parts = (size_t)std::max(1, atoi(e));
-	n_parts = std::min(n_parts, n_tables);
-	const bool tight = width > 768 && !debug_env("WHAMD_GROUP_LOOSE");   // more than three workgroups per CU: the variants held to 80 SGPRs (four workgroups per CU)
-	struct Batch { SlotGroupArgs args; uint32_t grid_x = 0, threads = 0; size_t lds = 0; };
-	struct Part {
-		std::vector<size_t> members;   // positions in `tables`
-		Impl* lead = nullptr;
-		std::vector<Batch> batches;    // per kernel variant: 0 single individual (four cells per thread); 1 .. 5 pedigree runs (TB, NF) = (2,2) (2,4) (4,2) (4,4) (2,16)
-	};
-	std::vector<Part> parts(n_parts);
-	for (size_t i = 0; i < n_tables; ++i) parts[i % n_parts].members.push_back(i);
-	constexpr int NV = 11;  // kernel variants (6: single individual, eight cells per thread; 7: trio, factorised lines; 8 / 9: X runs of a single individual with four / eight cells per thread, slot_groupx; 10: quartet, factorised lines)
-	for (Part& part : parts) { part.lead = tables[part.members[0]]->impl_; part.batches.resize(NV); }
-	auto abort_all = [&]() {
-		for (Part& part : parts) (void)hipStreamSynchronize(part.lead->stream);
+// One group solve in the making: what the steps of enqueue_group share.  A launch takes SLOT_GROUP_MAX runs (BT_GROUP_MAX tables for the
+// walk): a larger group flushes a variant's batch in the middle of a super-step and cuts the batched backtrace, and every member counts the launches it has a run in.
+// (Cutting a group into parts on streams of their own was measured and gave nothing: profiles/r04/experiments_not_kept.md, ROUND4.md row 1b)
+struct DeviceTable::Impl::GroupSubmission {
+	struct Batch { SlotGroupArgs args; uint32_t grid_x = 0, threads = 0; size_t lds = 0; };   // the runs collected for the next launch of one variant
+	DeviceTable* const* tables;
+	const Problem* const* problems;
+	Solution* const* solutions;
+	const size_t n;                          // members
+	Impl& lead;                              // the first member: the forward pass of all of them goes onto its stream
+	std::string& msg;
+	bool tight = false;                      // more than three workgroups per CU: the variants held to 80 SGPRs (four workgroups per CU)
+	size_t max_steps = 0;                    // super-steps of the longest member
+	std::vector<Batch> batches;              // [variant]
+	std::vector<uint8_t> counted;            // [member][variant]: the member has a run in the variant's open batch
+	std::vector<uint64_t> table_launches;    // [member]: forward launches it had a run in, and its own per-column steps (whamd_solve_stats::forward_launches)
+	std::vector<uint8_t> walked;             // [member]: a batched backtrace launch walked it
+#ifdef WHAMD_DEBUG_BUILD
+	const bool touch_fat = debug_env("WHAMD_GROUP_TOUCH_ENTRIES") != nullptr;
+	volatile uint64_t fat_sink = 0;
+#endif
+
+	GroupSubmission(DeviceTable* const* t, const Problem* const* p, Solution* const* s, size_t n_tables, std::string& m)
+		: tables(t), problems(p), solutions(s), n(n_tables), lead(*t[0]->impl_), msg(m), batches(GROUP_VARIANTS), counted(n_tables * GROUP_VARIANTS, 0),
+		  table_launches(n_tables, 0), walked(n_tables, 0) {}
+	Impl& member(size_t i) const { return *tables[i]->impl_; }
+
+	// Drops what has been submitted: every member can be solved again from the start.
+	whamd_status_t abort(whamd_status_t st) {
+		(void)hipStreamSynchronize(lead.stream);
 		(void)hipGetLastError();
-		for (size_t i = 0; i < n_tables; ++i) {
-			Impl& m = *tables[i]->impl_;
-			(void)hipStreamSynchronize(m.stream);
-			m.enqueue_open = false;
-			m.next_super = 0;
-			m.run_stream = m.stream;
+		for (size_t i = 0; i < n; ++i) {
+			(void)hipStreamSynchronize(member(i).stream);
+			member(i).inflight.rewind(member(i).stream);
 		}
-	};
-	size_t max_steps = 0;
-	for (Part& part : parts)
-		for (size_t i : part.members) {
-			Impl& m = *tables[i]->impl_;
-			m.enqueue_open = true;
-			m.run_stream = part.lead->stream;
-			m.group_tables = (uint32_t)part.members.size();
+		return st;
+	}
+	whamd_status_t fail(const char* what) { msg = what; return abort(WHAMD_ERR_DEVICE); }
+
+	// Every member's solve opens on the lead's stream.
+	whamd_status_t open_members() {
+		uint64_t width = 0;
+		for (size_t i = 0; i < n; ++i) width += member(i).max_grid_x;
+		tight = width > 768 && !debug_env("WHAMD_GROUP_LOOSE");
+		for (size_t i = 0; i < n; ++i) {
+			Impl& m = member(i);
+			m.inflight.enqueue_open = true;
+			m.inflight.run_stream = lead.stream;
+			m.inflight.group_tables = (uint32_t)n;
 			const whamd_status_t st = m.begin_solve(*problems[i], *solutions[i], msg);
-			if (st != WHAMD_OK) { abort_all(); return st; }
+			if (st != WHAMD_OK) return abort(st);
 			max_steps = std::max(max_steps, m.schedule.size());
 		}
-	auto flush = [&](Part& part, int variant) {
-		Batch& b = part.batches[variant];
+		return WHAMD_OK;
+	}
+
+	// The runs of super-step k of every member that has one, each into the batch of its variant.
+	void add_super_step(size_t k) {
+		std::fill(counted.begin(), counted.end(), 0);
+		for (size_t i = 0; i < n; ++i) {
+			Impl& m = member(i);
+			if (k >= m.step_brief.size()) continue;
+			const Impl::StepBrief& sb = m.step_brief[k];   // (a few bytes per table and super-step: Impl::StepBrief)
+#ifdef WHAMD_DEBUG_BUILD
+			if (touch_fat) {   // (A/B of the round-5 change: read what the loop used to read -- the super-step and its 320-byte entries)
+				const Impl::SuperStep& ss = m.schedule[k];
+				for (uint32_t q = 0; q < ss.entry_count; ++q) { const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q]; fat_sink += he.run.yflags + he.run.g + he.run.threads + he.ex.nf + (uint32_t)ss.lds; }
+			}
+#endif
+			for (uint32_t q = 0; q < sb.entry_count; ++q) {
+				const Impl::EntryBrief& eb = m.entry_brief[sb.entry_off + q];
+				const bool xrun = eb.variant.x != eb.variant.plain && !m.dp.dbg_flags;   // (the X kernel: operands streamed from the tables, 16 KB of LDS)
+				const GroupVariant v = xrun ? eb.variant.x : eb.variant.plain;
+				Batch& b = batches[v];
+				if (b.args.n == (uint32_t)SLOT_GROUP_MAX) flush(v);
+				b.args.entry[b.args.n++] = m.d_slot_entries + sb.entry_off + q;
+				b.grid_x = std::max<uint32_t>(b.grid_x, eb.grid_x);
+				b.threads = std::max<uint32_t>(b.threads, eb.threads);
+				b.lds = std::max<size_t>(b.lds, xrun ? eb.lds_x : sb.lds);
+				counted[i * GROUP_VARIANTS + v] = 1;
+			}
+		}
+	}
+
+	// The open batch of one variant goes out as one launch; every member with a run in it counts it.
+	void flush(GroupVariant v) {
+		Batch& b = batches[v];
 		if (!b.args.n) return;
 		// a table's workgroups on ONE XCD (slot_group_who): the table is the fast grid dimension, padded to a multiple of eight -- where that spreads the tables
 		// evenly over the eight XCDs (a multiple of eight of them, or so many that the remainder does not matter)
 		const bool by_table = (b.args.n % 8u == 0u || b.args.n >= 40u) && !debug_env("WHAMD_GROUP_BY_WORKGROUP");
 		b.args.pad = by_table ? 1u : 0u;
 		const dim3 grid = by_table ? dim3((b.args.n + 7u) & ~7u, b.grid_x) : dim3(b.grid_x, b.args.n), block(b.threads);
-		hipStream_t stream = part.lead->stream;
-		switch (variant) {
-			case 0:
-#ifdef WHAMD_DEBUG_BUILD
-				if (part.lead->dp.dbg_flags) hipLaunchKernelGGL((slot_group<2, true, false>), grid, block, b.lds, stream, b.args);
-				else
-#endif
-				if (tight) hipLaunchKernelGGL((slot_group<2, false, true>), grid, block, b.lds, stream, b.args);
-				else hipLaunchKernelGGL((slot_group<2, false, false>), grid, block, b.lds, stream, b.args);
-				break;
-			case 1: hipLaunchKernelGGL((pedslot_group<2, 2>), grid, block, b.lds, stream, b.args); break;
-			case 2: hipLaunchKernelGGL((pedslot_group<2, 4>), grid, block, b.lds, stream, b.args); break;
-			case 3: hipLaunchKernelGGL((pedslot_group<4, 2>), grid, block, b.lds, stream, b.args); break;
-			case 4: hipLaunchKernelGGL((pedslot_group<4, 4>), grid, block, b.lds, stream, b.args); break;
-			case 5: hipLaunchKernelGGL((pedslot_group<2, 16>), grid, block, b.lds, stream, b.args); break;
-			case 7: hipLaunchKernelGGL((pedslot_group<2, PSLOT_FACT>), grid, block, b.lds, stream, b.args); break;
-			case 10: hipLaunchKernelGGL((pedslot_group<4, PSLOT_FACT4>), grid, block, b.lds, stream, b.args); break;
-			case 8: hipLaunchKernelGGL((slot_groupx<2, false>), grid, block, b.lds, stream, b.args); break;
-			case 9: hipLaunchKernelGGL((slot_groupx<3, false>), grid, block, b.lds, stream, b.args); break;
-			default:
-				if (tight) hipLaunchKernelGGL((slot_group<3, false, true>), grid, block, b.lds, stream, b.args);
-				else hipLaunchKernelGGL((slot_group<3, false, false>), grid, block, b.lds, stream, b.args);
-				break;
-		}
+		const GroupFn kernel = group_kernel(v, DEBUG_BUILD && lead.dp.dbg_flags != 0, tight);
+		hipLaunchKernelGGL(kernel, grid, block, b.lds, lead.stream, b.args);
 		b.args.n = 0;
 		b.grid_x = b.threads = 0;
 		b.lds = 0;
-	};
-	std::vector<uint64_t> table_launches(n_tables, 0);
-	std::vector<uint8_t> counted(n_tables * NV, 0);
-	const auto t_submit0 = std::chrono::steady_clock::now();
-#ifdef WHAMD_DEBUG_BUILD
-	const bool touch_fat = debug_env("WHAMD_GROUP_TOUCH_ENTRIES") != nullptr;
-	volatile uint64_t fat_sink = 0;
-#endif
-	for (size_t k = 0; k < max_steps; ++k) {
-		for (Part& part : parts) {
-			for (size_t i : part.members) std::fill(counted.begin() + i * NV, counted.begin() + i * NV + NV, 0);
-			for (size_t i : part.members) {
-				Impl& m = *tables[i]->impl_;
-				if (k >= m.step_brief.size()) continue;
-				const Impl::StepBrief& sb = m.step_brief[k];   // (a few bytes per table and super-step: Impl::StepBrief)
-#ifdef WHAMD_DEBUG_BUILD
-				if (touch_fat) {   // (A/B of the round-5 change: read what the loop used to read -- the super-step and its 320-byte entries)
-					const Impl::SuperStep& ss = m.schedule[k];
-					for (uint32_t q = 0; q < ss.entry_count; ++q) { const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q]; fat_sink += he.run.yflags + he.run.g + he.run.threads + he.ex.nf + (uint32_t)ss.lds; }
-				}
-#endif
-				for (uint32_t q = 0; q < sb.entry_count; ++q) {
-					const Impl::EntryBrief& eb = m.entry_brief[sb.entry_off + q];
-					const bool xrun = eb.variant_x != eb.variant && !m.dp.dbg_flags;   // (the X kernel: operands streamed from the tables, 16 KB of LDS)
-					const int variant = xrun ? eb.variant_x : eb.variant;
-					Batch& b = part.batches[variant];
-					if (b.args.n == (uint32_t)SLOT_GROUP_MAX) {
-						flush(part, variant);
-						for (size_t j : part.members) if (counted[j * NV + variant]) { table_launches[j] += 1; counted[j * NV + variant] = 0; }
-					}
-					b.args.entry[b.args.n++] = m.d_slot_entries + sb.entry_off + q;
-					b.grid_x = std::max<uint32_t>(b.grid_x, eb.grid_x);
-					b.threads = std::max<uint32_t>(b.threads, eb.threads);
-					b.lds = std::max<size_t>(b.lds, xrun ? eb.lds_x : sb.lds);
-					counted[i * NV + variant] = 1;
-				}
-			}
-			for (int v = 0; v < NV; ++v) {
-				flush(part, v);
-				for (size_t j : part.members) if (counted[j * NV + v]) table_launches[j] += 1;
-			}
-			for (size_t i : part.members) {
-				Impl& m = *tables[i]->impl_;
-				if (k >= m.step_brief.size() || !m.step_brief[k].has_singles) continue;
-				const whamd_status_t st = m.submit_singles(*problems[i], m.schedule[k], table_launches[i], msg);
-				if (st != WHAMD_OK) { abort_all(); return st; }
-			}
+		for (size_t j = 0; j < n; ++j)
+			if (counted[j * GROUP_VARIANTS + v]) { table_launches[j] += 1; counted[j * GROUP_VARIANTS + v] = 0; }
+	}
+
+	// The per-column steps of super-step k, member by member.
+	whamd_status_t submit_singles(size_t k) {
+		for (size_t i = 0; i < n; ++i) {
+			Impl& m = member(i);
+			if (k >= m.step_brief.size() || !m.step_brief[k].has_singles) continue;
+			const whamd_status_t st = m.submit_singles(*problems[i], m.schedule[k], table_launches[i], msg);
+			if (st != WHAMD_OK) return abort(st);
 		}
+		return WHAMD_OK;
+	}
+
+	// "The forward pass of every member is submitted up to here."
+	whamd_status_t mark_forward_end() {
+		if (hipGetLastError() != hipSuccess) return fail("group launch failed");
+		if (hipEventRecord(lead.ev_group, lead.stream) != hipSuccess) return fail("hipEventRecord failed");
+		return WHAMD_OK;
+	}
+
+	// The chunked backtrace of the members that have one as ONE launch per mode + one gather (blockIdx.y = member), on the lead's stream.
+	whamd_status_t walk_back() {
+		if (debug_env("WHAMD_TAIL_OWN_STREAM") || debug_env("WHAMD_NO_GROUP_BACKTRACE")) return WHAMD_OK;
+		std::vector<size_t> batch;
+		for (size_t i = 0; i < n; ++i) {
+			const Impl& m = member(i);
+			if (!m.use_chunks || m.windowed || !m.d_bt_entry) continue;
+			batch.push_back(i);
+			if (batch.size() == (size_t)BT_GROUP_MAX && !walk_batch(batch)) return fail("group backtrace launch failed");
+		}
+		if (!walk_batch(batch)) return fail("group backtrace launch failed");
+		return WHAMD_OK;
+	}
+
+	// (a batch of one is left to the member's own tail)
+	bool walk_batch(std::vector<size_t>& batch) {
+		if (batch.size() < 2) { batch.clear(); return true; }
+		BtGroupArgs args{};
+		uint32_t gx = 1, gu = 1;
+		size_t lds = 0;
+		for (size_t i : batch) {
+			Impl& m = member(i);
+			args.entry[args.n++] = m.d_bt_entry;
+			gx = std::max(gx, m.n_orient_max * (uint32_t)m.chunks.size());
+			gu = std::max(gu, (uint32_t)m.units.size());
+			lds = std::max(lds, m.chunk_lds);
+			if (hipEventRecord(m.ev1, lead.stream) != hipSuccess) return false;
+		}
+		hipLaunchKernelGGL(backtrace_chunks_group, dim3(gx, args.n), dim3(256), lds, lead.stream, args, 0u);
+		hipLaunchKernelGGL(backtrace_chunks_group, dim3(1, args.n), dim3(256), lds, lead.stream, args, 1u);
+		hipLaunchKernelGGL(backtrace_gather_group, dim3(gu, args.n), dim3(64), 0, lead.stream, args);
+		uint32_t gs = 0;   // (the superreads of the members the device makes them for, behind the gather)
+		for (size_t i : batch) if (member(i).device_superreads) gs = std::max(gs, (problems[i]->n_cols + 255u) / 256u);
+		if (gs) hipLaunchKernelGGL(superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, args);
+		if (hipGetLastError() != hipSuccess) return false;
+		for (size_t i : batch) walked[i] = 1;
+		batch.clear();
+		return true;
+	}
+
+	// The tail (backtrace, downloads) of every member goes onto the LEAD's stream, behind the group's last launch in the same hardware queue.  On the members'
+	// own streams -- each waiting for the lead's event -- a 96-table step was bimodal: 67 ms or 95 ms, the device's forward pass 39 ms either way
+	// (hardware queues that hold only a barrier are rescheduled late; more queues, GPU_MAX_HW_QUEUES=16, made every step 180 ms).  WHAMD_TAIL_OWN_STREAM=1
+	// (debug library) restores the old placement.
+	// ... except a member that walks back through the SEQUENTIAL kernel (several jobs, or too few units for chunks): milliseconds of one workgroup per table --
+	// those run side by side on the members' own streams, behind the group's event, instead of one after the other on the lead's.
+	whamd_status_t submit_tails() {
+		for (size_t i = 0; i < n; ++i) {
+			Impl& m = member(i);
+			m.inflight.launches = table_launches[i];
+			const bool own = debug_env("WHAMD_TAIL_OWN_STREAM") != nullptr || (!walked[i] && !m.use_chunks && !m.windowed && m.stream != lead.stream);
+			if (own) m.own_stream_used = true;
+			if (own && m.stream != lead.stream && hipStreamWaitEvent(m.stream, lead.ev_group, 0) != hipSuccess) return fail("hipStreamWaitEvent failed");
+			const whamd_status_t st = m.submit_tail(*problems[i], msg, own ? nullptr : lead.stream, walked[i] != 0);
+			if (st != WHAMD_OK) return abort(st);
+			m.inflight.rewind(m.stream);
+		}
+		return WHAMD_OK;
+	}
+};
+
+whamd_status_t DeviceTable::enqueue_group(DeviceTable* const* tables, const Problem* const* problems, Solution* const* solutions, size_t n_tables, std::string& msg) {
+	if (n_tables == 0) return WHAMD_OK;
+	HIP_TRY(hipSetDevice(tables[0]->impl_->device));
+	Impl::GroupSubmission g(tables, problems, solutions, n_tables, msg);
+	whamd_status_t st = g.open_members();
+	if (st != WHAMD_OK) return st;
+	const auto t_submit0 = std::chrono::steady_clock::now();
+	for (size_t k = 0; k < g.max_steps; ++k) {
+		g.add_super_step(k);
+		for (int v = 0; v < GROUP_VARIANTS; ++v) g.flush((GroupVariant)v);   // (ascending: the order of the launches inside a super-step)
+		if ((st = g.submit_singles(k)) != WHAMD_OK) return st;
 	}
 	if (getenv("WHAMD_DEBUG_TIMING"))
-		fprintf(stderr, "[whamd timing] group of %zu tables in %zu part(s): %zu super-steps submitted in %.2f ms (host)\n", n_tables, n_parts, max_steps,
+		fprintf(stderr, "[whamd timing] group of %zu tables in 1 part(s): %zu super-steps submitted in %.2f ms (host)\n", n_tables, g.max_steps,
 		        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_submit0).count());
-	if (hipGetLastError() != hipSuccess) { msg = "group launch failed"; abort_all(); return WHAMD_ERR_DEVICE; }
-	for (Part& part : parts) {
-		if (hipEventRecord(part.lead->ev_group, part.lead->stream) != hipSuccess) { msg = "hipEventRecord failed"; abort_all(); return WHAMD_ERR_DEVICE; }
-		// the chunked backtrace of the part's members as ONE launch per mode + one gather (blockIdx.y = member), on the lead's stream
-		std::vector<uint8_t> walked(n_tables, 0);
-		if (!debug_env("WHAMD_TAIL_OWN_STREAM") && !debug_env("WHAMD_NO_GROUP_BACKTRACE")) {
-			std::vector<size_t> batch;
-			auto flush_bt = [&]() -> bool {
-				if (batch.size() < 2) { batch.clear(); return true; }
-				BtGroupArgs args{};
-				uint32_t gx = 1, gu = 1;
-				size_t lds = 0;
-				for (size_t i : batch) {
-					Impl& m = *tables[i]->impl_;
-					args.entry[args.n++] = m.d_bt_entry;
-					gx = std::max(gx, m.n_orient_max * (uint32_t)m.chunks.size());
-					gu = std::max(gu, (uint32_t)m.units.size());
-					lds = std::max(lds, m.chunk_lds);
-					if (hipEventRecord(m.ev1, part.lead->stream) != hipSuccess) return false;
-				}
-				hipLaunchKernelGGL(backtrace_chunks_group, dim3(gx, args.n), dim3(256), lds, part.lead->stream, args, 0u);
-				hipLaunchKernelGGL(backtrace_chunks_group, dim3(1, args.n), dim3(256), lds, part.lead->stream, args, 1u);
-				hipLaunchKernelGGL(backtrace_gather_group, dim3(gu, args.n), dim3(64), 0, part.lead->stream, args);
-				uint32_t gs = 0;   // (the superreads of the members the device makes them for, behind the gather)
-				for (size_t i : batch) if (tables[i]->impl_->device_superreads) gs = std::max(gs, (problems[i]->n_cols + 255u) / 256u);
-				if (gs) hipLaunchKernelGGL(superreads_group, dim3(gs, args.n), dim3(256), 0, part.lead->stream, args);
-				if (hipGetLastError() != hipSuccess) return false;
-				for (size_t i : batch) walked[i] = 1;
-				batch.clear();
-				return true;
-			};
-			for (size_t i : part.members) {
-				Impl& m = *tables[i]->impl_;
-				if (!m.use_chunks || m.windowed || !m.d_bt_entry) continue;
-				batch.push_back(i);
-				if (batch.size() == (size_t)BT_GROUP_MAX && !flush_bt()) { msg = "group backtrace launch failed"; abort_all(); return WHAMD_ERR_DEVICE; }
-			}
-			if (!flush_bt()) { msg = "group backtrace launch failed"; abort_all(); return WHAMD_ERR_DEVICE; }
-		}
-		for (size_t i : part.members) {
-			Impl& m = *tables[i]->impl_;
-			m.launches = table_launches[i];
-			m.next_super = m.schedule.size();
-			whamd_status_t st = WHAMD_OK;
-			// The tail (backtrace, downloads) of every member goes onto the LEAD's stream, behind the group's last launch in the same hardware queue.  On the members'
-			// own streams -- each waiting for the lead's event -- a 96-table step was bimodal: 67 ms or 95 ms, the device's forward pass 39 ms either way
-			// (hardware queues that hold only a barrier are rescheduled late; more queues, GPU_MAX_HW_QUEUES=16, made every step 180 ms).  WHAMD_TAIL_OWN_STREAM=1
-			// (debug library) restores the old placement.
-			// ... except a member that walks back through the SEQUENTIAL kernel (several jobs, or too few units for chunks): milliseconds of one workgroup per table --
-			// those run side by side on the members' own streams, behind the group's event, instead of one after the other on the lead's.
-			const bool own = debug_env("WHAMD_TAIL_OWN_STREAM") != nullptr || (!walked[i] && !m.use_chunks && !m.windowed && m.stream != part.lead->stream);
-			if (own) m.own_stream_used = true;
-			if (own && m.stream != part.lead->stream && hipStreamWaitEvent(m.stream, part.lead->ev_group, 0) != hipSuccess) { msg = "hipStreamWaitEvent failed"; st = WHAMD_ERR_DEVICE; }
-			if (st == WHAMD_OK) st = m.submit_tail(*problems[i], msg, own ? nullptr : part.lead->stream, walked[i] != 0, walked[i] != 0);
-			if (st != WHAMD_OK) { abort_all(); return st; }
-			m.enqueue_open = false;
-			m.run_stream = m.stream;
-		}
-	}
-	return WHAMD_OK;
+	if ((st = g.mark_forward_end()) != WHAMD_OK) return st;
+	if ((st = g.walk_back()) != WHAMD_OK) return st;
+	return g.submit_tails();
 }
 
 // Tables in flight whose tails share a stream (a group: every member's tail is on the lead's stream, in order) finish in that order: ONE wait for the last of each
@@ -2093,14 +2169,14 @@ void DeviceTable::wait_last_of_each_stream(DeviceTable* const* tables, size_t n_
 	std::vector<std::pair<hipStream_t, const Impl*>> last;
 	for (size_t i = 0; i < n_tables; ++i) {
 		const Impl& m = *tables[i]->impl_;
-		if (!m.tail_elsewhere || !m.ev3) continue;
+		if (!m.inflight.tail_elsewhere || !m.ev3) continue;
 		bool found = false;
 		for (auto& e : last) {
-			if (e.first != m.tail_stream || e.second->device != m.device) continue;
+			if (e.first != m.inflight.tail_stream || e.second->device != m.device) continue;
 			found = true;
-			if (m.tail_seq > e.second->tail_seq) e.second = &m;
+			if (m.inflight.tail_seq > e.second->inflight.tail_seq) e.second = &m;
 		}
-		if (!found) last.emplace_back(m.tail_stream, &m);
+		if (!found) last.emplace_back(m.inflight.tail_stream, &m);
 	}
 	for (const auto& e : last) {
 		if (hipSetDevice(e.second->device) != hipSuccess || hipEventSynchronize(e.second->ev3) != hipSuccess) (void)hipGetLastError();   // (the table's own wait() reports it)
@@ -2111,8 +2187,8 @@ void DeviceTable::wait_last_of_each_stream(DeviceTable* const* tables, size_t n_
 // read already or when a new solve has been submitted since (the events then belong to that one).
 void DeviceTable::read_timing(whamd_solve_stats& st) {
 	Impl& m = *impl_;
-	if (!m.timing_pending) return;
-	m.timing_pending = false;
+	if (!m.inflight.timing_pending) return;
+	m.inflight.timing_pending = false;
 	if (hipSetDevice(m.device) != hipSuccess) return;
 	float f01 = 0, f12 = 0, f03 = 0;
 	if (hipEventElapsedTime(&f01, m.ev0, m.ev1) != hipSuccess || hipEventElapsedTime(&f12, m.ev1, m.ev2) != hipSuccess || hipEventElapsedTime(&f03, m.ev0, m.ev3) != hipSuccess) {
@@ -2124,12 +2200,80 @@ void DeviceTable::read_timing(whamd_solve_stats& st) {
 	st.total_ms = f03;
 }
 
+// The in-kernel cycle stamps of the slot runs (WHAMD_SLOT_STAMPS, debug library): full-length runs, wave 0 of workgroup 0.
+whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
+	const Impl& m = *this;
+	std::vector<unsigned long long> d(m.splan.runs.size() * 48);
+	HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
+	double a[6] = {0, 0, 0, 0, 0, 0};
+	double percol[32] = {0};
+	size_t cnt = 0;
+	for (size_t i = 0; i < m.splan.runs.size(); ++i) {
+		if (m.splan.runs[i].ncols != 22 || d[48 * i + 5] == 0) continue;   // full-length runs only
+		for (int k = 0; k < 6; ++k) a[k] += (double)d[48 * i + k];
+		for (int k = 0; k < 22; ++k) percol[k] += (double)d[48 * i + 8 + k];
+		++cnt;
+	}
+	if (cnt) fprintf(stderr, "[whamd slot stamps] %zu runs, wave 0 of workgroup 0, shader cycles: prologue issue %.0f, loads landed %.0f, column loop %.0f (%.1f per column, %.1f columns), exit %.0f\n",
+	                 cnt, a[0] / cnt, a[1] / cnt, a[2] / cnt, a[2] / std::max(a[4], 1.0), a[4] / cnt, a[3] / cnt);
+	if (cnt) {
+		fprintf(stderr, "[whamd slot stamps] cycles after the loop start at which column c had its cost added:");
+		for (int k = 0; k < 22; ++k) fprintf(stderr, " %.0f", percol[k] / cnt);
+		fprintf(stderr, "\n");
+	}
+	return WHAMD_OK;
+}
+
+// The in-kernel cycle stamps of the LDS-resident runs (WHAMD_DEBUG_STAMPS, debug library), with the backtrace's and four runs' workgroup by workgroup.
+whamd_status_t DeviceTable::Impl::report_resident_stamps(std::string& msg) const {
+	const Impl& m = *this;
+	std::vector<unsigned long long> d(m.plan.segments.size() * 8);
+	HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
+	unsigned long long a = 0, b = 0, c2 = 0, cols = 0, p1 = 0, p2 = 0, p3 = 0, ns = 0;
+	for (size_t i = 0; i < m.plan.segments.size(); ++i) { a += d[8 * i]; b += d[8 * i + 1]; c2 += d[8 * i + 2]; cols += d[8 * i + 3]; p1 += d[8 * i + 4]; p2 += d[8 * i + 5]; p3 += d[8 * i + 6]; ns += d[8 * i + 7]; }
+	if (!m.plan.ped_columns.empty() || (m.dp.dbg_flags & 4u))
+		fprintf(stderr, "[whamd timing] run prologue (wave 0 of workgroup 0), cycles after the first instruction: kernel arguments usable %.0f, first loaded data %.0f, everything staged %.0f\n",
+		        (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1), (double)p1 / std::max<unsigned long long>(ns, 1));
+	else
+	fprintf(stderr, "[whamd timing] per barrier step (wave 0 of workgroup 0, %.1f steps per run): hot words %.0f, evaluate %.0f, barrier %.0f cycles\n",
+	        (double)ns / m.plan.segments.size(), (double)p1 / std::max<unsigned long long>(ns, 1), (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1));
+	{
+		unsigned long long b3[6] = {0, 0, 0, 0, 0, 0};
+		HIP_TRY(hipMemcpy(b3, m.dp.dbg + m.dp.dbg_wg_off + 4 * 512 * 2, sizeof b3, hipMemcpyDeviceToHost));
+		if (b3[2]) fprintf(stderr, "[whamd timing] backtrace per run: record load + prefetch %.0f cycles, walk + hand-over %.0f cycles (%llu runs); of the latter: local exit index %.0f, chain %.0f, logical indices + stores %.0f\n",
+		                   (double)b3[0] / b3[2], (double)b3[1] / b3[2], b3[2], (double)b3[3] / b3[2], (double)b3[4] / b3[2], (double)b3[5] / b3[2]);
+	}
+	if (m.plan.segments.size() > 104) {
+		std::vector<unsigned long long> wg(4 * 512 * 2);
+		HIP_TRY(hipMemcpy(wg.data(), m.dp.dbg + m.dp.dbg_wg_off, wg.size() * 8, hipMemcpyDeviceToHost));
+		unsigned long long prev_end = 0;
+		for (int sgi = 0; sgi < 4; ++sgi) {
+			const uint32_t G = 1u << m.plan.segments[100 + sgi].g;
+			unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
+			for (uint32_t ww = 0; ww < G; ++ww) {
+				const unsigned long long a2 = wg[((size_t)sgi * 512 + ww) * 2], b2 = wg[((size_t)sgi * 512 + ww) * 2 + 1];
+				s0 = std::min(s0, a2); s1 = std::max(s1, a2); e0 = std::min(e0, b2); e1 = std::max(e1, b2);
+			}
+			fprintf(stderr, "[whamd timing] run %d (%u workgroups): first start +%.2f us after previous run's last end; starts spread %.2f us; first end %.2f us, last end %.2f us after first start\n",
+			        100 + sgi, G, prev_end ? (double)(s0 - prev_end) / 100.0 : 0.0, (double)(s1 - s0) / 100.0, (double)(e0 - s0) / 100.0, (double)(e1 - s0) / 100.0);
+			prev_end = e1;
+		}
+	}
+	float f01 = 0;
+	(void)hipEventElapsedTime(&f01, m.ev0, m.ev1);
+	fprintf(stderr, "[whamd timing] segments %zu cols %llu | cycles/segment: prologue %.0f columns %.0f (%.0f per column) store %.0f | fwd %.3f ms, %.2f us per segment\n",
+	        m.plan.segments.size(), cols, (double)a / m.plan.segments.size(), (double)b / m.plan.segments.size(),
+	        (double)b / std::max<unsigned long long>(cols, 1), (double)c2 / m.plan.segments.size(), f01, f01 * 1e3 / m.plan.segments.size());
+	return WHAMD_OK;
+}
+
+// Synchronise, copy out, fill the stats.
 whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stats& st, std::string& msg) {
 	Impl& m = *impl_;
 	if (p.n_cols == 0) return WHAMD_OK;
 	HIP_TRY(hipSetDevice(m.device));
-	const uint64_t launches = m.launches;
-	if (m.tail_elsewhere) HIP_TRY(hipEventSynchronize(m.ev3));   // (the last thing submit_tail recorded, on the stream the tail went to)
+	const uint64_t launches = m.inflight.launches;
+	if (m.inflight.tail_elsewhere) HIP_TRY(hipEventSynchronize(m.ev3));   // (the last thing submit_tail recorded, on the stream the tail went to)
 	else { HIP_TRY(hipStreamSynchronize(m.stream)); m.own_stream_used = false; }
 	m.upload_pending = false;   // (the solve ran behind ev_upload: the uploads are there)
 	const uint32_t n = p.n_cols;
@@ -2153,9 +2297,9 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 	// (the event timings are read when somebody asks -- read_timing(), from whamd_dptable_get_stats: three runtime calls per table, from every
 	//  waiting thread at once, are a measurable part of collecting a 96-table step and most callers never look at them)
 	st.forward_ms = st.backtrace_ms = st.total_ms = 0;
-	m.timing_pending = true;
+	m.inflight.timing_pending = true;
 	st.forward_launches = launches;
-	st.group_tables = m.group_tables;
+	st.group_tables = m.inflight.group_tables;
 	st.bt_chunks = st.bt_missed = st.bt_rewalked = 0;
 	if (m.use_chunks) {
 		const uint32_t* c = m.h_pinned + 2 * (size_t)n + m.jobs.size();   // (downloaded with the path)
@@ -2164,66 +2308,9 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 		st.bt_rewalked = c[1];
 		if (debug_env("WHAMD_BT_STATS")) fprintf(stderr, "[whamd backtrace] %zu chunks, %u guesses missed (%u of them only in the transmission value), %u units walked again (of %zu)\n", m.chunks.size(), c[0], c[2], c[1], m.units.size());
 	}
-	if (m.dp.dbg && m.use_slots) {
-		std::vector<unsigned long long> d(m.splan.runs.size() * 48);
-		HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
-		double a[6] = {0, 0, 0, 0, 0, 0};
-		double percol[32] = {0};
-		size_t cnt = 0;
-		for (size_t i = 0; i < m.splan.runs.size(); ++i) {
-			if (m.splan.runs[i].ncols != 22 || d[48 * i + 5] == 0) continue;   // full-length runs only
-			for (int k = 0; k < 6; ++k) a[k] += (double)d[48 * i + k];
-			for (int k = 0; k < 22; ++k) percol[k] += (double)d[48 * i + 8 + k];
-			++cnt;
-		}
-		if (cnt) fprintf(stderr, "[whamd slot stamps] %zu runs, wave 0 of workgroup 0, shader cycles: prologue issue %.0f, loads landed %.0f, column loop %.0f (%.1f per column, %.1f columns), exit %.0f\n",
-		                 cnt, a[0] / cnt, a[1] / cnt, a[2] / cnt, a[2] / std::max(a[4], 1.0), a[4] / cnt, a[3] / cnt);
-		if (cnt) {
-			fprintf(stderr, "[whamd slot stamps] cycles after the loop start at which column c had its cost added:");
-			for (int k = 0; k < 22; ++k) fprintf(stderr, " %.0f", percol[k] / cnt);
-			fprintf(stderr, "\n");
-		}
-	}
-	if (m.dp.dbg && !m.plan.segments.empty()) {
-		std::vector<unsigned long long> d(m.plan.segments.size() * 8);
-		HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
-		unsigned long long a = 0, b = 0, c2 = 0, cols = 0, p1 = 0, p2 = 0, p3 = 0, ns = 0;
-		for (size_t i = 0; i < m.plan.segments.size(); ++i) { a += d[8 * i]; b += d[8 * i + 1]; c2 += d[8 * i + 2]; cols += d[8 * i + 3]; p1 += d[8 * i + 4]; p2 += d[8 * i + 5]; p3 += d[8 * i + 6]; ns += d[8 * i + 7]; }
-		if (!m.plan.ped_columns.empty() || (m.dp.dbg_flags & 4u))
-			fprintf(stderr, "[whamd timing] run prologue (wave 0 of workgroup 0), cycles after the first instruction: kernel arguments usable %.0f, first loaded data %.0f, everything staged %.0f\n",
-			        (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1), (double)p1 / std::max<unsigned long long>(ns, 1));
-		else
-		fprintf(stderr, "[whamd timing] per barrier step (wave 0 of workgroup 0, %.1f steps per run): hot words %.0f, evaluate %.0f, barrier %.0f cycles\n",
-		        (double)ns / m.plan.segments.size(), (double)p1 / std::max<unsigned long long>(ns, 1), (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1));
-		{
-			unsigned long long b3[6] = {0, 0, 0, 0, 0, 0};
-			HIP_TRY(hipMemcpy(b3, m.dp.dbg + m.dp.dbg_wg_off + 4 * 512 * 2, sizeof b3, hipMemcpyDeviceToHost));
-			if (b3[2]) fprintf(stderr, "[whamd timing] backtrace per run: record load + prefetch %.0f cycles, walk + hand-over %.0f cycles (%llu runs); of the latter: local exit index %.0f, chain %.0f, logical indices + stores %.0f\n",
-			                   (double)b3[0] / b3[2], (double)b3[1] / b3[2], b3[2], (double)b3[3] / b3[2], (double)b3[4] / b3[2], (double)b3[5] / b3[2]);
-		}
-		if (m.plan.segments.size() > 104) {
-			std::vector<unsigned long long> wg(4 * 512 * 2);
-			HIP_TRY(hipMemcpy(wg.data(), m.dp.dbg + m.dp.dbg_wg_off, wg.size() * 8, hipMemcpyDeviceToHost));
-			unsigned long long prev_end = 0;
-			for (int sgi = 0; sgi < 4; ++sgi) {
-				const uint32_t G = 1u << m.plan.segments[100 + sgi].g;
-				unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
-				for (uint32_t ww = 0; ww < G; ++ww) {
-					const unsigned long long a2 = wg[((size_t)sgi * 512 + ww) * 2], b2 = wg[((size_t)sgi * 512 + ww) * 2 + 1];
-					s0 = std::min(s0, a2); s1 = std::max(s1, a2); e0 = std::min(e0, b2); e1 = std::max(e1, b2);
-				}
-				fprintf(stderr, "[whamd timing] run %d (%u workgroups): first start +%.2f us after previous run's last end; starts spread %.2f us; first end %.2f us, last end %.2f us after first start\n",
-				        100 + sgi, G, prev_end ? (double)(s0 - prev_end) / 100.0 : 0.0, (double)(s1 - s0) / 100.0, (double)(e0 - s0) / 100.0, (double)(e1 - s0) / 100.0);
-				prev_end = e1;
-			}
-		}
-		float f01 = 0;
-		(void)hipEventElapsedTime(&f01, m.ev0, m.ev1);
-		fprintf(stderr, "[whamd timing] segments %zu cols %llu | cycles/segment: prologue %.0f columns %.0f (%.0f per column) store %.0f | fwd %.3f ms, %.2f us per segment\n",
-		        m.plan.segments.size(), cols, (double)a / m.plan.segments.size(), (double)b / m.plan.segments.size(),
-		        (double)b / std::max<unsigned long long>(cols, 1), (double)c2 / m.plan.segments.size(), f01, f01 * 1e3 / m.plan.segments.size());
-	}
-	return WHAMD_OK;
+	whamd_status_t reported = m.dp.dbg && m.use_slots ? m.report_slot_stamps(msg) : WHAMD_OK;   // (the debug library's in-kernel cycle stamps)
+	if (reported == WHAMD_OK && m.dp.dbg && !m.plan.segments.empty()) reported = m.report_resident_stamps(msg);
+	return reported;
 }
 
 }  // namespace whamd
