@@ -86,6 +86,56 @@ whamd_status_t whamd_debug_progeny_pair_score_host(const float* gl, uint64_t n_p
 whamd_status_t whamd_debug_progeny_variant_types_host(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
                                                       const uint32_t* nodes, uint64_t n_nodes, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
 
+/* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
+ * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
+ *
+ * The registry: every kernel a solve can launch, under the spelling of its instantiation ("slot_run<3, false, true, true>").
+ * large_lds_opted_in: the kernel is in the array the large-LDS opt-in walks (a launch with more than 64 KiB of dynamic LDS needs it);
+ * debug_only: an instantiation only this library has (cycle stamps, timing switches, pedigree X runs). */
+typedef struct whamd_debug_kernel {
+	const void* kernel;
+	const char* name;
+	int32_t large_lds_opted_in;
+	int32_t debug_only;
+} whamd_debug_kernel;
+/* Writes at most `capacity` entries to out[] (may be NULL) and returns how many there are. */
+size_t whamd_debug_solve_kernels(whamd_debug_kernel* out, size_t capacity);
+
+/* Where a launch was made. */
+enum {
+	WHAMD_LAUNCH_COLUMN = 0,      /* launch_column_step: column_step_fused | column_step_keys / column_step_wide + column_finalize */
+	WHAMD_LAUNCH_RUN = 1,         /* launch_run: an LDS-resident run on its own */
+	WHAMD_LAUNCH_SLOT_RUN = 2,    /* launch_slot_run: a slot run on its own */
+	WHAMD_LAUNCH_BATCH = 3,       /* submit_super_step: the runs of a super-step as one resident_batch / slot_batch launch */
+	WHAMD_LAUNCH_GROUP = 4,       /* GroupSubmission::flush: one variant's runs of several tables */
+	WHAMD_LAUNCH_GROUP_WALK = 5,  /* GroupSubmission::walk_batch: the batched backtrace and superreads */
+	WHAMD_LAUNCH_TAIL = 6,        /* submit_tail: backtrace and superreads of one table */
+	WHAMD_LAUNCH_WINDOW_WALK = 7, /* submit_super_step: the walk of one window of a windowed solve */
+	WHAMD_LAUNCH_TABLES = 8       /* begin_solve: ped_tables / resident_tables */
+};
+
+/* One line of a table's ledger: `count` launches that agree in everything else.  A fact the launch site does not have is -1.  A launch of a group
+ * is entered in every member that counts it in whamd_solve_stats::forward_launches. */
+typedef struct whamd_debug_launch {
+	const void* kernel;
+	uint32_t site;          /* WHAMD_LAUNCH_* */
+	uint32_t grid_x, grid_y, block;
+	uint32_t lds;           /* dynamic LDS bytes */
+	uint32_t own_stream;    /* 1: the table's own stream, 0: the stream of a group's lead */
+	uint32_t forward;       /* 1: counted in forward_launches */
+	/* what the choice was made from */
+	int32_t lr, yflags, spec, stamps, tb, nf, ncols, threads;   /* of a run launched on its own (run.threads ...) */
+	int32_t streamed, pack;                                     /* X runs */
+	int32_t tight, variant;                                     /* group launches: GroupVariant */
+	int32_t T, n_ind, mode, wide;                               /* per-column steps */
+	int32_t ped, sym;                                           /* LDS-resident runs: sg.kind, the complement symmetry */
+	int32_t entries;                                            /* runs of a batched launch */
+	uint64_t count;
+	const char* name;       /* the registry's name of `kernel`; NULL: the pointer is not registered (an error of the library) */
+} whamd_debug_launch;
+/* The ledger of the solve the table collected last (after whamd_dptable_wait): at most `capacity` lines to out[] (may be NULL), *n_out: how many there are. */
+whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_debug_launch* out, size_t capacity, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,3 +199,37 @@ def test_the_library_is_loaded_once_when_many_threads_ask_first():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     got = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=root, check=True).stdout.strip()
     assert got == "1"
+
+
+def test_the_registry_of_the_solves_kernels_without_a_device():
+    """The launch ledger's registry (whamd_debug_solve_kernels, dp_device.hip): names are instantiations spelled out and unique, so are the pointers;
+    the shipping entries are exactly what the rule table of tests/test_gpu_kernel_choice.py can name (a new instantiation must enter both); the
+    large-LDS flags are those of the array the opt-in walks -- every X run, LDS-resident and pedigree kernel but pedslot_run<2, 2, ...>, and none of
+    slot_run / slot_batch / slot_group, whose launches stay below 64 KiB; the product library has neither entry point."""
+    import subprocess
+
+    import test_gpu_kernel_choice as choice
+
+    kernels = _native.debug_solve_kernels()
+    names = [k["name"] for k in kernels]
+    assert len(set(names)) == len(names) and len({k["kernel"] for k in kernels}) == len(kernels)
+    assert all(re.fullmatch(r"[a-z_]+(<[A-Za-z0-9_, ]+>)?", n) for n in names), names
+    shipping = {k["name"] for k in kernels if not k["debug_only"]}
+    assert len(shipping) == 107 and len(kernels) == 148
+    assert shipping == choice.rule_range(), (sorted(shipping - choice.rule_range()), sorted(choice.rule_range() - shipping))
+    assert set(choice.EXCLUDED) <= shipping
+    for k in kernels:
+        if k["debug_only"]:
+            continue
+        n = k["name"]
+        family = n.split("<")[0]
+        if family in ("slot_run", "slot_batch", "slot_group", "column_step_fused", "column_step_keys", "column_step_wide", "column_finalize", "ped_tables",
+                      "resident_tables", "backtrace_chunks", "backtrace_gather", "backtrace_chunks_group", "backtrace_gather_group", "superreads_single",
+                      "superreads_group") or n.startswith("pedslot_run<2, 2,"):
+            assert not k["large_lds_opted_in"], n
+        else:
+            assert k["large_lds_opted_in"], n
+    exported = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert "whamd_debug_solve_kernels" not in exported and "whamd_debug_dptable_launches" not in exported
+    debug = subprocess.run(["nm", "-D", "--defined-only", _native.DEBUG_LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert "whamd_debug_solve_kernels" in debug and "whamd_debug_dptable_launches" in debug

@@ -345,6 +345,10 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_progeny_variant_types_host.restype = C.c_int
     L.whamd_debug_progeny_variant_types_host.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                                          C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_debug_solve_kernels.restype = C.c_size_t
+    L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
+    L.whamd_debug_dptable_launches.restype = C.c_int
+    L.whamd_debug_dptable_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_size_t, C.POINTER(C.c_size_t)]
     _debug_lib = L
     return L
 
@@ -687,6 +691,53 @@ def debug_lazy_terms_check(problem: ProblemArrays, need=None, rounds: int = 1) -
     _check(fn(*problem.call_args(), None if need_arr is None else _ptr(need_arr, C.c_uint8), C.c_int(int(rounds)), C.byref(lazy), C.byref(diff),
               C.byref(before), C.byref(after)), D)
     return {"lazy": bool(lazy.value), "differences": int(diff.value), "built_before": int(before.value), "built_after": int(after.value)}
+
+
+class DebugKernel(C.Structure):
+    """whamd_debug_kernel (include/whatshap_amd_debug.h)."""
+    _fields_ = [("kernel", C.c_void_p), ("name", C.c_char_p), ("large_lds_opted_in", C.c_int32), ("debug_only", C.c_int32)]
+
+
+LAUNCH_SITES = ("column", "run", "slot_run", "batch", "group", "group_walk", "tail", "window_walk", "tables")   # WHAMD_LAUNCH_*
+LAUNCH_FACTS = ("lr", "yflags", "spec", "stamps", "tb", "nf", "ncols", "threads", "streamed", "pack", "tight", "variant", "T", "n_ind", "mode", "wide",
+                "ped", "sym", "entries")
+
+
+class DebugLaunch(C.Structure):
+    """whamd_debug_launch (include/whatshap_amd_debug.h)."""
+    _fields_ = ([("kernel", C.c_void_p), ("site", C.c_uint32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("block", C.c_uint32), ("lds", C.c_uint32),
+                 ("own_stream", C.c_uint32), ("forward", C.c_uint32)] + [(f, C.c_int32) for f in LAUNCH_FACTS] + [("count", C.c_uint64), ("name", C.c_char_p)])
+
+
+def debug_solve_kernels() -> list:
+    """whamd_debug_solve_kernels: the registry of the solve's kernels -- dicts of name (the instantiation's spelling), large_lds_opted_in, debug_only."""
+    D = debug_lib()
+    n = D.whamd_debug_solve_kernels(None, 0)
+    arr = (DebugKernel * n)()
+    D.whamd_debug_solve_kernels(arr, n)
+    return [{"kernel": k.kernel, "name": k.name.decode(), "large_lds_opted_in": bool(k.large_lds_opted_in), "debug_only": bool(k.debug_only)} for k in arr]
+
+
+def debug_launches(table) -> list:
+    """whamd_debug_dptable_launches: the launch ledger of the solve `table` (made by the debug library) collected last.  One dict per distinct
+    launch: name (of the registry), site (LAUNCH_SITES), grid_x, grid_y, block, lds, own_stream, forward, count and the facts the choice was made
+    from (LAUNCH_FACTS; None where the launch site does not have the fact).  A kernel the registry does not know is an error."""
+    D = debug_lib()
+    if table._L is not D:
+        raise ValueError("the launch ledger exists in the debug library only (use_debug_library() before the table is made)")
+    n = C.c_size_t()
+    _check(D.whamd_debug_dptable_launches(table._h, None, 0, C.byref(n)), D)
+    arr = (DebugLaunch * max(n.value, 1))()
+    _check(D.whamd_debug_dptable_launches(table._h, arr, n.value, C.byref(n)), D)
+    out = []
+    for r in arr[:n.value]:
+        if r.name is None:
+            raise RuntimeError(f"a launch of site {LAUNCH_SITES[r.site]} (grid {r.grid_x} x {r.grid_y}, block {r.block}) took a kernel the registry does not list")
+        rec = {"name": r.name.decode(), "site": LAUNCH_SITES[r.site], "grid_x": r.grid_x, "grid_y": r.grid_y, "block": r.block, "lds": r.lds,
+               "own_stream": bool(r.own_stream), "forward": bool(r.forward), "count": int(r.count)}
+        rec.update({f: (None if getattr(r, f) < 0 else getattr(r, f)) for f in LAUNCH_FACTS})
+        out.append(rec)
+    return out
 
 
 def _heuristic_result(L, h) -> dict:

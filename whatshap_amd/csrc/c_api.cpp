@@ -788,6 +788,15 @@ whamd_status_t whamd_debug_lazy_terms_check(const whamd_readset_view* readset, c
 	return WHAMD_OK;
 	});
 }
+
+size_t whamd_debug_solve_kernels(whamd_debug_kernel* out, size_t capacity) { return DeviceTable::debug_solve_kernels(out, capacity); }
+
+whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_debug_launch* out, size_t capacity, size_t* n_out) {
+	if (!table || !n_out) return fail(WHAMD_ERR_INVALID, "null argument");
+	if (!table->solved) return fail(WHAMD_ERR_INVALID, "the table has not been solved: its ledger is read after whamd_dptable_wait");
+	*n_out = table->device.debug_launches(out, capacity);
+	return WHAMD_OK;
+}
 #endif   // WHAMD_DEBUG_BUILD
 
 }  // extern "C"

@@ -2,6 +2,9 @@
 #pragma once
 #include <string>
 
+#ifdef WHAMD_DEBUG_BUILD
+#include "../../include/whatshap_amd_debug.h"
+#endif
 #include "device_types.h"
 #include "problem.h"
 
@@ -65,6 +68,12 @@ public:
 	void set_shared_launches(bool v);
 	// the table's launches will run BESIDE other tables' on the same device (own streams, whamd_dptable_enqueue_many): kernels that leave room on a CU
 	void set_side_by_side(bool v);
+
+#ifdef WHAMD_DEBUG_BUILD
+	// The launch ledger of the debug library (include/whatshap_amd_debug.h): the registry of the solve's kernels, and the launches of the solve wait() collected last.
+	static size_t debug_solve_kernels(whamd_debug_kernel* out, size_t capacity);
+	size_t debug_launches(whamd_debug_launch* out, size_t capacity) const;
+#endif
 
 private:
 	whamd_status_t enqueue_some_unguarded(const Problem& p, Solution& s, uint64_t budget, bool& done, std::string& msg);

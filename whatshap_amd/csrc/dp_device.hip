@@ -29,6 +29,9 @@
 #include <vector>
 
 #include "debug_build.h"
+#ifdef WHAMD_DEBUG_BUILD
+#include "../../include/whatshap_amd_debug.h"
+#endif
 #include "device_runtime.h"
 #include "device_table.h"
 #include "genotype.h"
@@ -249,6 +252,26 @@ struct TableBuild {
 
 // ================================================================================================ DeviceTable
 
+#ifdef WHAMD_DEBUG_BUILD
+// What a launch site knows of the choice it made, for the ledger: a whamd_debug_launch with every fact "not known" (-1), filled by name.
+struct LaunchFacts : whamd_debug_launch {
+	LaunchFacts() {
+		std::memset(static_cast<whamd_debug_launch*>(this), 0, sizeof(whamd_debug_launch));
+		lr = yflags = spec = stamps = tb = nf = ncols = threads = streamed = pack = tight = variant = T = n_ind = mode = wide = ped = sym = entries = -1;
+	}
+	static LaunchFacts of_run(const SlotRun& run, bool spec_v, bool stamps_v) {
+		LaunchFacts f;
+		f.lr = (int32_t)run.lr; f.yflags = (int32_t)run.yflags; f.ncols = (int32_t)run.ncols; f.threads = (int32_t)run.threads;
+		f.spec = spec_v; f.stamps = stamps_v;
+		return f;
+	}
+};
+// WHAMD_NOTE(table, site, kernel, grid, block, lds, stream, forward, facts): the debug library enters the launch in the table's ledger; the product has no ledger.
+#define WHAMD_NOTE(table, ...) (table).note(__VA_ARGS__)
+#else
+#define WHAMD_NOTE(table, ...) ((void)0)
+#endif
+
 struct DeviceTable::Impl {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -414,6 +437,11 @@ struct DeviceTable::Impl {
 		// No solve is being submitted: the next enqueue begins with the preamble again, on the table's own stream.
 		void rewind(hipStream_t own) { enqueue_open = false; next_super = 0; run_stream = own; }
 	} inflight;
+#ifdef WHAMD_DEBUG_BUILD
+	// The launch ledger (whatshap_amd_debug.h): one line per distinct launch of the solve in flight, with a count.  begin_solve empties it.
+	std::vector<whamd_debug_launch> ledger;
+	void note(uint32_t site, const void* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t on, bool forward, const LaunchFacts& facts);
+#endif
 	// the solve, step by step
 	struct GroupSubmission;
 	void launch_column_step(const Problem& p, const Step& step, const Lane& lane, const uint32_t* prev, uint32_t* cur, uint64_t& launches);
@@ -1475,7 +1503,8 @@ whamd_status_t DeviceTable::Impl::arm_debug_stamps(TableUploader& up, std::strin
 
 // Kernels with more than 64 KiB of dynamic LDS need the opt-in on every device they run on -- once per process and device (23 driver calls
 // per table were a tenth of a coverage-15 create when many tables are built at once).
-static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
+// (The array is a function of its own because the debug library's kernel registry reads it too: the registry's large_lds_opted_in IS this array.)
+static const void* const* large_lds_kernels(size_t& count) {
 #define K(...) reinterpret_cast<const void*>((__VA_ARGS__))
 #define WHAMD_RUNX(XC, STAMPS) K(slot_runx<2, XC, STAMPS, false>), K(slot_runx<2, XC, STAMPS, true>)
 #define WHAMD_PSLOT(TBV, NFV) K(pedslot_run<TBV, NFV, false, false>), K(pedslot_run<TBV, NFV, false, true>), K(pedslot_run<TBV, NFV, true, false>), K(pedslot_run<TBV, NFV, true, true>)
@@ -1510,11 +1539,18 @@ static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
 #undef WHAMD_RUNX
 #undef WHAMD_PSLOT
 #undef WHAMD_PSLOTX
+	count = sizeof(kernels) / sizeof(kernels[0]);
+	return kernels;
+}
+
+static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
 	static std::mutex attr_mu;
 	static unsigned long long attr_done = 0;   // bit = device
 	std::lock_guard<std::mutex> lock(attr_mu);
 	if (device < 64 && ((attr_done >> device) & 1ull)) return WHAMD_OK;
-	for (const void* kernel : kernels) HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	size_t count = 0;
+	const void* const* kernels = large_lds_kernels(count);
+	for (size_t i = 0; i < count; ++i) HIP_TRY(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 	if (device < 64) attr_done |= 1ull << device;
 	return WHAMD_OK;
 }
@@ -1713,19 +1749,25 @@ void DeviceTable::Impl::launch_column_step(const Problem& p, const Step& step, c
 	dp.keys = lane.d_keys;
 	const uint32_t c = step.index;
 	const DevColumn& d = m.cols[c];
+#ifdef WHAMD_DEBUG_BUILD
+	const auto column_facts = [&m](const Problem& pr, const DevColumn& col) { LaunchFacts f; f.T = (int32_t)pr.T; f.n_ind = (int32_t)m.dp.n_ind; f.mode = (int32_t)col.mode; f.wide = m.wide; return f; };
+#endif
 	if (d.mode == 0) {
 		const uint32_t threads = 1u << d.f;
 		const uint32_t block = std::min<uint32_t>(256, threads);
 		hipLaunchKernelGGL(m.fused, dim3(threads / block), dim3(block), 0, rs, dp, c, prev, cur);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, (const void*)m.fused, dim3(threads / block), dim3(block), 0, rs, true, column_facts(p, d));
 		launches += 1;
 	} else {
 		const uint64_t total = (1ull << (d.f + d.ebits - d.eloop)) * (m.wide ? p.T : 1u);
 		const uint32_t block = (uint32_t)std::min<uint64_t>(256, (total + 63) / 64 * 64);
 		if (m.wide) hipLaunchKernelGGL(column_step_wide, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
 		else hipLaunchKernelGGL(m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, m.wide ? (const void*)column_step_wide : (const void*)m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, true, column_facts(p, d));
 		const uint32_t entries = (1u << d.f) * p.T;
 		const uint32_t fblock = std::min<uint32_t>(256, (entries + 63) / 64 * 64);
 		hipLaunchKernelGGL(column_finalize, dim3((entries + fblock - 1) / fblock), dim3(fblock), 0, rs, dp, c, cur, entries);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, (const void*)column_finalize, dim3((entries + fblock - 1) / fblock), dim3(fblock), 0, rs, true, column_facts(p, d));
 		launches += 2;
 	}
 }
@@ -1736,15 +1778,25 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 	const ResSegment& sg = e.sg;
 	const hipStream_t rs = m.inflight.run_stream;
 	const bool stamps = DEBUG_BUILD && m.dp.dbg != nullptr;
+#ifdef WHAMD_DEBUG_BUILD
+	const auto segment_facts = [&sg, stamps](bool spec, bool sym) {
+		LaunchFacts f;
+		f.ped = sg.kind == 1; f.stamps = stamps; f.ncols = (int32_t)sg.ncols; f.threads = (int32_t)sg.threads;
+		if (sg.kind == 1) f.spec = spec; else f.sym = sym;
+		return f;
+	};
+#endif
 	if (sg.kind == 1) {
 		const size_t words = ((size_t)sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)sg.n_terms * 2 + 3) & ~(size_t)3;
 		const size_t lds_ped = words * 4 + 2 * ((size_t)16 << sg.max_l) + (size_t)sg.stage_words * 8;
 		const PedSegmentFn kernel = ped_segment_kernel(stamps, sg.in_mirror_bit && m.use_chunks);
 		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, m.dp, sg, e.prev, e.cur);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, true, segment_facts(sg.in_mirror_bit && m.use_chunks, false));
 	} else {
 		const size_t lds = (size_t)sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << sg.max_l) + (size_t)sg.stage_words * 8;
 		const SegmentFn kernel = segment_kernel(stamps, sg.half || sg.in_half || sg.mirror_out);
 		hipLaunchKernelGGL(kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, m.dp, sg, e.prev, e.cur, e.score_out);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, true, segment_facts(false, sg.half || sg.in_half || sg.mirror_out));
 	}
 	launches += 1;
 }
@@ -1769,6 +1821,11 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 		}
 #endif
 		hipLaunchKernelGGL(kernel, dim3(1u << run.g), dim3(run.threads), lds, rs, m.dp, run, ex, e.prev, e.cur);
+#ifdef WHAMD_DEBUG_BUILD
+		LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
+		facts.ped = 1; facts.tb = (int32_t)ex.tb; facts.nf = (int32_t)ex.nf; facts.pack = (run.yflags & 16u) != 0;
+		WHAMD_NOTE(m, WHAMD_LAUNCH_SLOT_RUN, (const void*)kernel, dim3(1u << run.g), dim3(run.threads), lds, rs, true, facts);
+#endif
 		return;
 	}
 	const dim3 grid(1u << (run.g - run.half)), block(run.threads);
@@ -1783,11 +1840,21 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 		const uint32_t xc = streamed ? 0u : (run.ncols <= 8u && !stamps) ? 8u : (run.ncols <= 16u && !stamps) ? 16u : run.ncols <= 24u ? 24u : 32u;
 		const SlotRunXFn kernel = slot_runx_kernel(xc, stamps, spec);
 		hipLaunchKernelGGL(kernel, dim3(pack ? grid.x * 8u : grid.x), block, lds_x, rs, m.dp, run, e.prev, e.cur, e.score_out, pack);
+#ifdef WHAMD_DEBUG_BUILD
+		LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
+		facts.ped = 0; facts.streamed = streamed; facts.pack = (int32_t)pack;
+		WHAMD_NOTE(m, WHAMD_LAUNCH_SLOT_RUN, (const void*)kernel, dim3(pack ? grid.x * 8u : grid.x), block, lds_x, rs, true, facts);
+#endif
 		return;
 	}
 	const size_t lds = slot_run_lds_bytes(run.threads, run.lr, run.ncols);   // wave-slot exchange + hot lines + per-wave A + lane sums
 	const SlotRunFn kernel = slot_run_kernel(run.lr, (run.yflags & 1u) != 0, stamps, spec);
 	hipLaunchKernelGGL(kernel, grid, block, lds, rs, m.dp, run, e.prev, e.cur, e.score_out);
+#ifdef WHAMD_DEBUG_BUILD
+	LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
+	facts.ped = 0;
+	WHAMD_NOTE(m, WHAMD_LAUNCH_SLOT_RUN, (const void*)kernel, grid, block, lds, rs, true, facts);
+#endif
 }
 
 // Resumable submission: the first call does the preamble, every call submits super-steps until at least `budget`
@@ -1821,6 +1888,9 @@ whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std
 	s.superreads_done = false;
 	m.inflight.launches = 0;
 	m.inflight.next_super = 0;
+#ifdef WHAMD_DEBUG_BUILD
+	m.ledger.clear();
+#endif
 	if (n == 0) return WHAMD_OK;
 	if (rs == m.stream) m.own_stream_used = true;
 	if (m.ev_upload && (m.upload_pending || rs != m.stream)) HIP_TRY(hipStreamWaitEvent(rs, m.ev_upload, 0));   // (the uploads went through an upload stream; once a solve has been collected they are known to be there)
@@ -1833,9 +1903,11 @@ whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std
 	if (!m.plan.ped_columns.empty()) {
 		const uint32_t entries = (uint32_t)m.plan.ped_columns.size() * PED_TABLE;
 		hipLaunchKernelGGL(ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.ped_cols, (uint32_t)m.plan.ped_columns.size(), m.dp.ped_tables);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TABLES, (const void*)ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, false, LaunchFacts());
 	} else if (!m.use_slots && !m.plan.columns.empty()) {
 		const uint32_t entries = (uint32_t)m.plan.columns.size() * RES_TABLE;
 		hipLaunchKernelGGL(resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.res_cols, (uint32_t)m.plan.columns.size(), m.dp.res_tables);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TABLES, (const void*)resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, false, LaunchFacts());
 	}
 	return WHAMD_OK;
 }
@@ -1853,14 +1925,23 @@ whamd_status_t DeviceTable::Impl::submit_super_step(const Problem& p, const Supe
 	} else if (ss.entry_count > 1) {
 		if (m.use_slots) { const SlotBatchFn kernel = slot_batch_kernel(m.slot_lr_used); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_slot_entries + ss.entry_off); }
 		else { const ResBatchFn kernel = resident_batch_kernel(ss.sym); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_entries + ss.entry_off); }
+#ifdef WHAMD_DEBUG_BUILD
+		LaunchFacts facts;
+		facts.entries = (int32_t)ss.entry_count;
+		if (m.use_slots) facts.lr = m.slot_lr_used; else facts.sym = ss.sym;
+		WHAMD_NOTE(m, WHAMD_LAUNCH_BATCH, m.use_slots ? (const void*)slot_batch_kernel(m.slot_lr_used) : (const void*)resident_batch_kernel(ss.sym), grid, block, ss.lds, rs, true, facts);
+#endif
 		launches += 1;
 	}
 	const whamd_status_t st = m.submit_singles(p, ss, launches, msg);
 	if (st != WHAMD_OK) return st;
 	if (ss.ck_save >= 0) HIP_TRY(hipMemcpyAsync(m.d_checkpoints + (size_t)ss.ck_save * m.checkpoint_bytes, ss.io[1], m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
 	if (ss.bt_window >= 0)
+	{
 		hipLaunchKernelGGL(backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, rs, m.dp, m.d_units, m.d_window_jobs + ss.bt_window,
 		                   m.d_path_index, m.d_path_trans, m.d_score);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_WINDOW_WALK, (const void*)backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, rs, false, LaunchFacts());
+	}
 	return WHAMD_OK;
 }
 
@@ -1898,13 +1979,19 @@ whamd_status_t DeviceTable::Impl::submit_tail(const Problem& p, std::string& msg
 		                   (uint32_t)m.chunks.size(), (uint32_t)m.units.size(), 1u, m.n_orient_max, m.d_path2, m.d_trans2, m.d_score, m.d_unit_x, m.d_guess, m.d_sel, m.d_bt_counters);
 		hipLaunchKernelGGL(backtrace_gather, dim3((uint32_t)m.units.size()), dim3(64), 0, ts, m.d_units, (uint32_t)m.units.size(), n, m.d_path2, m.d_trans2, m.d_sel,
 		                   m.d_path_index, m.d_path_trans);
-	} else if (!m.windowed)   // (windowed: every window was walked right after its steps)
-	hipLaunchKernelGGL(backtrace_kernel, dim3((uint32_t)m.jobs.size()), dim3(1024), m.bt_lds, ts, m.dp, m.d_units, m.d_btjobs,
-	                   m.d_path_index, m.d_path_trans, m.d_score);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(m.n_orient_max * (uint32_t)m.chunks.size()), dim3(256), m.chunk_lds, ts, false, LaunchFacts());
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(1), dim3(256), m.chunk_lds, ts, false, LaunchFacts());
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_gather, dim3((uint32_t)m.units.size()), dim3(64), 0, ts, false, LaunchFacts());
+	} else if (!m.windowed) {   // (windowed: every window was walked right after its steps)
+		hipLaunchKernelGGL(backtrace_kernel, dim3((uint32_t)m.jobs.size()), dim3(1024), m.bt_lds, ts, m.dp, m.d_units, m.d_btjobs,
+		                   m.d_path_index, m.d_path_trans, m.d_score);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_kernel, dim3((uint32_t)m.jobs.size()), dim3(1024), m.bt_lds, ts, false, LaunchFacts());
+	}
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(m.ev2, ts));
 	if (m.device_superreads && !walked_by_group) {
 		hipLaunchKernelGGL(superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, m.super_args);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, false, LaunchFacts());
 		HIP_TRY(hipGetLastError());
 	}
 	// ONE download per table (the device block has the pinned buffer's layout, upload()); pinned: a copy into pageable memory would block this call until the stream drains
@@ -2056,11 +2143,23 @@ struct DeviceTable::Impl::GroupSubmission {
 		const dim3 grid = by_table ? dim3((b.args.n + 7u) & ~7u, b.grid_x) : dim3(b.grid_x, b.args.n), block(b.threads);
 		const GroupFn kernel = group_kernel(v, DEBUG_BUILD && lead.dp.dbg_flags != 0, tight);
 		hipLaunchKernelGGL(kernel, grid, block, b.lds, lead.stream, b.args);
+#ifdef WHAMD_DEBUG_BUILD
+		const uint32_t members = b.args.n;
+		const size_t lds = b.lds;
+#endif
 		b.args.n = 0;
 		b.grid_x = b.threads = 0;
 		b.lds = 0;
+#ifdef WHAMD_DEBUG_BUILD
+		LaunchFacts facts;
+		facts.variant = (int32_t)v; facts.tight = tight; facts.stamps = lead.dp.dbg_flags != 0; facts.entries = (int32_t)members;
+#endif
 		for (size_t j = 0; j < n; ++j)
-			if (counted[j * GROUP_VARIANTS + v]) { table_launches[j] += 1; counted[j * GROUP_VARIANTS + v] = 0; }
+			if (counted[j * GROUP_VARIANTS + v]) {
+				table_launches[j] += 1;
+				counted[j * GROUP_VARIANTS + v] = 0;
+				WHAMD_NOTE(member(j), WHAMD_LAUNCH_GROUP, (const void*)kernel, grid, block, lds, lead.stream, true, facts);
+			}
 	}
 
 	// The per-column steps of super-step k, member by member.
@@ -2116,6 +2215,17 @@ struct DeviceTable::Impl::GroupSubmission {
 		for (size_t i : batch) if (member(i).device_superreads) gs = std::max(gs, (problems[i]->n_cols + 255u) / 256u);
 		if (gs) hipLaunchKernelGGL(superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, args);
 		if (hipGetLastError() != hipSuccess) return false;
+#ifdef WHAMD_DEBUG_BUILD
+		for (size_t i : batch) {   // (every member the launches walk; superreads_group in those it makes superreads for)
+			Impl& m = member(i);
+			LaunchFacts facts;
+			facts.entries = (int32_t)args.n;
+			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_chunks_group, dim3(gx, args.n), dim3(256), lds, lead.stream, false, facts);
+			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_chunks_group, dim3(1, args.n), dim3(256), lds, lead.stream, false, facts);
+			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_gather_group, dim3(gu, args.n), dim3(64), 0, lead.stream, false, facts);
+			if (gs && m.device_superreads) m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, false, facts);
+		}
+#endif
 		for (size_t i : batch) walked[i] = 1;
 		batch.clear();
 		return true;
@@ -2312,5 +2422,106 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 	if (reported == WHAMD_OK && m.dp.dbg && !m.plan.segments.empty()) reported = m.report_resident_stamps(msg);
 	return reported;
 }
+
+// ================================================================================================ the launch ledger (debug library)
+#ifdef WHAMD_DEBUG_BUILD
+namespace {
+
+// The registry of the launch ledger: EVERY kernel a solve can launch, under the spelling of its instantiation.  A table of its own -- the *_kernel functions
+// do not feed it, so that a test can hold what they return against it -- and at the END of the file, behind every launch, so that it is nowhere the first to
+// name a kernel (the code object keeps its order: opt_in_large_lds).  A new instantiation is added HERE as well, and tests/test_gpu_kernel_choice.py must reach
+// it.  debug_only: cycle stamps, timing switches, pedigree X runs.
+template <int T, int NIND>
+const void* column_pair(bool keys) {
+	FusedFn ff;
+	KeysFn kf;
+	pick<T, NIND>(ff, kf);
+	return keys ? reinterpret_cast<const void*>(kf) : reinterpret_cast<const void*>(ff);
+}
+
+const std::vector<whamd_debug_kernel>& solve_kernels() {
+#define K(...) {reinterpret_cast<const void*>((__VA_ARGS__)), #__VA_ARGS__, 0, 0}
+#define D(...) {reinterpret_cast<const void*>((__VA_ARGS__)), #__VA_ARGS__, 0, 1}
+// (the per-column kernels are named by pick<T, NIND> alone, first in the code object: spelled here they would be named before pick is instantiated and move)
+#define WHAMD_COLUMN(T, NIND) {column_pair<T, NIND>(false), "column_step_fused<" #T ", " #NIND ">", 0, 0}, {column_pair<T, NIND>(true), "column_step_keys<" #T ", " #NIND ">", 0, 0}
+#define WHAMD_PSLOT(TB, NF) K(pedslot_run<TB, NF, true, true>), K(pedslot_run<TB, NF, true, false>), K(pedslot_run<TB, NF, false, true>), K(pedslot_run<TB, NF, false, false>)
+#define WHAMD_PSLOTX(TB, NF) D(pedslot_runx<TB, NF, 16, true>), D(pedslot_runx<TB, NF, 16, false>), D(pedslot_runx<TB, NF, 32, true>), D(pedslot_runx<TB, NF, 32, false>)
+#define WHAMD_RUNX(XC) K(slot_runx<2, XC, false, true>), K(slot_runx<2, XC, false, false>)
+#define WHAMD_RUN(LR, YF) K(slot_run<LR, false, true, YF>), K(slot_run<LR, false, false, YF>), D(slot_run<LR, true, true, YF>), D(slot_run<LR, true, false, YF>)
+	static const std::vector<whamd_debug_kernel> table = [] {
+		std::vector<whamd_debug_kernel> t = {
+			WHAMD_COLUMN(1, 1), WHAMD_COLUMN(1, 2), WHAMD_COLUMN(1, 3), WHAMD_COLUMN(1, 4), WHAMD_COLUMN(1, 5), WHAMD_COLUMN(1, 6),
+			WHAMD_COLUMN(4, 3), WHAMD_COLUMN(4, 4), WHAMD_COLUMN(4, 5), WHAMD_COLUMN(4, 6),
+			WHAMD_COLUMN(16, 4), WHAMD_COLUMN(16, 5), WHAMD_COLUMN(16, 6),
+			K(column_step_wide), K(column_finalize),
+			K(ped_tables), K(resident_tables),
+			K(resident_segment<false, false>), K(resident_segment<false, true>), D(resident_segment<true, true>),
+			K(resident_segment_ped<false>), K(resident_segment_ped<false, true>), D(resident_segment_ped<true>),
+			K(resident_batch<false>), K(resident_batch<true>),
+			WHAMD_RUN(1, false), WHAMD_RUN(2, false), WHAMD_RUN(2, true), WHAMD_RUN(3, false), WHAMD_RUN(3, true),
+			WHAMD_RUNX(0), WHAMD_RUNX(8), WHAMD_RUNX(16), WHAMD_RUNX(24), WHAMD_RUNX(32),
+			D(slot_runx<2, 24, true, true>), D(slot_runx<2, 24, true, false>), D(slot_runx<2, 32, true, true>), D(slot_runx<2, 32, true, false>),
+			K(slot_batch<1>), K(slot_batch<2>), K(slot_batch<3>),
+			WHAMD_PSLOT(2, 2), WHAMD_PSLOT(2, 4), WHAMD_PSLOT(4, 2), WHAMD_PSLOT(4, 4), WHAMD_PSLOT(2, 16), WHAMD_PSLOT(2, PSLOT_FACT), WHAMD_PSLOT(4, PSLOT_FACT4),
+			WHAMD_PSLOTX(2, 2), WHAMD_PSLOTX(2, 4), WHAMD_PSLOTX(4, 2), WHAMD_PSLOTX(4, 4), WHAMD_PSLOTX(2, 16), WHAMD_PSLOTX(2, PSLOT_FACT),
+			K(slot_group<2, false, false>), K(slot_group<2, false, true>), K(slot_group<3, false, false>), K(slot_group<3, false, true>), D(slot_group<2, true, false>),
+			K(slot_groupx<2, false>), K(slot_groupx<3, false>),
+			K(pedslot_group<2, 2>), K(pedslot_group<2, 4>), K(pedslot_group<4, 2>), K(pedslot_group<4, 4>), K(pedslot_group<2, 16>),
+			K(pedslot_group<2, PSLOT_FACT>), K(pedslot_group<4, PSLOT_FACT4>),
+			K(backtrace_kernel), K(backtrace_chunks), K(backtrace_gather), K(superreads_single),
+			K(backtrace_chunks_group), K(backtrace_gather_group), K(superreads_group),
+		};
+		size_t count = 0;
+		const void* const* opted = large_lds_kernels(count);   // (the very array opt_in_large_lds walks)
+		for (whamd_debug_kernel& k : t) k.large_lds_opted_in = std::find(opted, opted + count, k.kernel) != opted + count;
+		return t;
+	}();
+#undef K
+#undef D
+#undef WHAMD_COLUMN
+#undef WHAMD_PSLOT
+#undef WHAMD_PSLOTX
+#undef WHAMD_RUNX
+#undef WHAMD_RUN
+	return table;
+}
+
+}  // namespace
+
+size_t DeviceTable::debug_solve_kernels(whamd_debug_kernel* out, size_t capacity) {
+	const std::vector<whamd_debug_kernel>& t = solve_kernels();
+	for (size_t i = 0; out && i < t.size() && i < capacity; ++i) out[i] = t[i];
+	return t.size();
+}
+
+// The ledger of the last solve, every kernel resolved to its registry name (nullptr: not registered).
+size_t DeviceTable::debug_launches(whamd_debug_launch* out, size_t capacity) const {
+	const std::vector<whamd_debug_launch>& ledger = impl_->ledger;
+	for (size_t i = 0; out && i < ledger.size() && i < capacity; ++i) {
+		out[i] = ledger[i];
+		for (const whamd_debug_kernel& k : solve_kernels())
+			if (k.kernel == ledger[i].kernel) { out[i].name = k.name; break; }
+	}
+	return ledger.size();
+}
+
+// One launch into the ledger: a line that agrees in everything but the count takes it, else it opens a new line.
+void DeviceTable::Impl::note(uint32_t site, const void* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t on, bool forward, const LaunchFacts& facts) {
+	whamd_debug_launch rec = facts;
+	rec.kernel = kernel;
+	rec.site = site;
+	rec.grid_x = grid.x; rec.grid_y = grid.y; rec.block = block.x;
+	rec.lds = (uint32_t)lds;
+	rec.own_stream = on == stream ? 1u : 0u;
+	rec.forward = forward ? 1u : 0u;
+	rec.count = 0;
+	rec.name = nullptr;
+	for (whamd_debug_launch& have : ledger)
+		if (std::memcmp(&have, &rec, offsetof(whamd_debug_launch, count)) == 0) { have.count += 1; return; }
+	rec.count = 1;
+	ledger.push_back(rec);
+}
+#endif
+
 
 }  // namespace whamd
