@@ -586,6 +586,74 @@ void whamd_progeny_score_destroy(whamd_progeny_scores* s);
 whamd_status_t whamd_progeny_variant_types(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
                                            const uint32_t* nodes, uint64_t n_nodes, int device, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
 
+/* ---- Haplotagging (prepare_haplotag_information, whatshap/cli/haplotag.py:322-427) ------------------------------------------------------
+ * The assignment step of `whatshap haplotag`: every read -- or group of linked reads -- goes to the phase set and the haplotype its alleles
+ * support best.  One problem is one sample on one chromosome.  Strings stay with the caller: a read's representation (the key the
+ * reference marks as processed) and its BX tag arrive as dense integer ids.
+ * Grouping (host, in read order): a read whose representation was processed already is skipped; else it seeds a group, which, with
+ * linked_reads != 0 and a BX tag, also takes every read of the same tag whose representation is not yet processed and whose start lies
+ * within linked_read_cutoff of the seed's; all members are then processed.  Scoring (device, csrc/haplotag_device.hip): per phase set and
+ * haplotype the sum (int64) of the qualities of the entries whose allele equals the haplotype's; a phase set exists for a group once one of
+ * its entries matches a haplotype.  The winning phase set has the largest haplotype sum -- ties go to the one whose first matching entry
+ * comes first, in the order seed, then the other members in read-set order, each read's variants as listed --; in it the best haplotype
+ * is the lowest index among the maxima, quality = best - second best sum, and quality 0 leaves the group unassigned.  n_multiple_phase_sets
+ * counts the groups with more than one phase set, assigned or not.
+ * Errors (WHAMD_ERR_INVALID, nothing launched): ploidy outside 2 .. 16 (the reference raises IndexError at 1), an entry position that no
+ * variant has (KeyError there), an entry allele outside {0, 1} (its assertion), variant positions that repeat. */
+typedef struct whamd_haplotag_view {
+	uint32_t ploidy;
+	uint32_t linked_reads;              /* 0: --ignore-linked-read */
+	int64_t linked_read_cutoff;
+	uint64_t n_variants;
+	const int64_t* variant_position;    /* [n_variants] distinct */
+	const int64_t* variant_phaseset;    /* [n_variants] block_id */
+	const int8_t* variant_phasing;      /* [n_variants][ploidy] haplotype alleles; a value other than 0 or 1 matches nothing */
+	uint64_t n_reads;
+	const uint64_t* read_ptr;           /* [n_reads + 1] into the entry arrays */
+	const int64_t* entry_position;      /* [n_entries] */
+	const int8_t* entry_allele;         /* [n_entries] */
+	const int32_t* entry_quality;       /* [n_entries] */
+	const int64_t* read_start;          /* [n_reads] reference_start */
+	const uint32_t* read_repr;          /* [n_reads] dense id of the read's representation (equal ids: one representation) */
+	const uint32_t* read_bx;            /* [n_reads] dense id of the BX tag, 0xffffffff: none; NULL: no read has one */
+} whamd_haplotag_view;
+
+typedef struct whamd_haplotag_stats {
+	uint64_t n_reads;
+	uint64_t n_groups;                  /* groups formed (reads skipped as processed form none) */
+	uint64_t n_assigned;                /* groups that were assigned */
+	uint64_t n_multiple_phase_sets;
+	uint64_t n_entries;                 /* entries of all groups */
+	uint64_t groups_class_a;            /* groups of 1 .. 64 entries: eight lanes each */
+	uint64_t groups_class_b;            /* 65 .. 4096 entries: one wave each */
+	uint64_t groups_class_c;            /* more: one workgroup each */
+	uint64_t groups_many_phase_sets;    /* of them: more than 4 phase sets, one pass per phase set */
+	uint32_t launches;                  /* kernel launches of the whole call (0: nothing touched the device) */
+	double host_ms;                     /* wall, whole call: validation, grouping */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double total_ms;                    /* wall, whole call */
+} whamd_haplotag_stats;
+
+typedef struct whamd_haplotag_result whamd_haplotag_result; /* opaque: the result of one whamd_haplotag call */
+
+/* One call for a batch of problems (chromosomes x samples): one upload, at most three launches, one download. */
+whamd_status_t whamd_haplotag(const whamd_haplotag_view* problems, uint64_t n_problems, int device, whamd_haplotag_result** out);
+uint64_t whamd_haplotag_problem_count(const whamd_haplotag_result* r);
+/* Reads of problem m. */
+uint64_t whamd_haplotag_count(const whamd_haplotag_result* r, uint64_t m);
+/* Per read of problem m: the haplotype (-1: the read's representation got no assignment from its group, or the read formed none), the
+ * quality and the phase set; NULL skips. */
+whamd_status_t whamd_haplotag_get(const whamd_haplotag_result* r, uint64_t m, int32_t* haplotype_out, int64_t* quality_out, int64_t* phaseset_out);
+/* The assigned linked-read groups of problem m in processing order (what the reference appends to BX_tag_to_haplotype). */
+uint64_t whamd_haplotag_bx_count(const whamd_haplotag_result* r, uint64_t m);
+whamd_status_t whamd_haplotag_get_bx(const whamd_haplotag_result* r, uint64_t m, uint32_t* bx_out, int64_t* reference_start_out, int32_t* haplotype_out,
+                                     int64_t* phaseset_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_haplotag_get_stats(const whamd_haplotag_result* r, uint64_t m, whamd_haplotag_stats* stats_out);
+void whamd_haplotag_destroy(whamd_haplotag_result* r);
+
 #ifdef __cplusplus
 }
 #endif

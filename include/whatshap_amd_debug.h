@@ -86,6 +86,11 @@ whamd_status_t whamd_debug_progeny_pair_score_host(const float* gl, uint64_t n_p
 whamd_status_t whamd_debug_progeny_variant_types_host(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
                                                       const uint32_t* nodes, uint64_t n_nodes, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
 
+/* HOST-ONLY DIAGNOSTICS of haplotagging (csrc/haplotag.cpp): the same validation and grouping as whamd_haplotag, then every group scored on
+ * one CPU thread with the device's selection functions -- what the CPU test-suite holds to the recorded reference, identical in every
+ * field; never what the product calls.  Read with the whamd_haplotag_* getters of the debug library. */
+whamd_status_t whamd_debug_haplotag_host(const whamd_haplotag_view* problems, uint64_t n_problems, whamd_haplotag_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

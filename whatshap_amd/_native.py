@@ -187,6 +187,23 @@ class ProgenyScoreStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class HaplotagView(C.Structure):
+    _fields_ = [("ploidy", C.c_uint32), ("linked_reads", C.c_uint32), ("linked_read_cutoff", C.c_int64), ("n_variants", C.c_uint64),
+                ("variant_position", C.POINTER(C.c_int64)), ("variant_phaseset", C.POINTER(C.c_int64)), ("variant_phasing", C.POINTER(C.c_int8)),
+                ("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("entry_position", C.POINTER(C.c_int64)), ("entry_allele", C.POINTER(C.c_int8)),
+                ("entry_quality", C.POINTER(C.c_int32)), ("read_start", C.POINTER(C.c_int64)), ("read_repr", C.POINTER(C.c_uint32)),
+                ("read_bx", C.POINTER(C.c_uint32))]
+
+
+class HaplotagStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_groups", "n_assigned", "n_multiple_phase_sets", "n_entries", "groups_class_a", "groups_class_b",
+                                                "groups_class_c", "groups_many_phase_sets")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -345,6 +362,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_progeny_variant_types_host.restype = C.c_int
     L.whamd_debug_progeny_variant_types_host.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                                          C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_debug_haplotag_host.restype = C.c_int
+    L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
@@ -491,6 +510,22 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_progeny_variant_types.restype = C.c_int
     L.whamd_progeny_variant_types.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                               C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_haplotag.restype = C.c_int
+    L.whamd_haplotag.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_haplotag_problem_count.restype = C.c_uint64
+    L.whamd_haplotag_problem_count.argtypes = [C.c_void_p]
+    L.whamd_haplotag_count.restype = C.c_uint64
+    L.whamd_haplotag_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_haplotag_get.restype = C.c_int
+    L.whamd_haplotag_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.whamd_haplotag_bx_count.restype = C.c_uint64
+    L.whamd_haplotag_bx_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_haplotag_get_bx.restype = C.c_int
+    L.whamd_haplotag_get_bx.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.whamd_haplotag_get_stats.restype = C.c_int
+    L.whamd_haplotag_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(HaplotagStats)]
+    L.whamd_haplotag_destroy.restype = None
+    L.whamd_haplotag_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -515,6 +550,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_score_destroy", "whamd_poly_estimate_error_rate",
     "whamd_progeny_score", "whamd_progeny_score_problem_count", "whamd_progeny_score_count", "whamd_progeny_score_get", "whamd_progeny_score_get_stats",
     "whamd_progeny_score_destroy", "whamd_progeny_variant_types",
+    "whamd_haplotag", "whamd_haplotag_problem_count", "whamd_haplotag_count", "whamd_haplotag_get", "whamd_haplotag_bx_count", "whamd_haplotag_get_bx",
+    "whamd_haplotag_get_stats", "whamd_haplotag_destroy",
 ]
 
 
@@ -524,6 +561,15 @@ class SolverError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(message)
         self.status = status
+
+
+
+def raise_status(L, status: int):
+    """The library's last error as an exception: ValueError for invalid input (where the reference raises on the same input), else SolverError."""
+    msg = L.whamd_last_error().decode("utf-8", "replace")
+    if status == WHAMD_ERR_INVALID:
+        raise ValueError(msg)
+    raise SolverError(status, msg)
 
 
 def _check(status: int, L=None):
