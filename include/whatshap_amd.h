@@ -95,8 +95,11 @@ typedef struct whamd_solve_stats {
 	uint64_t n_cells;            /* sum_c 2^k_c (unique bipartitions) */
 	uint64_t n_costs;            /* n_cells * T */
 	uint64_t algorithmic_bytes;  /* sum_c 4*T*2^b_c + 12*T*2^f_c + 12*k_c   */
-	uint64_t forward_launches;   /* launches of the dominant (column-step) kernel */
-	double forward_ms;           /* HIP-event time of the forward pass (all column steps) */
+	uint64_t forward_launches;   /* launches of the dominant (column-step) kernel (a solve that continued behind the table's preview -- option "preview" -- counts the preview's too) */
+	double forward_ms;           /* HIP-event time of the forward pass (all column steps).  A solve that continued behind the table's preview: ONE interval, from the event
+	                              * in front of the preview's first launch (inside whamd_dptable_create) to the end of the forward pass -- it contains whatever time the device
+	                              * idled between the preview's last launch and the caller's enqueue, so it grows if the caller delays the enqueue; total_ms likewise.  A
+	                              * caller that reads these as kernel time passes "preview" = "0". */
 	double backtrace_ms;         /* HIP-event time of the device backtrace */
 	double total_ms;             /* HIP-event time forward + backtrace + path download */
 	double host_prepare_ms;      /* wall: flattening + descriptor build + upload (outside total_ms) */
@@ -239,7 +242,17 @@ whamd_status_t whamd_dptable_get_stats(const whamd_dptable* table, whamd_solve_s
  *   "symmetry"      single individual: D[~x] == D[x], so a run may compute half of its workgroups only: "0" never,
  *                   "1" runs that would fill the chip (default), "2" every run with a grid read (tests)
  *   "lanes"         how many connected components of a single-individual table advance side by side (default 32, their
- *                   runs go out as batched launches; "1" solves them one after the other) */
+ *                   runs go out as batched launches; "1" solves them one after the other)
+ *   "preview"       "auto" (default) | "0" | "1".  whamd_dptable_create of a single-individual table on slot runs may launch the table's leading
+ *                   runs itself, right behind the plan and from a small upload of their own, so that the device works while the rest of the table
+ *                   is built and uploaded; the first whamd_dptable_enqueue of the table, alone on its own stream and with no option changed since,
+ *                   continues behind them.  The finished schedule is compared with what was launched, run by run; where anything differs, and in
+ *                   every other case (whamd_dptable_enqueue_many with other tables, a second solve, an option set after the create), the solve
+ *                   starts at its first step as ever: the result never depends on the preview.  "auto": only a table of eight plan pieces (about
+ *                   65 000 columns) and more, one connected component, created without "host_threads" and "shared_launches" while no other
+ *                   table of the process holds resources on the device -- a caller with many tables in flight gains nothing from it.  "1": every
+ *                   table whose form allows it (tests).  Give it with whamd_dptable_create_with_options: the create is where it acts.
+ *   "preview_pieces"  how many plan pieces (of about 8 192 columns) the preview covers; "0" (default): a sixth of the table's. */
 whamd_status_t whamd_dptable_set_option(whamd_dptable* table, const char* key, const char* value);
 
 /*

@@ -135,11 +135,42 @@ typedef struct whamd_debug_launch {
 	int32_t T, n_ind, mode, wide;                               /* per-column steps */
 	int32_t ped, sym;                                           /* LDS-resident runs: sg.kind, the complement symmetry */
 	int32_t entries;                                            /* runs of a batched launch */
+	int32_t preview;        /* 1: the launch was made by whamd_dptable_create (the table's preview), 0: by the solve */
+	int32_t reserved;
 	uint64_t count;
 	const char* name;       /* the registry's name of `kernel`; NULL: the pointer is not registered (an error of the library) */
 } whamd_debug_launch;
 /* The ledger of the solve the table collected last (after whamd_dptable_wait): at most `capacity` lines to out[] (may be NULL), *n_out: how many there are. */
 whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_debug_launch* out, size_t capacity, size_t* n_out);
+
+/* THE PREVIEW of a table (options `preview`, `preview_pieces` of whatshap_amd.h): what became of it.
+ * ran: whamd_dptable_create launched the table's leading slot runs; pieces: the plan pieces they cover; launched_steps: how many super-steps;
+ * agreed_steps: S, the leading super-steps of the finished schedule that are launch for launch what was launched; continued: the solve in flight or
+ * collected last began behind the preview (only when S == launched_steps); why_not: "" when it ran, else a line that starts "no preview: ".
+ * WHAMD_PREVIEW_MISMATCH_AT=k (environment, this library only) makes the comparison report that step k differs. */
+typedef struct whamd_debug_preview {
+	int32_t ran, continued;
+	uint32_t pieces, launched_steps, agreed_steps, reserved;
+	const char* why_not;
+} whamd_debug_preview;
+whamd_status_t whamd_debug_dptable_preview(const whamd_dptable* table, whamd_debug_preview* out);
+
+/* HOST-ONLY check of what a preview works out ahead of the create (no device needed): the plan of a single-individual table as whamd_dptable_create makes it, the
+ * preview forced over `pieces` plan pieces (0: the library's rule), then the create's own host phases.  For the preview's steps k < steps (at most `capacity` are
+ * written; any array may be NULL): the record offset and the seed id the preview would launch step k with, and the ones the create's layout gives the same run.
+ * The scalars: what the preview predicts for the whole table beside what the create computes -- arena bytes, the seeds' count and stride, whether the backtrace is
+ * chunked, and the bytes of an exchange column (the preview's is a bound: at least the create's).  Free HBM is taken as 1 TiB. */
+typedef struct whamd_debug_preview_plan_result {
+	uint32_t n_pieces, pieces, steps, n_steps;   /* plan pieces of the table; pieces and leading steps of the preview (0 steps: none, see why_not); steps of the whole plan */
+	int32_t chunked_predicted, chunked, windowed, reserved;
+	uint32_t n_seeds_predicted, n_seeds, stride_predicted, stride;
+	uint64_t arena_predicted, arena_laid_out, exchange_predicted, exchange_laid_out;
+	const char* why_not;
+} whamd_debug_preview_plan_result;
+whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                        const whamd_pedigree_view* pedigree, int distrust_genotypes,
+                                        const uint32_t* positions, size_t n_positions, uint32_t pieces, whamd_debug_preview_plan_result* out,
+                                        uint64_t* rec_predicted, uint64_t* rec_laid_out, uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity);
 
 #ifdef __cplusplus
 }

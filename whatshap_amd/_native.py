@@ -368,6 +368,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
     L.whamd_debug_dptable_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.whamd_debug_dptable_preview.restype = C.c_int
+    L.whamd_debug_dptable_preview.argtypes = [C.c_void_p, C.POINTER(DebugPreview)]
     _debug_lib = L
     return L
 
@@ -752,7 +754,53 @@ LAUNCH_FACTS = ("lr", "yflags", "spec", "stamps", "tb", "nf", "ncols", "threads"
 class DebugLaunch(C.Structure):
     """whamd_debug_launch (include/whatshap_amd_debug.h)."""
     _fields_ = ([("kernel", C.c_void_p), ("site", C.c_uint32), ("grid_x", C.c_uint32), ("grid_y", C.c_uint32), ("block", C.c_uint32), ("lds", C.c_uint32),
-                 ("own_stream", C.c_uint32), ("forward", C.c_uint32)] + [(f, C.c_int32) for f in LAUNCH_FACTS] + [("count", C.c_uint64), ("name", C.c_char_p)])
+                 ("own_stream", C.c_uint32), ("forward", C.c_uint32)] + [(f, C.c_int32) for f in LAUNCH_FACTS] +
+                [("preview", C.c_int32), ("reserved", C.c_int32), ("count", C.c_uint64), ("name", C.c_char_p)])
+
+
+class DebugPreview(C.Structure):
+    """whamd_debug_preview (include/whatshap_amd_debug.h)."""
+    _fields_ = [("ran", C.c_int32), ("continued", C.c_int32), ("pieces", C.c_uint32), ("launched_steps", C.c_uint32), ("agreed_steps", C.c_uint32),
+                ("reserved", C.c_uint32), ("why_not", C.c_char_p)]
+
+
+def debug_preview(table) -> dict:
+    """whamd_debug_dptable_preview: what became of the preview of `table` (made by the debug library): ran, continued, pieces, launched_steps,
+    agreed_steps, why_not."""
+    D = debug_lib()
+    if table._L is not D:
+        raise ValueError("the preview's record exists in the debug library only (use_debug_library() before the table is made)")
+    out = DebugPreview()
+    _check(D.whamd_debug_dptable_preview(table._h, C.byref(out)), D)
+    return {"ran": bool(out.ran), "continued": bool(out.continued), "pieces": int(out.pieces), "launched_steps": int(out.launched_steps),
+            "agreed_steps": int(out.agreed_steps), "why_not": (out.why_not or b"").decode()}
+
+
+class DebugPreviewPlan(C.Structure):
+    """whamd_debug_preview_plan_result (include/whatshap_amd_debug.h)."""
+    _fields_ = [("n_pieces", C.c_uint32), ("pieces", C.c_uint32), ("steps", C.c_uint32), ("n_steps", C.c_uint32),
+                ("chunked_predicted", C.c_int32), ("chunked", C.c_int32), ("windowed", C.c_int32), ("reserved", C.c_int32),
+                ("n_seeds_predicted", C.c_uint32), ("n_seeds", C.c_uint32), ("stride_predicted", C.c_uint32), ("stride", C.c_uint32),
+                ("arena_predicted", C.c_uint64), ("arena_laid_out", C.c_uint64), ("exchange_predicted", C.c_uint64), ("exchange_laid_out", C.c_uint64),
+                ("why_not", C.c_char_p)]
+
+
+def debug_preview_plan(problem: ProblemArrays, pieces: int = 0) -> dict:
+    """whamd_debug_preview_plan (host only): what a preview over `pieces` plan pieces works out ahead of the create -- per leading step the record offset and
+    the seed id -- beside what the create's own layout gives (rec_predicted / rec_laid_out / spec_predicted / spec_laid_out), and the scalars of the struct."""
+    D = debug_lib()
+    fn = D.whamd_debug_preview_plan
+    fn.restype = C.c_int
+    out = DebugPreviewPlan()
+    _check(fn(*problem.call_args(), C.c_uint32(pieces), C.byref(out), None, None, None, None, C.c_size_t(0)), D)
+    n = int(out.steps)
+    arrays = {"rec_predicted": np.zeros(max(n, 1), dtype=np.uint64), "rec_laid_out": np.zeros(max(n, 1), dtype=np.uint64),
+              "spec_predicted": np.zeros(max(n, 1), dtype=np.uint32), "spec_laid_out": np.zeros(max(n, 1), dtype=np.uint32)}
+    _check(fn(*problem.call_args(), C.c_uint32(pieces), C.byref(out), _ptr(arrays["rec_predicted"], C.c_uint64), _ptr(arrays["rec_laid_out"], C.c_uint64),
+              _ptr(arrays["spec_predicted"], C.c_uint32), _ptr(arrays["spec_laid_out"], C.c_uint32), C.c_size_t(n)), D)
+    rec = {name: (getattr(out, name).decode() if name == "why_not" else int(getattr(out, name))) for name, _ in DebugPreviewPlan._fields_ if name != "reserved"}
+    rec.update({k: v[:n] for k, v in arrays.items()})
+    return rec
 
 
 def debug_solve_kernels() -> list:
@@ -766,7 +814,8 @@ def debug_solve_kernels() -> list:
 
 def debug_launches(table) -> list:
     """whamd_debug_dptable_launches: the launch ledger of the solve `table` (made by the debug library) collected last.  One dict per distinct
-    launch: name (of the registry), site (LAUNCH_SITES), grid_x, grid_y, block, lds, own_stream, forward, count and the facts the choice was made
+    launch: name (of the registry), site (LAUNCH_SITES), grid_x, grid_y, block, lds, own_stream, forward, count, preview (the launch was made by the
+    create: the table's preview) and the facts the choice was made
     from (LAUNCH_FACTS; None where the launch site does not have the fact).  A kernel the registry does not know is an error."""
     D = debug_lib()
     if table._L is not D:
@@ -780,7 +829,7 @@ def debug_launches(table) -> list:
         if r.name is None:
             raise RuntimeError(f"a launch of site {LAUNCH_SITES[r.site]} (grid {r.grid_x} x {r.grid_y}, block {r.block}) took a kernel the registry does not list")
         rec = {"name": r.name.decode(), "site": LAUNCH_SITES[r.site], "grid_x": r.grid_x, "grid_y": r.grid_y, "block": r.block, "lds": r.lds,
-               "own_stream": bool(r.own_stream), "forward": bool(r.forward), "count": int(r.count)}
+               "own_stream": bool(r.own_stream), "forward": bool(r.forward), "count": int(r.count), "preview": bool(r.preview)}
         rec.update({f: (None if getattr(r, f) < 0 else getattr(r, f)) for f in LAUNCH_FACTS})
         out.append(rec)
     return out

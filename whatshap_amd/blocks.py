@@ -161,12 +161,12 @@ def solve_blocks(problems: Sequence[ProblemArrays], device: int = 0, path=None, 
         n_workers = max(1, min(create_threads, max_in_flight))
         with _create_pool(n_workers) as pool:
             def options_of(window):
-                opts = {}
+                opts = {"preview": "0"}   # many tables in flight: a create does not start its own table's forward pass (whatshap_amd.h, option "preview")
                 if len(window) > 4:       # more than four tables per window share their launches: the library picks the layout for that
                     opts["shared_launches"] = "1"
                 if n_workers > 1 and len(window) > 1:   # several creates at once: each keeps to a few threads of its own (32 each would fight)
                     opts["host_threads"] = str(max(1, int(host_threads_per_create)))
-                return opts or None
+                return opts
 
             def create(sub, opts):
                 return NativeTable(sub, device=device, path=path, solve=False, options=opts)

@@ -112,12 +112,13 @@ whamd_status_t create_table(const whamd_readset_view* readset, const uint32_t* r
 	if (st != WHAMD_OK) return fail(st, msg);
 	const double t1 = now_ms();
 	t->device_index = device;
+	t->device.set_thread_budget(whamd::host_threads_override() != 0);   // (a caller that caps a create's threads runs many tables: no preview)
 	for (size_t i = 0; i < n_options; ++i) {   // before the (one) upload: the plan is made for them
 		if (std::string(keys[i]) == "host_threads") continue;
 		st = apply_option(t.get(), keys[i], values[i]);
 		if (st != WHAMD_OK) return st;
 	}
-	st = t->device.upload(t->problem, device, msg);
+	st = t->device.upload(t->problem, device, msg, /*from_create=*/true);
 	if (st != WHAMD_OK) return fail(st, msg);
 	if (getenv("WHAMD_DEBUG_TIMING"))
 		fprintf(stderr, "[whamd timing] create: flatten %.1f ms, plan + upload %.1f ms\n", t1 - t0, now_ms() - t1);
@@ -482,6 +483,17 @@ whamd_status_t apply_option(whamd_dptable* t, const std::string& k, const char* 
 		t->uploaded = false;
 		return WHAMD_OK;
 	}
+	if (k == "preview") {
+		if (v != "auto" && v != "0" && v != "1") return fail(WHAMD_ERR_INVALID, "option preview: auto, 0 or 1 expected, got '" + v + "'");
+		t->device.set_preview(v == "auto" ? -1 : std::atoi(value));
+		t->uploaded = false;
+		return WHAMD_OK;
+	}
+	if (k == "preview_pieces") {
+		t->device.set_preview_pieces((uint32_t)std::max(0, std::atoi(value)));
+		t->uploaded = false;
+		return WHAMD_OK;
+	}
 	if (k == "arena_limit_bytes") {
 		t->device.set_arena_limit(std::strtoull(value, nullptr, 10));
 		t->uploaded = false;
@@ -796,6 +808,27 @@ whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_de
 	if (!table->solved) return fail(WHAMD_ERR_INVALID, "the table has not been solved: its ledger is read after whamd_dptable_wait");
 	*n_out = table->device.debug_launches(out, capacity);
 	return WHAMD_OK;
+}
+
+whamd_status_t whamd_debug_dptable_preview(const whamd_dptable* table, whamd_debug_preview* out) {
+	if (!table || !out) return fail(WHAMD_ERR_INVALID, "null argument");
+	table->device.debug_preview(out);
+	return WHAMD_OK;
+}
+
+whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                        const whamd_pedigree_view* pedigree, int distrust_genotypes,
+                                        const uint32_t* positions, size_t n_positions, uint32_t pieces, whamd_debug_preview_plan_result* out,
+                                        uint64_t* rec_predicted, uint64_t* rec_laid_out, uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity) {
+	return guarded([&]() -> whamd_status_t {
+	if (!out) return fail(WHAMD_ERR_INVALID, "out is NULL");
+	Problem p;
+	std::string msg;
+	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, p, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	st = DeviceTable::debug_preview_plan(p, pieces, out, rec_predicted, rec_laid_out, spec_predicted, spec_laid_out, capacity, msg);
+	return st == WHAMD_OK ? WHAMD_OK : fail(st, msg);
+	});
 }
 #endif   // WHAMD_DEBUG_BUILD
 

@@ -21,7 +21,8 @@ public:
 	static bool device_pci_bus_id(int device, std::string& out);   // "0000:c5:00.0"; false if there is no such device
 	// Builds the per-column descriptors for `p` and uploads everything the kernels read.
 	// (`p` is not const: a table with lazy generic terms -- Problem::lazy_terms -- gets the term lists of the columns its plan leaves outside runs here)
-	whamd_status_t upload(Problem& p, int device, std::string& msg);
+	// from_create: the call is whamd_dptable_create's own upload -- the only one that may start a preview (set_preview).
+	whamd_status_t upload(Problem& p, int device, std::string& msg, bool from_create = false);
 	// Forward pass + backtrace on the device; fills s.path_*, s.optimal_score and the timing fields of st.
 	whamd_status_t solve(const Problem& p, Solution& s, whamd_solve_stats& st, std::string& msg);
 	// The two halves of solve(): enqueue() only submits the launches to the table's stream (several tables can be in
@@ -66,6 +67,12 @@ public:
 	// The table will be solved together with many others (whamd_dptable_enqueue_many): a wide single-individual table then plans eight cells
 	// per thread and twelve local slots (half the wavefronts per table); next upload().
 	void set_shared_launches(bool v);
+	// The preview: a lone single-individual table's leading slot runs are launched from inside the create and the first enqueue continues behind them
+	// (dp_device.hip start_preview).  mode -1 auto (the default: only a table that is alone on its device, of eight plan pieces and more, created
+	// without a thread budget), 0 never, 1 wherever the table's form allows it; pieces: plan pieces it covers (0: a sixth of them); next upload().
+	void set_preview(int mode);
+	void set_preview_pieces(uint32_t pieces);
+	void set_thread_budget(bool v);   // the create is held to a thread budget (option host_threads): a caller that runs many tables at once
 	// the table's launches will run BESIDE other tables' on the same device (own streams, whamd_dptable_enqueue_many): kernels that leave room on a CU
 	void set_side_by_side(bool v);
 
@@ -73,6 +80,9 @@ public:
 	// The launch ledger of the debug library (include/whatshap_amd_debug.h): the registry of the solve's kernels, and the launches of the solve wait() collected last.
 	static size_t debug_solve_kernels(whamd_debug_kernel* out, size_t capacity);
 	size_t debug_launches(whamd_debug_launch* out, size_t capacity) const;
+	void debug_preview(whamd_debug_preview* out) const;
+	static whamd_status_t debug_preview_plan(Problem& p, uint32_t pieces, whamd_debug_preview_plan_result* out, uint64_t* rec_predicted, uint64_t* rec_laid_out,
+	                                         uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity, std::string& msg);
 #endif
 
 private:

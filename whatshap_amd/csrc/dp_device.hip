@@ -403,12 +403,13 @@ struct DeviceTable::Impl {
 	size_t upload_bound(const Problem& p, const TableBuild& b) const;
 	whamd_status_t upload_column_arrays(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
 	void build_slot_blobs(TableBuild& b) const;
-	uint64_t lay_out_slot_tables(const TableBuild& b);
+	uint64_t lay_out_slot_tables(const TableBuild& b, bool report = true);
 	whamd_status_t upload_slot_arrays(TableBuild& b, TableUploader& up, std::string& msg);
 	void make_jobs();
 	void make_units(const TableBuild& b);
 	whamd_status_t make_windows(const TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t take_result_block(uint32_t n, TableUploader& up, std::string& msg);
+	void cut_chunks(const Problem& p);
 	whamd_status_t make_chunks(const Problem& p, TableUploader& up, std::string& msg);
 	whamd_status_t take_solve_buffers(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t make_lanes(const TableBuild& b, TableUploader& up, std::string& msg);
@@ -446,8 +447,8 @@ struct DeviceTable::Impl {
 	struct GroupSubmission;
 	void launch_column_step(const Problem& p, const Step& step, const Lane& lane, const uint32_t* prev, uint32_t* cur, uint64_t& launches);
 	void launch_run(const ResBatchEntry& e, uint64_t& launches);
-	void launch_slot_run(const SlotBatchEntry& e, uint64_t& launches);
-	whamd_status_t begin_solve(const Problem& p, Solution& s, std::string& msg);
+	void launch_slot_run(const DevProblem& dp, const SlotBatchEntry& e, uint64_t& launches);
+	whamd_status_t begin_solve(const Problem& p, Solution& s, std::string& msg, bool behind_preview = false);
 	whamd_status_t submit_super_step(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg);
 	whamd_status_t submit_singles(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg);
 	whamd_status_t submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream = nullptr, bool walked_by_group = false);
@@ -463,6 +464,51 @@ struct DeviceTable::Impl {
 	                                    // solve and tail are on the lead's stream, its uploads on an upload stream -- release() then has nothing to wait for there)
 	bool upload_pending = false;        // the uploads went through a shared upload stream and no solve has been ordered behind `ev_upload` yet
 	hipStream_t upload_stream = nullptr;
+
+	// The preview (DESIGN.md 6.1 "preview"): the leading slot runs of a lone table's forward pass, launched on `stream` from INSIDE the create -- from arrays of
+	// their own, uploaded first -- so that the device works while the host builds and uploads the whole table.  The finished schedule is then held against what
+	// was launched (verify_preview); the first enqueue continues behind the preview where every step agrees, and starts at step 0 as ever where not.
+	enum PreviewWhy : uint32_t { PV_RAN = 0, PV_OFF, PV_NOT_CREATE, PV_NOT_SLOTS, PV_DEBUG_SWITCH, PV_SHARED, PV_THREAD_BUDGET, PV_COMPONENTS, PV_FEW_PIECES, PV_NOT_ALONE, PV_NO_LEADING_RUNS,
+	                           PV_ROW_PAD, PV_ARENA, PV_WHYS };
+	struct Preview {
+		int mode = -1;                      // option preview: -1 auto, 0 never, 1 wherever the table's form allows it
+		uint32_t pieces_wanted = 0;         // option preview_pieces (0: the library's rule)
+		bool thread_budget = false;         // the create is held to a thread budget (option host_threads)
+		bool counted = false;               // this table is counted in tables_on_device
+		uint32_t why = PV_NOT_CREATE;       // PV_RAN, or why there was none
+		uint32_t pieces = 0;                // plan pieces the preview covered
+		uint32_t launched = 0;              // super-steps launched
+		uint32_t agreed = 0;                // S: leading super-steps of the finished schedule that are launch for launch what was launched (verify_preview)
+		bool launching = false;             // start_preview is submitting its launches
+		bool pending = false;               // launched, and no solve has been opened since
+		bool continued = false;             // the solve in flight / collected last began behind the preview
+		bool use_chunks = false;            // what the launches were chosen with
+		uint64_t launches = 0;              // forward launches of the preview
+		std::vector<SlotRun> runs;          // what every launched step was given by value
+		DevProblem dp{};                    // ... and as its problem: the preview's own rows, control words and tables; the TABLE's arena, exchange columns and seeds
+		uint32_t* d_pr[2] = {nullptr, nullptr};   // taken for the table before the launches (in the table's `allocations`); take_solve_buffers / make_chunks adopt them
+		size_t exchange_bytes = 0;
+		unsigned long long* spec_keys = nullptr;
+		size_t spec_bytes = 0;
+		std::vector<std::pair<void*, size_t>> allocations;   // the preview's own device block: given back by wait and release
+	} preview;
+	static inline std::atomic<int> tables_on_device[64];   // tables of the process that hold device resources, per device (open / release_device)
+	void give_preview_block() {   // (the caller knows the preview's launches are done)
+		for (auto& a : preview.allocations) devpool_give(device, a.first, a.second);
+		preview.allocations.clear();
+	}
+	struct PreviewPlan {   // plan_preview's answer
+		uint32_t why = PV_NOT_CREATE, pieces = 0, steps = 0, end_col = 0, n_spec = 0, stride = 64, max_f = 0;
+		bool chunked = false;
+		uint64_t arena = 0, tab_words = 0;   // bytes of the arena (all steps), words of the preview's table block
+		size_t ctrl_words = 0;
+		std::vector<uint64_t> rec;           // [steps] record offsets
+		std::vector<uint32_t> spec;          // [steps] seed ids
+	};
+	void plan_preview(const Problem& p, const TableBuild& b, bool from_create, PreviewPlan& out);
+	whamd_status_t start_preview(const Problem& p, TableBuild& b, bool from_create, std::string& msg);
+	void verify_preview();
+	whamd_status_t arm_keys(std::string& msg);
 
 	// the pooled stream and events (device_runtime.h), taken on the first create and given back by release_device
 	void adopt(const StreamSet& ss) { stream = ss.stream; ev0 = ss.ev[0]; ev1 = ss.ev[1]; ev2 = ss.ev[2]; ev3 = ss.ev[3]; ev_group = ss.ev[4]; ev_upload = ss.ev[5]; }
@@ -492,6 +538,12 @@ struct DeviceTable::Impl {
 		if (stream && own_stream_used && (!allocations.empty() || d_arena)) { (void)hipStreamSynchronize(stream); own_stream_used = false; }   // (hipFree used to wait for the table's last kernels)
 		for (auto& a : allocations) devpool_give(device, a.first, a.second);
 		allocations.clear();
+		give_preview_block();   // (its launches were on `stream`: synchronised above)
+		if (preview.why != PV_NOT_CREATE) {   // (a table that never got as far as start_preview has nothing to reset; the options and the count outlive a release)
+			Preview fresh;
+			fresh.mode = preview.mode; fresh.pieces_wanted = preview.pieces_wanted; fresh.thread_budget = preview.thread_budget; fresh.counted = preview.counted;
+			preview = std::move(fresh);
+		}
 		arena_give(device, d_arena, arena_bytes);
 		d_arena = nullptr;
 		arena_bytes = 0;
@@ -523,6 +575,8 @@ void DeviceTable::release_device() {
 		streamset_give(m.stream_set());
 	}
 	m.adopt(StreamSet());
+	if (m.preview.counted && m.device >= 0 && m.device < 64) Impl::tables_on_device[m.device].fetch_sub(1);
+	m.preview.counted = false;
 	m.inflight.run_stream = nullptr;
 	m.inflight.timing_pending = false;
 }
@@ -574,6 +628,9 @@ void DeviceTable::set_slot_lr(int lr) { impl_->slot_lr = lr >= 3 ? 3 : (lr <= 1 
 void DeviceTable::set_arena_limit(uint64_t bytes) { impl_->arena_limit = bytes; }
 void DeviceTable::set_shared_launches(bool v) { impl_->shared_hint = v; }
 void DeviceTable::set_side_by_side(bool v) { impl_->side_by_side = v; }
+void DeviceTable::set_preview(int mode) { impl_->preview.mode = mode < 0 ? -1 : (mode ? 1 : 0); }
+void DeviceTable::set_preview_pieces(uint32_t pieces) { impl_->preview.pieces_wanted = pieces; }
+void DeviceTable::set_thread_budget(bool v) { impl_->preview.thread_budget = v; }
 void DeviceTable::set_symmetry(int level) { impl_->symmetry = level < 0 ? 0 : (level > 2 ? 2 : level); }
 
 // ================================================================================================ create: the phases of DeviceTable::upload
@@ -592,6 +649,7 @@ whamd_status_t DeviceTable::Impl::open(int dev, std::string& msg) {
 		m.adopt(ss);
 	}
 	m.release();
+	if (!m.preview.counted && dev >= 0 && dev < 64) { Impl::tables_on_device[dev].fetch_add(1); m.preview.counted = true; }
 	return WHAMD_OK;
 }
 
@@ -715,6 +773,23 @@ whamd_status_t DeviceTable::Impl::describe_columns(const Problem& p, TableBuild&
 	return WHAMD_OK;
 }
 
+// The path a per-column step takes (0 fused, 1 keys) and the bytes of its backtrace record, from the column's sizes alone (lay_out_arena; the preview's arena bound).
+static uint32_t column_step_mode(bool force_keys, bool is_last, uint32_t f, uint32_t ebits) { return (!force_keys && !is_last && f >= 6 && ebits <= (uint32_t)QMAX) ? 0u : 1u; }
+static uint64_t column_record_bytes(uint32_t mode, uint32_t T, uint32_t f, uint32_t nplanes) {
+	return mode == 0 ? (uint64_t)nplanes * T * (1ull << (f - 6)) * 8ull : (uint64_t)T * (1ull << f) * 4ull;
+}
+// What the backtrace arena may take: free HBM minus the descriptors (~1 KiB per column), exchange buffers, tables and slack; at most the option arena_limit_bytes.
+static uint64_t arena_capacity(uint64_t free_b, uint32_t n, uint64_t table_bytes, uint64_t arena_limit) {
+	const uint64_t reserve = (3ull << 30) + (uint64_t)n * 1024ull + table_bytes;
+	uint64_t cap = free_b > reserve ? free_b - reserve : 0;
+	if (arena_limit) cap = std::min<uint64_t>(cap, arena_limit);
+	return cap;
+}
+// Where the next record starts behind one of `bytes` at `bt` (records are 16-byte aligned).
+static uint64_t arena_behind(uint64_t bt, uint64_t bytes) { return (bt + bytes + 15ull) & ~15ull; }
+// The record of one single-individual slot run: only launched workgroups write.
+static uint64_t slot_run_record_bytes(const SlotRun& run) { return (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half)); }
+
 // The offsets that run through the table, in column order: segment lists (b.segs), the place of every backtrace unit's record in the arena (DevColumn::bt_off, the
 // runs' rec / bt words), the windows where the arena is smaller than the records (b.window_first_col).  Produces b.arena_cap, b.bt, b.max_f, b.max_keys_f,
 // b.exchange_bytes; fails if a unit or the whole does not fit.  Host only.
@@ -726,15 +801,12 @@ whamd_status_t DeviceTable::Impl::lay_out_arena(const Problem& p, TableBuild& b,
 	uint64_t bt = 0, seg_bt = 0;
 	size_t seg_cursor = 0, slot_cursor = 0;
 	uint32_t max_f = 0, max_keys_f = 0;
-	// what the arena may take: free HBM minus the descriptors (~1 KiB per column), exchange buffers, tables and slack
-	const uint64_t reserve = (3ull << 30) + (uint64_t)n * 1024ull + m.table_bytes;
 	auto slot_record_bytes = [&m, ped_slots](size_t ri) -> uint64_t {   // record of one slot run: only launched workgroups write
 		const SlotRun& run = m.splan.runs[ri];
 		if (ped_slots) return (uint64_t)m.splan.pextra[ri].rec_words * 4ull << run.g;
-		return (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half));
+		return slot_run_record_bytes(run);
 	};
-	uint64_t arena_cap = b.free_b > reserve ? b.free_b - reserve : 0;
-	if (m.arena_limit) arena_cap = std::min<uint64_t>(arena_cap, m.arena_limit);
+	const uint64_t arena_cap = arena_capacity(b.free_b, n, m.table_bytes, m.arena_limit);
 	b.arena_cap = arena_cap;
 	std::vector<uint32_t>& window_first_col = b.window_first_col;
 	uint64_t bt_max = 0;
@@ -790,9 +862,8 @@ whamd_status_t DeviceTable::Impl::lay_out_arena(const Problem& p, TableBuild& b,
 			}
 			d.bt_off = seg_bt;
 		} else {
-			const bool fused_ok = !b.force_keys && !d.is_last && d.f >= 6 && d.ebits <= (uint32_t)QMAX;
-			d.mode = fused_ok ? 0u : 1u;
-			const uint64_t bytes = d.mode == 0 ? (uint64_t)d.nplanes * p.T * (1ull << (d.f - 6)) * 8ull : (uint64_t)p.T * (1ull << d.f) * 4ull;
+			d.mode = column_step_mode(b.force_keys, d.is_last, d.f, d.ebits);
+			const uint64_t bytes = column_record_bytes(d.mode, p.T, d.f, d.nplanes);
 			if (!open_unit(c, bytes)) return unit_too_large(c);
 			d.bt_off = bt;
 			bt += bytes;
@@ -919,8 +990,8 @@ void DeviceTable::Impl::build_slot_blobs(TableBuild& b) const {
 }
 
 // Single-individual slot runs: where the prologue's tables of every run (SlotRun::tab_g / tab_w / tab_sl, an X run's tab_kr / tab_par) lie in the table block that
-// slot_tables fills; marks the X runs.  Returns the block's size in words.  Host only.
-uint64_t DeviceTable::Impl::lay_out_slot_tables(const TableBuild& b) {
+// slot_tables fills; marks the X runs.  Returns the block's size in words.  Host only, and the same on every call (the preview lays the tables out before the create does).
+uint64_t DeviceTable::Impl::lay_out_slot_tables(const TableBuild& b, bool report) {
 	Impl& m = *this;
 	uint64_t slot_tab_words = 0;
 	for (SlotRun& run : m.splan.runs) {
@@ -946,7 +1017,7 @@ uint64_t DeviceTable::Impl::lay_out_slot_tables(const TableBuild& b) {
 		}
 	}
 	slot_tab_words += (uint64_t)SLOT_XCOLS * 64u;   // (an X run requests the lane parts of SLOT_XCOLS columns whatever its length)
-	if (b.laps.on) {
+	if (b.laps.on && report) {
 		size_t nx = 0, not_y = 0, not_lr = 0, long_run = 0, many_ends = 0;
 		for (const SlotRun& run : m.splan.runs) {
 			nx += (run.yflags & 8u) != 0;
@@ -1186,55 +1257,86 @@ struct OrientationGenerators {
 
 }  // namespace
 
-// Chunks of the speculative backtrace: a new chunk starts at every BT_CHUNK_RUNS-th run (single job only); the run that leaves a chunk's seed gets its spec id.
-// Produces m.use_chunks, m.chunks, the walk's buffers and m.dp.spec_keys / spec_stride (the schedule's entries carry them).
-whamd_status_t DeviceTable::Impl::make_chunks(const Problem& p, TableUploader& up, std::string& msg) {
+namespace {
+// The chunk rule of the speculative backtrace over a job's units, newest first (unit u is the job's step size - 1 - u): a run that finds BT_CHUNK_RUNS runs in the
+// chunk in front of it starts a new chunk and leaves that chunk's seed.  starts(u, id) is called for every such unit, id = 1, 2, ...; returns how many there are.
+// (make_chunks walks the units with it, the preview the plan's steps: one rule.)
+template <class IsRun, class Starts>
+uint32_t cut_chunk_starts(size_t n_units, IsRun is_run, Starts starts) {
+	uint32_t n_spec = 0, runs_in_chunk = 0;
+	for (size_t u = 0; u < n_units; ++u) {
+		const bool run = is_run(u);
+		if (run && runs_in_chunk >= (uint32_t)BT_CHUNK_RUNS && u > 0) {
+			starts(u, ++n_spec);
+			runs_in_chunk = 0;
+		}
+		runs_in_chunk += run;
+	}
+	return n_spec;
+}
+// Whether a table walks back in chunks at all: runs (slot runs, or the LDS-resident trio runs), one job, not windowed, more than two chunks' worth of units.
+bool backtrace_is_chunked(bool on_runs, size_t n_jobs, bool windowed, size_t n_units) {
+	return on_runs && n_jobs == 1 && !windowed && !getenv("WHAMD_BT_SEQUENTIAL") && n_units > 2u * BT_CHUNK_RUNS;
+}
+// The seeds' stride: the most waves any run that leaves a seed has (at least 64 words).
+uint32_t seed_stride_of(uint32_t stride, const SlotRun& run) { return std::max(stride, (run.threads >> 6) << (run.g - run.half)); }
+}  // namespace
+
+// Chunks of the speculative backtrace (single job only); the run that leaves a chunk's seed gets its spec id.  Host only.
+// Produces m.use_chunks, m.chunks, m.n_spec, m.n_orient_max and m.dp.spec_stride.
+void DeviceTable::Impl::cut_chunks(const Problem& p) {
 	Impl& m = *this;
-	const uint32_t n = p.n_cols;
 	m.use_chunks = false;
 	m.chunks.clear();
 	m.n_spec = 0;
 	for (SlotRun& run : m.splan.runs) run.spec_id = 0;
 	const bool trio_runs = !m.use_slots && !m.plan.ped_columns.empty();   // LDS-resident trio runs (kernels_trio.h)
 	if (trio_runs) for (ResSegment& sgm : m.plan.segments) sgm.in_mirror_bit = 0;   // (trio runs have no mirror: the field carries the spec id)
-	m.dp.spec_keys = nullptr;
-	if (!((m.use_slots || trio_runs) && m.jobs.size() == 1 && !m.windowed && !getenv("WHAMD_BT_SEQUENTIAL") && m.units.size() > 2u * BT_CHUNK_RUNS)) return WHAMD_OK;
+	if (!backtrace_is_chunked(m.use_slots || trio_runs, m.jobs.size(), m.windowed, m.units.size())) return;
 	m.use_chunks = true;
 	const OrientationGenerators generators(p);
-	BtChunk cur{};
-	cur.n_orient = 1;   // the newest chunk starts from the table's optimum
-	uint32_t runs_in_chunk = 0;
-	for (uint32_t u = 0; u < m.units.size(); ++u) {
-		const bool is_run = m.units[u].kind == 2 || m.units[u].kind == 3 || (trio_runs && m.units[u].kind == 1);
-		if (is_run && runs_in_chunk >= (uint32_t)BT_CHUNK_RUNS && u > 0) {
-			m.chunks.push_back(cur);
-			cur = BtChunk{};
-			cur.unit_off = u;
-			cur.spec_id = ++m.n_spec;
+	BtChunk first{};
+	first.n_orient = 1;   // the newest chunk starts from the table's optimum
+	m.chunks.push_back(first);
+	m.n_spec = cut_chunk_starts(m.units.size(),
+		[&m, trio_runs](size_t u) { return m.units[u].kind == 2 || m.units[u].kind == 3 || (trio_runs && m.units[u].kind == 1); },
+		[&m, &p, &generators, trio_runs](size_t u, uint32_t id) {
+			m.chunks.back().unit_count = (uint32_t)u - m.chunks.back().unit_off;
+			BtChunk cur{};
+			cur.unit_off = (uint32_t)u;
+			cur.spec_id = id;
 			generators.orient(p, m.units[u].c0 + m.units[u].ncols - 1, cur);   // (the last column of unit u's step)
-			runs_in_chunk = 0;
+			m.chunks.push_back(cur);
 			// the run of unit u leaves the seed: units are the job's steps in reverse order
 			const Step& st = m.plan.steps[m.jobs[0].steps[m.jobs[0].steps.size() - 1 - u]];
-			if (trio_runs) m.plan.segments[st.index].in_mirror_bit = m.n_spec;
-			else m.splan.runs[st.index].spec_id = m.n_spec;
-		}
-		runs_in_chunk += is_run;
-		++cur.unit_count;
-	}
-	m.chunks.push_back(cur);
-	HIP_TRY(up.up((void**)&m.d_chunks, m.chunks.data(), m.chunks.size() * sizeof(BtChunk)));
+			if (trio_runs) m.plan.segments[st.index].in_mirror_bit = id;
+			else m.splan.runs[st.index].spec_id = id;
+		});
+	m.chunks.back().unit_count = (uint32_t)m.units.size() - m.chunks.back().unit_off;
 	m.n_orient_max = 1;
 	for (const BtChunk& ch : m.chunks) m.n_orient_max = std::max(m.n_orient_max, ch.n_orient);
+	uint32_t stride = 64;
+	for (const SlotRun& run : m.splan.runs) if (run.spec_id) stride = seed_stride_of(stride, run);
+	if (trio_runs) for (const ResSegment& sgm : m.plan.segments) if (sgm.in_mirror_bit) stride = std::max(stride, (sgm.threads >> 6) << sgm.g);
+	m.dp.spec_stride = stride;
+}
+
+// The chunks (cut_chunks), their device copy, the walk's buffers and m.dp.spec_keys (the schedule's entries carry it and the stride).
+whamd_status_t DeviceTable::Impl::make_chunks(const Problem& p, TableUploader& up, std::string& msg) {
+	Impl& m = *this;
+	const uint32_t n = p.n_cols;
+	m.dp.spec_keys = nullptr;
+	m.cut_chunks(p);
+	if (!m.use_chunks) return WHAMD_OK;
+	const uint32_t stride = m.dp.spec_stride;
+	HIP_TRY(up.up((void**)&m.d_chunks, m.chunks.data(), m.chunks.size() * sizeof(BtChunk)));
 	HIP_TRY(up.alloc((void**)&m.d_unit_x, (size_t)m.n_orient_max * m.units.size() * 4));
 	HIP_TRY(up.alloc((void**)&m.d_path2, (size_t)m.n_orient_max * n * 4));
 	HIP_TRY(up.alloc((void**)&m.d_trans2, (size_t)m.n_orient_max * n * 4));
 	HIP_TRY(up.alloc((void**)&m.d_sel, m.units.size() + 16));
 	HIP_TRY(up.alloc((void**)&m.d_guess, m.chunks.size() * 4));
-	uint32_t stride = 64;
-	for (const SlotRun& run : m.splan.runs) if (run.spec_id) stride = std::max(stride, (run.threads >> 6) << (run.g - run.half));
-	if (trio_runs) for (const ResSegment& sgm : m.plan.segments) if (sgm.in_mirror_bit) stride = std::max(stride, (sgm.threads >> 6) << sgm.g);
-	m.dp.spec_stride = stride;
-	HIP_TRY(up.alloc((void**)&m.dp.spec_keys, ((size_t)m.n_spec + 1) * stride * 8));
+	if (m.preview.spec_keys && m.preview.spec_bytes >= ((size_t)m.n_spec + 1) * stride * 8) m.dp.spec_keys = m.preview.spec_keys;   // (armed, and being written by the preview's launches)
+	else HIP_TRY(up.alloc((void**)&m.dp.spec_keys, ((size_t)m.n_spec + 1) * stride * 8));
 	return WHAMD_OK;
 }
 
@@ -1259,22 +1361,35 @@ whamd_status_t DeviceTable::Impl::take_solve_buffers(const Problem& p, TableBuil
 	b.laps.lap("jobs, backtrace units, schedule");
 	b.laps.next_stage();
 	{
-		size_t got = 0;
-		void* d_bt = arena_take(m.device, b.bt, got);
-		if (!d_bt) {
-			HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(b.bt, 16)));
-			got = std::max<size_t>(b.bt, 16);
+		if (m.d_arena && m.arena_bytes < std::max<size_t>(b.bt, 16)) {   // the preview took an arena that turns out too small: its launches are given up
+			HIP_TRY(hipStreamSynchronize(m.stream));
+			arena_give(m.device, m.d_arena, m.arena_bytes);
+			m.d_arena = nullptr;
+			m.arena_bytes = 0;
 		}
-		m.d_arena = d_bt;
-		m.arena_bytes = got;
-		m.dp.bt = (uint8_t*)d_bt;
+		if (!m.d_arena) {   // (else: the arena the preview's launches are writing their records into)
+			size_t got = 0;
+			void* d_bt = arena_take(m.device, b.bt, got);
+			if (!d_bt) {
+				HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(b.bt, 16)));
+				got = std::max<size_t>(b.bt, 16);
+			}
+			m.d_arena = d_bt;
+			m.arena_bytes = got;
+		}
+		m.dp.bt = (uint8_t*)m.d_arena;
 	}
 	b.laps.next_stage();
 	m.key_entries = (size_t)(1ull << b.max_keys_f) * p.T;
 	HIP_TRY(up.alloc((void**)&m.dp.keys, m.key_entries * 8));
 	HIP_TRY(up.alloc((void**)&m.dp.last_keys, (size_t)MAX_T_WIDE * 8));
-	HIP_TRY(up.alloc((void**)&m.d_pr[0], b.exchange_bytes));
-	HIP_TRY(up.alloc((void**)&m.d_pr[1], b.exchange_bytes));
+	if (m.preview.d_pr[0] && m.preview.exchange_bytes >= b.exchange_bytes) {   // (the exchange columns the preview's launches are handing each other)
+		m.d_pr[0] = m.preview.d_pr[0];
+		m.d_pr[1] = m.preview.d_pr[1];
+	} else {
+		HIP_TRY(up.alloc((void**)&m.d_pr[0], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.d_pr[1], b.exchange_bytes));
+	}
 	HIP_TRY(pinned_take((m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t), (void**)&m.h_pinned, &m.h_pinned_bytes));
 	return WHAMD_OK;
 }
@@ -1576,8 +1691,220 @@ whamd_status_t DeviceTable::Impl::record_group_backtrace(uint32_t n, TableUpload
 	return WHAMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the preview
+// Which steps a preview would launch and what each is given by value, worked out ahead of the phases that normally produce it.  Host only (the debug library's
+// whamd_debug_preview_plan holds it against lay_out_arena and cut_chunks without a device).  out.why says whether there is one: the table's form, the options,
+// and -- under `auto` -- that the table is alone.  The record offsets are the sum lay_out_arena will make, from its own helpers; the seeds' ids come from the
+// chunk rule make_chunks walks (cut_chunk_starts), here over the plan's steps.
+void DeviceTable::Impl::plan_preview(const Problem& p, const TableBuild& b, bool from_create, PreviewPlan& out) {
+	Impl& m = *this;
+	const Preview& pv = m.preview;
+	const uint32_t n = b.n, n_pieces = slot_plan_pieces(n);
+	out = PreviewPlan();
+	auto none = [&out](uint32_t why) { out.why = why; };
+	if (pv.mode == 0 || debug_env("WHAMD_NO_PREVIEW")) return none(PV_OFF);
+	if (!from_create) return none(PV_NOT_CREATE);
+	if (!m.use_slots || m.splan.ped || p.T != 1) return none(PV_NOT_SLOTS);
+	if (debug_env("WHAMD_DEBUG_STAMPS") || debug_env("WHAMD_SLOT_STAMPS") || debug_env("WHAMD_SLOT_SKIP")) return none(PV_DEBUG_SWITCH);
+	if (m.shared_hint || m.side_by_side) return none(PV_SHARED);
+	if (m.plan.component_first_step.size() != 1) return none(PV_COMPONENTS);
+	if (n_pieces < 2) return none(PV_FEW_PIECES);
+	if (pv.mode < 0) {   // auto: only where a speculative forward pass competes with nothing
+		if (pv.thread_budget) return none(PV_THREAD_BUDGET);
+		if (n_pieces < 8) return none(PV_FEW_PIECES);
+		if (m.device < 0 || m.device >= 64 || Impl::tables_on_device[m.device].load() != 1) return none(PV_NOT_ALONE);
+	}
+	out.pieces = std::min(n_pieces - 1, pv.pieces_wanted ? pv.pieces_wanted : std::max(1u, n_pieces / 6));
+	const uint32_t col_limit = slot_plan_piece_begin(n, out.pieces);
+	// ---- the leading steps that are slot runs inside the pieces (a piece edge is a run boundary)
+	const std::vector<Step>& steps = m.plan.steps;
+	const std::vector<SlotRun>& runs = m.splan.runs;
+	uint32_t S = 0;
+	while (S < steps.size() && steps[S].kind == 2 && steps[S].index == S && runs[S].c0 + runs[S].ncols <= col_limit) ++S;
+	if (S == 0 || S >= steps.size()) return none(PV_NO_LEADING_RUNS);
+	out.end_col = runs[S - 1].c0 + runs[S - 1].ncols;
+	if ((size_t)out.end_col + SLOT_ROW_PAD > m.splan.rows.size()) return none(PV_ROW_PAD);   // (a run's scalar-cache warm-up touches a fixed number of rows behind its own)
+	// ---- what the runs carry by value: table offsets, record offsets, the ids of the seeds they leave
+	const uint64_t tab_words_all = m.lay_out_slot_tables(b, false);
+	out.tab_words = (S < runs.size() ? runs[S].tab_g : tab_words_all) + (uint64_t)SLOT_XCOLS * 64u;   // (lay_out_slot_tables: the slack an X run may request)
+	out.ctrl_words = (size_t)runs[S - 1].ctrl_off + SLOT_CTRL_WORDS;
+	if (tab_words_all >= 0xFFFFFFFFull || out.ctrl_words > m.splan.ctrl.size()) return none(PV_NO_LEADING_RUNS);
+	out.rec.assign(S, 0);
+	uint64_t bt = 0;
+	{
+		// the records of ALL steps, in order, as lay_out_arena places them when they fit one window (arena_capacity, arena_behind, the record sizes: its own)
+		const uint64_t cap = arena_capacity(b.free_b, n, m.table_bytes, m.arena_limit);
+		for (size_t k = 0; k < steps.size(); ++k) {
+			uint64_t bytes = 0;
+			if (steps[k].kind == 2) bytes = slot_run_record_bytes(runs[steps[k].index]);
+			else {
+				const uint32_t c = steps[k].index, f = p.f[c], ebits = p.k[c] - f;
+				bytes = column_record_bytes(column_step_mode(b.force_keys, c + 1 == n, f, ebits), p.T, f, ebits + b.tbits);
+			}
+			if (bt + bytes + 16 > cap) return none(PV_ARENA);   // (windowed, or too large altogether)
+			if (k < S) out.rec[k] = bt;
+			bt = arena_behind(bt, bytes);
+		}
+		if (bt + (1ull << 31) > b.free_b) return none(PV_ARENA);
+	}
+	out.arena = bt;
+	out.spec.assign(S, 0);
+	out.stride = 64;
+	out.chunked = backtrace_is_chunked(true, 1, false, steps.size());   // (one job of slot runs, not windowed: checked above)
+	if (out.chunked)
+		out.n_spec = cut_chunk_starts(steps.size(), [&steps](size_t u) { return steps[steps.size() - 1 - u].kind == 2; },
+			[&](size_t u, uint32_t id) {
+				const size_t k = steps.size() - 1 - u;
+				out.stride = seed_stride_of(out.stride, runs[steps[k].index]);
+				if (k < S) out.spec[k] = id;
+			});
+	out.max_f = p.max_k;   // (a bound of the widest exchange column: no column forwards more reads than it has, a run's entries are 2^(L + g))
+	for (const SlotRun& run : runs) out.max_f = std::max(out.max_f, run.L + run.g);
+	out.steps = S;
+	out.why = PV_RAN;
+}
+
+// A lone single-individual table's device sits idle through its whole create, and nothing of the create's second half -- column descriptors, the arena's layout,
+// staging and sending ~100 MB, backtrace units, schedule -- is needed by the FIRST launches, which read the rows, control words and tables of their own
+// columns only.  Right behind the plan this function therefore uploads exactly that for the runs plan_preview chose (a prefix of the arrays the table will
+// upload whole: every offset a run carries is the same in both), takes the buffers the solve will write -- arena, exchange columns, seeds -- and launches those
+// runs on the table's own stream, with an event behind the last.  Nothing plan_preview worked out is trusted: verify_preview holds the finished schedule against it.
+whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b, bool from_create, std::string& msg) {
+	Impl& m = *this;
+	Preview& pv = m.preview;
+	PreviewPlan pp;
+	m.plan_preview(p, b, from_create, pp);
+	pv.why = pp.why;
+	if (pp.why != PV_RAN) return WHAMD_OK;
+	const uint32_t n = b.n, S = pp.steps, pieces = pp.pieces, end_col = pp.end_col, n_spec = pp.n_spec, stride = pp.stride, max_f = pp.max_f;
+	const uint64_t bt = pp.arena, tab_words = pp.tab_words;
+	const size_t ctrl_words = pp.ctrl_words;
+	const bool chunked = pp.chunked;
+	const std::vector<uint64_t>& rec = pp.rec;
+	const std::vector<uint32_t>& spec = pp.spec;
+	const std::vector<SlotRun>& runs = m.splan.runs;
+	b.laps.lap("preview: steps, offsets, seeds (host)");
+	// ---- the buffers the solve writes: the table's from here on
+	auto take = [&m](void** out, size_t bytes) {
+		size_t got = 0;
+		const hipError_t e = devpool_take(m.device, std::max<size_t>(bytes, 16), out, &got);
+		if (e == hipSuccess) m.allocations.emplace_back(*out, got);
+		return e;
+	};
+	{
+		size_t got = 0;
+		void* d_bt = arena_take(m.device, bt, got);
+		if (!d_bt) {
+			HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(bt, 16)));
+			got = std::max<size_t>(bt, 16);
+		}
+		m.d_arena = d_bt;
+		m.arena_bytes = got;
+	}
+	pv.exchange_bytes = (size_t)(1ull << max_f) * p.T * 4;
+	HIP_TRY(take((void**)&pv.d_pr[0], pv.exchange_bytes));
+	HIP_TRY(take((void**)&pv.d_pr[1], pv.exchange_bytes));
+	pv.spec_bytes = chunked ? ((size_t)n_spec + 1) * stride * 8 : 0;
+	if (chunked) HIP_TRY(take((void**)&pv.spec_keys, pv.spec_bytes));
+	// ---- the preview's own arrays: a prefix of the table's rows, control words and runs; its tables
+	DevProblem hdp{};
+	hdp.n_cols = n; hdp.T = p.T; hdp.tbits = b.tbits; hdp.n_ind = p.n_ind;
+	{
+		const hipStream_t us = m.upload_stream;
+		TableUploader up(m.device, us, pv.allocations);
+		const size_t row_count = (size_t)end_col + SLOT_ROW_PAD;
+		up.open_block(row_count * sizeof(SlotRow) + ctrl_words * 4 + (size_t)S * sizeof(SlotRun) + 4096);
+		const SlotRun* d_runs = nullptr;
+		HIP_TRY(up.up((void**)&hdp.slot_rows, m.splan.rows.data(), row_count * sizeof(SlotRow)));
+		HIP_TRY(up.up((void**)&hdp.slot_ctrl, m.splan.ctrl.data(), ctrl_words * 4));
+		HIP_TRY(up.up((void**)&d_runs, runs.data(), (size_t)S * sizeof(SlotRun)));
+		HIP_TRY(up.alloc((void**)&hdp.slot_tab, tab_words * 4));
+		HIP_TRY(up.flush());
+		uint32_t most = 0;
+		for (uint32_t k = 0; k < S; ++k) most = std::max<uint32_t>(most, ((runs[k].ncols + 8u) << (runs[k].g - runs[k].half)) + (runs[k].ncols + 8u) * ((runs[k].threads >> 6) + 64u));
+		const uint32_t bx = std::max(1u, std::min(64u, (most + 255u) / 256u));
+		for (uint32_t r0 = 0; r0 < S; r0 += 32768) hipLaunchKernelGGL(slot_tables, dim3(bx, std::min<uint32_t>(32768, S - r0)), dim3(256), 0, us, hdp, d_runs + r0, (uint32_t*)hdp.slot_tab);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(m.ev_upload, us));   // (the create records it again behind the table's own uploads; the wait below keeps this record)
+		if (up.unstaged_copies || !up.stage.image || !up.stage.park()) {
+			HIP_TRY(hipStreamSynchronize(us));
+			up.stage.finish();
+		}
+	}
+	b.laps.lap("preview: rows, control words, tables: allocations + copies");
+	// ---- armed once, then the launches
+	{
+		const whamd_status_t opted = opt_in_large_lds(m.device, msg);   // (the first table of a process: an X run's LDS is above what a kernel gets without)
+		if (opted != WHAMD_OK) return opted;
+	}
+	const hipStream_t rs = m.stream;
+	m.inflight.run_stream = rs;
+	m.own_stream_used = true;
+	HIP_TRY(hipStreamWaitEvent(rs, m.ev_upload, 0));
+	hdp.bt = (uint8_t*)m.d_arena;
+	hdp.spec_keys = pv.spec_keys;
+	hdp.spec_stride = stride;
+	if (chunked) HIP_TRY(hipMemsetAsync(pv.spec_keys, 0xFF, pv.spec_bytes, rs));
+	m.inflight.timing_pending = false;   // (the events are the coming solve's from here on)
+	HIP_TRY(hipEventRecord(m.ev0, rs));
+	m.use_chunks = chunked;   // (launch_slot_run: a run leaves a seed where the backtrace is chunked)
+#ifdef WHAMD_DEBUG_BUILD
+	m.ledger.clear();
+#endif
+	pv.runs.resize(S);
+	uint64_t launches = 0;
+	pv.launching = true;   // (the ledger marks these lines)
+	for (uint32_t k = 0; k < S; ++k) {
+		SlotBatchEntry e{};
+		e.run = runs[k];
+		if (k == 0) e.run.has_prev = 0;   // (make_schedule: a job starts from cost 0)
+		e.run.rec_lo = (uint32_t)rec[k];
+		e.run.rec_hi = (uint32_t)(rec[k] >> 32);
+		e.run.spec_id = spec[k];
+		e.prev = pv.d_pr[k & 1u];
+		e.cur = pv.d_pr[(k & 1u) ^ 1u];
+		pv.runs[k] = e.run;
+		m.launch_slot_run(hdp, e, launches);
+	}
+	pv.launching = false;
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(m.ev3, rs));   // "the preview is done": a solve that starts over on another stream waits for it there (begin_solve); the solve's tail records ev3 anew
+	pv.dp = hdp;
+	pv.use_chunks = chunked;
+	pv.why = PV_RAN;
+	pv.pieces = pieces;
+	pv.launched = S;
+	pv.launches = launches;
+	pv.pending = true;
+	b.laps.lap("preview: launches submitted");
+	return WHAMD_OK;
+}
+
+// The finished table against its preview: S = the leading super-steps of the schedule that are, launch for launch, what the preview launched -- the same run by
+// value (every field: the preview's arrays are prefixes of the table's, so even the offsets into them agree), the same exchange columns, arena and seeds, and the
+// same facts behind the choice of kernel, grid and LDS (launch_slot_run decides from the run, the problem's debug fields, use_chunks and side_by_side).
+void DeviceTable::Impl::verify_preview() {
+	Impl& m = *this;
+	Preview& pv = m.preview;
+	pv.agreed = 0;
+	if (!pv.launched) return;
+	const bool same_ground = m.use_slots && !m.windowed && m.jobs.size() == 1 && m.lanes.size() == 1 && m.dp.bt == pv.dp.bt && m.dp.spec_keys == pv.dp.spec_keys &&
+	                         m.use_chunks == pv.use_chunks && (!m.use_chunks || m.dp.spec_stride == pv.dp.spec_stride) && !m.dp.dbg && !m.dp.dbg_flags &&
+	                         m.d_pr[0] == pv.d_pr[0] && m.d_pr[1] == pv.d_pr[1] && !m.side_by_side;
+	for (uint32_t k = 0; same_ground && k < pv.launched && k + 1 < m.schedule.size(); ++k) {
+		const Impl::SuperStep& ss = m.schedule[k];
+		if (ss.entry_count != 1 || !ss.singles.empty() || ss.ck_load >= 0 || ss.ck_save >= 0 || ss.bt_window >= 0) break;
+		const SlotBatchEntry& e = m.slot_entries[ss.entry_off];
+		if (std::memcmp(&e.run, &pv.runs[k], sizeof(SlotRun)) != 0 || e.prev != pv.d_pr[k & 1u] || e.cur != pv.d_pr[(k & 1u) ^ 1u] || e.score_out) break;
+		++pv.agreed;
+	}
+	if (const char* at = debug_env("WHAMD_PREVIEW_MISMATCH_AT")) pv.agreed = std::min<uint32_t>(pv.agreed, (uint32_t)std::max(0, atoi(at)));   // (debug library: "step `at` differs")
+	if (getenv("WHAMD_DEBUG_TIMING"))
+		fprintf(stderr, "[whamd timing] preview: %u plan pieces, %u steps launched, %u agree with the schedule\n", pv.pieces, pv.launched, pv.agreed);
+}
+
 // Everything whamd_dptable_create does after the planner, phase by phase (DESIGN.md 6.1 lists what crosses between them).
-whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
+whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg, bool from_create) {
 	Impl& m = *impl_;
 	whamd_status_t st = m.open(device, msg);
 	if (st != WHAMD_OK || p.n_cols == 0) return st;
@@ -1594,13 +1921,15 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 	b.ped_slots = m.use_slots && m.splan.ped;
 	b.laps.next_stage();
 	if (debug_env("WHAMD_DEBUG_PLAN")) m.dump_plan(p);
-	if ((st = m.describe_columns(p, b, msg)) != WHAMD_OK) return st;
-	if ((st = m.lay_out_arena(p, b, msg)) != WHAMD_OK) return st;
 	// ---- the upload opens: everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the
 	// solve behind ev_upload.  WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.
 	m.upload_stream = debug_env("WHAMD_UPLOAD_ON_TABLE_STREAM") ? nullptr : upload_stream_of(device);
 	if (!m.upload_stream) m.upload_stream = m.stream;
 	if (m.upload_stream == m.stream) m.own_stream_used = true;
+	// ---- a lone table: its first runs start on the device here, and the rest of the create happens under them
+	if ((st = m.start_preview(p, b, from_create, msg)) != WHAMD_OK) return st;
+	if ((st = m.describe_columns(p, b, msg)) != WHAMD_OK) return st;
+	if ((st = m.lay_out_arena(p, b, msg)) != WHAMD_OK) return st;
 	TableUploader up(device, m.upload_stream, m.allocations);
 	b.laps.lap("staging area taken");
 	up.open_block(m.upload_bound(p, b));
@@ -1623,7 +1952,9 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg) {
 	b.laps.summary((double)b.bt / 1e9);
 	if ((st = m.arm_debug_stamps(up, msg)) != WHAMD_OK) return st;
 	if ((st = opt_in_large_lds(device, msg)) != WHAMD_OK) return st;
-	return m.record_group_backtrace(b.n, up, msg);
+	if ((st = m.record_group_backtrace(b.n, up, msg)) != WHAMD_OK) return st;
+	m.verify_preview();
+	return WHAMD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- launch tables of the solve
@@ -1801,13 +2132,13 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 	launches += 1;
 }
 
-// One slot run as a launch of its own (kernel arguments by value).
-void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launches) {
+// One slot run as a launch of its own (kernel arguments by value); `dp`: the table's problem, or the preview's with arrays of its own.
+void DeviceTable::Impl::launch_slot_run(const DevProblem& dp, const SlotBatchEntry& e, uint64_t& launches) {
 	Impl& m = *this;
 	const SlotRun& run = e.run;
 	const hipStream_t rs = m.inflight.run_stream;
 	const bool spec = run.spec_id != 0 && m.use_chunks && !debug_env("WHAMD_NO_SPEC_KERNEL");
-	const bool stamps = DEBUG_BUILD && (m.dp.dbg != nullptr || m.dp.dbg_flags != 0);
+	const bool stamps = DEBUG_BUILD && (dp.dbg != nullptr || dp.dbg_flags != 0);
 	launches += 1;
 	if (m.splan.ped) {
 		const PedSlotExtra& ex = m.splan.pextra[e.pad];
@@ -1820,7 +2151,7 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 			kernel = pedslot_runx_kernel(ex.tb, ex.nf, xc, spec);
 		}
 #endif
-		hipLaunchKernelGGL(kernel, dim3(1u << run.g), dim3(run.threads), lds, rs, m.dp, run, ex, e.prev, e.cur);
+		hipLaunchKernelGGL(kernel, dim3(1u << run.g), dim3(run.threads), lds, rs, dp, run, ex, e.prev, e.cur);
 #ifdef WHAMD_DEBUG_BUILD
 		LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
 		facts.ped = 1; facts.tb = (int32_t)ex.tb; facts.nf = (int32_t)ex.nf; facts.pack = (run.yflags & 16u) != 0;
@@ -1839,7 +2170,7 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 		// the prologue forms the operands of XC columns (an irregular layout's runs are ~10 columns long); with stamps there are the two long forms only
 		const uint32_t xc = streamed ? 0u : (run.ncols <= 8u && !stamps) ? 8u : (run.ncols <= 16u && !stamps) ? 16u : run.ncols <= 24u ? 24u : 32u;
 		const SlotRunXFn kernel = slot_runx_kernel(xc, stamps, spec);
-		hipLaunchKernelGGL(kernel, dim3(pack ? grid.x * 8u : grid.x), block, lds_x, rs, m.dp, run, e.prev, e.cur, e.score_out, pack);
+		hipLaunchKernelGGL(kernel, dim3(pack ? grid.x * 8u : grid.x), block, lds_x, rs, dp, run, e.prev, e.cur, e.score_out, pack);
 #ifdef WHAMD_DEBUG_BUILD
 		LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
 		facts.ped = 0; facts.streamed = streamed; facts.pack = (int32_t)pack;
@@ -1849,7 +2180,7 @@ void DeviceTable::Impl::launch_slot_run(const SlotBatchEntry& e, uint64_t& launc
 	}
 	const size_t lds = slot_run_lds_bytes(run.threads, run.lr, run.ncols);   // wave-slot exchange + hot lines + per-wave A + lane sums
 	const SlotRunFn kernel = slot_run_kernel(run.lr, (run.yflags & 1u) != 0, stamps, spec);
-	hipLaunchKernelGGL(kernel, grid, block, lds, rs, m.dp, run, e.prev, e.cur, e.score_out);
+	hipLaunchKernelGGL(kernel, grid, block, lds, rs, dp, run, e.prev, e.cur, e.score_out);
 #ifdef WHAMD_DEBUG_BUILD
 	LaunchFacts facts = LaunchFacts::of_run(run, spec, stamps);
 	facts.ped = 0;
@@ -1878,24 +2209,45 @@ void DeviceTable::abort_enqueue() {
 	m.inflight.rewind(m.stream);
 }
 
+// The key scratch of the per-column kernels and of the last column, all-ones, on the run stream.
+whamd_status_t DeviceTable::Impl::arm_keys(std::string& msg) {
+	Impl& m = *this;
+	const hipStream_t rs = m.inflight.run_stream;
+	for (const Impl::Lane& lane : m.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.key_entries * 8, rs));
+	HIP_TRY(hipMemsetAsync(m.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, rs));
+	return WHAMD_OK;
+}
+
 // The preamble of a solve on its run stream: path buffers, key re-arm, the start event, the lookup tables of the LDS-resident paths.
-whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std::string& msg) {
+// behind_preview: the solve continues behind the table's preview (enqueue_some_unguarded decides) -- the cursor opens at the preview's last step; the seeds of
+// the speculative backtrace and the start event were armed in front of the preview and stay; the key scratch, which no slot run reads, is armed here.
+// In every other case a preview that is still pending is given up: the steps start over at 0, behind it in stream order or behind a host wait.
+whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std::string& msg, bool behind_preview) {
 	Impl& m = *this;
 	const hipStream_t rs = m.inflight.run_stream;
 	const uint32_t n = p.n_cols;
 	s.path_index.assign(n, 0);
 	s.path_trans.assign(n, 0);
 	s.superreads_done = false;
-	m.inflight.launches = 0;
-	m.inflight.next_super = 0;
+	if (m.preview.pending && !behind_preview && rs != m.stream) HIP_TRY(hipStreamWaitEvent(rs, m.ev3, 0));   // (its launches write what this solve's are about to write: ev3 stands behind the last)
+	m.preview.pending = false;
+	m.preview.continued = behind_preview;
+	m.inflight.launches = behind_preview ? m.preview.launches : 0;
+	m.inflight.next_super = behind_preview ? m.preview.agreed : 0;
 #ifdef WHAMD_DEBUG_BUILD
-	m.ledger.clear();
+	if (!behind_preview) m.ledger.clear();   // (the preview's launches are lines of this solve's ledger)
 #endif
 	if (n == 0) return WHAMD_OK;
 	if (rs == m.stream) m.own_stream_used = true;
 	if (m.ev_upload && (m.upload_pending || rs != m.stream)) HIP_TRY(hipStreamWaitEvent(rs, m.ev_upload, 0));   // (the uploads went through an upload stream; once a solve has been collected they are known to be there)
-	for (const Impl::Lane& lane : m.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.key_entries * 8, rs));
-	HIP_TRY(hipMemsetAsync(m.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, rs));
+	{
+		const whamd_status_t armed = m.arm_keys(msg);
+		if (armed != WHAMD_OK) return armed;
+	}
+	if (behind_preview) {
+		m.inflight.timing_pending = false;
+		return WHAMD_OK;
+	}
 	if (m.use_chunks) HIP_TRY(hipMemsetAsync(m.dp.spec_keys, 0xFF, ((size_t)m.n_spec + 1) * m.dp.spec_stride * 8, rs));
 	if (m.windowed) HIP_TRY(hipMemsetAsync(m.d_path_trans, 0, (size_t)n * 4, rs));
 	m.inflight.timing_pending = false;   // (the events are this solve's from here on)
@@ -1920,7 +2272,7 @@ whamd_status_t DeviceTable::Impl::submit_super_step(const Problem& p, const Supe
 	const dim3 grid(ss.grid_x, ss.entry_count), block(ss.threads);
 	if (ss.ck_load >= 0) HIP_TRY(hipMemcpyAsync(ss.io[0], m.d_checkpoints + (size_t)ss.ck_load * m.checkpoint_bytes, m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
 	if (ss.entry_count == 1) {
-		if (m.use_slots) m.launch_slot_run(m.slot_entries[ss.entry_off], launches);
+		if (m.use_slots) m.launch_slot_run(m.dp, m.slot_entries[ss.entry_off], launches);
 		else m.launch_run(m.entries[ss.entry_off], launches);
 	} else if (ss.entry_count > 1) {
 		if (m.use_slots) { const SlotBatchFn kernel = slot_batch_kernel(m.slot_lr_used); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_slot_entries + ss.entry_off); }
@@ -2009,7 +2361,9 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 		m.inflight.enqueue_open = true;
 		m.inflight.run_stream = m.stream;
 		m.inflight.group_tables = 1;
-		const whamd_status_t st = m.begin_solve(p, s, msg);
+		// behind the preview: the table alone on its own stream, every launched step agreed with the finished schedule, and its launches chosen as this solve's are
+		const bool behind_preview = n && m.preview.pending && m.preview.agreed > 0 && m.preview.agreed == m.preview.launched && !m.side_by_side;
+		const whamd_status_t st = m.begin_solve(p, s, msg, behind_preview);
 		if (st != WHAMD_OK) return st;
 		if (n == 0) {  // src/pedigreedptable.cpp:88-92
 			s.optimal_score = 0;
@@ -2386,6 +2740,7 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 	if (m.inflight.tail_elsewhere) HIP_TRY(hipEventSynchronize(m.ev3));   // (the last thing submit_tail recorded, on the stream the tail went to)
 	else { HIP_TRY(hipStreamSynchronize(m.stream)); m.own_stream_used = false; }
 	m.upload_pending = false;   // (the solve ran behind ev_upload: the uploads are there)
+	m.give_preview_block();     // (the preview ran in front of this solve, or was waited for when the solve began on another stream)
 	const uint32_t n = p.n_cols;
 	std::memcpy(s.path_index.data(), m.h_pinned, (size_t)n * 4);
 	std::memcpy(s.path_trans.data(), m.h_pinned + n, (size_t)n * 4);
@@ -2505,6 +2860,79 @@ size_t DeviceTable::debug_launches(whamd_debug_launch* out, size_t capacity) con
 	return ledger.size();
 }
 
+static const char* const* preview_why_lines() {   // [PreviewWhy]
+	static const char* const why[13] = {
+		"", "no preview: switched off", "no preview: not inside whamd_dptable_create", "no preview: not a single-individual table on slot runs", "no preview: a debug switch changes the launches",
+		"no preview: the table shares its launches", "no preview: the create is held to a thread budget", "no preview: more than one connected component", "no preview: too few plan pieces",
+		"no preview: not alone", "no preview: the table does not begin with slot runs", "no preview: too close to the table's end", "no preview: the backtrace arena does not fit one window"};
+	return why;
+}
+
+// plan_preview against the phases it runs ahead of, without a device (whamd_debug_preview_plan): the plan as choose_plan makes it for a single individual, the
+// preview forced with `pieces`, then describe_columns, lay_out_arena, the units and cut_chunks exactly as upload() runs them -- free HBM is taken as 1 TiB.
+whamd_status_t DeviceTable::debug_preview_plan(Problem& p, uint32_t pieces, whamd_debug_preview_plan_result* out, uint64_t* rec_predicted, uint64_t* rec_laid_out,
+                                               uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity, std::string& msg) {
+	Impl m;
+	TableBuild b;
+	b.n = p.n_cols;
+	b.tbits = 2 * p.n_triples;
+	b.ni = std::max<uint32_t>(p.n_ind, 1);
+	b.free_b = (size_t)1 << 40;
+	if (p.T != 1 || p.n_cols == 0) { msg = "a single-individual table expected"; return WHAMD_ERR_UNSUPPORTED; }
+	m.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
+	m.use_slots = plan_forward_slots(p, std::max(8, m.slot_l), m.symmetry, m.splan, m.slot_lr);
+	if (!m.use_slots) { msg = "the table is not planned on slot runs"; return WHAMD_ERR_UNSUPPORTED; }
+	m.plan = ResidentPlan();
+	m.plan.steps = m.splan.steps;
+	m.plan.component_first_step = m.splan.component_first_step;
+	m.plan.col_to_res.assign(p.n_cols, -1);
+	m.preview.mode = 1;
+	m.preview.pieces_wanted = pieces;
+	Impl::PreviewPlan pp;
+	m.plan_preview(p, b, true, pp);
+	whamd_status_t st = m.describe_columns(p, b, msg);
+	if (st == WHAMD_OK) st = m.lay_out_arena(p, b, msg);
+	if (st != WHAMD_OK) return st;
+	m.build_slot_blobs(b);
+	m.lay_out_slot_tables(b, false);
+	m.make_jobs();
+	m.make_units(b);
+	m.cut_chunks(p);
+	static const char* const* why = preview_why_lines();
+	*out = whamd_debug_preview_plan_result{};
+	out->n_pieces = slot_plan_pieces(p.n_cols);
+	out->pieces = pp.pieces;
+	out->steps = pp.steps;
+	out->n_steps = (uint32_t)m.plan.steps.size();
+	out->why_not = why[pp.why < Impl::PV_WHYS ? pp.why : 0];
+	out->chunked_predicted = pp.chunked; out->chunked = m.use_chunks;
+	out->n_seeds_predicted = pp.n_spec; out->n_seeds = m.n_spec;
+	out->stride_predicted = pp.stride; out->stride = m.use_chunks ? m.dp.spec_stride : 64u;
+	out->arena_predicted = pp.arena; out->arena_laid_out = b.bt;
+	out->windowed = m.windowed;
+	out->exchange_predicted = (uint64_t)(1ull << pp.max_f) * p.T * 4; out->exchange_laid_out = b.exchange_bytes;
+	for (uint32_t k = 0; k < pp.steps && k < capacity; ++k) {
+		const SlotRun& run = m.splan.runs[m.plan.steps[k].index];
+		if (rec_predicted) rec_predicted[k] = pp.rec[k];
+		if (rec_laid_out) rec_laid_out[k] = ((uint64_t)run.rec_hi << 32) | run.rec_lo;
+		if (spec_predicted) spec_predicted[k] = pp.spec[k];
+		if (spec_laid_out) spec_laid_out[k] = run.spec_id;
+	}
+	return WHAMD_OK;
+}
+
+// What became of the table's preview (whamd_debug_dptable_preview).
+void DeviceTable::debug_preview(whamd_debug_preview* out) const {
+	static const char* const* why = preview_why_lines();
+	const Impl::Preview& pv = impl_->preview;
+	out->ran = pv.why == Impl::PV_RAN;
+	out->continued = pv.continued;
+	out->pieces = pv.pieces;
+	out->launched_steps = pv.launched;
+	out->agreed_steps = pv.agreed;
+	out->why_not = why[pv.why < Impl::PV_WHYS ? pv.why : 0];
+}
+
 // One launch into the ledger: a line that agrees in everything but the count takes it, else it opens a new line.
 void DeviceTable::Impl::note(uint32_t site, const void* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t on, bool forward, const LaunchFacts& facts) {
 	whamd_debug_launch rec = facts;
@@ -2514,6 +2942,8 @@ void DeviceTable::Impl::note(uint32_t site, const void* kernel, dim3 grid, dim3 
 	rec.lds = (uint32_t)lds;
 	rec.own_stream = on == stream ? 1u : 0u;
 	rec.forward = forward ? 1u : 0u;
+	rec.preview = preview.launching ? 1 : 0;
+	rec.reserved = 0;
 	rec.count = 0;
 	rec.name = nullptr;
 	for (whamd_debug_launch& have : ledger)

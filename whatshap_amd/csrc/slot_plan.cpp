@@ -416,12 +416,11 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 	{
 		// The ranges planned independently become run boundaries: they follow from the INPUT alone (fixed pieces of ~PLAN_PIECE columns), not
 		// from how many host threads this machine has -- the same table gets the same runs, launches and record layout everywhere.
-		constexpr uint32_t PLAN_PIECE = 8192;
-		const uint32_t n_pieces = std::max<uint32_t>(1, n / PLAN_PIECE);
+		const uint32_t n_pieces = slot_plan_pieces(n);
 		std::vector<SlotPlan> parts(n_pieces);
 		std::vector<std::vector<RunDraft>> part_drafts(n_pieces);
 		std::vector<uint32_t> bounds(n_pieces + 1);
-		for (uint32_t t = 0; t <= n_pieces; ++t) bounds[t] = (uint32_t)((uint64_t)n * t / n_pieces);
+		for (uint32_t t = 0; t <= n_pieces; ++t) bounds[t] = slot_plan_piece_begin(n, t);
 		parallel_ranges(n_pieces, host_threads(n_pieces, 1), [&](uint64_t q0, uint64_t q1, uint32_t) {
 			for (uint64_t q = q0; q < q1; ++q) plan_range(bounds[q], bounds[q + 1], parts[q], part_drafts[q]);
 		});

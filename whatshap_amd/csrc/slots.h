@@ -292,6 +292,12 @@ struct SlotPlan {
 	uint64_t table_words = 0;
 };
 
+// The planner cuts a table into fixed pieces of ~PLAN_PIECE columns that are planned independently (slot_plan.cpp); their edges follow from the number of
+// columns alone and every edge is a run boundary.  Piece t covers the columns [slot_plan_piece_begin(n, t), slot_plan_piece_begin(n, t + 1)).
+constexpr uint32_t PLAN_PIECE = 8192;
+inline uint32_t slot_plan_pieces(uint32_t n_cols) { return n_cols / PLAN_PIECE > 1 ? n_cols / PLAN_PIECE : 1; }
+inline uint32_t slot_plan_piece_begin(uint32_t n_cols, uint32_t piece) { return (uint32_t)((uint64_t)n_cols * piece / slot_plan_pieces(n_cols)); }
+
 // Plans the forward pass of a single-individual table with slot runs wherever they apply (per-column steps elsewhere).
 // Returns false if the table is not eligible (values beyond 2^30; a pedigree other than one or two trios, or one whose
 // columns mostly need more than PSLOT_MAXFORMS forms per transmission value): the caller uses plan_forward().
