@@ -1,5 +1,4 @@
 // c_api.cpp -- the extern "C" boundary declared in include/whatshap_amd.h.
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +8,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "api_guard.h"
 #include "debug_build.h"
 #ifdef WHAMD_DEBUG_BUILD
 #include "../../include/whatshap_amd_debug.h"
@@ -41,34 +41,10 @@ namespace {
 
 thread_local std::string g_last_error;
 
-whamd_status_t fail(whamd_status_t st, const std::string& msg) {
-	g_last_error = msg;
-	return st;
-}
-
-// No C++ exception crosses the C boundary: std::bad_alloc of the flatten / plan vectors, std::system_error of a worker thread that could not
-// be started, anything a worker carried over (host_parallel.h) become WHAMD_ERR_HOST with the exception's message.
-template <class F>
-whamd_status_t guarded(F&& body) {
-	try {
-		return body();
-	} catch (const std::bad_alloc&) {
-		return fail(WHAMD_ERR_HOST, "out of host memory");
-	} catch (const std::exception& e) {
-		return fail(WHAMD_ERR_HOST, std::string("host-side failure: ") + e.what());
-	} catch (...) {
-		return fail(WHAMD_ERR_HOST, "host-side failure (unknown exception)");
-	}
-}
-
-double now_ms() {
-	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
 namespace whamd {
-// for the host-only entry points that live in other files (readselect.cpp)
+// (api_guard.h: every file with entry points reports through this)
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 }
 

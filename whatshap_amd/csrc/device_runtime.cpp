@@ -433,6 +433,42 @@ whamd_status_t Session::open(int dev_index, int n_events, std::string& msg) {
 		HIP_TRY(hipEventCreate(&e));
 		ev.push_back(e);
 	}
+	timed = n_events == 4;
+	return WHAMD_OK;
+}
+namespace {
+enum CallEvent { UPLOAD_BEGIN, UPLOAD_END, KERNELS_END, DOWNLOAD_END };   // what ev[0 .. 3] of a timed session mark
+double ms_between(hipEvent_t a, hipEvent_t b) {
+	float t = 0.0f;
+	return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0;
+}
+}  // namespace
+whamd_status_t Session::stage(const ImageLayout& layout, Image& image, std::string& msg) {
+	image.total = layout.total;
+	const whamd_status_t st = pinned_block(layout.total, (void**)&image.stage, msg);
+	return st != WHAMD_OK ? st : device_block(layout.total, (void**)&image.base, msg);
+}
+whamd_status_t Session::upload(const Image& image, size_t bytes, std::string& msg) {
+	if (timed) HIP_TRY(hipEventRecord(ev[UPLOAD_BEGIN], stream));
+	HIP_TRY(hipMemcpyAsync(image.base, image.stage, bytes, hipMemcpyHostToDevice, stream));
+	if (timed) HIP_TRY(hipEventRecord(ev[UPLOAD_END], stream));
+	return WHAMD_OK;
+}
+whamd_status_t Session::kernels_done(std::string& msg) {
+	if (timed) HIP_TRY(hipEventRecord(ev[KERNELS_END], stream));
+	return WHAMD_OK;
+}
+whamd_status_t Session::fetch(void* dst, const void* src, size_t bytes, std::string& msg) {
+	HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+	return WHAMD_OK;
+}
+whamd_status_t Session::finish(CallTimes& times, std::string& msg, bool downloaded) {
+	if (timed && downloaded) HIP_TRY(hipEventRecord(ev[DOWNLOAD_END], stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	if (!timed) return WHAMD_OK;
+	times.upload_ms = ms_between(ev[UPLOAD_BEGIN], ev[UPLOAD_END]);
+	times.kernel_ms = ms_between(ev[UPLOAD_END], ev[KERNELS_END]);
+	times.download_ms = downloaded ? ms_between(ev[KERNELS_END], ev[DOWNLOAD_END]) : 0.0;
 	return WHAMD_OK;
 }
 void Session::close() {

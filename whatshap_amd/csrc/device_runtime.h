@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
+#include "call_image.h"
 
 // `msg` (std::string&) is in scope; the enclosing function returns whamd_status_t.
 #define HIP_TRY(expr)                                                                                 \
@@ -90,10 +91,19 @@ struct StageSession {
 
 // ---------------------------------------------------------------------------------------------- one call on one device
 // What a call holds on the device and in pinned memory; given back on every way out.
+// The steps of a batch call (one image up, kernels, results down), in this order; each sets `msg` and returns the status:
+//   stage(layout, image)  the image's pinned and device block (call_image.h); the call fills image.host(piece)
+//   upload(image)         the image, or its first `bytes`, to the device
+//   ... the call's launches on `stream` ...
+//   kernels_done()
+//   fetch(dst, src, n)    device to pinned host; as many as the call needs (before kernels_done(): part of the kernel time)
+//   finish(times)         waits for the stream; upload / kernel / download ms of `times`
+// A session opened with four events records one around each phase; one opened with none records nothing and finish() leaves `times` alone.
 struct Session {
 	int device = -1;
 	hipStream_t stream = nullptr;
 	std::vector<hipEvent_t> ev;              // [0, n_events) of open() record times (ms); sync_event() appends
+	bool timed = false;                      // open() with four events: the steps record them
 	std::vector<hipStream_t> streams;        // add_stream()
 	std::vector<std::pair<void*, size_t>> dev, pinned;   // (pointer, size class) of the pools
 	std::vector<void*> fresh;                // fresh_block()
@@ -107,14 +117,17 @@ struct Session {
 	void close();
 	whamd_status_t device_block(size_t bytes, void** out, std::string& msg);
 	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg);
+	whamd_status_t stage(const ImageLayout& layout, Image& image, std::string& msg);
+	whamd_status_t upload(const Image& image, size_t bytes, std::string& msg);
+	whamd_status_t upload(const Image& image, std::string& msg) { return upload(image, image.total, msg); }
+	whamd_status_t kernels_done(std::string& msg);
+	whamd_status_t fetch(void* dst, const void* src, size_t bytes, std::string& msg);
+	// downloaded = false: nothing was fetched after kernels_done() -- no event is recorded for it and download_ms is exactly 0.
+	whamd_status_t finish(CallTimes& times, std::string& msg, bool downloaded = true);
 	// Not from the pool: hipMalloc -- after devpool_release() once more if the first fails -- and hipFree when the session ends.
 	hipError_t fresh_block(void** out, size_t bytes);
 	hipError_t add_stream(hipStream_t* out);
 	hipError_t sync_event(hipEvent_t* out);   // hipEventDisableTiming: orders streams, records no time
-	double ms(int a, int b) const {
-		float t = 0.0f;
-		return hipEventElapsedTime(&t, ev[a], ev[b]) == hipSuccess ? (double)t : 0.0;
-	}
 };
 
 }  // namespace whamd

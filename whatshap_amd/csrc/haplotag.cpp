@@ -4,7 +4,6 @@
 #include "haplotag.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -12,35 +11,12 @@
 #include <unordered_map>
 
 #include "../../include/whatshap_amd_debug.h"
+#include "api_guard.h"
 #include "debug_build.h"
-
-namespace whamd {
-void set_last_error(const std::string& msg);   // c_api.cpp
-}
 
 using namespace whamd;
 
 namespace {
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-whamd_status_t fail(whamd_status_t st, const std::string& msg) {
-	set_last_error(msg);
-	return st;
-}
-
-template <class F>
-whamd_status_t guarded(F&& body) {
-	try {
-		return body();
-	} catch (const std::bad_alloc&) {
-		return fail(WHAMD_ERR_HOST, "out of host memory");
-	} catch (const std::exception& e) {
-		return fail(WHAMD_ERR_HOST, std::string("host-side failure: ") + e.what());
-	} catch (...) {
-		return fail(WHAMD_ERR_HOST, "host-side failure");
-	}
-}
 
 constexpr uint64_t NONE = std::numeric_limits<uint64_t>::max();
 
@@ -337,7 +313,7 @@ whamd_status_t haplotag(const whamd_haplotag_view* views, uint64_t n, int device
 		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
 	}
 	const double t1 = now_ms();
-	HaplotagTimes times;
+	CallTimes times;
 	if (host) {
 #ifdef WHAMD_DEBUG_BUILD
 		for (uint64_t x = 0; x < n; x++) haplotag_score_host(problems[x], scores[x]);

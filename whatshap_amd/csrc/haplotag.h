@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
+#include "call_image.h"
 #include "host_parallel.h"
 
 #if defined(__HIPCC__)
@@ -120,11 +121,6 @@ struct HaplotagScores {
 	RawVec<HtOut> out;                        // per group (groups without entries: zeros)
 };
 
-struct HaplotagTimes {
-	double upload_ms = 0, kernel_ms = 0, download_ms = 0;
-	uint32_t launches = 0;
-};
-
 whamd_status_t haplotag_prepare(const whamd_haplotag_view& v, HaplotagProblem& p, std::string& msg);
 
 // The class boundaries of the call in progress: HT_CLASS_A_MAX / HT_CLASS_B_MAX.  In the debug library only, every call re-reads them from
@@ -139,7 +135,7 @@ inline uint32_t haplotag_class_of(uint64_t n_entries) {
 
 // All problems of a call: one upload, one launch per class that has groups (at most three, whatever the number of problems), one download.
 // Nothing to score: nothing touches the device (launches = 0).
-whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int device, std::vector<HaplotagScores>& out, HaplotagTimes& times,
+whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int device, std::vector<HaplotagScores>& out, CallTimes& times,
                                      std::string& msg);
 
 }  // namespace whamd

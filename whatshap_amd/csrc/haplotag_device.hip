@@ -7,6 +7,7 @@
 //             of a chunk are consecutive 64-byte pieces.
 //   class b   (65 .. 4096)       one wave per group.
 //   class c   (more)             one workgroup per group: every wave takes a contiguous quarter of the run, the quarters meet in LDS.
+// (The upload is one image of three typed pieces, call_image.h; the call runs through the steps of Session, device_runtime.h.)
 // A team (segment, wave) walks its run in chunks of its width, in order.  It keeps up to R = 4 phase sets in registers, in the order of
 // their first matching entry: the lanes of a chunk whose phase set has no slot yet are found with a ballot, the lowest of them names the
 // next slot (a chunk is consecutive entries, so the lowest lane is the first encounter).  Every lane adds its entry's quality to the sums of
@@ -318,13 +319,11 @@ void launch_class(uint32_t cls, const HtArgs& a, hipStream_t stream) {
 	else hipLaunchKernelGGL((haplotag_block_kernel<P>), dim3(a.n_groups), dim3(HT_BLOCK), 0, stream, a);
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
-whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int device, std::vector<HaplotagScores>& out, HaplotagTimes& times,
+whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int device, std::vector<HaplotagScores>& out, CallTimes& times,
                                      std::string& msg) {
-	times = HaplotagTimes{};
+	times = CallTimes{};
 	out.assign(ps.size(), HaplotagScores{});
 	// the records: groups with entries, by class, within a class in the order of the problems and of their groups
 	uint64_t n_rec[3] = {0, 0, 0}, n_ent[3] = {0, 0, 0}, n_variants = 0;
@@ -368,26 +367,24 @@ whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int
 			}
 		}
 	}
-	size_t o = 0;
-	const size_t o_var = o; o = align_up(o + n_variants * sizeof(HtVariant));
-	const size_t o_rec = o; o = align_up(o + total_rec * sizeof(HtGroup));
-	const size_t o_ent = o; o = align_up(o + total_ent * sizeof(HtEntry));
-	const size_t total_in = o, total_out = total_rec * sizeof(HtOut);
+	ImageLayout in;
+	const auto p_var = in.add<HtVariant>(n_variants);
+	const auto p_rec = in.add<HtGroup>(total_rec);
+	const auto p_ent = in.add<HtEntry>(total_ent);
+	const size_t total_out = total_rec * sizeof(HtOut);
 	Session s;
 	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
-	char* stage = nullptr;
-	char* base = nullptr;
+	Image im;
 	HtOut* dev_out = nullptr;
 	HtOut* res = nullptr;
-	if ((st = s.pinned_block(total_in, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total_in, (void**)&base, msg)) != WHAMD_OK) return st;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
 	if ((st = s.device_block(total_out, (void**)&dev_out, msg)) != WHAMD_OK) return st;
 	if ((st = s.pinned_block(total_out, (void**)&res, msg)) != WHAMD_OK) return st;
 	for (size_t x = 0; x < ps.size(); x++)
-		if (var_base[x + 1] > var_base[x]) std::memcpy(stage + o_var + var_base[x] * sizeof(HtVariant), ps[x].variants.data(), ps[x].variants.size() * sizeof(HtVariant));
-	HtGroup* recs = (HtGroup*)(stage + o_rec);
-	HtEntry* ents = (HtEntry*)(stage + o_ent);
+		if (var_base[x + 1] > var_base[x]) std::memcpy(im.host(p_var) + var_base[x], ps[x].variants.data(), ps[x].variants.size() * sizeof(HtVariant));
+	HtGroup* recs = im.host(p_rec);
+	HtEntry* ents = im.host(p_ent);
 	parallel_ranges(total_rec, host_threads(total_ent + total_rec, 1 << 16), [&](uint64_t b, uint64_t e, uint32_t) {
 		for (uint64_t x = b; x < e; x++) {
 			const Slot& sl = slots[x];
@@ -401,13 +398,10 @@ whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int
 			}
 		}
 	});
-	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-	HIP_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
 	for (uint32_t cls = 0; cls < 3; cls++) {
 		if (!n_rec[cls]) continue;
-		HtArgs a{(const HtEntry*)(base + o_ent), (const HtVariant*)(base + o_var), (const HtGroup*)(base + o_rec) + rec_base[cls], dev_out + rec_base[cls],
-		         (uint32_t)n_rec[cls]};
+		HtArgs a{im.dev(p_ent), im.dev(p_var), im.dev(p_rec) + rec_base[cls], dev_out + rec_base[cls], (uint32_t)n_rec[cls]};
 		const uint32_t k = max_ploidy[cls];
 		if (k <= 2) launch_class<2>(cls, a, s.stream);
 		else if (k <= 4) launch_class<4>(cls, a, s.stream);
@@ -416,13 +410,9 @@ whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int
 		HIP_TRY(hipGetLastError());
 		++times.launches;
 	}
-	HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-	HIP_TRY(hipMemcpyAsync(res, dev_out, total_out, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	times.upload_ms = s.ms(0, 1);
-	times.kernel_ms = s.ms(1, 2);
-	times.download_ms = s.ms(2, 3);
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res, dev_out, total_out, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
 	parallel_ranges(total_rec, host_threads(total_rec, 1 << 16), [&](uint64_t b, uint64_t e, uint32_t) {
 		for (uint64_t x = b; x < e; x++) out[slots[x].problem].out[slots[x].group] = res[x];
 	});

@@ -5,42 +5,18 @@
 #include "polyscore.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <functional>
 #include <limits>
 #include <memory>
 #include <unordered_map>
 
+#include "api_guard.h"
 #include "debug_build.h"
-
-namespace whamd {
-void set_last_error(const std::string& msg);   // c_api.cpp
-}
 
 using namespace whamd;
 
 namespace {
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-whamd_status_t fail(whamd_status_t st, const std::string& msg) {
-	set_last_error(msg);
-	return st;
-}
-
-template <class F>
-whamd_status_t guarded(F&& body) {
-	try {
-		return body();
-	} catch (const std::bad_alloc&) {
-		return fail(WHAMD_ERR_HOST, "out of host memory");
-	} catch (const std::exception& e) {
-		return fail(WHAMD_ERR_HOST, std::string("host-side failure: ") + e.what());
-	} catch (...) {
-		return fail(WHAMD_ERR_HOST, "host-side failure (unknown exception)");
-	}
-}
 
 // ---------------------------------------------------------------------------------------------- binomial.cpp / multinomial.cpp semantics
 int binomial_coefficient(int n, int k) {
@@ -434,8 +410,7 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 		});
 	}
 	const double t1 = now_ms();
-	double up = 0, kern = 0, down = 0;
-	uint32_t launches = 0;
+	CallTimes times;
 	if (scored) {
 		const float offset = poly_offset(ploidy);
 		if (host) {
@@ -443,7 +418,7 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 			for (uint64_t x = 0; x < n_matrices; x++) poly_score_host(ms[x], min_overlap, offset, r->results[x]);
 #endif
 		} else {
-			const whamd_status_t st = poly_score_device(ms, min_overlap, offset, device, r->results, &up, &kern, &down, &launches, msg);
+			const whamd_status_t st = poly_score_device(ms, min_overlap, offset, device, r->results, times, msg);
 			if (st != WHAMD_OK) return fail(st, msg);
 		}
 	}
@@ -458,11 +433,11 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 		s.n_entries = r->results[x].score.size();
 		s.n_nan = r->results[x].n_nan;
 		s.n_pair_positions = r->results[x].n_pair_positions;
-		s.launches = launches;
+		s.launches = times.launches;
 		s.host_ms = t1 - t0;
-		s.upload_ms = up;
-		s.kernel_ms = kern;
-		s.download_ms = down;
+		s.upload_ms = times.upload_ms;
+		s.kernel_ms = times.kernel_ms;
+		s.download_ms = times.download_ms;
 		s.total_ms = t2 - t0;
 	}
 	*out = r.release();

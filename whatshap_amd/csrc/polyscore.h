@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
+#include "call_image.h"
 #include "host_parallel.h"
 
 namespace whamd {
@@ -93,8 +94,8 @@ inline uint32_t poly_pair_sum(const uint32_t* pa, const uint8_t* aa, uint64_t na
 void poly_score_host(const PolyMatrix& m, uint32_t min_overlap, float offset, PolyResult& out);
 
 // The device pair loop for a batch of prepared matrices: one upload, one launch sequence, one download.  Matrices without candidate
-// pairs are not uploaded; with none at all nothing touches the device (*launches = 0).
+// pairs are not uploaded; with none at all nothing touches the device (times.launches = 0).
 whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min_overlap, float offset, int device, std::vector<PolyResult>& out,
-                                 double* upload_ms, double* kernel_ms, double* download_ms, uint32_t* launches, std::string& msg);
+                                 CallTimes& times, std::string& msg);
 
 }  // namespace whamd

@@ -8,7 +8,8 @@
 //   2. rocprim exclusive scan of keep (deterministic compaction).
 //   3. poly_compact_kernel: kept pairs -> (key, score), key = max(id) * N + min(id) over global read ids: the triangular order per matrix.
 //   4. rocprim radix sort of (key, score) on the bits the keys use.
-// Only the sorted (key, score) pairs come back.
+// Only the sorted (key, score) pairs come back.  The upload is one image (call_image.h); the steps are Session's (device_runtime.h), with one
+// wait of this call's own after step 2: the number of kept pairs sizes steps 3 and 4.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -127,14 +128,11 @@ __global__ void __launch_bounds__(BLOCK) poly_compact_kernel(CompactArgs a) {
 	}
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min_overlap, float offset, int device, std::vector<PolyResult>& out,
-                                 double* upload_ms, double* kernel_ms, double* download_ms, uint32_t* launches, std::string& msg) {
-	*upload_ms = *kernel_ms = *download_ms = 0.0;
-	*launches = 0;
+                                 CallTimes& times, std::string& msg) {
+	times = CallTimes{};
 	out.assign(ms.size(), PolyResult{});
 	// the matrices with candidate pairs, concatenated
 	std::vector<uint32_t> up;
@@ -153,26 +151,23 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 		return WHAMD_ERR_UNSUPPORTED;
 	}
 	const uint32_t n_mats = (uint32_t)up.size(), N = (uint32_t)n_reads;
-	// staging layout (one upload)
-	size_t o = 0;
-	const size_t o_prefix = o; o = align_up(o + (N + 1) * 8);
-	const size_t o_order = o; o = align_up(o + N * 4);
-	const size_t o_rowptr = o; o = align_up(o + (N + 1) * 8);
-	const size_t o_pos = o; o = align_up(o + n_entries * 4);
-	const size_t o_all = o; o = align_up(o + n_entries);
-	const size_t o_amat = o; o = align_up(o + N * 4);
-	const size_t o_toff = o; o = align_up(o + n_mats * 8);
-	const size_t o_na = o; o = align_up(o + n_mats * 4);
-	const size_t o_terms = o; o = align_up(o + n_terms * 4);
-	const size_t o_counts = o; o = align_up(o + n_mats * 24);
-	const size_t total_in = o;
+	// the image (one upload)
+	ImageLayout in;
+	const auto p_prefix = in.add<uint64_t>(N + 1);
+	const auto p_order = in.add<uint32_t>(N);
+	const auto p_rowptr = in.add<uint64_t>(N + 1);
+	const auto p_pos = in.add<uint32_t>(n_entries);
+	const auto p_all = in.add<uint8_t>(n_entries);
+	const auto p_amat = in.add<uint32_t>(N);
+	const auto p_toff = in.add<uint64_t>(n_mats);
+	const auto p_na = in.add<uint32_t>(n_mats);
+	const auto p_terms = in.add<float>(n_terms);
+	const auto p_counts = in.add<unsigned long long>(3 * (size_t)n_mats);   // zeros; the pair kernel adds to them
 	Session s;
 	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
-	char* stage = nullptr;
-	char* base = nullptr;
-	if ((st = s.pinned_block(total_in, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total_in, (void**)&base, msg)) != WHAMD_OK) return st;
+	Image im;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
 	std::vector<uint64_t> read_base(n_mats + 1, 0), entry_base(n_mats + 1, 0), term_base(n_mats + 1, 0), pair_base(n_mats + 1, 0);
 	for (uint32_t u = 0; u < n_mats; u++) {
 		const PolyMatrix& m = ms[up[u]];
@@ -185,10 +180,10 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 		for (uint64_t u = b; u < e; u++) {
 			const PolyMatrix& m = ms[up[u]];
 			const uint64_t rb = read_base[u], eb = entry_base[u];
-			uint64_t* prefix = (uint64_t*)(stage + o_prefix) + rb;
-			uint32_t* order = (uint32_t*)(stage + o_order) + rb;
-			uint64_t* rowptr = (uint64_t*)(stage + o_rowptr) + rb;
-			uint32_t* amat = (uint32_t*)(stage + o_amat) + rb;
+			uint64_t* prefix = im.host(p_prefix) + rb;
+			uint32_t* order = im.host(p_order) + rb;
+			uint64_t* rowptr = im.host(p_rowptr) + rb;
+			uint32_t* amat = im.host(p_amat) + rb;
 			uint64_t acc = pair_base[u];
 			for (uint32_t k = 0; k < m.n_reads; k++) {
 				prefix[k] = acc;
@@ -198,17 +193,17 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 				amat[k] = (uint32_t)u;
 			}
 			if (!m.row_pos.empty()) {
-				std::memcpy((uint32_t*)(stage + o_pos) + eb, m.row_pos.data(), m.row_pos.size() * 4);
-				std::memcpy((uint8_t*)(stage + o_all) + eb, m.row_allele.data(), m.row_allele.size());
+				std::memcpy(im.host(p_pos) + eb, m.row_pos.data(), m.row_pos.size() * 4);
+				std::memcpy(im.host(p_all) + eb, m.row_allele.data(), m.row_allele.size());
 			}
-			std::memcpy((float*)(stage + o_terms) + term_base[u], m.terms.data(), m.terms.size() * 4);
-			((uint64_t*)(stage + o_toff))[u] = term_base[u];
-			((uint32_t*)(stage + o_na))[u] = m.max_allele;
+			std::memcpy(im.host(p_terms) + term_base[u], m.terms.data(), m.terms.size() * 4);
+			im.host(p_toff)[u] = term_base[u];
+			im.host(p_na)[u] = m.max_allele;
 		}
 	});
-	((uint64_t*)(stage + o_prefix))[N] = n_pairs;
-	((uint64_t*)(stage + o_rowptr))[N] = n_entries;
-	std::memset(stage + o_counts, 0, n_mats * 24);
+	im.host(p_prefix)[N] = n_pairs;
+	im.host(p_rowptr)[N] = n_entries;
+	std::memset(im.host(p_counts), 0, p_counts.bytes());
 	// pair buffers
 	float* score = nullptr;
 	uint32_t *keep = nullptr, *slot = nullptr;
@@ -220,38 +215,38 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	void* scan_buf = nullptr;
 	if ((st = s.device_block(scan_tmp, &scan_buf, msg)) != WHAMD_OK) return st;
 	uint32_t* tail = nullptr;   // pinned: keep and slot of the last pair, then the counts
-	if ((st = s.pinned_block(8 + n_mats * 24, (void**)&tail, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(8 + p_counts.bytes(), (void**)&tail, msg)) != WHAMD_OK) return st;
 
 	PairArgs pa{};
 	pa.n_pairs = n_pairs;
 	pa.n_anchors = N;
-	pa.pair_prefix = (const uint64_t*)(base + o_prefix);
-	pa.order = (const uint32_t*)(base + o_order);
-	pa.row_ptr = (const uint64_t*)(base + o_rowptr);
-	pa.row_pos = (const uint32_t*)(base + o_pos);
-	pa.row_allele = (const uint8_t*)(base + o_all);
-	pa.anchor_mat = (const uint32_t*)(base + o_amat);
-	pa.mat_term_off = (const uint64_t*)(base + o_toff);
-	pa.mat_alleles = (const uint32_t*)(base + o_na);
-	pa.terms = (const float*)(base + o_terms);
+	pa.pair_prefix = im.dev(p_prefix);
+	pa.order = im.dev(p_order);
+	pa.row_ptr = im.dev(p_rowptr);
+	pa.row_pos = im.dev(p_pos);
+	pa.row_allele = im.dev(p_all);
+	pa.anchor_mat = im.dev(p_amat);
+	pa.mat_term_off = im.dev(p_toff);
+	pa.mat_alleles = im.dev(p_na);
+	pa.terms = im.dev(p_terms);
 	pa.min_overlap = min_overlap;
 	pa.offset = offset;
 	pa.score = score;
 	pa.keep = keep;
-	pa.counts = (unsigned long long*)(base + o_counts);
+	pa.counts = im.dev_out(p_counts);
 	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pairs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
 
-	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-	HIP_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
 	hipLaunchKernelGGL(poly_pair_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, pa);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(rocprim::exclusive_scan(scan_buf, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
-	HIP_TRY(hipMemcpyAsync(tail, keep + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipMemcpyAsync(tail + 1, slot + (n_pairs - 1), 4, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipMemcpyAsync(tail + 2, base + o_counts, n_mats * 24, hipMemcpyDeviceToHost, s.stream));
+	// the number of kept pairs sizes what follows: three small results come down in the middle of the kernel phase, and the host waits for them
+	// (Session's steps have no such wait: it is this call's alone)
+	if ((st = s.fetch(tail, keep + (n_pairs - 1), 4, msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(tail + 1, slot + (n_pairs - 1), 4, msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(tail + 2, im.dev(p_counts), p_counts.bytes(), msg)) != WHAMD_OK) return st;
 	HIP_TRY(hipStreamSynchronize(s.stream));
-	*launches = 2;
+	times.launches = 2;
 	const uint64_t n_kept = (uint64_t)tail[0] + tail[1];
 	const unsigned long long* counts = (const unsigned long long*)(tail + 2);
 	for (uint32_t u = 0; u < n_mats; u++) {
@@ -259,7 +254,6 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 		out[up[u]].n_nan = counts[3 * u + 1];
 		out[up[u]].n_pair_positions = counts[3 * u + 2];
 	}
-	float dl_ms = 0.0f;
 	if (n_kept) {
 		uint64_t *key = nullptr, *key2 = nullptr;
 		float *val = nullptr, *val2 = nullptr;
@@ -280,14 +274,11 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 		hipLaunchKernelGGL(poly_compact_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, ca);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(rocprim::radix_sort_pairs(sort_buf, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
-		HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-		HIP_TRY(hipMemcpyAsync(res, key2, n_kept * 8, hipMemcpyDeviceToHost, s.stream));
-		HIP_TRY(hipMemcpyAsync(res + n_kept * 8, val2, n_kept * 4, hipMemcpyDeviceToHost, s.stream));
-		HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-		HIP_TRY(hipStreamSynchronize(s.stream));
-		*launches = 4;
-		dl_ms = (float)s.ms(2, 3);
-		*kernel_ms = s.ms(1, 2);
+		if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+		if ((st = s.fetch(res, key2, n_kept * 8, msg)) != WHAMD_OK) return st;
+		if ((st = s.fetch(res + n_kept * 8, val2, n_kept * 4, msg)) != WHAMD_OK) return st;
+		if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+		times.launches = 4;
 		// per matrix: its keys form one contiguous range (global ids of matrix u are read_base[u] ..)
 		const uint64_t* keys = (const uint64_t*)res;
 		const float* vals = (const float*)(res + n_kept * 8);
@@ -307,13 +298,10 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 				}
 			}
 		});
-	} else {
-		HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-		HIP_TRY(hipStreamSynchronize(s.stream));
-		*kernel_ms = s.ms(1, 2);
+	} else {   // nothing kept, nothing more to fetch
+		if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+		if ((st = s.finish(times, msg, false)) != WHAMD_OK) return st;
 	}
-	*upload_ms = s.ms(0, 1);
-	*download_ms = dl_ms;
 	return WHAMD_OK;
 }
 

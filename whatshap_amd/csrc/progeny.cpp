@@ -4,41 +4,17 @@
 #include "progeny.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <limits>
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
+#include "api_guard.h"
 #include "debug_build.h"
-
-namespace whamd {
-void set_last_error(const std::string& msg);   // c_api.cpp
-}
 
 using namespace whamd;
 
 namespace {
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-whamd_status_t fail(whamd_status_t st, const std::string& msg) {
-	set_last_error(msg);
-	return st;
-}
-
-template <class F>
-whamd_status_t guarded(F&& body) {
-	try {
-		return body();
-	} catch (const std::bad_alloc&) {
-		return fail(WHAMD_ERR_HOST, "out of host memory");
-	} catch (const std::exception& e) {
-		return fail(WHAMD_ERR_HOST, std::string("host-side failure: ") + e.what());
-	} catch (...) {
-		return fail(WHAMD_ERR_HOST, "host-side failure");
-	}
-}
 
 constexpr uint64_t NO_ERROR = std::numeric_limits<uint64_t>::max();
 
@@ -298,14 +274,13 @@ whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bo
 		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
 	}
 	const double t1 = now_ms();
-	double up = 0, kern = 0, down = 0;
-	uint32_t launches = 0;
+	CallTimes times;
 	if (host) {
 #ifdef WHAMD_DEBUG_BUILD
 		for (uint64_t x = 0; x < n; x++) progeny_score_host(r->problems[x], r->results[x]);
 #endif
 	} else {
-		const whamd_status_t st = progeny_score_device(r->problems, device, r->results, &up, &kern, &down, &launches, msg);
+		const whamd_status_t st = progeny_score_device(r->problems, device, r->results, times, msg);
 		if (st != WHAMD_OK) return fail(st, msg);
 	}
 	const double t2 = now_ms();
@@ -317,11 +292,11 @@ whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bo
 		s.n_inf = p.n_inf;
 		s.n_reused = p.n_reused;
 		s.n_sample_terms = (p.lo.size() - p.n_inf) * (uint64_t)p.n_samples;
-		s.launches = launches;
+		s.launches = times.launches;
 		s.host_ms = t1 - t0;
-		s.upload_ms = up;
-		s.kernel_ms = kern;
-		s.download_ms = down;
+		s.upload_ms = times.upload_ms;
+		s.kernel_ms = times.kernel_ms;
+		s.download_ms = times.download_ms;
 		s.total_ms = t2 - t0;
 	}
 	*out = r.release();

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
+#include "call_image.h"
 #include "host_parallel.h"
 
 #if defined(__HIPCC__)
@@ -116,9 +117,9 @@ inline const float* progeny_row(const ProgenyProblem& p, uint64_t node, const fl
 }
 
 // The device pair loop for a batch: one upload, one launch, one download.  Problems whose entries are all -inf (or that have none) are not
-// uploaded; with nothing to compute nothing touches the device (*launches = 0).
-whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int device, std::vector<ProgenyResult>& out, double* upload_ms,
-                                    double* kernel_ms, double* download_ms, uint32_t* launches, std::string& msg);
+// uploaded; with nothing to compute nothing touches the device (times.launches = 0).
+whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int device, std::vector<ProgenyResult>& out, CallTimes& times,
+                                    std::string& msg);
 
 // llh[n][(k+1)(k+2)/2] of rows[n][n_samples][k+1] (gathered by the caller) under prior[(k+1)(k+2)/2][k+1] (types in loop order g0, g1 <= g0).
 whamd_status_t progeny_types_device(const float* rows, uint64_t n, uint32_t n_samples, uint32_t k1, const double* prior, int device, double* llh,

@@ -9,6 +9,7 @@
 //             the same code as the host twin -- so nothing is reduced across lanes and no sum is reordered.
 //   download  one double per entry; the float score is its rounding, taken on the host.
 // progeny_types_kernel: one lane per (variant, parental type), samples in order (progeny_type_llh); the argmax is taken on the host.
+// Both calls: the upload is one image of typed pieces (call_image.h), the call runs through the steps of Session (device_runtime.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,14 +85,11 @@ __global__ void __launch_bounds__(BLOCK) progeny_types_kernel(TypesKernelArgs a)
 	}
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
-whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int device, std::vector<ProgenyResult>& out, double* upload_ms,
-                                    double* kernel_ms, double* download_ms, uint32_t* launches, std::string& msg) {
-	*upload_ms = *kernel_ms = *download_ms = 0.0;
-	*launches = 0;
+whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int device, std::vector<ProgenyResult>& out, CallTimes& times,
+                                    std::string& msg) {
+	times = CallTimes{};
 	out.assign(ps.size(), ProgenyResult{});
 	// problems with something to compute go up; the others hold -inf entries only (or none) and are filled here
 	std::vector<uint32_t> up;
@@ -118,29 +116,26 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 		if (p.n_samples)
 			for (uint64_t node0 = 0; node0 < p.n_nodes; node0 += PACK_NODES) jobs.push_back(PackJob{u, node0});
 	}
-	// staging layout (one upload)
-	size_t o = 0;
-	const size_t o_prefix = o; o = align_up(o + (n_up + 1) * 8);
-	const size_t o_desc = o; o = align_up(o + n_up * sizeof(DevProblem));
-	const size_t o_lo = o; o = align_up(o + n_entries * 4);
-	const size_t o_eff = o; o = align_up(o + n_entries * 4);
-	const size_t o_kind = o; o = align_up(o + n_entries);
-	const size_t o_table = o; o = align_up(o + std::max<uint64_t>(n_floats, 1) * 4);
-	const size_t total_in = o;
+	// the image (one upload)
+	ImageLayout in;
+	const auto p_prefix = in.add<uint64_t>(n_up + 1);
+	const auto p_desc = in.add<DevProblem>(n_up);
+	const auto p_lo = in.add<uint32_t>(n_entries);
+	const auto p_eff = in.add<uint32_t>(n_entries);
+	const auto p_kind = in.add<uint8_t>(n_entries);
+	const auto p_table = in.add<float>(std::max<uint64_t>(n_floats, 1));
 	Session s;
 	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
-	char* stage = nullptr;
-	char* base = nullptr;
+	Image im;
 	double* score = nullptr;
 	double* res = nullptr;
-	if ((st = s.pinned_block(total_in, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total_in, (void**)&base, msg)) != WHAMD_OK) return st;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
 	if ((st = s.device_block(n_entries * 8, (void**)&score, msg)) != WHAMD_OK) return st;
 	if ((st = s.pinned_block(n_entries * 8, (void**)&res, msg)) != WHAMD_OK) return st;
 	for (uint32_t u = 0; u < n_up; u++) {
 		const ProgenyProblem& p = ps[up[u]];
-		((uint64_t*)(stage + o_prefix))[u] = entry_base[u];
+		im.host(p_prefix)[u] = entry_base[u];
 		DevProblem d{};
 		d.table_off = table_base[u];
 		d.n_nodes = (uint32_t)p.n_nodes;
@@ -148,14 +143,14 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 		d.start = p.w.start;
 		std::memcpy(d.same, p.w.same, sizeof(d.same));
 		std::memcpy(d.diff, p.w.diff, sizeof(d.diff));
-		std::memcpy(stage + o_desc + u * sizeof(DevProblem), &d, sizeof(d));
+		im.host(p_desc)[u] = d;
 	}
-	((uint64_t*)(stage + o_prefix))[n_up] = n_entries;
+	im.host(p_prefix)[n_up] = n_entries;
 	for (uint32_t u = 0; u < n_up; u++) {
 		const ProgenyProblem& p = ps[up[u]];
-		progeny_copy((uint32_t*)(stage + o_lo) + entry_base[u], p.lo.data(), p.lo.size() * 4);
-		progeny_copy((uint32_t*)(stage + o_eff) + entry_base[u], p.eff.data(), p.eff.size() * 4);
-		progeny_copy((uint8_t*)(stage + o_kind) + entry_base[u], p.kind.data(), p.kind.size());
+		progeny_copy(im.host(p_lo) + entry_base[u], p.lo.data(), p.lo.size() * 4);
+		progeny_copy(im.host(p_eff) + entry_base[u], p.eff.data(), p.eff.size() * 4);
+		progeny_copy(im.host(p_kind) + entry_base[u], p.kind.data(), p.kind.size());
 	}
 	// the repack: a block of nodes at a time (its rows stay in the host cache while every plane takes its piece)
 	parallel_ranges(jobs.size(), host_threads(n_floats, 1 << 18), [&](uint64_t b, uint64_t e, uint32_t) {
@@ -163,7 +158,7 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 			const ProgenyProblem& p = ps[up[jobs[x].u]];
 			const uint64_t node0 = jobs[x].node0, node1 = std::min<uint64_t>(node0 + PACK_NODES, p.n_nodes);
 			const uint64_t k1 = p.ploidy + 1, row = (uint64_t)p.n_samples * k1;
-			float* t = (float*)(stage + o_table) + table_base[jobs[x].u];
+			float* t = im.host(p_table) + table_base[jobs[x].u];
 			const uint64_t have = std::min<uint64_t>(node1, std::max<uint64_t>(p.n_positions, node0));   // nodes [node0, have) have rows
 			for (uint64_t sm = 0; sm < p.n_samples; sm++) {
 				for (uint32_t g = 0; g < 3; g++) {
@@ -179,27 +174,21 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 	PairArgs pa{};
 	pa.n_entries = n_entries;
 	pa.n_problems = n_up;
-	pa.entry_prefix = (const uint64_t*)(base + o_prefix);
-	pa.problems = (const DevProblem*)(base + o_desc);
-	pa.lo = (const uint32_t*)(base + o_lo);
-	pa.eff = (const uint32_t*)(base + o_eff);
-	pa.kind = (const uint8_t*)(base + o_kind);
-	pa.table = (const float*)(base + o_table);
+	pa.entry_prefix = im.dev(p_prefix);
+	pa.problems = im.dev(p_desc);
+	pa.lo = im.dev(p_lo);
+	pa.eff = im.dev(p_eff);
+	pa.kind = im.dev(p_kind);
+	pa.table = im.dev(p_table);
 	pa.score = score;
 	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_entries + BLOCK - 1) / BLOCK, MAX_BLOCKS);
-	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-	HIP_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
 	hipLaunchKernelGGL(progeny_pair_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, pa);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-	HIP_TRY(hipMemcpyAsync(res, score, n_entries * 8, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	*launches = 1;
-	*upload_ms = s.ms(0, 1);
-	*kernel_ms = s.ms(1, 2);
-	*download_ms = s.ms(2, 3);
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res, score, n_entries * 8, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	times.launches = 1;
 	for (uint32_t u = 0; u < n_up; u++) {
 		RawVec<double>& dst = out[up[u]].score;
 		dst.resize(entry_base[u + 1] - entry_base[u]);
@@ -213,30 +202,28 @@ whamd_status_t progeny_types_device(const float* rows, uint64_t n, uint32_t n_sa
 	const uint32_t n_types = k1 * (k1 + 1) / 2;
 	const uint64_t n_lanes = n * n_types;
 	if (!n_lanes) return WHAMD_OK;
-	size_t o = 0;
-	const size_t o_prior = o; o = align_up(o + (size_t)n_types * k1 * 8);
-	const size_t o_rows = o; o = align_up(o + n * n_samples * k1 * 4);
-	const size_t total_in = o;
+	ImageLayout in;
+	const auto p_prior = in.add<double>((size_t)n_types * k1);
+	const auto p_rows = in.add<float>(n * n_samples * k1);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
+	whamd_status_t st = s.open(device, 0, msg);   // (no events: the call reports no times)
 	if (st != WHAMD_OK) return st;
-	char* stage = nullptr;
-	char* base = nullptr;
+	Image im;
 	double* out = nullptr;
 	double* res = nullptr;
-	if ((st = s.pinned_block(total_in, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total_in, (void**)&base, msg)) != WHAMD_OK) return st;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
 	if ((st = s.device_block(n_lanes * 8, (void**)&out, msg)) != WHAMD_OK) return st;
 	if ((st = s.pinned_block(n_lanes * 8, (void**)&res, msg)) != WHAMD_OK) return st;
-	std::memcpy(stage + o_prior, prior, (size_t)n_types * k1 * 8);
-	std::memcpy(stage + o_rows, rows, n * n_samples * k1 * 4);
-	TypesKernelArgs ta{n_lanes, n_types, n_samples, k1, (const float*)(base + o_rows), (const double*)(base + o_prior), out};
+	std::memcpy(im.host(p_prior), prior, p_prior.bytes());
+	std::memcpy(im.host(p_rows), rows, p_rows.bytes());
+	TypesKernelArgs ta{n_lanes, n_types, n_samples, k1, im.dev(p_rows), im.dev(p_prior), out};
 	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_lanes + BLOCK - 1) / BLOCK, MAX_BLOCKS);
-	HIP_TRY(hipMemcpyAsync(base, stage, total_in, hipMemcpyHostToDevice, s.stream));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
 	hipLaunchKernelGGL(progeny_types_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, ta);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(res, out, n_lanes * 8, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipStreamSynchronize(s.stream));
+	CallTimes unused;
+	if ((st = s.fetch(res, out, n_lanes * 8, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(unused, msg)) != WHAMD_OK) return st;
 	std::memcpy(llh, res, n_lanes * 8);
 	return WHAMD_OK;
 }

@@ -30,10 +30,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
-
-namespace whamd {
-void set_last_error(const std::string& msg);
-}
+#include "api_guard.h"
 
 namespace {
 

@@ -5,22 +5,16 @@
 #include "realign.h"
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstring>
 #include <vector>
 
+#include "api_guard.h"
 #include "debug_build.h"
-
-namespace whamd {
-void set_last_error(const std::string& msg);   // c_api.cpp
-}
 
 using namespace whamd;
 
 namespace {
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 bool is_match_op(uint32_t op) { return op == 0 || op == 7 || op == 8; }   // M, =, X
 
@@ -183,24 +177,6 @@ struct Walker {
 		return ok;
 	}
 };
-
-whamd_status_t fail(whamd_status_t st, const std::string& msg) {
-	set_last_error(msg);
-	return st;
-}
-
-template <class F>
-whamd_status_t guarded(F&& body) {
-	try {
-		return body();
-	} catch (const std::bad_alloc&) {
-		return fail(WHAMD_ERR_HOST, "out of host memory");
-	} catch (const std::exception& e) {
-		return fail(WHAMD_ERR_HOST, std::string("host-side failure: ") + e.what());
-	} catch (...) {
-		return fail(WHAMD_ERR_HOST, "host-side failure (unknown exception)");
-	}
-}
 
 }  // namespace
 
@@ -449,9 +425,12 @@ whamd_status_t detect(const whamd_realign_alignments_view* alignments, const wha
 		}
 #endif
 	} else if (b.n_jobs) {
-		st = realign_device(b, device, allele.data(), params->use_affine ? quality.data() : nullptr, &r->stats.upload_ms, &r->stats.kernel_ms,
-		                    &r->stats.download_ms, msg);
+		CallTimes times;
+		st = realign_device(b, device, allele.data(), params->use_affine ? quality.data() : nullptr, times, msg);
 		if (st != WHAMD_OK) return fail(st, msg);
+		r->stats.upload_ms = times.upload_ms;
+		r->stats.kernel_ms = times.kernel_ms;
+		r->stats.download_ms = times.download_ms;
 	}
 	const double t2 = now_ms();
 	compact(b, alignments->n_alignments, allele.data(), params->use_affine ? quality.data() : nullptr, *r);

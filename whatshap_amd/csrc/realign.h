@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/whatshap_amd.h"
+#include "call_image.h"
 #include "host_parallel.h"
 
 namespace whamd {
@@ -97,8 +98,8 @@ whamd_status_t realign_walk(const whamd_realign_alignments_view& al, const whamd
 
 // Distances and decisions on `device` (realign_device.hip): allele_out[job] = the detected allele or -1, quality_out[job] (affine: d0 - d1 or
 // d0; unit: 30).  Times in ms of HIP events.
-whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, double* upload_ms,
-                              double* kernel_ms, double* download_ms, std::string& msg);
+whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, CallTimes& times,
+                              std::string& msg);
 
 whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr, const uint8_t* query, const uint64_t* target_ptr,
                                     const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start, int32_t gap_extend,

@@ -17,6 +17,8 @@
 //   decision      realign (variants.py:866-891): distances of the allowed alleles in index order, stable order by distance, the first
 //                 allele iff it is alone or strictly best; quality 30 (unit) or d0 - d1 / d0 (affine).
 // Only the per-job result (allele or -1, and the quality in affine mode) goes back to the host.
+// Both host drivers at the end lay their arrays out as one image (call_image.h: typed pieces, one upload) and run through the steps of
+// Session (device_runtime.h: stage, upload, kernels_done, fetch, finish); the raw distance batch keeps its result piece inside the image.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -297,8 +299,6 @@ constexpr uint32_t BLOCK = 256, MAX_BLOCKS = 8192, MAX_LONG_BLOCKS = 1024;
 constexpr size_t LDS_LIMIT = 64 << 10;
 constexpr size_t SCRATCH_BUDGET = (size_t)512 << 20;   // scratch rows of the long-job launch: the grid shrinks to stay within this (at least one block)
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Launch shape of the jobs with a query longer than 64 whose longest allele window is `max_target` bytes.
 struct LongShape {
 	uint32_t blocks = 0, block = 64;
@@ -333,63 +333,65 @@ LongShape long_shape(bool affine, uint64_t n_long, uint32_t max_target) {
 
 }  // namespace
 
-whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, double* upload_ms, double* kernel_ms,
-                              double* download_ms, std::string& msg) {
+whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, CallTimes& times, std::string& msg) {
 	Session s;
 	whamd_status_t st = s.open(device, 4, msg);
 	if (st != WHAMD_OK) return st;
 	const bool affine = b.params.use_affine != 0;
-	// one staging image, one device block: jobs | query windows | long jobs | variants | allowed alleles | alt offsets | alt bytes | reference slice
-	const size_t o_jobs = 0, o_q = align_up(o_jobs + b.n_jobs * sizeof(RealignJob)), o_long = align_up(o_q + b.n_query_bytes);
-	const size_t o_var = align_up(o_long + b.n_long * 4);
-	const size_t o_allow = align_up(o_var + b.variants.size() * sizeof(RealignVariant)), o_alt = align_up(o_allow + b.allow.size() * 4);
-	const size_t o_altb = align_up(o_alt + b.alt_off.size() * 8), o_ref = align_up(o_altb + b.n_alt_bytes), total = align_up(o_ref + b.ref_len);
-	char* stage = nullptr;
-	char* base = nullptr;
-	if ((st = s.pinned_block(total, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total, (void**)&base, msg)) != WHAMD_OK) return st;
+	// one image: jobs | query windows | long jobs | variants | allowed alleles | alt offsets | alt bytes | reference slice
+	ImageLayout in;
+	const auto p_jobs = in.add<RealignJob>(b.n_jobs);
+	const auto p_q = in.add<uint8_t>(b.n_query_bytes);
+	const auto p_long = in.add<uint32_t>(b.n_long);
+	const auto p_var = in.add<RealignVariant>(b.variants.size());
+	const auto p_allow = in.add<uint32_t>(b.allow.size());
+	const auto p_alt = in.add<uint64_t>(b.alt_off.size());
+	const auto p_altb = in.add<uint8_t>(b.n_alt_bytes);
+	const auto p_ref = in.add<uint8_t>(b.ref_len);
+	Image im;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
 	const uint32_t n_ranges = (uint32_t)b.range_jobs.size();
 	parallel_ranges(n_ranges + 1, host_threads(n_ranges + 1, 1), [&](uint64_t begin, uint64_t end, uint32_t) {
 		for (uint64_t r = begin; r < end; ++r) {
 			if (r == n_ranges) {   // the small tables and the reference slice
-				if (!b.variants.empty()) std::memcpy(stage + o_var, b.variants.data(), b.variants.size() * sizeof(RealignVariant));
-				if (!b.allow.empty()) std::memcpy(stage + o_allow, b.allow.data(), b.allow.size() * 4);
-				std::memcpy(stage + o_alt, b.alt_off.data(), b.alt_off.size() * 8);
-				if (b.n_alt_bytes) std::memcpy(stage + o_altb, b.alt_bytes, b.n_alt_bytes);
-				if (b.ref_len) std::memcpy(stage + o_ref, b.ref, b.ref_len);
+				if (!b.variants.empty()) std::memcpy(im.host(p_var), b.variants.data(), p_var.bytes());
+				if (!b.allow.empty()) std::memcpy(im.host(p_allow), b.allow.data(), p_allow.bytes());
+				std::memcpy(im.host(p_alt), b.alt_off.data(), p_alt.bytes());
+				if (b.n_alt_bytes) std::memcpy(im.host(p_altb), b.alt_bytes, b.n_alt_bytes);
+				if (b.ref_len) std::memcpy(im.host(p_ref), b.ref, b.ref_len);
 				continue;
 			}
-			RealignJob* dst = (RealignJob*)(stage + o_jobs) + b.range_job_base[r];
+			RealignJob* dst = im.host(p_jobs) + b.range_job_base[r];
 			const uint64_t qbase = b.range_query_base[r];
 			for (const RealignJob& j : b.range_jobs[r]) {
 				RealignJob k = j;
 				k.q_off += qbase;
 				*dst++ = k;
 			}
-			if (!b.range_query[r].empty()) std::memcpy(stage + o_q + qbase, b.range_query[r].data(), b.range_query[r].size());
-			uint32_t* ldst = (uint32_t*)(stage + o_long) + b.range_long_base[r];
+			if (!b.range_query[r].empty()) std::memcpy(im.host(p_q) + qbase, b.range_query[r].data(), b.range_query[r].size());
+			uint32_t* ldst = im.host(p_long) + b.range_long_base[r];
 			for (uint32_t x : b.range_long[r]) *ldst++ = (uint32_t)(b.range_job_base[r] + x);
 		}
 	});
-	// results: alleles | qualities
-	const size_t r_q = align_up(b.n_jobs * 4), r_total = r_q + (affine ? b.n_jobs * 8 : 0);
-	char* res = nullptr;
-	char* hres = nullptr;
-	if ((st = s.device_block(r_total, (void**)&res, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(r_total, (void**)&hres, msg)) != WHAMD_OK) return st;
+	// the results, a second image that only comes down: alleles | qualities
+	ImageLayout out;
+	const auto p_allele = out.add<int32_t>(b.n_jobs);
+	const auto p_quality = out.add<int64_t>(affine ? b.n_jobs : 0);
+	Image res;
+	if ((st = s.stage(out, res, msg)) != WHAMD_OK) return st;
 	RealignArgs a{};
-	a.jobs = (const RealignJob*)(base + o_jobs);
-	a.qbuf = (const uint8_t*)(base + o_q);
-	a.vars = (const RealignVariant*)(base + o_var);
-	a.allow = (const uint32_t*)(base + o_allow);
-	a.alt_off = (const uint64_t*)(base + o_alt);
-	a.alt_bytes = (const uint8_t*)(base + o_altb);
-	a.ref = (const uint8_t*)(base + o_ref);
+	a.jobs = im.dev(p_jobs);
+	a.qbuf = im.dev(p_q);
+	a.vars = im.dev(p_var);
+	a.allow = im.dev(p_allow);
+	a.alt_off = im.dev(p_alt);
+	a.alt_bytes = im.dev(p_altb);
+	a.ref = im.dev(p_ref);
 	a.gap_start = b.params.gap_start;
 	a.gap_extend = b.params.gap_extend;
 	a.mismatch = b.params.default_mismatch;
-	a.allele_out = (int32_t*)res;
-	a.quality_out = affine ? (int64_t*)(res + r_q) : nullptr;
+	a.allele_out = res.dev_out(p_allele);
+	a.quality_out = affine ? res.dev_out(p_quality) : nullptr;
 	// the launch over every job with a query of at most 64 (no scratch), then the one over the long jobs
 	RealignArgs shortj = a;
 	shortj.n_items = (uint32_t)b.n_jobs;
@@ -398,7 +400,7 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 	RealignArgs longj = a;
 	const LongShape ls = long_shape(affine, b.n_long, b.max_target_long);
 	if (b.n_long) {
-		longj.subset = (const uint32_t*)(base + o_long);
+		longj.subset = im.dev(p_long);
 		longj.n_items = (uint32_t)b.n_long;
 		longj.carry_words = ls.carry_words;
 		longj.row_floats = ls.row_floats;
@@ -409,9 +411,7 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 			else longj.carry = (uint64_t*)c;
 		}
 	}
-	HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-	HIP_TRY(hipMemcpyAsync(base, stage, total, hipMemcpyHostToDevice, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
 	if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
 	else hipLaunchKernelGGL(realign_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
 	HIP_TRY(hipGetLastError());
@@ -420,15 +420,11 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 		else hipLaunchKernelGGL(realign_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longj);
 		HIP_TRY(hipGetLastError());
 	}
-	HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-	HIP_TRY(hipMemcpyAsync(hres, res, r_total, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	*upload_ms = s.ms(0, 1);
-	*kernel_ms = s.ms(1, 2);
-	*download_ms = s.ms(2, 3);
-	std::memcpy(allele_out, hres, b.n_jobs * 4);
-	if (affine) std::memcpy(quality_out, hres + r_q, b.n_jobs * 8);
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res.stage, res.base, p_quality.end(), msg)) != WHAMD_OK) return st;   // (to the last byte in use)
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	std::memcpy(allele_out, res.host(p_allele), p_allele.bytes());
+	if (affine) std::memcpy(quality_out, res.host(p_quality), p_quality.bytes());
 	return WHAMD_OK;
 }
 
@@ -447,31 +443,35 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 		}
 	}
 	Session s;
-	whamd_status_t st = s.open(device, 0, msg);
+	whamd_status_t st = s.open(device, 0, msg);   // (no events: the call reports no times)
 	if (st != WHAMD_OK) return st;
 	const uint64_t nq = query_ptr[n_pairs], nt = target_ptr[n_pairs], n_long = long_pairs.size();
-	const size_t o_qp = 0, o_tp = align_up((n_pairs + 1) * 8), o_q = align_up(o_tp + (n_pairs + 1) * 8), o_t = align_up(o_q + nq);
-	const size_t o_c = align_up(o_t + nt), o_long = align_up(o_c + (use_affine ? nq * 4 : 0)), o_out = align_up(o_long + n_long * 4);
-	const size_t total = align_up(o_out + n_pairs * 8);
-	char* stage = nullptr;
-	char* base = nullptr;
-	if ((st = s.pinned_block(total, (void**)&stage, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total, (void**)&base, msg)) != WHAMD_OK) return st;
-	std::memcpy(stage + o_qp, query_ptr, (n_pairs + 1) * 8);
-	std::memcpy(stage + o_tp, target_ptr, (n_pairs + 1) * 8);
-	if (nq) std::memcpy(stage + o_q, query, nq);
-	if (nt) std::memcpy(stage + o_t, target, nt);
-	if (use_affine && nq) std::memcpy(stage + o_c, mismatch_cost, nq * 4);
-	if (n_long) std::memcpy(stage + o_long, long_pairs.data(), n_long * 4);
+	// one image: query offsets | target offsets | queries | targets | mismatch costs | long pairs | the distances (written by the kernels: not uploaded)
+	ImageLayout in;
+	const auto p_qp = in.add<uint64_t>(n_pairs + 1);
+	const auto p_tp = in.add<uint64_t>(n_pairs + 1);
+	const auto p_q = in.add<uint8_t>(nq);
+	const auto p_t = in.add<uint8_t>(nt);
+	const auto p_c = in.add<float>(use_affine ? nq : 0);
+	const auto p_long = in.add<uint32_t>(n_long);
+	const auto p_out = in.add<int64_t>(n_pairs);
+	Image im;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	std::memcpy(im.host(p_qp), query_ptr, p_qp.bytes());
+	std::memcpy(im.host(p_tp), target_ptr, p_tp.bytes());
+	if (nq) std::memcpy(im.host(p_q), query, nq);
+	if (nt) std::memcpy(im.host(p_t), target, nt);
+	if (use_affine && nq) std::memcpy(im.host(p_c), mismatch_cost, p_c.bytes());
+	if (n_long) std::memcpy(im.host(p_long), long_pairs.data(), p_long.bytes());
 	PairArgs a{};
-	a.qptr = (const uint64_t*)(base + o_qp);
-	a.tptr = (const uint64_t*)(base + o_tp);
-	a.q = (const uint8_t*)(base + o_q);
-	a.t = (const uint8_t*)(base + o_t);
-	a.cost = (const float*)(base + o_c);
+	a.qptr = im.dev(p_qp);
+	a.tptr = im.dev(p_tp);
+	a.q = im.dev(p_q);
+	a.t = im.dev(p_t);
+	a.cost = im.dev(p_c);
 	a.gap_start = gap_start;
 	a.gap_extend = gap_extend;
-	a.out = (int64_t*)(base + o_out);
+	a.out = im.dev_out(p_out);
 	PairArgs shortp = a;
 	shortp.n_items = (uint32_t)n_pairs;
 	shortp.skip_long = n_long > 0;
@@ -479,7 +479,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 	PairArgs longp = a;
 	const LongShape ls = long_shape(use_affine != 0, n_long, max_t_long);
 	if (n_long) {
-		longp.subset = (const uint32_t*)(base + o_long);
+		longp.subset = im.dev(p_long);
 		longp.n_items = (uint32_t)n_long;
 		longp.carry_words = ls.carry_words;
 		longp.row_floats = ls.row_floats;
@@ -490,7 +490,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 			else longp.carry = (uint64_t*)c;
 		}
 	}
-	HIP_TRY(hipMemcpyAsync(base, stage, o_out, hipMemcpyHostToDevice, s.stream));
+	if ((st = s.upload(im, p_out.offset, msg)) != WHAMD_OK) return st;
 	if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
 	else hipLaunchKernelGGL(distance_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
 	HIP_TRY(hipGetLastError());
@@ -499,9 +499,10 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 		else hipLaunchKernelGGL(distance_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longp);
 		HIP_TRY(hipGetLastError());
 	}
-	HIP_TRY(hipMemcpyAsync(stage + o_out, base + o_out, n_pairs * 8, hipMemcpyDeviceToHost, s.stream));
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	std::memcpy(distance_out, stage + o_out, n_pairs * 8);
+	CallTimes unused;
+	if ((st = s.fetch(im.host(p_out), im.dev(p_out), p_out.bytes(), msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(unused, msg)) != WHAMD_OK) return st;
+	std::memcpy(distance_out, im.host(p_out), p_out.bytes());
 	return WHAMD_OK;
 }
 
