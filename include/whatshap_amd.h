@@ -599,6 +599,50 @@ void whamd_progeny_score_destroy(whamd_progeny_scores* s);
 whamd_status_t whamd_progeny_variant_types(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
                                            const uint32_t* nodes, uint64_t n_nodes, int device, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
 
+/* ---- Progeny genotype likelihoods (get_offspring_gl / compute_gt_likelihoods, whatshap/polyphase/offspringscoring.py:86-140, 232-274) ----
+ * The table the two calls above read, made on the device from allele depths.  One cell is (depth row, sample) with ref_dp, alt_dp,
+ * n = ref_dp + alt_dp: n < ploidy leaves all ploidy + 1 values at -1 (no data, the fill value of the reference's constructor); else
+ * gl[g] = w_g / sum_g w_g, w_g = p_g^alt_dp * (1 - p_g)^ref_dp * prior[g] with p_g = (1 - g / ploidy) * error_rate + (g / ploidy) *
+ * (1 - error_rate) formed in double as the reference forms it, prior = priors[row_alt_count][row_co_alt_count] (1 without priors), the sum
+ * over g = 0 .. ploidy in that order, one division per value, rounded to float as setGlv stores it.  The binomial coefficient of the
+ * reference's pmf cancels and is never formed; the powers are taken on (mantissa, exponent) pairs (csrc/progeny.h), so no depth a uint32
+ * holds underflows or overflows; a weight 1000 binades or more below the largest counts 0.  Against the exact rational value of the doubles
+ * p_g, 1.0 - p_g and prior[g]: |gl - exact| <= gamma(2n + ploidy + 1) * exact + 2^-999, gamma(m) = m 2^-53 / (1 - m 2^-53).
+ * DIVERGENCE from the reference: where every pmf underflows it raises ZeroDivisionError or returns NaN (depths of a few hundred and more);
+ * this returns the correctly normalised values.
+ * A depth row is one progeny position under one (ref allele, alt allele, parental type); the nodes of one variant share it through
+ * node_row.  One device lane per (sample, node) cell (progeny_gl_kernel, csrc/progeny_device.hip); host twin in the debug library.
+ * Errors (WHAMD_ERR_INVALID, nothing launched): ploidy < 2, error_rate outside (0, 1), with priors a row_alt_count or row_co_alt_count
+ * above the ploidy or a prior row that is negative, not finite or all zero, a node_row entry outside the rows,
+ * (n_nodes + 1) * n_samples * (ploidy + 1) >= 2^32 (the reference's uint32 index, as whamd_progeny_score). */
+typedef struct whamd_progeny_depths_view {
+	const uint32_t* ref_depth;        /* [n_samples][n_rows]: allele_depths_of(sample)[progeny position][ref allele] */
+	const uint32_t* alt_depth;        /* [n_samples][n_rows] */
+	uint64_t n_rows;
+	uint32_t n_samples;
+	uint32_t ploidy;
+	double error_rate;                /* allele_error_rate */
+	const uint32_t* row_alt_count;    /* [n_rows] parental type of the row's first node (read with priors only) */
+	const uint32_t* row_co_alt_count; /* [n_rows] */
+	uint64_t n_nodes;                 /* rows of the table */
+	const uint32_t* node_row;         /* [n_nodes] */
+	const double* priors;             /* NULL: none, else [ploidy+1][ploidy+1][ploidy+1] (compute_gt_likelihood_priors) */
+	/* whamd_progeny_score_depths only (as in whamd_progeny_view): */
+	uint32_t scoring_window;
+	const uint32_t* node_variant;     /* [n_nodes] */
+	uint64_t n_variants;
+	const uint32_t* alt_count;        /* [n_variants] */
+	const uint32_t* co_alt_count;     /* [n_variants] */
+} whamd_progeny_depths_view;
+
+/* The tables of a batch of problems: one upload, one launch, one download.  table_out / table_f64_out: NULL, or [n_problems] pointers,
+ * each NULL or the caller's array [n_nodes][n_samples][ploidy + 1] of problem m -- the float table, the doubles it was rounded from. */
+whamd_status_t whamd_progeny_gl(const whamd_progeny_depths_view* problems, uint64_t n_problems, int device, float* const* table_out,
+                                double* const* table_f64_out);
+/* whamd_progeny_score on the tables of whamd_progeny_gl without either leaving the device: one upload (depths, entry lists), two launches
+ * (progeny_gl_kernel writes the packed planes, progeny_pair_kernel reads them), one download.  Same result object, getters and stats. */
+whamd_status_t whamd_progeny_score_depths(const whamd_progeny_depths_view* problems, uint64_t n_problems, int device, whamd_progeny_scores** out);
+
 /* ---- Haplotagging (prepare_haplotag_information, whatshap/cli/haplotag.py:322-427) ------------------------------------------------------
  * The assignment step of `whatshap haplotag`: every read -- or group of linked reads -- goes to the phase set and the haplotype its alleles
  * support best.  One problem is one sample on one chromosome.  Strings stay with the caller: a read's representation (the key the

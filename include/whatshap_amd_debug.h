@@ -85,6 +85,9 @@ whamd_status_t whamd_debug_progeny_pair_score_host(const float* gl, uint64_t n_p
 /* whamd_progeny_variant_types on one CPU thread. */
 whamd_status_t whamd_debug_progeny_variant_types_host(const float* gl, uint64_t n_positions, uint32_t n_samples, uint32_t ploidy, const double* priors,
                                                       const uint32_t* nodes, uint64_t n_nodes, double* llh_out, uint32_t* g0_out, uint32_t* g1_out);
+/* whamd_progeny_gl on one CPU thread: the same validation, then csrc/progeny.h's cell function -- the code the kernel runs -- per cell. */
+whamd_status_t whamd_debug_progeny_gl_host(const whamd_progeny_depths_view* problems, uint64_t n_problems, float* const* table_out,
+                                           double* const* table_f64_out);
 
 /* HOST-ONLY DIAGNOSTICS of haplotagging (csrc/haplotag.cpp): the same validation and grouping as whamd_haplotag, then every group scored on
  * one CPU thread with the device's selection functions -- what the CPU test-suite holds to the recorded reference, identical in every

@@ -179,6 +179,14 @@ class ProgenyView(C.Structure):
                 ("co_alt_count", C.POINTER(C.c_uint32)), ("scoring_window", C.c_uint32)]
 
 
+class ProgenyDepthsView(C.Structure):
+    _fields_ = [("ref_depth", C.POINTER(C.c_uint32)), ("alt_depth", C.POINTER(C.c_uint32)), ("n_rows", C.c_uint64), ("n_samples", C.c_uint32),
+                ("ploidy", C.c_uint32), ("error_rate", C.c_double), ("row_alt_count", C.POINTER(C.c_uint32)), ("row_co_alt_count", C.POINTER(C.c_uint32)),
+                ("n_nodes", C.c_uint64), ("node_row", C.POINTER(C.c_uint32)), ("priors", C.POINTER(C.c_double)), ("scoring_window", C.c_uint32),
+                ("node_variant", C.POINTER(C.c_uint32)), ("n_variants", C.c_uint64), ("alt_count", C.POINTER(C.c_uint32)),
+                ("co_alt_count", C.POINTER(C.c_uint32))]
+
+
 class ProgenyScoreStats(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("n_nodes", "n_entries", "n_inf", "n_reused", "n_sample_terms")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
@@ -362,6 +370,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_progeny_variant_types_host.restype = C.c_int
     L.whamd_debug_progeny_variant_types_host.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                                          C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_debug_progeny_gl_host.restype = C.c_int
+    L.whamd_debug_progeny_gl_host.argtypes = [C.POINTER(ProgenyDepthsView), C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_double))]
     L.whamd_debug_haplotag_host.restype = C.c_int
     L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
@@ -512,6 +522,10 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_progeny_variant_types.restype = C.c_int
     L.whamd_progeny_variant_types.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                               C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_progeny_gl.restype = C.c_int
+    L.whamd_progeny_gl.argtypes = [C.POINTER(ProgenyDepthsView), C.c_uint64, C.c_int, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_double))]
+    L.whamd_progeny_score_depths.restype = C.c_int
+    L.whamd_progeny_score_depths.argtypes = [C.POINTER(ProgenyDepthsView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
     L.whamd_haplotag.restype = C.c_int
     L.whamd_haplotag.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
     L.whamd_haplotag_problem_count.restype = C.c_uint64
@@ -551,7 +565,7 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_score", "whamd_poly_score_matrix_count", "whamd_poly_score_count", "whamd_poly_score_get", "whamd_poly_score_get_stats",
     "whamd_poly_score_destroy", "whamd_poly_estimate_error_rate",
     "whamd_progeny_score", "whamd_progeny_score_problem_count", "whamd_progeny_score_count", "whamd_progeny_score_get", "whamd_progeny_score_get_stats",
-    "whamd_progeny_score_destroy", "whamd_progeny_variant_types",
+    "whamd_progeny_score_destroy", "whamd_progeny_variant_types", "whamd_progeny_gl", "whamd_progeny_score_depths",
     "whamd_haplotag", "whamd_haplotag_problem_count", "whamd_haplotag_count", "whamd_haplotag_get", "whamd_haplotag_bx_count", "whamd_haplotag_get_bx",
     "whamd_haplotag_get_stats", "whamd_haplotag_destroy",
 ]

@@ -1,5 +1,5 @@
 // progeny.cpp -- the host side of progeny marker scoring (progeny.h): validation, the weight vectors and stride list, the entry list
-// with the row each stored entry really reads, the C ABI of whatshap_amd.h's progeny section; and, in the debug library only, the
+// with the row each stored entry really reads, the validation of depth problems (genotype likelihoods from allele depths), the C ABI of whatshap_amd.h's progeny section; and, in the debug library only, the
 // one-thread host twins (whamd_debug_progeny_*).
 #include "progeny.h"
 
@@ -54,7 +54,7 @@ uint64_t walk_anchor(const whamd_progeny_view& v, const std::vector<uint32_t>& s
 	return NO_ERROR;
 }
 
-whamd_status_t validate(const whamd_progeny_view& v, std::string& msg) {
+whamd_status_t validate(const whamd_progeny_view& v, std::string& msg, bool needs_table = true) {
 	if (v.ploidy < 2) {
 		msg = "ploidy " + std::to_string(v.ploidy) + " below 2: the reference's start value is log(1 / (ploidy - 1))";
 		return WHAMD_ERR_INVALID;
@@ -67,7 +67,7 @@ whamd_status_t validate(const whamd_progeny_view& v, std::string& msg) {
 		msg = "scoring_window " + std::to_string(v.scoring_window) + " below 4: the reference's stride list is undefined there (it raises IndexError)";
 		return WHAMD_ERR_INVALID;
 	}
-	if (v.n_samples && v.n_positions && !v.gl) {
+	if (needs_table && v.n_samples && v.n_positions && !v.gl) {
 		msg = "null table";
 		return WHAMD_ERR_INVALID;
 	}
@@ -156,8 +156,8 @@ std::vector<uint32_t> whamd::progeny_strides(uint32_t w) {
 }
 
 // ---------------------------------------------------------------------------------------------- the entry list
-whamd_status_t whamd::progeny_prepare(const whamd_progeny_view& v, ProgenyProblem& p, std::string& msg) {
-	const whamd_status_t st = validate(v, msg);
+whamd_status_t whamd::progeny_prepare(const whamd_progeny_view& v, ProgenyProblem& p, std::string& msg, bool needs_table) {
+	const whamd_status_t st = validate(v, msg, needs_table);
 	if (st != WHAMD_OK) return st;
 	p.gl = v.gl;
 	p.n_positions = v.n_positions;
@@ -232,6 +232,75 @@ whamd_status_t whamd::progeny_prepare(const whamd_progeny_view& v, ProgenyProble
 	return WHAMD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- depth problems
+whamd_status_t whamd::progeny_depths_prepare(const whamd_progeny_depths_view& v, ProgenyDepths& d, std::string& msg) {
+	if (v.ploidy < 2) {
+		msg = "ploidy " + std::to_string(v.ploidy) + " below 2";
+		return WHAMD_ERR_INVALID;
+	}
+	if (!(v.error_rate > 0.0 && v.error_rate < 1.0)) {
+		msg = "error_rate " + std::to_string(v.error_rate) + " outside (0, 1)";
+		return WHAMD_ERR_INVALID;
+	}
+	if ((v.n_rows && v.n_samples && (!v.ref_depth || !v.alt_depth)) || (v.n_nodes && !v.node_row) ||
+	    (v.priors && v.n_rows && (!v.row_alt_count || !v.row_co_alt_count))) {
+		msg = "null argument";
+		return WHAMD_ERR_INVALID;
+	}
+	// the table has n_nodes rows: the guard of the score call (getIndex is uint32 arithmetic, the constructor sizes for one row more)
+	const long double cells = ((long double)v.n_nodes + 1) * v.n_samples * ((long double)v.ploidy + 1);
+	if (cells >= 4294967296.0L) {
+		msg = "(n_nodes + 1) * n_samples * (ploidy + 1) reaches 2^32: the reference's uint32 index would wrap";
+		return WHAMD_ERR_INVALID;
+	}
+	if (v.n_rows >= 0xffffffffull) {
+		msg = "more than 2^32 - 2 depth rows";
+		return WHAMD_ERR_INVALID;
+	}
+	for (uint64_t x = 0; x < v.n_nodes; x++) {
+		if (v.node_row[x] >= v.n_rows) {
+			msg = "node " + std::to_string(x) + " names depth row " + std::to_string(v.node_row[x]) + ", but only " + std::to_string(v.n_rows) + " rows were given";
+			return WHAMD_ERR_INVALID;
+		}
+	}
+	d.ref = v.ref_depth;
+	d.alt = v.alt_depth;
+	d.n_rows = v.n_rows;
+	d.n_nodes = v.n_nodes;
+	d.n_samples = v.n_samples;
+	d.ploidy = v.ploidy;
+	d.error_rate = v.error_rate;
+	d.node_row = v.node_row;
+	d.priors = v.priors;
+	d.row_prior.clear();
+	if (v.priors) {
+		const uint64_t k1 = (uint64_t)v.ploidy + 1;
+		d.row_prior.resize(v.n_rows);
+		for (uint64_t r = 0; r < v.n_rows; r++) {
+			const uint32_t alt = v.row_alt_count[r], co = v.row_co_alt_count[r];
+			if (alt > v.ploidy || co > v.ploidy) {
+				msg = "depth row " + std::to_string(r) + " has (alt_count, co_alt_count) = (" + std::to_string(alt) + ", " + std::to_string(co) +
+				      "), above the ploidy " + std::to_string(v.ploidy) + ": the priors have no such row";
+				return WHAMD_ERR_INVALID;
+			}
+			const uint64_t first = (alt * k1 + co) * k1;
+			bool positive = false, bad = false;
+			for (uint64_t g = 0; g < k1; g++) {
+				const double p = v.priors[first + g];
+				bad = bad || !(p >= 0.0) || std::isinf(p);
+				positive = positive || p > 0.0;
+			}
+			if (bad || !positive) {
+				msg = "priors[" + std::to_string(alt) + "][" + std::to_string(co) + "] (depth row " + std::to_string(r) +
+				      ") is negative, not finite or all zero: the likelihoods cannot be normalised";
+				return WHAMD_ERR_INVALID;
+			}
+			d.row_prior[r] = (uint32_t)first;
+		}
+	}
+	return WHAMD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- host twins (debug library)
 #ifdef WHAMD_DEBUG_BUILD
 namespace {
@@ -248,6 +317,19 @@ void progeny_score_host(const ProgenyProblem& p, ProgenyResult& out) {
 	for (size_t x = 0; x < p.lo.size(); x++) out.score[x] = entry_score_host(p, p.lo[x], p.eff[x], p.kind[x], zero_row.data());
 }
 
+// progeny_gl_kernel's loop on one thread: the same cell function on the caller's arrays.
+void progeny_gl_host(const ProgenyDepths& d, float* table, double* table_f64) {
+	const uint64_t k1 = (uint64_t)d.ploidy + 1;
+	for (uint64_t node = 0; node < d.n_nodes; node++) {
+		const uint32_t row = d.node_row[node];
+		for (uint64_t s = 0; s < d.n_samples; s++) {
+			const uint64_t w = s * d.n_rows + row, v = (node * d.n_samples + s) * k1;
+			progeny_gl_cell(d.ref[w], d.alt[w], d.ploidy, d.error_rate, d.priors ? d.priors + d.row_prior[row] : nullptr, nullptr, 0,
+			                table ? table + v : nullptr, table_f64 ? table_f64 + v : nullptr);
+		}
+	}
+}
+
 }  // namespace
 #endif
 
@@ -259,6 +341,25 @@ struct whamd_progeny_scores {
 };
 
 namespace {
+
+// Counts and times of a finished call into its stats.
+void fill_stats(whamd_progeny_scores& r, const CallTimes& times, double t0, double t1, double t2) {
+	for (size_t x = 0; x < r.problems.size(); x++) {
+		const ProgenyProblem& p = r.problems[x];
+		whamd_progeny_score_stats& s = r.stats[x];
+		s.n_nodes = p.n_nodes;
+		s.n_entries = p.lo.size();
+		s.n_inf = p.n_inf;
+		s.n_reused = p.n_reused;
+		s.n_sample_terms = (p.lo.size() - p.n_inf) * (uint64_t)p.n_samples;
+		s.launches = times.launches;
+		s.host_ms = t1 - t0;
+		s.upload_ms = times.upload_ms;
+		s.kernel_ms = times.kernel_ms;
+		s.download_ms = times.download_ms;
+		s.total_ms = t2 - t0;
+	}
+}
 
 whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bool host, whamd_progeny_scores** out) {
 	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
@@ -283,22 +384,63 @@ whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bo
 		const whamd_status_t st = progeny_score_device(r->problems, device, r->results, times, msg);
 		if (st != WHAMD_OK) return fail(st, msg);
 	}
-	const double t2 = now_ms();
+	fill_stats(*r, times, t0, t1, now_ms());
+	*out = r.release();
+	return WHAMD_OK;
+}
+
+whamd_status_t prepare_depths(const whamd_progeny_depths_view* views, uint64_t n, std::vector<ProgenyDepths>& ds, std::string& msg) {
+	ds.resize(n);
 	for (uint64_t x = 0; x < n; x++) {
-		const ProgenyProblem& p = r->problems[x];
-		whamd_progeny_score_stats& s = r->stats[x];
-		s.n_nodes = p.n_nodes;
-		s.n_entries = p.lo.size();
-		s.n_inf = p.n_inf;
-		s.n_reused = p.n_reused;
-		s.n_sample_terms = (p.lo.size() - p.n_inf) * (uint64_t)p.n_samples;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
+		const whamd_status_t st = progeny_depths_prepare(views[x], ds[x], msg);
+		if (st != WHAMD_OK) {
+			if (n > 1) msg = "problem " + std::to_string(x) + ": " + msg;
+			return st;
+		}
 	}
+	return WHAMD_OK;
+}
+
+whamd_status_t gl(const whamd_progeny_depths_view* views, uint64_t n, int device, bool host, float* const* table_out, double* const* table_f64_out) {
+	if (n && !views) return fail(WHAMD_ERR_INVALID, "null argument");
+	std::vector<ProgenyDepths> ds;
+	std::string msg;
+	whamd_status_t st = prepare_depths(views, n, ds, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	if (host) {
+#ifdef WHAMD_DEBUG_BUILD
+		for (uint64_t x = 0; x < n; x++) progeny_gl_host(ds[x], table_out ? table_out[x] : nullptr, table_f64_out ? table_f64_out[x] : nullptr);
+#endif
+		return WHAMD_OK;
+	}
+	st = progeny_gl_device(ds, device, table_out, table_f64_out, msg);
+	return st == WHAMD_OK ? st : fail(st, msg);
+}
+
+whamd_status_t score_depths(const whamd_progeny_depths_view* views, uint64_t n, int device, whamd_progeny_scores** out) {
+	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
+	*out = nullptr;
+	const double t0 = now_ms();
+	std::unique_ptr<whamd_progeny_scores> r(new whamd_progeny_scores());
+	r->problems.resize(n);
+	r->results.resize(n);
+	r->stats.assign(n, whamd_progeny_score_stats{});
+	std::vector<ProgenyDepths> ds;
+	std::string msg;
+	whamd_status_t st = prepare_depths(views, n, ds, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	for (uint64_t x = 0; x < n; x++) {
+		const whamd_progeny_depths_view& v = views[x];
+		// the table the device makes has one row per node
+		const whamd_progeny_view pv{nullptr, v.n_nodes, v.n_samples, v.ploidy, v.n_nodes, v.node_variant, v.n_variants, v.alt_count, v.co_alt_count, v.scoring_window};
+		st = progeny_prepare(pv, r->problems[x], msg, false);
+		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
+	}
+	const double t1 = now_ms();
+	CallTimes times;
+	st = progeny_score_depths_device(ds, r->problems, device, r->results, times, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	fill_stats(*r, times, t0, t1, now_ms());
 	*out = r.release();
 	return WHAMD_OK;
 }
@@ -408,7 +550,21 @@ whamd_status_t whamd_progeny_variant_types(const float* gl, uint64_t n_positions
 	});
 }
 
+whamd_status_t whamd_progeny_gl(const whamd_progeny_depths_view* problems, uint64_t n_problems, int device, float* const* table_out,
+                                double* const* table_f64_out) {
+	return guarded([&]() -> whamd_status_t { return gl(problems, n_problems, device, false, table_out, table_f64_out); });
+}
+
+whamd_status_t whamd_progeny_score_depths(const whamd_progeny_depths_view* problems, uint64_t n_problems, int device, whamd_progeny_scores** out) {
+	return guarded([&]() -> whamd_status_t { return score_depths(problems, n_problems, device, out); });
+}
+
 #ifdef WHAMD_DEBUG_BUILD
+whamd_status_t whamd_debug_progeny_gl_host(const whamd_progeny_depths_view* problems, uint64_t n_problems, float* const* table_out,
+                                           double* const* table_f64_out) {
+	return guarded([&]() -> whamd_status_t { return gl(problems, n_problems, 0, true, table_out, table_f64_out); });
+}
+
 whamd_status_t whamd_debug_progeny_score_host(const whamd_progeny_view* problems, uint64_t n_problems, whamd_progeny_scores** out) {
 	return guarded([&]() -> whamd_status_t { return score(problems, n_problems, 0, true, out); });
 }
