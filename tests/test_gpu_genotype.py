@@ -109,6 +109,34 @@ def test_windowed_run_path_is_identical_to_the_unwindowed_one(kw, window_bytes, 
     assert np.allclose(windowed, want, rtol=RTOL, atol=ATOL), np.abs(windowed - want).max()
 
 
+@pytest.mark.parametrize("kw", [
+    dict(mode="single", n_variants=8, n_reads=8, max_len=4, max_coverage=4),
+    dict(mode="trio", n_variants=8, n_reads=8, max_len=4, max_coverage=4),
+    dict(mode="trio", n_variants=40, n_reads=120, max_len=7, max_coverage=9),
+], ids=str)
+def test_launch_counts_of_every_schedule(kw):
+    """What each schedule submits, through the `launches` figure of the stats (n columns, R slot runs per chain):
+    per-column kernels in windows:  1 table launch + (n - 1) kept backward steps + per window (its columns - 1) recomputed backward steps,
+                                    its columns' forward steps and one finish = 3 n;
+    per-column kernels, two chains: 1 + (n - 1) backward + (n - 1) forward + per 1024 columns one batched likelihood launch and one finish;
+    run path, one window:           one table launch per 32768 runs, R forward + R backward runs, per 512 columns one combine and one finish."""
+    ref = reference_core()
+    p = random_case(10, **kw)   # (a seed whose three tables are eligible for the run path: 3, 4 and 18 runs)
+    n = kw["n_variants"]
+    want = reference_likelihoods(p, ref)
+    for window in (3, n, 64):
+        got, stats = device_likelihoods(p, window)
+        assert stats["slot_runs"] == 0 and stats["window"] == min(window, n), stats
+        expected = 3 * n if window < n else 2 * n - 1 + 2 * -(-n // 1024)
+        assert stats["launches"] == expected, (window, stats, expected)
+        assert np.allclose(got, want, rtol=RTOL, atol=ATOL), (window, np.abs(got - want).max())
+    got, stats = device_likelihoods(p, 0)
+    runs = stats["slot_runs"]
+    assert runs > 0 and stats["window"] == n, stats   # an eligible table: the run path, one window
+    assert stats["launches"] == -(-runs // 32768) + 2 * runs + 2 * -(-n // 512), stats
+    assert np.allclose(got, want, rtol=RTOL, atol=ATOL), np.abs(got - want).max()
+
+
 def test_many_reads_starting_and_ending_in_one_column():
     """Columns in which more reads start / end than a thread loops over: the split (atomic) accumulation path."""
     ref = reference_core()

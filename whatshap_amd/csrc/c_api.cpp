@@ -1028,7 +1028,7 @@ whamd_status_t whamd_genotype_likelihoods(const whamd_readset_view* readset, con
 	if (st != WHAMD_OK) return fail(st, msg);
 	std::vector<double> gl;
 	GenotypeStats gs;
-	st = genotype_solve_device(p, model, device, window, gl, gs, msg);
+	st = genotype_solve(p, model, device, window, gl, gs, msg);
 	if (st != WHAMD_OK) return fail(st, msg);
 	if (need) std::memcpy(gl_out, gl.data(), need * sizeof(double));
 	if (stats_out) {

@@ -26,20 +26,20 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 
 #include "debug_build.h"
 #include "device_runtime.h"
 #include "genotype.h"
+#include "genotype_plan.h"
 
 namespace whamd {
 
 namespace {
 
-constexpr int GENO_BLOCK = 256;
 constexpr int GENO_MAXA = 16;      // allele assignments (P <= 4)
 constexpr int GENO_MAXGL = 1 + 3 * MAX_IND;
-constexpr uint32_t GENO_LOOP_BITS = 2;   // a thread loops over at most 4 cells of its projection entry
 
 struct GenoDev {
 	const uint64_t* col_ptr;
@@ -100,8 +100,6 @@ __device__ __forceinline__ void geno_stage(const GenoDev& G, uint32_t c, uint32_
 	}
 }
 
-constexpr uint32_t GENO_GROUP_BITS = 7;      // reads per lookup table
-constexpr uint32_t GENO_GROUP = 1u << GENO_GROUP_BITS;
 constexpr int GENO_MAXSLOTS = 8;             // 2 * individuals (P <= 4: at most a quartet)
 
 // Lookup tables of a column (global memory, geno_tables): for every group of 7 reads and every setting of their bits, the product over the
@@ -472,12 +470,6 @@ __global__ __launch_bounds__(64) void geno_finish(const double* __restrict__ gl_
 	}
 }
 
-uint32_t blocks_for(uint32_t k, uint32_t proj, uint32_t T) {   // grid of a column kernel: 2^(k - min(k - proj, LOOP)) entries x T threads
-	const uint32_t nfree = k - proj, loop_bits = std::min(nfree, GENO_LOOP_BITS);
-	const uint64_t threads = (1ull << (k - loop_bits)) * T;
-	return (uint32_t)((threads + GENO_BLOCK - 1) / GENO_BLOCK);
-}
-
 }  // namespace
 
 // The column store (tens of GB) is kept between calls, one block per device: mapping that much fresh device memory took 3 - 4 s
@@ -538,152 +530,192 @@ void genotype_release_cache() {
 	(void)hipSetDevice(current);
 }
 
-whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, int device, uint32_t window_hint,
-                                     std::vector<double>& gl_out, GenotypeStats& st, std::string& msg) {
-	const uint32_t n = p.n_cols, T = p.T, ni = p.n_ind;
-	gl_out.assign((size_t)ni * n * 3, 0.0);
+// ---------------------------------------------------------------------------------------------- what the two paths share (genotype.h)
+void genotype_begin(const Problem& p, std::vector<double>& gl_out, GenotypeStats& st) {
+	gl_out.assign((size_t)p.n_ind * p.n_cols * 3, 0.0);
 	st = GenotypeStats();
-	st.n_columns = n;
-	st.transmissions = T;
-	if (n == 0) return WHAMD_OK;
+	st.n_columns = p.n_cols;
+	st.transmissions = p.T;
+	for (uint32_t c = 0; c < p.n_cols; ++c) {
+		st.n_cells += 1ull << p.k[c];
+		st.max_coverage = std::max<uint32_t>(st.max_coverage, p.k[c]);
+	}
+}
+
+whamd_status_t genotype_free_bytes(int device, size_t& free_bytes, std::string& msg) {
+	size_t total_b = 0;
+	HIP_TRY(hipMemGetInfo(&free_bytes, &total_b));
+	if (free_bytes < total_b / 2) {   // a phasing table of this process may have left its arena in the cache (dp_device.hip)
+		arena_release();
+		HIP_TRY(hipMemGetInfo(&free_bytes, &total_b));
+	}
+	free_bytes += genotype_slab_idle_bytes(device);   // the block kept from an earlier call is available to this one
+	return WHAMD_OK;
+}
+
+hipError_t GenotypeCall::up(void** dptr, const void* src, size_t bytes) {
+	hipError_t e = alloc(dptr, bytes);
+	if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, ses.stream);
+	return e;
+}
+
+hipError_t GenotypeCall::take_store(void** dptr, size_t bytes) {
+	*dptr = genotype_slab_acquire(ses.device, bytes);
+	if (!*dptr) return alloc(dptr, bytes);
+	slab.device = ses.device;
+	return hipSuccess;
+}
+
+whamd_status_t genotype_solve(const Problem& p, const GenotypeModel& m, int device, uint32_t window_hint,
+                              std::vector<double>& gl_out, GenotypeStats& st, std::string& msg) {
+	if (p.n_cols == 0) { genotype_begin(p, gl_out, st); return WHAMD_OK; }
 	const whamd_status_t opened = open_device(device, msg);
 	if (opened != WHAMD_OK) return opened;
-	if (T != 1 && T != 4 && T != 16) { msg = "unsupported number of transmission values"; return WHAMD_ERR_UNSUPPORTED; }
+	if (p.T != 1 && p.T != 4 && p.T != 16) { msg = "unsupported number of transmission values"; return WHAMD_ERR_UNSUPPORTED; }
 	// the run-fused path wherever it applies (no forced window, every column in a run, stores fit in HBM)
 	if (!window_hint && !debug_env("WHAMD_GENOTYPE_COLUMNS")) {
 		bool used = false;
 		const whamd_status_t sst = genotype_solve_slots(p, m, device, gl_out, st, used, msg);
-		if (sst != WHAMD_OK) return sst;
-		if (used) return WHAMD_OK;
-		gl_out.assign((size_t)ni * n * 3, 0.0);
-		st = GenotypeStats();
-		st.n_columns = n;
-		st.transmissions = T;
+		if (sst != WHAMD_OK || used) return sst;
 	}
-	uint32_t max_k = 0, max_proj = 0;
-	for (uint32_t c = 0; c < n; ++c) {
-		max_k = std::max<uint32_t>(max_k, p.k[c]);
-		max_proj = std::max<uint32_t>(max_proj, std::max<uint32_t>(p.f[c], p.b[c]));
-		st.n_cells += 1ull << p.k[c];
-	}
-	st.max_coverage = max_k;
-	const size_t buf_doubles = ((size_t)1 << max_proj) * T;
-	const uint32_t max_blocks = (uint32_t)(((((size_t)1 << max_k) * T) + GENO_BLOCK - 1) / GENO_BLOCK);
-	const uint32_t n_gl = 1 + 3 * ni;
-	size_t free_b = 0, total_b = 0;
-	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-	if (free_b < total_b / 2) {   // a phasing table of this process may have left its arena in the cache (dp_device.hip)
-		arena_release();
-		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-	}
-	free_b += genotype_slab_idle_bytes(device);   // the block kept from an earlier call is available to this one
-	// Window = how many backward columns are kept at once.  If all of them fit in a quarter of the free memory there is one
-	// window and no column is computed twice; otherwise the reference's scheme: sqrt(n) kept columns, the rest recomputed.
-	uint32_t K = window_hint;
-	if (!K) {
-		const double per_column = (double)buf_doubles * 8 + (double)max_blocks * 8 * (1 + n_gl);
-		K = 2.0 * per_column * n <= 0.4 * (double)free_b ? n : (uint32_t)std::ceil(std::sqrt((double)n));   // (backward AND forward columns kept)
-	}
-	K = std::max(1u, std::min(K, n));
-	st.window = K;
-	const uint32_t n_windows = (n + K - 1) / K;
-	{
-		const double need = (double)(buf_doubles * 8 + (size_t)max_blocks * 8) * (n_windows + 2.0 * K + 4.0) + (double)K * max_blocks * n_gl * 8 + (double)p.entries.size() * 10 + (double)n * (64 + 8.0 * T * m.A)
-		                    + (double)n * ((max_k + GENO_GROUP_BITS - 1) / GENO_GROUP_BITS) * GENO_GROUP * 4 * ni * 8.0;
+	return genotype_solve_columns(p, m, device, window_hint, gl_out, st, msg);
+}
+
+// ---------------------------------------------------------------------------------------------- the per-column path
+namespace {
+
+// Kernel selection, and the list the LDS opt-in goes through.  forward[MODE]: 0 all of a forward step (windows), 1 A_c only (the forward
+// chain beside the backward chain), 2 the likelihood sums of a batch of columns.
+using BackwardFn = void (*)(GenoDev, GenoCol, const double*, const double*, uint32_t, double*, double*);
+using ForwardFn = void (*)(GenoDev, GenoFwdArgs, const GenoFwdArgs*);
+struct GenoColumnKernels { BackwardFn backward; ForwardFn forward[3]; };
+const BackwardFn GENO_BACKWARD[3] = {geno_backward<1>, geno_backward<4>, geno_backward<16>};   // by log4 T
+const ForwardFn GENO_FORWARD[3][3] = {{geno_forward<1, 0>, geno_forward<1, 1>, geno_forward<1, 2>},
+                                      {geno_forward<4, 0>, geno_forward<4, 1>, geno_forward<4, 2>},
+                                      {geno_forward<16, 0>, geno_forward<16, 1>, geno_forward<16, 2>}};
+GenoColumnKernels geno_column_kernels(uint32_t T) {
+	const int t = T == 1 ? 0 : (T == 4 ? 1 : 2);
+	return {GENO_BACKWARD[t], {GENO_FORWARD[t][0], GENO_FORWARD[t][1], GENO_FORWARD[t][2]}};
+}
+
+// a column buffer carries its per-block sums
+struct Buf { double* v = nullptr; double* partials = nullptr; uint32_t blocks = 0; };
+
+// One per-column solve: what the steps share, one member function per step (genotype_solve_columns is their sequence).
+struct ColumnCall : GenotypeCall {
+	const Problem& p;
+	const GenotypeModel& m;
+	const int device;
+	const uint32_t window_hint;
+	std::vector<double>& gl_out;
+	GenotypeStats& st;
+	std::string& msg;
+	const uint32_t n, T, ni, n_gl;
+	uint32_t max_k = 0, max_blocks = 0, K = 0, n_windows = 0, max_groups = 0;
+	size_t buf_doubles = 0, table_bytes = 0;
+	std::chrono::steady_clock::time_point t_phase0, t_enqueue0;
+	double ms_allocated = 0;
+	hipStream_t stream = nullptr, stream2 = nullptr;
+	hipEvent_t ev[3] = {nullptr, nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};   // times; a window's backward columns are recomputed
+	std::vector<uint32_t> fw_blocks, bw_blocks;
+	GenoDev G{};
+	void* d_fwb = nullptr;
+	double *d_tables = nullptr, *d_glpart = nullptr, *d_gl = nullptr;
+	Buf alpha[2], pp[2];
+	std::vector<Buf> ckpt, wstore, astore;
+	GenoColumnKernels kn{};
+	uint64_t launches = 0;
+
+	ColumnCall(const Problem& p_, const GenotypeModel& m_, int device_, uint32_t window_hint_, std::vector<double>& gl_out_, GenotypeStats& st_, std::string& msg_)
+	    : p(p_), m(m_), device(device_), window_hint(window_hint_), gl_out(gl_out_), st(st_), msg(msg_), n(p_.n_cols), T(p_.T), ni(p_.n_ind), n_gl(1 + 3 * p_.n_ind) {}
+
+	double phase_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase0).count(); }
+
+	// the sizes of the column buffers, the window, and whether all of it fits
+	whamd_status_t choose_window() {
+		uint32_t max_proj = 0;
+		for (uint32_t c = 0; c < n; ++c) max_proj = std::max(max_proj, std::max<uint32_t>(p.f[c], p.b[c]));
+		max_k = st.max_coverage;
+		buf_doubles = ((size_t)1 << max_proj) * T;
+		max_blocks = (uint32_t)(((((size_t)1 << max_k) * T) + GENO_BLOCK - 1) / GENO_BLOCK);
+		size_t free_b = 0;
+		const whamd_status_t queried = genotype_free_bytes(device, free_b, msg);
+		if (queried != WHAMD_OK) return queried;
+		K = geno_column_window(n, window_hint, (double)buf_doubles * 8 + (double)max_blocks * 8 * (1 + n_gl), (double)free_b);
+		st.window = K;
+		n_windows = (n + K - 1) / K;
+		const double need = geno_column_need(n, K, buf_doubles, max_blocks, n_gl, p.entries.size(), T, m.A, max_k, ni);
 		if (need + (double)(1ull << 30) > (double)free_b) {
 			msg = "genotyping buffers of " + std::to_string((uint64_t)(need / 1048576.0)) + " MiB do not fit in free HBM";
 			return WHAMD_ERR_UNSUPPORTED;
 		}
+		return WHAMD_OK;
 	}
-	const auto t_phase0 = std::chrono::steady_clock::now();
-	auto phase_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_phase0).count(); };
-	GenotypeSlabHold slab;
-	Session ses;   // the second chain's stream, every event and every block: the session's, whichever way the call ends
-	const whamd_status_t session_open = ses.open(device, 3, msg);
-	if (session_open != WHAMD_OK) return session_open;
-	const hipStream_t stream = ses.stream;
-	auto alloc = [&](void** dptr, size_t bytes) { return ses.fresh_block(dptr, bytes); };
-	auto up = [&](void** dptr, const void* src, size_t bytes) -> hipError_t {
-		hipError_t e = alloc(dptr, bytes);
-		if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, stream);
-		return e;
-	};
-	// ---- upload the model
-	std::vector<uint8_t> ent_ind(p.entries.size()), ent_allele(p.entries.size());
-	for (size_t e = 0; e < p.entries.size(); ++e) { ent_ind[e] = p.entries[e].sample; ent_allele[e] = p.entries[e].allele; }
-	std::vector<uint32_t> fw_blocks(n), bw_blocks(n);
-	for (uint32_t c = 0; c < n; ++c) {
-		fw_blocks[c] = blocks_for(p.k[c], c + 1 < n ? p.f[c] : 0u, T);
-		bw_blocks[c] = blocks_for(p.k[c], p.b[c], T);
+
+	whamd_status_t open() {
+		t_phase0 = std::chrono::steady_clock::now();
+		const whamd_status_t opened = ses.open(device, 3, msg);
+		if (opened != WHAMD_OK) return opened;
+		stream = ses.stream;
+		for (int q = 0; q < 3; ++q) ev[q] = ses.ev[q];
+		return WHAMD_OK;
 	}
-	GenoDev G{};
-	void *d_col_ptr, *d_ind, *d_allele, *d_pe, *d_k, *d_b, *d_f, *d_fmask, *d_bern, *d_prior, *d_gidx, *d_h2p, *d_fwb;
-	HIP_TRY(up(&d_col_ptr, p.col_ptr.data(), p.col_ptr.size() * 8));
-	HIP_TRY(up(&d_ind, ent_ind.data(), ent_ind.size()));
-	HIP_TRY(up(&d_allele, ent_allele.data(), ent_allele.size()));
-	HIP_TRY(up(&d_pe, m.error_prob.data(), m.error_prob.size() * 8));
-	HIP_TRY(up(&d_k, p.k.data(), n));
-	HIP_TRY(up(&d_b, p.b.data(), n));
-	HIP_TRY(up(&d_f, p.f.data(), n));
-	HIP_TRY(up(&d_fmask, p.fwd_mask.data(), (size_t)n * 4));
-	HIP_TRY(up(&d_bern, m.transition_bern.data(), m.transition_bern.size() * 8));
-	HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
-	HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
-	HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
-	HIP_TRY(up(&d_fwb, fw_blocks.data(), (size_t)n * 4));
-	G.col_ptr = (const uint64_t*)d_col_ptr; G.ent_ind = (const uint8_t*)d_ind; G.ent_allele = (const uint8_t*)d_allele; G.ent_pe = (const double*)d_pe;
-	G.k = (const uint8_t*)d_k; G.b = (const uint8_t*)d_b; G.f = (const uint8_t*)d_f; G.fwd_mask = (const uint32_t*)d_fmask;
-	G.bern = (const double*)d_bern; G.prior = (const double*)d_prior; G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p;
-	G.T = T; G.A = m.A; G.P = p.P; G.n_ind = ni; G.nb = 2 * p.n_triples + 1; G.n_cols = n;
-	{
-		// founders are the individuals whose two haplotypes ARE partitions (h2p does not depend on the transmission value)
-		std::vector<uint8_t> is_child(ni, 0);
-		for (uint32_t t3 = 0; t3 < p.n_triples; ++t3) is_child[p.triples[t3][2]] = 1;
-		uint32_t child_slots = 0;
-		for (uint32_t s = 0; s < ni; ++s) {
-			if (!is_child[s]) {
-				G.slot_of[2 * s] = (uint8_t)p.h2p[(size_t)s * 2];
-				G.slot_of[2 * s + 1] = (uint8_t)p.h2p[(size_t)s * 2 + 1];
-			} else {
-				if (p.P != 4 || child_slots + 2 > 4) { msg = "unsupported pedigree shape for device genotyping"; return WHAMD_ERR_UNSUPPORTED; }
-				for (uint32_t h = 0; h < 2; ++h) {
-					G.slot_of[2 * s + h] = (uint8_t)(p.P + child_slots + h);
-					for (uint32_t i = 0; i < T; ++i) G.child_part[i][child_slots + h] = (uint8_t)p.h2p[((size_t)i * ni + s) * 2 + h];
-				}
-				child_slots += 2;
-			}
+
+	// the model, one copy per array; the space of the lookup tables
+	whamd_status_t upload_model() {
+		std::vector<uint8_t> ent_ind(p.entries.size()), ent_allele(p.entries.size());
+		for (size_t e = 0; e < p.entries.size(); ++e) { ent_ind[e] = p.entries[e].sample; ent_allele[e] = p.entries[e].allele; }
+		fw_blocks.resize(n);
+		bw_blocks.resize(n);
+		for (uint32_t c = 0; c < n; ++c) {
+			fw_blocks[c] = blocks_for(p.k[c], c + 1 < n ? p.f[c] : 0u, T);
+			bw_blocks[c] = blocks_for(p.k[c], p.b[c], T);
 		}
-		G.n_child_slots = child_slots;
+		void *d_col_ptr, *d_ind, *d_allele, *d_pe, *d_k, *d_b, *d_f, *d_fmask, *d_bern, *d_prior, *d_gidx, *d_h2p;
+		HIP_TRY(up(&d_col_ptr, p.col_ptr.data(), p.col_ptr.size() * 8));
+		HIP_TRY(up(&d_ind, ent_ind.data(), ent_ind.size()));
+		HIP_TRY(up(&d_allele, ent_allele.data(), ent_allele.size()));
+		HIP_TRY(up(&d_pe, m.error_prob.data(), m.error_prob.size() * 8));
+		HIP_TRY(up(&d_k, p.k.data(), n));
+		HIP_TRY(up(&d_b, p.b.data(), n));
+		HIP_TRY(up(&d_f, p.f.data(), n));
+		HIP_TRY(up(&d_fmask, p.fwd_mask.data(), (size_t)n * 4));
+		HIP_TRY(up(&d_bern, m.transition_bern.data(), m.transition_bern.size() * 8));
+		HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
+		HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
+		HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
+		HIP_TRY(up(&d_fwb, fw_blocks.data(), (size_t)n * 4));
+		G.col_ptr = (const uint64_t*)d_col_ptr; G.ent_ind = (const uint8_t*)d_ind; G.ent_allele = (const uint8_t*)d_allele; G.ent_pe = (const double*)d_pe;
+		G.k = (const uint8_t*)d_k; G.b = (const uint8_t*)d_b; G.f = (const uint8_t*)d_f; G.fwd_mask = (const uint32_t*)d_fmask;
+		G.bern = (const double*)d_bern; G.prior = (const double*)d_prior; G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p;
+		G.T = T; G.A = m.A; G.P = p.P; G.n_ind = ni; G.nb = 2 * p.n_triples + 1; G.n_cols = n;
+		GenoSlotTable slots;
+		const whamd_status_t slotted = geno_slot_table(p, slots, msg);
+		if (slotted != WHAMD_OK) return slotted;
+		G.n_child_slots = slots.n_child_slots;
+		std::memcpy(G.slot_of, slots.slot_of, sizeof G.slot_of);
+		std::memcpy(G.child_part, slots.child_part, sizeof G.child_part);
+		// lookup tables of all columns (geno_tables): one launch before the chains start
+		max_groups = (max_k + GENO_GROUP_BITS - 1) / GENO_GROUP_BITS;
+		G.table_stride = std::max(1u, max_groups) * GENO_GROUP * 4 * ni;
+		HIP_TRY(alloc((void**)&d_tables, (size_t)n * G.table_stride * sizeof(double)));
+		G.tables = d_tables;
+		table_bytes = (size_t)G.table_stride * sizeof(double);   // the step kernels copy their column's tables into LDS
+		if (table_bytes + sizeof(GenoShared) > 160 * 1024) {   // (a quartet beyond coverage ~35: never reached below the 25-read limit, but never a bare launch failure)
+			msg = "lookup tables of " + std::to_string(table_bytes >> 10) + " KiB per column do not fit in LDS";
+			return WHAMD_ERR_UNSUPPORTED;
+		}
+		return WHAMD_OK;
 	}
-	// lookup tables of all columns (geno_tables): one launch before the chains start
-	const uint32_t max_groups = (max_k + GENO_GROUP_BITS - 1) / GENO_GROUP_BITS;
-	G.table_stride = std::max(1u, max_groups) * GENO_GROUP * 4 * ni;
-	double* d_tables = nullptr;
-	HIP_TRY(alloc((void**)&d_tables, (size_t)n * G.table_stride * sizeof(double)));
-	G.tables = d_tables;
-	const size_t table_bytes = (size_t)G.table_stride * sizeof(double);   // the step kernels copy their column's tables into LDS
-	if (table_bytes + sizeof(GenoShared) > 160 * 1024) {   // (a quartet beyond coverage ~35: never reached below the 25-read limit, but never a bare launch failure)
-		msg = "lookup tables of " + std::to_string(table_bytes >> 10) + " KiB per column do not fit in LDS";
-		return WHAMD_ERR_UNSUPPORTED;
-	}
-	if (table_bytes + sizeof(GenoShared) > 64 * 1024) {   // more than 64 KiB of LDS needs the opt-in on every kernel that asks for it
-		const void* fns[] = {(const void*)geno_backward<1>, (const void*)geno_backward<4>, (const void*)geno_backward<16>,
-		                     (const void*)geno_forward<1, 0>, (const void*)geno_forward<1, 1>, (const void*)geno_forward<1, 2>,
-		                     (const void*)geno_forward<4, 0>, (const void*)geno_forward<4, 1>, (const void*)geno_forward<4, 2>,
-		                     (const void*)geno_forward<16, 0>, (const void*)geno_forward<16, 1>, (const void*)geno_forward<16, 2>};
-		for (const void* fn : fns) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)sizeof(GenoShared)));
-	}
-	// ---- buffers: every column buffer carries its per-block sums
-	struct Buf { double* v = nullptr; double* partials = nullptr; uint32_t blocks = 0; };
-	Buf alpha[2], pp[2];
-	std::vector<Buf> ckpt(n_windows), wstore(n_windows == 1 ? K : 2 * (size_t)K), astore(n_windows == 1 ? K : 0);   // windowed: two halves, recompute of window w + 1 beside the forward pass of window w   // astore: the forward columns of the two-chain mode
-	{
-		// one slab for all of them (tens of thousands of hipMalloc calls would take seconds)
+
+	// every column buffer out of one slab (tens of thousands of hipMalloc calls would take seconds), the likelihood sums, the result
+	whamd_status_t take_buffers() {
+		ckpt.resize(n_windows);
+		wstore.resize(n_windows == 1 ? K : 2 * (size_t)K);   // windowed: two halves, recompute of window w + 1 beside the forward pass of window w
+		astore.resize(n_windows == 1 ? K : 0);               // the forward columns of the two-chain mode
 		const size_t count = 4 + (size_t)n_windows + wstore.size() + astore.size();
 		double *slab_v = nullptr, *slab_p = nullptr;
-		slab_v = (double*)genotype_slab_acquire(device, count * buf_doubles * 8);
-		if (slab_v) slab.device = device;
-		if (!slab_v) HIP_TRY(alloc((void**)&slab_v, count * buf_doubles * 8));
+		HIP_TRY(take_store((void**)&slab_v, count * buf_doubles * 8));
 		HIP_TRY(alloc((void**)&slab_p, count * (size_t)max_blocks * 8));
 		size_t next = 0;
 		auto take = [&](Buf& bf) { bf.v = slab_v + next * buf_doubles; bf.partials = slab_p + next * max_blocks; ++next; };
@@ -692,51 +724,48 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		for (Buf& bf : ckpt) take(bf);
 		for (Buf& bf : wstore) take(bf);
 		for (Buf& bf : astore) take(bf);
+		HIP_TRY(alloc((void**)&d_glpart, (size_t)std::min<uint32_t>(K, n_windows == 1 ? 1024u : K) * max_blocks * n_gl * 8));
+		HIP_TRY(alloc((void**)&d_gl, gl_out.size() * 8));
+		return WHAMD_OK;
 	}
-	double *d_glpart = nullptr, *d_gl = nullptr;
-	HIP_TRY(alloc((void**)&d_glpart, (size_t)std::min<uint32_t>(K, n_windows == 1 ? 1024u : K) * max_blocks * n_gl * 8));
-	HIP_TRY(alloc((void**)&d_gl, gl_out.size() * 8));
-	const hipEvent_t ev[3] = {ses.ev[0], ses.ev[1], ses.ev[2]};
-	uint64_t launches = 0;
+
+	// the kernels of this T; more than 64 KiB of LDS needs the opt-in on every kernel that asks for it
+	whamd_status_t launch_tables() {
+		kn = geno_column_kernels(T);
+		if (table_bytes + sizeof(GenoShared) > 64 * 1024) {
+			const int lds = 160 * 1024 - (int)sizeof(GenoShared);
+			for (BackwardFn fn : GENO_BACKWARD) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+			for (const auto& of_t : GENO_FORWARD)
+				for (ForwardFn fn : of_t) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+		}
+		return WHAMD_OK;
+	}
+
+	whamd_status_t fill_tables() {
+		ms_allocated = phase_ms();
+		t_enqueue0 = std::chrono::steady_clock::now();
+		HIP_TRY(hipEventRecord(ev[0], stream));
+		if (max_groups) {
+			hipLaunchKernelGGL(geno_tables, dim3((max_groups * GENO_GROUP + GENO_BLOCK - 1) / GENO_BLOCK, n), dim3(GENO_BLOCK), 0, stream, G, d_tables);
+			++launches;
+			HIP_TRY(hipGetLastError());
+		}
+		return WHAMD_OK;
+	}
+
 	// one backward step: column c, B_c in `in` (null: last column) -> B_{c-1} in `out`
-	auto backward = [&](uint32_t c, const Buf* in, Buf& out, hipStream_t on = nullptr) -> hipError_t {
-		if (!on) on = stream;
-		const uint32_t blocks = bw_blocks[c];
+	hipError_t backward(uint32_t c, const Buf* in, Buf& out, hipStream_t on) {
 		const uint32_t atomics = (uint32_t)p.k[c] - p.b[c] > GENO_LOOP_BITS ? 1u : 0u;
 		const GenoCol C{c, p.k[c], p.b[c], p.f[c], p.fwd_mask[c], std::min<uint32_t>((uint32_t)p.k[c] - p.b[c], GENO_LOOP_BITS), atomics, 0u};
 		if (atomics) { hipError_t e = hipMemsetAsync(out.v, 0, ((size_t)T << p.b[c]) * 8, on); if (e != hipSuccess) return e; }
-		out.blocks = blocks;
-		const double* iv = in ? in->v : nullptr;
-		const double* ip = in ? in->partials : nullptr;
-		const uint32_t ib = in ? in->blocks : 0u;
-		if (T == 1) hipLaunchKernelGGL(geno_backward<1>, dim3(blocks), dim3(GENO_BLOCK), table_bytes, on, G, C, iv, ip, ib, out.v, out.partials);
-		else if (T == 4) hipLaunchKernelGGL(geno_backward<4>, dim3(blocks), dim3(GENO_BLOCK), table_bytes, on, G, C, iv, ip, ib, out.v, out.partials);
-		else hipLaunchKernelGGL(geno_backward<16>, dim3(blocks), dim3(GENO_BLOCK), table_bytes, on, G, C, iv, ip, ib, out.v, out.partials);
+		out.blocks = bw_blocks[c];
+		hipLaunchKernelGGL(kn.backward, dim3(bw_blocks[c]), dim3(GENO_BLOCK), table_bytes, on, G, C, in ? in->v : nullptr, in ? in->partials : nullptr,
+		                   in ? in->blocks : 0u, out.v, out.partials);
 		++launches;
 		return hipGetLastError();
-	};
-	const double ms_allocated = phase_ms();
-	const auto t_enqueue0 = std::chrono::steady_clock::now();
-	HIP_TRY(hipEventRecord(ev[0], stream));
-	if (max_groups) {
-		hipLaunchKernelGGL(geno_tables, dim3((max_groups * GENO_GROUP + GENO_BLOCK - 1) / GENO_BLOCK, n), dim3(GENO_BLOCK), 0, stream, G, d_tables);
-		++launches;
-		HIP_TRY(hipGetLastError());
 	}
-	// ---- pass 1: B_{c-1} for c = n-1 .. 1, kept where c - 1 is the last column of a window (nothing to keep with one window)
-	if (n_windows > 1) {
-		const Buf* in = nullptr;
-		uint32_t flip = 0;
-		for (uint32_t c = n - 1; c >= 1; --c) {
-			const bool keep = (c - 1) % K == K - 1;
-			Buf& out = keep ? ckpt[(c - 1) / K] : pp[flip];
-			HIP_TRY(backward(c, in, out));
-			in = &out;
-			if (!keep) flip ^= 1u;
-		}
-	}
-	HIP_TRY(hipEventRecord(ev[1], stream));
-	auto fwd_args = [&](uint32_t c, const Buf* prev_alpha, const Buf* beta, Buf* out, double* glp) {
+
+	GenoFwdArgs fwd_args(uint32_t c, const Buf* prev_alpha, const Buf* beta, Buf* out, double* glp) const {
 		const bool last = c + 1 == n;
 		const uint32_t fc = last ? 0u : p.f[c], fm = last ? 0u : p.fwd_mask[c];
 		const uint32_t atomics = (!last && out && (uint32_t)p.k[c] - fc > GENO_LOOP_BITS) ? 1u : 0u;
@@ -749,21 +778,19 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		a.gl_partials = glp;
 		a.n_blocks = fw_blocks[c];
 		return a;
-	};
-	auto launch_forward = [&](const GenoFwdArgs& a, int mode, hipStream_t on) -> hipError_t {
+	}
+
+	hipError_t launch_forward(const GenoFwdArgs& a, int mode, hipStream_t on) {
 		if (a.C.use_atomics) { hipError_t e = hipMemsetAsync(a.out, 0, ((size_t)T << a.C.f) * 8, on); if (e != hipSuccess) return e; }
-		const dim3 grid(a.n_blocks), block(GENO_BLOCK);
-#define GENO_FWD(TT) do { if (mode == 0) hipLaunchKernelGGL((geno_forward<TT, 0>), grid, block, table_bytes, on, G, a, (const GenoFwdArgs*)nullptr); \
-		                     else hipLaunchKernelGGL((geno_forward<TT, 1>), grid, block, table_bytes, on, G, a, (const GenoFwdArgs*)nullptr); } while (0)
-		if (T == 1) GENO_FWD(1); else if (T == 4) GENO_FWD(4); else GENO_FWD(16);
-#undef GENO_FWD
+		hipLaunchKernelGGL(kn.forward[mode], dim3(a.n_blocks), dim3(GENO_BLOCK), table_bytes, on, G, a, (const GenoFwdArgs*)nullptr);
 		++launches;
 		return hipGetLastError();
-	};
-	if (n_windows == 1) {
-		// ---- everything fits: the backward chain (this stream) and the forward chain of the A columns (a second stream) run side
-		// by side -- they meet only in the likelihood sums, which one batched launch per 1024 columns computes afterwards
-		hipStream_t stream2 = nullptr;
+	}
+
+	// Everything fits: the backward chain (this stream) and the forward chain of the A columns (a second stream) run side by side -- they meet
+	// only in the likelihood sums, which one batched launch per 1024 columns computes afterwards.
+	whamd_status_t submit_two_chains() {
+		HIP_TRY(hipEventRecord(ev[1], stream));
 		HIP_TRY(ses.add_stream(&stream2));
 		hipEvent_t ev_start, ev_fwd;
 		HIP_TRY(ses.sync_event(&ev_start));
@@ -774,7 +801,7 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		uint32_t cb = n - 1, cf = 0;
 		while (cb >= 1 || cf + 1 < n) {
 			if (cb >= 1) {
-				HIP_TRY(backward(cb, cb == n - 1 ? nullptr : &wstore[cb], wstore[cb - 1]));
+				HIP_TRY(backward(cb, cb == n - 1 ? nullptr : &wstore[cb], wstore[cb - 1], stream));
 				--cb;
 			}
 			if (cf + 1 < n) {
@@ -785,7 +812,7 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 		}
 		HIP_TRY(hipEventRecord(ev_fwd, stream2));
 		HIP_TRY(hipStreamWaitEvent(stream, ev_fwd, 0));
-		HIP_TRY(hipEventRecord(ev[1], stream));
+		HIP_TRY(hipEventRecord(ev[1], stream));   // (again: backward_ms is the two chains, forward_ms the likelihood sums)
 		constexpr uint32_t BATCH = 1024;
 		std::vector<GenoFwdArgs> batch(n);
 		for (uint32_t c = 0; c < n; ++c)
@@ -796,12 +823,7 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 			const uint32_t cols = std::min(BATCH, n - c0);
 			uint32_t gx = 1;
 			for (uint32_t c = c0; c < c0 + cols; ++c) gx = std::max(gx, fw_blocks[c]);
-			const dim3 grid(gx, cols), block(GENO_BLOCK);
-			const GenoFwdArgs none{};
-			const GenoFwdArgs* bp = (const GenoFwdArgs*)d_batch + c0;
-			if (T == 1) hipLaunchKernelGGL((geno_forward<1, 2>), grid, block, table_bytes, stream, G, none, bp);
-			else if (T == 4) hipLaunchKernelGGL((geno_forward<4, 2>), grid, block, table_bytes, stream, G, none, bp);
-			else hipLaunchKernelGGL((geno_forward<16, 2>), grid, block, table_bytes, stream, G, none, bp);
+			hipLaunchKernelGGL(kn.forward[2], dim3(gx, cols), dim3(GENO_BLOCK), table_bytes, stream, G, GenoFwdArgs{}, (const GenoFwdArgs*)d_batch + c0);
 			++launches;
 			HIP_TRY(hipGetLastError());
 			hipLaunchKernelGGL(geno_finish, dim3(cols), dim3(64), 0, stream, d_glpart, (const uint32_t*)d_fwb, c0, max_blocks, ni, n, d_gl);
@@ -809,18 +831,11 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 			HIP_TRY(hipGetLastError());
 		}
 		HIP_TRY(hipStreamSynchronize(stream));
-	} else {
-	// ---- windows: the backward columns of window w + 1 are recomputed on a second stream (into the other half of the window
-	// store) while the forward pass runs through window w
-	hipStream_t stream2 = nullptr;
-	HIP_TRY(ses.add_stream(&stream2));
-	hipEvent_t ev_back[2], ev_fwd[2], ev_pass1;
-	for (hipEvent_t& e : ev_back) HIP_TRY(ses.sync_event(&e));
-	for (hipEvent_t& e : ev_fwd) HIP_TRY(ses.sync_event(&e));
-	HIP_TRY(ses.sync_event(&ev_pass1));
-	HIP_TRY(hipEventRecord(ev_pass1, stream));
-	HIP_TRY(hipStreamWaitEvent(stream2, ev_pass1, 0));   // the kept columns (and the uploads) are complete
-	auto recompute = [&](uint32_t w) -> hipError_t {      // B_c for the columns of window w but its last, on stream2
+		return WHAMD_OK;
+	}
+
+	// B_c for the columns of window w but its last, on stream2, into half w & 1 of the window store
+	hipError_t recompute(uint32_t w) {
 		const uint32_t lo = w * K, hi = std::min(n, lo + K);
 		Buf* half = wstore.data() + (size_t)(w & 1u) * K;
 		const Buf* last_beta = hi == n ? nullptr : &ckpt[w];   // B_{hi-1}
@@ -830,58 +845,101 @@ whamd_status_t genotype_solve_device(const Problem& p, const GenotypeModel& m, i
 			if (e != hipSuccess) return e;
 		}
 		return hipEventRecord(ev_back[w & 1u], stream2);
-	};
-	HIP_TRY(recompute(0));
-	uint32_t aflip = 0;
-	const Buf* prev_alpha = nullptr;
-	for (uint32_t w = 0; w < n_windows; ++w) {
-		const uint32_t lo = w * K, hi = std::min(n, lo + K);
-		const Buf* half = wstore.data() + (size_t)(w & 1u) * K;
-		const Buf* last_beta = hi == n ? nullptr : &ckpt[w];
-		HIP_TRY(hipStreamWaitEvent(stream, ev_back[w & 1u], 0));
-		if (w + 1 < n_windows) {
-			if (w >= 1) HIP_TRY(hipStreamWaitEvent(stream2, ev_fwd[(w - 1) & 1u], 0));   // the forward pass of window w - 1 is done with that half
-			HIP_TRY(recompute(w + 1));
-		}
-		for (uint32_t c = lo; c < hi; ++c) {
-			const Buf* beta = c == hi - 1 ? last_beta : &half[c - lo];
-			Buf& out = alpha[aflip];
-			out.blocks = fw_blocks[c];
-			HIP_TRY(launch_forward(fwd_args(c, prev_alpha, beta, &out, d_glpart + (size_t)(c - lo) * max_blocks * n_gl), 0, stream));
-			prev_alpha = &out;
-			aflip ^= 1u;
-		}
-		hipLaunchKernelGGL(geno_finish, dim3(hi - lo), dim3(64), 0, stream, d_glpart, (const uint32_t*)d_fwb, lo, max_blocks, ni, n, d_gl);
-		++launches;
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(ev_fwd[w & 1u], stream));
 	}
-	HIP_TRY(hipStreamSynchronize(stream));
-	HIP_TRY(hipStreamSynchronize(stream2));
-	}
-	HIP_TRY(hipEventRecord(ev[2], stream));
-	if (getenv("WHAMD_DEBUG_TIMING")) {
-		const double enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
+
+	// Pass 1: B_{c-1} for c = n-1 .. 1, kept where c - 1 is the last column of a window.  Then the windows: the backward columns of window
+	// w + 1 are recomputed on a second stream (into the other half of the window store) while the forward pass runs through window w.
+	whamd_status_t submit_windows() {
+		const Buf* in = nullptr;
+		uint32_t flip = 0;
+		for (uint32_t c = n - 1; c >= 1; --c) {
+			const bool keep = (c - 1) % K == K - 1;
+			Buf& out = keep ? ckpt[(c - 1) / K] : pp[flip];
+			HIP_TRY(backward(c, in, out, stream));
+			in = &out;
+			if (!keep) flip ^= 1u;
+		}
+		HIP_TRY(hipEventRecord(ev[1], stream));
+		HIP_TRY(ses.add_stream(&stream2));
+		hipEvent_t ev_fwd[2], ev_pass1;
+		for (hipEvent_t& e : ev_back) HIP_TRY(ses.sync_event(&e));
+		for (hipEvent_t& e : ev_fwd) HIP_TRY(ses.sync_event(&e));
+		HIP_TRY(ses.sync_event(&ev_pass1));
+		HIP_TRY(hipEventRecord(ev_pass1, stream));
+		HIP_TRY(hipStreamWaitEvent(stream2, ev_pass1, 0));   // the kept columns (and the uploads) are complete
+		HIP_TRY(recompute(0));
+		uint32_t aflip = 0;
+		const Buf* prev_alpha = nullptr;
+		for (uint32_t w = 0; w < n_windows; ++w) {
+			const uint32_t lo = w * K, hi = std::min(n, lo + K);
+			const Buf* half = wstore.data() + (size_t)(w & 1u) * K;
+			const Buf* last_beta = hi == n ? nullptr : &ckpt[w];
+			HIP_TRY(hipStreamWaitEvent(stream, ev_back[w & 1u], 0));
+			if (w + 1 < n_windows) {
+				if (w >= 1) HIP_TRY(hipStreamWaitEvent(stream2, ev_fwd[(w - 1) & 1u], 0));   // the forward pass of window w - 1 is done with that half
+				HIP_TRY(recompute(w + 1));
+			}
+			for (uint32_t c = lo; c < hi; ++c) {
+				const Buf* beta = c == hi - 1 ? last_beta : &half[c - lo];
+				Buf& out = alpha[aflip];
+				out.blocks = fw_blocks[c];
+				HIP_TRY(launch_forward(fwd_args(c, prev_alpha, beta, &out, d_glpart + (size_t)(c - lo) * max_blocks * n_gl), 0, stream));
+				prev_alpha = &out;
+				aflip ^= 1u;
+			}
+			hipLaunchKernelGGL(geno_finish, dim3(hi - lo), dim3(64), 0, stream, d_glpart, (const uint32_t*)d_fwb, lo, max_blocks, ni, n, d_gl);
+			++launches;
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipEventRecord(ev_fwd[w & 1u], stream));
+		}
 		HIP_TRY(hipStreamSynchronize(stream));
-		const double all = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
-		fprintf(stderr, "[whamd timing] genotype: %llu launches submitted in %.1f ms (host), stream drained after %.1f ms\n", (unsigned long long)launches, enq, all);
+		HIP_TRY(hipStreamSynchronize(stream2));
+		return WHAMD_OK;
 	}
-	HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, stream));
-	HIP_TRY(hipStreamSynchronize(stream));
-	float ms01 = 0, ms12 = 0, ms02 = 0;
-	HIP_TRY(hipEventElapsedTime(&ms01, ev[0], ev[1]));
-	HIP_TRY(hipEventElapsedTime(&ms12, ev[1], ev[2]));
-	HIP_TRY(hipEventElapsedTime(&ms02, ev[0], ev[2]));
-	st.backward_ms = ms01;
-	st.forward_ms = ms12;
-	st.total_ms = ms02;
-	st.launches = launches;
-	const double ms_done = phase_ms();
-	ses.close();   // (here, not at the return: the line below times it)
-	if (getenv("WHAMD_DEBUG_TIMING"))
-		fprintf(stderr, "[whamd timing] genotype phases (wall): allocations + uploads %.1f ms, submission + device %.1f ms, freeing %.1f ms\n",
-		        ms_allocated, ms_done - ms_allocated, phase_ms() - ms_done);
-	return WHAMD_OK;
+
+	// the likelihoods, the times of the events, the session's end
+	whamd_status_t collect() {
+		HIP_TRY(hipEventRecord(ev[2], stream));
+		if (getenv("WHAMD_DEBUG_TIMING")) {
+			const double enq = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
+			HIP_TRY(hipStreamSynchronize(stream));
+			const double all = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enqueue0).count();
+			fprintf(stderr, "[whamd timing] genotype: %llu launches submitted in %.1f ms (host), stream drained after %.1f ms\n", (unsigned long long)launches, enq, all);
+		}
+		HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(hipStreamSynchronize(stream));
+		float ms01 = 0, ms12 = 0, ms02 = 0;
+		HIP_TRY(hipEventElapsedTime(&ms01, ev[0], ev[1]));
+		HIP_TRY(hipEventElapsedTime(&ms12, ev[1], ev[2]));
+		HIP_TRY(hipEventElapsedTime(&ms02, ev[0], ev[2]));
+		st.backward_ms = ms01;
+		st.forward_ms = ms12;
+		st.total_ms = ms02;
+		st.launches = launches;
+		const double ms_done = phase_ms();
+		ses.close();   // (here, not at the return: the line below times it)
+		if (getenv("WHAMD_DEBUG_TIMING"))
+			fprintf(stderr, "[whamd timing] genotype phases (wall): allocations + uploads %.1f ms, submission + device %.1f ms, freeing %.1f ms\n",
+			        ms_allocated, ms_done - ms_allocated, phase_ms() - ms_done);
+		return WHAMD_OK;
+	}
+};
+
+}  // namespace
+
+whamd_status_t genotype_solve_columns(const Problem& p, const GenotypeModel& m, int device, uint32_t window_hint,
+                                      std::vector<double>& gl_out, GenotypeStats& st, std::string& msg) {
+	genotype_begin(p, gl_out, st);
+	ColumnCall call(p, m, device, window_hint, gl_out, st, msg);
+	whamd_status_t s = call.choose_window();
+	if (s == WHAMD_OK) s = call.open();
+	if (s == WHAMD_OK) s = call.upload_model();
+	if (s == WHAMD_OK) s = call.take_buffers();
+	if (s == WHAMD_OK) s = call.launch_tables();
+	if (s == WHAMD_OK) s = call.fill_tables();
+	if (s == WHAMD_OK) s = call.n_windows == 1 ? call.submit_two_chains() : call.submit_windows();
+	if (s == WHAMD_OK) s = call.collect();
+	return s;
 }
 
 }  // namespace whamd

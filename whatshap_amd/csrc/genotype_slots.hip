@@ -25,46 +25,21 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "debug_build.h"
 #include "device_runtime.h"
 #include "genotype.h"
+#include "genotype_plan.h"
 #include "slots.h"
 
 namespace whamd {
 
 namespace {
 
-constexpr int GS_MAXLOCAL = 12;      // local slots of a run (<= 6 lane + 3 wave)
 constexpr int GS_MAXA = 16;          // allele assignments (P <= 4)
 constexpr int GS_MAXGL = 1 + 3 * 4;  // normaliser + 3 genotypes of up to 4 individuals
 
-// Per column: which reads end / start in it (local slots, the order does not matter for sums) and which slots hold a read.
-struct GsCol {
-	uint32_t active;                 // slots (local and grid) that hold a read in this column
-	uint8_t n_end, n_start, first_of_table, last_of_table;
-	uint8_t end_slot[GS_MAXLOCAL], start_slot[GS_MAXLOCAL];
-};
-static_assert(sizeof(GsCol) == 32, "GsCol layout");
-// Per column: the read in every slot (tables kernel and combine kernel only).
-struct GsRow {
-	double pe[SLOT_MAXSLOTS];        // error probability of the read's entry (src/genotypecolumncostcomputer.cpp:26-48)
-	uint8_t ind[SLOT_MAXSLOTS + 2];
-	uint8_t allele[SLOT_MAXSLOTS + 2];   // 0 REF, 1 ALT, 2 BLANK
-};
-// Per run.
-struct GsRun {
-	uint32_t c0, ncols, g, L, lw, threads, has_prev, has_next;
-	uint32_t in_occ, in_identity, out_occ, pad0;
-	uint32_t in_pos[8], out_pos[8];      // entry / exit index bit of every slot (SlotRun)
-	unsigned long long tab_off;          // tables of the run: G [2^g][ncols][T][E], V [2^lw][ncols][T][E], S [ncols][64][E]  (doubles, E = 2 P)
-	unsigned long long store_off;        // the run's columns in the two column stores: [ncols][2^g * threads] doubles
-	uint32_t v_off, s_off;               // V and S relative to tab_off
-	uint32_t part_in_f, part_out_f, part_in_b, part_out_b;   // first per-wave partial sum of the exchange columns read / written (forward, backward)
-	uint32_t n_part_in_f, n_part_in_b;   // how many (0: this run does not rescale -- only every GS_RESCALE-th run does)
-	uint32_t emit_f, emit_b;             // 1: the neighbour rescales, leave the per-wave sums of what is handed on
-};
-constexpr uint32_t GS_RESCALE = 4;       // runs between two rescalings of a chain (a run shrinks the values by ~1e-10 at most: far from 1e-308)
 struct GsDev {
 	const GsCol* cols;        // by column
 	const GsRow* rows;        // by column
@@ -448,12 +423,6 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 }
 
 // ---- combine: blockIdx.y = column, blockIdx.x = 256-thread block of the column's lanes (workgroup-major, as the chains stored them)
-struct GsCombineCol {
-	unsigned long long tab_off, store_off;   // the column's run
-	uint32_t v_off, s_off;
-	uint32_t ci, ncols, g, L, threads, n_blocks;
-};
-constexpr uint32_t GS_COMBINE_LANES = 8;   // lanes of a column one thread of the combine kernel goes through (one reduction for all of them)
 // Per lane only U(x, i, a) = forward * backward * prod_p W_i(x)[p][a_p] is formed and summed over the cells x -- the prior and the
 // genotype of every individual depend on (i, a) alone, they are applied to the T x A sums of a column by geno_slot_finish.
 // A thread's lanes share lane & 63, hence the transmission value i: it accumulates A numbers; the block reduces them over the
@@ -587,210 +556,122 @@ __global__ __launch_bounds__(256) void geno_slot_finish(GsDev G, const double* _
 	}
 }
 
-}  // namespace
+// Kernel selection: the instantiations of a transmission count (tb = log2 T; a single individual has two partitions, a pedigree four).
+using RunFn = void (*)(GsDev, GsRun, const double*, double*);
+using CombineFn = void (*)(GsDev, const GsCombineCol*, uint32_t, uint32_t, double*);
+struct GenoRunKernels { RunFn fwd, bwd; CombineFn combine; };
+const RunFn GENO_RUN[3][2] = {{geno_slot_run<0, 2, 0>, geno_slot_run<0, 2, 1>}, {geno_slot_run<2, 4, 0>, geno_slot_run<2, 4, 1>}, {geno_slot_run<4, 4, 0>, geno_slot_run<4, 4, 1>}};
+const CombineFn GENO_COMBINE[3] = {geno_slot_combine<0, 2>, geno_slot_combine<2, 4>, geno_slot_combine<4, 4>};
+GenoRunKernels geno_run_kernels(uint32_t tb) { return {GENO_RUN[tb / 2][0], GENO_RUN[tb / 2][1], GENO_COMBINE[tb / 2]}; }
 
-// Returns WHAMD_OK with `used` = false when the table is not eligible (the caller takes the per-column kernels): a pedigree the
-// planner does not cover, a column that fits no run, stores that do not fit in HBM.
-whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, int device, std::vector<double>& gl_out, GenotypeStats& st,
-                                    bool& used, std::string& msg) {
-	used = false;
-	const uint32_t n = p.n_cols, T = p.T, ni = p.n_ind;
-	if (n < 2 || ni == 0 || ni > 4 || !(p.P == 2 || p.P == 4) || !(T == 1 || T == 4 || T == 16) || (T == 1) != (p.P == 2)) return WHAMD_OK;
-	int l_pref = 0;
-	if (const char* e = debug_env("WHAMD_GENO_SLOT_L")) l_pref = atoi(e);
-	SlotPlan plan;
-	if (!plan_forward_slots(p, l_pref > 0 ? -l_pref : 0, 0, plan, 0, /*genotype_mode=*/true)) return WHAMD_OK;
-	for (const Step& s : plan.steps) if (s.kind != 2) return WHAMD_OK;   // a column no run can take
-	const uint32_t tb = T == 1 ? 0u : (T == 4 ? 2u : 4u), E = 2u * p.P, A = m.A;
-	HIP_TRY(hipSetDevice(device));
-	const size_t n_runs = plan.runs.size();
-	// ---- host descriptors
-	std::vector<GsCol> cols(n);
-	std::vector<GsRow> rows(n);
-	std::vector<GsRun> runs(n_runs);
-	std::vector<GsCombineCol> ccols(n);
-	unsigned long long tab_words = 0, store_words = 0;
-	uint32_t n_partials = 0, max_f = 0, max_blocks = 1;
-	size_t max_lds = 0;
-	for (size_t ri = 0; ri < n_runs; ++ri) {
-		const SlotRun& sr = plan.runs[ri];
-		GsRun& r = runs[ri];
-		r.c0 = sr.c0; r.ncols = sr.ncols; r.g = sr.g; r.L = sr.L; r.lw = sr.lw; r.threads = sr.threads;
-		r.has_prev = sr.c0 > 0 ? 1u : 0u;
-		r.has_next = sr.c0 + sr.ncols < n ? 1u : 0u;
-		r.in_occ = sr.in_occ; r.in_identity = sr.in_identity; r.out_occ = sr.out_occ;
-		std::memcpy(r.in_pos, sr.in_pos, sizeof r.in_pos);
-		std::memcpy(r.out_pos, sr.out_pos, sizeof r.out_pos);
-		const unsigned long long per_unit = (unsigned long long)sr.ncols * T * E;
-		r.tab_off = tab_words;
-		r.v_off = (uint32_t)(per_unit << sr.g);
-		r.s_off = r.v_off + (uint32_t)(per_unit << sr.lw);
-		tab_words += (unsigned long long)r.s_off + (unsigned long long)sr.ncols * 64u * E;
-		r.store_off = store_words;
-		store_words += (unsigned long long)sr.ncols * ((unsigned long long)sr.threads << sr.g);
-		max_f = std::max(max_f, sr.L + sr.g);
-		const uint32_t nw = (sr.threads >> 6) << sr.g;   // per-wave partial sums of what the run hands on, one set per direction
-		r.part_out_f = n_partials; n_partials += nw;
-		r.part_out_b = n_partials; n_partials += nw;
-		const uint32_t blocks = (uint32_t)((((size_t)sr.threads << sr.g) + 256u * GS_COMBINE_LANES - 1u) / (256u * GS_COMBINE_LANES));
-		max_blocks = std::max(max_blocks, blocks);
-		const size_t waves = sr.threads >> 6;
-		max_lds = std::max(max_lds, ((size_t)2 * sr.threads + waves * sr.ncols * T * E + (size_t)sr.ncols * T * A + ((sr.ncols + 1) & ~1u) + 16) * 8 + (size_t)sr.ncols * sizeof(GsCol));
-		for (uint32_t ci = 0; ci < sr.ncols; ++ci) {
-			const uint32_t c = sr.c0 + ci;
-			const PedSlotRow& pr = plan.prows[c];
-			const SlotBtCol& bc = plan.bt_cols[c];
-			GsCol& cd = cols[c];
-			GsRow& rw = rows[c];
-			std::memset(&cd, 0, sizeof cd);
-			std::memset(&rw, 0, sizeof rw);
-			const ColumnEntry* col = p.col_begin(c);
-			for (uint32_t j = 0; j < p.k[c]; ++j) {
-				const uint32_t s = bc.slot[j];
-				cd.active |= 1u << s;
-				rw.pe[s] = m.error_prob[p.col_ptr[c] + j];
-				rw.ind[s] = col[j].sample;
-				rw.allele[s] = col[j].allele;
-			}
-			cd.first_of_table = c == 0;
-			cd.last_of_table = c + 1 == n;
-			if (pr.n_end > (uint32_t)GS_MAXLOCAL || pr.pad[0] > (uint32_t)GS_MAXLOCAL) return WHAMD_OK;
-			cd.n_end = (uint8_t)pr.n_end;
-			for (uint32_t e = 0; e < pr.n_end; ++e) cd.end_slot[e] = plan.end_slots[plan.end_off[ri] + bc.kf + e];
-			cd.n_start = (uint8_t)pr.pad[0];
-			for (uint32_t e = 0; e < pr.pad[0]; ++e) cd.start_slot[e] = plan.start_slots[plan.start_off[ri] + pr.pad[1] + e];
-			GsCombineCol& cc = ccols[c];
-			cc.tab_off = r.tab_off; cc.store_off = r.store_off; cc.v_off = r.v_off; cc.s_off = r.s_off;
-			cc.ci = ci; cc.ncols = sr.ncols; cc.g = sr.g; cc.L = sr.L; cc.threads = sr.threads; cc.n_blocks = blocks;
-		}
-	}
-	for (size_t ri = 0; ri < n_runs; ++ri) {   // the partial sums a run reads are the ones its neighbour writes; every GS_RESCALE-th run of a chain rescales
-		GsRun& r = runs[ri];
-		if (ri > 0 && ri % GS_RESCALE == 0) {
-			r.part_in_f = runs[ri - 1].part_out_f; r.n_part_in_f = (plan.runs[ri - 1].threads >> 6) << plan.runs[ri - 1].g;
-			runs[ri - 1].emit_f = 1;
-		}
-		if (ri + 1 < n_runs && (n_runs - 1 - ri) % GS_RESCALE == 0) {
-			r.part_in_b = runs[ri + 1].part_out_b; r.n_part_in_b = (plan.runs[ri + 1].threads >> 6) << plan.runs[ri + 1].g;
-			runs[ri + 1].emit_b = 1;
-		}
-	}
-	size_t free_b = 0, total_b = 0;
-	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-	if (free_b < total_b / 2) {   // a phasing table of this process may have left its arena in the cache (dp_device.hip)
-		arena_release();
-		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-	}
-	free_b += genotype_slab_idle_bytes(device);   // the column store kept from an earlier call is available to this one
-	constexpr uint32_t BATCH = 512;
-	const double fixed = (double)tab_words * 8 + (double)BATCH * max_blocks * T * A * 8 + 4.0 * ((double)(1ull << max_f) * T * 8) +
-	                     (double)n * (sizeof(GsCol) + sizeof(GsRow) + sizeof(GsCombineCol) + 8.0 * T * A + 8);
-	if (max_lds > 150 * 1024) return WHAMD_OK;
-	// ---- windows.  The column stores are what grows with the table (a trio at coverage 15: 2 MiB per column and chain).  When both do not fit,
-	// the runs are cut into WINDOWS (the reference keeps sqrt(n) columns and recomputes, src/genotypedptable.cpp:116-157,159-195,324): pass 1
-	// runs the whole forward chain keeping only the exchange column at every window boundary (and the columns of the newest window); then,
-	// newest window first, the forward columns of a window are recomputed from its kept exchange column, the backward chain runs through the
-	// window, and the window's likelihoods are formed.  Two sets of window stores: the recomputation of window w - 1 runs beside the backward
-	// chain and the combine of window w.  One more forward pass, any table length.
-	struct GsWindow { size_t r0, r1; unsigned long long words; uint32_t c0, c1; };
-	std::vector<GsWindow> windows;
-	{
-		const double room = 0.8 * (double)free_b - fixed - (double)(2ull << 30);
-		unsigned long long budget_words = ~0ull;   // per store
-		if (2.0 * (double)store_words * 8 > room) budget_words = room > 0 ? (unsigned long long)(room / 4.0 / 8.0) : 0ull;
-		if (const char* e = getenv("WHAMD_GENO_WINDOW_BYTES")) budget_words = std::min<unsigned long long>(budget_words, std::strtoull(e, nullptr, 10) / 8);
-		GsWindow cur{0, 0, 0, 0, 0};
-		for (size_t ri = 0; ri < n_runs; ++ri) {
-			const unsigned long long words = (unsigned long long)plan.runs[ri].ncols * ((unsigned long long)plan.runs[ri].threads << plan.runs[ri].g);
-			if (words > budget_words) return WHAMD_OK;   // a single run beyond the budget: the per-column path
-			if (cur.words + words > budget_words) {
-				cur.r1 = ri;
-				windows.push_back(cur);
-				cur = GsWindow{ri, ri, 0, 0, 0};
-			}
-			runs[ri].store_off = cur.words;   // (relative to the window's stores)
-			cur.words += words;
-		}
-		cur.r1 = n_runs;
-		windows.push_back(cur);
-		for (GsWindow& wdw : windows) {
-			wdw.c0 = plan.runs[wdw.r0].c0;
-			wdw.c1 = plan.runs[wdw.r1 - 1].c0 + plan.runs[wdw.r1 - 1].ncols;
-			for (uint32_t c = wdw.c0; c < wdw.c1; ++c) ccols[c].store_off = runs[0].store_off;   // (set per column below)
-		}
-		for (size_t ri = 0; ri < n_runs; ++ri)
-			for (uint32_t ci = 0; ci < plan.runs[ri].ncols; ++ci) ccols[plan.runs[ri].c0 + ci].store_off = runs[ri].store_off;
-	}
-	const size_t n_windows = windows.size();
-	unsigned long long window_words = 0;
-	for (const GsWindow& wdw : windows) window_words = std::max(window_words, wdw.words);
-	const size_t n_sets = n_windows > 1 ? 2 : 1;   // (fstore, bstore) pairs
-	used = true;
-	gl_out.assign((size_t)ni * n * 3, 0.0);
-	st = GenotypeStats();
-	st.n_columns = n;
-	st.transmissions = T;
-	st.window = n_windows > 1 ? windows[0].c1 - windows[0].c0 : n;
-	for (uint32_t c = 0; c < n; ++c) { st.n_cells += 1ull << p.k[c]; st.max_coverage = std::max<uint32_t>(st.max_coverage, p.k[c]); }
-	GenotypeSlabHold slab;
-	Session keep;   // its own stream carries the forward chain; four events for the times
-	const whamd_status_t opened = keep.open(device, 4, msg);
-	if (opened != WHAMD_OK) return opened;
-	hipStream_t sf = keep.stream, sb = nullptr, sc = nullptr;
-	HIP_TRY(keep.add_stream(&sb));
-	if (n_windows > 1 || debug_env("WHAMD_GENO_PIECES")) HIP_TRY(keep.add_stream(&sc));   // (likelihood sums beside the chains)
-	auto alloc = [&](void** dptr, size_t bytes) { return keep.fresh_block(dptr, bytes); };
-	auto up = [&](void** dptr, const void* src, size_t bytes) -> hipError_t {
-		hipError_t e = alloc(dptr, bytes);
-		if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dptr, src, bytes, hipMemcpyHostToDevice, sf);
-		return e;
-	};
-	std::vector<double> rho(n, 0.0);
-	const uint32_t nb = 2 * p.n_triples + 1;
-	if (T > 1) for (uint32_t c = 0; c < n; ++c) rho[c] = m.transition_bern[(size_t)c * nb + 1] / m.transition_bern[(size_t)c * nb];
+// One run-path solve: what the steps share, one member function per step (genotype_solve_slots is their sequence).
+struct RunCall : GenotypeCall {
+	const Problem& p;
+	const GenotypeModel& m;
+	const int device;
+	std::vector<double>& gl_out;
+	GenotypeStats& st;
+	std::string& msg;
+	const uint32_t n, T, ni, tb, E, A;
+	GenoRunPlan pl;
+	size_t n_runs = 0, n_windows = 0;
+	hipStream_t sf = nullptr, sb = nullptr, sc = nullptr;   // forward chain (the session's own stream), backward chain, likelihood sums beside the chains
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	GsDev G{};
-	void *d_cols, *d_rows, *d_prior, *d_rho, *d_gidx, *d_h2p, *d_runs, *d_ccols, *d_tab, *d_fs, *d_bs, *d_part, *d_glpart, *d_gl;
-	double* d_x[4];
-	HIP_TRY(up(&d_cols, cols.data(), cols.size() * sizeof(GsCol)));
-	HIP_TRY(up(&d_rows, rows.data(), rows.size() * sizeof(GsRow)));
-	HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
-	HIP_TRY(up(&d_rho, rho.data(), rho.size() * 8));
-	HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
-	HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
-	HIP_TRY(up(&d_runs, runs.data(), runs.size() * sizeof(GsRun)));
-	HIP_TRY(up(&d_ccols, ccols.data(), ccols.size() * sizeof(GsCombineCol)));
-	HIP_TRY(alloc(&d_tab, (size_t)tab_words * 8));
-	d_fs = genotype_slab_acquire(device, 2 * n_sets * (size_t)window_words * 8);   // the column stores in the block kept between calls
-	if (d_fs) slab.device = device;
-	else HIP_TRY(alloc(&d_fs, 2 * n_sets * (size_t)window_words * 8));
-	d_bs = (double*)d_fs + n_sets * window_words;
+	void *d_runs = nullptr, *d_ccols = nullptr, *d_fs = nullptr, *d_bs = nullptr, *d_glpart = nullptr, *d_gl = nullptr;
 	void* d_check = nullptr;   // the forward exchange column entering every window but the first
-	const size_t check_bytes = ((size_t)1 << max_f) * T * 8;
-	if (n_windows > 1) HIP_TRY(alloc(&d_check, (n_windows - 1) * check_bytes));
-	HIP_TRY(alloc(&d_part, (size_t)n_partials * 8));
-	HIP_TRY(alloc(&d_glpart, (size_t)BATCH * max_blocks * T * A * 8));
-	HIP_TRY(alloc(&d_gl, gl_out.size() * 8));
-	for (double*& x : d_x) HIP_TRY(alloc((void**)&x, ((size_t)1 << max_f) * T * 8));
-	G.cols = (const GsCol*)d_cols; G.rows = (const GsRow*)d_rows; G.prior = (const double*)d_prior; G.rho = (const double*)d_rho;
-	G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p; G.tab = (double*)d_tab; G.fstore = (double*)d_fs; G.bstore = (double*)d_bs;
-	G.dbg = nullptr;
-#ifdef WHAMD_GENO_STAMPS
-	{ void* d_dbg = nullptr; HIP_TRY(alloc(&d_dbg, 128)); HIP_TRY(hipMemset(d_dbg, 0, 128)); G.dbg = (unsigned long long*)d_dbg; }
-#endif
-	G.partials = (double*)d_part; G.T = T; G.A = A; G.P = p.P; G.n_ind = ni; G.n_cols = n;
-	const hipEvent_t ev[4] = {keep.ev[0], keep.ev[1], keep.ev[2], keep.ev[3]};
-	using RunFn = void (*)(GsDev, GsRun, const double*, double*);
-	RunFn fwd = nullptr, bwd = nullptr;
-	if (tb == 0) { fwd = geno_slot_run<0, 2, 0>; bwd = geno_slot_run<0, 2, 1>; }
-	else if (tb == 2) { fwd = geno_slot_run<2, 4, 0>; bwd = geno_slot_run<2, 4, 1>; }
-	else { fwd = geno_slot_run<4, 4, 0>; bwd = geno_slot_run<4, 4, 1>; }
-	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	size_t check_bytes = 0;
+	double* d_x[4] = {nullptr, nullptr, nullptr, nullptr};   // exchange columns: two of the forward chain, two of the backward chain
+	GenoRunKernels kn{};
 	uint64_t launches = 0;
-	HIP_TRY(hipEventRecord(ev[0], sf));
-	{
+
+	RunCall(const Problem& p_, const GenotypeModel& m_, int device_, std::vector<double>& gl_out_, GenotypeStats& st_, std::string& msg_)
+	    : p(p_), m(m_), device(device_), gl_out(gl_out_), st(st_), msg(msg_), n(p_.n_cols), T(p_.T), ni(p_.n_ind),
+	      tb(p_.T == 1 ? 0u : (p_.T == 4 ? 2u : 4u)), E(2u * p_.P), A(m_.A) {}
+
+	// the host plan (genotype_plan.cpp); eligible = false: the table takes the per-column kernels
+	whamd_status_t plan(bool& eligible) {
+		eligible = false;
+		int l_pref = 0;
+		if (const char* e = debug_env("WHAMD_GENO_SLOT_L")) l_pref = atoi(e);
+		if (!geno_plan_runs(p, m, l_pref, pl)) return WHAMD_OK;
+		HIP_TRY(hipSetDevice(device));
+		size_t free_b = 0;
+		const whamd_status_t queried = genotype_free_bytes(device, free_b, msg);
+		if (queried != WHAMD_OK) return queried;
+		unsigned long long cap_words = ~0ull;
+		if (const char* e = getenv("WHAMD_GENO_WINDOW_BYTES")) cap_words = std::strtoull(e, nullptr, 10) / 8;
+		if (!geno_plan_windows(pl, T, A, free_b, cap_words)) return WHAMD_OK;
+		n_runs = pl.runs.size();
+		n_windows = pl.windows.size();
+		eligible = true;
+		return WHAMD_OK;
+	}
+
+	whamd_status_t open() {
+		genotype_begin(p, gl_out, st);
+		st.window = n_windows > 1 ? pl.windows[0].c1 - pl.windows[0].c0 : n;
+		const whamd_status_t opened = ses.open(device, 4, msg);   // its own stream carries the forward chain; four events for the times
+		if (opened != WHAMD_OK) return opened;
+		sf = ses.stream;
+		HIP_TRY(ses.add_stream(&sb));
+		if (n_windows > 1 || debug_env("WHAMD_GENO_PIECES")) HIP_TRY(ses.add_stream(&sc));
+		for (int q = 0; q < 4; ++q) ev[q] = ses.ev[q];
+		return WHAMD_OK;
+	}
+
+	// descriptors and model, one copy per array
+	whamd_status_t upload_plan() {
+		std::vector<double> rho(n, 0.0);
+		const uint32_t nb = 2 * p.n_triples + 1;
+		if (T > 1) for (uint32_t c = 0; c < n; ++c) rho[c] = m.transition_bern[(size_t)c * nb + 1] / m.transition_bern[(size_t)c * nb];
+		void *d_cols, *d_rows, *d_prior, *d_rho, *d_gidx, *d_h2p;
+		HIP_TRY(up(&d_cols, pl.cols.data(), pl.cols.size() * sizeof(GsCol)));
+		HIP_TRY(up(&d_rows, pl.rows.data(), pl.rows.size() * sizeof(GsRow)));
+		HIP_TRY(up(&d_prior, m.allele_prior.data(), m.allele_prior.size() * 8));
+		HIP_TRY(up(&d_rho, rho.data(), rho.size() * 8));
+		HIP_TRY(up(&d_gidx, m.genotype_index.data(), m.genotype_index.size()));
+		HIP_TRY(up(&d_h2p, p.h2p.data(), p.h2p.size()));
+		HIP_TRY(up(&d_runs, pl.runs.data(), pl.runs.size() * sizeof(GsRun)));
+		HIP_TRY(up(&d_ccols, pl.ccols.data(), pl.ccols.size() * sizeof(GsCombineCol)));
+		G.cols = (const GsCol*)d_cols; G.rows = (const GsRow*)d_rows; G.prior = (const double*)d_prior; G.rho = (const double*)d_rho;
+		G.gidx = (const uint8_t*)d_gidx; G.h2p = (const int8_t*)d_h2p;
+		G.T = T; G.A = A; G.P = p.P; G.n_ind = ni; G.n_cols = n;
+		return WHAMD_OK;
+	}
+
+	// tables, the column stores (in the block kept between calls), exchange columns, partial sums, the result
+	whamd_status_t take_buffers() {
+		void *d_tab = nullptr, *d_part = nullptr;
+		HIP_TRY(alloc(&d_tab, (size_t)pl.tab_words * 8));
+		HIP_TRY(take_store(&d_fs, 2 * pl.n_sets * (size_t)pl.window_words * 8));
+		d_bs = (double*)d_fs + pl.n_sets * pl.window_words;
+		check_bytes = ((size_t)1 << pl.max_f) * T * 8;
+		if (n_windows > 1) HIP_TRY(alloc(&d_check, (n_windows - 1) * check_bytes));
+		HIP_TRY(alloc(&d_part, (size_t)pl.n_partials * 8));
+		HIP_TRY(alloc(&d_glpart, (size_t)GS_COMBINE_BATCH * pl.max_blocks * T * A * 8));
+		HIP_TRY(alloc(&d_gl, gl_out.size() * 8));
+		for (double*& x : d_x) HIP_TRY(alloc((void**)&x, ((size_t)1 << pl.max_f) * T * 8));
+		G.tab = (double*)d_tab; G.fstore = (double*)d_fs; G.bstore = (double*)d_bs; G.partials = (double*)d_part;
+		G.dbg = nullptr;
+#ifdef WHAMD_GENO_STAMPS
+		{ void* d_dbg = nullptr; HIP_TRY(alloc(&d_dbg, 128)); HIP_TRY(hipMemset(d_dbg, 0, 128)); G.dbg = (unsigned long long*)d_dbg; }
+#endif
+		return WHAMD_OK;
+	}
+
+	// the kernels of this T; the run kernels take up to 160 KiB of LDS
+	whamd_status_t launch_tables() {
+		kn = geno_run_kernels(tb);
+		for (RunFn fn : {kn.fwd, kn.bwd}) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		return WHAMD_OK;
+	}
+
+	// the G / V / S tables of every run, at full-chip width, before the chains start
+	whamd_status_t fill_tables() {
+		HIP_TRY(hipEventRecord(ev[0], sf));
 		uint32_t most = 0;
-		for (const GsRun& r : runs) most = std::max<uint32_t>(most, ((r.ncols * T) << r.g) + ((r.ncols * T) << r.lw) + r.ncols * 64u);
+		for (const GsRun& r : pl.runs) most = std::max<uint32_t>(most, ((r.ncols * T) << r.g) + ((r.ncols * T) << r.lw) + r.ncols * 64u);
 		const uint32_t bx = std::max(1u, std::min(256u, (most + 255u) / 256u));
 		for (size_t r0 = 0; r0 < n_runs; r0 += 32768) {
 			const uint32_t ny = (uint32_t)std::min<size_t>(32768, n_runs - r0);
@@ -798,46 +679,44 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 			++launches;
 		}
 		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ev[1], sf));
+		HIP_TRY(hipStreamWaitEvent(sb, ev[1], 0));   // uploads and tables are complete
+		return WHAMD_OK;
 	}
-	HIP_TRY(hipEventRecord(ev[1], sf));
-	HIP_TRY(hipStreamWaitEvent(sb, ev[1], 0));   // uploads and tables are complete
-	auto lds_of = [&](const GsRun& r) {
-		const size_t waves = r.threads >> 6;
-		return ((size_t)2 * r.threads + waves * r.ncols * T * E + (size_t)r.ncols * T * A + ((r.ncols + 1) & ~1u) + 16) * 8 + (size_t)r.ncols * sizeof(GsCol);
-	};
-	auto with_stores = [&](size_t set) {
+
+	GsDev with_stores(size_t set) const {
 		GsDev g = G;
-		g.fstore = (double*)d_fs + set * window_words;
-		g.bstore = (double*)d_bs + set * window_words;
+		g.fstore = (double*)d_fs + set * pl.window_words;
+		g.bstore = (double*)d_bs + set * pl.window_words;
 		return g;
-	};
-	auto launch_fwd = [&](size_t ri, const GsDev& g) {
-		const GsRun& r = runs[ri];
-		hipLaunchKernelGGL(fwd, dim3(1u << r.g), dim3(r.threads), lds_of(r), sf, g, r, (const double*)d_x[ri & 1], d_x[(ri & 1) ^ 1]);
+	}
+	void launch_fwd(size_t ri, const GsDev& g) {
+		const GsRun& r = pl.runs[ri];
+		hipLaunchKernelGGL(kn.fwd, dim3(1u << r.g), dim3(r.threads), run_lds_bytes(r.threads, r.ncols, T, E, A), sf, g, r, (const double*)d_x[ri & 1], d_x[(ri & 1) ^ 1]);
 		++launches;
-	};
-	auto launch_bwd = [&](size_t ri, const GsDev& g) {
-		const GsRun& r = runs[ri];
-		hipLaunchKernelGGL(bwd, dim3(1u << r.g), dim3(r.threads), lds_of(r), sb, g, r, (const double*)d_x[2 + (ri & 1)], d_x[2 + ((ri & 1) ^ 1)]);
+	}
+	void launch_bwd(size_t ri, const GsDev& g) {
+		const GsRun& r = pl.runs[ri];
+		hipLaunchKernelGGL(kn.bwd, dim3(1u << r.g), dim3(r.threads), run_lds_bytes(r.threads, r.ncols, T, E, A), sb, g, r, (const double*)d_x[2 + (ri & 1)], d_x[2 + ((ri & 1) ^ 1)]);
 		++launches;
-	};
-	auto launch_combine = [&](const GsWindow& wdw, const GsDev& g, hipStream_t stream) {
-		for (uint32_t c0 = wdw.c0; c0 < wdw.c1; c0 += BATCH) {
-			const uint32_t ncol = std::min(BATCH, wdw.c1 - c0);
+	}
+	// likelihood sums and normalisation of columns [c0, c1): a combine and a finish launch per GS_COMBINE_BATCH columns
+	void launch_combine(uint32_t c_first, uint32_t c_end, const GsDev& g, hipStream_t stream) {
+		for (uint32_t c0 = c_first; c0 < c_end; c0 += GS_COMBINE_BATCH) {
+			const uint32_t ncol = std::min(GS_COMBINE_BATCH, c_end - c0);
 			uint32_t gx = 1;
-			for (uint32_t c = c0; c < c0 + ncol; ++c) gx = std::max(gx, ccols[c].n_blocks);
-			if (tb == 0) hipLaunchKernelGGL((geno_slot_combine<0, 2>), dim3(gx, ncol), dim3(256), 0, stream, g, (const GsCombineCol*)d_ccols, c0, max_blocks, (double*)d_glpart);
-			else if (tb == 2) hipLaunchKernelGGL((geno_slot_combine<2, 4>), dim3(gx, ncol), dim3(256), 0, stream, g, (const GsCombineCol*)d_ccols, c0, max_blocks, (double*)d_glpart);
-			else hipLaunchKernelGGL((geno_slot_combine<4, 4>), dim3(gx, ncol), dim3(256), 0, stream, g, (const GsCombineCol*)d_ccols, c0, max_blocks, (double*)d_glpart);
-			hipLaunchKernelGGL(geno_slot_finish, dim3(ncol), dim3(256), 0, stream, g, (const double*)d_glpart, (const GsCombineCol*)d_ccols, c0, max_blocks, (double*)d_gl);
+			for (uint32_t c = c0; c < c0 + ncol; ++c) gx = std::max(gx, pl.ccols[c].n_blocks);
+			hipLaunchKernelGGL(kn.combine, dim3(gx, ncol), dim3(256), 0, stream, g, (const GsCombineCol*)d_ccols, c0, pl.max_blocks, (double*)d_glpart);
+			hipLaunchKernelGGL(geno_slot_finish, dim3(ncol), dim3(256), 0, stream, g, (const double*)d_glpart, (const GsCombineCol*)d_ccols, c0, pl.max_blocks, (double*)d_gl);
 			launches += 2;
 		}
-	};
-	if (n_windows == 1) {
-		// the two chains, submissions interleaved so that neither hardware queue runs dry.  (WHAMD_GENO_PIECES = k forms the likelihood sums of
-		// a k-th of the table on a third stream as soon as both chains have passed it, beside the rest of the chains.  Measured: no gain --
-		// the combine streams the stores at 3 TB/s and the chains slow down by what it saves: trio of 20 000 columns, chains 37 -> 54 ms,
-		// combine 24 -> 6 ms.  One piece after the chains is the default.)
+	}
+
+	// The two chains, submissions interleaved so that neither hardware queue runs dry.  (WHAMD_GENO_PIECES = k forms the likelihood sums of
+	// a k-th of the table on a third stream as soon as both chains have passed it, beside the rest of the chains.  Measured: no gain --
+	// the combine streams the stores at 3 TB/s and the chains slow down by what it saves: trio of 20 000 columns, chains 37 -> 54 ms,
+	// combine 24 -> 6 ms.  One piece after the chains is the default.)
+	whamd_status_t submit_one_window() {
 		const GsDev g = with_stores(0);
 		size_t n_pieces = 1;
 		const bool third_stream = debug_env("WHAMD_GENO_PIECES") != nullptr;
@@ -845,7 +724,7 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 		auto piece_lo = [&](size_t k) { return n_runs * k / n_pieces; };
 		std::vector<hipEvent_t> pf(n_pieces), pb(n_pieces);
 		for (size_t k = 0; k < n_pieces; ++k)
-			for (hipEvent_t* e : {&pf[k], &pb[k]}) HIP_TRY(keep.sync_event(e));
+			for (hipEvent_t* e : {&pf[k], &pb[k]}) HIP_TRY(ses.sync_event(e));
 		size_t rf = 0, rb = n_runs, kf = 0, kb = n_pieces;
 		while (rf < n_runs || rb > 0) {
 			if (rf < n_runs) {
@@ -877,34 +756,36 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 				HIP_TRY(hipStreamWaitEvent(sc, pb[k], 0));
 			}
 			const size_t r0 = piece_lo(k), r1 = piece_lo(k + 1);
-			GsWindow piece{r0, r1, 0, plan.runs[r0].c0, plan.runs[r1 - 1].c0 + plan.runs[r1 - 1].ncols};
-			launch_combine(piece, g, cs);
+			launch_combine(pl.runs[r0].c0, pl.runs[r1 - 1].c0 + pl.runs[r1 - 1].ncols, g, cs);
 		}
 		if (third_stream) {
 			hipEvent_t done = nullptr;
-			HIP_TRY(keep.sync_event(&done));
+			HIP_TRY(ses.sync_event(&done));
 			HIP_TRY(hipEventRecord(done, sc));
 			HIP_TRY(hipStreamWaitEvent(sf, done, 0));
 		}
-	} else {
-		// pass 1: the whole forward chain; the exchange column entering every window is kept.  Every window writes its columns into its set and
-		// only the newest window's survive: the store of the run kernel is unconditional (under a `keep` branch the counter wait at the join
-		// became a wait for the store itself, every column: 42 -> 48 ms for the chains of 50 000 columns)
+		return WHAMD_OK;
+	}
+
+	// Pass 1: the whole forward chain; the exchange column entering every window is kept.  Every window writes its columns into its set and
+	// only the newest window's survive: the store of the run kernel is unconditional (under a `keep` branch the counter wait at the join
+	// became a wait for the store itself, every column: 42 -> 48 ms for the chains of 50 000 columns).  Then, newest window first: (recompute
+	// the forward columns,) backward chain, likelihoods -- forward of window w - 1 beside backward / combine of w.
+	whamd_status_t submit_windows() {
 		const size_t last = n_windows - 1;
 		std::vector<hipEvent_t> ef(n_windows), eb(n_windows), ec(n_windows);
 		for (size_t w = 0; w < n_windows; ++w)
-			for (hipEvent_t* e : {&ef[w], &eb[w], &ec[w]}) HIP_TRY(keep.sync_event(e));
+			for (hipEvent_t* e : {&ef[w], &eb[w], &ec[w]}) HIP_TRY(ses.sync_event(e));
 		for (size_t w = 0; w < n_windows; ++w) {
-			const GsWindow& wdw = windows[w];
+			const GsWindow& wdw = pl.windows[w];
 			if (w > 0) HIP_TRY(hipMemcpyAsync((char*)d_check + (w - 1) * check_bytes, d_x[wdw.r0 & 1], check_bytes, hipMemcpyDeviceToDevice, sf));
 			const GsDev g = with_stores(w % 2);
 			for (size_t ri = wdw.r0; ri < wdw.r1; ++ri) launch_fwd(ri, g);
 		}
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(ef[last], sf));
-		// newest window first: (recompute the forward columns,) backward chain, likelihoods -- forward of window w - 1 beside backward / combine of w
 		for (size_t w = n_windows; w-- > 0;) {
-			const GsWindow& wdw = windows[w];
+			const GsWindow& wdw = pl.windows[w];
 			const GsDev g = with_stores(w % 2);
 			if (w != last) {
 				if (w + 2 < n_windows) HIP_TRY(hipStreamWaitEvent(sf, ec[w + 2], 0));   // the stores of this set are free again
@@ -917,44 +798,68 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 			for (size_t ri = wdw.r1; ri-- > wdw.r0;) launch_bwd(ri, g);
 			HIP_TRY(hipEventRecord(eb[w], sb));
 			HIP_TRY(hipStreamWaitEvent(sc, eb[w], 0));
-			launch_combine(wdw, g, sc);
+			launch_combine(wdw.c0, wdw.c1, g, sc);
 			HIP_TRY(hipEventRecord(ec[w], sc));
 			HIP_TRY(hipGetLastError());
 		}
 		HIP_TRY(hipEventRecord(ev[2], sb));
 		HIP_TRY(hipStreamWaitEvent(sf, ec[0], 0));
-		HIP_TRY(hipStreamWaitEvent(sf, ec[n_windows > 1 ? 1 : 0], 0));
+		HIP_TRY(hipStreamWaitEvent(sf, ec[1], 0));
+		return WHAMD_OK;
 	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ev[3], sf));
-	HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, sf));
-	HIP_TRY(hipStreamSynchronize(sf));
-	HIP_TRY(hipStreamSynchronize(sb));
-	if (sc) HIP_TRY(hipStreamSynchronize(sc));
+
+	// the likelihoods, the times of the events
+	whamd_status_t collect() {
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(ev[3], sf));
+		HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, sf));
+		HIP_TRY(hipStreamSynchronize(sf));
+		HIP_TRY(hipStreamSynchronize(sb));
+		if (sc) HIP_TRY(hipStreamSynchronize(sc));
 #ifdef WHAMD_GENO_STAMPS
-	{
-		unsigned long long d[16];
-		HIP_TRY(hipMemcpy(d, G.dbg, sizeof d, hipMemcpyDeviceToHost));
-		for (int dir = 0; dir < 2; ++dir) {
-			const double runs = (double)std::max<unsigned long long>(d[dir * 8 + 6], 1);
-			fprintf(stderr, "[whamd geno stamps] %s: %llu runs, %.1f columns each; cycles since kernel start (wave 0 / workgroup 0): staged %.0f, entered + reduced %.0f, loop done %.0f, exit %.0f\n",
-			        dir ? "backward" : "forward", d[dir * 8 + 6], d[dir * 8 + 7] / runs, d[dir * 8 + 0] / runs, d[dir * 8 + 1] / runs, d[dir * 8 + 2] / runs, d[dir * 8 + 3] / runs);
+		{
+			unsigned long long d[16];
+			HIP_TRY(hipMemcpy(d, G.dbg, sizeof d, hipMemcpyDeviceToHost));
+			for (int dir = 0; dir < 2; ++dir) {
+				const double runs = (double)std::max<unsigned long long>(d[dir * 8 + 6], 1);
+				fprintf(stderr, "[whamd geno stamps] %s: %llu runs, %.1f columns each; cycles since kernel start (wave 0 / workgroup 0): staged %.0f, entered + reduced %.0f, loop done %.0f, exit %.0f\n",
+				        dir ? "backward" : "forward", d[dir * 8 + 6], d[dir * 8 + 7] / runs, d[dir * 8 + 0] / runs, d[dir * 8 + 1] / runs, d[dir * 8 + 2] / runs, d[dir * 8 + 3] / runs);
+			}
 		}
-	}
 #endif
-	float t_tab = 0, t_chain = 0, t_all = 0;
-	HIP_TRY(hipEventElapsedTime(&t_tab, ev[0], ev[1]));
-	HIP_TRY(hipEventElapsedTime(&t_chain, ev[1], ev[2]));
-	HIP_TRY(hipEventElapsedTime(&t_all, ev[0], ev[3]));
-	st.backward_ms = t_chain;              // the two chains side by side
-	st.forward_ms = t_all - t_chain;       // tables + combine
-	st.total_ms = t_all;
-	st.launches = launches;
-	st.slot_runs = (uint32_t)n_runs;
-	if (getenv("WHAMD_DEBUG_TIMING"))
-		fprintf(stderr, "[whamd timing] genotype slot runs: %zu runs (%.1f columns per run), %zu window(s), tables %.2f ms, chains %.2f ms, combine %.2f ms; tables %.1f MB, stores %zu x %.1f MB\n",
-		        n_runs, (double)n / n_runs, n_windows, t_tab, t_chain, t_all - t_chain - t_tab, tab_words * 8e-6, 2 * n_sets, window_words * 8e-6);
-	return WHAMD_OK;
+		float t_tab = 0, t_chain = 0, t_all = 0;
+		HIP_TRY(hipEventElapsedTime(&t_tab, ev[0], ev[1]));
+		HIP_TRY(hipEventElapsedTime(&t_chain, ev[1], ev[2]));
+		HIP_TRY(hipEventElapsedTime(&t_all, ev[0], ev[3]));
+		st.backward_ms = t_chain;              // the two chains side by side
+		st.forward_ms = t_all - t_chain;       // tables + combine
+		st.total_ms = t_all;
+		st.launches = launches;
+		st.slot_runs = (uint32_t)n_runs;
+		if (getenv("WHAMD_DEBUG_TIMING"))
+			fprintf(stderr, "[whamd timing] genotype slot runs: %zu runs (%.1f columns per run), %zu window(s), tables %.2f ms, chains %.2f ms, combine %.2f ms; tables %.1f MB, stores %zu x %.1f MB\n",
+			        n_runs, (double)n / n_runs, n_windows, t_tab, t_chain, t_all - t_chain - t_tab, pl.tab_words * 8e-6, 2 * pl.n_sets, pl.window_words * 8e-6);
+		return WHAMD_OK;
+	}
+};
+
+}  // namespace
+
+// Returns WHAMD_OK with `used` = false when the table is not eligible (the caller takes the per-column kernels): a pedigree the
+// planner does not cover, a column that fits no run, stores that do not fit in HBM.
+whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, int device, std::vector<double>& gl_out, GenotypeStats& st,
+                                    bool& used, std::string& msg) {
+	RunCall call(p, m, device, gl_out, st, msg);
+	whamd_status_t s = call.plan(used);
+	if (s != WHAMD_OK || !used) return s;
+	s = call.open();
+	if (s == WHAMD_OK) s = call.upload_plan();
+	if (s == WHAMD_OK) s = call.take_buffers();
+	if (s == WHAMD_OK) s = call.launch_tables();
+	if (s == WHAMD_OK) s = call.fill_tables();
+	if (s == WHAMD_OK) s = call.n_windows == 1 ? call.submit_one_window() : call.submit_windows();
+	if (s == WHAMD_OK) s = call.collect();
+	return s;
 }
 
 }  // namespace whamd
