@@ -175,6 +175,25 @@ whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const
                                         const uint32_t* positions, size_t n_positions, uint32_t pieces, whamd_debug_preview_plan_result* out,
                                         uint64_t* rec_predicted, uint64_t* rec_laid_out, uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity);
 
+/* HOST-ONLY export of the genotyper's run plan (csrc/genotype_plan.h; no device needed): the runs of the run-fused path in table order, and for
+ * each where its chains rescale.  rescale_f / rescale_b: the run divides the column that enters it, forward (from run - 1) / backward
+ * (from run + 1), by that column's total -- the run starts from a scaled total of 1; nothing is rescaled inside a run.  The wiring
+ * behind it: a rescaling run reads n_part_in_* per-workgroup partial sums from part_in_* on, which are the n_part_out sums its neighbour leaves at
+ * part_out_* when its emit_* is set.  *min_total_out: the scaled column total below which a solve discards the run path's result and takes
+ * the per-column kernels (GS_MIN_TOTAL).  With both, a test can work out from a reference's per-column normalisers how small the numbers
+ * of the device get.  WHAMD_ERR_UNSUPPORTED: the table is not eligible for the run path.  At most `capacity` runs are written to out[]
+ * (may be NULL), *n_out: how many there are. */
+typedef struct whamd_debug_genotype_run {
+	uint32_t c0, ncols;
+	uint32_t rescale_f, rescale_b, emit_f, emit_b;
+	uint32_t n_part_out, part_out_f, part_out_b;
+	uint32_t part_in_f, n_part_in_f, part_in_b, n_part_in_b;
+	uint32_t reserved;
+} whamd_debug_genotype_run;
+whamd_status_t whamd_debug_genotype_run_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                             const whamd_pedigree_view* pedigree, const uint32_t* positions, size_t n_positions,
+                                             whamd_debug_genotype_run* out, size_t capacity, size_t* n_out, double* min_total_out);
+
 #ifdef __cplusplus
 }
 #endif

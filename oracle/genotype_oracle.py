@@ -44,8 +44,15 @@ def _phred_probability(q):
     return LD("0.9999") if q == 0 else LD(10) ** (-LD(q) / LD(10))
 
 
-def genotype_likelihoods(problem, h2p_tables=None):
-    """[individuals][columns][3] normalised genotype likelihoods as numpy.longdouble."""
+def genotype_likelihoods(problem, h2p_tables=None, normalisers=None):
+    """[individuals][columns][3] normalised genotype likelihoods as numpy.longdouble.
+
+    normalisers: a dict that receives, as float64 log10 and one per column, what the per-column normalisation divides out -- the factor by
+    which a chain that is NOT rescaled shrinks in that column:
+      "forward"[c]   the total of the forward column c computed from the normalised column c - 1;
+      "backward"[c]  the total of the backward column B[c] computed from the normalised B[c + 1] (0 for the last column, where B is 1);
+      "combined"[c]  the total of forward * emission * prior * backward of column c, from the normalised forward column c - 1 and B[c].
+    The likelihoods returned do not depend on it."""
     n_ind = problem.n_individuals
     triples_ids = problem.triple_ids.reshape(-1, 3)
     ind_of = {int(v): i for i, v in enumerate(problem.individual_id)}
@@ -128,6 +135,7 @@ def genotype_likelihoods(problem, h2p_tables=None):
     costs = [[cell_costs(columns[c], x) for x in range(1 << k[c])] for c in range(n)]
     # backward: B[c][y][i] indexed by the forward projection of column c
     B = [None] * n
+    log_forward, log_backward, log_combined = np.zeros(n), np.zeros(n), np.zeros(n)
     for c in range(n - 1, 0, -1):
         cur = np.zeros((1 << b[c], T), dtype=LD)
         for x in range(1 << k[c]):
@@ -138,6 +146,7 @@ def genotype_likelihoods(problem, h2p_tables=None):
                 for j in range(T):
                     cur[y, j] += s * trans[c][j][i]
         B[c - 1] = cur / cur.sum()
+        log_backward[c - 1] = float(np.log10(cur.sum()))
     prev = None
     for c in range(n):
         cur = np.zeros((1 << len(fwd_bits[c]), T), dtype=LD)
@@ -159,6 +168,10 @@ def genotype_likelihoods(problem, h2p_tables=None):
                         like[s, g] += fb
         out[:, c, :] = like / norm
         prev = cur / cur.sum()
+        log_forward[c] = float(np.log10(cur.sum()))
+        log_combined[c] = float(np.log10(norm))
+    if normalisers is not None:
+        normalisers.update(forward=log_forward, backward=log_backward, combined=log_combined)
     return out
 
 

@@ -1,5 +1,5 @@
 """The host arithmetic of the genotyper's device paths (whatshap_amd/csrc/genotype_plan.h), on the host alone: a stand-alone C++ program built
-with the address and undefined-behaviour sanitizers cuts runs into windows, chooses the per-column window and sizes column grids.
+with the address and undefined-behaviour sanitizers cuts runs into windows, wires the rescaling of the runs, chooses the per-column window and sizes column grids.
 Nothing is loaded into Python."""
 import os
 import shutil
@@ -56,6 +56,36 @@ int main() {
 		CHECK(cut.windows.size() == 3 && window_is(cut.windows[0], 0, 2, 6) && window_is(cut.windows[1], 2, 4, 7) && window_is(cut.windows[2], 4, 5, 6));
 		CHECK((cut.store_off == Words{0, 3, 0, 5, 0}) && cut.window_words == 7);
 	}
+
+	// rescaling: runs in groups of GS_RESCALE; a forward run that is the first of its group and a backward run that is the last of its group
+	// read exactly the per-workgroup sums their neighbour leaves, and the neighbour is told to leave them
+	CHECK(GS_RESCALE >= 1 && GS_MIN_TOTAL > 1e-200 && GS_MIN_TOTAL < 1e-100);
+	for (size_t n_runs : {1u, 2u, 4u, 5u, 9u}) {
+		std::vector<GsRun> runs(n_runs);
+		uint32_t next = 0;
+		for (size_t ri = 0; ri < n_runs; ++ri) {
+			runs[ri] = GsRun();
+			runs[ri].g = (uint32_t)(ri % 3);   // 1, 2, 4 workgroups
+			runs[ri].threads = 64u << (ri % 4);
+			runs[ri].part_out_f = next; next += 1u << runs[ri].g;
+			runs[ri].part_out_b = next; next += 1u << runs[ri].g;
+		}
+		geno_wire_rescaling(runs);
+		for (size_t ri = 0; ri < n_runs; ++ri) {
+			const GsRun& r = runs[ri];
+			const bool first_of_group = ri > 0 && ri % GS_RESCALE == 0, last_of_group = ri + 1 < n_runs && (ri + 1) % GS_RESCALE == 0;
+			CHECK((r.n_part_in_f != 0) == first_of_group);
+			CHECK((r.n_part_in_b != 0) == last_of_group);
+			if (first_of_group) CHECK(r.part_in_f == runs[ri - 1].part_out_f && r.n_part_in_f == 1u << runs[ri - 1].g && runs[ri - 1].emit_f == 1);
+			if (last_of_group) CHECK(r.part_in_b == runs[ri + 1].part_out_b && r.n_part_in_b == 1u << runs[ri + 1].g && runs[ri + 1].emit_b == 1);
+			// nobody emits what nobody reads
+			CHECK(r.emit_f == (ri + 1 < n_runs && runs[ri + 1].n_part_in_f != 0 ? 1u : 0u));
+			CHECK(r.emit_b == (ri > 0 && runs[ri - 1].n_part_in_b != 0 ? 1u : 0u));
+			// the two chains rescale at the same boundaries: their product never carries more than one group
+			if (ri > 0) CHECK((r.n_part_in_f != 0) == (runs[ri - 1].n_part_in_b != 0));
+		}
+	}
+	CHECK(run_lds_bytes(256, 24, 16, 8, 16) <= GS_MAX_LDS && run_lds_bytes(256, 25, 16, 8, 16) > GS_MAX_LDS);   // a quartet's runs of four waves: 24 columns
 
 	// per-column path: columns kept per window (per_column = 1000 bytes)
 	CHECK(geno_column_window(10, 0, 1000.0, 1e9) == 10);   // everything fits: one window

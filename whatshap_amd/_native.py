@@ -755,6 +755,31 @@ def debug_lazy_terms_check(problem: ProblemArrays, need=None, rounds: int = 1) -
     return {"lazy": bool(lazy.value), "differences": int(diff.value), "built_before": int(before.value), "built_after": int(after.value)}
 
 
+class DebugGenotypeRun(C.Structure):
+    """whamd_debug_genotype_run (include/whatshap_amd_debug.h)."""
+    _fields_ = [(name, C.c_uint32) for name in ("c0", "ncols", "rescale_f", "rescale_b", "emit_f", "emit_b", "n_part_out", "part_out_f", "part_out_b",
+                                                "part_in_f", "n_part_in_f", "part_in_b", "n_part_in_b", "reserved")]
+
+
+def debug_genotype_run_plan(problem: ProblemArrays):
+    """Host-only (whamd_debug_genotype_run_plan): (the runs of the genotyper's run path as dicts, the scaled column total below which a solve
+    leaves the run path); None when the table is not eligible for the run path."""
+    D = debug_lib()
+    fn = D.whamd_debug_genotype_run_plan
+    fn.restype = C.c_int
+    a = problem.call_args()
+    args = (a[0], a[1], a[2], a[3], a[5], a[6])
+    n, min_total = C.c_size_t(), C.c_double()
+    status = fn(*args, None, C.c_size_t(0), C.byref(n), C.byref(min_total))
+    if status == WHAMD_ERR_UNSUPPORTED:
+        return None
+    _check(status, D)
+    runs = (DebugGenotypeRun * max(n.value, 1))()
+    _check(fn(*args, runs, C.c_size_t(n.value), C.byref(n), C.byref(min_total)), D)
+    names = [f[0] for f in DebugGenotypeRun._fields_ if f[0] != "reserved"]
+    return [{k: int(getattr(runs[i], k)) for k in names} for i in range(n.value)], float(min_total.value)
+
+
 class DebugKernel(C.Structure):
     """whamd_debug_kernel (include/whatshap_amd_debug.h)."""
     _fields_ = [("kernel", C.c_void_p), ("name", C.c_char_p), ("large_lds_opted_in", C.c_int32), ("debug_only", C.c_int32)]

@@ -16,6 +16,7 @@
 #include "device_runtime.h"
 #include "device_table.h"
 #include "genotype.h"
+#include "genotype_plan.h"
 #include "heuristic.h"
 #include "host_parallel.h"
 #include "problem.h"
@@ -804,6 +805,38 @@ whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const
 	if (st != WHAMD_OK) return fail(st, msg);
 	st = DeviceTable::debug_preview_plan(p, pieces, out, rec_predicted, rec_laid_out, spec_predicted, spec_laid_out, capacity, msg);
 	return st == WHAMD_OK ? WHAMD_OK : fail(st, msg);
+	});
+}
+
+whamd_status_t whamd_debug_genotype_run_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                             const whamd_pedigree_view* pedigree, const uint32_t* positions, size_t n_positions,
+                                             whamd_debug_genotype_run* out, size_t capacity, size_t* n_out, double* min_total_out) {
+	return guarded([&]() -> whamd_status_t {
+	if (!n_out) return fail(WHAMD_ERR_INVALID, "n_out is NULL");
+	Problem p;
+	std::string msg;
+	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, false, positions, n_positions, p, msg, /*columns_only=*/true);
+	if (st != WHAMD_OK) return fail(st, msg);
+	GenotypeModel model;
+	st = build_genotype_model(p, model, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	GenoRunPlan pl;
+	if (!geno_plan_runs(p, model, 0, pl)) return fail(WHAMD_ERR_UNSUPPORTED, "the table is not eligible for the genotyper's run path");
+	*n_out = pl.runs.size();
+	if (min_total_out) *min_total_out = GS_MIN_TOTAL;
+	for (size_t ri = 0; out && ri < pl.runs.size() && ri < capacity; ++ri) {
+		const GsRun& r = pl.runs[ri];
+		whamd_debug_genotype_run o{};
+		o.c0 = r.c0; o.ncols = r.ncols;
+		o.rescale_f = r.n_part_in_f ? 1u : 0u; o.rescale_b = r.n_part_in_b ? 1u : 0u;
+		o.emit_f = r.emit_f; o.emit_b = r.emit_b;
+		o.n_part_out = 1u << r.g;
+		o.part_out_f = r.part_out_f; o.part_out_b = r.part_out_b;
+		o.part_in_f = r.part_in_f; o.n_part_in_f = r.n_part_in_f;
+		o.part_in_b = r.part_in_b; o.n_part_in_b = r.n_part_in_b;
+		out[ri] = o;
+	}
+	return WHAMD_OK;
 	});
 }
 #endif   // WHAMD_DEBUG_BUILD

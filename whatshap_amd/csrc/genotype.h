@@ -46,7 +46,8 @@ whamd_status_t genotype_solve_columns(const Problem& p, const GenotypeModel& m, 
                                       std::vector<double>& gl_out, GenotypeStats& st, std::string& msg);
 
 // The run-fused path (genotype_slots.hip): slot runs with sums instead of minima, both chains side by side, one combine launch.
-// `used` = false (and WHAMD_OK): the table is not eligible and nothing was written, take the per-column kernels.
+// `used` = false (and WHAMD_OK): take the per-column kernels -- the table is not eligible, or the f64 range ran out inside a run (a column's
+// scaled total below GS_MIN_TOTAL, genotype_plan.h) and what was written to gl_out / st is to be discarded.
 whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, int device, std::vector<double>& gl_out, GenotypeStats& st,
                                     bool& used, std::string& msg);
 

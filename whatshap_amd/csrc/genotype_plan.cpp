@@ -35,7 +35,7 @@ bool geno_plan_runs(const Problem& p, const GenotypeModel& m, int l_pref, GenoRu
 		r.s_off = r.v_off + (uint32_t)(per_unit << sr.lw);
 		pl.tab_words += (unsigned long long)r.s_off + (unsigned long long)sr.ncols * 64u * E;
 		pl.max_f = std::max(pl.max_f, sr.L + sr.g);
-		const uint32_t nw = (sr.threads >> 6) << sr.g;   // per-wave partial sums of what the run hands on, one set per direction
+		const uint32_t nw = 1u << sr.g;   // per-workgroup partial sums of what the run hands on, one set per direction
 		r.part_out_f = pl.n_partials; pl.n_partials += nw;
 		r.part_out_b = pl.n_partials; pl.n_partials += nw;
 		const uint32_t blocks = (uint32_t)((((size_t)sr.threads << sr.g) + 256u * GS_COMBINE_LANES - 1u) / (256u * GS_COMBINE_LANES));
@@ -69,17 +69,7 @@ bool geno_plan_runs(const Problem& p, const GenotypeModel& m, int l_pref, GenoRu
 			cc.ci = ci; cc.ncols = sr.ncols; cc.g = sr.g; cc.L = sr.L; cc.threads = sr.threads; cc.n_blocks = blocks;
 		}
 	}
-	for (size_t ri = 0; ri < n_runs; ++ri) {   // the partial sums a run reads are the ones its neighbour writes; every GS_RESCALE-th run of a chain rescales
-		GsRun& r = pl.runs[ri];
-		if (ri > 0 && ri % GS_RESCALE == 0) {
-			r.part_in_f = pl.runs[ri - 1].part_out_f; r.n_part_in_f = (pl.runs[ri - 1].threads >> 6) << pl.runs[ri - 1].g;
-			pl.runs[ri - 1].emit_f = 1;
-		}
-		if (ri + 1 < n_runs && (n_runs - 1 - ri) % GS_RESCALE == 0) {
-			r.part_in_b = pl.runs[ri + 1].part_out_b; r.n_part_in_b = (pl.runs[ri + 1].threads >> 6) << pl.runs[ri + 1].g;
-			pl.runs[ri + 1].emit_b = 1;
-		}
-	}
+	geno_wire_rescaling(pl.runs);
 	return true;
 }
 
@@ -93,7 +83,7 @@ bool geno_plan_windows(GenoRunPlan& pl, uint32_t T, uint32_t A, size_t free_byte
 	const size_t n = pl.cols.size(), n_runs = pl.runs.size();
 	const double fixed = (double)pl.tab_words * 8 + (double)GS_COMBINE_BATCH * pl.max_blocks * T * A * 8 + 4.0 * ((double)(1ull << pl.max_f) * T * 8) +
 	                     (double)n * (sizeof(GsCol) + sizeof(GsRow) + sizeof(GsCombineCol) + 8.0 * T * A + 8);
-	if (pl.max_lds > 150 * 1024) return false;
+	if (pl.max_lds > GS_MAX_LDS) return false;
 	std::vector<unsigned long long> run_words(n_runs);
 	unsigned long long store_words = 0;
 	for (size_t ri = 0; ri < n_runs; ++ri) {

@@ -43,12 +43,46 @@ struct GsRun {
 	unsigned long long tab_off;          // tables of the run: G [2^g][ncols][T][E], V [2^lw][ncols][T][E], S [ncols][64][E]  (doubles, E = 2 P)
 	unsigned long long store_off;        // the run's columns in the two column stores: [ncols][2^g * threads] doubles
 	uint32_t v_off, s_off;               // V and S relative to tab_off
-	uint32_t part_in_f, part_out_f, part_in_b, part_out_b;   // first per-wave partial sum of the exchange columns read / written (forward, backward)
-	uint32_t n_part_in_f, n_part_in_b;   // how many (0: this run does not rescale -- only every GS_RESCALE-th run does)
-	uint32_t emit_f, emit_b;             // 1: the neighbour rescales, leave the per-wave sums of what is handed on
+	uint32_t part_in_f, part_out_f, part_in_b, part_out_b;   // first per-workgroup partial sum of the exchange columns read / written (forward, backward)
+	uint32_t n_part_in_f, n_part_in_b;   // how many (0: this run does not rescale; geno_wire_rescaling)
+	uint32_t emit_f, emit_b;             // 1: the neighbour rescales, leave the per-workgroup sum of what is handed on
 };
 static_assert(sizeof(GsRun) == 168, "GsRun layout");
-constexpr uint32_t GS_RESCALE = 4;       // runs between two rescalings of a chain (a run shrinks the values by ~1e-10 at most: far from 1e-308)
+// The f64 range between two rescalings.  A chain multiplies every cell by S(x) <= 1 per column and is never rescaled inside a launch (a run spans
+// 2^g workgroups: no maximum across them).  Measured with the long-double restatement (oracle/genotype_oracle.py returns log10 of the column
+// totals its normalisation divides out; DESIGN.md has the table): the total of a column shrinks by 1e-1.1 per column on the synthetic generator at
+// coverage 6, by 1e-1.8 with phred-93 qualities, by 1e-2.1 .. 1e-8.8 per column on conflict-rich tables and by 1e-6.3 under priors of 1e-30 against
+// the reads -- over ONE run of 32 columns by 1e-46, 1e-92 (1e-119 in a table of 3000 columns) and 1e-101 .. 1e-337 -- and the combine kernel
+// multiplies the two chains.  Rescaling a chain every fourth run, the two chains at different runs, the factor applied to what a run hands on
+// (the first schedule), let the product carry seven runs: 1e-205 for the generator, NaN from phred 93 on.  Hence:
+//   every run rescales on entry, in both directions (GS_RESCALE = 1): a run starts from a total of 1, and the scaled total of a column of the
+//     combine, sum f * b * cost * prior, is the shrink of that column's own run alone (the totals divided out of the two chains make up the rest of
+//     the table's constant probability): 1e-44 at worst for the generator, 1e-87 at phred 93 (1e-118 in the long table), 1e-107 at 10 % errors.
+//     With GS_RESCALE = R the runs form groups [k R, (k + 1) R) that both chains rescale on entering: the product carries one group, never two;
+//   geno_slot_finish sees that total (tot[0]) for every column.  Below GS_MIN_TOTAL = 1e-150 -- or zero, or NaN -- it raises a flag, the host
+//     discards the result and the table takes the per-column kernels, which normalise every column.  The stored chains are bounded by it: a
+//     column's forward total and backward total are each >= tot[0] / (growth of the other chain inside the run, (1 - r)^(-2 triples) per column:
+//     at most 1e88 over 32 columns of a quartet at recombination cost 1 -- no overflow either).
+//   1e-150 splits the exponent range of f64 in two: a run may shrink the totals by 150 decades, and every cell within 1e-158 of its column's total
+//     is still a normal number with all its digits (the per-column path keeps cells down to 1e-308 of the total, the reference 1e-4932).
+constexpr uint32_t GS_RESCALE = 1;       // runs per group; both chains rescale when they enter a group
+constexpr double GS_MIN_TOTAL = 1e-150;  // scaled column totals below this: the run path hands the table over
+// The partial sums a run reads are the ones its neighbour writes (part_out_* and g are filled in): a forward run rescales when it is
+// the first of a group, a backward run when it is the last of one.
+inline void geno_wire_rescaling(std::vector<GsRun>& runs) {
+	const size_t n_runs = runs.size();
+	for (size_t ri = 0; ri < n_runs; ++ri) {
+		GsRun& r = runs[ri];
+		if (ri > 0 && ri % GS_RESCALE == 0) {
+			r.part_in_f = runs[ri - 1].part_out_f; r.n_part_in_f = 1u << runs[ri - 1].g;
+			runs[ri - 1].emit_f = 1;
+		}
+		if (ri + 1 < n_runs && (ri + 1) % GS_RESCALE == 0) {
+			r.part_in_b = runs[ri + 1].part_out_b; r.n_part_in_b = 1u << runs[ri + 1].g;
+			runs[ri + 1].emit_b = 1;
+		}
+	}
+}
 // Per column, for the combine kernel: blockIdx.y = column, blockIdx.x = 256-thread block of the column's lanes.
 struct GsCombineCol {
 	unsigned long long tab_off, store_off;   // the column's run
@@ -65,6 +99,9 @@ inline size_t run_lds_bytes(uint32_t threads, uint32_t ncols, uint32_t T, uint32
 	const size_t waves = threads >> 6;
 	return ((size_t)2 * threads + waves * ncols * T * E + (size_t)ncols * T * A + ((ncols + 1) & ~1u) + 16) * 8 + (size_t)ncols * sizeof(GsCol);
 }
+// What a run kernel may take of the 160 KiB: the planner (slot_plan.cpp, genotype_mode) ends a run before it needs more -- a quartet's run of 32
+// columns and four waves would need 197 KiB, it gets 24 columns --, geno_plan_windows refuses a plan that needs more all the same.
+constexpr size_t GS_MAX_LDS = 150 * 1024;
 
 // ---------------------------------------------------------------------------------------------- run path: windows
 // Runs [r0, r1) = columns [c0, c1); `words` doubles in each of the two column stores.
@@ -105,13 +142,13 @@ struct GenoRunPlan {
 	std::vector<GsCombineCol> ccols;   // by column
 	std::vector<GsWindow> windows;
 	unsigned long long tab_words = 0, window_words = 0;   // all runs' tables; one column store of the largest window
-	uint32_t n_partials = 0;           // per-wave partial sums of the exchange columns, both directions
+	uint32_t n_partials = 0;           // per-workgroup partial sums of the exchange columns, both directions
 	uint32_t max_f = 0;                // widest exchange column: 2^max_f cells
 	uint32_t max_blocks = 1;           // most combine blocks of a column
 	size_t max_lds = 0;                // largest run_lds_bytes
 	size_t n_sets = 1;                 // (forward store, backward store) pairs: 2 with more than one window
 };
-// Runs and descriptors of `p`, the GS_RESCALE wiring of the partial sums.  false: the table is not eligible for the run path (a pedigree the
+// Runs and descriptors of `p`, the wiring of the partial sums (geno_wire_rescaling).  false: the table is not eligible for the run path (a pedigree the
 // planner does not cover, a column that fits no run, more reads starting / ending in a column than a run kernel loops over).
 bool geno_plan_runs(const Problem& p, const GenotypeModel& m, int l_pref, GenoRunPlan& pl);
 // The windows, for `free_bytes` of device memory and at most `cap_words` doubles per column store (~0: no cap).  false: not eligible (a run kernel

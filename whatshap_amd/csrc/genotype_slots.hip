@@ -11,7 +11,9 @@
 //   combine: ONE full-chip launch over (column, cell) after both chains: the genotype-likelihood sums
 //       L_c[individual][genotype] = sum over x, i, a of stored forward * prior * cost * stored backward (:376-383), per-block partial
 //       sums, then the normalisation of every column.  Any constant factor on a whole stored column cancels there, so the
-//       chains rescale freely: every run divides what it hands on by the total of what it received.
+//       chains rescale freely: every run divides what enters it by the total of that column.  Inside a run nothing is rescaled: a
+//       column whose scaled total falls below GS_MIN_TOTAL (genotype_plan.h has the argument) raises a flag and the table takes the
+//       per-column kernels instead.
 // cost_i(x, a) = prod_p W_i(x)[p][a_p]; W splits over the slot classes into TABLES computed once per solve at full-chip width
 // (geno_slot_tables): G[workgroup], V[wave], S[lane] per (column, transmission value): a column costs two LDS reads of 2P doubles
 // and 2P multiplications per lane for W, then 2^(P+1) - 2 multiplications for the products of all assignments.
@@ -50,8 +52,9 @@ struct GsDev {
 	double* tab;
 	double* fstore;           // forward column store
 	double* bstore;           // backward column store
-	double* partials;         // per-wave sums of the exchange columns
+	double* partials;         // per-workgroup sums of the exchange columns
 	uint32_t T, A, P, n_ind, n_cols, pad;
+	uint32_t* low;            // set to 1 by geno_slot_finish: a column's scaled total is below GS_MIN_TOTAL (or not a number)
 	unsigned long long* dbg;  // -DWHAMD_GENO_STAMPS: cycle sums of the run kernel's phases (wave 0 of workgroup 0)
 };
 
@@ -119,6 +122,14 @@ __device__ __forceinline__ double gs_lane_xor(double v, uint32_t mask) {
 	if (mask == 4u) return gs_dpp<0x1B>(gs_dpp<0x141>(v));        // row_half_mirror (i ^ 7), quad_perm [3,2,1,0] (i ^ 3)
 	if (mask == 8u) return gs_dpp<0x141>(gs_dpp<0x140>(v));       // row_mirror (i ^ 15), row_half_mirror (i ^ 7)
 	return __shfl_xor(v, (int)mask);
+}
+
+// sum over the wave, the same number in every lane: four DPP exchanges inside the rows of 16 lanes, two across them (as six cross-lane
+// reads through LDS the two reductions of a rescaling run were most of what rescaling EVERY run cost)
+__device__ __forceinline__ double gs_wave_sum(double v) {
+#pragma unroll
+	for (uint32_t mask = 1; mask <= 32u; mask <<= 1) v += gs_lane_xor(v, mask);
+	return v;
 }
 
 template <int P>
@@ -228,7 +239,7 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 	#pragma unroll
 			for (uint32_t u = 0; u < PS_N; ++u) if (u * threads + tid < np) psum += psv[u];
 			for (uint32_t q = PS_N * threads + tid; q < np; q += threads) psum += G.partials[p0 + q];
-			for (int off = 32; off > 0; off >>= 1) psum += __shfl_xor(psum, off);
+			psum = gs_wave_sum(psum);
 			if (lane == 0) red[wave] = psum;
 		}
 	} else {
@@ -274,7 +285,7 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 		if (np) {
 			const uint32_t p0 = DIR == 0 ? run.part_in_f : run.part_in_b;
 			for (uint32_t q = tid; q < np; q += threads) psum += G.partials[p0 + q];
-			for (int off = 32; off > 0; off >>= 1) psum += __shfl_xor(psum, off);
+			psum = gs_wave_sum(psum);
 			if (lane == 0) red[wave] = psum;
 		}
 	}
@@ -286,6 +297,7 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 		for (uint32_t q = 0; q < nwaves; ++q) total += red[q];
 		inv = total > 0.0 ? 1.0 / total : 1.0;
 	}
+	val *= inv;   // the run's own columns carry the factor: the total of what a rescaling run starts from is 1
 	double* __restrict__ store = (DIR == 0 ? G.fstore : G.bstore) + run.store_off + (size_t)w * threads + tid;
 	const size_t col_stride = (size_t)threads << run.g;
 	uint32_t xsel = 0;
@@ -395,7 +407,7 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 		}
 	}
 	GS_STAMP(2);   // column loop
-	// ---- exit: hand on what was received times 1 / (total received), and the per-wave sums of what is handed on
+	// ---- exit: hand on the last column (scaled on entry), and the per-workgroup sum of what is handed on
 	const bool to_other = DIR == 0 ? run.has_next != 0u : run.has_prev != 0u;
 	if (to_other) {
 		const uint32_t occ = DIR == 0 ? run.out_occ : run.in_occ;
@@ -407,12 +419,18 @@ __global__ __launch_bounds__(512) void geno_slot_run(GsDev G, GsRun run, const d
 #pragma unroll
 			for (int s = 0; s < SLOT_MAXSLOTS; ++s) idx |= (((Pcell & occ) >> s) & 1u) << (DIR == 0 ? gs_pos(run.out_pos, s) : gs_pos(run.in_pos, s));
 		}
-		const double outv = val * inv;
+		const double outv = val;
 		if (writes) cur[(size_t)idx * T + i] = outv;
-		if (DIR == 0 ? run.emit_f : run.emit_b) {
+		if (DIR == 0 ? run.emit_f : run.emit_b) {   // (one sum per workgroup: every workgroup of the neighbour reads all of them)
 			double ps = writes ? outv : 0.0;
-			for (int off = 32; off > 0; off >>= 1) ps += __shfl_xor(ps, off);
-			if (lane == 0) G.partials[(DIR == 0 ? run.part_out_f : run.part_out_b) + w * nwaves + wave] = ps;
+			ps = gs_wave_sum(ps);
+			if (lane == 0) red[8u + wave] = ps;
+			__syncthreads();
+			if (tid == 0) {
+				double wsum = 0.0;
+				for (uint32_t q = 0; q < nwaves; ++q) wsum += red[8u + q];
+				G.partials[(DIR == 0 ? run.part_out_f : run.part_out_b) + w] = wsum;
+			}
 		}
 	}
 	GS_STAMP(3);   // exit
@@ -548,6 +566,7 @@ __global__ __launch_bounds__(256) void geno_slot_finish(GsDev G, const double* _
 		for (uint32_t q = 0; q < TA; ++q)
 			if (threadIdx.x == 0 || gsh[q * n_ind + s] == g) v += u[q];
 		tot[threadIdx.x] = v;
+		if (threadIdx.x == 0 && !(v >= GS_MIN_TOTAL)) *G.low = 1u;   // (zero and NaN too; the host discards every column)
 	}
 	__syncthreads();
 	if (threadIdx.x >= 1 && threadIdx.x < n_gl) {
@@ -580,6 +599,7 @@ struct RunCall : GenotypeCall {
 	GsDev G{};
 	void *d_runs = nullptr, *d_ccols = nullptr, *d_fs = nullptr, *d_bs = nullptr, *d_glpart = nullptr, *d_gl = nullptr;
 	void* d_check = nullptr;   // the forward exchange column entering every window but the first
+	uint32_t low = 0;          // G.low after the solve: 1 = the f64 range ran out inside a run, the result is discarded
 	size_t check_bytes = 0;
 	double* d_x[4] = {nullptr, nullptr, nullptr, nullptr};   // exchange columns: two of the forward chain, two of the backward chain
 	GenoRunKernels kn{};
@@ -652,6 +672,10 @@ struct RunCall : GenotypeCall {
 		HIP_TRY(alloc(&d_glpart, (size_t)GS_COMBINE_BATCH * pl.max_blocks * T * A * 8));
 		HIP_TRY(alloc(&d_gl, gl_out.size() * 8));
 		for (double*& x : d_x) HIP_TRY(alloc((void**)&x, ((size_t)1 << pl.max_f) * T * 8));
+		void* d_low = nullptr;
+		HIP_TRY(alloc(&d_low, sizeof(uint32_t)));
+		HIP_TRY(hipMemsetAsync(d_low, 0, sizeof(uint32_t), ses.stream));   // (the forward chain's stream: before the tables, which every launch waits for)
+		G.low = (uint32_t*)d_low;
 		G.tab = (double*)d_tab; G.fstore = (double*)d_fs; G.bstore = (double*)d_bs; G.partials = (double*)d_part;
 		G.dbg = nullptr;
 #ifdef WHAMD_GENO_STAMPS
@@ -813,6 +837,7 @@ struct RunCall : GenotypeCall {
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipEventRecord(ev[3], sf));
 		HIP_TRY(hipMemcpyAsync(gl_out.data(), d_gl, gl_out.size() * 8, hipMemcpyDeviceToHost, sf));
+		HIP_TRY(hipMemcpyAsync(&low, G.low, sizeof low, hipMemcpyDeviceToHost, sf));
 		HIP_TRY(hipStreamSynchronize(sf));
 		HIP_TRY(hipStreamSynchronize(sb));
 		if (sc) HIP_TRY(hipStreamSynchronize(sc));
@@ -845,8 +870,9 @@ struct RunCall : GenotypeCall {
 
 }  // namespace
 
-// Returns WHAMD_OK with `used` = false when the table is not eligible (the caller takes the per-column kernels): a pedigree the
-// planner does not cover, a column that fits no run, stores that do not fit in HBM.
+// Returns WHAMD_OK with `used` = false when the caller is to take the per-column kernels: the table is not eligible (a pedigree the
+// planner does not cover, a column that fits no run, stores that do not fit in HBM), or the solve ran and a column's scaled total left
+// the range the runs keep (GS_MIN_TOTAL): what it wrote to gl_out and st is then to be discarded (genotype_solve_columns starts afresh).
 whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, int device, std::vector<double>& gl_out, GenotypeStats& st,
                                     bool& used, std::string& msg) {
 	RunCall call(p, m, device, gl_out, st, msg);
@@ -859,6 +885,10 @@ whamd_status_t genotype_solve_slots(const Problem& p, const GenotypeModel& m, in
 	if (s == WHAMD_OK) s = call.fill_tables();
 	if (s == WHAMD_OK) s = call.n_windows == 1 ? call.submit_one_window() : call.submit_windows();
 	if (s == WHAMD_OK) s = call.collect();
+	if (s == WHAMD_OK && call.low) {
+		if (getenv("WHAMD_DEBUG_TIMING")) fprintf(stderr, "[whamd timing] genotype slot runs: a column total below %g inside a run, the per-column kernels take the table\n", GS_MIN_TOTAL);
+		used = false;
+	}
 	return s;
 }
 

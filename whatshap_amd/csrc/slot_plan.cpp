@@ -16,6 +16,7 @@
 
 #include "debug_build.h"
 #include "slots.h"
+#include "genotype_plan.h"
 
 namespace whamd {
 
@@ -188,6 +189,7 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 			const uint32_t n_new = kc - bc, n_end = kc - p.f[c1];
 			if (!genotype_mode && (n_end > (uint32_t)(ped ? PSLOT_MAXEND : SLOT_MAXEND) || n_ends + n_end > (uint32_t)SLOT_MAXENDS_RUN)) break;
 			if (genotype_mode && n_ends + n_end > 250u) break;
+			if (genotype_mode && c1 > c && run_lds_bytes(64u << d.lw, c1 - c + 1, p.T, 2u * p.P, 1u << p.P) > GS_MAX_LDS) break;   // (the run kernel's tables, per column)
 			uint32_t n_free = 0;
 			for (uint32_t s = 0; s < L; ++s) n_free += cur[s] < 0;
 			if (n_new > n_free) break;
