@@ -149,11 +149,12 @@ whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_de
 /* THE PREVIEW of a table (options `preview`, `preview_pieces` of whatshap_amd.h): what became of it.
  * ran: whamd_dptable_create launched the table's leading slot runs; pieces: the plan pieces they cover; launched_steps: how many super-steps;
  * agreed_steps: S, the leading super-steps of the finished schedule that are launch for launch what was launched; continued: the solve in flight or
- * collected last began behind the preview (only when S == launched_steps); why_not: "" when it ran, else a line that starts "no preview: ".
+ * collected last began behind the preview (only when S == launched_steps); from_hook: 1 when the launches went out from the planner's head hook (in front of
+ * the plan's second half), 0 when behind the whole plan; why_not: "" when it ran, else a line that starts "no preview: ".
  * WHAMD_PREVIEW_MISMATCH_AT=k (environment, this library only) makes the comparison report that step k differs. */
 typedef struct whamd_debug_preview {
 	int32_t ran, continued;
-	uint32_t pieces, launched_steps, agreed_steps, reserved;
+	uint32_t pieces, launched_steps, agreed_steps, from_hook;
 	const char* why_not;
 } whamd_debug_preview;
 whamd_status_t whamd_debug_dptable_preview(const whamd_dptable* table, whamd_debug_preview* out);
@@ -174,6 +175,22 @@ whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const
                                         const whamd_pedigree_view* pedigree, int distrust_genotypes,
                                         const uint32_t* positions, size_t n_positions, uint32_t pieces, whamd_debug_preview_plan_result* out,
                                         uint64_t* rec_predicted, uint64_t* rec_laid_out, uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity);
+
+/* HOST-ONLY check of the planner's head hook (csrc/slots.h SlotPlanHead; no device needed): the slot plan of a single-individual table as whamd_dptable_create
+ * makes it, with the head -- the leading slot runs inside the first `head_pieces` plan pieces -- finished first (head_pieces = 0: without the hook, one pass).
+ * digest: a hash over the finished plan (steps, runs, the rows and backtrace columns of every run, control words, ending and starting slots, their offsets, exit
+ * slots, the component list): equal for every head_pieces exactly when the plans are.  head_digest_in_hook: the same hash over the head's part (runs [0, head_steps),
+ * their rows, control words, ending slots and backtrace columns) taken INSIDE the callback; head_digest: over the same part of the finished plan.  hook_calls: how
+ * often the callback was made.  edge_yflags: SlotRun::yflags of the last run of the head and of the first step behind it (0xFFFFFFFF: not a run, or no head). */
+typedef struct whamd_debug_head_plan_result {
+	uint32_t n_pieces, head_steps, n_steps, hook_calls;
+	uint64_t digest, head_digest_in_hook, head_digest;
+	uint32_t edge_yflags[2];
+	uint32_t n_runs, n_components;
+} whamd_debug_head_plan_result;
+whamd_status_t whamd_debug_head_first_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                           const whamd_pedigree_view* pedigree, int distrust_genotypes,
+                                           const uint32_t* positions, size_t n_positions, uint32_t head_pieces, whamd_debug_head_plan_result* out);
 
 /* HOST-ONLY export of the genotyper's run plan (csrc/genotype_plan.h; no device needed): the runs of the run-fused path in table order, and for
  * each where its chains rescale.  rescale_f / rescale_b: the run divides the column that enters it, forward (from run - 1) / backward

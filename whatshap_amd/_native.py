@@ -800,19 +800,39 @@ class DebugLaunch(C.Structure):
 class DebugPreview(C.Structure):
     """whamd_debug_preview (include/whatshap_amd_debug.h)."""
     _fields_ = [("ran", C.c_int32), ("continued", C.c_int32), ("pieces", C.c_uint32), ("launched_steps", C.c_uint32), ("agreed_steps", C.c_uint32),
-                ("reserved", C.c_uint32), ("why_not", C.c_char_p)]
+                ("from_hook", C.c_uint32), ("why_not", C.c_char_p)]
 
 
 def debug_preview(table) -> dict:
     """whamd_debug_dptable_preview: what became of the preview of `table` (made by the debug library): ran, continued, pieces, launched_steps,
-    agreed_steps, why_not."""
+    agreed_steps, from_hook (the launches went out from the planner's head hook), why_not."""
     D = debug_lib()
     if table._L is not D:
         raise ValueError("the preview's record exists in the debug library only (use_debug_library() before the table is made)")
     out = DebugPreview()
     _check(D.whamd_debug_dptable_preview(table._h, C.byref(out)), D)
     return {"ran": bool(out.ran), "continued": bool(out.continued), "pieces": int(out.pieces), "launched_steps": int(out.launched_steps),
-            "agreed_steps": int(out.agreed_steps), "why_not": (out.why_not or b"").decode()}
+            "agreed_steps": int(out.agreed_steps), "from_hook": bool(out.from_hook), "why_not": (out.why_not or b"").decode()}
+
+
+class DebugHeadPlan(C.Structure):
+    """whamd_debug_head_plan_result (include/whatshap_amd_debug.h)."""
+    _fields_ = [("n_pieces", C.c_uint32), ("head_steps", C.c_uint32), ("n_steps", C.c_uint32), ("hook_calls", C.c_uint32),
+                ("digest", C.c_uint64), ("head_digest_in_hook", C.c_uint64), ("head_digest", C.c_uint64),
+                ("edge_yflags", C.c_uint32 * 2), ("n_runs", C.c_uint32), ("n_components", C.c_uint32)]
+
+
+def debug_head_first_plan(problem: ProblemArrays, head_pieces: int = 0) -> dict:
+    """whamd_debug_head_first_plan (host only): the slot plan of a single-individual table with the head -- the leading slot runs inside the first `head_pieces`
+    plan pieces -- finished first (0: without the hook), as digests: of the whole plan, of the head's part inside the callback and in the finished plan."""
+    D = debug_lib()
+    fn = D.whamd_debug_head_first_plan
+    fn.restype = C.c_int
+    out = DebugHeadPlan()
+    _check(fn(*problem.call_args(), C.c_uint32(head_pieces), C.byref(out)), D)
+    rec = {name: int(getattr(out, name)) for name, _ in DebugHeadPlan._fields_ if name != "edge_yflags"}
+    rec["edge_yflags"] = tuple(None if v == 0xFFFFFFFF else int(v) for v in out.edge_yflags)
+    return rec
 
 
 class DebugPreviewPlan(C.Structure):

@@ -808,6 +808,74 @@ whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const
 	});
 }
 
+whamd_status_t whamd_debug_head_first_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
+                                           const whamd_pedigree_view* pedigree, int distrust_genotypes,
+                                           const uint32_t* positions, size_t n_positions, uint32_t head_pieces, whamd_debug_head_plan_result* out) {
+	return guarded([&]() -> whamd_status_t {
+	if (!out) return fail(WHAMD_ERR_INVALID, "out is NULL");
+	Problem p;
+	std::string msg;
+	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, p, msg);
+	if (st != WHAMD_OK) return fail(st, msg);
+	if (p.T != 1) return fail(WHAMD_ERR_UNSUPPORTED, "the head hook applies to a single individual only");
+	*out = whamd_debug_head_plan_result{};
+	auto mix = [](uint64_t& h, const void* data, size_t bytes) {   // FNV-1a
+		const unsigned char* b = static_cast<const unsigned char*>(data);
+		for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+	};
+	// the part of the plan that belongs to the runs [0, n_runs): what a launch of one of them reads, and what its backtrace reads
+	auto runs_digest = [&mix](const SlotPlan& sp, size_t n_runs) {
+		uint64_t h = 1469598103934665603ull;
+		for (size_t ri = 0; ri < n_runs; ++ri) {
+			const SlotRun& run = sp.runs[ri];
+			mix(h, &run, sizeof run);
+			mix(h, sp.rows.data() + run.row_off, (size_t)run.ncols * sizeof(SlotRow));
+			mix(h, sp.bt_cols.data() + run.row_off, (size_t)run.ncols * sizeof(SlotBtCol));
+			mix(h, sp.ctrl.data() + run.ctrl_off, (size_t)SLOT_CTRL_WORDS * 4);
+			mix(h, sp.end_slots.data() + sp.end_off[ri], run.n_ends);
+		}
+		return h;
+	};
+	SlotPlan sp;
+	SlotPlanHead head;
+	const uint32_t n_pieces = slot_plan_pieces(p.n_cols);
+	head.col_limit = slot_plan_piece_begin(p.n_cols, std::min(head_pieces, n_pieces));
+	uint32_t calls = 0, head_steps = 0;
+	uint64_t in_hook = 0;
+	head.at_head = [&](uint32_t n_head) {
+		++calls;
+		head_steps = n_head;
+		in_hook = runs_digest(sp, n_head);
+	};
+	if (!plan_forward_slots(p, 11, 1, sp, 2, false, head_pieces ? &head : nullptr)) return fail(WHAMD_ERR_UNSUPPORTED, "the table is not eligible for slot runs");
+	out->n_pieces = n_pieces;
+	out->head_steps = head_steps;
+	out->n_steps = (uint32_t)sp.steps.size();
+	out->hook_calls = calls;
+	out->head_digest_in_hook = in_hook;
+	out->head_digest = runs_digest(sp, head_steps);
+	out->n_runs = (uint32_t)sp.runs.size();
+	out->n_components = (uint32_t)sp.component_first_step.size();
+	uint64_t h = runs_digest(sp, sp.runs.size());
+	mix(h, sp.steps.data(), sp.steps.size() * sizeof(Step));
+	mix(h, sp.end_off.data(), sp.end_off.size() * 4);
+	mix(h, sp.start_slots.data(), sp.start_slots.size());
+	mix(h, sp.start_off.data(), sp.start_off.size() * 4);
+	mix(h, sp.f_exit.data(), sp.f_exit.size() * 4);
+	for (const std::vector<uint8_t>& e : sp.exit_slot) mix(h, e.data(), e.size());
+	mix(h, sp.col_to_row.data(), sp.col_to_row.size() * 4);
+	mix(h, sp.component_first_step.data(), sp.component_first_step.size() * 4);
+	mix(h, &sp.n_run_columns, sizeof sp.n_run_columns);
+	out->digest = h;
+	out->edge_yflags[0] = out->edge_yflags[1] = 0xFFFFFFFFu;
+	if (head_steps) {
+		out->edge_yflags[0] = sp.runs[head_steps - 1].yflags;
+		if (head_steps < sp.steps.size() && sp.steps[head_steps].kind == 2) out->edge_yflags[1] = sp.runs[sp.steps[head_steps].index].yflags;
+	}
+	return WHAMD_OK;
+	});
+}
+
 whamd_status_t whamd_debug_genotype_run_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
                                              const whamd_pedigree_view* pedigree, const uint32_t* positions, size_t n_positions,
                                              whamd_debug_genotype_run* out, size_t capacity, size_t* n_out, double* min_total_out) {

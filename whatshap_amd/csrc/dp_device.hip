@@ -106,7 +106,9 @@ namespace {
 struct CreateLaps {
 	using Clock = std::chrono::steady_clock;
 	const bool on = getenv("WHAMD_DEBUG_TIMING") != nullptr;
-	Clock::time_point last = Clock::now();
+	const Clock::time_point origin = Clock::now();   // (the create's upload begins)
+	Clock::time_point last = origin;
+	double since_origin_ms() const { return std::chrono::duration<double, std::milli>(Clock::now() - origin).count(); }
 	double stage_ms[4] = {0.0, 0.0, 0.0, 0.0};
 	int stage = 0;
 	double take() {
@@ -396,7 +398,7 @@ struct DeviceTable::Impl {
 
 	// the phases of a create (DeviceTable::upload), in the order they run
 	whamd_status_t open(int dev, std::string& msg);
-	whamd_status_t choose_plan(Problem& p, TableBuild& b, std::string& msg);
+	whamd_status_t choose_plan(Problem& p, TableBuild& b, bool from_create, std::string& msg);
 	void dump_plan(const Problem& p) const;
 	whamd_status_t describe_columns(const Problem& p, TableBuild& b, std::string& msg);
 	whamd_status_t lay_out_arena(const Problem& p, TableBuild& b, std::string& msg);
@@ -480,6 +482,8 @@ struct DeviceTable::Impl {
 		uint32_t launched = 0;              // super-steps launched
 		uint32_t agreed = 0;                // S: leading super-steps of the finished schedule that are launch for launch what was launched (verify_preview)
 		bool launching = false;             // start_preview is submitting its launches
+		bool tried = false;                 // start_preview has been called for this upload (choose_plan's head hook, or upload() itself)
+		bool from_hook = false;             // ... from the planner's head hook: the launches went out before the plan's second half
 		bool pending = false;               // launched, and no solve has been opened since
 		bool continued = false;             // the solve in flight / collected last began behind the preview
 		bool use_chunks = false;            // what the launches were chosen with
@@ -653,10 +657,15 @@ whamd_status_t DeviceTable::Impl::open(int dev, std::string& msg) {
 	return WHAMD_OK;
 }
 
+// The plan pieces a preview covers: what the option asks for, else a sixth of the table's (plan_preview; choose_plan's head hook asks the planner for the same).
+static uint32_t preview_pieces_of(uint32_t wanted, uint32_t n_pieces) { return wanted ? wanted : std::max(1u, n_pieces / 6); }
+
 // The kernels (templated or wide), the forward path (slot runs, LDS-resident runs, per column) and its plan.  Produces b.force_keys and b.free_b, decides where the superreads
 // are made, and fills the problem's lazy term lists where the chosen path reads them.
-whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::string& msg) {
+whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, bool from_create, std::string& msg) {
 	Impl& m = *this;
+	m.preview.tried = false;
+	m.preview.from_hook = false;
 	// pedigrees beyond the templated kernels (three trios, more than six individuals): the generic per-column kernel, key path only
 	m.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
 	if (m.wide && (p.T > (uint32_t)MAX_T_WIDE || p.n_ind > (uint32_t)MAX_IND_WIDE)) {
@@ -666,6 +675,7 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::st
 	// ... and a column with more allele-assignment terms than the templated kernels stage in LDS (genotypes not trusted, seven and more
 	// individuals): the generic kernel reads them from global memory
 	for (uint32_t c = 0; c < p.n_cols && !m.wide; ++c) m.wide = p.term_end(c, p.T - 1) - p.term_begin(c, 0) > (uint64_t)COL_MAXTERMS;
+	b.laps.lap("plan: kernels chosen, term counts scanned");
 	b.force_keys = m.path == "column_keys" || m.wide;
 	const bool want_resident = (m.path == "auto" || m.path == "resident") && !m.wide;
 	size_t free_b = 0, total_b = 0;
@@ -681,6 +691,7 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::st
 	}
 	free_b += arena_idle_bytes(m.device);   // (taken by take_solve_buffers, or freed before this table's own arena is allocated)
 	b.free_b = free_b;
+	b.laps.lap("plan: free device memory asked");
 	// A wide single-individual table (coverage >= 18: 128 and more workgroups per launch) that will share its launches with many others
 	// takes EIGHT cells per thread and twelve local slots: half the wavefronts per table and longer runs -- 24 coverage-20 tables
 	// 7.7 M columns/s instead of 6.4 M; alone the same table is slower that way (1.87 M against 2.26 M), and narrow tables gain nothing.
@@ -691,7 +702,43 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::st
 	// kernels with their operands streamed: 14.4 / 22.6).  At 23 the four-cell kernel with streamed operands wins (36.2 against 43.0 us): launch_slot_run.
 	if (p.T == 1 && p.max_k >= 21 && p.max_k <= 22 && !m.slot_l_set && m.slot_lr == 2 && !debug_env("WHAMD_NO_WIDE_LAYOUT")) { slot_lr = 3; slot_l = 12; }
 	m.slot_lr_used = slot_lr;
-	m.use_slots = (m.path == "auto" || m.path == "slots") && !m.wide && plan_forward_slots(p, p.T > 1 ? (m.slot_l_set ? -m.slot_l : 0) : std::max(8, slot_l), m.symmetry, m.splan, slot_lr);
+	// A lone single-individual table: the planner finishes the steps of the table's preview first and calls back (slots.h SlotPlanHead); the preview's runs are
+	// launched from there, and the planner's second half happens under them.  What start_preview reads of this function's results is set here, as it will be below.
+	whamd_status_t head_status = WHAMD_OK;
+	bool steps_adopted = false;
+	auto adopt_steps = [&]() {   // the driver walks plan.steps / plan.component_first_step; slot runs are steps of kind 2
+		m.plan = ResidentPlan();
+		m.plan.steps = m.splan.steps;
+		m.plan.component_first_step = m.splan.component_first_step;
+		m.plan.col_to_res.assign(p.n_cols, -1);
+		steps_adopted = true;
+	};
+	SlotPlanHead head;
+	{
+		const uint32_t n_pieces = slot_plan_pieces(p.n_cols);
+		const uint32_t pieces = std::min(n_pieces - 1, preview_pieces_of(m.preview.pieces_wanted, n_pieces));
+		head.col_limit = slot_plan_piece_begin(p.n_cols, pieces);
+		head.at_head = [&](uint32_t n_head) {
+			if (n_head == 0) return;   // (the table does not begin with slot runs: upload() asks start_preview, which says why there is none)
+			m.use_slots = true;
+			m.table_bytes = 0;
+			adopt_steps();
+			b.laps.lap("plan: the planner up to the head's callback");
+			m.preview.tried = true;
+			m.preview.from_hook = true;
+			head_status = m.start_preview(p, b, from_create, msg);
+			if (m.preview.why != PV_RAN) m.preview.from_hook = false;
+		};
+	}
+	// (only where a preview can still come about: what rules it out whatever the plan says -- plan_preview's first checks -- leaves the planner as it was)
+	bool head_first = from_create && p.T == 1 && m.preview.mode != 0 && slot_plan_pieces(p.n_cols) >= 2 && !m.shared_hint && !m.side_by_side && !debug_env("WHAMD_NO_PREVIEW") &&
+	                  !debug_env("WHAMD_NO_HEAD_FIRST");
+	if (head_first && m.preview.mode < 0)
+		head_first = !m.preview.thread_budget && slot_plan_pieces(p.n_cols) >= 8 && m.device >= 0 && m.device < 64 && Impl::tables_on_device[m.device].load() == 1;
+	m.use_slots = (m.path == "auto" || m.path == "slots") && !m.wide &&
+	              plan_forward_slots(p, p.T > 1 ? (m.slot_l_set ? -m.slot_l : 0) : std::max(8, slot_l), m.symmetry, m.splan, slot_lr, false, head_first ? &head : nullptr);
+	if (head_status != WHAMD_OK) return head_status;
+	b.laps.lap("plan: the planner");
 	// pedigree slot runs keep their cost-form tables in HBM (slots.h): at most a quarter of what is free, else the older paths
 	if (m.use_slots && m.splan.ped && m.splan.table_words * 4ull > free_b / 4) m.use_slots = false;
 	m.table_bytes = m.use_slots && m.splan.ped ? m.splan.table_words * 4ull : 0ull;
@@ -703,11 +750,7 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::st
 		if (st != WHAMD_OK) return st;
 	}
 	if (m.use_slots) {
-		// the driver walks plan.steps / plan.component_first_step; slot runs are steps of kind 2
-		m.plan = ResidentPlan();
-		m.plan.steps = m.splan.steps;
-		m.plan.component_first_step = m.splan.component_first_step;
-		m.plan.col_to_res.assign(p.n_cols, -1);
+		if (!steps_adopted) adopt_steps();
 	} else {
 		m.splan = SlotPlan();
 		plan_forward(p, want_resident, m.l_pref, m.fold, m.plan, m.symmetry);
@@ -715,6 +758,7 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, std::st
 	// The superreads of a single-individual table with trusted genotypes are made on the device, behind the backtrace (the condition is finish_columns' first branch).
 	m.device_superreads = p.n_ind == 1 && p.T == 1 && p.P == 2 && !p.distrust && p.h2p.size() >= 2 && p.h2p[0] == 0 && p.h2p[1] == 1 && p.genotype.size() >= p.n_cols &&
 	                      !debug_env("WHAMD_HOST_SUPERREADS");
+	b.laps.lap("plan: steps adopted, lazy terms");
 	return WHAMD_OK;
 }
 
@@ -1714,7 +1758,7 @@ void DeviceTable::Impl::plan_preview(const Problem& p, const TableBuild& b, bool
 		if (n_pieces < 8) return none(PV_FEW_PIECES);
 		if (m.device < 0 || m.device >= 64 || Impl::tables_on_device[m.device].load() != 1) return none(PV_NOT_ALONE);
 	}
-	out.pieces = std::min(n_pieces - 1, pv.pieces_wanted ? pv.pieces_wanted : std::max(1u, n_pieces / 6));
+	out.pieces = std::min(n_pieces - 1, preview_pieces_of(pv.pieces_wanted, n_pieces));
 	const uint32_t col_limit = slot_plan_piece_begin(n, out.pieces);
 	// ---- the leading steps that are slot runs inside the pieces (a piece edge is a run boundary)
 	const std::vector<Step>& steps = m.plan.steps;
@@ -1854,6 +1898,9 @@ whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b,
 	pv.runs.resize(S);
 	uint64_t launches = 0;
 	pv.launching = true;   // (the ledger marks these lines)
+	if (b.laps.on)
+		fprintf(stderr, "[whamd timing] preview: first launch %.2f ms after the create's upload began, at t = %.2f ms (%s)\n", b.laps.since_origin_ms(), timing_stamp_ms(),
+		        pv.from_hook ? "from the planner's head hook" : "behind the plan");
 	for (uint32_t k = 0; k < S; ++k) {
 		SlotBatchEntry e{};
 		e.run = runs[k];
@@ -1916,18 +1963,18 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg, boo
 	m.dp.T = p.T;
 	m.dp.tbits = b.tbits;
 	m.dp.n_ind = p.n_ind;
-	// ---- host: path and plan, column descriptors, the layout of the backtrace arena
-	if ((st = m.choose_plan(p, b, msg)) != WHAMD_OK) return st;
-	b.ped_slots = m.use_slots && m.splan.ped;
-	b.laps.next_stage();
-	if (debug_env("WHAMD_DEBUG_PLAN")) m.dump_plan(p);
-	// ---- the upload opens: everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the
-	// solve behind ev_upload.  WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.
+	// ---- everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the solve behind
+	// ev_upload.  WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.  (Chosen in front of the plan: a preview may start inside it.)
 	m.upload_stream = debug_env("WHAMD_UPLOAD_ON_TABLE_STREAM") ? nullptr : upload_stream_of(device);
 	if (!m.upload_stream) m.upload_stream = m.stream;
 	if (m.upload_stream == m.stream) m.own_stream_used = true;
-	// ---- a lone table: its first runs start on the device here, and the rest of the create happens under them
-	if ((st = m.start_preview(p, b, from_create, msg)) != WHAMD_OK) return st;
+	// ---- host: path and plan, column descriptors, the layout of the backtrace arena
+	if ((st = m.choose_plan(p, b, from_create, msg)) != WHAMD_OK) return st;
+	b.ped_slots = m.use_slots && m.splan.ped;
+	b.laps.next_stage();
+	if (debug_env("WHAMD_DEBUG_PLAN")) m.dump_plan(p);
+	// ---- a lone table: its first runs start on the device -- from inside the planner (choose_plan's head hook), or here --, and the rest of the create happens under them
+	if (!m.preview.tried && (st = m.start_preview(p, b, from_create, msg)) != WHAMD_OK) return st;
 	if ((st = m.describe_columns(p, b, msg)) != WHAMD_OK) return st;
 	if ((st = m.lay_out_arena(p, b, msg)) != WHAMD_OK) return st;
 	TableUploader up(device, m.upload_stream, m.allocations);
@@ -2930,6 +2977,7 @@ void DeviceTable::debug_preview(whamd_debug_preview* out) const {
 	out->pieces = pv.pieces;
 	out->launched_steps = pv.launched;
 	out->agreed_steps = pv.agreed;
+	out->from_hook = pv.why == Impl::PV_RAN && pv.from_hook ? 1u : 0u;
 	out->why_not = why[pv.why < Impl::PV_WHYS ? pv.why : 0];
 }
 

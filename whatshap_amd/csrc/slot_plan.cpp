@@ -33,7 +33,7 @@ inline uint32_t parity32(uint32_t v) { return (uint32_t)__builtin_popcount(v) & 
 
 }  // namespace
 
-bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan& plan, int lr, bool genotype_mode) {
+bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan& plan, int lr, bool genotype_mode, const SlotPlanHead* head) {
 	const auto tp0 = std::chrono::steady_clock::now();
 	const long pf0 = thread_minor_faults();
 	plan = SlotPlan();
@@ -457,19 +457,42 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 	}
 	const auto tp3 = std::chrono::steady_clock::now();
 	const long pf3 = thread_minor_faults();
-	for (size_t si = 0; si < plan.steps.size(); ++si) {
+	const bool timing = getenv("WHAMD_DEBUG_TIMING") != nullptr;
+	const double concatenated_at = timing ? timing_stamp_ms() : 0.0;
+	// (the laps of what follows: [0] component list, [1] Y form per column + prefix sum, [2] which runs are in Y form, [3] rows rewritten, [4] exit slots,
+	//  [5] entry / exit layouts, [6] inside the head's callback; [3] .. [5] add up over the head and the rest)
+	double lap_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+	auto lap_from = tp3;
+	auto lap = [&](int which) {
+		if (!timing) return;
+		const auto now = std::chrono::steady_clock::now();
+		lap_ms[which] += std::chrono::duration<double, std::milli>(now - lap_from).count();
+		lap_from = now;
+	};
+	const size_t n_steps = plan.steps.size();
+	for (size_t si = 0; si < n_steps; ++si) {
 		const uint32_t c0 = plan.steps[si].kind == 2 ? plan.runs[plan.steps[si].index].c0 : plan.steps[si].index;
 		// (a pedigree table is ONE job: across a column no read spans the T transmission values still couple the two sides)
 		if (!ped && (si == 0 || p.b[c0] == 0)) plan.component_first_step.push_back((uint32_t)si);
 	}
+	lap(0);
+	// ---- the head (slots.h SlotPlanHead): the leading steps that are slot runs ending at or before the limit are finished first
+	const bool head_first = head && head->at_head && !ped && !genotype_mode;
+	size_t n_head = 0;
+	if (head_first)
+		while (n_head < n_steps && plan.steps[n_head].kind == 2 && plan.steps[n_head].index == n_head && plan.runs[n_head].c0 + plan.runs[n_head].ncols <= head->col_limit) ++n_head;
 	// ---- Y form (kernels_slots.h).  A run whose columns all have both orientation terms and no constant one -- every column of a
 	// `whatshap phase` table with trusted genotypes: only heterozygous variants are phased -- computes with Y = B_c - 2 D instead of D, where
 	// B_c is the same for every cell of column c (the prefix sum below): min(A, K - A) = (K - |2A - K|) / 2, so a cell-column is ONE absolute
 	// difference accumulated into Y (v_sad_u32) instead of subtract, min3, add; minima become maxima, the tie rule keeps its form.
 	// Between two such runs the exchange column stays in Y form; at any other neighbour the run converts (D = (B - Y) / 2 exactly).
+	// What is decided for the whole table stands here -- the base B of every column, its gate, which runs are in Y form (a step reads its neighbours' flag) --;
+	// the rows are rewritten step by step below.
+	std::vector<uint64_t> B;     // B[c + 1] = base after column c
+	std::vector<uint8_t> yrun;   // per run: computes in Y form (empty: the table is not in Y form at all)
 	if (!ped && (lr == 2 || lr == 3) && !debug_env("WHAMD_NO_YFORM")) {
 		std::vector<uint8_t> pure(n, 0);
-		std::vector<uint64_t> B((size_t)n + 1, 0);   // B[c + 1] = base after column c
+		B.assign((size_t)n + 1, 0);
 		// (per column in parallel -- this pass, serial, was 4 of the 8.6 ms of planning configs[2] on 32 threads --, then one running sum)
 		parallel_ranges(n, host_threads(n, 8192), [&](uint64_t c_lo, uint64_t c_hi, uint32_t) {
 			for (uint32_t c = (uint32_t)c_lo; c < (uint32_t)c_hi; ++c) {
@@ -498,8 +521,9 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 			}
 		});
 		for (uint32_t c = 0; c < n; ++c) B[c + 1] += B[c];
+		lap(1);
 		if (B[n] < 0xFFFFFFF0ull) {
-			std::vector<uint8_t> yrun(plan.runs.size(), 0);
+			yrun.assign(plan.runs.size(), 0);
 			parallel_ranges(plan.runs.size(), host_threads(plan.runs.size(), 512), [&](uint64_t r_lo, uint64_t r_hi, uint32_t) {
 				for (size_t ri = r_lo; ri < r_hi; ++ri) {
 					const SlotRun& run = plan.runs[ri];
@@ -508,35 +532,39 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 					yrun[ri] = ok;
 				}
 			});
-			// (a step rewrites the rows of its own run only and reads its neighbours' flags: steps are independent)
-			parallel_ranges(plan.steps.size(), host_threads(plan.steps.size(), 256), [&](uint64_t s_lo, uint64_t s_hi, uint32_t) {
-			for (size_t si = s_lo; si < s_hi; ++si) {
-				if (plan.steps[si].kind != 2 || !yrun[plan.steps[si].index]) continue;
-				SlotRun& run = plan.runs[plan.steps[si].index];
-				auto y_neighbour = [&](size_t sj) { return plan.steps[sj].kind == 2 && yrun[plan.steps[sj].index]; };
-				// (a step that starts a connected component reads one value of the previous component, or starts from cost 0 as a job of its own)
-				const bool in = si > 0 && p.b[run.c0] != 0 && y_neighbour(si - 1);
-				bool out = false;
-				if (si + 1 < plan.steps.size() && y_neighbour(si + 1)) out = p.b[plan.runs[plan.steps[si + 1].index].c0] != 0;
-				run.yflags = 1u | (in ? 2u : 0u) | (out ? 4u : 0u);
-				run.base_in = (uint32_t)B[run.c0];
-				run.base_out = (uint32_t)B[run.c0 + run.ncols];
-				for (uint32_t i = 0; i < run.ncols; ++i) {
-					SlotRow& row = plan.rows[run.row_off + i];
-					// Kr[r] = K - 2 * (sum of the reg-slot deltas set in r) + bias over the row's first 2^lr words (K, Cc, dreg[0..2], dlane[0..2]: the
-					// run kernel reads none of them in Y form; slot_tables takes the lane deltas from dslot)
-					const uint32_t K = row.K, dreg[3] = {(uint32_t)row.dreg[0], (uint32_t)row.dreg[1], (uint32_t)row.dreg[2]};
-					uint32_t* words = reinterpret_cast<uint32_t*>(&row);
-					for (uint32_t r = 0; r < (1u << run.lr); ++r) {
-						uint32_t dsum = 0;
-						for (uint32_t sb = 0; sb < run.lr; ++sb) if ((r >> sb) & 1u) dsum += dreg[sb];
-						words[r] = K - 2u * dsum + SLOT_YBIAS;
-					}
+		}
+		lap(2);
+	}
+	// (a step rewrites the rows of its own run only and reads its neighbours' flags: steps are independent)
+	auto rewrite_rows = [&](const size_t s_first, const size_t s_last) {
+		if (yrun.empty()) return;
+		parallel_ranges(s_last - s_first, host_threads(s_last - s_first, 256), [&](uint64_t s_lo, uint64_t s_hi, uint32_t) {
+		for (size_t si = s_first + s_lo; si < s_first + s_hi; ++si) {
+			if (plan.steps[si].kind != 2 || !yrun[plan.steps[si].index]) continue;
+			SlotRun& run = plan.runs[plan.steps[si].index];
+			auto y_neighbour = [&](size_t sj) { return plan.steps[sj].kind == 2 && yrun[plan.steps[sj].index]; };
+			// (a step that starts a connected component reads one value of the previous component, or starts from cost 0 as a job of its own)
+			const bool in = si > 0 && p.b[run.c0] != 0 && y_neighbour(si - 1);
+			bool out = false;
+			if (si + 1 < n_steps && y_neighbour(si + 1)) out = p.b[plan.runs[plan.steps[si + 1].index].c0] != 0;
+			run.yflags = 1u | (in ? 2u : 0u) | (out ? 4u : 0u);
+			run.base_in = (uint32_t)B[run.c0];
+			run.base_out = (uint32_t)B[run.c0 + run.ncols];
+			for (uint32_t i = 0; i < run.ncols; ++i) {
+				SlotRow& row = plan.rows[run.row_off + i];
+				// Kr[r] = K - 2 * (sum of the reg-slot deltas set in r) + bias over the row's first 2^lr words (K, Cc, dreg[0..2], dlane[0..2]: the
+				// run kernel reads none of them in Y form; slot_tables takes the lane deltas from dslot)
+				const uint32_t K = row.K, dreg[3] = {(uint32_t)row.dreg[0], (uint32_t)row.dreg[1], (uint32_t)row.dreg[2]};
+				uint32_t* words = reinterpret_cast<uint32_t*>(&row);
+				for (uint32_t r = 0; r < (1u << run.lr); ++r) {
+					uint32_t dsum = 0;
+					for (uint32_t sb = 0; sb < run.lr; ++sb) if ((r >> sb) & 1u) dsum += dreg[sb];
+					words[r] = K - 2u * dsum + SLOT_YBIAS;
 				}
 			}
-			});
 		}
-	}
+		});
+	};
 	if (ped && !genotype_mode) {
 		// a table that mostly falls back to per-column steps (genotypes not trusted: up to 16 forms per value) is better off
 		// with the LDS-resident trio runs / the per-column kernels
@@ -570,8 +598,11 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 	// ---- entry / exit layouts.  Exit index of a run in LOGICAL order: bit j = j-th continuing read of its last column.
 	plan.f_exit.assign(plan.runs.size(), 0);
 	plan.exit_slot.assign(plan.runs.size(), std::vector<uint8_t>());
-	parallel_ranges(plan.runs.size(), host_threads(plan.runs.size(), 512), [&](uint64_t r_begin, uint64_t r_end, uint32_t) {
-	for (size_t ri = r_begin; ri < r_end; ++ri) {
+	auto exit_slots = [&](const size_t s_first, const size_t s_last) {
+	parallel_ranges(s_last - s_first, host_threads(s_last - s_first, 512), [&](uint64_t s_begin, uint64_t s_end, uint32_t) {
+	for (size_t si = s_first + s_begin; si < s_first + s_end; ++si) {
+		if (plan.steps[si].kind != 2) continue;
+		const size_t ri = plan.steps[si].index;
 		const SlotRun& run = plan.runs[ri];
 		const uint32_t cl = run.c0 + run.ncols - 1;
 		const SlotBtCol& bc = plan.bt_cols[run.row_off + run.ncols - 1];
@@ -580,9 +611,12 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 		plan.f_exit[ri] = (uint32_t)plan.exit_slot[ri].size();
 	}
 	});
-	// (step si writes the exit side of its own run and the entry side of the next one: steps are independent)
-	parallel_ranges(plan.steps.size(), host_threads(plan.steps.size(), 512), [&](uint64_t s_begin, uint64_t s_end, uint32_t) {
-	for (size_t si = s_begin; si < s_end; ++si) {
+	};
+	// (step si writes the exit side of its own run and the entry side of the next one: steps are independent -- the last step of the head
+	//  writes the entry side of the first run behind it, which that run's own step leaves alone)
+	auto link_layouts = [&](const size_t s_first, const size_t s_last) {
+	parallel_ranges(s_last - s_first, host_threads(s_last - s_first, 512), [&](uint64_t s_begin, uint64_t s_end, uint32_t) {
+	for (size_t si = s_first + s_begin; si < s_first + s_end; ++si) {
 		if (plan.steps[si].kind != 2) continue;
 		const uint32_t ri = plan.steps[si].index;
 		SlotRun& B = plan.runs[ri];
@@ -649,10 +683,35 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 		}
 	}
 	});
-	if (getenv("WHAMD_DEBUG_TIMING")) {
+	};
+	auto finish_steps = [&](const size_t s_first, const size_t s_last) {
+		rewrite_rows(s_first, s_last);
+		lap(3);
+		exit_slots(s_first, s_last);
+		lap(4);
+		link_layouts(s_first, s_last);
+		lap(5);
+	};
+	double head_done_at = 0.0;
+	if (head_first) {
+		finish_steps(0, n_head);
+		head_done_at = timing ? timing_stamp_ms() : 0.0;
+		head->at_head((uint32_t)n_head);
+		lap(6);
+		finish_steps(n_head, n_steps);
+	} else {
+		finish_steps(0, n_steps);
+	}
+	if (timing) {
 		auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+		const double inside = head_first ? lap_ms[6] : 0.0;
 		fprintf(stderr, "[whamd timing] slot plan: setup %.1f ms, column ranges %.1f ms, concatenation %.1f ms, layouts %.1f ms (page faults of this thread: %ld, %ld, %ld, %ld)\n",
-		        ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, std::chrono::steady_clock::now()), pf1 - pf0, pf2 - pf1, pf3 - pf2, thread_minor_faults() - pf3);
+		        ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, std::chrono::steady_clock::now()) - inside, pf1 - pf0, pf2 - pf1, pf3 - pf2, thread_minor_faults() - pf3);
+		fprintf(stderr, "[whamd timing] slot plan layouts: component list %.2f ms, Y form per column + prefix sum %.2f ms, runs in Y form %.2f ms, rows rewritten %.2f ms, exit slots %.2f ms, "
+		        "entry / exit layouts %.2f ms; concatenation done at t = %.2f ms\n", lap_ms[0], lap_ms[1], lap_ms[2], lap_ms[3], lap_ms[4], lap_ms[5], concatenated_at);
+		if (head_first)
+			fprintf(stderr, "[whamd timing] slot plan head: %zu of %zu steps finished %.2f ms behind the concatenation, %.2f ms inside the callback\n", n_head, n_steps,
+			        head_done_at - concatenated_at, inside);
 	}
 	return true;
 }

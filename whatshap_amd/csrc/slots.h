@@ -25,7 +25,10 @@
 // (all bits complemented) -- a halved run (complement symmetry, D[~x] = D[x]) computes only the workgroups whose top
 // grid-slot bit is 0, and the backtrace reads the mirror decisions where the path runs through the other half.
 #pragma once
+#include <chrono>
+#include <cmath>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -307,7 +310,22 @@ inline uint32_t slot_plan_piece_begin(uint32_t n_cols, uint32_t piece) { return 
 // genotype_mode (genotype_slots.hip): the same one-value-per-lane layout for the forward-backward genotyper, for any T in {1, 4, 16}
 // (T = 1: six lane slots); only the slot assignment, the ending reads (prows / ctrl / bt_cols) and the exchange layouts are
 // planned -- no cost forms (Problem::terms is not needed), no tables.
-bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan& plan, int lr = 2, bool genotype_mode = false);
+//
+// head (single individual only; ignored for pedigree tables and in genotype_mode): finish the HEAD of the plan first.  The head is the leading steps that are
+// slot runs ending at or before column `col_limit` -- S of them, the rule of a table's preview (dp_device.hip plan_preview).  Behind the concatenation of
+// the pieces the planner then does, for the whole table, only what is cheap and what a head step reads of its neighbours (the component list, pure / kstar per
+// column, the base B and its gate, which runs compute in Y form), finishes the steps [0, S) -- rows rewritten, exit slots, entry / exit layouts --, calls
+// at_head(S) exactly once, and finishes [S, end).  Inside at_head the runs [0, S), their rows, control words, ending slots and backtrace columns are what they
+// will be when the function returns, and so are `steps`, `component_first_step`, `ctrl`, `end_slots` and the sizes of every array; of the later runs only what
+// the pieces planned (c0, ncols, g, L, lw, n_ends, threads, half, ...) is final.  The second half writes no field of a head run.  S may be 0 (the table does
+// not begin with a slot run): the callback is still made, in front of all of it.  Without `head`: one pass over all steps, as ever.  The plan is the same.
+struct SlotPlanHead {
+	uint32_t col_limit = 0;
+	std::function<void(uint32_t)> at_head;
+};
+bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan& plan, int lr = 2, bool genotype_mode = false, const SlotPlanHead* head = nullptr);
+// Milliseconds of the steady clock, for the WHAMD_DEBUG_TIMING lines of different files that are read against each other ("t = ...").
+inline double timing_stamp_ms() { return std::fmod(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), 1e6); }
 
 // Host-only diagnostic (slot_emulate.cpp): executes `plan` cell by cell the way the kernels do.  For planner tests on
 // small inputs; never part of a solve.
