@@ -13,6 +13,9 @@ namespace whamd {
 //   state of the walk (u32)    = logical index | transmission value << BT_STATE_TSHIFT
 constexpr uint32_t KEY_JBITS = 6, KEY_JMASK = 63u;          // argj of up to 64 transmission values (three trios)
 constexpr uint32_t BT_STATE_TSHIFT = 26, BT_STATE_XMASK = 0x03FFFFFFu;
+// Per-column kernels (kernels_column.h):
+constexpr int QMAX = 4;             // a thread enumerates at most 2^QMAX ending-bit patterns itself
+constexpr int COL_MAXTERMS = 1024;  // allele-assignment terms of a column the templated kernels stage in LDS
 
 // Per-column descriptor, read wave-uniformly (scalar loads) by every kernel.
 struct DevColumn {
@@ -71,7 +74,7 @@ struct DevProblem {
 	uint32_t T;
 	uint32_t tbits;         // 2 * triples
 	uint32_t n_ind;
-	uint32_t* bt_state;     // windowed solve (DeviceTable::Impl::Window): (x, transmission value) at the oldest column walked so far
+	uint32_t* bt_state;     // windowed solve (table_plan.h Window): (x, transmission value) at the oldest column walked so far
 };
 
 }  // namespace whamd

@@ -13,7 +13,10 @@
 //   kernels_resident.h   single-individual runs: ~23 columns per launch, the projection column lives in LDS
 //   kernels_trio.h       trio runs (T = 4)
 //   kernels_backtrace.h  follows the stored argmins from the last column to the first (src/pedigreedptable.cpp:137-173)
-// This file: launch tables and the host driver (DeviceTable: upload, jobs / lanes, resumable submission, wait).
+// This file: the launch tables and what of the host driver touches the device (DeviceTable: the phases of upload() that allocate, copy or launch; the
+// preview; resumable submission, the group solve, wait; the debug library's launch ledger).  What a create decides on the host alone -- the arena's layout,
+// windows, jobs, lanes, backtrace units, chunks, the schedule, the preview's plan -- is table_plan.h / table_plan.cpp, which no HIP header reaches; Impl
+// holds its result (TablePlan) beside the caller's options (TableOptions), the table's device arrays (TableArrays) and the solve in flight.
 // No MFMA (integer min-plus), no CUDA compatibility layer.
 #include <hip/hip_runtime.h>
 
@@ -35,6 +38,7 @@
 #include "device_runtime.h"
 #include "device_table.h"
 #include "genotype.h"
+#include "table_plan.h"
 
 namespace whamd {
 
@@ -81,58 +85,19 @@ using PedSlotRunFn = void (*)(DevProblem, SlotRun, PedSlotExtra, const uint32_t*
 using SlotBatchFn = void (*)(DevProblem, const SlotBatchEntry*);
 using GroupFn = void (*)(SlotGroupArgs);
 
-// The kernel variants of a group launch (DESIGN.md 6.2 has the table).  The values are the order of the launches inside a super-step.
-enum GroupVariant : uint8_t { GV_SINGLE4 = 0, GV_PED_2_2, GV_PED_2_4, GV_PED_4_2, GV_PED_4_4, GV_PED_2_16, GV_SINGLE8, GV_TRIO_FACT, GV_X4, GV_X8, GV_QUARTET_FACT, GROUP_VARIANTS };
-struct GroupVariantPair { GroupVariant plain, x; };   // x: the X kernel's variant where the run is eligible (else = plain)
-
-GroupVariantPair group_variants_of(const SlotBatchEntry& he, bool ped) {
-	if (ped) {
-		const GroupVariant v = he.ex.nf == (uint32_t)PSLOT_FACT4 ? GV_QUARTET_FACT : he.ex.nf == (uint32_t)PSLOT_FACT ? GV_TRIO_FACT : he.ex.nf == 16 ? GV_PED_2_16
-		                       : he.ex.tb == 4 ? (he.ex.nf == 4 ? GV_PED_4_4 : GV_PED_4_2) : (he.ex.nf == 4 ? GV_PED_2_4 : GV_PED_2_2);
-		return {v, v};
-	}
-	const GroupVariant v = he.run.lr == 3 ? GV_SINGLE8 : GV_SINGLE4;
-	return {v, (he.run.yflags & 8u) ? (he.run.lr == 3 ? GV_X8 : GV_X4) : v};
-}
-
 }  // namespace
 
 // ================================================================================================ what a create shares between its phases
 
 namespace {
 
-// The laps of a create under WHAMD_DEBUG_TIMING: lap() prints the time since the previous lap; every lap also counts towards one of the four stages of
-// the closing summary line (plan | descriptors + copies | backtrace arena | rest).  Without the switch nothing is measured.
-struct CreateLaps {
-	using Clock = std::chrono::steady_clock;
-	const bool on = getenv("WHAMD_DEBUG_TIMING") != nullptr;
-	const Clock::time_point origin = Clock::now();   // (the create's upload begins)
-	Clock::time_point last = origin;
-	double since_origin_ms() const { return std::chrono::duration<double, std::milli>(Clock::now() - origin).count(); }
-	double stage_ms[4] = {0.0, 0.0, 0.0, 0.0};
-	int stage = 0;
-	double take() {
-		const auto now = Clock::now();
-		const double ms = std::chrono::duration<double, std::milli>(now - last).count();
-		last = now;
-		stage_ms[stage] += ms;
-		return ms;
-	}
-	void lap(const char* what) {
-		if (on) fprintf(stderr, "[whamd timing]   upload: %s %.2f ms\n", what, take());
-	}
-	void next_stage() {
-		if (!on) return;
-		take();
-		if (stage < 3) ++stage;
-	}
-	void summary(double arena_gb) {
-		if (!on) return;
-		take();
-		fprintf(stderr, "[whamd timing] upload: plan %.1f ms, descriptors + copies %.1f ms, backtrace arena (%.2f GB) %.1f ms, rest %.1f ms\n", stage_ms[0], stage_ms[1], arena_gb, stage_ms[2],
-		        stage_ms[3]);
-	}
-};
+// `bytes` from the device pool, entered in `allocations`: whoever owns that list gives them back (Impl::release, Impl::give_preview_block).
+hipError_t pool_alloc(int device, std::vector<std::pair<void*, size_t>>& allocations, void** dptr, size_t bytes) {
+	size_t got = 0;
+	const hipError_t e = devpool_take(device, std::max<size_t>(bytes, 16), dptr, &got);
+	if (e == hipSuccess) allocations.emplace_back(*dptr, got);
+	return e;
+}
 
 // The upload half of a create.  ONE device block and ONE staging image per table: every uploaded array is a piece of the block at the offset it has in the
 // pinned area, and the pieces leave as a few large copies.  (Per-array copies of ~1 MB ran at 25 GB/s -- 96 coverage-15 tables, 28 MB each, spent their
@@ -149,12 +114,7 @@ struct TableUploader {
 
 	TableUploader(int dev, hipStream_t us, std::vector<std::pair<void*, size_t>>& table_allocations) : device(dev), stream(us), stage(us), allocations(table_allocations) {}
 
-	hipError_t alloc(void** dptr, size_t bytes) {
-		size_t got = 0;
-		hipError_t e = devpool_take(device, std::max<size_t>(bytes, 16), dptr, &got);
-		if (e == hipSuccess) allocations.emplace_back(*dptr, got);
-		return e;
-	}
+	hipError_t alloc(void** dptr, size_t bytes) { return pool_alloc(device, allocations, dptr, bytes); }
 	// The staging image and the device block for `upload_bytes` (an upper bound of everything up() will be given); where either is not to be had, up() falls back.
 	void open_block(size_t upload_bytes) {
 		stage.expect(upload_bytes);
@@ -222,34 +182,6 @@ struct TableUploader {
 	}
 };
 
-// What one create passes from phase to phase (DeviceTable::upload); everything that outlives the create is in Impl.
-struct TableBuild {
-	CreateLaps laps;
-	// sizes
-	uint32_t n = 0;              // columns
-	uint32_t tbits = 0;          // transmission bits of an argmin
-	uint32_t ni = 1;             // individuals, at least one
-	size_t free_b = 0;           // free HBM when the create began, idle arenas included
-	uint64_t arena_cap = 0;      // what the backtrace arena may take
-	uint64_t bt = 0;             // bytes of the arena (the largest window's)
-	uint32_t max_f = 0, max_keys_f = 0;   // log2 of the widest exchange column / of the widest column on the key path
-	size_t exchange_bytes = 0;   // one exchange column at max_f: a d_pr buffer of a lane, a kept window boundary
-	// flags
-	bool force_keys = false;     // every per-column step takes the key path
-	bool ped_slots = false;      // pedigree slot runs
-	// host arrays whose copies may still be reading them when their phase returns, or that a later phase reads
-	std::vector<uint32_t> segs;               // deposit segments of the columns outside slot runs (the column backtrace units inline them)
-	RawVec<uint32_t> term_ptr32;
-	std::vector<uint32_t> window_first_col;   // first column of every window after the first
-	RawVec<uint32_t> slot_blob;
-	std::vector<uint32_t> slot_blob_off, slot_blob_words;   // per slot run: its piece of the blob (the slot backtrace units)
-	std::vector<int32_t> delta_fallback;
-	// device arrays only the table kernels read
-	const SlotRun* d_runs = nullptr;
-	const PedSlotExtra* d_pextra = nullptr;
-	const DevTerm* d_fterms = nullptr;
-};
-
 }  // namespace
 
 // ================================================================================================ DeviceTable
@@ -274,154 +206,83 @@ struct LaunchFacts : whamd_debug_launch {
 #define WHAMD_NOTE(table, ...) ((void)0)
 #endif
 
+// The table's device arrays, and the two host blocks that mirror device memory.  release() gives `allocations`, the arena and the pinned block back and
+// default-constructs the rest with them.
+struct TableArrays {
+	std::vector<std::pair<void*, size_t>> allocations;   // (pointer, size class) of device_pool.h: everything below but the arena
+	void* d_arena = nullptr;    // the backtrace arena: not in `allocations`, handed to the arena cache on release
+	size_t arena_bytes = 0;
+	DevProblem dp{};
+	DevColumn* d_cols = nullptr;
+	uint32_t* d_pr[2] = {nullptr, nullptr};
+	size_t key_entries = 0;     // of dp.keys and of every lane's key scratch
+	// one result block, laid out like h_pinned (take_result_block)
+	uint32_t* d_path_index = nullptr;
+	uint32_t* d_path_trans = nullptr;
+	uint32_t* d_score = nullptr;
+	uint32_t* d_job_scores = nullptr;
+	uint32_t* d_bt_counters = nullptr;
+	size_t h_pinned_bytes = 0;
+	uint32_t* h_pinned = nullptr;  // [2 n + jobs + 3]: path index, path transmission, score of the final job, scores of the others, the chunked backtrace's three counters
+	// schedule and backtrace
+	BtUnit* d_units = nullptr;
+	ResBatchEntry* d_entries = nullptr;
+	SlotBatchEntry* d_slot_entries = nullptr;
+	BtJob* d_btjobs = nullptr;
+	// chunked speculative backtrace (kernels_backtrace.h)
+	BtChunk* d_chunks = nullptr;
+	uint32_t* d_unit_x = nullptr;   // [2][units]
+	uint32_t* d_path2 = nullptr;    // [2][columns]: speculative walks of the two orientations
+	uint32_t* d_trans2 = nullptr;   // [orientations][columns]: their transmission values
+	uint8_t* d_sel = nullptr;
+	uint32_t* d_guess = nullptr;
+	BtGroupEntry h_bt_entry{};          // what a batched backtrace launch reads for this table (kernels_backtrace.h backtrace_chunks_group), and its device copy
+	BtGroupEntry* d_bt_entry = nullptr;
+	// windowed solve (Window)
+	uint8_t* d_checkpoints = nullptr;   // [windows - 1] exchange columns
+	uint32_t* d_bt_state = nullptr;     // (x, transmission) the walk of a window hands to the next older one
+	BtJob* d_window_jobs = nullptr;
+	SuperreadArgs super_args{};         // superreads_single: where its inputs and its result lie
+};
+
 struct DeviceTable::Impl {
+	// ---- the device, the pooled stream and events (open / release_device), and what is known of the stream and the upload
 	int device = 0;
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	hipEvent_t ev_group = nullptr;      // group solve: "the forward pass of every table of the group is submitted up to here"
 	hipEvent_t ev_upload = nullptr;     // "everything upload() put on `stream` -- the copies, the table kernels -- is done": a solve waits for it ON THE DEVICE (begin_solve)
-	std::vector<std::pair<void*, size_t>> allocations;   // (pointer, size class) of device_pool.h
-	void* d_arena = nullptr;    // the backtrace arena: not in `allocations`, handed to the arena cache on release
-	size_t arena_bytes = 0;
-	DevColumn* d_cols = nullptr;
-	uint32_t* d_pr[2] = {nullptr, nullptr};
-	uint32_t* d_path_index = nullptr;
-	uint32_t* d_path_trans = nullptr;
-	uint32_t* d_score = nullptr;
-	BtUnit* d_units = nullptr;
-	std::vector<BtUnit> units;
-	size_t bt_lds = 0;
-	RawVec<DevColumn> cols;
-	ResidentPlan plan;
-	DevProblem dp{};
-	FusedFn fused = nullptr;
+	bool counted = false;               // this table is counted in tables_on_device
+	static inline std::atomic<int> tables_on_device[64];   // tables of the process that hold device resources, per device (open / release_device)
+	bool alone_on_device() const { return device >= 0 && device < 64 && tables_on_device[device].load() == 1; }
+	bool own_stream_used = false;       // something has been submitted to `stream` since it was last synchronised (a member of a group solve never touches its own: its
+	                                    // solve and tail are on the lead's stream, its uploads on an upload stream -- release() then has nothing to wait for there)
+	bool upload_pending = false;        // the uploads went through a shared upload stream and no solve has been ordered behind `ev_upload` yet
+	hipStream_t upload_stream = nullptr;
+	// ---- the four kinds of state
+	TableOptions opt;    // what the caller set: only the set_* functions write it, no release touches it
+	TablePlan tp;        // the host description of the built table (table_plan.h)
+	TableArrays dev;     // its device arrays
+	FusedFn fused = nullptr;   // the templated per-column kernels of (T, individuals): choose_plan sets both with tp.wide in every create; null where the table is wide
 	KeysFn keysfn = nullptr;
-	bool wide = false;   // column_step_wide instead of the templated per-column kernels
-	size_t key_entries = 0;
-	std::string path = "auto";
-	int l_pref = 11;
-	bool fold = true;
-	int symmetry = 1;  // single individual: compute only half of a run, the rest is its mirror image (plan_forward)
-	uint64_t bt_bytes = 0;
-	uint32_t max_grid_x = 1;    // widest launch of the schedule, in workgroups
-	size_t h_pinned_bytes = 0;
-	uint32_t* h_pinned = nullptr;  // [2 n + jobs + 3]: path index, path transmission, score of the final job, scores of the others, the chunked backtrace's three counters
-	// A job is a sequence of forward steps with its own backtrace.  Job 0 ("final") is the last connected component (it
-	// ends with the table's last column, whose optimum comes from the key scratch); every other job is one earlier
-	// connected component: it starts from cost 0, its last column projects onto a single entry -- that value is added on
-	// the host -- and its backtrace starts at entry 0.  Jobs are independent: they are spread over lanes (private
-	// exchange buffers and key scratch) and the lanes advance in lockstep, one *super-step* at a time: the runs of a
-	// super-step go out as ONE batched launch (resident_batch), per-column steps as launches of their own; one backtrace
-	// launch at the end walks all jobs, one workgroup each.
-	struct Job {
-		std::vector<uint32_t> steps;  // indices into plan.steps, execution order
-		uint32_t unit_off = 0, unit_count = 0;
-		bool final = false;
-	};
-	struct Lane {
-		uint32_t* d_pr[2] = {nullptr, nullptr};
-		unsigned long long* d_keys = nullptr;  // atomic-min scratch of the per-column kernels
-		std::vector<uint32_t> jobs;
-	};
-	struct Single {        // a per-column step inside a super-step
-		uint32_t lane, step, flip;
-		bool zero_prev;    // first step of its job: the entry it may read must hold cost 0
-		int32_t score_job; // >= 0: last step of that (non-final) job: copy its single exit value aside
-	};
-	struct SuperStep {
-		uint32_t entry_off = 0, entry_count = 0, grid_x = 0, threads = 0;
-		size_t lds = 0;
-		bool sym = false;  // some run of the batch takes part in the complement symmetry
-		std::vector<Single> singles;
-		// windowed solve: restore the kept column of boundary ck_load into this step's input before it runs; keep this
-		// step's output as boundary ck_save; walk window bt_window after it
-		int32_t ck_load = -1, ck_save = -1, bt_window = -1;
-		uint32_t* io[2] = {nullptr, nullptr};   // input / output exchange buffer of the step (single lane)
-	};
-	std::vector<Job> jobs;
-	std::vector<Lane> lanes;
-	std::vector<SuperStep> schedule;
-	// What a GROUP submission (enqueue_group) needs of a super-step and of its entries, a few bytes each: with 96 tables per launch the submitting thread read a
-	// 320-byte SlotBatchEntry and a SuperStep per table and super-step out of cold memory -- 31 ms of host time for 2 276 super-steps, 13 ms with these
-	// (scripts/gpu_group_submit_ab.py).  Built at create time (where the entries are made, on the create's own threads).
-	struct StepBrief { uint32_t entry_off, lds; uint16_t entry_count; uint8_t has_singles, pad; };
-	struct EntryBrief { uint16_t grid_x, threads; uint32_t lds_x; GroupVariantPair variant; uint8_t pad[2]; };
-	std::vector<StepBrief> step_brief;
-	std::vector<EntryBrief> entry_brief;
-	std::vector<ResBatchEntry> entries;
-	ResBatchEntry* d_entries = nullptr;
-	// chunked speculative backtrace (kernels_backtrace.h) of a table made of slot runs
-	bool use_chunks = false;
-	std::vector<BtChunk> chunks;
-	BtChunk* d_chunks = nullptr;
-	uint32_t* d_unit_x = nullptr;   // [2][units]
-	uint32_t* d_path2 = nullptr;    // [2][columns]: speculative walks of the two orientations
-	uint32_t* d_trans2 = nullptr;   // [orientations][columns]: their transmission values
-	uint32_t n_orient_max = 1;      // most orientations any chunk has (2 for a single individual, 8 for a trio)
-	uint8_t* d_sel = nullptr;
-	uint32_t* d_guess = nullptr;
-	uint32_t* d_bt_counters = nullptr;
-	uint32_t n_spec = 0;
-	size_t chunk_lds = 0;
-	// slot runs (slots.h): the default forward path of a single individual
-	SlotPlan splan;
-	bool use_slots = false;
-	int slot_l = 11;            // preferred number of local slots (lr + 6 .. lr + 9; pedigree runs: 6 - log2 T .. + 3, only when set explicitly)
-	bool slot_l_set = false;
-	int slot_lr = 2;            // reg slots: 4 cells per thread -> 8 waves per workgroup at 11 local slots (two waves per SIMD)
-	int slot_lr_used = 2;       // ... of the plan in use (the shared-launches layout takes 3)
-	std::vector<SlotBatchEntry> slot_entries;   // (pedigree runs: `pad` holds the run's index into splan.pextra)
-	SlotBatchEntry* d_slot_entries = nullptr;
-	uint64_t table_bytes = 0;   // pedigree slot runs: cost-form tables
-	BtJob* d_btjobs = nullptr;
-	uint32_t* d_job_scores = nullptr;
-	bool shared_hint = false;   // option shared_launches: the table will be solved together with many others (enqueue_many)
-	bool side_by_side = false;  // this solve's launches run beside other tables' on their own streams: X runs take the streamed variant (16 KB of LDS instead of ~90:
-	                            // three tables on three streams, 3.1 M columns/s with the LDS lines -- one workgroup per CU, the streams take turns -- 5 M without)
-	int max_lanes = 32;
-	// Windowed solve (backtrace arena larger than what HBM can hold): the steps are cut into WINDOWS whose records fit the
-	// arena one at a time.  Pass 1 runs the whole forward pass (records of all windows but the last are written and
-	// dropped) and keeps the exchange column at every window boundary; then, newest window first, the window's steps
-	// are run again from the kept column -- this time its records survive until its units have been walked.  Twice the
-	// forward work, any table length.  Offsets into the arena are window-relative.
-	struct Window {
-		uint32_t step_lo = 0, step_hi = 0;   // positions in the job's step list
-		uint32_t unit_off = 0, unit_count = 0;
-	};
-	uint64_t arena_limit = 0;   // option arena_limit_bytes (0: what hipMemGetInfo leaves)
-	bool windowed = false;
-	std::vector<Window> windows;
-	uint8_t* d_checkpoints = nullptr;   // [windows - 1] exchange columns
-	size_t checkpoint_bytes = 0;
-	uint32_t* d_bt_state = nullptr;     // (x, transmission) the walk of a window hands to the next older one
-	BtJob* d_window_jobs = nullptr;
 
-	// the phases of a create (DeviceTable::upload), in the order they run
+	// the phases of a create (DeviceTable::upload) that touch the device or the planner, in the order they run; the host-only phases between them are table_plan.h's
 	whamd_status_t open(int dev, std::string& msg);
 	whamd_status_t choose_plan(Problem& p, TableBuild& b, bool from_create, std::string& msg);
 	void dump_plan(const Problem& p) const;
-	whamd_status_t describe_columns(const Problem& p, TableBuild& b, std::string& msg);
-	whamd_status_t lay_out_arena(const Problem& p, TableBuild& b, std::string& msg);
-	size_t upload_bound(const Problem& p, const TableBuild& b) const;
 	whamd_status_t upload_column_arrays(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
-	void build_slot_blobs(TableBuild& b) const;
-	uint64_t lay_out_slot_tables(const TableBuild& b, bool report = true);
 	whamd_status_t upload_slot_arrays(TableBuild& b, TableUploader& up, std::string& msg);
-	void make_jobs();
-	void make_units(const TableBuild& b);
 	whamd_status_t make_windows(const TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t take_result_block(uint32_t n, TableUploader& up, std::string& msg);
-	void cut_chunks(const Problem& p);
 	whamd_status_t make_chunks(const Problem& p, TableUploader& up, std::string& msg);
+	whamd_status_t take_arena(uint64_t bytes, std::string& msg);
 	whamd_status_t take_solve_buffers(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t make_lanes(const TableBuild& b, TableUploader& up, std::string& msg);
-	whamd_status_t make_schedule(const TableBuild& b, std::string& msg);
-	void make_briefs();
 	whamd_status_t upload_entries(TableUploader& up, std::string& msg);
 	whamd_status_t launch_table_kernels(const Problem& p, const TableBuild& b, TableUploader& up, std::string& msg);
 	whamd_status_t arm_debug_stamps(TableUploader& up, std::string& msg);
 	whamd_status_t record_group_backtrace(uint32_t n, TableUploader& up, std::string& msg);
-	// The solve being submitted or awaiting collection.  (own_stream_used and upload_pending below describe the stream and the upload, not a solve.)
+	// The solve being submitted or awaiting collection.  (own_stream_used and upload_pending above describe the stream and the upload, not a solve.)
 	struct SolveInFlight {
 		hipStream_t run_stream = nullptr;   // where the forward steps go: `stream`, or the stream of the group's lead.  Set where a solve opens (enqueue_some_unguarded,
 		                                    // GroupSubmission::open_members); read by begin_solve, the launch_* functions, submit_super_step, submit_singles
@@ -456,27 +317,11 @@ struct DeviceTable::Impl {
 	whamd_status_t submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream = nullptr, bool walked_by_group = false);
 	whamd_status_t report_slot_stamps(std::string& msg) const;
 	whamd_status_t report_resident_stamps(std::string& msg) const;
-	BtGroupEntry h_bt_entry{};          // what a batched backtrace launch reads for this table (kernels_backtrace.h backtrace_chunks_group), and its device copy
-	BtGroupEntry* d_bt_entry = nullptr;
-	// get_super_reads on the device (kernels_backtrace.h superreads_single): a table with one individual and trusted genotypes
-	bool device_superreads = false;
-	SuperreadArgs super_args{};
-	size_t super_words = 0, super_off = 0;   // size of the result (u32 words) and where it lies in h_pinned
-	bool own_stream_used = false;       // something has been submitted to `stream` since it was last synchronised (a member of a group solve never touches its own: its
-	                                    // solve and tail are on the lead's stream, its uploads on an upload stream -- release() then has nothing to wait for there)
-	bool upload_pending = false;        // the uploads went through a shared upload stream and no solve has been ordered behind `ev_upload` yet
-	hipStream_t upload_stream = nullptr;
 
 	// The preview (DESIGN.md 6.1 "preview"): the leading slot runs of a lone table's forward pass, launched on `stream` from INSIDE the create -- from arrays of
 	// their own, uploaded first -- so that the device works while the host builds and uploads the whole table.  The finished schedule is then held against what
 	// was launched (verify_preview); the first enqueue continues behind the preview where every step agrees, and starts at step 0 as ever where not.
-	enum PreviewWhy : uint32_t { PV_RAN = 0, PV_OFF, PV_NOT_CREATE, PV_NOT_SLOTS, PV_DEBUG_SWITCH, PV_SHARED, PV_THREAD_BUDGET, PV_COMPONENTS, PV_FEW_PIECES, PV_NOT_ALONE, PV_NO_LEADING_RUNS,
-	                           PV_ROW_PAD, PV_ARENA, PV_WHYS };
 	struct Preview {
-		int mode = -1;                      // option preview: -1 auto, 0 never, 1 wherever the table's form allows it
-		uint32_t pieces_wanted = 0;         // option preview_pieces (0: the library's rule)
-		bool thread_budget = false;         // the create is held to a thread budget (option host_threads)
-		bool counted = false;               // this table is counted in tables_on_device
 		uint32_t why = PV_NOT_CREATE;       // PV_RAN, or why there was none
 		uint32_t pieces = 0;                // plan pieces the preview covered
 		uint32_t launched = 0;              // super-steps launched
@@ -496,20 +341,10 @@ struct DeviceTable::Impl {
 		size_t spec_bytes = 0;
 		std::vector<std::pair<void*, size_t>> allocations;   // the preview's own device block: given back by wait and release
 	} preview;
-	static inline std::atomic<int> tables_on_device[64];   // tables of the process that hold device resources, per device (open / release_device)
 	void give_preview_block() {   // (the caller knows the preview's launches are done)
 		for (auto& a : preview.allocations) devpool_give(device, a.first, a.second);
 		preview.allocations.clear();
 	}
-	struct PreviewPlan {   // plan_preview's answer
-		uint32_t why = PV_NOT_CREATE, pieces = 0, steps = 0, end_col = 0, n_spec = 0, stride = 64, max_f = 0;
-		bool chunked = false;
-		uint64_t arena = 0, tab_words = 0;   // bytes of the arena (all steps), words of the preview's table block
-		size_t ctrl_words = 0;
-		std::vector<uint64_t> rec;           // [steps] record offsets
-		std::vector<uint32_t> spec;          // [steps] seed ids
-	};
-	void plan_preview(const Problem& p, const TableBuild& b, bool from_create, PreviewPlan& out);
 	whamd_status_t start_preview(const Problem& p, TableBuild& b, bool from_create, std::string& msg);
 	void verify_preview();
 	whamd_status_t arm_keys(std::string& msg);
@@ -522,41 +357,20 @@ struct DeviceTable::Impl {
 		return ss;
 	}
 
-	void release_lanes() {
-		max_grid_x = 1;
-		lanes.clear();
-		jobs.clear();
-		schedule.clear();
-		entries.clear();
-		slot_entries.clear();
-		windows.clear();
-	}
-
+	// Waits for whatever may still read the table's memory, gives the memory back, and leaves plan, device arrays and preview as a new table has them.
 	void release() {
 		if (inflight.tail_elsewhere && ev3) (void)hipEventSynchronize(ev3);   // (a solve whose tail ran on the group's lead stream: nothing of it may still be reading the buffers)
 		inflight.tail_elsewhere = false;
 		if (upload_pending && ev_upload) (void)hipEventSynchronize(ev_upload);   // (a table closed without a solve: its copies may still be on the upload stream)
 		upload_pending = false;
-		release_lanes();
-		windowed = false;
-		if (stream && own_stream_used && (!allocations.empty() || d_arena)) { (void)hipStreamSynchronize(stream); own_stream_used = false; }   // (hipFree used to wait for the table's last kernels)
-		for (auto& a : allocations) devpool_give(device, a.first, a.second);
-		allocations.clear();
+		if (stream && own_stream_used && (!dev.allocations.empty() || dev.d_arena)) { (void)hipStreamSynchronize(stream); own_stream_used = false; }   // (hipFree used to wait for the table's last kernels)
+		for (auto& a : dev.allocations) devpool_give(device, a.first, a.second);
 		give_preview_block();   // (its launches were on `stream`: synchronised above)
-		if (preview.why != PV_NOT_CREATE) {   // (a table that never got as far as start_preview has nothing to reset; the options and the count outlive a release)
-			Preview fresh;
-			fresh.mode = preview.mode; fresh.pieces_wanted = preview.pieces_wanted; fresh.thread_budget = preview.thread_budget; fresh.counted = preview.counted;
-			preview = std::move(fresh);
-		}
-		arena_give(device, d_arena, arena_bytes);
-		d_arena = nullptr;
-		arena_bytes = 0;
-		pinned_give(h_pinned, h_pinned_bytes);
-		h_pinned = nullptr;
-		d_cols = nullptr;
-		d_units = nullptr;
-		d_pr[0] = d_pr[1] = nullptr;
-		d_path_index = d_path_trans = d_score = nullptr;
+		arena_give(device, dev.d_arena, dev.arena_bytes);
+		pinned_give(dev.h_pinned, dev.h_pinned_bytes);
+		tp = TablePlan();
+		dev = TableArrays();
+		preview = Preview();
 	}
 };
 
@@ -579,8 +393,8 @@ void DeviceTable::release_device() {
 		streamset_give(m.stream_set());
 	}
 	m.adopt(StreamSet());
-	if (m.preview.counted && m.device >= 0 && m.device < 64) Impl::tables_on_device[m.device].fetch_sub(1);
-	m.preview.counted = false;
+	if (m.counted && m.device >= 0 && m.device < 64) Impl::tables_on_device[m.device].fetch_sub(1);
+	m.counted = false;
 	m.inflight.run_stream = nullptr;
 	m.inflight.timing_pending = false;
 }
@@ -601,46 +415,32 @@ bool DeviceTable::device_pci_bus_id(int device, std::string& out) {
 	return true;
 }
 
-// Runs of set bits of `mask` as deposit segments (compact position | mask position << 8 | length << 16).
-static void append_segments(uint32_t mask, std::vector<uint32_t>& out, uint16_t& count) {
-	uint32_t src = 0;
-	count = 0;
-	for (uint32_t bit = 0; bit < 32;) {
-		if (!((mask >> bit) & 1u)) { ++bit; continue; }
-		uint32_t len = 0;
-		while (bit + len < 32 && ((mask >> (bit + len)) & 1u)) ++len;
-		out.push_back(src | (bit << 8) | (len << 16));
-		++count;
-		src += len;
-		bit += len;
-	}
-}
-
 bool DeviceTable::set_path(const std::string& path) {
 	if (path != "auto" && path != "column" && path != "column_keys" && path != "resident" && path != "slots") return false;
-	impl_->path = path;
+	impl_->opt.path = path;
 	return true;
 }
 
-void DeviceTable::set_l_pref(int l) { impl_->l_pref = std::max(4, std::min(l, RES_LMAX)); }
-void DeviceTable::set_lanes(int n) { impl_->max_lanes = n < 1 ? 1 : (n > 64 ? 64 : n); }
+void DeviceTable::set_l_pref(int l) { impl_->opt.l_pref = std::max(4, std::min(l, RES_LMAX)); }
+void DeviceTable::set_lanes(int n) { impl_->opt.max_lanes = n < 1 ? 1 : (n > 64 ? 64 : n); }
 
-void DeviceTable::set_fold(bool v) { impl_->fold = v; }
-void DeviceTable::set_slot_l(int l) { impl_->slot_l = std::max(2, std::min(l, 12)); impl_->slot_l_set = true; }
-void DeviceTable::set_slot_lr(int lr) { impl_->slot_lr = lr >= 3 ? 3 : (lr <= 1 ? 1 : 2); }
+void DeviceTable::set_fold(bool v) { impl_->opt.fold = v; }
+void DeviceTable::set_slot_l(int l) { impl_->opt.slot_l = std::max(2, std::min(l, 12)); impl_->opt.slot_l_set = true; }
+void DeviceTable::set_slot_lr(int lr) { impl_->opt.slot_lr = lr >= 3 ? 3 : (lr <= 1 ? 1 : 2); }
 
-void DeviceTable::set_arena_limit(uint64_t bytes) { impl_->arena_limit = bytes; }
-void DeviceTable::set_shared_launches(bool v) { impl_->shared_hint = v; }
-void DeviceTable::set_side_by_side(bool v) { impl_->side_by_side = v; }
-void DeviceTable::set_preview(int mode) { impl_->preview.mode = mode < 0 ? -1 : (mode ? 1 : 0); }
-void DeviceTable::set_preview_pieces(uint32_t pieces) { impl_->preview.pieces_wanted = pieces; }
-void DeviceTable::set_thread_budget(bool v) { impl_->preview.thread_budget = v; }
-void DeviceTable::set_symmetry(int level) { impl_->symmetry = level < 0 ? 0 : (level > 2 ? 2 : level); }
+void DeviceTable::set_arena_limit(uint64_t bytes) { impl_->opt.arena_limit = bytes; }
+void DeviceTable::set_shared_launches(bool v) { impl_->opt.shared_hint = v; }
+void DeviceTable::set_side_by_side(bool v) { impl_->opt.side_by_side = v; }
+void DeviceTable::set_preview(int mode) { impl_->opt.preview_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
+void DeviceTable::set_preview_pieces(uint32_t pieces) { impl_->opt.preview_pieces = pieces; }
+void DeviceTable::set_thread_budget(bool v) { impl_->opt.thread_budget = v; }
+void DeviceTable::set_symmetry(int level) { impl_->opt.symmetry = level < 0 ? 0 : (level > 2 ? 2 : level); }
 
 // ================================================================================================ create: the phases of DeviceTable::upload
-// Each phase says in its parameters what it touches: `Problem`, the build object (TableBuild: what later phases read), the uploader (TableUploader: the phase
-// allocates, copies or launches).  Everything else it reads and writes is the table's own state in Impl.  The order of the phases that take an uploader IS the
-// layout of the table's device block and the order of its driver calls.
+// The phases that decide something on the host alone are free functions of table_plan.h over the options, the build object and the plan; upload() calls them
+// between the phases below, which are the ones that ask the device, allocate, copy or launch.  Each of these says in its parameters what it touches: `Problem`,
+// the build object (TableBuild: what later phases read), the uploader (TableUploader).  Everything else it reads and writes is Impl's: `opt` (read only), the
+// plan `tp`, the device arrays `dev`.  The order of the phases that take an uploader IS the layout of the table's device block and the order of its driver calls.
 
 whamd_status_t DeviceTable::Impl::open(int dev, std::string& msg) {
 	Impl& m = *this;
@@ -653,12 +453,9 @@ whamd_status_t DeviceTable::Impl::open(int dev, std::string& msg) {
 		m.adopt(ss);
 	}
 	m.release();
-	if (!m.preview.counted && dev >= 0 && dev < 64) { Impl::tables_on_device[dev].fetch_add(1); m.preview.counted = true; }
+	if (!m.counted && dev >= 0 && dev < 64) { Impl::tables_on_device[dev].fetch_add(1); m.counted = true; }
 	return WHAMD_OK;
 }
-
-// The plan pieces a preview covers: what the option asks for, else a sixth of the table's (plan_preview; choose_plan's head hook asks the planner for the same).
-static uint32_t preview_pieces_of(uint32_t wanted, uint32_t n_pieces) { return wanted ? wanted : std::max(1u, n_pieces / 6); }
 
 // The kernels (templated or wide), the forward path (slot runs, LDS-resident runs, per column) and its plan.  Produces b.force_keys and b.free_b, decides where the superreads
 // are made, and fills the problem's lazy term lists where the chosen path reads them.
@@ -667,17 +464,17 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, bool fr
 	m.preview.tried = false;
 	m.preview.from_hook = false;
 	// pedigrees beyond the templated kernels (three trios, more than six individuals): the generic per-column kernel, key path only
-	m.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
-	if (m.wide && (p.T > (uint32_t)MAX_T_WIDE || p.n_ind > (uint32_t)MAX_IND_WIDE)) {
+	m.tp.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
+	if (m.tp.wide && (p.T > (uint32_t)MAX_T_WIDE || p.n_ind > (uint32_t)MAX_IND_WIDE)) {
 		msg = "no device kernel for T=" + std::to_string(p.T) + ", individuals=" + std::to_string(p.n_ind);
 		return WHAMD_ERR_UNSUPPORTED;
 	}
 	// ... and a column with more allele-assignment terms than the templated kernels stage in LDS (genotypes not trusted, seven and more
 	// individuals): the generic kernel reads them from global memory
-	for (uint32_t c = 0; c < p.n_cols && !m.wide; ++c) m.wide = p.term_end(c, p.T - 1) - p.term_begin(c, 0) > (uint64_t)COL_MAXTERMS;
+	for (uint32_t c = 0; c < p.n_cols && !m.tp.wide; ++c) m.tp.wide = p.term_end(c, p.T - 1) - p.term_begin(c, 0) > (uint64_t)COL_MAXTERMS;
 	b.laps.lap("plan: kernels chosen, term counts scanned");
-	b.force_keys = m.path == "column_keys" || m.wide;
-	const bool want_resident = (m.path == "auto" || m.path == "resident") && !m.wide;
+	b.force_keys = m.opt.path == "column_keys" || m.tp.wide;
+	const bool want_resident = (m.opt.path == "auto" || m.opt.path == "resident") && !m.tp.wide;
 	size_t free_b = 0, total_b = 0;
 	HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 	if (free_b < total_b / 2) {   // a genotyping call of this process may be holding its column store (genotype.h): give it back first
@@ -695,33 +492,33 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, bool fr
 	// A wide single-individual table (coverage >= 18: 128 and more workgroups per launch) that will share its launches with many others
 	// takes EIGHT cells per thread and twelve local slots: half the wavefronts per table and longer runs -- 24 coverage-20 tables
 	// 7.7 M columns/s instead of 6.4 M; alone the same table is slower that way (1.87 M against 2.26 M), and narrow tables gain nothing.
-	int slot_lr = m.slot_lr, slot_l = m.slot_l;
-	if (m.shared_hint && p.T == 1 && p.max_k >= 18 && !m.slot_l_set && m.slot_lr == 2) { slot_lr = 3; slot_l = 12; }
+	int slot_lr = m.opt.slot_lr, slot_l = m.opt.slot_l;
+	if (m.opt.shared_hint && p.T == 1 && p.max_k >= 18 && !m.opt.slot_l_set && m.opt.slot_lr == 2) { slot_lr = 3; slot_l = 12; }
 	// Coverage 21 and 22 (512 / 1 024 workgroups of four cells per launch: the table fills the chip by itself, rounds of workgroups queue behind each
 	// other) take the eight-cell layout ALONE as well: 14.0 against 17.9 us per launch at 21, 20.3 against 30.1 at 22 (scripts/gpu_wide_ab.py; the same
 	// kernels with their operands streamed: 14.4 / 22.6).  At 23 the four-cell kernel with streamed operands wins (36.2 against 43.0 us): launch_slot_run.
-	if (p.T == 1 && p.max_k >= 21 && p.max_k <= 22 && !m.slot_l_set && m.slot_lr == 2 && !debug_env("WHAMD_NO_WIDE_LAYOUT")) { slot_lr = 3; slot_l = 12; }
-	m.slot_lr_used = slot_lr;
+	if (p.T == 1 && p.max_k >= 21 && p.max_k <= 22 && !m.opt.slot_l_set && m.opt.slot_lr == 2 && !debug_env("WHAMD_NO_WIDE_LAYOUT")) { slot_lr = 3; slot_l = 12; }
+	m.tp.slot_lr_used = slot_lr;
 	// A lone single-individual table: the planner finishes the steps of the table's preview first and calls back (slots.h SlotPlanHead); the preview's runs are
 	// launched from there, and the planner's second half happens under them.  What start_preview reads of this function's results is set here, as it will be below.
 	whamd_status_t head_status = WHAMD_OK;
 	bool steps_adopted = false;
 	auto adopt_steps = [&]() {   // the driver walks plan.steps / plan.component_first_step; slot runs are steps of kind 2
-		m.plan = ResidentPlan();
-		m.plan.steps = m.splan.steps;
-		m.plan.component_first_step = m.splan.component_first_step;
-		m.plan.col_to_res.assign(p.n_cols, -1);
+		m.tp.plan = ResidentPlan();
+		m.tp.plan.steps = m.tp.splan.steps;
+		m.tp.plan.component_first_step = m.tp.splan.component_first_step;
+		m.tp.plan.col_to_res.assign(p.n_cols, -1);
 		steps_adopted = true;
 	};
 	SlotPlanHead head;
 	{
 		const uint32_t n_pieces = slot_plan_pieces(p.n_cols);
-		const uint32_t pieces = std::min(n_pieces - 1, preview_pieces_of(m.preview.pieces_wanted, n_pieces));
+		const uint32_t pieces = std::min(n_pieces - 1, preview_pieces_of(m.opt.preview_pieces, n_pieces));
 		head.col_limit = slot_plan_piece_begin(p.n_cols, pieces);
 		head.at_head = [&](uint32_t n_head) {
 			if (n_head == 0) return;   // (the table does not begin with slot runs: upload() asks start_preview, which says why there is none)
-			m.use_slots = true;
-			m.table_bytes = 0;
+			m.tp.use_slots = true;
+			m.tp.table_bytes = 0;
 			adopt_steps();
 			b.laps.lap("plan: the planner up to the head's callback");
 			m.preview.tried = true;
@@ -731,32 +528,32 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, bool fr
 		};
 	}
 	// (only where a preview can still come about: what rules it out whatever the plan says -- plan_preview's first checks -- leaves the planner as it was)
-	bool head_first = from_create && p.T == 1 && m.preview.mode != 0 && slot_plan_pieces(p.n_cols) >= 2 && !m.shared_hint && !m.side_by_side && !debug_env("WHAMD_NO_PREVIEW") &&
+	bool head_first = from_create && p.T == 1 && m.opt.preview_mode != 0 && slot_plan_pieces(p.n_cols) >= 2 && !m.opt.shared_hint && !m.opt.side_by_side && !debug_env("WHAMD_NO_PREVIEW") &&
 	                  !debug_env("WHAMD_NO_HEAD_FIRST");
-	if (head_first && m.preview.mode < 0)
-		head_first = !m.preview.thread_budget && slot_plan_pieces(p.n_cols) >= 8 && m.device >= 0 && m.device < 64 && Impl::tables_on_device[m.device].load() == 1;
-	m.use_slots = (m.path == "auto" || m.path == "slots") && !m.wide &&
-	              plan_forward_slots(p, p.T > 1 ? (m.slot_l_set ? -m.slot_l : 0) : std::max(8, slot_l), m.symmetry, m.splan, slot_lr, false, head_first ? &head : nullptr);
+	if (head_first && m.opt.preview_mode < 0)
+		head_first = !m.opt.thread_budget && slot_plan_pieces(p.n_cols) >= 8 && m.alone_on_device();
+	m.tp.use_slots = (m.opt.path == "auto" || m.opt.path == "slots") && !m.tp.wide &&
+	              plan_forward_slots(p, p.T > 1 ? (m.opt.slot_l_set ? -m.opt.slot_l : 0) : std::max(8, slot_l), m.opt.symmetry, m.tp.splan, slot_lr, false, head_first ? &head : nullptr);
 	if (head_status != WHAMD_OK) return head_status;
 	b.laps.lap("plan: the planner");
 	// pedigree slot runs keep their cost-form tables in HBM (slots.h): at most a quarter of what is free, else the older paths
-	if (m.use_slots && m.splan.ped && m.splan.table_words * 4ull > free_b / 4) m.use_slots = false;
-	m.table_bytes = m.use_slots && m.splan.ped ? m.splan.table_words * 4ull : 0ull;
+	if (m.tp.use_slots && m.tp.splan.ped && m.tp.splan.table_words * 4ull > free_b / 4) m.tp.use_slots = false;
+	m.tp.table_bytes = m.tp.use_slots && m.tp.splan.ped ? m.tp.splan.table_words * 4ull : 0ull;
 	if (p.lazy_terms) {
 		// generic term lists where something will read them: the columns a pedigree slot plan leaves to the per-column kernels; every column on any other path
 		std::vector<uint8_t> need(p.n_cols, 1);
-		if (m.use_slots && m.splan.ped) for (uint32_t c = 0; c < p.n_cols; ++c) need[c] = m.splan.col_to_row[c] < 0;
+		if (m.tp.use_slots && m.tp.splan.ped) for (uint32_t c = 0; c < p.n_cols; ++c) need[c] = m.tp.splan.col_to_row[c] < 0;
 		const whamd_status_t st = fill_lazy_terms(p, need, msg);
 		if (st != WHAMD_OK) return st;
 	}
-	if (m.use_slots) {
+	if (m.tp.use_slots) {
 		if (!steps_adopted) adopt_steps();
 	} else {
-		m.splan = SlotPlan();
-		plan_forward(p, want_resident, m.l_pref, m.fold, m.plan, m.symmetry);
+		m.tp.splan = SlotPlan();
+		plan_forward(p, want_resident, m.opt.l_pref, m.opt.fold, m.tp.plan, m.opt.symmetry);
 	}
 	// The superreads of a single-individual table with trusted genotypes are made on the device, behind the backtrace (the condition is finish_columns' first branch).
-	m.device_superreads = p.n_ind == 1 && p.T == 1 && p.P == 2 && !p.distrust && p.h2p.size() >= 2 && p.h2p[0] == 0 && p.h2p[1] == 1 && p.genotype.size() >= p.n_cols &&
+	m.tp.device_superreads = p.n_ind == 1 && p.T == 1 && p.P == 2 && !p.distrust && p.h2p.size() >= 2 && p.h2p[0] == 0 && p.h2p[1] == 1 && p.genotype.size() >= p.n_cols &&
 	                      !debug_env("WHAMD_HOST_SUPERREADS");
 	b.laps.lap("plan: steps adopted, lazy terms");
 	return WHAMD_OK;
@@ -765,183 +562,25 @@ whamd_status_t DeviceTable::Impl::choose_plan(Problem& p, TableBuild& b, bool fr
 // WHAMD_DEBUG_PLAN (debug library): the chosen plan, one line per step.
 void DeviceTable::Impl::dump_plan(const Problem& p) const {
 	const Impl& m = *this;
-	for (const Step& st : m.plan.steps) {
+	for (const Step& st : m.tp.plan.steps) {
 		if (st.kind == 0) { fprintf(stderr, "[plan] column %u k=%u b=%u f=%u\n", st.index, p.k[st.index], p.b[st.index], p.f[st.index]); continue; }
 		if (st.kind == 2) {
-			const SlotRun& r = m.splan.runs[st.index];
+			const SlotRun& r = m.tp.splan.runs[st.index];
 			fprintf(stderr, "[plan] slot run c0=%u ncols=%u g=%u L=%u half=%u ends=%u has_prev=%u in_identity=%u in_half=%u mirror_pos=%u in_occ=%x out_occ=%x mirror_out=%u\n",
 			        r.c0, r.ncols, r.g, r.L, r.half, r.n_ends, r.has_prev, r.in_identity, r.in_half, r.in_mirror_pos, r.in_occ, r.out_occ, r.mirror_out);
-			if (m.splan.ped) fprintf(stderr, "[plan]   pedigree run: T=%u forms per value=%u table words=%u record words per workgroup=%u\n", 1u << m.splan.pextra[st.index].tb,
-			                         m.splan.pextra[st.index].nf, m.splan.pextra[st.index].s_off + r.ncols * 64u * pslot_ns(m.splan.pextra[st.index].nf), m.splan.pextra[st.index].rec_words);
+			if (m.tp.splan.ped) fprintf(stderr, "[plan]   pedigree run: T=%u forms per value=%u table words=%u record words per workgroup=%u\n", 1u << m.tp.splan.pextra[st.index].tb,
+			                         m.tp.splan.pextra[st.index].nf, m.tp.splan.pextra[st.index].s_off + r.ncols * 64u * pslot_ns(m.tp.splan.pextra[st.index].nf), m.tp.splan.pextra[st.index].rec_words);
 			continue;
 		}
-		const ResSegment& sgm = m.plan.segments[st.index];
+		const ResSegment& sgm = m.tp.plan.segments[st.index];
 		fprintf(stderr, "[plan] run c0=%u ncols=%u g=%u threads=%u max_l=%u stage_words=%u\n", sgm.c0, sgm.ncols, sgm.g, sgm.threads, sgm.max_l, sgm.stage_words);
 		for (uint32_t i = 0; i < sgm.ncols; ++i) {
-			const ResColumn& rc = m.plan.columns[sgm.col_off + i];
-			const ResBacktrace& rb = m.plan.backtrace[sgm.col_off + i];
+			const ResColumn& rc = m.tp.plan.columns[sgm.col_off + i];
+			const ResBacktrace& rb = m.tp.plan.backtrace[sgm.col_off + i];
 			fprintf(stderr, "[plan]   col %u mode=%u nfold=%u Lb=%u Lf=%u ebits=%u epos0=%u nthr=%u stage_off=%u nwords=%u | bt layout=%u n_g=%u n_l=%u\n",
 			        sgm.c0 + i, rc.mode, rc.nfold, rc.Lb, rc.Lf, rc.ebits, rc.epos[0], rc.nthr, rc.stage_off, rc.nwords, rb.layout, rb.n_g, rb.n_l);
 		}
 	}
-}
-
-// What a column's descriptor holds by itself, and its 32-bit term offsets (b.term_ptr32): a few host threads.  Fails if the problem exceeds 32-bit offsets.  Host only.
-whamd_status_t DeviceTable::Impl::describe_columns(const Problem& p, TableBuild& b, std::string& msg) {
-	Impl& m = *this;
-	const uint32_t n = b.n, ni = b.ni, tbits = b.tbits;
-	if (p.terms.size() >= 0xFFFFFFFFull || (uint64_t)p.col_ptr[n] * ni >= 0xFFFFFFFFull) {
-		msg = "problem too large for 32-bit device offsets";
-		return WHAMD_ERR_UNSUPPORTED;
-	}
-	m.cols.resize(n);
-	b.term_ptr32.resize((size_t)n * (p.T + 1));
-	RawVec<uint32_t>& term_ptr32 = b.term_ptr32;
-	parallel_ranges(n, host_threads(n, 16384), [&m, &p, &term_ptr32, n, ni, tbits](uint64_t c0, uint64_t c1, uint32_t) {
-		for (uint32_t c = (uint32_t)c0; c < (uint32_t)c1; ++c) {
-			DevColumn d{};
-			d.k = p.k[c];
-			d.b = p.b[c];
-			d.f = p.f[c];
-			d.recomb = p.recomb[c];
-			d.delta_off = (uint32_t)(p.col_ptr[c] * ni);
-			d.term_off = (uint32_t)((size_t)c * (p.T + 1));
-			for (uint32_t t = 0; t <= p.T; ++t) term_ptr32[(size_t)c * (p.T + 1) + t] = (uint32_t)p.term_ptr[(size_t)c * p.T + t];
-			d.ebits = d.k - d.f;
-			d.is_last = (c + 1 == n);
-			d.eloop = std::min<uint32_t>(d.ebits, QMAX);
-			d.nplanes = d.ebits + tbits;
-			m.cols[c] = d;
-		}
-	});
-	return WHAMD_OK;
-}
-
-// The path a per-column step takes (0 fused, 1 keys) and the bytes of its backtrace record, from the column's sizes alone (lay_out_arena; the preview's arena bound).
-static uint32_t column_step_mode(bool force_keys, bool is_last, uint32_t f, uint32_t ebits) { return (!force_keys && !is_last && f >= 6 && ebits <= (uint32_t)QMAX) ? 0u : 1u; }
-static uint64_t column_record_bytes(uint32_t mode, uint32_t T, uint32_t f, uint32_t nplanes) {
-	return mode == 0 ? (uint64_t)nplanes * T * (1ull << (f - 6)) * 8ull : (uint64_t)T * (1ull << f) * 4ull;
-}
-// What the backtrace arena may take: free HBM minus the descriptors (~1 KiB per column), exchange buffers, tables and slack; at most the option arena_limit_bytes.
-static uint64_t arena_capacity(uint64_t free_b, uint32_t n, uint64_t table_bytes, uint64_t arena_limit) {
-	const uint64_t reserve = (3ull << 30) + (uint64_t)n * 1024ull + table_bytes;
-	uint64_t cap = free_b > reserve ? free_b - reserve : 0;
-	if (arena_limit) cap = std::min<uint64_t>(cap, arena_limit);
-	return cap;
-}
-// Where the next record starts behind one of `bytes` at `bt` (records are 16-byte aligned).
-static uint64_t arena_behind(uint64_t bt, uint64_t bytes) { return (bt + bytes + 15ull) & ~15ull; }
-// The record of one single-individual slot run: only launched workgroups write.
-static uint64_t slot_run_record_bytes(const SlotRun& run) { return (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half)); }
-
-// The offsets that run through the table, in column order: segment lists (b.segs), the place of every backtrace unit's record in the arena (DevColumn::bt_off, the
-// runs' rec / bt words), the windows where the arena is smaller than the records (b.window_first_col).  Produces b.arena_cap, b.bt, b.max_f, b.max_keys_f,
-// b.exchange_bytes; fails if a unit or the whole does not fit.  Host only.
-whamd_status_t DeviceTable::Impl::lay_out_arena(const Problem& p, TableBuild& b, std::string& msg) {
-	Impl& m = *this;
-	const uint32_t n = b.n;
-	const bool ped_slots = b.ped_slots;
-	std::vector<uint32_t>& segs = b.segs;
-	uint64_t bt = 0, seg_bt = 0;
-	size_t seg_cursor = 0, slot_cursor = 0;
-	uint32_t max_f = 0, max_keys_f = 0;
-	auto slot_record_bytes = [&m, ped_slots](size_t ri) -> uint64_t {   // record of one slot run: only launched workgroups write
-		const SlotRun& run = m.splan.runs[ri];
-		if (ped_slots) return (uint64_t)m.splan.pextra[ri].rec_words * 4ull << run.g;
-		return slot_run_record_bytes(run);
-	};
-	const uint64_t arena_cap = arena_capacity(b.free_b, n, m.table_bytes, m.arena_limit);
-	b.arena_cap = arena_cap;
-	std::vector<uint32_t>& window_first_col = b.window_first_col;
-	uint64_t bt_max = 0;
-	auto open_unit = [&bt, &bt_max, &window_first_col, arena_cap](uint32_t c, uint64_t bytes) -> bool {   // a backtrace unit of `bytes` starts at column c
-		if (bytes + 16 > arena_cap) return false;
-		if (bt + bytes + 16 > arena_cap) {
-			bt_max = std::max(bt_max, bt);
-			bt = 0;
-			window_first_col.push_back(c);
-		}
-		return true;
-	};
-	auto unit_too_large = [&msg, &b](uint32_t c) {
-		msg = "the backtrace record of the unit at column " + std::to_string(c) + " alone does not fit in the arena (" + std::to_string(b.arena_cap >> 20) +
-		      " MiB of " + std::to_string(b.free_b >> 20) + " MiB free HBM)";
-		return WHAMD_ERR_UNSUPPORTED;
-	};
-	for (uint32_t c = 0; c < n; ++c) {
-		DevColumn& d = m.cols[c];
-		const bool in_slot_run = m.use_slots && m.splan.col_to_row[c] >= 0;   // (the run kernels read none of the per-column arrays)
-		d.seg_off = (uint32_t)segs.size();
-		const uint32_t kmask = d.k >= 32 ? 0xFFFFFFFFu : ((1u << d.k) - 1u);
-		if (!in_slot_run) {
-			append_segments(p.fwd_mask[c], segs, d.nseg_fwd);
-			append_segments(kmask & ~p.fwd_mask[c], segs, d.nseg_end);
-		}
-		d.bt_off = bt;
-		if (m.use_slots && m.splan.col_to_row[c] >= 0) {
-			d.mode = 3;
-			d.res_idx = (uint32_t)m.splan.col_to_row[c];
-			if (slot_cursor < m.splan.runs.size() && m.splan.runs[slot_cursor].c0 == c) {  // first column of a slot run
-				SlotRun& run = m.splan.runs[slot_cursor];
-				if (!open_unit(c, slot_record_bytes(slot_cursor))) return unit_too_large(c);
-				run.rec_lo = (uint32_t)bt;
-				run.rec_hi = (uint32_t)(bt >> 32);
-				seg_bt = bt;
-				bt += slot_record_bytes(slot_cursor);
-				max_f = std::max(max_f, run.L + run.g);   // entry / exit indices in physical order need 2^(L + g) entries
-				++slot_cursor;
-			}
-			d.bt_off = seg_bt;
-		} else if (m.plan.col_to_res[c] >= 0) {
-			d.mode = 2;
-			d.res_idx = (uint32_t)m.plan.col_to_res[c];
-			if (seg_cursor < m.plan.segments.size() && m.plan.segments[seg_cursor].c0 == c) {  // first column of a run
-				ResSegment& sgm = m.plan.segments[seg_cursor];
-				if (!open_unit(c, (uint64_t)sgm.stage_words * (1ull << sgm.g) * 8ull)) return unit_too_large(c);
-				sgm.bt_lo = (uint32_t)bt;
-				sgm.bt_hi = (uint32_t)(bt >> 32);
-				seg_bt = bt;
-				bt += (uint64_t)sgm.stage_words * (1ull << sgm.g) * 8ull;
-				++seg_cursor;
-			}
-			d.bt_off = seg_bt;
-		} else {
-			d.mode = column_step_mode(b.force_keys, d.is_last, d.f, d.ebits);
-			const uint64_t bytes = column_record_bytes(d.mode, p.T, d.f, d.nplanes);
-			if (!open_unit(c, bytes)) return unit_too_large(c);
-			d.bt_off = bt;
-			bt += bytes;
-			if (d.mode != 0) max_keys_f = std::max(max_keys_f, d.f);
-		}
-		bt = (bt + 15ull) & ~15ull;
-		max_f = std::max(max_f, d.f);
-	}
-	b.laps.lap("column descriptors (host)");
-	bt = std::max(bt_max, bt);
-	b.bt = bt;
-	b.max_f = max_f;
-	b.max_keys_f = max_keys_f;
-	b.exchange_bytes = (size_t)(1ull << max_f) * p.T * 4;
-	m.bt_bytes = bt;
-	m.windowed = !window_first_col.empty();
-	m.checkpoint_bytes = b.exchange_bytes;
-	const uint64_t need = bt + (2ull + window_first_col.size()) * b.exchange_bytes + (1ull << max_keys_f) * p.T * 8ull;
-	if (need + (1ull << 30) > b.free_b) {
-		msg = "backtrace arena of " + std::to_string(need >> 20) + " MiB does not fit in free HBM (" + std::to_string(b.free_b >> 20) + " MiB)";
-		return WHAMD_ERR_UNSUPPORTED;
-	}
-	return WHAMD_OK;
-}
-
-// An upper bound of what the phases below hand to TableUploader::up (the size of the table's device block and staging image).
-size_t DeviceTable::Impl::upload_bound(const Problem& p, const TableBuild& b) const {
-	const Impl& m = *this;
-	const size_t delta_count = p.n_ind == 0 ? std::max<size_t>(p.col_ptr[b.n], 1) : (size_t)p.col_ptr[b.n] * p.n_ind;
-	const size_t super_upload = m.device_superreads ? ((size_t)b.n + 1) * 8 + b.n + 1024 : 0;
-	return m.cols.size() * sizeof(DevColumn) + delta_count * sizeof(int32_t) + b.term_ptr32.size() * 4 + (p.terms.size() + p.fterms.size()) * sizeof(DevTerm) + b.segs.size() * 4 +
-	       m.plan.columns.size() * (sizeof(ResColumn) + sizeof(ResBacktrace) + sizeof(PedColumn)) + m.plan.ped_terms.size() * sizeof(PedTerm) +
-	       (m.splan.rows.size() + SLOT_ROW_PAD) * sizeof(SlotRow) + m.splan.prows.size() * sizeof(PedSlotRow) + m.splan.bt_cols.size() * (sizeof(SlotBtCol) + 8) +
-	       m.splan.runs.size() * (sizeof(SlotRun) + sizeof(PedSlotExtra) + sizeof(BtUnit) + sizeof(SlotBatchEntry) + 64) + m.plan.segments.size() * (sizeof(ResBatchEntry) + sizeof(BtUnit)) + super_upload + ((size_t)8 << 20);
 }
 
 // The per-column arrays (descriptors, deltas, term offsets, terms -- whole, or only the columns outside slot runs), the superread inputs, segment lists and the
@@ -958,276 +597,99 @@ whamd_status_t DeviceTable::Impl::upload_column_arrays(const Problem& p, TableBu
 	// kernels and slot_tables work from the rows, the backtrace from its units -- so only the columns outside runs travel (the coverage ramp, the last column, what an
 	// irregular layout leaves between runs): 96 of a column's 450 bytes, and concurrent creates are bound by bytes through the link.  The arrays keep
 	// their size and indexing on the device; the pieces that are not sent are never read.
-	const bool sparse_columns = m.use_slots && !b.ped_slots && p.T == 1 && !m.windowed && !debug_env("WHAMD_DENSE_COLUMN_UPLOAD");
+	const bool sparse_columns = m.tp.use_slots && !b.ped_slots && p.T == 1 && !m.tp.windowed && !debug_env("WHAMD_DENSE_COLUMN_UPLOAD");
 	if (sparse_columns) {
 		std::vector<std::pair<size_t, size_t>> pc_cols, pc_delta, pc_tptr, pc_terms;   // byte ranges of the columns [c, e) outside runs
 		for (uint32_t c = 0; c < n;) {
-			if (m.splan.col_to_row[c] >= 0) { ++c; continue; }
+			if (m.tp.splan.col_to_row[c] >= 0) { ++c; continue; }
 			uint32_t e = c + 1;
-			while (e < n && m.splan.col_to_row[e] < 0) ++e;
+			while (e < n && m.tp.splan.col_to_row[e] < 0) ++e;
 			pc_cols.emplace_back((size_t)c * sizeof(DevColumn), (size_t)e * sizeof(DevColumn));
 			pc_delta.emplace_back((size_t)p.col_ptr[c] * p.n_ind * sizeof(int32_t), (size_t)p.col_ptr[e] * p.n_ind * sizeof(int32_t));
 			pc_tptr.emplace_back((size_t)c * (p.T + 1) * sizeof(uint32_t), (size_t)e * (p.T + 1) * sizeof(uint32_t));
 			pc_terms.emplace_back((size_t)p.term_ptr[(size_t)c * p.T] * sizeof(DevTerm), (size_t)p.term_ptr[(size_t)e * p.T] * sizeof(DevTerm));
 			c = e;
 		}
-		HIP_TRY(up.up_pieces((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn), pc_cols));
+		HIP_TRY(up.up_pieces((void**)&m.dev.d_cols, m.tp.cols.data(), m.tp.cols.size() * sizeof(DevColumn), pc_cols));
 		// (the deltas travel whole when the device makes the superreads: superreads_single reads every column's)
-		if (m.device_superreads) HIP_TRY(up.up((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t)));
-		else HIP_TRY(up.up_pieces((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t), pc_delta));
-		HIP_TRY(up.up_pieces((void**)&m.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t), pc_tptr));
-		HIP_TRY(up.up_pieces((void**)&m.dp.terms, terms.data(), terms.size() * sizeof(DevTerm), pc_terms));
+		if (m.tp.device_superreads) HIP_TRY(up.up((void**)&m.dev.dp.delta, delta_src, delta_count * sizeof(int32_t)));
+		else HIP_TRY(up.up_pieces((void**)&m.dev.dp.delta, delta_src, delta_count * sizeof(int32_t), pc_delta));
+		HIP_TRY(up.up_pieces((void**)&m.dev.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t), pc_tptr));
+		HIP_TRY(up.up_pieces((void**)&m.dev.dp.terms, terms.data(), terms.size() * sizeof(DevTerm), pc_terms));
 	} else {
-		HIP_TRY(up.up((void**)&m.d_cols, m.cols.data(), m.cols.size() * sizeof(DevColumn)));
-		HIP_TRY(up.up((void**)&m.dp.delta, delta_src, delta_count * sizeof(int32_t)));
-		HIP_TRY(up.up((void**)&m.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t)));
-		HIP_TRY(up.up((void**)&m.dp.terms, terms.data(), terms.size() * sizeof(DevTerm)));
+		HIP_TRY(up.up((void**)&m.dev.d_cols, m.tp.cols.data(), m.tp.cols.size() * sizeof(DevColumn)));
+		HIP_TRY(up.up((void**)&m.dev.dp.delta, delta_src, delta_count * sizeof(int32_t)));
+		HIP_TRY(up.up((void**)&m.dev.dp.term_ptr, b.term_ptr32.data(), b.term_ptr32.size() * sizeof(uint32_t)));
+		HIP_TRY(up.up((void**)&m.dev.dp.terms, terms.data(), terms.size() * sizeof(DevTerm)));
 	}
-	m.dp.cols = m.d_cols;
-	if (m.device_superreads) {
-		m.super_args = SuperreadArgs{};
-		HIP_TRY(up.up((void**)&m.super_args.col_ptr, p.col_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t)));
-		HIP_TRY(up.up((void**)&m.super_args.genotype, p.genotype.data(), (size_t)n));
-		m.super_args.delta = m.dp.delta;
-		m.super_args.n_cols = n;
-		m.super_words = (size_t)n + ((size_t)2 * n + 3) / 4;
+	m.dev.dp.cols = m.dev.d_cols;
+	if (m.tp.device_superreads) {
+		m.dev.super_args = SuperreadArgs{};
+		HIP_TRY(up.up((void**)&m.dev.super_args.col_ptr, p.col_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t)));
+		HIP_TRY(up.up((void**)&m.dev.super_args.genotype, p.genotype.data(), (size_t)n));
+		m.dev.super_args.delta = m.dev.dp.delta;
+		m.dev.super_args.n_cols = n;
+		m.tp.super_words = (size_t)n + ((size_t)2 * n + 3) / 4;
 	}
 	b.d_fterms = nullptr;
 	if (!p.fterms.empty()) HIP_TRY(up.up((void**)&b.d_fterms, p.fterms.data(), p.fterms.size() * sizeof(DevTerm)));   // factorised lines (pedslot_tables, PSLOT_FACT)
-	HIP_TRY(up.up((void**)&m.dp.segs, b.segs.data(), b.segs.size() * sizeof(uint32_t)));
-	HIP_TRY(up.up((void**)&m.dp.res_cols, m.plan.columns.data(), m.plan.columns.size() * sizeof(ResColumn)));
-	HIP_TRY(up.up((void**)&m.dp.res_bt, m.plan.backtrace.data(), m.plan.backtrace.size() * sizeof(ResBacktrace)));
-	m.plan.ped_columns.resize(m.plan.ped_columns.empty() ? 0 : m.plan.columns.size());
-	HIP_TRY(up.up((void**)&m.dp.ped_cols, m.plan.ped_columns.data(), m.plan.ped_columns.size() * sizeof(PedColumn)));
-	HIP_TRY(up.up((void**)&m.dp.ped_terms, m.plan.ped_terms.data(), m.plan.ped_terms.size() * sizeof(PedTerm)));
+	HIP_TRY(up.up((void**)&m.dev.dp.segs, b.segs.data(), b.segs.size() * sizeof(uint32_t)));
+	HIP_TRY(up.up((void**)&m.dev.dp.res_cols, m.tp.plan.columns.data(), m.tp.plan.columns.size() * sizeof(ResColumn)));
+	HIP_TRY(up.up((void**)&m.dev.dp.res_bt, m.tp.plan.backtrace.data(), m.tp.plan.backtrace.size() * sizeof(ResBacktrace)));
+	m.tp.plan.ped_columns.resize(m.tp.plan.ped_columns.empty() ? 0 : m.tp.plan.columns.size());
+	HIP_TRY(up.up((void**)&m.dev.dp.ped_cols, m.tp.plan.ped_columns.data(), m.tp.plan.ped_columns.size() * sizeof(PedColumn)));
+	HIP_TRY(up.up((void**)&m.dev.dp.ped_terms, m.tp.plan.ped_terms.data(), m.tp.plan.ped_terms.size() * sizeof(PedTerm)));
 	b.laps.lap("column arrays: allocations + copies");
 	return WHAMD_OK;
-}
-
-// Slot runs: the backtrace blob ([ncols] SlotBtCol + ending slots per run) and where every run's piece lies in it (b.slot_blob_off / _words).  Host only.
-void DeviceTable::Impl::build_slot_blobs(TableBuild& b) const {
-	const Impl& m = *this;
-	b.slot_blob_off.assign(m.splan.runs.size(), 0);
-	b.slot_blob_words.assign(m.splan.runs.size(), 0);
-	// offsets first (one pass over the runs), then every run copies its own piece (8 MB for configs[2]: 0.9 ms when it was one growing vector)
-	size_t words = 0;
-	for (size_t ri = 0; ri < m.splan.runs.size(); ++ri) {
-		const SlotRun& run = m.splan.runs[ri];
-		b.slot_blob_off[ri] = (uint32_t)words;
-		b.slot_blob_words[ri] = (uint32_t)((size_t)run.ncols * (sizeof(SlotBtCol) / 4) + (run.n_ends + 3) / 4 + 1);
-		words += b.slot_blob_words[ri];
-	}
-	b.slot_blob.resize(words);
-	uint32_t* blob = b.slot_blob.data();
-	const uint32_t* blob_off = b.slot_blob_off.data();
-	parallel_ranges(m.splan.runs.size(), host_threads(m.splan.runs.size(), 512), [&m, blob, blob_off](uint64_t r0, uint64_t r1, uint32_t) {
-		for (size_t ri = r0; ri < r1; ++ri) {
-			const SlotRun& run = m.splan.runs[ri];
-			uint32_t* dst = blob + blob_off[ri];
-			const size_t col_words = (size_t)run.ncols * (sizeof(SlotBtCol) / 4);
-			std::memcpy(dst, m.splan.bt_cols.data() + run.row_off, col_words * 4);
-			const size_t end_words = (run.n_ends + 3) / 4 + 1;
-			std::memset(dst + col_words, 0, end_words * 4);
-			if (run.n_ends) std::memcpy(dst + col_words, m.splan.end_slots.data() + m.splan.end_off[ri], run.n_ends);
-		}
-	});
-}
-
-// Single-individual slot runs: where the prologue's tables of every run (SlotRun::tab_g / tab_w / tab_sl, an X run's tab_kr / tab_par) lie in the table block that
-// slot_tables fills; marks the X runs.  Returns the block's size in words.  Host only, and the same on every call (the preview lays the tables out before the create does).
-uint64_t DeviceTable::Impl::lay_out_slot_tables(const TableBuild& b, bool report) {
-	Impl& m = *this;
-	uint64_t slot_tab_words = 0;
-	for (SlotRun& run : m.splan.runs) {
-		auto pad4 = [](uint64_t v) { return (v + 3ull) & ~3ull; };
-		// X runs (kernels_slots.h, slot_runx_body): a Y-form run with four cells per thread whose columns and ending reads fit the kernel's registers; the
-		// rows of its tables are padded with zero columns to a pair of trips
-		const bool xrun = (run.yflags & 1u) && (run.lr == 2u || (run.lr == 3u && !debug_env("WHAMD_NO_XRUN8"))) && run.ncols <= (uint32_t)SLOT_XCOLS &&
-		                  run.n_ends <= (uint32_t)SLOT_XENDS && !debug_env("WHAMD_NO_XRUN");
-		const uint64_t ncp = xrun ? ((run.ncols + 7u) & ~7u) : run.ncols;
-		run.tab_g = (uint32_t)slot_tab_words;
-		slot_tab_words += pad4(ncp << (run.g - run.half));
-		run.tab_w = (uint32_t)slot_tab_words;
-		slot_tab_words += pad4(ncp * (run.threads >> 6));
-		run.tab_sl = (uint32_t)slot_tab_words;
-		slot_tab_words += ncp * 64u;
-		if (xrun) {
-			run.yflags |= 8u;
-			slot_tab_words = (slot_tab_words + 15u) & ~(uint64_t)15;   // (a trip's sixteen Kr words are ONE 64-byte line of the scalar cache)
-			run.tab_kr = (uint32_t)slot_tab_words;
-			slot_tab_words += pad4((((uint64_t)run.ncols + SLOT_XPAD) << run.lr) + run.ncols + SLOT_XPAD);   // Kr words, then one control word per column
-			run.tab_par = (uint32_t)slot_tab_words;
-			slot_tab_words += pad4((uint64_t)run.threads + (1ull << (run.g - run.half)));
-		}
-	}
-	slot_tab_words += (uint64_t)SLOT_XCOLS * 64u;   // (an X run requests the lane parts of SLOT_XCOLS columns whatever its length)
-	if (b.laps.on && report) {
-		size_t nx = 0, not_y = 0, not_lr = 0, long_run = 0, many_ends = 0;
-		for (const SlotRun& run : m.splan.runs) {
-			nx += (run.yflags & 8u) != 0;
-			not_y += !(run.yflags & 1u); not_lr += run.lr != 2u && run.lr != 3u; long_run += run.ncols > (uint32_t)SLOT_XCOLS; many_ends += run.n_ends > (uint32_t)SLOT_XENDS;
-		}
-		fprintf(stderr, "[whamd timing]   X runs: %zu of %zu (not Y form %zu, cells per thread %zu, more than %d columns %zu, more than %d ending reads %zu)\n", nx, m.splan.runs.size(), not_y,
-		        not_lr, SLOT_XCOLS, long_run, SLOT_XENDS, many_ends);
-	}
-	return slot_tab_words;
 }
 
 // What the slot-run kernels read: rows, backtrace blobs, control words, the runs themselves and the block their tables are built in (single individual:
 // slot_tables; pedigree: pedslot_tables, with the pedigree rows and extras).  Produces b.d_runs / b.d_pextra for launch_table_kernels.
 whamd_status_t DeviceTable::Impl::upload_slot_arrays(TableBuild& b, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	build_slot_blobs(b);
+	build_slot_blobs(m.tp, b);
 	b.laps.lap("slot backtrace blobs (host)");
-	if (!m.splan.rows.empty()) m.splan.rows.resize(m.splan.rows.size() + SLOT_ROW_PAD);   // the kernel's scalar-cache warm-up touches a fixed number of rows
-	HIP_TRY(up.up((void**)&m.dp.slot_rows, m.splan.rows.data(), m.splan.rows.size() * sizeof(SlotRow)));
+	if (!m.tp.splan.rows.empty()) m.tp.splan.rows.resize(m.tp.splan.rows.size() + SLOT_ROW_PAD);   // the kernel's scalar-cache warm-up touches a fixed number of rows
+	HIP_TRY(up.up((void**)&m.dev.dp.slot_rows, m.tp.splan.rows.data(), m.tp.splan.rows.size() * sizeof(SlotRow)));
 	b.laps.lap("slot rows: allocation + copy");
-	HIP_TRY(up.up((void**)&m.dp.slot_blob, b.slot_blob.data(), b.slot_blob.size() * sizeof(uint32_t)));
-	HIP_TRY(up.up((void**)&m.dp.slot_ctrl, m.splan.ctrl.data(), m.splan.ctrl.size() * sizeof(uint32_t)));
-	m.dp.slot_tab = nullptr;
+	HIP_TRY(up.up((void**)&m.dev.dp.slot_blob, b.slot_blob.data(), b.slot_blob.size() * sizeof(uint32_t)));
+	HIP_TRY(up.up((void**)&m.dev.dp.slot_ctrl, m.tp.splan.ctrl.data(), m.tp.splan.ctrl.size() * sizeof(uint32_t)));
+	m.dev.dp.slot_tab = nullptr;
 	b.d_runs = nullptr;
-	if (m.use_slots && !b.ped_slots) {
-		const uint64_t slot_tab_words = lay_out_slot_tables(b);
+	if (m.tp.use_slots && !b.ped_slots) {
+		const uint64_t slot_tab_words = lay_out_slot_tables(m.tp, b);
 		if (slot_tab_words >= 0xFFFFFFFFull) { msg = "slot-run tables exceed 32-bit offsets"; return WHAMD_ERR_UNSUPPORTED; }
-		HIP_TRY(up.up((void**)&b.d_runs, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
+		HIP_TRY(up.up((void**)&b.d_runs, m.tp.splan.runs.data(), m.tp.splan.runs.size() * sizeof(SlotRun)));
 		b.laps.lap("slot blobs, control words, runs: allocations + copies");
-		HIP_TRY(up.alloc((void**)&m.dp.slot_tab, slot_tab_words * 4));
+		HIP_TRY(up.alloc((void**)&m.dev.dp.slot_tab, slot_tab_words * 4));
 		b.laps.lap("slot tables: allocation");
 	}
-	m.dp.pslot_rows = nullptr;
-	m.dp.pslot_tab = nullptr;
+	m.dev.dp.pslot_rows = nullptr;
+	m.dev.dp.pslot_tab = nullptr;
 	b.d_pextra = nullptr;
 	if (b.ped_slots) {
-		HIP_TRY(up.up((void**)&m.dp.pslot_rows, m.splan.prows.data(), m.splan.prows.size() * sizeof(PedSlotRow)));
-		HIP_TRY(up.up((void**)&b.d_runs, m.splan.runs.data(), m.splan.runs.size() * sizeof(SlotRun)));
-		HIP_TRY(up.up((void**)&b.d_pextra, m.splan.pextra.data(), m.splan.pextra.size() * sizeof(PedSlotExtra)));
-		HIP_TRY(up.alloc((void**)&m.dp.pslot_tab, m.table_bytes));
+		HIP_TRY(up.up((void**)&m.dev.dp.pslot_rows, m.tp.splan.prows.data(), m.tp.splan.prows.size() * sizeof(PedSlotRow)));
+		HIP_TRY(up.up((void**)&b.d_runs, m.tp.splan.runs.data(), m.tp.splan.runs.size() * sizeof(SlotRun)));
+		HIP_TRY(up.up((void**)&b.d_pextra, m.tp.splan.pextra.data(), m.tp.splan.pextra.size() * sizeof(PedSlotExtra)));
+		HIP_TRY(up.alloc((void**)&m.dev.dp.pslot_tab, m.tp.table_bytes));
 	}
 	b.laps.lap("slot rows / blobs / control words: allocations + copies");
 	return WHAMD_OK;
 }
 
-// Jobs (see Impl::Job): connected components made of runs only get their own job.  Host only.
-void DeviceTable::Impl::make_jobs() {
-	Impl& m = *this;
-	m.release_lanes();
-	Impl::Job final_job;
-	final_job.final = true;
-	std::vector<Impl::Job> component_jobs;
-	const std::vector<uint32_t>& first = m.plan.component_first_step;
-	// Components as jobs of their own run side by side on lanes -- and walk back one after the other through the SEQUENTIAL backtrace (the chunked one takes a
-	// single job): 16 ms for an irregular coverage-20 table of 200 000 columns whose forward pass is 57 ms, nearly all of it one giant component (a Poisson layout
-	// leaves a gap every few ten thousand columns).  A table whose largest component holds four fifths of its steps or more stays ONE job: the lanes would gain
-	// less than the walk loses ((1 - s) x forward against s x 16 ms).  WHAMD_SPLIT_COMPONENTS=1 (debug library): always split, as before.
-	size_t largest = 0;
-	for (size_t k = 0; k < first.size(); ++k) largest = std::max<size_t>(largest, (k + 1 < first.size() ? first[k + 1] : m.plan.steps.size()) - first[k]);
-	const bool worth_splitting = largest * 5 < m.plan.steps.size() * 4 || debug_env("WHAMD_SPLIT_COMPONENTS");
-	const bool split = m.max_lanes > 1 && first.size() > 1 && worth_splitting && !debug_env("WHAMD_DEBUG_STAMPS") && !m.windowed;
-	if (!split) {
-		for (uint32_t si = 0; si < m.plan.steps.size(); ++si) final_job.steps.push_back(si);
-	} else {
-		for (size_t k = 0; k < first.size(); ++k) {
-			const uint32_t s0 = first[k], s1 = k + 1 < first.size() ? first[k + 1] : (uint32_t)m.plan.steps.size();
-			Impl::Job* job = &final_job;
-			if (k + 1 < first.size()) { component_jobs.emplace_back(); job = &component_jobs.back(); }
-			for (uint32_t si = s0; si < s1; ++si) job->steps.push_back(si);
-		}
-	}
-	m.jobs.push_back(std::move(final_job));
-	for (Impl::Job& j : component_jobs) m.jobs.push_back(std::move(j));
-}
-
-// The backtrace units: every job's steps in reverse order, each with everything the walk needs of it.  Reads b.segs, b.slot_blob_off / _words.  Host only.
-void DeviceTable::Impl::make_units(const TableBuild& b) {
-	Impl& m = *this;
-	m.units.clear();
-	for (Impl::Job& job : m.jobs) {
-		job.unit_off = (uint32_t)m.units.size();
-		for (size_t sj = job.steps.size(); sj-- > 0;) {
-			const Step& st = m.plan.steps[job.steps[sj]];
-			BtUnit u{};
-			u.kind = st.kind;
-			if (st.kind == 0) {
-				// column step: everything the backtrace needs, so that its chain holds no descriptor load
-				const DevColumn& d = m.cols[st.index];
-				u.c0 = st.index;
-				u.ncols = 1;
-				u.g = d.f; u.Lf_last = d.mode; u.stage_words = d.nplanes; u.n_wext = d.ebits;
-				u.bt_lo = (uint32_t)d.bt_off; u.bt_hi = (uint32_t)(d.bt_off >> 32);
-				u.n_lext = d.nseg_fwd; u.pad0 = d.nseg_end;
-				const uint32_t nseg = (uint32_t)d.nseg_fwd + d.nseg_end;
-				if (nseg <= (uint32_t)(RES_IOSEG + RES_BT_LRUNS)) {
-					uint32_t* dst = u.wext;  // wext[6] and lext[10] are contiguous: 16 run slots
-					for (uint32_t i = 0; i < nseg; ++i) dst[i] = b.segs[d.seg_off + i];
-					u.pad1[0] = 1;  // runs are inline
-				}
-			} else if (st.kind == 2) {
-				const SlotRun& run = m.splan.runs[st.index];
-				SlotBtUnit su{};
-				su.kind = b.ped_slots ? 3 : 2; su.c0 = run.c0; su.ncols = run.ncols; su.blob_off = b.slot_blob_off[st.index];
-				su.g = run.g; su.L = run.L; su.n_ends = run.n_ends; su.threads = run.threads;
-				su.bt_lo = run.rec_lo; su.bt_hi = run.rec_hi; su.half = run.half; su.blob_words = b.slot_blob_words[st.index];
-				su.f_exit = m.splan.f_exit[st.index];
-				for (uint32_t j = 0; j < su.f_exit && j < 32; ++j) su.exit_pos[j] = (uint8_t)slot_pos(run.out_pos, m.splan.exit_slot[st.index][j]);
-				su.lr = run.lr;
-				if (b.ped_slots) { su.n_ends = m.splan.pextra[st.index].rec_words; su.lr = m.splan.pextra[st.index].tb; }   // kind 3: words of one workgroup's record, log2 T
-				for (uint32_t j = 0; j < su.f_exit && j < 32; ++j) su.exit_slot[j] = m.splan.exit_slot[st.index][j];
-				static_assert(sizeof(SlotBtUnit) == sizeof(BtUnit), "unit headers share one array");
-				std::memcpy(&u, &su, sizeof u);
-			} else {
-				const ResSegment& sgm = m.plan.segments[st.index];
-				u.c0 = sgm.c0; u.ncols = sgm.ncols; u.col_off = sgm.col_off; u.g = sgm.g; u.Lf_last = sgm.Lf_last;
-				u.stage_words = sgm.stage_words; u.n_wext = sgm.n_wext; u.bt_lo = sgm.bt_lo; u.bt_hi = sgm.bt_hi;
-				u.n_lext = sgm.n_lext;
-				u.pad0 = (uint32_t)sgm.bt_active | ((uint32_t)sgm.bt_simple << 16) | (sgm.half << 20);
-				std::copy(sgm.wext, sgm.wext + RES_IOSEG, u.wext);
-				std::copy(sgm.lext, sgm.lext + RES_BT_LRUNS, u.lext);
-			}
-			m.units.push_back(u);
-		}
-		job.unit_count = (uint32_t)m.units.size() - job.unit_off;
-	}
-}
-
-// Windows (see Impl::Window): the single job's steps cut where the arena offsets start over (b.window_first_col); their backtrace jobs, the kept boundary columns
-// and the state one window's walk hands to the next.
+// A windowed table (see Window): the windows and their backtrace jobs (cut_windows), the kept boundary columns and the state one window's walk hands to the next.
 whamd_status_t DeviceTable::Impl::make_windows(const TableBuild& b, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	m.dp.bt_state = nullptr;
-	if (!m.windowed) return WHAMD_OK;
-	const std::vector<uint32_t>& window_first_col = b.window_first_col;
-	const std::vector<uint32_t>& steps = m.jobs[0].steps;
-	const uint32_t n_steps = (uint32_t)steps.size();
-	auto first_col = [&m, &steps](uint32_t pos) {
-		const Step& st = m.plan.steps[steps[pos]];
-		return st.kind == 0 ? st.index : (st.kind == 2 ? m.splan.runs[st.index].c0 : m.plan.segments[st.index].c0);
-	};
-	Impl::Window w;
-	size_t next = 0;
-	for (uint32_t pos = 0; pos < n_steps; ++pos) {
-		if (next < window_first_col.size() && first_col(pos) == window_first_col[next]) {
-			w.step_hi = pos;
-			m.windows.push_back(w);
-			w = Impl::Window();
-			w.step_lo = pos;
-			++next;
-		}
-	}
-	w.step_hi = n_steps;
-	m.windows.push_back(w);
-	if (next != window_first_col.size()) { msg = "internal error: a window does not start at a step"; return WHAMD_ERR_DEVICE; }
+	m.dev.dp.bt_state = nullptr;
+	if (!m.tp.windowed) return WHAMD_OK;
 	std::vector<BtJob> wjobs;
-	for (size_t wi = 0; wi < m.windows.size(); ++wi) {   // units are the steps in reverse order
-		Impl::Window& win = m.windows[wi];
-		win.unit_off = n_steps - win.step_hi;
-		win.unit_count = win.step_hi - win.step_lo;
-		wjobs.push_back(BtJob{win.unit_off, win.unit_count, wi + 1 == m.windows.size() ? 1u : 2u, 0u});
-	}
-	HIP_TRY(up.up((void**)&m.d_window_jobs, wjobs.data(), wjobs.size() * sizeof(BtJob)));
-	HIP_TRY(up.alloc((void**)&m.d_checkpoints, (m.windows.size() - 1) * m.checkpoint_bytes));
-	HIP_TRY(up.alloc((void**)&m.d_bt_state, 16));
-	m.dp.bt_state = m.d_bt_state;
-	if (b.laps.on) fprintf(stderr, "[whamd timing] windowed solve: %zu windows, arena %.2f GB\n", m.windows.size(), (double)b.bt / 1e9);
+	const whamd_status_t cut = cut_windows(b, m.tp, wjobs, msg);
+	if (cut != WHAMD_OK) return cut;
+	HIP_TRY(up.up((void**)&m.dev.d_window_jobs, wjobs.data(), wjobs.size() * sizeof(BtJob)));
+	HIP_TRY(up.alloc((void**)&m.dev.d_checkpoints, (m.tp.windows.size() - 1) * m.tp.checkpoint_bytes));
+	HIP_TRY(up.alloc((void**)&m.dev.d_bt_state, 16));
+	m.dev.dp.bt_state = m.dev.d_bt_state;
+	if (b.laps.on) fprintf(stderr, "[whamd timing] windowed solve: %zu windows, arena %.2f GB\n", m.tp.windows.size(), (double)b.bt / 1e9);
 	return WHAMD_OK;
 }
 
@@ -1236,365 +698,121 @@ whamd_status_t DeviceTable::Impl::make_windows(const TableBuild& b, TableUploade
 // counters, the superreads.  Five copies per table -- 4.6 us each as blit kernels, one after the other on a group's stream: 2.6 ms behind a 96-table solve -- are one.
 whamd_status_t DeviceTable::Impl::take_result_block(uint32_t n, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	m.super_off = 2 * (size_t)n + 4 + m.jobs.size();
+	m.tp.super_off = 2 * (size_t)n + 4 + m.tp.jobs.size();
 	void* d_res = nullptr;
-	HIP_TRY(up.alloc(&d_res, (m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t) + 16));
+	HIP_TRY(up.alloc(&d_res, (m.tp.super_off + (m.tp.device_superreads ? m.tp.super_words : 0)) * sizeof(uint32_t) + 16));
 	uint32_t* res = (uint32_t*)d_res;
-	m.d_path_index = res;
-	m.d_path_trans = res + n;
-	m.d_score = res + 2 * (size_t)n;
-	m.d_job_scores = res + 2 * (size_t)n;
-	m.d_bt_counters = res + 2 * (size_t)n + m.jobs.size();
-	if (m.device_superreads) {
-		m.super_args.out = res + m.super_off;
-		m.super_args.path_index = m.d_path_index;
+	m.dev.d_path_index = res;
+	m.dev.d_path_trans = res + n;
+	m.dev.d_score = res + 2 * (size_t)n;
+	m.dev.d_job_scores = res + 2 * (size_t)n;
+	m.dev.d_bt_counters = res + 2 * (size_t)n + m.tp.jobs.size();
+	if (m.tp.device_superreads) {
+		m.dev.super_args.out = res + m.tp.super_off;
+		m.dev.super_args.path_index = m.dev.d_path_index;
 	}
 	return WHAMD_OK;
 }
 
-namespace {
-
-// Orientation generators of the speculative backtrace (BtChunk): per individual the transmission bits its relabelling flips -- a founder those of the
-// trios it is a parent of, a child both of its own trio (exact where genotypes are heterozygous); individuals that are
-// both, or pedigrees with more than BT_GENERATORS individuals, get no generator (still exact, more walked twice).  Pure in the problem.
-struct OrientationGenerators {
-	std::vector<int> of_individual;   // -1: none
-	std::vector<uint32_t> tflip;
-	explicit OrientationGenerators(const Problem& p) : of_individual(std::max<uint32_t>(p.n_ind, 1), -1) {
-		if (p.n_ind < 2 || p.n_ind > BT_GENERATORS) return;
-		for (uint32_t s = 0; s < p.n_ind; ++s) {
-			uint32_t as_parent = 0, as_child = 0;
-			for (uint32_t t3 = 0; t3 < p.n_triples; ++t3) {
-				if (p.triples[t3][0] == s) as_parent |= 1u << (2 * t3);
-				if (p.triples[t3][1] == s) as_parent |= 1u << (2 * t3 + 1);
-				if (p.triples[t3][2] == s) as_child |= 3u << (2 * t3);
-			}
-			if (as_parent && as_child) continue;
-			if (!as_parent && !as_child) continue;   // unrelated individual of a multi-sample table
-			of_individual[s] = (int)tflip.size();
-			tflip.push_back(as_parent | as_child);
-		}
-	}
-	// the orientations of a chunk that starts from the projection column of column c_last: bit j = j-th forwarded read
-	void orient(const Problem& p, uint32_t c_last, BtChunk& ch) const {
-		ch.n_orient = 1;
-		for (uint32_t q = 0; q < BT_GENERATORS; ++q) ch.flip[q] = 0;
-		if (p.n_triples == 0 && p.n_ind <= 1) {
-			const uint32_t fb = p.f[c_last];
-			ch.flip[0] = fb >= BT_STATE_TSHIFT ? BT_STATE_XMASK : ((1u << fb) - 1u);
-			ch.n_orient = 2;
-			return;
-		}
-		if (tflip.empty()) return;
-		const ColumnEntry* col = p.col_begin(c_last);
-		uint32_t bit = 0;
-		for (uint32_t j = 0; j < p.k[c_last]; ++j) {
-			if (!((p.fwd_mask[c_last] >> j) & 1u)) continue;
-			const int gq = of_individual[col[j].sample];
-			if (gq >= 0) ch.flip[gq] |= 1u << bit;
-			++bit;
-		}
-		for (size_t q = 0; q < tflip.size(); ++q) ch.flip[q] |= tflip[q] << BT_STATE_TSHIFT;
-		ch.n_orient = 1u << tflip.size();
-	}
-};
-
-}  // namespace
-
-namespace {
-// The chunk rule of the speculative backtrace over a job's units, newest first (unit u is the job's step size - 1 - u): a run that finds BT_CHUNK_RUNS runs in the
-// chunk in front of it starts a new chunk and leaves that chunk's seed.  starts(u, id) is called for every such unit, id = 1, 2, ...; returns how many there are.
-// (make_chunks walks the units with it, the preview the plan's steps: one rule.)
-template <class IsRun, class Starts>
-uint32_t cut_chunk_starts(size_t n_units, IsRun is_run, Starts starts) {
-	uint32_t n_spec = 0, runs_in_chunk = 0;
-	for (size_t u = 0; u < n_units; ++u) {
-		const bool run = is_run(u);
-		if (run && runs_in_chunk >= (uint32_t)BT_CHUNK_RUNS && u > 0) {
-			starts(u, ++n_spec);
-			runs_in_chunk = 0;
-		}
-		runs_in_chunk += run;
-	}
-	return n_spec;
-}
-// Whether a table walks back in chunks at all: runs (slot runs, or the LDS-resident trio runs), one job, not windowed, more than two chunks' worth of units.
-bool backtrace_is_chunked(bool on_runs, size_t n_jobs, bool windowed, size_t n_units) {
-	return on_runs && n_jobs == 1 && !windowed && !getenv("WHAMD_BT_SEQUENTIAL") && n_units > 2u * BT_CHUNK_RUNS;
-}
-// The seeds' stride: the most waves any run that leaves a seed has (at least 64 words).
-uint32_t seed_stride_of(uint32_t stride, const SlotRun& run) { return std::max(stride, (run.threads >> 6) << (run.g - run.half)); }
-}  // namespace
-
-// Chunks of the speculative backtrace (single job only); the run that leaves a chunk's seed gets its spec id.  Host only.
-// Produces m.use_chunks, m.chunks, m.n_spec, m.n_orient_max and m.dp.spec_stride.
-void DeviceTable::Impl::cut_chunks(const Problem& p) {
-	Impl& m = *this;
-	m.use_chunks = false;
-	m.chunks.clear();
-	m.n_spec = 0;
-	for (SlotRun& run : m.splan.runs) run.spec_id = 0;
-	const bool trio_runs = !m.use_slots && !m.plan.ped_columns.empty();   // LDS-resident trio runs (kernels_trio.h)
-	if (trio_runs) for (ResSegment& sgm : m.plan.segments) sgm.in_mirror_bit = 0;   // (trio runs have no mirror: the field carries the spec id)
-	if (!backtrace_is_chunked(m.use_slots || trio_runs, m.jobs.size(), m.windowed, m.units.size())) return;
-	m.use_chunks = true;
-	const OrientationGenerators generators(p);
-	BtChunk first{};
-	first.n_orient = 1;   // the newest chunk starts from the table's optimum
-	m.chunks.push_back(first);
-	m.n_spec = cut_chunk_starts(m.units.size(),
-		[&m, trio_runs](size_t u) { return m.units[u].kind == 2 || m.units[u].kind == 3 || (trio_runs && m.units[u].kind == 1); },
-		[&m, &p, &generators, trio_runs](size_t u, uint32_t id) {
-			m.chunks.back().unit_count = (uint32_t)u - m.chunks.back().unit_off;
-			BtChunk cur{};
-			cur.unit_off = (uint32_t)u;
-			cur.spec_id = id;
-			generators.orient(p, m.units[u].c0 + m.units[u].ncols - 1, cur);   // (the last column of unit u's step)
-			m.chunks.push_back(cur);
-			// the run of unit u leaves the seed: units are the job's steps in reverse order
-			const Step& st = m.plan.steps[m.jobs[0].steps[m.jobs[0].steps.size() - 1 - u]];
-			if (trio_runs) m.plan.segments[st.index].in_mirror_bit = id;
-			else m.splan.runs[st.index].spec_id = id;
-		});
-	m.chunks.back().unit_count = (uint32_t)m.units.size() - m.chunks.back().unit_off;
-	m.n_orient_max = 1;
-	for (const BtChunk& ch : m.chunks) m.n_orient_max = std::max(m.n_orient_max, ch.n_orient);
-	uint32_t stride = 64;
-	for (const SlotRun& run : m.splan.runs) if (run.spec_id) stride = seed_stride_of(stride, run);
-	if (trio_runs) for (const ResSegment& sgm : m.plan.segments) if (sgm.in_mirror_bit) stride = std::max(stride, (sgm.threads >> 6) << sgm.g);
-	m.dp.spec_stride = stride;
-}
-
-// The chunks (cut_chunks), their device copy, the walk's buffers and m.dp.spec_keys (the schedule's entries carry it and the stride).
+// The chunks (cut_chunks), their device copy, the walk's buffers and m.dev.dp.spec_keys (the schedule's entries carry it and the stride).
 whamd_status_t DeviceTable::Impl::make_chunks(const Problem& p, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
 	const uint32_t n = p.n_cols;
-	m.dp.spec_keys = nullptr;
-	m.cut_chunks(p);
-	if (!m.use_chunks) return WHAMD_OK;
-	const uint32_t stride = m.dp.spec_stride;
-	HIP_TRY(up.up((void**)&m.d_chunks, m.chunks.data(), m.chunks.size() * sizeof(BtChunk)));
-	HIP_TRY(up.alloc((void**)&m.d_unit_x, (size_t)m.n_orient_max * m.units.size() * 4));
-	HIP_TRY(up.alloc((void**)&m.d_path2, (size_t)m.n_orient_max * n * 4));
-	HIP_TRY(up.alloc((void**)&m.d_trans2, (size_t)m.n_orient_max * n * 4));
-	HIP_TRY(up.alloc((void**)&m.d_sel, m.units.size() + 16));
-	HIP_TRY(up.alloc((void**)&m.d_guess, m.chunks.size() * 4));
-	if (m.preview.spec_keys && m.preview.spec_bytes >= ((size_t)m.n_spec + 1) * stride * 8) m.dp.spec_keys = m.preview.spec_keys;   // (armed, and being written by the preview's launches)
-	else HIP_TRY(up.alloc((void**)&m.dp.spec_keys, ((size_t)m.n_spec + 1) * stride * 8));
+	m.dev.dp.spec_keys = nullptr;
+	cut_chunks(p, m.tp, m.dev.dp.spec_stride);
+	if (!m.tp.use_chunks) return WHAMD_OK;
+	const uint32_t stride = m.dev.dp.spec_stride;
+	HIP_TRY(up.up((void**)&m.dev.d_chunks, m.tp.chunks.data(), m.tp.chunks.size() * sizeof(BtChunk)));
+	HIP_TRY(up.alloc((void**)&m.dev.d_unit_x, (size_t)m.tp.n_orient_max * m.tp.units.size() * 4));
+	HIP_TRY(up.alloc((void**)&m.dev.d_path2, (size_t)m.tp.n_orient_max * n * 4));
+	HIP_TRY(up.alloc((void**)&m.dev.d_trans2, (size_t)m.tp.n_orient_max * n * 4));
+	HIP_TRY(up.alloc((void**)&m.dev.d_sel, m.tp.units.size() + 16));
+	HIP_TRY(up.alloc((void**)&m.dev.d_guess, m.tp.chunks.size() * 4));
+	if (m.preview.spec_keys && m.preview.spec_bytes >= ((size_t)m.tp.n_spec + 1) * stride * 8) m.dev.dp.spec_keys = m.preview.spec_keys;   // (armed, and being written by the preview's launches)
+	else HIP_TRY(up.alloc((void**)&m.dev.dp.spec_keys, ((size_t)m.tp.n_spec + 1) * stride * 8));
 	return WHAMD_OK;
 }
 
-// The units' device copy, the LDS sizes of the two backtrace kernels, the runs' table block, the backtrace arena (b.bt bytes: from the arena cache, else from the
-// driver), key scratch, the two exchange buffers of lane 0 and the pinned block a solve downloads into.
+// The backtrace arena of `bytes`: from the arena cache, else from the driver.
+whamd_status_t DeviceTable::Impl::take_arena(uint64_t bytes, std::string& msg) {
+	Impl& m = *this;
+	size_t got = 0;
+	void* d_bt = arena_take(m.device, bytes, got);
+	if (!d_bt) {
+		HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(bytes, 16)));
+		got = std::max<size_t>(bytes, 16);
+	}
+	m.dev.d_arena = d_bt;
+	m.dev.arena_bytes = got;
+	return WHAMD_OK;
+}
+
+// The units' device copy, the LDS sizes of the two backtrace kernels, the runs' table block, the backtrace arena (b.bt bytes), key scratch, the two exchange
+// buffers of lane 0 and the pinned block a solve downloads into.
 whamd_status_t DeviceTable::Impl::take_solve_buffers(const Problem& p, TableBuild& b, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	HIP_TRY(up.up((void**)&m.d_units, m.units.data(), m.units.size() * sizeof(BtUnit)));
-	{
-		uint32_t max_stage = 0;
-		for (const ResSegment& sgm : m.plan.segments) max_stage = std::max(max_stage, sgm.stage_words);
-		for (size_t ri = 0; ri < m.splan.runs.size(); ++ri)
-			max_stage = std::max(max_stage, b.ped_slots ? m.splan.pextra[ri].rec_words / 2u : (m.splan.runs[ri].n_ends * m.splan.runs[ri].threads + 7) / 8);
-		m.bt_lds = (size_t)2 * RES_MAXCOLS * 128 + 512 + 16 + (size_t)BT_CELLS * 4 + (size_t)RES_MAXCOLS * 4 + (size_t)max_stage * 8 + 16;
-		m.chunk_lds = (size_t)(32 + 4 + BT_CELLS + BT_CHUNK_BLOB) * 4 + (size_t)max_stage * 8 + 16;
-	}
+	HIP_TRY(up.up((void**)&m.dev.d_units, m.tp.units.data(), m.tp.units.size() * sizeof(BtUnit)));
+	backtrace_lds_sizes(b, m.tp);
 	void* d_rtab = nullptr;
-	const bool ped_plan = !m.plan.ped_columns.empty();
-	HIP_TRY(up.alloc(&d_rtab, m.plan.columns.size() * (ped_plan ? PED_TABLE : RES_TABLE) * sizeof(int32_t)));
-	m.dp.res_tables = ped_plan ? nullptr : (int32_t*)d_rtab;
-	m.dp.ped_tables = ped_plan ? (int32_t*)d_rtab : nullptr;
+	const bool ped_plan = !m.tp.plan.ped_columns.empty();
+	HIP_TRY(up.alloc(&d_rtab, m.tp.plan.columns.size() * (ped_plan ? PED_TABLE : RES_TABLE) * sizeof(int32_t)));
+	m.dev.dp.res_tables = ped_plan ? nullptr : (int32_t*)d_rtab;
+	m.dev.dp.ped_tables = ped_plan ? (int32_t*)d_rtab : nullptr;
 	b.laps.lap("jobs, backtrace units, schedule");
 	b.laps.next_stage();
 	{
-		if (m.d_arena && m.arena_bytes < std::max<size_t>(b.bt, 16)) {   // the preview took an arena that turns out too small: its launches are given up
+		if (m.dev.d_arena && m.dev.arena_bytes < std::max<size_t>(b.bt, 16)) {   // the preview took an arena that turns out too small: its launches are given up
 			HIP_TRY(hipStreamSynchronize(m.stream));
-			arena_give(m.device, m.d_arena, m.arena_bytes);
-			m.d_arena = nullptr;
-			m.arena_bytes = 0;
+			arena_give(m.device, m.dev.d_arena, m.dev.arena_bytes);
+			m.dev.d_arena = nullptr;
+			m.dev.arena_bytes = 0;
 		}
-		if (!m.d_arena) {   // (else: the arena the preview's launches are writing their records into)
-			size_t got = 0;
-			void* d_bt = arena_take(m.device, b.bt, got);
-			if (!d_bt) {
-				HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(b.bt, 16)));
-				got = std::max<size_t>(b.bt, 16);
-			}
-			m.d_arena = d_bt;
-			m.arena_bytes = got;
+		if (!m.dev.d_arena) {   // (else: the arena the preview's launches are writing their records into)
+			const whamd_status_t taken = m.take_arena(b.bt, msg);
+			if (taken != WHAMD_OK) return taken;
 		}
-		m.dp.bt = (uint8_t*)m.d_arena;
+		m.dev.dp.bt = (uint8_t*)m.dev.d_arena;
 	}
 	b.laps.next_stage();
-	m.key_entries = (size_t)(1ull << b.max_keys_f) * p.T;
-	HIP_TRY(up.alloc((void**)&m.dp.keys, m.key_entries * 8));
-	HIP_TRY(up.alloc((void**)&m.dp.last_keys, (size_t)MAX_T_WIDE * 8));
+	m.dev.key_entries = (size_t)(1ull << b.max_keys_f) * p.T;
+	HIP_TRY(up.alloc((void**)&m.dev.dp.keys, m.dev.key_entries * 8));
+	HIP_TRY(up.alloc((void**)&m.dev.dp.last_keys, (size_t)MAX_T_WIDE * 8));
 	if (m.preview.d_pr[0] && m.preview.exchange_bytes >= b.exchange_bytes) {   // (the exchange columns the preview's launches are handing each other)
-		m.d_pr[0] = m.preview.d_pr[0];
-		m.d_pr[1] = m.preview.d_pr[1];
+		m.dev.d_pr[0] = m.preview.d_pr[0];
+		m.dev.d_pr[1] = m.preview.d_pr[1];
 	} else {
-		HIP_TRY(up.alloc((void**)&m.d_pr[0], b.exchange_bytes));
-		HIP_TRY(up.alloc((void**)&m.d_pr[1], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.dev.d_pr[0], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.dev.d_pr[1], b.exchange_bytes));
 	}
-	HIP_TRY(pinned_take((m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t), (void**)&m.h_pinned, &m.h_pinned_bytes));
+	HIP_TRY(pinned_take((m.tp.super_off + (m.tp.device_superreads ? m.tp.super_words : 0)) * sizeof(uint32_t), (void**)&m.dev.h_pinned, &m.dev.h_pinned_bytes));
 	return WHAMD_OK;
 }
 
-// Lanes: longest job first to the least loaded lane; lane 0 always runs the final job.  Every lane but the first gets exchange buffers and key scratch of its own.
+// Lanes (assign_lanes): lane 0 runs on the table's buffers; every other lane gets exchange buffers and key scratch of its own.
 whamd_status_t DeviceTable::Impl::make_lanes(const TableBuild& b, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	// at most 1 GiB of private exchange buffers (coverage 23: 64 MiB per lane)
-	const size_t lane_bytes = 2 * b.exchange_bytes;
-	const size_t by_memory = std::max<size_t>(1, ((size_t)1 << 30) / std::max<size_t>(lane_bytes, 1));
-	const size_t n_lanes = std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)m.max_lanes, by_memory), m.jobs.size()));
-	m.lanes.assign(n_lanes, Impl::Lane());
-	std::vector<uint64_t> load(n_lanes, 0);
-	std::vector<uint32_t> order;
-	for (uint32_t j = 1; j < m.jobs.size(); ++j) order.push_back(j);
-	std::stable_sort(order.begin(), order.end(), [&m](uint32_t x, uint32_t y) { return m.jobs[x].steps.size() > m.jobs[y].steps.size(); });
-	m.lanes[0].jobs.push_back(0);
-	load[0] = m.jobs[0].steps.size() + 1;
-	for (uint32_t j : order) {
-		const size_t l = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-		m.lanes[l].jobs.push_back(j);
-		load[l] += m.jobs[j].steps.size() + 1;
-	}
-	m.lanes[0].d_pr[0] = m.d_pr[0];
-	m.lanes[0].d_pr[1] = m.d_pr[1];
-	m.lanes[0].d_keys = m.dp.keys;
-	for (size_t l = 1; l < n_lanes; ++l) {
-		HIP_TRY(up.alloc((void**)&m.lanes[l].d_pr[0], b.exchange_bytes));
-		HIP_TRY(up.alloc((void**)&m.lanes[l].d_pr[1], b.exchange_bytes));
-		HIP_TRY(up.alloc((void**)&m.lanes[l].d_keys, m.key_entries * 8));
+	assign_lanes(m.opt, b, m.tp);
+	m.tp.lanes[0].d_pr[0] = m.dev.d_pr[0];
+	m.tp.lanes[0].d_pr[1] = m.dev.d_pr[1];
+	m.tp.lanes[0].d_keys = m.dev.dp.keys;
+	for (size_t l = 1; l < m.tp.lanes.size(); ++l) {
+		HIP_TRY(up.alloc((void**)&m.tp.lanes[l].d_pr[0], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.tp.lanes[l].d_pr[1], b.exchange_bytes));
+		HIP_TRY(up.alloc((void**)&m.tp.lanes[l].d_keys, m.dev.key_entries * 8));
 	}
 	return WHAMD_OK;
-}
-
-// The schedule: the lanes advance in lockstep; super-step t holds step t of every lane that still has one.  Makes the entries of the batched launches
-// (m.entries / m.slot_entries: they carry the device pointers of everything above) and, windowed, the replay of every older window.  Host only.
-whamd_status_t DeviceTable::Impl::make_schedule(const TableBuild& b, std::string& msg) {
-	Impl& m = *this;
-	const bool ped_slots = b.ped_slots;
-	struct Cursor { size_t job_i = 0, step_i = 0; uint32_t flip = 0; };
-	std::vector<Cursor> cur(m.lanes.size());
-	for (;;) {
-		Impl::SuperStep ss;
-		ss.entry_off = (uint32_t)(m.use_slots ? m.slot_entries.size() : m.entries.size());
-		for (size_t li = 0; li < m.lanes.size(); ++li) {
-			Impl::Lane& lane = m.lanes[li];
-			Cursor& c = cur[li];
-			if (c.job_i == lane.jobs.size()) continue;
-			const uint32_t job_id = lane.jobs[c.job_i];
-			const Impl::Job& job = m.jobs[job_id];
-			const uint32_t si = job.steps[c.step_i];
-			const bool first = c.step_i == 0, last = c.step_i + 1 == job.steps.size();
-			const Step& step = m.plan.steps[si];
-			ss.io[0] = lane.d_pr[c.flip]; ss.io[1] = lane.d_pr[c.flip ^ 1];
-			if (step.kind == 2) {
-				SlotBatchEntry e{};
-				e.run = m.splan.runs[step.index];
-				if (first) e.run.has_prev = 0;  // a job starts from cost 0
-				e.prev = lane.d_pr[c.flip];
-				e.cur = lane.d_pr[c.flip ^ 1];
-				e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
-				if (m.splan.ped) {
-					const PedSlotExtra& pex = m.splan.pextra[step.index];
-					ss.lds = std::max<size_t>(ss.lds, pedslot_lds_bytes(e.run.threads, e.run.ncols, pex));
-				} else
-				ss.lds = std::max<size_t>(ss.lds, slot_run_lds_bytes(e.run.threads, e.run.lr, e.run.ncols));
-				e.pad = step.index;
-				// the owning table's arrays: a group launch (slot_group / pedslot_group) serves runs of several tables
-				if (ped_slots) e.ex = m.splan.pextra[step.index];
-				e.tab = ped_slots ? m.dp.pslot_tab : m.dp.slot_tab;
-				e.rows = ped_slots ? (const void*)m.dp.pslot_rows : (const void*)m.dp.slot_rows;
-				e.ctrl = m.dp.slot_ctrl;
-				e.bt = m.dp.bt;
-				e.spec_keys = m.dp.spec_keys;
-				e.spec_stride = m.dp.spec_stride;
-				if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) e.pad2 = (uint32_t)atoi(skip);   // (timing experiments in a group launch)
-				if (debug_env("WHAMD_NO_WARM")) e.pad2 |= 0x10000u;
-				ss.grid_x = std::max(ss.grid_x, 1u << (e.run.g - e.run.half));
-				ss.threads = std::max(ss.threads, e.run.threads);
-				m.slot_entries.push_back(e);
-				++ss.entry_count;
-			} else if (step.kind == 1) {
-				ResBatchEntry e{};
-				e.sg = m.plan.segments[step.index];
-				e.sg.pad = step.index;
-				if (first) e.sg.has_prev = 0;  // a job starts from cost 0
-				e.prev = lane.d_pr[c.flip];
-				e.cur = lane.d_pr[c.flip ^ 1];
-				e.score_out = (last && !job.final) ? m.d_job_scores + job_id : nullptr;
-				const size_t lds = e.sg.kind == 1
-					? ((((size_t)e.sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)e.sg.n_terms * 2 + 3) & ~(size_t)3) * 4 + 2 * ((size_t)16 << e.sg.max_l) + (size_t)e.sg.stage_words * 8)
-					: ((size_t)e.sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << e.sg.max_l) + (size_t)e.sg.stage_words * 8);
-				ss.lds = std::max(ss.lds, lds);
-				ss.grid_x = std::max(ss.grid_x, 1u << (e.sg.g - e.sg.half));
-				ss.threads = std::max(ss.threads, e.sg.threads);
-				ss.sym = ss.sym || e.sg.half || e.sg.in_half || e.sg.mirror_out;
-				m.entries.push_back(e);
-				++ss.entry_count;
-			} else {
-				ss.singles.push_back(Impl::Single{(uint32_t)li, si, c.flip, first, (last && !job.final) ? (int32_t)job_id : -1});
-			}
-			c.flip ^= 1;
-			if (last) { ++c.job_i; c.step_i = 0; } else ++c.step_i;
-		}
-		if (!ss.entry_count && ss.singles.empty()) break;
-		m.max_grid_x = std::max(m.max_grid_x, ss.grid_x * std::max(1u, ss.entry_count));
-		m.schedule.push_back(std::move(ss));
-	}
-	if (m.windowed) {
-		// one lane, one job: super-step i is step i.  Pass 1 = the schedule as it is, plus the kept columns and the
-		// walk of the newest window; then every older window again, newest first.
-		if (m.schedule.size() != m.jobs[0].steps.size()) { msg = "internal error: windowed schedule"; return WHAMD_ERR_DEVICE; }
-		const size_t nw = m.windows.size();
-		for (size_t wi = 0; wi + 1 < nw; ++wi) m.schedule[m.windows[wi].step_hi - 1].ck_save = (int32_t)wi;
-		m.schedule.back().bt_window = (int32_t)(nw - 1);
-		for (size_t wi = nw - 1; wi-- > 0;) {
-			const Impl::Window& win = m.windows[wi];
-			for (uint32_t pos = win.step_lo; pos < win.step_hi; ++pos) {
-				Impl::SuperStep again = m.schedule[pos];
-				again.ck_save = -1;
-				again.ck_load = (pos == win.step_lo && wi > 0) ? (int32_t)(wi - 1) : -1;
-				again.bt_window = pos + 1 == win.step_hi ? (int32_t)wi : -1;
-				m.schedule.push_back(std::move(again));
-			}
-		}
-	}
-	return WHAMD_OK;
-}
-
-// What a group submission reads of the schedule (see StepBrief / EntryBrief).  Host only.
-void DeviceTable::Impl::make_briefs() {
-	Impl& m = *this;
-	m.step_brief.clear();
-	m.entry_brief.clear();
-	if (!m.use_slots) return;
-	m.step_brief.reserve(m.schedule.size());
-	m.entry_brief.reserve(m.slot_entries.size());
-	for (const Impl::SuperStep& ss : m.schedule) {
-		m.step_brief.push_back(Impl::StepBrief{(uint32_t)m.entry_brief.size(), (uint32_t)ss.lds, (uint16_t)ss.entry_count, (uint8_t)(ss.singles.empty() ? 0 : 1), 0});
-		for (uint32_t q = 0; q < ss.entry_count; ++q) {
-			const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q];
-			Impl::EntryBrief eb{};
-			eb.grid_x = (uint16_t)(1u << (he.run.g - he.run.half));
-			eb.threads = (uint16_t)he.run.threads;
-			eb.lds_x = (uint32_t)((size_t)2 * he.run.threads * (4u << he.run.lr));
-			eb.variant = group_variants_of(he, m.splan.ped);
-			m.entry_brief.push_back(eb);
-		}
-	}
 }
 
 // The entries of the batched launches and the backtrace jobs: the last arrays of the image.
 whamd_status_t DeviceTable::Impl::upload_entries(TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	HIP_TRY(up.up((void**)&m.d_entries, m.entries.data(), m.entries.size() * sizeof(ResBatchEntry)));
-	m.slot_entries.resize(m.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_core)
-	HIP_TRY(up.up((void**)&m.d_slot_entries, m.slot_entries.data(), m.slot_entries.size() * sizeof(SlotBatchEntry)));
-	m.slot_entries.resize(m.slot_entries.size() - 2);
+	HIP_TRY(up.up((void**)&m.dev.d_entries, m.tp.entries.data(), m.tp.entries.size() * sizeof(ResBatchEntry)));
+	m.tp.slot_entries.resize(m.tp.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_core)
+	HIP_TRY(up.up((void**)&m.dev.d_slot_entries, m.tp.slot_entries.data(), m.tp.slot_entries.size() * sizeof(SlotBatchEntry)));
+	m.tp.slot_entries.resize(m.tp.slot_entries.size() - 2);
 	std::vector<BtJob> btjobs;
-	for (const Impl::Job& job : m.jobs) btjobs.push_back(BtJob{job.unit_off, job.unit_count, job.final ? 1u : 0u, 0u});
-	HIP_TRY(up.up((void**)&m.d_btjobs, btjobs.data(), btjobs.size() * sizeof(BtJob)));
+	for (const Job& job : m.tp.jobs) btjobs.push_back(BtJob{job.unit_off, job.unit_count, job.final ? 1u : 0u, 0u});
+	HIP_TRY(up.up((void**)&m.dev.d_btjobs, btjobs.data(), btjobs.size() * sizeof(BtJob)));
 	return WHAMD_OK;
 }
 
@@ -1606,22 +824,22 @@ whamd_status_t DeviceTable::Impl::launch_table_kernels(const Problem& p, const T
 	if (b.ped_slots) {
 		// the cost-form tables of every run (slots.h)
 		uint32_t most = 0;
-		for (size_t ri = 0; ri < m.splan.runs.size(); ++ri)
-			most = std::max<uint32_t>(most, (m.splan.pextra[ri].fwn << m.splan.runs[ri].g) + (m.splan.pextra[ri].fwn << m.splan.runs[ri].lw) + m.splan.runs[ri].ncols * (64u * pslot_ns(m.splan.pextra[ri].nf) + p.T * pslot_nk(m.splan.pextra[ri].nf)));
+		for (size_t ri = 0; ri < m.tp.splan.runs.size(); ++ri)
+			most = std::max<uint32_t>(most, (m.tp.splan.pextra[ri].fwn << m.tp.splan.runs[ri].g) + (m.tp.splan.pextra[ri].fwn << m.tp.splan.runs[ri].lw) + m.tp.splan.runs[ri].ncols * (64u * pslot_ns(m.tp.splan.pextra[ri].nf) + p.T * pslot_nk(m.tp.splan.pextra[ri].nf)));
 		const uint32_t bx = std::max(1u, std::min(1024u, (most + 255u) / 256u));
-		for (size_t r0 = 0; r0 < m.splan.runs.size(); r0 += 32768) {   // (gridDim.y <= 65535)
-			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.splan.runs.size() - r0);
-			hipLaunchKernelGGL(pedslot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, b.d_runs + r0, b.d_pextra + r0, (uint32_t*)m.dp.pslot_tab, b.d_fterms);
+		for (size_t r0 = 0; r0 < m.tp.splan.runs.size(); r0 += 32768) {   // (gridDim.y <= 65535)
+			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.tp.splan.runs.size() - r0);
+			hipLaunchKernelGGL(pedslot_tables, dim3(bx, ny), dim3(256), 0, us, m.dev.dp, b.d_runs + r0, b.d_pextra + r0, (uint32_t*)m.dev.dp.pslot_tab, b.d_fterms);
 		}
 		HIP_TRY(hipGetLastError());
 	}
-	if (m.use_slots && !b.ped_slots && !m.splan.runs.empty()) {
+	if (m.tp.use_slots && !b.ped_slots && !m.tp.splan.runs.empty()) {
 		uint32_t most = 0;
-		for (const SlotRun& run : m.splan.runs) most = std::max<uint32_t>(most, ((run.ncols + 8u) << (run.g - run.half)) + (run.ncols + 8u) * ((run.threads >> 6) + 64u));
+		for (const SlotRun& run : m.tp.splan.runs) most = std::max<uint32_t>(most, ((run.ncols + 8u) << (run.g - run.half)) + (run.ncols + 8u) * ((run.threads >> 6) + 64u));
 		const uint32_t bx = std::max(1u, std::min(64u, (most + 255u) / 256u));
-		for (size_t r0 = 0; r0 < m.splan.runs.size(); r0 += 32768) {
-			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.splan.runs.size() - r0);
-			hipLaunchKernelGGL(slot_tables, dim3(bx, ny), dim3(256), 0, us, m.dp, b.d_runs + r0, (uint32_t*)m.dp.slot_tab);
+		for (size_t r0 = 0; r0 < m.tp.splan.runs.size(); r0 += 32768) {
+			const uint32_t ny = (uint32_t)std::min<size_t>(32768, m.tp.splan.runs.size() - r0);
+			hipLaunchKernelGGL(slot_tables, dim3(bx, ny), dim3(256), 0, us, m.dev.dp, b.d_runs + r0, (uint32_t*)m.dev.dp.slot_tab);
 		}
 		HIP_TRY(hipGetLastError());
 	}
@@ -1637,25 +855,25 @@ whamd_status_t DeviceTable::Impl::launch_table_kernels(const Problem& p, const T
 	return WHAMD_OK;
 }
 
-// The in-kernel cycle stamps and timing experiments of the debug library (m.dp.dbg, dbg_wg_off, dbg_flags).
+// The in-kernel cycle stamps and timing experiments of the debug library (m.dev.dp.dbg, dbg_wg_off, dbg_flags).
 whamd_status_t DeviceTable::Impl::arm_debug_stamps(TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	m.dp.dbg = nullptr;
-	if (debug_env("WHAMD_DEBUG_STAMPS") && !m.use_slots) {   // in-kernel cycle stamps of the LDS-resident runs (WHAMD_DEBUG_TIMING: host phases only)
-		const size_t dbg_bytes = (m.plan.segments.size() + 1) * 64 + 4 * 512 * 16 + 64;
-		HIP_TRY(up.alloc((void**)&m.dp.dbg, dbg_bytes));
-		HIP_TRY(hipMemset(m.dp.dbg, 0, dbg_bytes));
-		m.dp.dbg_wg_off = (uint32_t)((m.plan.segments.size() + 1) * 8);
-		m.dp.dbg_flags = (uint32_t)atoi(debug_env("WHAMD_DEBUG_STAMPS"));
+	m.dev.dp.dbg = nullptr;
+	if (debug_env("WHAMD_DEBUG_STAMPS") && !m.tp.use_slots) {   // in-kernel cycle stamps of the LDS-resident runs (WHAMD_DEBUG_TIMING: host phases only)
+		const size_t dbg_bytes = (m.tp.plan.segments.size() + 1) * 64 + 4 * 512 * 16 + 64;
+		HIP_TRY(up.alloc((void**)&m.dev.dp.dbg, dbg_bytes));
+		HIP_TRY(hipMemset(m.dev.dp.dbg, 0, dbg_bytes));
+		m.dev.dp.dbg_wg_off = (uint32_t)((m.tp.plan.segments.size() + 1) * 8);
+		m.dev.dp.dbg_flags = (uint32_t)atoi(debug_env("WHAMD_DEBUG_STAMPS"));
 	}
-	if (debug_env("WHAMD_SLOT_STAMPS") && m.use_slots) {   // in-kernel cycle stamps of workgroup 0 / wave 0 of every slot run
-		const size_t dbg_bytes = (m.splan.runs.size() + 1) * 48 * 8 + 4 * 512 * 16 + 128;   // + the backtrace kernel's own stamps
-		HIP_TRY(up.alloc((void**)&m.dp.dbg, dbg_bytes));
-		HIP_TRY(hipMemset(m.dp.dbg, 0, dbg_bytes));
-		m.dp.dbg_wg_off = (uint32_t)((m.splan.runs.size() + 1) * 48);
-		for (size_t i = 0; i < m.slot_entries.size(); ++i) m.slot_entries[i].run.pad = (uint32_t)i;
+	if (debug_env("WHAMD_SLOT_STAMPS") && m.tp.use_slots) {   // in-kernel cycle stamps of workgroup 0 / wave 0 of every slot run
+		const size_t dbg_bytes = (m.tp.splan.runs.size() + 1) * 48 * 8 + 4 * 512 * 16 + 128;   // + the backtrace kernel's own stamps
+		HIP_TRY(up.alloc((void**)&m.dev.dp.dbg, dbg_bytes));
+		HIP_TRY(hipMemset(m.dev.dp.dbg, 0, dbg_bytes));
+		m.dev.dp.dbg_wg_off = (uint32_t)((m.tp.splan.runs.size() + 1) * 48);
+		for (size_t i = 0; i < m.tp.slot_entries.size(); ++i) m.tp.slot_entries[i].run.pad = (uint32_t)i;
 	}
-	if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) m.dp.dbg_flags = (uint32_t)atoi(skip);  // timing experiments (results invalid): 1 no exit
+	if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) m.dev.dp.dbg_flags = (uint32_t)atoi(skip);  // timing experiments (results invalid): 1 no exit
 	                                                                                          // stores, 2 no records, 4 one column per run, 8 no ending reads, 16 no cost update
 	return WHAMD_OK;
 }
@@ -1714,100 +932,28 @@ static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
 	return WHAMD_OK;
 }
 
-// What a batched backtrace launch reads for this table (BtGroupEntry): a copy of the finished m.dp and the walk's buffers, on the device behind `ev_upload`.
+// What a batched backtrace launch reads for this table (BtGroupEntry): a copy of the finished m.dev.dp and the walk's buffers, on the device behind `ev_upload`.
 whamd_status_t DeviceTable::Impl::record_group_backtrace(uint32_t n, TableUploader& up, std::string& msg) {
 	Impl& m = *this;
-	m.d_bt_entry = nullptr;
-	if (!m.use_chunks) return WHAMD_OK;
-	BtGroupEntry& e = m.h_bt_entry;
+	m.dev.d_bt_entry = nullptr;
+	if (!m.tp.use_chunks) return WHAMD_OK;
+	BtGroupEntry& e = m.dev.h_bt_entry;
 	e = BtGroupEntry{};
-	e.P = m.dp;
-	e.units = m.d_units; e.chunks = m.d_chunks;
-	e.n_chunks = (uint32_t)m.chunks.size(); e.n_units = (uint32_t)m.units.size(); e.n_orient_max = m.n_orient_max; e.n_cols = n;
-	e.path2 = m.d_path2; e.trans2 = m.d_trans2; e.out_score = m.d_score; e.unit_x2 = m.d_unit_x; e.guess = m.d_guess; e.sel = m.d_sel; e.counters = m.d_bt_counters;
-	e.path_index = m.d_path_index; e.path_trans = m.d_path_trans;
-	if (m.device_superreads) e.super = m.super_args;
+	e.P = m.dev.dp;
+	e.units = m.dev.d_units; e.chunks = m.dev.d_chunks;
+	e.n_chunks = (uint32_t)m.tp.chunks.size(); e.n_units = (uint32_t)m.tp.units.size(); e.n_orient_max = m.tp.n_orient_max; e.n_cols = n;
+	e.path2 = m.dev.d_path2; e.trans2 = m.dev.d_trans2; e.out_score = m.dev.d_score; e.unit_x2 = m.dev.d_unit_x; e.guess = m.dev.d_guess; e.sel = m.dev.d_sel; e.counters = m.dev.d_bt_counters;
+	e.path_index = m.dev.d_path_index; e.path_trans = m.dev.d_path_trans;
+	if (m.tp.device_superreads) e.super = m.dev.super_args;
 	void* d_entry = nullptr;
 	HIP_TRY(up.alloc(&d_entry, sizeof(BtGroupEntry)));
-	HIP_TRY(hipMemcpyAsync(d_entry, &m.h_bt_entry, sizeof(BtGroupEntry), hipMemcpyHostToDevice, up.stream));   // (the source is a member: it outlives the copy)
+	HIP_TRY(hipMemcpyAsync(d_entry, &m.dev.h_bt_entry, sizeof(BtGroupEntry), hipMemcpyHostToDevice, up.stream));   // (the source is a member: it outlives the copy)
 	HIP_TRY(hipEventRecord(m.ev_upload, up.stream));
-	m.d_bt_entry = (BtGroupEntry*)d_entry;
+	m.dev.d_bt_entry = (BtGroupEntry*)d_entry;
 	return WHAMD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------- the preview
-// Which steps a preview would launch and what each is given by value, worked out ahead of the phases that normally produce it.  Host only (the debug library's
-// whamd_debug_preview_plan holds it against lay_out_arena and cut_chunks without a device).  out.why says whether there is one: the table's form, the options,
-// and -- under `auto` -- that the table is alone.  The record offsets are the sum lay_out_arena will make, from its own helpers; the seeds' ids come from the
-// chunk rule make_chunks walks (cut_chunk_starts), here over the plan's steps.
-void DeviceTable::Impl::plan_preview(const Problem& p, const TableBuild& b, bool from_create, PreviewPlan& out) {
-	Impl& m = *this;
-	const Preview& pv = m.preview;
-	const uint32_t n = b.n, n_pieces = slot_plan_pieces(n);
-	out = PreviewPlan();
-	auto none = [&out](uint32_t why) { out.why = why; };
-	if (pv.mode == 0 || debug_env("WHAMD_NO_PREVIEW")) return none(PV_OFF);
-	if (!from_create) return none(PV_NOT_CREATE);
-	if (!m.use_slots || m.splan.ped || p.T != 1) return none(PV_NOT_SLOTS);
-	if (debug_env("WHAMD_DEBUG_STAMPS") || debug_env("WHAMD_SLOT_STAMPS") || debug_env("WHAMD_SLOT_SKIP")) return none(PV_DEBUG_SWITCH);
-	if (m.shared_hint || m.side_by_side) return none(PV_SHARED);
-	if (m.plan.component_first_step.size() != 1) return none(PV_COMPONENTS);
-	if (n_pieces < 2) return none(PV_FEW_PIECES);
-	if (pv.mode < 0) {   // auto: only where a speculative forward pass competes with nothing
-		if (pv.thread_budget) return none(PV_THREAD_BUDGET);
-		if (n_pieces < 8) return none(PV_FEW_PIECES);
-		if (m.device < 0 || m.device >= 64 || Impl::tables_on_device[m.device].load() != 1) return none(PV_NOT_ALONE);
-	}
-	out.pieces = std::min(n_pieces - 1, preview_pieces_of(pv.pieces_wanted, n_pieces));
-	const uint32_t col_limit = slot_plan_piece_begin(n, out.pieces);
-	// ---- the leading steps that are slot runs inside the pieces (a piece edge is a run boundary)
-	const std::vector<Step>& steps = m.plan.steps;
-	const std::vector<SlotRun>& runs = m.splan.runs;
-	uint32_t S = 0;
-	while (S < steps.size() && steps[S].kind == 2 && steps[S].index == S && runs[S].c0 + runs[S].ncols <= col_limit) ++S;
-	if (S == 0 || S >= steps.size()) return none(PV_NO_LEADING_RUNS);
-	out.end_col = runs[S - 1].c0 + runs[S - 1].ncols;
-	if ((size_t)out.end_col + SLOT_ROW_PAD > m.splan.rows.size()) return none(PV_ROW_PAD);   // (a run's scalar-cache warm-up touches a fixed number of rows behind its own)
-	// ---- what the runs carry by value: table offsets, record offsets, the ids of the seeds they leave
-	const uint64_t tab_words_all = m.lay_out_slot_tables(b, false);
-	out.tab_words = (S < runs.size() ? runs[S].tab_g : tab_words_all) + (uint64_t)SLOT_XCOLS * 64u;   // (lay_out_slot_tables: the slack an X run may request)
-	out.ctrl_words = (size_t)runs[S - 1].ctrl_off + SLOT_CTRL_WORDS;
-	if (tab_words_all >= 0xFFFFFFFFull || out.ctrl_words > m.splan.ctrl.size()) return none(PV_NO_LEADING_RUNS);
-	out.rec.assign(S, 0);
-	uint64_t bt = 0;
-	{
-		// the records of ALL steps, in order, as lay_out_arena places them when they fit one window (arena_capacity, arena_behind, the record sizes: its own)
-		const uint64_t cap = arena_capacity(b.free_b, n, m.table_bytes, m.arena_limit);
-		for (size_t k = 0; k < steps.size(); ++k) {
-			uint64_t bytes = 0;
-			if (steps[k].kind == 2) bytes = slot_run_record_bytes(runs[steps[k].index]);
-			else {
-				const uint32_t c = steps[k].index, f = p.f[c], ebits = p.k[c] - f;
-				bytes = column_record_bytes(column_step_mode(b.force_keys, c + 1 == n, f, ebits), p.T, f, ebits + b.tbits);
-			}
-			if (bt + bytes + 16 > cap) return none(PV_ARENA);   // (windowed, or too large altogether)
-			if (k < S) out.rec[k] = bt;
-			bt = arena_behind(bt, bytes);
-		}
-		if (bt + (1ull << 31) > b.free_b) return none(PV_ARENA);
-	}
-	out.arena = bt;
-	out.spec.assign(S, 0);
-	out.stride = 64;
-	out.chunked = backtrace_is_chunked(true, 1, false, steps.size());   // (one job of slot runs, not windowed: checked above)
-	if (out.chunked)
-		out.n_spec = cut_chunk_starts(steps.size(), [&steps](size_t u) { return steps[steps.size() - 1 - u].kind == 2; },
-			[&](size_t u, uint32_t id) {
-				const size_t k = steps.size() - 1 - u;
-				out.stride = seed_stride_of(out.stride, runs[steps[k].index]);
-				if (k < S) out.spec[k] = id;
-			});
-	out.max_f = p.max_k;   // (a bound of the widest exchange column: no column forwards more reads than it has, a run's entries are 2^(L + g))
-	for (const SlotRun& run : runs) out.max_f = std::max(out.max_f, run.L + run.g);
-	out.steps = S;
-	out.why = PV_RAN;
-}
-
 // A lone single-individual table's device sits idle through its whole create, and nothing of the create's second half -- column descriptors, the arena's layout,
 // staging and sending ~100 MB, backtrace units, schedule -- is needed by the FIRST launches, which read the rows, control words and tables of their own
 // columns only.  Right behind the plan this function therefore uploads exactly that for the runs plan_preview chose (a prefix of the arrays the table will
@@ -1817,7 +963,7 @@ whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b,
 	Impl& m = *this;
 	Preview& pv = m.preview;
 	PreviewPlan pp;
-	m.plan_preview(p, b, from_create, pp);
+	plan_preview(p, m.opt, b, m.tp, from_create, m.alone_on_device(), pp);
 	pv.why = pp.why;
 	if (pp.why != PV_RAN) return WHAMD_OK;
 	const uint32_t n = b.n, S = pp.steps, pieces = pp.pieces, end_col = pp.end_col, n_spec = pp.n_spec, stride = pp.stride, max_f = pp.max_f;
@@ -1826,30 +972,18 @@ whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b,
 	const bool chunked = pp.chunked;
 	const std::vector<uint64_t>& rec = pp.rec;
 	const std::vector<uint32_t>& spec = pp.spec;
-	const std::vector<SlotRun>& runs = m.splan.runs;
+	const std::vector<SlotRun>& runs = m.tp.splan.runs;
 	b.laps.lap("preview: steps, offsets, seeds (host)");
 	// ---- the buffers the solve writes: the table's from here on
-	auto take = [&m](void** out, size_t bytes) {
-		size_t got = 0;
-		const hipError_t e = devpool_take(m.device, std::max<size_t>(bytes, 16), out, &got);
-		if (e == hipSuccess) m.allocations.emplace_back(*out, got);
-		return e;
-	};
 	{
-		size_t got = 0;
-		void* d_bt = arena_take(m.device, bt, got);
-		if (!d_bt) {
-			HIP_TRY(hipMalloc(&d_bt, std::max<size_t>(bt, 16)));
-			got = std::max<size_t>(bt, 16);
-		}
-		m.d_arena = d_bt;
-		m.arena_bytes = got;
+		const whamd_status_t taken = m.take_arena(bt, msg);
+		if (taken != WHAMD_OK) return taken;
 	}
 	pv.exchange_bytes = (size_t)(1ull << max_f) * p.T * 4;
-	HIP_TRY(take((void**)&pv.d_pr[0], pv.exchange_bytes));
-	HIP_TRY(take((void**)&pv.d_pr[1], pv.exchange_bytes));
+	HIP_TRY(pool_alloc(m.device, m.dev.allocations, (void**)&pv.d_pr[0], pv.exchange_bytes));
+	HIP_TRY(pool_alloc(m.device, m.dev.allocations, (void**)&pv.d_pr[1], pv.exchange_bytes));
 	pv.spec_bytes = chunked ? ((size_t)n_spec + 1) * stride * 8 : 0;
-	if (chunked) HIP_TRY(take((void**)&pv.spec_keys, pv.spec_bytes));
+	if (chunked) HIP_TRY(pool_alloc(m.device, m.dev.allocations, (void**)&pv.spec_keys, pv.spec_bytes));
 	// ---- the preview's own arrays: a prefix of the table's rows, control words and runs; its tables
 	DevProblem hdp{};
 	hdp.n_cols = n; hdp.T = p.T; hdp.tbits = b.tbits; hdp.n_ind = p.n_ind;
@@ -1859,8 +993,8 @@ whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b,
 		const size_t row_count = (size_t)end_col + SLOT_ROW_PAD;
 		up.open_block(row_count * sizeof(SlotRow) + ctrl_words * 4 + (size_t)S * sizeof(SlotRun) + 4096);
 		const SlotRun* d_runs = nullptr;
-		HIP_TRY(up.up((void**)&hdp.slot_rows, m.splan.rows.data(), row_count * sizeof(SlotRow)));
-		HIP_TRY(up.up((void**)&hdp.slot_ctrl, m.splan.ctrl.data(), ctrl_words * 4));
+		HIP_TRY(up.up((void**)&hdp.slot_rows, m.tp.splan.rows.data(), row_count * sizeof(SlotRow)));
+		HIP_TRY(up.up((void**)&hdp.slot_ctrl, m.tp.splan.ctrl.data(), ctrl_words * 4));
 		HIP_TRY(up.up((void**)&d_runs, runs.data(), (size_t)S * sizeof(SlotRun)));
 		HIP_TRY(up.alloc((void**)&hdp.slot_tab, tab_words * 4));
 		HIP_TRY(up.flush());
@@ -1885,13 +1019,13 @@ whamd_status_t DeviceTable::Impl::start_preview(const Problem& p, TableBuild& b,
 	m.inflight.run_stream = rs;
 	m.own_stream_used = true;
 	HIP_TRY(hipStreamWaitEvent(rs, m.ev_upload, 0));
-	hdp.bt = (uint8_t*)m.d_arena;
+	hdp.bt = (uint8_t*)m.dev.d_arena;
 	hdp.spec_keys = pv.spec_keys;
 	hdp.spec_stride = stride;
 	if (chunked) HIP_TRY(hipMemsetAsync(pv.spec_keys, 0xFF, pv.spec_bytes, rs));
 	m.inflight.timing_pending = false;   // (the events are the coming solve's from here on)
 	HIP_TRY(hipEventRecord(m.ev0, rs));
-	m.use_chunks = chunked;   // (launch_slot_run: a run leaves a seed where the backtrace is chunked)
+	m.tp.use_chunks = chunked;   // (launch_slot_run: a run leaves a seed where the backtrace is chunked)
 #ifdef WHAMD_DEBUG_BUILD
 	m.ledger.clear();
 #endif
@@ -1935,13 +1069,13 @@ void DeviceTable::Impl::verify_preview() {
 	Preview& pv = m.preview;
 	pv.agreed = 0;
 	if (!pv.launched) return;
-	const bool same_ground = m.use_slots && !m.windowed && m.jobs.size() == 1 && m.lanes.size() == 1 && m.dp.bt == pv.dp.bt && m.dp.spec_keys == pv.dp.spec_keys &&
-	                         m.use_chunks == pv.use_chunks && (!m.use_chunks || m.dp.spec_stride == pv.dp.spec_stride) && !m.dp.dbg && !m.dp.dbg_flags &&
-	                         m.d_pr[0] == pv.d_pr[0] && m.d_pr[1] == pv.d_pr[1] && !m.side_by_side;
-	for (uint32_t k = 0; same_ground && k < pv.launched && k + 1 < m.schedule.size(); ++k) {
-		const Impl::SuperStep& ss = m.schedule[k];
+	const bool same_ground = m.tp.use_slots && !m.tp.windowed && m.tp.jobs.size() == 1 && m.tp.lanes.size() == 1 && m.dev.dp.bt == pv.dp.bt && m.dev.dp.spec_keys == pv.dp.spec_keys &&
+	                         m.tp.use_chunks == pv.use_chunks && (!m.tp.use_chunks || m.dev.dp.spec_stride == pv.dp.spec_stride) && !m.dev.dp.dbg && !m.dev.dp.dbg_flags &&
+	                         m.dev.d_pr[0] == pv.d_pr[0] && m.dev.d_pr[1] == pv.d_pr[1] && !m.opt.side_by_side;
+	for (uint32_t k = 0; same_ground && k < pv.launched && k + 1 < m.tp.schedule.size(); ++k) {
+		const SuperStep& ss = m.tp.schedule[k];
 		if (ss.entry_count != 1 || !ss.singles.empty() || ss.ck_load >= 0 || ss.ck_save >= 0 || ss.bt_window >= 0) break;
-		const SlotBatchEntry& e = m.slot_entries[ss.entry_off];
+		const SlotBatchEntry& e = m.tp.slot_entries[ss.entry_off];
 		if (std::memcmp(&e.run, &pv.runs[k], sizeof(SlotRun)) != 0 || e.prev != pv.d_pr[k & 1u] || e.cur != pv.d_pr[(k & 1u) ^ 1u] || e.score_out) break;
 		++pv.agreed;
 	}
@@ -1959,10 +1093,10 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg, boo
 	b.n = p.n_cols;
 	b.tbits = 2 * p.n_triples;
 	b.ni = std::max<uint32_t>(p.n_ind, 1);
-	m.dp.n_cols = b.n;
-	m.dp.T = p.T;
-	m.dp.tbits = b.tbits;
-	m.dp.n_ind = p.n_ind;
+	m.dev.dp.n_cols = b.n;
+	m.dev.dp.T = p.T;
+	m.dev.dp.tbits = b.tbits;
+	m.dev.dp.n_ind = p.n_ind;
 	// ---- everything this function sends or launches goes through one of the device's upload streams (upload_stream_of); begin_solve orders the solve behind
 	// ev_upload.  WHAMD_UPLOAD_ON_TABLE_STREAM=1 (debug library): the table's own stream, as before.  (Chosen in front of the plan: a preview may start inside it.)
 	m.upload_stream = debug_env("WHAMD_UPLOAD_ON_TABLE_STREAM") ? nullptr : upload_stream_of(device);
@@ -1970,29 +1104,29 @@ whamd_status_t DeviceTable::upload(Problem& p, int device, std::string& msg, boo
 	if (m.upload_stream == m.stream) m.own_stream_used = true;
 	// ---- host: path and plan, column descriptors, the layout of the backtrace arena
 	if ((st = m.choose_plan(p, b, from_create, msg)) != WHAMD_OK) return st;
-	b.ped_slots = m.use_slots && m.splan.ped;
+	b.ped_slots = m.tp.use_slots && m.tp.splan.ped;
 	b.laps.next_stage();
 	if (debug_env("WHAMD_DEBUG_PLAN")) m.dump_plan(p);
 	// ---- a lone table: its first runs start on the device -- from inside the planner (choose_plan's head hook), or here --, and the rest of the create happens under them
 	if (!m.preview.tried && (st = m.start_preview(p, b, from_create, msg)) != WHAMD_OK) return st;
-	if ((st = m.describe_columns(p, b, msg)) != WHAMD_OK) return st;
-	if ((st = m.lay_out_arena(p, b, msg)) != WHAMD_OK) return st;
-	TableUploader up(device, m.upload_stream, m.allocations);
+	if ((st = describe_columns(p, b, m.tp, msg)) != WHAMD_OK) return st;
+	if ((st = lay_out_arena(p, m.opt, b, m.tp, msg)) != WHAMD_OK) return st;
+	TableUploader up(device, m.upload_stream, m.dev.allocations);
 	b.laps.lap("staging area taken");
-	up.open_block(m.upload_bound(p, b));
+	up.open_block(upload_bound(p, b, m.tp));
 	b.laps.lap("staging image sized, device block taken");
 	// ---- the device block fills in this order; the image leaves in pieces of 32 MB
 	if ((st = m.upload_column_arrays(p, b, up, msg)) != WHAMD_OK) return st;
 	if ((st = m.upload_slot_arrays(b, up, msg)) != WHAMD_OK) return st;
-	m.make_jobs();
-	m.make_units(b);
+	make_jobs(m.opt, m.tp);
+	make_units(b, m.tp);
 	if ((st = m.make_windows(b, up, msg)) != WHAMD_OK) return st;
 	if ((st = m.take_result_block(b.n, up, msg)) != WHAMD_OK) return st;
 	if ((st = m.make_chunks(p, up, msg)) != WHAMD_OK) return st;
 	if ((st = m.take_solve_buffers(p, b, up, msg)) != WHAMD_OK) return st;
 	if ((st = m.make_lanes(b, up, msg)) != WHAMD_OK) return st;
-	if ((st = m.make_schedule(b, msg)) != WHAMD_OK) return st;
-	m.make_briefs();
+	if ((st = make_schedule(b, m.dev.dp, m.dev.d_job_scores, m.tp, msg)) != WHAMD_OK) return st;
+	make_briefs(m.tp);
 	if ((st = m.upload_entries(up, msg)) != WHAMD_OK) return st;
 	// ---- the image's tail and the table kernels go out; what follows only completes what the solve's launches read
 	if ((st = m.launch_table_kernels(p, b, up, msg)) != WHAMD_OK) return st;
@@ -2123,12 +1257,12 @@ void DeviceTable::Impl::launch_column_step(const Problem& p, const Step& step, c
                                            uint64_t& launches) {
 	Impl& m = *this;
 	const hipStream_t rs = m.inflight.run_stream;
-	DevProblem dp = m.dp;
+	DevProblem dp = m.dev.dp;
 	dp.keys = lane.d_keys;
 	const uint32_t c = step.index;
-	const DevColumn& d = m.cols[c];
+	const DevColumn& d = m.tp.cols[c];
 #ifdef WHAMD_DEBUG_BUILD
-	const auto column_facts = [&m](const Problem& pr, const DevColumn& col) { LaunchFacts f; f.T = (int32_t)pr.T; f.n_ind = (int32_t)m.dp.n_ind; f.mode = (int32_t)col.mode; f.wide = m.wide; return f; };
+	const auto column_facts = [&m](const Problem& pr, const DevColumn& col) { LaunchFacts f; f.T = (int32_t)pr.T; f.n_ind = (int32_t)m.dev.dp.n_ind; f.mode = (int32_t)col.mode; f.wide = m.tp.wide; return f; };
 #endif
 	if (d.mode == 0) {
 		const uint32_t threads = 1u << d.f;
@@ -2137,11 +1271,11 @@ void DeviceTable::Impl::launch_column_step(const Problem& p, const Step& step, c
 		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, (const void*)m.fused, dim3(threads / block), dim3(block), 0, rs, true, column_facts(p, d));
 		launches += 1;
 	} else {
-		const uint64_t total = (1ull << (d.f + d.ebits - d.eloop)) * (m.wide ? p.T : 1u);
+		const uint64_t total = (1ull << (d.f + d.ebits - d.eloop)) * (m.tp.wide ? p.T : 1u);
 		const uint32_t block = (uint32_t)std::min<uint64_t>(256, (total + 63) / 64 * 64);
-		if (m.wide) hipLaunchKernelGGL(column_step_wide, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
+		if (m.tp.wide) hipLaunchKernelGGL(column_step_wide, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
 		else hipLaunchKernelGGL(m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, dp, c, prev, (uint32_t)total);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, m.wide ? (const void*)column_step_wide : (const void*)m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, true, column_facts(p, d));
+		WHAMD_NOTE(m, WHAMD_LAUNCH_COLUMN, m.tp.wide ? (const void*)column_step_wide : (const void*)m.keysfn, dim3((uint32_t)((total + block - 1) / block)), dim3(block), 0, rs, true, column_facts(p, d));
 		const uint32_t entries = (1u << d.f) * p.T;
 		const uint32_t fblock = std::min<uint32_t>(256, (entries + 63) / 64 * 64);
 		hipLaunchKernelGGL(column_finalize, dim3((entries + fblock - 1) / fblock), dim3(fblock), 0, rs, dp, c, cur, entries);
@@ -2155,7 +1289,7 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 	Impl& m = *this;
 	const ResSegment& sg = e.sg;
 	const hipStream_t rs = m.inflight.run_stream;
-	const bool stamps = DEBUG_BUILD && m.dp.dbg != nullptr;
+	const bool stamps = DEBUG_BUILD && m.dev.dp.dbg != nullptr;
 #ifdef WHAMD_DEBUG_BUILD
 	const auto segment_facts = [&sg, stamps](bool spec, bool sym) {
 		LaunchFacts f;
@@ -2167,13 +1301,13 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 	if (sg.kind == 1) {
 		const size_t words = ((size_t)sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)sg.n_terms * 2 + 3) & ~(size_t)3;
 		const size_t lds_ped = words * 4 + 2 * ((size_t)16 << sg.max_l) + (size_t)sg.stage_words * 8;
-		const PedSegmentFn kernel = ped_segment_kernel(stamps, sg.in_mirror_bit && m.use_chunks);
-		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, m.dp, sg, e.prev, e.cur);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, true, segment_facts(sg.in_mirror_bit && m.use_chunks, false));
+		const PedSegmentFn kernel = ped_segment_kernel(stamps, sg.in_mirror_bit && m.tp.use_chunks);
+		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, m.dev.dp, sg, e.prev, e.cur);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, true, segment_facts(sg.in_mirror_bit && m.tp.use_chunks, false));
 	} else {
 		const size_t lds = (size_t)sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << sg.max_l) + (size_t)sg.stage_words * 8;
 		const SegmentFn kernel = segment_kernel(stamps, sg.half || sg.in_half || sg.mirror_out);
-		hipLaunchKernelGGL(kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, m.dp, sg, e.prev, e.cur, e.score_out);
+		hipLaunchKernelGGL(kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, m.dev.dp, sg, e.prev, e.cur, e.score_out);
 		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, true, segment_facts(false, sg.half || sg.in_half || sg.mirror_out));
 	}
 	launches += 1;
@@ -2184,15 +1318,15 @@ void DeviceTable::Impl::launch_slot_run(const DevProblem& dp, const SlotBatchEnt
 	Impl& m = *this;
 	const SlotRun& run = e.run;
 	const hipStream_t rs = m.inflight.run_stream;
-	const bool spec = run.spec_id != 0 && m.use_chunks && !debug_env("WHAMD_NO_SPEC_KERNEL");
+	const bool spec = run.spec_id != 0 && m.tp.use_chunks && !debug_env("WHAMD_NO_SPEC_KERNEL");
 	const bool stamps = DEBUG_BUILD && (dp.dbg != nullptr || dp.dbg_flags != 0);
 	launches += 1;
-	if (m.splan.ped) {
-		const PedSlotExtra& ex = m.splan.pextra[e.pad];
+	if (m.tp.splan.ped) {
+		const PedSlotExtra& ex = m.tp.splan.pextra[e.pad];
 		size_t lds = pedslot_lds_bytes(run.threads, run.ncols, ex);
 		PedSlotRunFn kernel = pedslot_run_kernel(ex.tb, ex.nf, spec, (run.yflags & 16u) != 0);
 #ifdef WHAMD_DEBUG_BUILD
-		if ((run.yflags & 8u) && !m.side_by_side) {   // X run (WHAMD_PED_XRUN=1)
+		if ((run.yflags & 8u) && !m.opt.side_by_side) {   // X run (WHAMD_PED_XRUN=1)
 			const uint32_t xc = run.ncols <= 16u ? 16u : 32u;
 			lds = pedslotx_lds_bytes(run.threads, xc);
 			kernel = pedslot_runx_kernel(ex.tb, ex.nf, xc, spec);
@@ -2210,10 +1344,10 @@ void DeviceTable::Impl::launch_slot_run(const DevProblem& dp, const SlotBatchEnt
 	if ((run.yflags & 8u) && run.lr == 2u) {   // X run with four cells per thread: registers instead of LDS lines (LDS: the wave-slot exchange buffers + the threads' own operand lines)
 		// (no LDS lines: room for other tables' workgroups on the CU -- or, from 1 024 workgroups on, for FOUR of this table's own instead of two:
 		// a launch of 2 048 workgroups -- coverage 23 -- takes 36.2 instead of 56.2 us, scripts/gpu_wide_ab.py)
-		const bool streamed = m.side_by_side || debug_env("WHAMD_XSTREAM") || (grid.x >= 1024u && !debug_env("WHAMD_NO_WIDE_LAYOUT"));
+		const bool streamed = m.opt.side_by_side || debug_env("WHAMD_XSTREAM") || (grid.x >= 1024u && !debug_env("WHAMD_NO_WIDE_LAYOUT"));
 		const size_t lds_x = streamed ? (size_t)2 * run.threads * 16 : slotx_lds_bytes(run.threads, (run.ncols + 7u) & ~7u);
 		// narrow tables: the run's workgroups packed onto one XCD (slot_runx: eight times the grid, every eighth workgroup works)
-		const uint32_t pack = (grid.x <= 32u && !m.side_by_side && !debug_env("WHAMD_NO_XCD_PACK")) ? 1u : 0u;
+		const uint32_t pack = (grid.x <= 32u && !m.opt.side_by_side && !debug_env("WHAMD_NO_XCD_PACK")) ? 1u : 0u;
 		// the prologue forms the operands of XC columns (an irregular layout's runs are ~10 columns long); with stamps there are the two long forms only
 		const uint32_t xc = streamed ? 0u : (run.ncols <= 8u && !stamps) ? 8u : (run.ncols <= 16u && !stamps) ? 16u : run.ncols <= 24u ? 24u : 32u;
 		const SlotRunXFn kernel = slot_runx_kernel(xc, stamps, spec);
@@ -2260,8 +1394,8 @@ void DeviceTable::abort_enqueue() {
 whamd_status_t DeviceTable::Impl::arm_keys(std::string& msg) {
 	Impl& m = *this;
 	const hipStream_t rs = m.inflight.run_stream;
-	for (const Impl::Lane& lane : m.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.key_entries * 8, rs));
-	HIP_TRY(hipMemsetAsync(m.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, rs));
+	for (const Lane& lane : m.tp.lanes) HIP_TRY(hipMemsetAsync(lane.d_keys, 0xFF, m.dev.key_entries * 8, rs));
+	HIP_TRY(hipMemsetAsync(m.dev.dp.last_keys, 0xFF, (size_t)MAX_T_WIDE * 8, rs));
 	return WHAMD_OK;
 }
 
@@ -2295,17 +1429,17 @@ whamd_status_t DeviceTable::Impl::begin_solve(const Problem& p, Solution& s, std
 		m.inflight.timing_pending = false;
 		return WHAMD_OK;
 	}
-	if (m.use_chunks) HIP_TRY(hipMemsetAsync(m.dp.spec_keys, 0xFF, ((size_t)m.n_spec + 1) * m.dp.spec_stride * 8, rs));
-	if (m.windowed) HIP_TRY(hipMemsetAsync(m.d_path_trans, 0, (size_t)n * 4, rs));
+	if (m.tp.use_chunks) HIP_TRY(hipMemsetAsync(m.dev.dp.spec_keys, 0xFF, ((size_t)m.tp.n_spec + 1) * m.dev.dp.spec_stride * 8, rs));
+	if (m.tp.windowed) HIP_TRY(hipMemsetAsync(m.dev.d_path_trans, 0, (size_t)n * 4, rs));
 	m.inflight.timing_pending = false;   // (the events are this solve's from here on)
 	HIP_TRY(hipEventRecord(m.ev0, rs));
-	if (!m.plan.ped_columns.empty()) {
-		const uint32_t entries = (uint32_t)m.plan.ped_columns.size() * PED_TABLE;
-		hipLaunchKernelGGL(ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.ped_cols, (uint32_t)m.plan.ped_columns.size(), m.dp.ped_tables);
+	if (!m.tp.plan.ped_columns.empty()) {
+		const uint32_t entries = (uint32_t)m.tp.plan.ped_columns.size() * PED_TABLE;
+		hipLaunchKernelGGL(ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dev.dp.ped_cols, (uint32_t)m.tp.plan.ped_columns.size(), m.dev.dp.ped_tables);
 		WHAMD_NOTE(m, WHAMD_LAUNCH_TABLES, (const void*)ped_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, false, LaunchFacts());
-	} else if (!m.use_slots && !m.plan.columns.empty()) {
-		const uint32_t entries = (uint32_t)m.plan.columns.size() * RES_TABLE;
-		hipLaunchKernelGGL(resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dp.res_cols, (uint32_t)m.plan.columns.size(), m.dp.res_tables);
+	} else if (!m.tp.use_slots && !m.tp.plan.columns.empty()) {
+		const uint32_t entries = (uint32_t)m.tp.plan.columns.size() * RES_TABLE;
+		hipLaunchKernelGGL(resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, m.dev.dp.res_cols, (uint32_t)m.tp.plan.columns.size(), m.dev.dp.res_tables);
 		WHAMD_NOTE(m, WHAMD_LAUNCH_TABLES, (const void*)resident_tables, dim3((entries + 255) / 256), dim3(256), 0, rs, false, LaunchFacts());
 	}
 	return WHAMD_OK;
@@ -2317,29 +1451,29 @@ whamd_status_t DeviceTable::Impl::submit_super_step(const Problem& p, const Supe
 	Impl& m = *this;
 	const hipStream_t rs = m.inflight.run_stream;
 	const dim3 grid(ss.grid_x, ss.entry_count), block(ss.threads);
-	if (ss.ck_load >= 0) HIP_TRY(hipMemcpyAsync(ss.io[0], m.d_checkpoints + (size_t)ss.ck_load * m.checkpoint_bytes, m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
+	if (ss.ck_load >= 0) HIP_TRY(hipMemcpyAsync(ss.io[0], m.dev.d_checkpoints + (size_t)ss.ck_load * m.tp.checkpoint_bytes, m.tp.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
 	if (ss.entry_count == 1) {
-		if (m.use_slots) m.launch_slot_run(m.dp, m.slot_entries[ss.entry_off], launches);
-		else m.launch_run(m.entries[ss.entry_off], launches);
+		if (m.tp.use_slots) m.launch_slot_run(m.dev.dp, m.tp.slot_entries[ss.entry_off], launches);
+		else m.launch_run(m.tp.entries[ss.entry_off], launches);
 	} else if (ss.entry_count > 1) {
-		if (m.use_slots) { const SlotBatchFn kernel = slot_batch_kernel(m.slot_lr_used); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_slot_entries + ss.entry_off); }
-		else { const ResBatchFn kernel = resident_batch_kernel(ss.sym); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dp, m.d_entries + ss.entry_off); }
+		if (m.tp.use_slots) { const SlotBatchFn kernel = slot_batch_kernel(m.tp.slot_lr_used); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dev.dp, m.dev.d_slot_entries + ss.entry_off); }
+		else { const ResBatchFn kernel = resident_batch_kernel(ss.sym); hipLaunchKernelGGL(kernel, grid, block, ss.lds, rs, m.dev.dp, m.dev.d_entries + ss.entry_off); }
 #ifdef WHAMD_DEBUG_BUILD
 		LaunchFacts facts;
 		facts.entries = (int32_t)ss.entry_count;
-		if (m.use_slots) facts.lr = m.slot_lr_used; else facts.sym = ss.sym;
-		WHAMD_NOTE(m, WHAMD_LAUNCH_BATCH, m.use_slots ? (const void*)slot_batch_kernel(m.slot_lr_used) : (const void*)resident_batch_kernel(ss.sym), grid, block, ss.lds, rs, true, facts);
+		if (m.tp.use_slots) facts.lr = m.tp.slot_lr_used; else facts.sym = ss.sym;
+		WHAMD_NOTE(m, WHAMD_LAUNCH_BATCH, m.tp.use_slots ? (const void*)slot_batch_kernel(m.tp.slot_lr_used) : (const void*)resident_batch_kernel(ss.sym), grid, block, ss.lds, rs, true, facts);
 #endif
 		launches += 1;
 	}
 	const whamd_status_t st = m.submit_singles(p, ss, launches, msg);
 	if (st != WHAMD_OK) return st;
-	if (ss.ck_save >= 0) HIP_TRY(hipMemcpyAsync(m.d_checkpoints + (size_t)ss.ck_save * m.checkpoint_bytes, ss.io[1], m.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
+	if (ss.ck_save >= 0) HIP_TRY(hipMemcpyAsync(m.dev.d_checkpoints + (size_t)ss.ck_save * m.tp.checkpoint_bytes, ss.io[1], m.tp.checkpoint_bytes, hipMemcpyDeviceToDevice, rs));
 	if (ss.bt_window >= 0)
 	{
-		hipLaunchKernelGGL(backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, rs, m.dp, m.d_units, m.d_window_jobs + ss.bt_window,
-		                   m.d_path_index, m.d_path_trans, m.d_score);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_WINDOW_WALK, (const void*)backtrace_kernel, dim3(1), dim3(1024), m.bt_lds, rs, false, LaunchFacts());
+		hipLaunchKernelGGL(backtrace_kernel, dim3(1), dim3(1024), m.tp.bt_lds, rs, m.dev.dp, m.dev.d_units, m.dev.d_window_jobs + ss.bt_window,
+		                   m.dev.d_path_index, m.dev.d_path_trans, m.dev.d_score);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_WINDOW_WALK, (const void*)backtrace_kernel, dim3(1), dim3(1024), m.tp.bt_lds, rs, false, LaunchFacts());
 	}
 	return WHAMD_OK;
 }
@@ -2348,12 +1482,12 @@ whamd_status_t DeviceTable::Impl::submit_super_step(const Problem& p, const Supe
 whamd_status_t DeviceTable::Impl::submit_singles(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg) {
 	Impl& m = *this;
 	const hipStream_t rs = m.inflight.run_stream;
-	for (const Impl::Single& sg : ss.singles) {
-		const Impl::Lane& lane = m.lanes[sg.lane];
+	for (const Single& sg : ss.singles) {
+		const Lane& lane = m.tp.lanes[sg.lane];
 		if (sg.zero_prev) HIP_TRY(hipMemsetAsync(lane.d_pr[sg.flip], 0, 4 * (size_t)p.T, rs));
-		m.launch_column_step(p, m.plan.steps[sg.step], lane, lane.d_pr[sg.flip], lane.d_pr[sg.flip ^ 1], launches);
+		m.launch_column_step(p, m.tp.plan.steps[sg.step], lane, lane.d_pr[sg.flip], lane.d_pr[sg.flip ^ 1], launches);
 		if (sg.score_job >= 0)
-			HIP_TRY(hipMemcpyAsync(m.d_job_scores + sg.score_job, lane.d_pr[sg.flip ^ 1], 4, hipMemcpyDeviceToDevice, rs));
+			HIP_TRY(hipMemcpyAsync(m.dev.d_job_scores + sg.score_job, lane.d_pr[sg.flip ^ 1], 4, hipMemcpyDeviceToDevice, rs));
 	}
 	return WHAMD_OK;
 }
@@ -2371,30 +1505,30 @@ whamd_status_t DeviceTable::Impl::submit_tail(const Problem& p, std::string& msg
 	HIP_TRY(hipGetLastError());
 	if (!walked_by_group) HIP_TRY(hipEventRecord(m.ev1, ts));
 	if (walked_by_group) {
-	} else if (m.use_chunks) {
-		hipLaunchKernelGGL(backtrace_chunks, dim3(m.n_orient_max * (uint32_t)m.chunks.size()), dim3(256), m.chunk_lds, ts, m.dp, m.d_units, m.d_chunks,
-		                   (uint32_t)m.chunks.size(), (uint32_t)m.units.size(), 0u, m.n_orient_max, m.d_path2, m.d_trans2, m.d_score, m.d_unit_x, m.d_guess, m.d_sel, m.d_bt_counters);
-		hipLaunchKernelGGL(backtrace_chunks, dim3(1), dim3(256), m.chunk_lds, ts, m.dp, m.d_units, m.d_chunks,
-		                   (uint32_t)m.chunks.size(), (uint32_t)m.units.size(), 1u, m.n_orient_max, m.d_path2, m.d_trans2, m.d_score, m.d_unit_x, m.d_guess, m.d_sel, m.d_bt_counters);
-		hipLaunchKernelGGL(backtrace_gather, dim3((uint32_t)m.units.size()), dim3(64), 0, ts, m.d_units, (uint32_t)m.units.size(), n, m.d_path2, m.d_trans2, m.d_sel,
-		                   m.d_path_index, m.d_path_trans);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(m.n_orient_max * (uint32_t)m.chunks.size()), dim3(256), m.chunk_lds, ts, false, LaunchFacts());
-		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(1), dim3(256), m.chunk_lds, ts, false, LaunchFacts());
-		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_gather, dim3((uint32_t)m.units.size()), dim3(64), 0, ts, false, LaunchFacts());
-	} else if (!m.windowed) {   // (windowed: every window was walked right after its steps)
-		hipLaunchKernelGGL(backtrace_kernel, dim3((uint32_t)m.jobs.size()), dim3(1024), m.bt_lds, ts, m.dp, m.d_units, m.d_btjobs,
-		                   m.d_path_index, m.d_path_trans, m.d_score);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_kernel, dim3((uint32_t)m.jobs.size()), dim3(1024), m.bt_lds, ts, false, LaunchFacts());
+	} else if (m.tp.use_chunks) {
+		hipLaunchKernelGGL(backtrace_chunks, dim3(m.tp.n_orient_max * (uint32_t)m.tp.chunks.size()), dim3(256), m.tp.chunk_lds, ts, m.dev.dp, m.dev.d_units, m.dev.d_chunks,
+		                   (uint32_t)m.tp.chunks.size(), (uint32_t)m.tp.units.size(), 0u, m.tp.n_orient_max, m.dev.d_path2, m.dev.d_trans2, m.dev.d_score, m.dev.d_unit_x, m.dev.d_guess, m.dev.d_sel, m.dev.d_bt_counters);
+		hipLaunchKernelGGL(backtrace_chunks, dim3(1), dim3(256), m.tp.chunk_lds, ts, m.dev.dp, m.dev.d_units, m.dev.d_chunks,
+		                   (uint32_t)m.tp.chunks.size(), (uint32_t)m.tp.units.size(), 1u, m.tp.n_orient_max, m.dev.d_path2, m.dev.d_trans2, m.dev.d_score, m.dev.d_unit_x, m.dev.d_guess, m.dev.d_sel, m.dev.d_bt_counters);
+		hipLaunchKernelGGL(backtrace_gather, dim3((uint32_t)m.tp.units.size()), dim3(64), 0, ts, m.dev.d_units, (uint32_t)m.tp.units.size(), n, m.dev.d_path2, m.dev.d_trans2, m.dev.d_sel,
+		                   m.dev.d_path_index, m.dev.d_path_trans);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(m.tp.n_orient_max * (uint32_t)m.tp.chunks.size()), dim3(256), m.tp.chunk_lds, ts, false, LaunchFacts());
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_chunks, dim3(1), dim3(256), m.tp.chunk_lds, ts, false, LaunchFacts());
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_gather, dim3((uint32_t)m.tp.units.size()), dim3(64), 0, ts, false, LaunchFacts());
+	} else if (!m.tp.windowed) {   // (windowed: every window was walked right after its steps)
+		hipLaunchKernelGGL(backtrace_kernel, dim3((uint32_t)m.tp.jobs.size()), dim3(1024), m.tp.bt_lds, ts, m.dev.dp, m.dev.d_units, m.dev.d_btjobs,
+		                   m.dev.d_path_index, m.dev.d_path_trans, m.dev.d_score);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)backtrace_kernel, dim3((uint32_t)m.tp.jobs.size()), dim3(1024), m.tp.bt_lds, ts, false, LaunchFacts());
 	}
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(m.ev2, ts));
-	if (m.device_superreads && !walked_by_group) {
-		hipLaunchKernelGGL(superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, m.super_args);
+	if (m.tp.device_superreads && !walked_by_group) {
+		hipLaunchKernelGGL(superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, m.dev.super_args);
 		WHAMD_NOTE(m, WHAMD_LAUNCH_TAIL, (const void*)superreads_single, dim3((n + 255u) / 256u), dim3(256), 0, ts, false, LaunchFacts());
 		HIP_TRY(hipGetLastError());
 	}
 	// ONE download per table (the device block has the pinned buffer's layout, upload()); pinned: a copy into pageable memory would block this call until the stream drains
-	HIP_TRY(hipMemcpyAsync(m.h_pinned, m.d_path_index, (m.super_off + (m.device_superreads ? m.super_words : 0)) * sizeof(uint32_t), hipMemcpyDeviceToHost, ts));
+	HIP_TRY(hipMemcpyAsync(m.dev.h_pinned, m.dev.d_path_index, (m.tp.super_off + (m.tp.device_superreads ? m.tp.super_words : 0)) * sizeof(uint32_t), hipMemcpyDeviceToHost, ts));
 	HIP_TRY(hipEventRecord(m.ev3, ts));
 	return WHAMD_OK;
 }
@@ -2409,7 +1543,7 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 		m.inflight.run_stream = m.stream;
 		m.inflight.group_tables = 1;
 		// behind the preview: the table alone on its own stream, every launched step agreed with the finished schedule, and its launches chosen as this solve's are
-		const bool behind_preview = n && m.preview.pending && m.preview.agreed > 0 && m.preview.agreed == m.preview.launched && !m.side_by_side;
+		const bool behind_preview = n && m.preview.pending && m.preview.agreed > 0 && m.preview.agreed == m.preview.launched && !m.opt.side_by_side;
 		const whamd_status_t st = m.begin_solve(p, s, msg, behind_preview);
 		if (st != WHAMD_OK) return st;
 		if (n == 0) {  // src/pedigreedptable.cpp:88-92
@@ -2420,12 +1554,12 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 		}
 	}
 	uint64_t launches = 0;
-	while (m.inflight.next_super < m.schedule.size() && launches < budget) {
-		const whamd_status_t st = m.submit_super_step(p, m.schedule[m.inflight.next_super++], launches, msg);
+	while (m.inflight.next_super < m.tp.schedule.size() && launches < budget) {
+		const whamd_status_t st = m.submit_super_step(p, m.tp.schedule[m.inflight.next_super++], launches, msg);
 		if (st != WHAMD_OK) return st;
 	}
 	m.inflight.launches += launches;
-	if (m.inflight.next_super < m.schedule.size()) return WHAMD_OK;
+	if (m.inflight.next_super < m.tp.schedule.size()) return WHAMD_OK;
 	const whamd_status_t st = m.submit_tail(p, msg);
 	if (st != WHAMD_OK) return st;
 	m.inflight.enqueue_open = false;
@@ -2441,13 +1575,13 @@ whamd_status_t DeviceTable::enqueue_some_unguarded(const Problem& p, Solution& s
 // those overlap across the members -- so whamd_dptable_wait works per table as before.
 bool DeviceTable::group_eligible(const Problem& p) const {
 	const Impl& m = *impl_;
-	if (p.n_cols == 0 || !m.use_slots || m.windowed || m.inflight.enqueue_open || m.dp.dbg || (m.dp.dbg_flags && m.splan.ped)) return false;
-	if (!m.splan.ped && m.slot_lr_used != 2 && m.slot_lr_used != 3) return false;   // (group kernels: four or eight cells per thread)
+	if (p.n_cols == 0 || !m.tp.use_slots || m.tp.windowed || m.inflight.enqueue_open || m.dev.dp.dbg || (m.dev.dp.dbg_flags && m.tp.splan.ped)) return false;
+	if (!m.tp.splan.ped && m.tp.slot_lr_used != 2 && m.tp.slot_lr_used != 3) return false;   // (group kernels: four or eight cells per thread)
 	return debug_env("WHAMD_NO_GROUP") == nullptr;
 }
 
 int DeviceTable::device_index() const { return impl_->device; }
-uint32_t DeviceTable::widest_launch() const { return impl_->max_grid_x; }
+uint32_t DeviceTable::widest_launch() const { return impl_->tp.max_grid_x; }
 
 // One group solve in the making: what the steps of enqueue_group share.  A launch takes SLOT_GROUP_MAX runs (BT_GROUP_MAX tables for the
 // walk): a larger group flushes a variant's batch in the middle of a super-step and cuts the batched backtrace, and every member counts the launches it has a run in.
@@ -2491,7 +1625,7 @@ struct DeviceTable::Impl::GroupSubmission {
 	// Every member's solve opens on the lead's stream.
 	whamd_status_t open_members() {
 		uint64_t width = 0;
-		for (size_t i = 0; i < n; ++i) width += member(i).max_grid_x;
+		for (size_t i = 0; i < n; ++i) width += member(i).tp.max_grid_x;
 		tight = width > 768 && !debug_env("WHAMD_GROUP_LOOSE");
 		for (size_t i = 0; i < n; ++i) {
 			Impl& m = member(i);
@@ -2500,7 +1634,7 @@ struct DeviceTable::Impl::GroupSubmission {
 			m.inflight.group_tables = (uint32_t)n;
 			const whamd_status_t st = m.begin_solve(*problems[i], *solutions[i], msg);
 			if (st != WHAMD_OK) return abort(st);
-			max_steps = std::max(max_steps, m.schedule.size());
+			max_steps = std::max(max_steps, m.tp.schedule.size());
 		}
 		return WHAMD_OK;
 	}
@@ -2510,21 +1644,21 @@ struct DeviceTable::Impl::GroupSubmission {
 		std::fill(counted.begin(), counted.end(), 0);
 		for (size_t i = 0; i < n; ++i) {
 			Impl& m = member(i);
-			if (k >= m.step_brief.size()) continue;
-			const Impl::StepBrief& sb = m.step_brief[k];   // (a few bytes per table and super-step: Impl::StepBrief)
+			if (k >= m.tp.step_brief.size()) continue;
+			const StepBrief& sb = m.tp.step_brief[k];   // (a few bytes per table and super-step: StepBrief)
 #ifdef WHAMD_DEBUG_BUILD
 			if (touch_fat) {   // (A/B of the round-5 change: read what the loop used to read -- the super-step and its 320-byte entries)
-				const Impl::SuperStep& ss = m.schedule[k];
-				for (uint32_t q = 0; q < ss.entry_count; ++q) { const SlotBatchEntry& he = m.slot_entries[ss.entry_off + q]; fat_sink += he.run.yflags + he.run.g + he.run.threads + he.ex.nf + (uint32_t)ss.lds; }
+				const SuperStep& ss = m.tp.schedule[k];
+				for (uint32_t q = 0; q < ss.entry_count; ++q) { const SlotBatchEntry& he = m.tp.slot_entries[ss.entry_off + q]; fat_sink += he.run.yflags + he.run.g + he.run.threads + he.ex.nf + (uint32_t)ss.lds; }
 			}
 #endif
 			for (uint32_t q = 0; q < sb.entry_count; ++q) {
-				const Impl::EntryBrief& eb = m.entry_brief[sb.entry_off + q];
-				const bool xrun = eb.variant.x != eb.variant.plain && !m.dp.dbg_flags;   // (the X kernel: operands streamed from the tables, 16 KB of LDS)
+				const EntryBrief& eb = m.tp.entry_brief[sb.entry_off + q];
+				const bool xrun = eb.variant.x != eb.variant.plain && !m.dev.dp.dbg_flags;   // (the X kernel: operands streamed from the tables, 16 KB of LDS)
 				const GroupVariant v = xrun ? eb.variant.x : eb.variant.plain;
 				Batch& b = batches[v];
 				if (b.args.n == (uint32_t)SLOT_GROUP_MAX) flush(v);
-				b.args.entry[b.args.n++] = m.d_slot_entries + sb.entry_off + q;
+				b.args.entry[b.args.n++] = m.dev.d_slot_entries + sb.entry_off + q;
 				b.grid_x = std::max<uint32_t>(b.grid_x, eb.grid_x);
 				b.threads = std::max<uint32_t>(b.threads, eb.threads);
 				b.lds = std::max<size_t>(b.lds, xrun ? eb.lds_x : sb.lds);
@@ -2542,7 +1676,7 @@ struct DeviceTable::Impl::GroupSubmission {
 		const bool by_table = (b.args.n % 8u == 0u || b.args.n >= 40u) && !debug_env("WHAMD_GROUP_BY_WORKGROUP");
 		b.args.pad = by_table ? 1u : 0u;
 		const dim3 grid = by_table ? dim3((b.args.n + 7u) & ~7u, b.grid_x) : dim3(b.grid_x, b.args.n), block(b.threads);
-		const GroupFn kernel = group_kernel(v, DEBUG_BUILD && lead.dp.dbg_flags != 0, tight);
+		const GroupFn kernel = group_kernel(v, DEBUG_BUILD && lead.dev.dp.dbg_flags != 0, tight);
 		hipLaunchKernelGGL(kernel, grid, block, b.lds, lead.stream, b.args);
 #ifdef WHAMD_DEBUG_BUILD
 		const uint32_t members = b.args.n;
@@ -2553,7 +1687,7 @@ struct DeviceTable::Impl::GroupSubmission {
 		b.lds = 0;
 #ifdef WHAMD_DEBUG_BUILD
 		LaunchFacts facts;
-		facts.variant = (int32_t)v; facts.tight = tight; facts.stamps = lead.dp.dbg_flags != 0; facts.entries = (int32_t)members;
+		facts.variant = (int32_t)v; facts.tight = tight; facts.stamps = lead.dev.dp.dbg_flags != 0; facts.entries = (int32_t)members;
 #endif
 		for (size_t j = 0; j < n; ++j)
 			if (counted[j * GROUP_VARIANTS + v]) {
@@ -2567,8 +1701,8 @@ struct DeviceTable::Impl::GroupSubmission {
 	whamd_status_t submit_singles(size_t k) {
 		for (size_t i = 0; i < n; ++i) {
 			Impl& m = member(i);
-			if (k >= m.step_brief.size() || !m.step_brief[k].has_singles) continue;
-			const whamd_status_t st = m.submit_singles(*problems[i], m.schedule[k], table_launches[i], msg);
+			if (k >= m.tp.step_brief.size() || !m.tp.step_brief[k].has_singles) continue;
+			const whamd_status_t st = m.submit_singles(*problems[i], m.tp.schedule[k], table_launches[i], msg);
 			if (st != WHAMD_OK) return abort(st);
 		}
 		return WHAMD_OK;
@@ -2587,7 +1721,7 @@ struct DeviceTable::Impl::GroupSubmission {
 		std::vector<size_t> batch;
 		for (size_t i = 0; i < n; ++i) {
 			const Impl& m = member(i);
-			if (!m.use_chunks || m.windowed || !m.d_bt_entry) continue;
+			if (!m.tp.use_chunks || m.tp.windowed || !m.dev.d_bt_entry) continue;
 			batch.push_back(i);
 			if (batch.size() == (size_t)BT_GROUP_MAX && !walk_batch(batch)) return fail("group backtrace launch failed");
 		}
@@ -2603,17 +1737,17 @@ struct DeviceTable::Impl::GroupSubmission {
 		size_t lds = 0;
 		for (size_t i : batch) {
 			Impl& m = member(i);
-			args.entry[args.n++] = m.d_bt_entry;
-			gx = std::max(gx, m.n_orient_max * (uint32_t)m.chunks.size());
-			gu = std::max(gu, (uint32_t)m.units.size());
-			lds = std::max(lds, m.chunk_lds);
+			args.entry[args.n++] = m.dev.d_bt_entry;
+			gx = std::max(gx, m.tp.n_orient_max * (uint32_t)m.tp.chunks.size());
+			gu = std::max(gu, (uint32_t)m.tp.units.size());
+			lds = std::max(lds, m.tp.chunk_lds);
 			if (hipEventRecord(m.ev1, lead.stream) != hipSuccess) return false;
 		}
 		hipLaunchKernelGGL(backtrace_chunks_group, dim3(gx, args.n), dim3(256), lds, lead.stream, args, 0u);
 		hipLaunchKernelGGL(backtrace_chunks_group, dim3(1, args.n), dim3(256), lds, lead.stream, args, 1u);
 		hipLaunchKernelGGL(backtrace_gather_group, dim3(gu, args.n), dim3(64), 0, lead.stream, args);
 		uint32_t gs = 0;   // (the superreads of the members the device makes them for, behind the gather)
-		for (size_t i : batch) if (member(i).device_superreads) gs = std::max(gs, (problems[i]->n_cols + 255u) / 256u);
+		for (size_t i : batch) if (member(i).tp.device_superreads) gs = std::max(gs, (problems[i]->n_cols + 255u) / 256u);
 		if (gs) hipLaunchKernelGGL(superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, args);
 		if (hipGetLastError() != hipSuccess) return false;
 #ifdef WHAMD_DEBUG_BUILD
@@ -2624,7 +1758,7 @@ struct DeviceTable::Impl::GroupSubmission {
 			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_chunks_group, dim3(gx, args.n), dim3(256), lds, lead.stream, false, facts);
 			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_chunks_group, dim3(1, args.n), dim3(256), lds, lead.stream, false, facts);
 			m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)backtrace_gather_group, dim3(gu, args.n), dim3(64), 0, lead.stream, false, facts);
-			if (gs && m.device_superreads) m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, false, facts);
+			if (gs && m.tp.device_superreads) m.note(WHAMD_LAUNCH_GROUP_WALK, (const void*)superreads_group, dim3(gs, args.n), dim3(256), 0, lead.stream, false, facts);
 		}
 #endif
 		for (size_t i : batch) walked[i] = 1;
@@ -2642,7 +1776,7 @@ struct DeviceTable::Impl::GroupSubmission {
 		for (size_t i = 0; i < n; ++i) {
 			Impl& m = member(i);
 			m.inflight.launches = table_launches[i];
-			const bool own = debug_env("WHAMD_TAIL_OWN_STREAM") != nullptr || (!walked[i] && !m.use_chunks && !m.windowed && m.stream != lead.stream);
+			const bool own = debug_env("WHAMD_TAIL_OWN_STREAM") != nullptr || (!walked[i] && !m.tp.use_chunks && !m.tp.windowed && m.stream != lead.stream);
 			if (own) m.own_stream_used = true;
 			if (own && m.stream != lead.stream && hipStreamWaitEvent(m.stream, lead.ev_group, 0) != hipSuccess) return fail("hipStreamWaitEvent failed");
 			const whamd_status_t st = m.submit_tail(*problems[i], msg, own ? nullptr : lead.stream, walked[i] != 0);
@@ -2714,13 +1848,13 @@ void DeviceTable::read_timing(whamd_solve_stats& st) {
 // The in-kernel cycle stamps of the slot runs (WHAMD_SLOT_STAMPS, debug library): full-length runs, wave 0 of workgroup 0.
 whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
 	const Impl& m = *this;
-	std::vector<unsigned long long> d(m.splan.runs.size() * 48);
-	HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
+	std::vector<unsigned long long> d(m.tp.splan.runs.size() * 48);
+	HIP_TRY(hipMemcpy(d.data(), m.dev.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
 	double a[6] = {0, 0, 0, 0, 0, 0};
 	double percol[32] = {0};
 	size_t cnt = 0;
-	for (size_t i = 0; i < m.splan.runs.size(); ++i) {
-		if (m.splan.runs[i].ncols != 22 || d[48 * i + 5] == 0) continue;   // full-length runs only
+	for (size_t i = 0; i < m.tp.splan.runs.size(); ++i) {
+		if (m.tp.splan.runs[i].ncols != 22 || d[48 * i + 5] == 0) continue;   // full-length runs only
 		for (int k = 0; k < 6; ++k) a[k] += (double)d[48 * i + k];
 		for (int k = 0; k < 22; ++k) percol[k] += (double)d[48 * i + 8 + k];
 		++cnt;
@@ -2738,28 +1872,28 @@ whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
 // The in-kernel cycle stamps of the LDS-resident runs (WHAMD_DEBUG_STAMPS, debug library), with the backtrace's and four runs' workgroup by workgroup.
 whamd_status_t DeviceTable::Impl::report_resident_stamps(std::string& msg) const {
 	const Impl& m = *this;
-	std::vector<unsigned long long> d(m.plan.segments.size() * 8);
-	HIP_TRY(hipMemcpy(d.data(), m.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
+	std::vector<unsigned long long> d(m.tp.plan.segments.size() * 8);
+	HIP_TRY(hipMemcpy(d.data(), m.dev.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
 	unsigned long long a = 0, b = 0, c2 = 0, cols = 0, p1 = 0, p2 = 0, p3 = 0, ns = 0;
-	for (size_t i = 0; i < m.plan.segments.size(); ++i) { a += d[8 * i]; b += d[8 * i + 1]; c2 += d[8 * i + 2]; cols += d[8 * i + 3]; p1 += d[8 * i + 4]; p2 += d[8 * i + 5]; p3 += d[8 * i + 6]; ns += d[8 * i + 7]; }
-	if (!m.plan.ped_columns.empty() || (m.dp.dbg_flags & 4u))
+	for (size_t i = 0; i < m.tp.plan.segments.size(); ++i) { a += d[8 * i]; b += d[8 * i + 1]; c2 += d[8 * i + 2]; cols += d[8 * i + 3]; p1 += d[8 * i + 4]; p2 += d[8 * i + 5]; p3 += d[8 * i + 6]; ns += d[8 * i + 7]; }
+	if (!m.tp.plan.ped_columns.empty() || (m.dev.dp.dbg_flags & 4u))
 		fprintf(stderr, "[whamd timing] run prologue (wave 0 of workgroup 0), cycles after the first instruction: kernel arguments usable %.0f, first loaded data %.0f, everything staged %.0f\n",
 		        (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1), (double)p1 / std::max<unsigned long long>(ns, 1));
 	else
 	fprintf(stderr, "[whamd timing] per barrier step (wave 0 of workgroup 0, %.1f steps per run): hot words %.0f, evaluate %.0f, barrier %.0f cycles\n",
-	        (double)ns / m.plan.segments.size(), (double)p1 / std::max<unsigned long long>(ns, 1), (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1));
+	        (double)ns / m.tp.plan.segments.size(), (double)p1 / std::max<unsigned long long>(ns, 1), (double)p2 / std::max<unsigned long long>(ns, 1), (double)p3 / std::max<unsigned long long>(ns, 1));
 	{
 		unsigned long long b3[6] = {0, 0, 0, 0, 0, 0};
-		HIP_TRY(hipMemcpy(b3, m.dp.dbg + m.dp.dbg_wg_off + 4 * 512 * 2, sizeof b3, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(b3, m.dev.dp.dbg + m.dev.dp.dbg_wg_off + 4 * 512 * 2, sizeof b3, hipMemcpyDeviceToHost));
 		if (b3[2]) fprintf(stderr, "[whamd timing] backtrace per run: record load + prefetch %.0f cycles, walk + hand-over %.0f cycles (%llu runs); of the latter: local exit index %.0f, chain %.0f, logical indices + stores %.0f\n",
 		                   (double)b3[0] / b3[2], (double)b3[1] / b3[2], b3[2], (double)b3[3] / b3[2], (double)b3[4] / b3[2], (double)b3[5] / b3[2]);
 	}
-	if (m.plan.segments.size() > 104) {
+	if (m.tp.plan.segments.size() > 104) {
 		std::vector<unsigned long long> wg(4 * 512 * 2);
-		HIP_TRY(hipMemcpy(wg.data(), m.dp.dbg + m.dp.dbg_wg_off, wg.size() * 8, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(wg.data(), m.dev.dp.dbg + m.dev.dp.dbg_wg_off, wg.size() * 8, hipMemcpyDeviceToHost));
 		unsigned long long prev_end = 0;
 		for (int sgi = 0; sgi < 4; ++sgi) {
-			const uint32_t G = 1u << m.plan.segments[100 + sgi].g;
+			const uint32_t G = 1u << m.tp.plan.segments[100 + sgi].g;
 			unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
 			for (uint32_t ww = 0; ww < G; ++ww) {
 				const unsigned long long a2 = wg[((size_t)sgi * 512 + ww) * 2], b2 = wg[((size_t)sgi * 512 + ww) * 2 + 1];
@@ -2773,8 +1907,8 @@ whamd_status_t DeviceTable::Impl::report_resident_stamps(std::string& msg) const
 	float f01 = 0;
 	(void)hipEventElapsedTime(&f01, m.ev0, m.ev1);
 	fprintf(stderr, "[whamd timing] segments %zu cols %llu | cycles/segment: prologue %.0f columns %.0f (%.0f per column) store %.0f | fwd %.3f ms, %.2f us per segment\n",
-	        m.plan.segments.size(), cols, (double)a / m.plan.segments.size(), (double)b / m.plan.segments.size(),
-	        (double)b / std::max<unsigned long long>(cols, 1), (double)c2 / m.plan.segments.size(), f01, f01 * 1e3 / m.plan.segments.size());
+	        m.tp.plan.segments.size(), cols, (double)a / m.tp.plan.segments.size(), (double)b / m.tp.plan.segments.size(),
+	        (double)b / std::max<unsigned long long>(cols, 1), (double)c2 / m.tp.plan.segments.size(), f01, f01 * 1e3 / m.tp.plan.segments.size());
 	return WHAMD_OK;
 }
 
@@ -2789,11 +1923,11 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 	m.upload_pending = false;   // (the solve ran behind ev_upload: the uploads are there)
 	m.give_preview_block();     // (the preview ran in front of this solve, or was waited for when the solve began on another stream)
 	const uint32_t n = p.n_cols;
-	std::memcpy(s.path_index.data(), m.h_pinned, (size_t)n * 4);
-	std::memcpy(s.path_trans.data(), m.h_pinned + n, (size_t)n * 4);
-	s.optimal_score = m.h_pinned[2 * (size_t)n];
-	if (m.device_superreads) {
-		const uint32_t* q = m.h_pinned + m.super_off;
+	std::memcpy(s.path_index.data(), m.dev.h_pinned, (size_t)n * 4);
+	std::memcpy(s.path_trans.data(), m.dev.h_pinned + n, (size_t)n * 4);
+	s.optimal_score = m.dev.h_pinned[2 * (size_t)n];
+	if (m.tp.device_superreads) {
+		const uint32_t* q = m.dev.h_pinned + m.tp.super_off;
 		const uint8_t* h = (const uint8_t*)(q + n);
 		if (std::memchr(h, SUPERREAD_CONFLICT, (size_t)2 * n) == nullptr) {   // (a conflict: the host's loop runs and reports it, finish_solution)
 			s.quality.resize(n);
@@ -2805,7 +1939,7 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 			s.superreads_done = true;
 		}
 	}
-	for (size_t j = 1; j < m.jobs.size(); ++j) s.optimal_score += m.h_pinned[2 * (size_t)n + j];  // connected components solved as their own jobs
+	for (size_t j = 1; j < m.tp.jobs.size(); ++j) s.optimal_score += m.dev.h_pinned[2 * (size_t)n + j];  // connected components solved as their own jobs
 	// (the event timings are read when somebody asks -- read_timing(), from whamd_dptable_get_stats: three runtime calls per table, from every
 	//  waiting thread at once, are a measurable part of collecting a 96-table step and most callers never look at them)
 	st.forward_ms = st.backtrace_ms = st.total_ms = 0;
@@ -2813,15 +1947,15 @@ whamd_status_t DeviceTable::wait(const Problem& p, Solution& s, whamd_solve_stat
 	st.forward_launches = launches;
 	st.group_tables = m.inflight.group_tables;
 	st.bt_chunks = st.bt_missed = st.bt_rewalked = 0;
-	if (m.use_chunks) {
-		const uint32_t* c = m.h_pinned + 2 * (size_t)n + m.jobs.size();   // (downloaded with the path)
-		st.bt_chunks = (uint32_t)m.chunks.size();
+	if (m.tp.use_chunks) {
+		const uint32_t* c = m.dev.h_pinned + 2 * (size_t)n + m.tp.jobs.size();   // (downloaded with the path)
+		st.bt_chunks = (uint32_t)m.tp.chunks.size();
 		st.bt_missed = c[0];
 		st.bt_rewalked = c[1];
-		if (debug_env("WHAMD_BT_STATS")) fprintf(stderr, "[whamd backtrace] %zu chunks, %u guesses missed (%u of them only in the transmission value), %u units walked again (of %zu)\n", m.chunks.size(), c[0], c[2], c[1], m.units.size());
+		if (debug_env("WHAMD_BT_STATS")) fprintf(stderr, "[whamd backtrace] %zu chunks, %u guesses missed (%u of them only in the transmission value), %u units walked again (of %zu)\n", m.tp.chunks.size(), c[0], c[2], c[1], m.tp.units.size());
 	}
-	whamd_status_t reported = m.dp.dbg && m.use_slots ? m.report_slot_stamps(msg) : WHAMD_OK;   // (the debug library's in-kernel cycle stamps)
-	if (reported == WHAMD_OK && m.dp.dbg && !m.plan.segments.empty()) reported = m.report_resident_stamps(msg);
+	whamd_status_t reported = m.dev.dp.dbg && m.tp.use_slots ? m.report_slot_stamps(msg) : WHAMD_OK;   // (the debug library's in-kernel cycle stamps)
+	if (reported == WHAMD_OK && m.dev.dp.dbg && !m.tp.plan.segments.empty()) reported = m.report_resident_stamps(msg);
 	return reported;
 }
 
@@ -2916,50 +2050,51 @@ static const char* const* preview_why_lines() {   // [PreviewWhy]
 }
 
 // plan_preview against the phases it runs ahead of, without a device (whamd_debug_preview_plan): the plan as choose_plan makes it for a single individual, the
-// preview forced with `pieces`, then describe_columns, lay_out_arena, the units and cut_chunks exactly as upload() runs them -- free HBM is taken as 1 TiB.
+// preview forced with `pieces`, then table_plan.h's describe_columns, lay_out_arena, the units and cut_chunks in upload()'s order -- free HBM is taken as 1 TiB.
 whamd_status_t DeviceTable::debug_preview_plan(Problem& p, uint32_t pieces, whamd_debug_preview_plan_result* out, uint64_t* rec_predicted, uint64_t* rec_laid_out,
                                                uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity, std::string& msg) {
-	Impl m;
+	TableOptions opt;
+	TablePlan tp;
+	uint32_t spec_stride = 64;
 	TableBuild b;
 	b.n = p.n_cols;
 	b.tbits = 2 * p.n_triples;
 	b.ni = std::max<uint32_t>(p.n_ind, 1);
 	b.free_b = (size_t)1 << 40;
 	if (p.T != 1 || p.n_cols == 0) { msg = "a single-individual table expected"; return WHAMD_ERR_UNSUPPORTED; }
-	m.wide = !select_kernels(p.T, p.n_ind, m.fused, m.keysfn);
-	m.use_slots = plan_forward_slots(p, std::max(8, m.slot_l), m.symmetry, m.splan, m.slot_lr);
-	if (!m.use_slots) { msg = "the table is not planned on slot runs"; return WHAMD_ERR_UNSUPPORTED; }
-	m.plan = ResidentPlan();
-	m.plan.steps = m.splan.steps;
-	m.plan.component_first_step = m.splan.component_first_step;
-	m.plan.col_to_res.assign(p.n_cols, -1);
-	m.preview.mode = 1;
-	m.preview.pieces_wanted = pieces;
-	Impl::PreviewPlan pp;
-	m.plan_preview(p, b, true, pp);
-	whamd_status_t st = m.describe_columns(p, b, msg);
-	if (st == WHAMD_OK) st = m.lay_out_arena(p, b, msg);
+	tp.use_slots = plan_forward_slots(p, std::max(8, opt.slot_l), opt.symmetry, tp.splan, opt.slot_lr);
+	if (!tp.use_slots) { msg = "the table is not planned on slot runs"; return WHAMD_ERR_UNSUPPORTED; }
+	tp.plan = ResidentPlan();
+	tp.plan.steps = tp.splan.steps;
+	tp.plan.component_first_step = tp.splan.component_first_step;
+	tp.plan.col_to_res.assign(p.n_cols, -1);
+	opt.preview_mode = 1;
+	opt.preview_pieces = pieces;
+	PreviewPlan pp;
+	plan_preview(p, opt, b, tp, true, true, pp);   // (forced: `alone` is not asked)
+	whamd_status_t st = describe_columns(p, b, tp, msg);
+	if (st == WHAMD_OK) st = lay_out_arena(p, opt, b, tp, msg);
 	if (st != WHAMD_OK) return st;
-	m.build_slot_blobs(b);
-	m.lay_out_slot_tables(b, false);
-	m.make_jobs();
-	m.make_units(b);
-	m.cut_chunks(p);
+	build_slot_blobs(tp, b);
+	lay_out_slot_tables(tp, b, false);
+	make_jobs(opt, tp);
+	make_units(b, tp);
+	cut_chunks(p, tp, spec_stride);
 	static const char* const* why = preview_why_lines();
 	*out = whamd_debug_preview_plan_result{};
 	out->n_pieces = slot_plan_pieces(p.n_cols);
 	out->pieces = pp.pieces;
 	out->steps = pp.steps;
-	out->n_steps = (uint32_t)m.plan.steps.size();
-	out->why_not = why[pp.why < Impl::PV_WHYS ? pp.why : 0];
-	out->chunked_predicted = pp.chunked; out->chunked = m.use_chunks;
-	out->n_seeds_predicted = pp.n_spec; out->n_seeds = m.n_spec;
-	out->stride_predicted = pp.stride; out->stride = m.use_chunks ? m.dp.spec_stride : 64u;
+	out->n_steps = (uint32_t)tp.plan.steps.size();
+	out->why_not = why[pp.why < PV_WHYS ? pp.why : 0];
+	out->chunked_predicted = pp.chunked; out->chunked = tp.use_chunks;
+	out->n_seeds_predicted = pp.n_spec; out->n_seeds = tp.n_spec;
+	out->stride_predicted = pp.stride; out->stride = tp.use_chunks ? spec_stride : 64u;
 	out->arena_predicted = pp.arena; out->arena_laid_out = b.bt;
-	out->windowed = m.windowed;
+	out->windowed = tp.windowed;
 	out->exchange_predicted = (uint64_t)(1ull << pp.max_f) * p.T * 4; out->exchange_laid_out = b.exchange_bytes;
 	for (uint32_t k = 0; k < pp.steps && k < capacity; ++k) {
-		const SlotRun& run = m.splan.runs[m.plan.steps[k].index];
+		const SlotRun& run = tp.splan.runs[tp.plan.steps[k].index];
 		if (rec_predicted) rec_predicted[k] = pp.rec[k];
 		if (rec_laid_out) rec_laid_out[k] = ((uint64_t)run.rec_hi << 32) | run.rec_lo;
 		if (spec_predicted) spec_predicted[k] = pp.spec[k];
@@ -2972,13 +2107,13 @@ whamd_status_t DeviceTable::debug_preview_plan(Problem& p, uint32_t pieces, wham
 void DeviceTable::debug_preview(whamd_debug_preview* out) const {
 	static const char* const* why = preview_why_lines();
 	const Impl::Preview& pv = impl_->preview;
-	out->ran = pv.why == Impl::PV_RAN;
+	out->ran = pv.why == PV_RAN;
 	out->continued = pv.continued;
 	out->pieces = pv.pieces;
 	out->launched_steps = pv.launched;
 	out->agreed_steps = pv.agreed;
-	out->from_hook = pv.why == Impl::PV_RAN && pv.from_hook ? 1u : 0u;
-	out->why_not = why[pv.why < Impl::PV_WHYS ? pv.why : 0];
+	out->from_hook = pv.why == PV_RAN && pv.from_hook ? 1u : 0u;
+	out->why_not = why[pv.why < PV_WHYS ? pv.why : 0];
 }
 
 // One launch into the ledger: a line that agrees in everything but the count takes it, else it opens a new line.

@@ -10,10 +10,7 @@
 // One workgroup per job (BtJob).  `with_last_column` != 0: units[0] is the table's last column (its optimum comes from
 // P.last_keys), the walk starts at units[1].  == 0: the units are the steps of ONE connected component that ends before
 // the table does (its last column projects onto a single entry): the walk starts at units[0] with entry 0 and no score
-// is written.
-constexpr int BT_CELLS = 128;
-constexpr int BT_CHUNK_BLOB = RES_MAXCOLS * 32;   // words of the chunk walker's per-unit descriptor area (>= SLOT_MAXCOLS * 8 + 32)
-constexpr int BT_CHUNK_RUNS = 16;   // slot runs per chunk of the speculative backtrace  // >= RES_MAXCOLS and >= SLOT_MAXENDS_RUN + 1
+// is written.  (BT_CELLS, BT_CHUNK_BLOB, BT_CHUNK_RUNS: resident.h, the host sizes the walkers' LDS with them.)
 
 // One pedigree slot run (slots.h, kernels_pedslots.h) for the calling wave: the record holds one byte per (lane, column) =
 // argj | ending-read decisions << 4, four columns per word.  Walks the columns newest first from local cell `l` and
@@ -442,15 +439,7 @@ __global__ __launch_bounds__(1024) void backtrace_kernel(DevProblem P, const BtU
 // Where every genotype is heterozygous (the synthetic benchmarks; long stretches of real data) complementing a CHILD's reads
 // together with both of its transmission bits is a symmetry too: the child then carries its parents' other haplotypes, which
 // hold the complementary alleles.  It is not exact in general -- a guess only has to be right often, the verification keeps the
-// result exact -- so children are generators as well: up to 4 generators (a quartet), 16 guesses per chunk.
-constexpr uint32_t BT_GENERATORS = 4;
-constexpr uint32_t BT_ORIENT = 1u << BT_GENERATORS;
-struct BtChunk {
-	uint32_t unit_off, unit_count;
-	uint32_t spec_id;   // 0: the newest chunk (units[0] is the table's last column, the optimum comes from P.last_keys)
-	uint32_t n_orient;  // 2^generators in use
-	uint32_t flip[BT_GENERATORS];   // packed-state XOR of each generator at this chunk's entry (index bits | transmission bits << BT_STATE_TSHIFT)
-};
+// result exact -- so children are generators as well: up to 4 generators (a quartet), 16 guesses per chunk.  (BtChunk, BT_GENERATORS, BT_ORIENT: resident.h.)
 __device__ __forceinline__ uint32_t bt_orient(const BtChunk& ch, uint32_t state, uint32_t o) {
 #pragma unroll
 	for (uint32_t q = 0; q < BT_GENERATORS; ++q) state ^= ((o >> q) & 1u) ? ch.flip[q] : 0u;

@@ -1,7 +1,6 @@
 // kernels_column.h -- per-column kernels (one launch per column): column_step_fused, column_step_keys, column_finalize, and the device helpers every kernel shares (bit deposit, Gray rank, LDS staging of a column).
 // Included by dp_device.hip inside namespace whamd { namespace { ... } }: not a stand-alone header.
-
-constexpr int QMAX = 4;  // a thread enumerates at most 2^QMAX ending-bit patterns itself
+// (QMAX, COL_MAXTERMS: device_types.h -- the host's column descriptors and kernel choice read them.)
 
 // Bit deposit through host-precomputed runs of the mask (gfx950 has no PDEP): the segment list is wave-uniform.
 __device__ __forceinline__ uint32_t deposit(uint32_t v, const uint32_t* __restrict__ segs, uint32_t nseg) {
@@ -27,7 +26,7 @@ __device__ __forceinline__ uint32_t gray_rank(uint32_t x) {
 // Per-launch staging of a column's cost data in LDS: 5-bit lookup tables of the per-individual sums L_s(x) and the
 // term lists of every transmission value, so that a cell costs ceil(k/5) LDS reads per individual instead of a
 // k-step loop over scalar global loads.
-constexpr int COL_CHUNKS = 5, COL_MAXTERMS = 1024;
+constexpr int COL_CHUNKS = 5;
 template <int T, int NIND>
 struct ColumnStage {
 	int32_t lut[NIND][COL_CHUNKS][32];

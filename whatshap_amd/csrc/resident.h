@@ -191,6 +191,21 @@ struct BtJob {
 	uint32_t pad;
 };
 
+// LDS of the backtrace kernels (kernels_backtrace.h; the host sizes their launches: table_plan.cpp backtrace_lds_sizes).
+constexpr int BT_CELLS = 128;
+constexpr int BT_CHUNK_BLOB = RES_MAXCOLS * 32;   // words of the chunk walker's per-unit descriptor area (>= SLOT_MAXCOLS * 8 + 32)
+constexpr int BT_CHUNK_RUNS = 16;   // slot runs per chunk of the speculative backtrace  // >= RES_MAXCOLS and >= SLOT_MAXENDS_RUN + 1
+
+// One chunk of the speculative backtrace and its orientations (kernels_backtrace.h "Orientations" says what they are).
+constexpr uint32_t BT_GENERATORS = 4;
+constexpr uint32_t BT_ORIENT = 1u << BT_GENERATORS;
+struct BtChunk {
+	uint32_t unit_off, unit_count;
+	uint32_t spec_id;   // 0: the newest chunk (units[0] is the table's last column, the optimum comes from P.last_keys)
+	uint32_t n_orient;  // 2^generators in use
+	uint32_t flip[BT_GENERATORS];   // packed-state XOR of each generator at this chunk's entry (index bits | transmission bits << BT_STATE_TSHIFT)
+};
+
 struct Step {
 	uint32_t kind;         // 0 = one column through the column kernels, 1 = resident run
 	uint32_t index;        // column index, or index into segments
