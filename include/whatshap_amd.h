@@ -711,6 +711,83 @@ whamd_status_t whamd_haplotag_get_bx(const whamd_haplotag_result* r, uint64_t m,
 whamd_status_t whamd_haplotag_get_stats(const whamd_haplotag_result* r, uint64_t m, whamd_haplotag_stats* stats_out);
 void whamd_haplotag_destroy(whamd_haplotag_result* r);
 
+/* ---- Polyphase reordering (run_reordering without prephasing, whatshap/polyphase/reorder.py:139-194, 220-292, 351-407, 497-527) -----------
+ * The third phase of `whatshap polyphase`: at every breakpoint of the threading, the log likelihood of each of the k! ways to link the k
+ * affected haplotypes across it, the most likely linkage, and the threads and haplotypes permuted block by block accordingly.
+ * One problem is one block: an AlleleMatrix (positions are its local indices 0 .. n_pos-1: n_pos must be the number of distinct positions
+ * of the matrix), haplotypes[ploidy][n_pos] (any int8, -1 is a value like any other), threads[n_pos][ploidy], the clustering as CSR of read
+ * ids, and per breakpoint its position in [1, n_pos), its sorted affected haplotypes (2 .. 8 of them) and the clusters whose reads are
+ * collected, IN THE ORDER they are to be walked (the reference iterates a Python set of threads[pos][h] and threads[pos-1][h] over the
+ * affected h; the Python wrapper evaluates the same expression).
+ * Per breakpoint (host, csrc/polyreorder.cpp): the window -- up to 32 positions left of the breakpoint and up to 32 from it on at which
+ * the affected haplotypes carry at least two values --; the reads of the listed clusters, in cluster order, with first < pos <= last
+ * (getFirstPos / getLastPos of the matrix above), minus those extractSubMatrix(.., removeEmpty = true) drops: first >= the last window
+ * position or last < the first (allelematrix.cpp:193; an empty window drops every read).
+ * Device (csrc/polyreorder_device.hip): per kept read and affected haplotype, matches and errors left and right of the breakpoint over
+ * the read's alleles at window positions, llh = log_match * (overlap - errors) + log_err * errors in double with every product and the
+ * sum rounded on its own; per permutation, in lexicographic order, the sum over the reads IN ORDER, starting from +0.0, of the largest
+ * left[affected[i]] + right[perm[i]].  log_match / log_err are the caller's log(1 - error_rate) / log(error_rate): the library calls no log.
+ * Host again: per breakpoint the first largest llh in permutation order, the chained assignments (reorder.py:398-407), permute_blocks and
+ * compute_breakpoint_confidence (host exp).
+ * Errors (WHAMD_ERR_INVALID, nothing launched): what the matrix section lists; ploidy 0 or above 16; n_pos other than the matrix's
+ * positions; an affected list unsorted, with repeats, shorter than 2, longer than 8 or naming a haplotype >= ploidy; a cluster or read
+ * id out of range; breakpoint positions not strictly ascending or outside [1, n_pos). */
+typedef struct whamd_poly_reorder_view {
+	whamd_poly_matrix_view matrix;
+	uint32_t ploidy;
+	uint32_t reserved;                  /* 0 */
+	uint64_t n_pos;
+	const int8_t* haplotypes;           /* [ploidy][n_pos] */
+	const int32_t* threads;             /* [n_pos][ploidy] */
+	uint64_t n_clusters;
+	const uint64_t* cluster_ptr;        /* [n_clusters + 1] into cluster_reads */
+	const uint32_t* cluster_reads;      /* read ids of the matrix */
+	uint64_t n_breakpoints;
+	const uint64_t* bp_position;        /* [n_breakpoints] strictly ascending, in [1, n_pos) */
+	const uint64_t* bp_affected_ptr;    /* [n_breakpoints + 1] into bp_affected */
+	const uint32_t* bp_affected;        /* sorted haplotype indices */
+	const uint64_t* bp_cluster_ptr;     /* [n_breakpoints + 1] into bp_clusters */
+	const uint32_t* bp_clusters;        /* cluster ids in the order their reads are walked */
+} whamd_poly_reorder_view;
+
+typedef struct whamd_poly_reorder_stats {
+	uint64_t n_breakpoints;
+	uint64_t n_reads_visited;           /* kept reads summed over the breakpoints (rows of the left / right table) */
+	uint64_t n_permutations;            /* k! summed over the breakpoints */
+	uint64_t n_window_positions;        /* window positions summed over the breakpoints */
+	uint32_t launches;                  /* kernel launches of the whole call: at most 2 (0: nothing touched the device) */
+	double host_ms;                     /* wall, whole call: validation, matrices, windows, read lists */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double total_ms;                    /* wall, whole call */
+} whamd_poly_reorder_stats;
+
+typedef struct whamd_poly_reorder_result whamd_poly_reorder_result; /* opaque: the result of one whamd_poly_reorder call */
+
+/* One call for a batch of problems: one upload, at most two launches, one download. */
+whamd_status_t whamd_poly_reorder(const whamd_poly_reorder_view* problems, uint64_t n_problems, double log_match, double log_err, int device,
+                                  whamd_poly_reorder_result** out);
+uint64_t whamd_poly_reorder_problem_count(const whamd_poly_reorder_result* r);
+/* Breakpoints, llh values (k! summed over the breakpoints) and window positions of problem m. */
+uint64_t whamd_poly_reorder_breakpoint_count(const whamd_poly_reorder_result* r, uint64_t m);
+uint64_t whamd_poly_reorder_llh_count(const whamd_poly_reorder_result* r, uint64_t m);
+uint64_t whamd_poly_reorder_window_count(const whamd_poly_reorder_result* r, uint64_t m);
+/* llh_ptr_out: [breakpoints + 1] into llh_out; llh_out: per breakpoint its k! values in permutation order; best_out: [breakpoints] the
+ * rank, in permutation order, of the first largest value; NULL skips. */
+whamd_status_t whamd_poly_reorder_get_llh(const whamd_poly_reorder_result* r, uint64_t m, uint64_t* llh_ptr_out, double* llh_out, uint32_t* best_out);
+/* window_ptr_out: [breakpoints + 1] into position_out; left_count_out: [breakpoints] how many of a breakpoint's positions lie left of it;
+ * position_out: the window positions, ascending per breakpoint; NULL skips. */
+whamd_status_t whamd_poly_reorder_get_windows(const whamd_poly_reorder_result* r, uint64_t m, uint64_t* window_ptr_out, uint32_t* left_count_out,
+                                              uint32_t* position_out);
+/* assignments_out: [breakpoints + 1][ploidy] (get_optimal_assignments); threads_out: [n_pos][ploidy] and haplotypes_out: [ploidy][n_pos]
+ * after permute_blocks; confidence_out: [breakpoints]; NULL skips. */
+whamd_status_t whamd_poly_reorder_get_phasing(const whamd_poly_reorder_result* r, uint64_t m, uint32_t* assignments_out, int32_t* threads_out,
+                                              int8_t* haplotypes_out, double* confidence_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_poly_reorder_get_stats(const whamd_poly_reorder_result* r, uint64_t m, whamd_poly_reorder_stats* stats_out);
+void whamd_poly_reorder_destroy(whamd_poly_reorder_result* r);
+
 #ifdef __cplusplus
 }
 #endif

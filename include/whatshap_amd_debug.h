@@ -94,6 +94,13 @@ whamd_status_t whamd_debug_progeny_gl_host(const whamd_progeny_depths_view* prob
  * field; never what the product calls.  Read with the whamd_haplotag_* getters of the debug library. */
 whamd_status_t whamd_debug_haplotag_host(const whamd_haplotag_view* problems, uint64_t n_problems, whamd_haplotag_result** out);
 
+/* HOST-ONLY DIAGNOSTICS of polyphase reordering (csrc/polyreorder.cpp): the same validation, windows and read lists as whamd_poly_reorder,
+ * then the left / right table and every permutation's sum on one CPU thread with the functions the kernels call (csrc/polyreorder.h) --
+ * what the CPU test-suite holds to the recorded reference, bit for bit; never what the product calls.  Read with the
+ * whamd_poly_reorder_* getters of the debug library. */
+whamd_status_t whamd_debug_poly_reorder_host(const whamd_poly_reorder_view* problems, uint64_t n_problems, double log_match, double log_err,
+                                             whamd_poly_reorder_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

@@ -212,6 +212,21 @@ class HaplotagStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PolyReorderView(C.Structure):
+    _fields_ = [("matrix", PolyMatrixView), ("ploidy", C.c_uint32), ("reserved", C.c_uint32), ("n_pos", C.c_uint64), ("haplotypes", C.POINTER(C.c_int8)),
+                ("threads", C.POINTER(C.c_int32)), ("n_clusters", C.c_uint64), ("cluster_ptr", C.POINTER(C.c_uint64)), ("cluster_reads", C.POINTER(C.c_uint32)),
+                ("n_breakpoints", C.c_uint64), ("bp_position", C.POINTER(C.c_uint64)), ("bp_affected_ptr", C.POINTER(C.c_uint64)),
+                ("bp_affected", C.POINTER(C.c_uint32)), ("bp_cluster_ptr", C.POINTER(C.c_uint64)), ("bp_clusters", C.POINTER(C.c_uint32))]
+
+
+class PolyReorderStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_breakpoints", "n_reads_visited", "n_permutations", "n_window_positions")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -374,6 +389,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_progeny_gl_host.argtypes = [C.POINTER(ProgenyDepthsView), C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_double))]
     L.whamd_debug_haplotag_host.restype = C.c_int
     L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_poly_reorder_host.restype = C.c_int
+    L.whamd_debug_poly_reorder_host.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
@@ -542,6 +559,23 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_haplotag_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(HaplotagStats)]
     L.whamd_haplotag_destroy.restype = None
     L.whamd_haplotag_destroy.argtypes = [C.c_void_p]
+    L.whamd_poly_reorder.restype = C.c_int
+    L.whamd_poly_reorder.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_poly_reorder_problem_count.restype = C.c_uint64
+    L.whamd_poly_reorder_problem_count.argtypes = [C.c_void_p]
+    for name in ("whamd_poly_reorder_breakpoint_count", "whamd_poly_reorder_llh_count", "whamd_poly_reorder_window_count"):
+        getattr(L, name).restype = C.c_uint64
+        getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_poly_reorder_get_llh.restype = C.c_int
+    L.whamd_poly_reorder_get_llh.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+    L.whamd_poly_reorder_get_windows.restype = C.c_int
+    L.whamd_poly_reorder_get_windows.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_poly_reorder_get_phasing.restype = C.c_int
+    L.whamd_poly_reorder_get_phasing.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_int8), C.POINTER(C.c_double)]
+    L.whamd_poly_reorder_get_stats.restype = C.c_int
+    L.whamd_poly_reorder_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PolyReorderStats)]
+    L.whamd_poly_reorder_destroy.restype = None
+    L.whamd_poly_reorder_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -568,6 +602,9 @@ EXPORTED_SYMBOLS = [
     "whamd_progeny_score_destroy", "whamd_progeny_variant_types", "whamd_progeny_gl", "whamd_progeny_score_depths",
     "whamd_haplotag", "whamd_haplotag_problem_count", "whamd_haplotag_count", "whamd_haplotag_get", "whamd_haplotag_bx_count", "whamd_haplotag_get_bx",
     "whamd_haplotag_get_stats", "whamd_haplotag_destroy",
+    "whamd_poly_reorder", "whamd_poly_reorder_problem_count", "whamd_poly_reorder_breakpoint_count", "whamd_poly_reorder_llh_count",
+    "whamd_poly_reorder_window_count", "whamd_poly_reorder_get_llh", "whamd_poly_reorder_get_windows", "whamd_poly_reorder_get_phasing",
+    "whamd_poly_reorder_get_stats", "whamd_poly_reorder_destroy",
 ]
 
 
