@@ -788,6 +788,83 @@ whamd_status_t whamd_poly_reorder_get_phasing(const whamd_poly_reorder_result* r
 whamd_status_t whamd_poly_reorder_get_stats(const whamd_poly_reorder_result* r, uint64_t m, whamd_poly_reorder_stats* stats_out);
 void whamd_poly_reorder_destroy(whamd_poly_reorder_result* r);
 
+/* ---- Comparing polyploid phasings (`whatshap compare` above ploidy 2: compare_block, compute_switch_errors_poly and
+ * compute_switch_flips_poly of whatshap/cli/compare.py on SwitchFlipCalculator::compare, src/polyphase/switchflipcalculator.cpp) -----------
+ * One job is two phasings of the same positions, phasing0 and phasing1 as [n_pos][ploidy] alleles, and two costs.  The program is a
+ * Viterbi pass over the ploidy! permutations of the haplotypes per visited position: a state costs flip_cost times the number of i with
+ * phasing0[perm[i]] != phasing1[i], a transition switch_cost times the places in which two permutations differ.  matched_only visits
+ * only the positions at which the two columns hold the same multiset of alleles (compute_matching_genotype_pos) and skips the rest.
+ * States are ranked in the order of std::next_permutation from the identity (itertools.permutations(range(ploidy))).
+ *
+ * Identical to the reference: the total cost; the minimum Hamming distance; the matching positions; the switch-error count (flip cost
+ * 2 * num_vars * ploidy + 1: no flip is chosen and the count is unique); the result for ONE visited position, switches = ploidy - 1 (the
+ * reference's backtrace start counts the differences to Permutation::INVALID without a guard for position 0).
+ * Defined here, because the reference's answer is an artefact of hash order (among equal candidates it takes the first in the iteration
+ * order of a std::unordered_map): among the paths of minimum total cost the one with the fewest flips; among those, the predecessor of
+ * lowest rank at every step and the end state of lowest rank.  Under this rule switches and flips depend on the input alone.  The
+ * reference never has fewer flips.
+ * Scores: min over q (score[q] + switch_cost * d) first, + flip_cost * f after, column 0 flip_cost * f alone, every product and sum
+ * rounded on its own in double.
+ * Device (csrc/polycompare_device.hip): one workgroup per job, one launch per call whatever the batch size (at most two are allowed
+ * for).  Jobs with n_pos == 0 and matched_only jobs without a matching position return zeros; a call of only such jobs launches nothing.
+ * Errors, all with nothing launched.  WHAMD_ERR_INVALID: ploidy below 2; a cost that is negative, NaN or infinite; a null array with
+ * n_pos > 0.  WHAMD_ERR_UNSUPPORTED: ploidy above 6 (7! states are 25 M candidates per column; the reference itself warns above 6);
+ * more than 2^28 positions in one job; want_path tables, n_visited * ploidy! * 2 bytes each, above WHAMD_POLY_COMPARE_MAX_PATH_BYTES in
+ * total per call -- a limit, not a tuned number. */
+#define WHAMD_POLY_COMPARE_MAX_PATH_BYTES ((uint64_t)1 << 30)
+
+typedef struct whamd_poly_compare_view {
+	uint32_t ploidy;
+	uint32_t matched_only;              /* 0 / 1 */
+	uint64_t n_pos;
+	const uint8_t* phasing0;            /* [n_pos][ploidy] */
+	const uint8_t* phasing1;            /* [n_pos][ploidy] */
+	double switch_cost;
+	double flip_cost;
+	uint32_t want_path;                 /* 0 / 1: keep the state of every visited position */
+	uint32_t reserved;                  /* 0 */
+} whamd_poly_compare_view;
+
+typedef struct whamd_poly_compare_job_result {
+	double total;                       /* the minimum of the program: switch_cost * switches + flip_cost * flips of the chosen path */
+	uint64_t n_matched;                 /* positions whose two allele multisets are equal (counted for every job) */
+	uint64_t n_visited;                 /* n_matched with matched_only, else n_pos */
+	uint64_t min_hamming_sum;           /* min over permutations of the disagreements summed over the visited positions */
+	uint32_t switches;                  /* raw: not divided by ploidy */
+	uint32_t flips;
+} whamd_poly_compare_job_result;
+
+typedef struct whamd_poly_compare_stats {
+	uint64_t n_jobs;
+	uint64_t n_positions;               /* summed over the jobs */
+	uint64_t n_visited;                 /* positions visited, summed over the jobs */
+	uint64_t path_bytes;                /* predecessor tables of the want_path jobs */
+	uint32_t launches;                  /* kernel launches of the whole call: at most 2 (0: nothing touched the device) */
+	double host_ms;                     /* wall: validation, matching positions */
+	double upload_ms;                   /* HIP events */
+	double kernel_ms;                   /* HIP events */
+	double download_ms;                 /* HIP events */
+	double total_ms;                    /* wall, whole call */
+} whamd_poly_compare_stats;
+
+typedef struct whamd_poly_compare_result whamd_poly_compare_result; /* opaque: the result of one whamd_poly_compare call */
+
+/* One call for a batch of jobs: one upload, at most two launches, one download. */
+whamd_status_t whamd_poly_compare(const whamd_poly_compare_view* jobs, uint64_t n_jobs, int device, whamd_poly_compare_result** out);
+uint64_t whamd_poly_compare_job_count(const whamd_poly_compare_result* r);
+/* Visited positions of job j that carry a path entry (0 without want_path). */
+uint64_t whamd_poly_compare_path_count(const whamd_poly_compare_result* r, uint64_t j);
+/* results_out: [jobs]. */
+whamd_status_t whamd_poly_compare_get(const whamd_poly_compare_result* r, whamd_poly_compare_job_result* results_out);
+/* Per visited position of job j, front to back like the reference's three lists after its reverse: position_out the position's index in
+ * the job; rank_out the state's rank; perm_out [..][ploidy] the permutation; flipped_out [..][ploidy] 1 where phasing0[perm[i]] !=
+ * phasing1[i]; switches_out the places in which the permutation differs from the previous position's (first position: 0, or ploidy - 1
+ * when it is the only one).  NULL skips. */
+whamd_status_t whamd_poly_compare_get_path(const whamd_poly_compare_result* r, uint64_t j, uint64_t* position_out, uint16_t* rank_out, uint8_t* perm_out,
+                                           uint8_t* flipped_out, uint32_t* switches_out);
+whamd_status_t whamd_poly_compare_get_stats(const whamd_poly_compare_result* r, whamd_poly_compare_stats* stats_out);
+void whamd_poly_compare_destroy(whamd_poly_compare_result* r);
+
 #ifdef __cplusplus
 }
 #endif

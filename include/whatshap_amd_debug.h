@@ -101,6 +101,11 @@ whamd_status_t whamd_debug_haplotag_host(const whamd_haplotag_view* problems, ui
 whamd_status_t whamd_debug_poly_reorder_host(const whamd_poly_reorder_view* problems, uint64_t n_problems, double log_match, double log_err,
                                              whamd_poly_reorder_result** out);
 
+/* HOST-ONLY DIAGNOSTICS of comparing polyploid phasings (csrc/polycompare.cpp): the same validation as whamd_poly_compare, then every job
+ * state by state on one CPU thread with the functions the kernel calls (csrc/polycompare.h) -- bit-identical to the device, launches
+ * nothing; what the CPU test-suite holds to the recorded reference.  Read with the whamd_poly_compare_* getters of the debug library. */
+whamd_status_t whamd_debug_poly_compare_host(const whamd_poly_compare_view* jobs, uint64_t n_jobs, whamd_poly_compare_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

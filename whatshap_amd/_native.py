@@ -227,6 +227,24 @@ class PolyReorderStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PolyCompareView(C.Structure):
+    _fields_ = [("ploidy", C.c_uint32), ("matched_only", C.c_uint32), ("n_pos", C.c_uint64), ("phasing0", C.POINTER(C.c_uint8)),
+                ("phasing1", C.POINTER(C.c_uint8)), ("switch_cost", C.c_double), ("flip_cost", C.c_double), ("want_path", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PolyCompareJobResult(C.Structure):
+    _fields_ = [("total", C.c_double), ("n_matched", C.c_uint64), ("n_visited", C.c_uint64), ("min_hamming_sum", C.c_uint64), ("switches", C.c_uint32),
+                ("flips", C.c_uint32)]
+
+
+class PolyCompareStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_jobs", "n_positions", "n_visited", "path_bytes")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -391,6 +409,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_reorder_host.restype = C.c_int
     L.whamd_debug_poly_reorder_host.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
+    L.whamd_debug_poly_compare_host.restype = C.c_int
+    L.whamd_debug_poly_compare_host.argtypes = [C.POINTER(PolyCompareView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
@@ -576,6 +596,21 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_poly_reorder_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PolyReorderStats)]
     L.whamd_poly_reorder_destroy.restype = None
     L.whamd_poly_reorder_destroy.argtypes = [C.c_void_p]
+    L.whamd_poly_compare.restype = C.c_int
+    L.whamd_poly_compare.argtypes = [C.POINTER(PolyCompareView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_poly_compare_job_count.restype = C.c_uint64
+    L.whamd_poly_compare_job_count.argtypes = [C.c_void_p]
+    L.whamd_poly_compare_path_count.restype = C.c_uint64
+    L.whamd_poly_compare_path_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_poly_compare_get.restype = C.c_int
+    L.whamd_poly_compare_get.argtypes = [C.c_void_p, C.POINTER(PolyCompareJobResult)]
+    L.whamd_poly_compare_get_path.restype = C.c_int
+    L.whamd_poly_compare_get_path.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                              C.POINTER(C.c_uint32)]
+    L.whamd_poly_compare_get_stats.restype = C.c_int
+    L.whamd_poly_compare_get_stats.argtypes = [C.c_void_p, C.POINTER(PolyCompareStats)]
+    L.whamd_poly_compare_destroy.restype = None
+    L.whamd_poly_compare_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -605,6 +640,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_reorder", "whamd_poly_reorder_problem_count", "whamd_poly_reorder_breakpoint_count", "whamd_poly_reorder_llh_count",
     "whamd_poly_reorder_window_count", "whamd_poly_reorder_get_llh", "whamd_poly_reorder_get_windows", "whamd_poly_reorder_get_phasing",
     "whamd_poly_reorder_get_stats", "whamd_poly_reorder_destroy",
+    "whamd_poly_compare", "whamd_poly_compare_job_count", "whamd_poly_compare_path_count", "whamd_poly_compare_get", "whamd_poly_compare_get_path",
+    "whamd_poly_compare_get_stats", "whamd_poly_compare_destroy",
 ]
 
 
