@@ -865,6 +865,87 @@ whamd_status_t whamd_poly_compare_get_path(const whamd_poly_compare_result* r, u
 whamd_status_t whamd_poly_compare_get_stats(const whamd_poly_compare_result* r, whamd_poly_compare_stats* stats_out);
 void whamd_poly_compare_destroy(whamd_poly_compare_result* r);
 
+/* ---- Haplotagphase votes and consensus (compute_votes, consensus, best_candidate of whatshap/cli/haplotagphase.py:347-395, 203-304) -----------
+ * `whatshap haplotagphase` phases the variants that are still unphased from reads that carry a phase set and a haplotype already.  One
+ * problem is one sample on one chromosome: per variant a flag byte, the reads as CSR of (variant index, id, quality) -- id the index, 0 or
+ * 1, of the read's allele in the sample's genotype vector at that variant -- and per read its phase set and haplotype, both reduced by 1
+ * as the reference does (PS_tag - 1, HP_tag - 1).
+ * Votes: a read with hp < 0 or ps < 0 is ignored; else one with hp > 1 is ignored and counted in n_skipped; every entry of any other read
+ * whose variant is not homozygous adds its quality (int64 sums) to votes[variant][(ps, hp ^ id)].  Choice, per voted variant: the key with
+ * the largest sum, ties to the phase set whose first voting entry at the variant comes first in the problem, within a phase set to
+ * haplotype 0; score = that sum, total = all sums of the variant.  total == 0 sets zero_total (ZeroDivisionError there) and keeps nothing.
+ * Filters, only where the variant is not phased: dropped if 100 * ((double)score / (double)total) < gap_threshold, or if only_indels and
+ * the variant is an SNV.  (The reference's homopolymer filter can drop nothing -- its length is capped at the threshold it must exceed --
+ * so no reference sequence is part of a problem.)
+ * Device (csrc/tagphase_device.hip): count per variant, scan, place every voting entry into its variant's run, one team per variant
+ * reduces and decides: 7 launches per call whatever the problems, 11 with a table; a call in which no entry votes launches nothing.
+ * Errors, all with nothing launched.  WHAMD_ERR_INVALID: a null array, read_ptr that decreases or does not start at 0, a variant index
+ * out of range, an id outside {0, 1}, flag bits above bit 2, a gap_threshold that is NaN.  WHAMD_ERR_UNSUPPORTED: the |quality| of a
+ * problem's voting entries sum to more than 2^53 (beyond it the fraction would no longer be Python's: never answered approximately);
+ * 2^32 - 1 or more variants or entries in one call; 2^30 or more phase sets in one problem. */
+#define WHAMD_TAGPHASE_HOMOZYGOUS 1u
+#define WHAMD_TAGPHASE_PHASED 2u
+#define WHAMD_TAGPHASE_SNV 4u
+
+typedef struct whamd_tagphase_view {
+	uint64_t n_variants;
+	const uint8_t* variant_flags;       /* [n_variants] WHAMD_TAGPHASE_* */
+	uint64_t n_reads;
+	const uint64_t* read_ptr;           /* [n_reads + 1] into the entry arrays */
+	const uint32_t* entry_variant;      /* [n_entries] index of the variant */
+	const uint8_t* entry_id;            /* [n_entries] 0 / 1 */
+	const int32_t* entry_quality;       /* [n_entries] */
+	const int64_t* read_ps;             /* [n_reads] PS_tag - 1 */
+	const int32_t* read_hp;             /* [n_reads] HP_tag - 1 */
+	double gap_threshold;
+	uint32_t only_indels;               /* 0 / 1 */
+	uint32_t want_table;                /* 0 / 1: keep every (phase set, sum0, sum1, first) row */
+} whamd_tagphase_view;
+
+typedef struct whamd_tagphase_stats {
+	uint64_t n_reads;
+	uint64_t n_variants;
+	uint64_t n_entries;
+	uint64_t n_voting;                  /* entries that vote */
+	uint64_t n_skipped;                 /* reads with ps >= 0 and hp > 1 */
+	uint64_t n_voted;                   /* variants with a vote */
+	uint64_t n_kept;
+	uint64_t n_zero_total;
+	uint64_t variants_class_a;          /* voted variants of 1 .. 64 voting entries: eight lanes each */
+	uint64_t variants_class_b;          /* 65 .. 4096: one wave each */
+	uint64_t variants_class_c;          /* more: one workgroup each */
+	uint64_t variants_many_phase_sets;  /* of them: more than 4 phase sets, one pass per phase set */
+	uint64_t table_rows;                /* 0 without want_table */
+	uint32_t launches;                  /* kernel launches of the whole call: 0, 7 or 11 */
+	double host_ms;                     /* wall, whole call: validation, phase sets to dense ids */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double total_ms;                    /* wall, whole call */
+} whamd_tagphase_stats;
+
+typedef struct whamd_tagphase_result whamd_tagphase_result; /* opaque: the result of one whamd_tagphase call */
+
+/* One call for a batch of problems (chromosomes x samples): one upload, a constant number of launches. */
+whamd_status_t whamd_tagphase(const whamd_tagphase_view* problems, uint64_t n_problems, int device, whamd_tagphase_result** out);
+uint64_t whamd_tagphase_problem_count(const whamd_tagphase_result* r);
+/* Variants of problem m. */
+uint64_t whamd_tagphase_count(const whamd_tagphase_result* r, uint64_t m);
+/* Per variant of problem m: voted (0 / 1); first, the index in the problem's entry arrays of its first voting entry (orders the
+ * reference's votes and components dicts; UINT64_MAX: not voted); n_phasesets; the winner's phase set (the caller's value) and haplotype;
+ * score; total; kept; zero_total.  NULL skips. */
+whamd_status_t whamd_tagphase_get(const whamd_tagphase_result* r, uint64_t m, uint8_t* voted_out, uint64_t* first_out, uint32_t* n_phasesets_out,
+                                  int64_t* best_ps_out, uint8_t* best_id_out, int64_t* score_out, int64_t* total_out, uint8_t* kept_out,
+                                  uint8_t* zero_total_out);
+/* The vote table of problem m (want_table): row_ptr_out [variants + 1]; per row the phase set, the sums of haplotype 0 and 1 and the
+ * index of the phase set's first voting entry at the variant; a variant's rows ascend in `first`.  NULL skips. */
+uint64_t whamd_tagphase_row_count(const whamd_tagphase_result* r, uint64_t m);
+whamd_status_t whamd_tagphase_get_table(const whamd_tagphase_result* r, uint64_t m, uint64_t* row_ptr_out, int64_t* ps_out, int64_t* sum0_out,
+                                        int64_t* sum1_out, uint64_t* first_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_tagphase_get_stats(const whamd_tagphase_result* r, uint64_t m, whamd_tagphase_stats* stats_out);
+void whamd_tagphase_destroy(whamd_tagphase_result* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,11 @@ whamd_status_t whamd_debug_poly_reorder_host(const whamd_poly_reorder_view* prob
  * nothing; what the CPU test-suite holds to the recorded reference.  Read with the whamd_poly_compare_* getters of the debug library. */
 whamd_status_t whamd_debug_poly_compare_host(const whamd_poly_compare_view* jobs, uint64_t n_jobs, whamd_poly_compare_result** out);
 
+/* HOST-ONLY DIAGNOSTICS of haplotagphase (csrc/tagphase.cpp): the same validation as whamd_tagphase, then every vote on one CPU thread
+ * with the device's selection function (csrc/tagphase.h) -- what the CPU test-suite holds to the recorded reference, identical in every
+ * field; never what the product calls.  Read with the whamd_tagphase_* getters of the debug library. */
+whamd_status_t whamd_debug_tagphase_host(const whamd_tagphase_view* problems, uint64_t n_problems, whamd_tagphase_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

@@ -212,6 +212,22 @@ class HaplotagStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class TagphaseView(C.Structure):
+    _fields_ = [("n_variants", C.c_uint64), ("variant_flags", C.POINTER(C.c_uint8)), ("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)),
+                ("entry_variant", C.POINTER(C.c_uint32)), ("entry_id", C.POINTER(C.c_uint8)), ("entry_quality", C.POINTER(C.c_int32)),
+                ("read_ps", C.POINTER(C.c_int64)), ("read_hp", C.POINTER(C.c_int32)), ("gap_threshold", C.c_double), ("only_indels", C.c_uint32),
+                ("want_table", C.c_uint32)]
+
+
+class TagphaseStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_variants", "n_entries", "n_voting", "n_skipped", "n_voted", "n_kept", "n_zero_total",
+                                                "variants_class_a", "variants_class_b", "variants_class_c", "variants_many_phase_sets", "table_rows")] + [
+        ("launches", C.c_uint32)] + [(name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class PolyReorderView(C.Structure):
     _fields_ = [("matrix", PolyMatrixView), ("ploidy", C.c_uint32), ("reserved", C.c_uint32), ("n_pos", C.c_uint64), ("haplotypes", C.POINTER(C.c_int8)),
                 ("threads", C.POINTER(C.c_int32)), ("n_clusters", C.c_uint64), ("cluster_ptr", C.POINTER(C.c_uint64)), ("cluster_reads", C.POINTER(C.c_uint32)),
@@ -407,6 +423,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_progeny_gl_host.argtypes = [C.POINTER(ProgenyDepthsView), C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_double))]
     L.whamd_debug_haplotag_host.restype = C.c_int
     L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_tagphase_host.restype = C.c_int
+    L.whamd_debug_tagphase_host.argtypes = [C.POINTER(TagphaseView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_reorder_host.restype = C.c_int
     L.whamd_debug_poly_reorder_host.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_compare_host.restype = C.c_int
@@ -611,6 +629,23 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_poly_compare_get_stats.argtypes = [C.c_void_p, C.POINTER(PolyCompareStats)]
     L.whamd_poly_compare_destroy.restype = None
     L.whamd_poly_compare_destroy.argtypes = [C.c_void_p]
+    L.whamd_tagphase.restype = C.c_int
+    L.whamd_tagphase.argtypes = [C.POINTER(TagphaseView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_tagphase_problem_count.restype = C.c_uint64
+    L.whamd_tagphase_problem_count.argtypes = [C.c_void_p]
+    for name in ("whamd_tagphase_count", "whamd_tagphase_row_count"):
+        getattr(L, name).restype = C.c_uint64
+        getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_tagphase_get.restype = C.c_int
+    L.whamd_tagphase_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+    L.whamd_tagphase_get_table.restype = C.c_int
+    L.whamd_tagphase_get_table.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_uint64)]
+    L.whamd_tagphase_get_stats.restype = C.c_int
+    L.whamd_tagphase_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(TagphaseStats)]
+    L.whamd_tagphase_destroy.restype = None
+    L.whamd_tagphase_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -642,6 +677,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_reorder_get_stats", "whamd_poly_reorder_destroy",
     "whamd_poly_compare", "whamd_poly_compare_job_count", "whamd_poly_compare_path_count", "whamd_poly_compare_get", "whamd_poly_compare_get_path",
     "whamd_poly_compare_get_stats", "whamd_poly_compare_destroy",
+    "whamd_tagphase", "whamd_tagphase_problem_count", "whamd_tagphase_count", "whamd_tagphase_get", "whamd_tagphase_row_count", "whamd_tagphase_get_table",
+    "whamd_tagphase_get_stats", "whamd_tagphase_destroy",
 ]
 
 

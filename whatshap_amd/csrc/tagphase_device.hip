@@ -1,0 +1,686 @@
+// tagphase_device.hip -- the votes and the consensus of haplotagphase on gfx950 (tagphase.h).  The reads arrive read-major, the sums are
+// per variant: a scatter.  It is done as a store pass and a per-destination sum, nothing is summed through global atomics:
+//   upload    per variant {flags | problem << 8}, per problem the gap threshold, per read {phase set << 1 | haplotype, first variant of its
+//             problem} and its first entry, the three entry arrays as the caller holds them (variant, id, quality).
+//   count     one thread per entry: its read (a search of the read offsets, narrowed to the reads of the workgroup's 256 entries), does it
+//             vote, and an integer atomic on the variant's counter -- one per run of neighbouring lanes that hit the same variant.
+//   scan      exclusive, two launches: tiles of 2048 counters (the tile's own prefix, the tile's total), then the totals by one workgroup.
+//             The first also appends every variant of more than 64 / 4096 entries to the class b / c list.
+//   place     one thread per entry again: a voting entry goes to run begin + atomic cursor of its variant as {phase set << 1 | (haplotype
+//             ^ id), quality, entry index}.  The order inside a run is whatever the atomics give; nothing below depends on it.
+//   reduce    one team per variant -- class a (0 .. 64 entries) eight lanes, over all variants; class b (.. 4096) one wave and class c one
+//             workgroup, both walking their list with a fixed grid.  A team keeps up to R = 4 phase sets in registers (sums of both
+//             haplotypes, smallest entry index); with more it takes one pass per phase set in the order of the ids.  Either way (sum0,
+//             sum1, phase set, first) go to tp_consider and the choice to tp_result (tagphase.h, shared with the host twin), which applies
+//             the consensus filters; one lane writes the variant's 32 bytes.
+//   rows      want_table only: the phase-set counts are scanned like the entry counts, the call waits once to size the table, then the
+//             pass-per-phase-set route writes every variant's rows (eight lanes for class a, one wave for the listed variants).
+// 7 launches per call, 11 with a table, whatever the problems, reads and variants (TP_LAUNCHES, TP_LAUNCHES_TABLE).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "device_runtime.h"
+#include "tagphase.h"
+
+namespace whamd {
+namespace {
+
+constexpr int R = (int)TP_REG_PHASESETS;
+constexpr int NW = (int)TP_BLOCK / 64;
+constexpr uint32_t PER_THREAD = TP_SCAN_TILE / TP_BLOCK;
+
+struct TpArgs {
+	// the image
+	const uint32_t* vinfo;        // [n_var]
+	const double* gap;            // [problems of the call]
+	const TpRead* reads;          // [n_reads]
+	const uint32_t* read_ptr;     // [n_reads + 1]
+	const uint32_t* entry_var;    // [n_entries] local to the read's problem
+	const uint8_t* entry_id;
+	const int32_t* entry_quality;
+	// made on the device
+	uint32_t* counts;             // [n_var] voting entries
+	uint32_t* cursor;             // [n_var] zero before place
+	uint32_t* local;              // [n_var] prefix of counts inside the tile
+	uint32_t* tile_sums;          // [tiles] exclusive after the second scan launch
+	uint32_t* list_n;             // [2] lengths of list b, list c
+	uint32_t* list_b;             // [n_var]
+	uint32_t* list_c;             // [n_var]
+	TpPlaced* placed;             // [n_placed]
+	TpOut* out;                   // [n_var]
+	uint32_t* nps;                // [n_var] phase sets per variant; nullptr: no table
+	uint32_t* nps_local;
+	uint32_t* nps_tile_sums;
+	uint32_t* n_rows;             // [1]
+	TpRow* rows;
+	uint32_t n_var, n_reads, n_entries, n_placed, a_max, b_max;
+};
+
+__device__ inline uint32_t run_begin(const uint32_t* local, const uint32_t* tile_sums, uint32_t v) { return local[v] + tile_sums[v / TP_SCAN_TILE]; }
+
+// ---------------------------------------------------------------------------------------------- count, place
+// The largest r in [lo, hi] with read_ptr[r] <= i (read_ptr[lo] <= i).
+__device__ inline uint32_t find_read(const uint32_t* read_ptr, uint32_t lo, uint32_t hi, uint32_t i) {
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo + 1) / 2;
+		if (read_ptr[mid] <= i) lo = mid;
+		else hi = mid - 1;
+	}
+	return lo;
+}
+
+// Entry i of the call: the variant it votes at (TP_NONE: it does not vote) and the key it votes for.
+__device__ inline uint32_t voting_variant(const TpArgs& a, uint32_t i, uint32_t& key) {
+	key = 0;
+	if (i >= a.n_entries) return TP_NONE;
+	const uint32_t i0 = blockIdx.x * TP_BLOCK, i1 = min(i0 + TP_BLOCK - 1, a.n_entries - 1);
+	const uint32_t lo = find_read(a.read_ptr, 0, a.n_reads - 1, i0), hi = find_read(a.read_ptr, lo, a.n_reads - 1, i1);
+	const TpRead rd = a.reads[find_read(a.read_ptr, lo, hi, i)];
+	if (rd.code == TP_NOT_COUNTED) return TP_NONE;
+	const uint32_t v = rd.var_base + a.entry_var[i];
+	if (v >= a.n_var || (a.vinfo[v] & TP_HOMOZYGOUS)) return TP_NONE;
+	key = rd.code ^ (uint32_t)(a.entry_id[i] & 1u);
+	return v;
+}
+
+// Neighbouring lanes of a wave with the same variant form a run: its first lane and its length.  Every lane of the wave calls this.
+__device__ inline void lane_run(uint32_t v, uint32_t lane, uint32_t& head_lane, uint32_t& length) {
+	const uint32_t prev = (uint32_t)__shfl_up((int)v, 1);
+	const uint64_t heads = __ballot(lane == 0 || v != prev);
+	head_lane = 63u - (uint32_t)__clzll((long long)(heads & ((2ull << lane) - 1)));
+	const uint64_t rest = head_lane == 63u ? 0ull : heads >> (head_lane + 1);
+	const uint32_t next = rest ? head_lane + (uint32_t)__ffsll((unsigned long long)rest) : 64u;
+	length = next - head_lane;
+}
+
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_count_kernel(TpArgs a) {
+	const uint32_t i = blockIdx.x * TP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
+	uint32_t key, head_lane, length;
+	const uint32_t v = voting_variant(a, i, key);
+	lane_run(v, lane, head_lane, length);
+	if (v != TP_NONE && lane == head_lane) atomicAdd(a.counts + v, length);
+}
+
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_place_kernel(TpArgs a) {
+	const uint32_t i = blockIdx.x * TP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
+	uint32_t key, head_lane, length;
+	const uint32_t v = voting_variant(a, i, key);
+	lane_run(v, lane, head_lane, length);
+	uint32_t base = 0;
+	if (v != TP_NONE && lane == head_lane) base = atomicAdd(a.cursor + v, length);
+	base = (uint32_t)__shfl((int)base, (int)head_lane);
+	if (v == TP_NONE) return;
+	const uint32_t at = run_begin(a.local, a.tile_sums, v) + base + (lane - head_lane);
+	if (at < a.n_placed) a.placed[at] = TpPlaced{key, a.entry_quality[i], i};
+}
+
+// ---------------------------------------------------------------------------------------------- scan
+__device__ inline uint32_t wave_inclusive(uint32_t v, uint32_t lane) {
+#pragma unroll
+	for (int o = 1; o < 64; o <<= 1) {
+		const uint32_t up = (uint32_t)__shfl_up((int)v, o);
+		if (lane >= (uint32_t)o) v += up;
+	}
+	return v;
+}
+
+// The workgroup's exclusive prefix of `mine` (one value per thread, in thread order) and the workgroup's total.
+__device__ inline uint32_t block_exclusive(uint32_t mine, uint32_t* wave_total, uint32_t& total) {
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	const uint32_t inc = wave_inclusive(mine, lane);
+	if (lane == 63) wave_total[w] = inc;
+	__syncthreads();
+	uint32_t before = 0;
+	total = 0;
+#pragma unroll
+	for (int ww = 0; ww < NW; ww++) {
+		if ((uint32_t)ww < w) before += wave_total[ww];
+		total += wave_total[ww];
+	}
+	__syncthreads();
+	return before + inc - mine;
+}
+
+// in[n] -> local[n] (prefix inside the tile), tile_sums[tile] (the tile's total).  With lists: the variants beyond class a are appended.
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_scan_tiles_kernel(const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n, uint32_t* list_n,
+                                                                       uint32_t* list_b, uint32_t* list_c, uint32_t a_max, uint32_t b_max) {
+	__shared__ uint32_t wave_total[NW];
+	const uint32_t base = blockIdx.x * TP_SCAN_TILE + threadIdx.x * PER_THREAD;
+	uint32_t val[PER_THREAD], mine = 0;
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		val[k] = base + k < n ? in[base + k] : 0;
+		mine += val[k];
+	}
+	uint32_t total;
+	uint32_t at = block_exclusive(mine, wave_total, total);
+#pragma unroll
+	for (uint32_t k = 0; k < PER_THREAD; k++) {
+		if (base + k < n) {
+			local[base + k] = at;
+			if (list_n && val[k] > a_max) {
+				if (val[k] <= b_max) list_b[atomicAdd(list_n, 1u)] = base + k;
+				else list_c[atomicAdd(list_n + 1, 1u)] = base + k;
+			}
+		}
+		at += val[k];
+	}
+	if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// tile_sums[n_tiles] exclusive in place by one workgroup; *total_out, if wanted, the sum of all.
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_scan_sums_kernel(uint32_t* tile_sums, uint32_t n_tiles, uint32_t* total_out) {
+	__shared__ uint32_t wave_total[NW];
+	uint32_t carry = 0;
+	for (uint32_t base = 0; base < n_tiles; base += TP_BLOCK) {
+		const uint32_t x = base + threadIdx.x;
+		const uint32_t mine = x < n_tiles ? tile_sums[x] : 0;
+		uint32_t total;
+		const uint32_t before = block_exclusive(mine, wave_total, total);
+		if (x < n_tiles) tile_sums[x] = carry + before;
+		carry += total;
+	}
+	if (total_out && threadIdx.x == 0) *total_out = carry;
+}
+
+// ---------------------------------------------------------------------------------------------- reduce and decide
+struct Slots {
+	int64_t s[R][2];
+	uint32_t ps[R], first[R];
+	uint32_t n;
+	bool overflow;
+};
+
+template <int W>
+__device__ inline int64_t team_sum(int64_t v) {
+#pragma unroll
+	for (int o = W / 2; o; o >>= 1) v += __shfl_xor(v, o);
+	return v;
+}
+template <int W>
+__device__ inline uint32_t team_min(uint32_t v) {
+#pragma unroll
+	for (int o = W / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+	return v;
+}
+
+// Placed entry i of the run, or nothing (ps = TP_NONE) beyond it.
+__device__ inline void load_placed(const TpPlaced* run, uint32_t i, uint32_t n, bool on, uint32_t& ps, uint32_t& hap, int64_t& q, uint32_t& index) {
+	ps = TP_NONE;
+	hap = 0;
+	q = 0;
+	index = TP_NONE;
+	if (on && i < n) {
+		const TpPlaced e = run[i];
+		ps = e.key >> 1;
+		hap = e.key & 1u;
+		q = (int64_t)e.quality;
+		index = e.index;
+	}
+}
+
+// The register route over run[0, n) by the W lanes of a team (lane l of the team, the team's lanes `teammask`, its first lane `lane0`).
+// Every lane of the wave calls this together; n is the team's.
+template <int W>
+__device__ inline void scan_run(const TpPlaced* run, uint32_t n, uint32_t l, uint64_t teammask, uint32_t lane0, Slots& S) {
+	S.n = 0;
+	S.overflow = false;
+#pragma unroll
+	for (int s = 0; s < R; s++) {
+		S.ps[s] = TP_NONE;
+		S.first[s] = TP_NONE;
+		S.s[s][0] = S.s[s][1] = 0;
+	}
+	for (uint32_t base = 0; __any(base < n && !S.overflow); base += W) {   // (a team that has overflowed takes the other route: its sums are not used)
+		uint32_t ps, hap, index;
+		int64_t q;
+		load_placed(run, base + l, n, !S.overflow, ps, hap, q, index);
+		const bool valid = ps != TP_NONE;
+		int slot = -1;
+#pragma unroll
+		for (int s = 0; s < R; s++)
+			if (valid && S.ps[s] == ps) slot = s;
+		for (;;) {
+			const uint64_t un = __ballot(valid && slot < 0 && !S.overflow) & teammask;
+			if (!__any(un != 0)) break;
+			const uint32_t src = un ? (uint32_t)__ffsll((unsigned long long)un) - 1 : lane0 + l;
+			const uint32_t fresh = (uint32_t)__shfl((int)ps, (int)src);
+			if (un) {
+				if (S.n < (uint32_t)R) {
+#pragma unroll
+					for (int s = 0; s < R; s++)
+						if (S.n == (uint32_t)s) S.ps[s] = fresh;
+					if (valid && ps == fresh) slot = (int)S.n;
+					S.n++;
+				} else {
+					S.overflow = true;
+				}
+			}
+		}
+#pragma unroll
+		for (int s = 0; s < R; s++) {
+			const bool here = slot == s;
+			S.s[s][0] += (here && hap == 0) ? q : 0;
+			S.s[s][1] += (here && hap == 1) ? q : 0;
+			S.first[s] = here ? min(S.first[s], index) : S.first[s];
+		}
+	}
+#pragma unroll
+	for (int s = 0; s < R; s++)
+		if (__any(S.n > (uint32_t)s)) {
+			S.s[s][0] = team_sum<W>(S.s[s][0]);
+			S.s[s][1] = team_sum<W>(S.s[s][1]);
+			S.first[s] = team_min<W>(S.first[s]);
+		}
+}
+
+// Who owns a variant on the pass-per-phase-set route: how far apart its lanes' entries lie and how they combine a minimum and a phase set's sums.
+template <int W>
+struct TeamScope {
+	static constexpr uint32_t STRIDE = W;
+	__device__ uint32_t all_min(uint32_t v) const { return team_min<W>(v); }
+	__device__ void all_sums(int64_t (&sums)[2], uint32_t& first) const {
+		sums[0] = team_sum<W>(sums[0]);
+		sums[1] = team_sum<W>(sums[1]);
+		first = team_min<W>(first);
+	}
+};
+struct BlockScope {   // (one variant per workgroup: every thread takes the same branches, so the barriers are met by all)
+	static constexpr uint32_t STRIDE = TP_BLOCK;
+	uint32_t* word;          // LDS [NW]
+	int64_t (*part)[2];      // LDS [NW][2]
+	uint32_t lane, w;
+	__device__ uint32_t all_min(uint32_t v) const {
+		v = team_min<64>(v);
+		if (lane == 0) word[w] = v;
+		__syncthreads();
+		v = word[0];
+#pragma unroll
+		for (int ww = 1; ww < NW; ww++) v = min(v, word[ww]);
+		__syncthreads();
+		return v;
+	}
+	__device__ void all_sums(int64_t (&sums)[2], uint32_t& first) const {
+		sums[0] = team_sum<64>(sums[0]);
+		sums[1] = team_sum<64>(sums[1]);
+		first = team_min<64>(first);
+		if (lane == 0) {
+			word[w] = first;
+			part[w][0] = sums[0];
+			part[w][1] = sums[1];
+		}
+		__syncthreads();
+		first = word[0];
+		sums[0] = part[0][0];
+		sums[1] = part[0][1];
+#pragma unroll
+		for (int ww = 1; ww < NW; ww++) {
+			first = min(first, word[ww]);
+			sums[0] += part[ww][0];
+			sums[1] += part[ww][1];
+		}
+		__syncthreads();
+	}
+};
+
+// The pass-per-phase-set route for the owners with `need` (the other teams of the wave walk along idle): phase sets in id order, per
+// phase set one pass for the next id and one for its sums and first entry.  Lane l of the owner takes entries l, l + STRIDE, ...
+// rows: where the owner's `leader` lane writes one row per phase set, at most max_rows (nullptr: none).
+template <class Scope>
+__device__ inline void pass_per_phase_set(const TpPlaced* run, uint32_t n, uint32_t l, bool need, const Scope& scope, TpBest& best, TpRow* rows, uint32_t max_rows, bool leader) {
+	bool active = need;
+	uint32_t lower = 0, n_rows = 0;
+	while (__any(active)) {
+		uint32_t next = TP_NONE;
+		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
+			uint32_t ps, hap, index;
+			int64_t q;
+			load_placed(run, base + l, n, active, ps, hap, q, index);
+			if (ps != TP_NONE && ps >= lower) next = min(next, ps);
+		}
+		next = scope.all_min(next);
+		if (next == TP_NONE) active = false;
+		int64_t sums[2] = {0, 0};
+		uint32_t first = TP_NONE;
+		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
+			uint32_t ps, hap, index;
+			int64_t q;
+			load_placed(run, base + l, n, active, ps, hap, q, index);
+			if (ps != TP_NONE && ps == next) {
+				first = min(first, index);
+				sums[0] += hap == 0 ? q : 0;
+				sums[1] += hap == 1 ? q : 0;
+			}
+		}
+		scope.all_sums(sums, first);
+		if (active) {
+			tp_consider(best, sums[0], sums[1], next, first);
+			if (rows && leader && n_rows < max_rows) rows[n_rows] = TpRow{sums[0], sums[1], next, first, {0, 0}};
+			n_rows++;
+			lower = next + 1;
+		}
+	}
+}
+
+__device__ inline void write_result(const TpArgs& a, uint32_t v, const TpBest& best) {
+	const uint32_t info = a.vinfo[v];
+	a.out[v] = tp_result(best, info, a.gap[info >> 8]);
+	if (a.nps) a.nps[v] = best.n_ps;
+}
+
+// A team of W lanes reduces the run of variant v (have: the team has one) and its first lane writes the result.
+template <int W>
+__device__ inline void reduce_by_team(const TpArgs& a, uint32_t v, bool have, uint32_t l, uint32_t lane) {
+	const uint32_t lane0 = lane - l;
+	const uint64_t teammask = (W == 64 ? ~0ull : ((1ull << W) - 1)) << lane0;
+	const uint32_t n = have ? a.counts[v] : 0;
+	const TpPlaced* run = a.placed + (have ? run_begin(a.local, a.tile_sums, v) : 0);
+	Slots S;
+	scan_run<W>(run, n, l, teammask, lane0, S);
+	TpBest best = tp_start();
+	if (!S.overflow) {
+#pragma unroll
+		for (int s = 0; s < R; s++)
+			if ((uint32_t)s < S.n) tp_consider(best, S.s[s][0], S.s[s][1], S.ps[s], S.first[s]);
+	}
+	if (__any(S.overflow)) pass_per_phase_set(run, n, l, S.overflow, TeamScope<W>{}, best, nullptr, 0, false);
+	if (have && l == 0) write_result(a, v, best);
+}
+
+// Class a: eight lanes per variant, over all variants; those of more entries are left to the lists.
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_a_kernel(TpArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, l = threadIdx.x & (TP_SEGMENT - 1);
+	const uint64_t v64 = (uint64_t)blockIdx.x * (TP_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
+	const bool have = v64 < a.n_var && a.counts[v64] <= a.a_max;
+	reduce_by_team<(int)TP_SEGMENT>(a, (uint32_t)v64, have, l, lane);
+}
+
+// Class b: one wave per listed variant.
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_b_kernel(TpArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, n_list = a.list_n[0];
+	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW) reduce_by_team<64>(a, a.list_b[k], true, lane, lane);
+}
+
+// Class c: one workgroup per listed variant; every wave takes a contiguous quarter of the run, the quarters meet in LDS.
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
+	__shared__ int64_t w_sums[NW][R][2];
+	__shared__ uint32_t w_ps[NW][R], w_first[NW][R], w_n[NW], w_overflow[NW];
+	__shared__ int64_t r_sums[NW][2];
+	__shared__ uint32_t r_word[NW];
+	__shared__ uint32_t go_slow;
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, n_list = a.list_n[1];
+	for (uint32_t k = blockIdx.x; k < n_list; k += gridDim.x) {
+		const uint32_t v = a.list_c[k], n = a.counts[v];
+		const TpPlaced* run = a.placed + run_begin(a.local, a.tile_sums, v);
+		const uint32_t per = ((n + NW - 1) / NW + 63u) & ~63u;
+		const uint64_t b64 = (uint64_t)w * per;
+		const uint32_t begin = (uint32_t)min(b64, (uint64_t)n), end = (uint32_t)min(b64 + per, (uint64_t)n);
+		Slots S;
+		scan_run<64>(run + begin, end - begin, lane, ~0ull, 0, S);
+		if (lane == 0) {
+			w_n[w] = S.n;
+			w_overflow[w] = S.overflow;
+#pragma unroll
+			for (int s = 0; s < R; s++) {
+				w_ps[w][s] = S.ps[s];
+				w_first[w][s] = S.first[s];
+				w_sums[w][s][0] = S.s[s][0];
+				w_sums[w][s][1] = S.s[s][1];
+			}
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			// merge the waves' slots by phase set; more than R distinct ones: the slower route
+			uint32_t m_ps[R], m_first[R], m_n = 0;
+			int64_t m_sums[R][2];
+			bool slow = false;
+			for (int ww = 0; ww < NW && !slow; ww++) {
+				if (w_overflow[ww]) slow = true;
+				for (uint32_t s = 0; s < w_n[ww] && !slow; s++) {
+					uint32_t at = m_n;
+					for (uint32_t y = 0; y < m_n; y++)
+						if (m_ps[y] == w_ps[ww][s]) at = y;
+					if (at == m_n) {
+						if (m_n == (uint32_t)R) {
+							slow = true;
+							break;
+						}
+						m_ps[at] = w_ps[ww][s];
+						m_first[at] = TP_NONE;
+						m_sums[at][0] = m_sums[at][1] = 0;
+						m_n++;
+					}
+					m_first[at] = min(m_first[at], w_first[ww][s]);
+					m_sums[at][0] += w_sums[ww][s][0];
+					m_sums[at][1] += w_sums[ww][s][1];
+				}
+			}
+			go_slow = slow;
+			if (!slow) {
+				TpBest best = tp_start();
+				for (uint32_t y = 0; y < m_n; y++) tp_consider(best, m_sums[y][0], m_sums[y][1], m_ps[y], m_first[y]);
+				write_result(a, v, best);
+			}
+		}
+		__syncthreads();
+		if (go_slow) {
+			TpBest best = tp_start();
+			pass_per_phase_set(run, n, threadIdx.x, true, BlockScope{r_word, r_sums, lane, w}, best, nullptr, 0, false);
+			if (threadIdx.x == 0) write_result(a, v, best);
+		}
+		__syncthreads();
+	}
+}
+
+// ---------------------------------------------------------------------------------------------- table rows
+__device__ inline uint32_t row_begin(const TpArgs& a, uint32_t v) { return run_begin(a.nps_local, a.nps_tile_sums, v); }
+
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_rows_a_kernel(TpArgs a) {
+	const uint32_t l = threadIdx.x & (TP_SEGMENT - 1);
+	const uint64_t v64 = (uint64_t)blockIdx.x * (TP_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
+	const bool have = v64 < a.n_var && a.counts[v64] <= a.a_max && a.counts[v64] > 0;
+	const uint32_t v = (uint32_t)v64;
+	TpBest best = tp_start();
+	pass_per_phase_set(a.placed + (have ? run_begin(a.local, a.tile_sums, v) : 0), have ? a.counts[v] : 0, l, have, TeamScope<(int)TP_SEGMENT>{}, best,
+	                   a.rows + (have ? row_begin(a, v) : 0), have ? a.nps[v] : 0, l == 0);
+}
+
+__global__ void __launch_bounds__(TP_BLOCK) tagphase_rows_list_kernel(TpArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, n_b = a.list_n[0], n_list = n_b + a.list_n[1];
+	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW) {
+		const uint32_t v = k < n_b ? a.list_b[k] : a.list_c[k - n_b];
+		TpBest best = tp_start();
+		pass_per_phase_set(a.placed + run_begin(a.local, a.tile_sums, v), a.counts[v], lane, true, TeamScope<64>{}, best, a.rows + row_begin(a, v), a.nps[v], lane == 0);
+	}
+}
+
+}  // namespace
+
+whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int device, std::vector<TagphaseScores>& out, CallTimes& times, std::string& msg) {
+	times = CallTimes{};
+	out.assign(ps.size(), TagphaseScores{});
+	// the problems with a voting entry are the call's: their variants, reads and entries one after the other
+	std::vector<uint64_t> var_base(ps.size() + 1, 0), read_base(ps.size() + 1, 0), ent_base(ps.size() + 1, 0), slot(ps.size() + 1, 0);
+	uint64_t n_placed = 0;
+	bool want_table = false;
+	for (size_t x = 0; x < ps.size(); x++) {
+		const bool in = ps[x].n_voting > 0;
+		var_base[x + 1] = var_base[x] + (in ? ps[x].n_variants : 0);
+		read_base[x + 1] = read_base[x] + (in ? ps[x].n_reads : 0);
+		ent_base[x + 1] = ent_base[x] + (in ? ps[x].n_entries : 0);
+		slot[x + 1] = slot[x] + (in ? 1 : 0);
+		n_placed += ps[x].n_voting;
+		want_table = want_table || (in && ps[x].want_table);
+	}
+	const uint64_t n_var = var_base[ps.size()], n_reads = read_base[ps.size()], n_entries = ent_base[ps.size()], n_in = slot[ps.size()];
+	if (!n_placed) return WHAMD_OK;   // nothing votes: no device work at all
+	if (n_var >= 0xfffff000ull || n_entries >= 0xfffff000ull || n_in >= (1ull << 24)) {   // (indices are uint32 with room to round grids up)
+		msg = "2^32 - 4096 or more variants or entries, or 2^24 or more problems, in one call";
+		return WHAMD_ERR_UNSUPPORTED;
+	}
+	const uint32_t n_tiles = (uint32_t)((n_var + TP_SCAN_TILE - 1) / TP_SCAN_TILE);
+	ImageLayout in;
+	const auto p_vinfo = in.add<uint32_t>(n_var);
+	const auto p_gap = in.add<double>(n_in);
+	const auto p_reads = in.add<TpRead>(n_reads);
+	const auto p_rptr = in.add<uint32_t>(n_reads + 1);
+	const auto p_evar = in.add<uint32_t>(n_entries);
+	const auto p_eq = in.add<int32_t>(n_entries);
+	const auto p_eid = in.add<uint8_t>(n_entries);
+	// what the kernels make: the zeroed words first
+	ImageLayout work;
+	const auto w_counts = work.add<uint32_t>(n_var);
+	const auto w_cursor = work.add<uint32_t>(n_var);
+	const auto w_listn = work.add<uint32_t>(4);   // list lengths, the number of rows
+	const size_t zeroed = work.total;
+	const auto w_local = work.add<uint32_t>(n_var);
+	const auto w_tiles = work.add<uint32_t>(n_tiles);
+	const auto w_list_b = work.add<uint32_t>(n_var);
+	const auto w_list_c = work.add<uint32_t>(n_var);
+	const auto w_nps = work.add<uint32_t>(want_table ? n_var : 0);
+	const auto w_nps_local = work.add<uint32_t>(want_table ? n_var : 0);
+	const auto w_nps_tiles = work.add<uint32_t>(want_table ? n_tiles : 0);
+	const auto w_placed = work.add<TpPlaced>(n_placed);
+	const auto w_out = work.add<TpOut>(n_var);
+	Session s;
+	whamd_status_t st = s.open(device, 4, msg);
+	if (st != WHAMD_OK) return st;
+	Image im, wk;
+	char* dev_work = nullptr;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
+	wk.base = dev_work;
+	wk.total = work.total;
+	TpOut* res_out = nullptr;
+	uint32_t* res_counts = nullptr;
+	uint32_t* res_rows_n = nullptr;
+	if ((st = s.pinned_block(n_var * sizeof(TpOut), (void**)&res_out, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(n_var * sizeof(uint32_t), (void**)&res_counts, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(sizeof(uint32_t), (void**)&res_rows_n, msg)) != WHAMD_OK) return st;
+	// the image: per variant and per read a few words; the entry arrays are copied as they are
+	for (size_t x = 0; x < ps.size(); x++) {
+		const TagphaseProblem& p = ps[x];
+		if (!p.n_voting) continue;
+		const whamd_tagphase_view& v = *p.view;
+		const uint32_t bits = (v.only_indels ? (uint32_t)TP_ONLY_INDELS : 0u) | ((uint32_t)slot[x] << 8);
+		im.host(p_gap)[slot[x]] = v.gap_threshold;
+		uint32_t* vinfo = im.host(p_vinfo) + var_base[x];
+		for (uint64_t y = 0; y < p.n_variants; y++) vinfo[y] = v.variant_flags[y] | bits;
+		TpRead* reads = im.host(p_reads) + read_base[x];
+		uint32_t* rptr = im.host(p_rptr) + read_base[x];
+		for (uint64_t r = 0; r < p.n_reads; r++) {
+			reads[r] = TpRead{p.read_code[r], (uint32_t)var_base[x]};
+			rptr[r] = (uint32_t)(ent_base[x] + v.read_ptr[r]);
+		}
+		const uint64_t chunk = (uint64_t)1 << 20, n_chunks = (p.n_entries + chunk - 1) / chunk;
+		parallel_ranges(n_chunks, host_threads(p.n_entries, 1 << 20), [&](uint64_t b, uint64_t e, uint32_t) {
+			const uint64_t from = b * chunk, n = std::min(e * chunk, p.n_entries) - from;
+			std::memcpy(im.host(p_evar) + ent_base[x] + from, v.entry_variant + from, n * sizeof(uint32_t));
+			std::memcpy(im.host(p_eq) + ent_base[x] + from, v.entry_quality + from, n * sizeof(int32_t));
+			std::memcpy(im.host(p_eid) + ent_base[x] + from, v.entry_id + from, n);
+		});
+	}
+	im.host(p_rptr)[n_reads] = (uint32_t)n_entries;
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	HIP_TRY(hipMemsetAsync(dev_work, 0, zeroed, s.stream));
+	TpArgs a{};
+	a.vinfo = im.dev(p_vinfo);
+	a.gap = im.dev(p_gap);
+	a.reads = im.dev(p_reads);
+	a.read_ptr = im.dev(p_rptr);
+	a.entry_var = im.dev(p_evar);
+	a.entry_id = im.dev(p_eid);
+	a.entry_quality = im.dev(p_eq);
+	a.counts = wk.dev_out(w_counts);
+	a.cursor = wk.dev_out(w_cursor);
+	a.list_n = wk.dev_out(w_listn);
+	a.n_rows = a.list_n + 2;
+	a.local = wk.dev_out(w_local);
+	a.tile_sums = wk.dev_out(w_tiles);
+	a.list_b = wk.dev_out(w_list_b);
+	a.list_c = wk.dev_out(w_list_c);
+	a.nps = want_table ? wk.dev_out(w_nps) : nullptr;
+	a.nps_local = want_table ? wk.dev_out(w_nps_local) : nullptr;
+	a.nps_tile_sums = want_table ? wk.dev_out(w_nps_tiles) : nullptr;
+	a.placed = wk.dev_out(w_placed);
+	a.out = wk.dev_out(w_out);
+	a.rows = nullptr;
+	a.n_var = (uint32_t)n_var;
+	a.n_reads = (uint32_t)n_reads;
+	a.n_entries = (uint32_t)n_entries;
+	a.n_placed = (uint32_t)n_placed;
+	a.a_max = TP_CLASS_A_MAX;
+	a.b_max = TP_CLASS_B_MAX;
+	const dim3 block(TP_BLOCK);
+	const dim3 per_entry((uint32_t)((n_entries + TP_BLOCK - 1) / TP_BLOCK)), per_segment((uint32_t)((n_var + TP_BLOCK / TP_SEGMENT - 1) / (TP_BLOCK / TP_SEGMENT)));
+#define TP_LAUNCH(kernel, grid, ...)                                         \
+	do {                                                                     \
+		hipLaunchKernelGGL(kernel, grid, block, 0, s.stream, __VA_ARGS__);   \
+		HIP_TRY(hipGetLastError());                                          \
+		++times.launches;                                                    \
+	} while (0)
+	TP_LAUNCH(tagphase_count_kernel, per_entry, a);
+	TP_LAUNCH(tagphase_scan_tiles_kernel, dim3(n_tiles), a.counts, a.local, a.tile_sums, a.n_var, a.list_n, a.list_b, a.list_c, a.a_max, a.b_max);
+	TP_LAUNCH(tagphase_scan_sums_kernel, dim3(1), a.tile_sums, n_tiles, (uint32_t*)nullptr);
+	TP_LAUNCH(tagphase_place_kernel, per_entry, a);
+	TP_LAUNCH(tagphase_reduce_a_kernel, per_segment, a);
+	TP_LAUNCH(tagphase_reduce_b_kernel, dim3(TP_LIST_GRID), a);
+	TP_LAUNCH(tagphase_reduce_c_kernel, dim3(TP_LIST_GRID), a);
+	TpRow* res_rows = nullptr;
+	uint64_t n_rows = 0;
+	if (want_table) {
+		TP_LAUNCH(tagphase_scan_tiles_kernel, dim3(n_tiles), (const uint32_t*)a.nps, a.nps_local, a.nps_tile_sums, a.n_var, (uint32_t*)nullptr, (uint32_t*)nullptr,
+		          (uint32_t*)nullptr, 0u, 0u);
+		TP_LAUNCH(tagphase_scan_sums_kernel, dim3(1), a.nps_tile_sums, n_tiles, a.n_rows);
+		// the one wait in the middle of the call: the table's size
+		if ((st = s.fetch(res_rows_n, a.n_rows, sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+		HIP_TRY(hipStreamSynchronize(s.stream));
+		n_rows = *res_rows_n;
+		if (n_rows > n_placed) {
+			msg = "internal error: more table rows than voting entries";
+			return WHAMD_ERR_DEVICE;
+		}
+		if ((st = s.device_block(n_rows * sizeof(TpRow), (void**)&a.rows, msg)) != WHAMD_OK) return st;
+		if ((st = s.pinned_block(n_rows * sizeof(TpRow), (void**)&res_rows, msg)) != WHAMD_OK) return st;
+		TP_LAUNCH(tagphase_rows_a_kernel, per_segment, a);
+		TP_LAUNCH(tagphase_rows_list_kernel, dim3(TP_LIST_GRID), a);
+	}
+#undef TP_LAUNCH
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_out, a.out, n_var * sizeof(TpOut), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_counts, a.counts, n_var * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if (n_rows && (st = s.fetch(res_rows, a.rows, n_rows * sizeof(TpRow), msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	// back to the problems: entry indices become local to each
+	uint64_t row_at = 0;
+	for (size_t x = 0; x < ps.size(); x++) {
+		const TagphaseProblem& p = ps[x];
+		if (!p.n_voting) continue;
+		TagphaseScores& sc = out[x];
+		sc.out.assign(res_out + var_base[x], res_out + var_base[x + 1]);
+		sc.count.assign(res_counts + var_base[x], res_counts + var_base[x + 1]);
+		const uint32_t eb = (uint32_t)ent_base[x];
+		for (TpOut& o : sc.out)
+			if (o.flags & TP_VOTED) o.first -= eb;
+		if (!want_table) continue;
+		sc.row_ptr.assign(p.n_variants + 1, 0);
+		for (uint64_t y = 0; y < p.n_variants; y++) sc.row_ptr[y + 1] = sc.row_ptr[y] + sc.out[y].n_ps;
+		const uint64_t mine = sc.row_ptr[p.n_variants];
+		if (row_at + mine > n_rows) {
+			msg = "internal error: the table's rows and the phase-set counts disagree";
+			return WHAMD_ERR_DEVICE;
+		}
+		if (p.want_table) {
+			sc.rows.assign(res_rows + row_at, res_rows + row_at + mine);
+			for (TpRow& row : sc.rows) row.first -= eb;
+		} else {
+			sc.row_ptr.clear();
+		}
+		row_at += mine;
+	}
+	return WHAMD_OK;
+}
+
+}  // namespace whamd
