@@ -946,6 +946,78 @@ whamd_status_t whamd_tagphase_get_table(const whamd_tagphase_result* r, uint64_t
 whamd_status_t whamd_tagphase_get_stats(const whamd_tagphase_result* r, uint64_t m, whamd_tagphase_stats* stats_out);
 void whamd_tagphase_destroy(whamd_tagphase_result* r);
 
+/* ---- Prior genotype likelihoods (compute_genotypes of src/genotyper.cpp, core.pyx:603; the loop of whatshap/cli/genotype.py:245-262) ---------
+ * The first compute step of `whatshap genotype`: for every position of the list, the distribution over the genotypes 0/0, 0/1, 1/1 that
+ * all reads of the sample give it; it becomes the prior of the genotyping table.  One problem is one sample on one chromosome: the
+ * position list and the reads as CSR of (position, allele, quality).
+ * Which entries count: for position c, in read order, every read with an entry at positions[c] whose allele is 0 or 1.  Other alleles
+ * and entries at positions that are not in the list are passed over.
+ * The chain: from (1/3, 1/3, 1/3); per entry p = max(0.05, pow(10.0, -(double)quality / 10.0)), allele 0 multiplies by
+ * (2.0/3.0 - 1.0/3.0*p, 1.0/3.0, 1.0/3.0*p), allele 1 by the mirror image, then sum = 0.0 + d0 + d1 + d2 and d[i] /= sum; every operation
+ * rounds on its own.  After the last entry the same sum once more (<= 0: three thirds).  The genotype is the first index with the
+ * largest value if the other two, added in index order to 0.0, stay below 0.1; else none (-1).
+ * The result depends on the order of the entries (double rounding), so the device orders every run by entry index before one lane walks
+ * it: the output is bit for bit the reference's, and independent of the order in which the device's atomics arrive.
+ * want_regularized: norm_sum = g0 + g1 + g2 + 3 * constant (left to right), reg[i] = (g[i] + constant) / norm_sum; reg_genotype = the
+ * index of the largest reg if it is strictly greater than the second largest and than gt_prob, else -1.
+ * Device (csrc/priorgt_device.hip): count per column, scan, place, order the runs (three classes by length; the last takes any length),
+ * chain: WHAMD_PRIOR_GENOTYPES_LAUNCHES launches per call whatever the problems; a call without a counted entry launches nothing.
+ * Errors, all with nothing launched.  WHAMD_ERR_INVALID (the message names the read): a read without entries; a read whose positions
+ * are not strictly increasing; a read whose first position is smaller than that of the read before it; a read whose first or last
+ * position is not in `positions`; also positions that are not strictly increasing (a duplicate, or a list that is not sorted: the
+ * reference's iterator needs the order), a null array, read_ptr that decreases or does not start at 0, a constant that is negative or
+ * NaN, a gt_prob that is NaN.  WHAMD_ERR_UNSUPPORTED: 2^32 - 4096 or more positions or entries in one call. */
+#define WHAMD_PRIOR_GENOTYPES_LAUNCHES 8u
+
+typedef struct whamd_prior_genotypes_view {
+	uint64_t n_positions;
+	const uint32_t* positions;          /* [n_positions] strictly increasing */
+	uint64_t n_reads;
+	const uint64_t* read_ptr;           /* [n_reads + 1] into the entry arrays */
+	const uint32_t* entry_position;     /* [n_entries] */
+	const uint8_t* entry_allele;        /* [n_entries] 0 / 1 count, anything else is passed over */
+	const uint32_t* entry_quality;      /* [n_entries] phred, unsigned as in the reference */
+	double constant;                    /* want_regularized */
+	double gt_prob;                     /* want_regularized: 1 - 10^(-gt_qual_threshold / 10), computed by the caller */
+	uint32_t want_regularized;          /* 0 / 1 */
+	uint32_t reserved;
+} whamd_prior_genotypes_view;
+
+typedef struct whamd_prior_genotypes_stats {
+	uint64_t n_reads;
+	uint64_t n_positions;
+	uint64_t n_entries;
+	uint64_t n_counted;                 /* entries of allele 0 / 1 at a position of the list */
+	uint64_t n_covered;                 /* positions with a counted entry */
+	uint64_t n_genotyped;               /* positions whose genotype is not none */
+	uint64_t columns_class_a;           /* covered positions of 1 .. 64 counted entries: eight lanes order each run */
+	uint64_t columns_class_b;           /* 65 .. 1024: one wave, the run in LDS */
+	uint64_t columns_class_c;           /* more: one workgroup, the run through LDS in tiles; any length */
+	uint64_t longest_run;
+	uint32_t launches;                  /* kernel launches of the whole call: 0 or WHAMD_PRIOR_GENOTYPES_LAUNCHES */
+	double map_ms;                      /* wall, whole call: entry positions to columns -- done on the host, fused with the validation */
+	double host_ms;                     /* wall, whole call: everything before the device (map_ms is part of it) */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double total_ms;                    /* wall, whole call */
+} whamd_prior_genotypes_stats;
+
+typedef struct whamd_prior_genotypes_result whamd_prior_genotypes_result; /* opaque: the result of one whamd_prior_genotypes call */
+
+/* One call for a batch of problems (samples x chromosomes): one upload, a constant number of launches, one download. */
+whamd_status_t whamd_prior_genotypes(const whamd_prior_genotypes_view* problems, uint64_t n_problems, int device, whamd_prior_genotypes_result** out);
+uint64_t whamd_prior_genotypes_problem_count(const whamd_prior_genotypes_result* r);
+/* Positions of problem m. */
+uint64_t whamd_prior_genotypes_count(const whamd_prior_genotypes_result* r, uint64_t m);
+/* Per position of problem m: gl_out [..][3]; genotype_out 0 .. 2 or -1; with want_regularized reg_out [..][3] and reg_genotype_out
+ * (without: zeros and -1).  NULL skips. */
+whamd_status_t whamd_prior_genotypes_get(const whamd_prior_genotypes_result* r, uint64_t m, double* gl_out, int8_t* genotype_out, double* reg_out,
+                                         int8_t* reg_genotype_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_prior_genotypes_get_stats(const whamd_prior_genotypes_result* r, uint64_t m, whamd_prior_genotypes_stats* stats_out);
+void whamd_prior_genotypes_destroy(whamd_prior_genotypes_result* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,12 @@ whamd_status_t whamd_debug_poly_compare_host(const whamd_poly_compare_view* jobs
  * field; never what the product calls.  Read with the whamd_tagphase_* getters of the debug library. */
 whamd_status_t whamd_debug_tagphase_host(const whamd_tagphase_view* problems, uint64_t n_problems, whamd_tagphase_result** out);
 
+/* HOST-ONLY DIAGNOSTICS of the prior genotype likelihoods (csrc/priorgt.cpp): the same validation and mapping as whamd_prior_genotypes,
+ * then every column's chain and tail on one CPU thread with the functions the kernel calls (csrc/priorgt.h) -- what the CPU test-suite
+ * holds to the recorded reference, bit for bit; never what the product calls.  Read with the whamd_prior_genotypes_* getters of the
+ * debug library. */
+whamd_status_t whamd_debug_prior_genotypes_host(const whamd_prior_genotypes_view* problems, uint64_t n_problems, whamd_prior_genotypes_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

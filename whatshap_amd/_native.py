@@ -228,6 +228,24 @@ class TagphaseStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PriorGenotypesView(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("positions", C.POINTER(C.c_uint32)), ("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)),
+                ("entry_position", C.POINTER(C.c_uint32)), ("entry_allele", C.POINTER(C.c_uint8)), ("entry_quality", C.POINTER(C.c_uint32)),
+                ("constant", C.c_double), ("gt_prob", C.c_double), ("want_regularized", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PriorGenotypesStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_entries", "n_counted", "n_covered", "n_genotyped", "columns_class_a",
+                                                "columns_class_b", "columns_class_c", "longest_run")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("map_ms", "host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+PRIOR_GENOTYPES_LAUNCHES = 8   # WHAMD_PRIOR_GENOTYPES_LAUNCHES of include/whatshap_amd.h
+
+
 class PolyReorderView(C.Structure):
     _fields_ = [("matrix", PolyMatrixView), ("ploidy", C.c_uint32), ("reserved", C.c_uint32), ("n_pos", C.c_uint64), ("haplotypes", C.POINTER(C.c_int8)),
                 ("threads", C.POINTER(C.c_int32)), ("n_clusters", C.c_uint64), ("cluster_ptr", C.POINTER(C.c_uint64)), ("cluster_reads", C.POINTER(C.c_uint32)),
@@ -425,6 +443,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_haplotag_host.argtypes = [C.POINTER(HaplotagView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_tagphase_host.restype = C.c_int
     L.whamd_debug_tagphase_host.argtypes = [C.POINTER(TagphaseView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_prior_genotypes_host.restype = C.c_int
+    L.whamd_debug_prior_genotypes_host.argtypes = [C.POINTER(PriorGenotypesView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_reorder_host.restype = C.c_int
     L.whamd_debug_poly_reorder_host.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_compare_host.restype = C.c_int
@@ -646,6 +666,18 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_tagphase_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(TagphaseStats)]
     L.whamd_tagphase_destroy.restype = None
     L.whamd_tagphase_destroy.argtypes = [C.c_void_p]
+    L.whamd_prior_genotypes.restype = C.c_int
+    L.whamd_prior_genotypes.argtypes = [C.POINTER(PriorGenotypesView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_prior_genotypes_problem_count.restype = C.c_uint64
+    L.whamd_prior_genotypes_problem_count.argtypes = [C.c_void_p]
+    L.whamd_prior_genotypes_count.restype = C.c_uint64
+    L.whamd_prior_genotypes_count.argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_prior_genotypes_get.restype = C.c_int
+    L.whamd_prior_genotypes_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_int8)]
+    L.whamd_prior_genotypes_get_stats.restype = C.c_int
+    L.whamd_prior_genotypes_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PriorGenotypesStats)]
+    L.whamd_prior_genotypes_destroy.restype = None
+    L.whamd_prior_genotypes_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -679,6 +711,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_compare_get_stats", "whamd_poly_compare_destroy",
     "whamd_tagphase", "whamd_tagphase_problem_count", "whamd_tagphase_count", "whamd_tagphase_get", "whamd_tagphase_row_count", "whamd_tagphase_get_table",
     "whamd_tagphase_get_stats", "whamd_tagphase_destroy",
+    "whamd_prior_genotypes", "whamd_prior_genotypes_problem_count", "whamd_prior_genotypes_count", "whamd_prior_genotypes_get",
+    "whamd_prior_genotypes_get_stats", "whamd_prior_genotypes_destroy",
 ]
 
 

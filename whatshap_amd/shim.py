@@ -328,3 +328,40 @@ def install_genotype(genotype_module, reference_core=None, allow_cpu_fallback=Fa
         genotype_module.Pedigree = recording_pedigree_class(ref_pedigree)
     genotype_module.GenotypeDPTable = genotype_table_factory(reference_core, fallback_table_class=previous[1] if allow_cpu_fallback else None, **options)
     return previous
+
+
+class _PreviousBindings:
+    """What an installer replaced in a module: ``.bindings`` (name -> object) and ``restore()``."""
+
+    def __init__(self, module, bindings):
+        self._module = module
+        self.bindings = dict(bindings)
+
+    def restore(self):
+        for name, value in self.bindings.items():
+            setattr(self._module, name, value)
+
+
+def compute_genotypes_factory(reference_core=None, device: int = 0):
+    """Callable with the signature of the reference's ``compute_genotypes`` (core.pyx:603): ``(readset, positions=None)``.  The chains run
+    on the device (``whatshap_amd.genotype.compute_genotypes``); with the reference module handed in the genotypes come back as its own
+    ``Genotype`` objects (``cli/genotype.py:260-267`` stores them in the variant table).  No fallback: a refusal raises."""
+    from . import genotype as _genotype
+
+    def compute_genotypes(readset, positions=None):
+        _counters["prior_genotype_calls"] = _counters.get("prior_genotype_calls", 0) + 1
+        genotypes, likelihoods = _genotype.compute_genotypes(readset, positions, device=device)
+        if reference_core is not None:
+            genotypes = [reference_core.Genotype(g.as_vector()) for g in genotypes]
+        return genotypes, likelihoods
+
+    return compute_genotypes
+
+
+def install_genotype_priors(genotype_module, reference_core=None, device: int = 0):
+    """Rebinds ``compute_genotypes`` in ``genotype_module`` (normally ``whatshap.cli.genotype``, which binds it at import and calls it
+    at ``:243`` for every sample and chromosome): the priors of ``whatshap genotype`` then come from the device, bit for bit the
+    reference's.  Independent of ``install_genotype`` (the table).  Returns the previous binding: ``.bindings`` and ``.restore()``."""
+    previous = _PreviousBindings(genotype_module, {"compute_genotypes": genotype_module.compute_genotypes})
+    genotype_module.compute_genotypes = compute_genotypes_factory(reference_core, device)
+    return previous
