@@ -143,6 +143,24 @@ def test_a_million_entries_with_heavy_tailed_coverage():
     assert with_table.stats["table_rows"] == int(without.n_phasesets.sum()) == with_table.row_ps.size
 
 
+def test_more_scan_tiles_than_one_pass_of_the_second_scan_launch():
+    """2048 * 512 + 1 variants are 513 scan tiles: the one workgroup that scans the tile totals takes 256 per pass, so it carries over
+    twice and its last pass holds a single tile with a single variant.  Almost every variant is empty.  Voting entries lie on both sides
+    of the first tile's end (2047 | 2048), of the first pass's end (524 287 | 524 288) and of the last full tile's end (1 048 575 |
+    1 048 576); a class b and a class c run lie inside the last full tile, so their list entries, and the run begins behind them, come
+    from the second pass.  The idle reads' entries, which do not vote, fall anywhere."""
+    n_var, last_full = 2048 * 512 + 1, 2048 * 511
+    runs = np.zeros(n_var, dtype=np.int64)
+    runs[[0, 2047, 2048, 2049, 524_287, 524_288, 1_048_575, 1_048_576]] = [3, 1, 2, 5, 7, 1, 4, 6]
+    runs[last_full + 100], runs[last_full + 1000] = A_MAX + 1, B_MAX + 1
+    p = hc.array_problem(runs, seed=77, n_phasesets=R + 1, n_homozygous=0)
+    for want_table in (True, False):
+        s = device_and_host([p], want_table=want_table)[0].stats
+        assert s["n_variants"] == n_var and s["n_voting"] == int(runs.sum()) and s["n_voted"] == 10
+        assert (s["variants_class_b"], s["variants_class_c"]) == (1, 1)
+        assert s["launches"] == (LAUNCHES_TABLE if want_table else LAUNCHES)
+
+
 def test_calls_without_a_voting_entry_launch_nothing():
     empty = hc.array_problem([], seed=1, n_homozygous=0)   # (no variants at all)
     hollow = hc.array_problem([0, 0, 0, 0], seed=2)

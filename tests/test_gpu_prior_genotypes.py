@@ -6,6 +6,7 @@ import os
 import re
 import types
 
+import numpy as np
 import pytest
 
 import prior_genotype_cases as pc
@@ -99,6 +100,29 @@ def test_two_calls_on_one_input_give_identical_bytes():
             assert getattr(a, field).tobytes() == getattr(b, field).tobytes(), field
         same(a, h)
     assert (first[1].stats["columns_class_b"], first[1].stats["columns_class_c"]) == (2, 14)
+
+
+def test_more_scan_tiles_than_one_pass_of_the_second_scan_launch():
+    """2048 * 512 + 1 positions are 513 scan tiles: the one workgroup that scans the tile totals takes 256 per pass, so it carries over
+    twice and its last pass holds a single tile with a single column.  Almost every column is empty.  Counted entries lie on both sides
+    of the first tile's end (2047 | 2048), of the first pass's end (524 287 | 524 288) and of the last full tile's end (1 048 575 |
+    1 048 576); a class b run (65) and a class c run (1 025) lie inside the last full tile, so their list entries, and the run begins
+    behind them, come from the second pass.  300 entries of allele 2, which are not counted, fall anywhere."""
+    n_col, last_full = 2048 * 512 + 1, 2048 * 511
+    keys = np.array([0, 2047, 2048, 2049, 524_287, 524_288, last_full + 100, last_full + 1000, 1_048_575, 1_048_576])
+    runs = np.array([3, 1, 2, 5, 7, 1, 65, 1025, 4, 6])
+    rng = np.random.default_rng(5)
+    n_counted, n_other = int(runs.sum()), 300
+    pos = np.concatenate([np.repeat(keys, runs), rng.integers(0, n_col, size=n_other)])
+    allele = np.concatenate([rng.integers(0, 2, size=n_counted), np.full(n_other, 2)])
+    order = np.argsort(pos, kind="stable")   # reads of one entry each, in the order of their positions
+    problem = gt.PriorProblem(np.arange(pos.size + 1), pos[order], allele[order], rng.integers(0, 40, size=pos.size), np.arange(n_col), constant=1e-3,
+                              gt_prob=0.9, want_regularized=True)
+    dev, host = gt.prior_genotypes_batch([problem])[0], gt.prior_genotypes_batch([problem], host=True)[0]
+    same(dev, host)
+    s = dev.stats
+    assert s["n_positions"] == n_col and s["n_counted"] == n_counted and s["n_covered"] == keys.size and s["launches"] == LAUNCHES
+    assert (s["columns_class_b"], s["columns_class_c"], s["longest_run"]) == (1, 1, 1025)
 
 
 def test_shim_round_trip():

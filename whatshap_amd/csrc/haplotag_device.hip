@@ -23,6 +23,7 @@
 
 #include "device_runtime.h"
 #include "haplotag.h"
+#include "run_scatter.h"   // team_sum, team_min
 
 namespace whamd {
 namespace {
@@ -46,19 +47,6 @@ struct Slots {
 	uint32_t n;
 	bool overflow;
 };
-
-template <int W>
-__device__ inline int64_t team_sum(int64_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-template <int W>
-__device__ inline uint32_t team_min(uint32_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-	return v;
-}
 
 // Entry i of the run, or a no-match entry beyond it.
 __device__ inline void load_entry(const HtArgs& a, const HtEntry* run, uint32_t i, uint32_t n, bool on, uint32_t& ps, uint32_t& match, int64_t& q) {

@@ -17,6 +17,7 @@
 #include "../../include/whatshap_amd.h"
 #include "call_image.h"
 #include "host_parallel.h"
+#include "run_scatter.h"
 
 #if defined(__HIPCC__)
 #define WHAMD_HD __host__ __device__
@@ -26,18 +27,14 @@
 
 namespace whamd {
 
-constexpr uint32_t PG_SEGMENT = 8;                // lanes per column in class a
 constexpr uint32_t PG_CLASS_A_MAX = 64;           // class a: 0 .. 64 counted entries, ordered by eight lanes straight from memory
 constexpr uint32_t PG_CLASS_B_MAX = 1024;         // class b: 65 .. 1024, one wave with the whole run in LDS
 constexpr uint32_t PG_TILE = 4096;                // class c: beyond, one workgroup; the run passes through LDS in tiles of this many (a multiple of 4) -- any length
 constexpr uint32_t PG_OWN = 8;                    // class c: entries a thread ranks per pass over the run
-constexpr uint32_t PG_BLOCK = 256;                // threads per workgroup, every kernel
-constexpr uint32_t PG_SCAN_TILE = 2048;           // elements a workgroup of the scan takes
-constexpr uint32_t PG_LIST_GRID = 1024;           // workgroups of the class b / c launches (they walk the device-made lists)
 constexpr uint32_t PG_LAUNCHES = WHAMD_PRIOR_GENOTYPES_LAUNCHES;   // count, scan (2), place, order a / b / c, chain
 constexpr uint32_t PG_QUALITIES = 15;             // p = max(0.05, 10^(-q / 10)) is 0.05 from q = 14 on: 15 distinct values
 constexpr uint32_t PG_CODES = 2 * PG_QUALITIES;   // code = allele * 15 + min(q, 14)
-constexpr uint32_t PG_NONE = 0xffffffffu;         // column of an entry that is not counted
+constexpr uint32_t PG_NONE = RS_NONE;             // column of an entry that is not counted
 
 // What one column's lane writes.
 struct PgOut {

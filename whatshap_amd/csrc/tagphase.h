@@ -17,6 +17,7 @@
 #include "../../include/whatshap_amd.h"
 #include "call_image.h"
 #include "host_parallel.h"
+#include "run_scatter.h"
 
 #if defined(__HIPCC__)
 #define WHAMD_HD __host__ __device__
@@ -27,17 +28,15 @@
 namespace whamd {
 
 constexpr uint32_t TP_REG_PHASESETS = 4;          // R: phase sets a team keeps in registers; a variant with more takes the pass-per-phase-set route
-constexpr uint32_t TP_SEGMENT = 8;                // lanes per variant in class a
+constexpr uint32_t TP_SEGMENT = 8;                // lanes per variant in class a (the tests read this line, so it is no alias)
+static_assert(TP_SEGMENT == RS_SEGMENT, "class a teams are the shared scatter's");
 constexpr uint32_t TP_CLASS_A_MAX = 64;           // class a: 0 .. 64 placed entries (at most 8 per lane of a segment)
 constexpr uint32_t TP_CLASS_B_MAX = 4096;         // class b: 65 .. 4096 (one wave); class c beyond (one workgroup)
-constexpr uint32_t TP_BLOCK = 256;                // threads per workgroup, every kernel
-constexpr uint32_t TP_SCAN_TILE = 2048;           // elements a workgroup of the scan takes
-constexpr uint32_t TP_LIST_GRID = 1024;           // workgroups of the class b / c launches (they walk the device-made lists)
 constexpr uint32_t TP_LAUNCHES = 7;               // count, scan (2), place, reduce a / b / c
 constexpr uint32_t TP_LAUNCHES_TABLE = 11;        // ... and with want_table: scan of the row counts (2), rows a, rows b + c
 constexpr uint32_t TP_MAX_PHASESETS = 1u << 30;   // per problem (the dense id shares a word with the haplotype)
 constexpr uint32_t TP_NOT_COUNTED = 0xffffffffu;  // TpRead::code of a read that does not vote
-constexpr uint32_t TP_NONE = 0xffffffffu;
+constexpr uint32_t TP_NONE = RS_NONE;
 constexpr int64_t TP_MAX_MAGNITUDE = (int64_t)1 << 53;   // sum of |quality| of a problem's voting entries: up to here (double)score / (double)total is Python's score / total
 
 enum : uint32_t { TP_HOMOZYGOUS = 1, TP_PHASED = 2, TP_SNV = 4, TP_ONLY_INDELS = 8 };   // the word per variant: bits 0 .. 3 (bit 3: the problem's only_indels); bits 8 ..: the problem's place in the call

@@ -1,5 +1,6 @@
 // tagphase_device.hip -- the votes and the consensus of haplotagphase on gfx950 (tagphase.h).  The reads arrive read-major, the sums are
-// per variant: a scatter.  It is done as a store pass and a per-destination sum, nothing is summed through global atomics:
+// per variant: a scatter.  It is done as a store pass and a per-destination sum, nothing is summed through global atomics; count, scan
+// and place are the shared ones of run_scatter.h, with this layer's key and payload:
 //   upload    per variant {flags | problem << 8}, per problem the gap threshold, per read {phase set << 1 | haplotype, first variant of its
 //             problem} and its first entry, the three entry arrays as the caller holds them (variant, id, quality).
 //   count     one thread per entry: its read (a search of the read offsets, narrowed to the reads of the workgroup's 256 entries), does it
@@ -28,8 +29,7 @@ namespace whamd {
 namespace {
 
 constexpr int R = (int)TP_REG_PHASESETS;
-constexpr int NW = (int)TP_BLOCK / 64;
-constexpr uint32_t PER_THREAD = TP_SCAN_TILE / TP_BLOCK;
+constexpr int NW = (int)RS_BLOCK / 64;
 
 struct TpArgs {
 	// the image
@@ -41,13 +41,7 @@ struct TpArgs {
 	const uint8_t* entry_id;
 	const int32_t* entry_quality;
 	// made on the device
-	uint32_t* counts;             // [n_var] voting entries
-	uint32_t* cursor;             // [n_var] zero before place
-	uint32_t* local;              // [n_var] prefix of counts inside the tile
-	uint32_t* tile_sums;          // [tiles] exclusive after the second scan launch
-	uint32_t* list_n;             // [2] lengths of list b, list c
-	uint32_t* list_b;             // [n_var]
-	uint32_t* list_c;             // [n_var]
+	RunIndex run;                 // keys: the n_var variants; counted: the voting entries
 	TpPlaced* placed;             // [n_placed]
 	TpOut* out;                   // [n_var]
 	uint32_t* nps;                // [n_var] phase sets per variant; nullptr: no table
@@ -55,10 +49,8 @@ struct TpArgs {
 	uint32_t* nps_tile_sums;
 	uint32_t* n_rows;             // [1]
 	TpRow* rows;
-	uint32_t n_var, n_reads, n_entries, n_placed, a_max, b_max;
+	uint32_t n_reads, n_entries;
 };
-
-__device__ inline uint32_t run_begin(const uint32_t* local, const uint32_t* tile_sums, uint32_t v) { return local[v] + tile_sums[v / TP_SCAN_TILE]; }
 
 // ---------------------------------------------------------------------------------------------- count, place
 // The largest r in [lo, hi] with read_ptr[r] <= i (read_ptr[lo] <= i).
@@ -75,114 +67,28 @@ __device__ inline uint32_t find_read(const uint32_t* read_ptr, uint32_t lo, uint
 __device__ inline uint32_t voting_variant(const TpArgs& a, uint32_t i, uint32_t& key) {
 	key = 0;
 	if (i >= a.n_entries) return TP_NONE;
-	const uint32_t i0 = blockIdx.x * TP_BLOCK, i1 = min(i0 + TP_BLOCK - 1, a.n_entries - 1);
+	const uint32_t i0 = blockIdx.x * RS_BLOCK, i1 = min(i0 + RS_BLOCK - 1, a.n_entries - 1);
 	const uint32_t lo = find_read(a.read_ptr, 0, a.n_reads - 1, i0), hi = find_read(a.read_ptr, lo, a.n_reads - 1, i1);
 	const TpRead rd = a.reads[find_read(a.read_ptr, lo, hi, i)];
 	if (rd.code == TP_NOT_COUNTED) return TP_NONE;
 	const uint32_t v = rd.var_base + a.entry_var[i];
-	if (v >= a.n_var || (a.vinfo[v] & TP_HOMOZYGOUS)) return TP_NONE;
+	if (v >= a.run.n_keys || (a.vinfo[v] & TP_HOMOZYGOUS)) return TP_NONE;
 	key = rd.code ^ (uint32_t)(a.entry_id[i] & 1u);
 	return v;
 }
 
-// Neighbouring lanes of a wave with the same variant form a run: its first lane and its length.  Every lane of the wave calls this.
-__device__ inline void lane_run(uint32_t v, uint32_t lane, uint32_t& head_lane, uint32_t& length) {
-	const uint32_t prev = (uint32_t)__shfl_up((int)v, 1);
-	const uint64_t heads = __ballot(lane == 0 || v != prev);
-	head_lane = 63u - (uint32_t)__clzll((long long)(heads & ((2ull << lane) - 1)));
-	const uint64_t rest = head_lane == 63u ? 0ull : heads >> (head_lane + 1);
-	const uint32_t next = rest ? head_lane + (uint32_t)__ffsll((unsigned long long)rest) : 64u;
-	length = next - head_lane;
+// The scatter's key is the variant; what is placed carries the vote's key.
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_count_kernel(TpArgs a) {
+	const uint32_t i = blockIdx.x * RS_BLOCK + threadIdx.x;
+	uint32_t key;
+	scatter_count(a.run, voting_variant(a, i, key), threadIdx.x & 63u);
 }
 
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_count_kernel(TpArgs a) {
-	const uint32_t i = blockIdx.x * TP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
-	uint32_t key, head_lane, length;
-	const uint32_t v = voting_variant(a, i, key);
-	lane_run(v, lane, head_lane, length);
-	if (v != TP_NONE && lane == head_lane) atomicAdd(a.counts + v, length);
-}
-
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_place_kernel(TpArgs a) {
-	const uint32_t i = blockIdx.x * TP_BLOCK + threadIdx.x, lane = threadIdx.x & 63u;
-	uint32_t key, head_lane, length;
-	const uint32_t v = voting_variant(a, i, key);
-	lane_run(v, lane, head_lane, length);
-	uint32_t base = 0;
-	if (v != TP_NONE && lane == head_lane) base = atomicAdd(a.cursor + v, length);
-	base = (uint32_t)__shfl((int)base, (int)head_lane);
-	if (v == TP_NONE) return;
-	const uint32_t at = run_begin(a.local, a.tile_sums, v) + base + (lane - head_lane);
-	if (at < a.n_placed) a.placed[at] = TpPlaced{key, a.entry_quality[i], i};
-}
-
-// ---------------------------------------------------------------------------------------------- scan
-__device__ inline uint32_t wave_inclusive(uint32_t v, uint32_t lane) {
-#pragma unroll
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t up = (uint32_t)__shfl_up((int)v, o);
-		if (lane >= (uint32_t)o) v += up;
-	}
-	return v;
-}
-
-// The workgroup's exclusive prefix of `mine` (one value per thread, in thread order) and the workgroup's total.
-__device__ inline uint32_t block_exclusive(uint32_t mine, uint32_t* wave_total, uint32_t& total) {
-	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-	const uint32_t inc = wave_inclusive(mine, lane);
-	if (lane == 63) wave_total[w] = inc;
-	__syncthreads();
-	uint32_t before = 0;
-	total = 0;
-#pragma unroll
-	for (int ww = 0; ww < NW; ww++) {
-		if ((uint32_t)ww < w) before += wave_total[ww];
-		total += wave_total[ww];
-	}
-	__syncthreads();
-	return before + inc - mine;
-}
-
-// in[n] -> local[n] (prefix inside the tile), tile_sums[tile] (the tile's total).  With lists: the variants beyond class a are appended.
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_scan_tiles_kernel(const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n, uint32_t* list_n,
-                                                                       uint32_t* list_b, uint32_t* list_c, uint32_t a_max, uint32_t b_max) {
-	__shared__ uint32_t wave_total[NW];
-	const uint32_t base = blockIdx.x * TP_SCAN_TILE + threadIdx.x * PER_THREAD;
-	uint32_t val[PER_THREAD], mine = 0;
-#pragma unroll
-	for (uint32_t k = 0; k < PER_THREAD; k++) {
-		val[k] = base + k < n ? in[base + k] : 0;
-		mine += val[k];
-	}
-	uint32_t total;
-	uint32_t at = block_exclusive(mine, wave_total, total);
-#pragma unroll
-	for (uint32_t k = 0; k < PER_THREAD; k++) {
-		if (base + k < n) {
-			local[base + k] = at;
-			if (list_n && val[k] > a_max) {
-				if (val[k] <= b_max) list_b[atomicAdd(list_n, 1u)] = base + k;
-				else list_c[atomicAdd(list_n + 1, 1u)] = base + k;
-			}
-		}
-		at += val[k];
-	}
-	if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// tile_sums[n_tiles] exclusive in place by one workgroup; *total_out, if wanted, the sum of all.
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_scan_sums_kernel(uint32_t* tile_sums, uint32_t n_tiles, uint32_t* total_out) {
-	__shared__ uint32_t wave_total[NW];
-	uint32_t carry = 0;
-	for (uint32_t base = 0; base < n_tiles; base += TP_BLOCK) {
-		const uint32_t x = base + threadIdx.x;
-		const uint32_t mine = x < n_tiles ? tile_sums[x] : 0;
-		uint32_t total;
-		const uint32_t before = block_exclusive(mine, wave_total, total);
-		if (x < n_tiles) tile_sums[x] = carry + before;
-		carry += total;
-	}
-	if (total_out && threadIdx.x == 0) *total_out = carry;
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_place_kernel(TpArgs a) {
+	const uint32_t i = blockIdx.x * RS_BLOCK + threadIdx.x;
+	uint32_t key;
+	const uint32_t at = scatter_place(a.run, voting_variant(a, i, key), threadIdx.x & 63u);
+	if (at != RS_NONE) a.placed[at] = TpPlaced{key, a.entry_quality[i], i};
 }
 
 // ---------------------------------------------------------------------------------------------- reduce and decide
@@ -192,19 +98,6 @@ struct Slots {
 	uint32_t n;
 	bool overflow;
 };
-
-template <int W>
-__device__ inline int64_t team_sum(int64_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-template <int W>
-__device__ inline uint32_t team_min(uint32_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-	return v;
-}
 
 // Placed entry i of the run, or nothing (ps = TP_NONE) beyond it.
 __device__ inline void load_placed(const TpPlaced* run, uint32_t i, uint32_t n, bool on, uint32_t& ps, uint32_t& hap, int64_t& q, uint32_t& index) {
@@ -288,7 +181,7 @@ struct TeamScope {
 	}
 };
 struct BlockScope {   // (one variant per workgroup: every thread takes the same branches, so the barriers are met by all)
-	static constexpr uint32_t STRIDE = TP_BLOCK;
+	static constexpr uint32_t STRIDE = RS_BLOCK;
 	uint32_t* word;          // LDS [NW]
 	int64_t (*part)[2];      // LDS [NW][2]
 	uint32_t lane, w;
@@ -375,8 +268,8 @@ template <int W>
 __device__ inline void reduce_by_team(const TpArgs& a, uint32_t v, bool have, uint32_t l, uint32_t lane) {
 	const uint32_t lane0 = lane - l;
 	const uint64_t teammask = (W == 64 ? ~0ull : ((1ull << W) - 1)) << lane0;
-	const uint32_t n = have ? a.counts[v] : 0;
-	const TpPlaced* run = a.placed + (have ? run_begin(a.local, a.tile_sums, v) : 0);
+	const uint32_t n = have ? a.run.counts[v] : 0;
+	const TpPlaced* run = a.placed + (have ? run_begin(a.run.local, a.run.tile_sums, v) : 0);
 	Slots S;
 	scan_run<W>(run, n, l, teammask, lane0, S);
 	TpBest best = tp_start();
@@ -390,30 +283,30 @@ __device__ inline void reduce_by_team(const TpArgs& a, uint32_t v, bool have, ui
 }
 
 // Class a: eight lanes per variant, over all variants; those of more entries are left to the lists.
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_a_kernel(TpArgs a) {
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_a_kernel(TpArgs a) {
 	const uint32_t lane = threadIdx.x & 63u, l = threadIdx.x & (TP_SEGMENT - 1);
-	const uint64_t v64 = (uint64_t)blockIdx.x * (TP_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
-	const bool have = v64 < a.n_var && a.counts[v64] <= a.a_max;
+	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
+	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max;
 	reduce_by_team<(int)TP_SEGMENT>(a, (uint32_t)v64, have, l, lane);
 }
 
 // Class b: one wave per listed variant.
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_b_kernel(TpArgs a) {
-	const uint32_t lane = threadIdx.x & 63u, n_list = a.list_n[0];
-	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW) reduce_by_team<64>(a, a.list_b[k], true, lane, lane);
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_b_kernel(TpArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, n_list = a.run.list_n[0];
+	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW) reduce_by_team<64>(a, a.run.list_b[k], true, lane, lane);
 }
 
 // Class c: one workgroup per listed variant; every wave takes a contiguous quarter of the run, the quarters meet in LDS.
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
 	__shared__ int64_t w_sums[NW][R][2];
 	__shared__ uint32_t w_ps[NW][R], w_first[NW][R], w_n[NW], w_overflow[NW];
 	__shared__ int64_t r_sums[NW][2];
 	__shared__ uint32_t r_word[NW];
 	__shared__ uint32_t go_slow;
-	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, n_list = a.list_n[1];
+	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, n_list = a.run.list_n[1];
 	for (uint32_t k = blockIdx.x; k < n_list; k += gridDim.x) {
-		const uint32_t v = a.list_c[k], n = a.counts[v];
-		const TpPlaced* run = a.placed + run_begin(a.local, a.tile_sums, v);
+		const uint32_t v = a.run.list_c[k], n = a.run.counts[v];
+		const TpPlaced* run = a.placed + run_begin(a.run.local, a.run.tile_sums, v);
 		const uint32_t per = ((n + NW - 1) / NW + 63u) & ~63u;
 		const uint64_t b64 = (uint64_t)w * per;
 		const uint32_t begin = (uint32_t)min(b64, (uint64_t)n), end = (uint32_t)min(b64 + per, (uint64_t)n);
@@ -477,22 +370,22 @@ __global__ void __launch_bounds__(TP_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
 // ---------------------------------------------------------------------------------------------- table rows
 __device__ inline uint32_t row_begin(const TpArgs& a, uint32_t v) { return run_begin(a.nps_local, a.nps_tile_sums, v); }
 
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_rows_a_kernel(TpArgs a) {
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_rows_a_kernel(TpArgs a) {
 	const uint32_t l = threadIdx.x & (TP_SEGMENT - 1);
-	const uint64_t v64 = (uint64_t)blockIdx.x * (TP_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
-	const bool have = v64 < a.n_var && a.counts[v64] <= a.a_max && a.counts[v64] > 0;
+	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
+	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max && a.run.counts[v64] > 0;
 	const uint32_t v = (uint32_t)v64;
 	TpBest best = tp_start();
-	pass_per_phase_set(a.placed + (have ? run_begin(a.local, a.tile_sums, v) : 0), have ? a.counts[v] : 0, l, have, TeamScope<(int)TP_SEGMENT>{}, best,
+	pass_per_phase_set(a.placed + (have ? run_begin(a.run.local, a.run.tile_sums, v) : 0), have ? a.run.counts[v] : 0, l, have, TeamScope<(int)TP_SEGMENT>{}, best,
 	                   a.rows + (have ? row_begin(a, v) : 0), have ? a.nps[v] : 0, l == 0);
 }
 
-__global__ void __launch_bounds__(TP_BLOCK) tagphase_rows_list_kernel(TpArgs a) {
-	const uint32_t lane = threadIdx.x & 63u, n_b = a.list_n[0], n_list = n_b + a.list_n[1];
+__global__ void __launch_bounds__(RS_BLOCK) tagphase_rows_list_kernel(TpArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, n_b = a.run.list_n[0], n_list = n_b + a.run.list_n[1];
 	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW) {
-		const uint32_t v = k < n_b ? a.list_b[k] : a.list_c[k - n_b];
+		const uint32_t v = k < n_b ? a.run.list_b[k] : a.run.list_c[k - n_b];
 		TpBest best = tp_start();
-		pass_per_phase_set(a.placed + run_begin(a.local, a.tile_sums, v), a.counts[v], lane, true, TeamScope<64>{}, best, a.rows + row_begin(a, v), a.nps[v], lane == 0);
+		pass_per_phase_set(a.placed + run_begin(a.run.local, a.run.tile_sums, v), a.run.counts[v], lane, true, TeamScope<64>{}, best, a.rows + row_begin(a, v), a.nps[v], lane == 0);
 	}
 }
 
@@ -520,7 +413,6 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 		msg = "2^32 - 4096 or more variants or entries, or 2^24 or more problems, in one call";
 		return WHAMD_ERR_UNSUPPORTED;
 	}
-	const uint32_t n_tiles = (uint32_t)((n_var + TP_SCAN_TILE - 1) / TP_SCAN_TILE);
 	ImageLayout in;
 	const auto p_vinfo = in.add<uint32_t>(n_var);
 	const auto p_gap = in.add<double>(n_in);
@@ -531,17 +423,14 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 	const auto p_eid = in.add<uint8_t>(n_entries);
 	// what the kernels make: the zeroed words first
 	ImageLayout work;
-	const auto w_counts = work.add<uint32_t>(n_var);
-	const auto w_cursor = work.add<uint32_t>(n_var);
-	const auto w_listn = work.add<uint32_t>(4);   // list lengths, the number of rows
+	RunPieces w_run;
+	rs_add_zeroed(work, n_var, w_run);
+	const auto w_n_rows = work.add<uint32_t>(1);
 	const size_t zeroed = work.total;
-	const auto w_local = work.add<uint32_t>(n_var);
-	const auto w_tiles = work.add<uint32_t>(n_tiles);
-	const auto w_list_b = work.add<uint32_t>(n_var);
-	const auto w_list_c = work.add<uint32_t>(n_var);
+	rs_add_rest(work, n_var, w_run);
 	const auto w_nps = work.add<uint32_t>(want_table ? n_var : 0);
 	const auto w_nps_local = work.add<uint32_t>(want_table ? n_var : 0);
-	const auto w_nps_tiles = work.add<uint32_t>(want_table ? n_tiles : 0);
+	const auto w_nps_tiles = work.add<uint32_t>(want_table ? rs_tiles(n_var) : 0);
 	const auto w_placed = work.add<TpPlaced>(n_placed);
 	const auto w_out = work.add<TpOut>(n_var);
 	Session s;
@@ -593,47 +482,29 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 	a.entry_var = im.dev(p_evar);
 	a.entry_id = im.dev(p_eid);
 	a.entry_quality = im.dev(p_eq);
-	a.counts = wk.dev_out(w_counts);
-	a.cursor = wk.dev_out(w_cursor);
-	a.list_n = wk.dev_out(w_listn);
-	a.n_rows = a.list_n + 2;
-	a.local = wk.dev_out(w_local);
-	a.tile_sums = wk.dev_out(w_tiles);
-	a.list_b = wk.dev_out(w_list_b);
-	a.list_c = wk.dev_out(w_list_c);
+	a.run = rs_bind(wk, w_run, n_var, n_placed, TP_CLASS_A_MAX, TP_CLASS_B_MAX);
+	a.n_rows = wk.dev_out(w_n_rows);
 	a.nps = want_table ? wk.dev_out(w_nps) : nullptr;
 	a.nps_local = want_table ? wk.dev_out(w_nps_local) : nullptr;
 	a.nps_tile_sums = want_table ? wk.dev_out(w_nps_tiles) : nullptr;
 	a.placed = wk.dev_out(w_placed);
 	a.out = wk.dev_out(w_out);
 	a.rows = nullptr;
-	a.n_var = (uint32_t)n_var;
 	a.n_reads = (uint32_t)n_reads;
 	a.n_entries = (uint32_t)n_entries;
-	a.n_placed = (uint32_t)n_placed;
-	a.a_max = TP_CLASS_A_MAX;
-	a.b_max = TP_CLASS_B_MAX;
-	const dim3 block(TP_BLOCK);
-	const dim3 per_entry((uint32_t)((n_entries + TP_BLOCK - 1) / TP_BLOCK)), per_segment((uint32_t)((n_var + TP_BLOCK / TP_SEGMENT - 1) / (TP_BLOCK / TP_SEGMENT)));
-#define TP_LAUNCH(kernel, grid, ...)                                         \
-	do {                                                                     \
-		hipLaunchKernelGGL(kernel, grid, block, 0, s.stream, __VA_ARGS__);   \
-		HIP_TRY(hipGetLastError());                                          \
-		++times.launches;                                                    \
-	} while (0)
-	TP_LAUNCH(tagphase_count_kernel, per_entry, a);
-	TP_LAUNCH(tagphase_scan_tiles_kernel, dim3(n_tiles), a.counts, a.local, a.tile_sums, a.n_var, a.list_n, a.list_b, a.list_c, a.a_max, a.b_max);
-	TP_LAUNCH(tagphase_scan_sums_kernel, dim3(1), a.tile_sums, n_tiles, (uint32_t*)nullptr);
-	TP_LAUNCH(tagphase_place_kernel, per_entry, a);
-	TP_LAUNCH(tagphase_reduce_a_kernel, per_segment, a);
-	TP_LAUNCH(tagphase_reduce_b_kernel, dim3(TP_LIST_GRID), a);
-	TP_LAUNCH(tagphase_reduce_c_kernel, dim3(TP_LIST_GRID), a);
+	const RunIndex& run = a.run;
+	const dim3 per_entry((uint32_t)((n_entries + RS_BLOCK - 1) / RS_BLOCK)), per_segment((uint32_t)((n_var + RS_BLOCK / TP_SEGMENT - 1) / (RS_BLOCK / TP_SEGMENT)));
+	const auto launch = [&](void (*kernel)(TpArgs), dim3 grid) { return rs_launch(s.stream, times, msg, kernel, grid, a); };
+	if ((st = launch(tagphase_count_kernel, per_entry)) != WHAMD_OK) return st;
+	if ((st = rs_scan(s.stream, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr)) != WHAMD_OK) return st;
+	if ((st = launch(tagphase_place_kernel, per_entry)) != WHAMD_OK) return st;
+	if ((st = launch(tagphase_reduce_a_kernel, per_segment)) != WHAMD_OK) return st;
+	if ((st = launch(tagphase_reduce_b_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
+	if ((st = launch(tagphase_reduce_c_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
 	TpRow* res_rows = nullptr;
 	uint64_t n_rows = 0;
 	if (want_table) {
-		TP_LAUNCH(tagphase_scan_tiles_kernel, dim3(n_tiles), (const uint32_t*)a.nps, a.nps_local, a.nps_tile_sums, a.n_var, (uint32_t*)nullptr, (uint32_t*)nullptr,
-		          (uint32_t*)nullptr, 0u, 0u);
-		TP_LAUNCH(tagphase_scan_sums_kernel, dim3(1), a.nps_tile_sums, n_tiles, a.n_rows);
+		if ((st = rs_scan(s.stream, times, msg, a.nps, a.nps_local, a.nps_tile_sums, run.n_keys, nullptr, a.n_rows)) != WHAMD_OK) return st;
 		// the one wait in the middle of the call: the table's size
 		if ((st = s.fetch(res_rows_n, a.n_rows, sizeof(uint32_t), msg)) != WHAMD_OK) return st;
 		HIP_TRY(hipStreamSynchronize(s.stream));
@@ -644,13 +515,12 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 		}
 		if ((st = s.device_block(n_rows * sizeof(TpRow), (void**)&a.rows, msg)) != WHAMD_OK) return st;
 		if ((st = s.pinned_block(n_rows * sizeof(TpRow), (void**)&res_rows, msg)) != WHAMD_OK) return st;
-		TP_LAUNCH(tagphase_rows_a_kernel, per_segment, a);
-		TP_LAUNCH(tagphase_rows_list_kernel, dim3(TP_LIST_GRID), a);
+		if ((st = launch(tagphase_rows_a_kernel, per_segment)) != WHAMD_OK) return st;
+		if ((st = launch(tagphase_rows_list_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
 	}
-#undef TP_LAUNCH
 	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
 	if ((st = s.fetch(res_out, a.out, n_var * sizeof(TpOut), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_counts, a.counts, n_var * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_counts, run.counts,n_var * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
 	if (n_rows && (st = s.fetch(res_rows, a.rows, n_rows * sizeof(TpRow), msg)) != WHAMD_OK) return st;
 	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
 	// back to the problems: entry indices become local to each
