@@ -38,7 +38,7 @@ extern "C" {
 
 /* 2: whamd_plan_summary grew (n_yform_runs, n_fact_runs), whamd_solve_stats.group_tables / host_flatten_ms: a caller built against
  * version 1 must not be handed the larger structs -- bindings compare whamd_abi_version() with the header they were built from. */
-#define WHAMD_ABI_VERSION 2
+#define WHAMD_ABI_VERSION 3
 
 /* allele codes, identical to Entry::allele_t (src/entry.h:8) */
 #define WHAMD_ALLELE_REF 0
@@ -1017,6 +1017,106 @@ whamd_status_t whamd_prior_genotypes_get(const whamd_prior_genotypes_result* r, 
 /* Counts of problem m; launches and times are those of the whole call. */
 whamd_status_t whamd_prior_genotypes_get_stats(const whamd_prior_genotypes_result* r, uint64_t m, whamd_prior_genotypes_stats* stats_out);
 void whamd_prior_genotypes_destroy(whamd_prior_genotypes_result* r);
+
+/* ---- Polyphase threading inputs (get_allele_depths, select_clusters, compute_haplotypes of whatshap/polyphase/threading.py:274-317,
+ * 228-271, 112-131) ------------------------------------------------------------------------------------------------------------------
+ * What `whatshap polyphase` computes on both sides of its threader.  One problem is one block: the allele matrix (as in the read
+ * scoring above: rows by local position, a position listed twice keeps the allele listed last), the clustering as CSR -- cluster c
+ * lists the reads cluster_reads[cluster_ptr[c] .. cluster_ptr[c+1]-1] IN THE ORDER OF ITS LIST --, the ploidy, max_cluster_gap and the
+ * number of alleles.
+ * Rows: one per (position, cluster) with at least one row entry of a read of the cluster, a position's rows ascending in the cluster.
+ * depth[allele] = reads of the cluster with that allele there; first[allele] = the smallest rank, in the cluster's list, of such a read
+ * (UINT32_MAX: none) -- ascending `first` is the insertion order of the reference's inner dict.  consensus: `ploidy` picks, each the
+ * allele with the largest (double)depth / (double)(1 + times picked), equal quotients to the smaller `first`.
+ * Selection, per position: rows by total depth descending, equal depths by cluster ascending; the first always, then up to
+ * min(rows, ploidy + 2) in all while (double)depth / (double)(depth of all rows) < 1.0 / (8.0 * ploidy) is false -- the first row for
+ * which it is true ends the list.  Gap filling, positions 1 .. n-2 in increasing order: every cluster of the list of position - 1 (as
+ * extended, in that list's order: depth order, then the order of appending) that is not in the list yet and is in the original
+ * selection of one of the next min(max_cluster_gap, n - position - 1) positions is appended while the list holds fewer than ploidy + 2;
+ * an appended cluster's depth row at that position, if it has one, is zeroed (its consensus and `first` stay).  Finally every list is
+ * sorted ascending; cov_rank keeps an entry's place before that sort, cov_readded marks the appended ones.
+ * WHAMD_POLY_THREAD_DEPTHS_ONLY: rows only -- no selection (empty lists), positions without a row allowed.
+ * Device (csrc/polythread_device.hip): count per position, scan, place, the distinct clusters of every run, scan, the rows, the
+ * selection: WHAMD_POLY_THREAD_LAUNCHES launches per call whatever the problems; a call without a counted entry launches nothing.  The
+ * gap filling is sequential and runs on the host after the download.
+ * Errors, all with nothing launched.  WHAMD_ERR_INVALID: what the matrix refuses (see above), a ploidy below 1 or above
+ * WHAMD_POLY_THREAD_MAX_PLOIDY, n_alleles below 1 or above WHAMD_POLY_THREAD_MAX_ALLELES, an allele outside 0 .. n_alleles-1, a read id
+ * outside the matrix, a read in two clusters or twice in one, a position without a row (the message names it; not with DEPTHS_ONLY),
+ * a null array, cluster_ptr that decreases or does not start at 0.  WHAMD_ERR_UNSUPPORTED: 2^32 - 4096 or more positions or row entries
+ * in one call (every count stays inside uint32), 2^28 or more reads in one cluster. */
+#define WHAMD_POLY_THREAD_MAX_PLOIDY 16u
+#define WHAMD_POLY_THREAD_MAX_ALLELES 16u
+#define WHAMD_POLY_THREAD_LAUNCHES 13u
+#define WHAMD_POLY_THREAD_DEPTHS_ONLY 1u
+
+typedef struct whamd_poly_thread_view {
+	whamd_poly_matrix_view matrix;
+	uint64_t n_clusters;
+	const uint64_t* cluster_ptr;        /* [n_clusters + 1] */
+	const uint32_t* cluster_reads;      /* [cluster_ptr[n_clusters]] read ids, in list order */
+	uint32_t ploidy;
+	uint32_t max_cluster_gap;
+	uint32_t n_alleles;
+	uint32_t flags;                     /* WHAMD_POLY_THREAD_DEPTHS_ONLY */
+} whamd_poly_thread_view;
+
+typedef struct whamd_poly_thread_stats {
+	uint64_t n_reads;
+	uint64_t n_positions;
+	uint64_t n_entries;                 /* row entries of the matrix */
+	uint64_t n_counted;                 /* of them: of reads that are in a cluster */
+	uint64_t n_rows;                    /* (position, cluster) rows */
+	uint64_t n_selected;                /* entries of the lists before the gap filling */
+	uint64_t n_readded;                 /* entries the gap filling appended */
+	uint64_t n_emptied;                 /* of them: with a depth row, now zeroed */
+	uint64_t positions_class_a;         /* positions of 1 .. 64 counted entries: eight lanes each */
+	uint64_t positions_class_b;         /* 65 .. 4096: one wave each */
+	uint64_t positions_class_c;         /* more: one workgroup each */
+	uint32_t launches;                  /* kernel launches of the whole call: 0 or WHAMD_POLY_THREAD_LAUNCHES */
+	double host_ms;                     /* wall, whole call: validation, matrix rows, reads to (cluster, rank) */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double fill_ms;                     /* wall, whole call: gap filling and result assembly on the host */
+	double total_ms;                    /* wall, whole call */
+} whamd_poly_thread_stats;
+
+typedef struct whamd_poly_thread_result whamd_poly_thread_result; /* opaque: the result of one whamd_poly_thread_inputs call */
+
+/* One call for a batch of problems (blocks): one upload, a constant number of launches. */
+whamd_status_t whamd_poly_thread_inputs(const whamd_poly_thread_view* problems, uint64_t n_problems, int device, whamd_poly_thread_result** out);
+uint64_t whamd_poly_thread_problem_count(const whamd_poly_thread_result* r);
+/* Positions, rows and list entries of problem m. */
+uint64_t whamd_poly_thread_position_count(const whamd_poly_thread_result* r, uint64_t m);
+uint64_t whamd_poly_thread_row_count(const whamd_poly_thread_result* r, uint64_t m);
+uint64_t whamd_poly_thread_cov_count(const whamd_poly_thread_result* r, uint64_t m);
+/* The rows of problem m: pc_ptr_out [positions + 1]; per row the cluster, depth_out [rows][n_alleles] (after the gap filling zeroed what
+ * it zeroes), first_out [rows][n_alleles], consensus_out [rows][ploidy].  NULL skips. */
+whamd_status_t whamd_poly_thread_get_rows(const whamd_poly_thread_result* r, uint64_t m, uint64_t* pc_ptr_out, uint32_t* cluster_out, uint32_t* depth_out,
+                                          uint32_t* first_out, int8_t* consensus_out);
+/* The lists of problem m: cov_ptr_out [positions + 1]; per entry the cluster (ascending within a position), readded (0 / 1) and rank (its
+ * place in the position's list before the final sort).  NULL skips. */
+whamd_status_t whamd_poly_thread_get_cov(const whamd_poly_thread_result* r, uint64_t m, uint64_t* cov_ptr_out, uint32_t* cluster_out, uint8_t* readded_out,
+                                         uint32_t* rank_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_poly_thread_get_stats(const whamd_poly_thread_result* r, uint64_t m, whamd_poly_thread_stats* stats_out);
+void whamd_poly_thread_destroy(whamd_poly_thread_result* r);
+
+/* The selection and the gap filling alone, from a (position, cluster, total depth) CSR as select_clusters is handed it: position p lists
+ * pc_cluster[pc_ptr[p] .. pc_ptr[p+1]-1], distinct, in any order -- equal depths go to the cluster listed earlier (the reference's stable
+ * sort over dict order).  The selection is the kernel of whamd_poly_thread_inputs (one launch), the filling its host function.
+ * Outputs: cov_ptr_out [n_pos + 1]; cluster / readded / rank [n_pos * (ploidy + 2)], the first cov_ptr_out[n_pos] used.
+ * WHAMD_ERR_INVALID: a position without a cluster, a cluster listed twice at a position, two or more clusters of total depth 0 (the
+ * reference divides by zero), a position's depths summing beyond uint32, a ploidy outside 1 .. WHAMD_POLY_THREAD_MAX_PLOIDY. */
+whamd_status_t whamd_poly_select_clusters(uint64_t n_pos, const uint64_t* pc_ptr, const uint32_t* pc_cluster, const uint32_t* pc_total, uint32_t ploidy,
+                                          uint32_t max_cluster_gap, int device, uint64_t* cov_ptr_out, uint32_t* cluster_out, uint8_t* readded_out,
+                                          uint32_t* rank_out, uint32_t* launches_out);
+
+/* compute_haplotypes over arrays (one launch): paths [n_pos][ploidy] cluster ids; the rows as above with consensus [rows][ploidy];
+ * haplotypes_out [ploidy][n_pos]: slot i at p gets pick number (earlier slots of p with the same cluster) of that cluster's consensus, -1
+ * where the cluster has no row at p. */
+whamd_status_t whamd_poly_haplotypes(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
+                                     const int8_t* pc_consensus, int device, int8_t* haplotypes_out, uint32_t* launches_out);
 
 #ifdef __cplusplus
 }

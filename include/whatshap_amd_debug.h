@@ -234,6 +234,14 @@ whamd_status_t whamd_debug_genotype_run_plan(const whamd_readset_view* readset, 
                                              const whamd_pedigree_view* pedigree, const uint32_t* positions, size_t n_positions,
                                              whamd_debug_genotype_run* out, size_t capacity, size_t* n_out, double* min_total_out);
 
+/* HOST-ONLY twins of the polyphase threading inputs (csrc/polythread.cpp): the same validation, then rows, selection and haplotypes on one
+ * host thread through the functions the kernels call (csrc/polythread.h); bit-identical to the device. */
+whamd_status_t whamd_debug_poly_thread_inputs_host(const whamd_poly_thread_view* problems, uint64_t n_problems, whamd_poly_thread_result** out);
+whamd_status_t whamd_debug_poly_select_clusters_host(uint64_t n_pos, const uint64_t* pc_ptr, const uint32_t* pc_cluster, const uint32_t* pc_total, uint32_t ploidy,
+                                                     uint32_t max_cluster_gap, uint64_t* cov_ptr_out, uint32_t* cluster_out, uint8_t* readded_out, uint32_t* rank_out);
+whamd_status_t whamd_debug_poly_haplotypes_host(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
+                                                const int8_t* pc_consensus, int8_t* haplotypes_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libwhatshap_amd.so")
 DEBUG_LIB_PATH = os.path.join(_HERE, "libwhatshap_amd_debug.so")   # test infrastructure (debug_lib)
-ABI_VERSION = 2   # WHAMD_ABI_VERSION of include/whatshap_amd.h this file mirrors (struct layouts below)
+ABI_VERSION = 3   # WHAMD_ABI_VERSION of include/whatshap_amd.h this file mirrors (struct layouts below)
 
 WHAMD_OK = 0
 WHAMD_ERR_INVALID = 1
@@ -279,6 +279,26 @@ class PolyCompareStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PolyThreadView(C.Structure):
+    _fields_ = [("matrix", PolyMatrixView), ("n_clusters", C.c_uint64), ("cluster_ptr", C.POINTER(C.c_uint64)), ("cluster_reads", C.POINTER(C.c_uint32)),
+                ("ploidy", C.c_uint32), ("max_cluster_gap", C.c_uint32), ("n_alleles", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PolyThreadStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_entries", "n_counted", "n_rows", "n_selected", "n_readded", "n_emptied",
+                                                "positions_class_a", "positions_class_b", "positions_class_c")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "fill_ms", "total_ms")]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+POLY_THREAD_LAUNCHES = 13       # WHAMD_POLY_THREAD_LAUNCHES of include/whatshap_amd.h
+POLY_THREAD_MAX_PLOIDY = 16     # WHAMD_POLY_THREAD_MAX_PLOIDY
+POLY_THREAD_MAX_ALLELES = 16    # WHAMD_POLY_THREAD_MAX_ALLELES
+POLY_THREAD_DEPTHS_ONLY = 1     # WHAMD_POLY_THREAD_DEPTHS_ONLY
+
+
 def _ptr(arr: Optional[np.ndarray], ctype):
     if arr is None:
         return C.cast(None, C.POINTER(ctype))
@@ -449,6 +469,14 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_poly_reorder_host.argtypes = [C.POINTER(PolyReorderView), C.c_uint64, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
     L.whamd_debug_poly_compare_host.restype = C.c_int
     L.whamd_debug_poly_compare_host.argtypes = [C.POINTER(PolyCompareView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_poly_thread_inputs_host.restype = C.c_int
+    L.whamd_debug_poly_thread_inputs_host.argtypes = [C.POINTER(PolyThreadView), C.c_uint64, C.POINTER(C.c_void_p)]
+    L.whamd_debug_poly_select_clusters_host.restype = C.c_int
+    L.whamd_debug_poly_select_clusters_host.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+    L.whamd_debug_poly_haplotypes_host.restype = C.c_int
+    L.whamd_debug_poly_haplotypes_host.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8),
+                                                   C.POINTER(C.c_int8)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
@@ -678,6 +706,28 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_prior_genotypes_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PriorGenotypesStats)]
     L.whamd_prior_genotypes_destroy.restype = None
     L.whamd_prior_genotypes_destroy.argtypes = [C.c_void_p]
+    L.whamd_poly_thread_inputs.restype = C.c_int
+    L.whamd_poly_thread_inputs.argtypes = [C.POINTER(PolyThreadView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_poly_thread_problem_count.restype = C.c_uint64
+    L.whamd_poly_thread_problem_count.argtypes = [C.c_void_p]
+    for name in ("whamd_poly_thread_position_count", "whamd_poly_thread_row_count", "whamd_poly_thread_cov_count"):
+        getattr(L, name).restype = C.c_uint64
+        getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_poly_thread_get_rows.restype = C.c_int
+    L.whamd_poly_thread_get_rows.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_int8)]
+    L.whamd_poly_thread_get_cov.restype = C.c_int
+    L.whamd_poly_thread_get_cov.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+    L.whamd_poly_thread_get_stats.restype = C.c_int
+    L.whamd_poly_thread_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PolyThreadStats)]
+    L.whamd_poly_thread_destroy.restype = None
+    L.whamd_poly_thread_destroy.argtypes = [C.c_void_p]
+    L.whamd_poly_select_clusters.restype = C.c_int
+    L.whamd_poly_select_clusters.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.whamd_poly_haplotypes.restype = C.c_int
+    L.whamd_poly_haplotypes.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8), C.c_int,
+                                        C.POINTER(C.c_int8), C.POINTER(C.c_uint32)]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -713,6 +763,9 @@ EXPORTED_SYMBOLS = [
     "whamd_tagphase_get_stats", "whamd_tagphase_destroy",
     "whamd_prior_genotypes", "whamd_prior_genotypes_problem_count", "whamd_prior_genotypes_count", "whamd_prior_genotypes_get",
     "whamd_prior_genotypes_get_stats", "whamd_prior_genotypes_destroy",
+    "whamd_poly_thread_inputs", "whamd_poly_thread_problem_count", "whamd_poly_thread_position_count", "whamd_poly_thread_row_count",
+    "whamd_poly_thread_cov_count", "whamd_poly_thread_get_rows", "whamd_poly_thread_get_cov", "whamd_poly_thread_get_stats", "whamd_poly_thread_destroy",
+    "whamd_poly_select_clusters", "whamd_poly_haplotypes",
 ]
 
 

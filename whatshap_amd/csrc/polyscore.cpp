@@ -224,9 +224,34 @@ whamd_status_t whamd::poly_build_matrix(const whamd_poly_matrix_view& v, PolyMat
 	}
 	m.n_reads = (uint32_t)n;
 	m.max_allele = (uint32_t)(max_allele + 1);
-	m.positions = glob;
-	std::sort(m.positions.begin(), m.positions.end());
-	m.positions.erase(std::unique(m.positions.begin(), m.positions.end()), m.positions.end());
+	// the sorted distinct positions and every entry's local index.  Where the positions span little more than there are entries (a
+	// block, a chromosome) a bitmap of the span gives both in two passes; else a sort and a search per entry.
+	std::vector<uint32_t> local(n_entries);
+	uint32_t lo = UINT32_MAX, hi = 0;
+	for (uint64_t e = 0; e < n_entries; e++) {
+		lo = std::min(lo, glob[e]);
+		hi = std::max(hi, glob[e]);
+	}
+	const uint64_t span = n_entries ? (uint64_t)hi - lo + 1 : 0;
+	m.positions.clear();
+	if (n_entries && span <= 64 * n_entries + (1u << 20)) {
+		std::vector<uint64_t> bits((span + 63) / 64, 0);
+		for (uint64_t e = 0; e < n_entries; e++) bits[(glob[e] - lo) >> 6] |= 1ull << ((glob[e] - lo) & 63u);
+		std::vector<uint32_t> before(bits.size() + 1, 0);
+		for (size_t w = 0; w < bits.size(); w++) before[w + 1] = before[w] + (uint32_t)__builtin_popcountll(bits[w]);
+		m.positions.reserve(before[bits.size()]);
+		for (size_t w = 0; w < bits.size(); w++)
+			for (uint64_t rest = bits[w]; rest; rest &= rest - 1) m.positions.push_back(lo + (uint32_t)(w * 64) + (uint32_t)__builtin_ctzll(rest));
+		for (uint64_t e = 0; e < n_entries; e++) {
+			const uint32_t off = glob[e] - lo;
+			local[e] = before[off >> 6] + (uint32_t)__builtin_popcountll(bits[off >> 6] & ((1ull << (off & 63u)) - 1));
+		}
+	} else {
+		m.positions = glob;
+		std::sort(m.positions.begin(), m.positions.end());
+		m.positions.erase(std::unique(m.positions.begin(), m.positions.end()), m.positions.end());
+		for (uint64_t e = 0; e < n_entries; e++) local[e] = (uint32_t)(std::lower_bound(m.positions.begin(), m.positions.end(), glob[e]) - m.positions.begin());
+	}
 	m.n_positions = (uint32_t)m.positions.size();
 	m.depths.assign((size_t)m.n_positions * m.max_allele, 0);
 	m.row_ptr.assign(n + 1, 0);
@@ -240,11 +265,25 @@ whamd_status_t whamd::poly_build_matrix(const whamd_poly_matrix_view& v, PolyMat
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t b = v.read_ptr[r], e = v.read_ptr[r + 1];
 		row.clear();
+		bool increasing = true;
 		for (uint64_t x = b; x < e; x++) {
-			const uint32_t p = (uint32_t)(std::lower_bound(m.positions.begin(), m.positions.end(), glob[x]) - m.positions.begin());
-			row.emplace_back(p, (uint32_t)(x - b));
+			const uint32_t p = local[x];
+			increasing = increasing && (x == b || p > local[x - 1]);
 			m.depths[(size_t)p * m.max_allele + (uint8_t)v.allele[x]] += 1;
 		}
+		if (increasing) {   // (the usual read: already in row order, nothing listed twice)
+			for (uint64_t x = b; x < e; x++) {
+				m.row_pos.push_back(local[x]);
+				m.row_allele.push_back((uint8_t)v.allele[x]);
+			}
+			if (e > b) {
+				m.first[r] = local[b];
+				m.last[r] = local[e - 1];
+			}
+			m.row_ptr[r + 1] = m.row_pos.size();
+			continue;
+		}
+		for (uint64_t x = b; x < e; x++) row.emplace_back(local[x], (uint32_t)(x - b));
 		if (!row.empty()) {
 			m.first[r] = row.front().first;
 			m.last[r] = row.back().first;

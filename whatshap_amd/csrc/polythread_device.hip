@@ -1,0 +1,603 @@
+// polythread_device.hip -- allele depths, consensus lists and the cluster selection of polyphase threading on gfx950 (polythread.h).
+// The matrix rows arrive read-major, the depths are per position: count, scan and place are the shared ones of run_scatter.h with the
+// key "position of the call" (the problem's first position plus the local one):
+//   upload    per read {cluster, rank in the cluster's list, first position of its problem} and its first row entry, the row entries
+//             (local position, allele), per position the ploidy of its problem.
+//   count     one thread per row entry: its read (a search of the read offsets, narrowed to the reads of the workgroup's 256 entries);
+//             a read in no cluster is not counted (RS_NONE).
+//   scan      exclusive, two launches; also appends the positions of more than 64 / 4096 entries to the class b / c list.
+//   place     a counted entry goes to its position's run as {cluster, rank << 4 | allele}.  The order inside a run is whatever the
+//             atomics give; nothing below depends on it.
+//   clusters  one team per position -- class a eight lanes over all positions, class b one wave, class c one workgroup (any length),
+//             both walking their list with a fixed grid -- counts the distinct clusters of the run: one pass per cluster for the
+//             smallest cluster not below the last one's successor.
+//   scan      of those counts: where every position's rows begin, and how many there are (the one wait of the call, to size the rows).
+//   rows      the same teams, the same passes, and per cluster a second pass for the depth of every allele and the smallest rank of a
+//             read with it (sums and minima: no order); the team's first lane writes the row and its consensus list (pt_consensus).
+//   select    one thread per position: pt_select over the totals of its rows.
+// 13 launches per call whatever the problems (PT_LAUNCHES).  The rows keep NA = 4 or 16 alleles, by the largest n_alleles of the call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
+#include "device_runtime.h"
+#include "polythread.h"
+
+namespace whamd {
+namespace {
+
+constexpr int NW = (int)RS_BLOCK / 64;
+
+struct PtArgs {
+	// the image
+	const PtRead* reads;          // [n_reads]
+	const uint32_t* read_ptr;     // [n_reads + 1]
+	const uint32_t* row_pos;      // [n_entries] local to the read's problem
+	const uint8_t* row_allele;
+	const uint32_t* pos_ploidy;   // [n_keys]
+	// made on the device
+	RunIndex run;                 // keys: the positions of the call; counted: the entries of reads that are in a cluster
+	PtPlaced* placed;             // [n_placed]
+	uint32_t* npc;                // [n_keys] rows (distinct clusters) per position
+	uint32_t* npc_local;
+	uint32_t* npc_tile_sums;
+	uint32_t* n_rows;             // [1]
+	uint32_t* pc_cluster;         // [n_pc]
+	uint32_t* pc_total;
+	uint32_t* pc_depth;           // [n_pc][NA]
+	uint32_t* pc_first;
+	int8_t* pc_cons;              // [n_pc][max_ploidy]
+	uint32_t* n_sel;              // [n_keys]
+	uint32_t* sel;                // [n_keys][max_ploidy + 2]
+	uint32_t n_reads, n_entries, n_pc, max_ploidy;
+};
+
+// ---------------------------------------------------------------------------------------------- count, place
+// The largest r in [lo, hi] with read_ptr[r] <= i (read_ptr[lo] <= i).
+__device__ inline uint32_t find_read(const uint32_t* read_ptr, uint32_t lo, uint32_t hi, uint32_t i) {
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo + 1) / 2;
+		if (read_ptr[mid] <= i) lo = mid;
+		else hi = mid - 1;
+	}
+	return lo;
+}
+
+// Row entry i of the call: the position it is counted at (PT_NONE: its read is in no cluster) and what is placed for it.
+__device__ inline uint32_t counted_position(const PtArgs& a, uint32_t i, PtPlaced& what) {
+	what = PtPlaced{0, 0};
+	if (i >= a.n_entries) return PT_NONE;
+	const uint32_t i0 = blockIdx.x * RS_BLOCK, i1 = min(i0 + RS_BLOCK - 1, a.n_entries - 1);
+	const uint32_t lo = find_read(a.read_ptr, 0, a.n_reads - 1, i0), hi = find_read(a.read_ptr, lo, a.n_reads - 1, i1);
+	const PtRead rd = a.reads[find_read(a.read_ptr, lo, hi, i)];
+	if (rd.cluster == PT_NONE) return PT_NONE;
+	const uint32_t v = rd.pos_base + a.row_pos[i];
+	if (v >= a.run.n_keys) return PT_NONE;
+	what = PtPlaced{rd.cluster, rd.rank << 4 | (uint32_t)(a.row_allele[i] & 15u)};
+	return v;
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) polythread_count_kernel(PtArgs a) {
+	const uint32_t i = blockIdx.x * RS_BLOCK + threadIdx.x;
+	PtPlaced what;
+	scatter_count(a.run, counted_position(a, i, what), threadIdx.x & 63u);
+}
+
+__global__ void __launch_bounds__(RS_BLOCK) polythread_place_kernel(PtArgs a) {
+	const uint32_t i = blockIdx.x * RS_BLOCK + threadIdx.x;
+	PtPlaced what;
+	const uint32_t at = scatter_place(a.run, counted_position(a, i, what), threadIdx.x & 63u);
+	if (at != RS_NONE) a.placed[at] = what;
+}
+
+// ---------------------------------------------------------------------------------------------- a run, cluster by cluster
+template <int W>
+__device__ inline uint32_t team_add(uint32_t v) {
+#pragma unroll
+	for (int o = W / 2; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+	return v;
+}
+
+// Who owns a position: how far apart its lanes' entries lie and how they combine a minimum and a cluster's counts.
+template <int W>
+struct TeamScope {
+	static constexpr uint32_t STRIDE = W;
+	__device__ uint32_t all_min(uint32_t v) const { return team_min<W>(v); }
+	template <int NA>
+	__device__ void all_rows(uint32_t (&cnt)[NA], uint32_t (&first)[NA]) const {
+#pragma unroll
+		for (int x = 0; x < NA; x++) {
+			cnt[x] = team_add<W>(cnt[x]);
+			first[x] = team_min<W>(first[x]);
+		}
+	}
+};
+struct BlockScope {   // (one position per workgroup: every thread takes the same branches, so the barriers are met by all)
+	static constexpr uint32_t STRIDE = RS_BLOCK;
+	uint32_t* word;    // LDS [NW]
+	uint32_t* cnts;    // LDS [NW][16]
+	uint32_t* firsts;  // LDS [NW][16]
+	uint32_t lane, w;
+	__device__ uint32_t all_min(uint32_t v) const {
+		v = team_min<64>(v);
+		if (lane == 0) word[w] = v;
+		__syncthreads();
+		v = word[0];
+#pragma unroll
+		for (int ww = 1; ww < NW; ww++) v = min(v, word[ww]);
+		__syncthreads();
+		return v;
+	}
+	template <int NA>
+	__device__ void all_rows(uint32_t (&cnt)[NA], uint32_t (&first)[NA]) const {
+#pragma unroll
+		for (int x = 0; x < NA; x++) {
+			cnt[x] = team_add<64>(cnt[x]);
+			first[x] = team_min<64>(first[x]);
+			if (lane == 0) {
+				cnts[w * 16 + x] = cnt[x];
+				firsts[w * 16 + x] = first[x];
+			}
+		}
+		__syncthreads();
+#pragma unroll
+		for (int x = 0; x < NA; x++) {
+			cnt[x] = cnts[x];
+			first[x] = firsts[x];
+#pragma unroll
+			for (int ww = 1; ww < NW; ww++) {
+				cnt[x] += cnts[ww * 16 + x];
+				first[x] = min(first[x], firsts[ww * 16 + x]);
+			}
+		}
+		__syncthreads();
+	}
+};
+
+// The clusters of run[0, n) in ascending order, for the owners with `need` (the other teams of the wave walk along idle); lane l of the
+// owner takes entries l, l + STRIDE, ...  Returns how many there are.  ROWS: the owner's `leader` lane also writes one row per cluster from
+// row0 on, at most max_rows and none at or beyond a.n_pc.
+template <int NA, bool ROWS, class Scope>
+__device__ inline uint32_t per_cluster(const PtArgs& a, const PtPlaced* run, uint32_t n, uint32_t l, bool need, const Scope& scope, uint32_t row0, uint32_t max_rows,
+                                       uint32_t ploidy, bool leader) {
+	bool active = need;
+	uint32_t lower = 0, n_rows = 0;
+	while (__any(active)) {
+		uint32_t next = PT_NONE;
+		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
+			const uint32_t i = base + l;
+			if (active && i < n) {
+				const uint32_t c = run[i].cluster;
+				if (c >= lower) next = min(next, c);
+			}
+		}
+		next = scope.all_min(next);
+		if (next == PT_NONE) active = false;
+		if (ROWS) {
+			uint32_t cnt[NA], first[NA];
+#pragma unroll
+			for (int x = 0; x < NA; x++) {
+				cnt[x] = 0;
+				first[x] = PT_NONE;
+			}
+			for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
+				const uint32_t i = base + l;
+				if (active && i < n) {
+					const PtPlaced e = run[i];
+					const uint32_t allele = e.rank_allele & 15u, rank = e.rank_allele >> 4;
+#pragma unroll
+					for (int x = 0; x < NA; x++) {
+						const bool hit = e.cluster == next && allele == (uint32_t)x;
+						cnt[x] += hit ? 1u : 0u;
+						first[x] = hit ? min(first[x], rank) : first[x];
+					}
+				}
+			}
+			scope.template all_rows<NA>(cnt, first);
+			const uint64_t row = (uint64_t)row0 + n_rows;
+			if (active && leader && n_rows < max_rows && row < a.n_pc) {
+				uint32_t total = 0;
+#pragma unroll
+				for (int x = 0; x < NA; x++) {
+					total += cnt[x];
+					a.pc_depth[row * NA + x] = cnt[x];
+					a.pc_first[row * NA + x] = first[x];
+				}
+				a.pc_cluster[row] = next;
+				a.pc_total[row] = total;
+				pt_consensus<NA>(cnt, first, ploidy, a.pc_cons + row * a.max_ploidy);
+			}
+		}
+		if (active) {
+			n_rows++;
+			lower = next + 1;
+		}
+	}
+	return n_rows;
+}
+
+__device__ inline uint32_t row_begin(const PtArgs& a, uint32_t v) { return run_begin(a.npc_local, a.npc_tile_sums, v); }
+
+// One owner, one position: count its clusters (ROWS false) or write its rows.
+template <int NA, bool ROWS, class Scope>
+__device__ inline void position_by(const PtArgs& a, uint32_t v, bool have, uint32_t l, const Scope& scope, bool leader) {
+	const uint32_t n = have ? a.run.counts[v] : 0;
+	const PtPlaced* run = a.placed + (have ? run_begin(a.run.local, a.run.tile_sums, v) : 0);
+	const uint32_t row0 = ROWS && have ? row_begin(a, v) : 0, max_rows = ROWS && have ? a.npc[v] : 0, ploidy = have ? a.pos_ploidy[v] : 1;
+	const uint32_t n_rows = per_cluster<NA, ROWS>(a, run, n, l, have, scope, row0, max_rows, ploidy, leader);
+	if (!ROWS && have && leader) a.npc[v] = n_rows;
+}
+
+// Class a: eight lanes per position, over all positions; those of more entries are left to the lists.
+template <int NA, bool ROWS>
+__global__ void __launch_bounds__(RS_BLOCK) polythread_a_kernel(PtArgs a) {
+	const uint32_t l = threadIdx.x & (PT_SEGMENT - 1);
+	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / PT_SEGMENT) + threadIdx.x / PT_SEGMENT;
+	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max;
+	position_by<NA, ROWS>(a, (uint32_t)v64, have, l, TeamScope<(int)PT_SEGMENT>{}, l == 0);
+}
+
+// Class b: one wave per listed position.
+template <int NA, bool ROWS>
+__global__ void __launch_bounds__(RS_BLOCK) polythread_b_kernel(PtArgs a) {
+	const uint32_t lane = threadIdx.x & 63u, n_list = a.run.list_n[0];
+	for (uint32_t k = blockIdx.x * NW + (threadIdx.x >> 6); k < n_list; k += gridDim.x * NW)
+		position_by<NA, ROWS>(a, a.run.list_b[k], true, lane, TeamScope<64>{}, lane == 0);
+}
+
+// Class c: one workgroup per listed position, a run of any length.
+template <int NA, bool ROWS>
+__global__ void __launch_bounds__(RS_BLOCK) polythread_c_kernel(PtArgs a) {
+	__shared__ uint32_t word[NW], cnts[NW * 16], firsts[NW * 16];
+	const uint32_t n_list = a.run.list_n[1];
+	const BlockScope scope{word, cnts, firsts, threadIdx.x & 63u, threadIdx.x >> 6};
+	for (uint32_t k = blockIdx.x; k < n_list; k += gridDim.x) position_by<NA, ROWS>(a, a.run.list_c[k], true, threadIdx.x, scope, threadIdx.x == 0);
+}
+
+// ---------------------------------------------------------------------------------------------- selection, haplotypes
+struct PtSelectArgs {
+	const uint32_t* total;        // per row
+	const uint32_t* begin;        // [n_keys] first row of the position; nullptr: run_begin(begin_local, begin_tile_sums)
+	const uint32_t* begin_local;
+	const uint32_t* begin_tile_sums;
+	const uint32_t* count;        // [n_keys] rows of the position
+	const uint32_t* pos_ploidy;   // [n_keys]; nullptr: `ploidy` for all
+	uint32_t* n_sel;              // [n_keys]
+	uint32_t* sel;                // [n_keys][stride]
+	uint32_t n_keys, n_total, ploidy, stride;
+};
+
+__global__ void __launch_bounds__(RS_BLOCK) polythread_select_kernel(PtSelectArgs a) {
+	const uint64_t v = (uint64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+	if (v >= a.n_keys) return;
+	const uint32_t begin = a.begin ? a.begin[v] : run_begin(a.begin_local, a.begin_tile_sums, (uint32_t)v);
+	uint32_t n = a.count[v];
+	if (begin > a.n_total || n > a.n_total - begin) n = 0;   // (never: the rows were sized by the same counts)
+	const uint32_t ploidy = a.pos_ploidy ? a.pos_ploidy[v] : a.ploidy;
+	a.n_sel[v] = ploidy + 2 <= a.stride ? pt_select(a.total + begin, n, ploidy, a.sel + v * a.stride) : 0;
+}
+
+struct PtHaplotypeArgs {
+	const uint32_t* paths;        // [n_pos][ploidy]
+	const uint32_t* row_begin;    // [n_pos + 1]
+	const uint32_t* cluster;      // per row
+	const int8_t* cons;           // [rows][ploidy]
+	int8_t* out;                  // [ploidy][n_pos]
+	uint32_t n_pos, ploidy;
+};
+
+__global__ void __launch_bounds__(RS_BLOCK) polythread_haplotypes_kernel(PtHaplotypeArgs a) {
+	const uint64_t x = (uint64_t)blockIdx.x * RS_BLOCK + threadIdx.x;
+	if (x >= a.n_pos) return;
+	const uint32_t b = a.row_begin[x], e = a.row_begin[x + 1];
+	pt_haplotype_position(a.paths + x * a.ploidy, a.ploidy, a.cluster + b, a.cons + (uint64_t)b * a.ploidy, e - b, a.out + x, a.n_pos);
+}
+
+template <int NA>
+whamd_status_t launch_clusters_and_rows(hipStream_t stream, CallTimes& times, std::string& msg, const PtArgs& a, bool rows, dim3 per_segment) {
+	whamd_status_t st;
+	if (rows) {
+		if ((st = rs_launch(stream, times, msg, polythread_a_kernel<NA, true>, per_segment, a)) != WHAMD_OK) return st;
+		if ((st = rs_launch(stream, times, msg, polythread_b_kernel<NA, true>, dim3(RS_LIST_GRID), a)) != WHAMD_OK) return st;
+		return rs_launch(stream, times, msg, polythread_c_kernel<NA, true>, dim3(RS_LIST_GRID), a);
+	}
+	if ((st = rs_launch(stream, times, msg, polythread_a_kernel<NA, false>, per_segment, a)) != WHAMD_OK) return st;
+	if ((st = rs_launch(stream, times, msg, polythread_b_kernel<NA, false>, dim3(RS_LIST_GRID), a)) != WHAMD_OK) return st;
+	return rs_launch(stream, times, msg, polythread_c_kernel<NA, false>, dim3(RS_LIST_GRID), a);
+}
+
+}  // namespace
+
+whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int device, std::vector<ThreadRows>& out, CallTimes& times, std::string& msg) {
+	times = CallTimes{};
+	out.assign(ps.size(), ThreadRows{});
+	std::vector<uint64_t> pos_base(ps.size() + 1, 0), read_base(ps.size() + 1, 0), ent_base(ps.size() + 1, 0);
+	uint64_t n_placed = 0;
+	uint32_t max_ploidy = 1, max_alleles = 1;
+	for (size_t x = 0; x < ps.size(); x++) {
+		pos_base[x + 1] = pos_base[x] + ps[x].m.n_positions;
+		read_base[x + 1] = read_base[x] + ps[x].m.n_reads;
+		ent_base[x + 1] = ent_base[x] + ps[x].m.row_pos.size();
+		n_placed += ps[x].n_counted;
+		max_ploidy = std::max(max_ploidy, ps[x].ploidy);
+		max_alleles = std::max(max_alleles, ps[x].n_alleles);
+	}
+	const uint64_t n_keys = pos_base[ps.size()], n_reads = read_base[ps.size()], n_entries = ent_base[ps.size()];
+	if (!n_placed) return WHAMD_OK;   // nothing is counted: no device work at all
+	if (n_keys >= 0xfffff000ull || n_entries >= 0xfffff000ull || n_keys * (max_ploidy + 2) >= 0xfffff000ull) {   // (indices are uint32 with room to round grids up)
+		msg = "2^32 - 4096 or more positions, row entries or list slots in one call";
+		return WHAMD_ERR_UNSUPPORTED;
+	}
+	const uint32_t na = max_alleles <= 4 ? 4 : 16, sel_stride = max_ploidy + 2;
+	ImageLayout in;
+	const auto p_reads = in.add<PtRead>(n_reads);
+	const auto p_rptr = in.add<uint32_t>(n_reads + 1);
+	const auto p_rpos = in.add<uint32_t>(n_entries);
+	const auto p_ploidy = in.add<uint32_t>(n_keys);
+	const auto p_rallele = in.add<uint8_t>(n_entries);
+	// what the kernels make: the zeroed words first
+	ImageLayout work;
+	RunPieces w_run;
+	rs_add_zeroed(work, n_keys, w_run);
+	const auto w_n_rows = work.add<uint32_t>(1);
+	const auto w_npc = work.add<uint32_t>(n_keys);
+	const size_t zeroed = work.total;
+	rs_add_rest(work, n_keys, w_run);
+	const auto w_npc_local = work.add<uint32_t>(n_keys);
+	const auto w_npc_tiles = work.add<uint32_t>(rs_tiles(n_keys));
+	const auto w_placed = work.add<PtPlaced>(n_placed);
+	const auto w_n_sel = work.add<uint32_t>(n_keys);
+	const auto w_sel = work.add<uint32_t>(n_keys * sel_stride);
+	Session s;
+	whamd_status_t st = s.open(device, 4, msg);
+	if (st != WHAMD_OK) return st;
+	Image im, wk;
+	char* dev_work = nullptr;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
+	wk.base = dev_work;
+	wk.total = work.total;
+	uint32_t *res_counts = nullptr, *res_npc = nullptr, *res_n_sel = nullptr, *res_sel = nullptr, *res_rows_n = nullptr;
+	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_counts, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_npc, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_n_sel, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(n_keys * sel_stride * sizeof(uint32_t), (void**)&res_sel, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(sizeof(uint32_t), (void**)&res_rows_n, msg)) != WHAMD_OK) return st;
+	// the image
+	for (size_t x = 0; x < ps.size(); x++) {
+		const ThreadProblem& p = ps[x];
+		PtRead* reads = im.host(p_reads) + read_base[x];
+		uint32_t* rptr = im.host(p_rptr) + read_base[x];
+		for (uint64_t r = 0; r < p.m.n_reads; r++) {
+			reads[r] = PtRead{p.reads[r].cluster, p.reads[r].rank, (uint32_t)pos_base[x]};
+			rptr[r] = (uint32_t)(ent_base[x] + p.m.row_ptr[r]);
+		}
+		std::fill_n(im.host(p_ploidy) + pos_base[x], p.m.n_positions, p.ploidy);
+		const uint64_t n = p.m.row_pos.size();
+		if (n) {
+			std::memcpy(im.host(p_rpos) + ent_base[x], p.m.row_pos.data(), n * sizeof(uint32_t));
+			std::memcpy(im.host(p_rallele) + ent_base[x], p.m.row_allele.data(), n);
+		}
+	}
+	im.host(p_rptr)[n_reads] = (uint32_t)n_entries;
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	HIP_TRY(hipMemsetAsync(dev_work, 0, zeroed, s.stream));
+	PtArgs a{};
+	a.reads = im.dev(p_reads);
+	a.read_ptr = im.dev(p_rptr);
+	a.row_pos = im.dev(p_rpos);
+	a.row_allele = im.dev(p_rallele);
+	a.pos_ploidy = im.dev(p_ploidy);
+	a.run = rs_bind(wk, w_run, n_keys, n_placed, PT_CLASS_A_MAX, PT_CLASS_B_MAX);
+	a.placed = wk.dev_out(w_placed);
+	a.npc = wk.dev_out(w_npc);
+	a.npc_local = wk.dev_out(w_npc_local);
+	a.npc_tile_sums = wk.dev_out(w_npc_tiles);
+	a.n_rows = wk.dev_out(w_n_rows);
+	a.n_sel = wk.dev_out(w_n_sel);
+	a.sel = wk.dev_out(w_sel);
+	a.n_reads = (uint32_t)n_reads;
+	a.n_entries = (uint32_t)n_entries;
+	a.n_pc = 0;
+	a.max_ploidy = max_ploidy;
+	const RunIndex& run = a.run;
+	const dim3 per_entry((uint32_t)((n_entries + RS_BLOCK - 1) / RS_BLOCK)), per_segment((uint32_t)((n_keys + RS_BLOCK / PT_SEGMENT - 1) / (RS_BLOCK / PT_SEGMENT)));
+	const dim3 per_key((uint32_t)((n_keys + RS_BLOCK - 1) / RS_BLOCK));
+	if ((st = rs_launch(s.stream, times, msg, polythread_count_kernel, per_entry, a)) != WHAMD_OK) return st;
+	if ((st = rs_scan(s.stream, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr)) != WHAMD_OK) return st;
+	if ((st = rs_launch(s.stream, times, msg, polythread_place_kernel, per_entry, a)) != WHAMD_OK) return st;
+	if ((st = launch_clusters_and_rows<4>(s.stream, times, msg, a, false, per_segment)) != WHAMD_OK) return st;
+	if ((st = rs_scan(s.stream, times, msg, a.npc, a.npc_local, a.npc_tile_sums, run.n_keys, nullptr, a.n_rows)) != WHAMD_OK) return st;
+	// the one wait in the middle of the call: the number of rows
+	if ((st = s.fetch(res_rows_n, a.n_rows, sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	HIP_TRY(hipStreamSynchronize(s.stream));
+	const uint64_t n_pc = *res_rows_n;
+	if (!n_pc || n_pc > n_placed) {
+		msg = "internal error: the rows and the counted entries disagree";
+		return WHAMD_ERR_DEVICE;
+	}
+	a.n_pc = (uint32_t)n_pc;
+	ImageLayout rows;
+	const auto r_cluster = rows.add<uint32_t>(n_pc);
+	const auto r_total = rows.add<uint32_t>(n_pc);
+	const auto r_depth = rows.add<uint32_t>(n_pc * na);
+	const auto r_first = rows.add<uint32_t>(n_pc * na);
+	const auto r_cons = rows.add<int8_t>(n_pc * max_ploidy);
+	char *dev_rows = nullptr, *res_rows = nullptr;
+	if ((st = s.device_block(rows.total, (void**)&dev_rows, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(rows.total, (void**)&res_rows, msg)) != WHAMD_OK) return st;
+	Image rw;
+	rw.base = dev_rows;
+	rw.stage = res_rows;
+	rw.total = rows.total;
+	a.pc_cluster = rw.dev_out(r_cluster);
+	a.pc_total = rw.dev_out(r_total);
+	a.pc_depth = rw.dev_out(r_depth);
+	a.pc_first = rw.dev_out(r_first);
+	a.pc_cons = rw.dev_out(r_cons);
+	HIP_TRY(hipMemsetAsync(a.pc_cons, 0, n_pc * max_ploidy, s.stream));
+	if (na == 4) st = launch_clusters_and_rows<4>(s.stream, times, msg, a, true, per_segment);
+	else st = launch_clusters_and_rows<16>(s.stream, times, msg, a, true, per_segment);
+	if (st != WHAMD_OK) return st;
+	PtSelectArgs sa{};
+	sa.total = a.pc_total;
+	sa.begin = nullptr;
+	sa.begin_local = a.npc_local;
+	sa.begin_tile_sums = a.npc_tile_sums;
+	sa.count = a.npc;
+	sa.pos_ploidy = a.pos_ploidy;
+	sa.n_sel = a.n_sel;
+	sa.sel = a.sel;
+	sa.n_keys = (uint32_t)n_keys;
+	sa.n_total = (uint32_t)n_pc;
+	sa.ploidy = 0;
+	sa.stride = sel_stride;
+	if ((st = rs_launch(s.stream, times, msg, polythread_select_kernel, per_key, sa)) != WHAMD_OK) return st;
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_counts, run.counts, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_npc, a.npc, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_n_sel, a.n_sel, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_sel, a.sel, n_keys * sel_stride * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res_rows, dev_rows, rows.total, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	// back to the problems
+	uint64_t row_at = 0;
+	for (size_t x = 0; x < ps.size(); x++) {
+		const ThreadProblem& p = ps[x];
+		ThreadRows& o = out[x];
+		const uint64_t n_pos = p.m.n_positions, stride = p.ploidy + 2;
+		o.na = na;
+		o.npc.assign(res_npc + pos_base[x], res_npc + pos_base[x + 1]);
+		uint64_t mine = 0;
+		for (uint32_t c : o.npc) mine += c;
+		if (row_at + mine > n_pc) {
+			msg = "internal error: the rows and their counts per position disagree";
+			return WHAMD_ERR_DEVICE;
+		}
+		o.cluster.assign(rw.host(r_cluster) + row_at, rw.host(r_cluster) + row_at + mine);
+		o.total.assign(rw.host(r_total) + row_at, rw.host(r_total) + row_at + mine);
+		o.depth.assign(rw.host(r_depth) + row_at * na, rw.host(r_depth) + (row_at + mine) * na);
+		o.first.assign(rw.host(r_first) + row_at * na, rw.host(r_first) + (row_at + mine) * na);
+		o.cons.resize(mine * p.ploidy);
+		for (uint64_t r = 0; r < mine; r++) std::memcpy(o.cons.data() + r * p.ploidy, rw.host(r_cons) + (row_at + r) * max_ploidy, p.ploidy);
+		o.n_sel.assign(n_pos, 0);
+		o.sel.assign(n_pos * stride, 0);
+		for (uint64_t y = 0; y < n_pos; y++) {
+			const uint64_t v = pos_base[x] + y;
+			const uint32_t c = res_counts[v], m = res_n_sel[v];
+			if (c) ++(c <= PT_CLASS_A_MAX ? o.class_a : c <= PT_CLASS_B_MAX ? o.class_b : o.class_c);
+			if (m > stride || m > o.npc[y]) {
+				msg = "internal error: a position's selection is longer than its rows";
+				return WHAMD_ERR_DEVICE;
+			}
+			o.n_sel[y] = m;
+			for (uint32_t k = 0; k < m; k++) {
+				o.sel[y * stride + k] = res_sel[v * sel_stride + k];
+				if (o.sel[y * stride + k] >= o.npc[y]) {
+					msg = "internal error: a selected row outside its position";
+					return WHAMD_ERR_DEVICE;
+				}
+			}
+		}
+		row_at += mine;
+	}
+	return WHAMD_OK;
+}
+
+whamd_status_t polythread_select_device(const std::vector<uint32_t>& begin, const std::vector<uint32_t>& count, const std::vector<uint32_t>& total, uint32_t ploidy,
+                                        int device, std::vector<uint32_t>& n_sel, std::vector<uint32_t>& sel, CallTimes& times, std::string& msg) {
+	times = CallTimes{};
+	const uint64_t n_keys = count.size(), stride = ploidy + 2;
+	n_sel.assign(n_keys, 0);
+	sel.assign(n_keys * stride, 0);
+	if (!n_keys) return WHAMD_OK;
+	if (n_keys * stride >= 0xfffff000ull) {
+		msg = "2^32 - 4096 or more list slots in one call";
+		return WHAMD_ERR_UNSUPPORTED;
+	}
+	ImageLayout in;
+	const auto p_begin = in.add<uint32_t>(n_keys);
+	const auto p_count = in.add<uint32_t>(n_keys);
+	const auto p_total = in.add<uint32_t>(total.size());
+	ImageLayout work;
+	const auto w_n_sel = work.add<uint32_t>(n_keys);
+	const auto w_sel = work.add<uint32_t>(n_keys * stride);
+	Session s;
+	whamd_status_t st = s.open(device, 4, msg);
+	if (st != WHAMD_OK) return st;
+	Image im, wk;
+	char* dev_work = nullptr;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(work.total, (void**)&wk.stage, msg)) != WHAMD_OK) return st;
+	wk.base = dev_work;
+	wk.total = work.total;
+	std::memcpy(im.host(p_begin), begin.data(), n_keys * sizeof(uint32_t));
+	std::memcpy(im.host(p_count), count.data(), n_keys * sizeof(uint32_t));
+	if (!total.empty()) std::memcpy(im.host(p_total), total.data(), total.size() * sizeof(uint32_t));
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	PtSelectArgs sa{};
+	sa.total = im.dev(p_total);
+	sa.begin = im.dev(p_begin);
+	sa.count = im.dev(p_count);
+	sa.pos_ploidy = nullptr;
+	sa.n_sel = wk.dev_out(w_n_sel);
+	sa.sel = wk.dev_out(w_sel);
+	sa.n_keys = (uint32_t)n_keys;
+	sa.n_total = (uint32_t)total.size();
+	sa.ploidy = ploidy;
+	sa.stride = (uint32_t)stride;
+	if ((st = rs_launch(s.stream, times, msg, polythread_select_kernel, dim3((uint32_t)((n_keys + RS_BLOCK - 1) / RS_BLOCK)), sa)) != WHAMD_OK) return st;
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(wk.stage, dev_work, work.total, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	std::memcpy(n_sel.data(), wk.host(w_n_sel), n_keys * sizeof(uint32_t));
+	std::memcpy(sel.data(), wk.host(w_sel), n_keys * stride * sizeof(uint32_t));
+	for (uint64_t v = 0; v < n_keys; v++) {
+		bool ok = n_sel[v] <= stride && n_sel[v] <= count[v];
+		for (uint32_t k = 0; ok && k < n_sel[v]; k++) ok = sel[v * stride + k] < count[v];
+		if (!ok) {
+			msg = "internal error: a position's selection does not fit its rows";
+			return WHAMD_ERR_DEVICE;
+		}
+	}
+	return WHAMD_OK;
+}
+
+whamd_status_t polythread_haplotypes_device(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
+                                            const int8_t* pc_cons, int device, std::vector<int8_t>& out, CallTimes& times, std::string& msg) {
+	times = CallTimes{};
+	out.assign(n_pos * ploidy, -1);
+	if (!n_pos) return WHAMD_OK;
+	const uint64_t n_rows = pc_ptr[n_pos];
+	ImageLayout in;
+	const auto p_paths = in.add<uint32_t>(n_pos * ploidy);
+	const auto p_begin = in.add<uint32_t>(n_pos + 1);
+	const auto p_cluster = in.add<uint32_t>(n_rows);
+	const auto p_cons = in.add<int8_t>(n_rows * ploidy);
+	Session s;
+	whamd_status_t st = s.open(device, 4, msg);
+	if (st != WHAMD_OK) return st;
+	Image im;
+	int8_t *dev_out = nullptr, *res = nullptr;
+	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	if ((st = s.device_block(n_pos * ploidy, (void**)&dev_out, msg)) != WHAMD_OK) return st;
+	if ((st = s.pinned_block(n_pos * ploidy, (void**)&res, msg)) != WHAMD_OK) return st;
+	std::memcpy(im.host(p_paths), paths, n_pos * ploidy * sizeof(uint32_t));
+	for (uint64_t x = 0; x <= n_pos; x++) im.host(p_begin)[x] = (uint32_t)pc_ptr[x];
+	if (n_rows) {
+		std::memcpy(im.host(p_cluster), pc_cluster, n_rows * sizeof(uint32_t));
+		std::memcpy(im.host(p_cons), pc_cons, n_rows * ploidy);
+	}
+	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	PtHaplotypeArgs ha{im.dev(p_paths), im.dev(p_begin), im.dev(p_cluster), im.dev(p_cons), dev_out, (uint32_t)n_pos, ploidy};
+	if ((st = rs_launch(s.stream, times, msg, polythread_haplotypes_kernel, dim3((uint32_t)((n_pos + RS_BLOCK - 1) / RS_BLOCK)), ha)) != WHAMD_OK) return st;
+	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
+	if ((st = s.fetch(res, dev_out, n_pos * ploidy, msg)) != WHAMD_OK) return st;
+	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	std::memcpy(out.data(), res, n_pos * ploidy);
+	return WHAMD_OK;
+}
+
+}  // namespace whamd
