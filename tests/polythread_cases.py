@@ -263,6 +263,50 @@ def long_run_case():
     return case("long_run", reads, clustering, 3, 4)
 
 
+def sixteen_allele_long_runs_case(deep=4200, wide=300):
+    """Ploidy 16, all sixteen alleles: one position of ``deep`` entries (one workgroup: more than PT_CLASS_B_MAX = 4096), one of ``wide``
+    (one wave), each over four clusters and every allele, next to positions of one entry."""
+    rng = np.random.default_rng(16)
+
+    def spread(total, clusters):
+        """total entries over the clusters and the sixteen alleles, every (cluster, allele) at least once."""
+        cells = rng.multinomial(total - 16 * len(clusters), np.full(16 * len(clusters), 1.0 / (16 * len(clusters)))) + 1
+        return {c: cells[16 * k:16 * k + 16].tolist() for k, c in enumerate(clusters)}
+
+    one = lambda c, allele: {c: [0] * allele + [1]}
+    table = [one(0, 3), spread(wide, (0, 2, 3, 5)), one(4, 15), one(1, 0), spread(deep, (1, 2, 4, 5)), one(5, 9), one(3, 7)]
+    return from_depths("sixteen_alleles_long_runs", table, 16, 2, reverse=(2, 5))
+
+
+# The reads around a workgroup's edge (256 entries per workgroup in the count and place launches): entries 255 and 256 are single-entry
+# reads with empty reads before, between and behind.
+EDGE_READ_LENGTHS = (0, 255, 0, 0, 1, 1, 0, 343, 0)
+
+
+def edge_read_ptr(n_entries=600):
+    """EDGE_READ_LENGTHS as offsets, the reads cut at ``n_entries`` (the reads behind the cut stay, empty)."""
+    ptr = np.minimum(np.concatenate([[0], np.cumsum(EDGE_READ_LENGTHS)]), n_entries)
+    assert ptr[-1] == n_entries
+    return ptr.astype(np.uint64)
+
+
+def edge_reads_arrays(n_entries=600, n_clusters=5):
+    """A block on the reads of edge_read_ptr: a read's k-th entry lies at position k (the matrix keeps one entry per read and position,
+    so a read of 343 entries needs as many positions), a single-entry read's in the middle of the block; the alleles are random, every
+    read -- the empty ones too -- is in one of ``n_clusters`` clusters."""
+    rng = np.random.default_rng(600 + n_entries)
+    read_ptr = edge_read_ptr(n_entries)
+    lengths = np.diff(read_ptr.astype(np.int64))
+    local = np.arange(n_entries) - np.repeat(read_ptr[:-1].astype(np.int64), lengths)
+    single = np.flatnonzero(np.repeat(lengths, lengths) == 1)
+    if n_entries > 1:
+        local[single] = 100 + 50 * np.arange(single.size)
+    alle = rng.integers(0, 2, size=n_entries)
+    cluster_of = rng.integers(0, n_clusters, size=len(read_ptr) - 1)
+    clustering = [rng.permutation(np.flatnonzero(cluster_of == c)).astype(np.uint32) for c in range(n_clusters)]
+    return read_ptr, 100 + 7 * local, alle, clustering
+
+
 # ---------------------------------------------------------------------------------------------- what both test files share
 def load_golden():
     import gzip

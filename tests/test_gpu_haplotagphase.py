@@ -100,6 +100,34 @@ def test_waves_of_a_workgroup_that_meet_different_phase_sets():
     assert dev[1].stats["variants_class_c"] == 2 and dev[1].stats["variants_many_phase_sets"] == 0
 
 
+EDGE_READ_LENGTHS = (0, 255, 0, 0, 1, 1, 0, 343, 0)
+
+
+def edge_reads_problem(n_entries):
+    """The reads around a workgroup's edge (256 entries per workgroup in the count and place launches), from arrays: entries 255 and 256
+    are single-entry reads with empty reads before, between and behind; cut at n_entries (the reads behind the cut stay, empty).  Every
+    read votes: twenty heterozygous variants, R + 1 phase sets."""
+    rng = np.random.default_rng(600 + n_entries)
+    read_ptr = np.minimum(np.concatenate([[0], np.cumsum(EDGE_READ_LENGTHS)]), n_entries).astype(np.uint64)
+    n_reads = len(EDGE_READ_LENGTHS)
+    flags = rng.choice(np.array([0, tp.PHASED, tp.SNV, tp.PHASED | tp.SNV], dtype=np.uint8), size=20)
+    tags = rng.integers(0, 1 << 40, size=R + 1, dtype=np.int64)
+    read_ps = tags[[R, 0, R, 2, 1, 2, 3, 3, 0]]   # (the four reads with entries carry four of them)
+    return tp.TagphaseProblem(flags, read_ptr, rng.integers(0, 20, size=n_entries), rng.integers(0, 2, size=n_entries),
+                              rng.integers(1, 61, size=n_entries, dtype=np.int64), read_ps, rng.integers(0, 2, size=n_reads).astype(np.int32), 60.0, False)
+
+
+@pytest.mark.parametrize("n_entries", [1, 256, 257, 600])
+@pytest.mark.parametrize("want_table", [False, True])
+def test_reads_at_a_workgroup_edge(n_entries, want_table):
+    """The read lookup where a workgroup's 256 entries end, and the same reads cut to 1, 256 and 257 entries."""
+    res = device_and_host([edge_reads_problem(n_entries)], want_table=want_table)[0]
+    s = res.stats
+    assert s["n_reads"] == len(EDGE_READ_LENGTHS) and s["n_entries"] == s["n_voting"] == n_entries
+    assert s["launches"] == (LAUNCHES_TABLE if want_table else LAUNCHES)
+    assert int(res.n_phasesets.max()) >= (2 if n_entries == 600 else 1)   # (the two long reads carry different phase sets)
+
+
 def test_two_calls_on_one_input_give_identical_bytes():
     """The order inside a run is whatever the atomics gave; it must not show."""
     p = hc.array_problem(hc.heavy_tail_runs(3_000, seed=8, mean=20, tail=0.01, tail_max=9_000), seed=9, n_phasesets=5, quality=(1, 2))

@@ -93,6 +93,27 @@ def test_sixteen_alleles_and_ploidy_sixteen():
     same_bytes([pc.problem_of_arrays(arrays, 16, 3), pc.problem_of_arrays(pc.array_problem(23, 50, 9, 2, 2, 5, 1), 2, 0)])
 
 
+def test_sixteen_alleles_in_one_wave_and_in_one_workgroup():
+    """The sixteen-allele rows of class b (one wave) and class c (one workgroup): a position of 300 entries and one of 4 200, each over
+    four clusters and all sixteen alleles, ploidy 16, next to positions of one entry."""
+    got, stats = same_bytes([pc.problem_of(pc.sixteen_allele_long_runs_case())])
+    s = stats[0]
+    assert s["positions_class_b"] >= 1 and s["positions_class_c"] >= 1 and s["positions_class_a"] == 5
+    assert got[0].n_alleles == 16 and got[0].pc_depth.shape[1] == 16   # (more than four alleles: the rows keep NA = 16)
+    assert s["n_counted"] == 4200 + 300 + 5 and int(got[0].pc_depth.sum()) <= s["n_counted"]   # (emptied rows count no more)
+
+
+@pytest.mark.parametrize("n_entries", [1, 256, 257, 600])
+def test_reads_at_a_workgroup_edge(n_entries):
+    """The read lookup of the count and place launches where a workgroup's 256 entries end: single-entry reads at entries 255 and 256
+    with empty reads before, between and behind them (polythread_cases.EDGE_READ_LENGTHS), and the same reads cut to 1, 256 and 257
+    entries.  AlleleMatrix.from_csr takes reads without entries as they are."""
+    arrays = pc.edge_reads_arrays(n_entries)
+    assert np.diff(arrays[0].astype(np.int64)).tolist() == np.diff(np.minimum(np.cumsum((0,) + pc.EDGE_READ_LENGTHS), n_entries)).tolist()
+    got, stats = same_bytes([pc.problem_of_arrays(arrays, 2, 3)])
+    assert stats[0]["n_entries"] == stats[0]["n_counted"] == n_entries and stats[0]["n_reads"] == len(pc.EDGE_READ_LENGTHS)
+
+
 def test_a_batch_of_200_blocks_and_the_launch_count():
     blocks = [pc.problem_of_arrays(arrays, ploidy, gap) for arrays, ploidy, gap in pc.small_blocks(200)]
     got, stats = same_bytes(blocks)

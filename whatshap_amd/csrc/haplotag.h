@@ -17,6 +17,7 @@
 #include "../../include/whatshap_amd.h"
 #include "call_image.h"
 #include "host_parallel.h"
+#include "run_scatter.h"
 
 #if defined(__HIPCC__)
 #define WHAMD_HD __host__ __device__
@@ -32,6 +33,7 @@ constexpr uint32_t HT_SEGMENT = 8;                // lanes per group in class a
 constexpr uint32_t HT_CLASS_A_MAX = 64;           // class a: 1 .. 64 entries (at most 8 per lane of a segment)
 constexpr uint32_t HT_CLASS_B_MAX = 4096;         // class b: 65 .. 4096 entries (one wave, at most 64 per lane); class c beyond (one workgroup)
 constexpr uint32_t HT_BLOCK = 256;                // threads per workgroup, all classes
+static_assert(HT_BLOCK == RS_BLOCK, "class c's workgroup is the shared teams' (run_teams.h BlockScope)");
 constexpr uint32_t HT_MAX_PHASESETS = 1u << 27;   // per problem (the count shares a word with the haplotype in HtOut)
 constexpr uint32_t HT_NO_BX = 0xffffffffu;
 

@@ -9,13 +9,13 @@
 //   class c   (more)             one workgroup per group: every wave takes a contiguous quarter of the run, the quarters meet in LDS.
 // (The upload is one image of three typed pieces, call_image.h; the call runs through the steps of Session, device_runtime.h.)
 // A team (segment, wave) walks its run in chunks of its width, in order.  It keeps up to R = 4 phase sets in registers, in the order of
-// their first matching entry: the lanes of a chunk whose phase set has no slot yet are found with a ballot, the lowest of them names the
-// next slot (a chunk is consecutive entries, so the lowest lane is the first encounter).  Every lane adds its entry's quality to the sums of
-// its slot under the entry's haplotype mask (R x P predicated adds, P = the launch's ploidy rounded up to 2, 4, 8 or 16); the sums meet in
-// a butterfly of the team.  A group with more than R phase sets takes the slower route: one pass over its run per phase set, in the order
-// of the ids (the next id is the minimum above the last), summing that phase set alone and keeping the index of its first matching
-// entry.  Both routes hand (sums, phase set, first index) to ht_consider (haplotag.h, shared with the host twin), which is independent of
-// the order in which the phase sets arrive.  One lane per group writes the 16-byte result; nothing is reduced through global memory.
+// their first matching entry (SlotNames of run_teams.h; its hook records the index of the entry that names a slot).  Every lane adds its
+// entry's quality to the sums of its slot under the entry's haplotype mask (R x P predicated adds, P = the launch's ploidy rounded up to
+// 2, 4, 8 or 16); the sums meet in a butterfly of the team.  A group with more than R phase sets takes the slower route: walk_ids of
+// run_teams.h over its phase sets in the order of the ids, the body summing that phase set alone and keeping the index of its first
+// matching entry (PsAcc, combined by the team's scope).  Both routes hand (sums, phase set, first index) to ht_consider (haplotag.h,
+// shared with the host twin), which is independent of the order in which the phase sets arrive.  One lane per group writes the 16-byte
+// result; nothing is reduced through global memory.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,14 +23,14 @@
 
 #include "device_runtime.h"
 #include "haplotag.h"
-#include "run_scatter.h"   // team_sum, team_min
+#include "run_teams.h"
 
 namespace whamd {
 namespace {
 
 constexpr int R = (int)HT_REG_PHASESETS;
-constexpr int NW = (int)HT_BLOCK / 64;
-constexpr uint32_t NO_PS = 0xffffffffu;
+constexpr int NW = RT_WAVES;
+constexpr uint32_t NO_PS = RT_NONE;
 
 struct HtArgs {
 	const HtEntry* entries;
@@ -40,12 +40,29 @@ struct HtArgs {
 	uint32_t n_groups;
 };
 
+// The register route's phase sets (SlotNames, run_teams.h) with their sums and the index of their first matching entry.
 template <int P>
-struct Slots {
+struct Slots : SlotNames<R> {
 	int64_t s[R][P];
-	uint32_t ps[R], first[R];
-	uint32_t n;
-	bool overflow;
+	uint32_t first[R];
+};
+
+// One phase set on the pass-per-phase-set route: its sums and the index of its first matching entry.
+template <int P>
+struct PsAcc {
+	int64_t s[P];
+	uint32_t first;
+	template <int W>
+	__device__ void across() {
+#pragma unroll
+		for (int h = 0; h < P; h++) s[h] = team_sum<W>(s[h]);
+		first = team_min<W>(first);
+	}
+	__device__ void merge(const PsAcc& o) {
+#pragma unroll
+		for (int h = 0; h < P; h++) s[h] += o.s[h];
+		first = min(first, o.first);
+	}
 };
 
 // Entry i of the run, or a no-match entry beyond it.
@@ -66,11 +83,9 @@ __device__ inline void load_entry(const HtArgs& a, const HtEntry* run, uint32_t 
 // index0: index, in the whole group, of run[0].  Every lane of the wave calls this together; n, index0 are the team's.
 template <int P, int W>
 __device__ inline void scan_run(const HtArgs& a, const HtEntry* run, uint32_t n, uint32_t index0, uint32_t l, uint64_t teammask, uint32_t lane0, Slots<P>& S) {
-	S.n = 0;
-	S.overflow = false;
+	S.clear();
 #pragma unroll
 	for (int s = 0; s < R; s++) {
-		S.ps[s] = NO_PS;
 		S.first[s] = 0;
 #pragma unroll
 		for (int h = 0; h < P; h++) S.s[s][h] = 0;
@@ -79,30 +94,7 @@ __device__ inline void scan_run(const HtArgs& a, const HtEntry* run, uint32_t n,
 		uint32_t ps, match;
 		int64_t q;
 		load_entry(a, run, base + l, n, !S.overflow, ps, match, q);
-		int slot = -1;
-#pragma unroll
-		for (int s = 0; s < R; s++)
-			if (match && S.ps[s] == ps) slot = s;
-		for (;;) {
-			const uint64_t un = __ballot(match != 0 && slot < 0 && !S.overflow) & teammask;
-			if (!__any(un != 0)) break;
-			const uint32_t src = un ? (uint32_t)__ffsll((unsigned long long)un) - 1 : lane0 + l;
-			const uint32_t fresh = (uint32_t)__shfl((int)ps, (int)src);
-			if (un) {
-				if (S.n < (uint32_t)R) {
-#pragma unroll
-					for (int s = 0; s < R; s++)
-						if (S.n == (uint32_t)s) {
-							S.ps[s] = fresh;
-							S.first[s] = index0 + base + (src - lane0);
-						}
-					if (match && ps == fresh) slot = (int)S.n;
-					S.n++;
-				} else {
-					S.overflow = true;
-				}
-			}
-		}
+		const int slot = S.claim(match != 0, ps, teammask, lane0 + l, [&](int s, uint32_t src) { S.first[s] = index0 + base + (src - lane0); });
 #pragma unroll
 		for (int s = 0; s < R; s++)
 #pragma unroll
@@ -116,95 +108,39 @@ __device__ inline void scan_run(const HtArgs& a, const HtEntry* run, uint32_t n,
 		}
 }
 
-// Who owns a group on the pass-per-phase-set route: how far apart its lanes' entries lie and how its lanes combine a minimum and a phase set's sums.
-template <int W>
-struct TeamScope {
-	static constexpr uint32_t STRIDE = W;
-	__device__ uint32_t all_min(uint32_t v) const { return team_min<W>(v); }
-	template <int P>
-	__device__ void all_sums(int64_t (&sums)[P], uint32_t& first) const {
-#pragma unroll
-		for (int h = 0; h < P; h++) sums[h] = team_sum<W>(sums[h]);
-		first = team_min<W>(first);
-	}
-};
-template <int P>
-struct BlockScope {   // (one group per workgroup: every thread takes the same branches, so the barriers are met by all)
-	static constexpr uint32_t STRIDE = HT_BLOCK;
-	uint32_t* word;          // LDS [NW]
-	int64_t (*part)[P];      // LDS [NW][P]
-	uint32_t lane, w;
-	__device__ uint32_t all_min(uint32_t v) const {
-		v = team_min<64>(v);
-		if (lane == 0) word[w] = v;
-		__syncthreads();
-		v = word[0];
-#pragma unroll
-		for (int ww = 1; ww < NW; ww++) v = min(v, word[ww]);
-		__syncthreads();
-		return v;
-	}
-	__device__ void all_sums(int64_t (&sums)[P], uint32_t& first) const {
-#pragma unroll
-		for (int h = 0; h < P; h++) sums[h] = team_sum<64>(sums[h]);
-		first = team_min<64>(first);
-		if (lane == 0) {
-			word[w] = first;
-#pragma unroll
-			for (int h = 0; h < P; h++) part[w][h] = sums[h];
-		}
-		__syncthreads();
-		first = word[0];
-#pragma unroll
-		for (int h = 0; h < P; h++) sums[h] = part[0][h];
-#pragma unroll
-		for (int ww = 1; ww < NW; ww++) {
-			first = min(first, word[ww]);
-#pragma unroll
-			for (int h = 0; h < P; h++) sums[h] += part[ww][h];
-		}
-		__syncthreads();
-	}
-};
-
-// The pass-per-phase-set route for the owners with `need` (the other teams of the wave walk along idle): phase sets in id order, per
-// phase set one pass for the next id and one for its sums and first matching entry.  Lane l of the owner takes entries l, l + STRIDE, ...
+// The pass-per-phase-set route for the owners with `need`: walk_ids over the phase sets with a matching entry; per phase set a second
+// pass for its sums and first matching entry, which go to ht_consider.  Returns the number of phase sets.
 template <int P, class Scope>
-__device__ inline void pass_per_phase_set(const HtArgs& a, const HtEntry* run, uint32_t n, uint32_t ploidy, uint32_t l, bool need, const Scope& scope, HtBest& best,
-                                          uint32_t& n_ps) {
-	bool active = need;
-	uint32_t lower = 0;
-	while (__any(active)) {
-		uint32_t next = NO_PS;
-		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-			uint32_t ps, match;
-			int64_t q;
-			load_entry(a, run, base + l, n, active, ps, match, q);
-			if (match && ps >= lower) next = min(next, ps);
-		}
-		next = scope.all_min(next);
-		if (next == NO_PS) active = false;
-		int64_t sums[P];
+__device__ inline uint32_t pass_per_phase_set(const HtArgs& a, const HtEntry* run, uint32_t n, uint32_t ploidy, uint32_t l, bool need, const Scope& scope, HtBest& best) {
+	const auto entry = [&](uint32_t i, uint32_t& match, int64_t& q) {
+		uint32_t ps;
+		load_entry(a, run, i, n, true, ps, match, q);
+		return match ? ps : NO_PS;
+	};
+	return walk_ids(
+	    scope, n, l, need,
+	    [&](uint32_t i) {
+		    uint32_t match;
+		    int64_t q;
+		    return entry(i, match, q);
+	    },
+	    [&](uint32_t next, bool active, uint32_t) {
+		    PsAcc<P> acc;
 #pragma unroll
-		for (int h = 0; h < P; h++) sums[h] = 0;
-		uint32_t first = NO_PS;
-		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-			uint32_t ps, match;
-			int64_t q;
-			load_entry(a, run, base + l, n, active, ps, match, q);
-			if (match && ps == next) {
-				first = min(first, base + l);
+		    for (int h = 0; h < P; h++) acc.s[h] = 0;
+		    acc.first = NO_PS;
+		    team_pass<Scope>(n, l, active, [&](uint32_t i) {
+			    uint32_t match;
+			    int64_t q;
+			    if (entry(i, match, q) == next) {
+				    acc.first = min(acc.first, i);
 #pragma unroll
-				for (int h = 0; h < P; h++) sums[h] += (match >> h & 1) ? q : 0;
-			}
-		}
-		scope.all_sums(sums, first);
-		if (active) {
-			ht_consider<P>(best, sums, ploidy, next, first);
-			n_ps++;
-			lower = next + 1;
-		}
-	}
+				    for (int h = 0; h < P; h++) acc.s[h] += (match >> h & 1) ? q : 0;
+			    }
+		    });
+		    scope.combine(acc);
+		    if (active) ht_consider<P>(best, acc.s, ploidy, next, acc.first);
+	    });
 }
 
 // Classes a and b: W lanes per group.
@@ -228,7 +164,7 @@ __global__ void __launch_bounds__(HT_BLOCK) haplotag_team_kernel(HtArgs a) {
 			if ((uint32_t)s < S.n) ht_consider<P>(best, S.s[s], grp.ploidy, S.ps[s], S.first[s]);
 		n_ps = S.n;
 	}
-	if (__any(S.overflow)) pass_per_phase_set<P>(a, run, grp.n, grp.ploidy, l, S.overflow, TeamScope<W>{}, best, n_ps);
+	if (__any(S.overflow)) n_ps += pass_per_phase_set<P>(a, run, grp.n, grp.ploidy, l, S.overflow, TeamScope<W>{}, best);
 	if (have && l == 0) a.out[g] = ht_result(best, n_ps);
 }
 
@@ -237,7 +173,7 @@ template <int P>
 __global__ void __launch_bounds__(HT_BLOCK) haplotag_block_kernel(HtArgs a) {
 	__shared__ int64_t w_sums[NW][R][P];
 	__shared__ uint32_t w_ps[NW][R], w_first[NW][R], w_n[NW], w_overflow[NW];
-	__shared__ int64_t r_sums[NW][P];
+	__shared__ PsAcc<P> r_part[NW];
 	__shared__ uint32_t r_word[NW];
 	__shared__ uint32_t go_slow;
 	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -295,8 +231,7 @@ __global__ void __launch_bounds__(HT_BLOCK) haplotag_block_kernel(HtArgs a) {
 	__syncthreads();
 	if (!go_slow) return;
 	HtBest best{};
-	uint32_t n_ps = 0;
-	pass_per_phase_set<P>(a, run, grp.n, grp.ploidy, threadIdx.x, true, BlockScope<P>{r_word, r_sums, lane, w}, best, n_ps);
+	const uint32_t n_ps = pass_per_phase_set<P>(a, run, grp.n, grp.ploidy, threadIdx.x, true, BlockScope<PsAcc<P>>{r_word, r_part, lane, w}, best);
 	if (threadIdx.x == 0) a.out[blockIdx.x] = ht_result(best, n_ps);
 }
 

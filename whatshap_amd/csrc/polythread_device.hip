@@ -3,17 +3,16 @@
 // key "position of the call" (the problem's first position plus the local one):
 //   upload    per read {cluster, rank in the cluster's list, first position of its problem} and its first row entry, the row entries
 //             (local position, allele), per position the ploidy of its problem.
-//   count     one thread per row entry: its read (a search of the read offsets, narrowed to the reads of the workgroup's 256 entries);
-//             a read in no cluster is not counted (RS_NONE).
+//   count     one thread per row entry: its read (read_of_entry, run_teams.h); a read in no cluster is not counted (RS_NONE).
 //   scan      exclusive, two launches; also appends the positions of more than 64 / 4096 entries to the class b / c list.
 //   place     a counted entry goes to its position's run as {cluster, rank << 4 | allele}.  The order inside a run is whatever the
 //             atomics give; nothing below depends on it.
 //   clusters  one team per position -- class a eight lanes over all positions, class b one wave, class c one workgroup (any length),
-//             both walking their list with a fixed grid -- counts the distinct clusters of the run: one pass per cluster for the
-//             smallest cluster not below the last one's successor.
+//             both walking their list with a fixed grid -- counts the distinct clusters of the run: walk_ids of run_teams.h (scopes
+//             and walk are shared with haplotagging and haplotagphase) with an empty body.
 //   scan      of those counts: where every position's rows begin, and how many there are (the one wait of the call, to size the rows).
-//   rows      the same teams, the same passes, and per cluster a second pass for the depth of every allele and the smallest rank of a
-//             read with it (sums and minima: no order); the team's first lane writes the row and its consensus list (pt_consensus).
+//   rows      the same teams, the same walk; its body is a second pass for the depth of every allele and the smallest rank of a read
+//             with it (RowAcc; sums and minima: no order), and the team's first lane writes the row and its consensus list (pt_consensus).
 //   select    one thread per position: pt_select over the totals of its rows.
 // 13 launches per call whatever the problems (PT_LAUNCHES).  The rows keep NA = 4 or 16 alleles, by the largest n_alleles of the call.
 #include <hip/hip_runtime.h>
@@ -23,11 +22,12 @@
 
 #include "device_runtime.h"
 #include "polythread.h"
+#include "run_teams.h"
 
 namespace whamd {
 namespace {
 
-constexpr int NW = (int)RS_BLOCK / 64;
+constexpr int NW = RT_WAVES;
 
 struct PtArgs {
 	// the image
@@ -54,23 +54,11 @@ struct PtArgs {
 };
 
 // ---------------------------------------------------------------------------------------------- count, place
-// The largest r in [lo, hi] with read_ptr[r] <= i (read_ptr[lo] <= i).
-__device__ inline uint32_t find_read(const uint32_t* read_ptr, uint32_t lo, uint32_t hi, uint32_t i) {
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo + 1) / 2;
-		if (read_ptr[mid] <= i) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
-
 // Row entry i of the call: the position it is counted at (PT_NONE: its read is in no cluster) and what is placed for it.
 __device__ inline uint32_t counted_position(const PtArgs& a, uint32_t i, PtPlaced& what) {
 	what = PtPlaced{0, 0};
 	if (i >= a.n_entries) return PT_NONE;
-	const uint32_t i0 = blockIdx.x * RS_BLOCK, i1 = min(i0 + RS_BLOCK - 1, a.n_entries - 1);
-	const uint32_t lo = find_read(a.read_ptr, 0, a.n_reads - 1, i0), hi = find_read(a.read_ptr, lo, a.n_reads - 1, i1);
-	const PtRead rd = a.reads[find_read(a.read_ptr, lo, hi, i)];
+	const PtRead rd = a.reads[read_of_entry(a.read_ptr, a.n_reads, a.n_entries, i)];
 	if (rd.cluster == PT_NONE) return PT_NONE;
 	const uint32_t v = rd.pos_base + a.row_pos[i];
 	if (v >= a.run.n_keys) return PT_NONE;
@@ -92,129 +80,67 @@ __global__ void __launch_bounds__(RS_BLOCK) polythread_place_kernel(PtArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- a run, cluster by cluster
-template <int W>
-__device__ inline uint32_t team_add(uint32_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-	return v;
-}
-
-// Who owns a position: how far apart its lanes' entries lie and how they combine a minimum and a cluster's counts.
-template <int W>
-struct TeamScope {
-	static constexpr uint32_t STRIDE = W;
-	__device__ uint32_t all_min(uint32_t v) const { return team_min<W>(v); }
-	template <int NA>
-	__device__ void all_rows(uint32_t (&cnt)[NA], uint32_t (&first)[NA]) const {
+// One cluster of a run: per allele the depth and the smallest rank of a read with it.
+template <int NA>
+struct RowAcc {
+	uint32_t cnt[NA], first[NA];
+	template <int W>
+	__device__ void across() {
 #pragma unroll
 		for (int x = 0; x < NA; x++) {
-			cnt[x] = team_add<W>(cnt[x]);
+			cnt[x] = team_sum<W>(cnt[x]);
 			first[x] = team_min<W>(first[x]);
 		}
 	}
-};
-struct BlockScope {   // (one position per workgroup: every thread takes the same branches, so the barriers are met by all)
-	static constexpr uint32_t STRIDE = RS_BLOCK;
-	uint32_t* word;    // LDS [NW]
-	uint32_t* cnts;    // LDS [NW][16]
-	uint32_t* firsts;  // LDS [NW][16]
-	uint32_t lane, w;
-	__device__ uint32_t all_min(uint32_t v) const {
-		v = team_min<64>(v);
-		if (lane == 0) word[w] = v;
-		__syncthreads();
-		v = word[0];
-#pragma unroll
-		for (int ww = 1; ww < NW; ww++) v = min(v, word[ww]);
-		__syncthreads();
-		return v;
-	}
-	template <int NA>
-	__device__ void all_rows(uint32_t (&cnt)[NA], uint32_t (&first)[NA]) const {
+	__device__ void merge(const RowAcc& o) {
 #pragma unroll
 		for (int x = 0; x < NA; x++) {
-			cnt[x] = team_add<64>(cnt[x]);
-			first[x] = team_min<64>(first[x]);
-			if (lane == 0) {
-				cnts[w * 16 + x] = cnt[x];
-				firsts[w * 16 + x] = first[x];
-			}
+			cnt[x] += o.cnt[x];
+			first[x] = min(first[x], o.first[x]);
 		}
-		__syncthreads();
-#pragma unroll
-		for (int x = 0; x < NA; x++) {
-			cnt[x] = cnts[x];
-			first[x] = firsts[x];
-#pragma unroll
-			for (int ww = 1; ww < NW; ww++) {
-				cnt[x] += cnts[ww * 16 + x];
-				first[x] = min(first[x], firsts[ww * 16 + x]);
-			}
-		}
-		__syncthreads();
 	}
 };
 
-// The clusters of run[0, n) in ascending order, for the owners with `need` (the other teams of the wave walk along idle); lane l of the
-// owner takes entries l, l + STRIDE, ...  Returns how many there are.  ROWS: the owner's `leader` lane also writes one row per cluster from
-// row0 on, at most max_rows and none at or beyond a.n_pc.
+// The clusters of run[0, n) in ascending order (walk_ids), for the owners with `need`.  Returns how many there are.  ROWS: per cluster a
+// second pass for its depths; the owner's `leader` lane writes one row per cluster from row0 on, at most max_rows and none at or beyond
+// a.n_pc.
 template <int NA, bool ROWS, class Scope>
 __device__ inline uint32_t per_cluster(const PtArgs& a, const PtPlaced* run, uint32_t n, uint32_t l, bool need, const Scope& scope, uint32_t row0, uint32_t max_rows,
                                        uint32_t ploidy, bool leader) {
-	bool active = need;
-	uint32_t lower = 0, n_rows = 0;
-	while (__any(active)) {
-		uint32_t next = PT_NONE;
-		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-			const uint32_t i = base + l;
-			if (active && i < n) {
-				const uint32_t c = run[i].cluster;
-				if (c >= lower) next = min(next, c);
-			}
+	const auto cluster_of = [&](uint32_t i) { return run[i].cluster; };
+	if constexpr (!ROWS) return walk_ids(scope, n, l, need, cluster_of, [](uint32_t, bool, uint32_t) {});
+	else return walk_ids(scope, n, l, need, cluster_of, [&](uint32_t next, bool active, uint32_t ordinal) {
+		RowAcc<NA> acc;
+#pragma unroll
+		for (int x = 0; x < NA; x++) {
+			acc.cnt[x] = 0;
+			acc.first[x] = PT_NONE;
 		}
-		next = scope.all_min(next);
-		if (next == PT_NONE) active = false;
-		if (ROWS) {
-			uint32_t cnt[NA], first[NA];
+		team_pass<Scope>(n, l, active, [&](uint32_t i) {
+			const PtPlaced e = run[i];
+			const uint32_t allele = e.rank_allele & 15u, rank = e.rank_allele >> 4;
 #pragma unroll
 			for (int x = 0; x < NA; x++) {
-				cnt[x] = 0;
-				first[x] = PT_NONE;
+				const bool hit = e.cluster == next && allele == (uint32_t)x;
+				acc.cnt[x] += hit ? 1u : 0u;
+				acc.first[x] = hit ? min(acc.first[x], rank) : acc.first[x];
 			}
-			for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-				const uint32_t i = base + l;
-				if (active && i < n) {
-					const PtPlaced e = run[i];
-					const uint32_t allele = e.rank_allele & 15u, rank = e.rank_allele >> 4;
+		});
+		scope.combine(acc);
+		const uint64_t row = (uint64_t)row0 + ordinal;
+		if (active && leader && ordinal < max_rows && row < a.n_pc) {
+			uint32_t total = 0;
 #pragma unroll
-					for (int x = 0; x < NA; x++) {
-						const bool hit = e.cluster == next && allele == (uint32_t)x;
-						cnt[x] += hit ? 1u : 0u;
-						first[x] = hit ? min(first[x], rank) : first[x];
-					}
-				}
+			for (int x = 0; x < NA; x++) {
+				total += acc.cnt[x];
+				a.pc_depth[row * NA + x] = acc.cnt[x];
+				a.pc_first[row * NA + x] = acc.first[x];
 			}
-			scope.template all_rows<NA>(cnt, first);
-			const uint64_t row = (uint64_t)row0 + n_rows;
-			if (active && leader && n_rows < max_rows && row < a.n_pc) {
-				uint32_t total = 0;
-#pragma unroll
-				for (int x = 0; x < NA; x++) {
-					total += cnt[x];
-					a.pc_depth[row * NA + x] = cnt[x];
-					a.pc_first[row * NA + x] = first[x];
-				}
-				a.pc_cluster[row] = next;
-				a.pc_total[row] = total;
-				pt_consensus<NA>(cnt, first, ploidy, a.pc_cons + row * a.max_ploidy);
-			}
+			a.pc_cluster[row] = next;
+			a.pc_total[row] = total;
+			pt_consensus<NA>(acc.cnt, acc.first, ploidy, a.pc_cons + row * a.max_ploidy);
 		}
-		if (active) {
-			n_rows++;
-			lower = next + 1;
-		}
-	}
-	return n_rows;
+	});
 }
 
 __device__ inline uint32_t row_begin(const PtArgs& a, uint32_t v) { return run_begin(a.npc_local, a.npc_tile_sums, v); }
@@ -232,10 +158,8 @@ __device__ inline void position_by(const PtArgs& a, uint32_t v, bool have, uint3
 // Class a: eight lanes per position, over all positions; those of more entries are left to the lists.
 template <int NA, bool ROWS>
 __global__ void __launch_bounds__(RS_BLOCK) polythread_a_kernel(PtArgs a) {
-	const uint32_t l = threadIdx.x & (PT_SEGMENT - 1);
-	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / PT_SEGMENT) + threadIdx.x / PT_SEGMENT;
-	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max;
-	position_by<NA, ROWS>(a, (uint32_t)v64, have, l, TeamScope<(int)PT_SEGMENT>{}, l == 0);
+	const SegmentKey k = segment_key(a.run);
+	position_by<NA, ROWS>(a, k.v, k.have, k.l, TeamScope<(int)PT_SEGMENT>{}, k.l == 0);
 }
 
 // Class b: one wave per listed position.
@@ -249,9 +173,10 @@ __global__ void __launch_bounds__(RS_BLOCK) polythread_b_kernel(PtArgs a) {
 // Class c: one workgroup per listed position, a run of any length.
 template <int NA, bool ROWS>
 __global__ void __launch_bounds__(RS_BLOCK) polythread_c_kernel(PtArgs a) {
-	__shared__ uint32_t word[NW], cnts[NW * 16], firsts[NW * 16];
+	__shared__ uint32_t word[NW];
+	__shared__ RowAcc<NA> part[NW];
 	const uint32_t n_list = a.run.list_n[1];
-	const BlockScope scope{word, cnts, firsts, threadIdx.x & 63u, threadIdx.x >> 6};
+	const BlockScope<RowAcc<NA>> scope{word, part, threadIdx.x & 63u, threadIdx.x >> 6};
 	for (uint32_t k = blockIdx.x; k < n_list; k += gridDim.x) position_by<NA, ROWS>(a, a.run.list_c[k], true, threadIdx.x, scope, threadIdx.x == 0);
 }
 

@@ -1,5 +1,6 @@
-// run_scatter.h -- the transposition the read-major layers share (tagphase_device.hip, priorgt_device.hip): entries arrive in the order
-// of the reads, results are per key (a variant, a column), so every counted entry is moved into its key's run:
+// run_scatter.h -- the transposition the read-major layers share (tagphase_device.hip, priorgt_device.hip, polythread_device.hip):
+// entries arrive in the order of the reads, results are per key (a variant, a column, a position), so every counted entry is moved into
+// its key's run:
 //   count     one thread per entry: an integer atomic on the key's counter -- one per run of neighbouring lanes with the same key.
 //   scan      exclusive, two launches (run_scatter.hip): tiles of RS_SCAN_TILE counters (the tile's own prefix, the tile's total), then
 //             the totals by one workgroup; run_begin() adds the two.  The first also appends every key of more than a_max / b_max
@@ -7,7 +8,8 @@
 //   place     one thread per entry again: a counted entry gets the slot run begin + atomic cursor of its key.  The order inside a run
 //             is whatever the atomics give.
 // The layer decides which entry counts and for which key, what it stores at the slot, and how a run is reduced or ordered (class a:
-// RS_SEGMENT lanes per key over all keys; b and c: a fixed grid of RS_LIST_GRID workgroups that walks the list).  Its count and place
+// RS_SEGMENT lanes per key over all keys; b and c: a fixed grid of RS_LIST_GRID workgroups that walks the list; what the teams that
+// reduce a placed run share is run_teams.h).  Its count and place
 // kernels compute the key and call scatter_count / scatter_place; its host code lays the pieces out, binds them and launches through
 // the functions at the end.  Host code that is not HIP sees the constants only.
 #pragma once
@@ -101,20 +103,6 @@ __device__ inline uint32_t block_exclusive(uint32_t mine, uint32_t* wave_total, 
 	}
 	__syncthreads();
 	return before + inc - mine;
-}
-
-// ---------------------------------------------------------------------------------------------- teams of W neighbouring lanes
-template <int W>
-__device__ inline int64_t team_sum(int64_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-template <int W>
-__device__ inline uint32_t team_min(uint32_t v) {
-#pragma unroll
-	for (int o = W / 2; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-	return v;
 }
 
 // ---------------------------------------------------------------------------------------------- host

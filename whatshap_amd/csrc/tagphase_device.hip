@@ -3,15 +3,16 @@
 // and place are the shared ones of run_scatter.h, with this layer's key and payload:
 //   upload    per variant {flags | problem << 8}, per problem the gap threshold, per read {phase set << 1 | haplotype, first variant of its
 //             problem} and its first entry, the three entry arrays as the caller holds them (variant, id, quality).
-//   count     one thread per entry: its read (a search of the read offsets, narrowed to the reads of the workgroup's 256 entries), does it
-//             vote, and an integer atomic on the variant's counter -- one per run of neighbouring lanes that hit the same variant.
+//   count     one thread per entry: its read (read_of_entry, run_teams.h), does it vote, and an integer atomic on the variant's counter
+//             -- one per run of neighbouring lanes that hit the same variant.
 //   scan      exclusive, two launches: tiles of 2048 counters (the tile's own prefix, the tile's total), then the totals by one workgroup.
 //             The first also appends every variant of more than 64 / 4096 entries to the class b / c list.
 //   place     one thread per entry again: a voting entry goes to run begin + atomic cursor of its variant as {phase set << 1 | (haplotype
 //             ^ id), quality, entry index}.  The order inside a run is whatever the atomics give; nothing below depends on it.
 //   reduce    one team per variant -- class a (0 .. 64 entries) eight lanes, over all variants; class b (.. 4096) one wave and class c one
 //             workgroup, both walking their list with a fixed grid.  A team keeps up to R = 4 phase sets in registers (sums of both
-//             haplotypes, smallest entry index); with more it takes one pass per phase set in the order of the ids.  Either way (sum0,
+//             haplotypes, smallest entry index); with more it walks them in the order of the ids, one phase set per trip (slot naming,
+//             scopes and walk: run_teams.h; this file has the payload, Slots and PsAcc, and the walk's body).  Either way (sum0,
 //             sum1, phase set, first) go to tp_consider and the choice to tp_result (tagphase.h, shared with the host twin), which applies
 //             the consensus filters; one lane writes the variant's 32 bytes.
 //   rows      want_table only: the phase-set counts are scanned like the entry counts, the call waits once to size the table, then the
@@ -23,13 +24,14 @@
 #include <cstring>
 
 #include "device_runtime.h"
+#include "run_teams.h"
 #include "tagphase.h"
 
 namespace whamd {
 namespace {
 
 constexpr int R = (int)TP_REG_PHASESETS;
-constexpr int NW = (int)RS_BLOCK / 64;
+constexpr int NW = RT_WAVES;
 
 struct TpArgs {
 	// the image
@@ -53,23 +55,11 @@ struct TpArgs {
 };
 
 // ---------------------------------------------------------------------------------------------- count, place
-// The largest r in [lo, hi] with read_ptr[r] <= i (read_ptr[lo] <= i).
-__device__ inline uint32_t find_read(const uint32_t* read_ptr, uint32_t lo, uint32_t hi, uint32_t i) {
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo + 1) / 2;
-		if (read_ptr[mid] <= i) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
-
 // Entry i of the call: the variant it votes at (TP_NONE: it does not vote) and the key it votes for.
 __device__ inline uint32_t voting_variant(const TpArgs& a, uint32_t i, uint32_t& key) {
 	key = 0;
 	if (i >= a.n_entries) return TP_NONE;
-	const uint32_t i0 = blockIdx.x * RS_BLOCK, i1 = min(i0 + RS_BLOCK - 1, a.n_entries - 1);
-	const uint32_t lo = find_read(a.read_ptr, 0, a.n_reads - 1, i0), hi = find_read(a.read_ptr, lo, a.n_reads - 1, i1);
-	const TpRead rd = a.reads[find_read(a.read_ptr, lo, hi, i)];
+	const TpRead rd = a.reads[read_of_entry(a.read_ptr, a.n_reads, a.n_entries, i)];
 	if (rd.code == TP_NOT_COUNTED) return TP_NONE;
 	const uint32_t v = rd.var_base + a.entry_var[i];
 	if (v >= a.run.n_keys || (a.vinfo[v] & TP_HOMOZYGOUS)) return TP_NONE;
@@ -92,11 +82,27 @@ __global__ void __launch_bounds__(RS_BLOCK) tagphase_place_kernel(TpArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- reduce and decide
-struct Slots {
+// The register route's phase sets (SlotNames, run_teams.h) with their sums and smallest entry index.
+struct Slots : SlotNames<R> {
 	int64_t s[R][2];
-	uint32_t ps[R], first[R];
-	uint32_t n;
-	bool overflow;
+	uint32_t first[R];
+};
+
+// One phase set on the pass-per-phase-set route: the sums of both haplotypes and the smallest entry index.
+struct PsAcc {
+	int64_t s[2];
+	uint32_t first;
+	template <int W>
+	__device__ void across() {
+		s[0] = team_sum<W>(s[0]);
+		s[1] = team_sum<W>(s[1]);
+		first = team_min<W>(first);
+	}
+	__device__ void merge(const PsAcc& o) {
+		s[0] += o.s[0];
+		s[1] += o.s[1];
+		first = min(first, o.first);
+	}
 };
 
 // Placed entry i of the run, or nothing (ps = TP_NONE) beyond it.
@@ -118,11 +124,9 @@ __device__ inline void load_placed(const TpPlaced* run, uint32_t i, uint32_t n, 
 // Every lane of the wave calls this together; n is the team's.
 template <int W>
 __device__ inline void scan_run(const TpPlaced* run, uint32_t n, uint32_t l, uint64_t teammask, uint32_t lane0, Slots& S) {
-	S.n = 0;
-	S.overflow = false;
+	S.clear();
 #pragma unroll
 	for (int s = 0; s < R; s++) {
-		S.ps[s] = TP_NONE;
 		S.first[s] = TP_NONE;
 		S.s[s][0] = S.s[s][1] = 0;
 	}
@@ -130,28 +134,7 @@ __device__ inline void scan_run(const TpPlaced* run, uint32_t n, uint32_t l, uin
 		uint32_t ps, hap, index;
 		int64_t q;
 		load_placed(run, base + l, n, !S.overflow, ps, hap, q, index);
-		const bool valid = ps != TP_NONE;
-		int slot = -1;
-#pragma unroll
-		for (int s = 0; s < R; s++)
-			if (valid && S.ps[s] == ps) slot = s;
-		for (;;) {
-			const uint64_t un = __ballot(valid && slot < 0 && !S.overflow) & teammask;
-			if (!__any(un != 0)) break;
-			const uint32_t src = un ? (uint32_t)__ffsll((unsigned long long)un) - 1 : lane0 + l;
-			const uint32_t fresh = (uint32_t)__shfl((int)ps, (int)src);
-			if (un) {
-				if (S.n < (uint32_t)R) {
-#pragma unroll
-					for (int s = 0; s < R; s++)
-						if (S.n == (uint32_t)s) S.ps[s] = fresh;
-					if (valid && ps == fresh) slot = (int)S.n;
-					S.n++;
-				} else {
-					S.overflow = true;
-				}
-			}
-		}
+		const int slot = S.claim(ps != TP_NONE, ps, teammask, lane0 + l, [](int, uint32_t) {});
 #pragma unroll
 		for (int s = 0; s < R; s++) {
 			const bool here = slot == s;
@@ -169,92 +152,30 @@ __device__ inline void scan_run(const TpPlaced* run, uint32_t n, uint32_t l, uin
 		}
 }
 
-// Who owns a variant on the pass-per-phase-set route: how far apart its lanes' entries lie and how they combine a minimum and a phase set's sums.
-template <int W>
-struct TeamScope {
-	static constexpr uint32_t STRIDE = W;
-	__device__ uint32_t all_min(uint32_t v) const { return team_min<W>(v); }
-	__device__ void all_sums(int64_t (&sums)[2], uint32_t& first) const {
-		sums[0] = team_sum<W>(sums[0]);
-		sums[1] = team_sum<W>(sums[1]);
-		first = team_min<W>(first);
-	}
-};
-struct BlockScope {   // (one variant per workgroup: every thread takes the same branches, so the barriers are met by all)
-	static constexpr uint32_t STRIDE = RS_BLOCK;
-	uint32_t* word;          // LDS [NW]
-	int64_t (*part)[2];      // LDS [NW][2]
-	uint32_t lane, w;
-	__device__ uint32_t all_min(uint32_t v) const {
-		v = team_min<64>(v);
-		if (lane == 0) word[w] = v;
-		__syncthreads();
-		v = word[0];
-#pragma unroll
-		for (int ww = 1; ww < NW; ww++) v = min(v, word[ww]);
-		__syncthreads();
-		return v;
-	}
-	__device__ void all_sums(int64_t (&sums)[2], uint32_t& first) const {
-		sums[0] = team_sum<64>(sums[0]);
-		sums[1] = team_sum<64>(sums[1]);
-		first = team_min<64>(first);
-		if (lane == 0) {
-			word[w] = first;
-			part[w][0] = sums[0];
-			part[w][1] = sums[1];
-		}
-		__syncthreads();
-		first = word[0];
-		sums[0] = part[0][0];
-		sums[1] = part[0][1];
-#pragma unroll
-		for (int ww = 1; ww < NW; ww++) {
-			first = min(first, word[ww]);
-			sums[0] += part[ww][0];
-			sums[1] += part[ww][1];
-		}
-		__syncthreads();
-	}
-};
-
-// The pass-per-phase-set route for the owners with `need` (the other teams of the wave walk along idle): phase sets in id order, per
-// phase set one pass for the next id and one for its sums and first entry.  Lane l of the owner takes entries l, l + STRIDE, ...
-// rows: where the owner's `leader` lane writes one row per phase set, at most max_rows (nullptr: none).
+// The pass-per-phase-set route for the owners with `need`: walk_ids over the run's phase sets; per phase set a second pass for its sums
+// and first entry, which go to tp_consider.  rows: where the owner's `leader` lane writes one row per phase set, at most max_rows
+// (nullptr: none).
 template <class Scope>
 __device__ inline void pass_per_phase_set(const TpPlaced* run, uint32_t n, uint32_t l, bool need, const Scope& scope, TpBest& best, TpRow* rows, uint32_t max_rows, bool leader) {
-	bool active = need;
-	uint32_t lower = 0, n_rows = 0;
-	while (__any(active)) {
-		uint32_t next = TP_NONE;
-		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-			uint32_t ps, hap, index;
-			int64_t q;
-			load_placed(run, base + l, n, active, ps, hap, q, index);
-			if (ps != TP_NONE && ps >= lower) next = min(next, ps);
-		}
-		next = scope.all_min(next);
-		if (next == TP_NONE) active = false;
-		int64_t sums[2] = {0, 0};
-		uint32_t first = TP_NONE;
-		for (uint32_t base = 0; __any(active && base < n); base += Scope::STRIDE) {
-			uint32_t ps, hap, index;
-			int64_t q;
-			load_placed(run, base + l, n, active, ps, hap, q, index);
-			if (ps != TP_NONE && ps == next) {
-				first = min(first, index);
-				sums[0] += hap == 0 ? q : 0;
-				sums[1] += hap == 1 ? q : 0;
-			}
-		}
-		scope.all_sums(sums, first);
-		if (active) {
-			tp_consider(best, sums[0], sums[1], next, first);
-			if (rows && leader && n_rows < max_rows) rows[n_rows] = TpRow{sums[0], sums[1], next, first, {0, 0}};
-			n_rows++;
-			lower = next + 1;
-		}
-	}
+	walk_ids(
+	    scope, n, l, need, [&](uint32_t i) { return run[i].key >> 1; },
+	    [&](uint32_t next, bool active, uint32_t ordinal) {
+		    PsAcc acc{{0, 0}, TP_NONE};
+		    team_pass<Scope>(n, l, active, [&](uint32_t i) {
+			    uint32_t ps, hap, index;
+			    int64_t q;
+			    load_placed(run, i, n, true, ps, hap, q, index);
+			    const bool here = ps == next;   // (selects, not a branch: the entry stays one load)
+			    acc.first = here ? min(acc.first, index) : acc.first;
+			    acc.s[0] += (here && hap == 0) ? q : 0;
+			    acc.s[1] += (here && hap == 1) ? q : 0;
+		    });
+		    scope.combine(acc);
+		    if (active) {
+			    tp_consider(best, acc.s[0], acc.s[1], next, acc.first);
+			    if (rows && leader && ordinal < max_rows) rows[ordinal] = TpRow{acc.s[0], acc.s[1], next, acc.first, {0, 0}};
+		    }
+	    });
 }
 
 __device__ inline void write_result(const TpArgs& a, uint32_t v, const TpBest& best) {
@@ -284,10 +205,8 @@ __device__ inline void reduce_by_team(const TpArgs& a, uint32_t v, bool have, ui
 
 // Class a: eight lanes per variant, over all variants; those of more entries are left to the lists.
 __global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_a_kernel(TpArgs a) {
-	const uint32_t lane = threadIdx.x & 63u, l = threadIdx.x & (TP_SEGMENT - 1);
-	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
-	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max;
-	reduce_by_team<(int)TP_SEGMENT>(a, (uint32_t)v64, have, l, lane);
+	const SegmentKey k = segment_key(a.run);
+	reduce_by_team<(int)TP_SEGMENT>(a, k.v, k.have, k.l, threadIdx.x & 63u);
 }
 
 // Class b: one wave per listed variant.
@@ -300,7 +219,7 @@ __global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_b_kernel(TpArgs a) {
 __global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
 	__shared__ int64_t w_sums[NW][R][2];
 	__shared__ uint32_t w_ps[NW][R], w_first[NW][R], w_n[NW], w_overflow[NW];
-	__shared__ int64_t r_sums[NW][2];
+	__shared__ PsAcc r_part[NW];
 	__shared__ uint32_t r_word[NW];
 	__shared__ uint32_t go_slow;
 	const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, n_list = a.run.list_n[1];
@@ -360,7 +279,7 @@ __global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
 		__syncthreads();
 		if (go_slow) {
 			TpBest best = tp_start();
-			pass_per_phase_set(run, n, threadIdx.x, true, BlockScope{r_word, r_sums, lane, w}, best, nullptr, 0, false);
+			pass_per_phase_set(run, n, threadIdx.x, true, BlockScope<PsAcc>{r_word, r_part, lane, w}, best, nullptr, 0, false);
 			if (threadIdx.x == 0) write_result(a, v, best);
 		}
 		__syncthreads();
@@ -371,10 +290,9 @@ __global__ void __launch_bounds__(RS_BLOCK) tagphase_reduce_c_kernel(TpArgs a) {
 __device__ inline uint32_t row_begin(const TpArgs& a, uint32_t v) { return run_begin(a.nps_local, a.nps_tile_sums, v); }
 
 __global__ void __launch_bounds__(RS_BLOCK) tagphase_rows_a_kernel(TpArgs a) {
-	const uint32_t l = threadIdx.x & (TP_SEGMENT - 1);
-	const uint64_t v64 = (uint64_t)blockIdx.x * (RS_BLOCK / TP_SEGMENT) + threadIdx.x / TP_SEGMENT;
-	const bool have = v64 < a.run.n_keys && a.run.counts[v64] <= a.run.a_max && a.run.counts[v64] > 0;
-	const uint32_t v = (uint32_t)v64;
+	const SegmentKey k = segment_key(a.run);
+	const uint32_t v = k.v, l = k.l;
+	const bool have = k.have && a.run.counts[v] > 0;
 	TpBest best = tp_start();
 	pass_per_phase_set(a.placed + (have ? run_begin(a.run.local, a.run.tile_sums, v) : 0), have ? a.run.counts[v] : 0, l, have, TeamScope<(int)TP_SEGMENT>{}, best,
 	                   a.rows + (have ? row_begin(a, v) : 0), have ? a.nps[v] : 0, l == 0);
