@@ -8,6 +8,7 @@ without a HIP device raises ``RuntimeError`` from the library's own message.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -29,6 +30,13 @@ WHAMD_ERR_DEVICE = 5
 WHAMD_ERR_OVERFLOW = 6
 WHAMD_ERR_HOST = 7
 GT_OTHER = 255
+
+
+class Record(C.Structure):
+    """A struct the library fills (statistics, a plan's summary), readable as a dict."""
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class ReadSetView(C.Structure):
@@ -55,17 +63,14 @@ class PedigreeView(C.Structure):
     ]
 
 
-class PlanSummary(C.Structure):
+class PlanSummary(Record):
     _fields_ = [(name, C.c_uint64) for name in (
         "n_columns", "n_steps", "n_runs", "n_resident_columns", "n_folded_columns", "n_vectorised_columns",
         "max_run_columns", "max_workgroups", "max_lds_bytes", "backtrace_bytes", "n_components", "n_halved_runs")] + [
         ("max_coverage", C.c_uint32), ("invariants_ok", C.c_uint32), ("n_yform_runs", C.c_uint64), ("n_fact_runs", C.c_uint64)]
 
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
-
-class SolveStats(C.Structure):
+class SolveStats(Record):
     _fields_ = [
         ("n_columns", C.c_uint64),
         ("n_cells", C.c_uint64),
@@ -86,11 +91,8 @@ class SolveStats(C.Structure):
         ("host_flatten_ms", C.c_double),
     ]
 
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "pad"}
 
-
-class GenotypeStats(C.Structure):
+class GenotypeStats(Record):
     _fields_ = [
         ("n_columns", C.c_uint64),
         ("n_cells", C.c_uint64),
@@ -105,11 +107,8 @@ class GenotypeStats(C.Structure):
         ("slot_runs", C.c_uint32),
     ]
 
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_ if name != "pad"}
 
-
-class HeuristicStats(C.Structure):
+class HeuristicStats(Record):
     _fields_ = [
         ("n_columns", C.c_uint64),
         ("n_reads", C.c_uint64),
@@ -121,9 +120,6 @@ class HeuristicStats(C.Structure):
         ("n_samples", C.c_uint32),
         ("row_limit", C.c_uint32),
     ]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class HeuristicJob(C.Structure):
@@ -153,24 +149,18 @@ class RealignParams(C.Structure):
                 ("affine_unset", C.c_int32)]
 
 
-class RealignStats(C.Structure):
+class RealignStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_alignments", "n_jobs", "n_pairs", "n_results")] + [
         (name, C.c_double) for name in ("host_walk_ms", "upload_ms", "kernel_ms", "download_ms", "host_finish_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PolyMatrixView(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("position", C.POINTER(C.c_int64)), ("allele", C.POINTER(C.c_int8))]
 
 
-class PolyScoreStats(C.Structure):
+class PolyScoreStats(Record):
     _fields_ = [("err", C.c_double)] + [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_candidates", "n_overlapping", "n_entries", "n_nan", "n_pair_positions")] + [
         ("launches", C.c_uint32)] + [(name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class ProgenyView(C.Structure):
@@ -187,12 +177,9 @@ class ProgenyDepthsView(C.Structure):
                 ("co_alt_count", C.POINTER(C.c_uint32))]
 
 
-class ProgenyScoreStats(C.Structure):
+class ProgenyScoreStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_nodes", "n_entries", "n_inf", "n_reused", "n_sample_terms")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class HaplotagView(C.Structure):
@@ -203,13 +190,10 @@ class HaplotagView(C.Structure):
                 ("read_bx", C.POINTER(C.c_uint32))]
 
 
-class HaplotagStats(C.Structure):
+class HaplotagStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_groups", "n_assigned", "n_multiple_phase_sets", "n_entries", "groups_class_a", "groups_class_b",
                                                 "groups_class_c", "groups_many_phase_sets")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class TagphaseView(C.Structure):
@@ -219,13 +203,10 @@ class TagphaseView(C.Structure):
                 ("want_table", C.c_uint32)]
 
 
-class TagphaseStats(C.Structure):
+class TagphaseStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_variants", "n_entries", "n_voting", "n_skipped", "n_voted", "n_kept", "n_zero_total",
                                                 "variants_class_a", "variants_class_b", "variants_class_c", "variants_many_phase_sets", "table_rows")] + [
         ("launches", C.c_uint32)] + [(name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PriorGenotypesView(C.Structure):
@@ -234,13 +215,10 @@ class PriorGenotypesView(C.Structure):
                 ("constant", C.c_double), ("gt_prob", C.c_double), ("want_regularized", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-class PriorGenotypesStats(C.Structure):
+class PriorGenotypesStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_entries", "n_counted", "n_covered", "n_genotyped", "columns_class_a",
                                                 "columns_class_b", "columns_class_c", "longest_run")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("map_ms", "host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 PRIOR_GENOTYPES_LAUNCHES = 8   # WHAMD_PRIOR_GENOTYPES_LAUNCHES of include/whatshap_amd.h
@@ -253,12 +231,9 @@ class PolyReorderView(C.Structure):
                 ("bp_affected", C.POINTER(C.c_uint32)), ("bp_cluster_ptr", C.POINTER(C.c_uint64)), ("bp_clusters", C.POINTER(C.c_uint32))]
 
 
-class PolyReorderStats(C.Structure):
+class PolyReorderStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_breakpoints", "n_reads_visited", "n_permutations", "n_window_positions")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PolyCompareView(C.Structure):
@@ -271,12 +246,9 @@ class PolyCompareJobResult(C.Structure):
                 ("flips", C.c_uint32)]
 
 
-class PolyCompareStats(C.Structure):
+class PolyCompareStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_jobs", "n_positions", "n_visited", "path_bytes")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class PolyThreadView(C.Structure):
@@ -284,13 +256,10 @@ class PolyThreadView(C.Structure):
                 ("ploidy", C.c_uint32), ("max_cluster_gap", C.c_uint32), ("n_alleles", C.c_uint32), ("flags", C.c_uint32)]
 
 
-class PolyThreadStats(C.Structure):
+class PolyThreadStats(Record):
     _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_positions", "n_entries", "n_counted", "n_rows", "n_selected", "n_readded", "n_emptied",
                                                 "positions_class_a", "positions_class_b", "positions_class_c")] + [("launches", C.c_uint32)] + [
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "fill_ms", "total_ms")]
-
-    def as_dict(self) -> dict:
-        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 POLY_THREAD_LAUNCHES = 13       # WHAMD_POLY_THREAD_LAUNCHES of include/whatshap_amd.h
@@ -777,13 +746,44 @@ class SolverError(RuntimeError):
         self.status = status
 
 
-
 def raise_status(L, status: int):
     """The library's last error as an exception: ValueError for invalid input (where the reference raises on the same input), else SolverError."""
     msg = L.whamd_last_error().decode("utf-8", "replace")
     if status == WHAMD_ERR_INVALID:
         raise ValueError(msg)
     raise SolverError(status, msg)
+
+
+def checked(L, status: int) -> None:
+    """A getter's or an entry point's status: raises through raise_status unless it is WHAMD_OK."""
+    if status != WHAMD_OK:
+        raise_status(L, status)
+
+
+@contextlib.contextmanager
+def batch_handle(host: bool, views, product_entry: str, debug_entry: Optional[str], destroy_name: str, *extra_args, device: int = 0):
+    """One batch call and the life of its result handle: ``with batch_handle(...) as (L, h)``.  ``views`` is the list of the problems'
+    view structs; the product entry point is called as (views, n, *extra_args, device, &h), with ``host`` the debug library's twin as
+    (views, n, *extra_args, &h).  A failed call raises (raise_status) before the block is entered; the handle is destroyed on exit."""
+    L = debug_lib() if host else lib()
+    n = len(views)
+    array = (type(views[0]) * n)(*views) if n else None
+    h = C.c_void_p()
+    if host:
+        checked(L, getattr(L, debug_entry)(array, n, *extra_args, C.byref(h)))
+    else:
+        checked(L, getattr(L, product_entry)(array, n, *extra_args, int(device), C.byref(h)))
+    try:
+        yield L, h
+    finally:
+        getattr(L, destroy_name)(h)
+
+
+def read_stats(L, getter: str, StatsType, h, *index) -> dict:
+    """The stats struct of a result handle (of problem ``index``, where the result has one per problem) as a dict."""
+    s = StatsType()
+    checked(L, getattr(L, getter)(h, *index, C.byref(s)))
+    return s.as_dict()
 
 
 def _check(status: int, L=None):

@@ -127,20 +127,11 @@ class CompareResult:
 def switch_flips_batch(jobs: Sequence[CompareJob], device: int = 0, host: bool = False, stats: Optional[list] = None) -> List[CompareResult]:
     """Every job in one native call (one upload, at most two launches, one download for the whole batch).  ``stats``, if given,
     receives one dict for the call (counts, launches and timings)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(jobs)
-    views = (_native.PolyCompareView * max(n, 1))()
-    for x, job in enumerate(jobs):
-        views[x] = job.view()
-    h = C.c_void_p()
-    st = L.whamd_debug_poly_compare_host(views, n, C.byref(h)) if host else L.whamd_poly_compare(views, n, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _native.raise_status(L, st)
     p = _native._ptr
-    try:
-        res = (_native.PolyCompareJobResult * max(n, 1))()
-        if L.whamd_poly_compare_get(h, res) != _native.WHAMD_OK:
-            _native.raise_status(L, _native.WHAMD_ERR_INVALID)
+    with _native.batch_handle(host, [job.view() for job in jobs], "whamd_poly_compare", "whamd_debug_poly_compare_host", "whamd_poly_compare_destroy",
+                              device=device) as (L, h):
+        res = (_native.PolyCompareJobResult * max(len(jobs), 1))()
+        _native.checked(L, L.whamd_poly_compare_get(h, res))
         out = []
         for x, job in enumerate(jobs):
             path = None
@@ -149,19 +140,13 @@ def switch_flips_batch(jobs: Sequence[CompareJob], device: int = 0, host: bool =
                 positions, ranks = np.empty(m, dtype=np.uint64), np.empty(m, dtype=np.uint16)
                 perms, flipped = np.empty((m, job.ploidy), dtype=np.uint8), np.empty((m, job.ploidy), dtype=np.uint8)
                 switches = np.empty(m, dtype=np.uint32)
-                st = L.whamd_poly_compare_get_path(h, x, p(positions, C.c_uint64), p(ranks, C.c_uint16), p(perms, C.c_uint8), p(flipped, C.c_uint8),
-                                                   p(switches, C.c_uint32))
-                if st != _native.WHAMD_OK:
-                    _native.raise_status(L, st)
+                _native.checked(L, L.whamd_poly_compare_get_path(h, x, p(positions, C.c_uint64), p(ranks, C.c_uint16), p(perms, C.c_uint8),
+                                                                 p(flipped, C.c_uint8), p(switches, C.c_uint32)))
                 path = (positions, ranks, perms, flipped, switches)
             out.append(CompareResult(res[x], path))
         if stats is not None:
-            s = _native.PolyCompareStats()
-            L.whamd_poly_compare_get_stats(h, C.byref(s))
-            stats.append(s.as_dict())
+            stats.append(_native.read_stats(L, "whamd_poly_compare_get_stats", _native.PolyCompareStats, h))
         return out
-    finally:
-        L.whamd_poly_compare_destroy(h)
 
 
 # ---------------------------------------------------------------------------------------------- blocks

@@ -11,7 +11,7 @@
 #include <unordered_map>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -58,20 +58,12 @@ whamd_status_t whamd::haplotag_prepare(const whamd_haplotag_view& v, HaplotagPro
 		return WHAMD_ERR_UNSUPPORTED;
 	}
 	const uint64_t n_reads = v.n_reads, n_entries = n_reads ? v.read_ptr[n_reads] : 0;
-	for (uint64_t r = 0; r < n_reads; r++) {
-		if (v.read_ptr[r] > v.read_ptr[r + 1]) {
-			msg = "read_ptr decreases at read " + std::to_string(r);
-			return WHAMD_ERR_INVALID;
-		}
+	if (!check_offsets(v.read_ptr, n_reads, "read_ptr", "read", msg)) return WHAMD_ERR_INVALID;
+	for (uint64_t r = 0; r < n_reads; r++)
 		if (v.read_repr[r] >= n_reads || (v.read_bx && v.read_bx[r] != HT_NO_BX && v.read_bx[r] >= n_reads)) {
 			msg = "read " + std::to_string(r) + ": representation and BX ids must be dense (below the number of reads)";
 			return WHAMD_ERR_INVALID;
 		}
-	}
-	if (n_reads && v.read_ptr[0] != 0) {
-		msg = "read_ptr does not start at 0";
-		return WHAMD_ERR_INVALID;
-	}
 	if (n_entries && (!v.entry_position || !v.entry_allele || !v.entry_quality)) {
 		msg = "null argument";
 		return WHAMD_ERR_INVALID;
@@ -301,42 +293,16 @@ void assemble(const HaplotagProblem& p, const HaplotagScores& sc, whamd_haplotag
 }
 
 whamd_status_t haplotag(const whamd_haplotag_view* views, uint64_t n, int device, bool host, whamd_haplotag_result** out) {
-	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
-	*out = nullptr;
-	refresh_bounds();
-	const double t0 = now_ms();
-	std::vector<HaplotagProblem> problems(n);
-	std::vector<HaplotagScores> scores(n);
-	std::string msg;
-	for (uint64_t x = 0; x < n; x++) {
-		const whamd_status_t st = haplotag_prepare(views[x], problems[x], msg);
-		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
-	}
-	const double t1 = now_ms();
-	CallTimes times;
-	if (host) {
-#ifdef WHAMD_DEBUG_BUILD
-		for (uint64_t x = 0; x < n; x++) haplotag_score_host(problems[x], scores[x]);
-#endif
-	} else {
-		const whamd_status_t st = haplotag_score_device(problems, device, scores, times, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	std::unique_ptr<whamd_haplotag_result> r(new whamd_haplotag_result());
-	r->problems.resize(n);
-	for (uint64_t x = 0; x < n; x++) assemble(problems[x], scores[x], r->problems[x]);
-	const double t2 = now_ms();
-	for (uint64_t x = 0; x < n; x++) {
-		whamd_haplotag_stats& s = r->problems[x].stats;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
-	}
-	*out = r.release();
-	return WHAMD_OK;
+	return run_batch<HaplotagProblem, HaplotagScores>(
+		views, n, host, out,
+		[](const whamd_haplotag_view& v, HaplotagProblem& p, std::string& msg) {
+			refresh_bounds();   // (the debug library's class bounds may change between calls)
+			return haplotag_prepare(v, p, msg);
+		},
+		[](auto& problems, auto& scores) {
+			for (size_t x = 0; x < problems.size(); x++) haplotag_score_host(problems[x], scores[x]);
+		},
+		[&](auto& problems, auto& scores, CallTimes& times, std::string& msg) { return haplotag_score_device(problems, device, scores, times, msg); }, assemble);
 }
 
 }  // namespace
@@ -352,9 +318,9 @@ uint64_t whamd_haplotag_problem_count(const whamd_haplotag_result* r) { return r
 uint64_t whamd_haplotag_count(const whamd_haplotag_result* r, uint64_t m) { return r && m < r->problems.size() ? r->problems[m].haplotype.size() : 0; }
 
 whamd_status_t whamd_haplotag_get(const whamd_haplotag_result* r, uint64_t m, int32_t* haplotype_out, int64_t* quality_out, int64_t* phaseset_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	const whamd_haplotag_result::Problem& p = r->problems[m];
+	const auto* found = problem_of(r, m);
+	if (!found) return no_problem(r);
+	const whamd_haplotag_result::Problem& p = *found;
 	const size_t n = p.haplotype.size();
 	if (haplotype_out && n) std::memcpy(haplotype_out, p.haplotype.data(), n * 4);
 	if (quality_out && n) std::memcpy(quality_out, p.quality.data(), n * 8);
@@ -366,9 +332,9 @@ uint64_t whamd_haplotag_bx_count(const whamd_haplotag_result* r, uint64_t m) { r
 
 whamd_status_t whamd_haplotag_get_bx(const whamd_haplotag_result* r, uint64_t m, uint32_t* bx_out, int64_t* reference_start_out, int32_t* haplotype_out,
                                      int64_t* phaseset_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	const whamd_haplotag_result::Problem& p = r->problems[m];
+	const auto* found = problem_of(r, m);
+	if (!found) return no_problem(r);
+	const whamd_haplotag_result::Problem& p = *found;
 	const size_t n = p.bx.size();
 	if (bx_out && n) std::memcpy(bx_out, p.bx.data(), n * 4);
 	if (reference_start_out && n) std::memcpy(reference_start_out, p.bx_start.data(), n * 8);
@@ -378,10 +344,7 @@ whamd_status_t whamd_haplotag_get_bx(const whamd_haplotag_result* r, uint64_t m,
 }
 
 whamd_status_t whamd_haplotag_get_stats(const whamd_haplotag_result* r, uint64_t m, whamd_haplotag_stats* stats_out) {
-	if (!r || !stats_out) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	*stats_out = r->problems[m].stats;
-	return WHAMD_OK;
+	return get_stats_of(r, m, stats_out);
 }
 
 void whamd_haplotag_destroy(whamd_haplotag_result* r) { delete r; }

@@ -8,7 +8,7 @@
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -145,7 +145,8 @@ void expand_path(const CompareJob& job, const std::vector<uint16_t>& path, whamd
 whamd_status_t compare(const whamd_poly_compare_view* views, uint64_t n, int device, bool host, whamd_poly_compare_result** out) {
 	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
 	*out = nullptr;
-	const double t0 = now_ms();
+	BatchClock clock;
+	clock.t0 = now_ms();
 	std::vector<CompareJob> jobs(n);
 	std::vector<CompareResult> results(n);
 	std::string msg;
@@ -160,7 +161,7 @@ whamd_status_t compare(const whamd_poly_compare_view* views, uint64_t n, int dev
 	if (path_bytes > WHAMD_POLY_COMPARE_MAX_PATH_BYTES)
 		return fail(WHAMD_ERR_UNSUPPORTED, "the want_path tables of this call take " + std::to_string(path_bytes) + " bytes, above WHAMD_POLY_COMPARE_MAX_PATH_BYTES (" +
 		                                       std::to_string(WHAMD_POLY_COMPARE_MAX_PATH_BYTES) + ")");
-	const double t1 = now_ms();
+	clock.t1 = now_ms();
 	CallTimes times;
 	if (host) {
 #ifdef WHAMD_DEBUG_BUILD
@@ -184,19 +185,10 @@ whamd_status_t compare(const whamd_poly_compare_view* views, uint64_t n, int dev
 	s.n_positions = n_positions;
 	s.n_visited = n_visited;
 	s.path_bytes = path_bytes;
-	s.launches = times.launches;
-	s.host_ms = t1 - t0;
-	s.upload_ms = times.upload_ms;
-	s.kernel_ms = times.kernel_ms;
-	s.download_ms = times.download_ms;
-	s.total_ms = now_ms() - t0;
+	clock.t3 = now_ms();
+	stamp_times(s, times, clock);
 	*out = r.release();
 	return WHAMD_OK;
-}
-
-template <class T>
-void copy_out(T* dst, const std::vector<T>& src) {
-	if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
 }
 
 }  // namespace

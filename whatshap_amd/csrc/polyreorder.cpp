@@ -10,7 +10,7 @@
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -276,65 +276,26 @@ namespace {
 
 whamd_status_t reorder(const whamd_poly_reorder_view* views, uint64_t n, double log_match, double log_err, int device, bool host,
                        whamd_poly_reorder_result** out) {
-	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
-	*out = nullptr;
-	const double t0 = now_ms();
-	std::vector<ReorderProblem> problems(n);
-	std::vector<ReorderScores> scores(n);
-	std::string msg;
-	for (uint64_t x = 0; x < n; x++) {
-		const whamd_status_t st = reorder_prepare(views[x], problems[x], msg);
-		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
-	}
-	const double t1 = now_ms();
-	CallTimes times;
-	if (host) {
-#ifdef WHAMD_DEBUG_BUILD
-		for (uint64_t x = 0; x < n; x++) reorder_score_host(problems[x], log_match, log_err, scores[x]);
-#endif
-	} else {
-		const whamd_status_t st = reorder_score_device(problems, log_match, log_err, device, scores, times, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	std::unique_ptr<whamd_poly_reorder_result> r(new whamd_poly_reorder_result());
-	r->problems.resize(n);
-	for (uint64_t x = 0; x < n; x++) {
-		ReorderProblem& p = problems[x];
-		whamd_poly_reorder_result::Problem& o = r->problems[x];
-		reorder_tail(p, scores[x], o.tail);
-		o.ploidy = p.ploidy;
-		o.stats.n_breakpoints = p.n_breakpoints();
-		o.stats.n_reads_visited = p.item_read.size();
-		o.stats.n_permutations = p.llh_ptr.back();
-		o.stats.n_window_positions = p.win.size();
-		o.llh_ptr = std::move(p.llh_ptr);
-		o.win_ptr = std::move(p.win_ptr);
-		o.win = std::move(p.win);
-		o.left = std::move(p.bp_left);
-		o.llh = std::move(scores[x].llh);
-	}
-	const double t2 = now_ms();
-	for (uint64_t x = 0; x < n; x++) {
-		whamd_poly_reorder_stats& s = r->problems[x].stats;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
-	}
-	*out = r.release();
-	return WHAMD_OK;
+	return run_batch<ReorderProblem, ReorderScores>(
+		views, n, host, out, reorder_prepare,
+		[&](auto& problems, auto& scores) {
+			for (size_t x = 0; x < problems.size(); x++) reorder_score_host(problems[x], log_match, log_err, scores[x]);
+		},
+		[&](auto& problems, auto& scores, CallTimes& times, std::string& msg) { return reorder_score_device(problems, log_match, log_err, device, scores, times, msg); },
+		[](ReorderProblem& p, ReorderScores& sc, whamd_poly_reorder_result::Problem& o) {
+			reorder_tail(p, sc, o.tail);
+			o.ploidy = p.ploidy;
+			o.stats.n_breakpoints = p.n_breakpoints();
+			o.stats.n_reads_visited = p.item_read.size();
+			o.stats.n_permutations = p.llh_ptr.back();
+			o.stats.n_window_positions = p.win.size();
+			o.llh_ptr = std::move(p.llh_ptr);
+			o.win_ptr = std::move(p.win_ptr);
+			o.win = std::move(p.win);
+			o.left = std::move(p.bp_left);
+			o.llh = std::move(sc.llh);
+		});
 }
-
-template <class T>
-void copy_out(T* dst, const std::vector<T>& src) {
-	if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
-}
-
-const whamd_poly_reorder_result::Problem* problem_of(const whamd_poly_reorder_result* r, uint64_t m) { return r && m < r->problems.size() ? &r->problems[m] : nullptr; }
-
-whamd_status_t no_problem(const whamd_poly_reorder_result* r) { return fail(WHAMD_ERR_INVALID, r ? "problem index out of range" : "null argument"); }
 
 }  // namespace
 
@@ -393,10 +354,7 @@ whamd_status_t whamd_poly_reorder_get_phasing(const whamd_poly_reorder_result* r
 }
 
 whamd_status_t whamd_poly_reorder_get_stats(const whamd_poly_reorder_result* r, uint64_t m, whamd_poly_reorder_stats* stats_out) {
-	const auto* p = problem_of(r, m);
-	if (!p || !stats_out) return !stats_out && r ? fail(WHAMD_ERR_INVALID, "null argument") : no_problem(r);
-	*stats_out = p->stats;
-	return WHAMD_OK;
+	return get_stats_of(r, m, stats_out);
 }
 
 void whamd_poly_reorder_destroy(whamd_poly_reorder_result* r) { delete r; }

@@ -11,7 +11,7 @@
 #include <memory>
 #include <unordered_map>
 
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -429,7 +429,8 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
                      whamd_poly_scores** out) {
 	if (!out || (n_matrices && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
 	*out = nullptr;
-	const double t0 = now_ms();
+	BatchClock clock;
+	clock.t0 = now_ms();
 	if (ploidy > 15) return fail(WHAMD_ERR_INVALID, "ploidy " + std::to_string(ploidy) + " above 15: the reference's Genotype holds at most 15 alleles");
 	std::vector<PolyMatrix> ms(n_matrices);
 	std::string msg;
@@ -448,7 +449,7 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 			for (uint64_t x = b; x < e; x++) poly_prepare(ms[x], min_overlap, ploidy, err);
 		});
 	}
-	const double t1 = now_ms();
+	clock.t1 = now_ms();
 	CallTimes times;
 	if (scored) {
 		const float offset = poly_offset(ploidy);
@@ -461,7 +462,7 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 			if (st != WHAMD_OK) return fail(st, msg);
 		}
 	}
-	const double t2 = now_ms();
+	clock.t2 = clock.t3 = now_ms();   // (nothing is assembled: the results are the scores)
 	for (uint64_t x = 0; x < n_matrices; x++) {
 		whamd_poly_score_stats& s = r->stats[x];
 		s.err = scored ? ms[x].err : err;
@@ -472,12 +473,7 @@ whamd_status_t score(const whamd_poly_matrix_view* views, uint64_t n_matrices, u
 		s.n_entries = r->results[x].score.size();
 		s.n_nan = r->results[x].n_nan;
 		s.n_pair_positions = r->results[x].n_pair_positions;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
+		stamp_times(s, times, clock);
 	}
 	*out = r.release();
 	return WHAMD_OK;

@@ -9,7 +9,7 @@
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -56,20 +56,12 @@ whamd_status_t whamd::polythread_prepare(const whamd_poly_thread_view& v, Thread
 		msg = "null argument";
 		return WHAMD_ERR_INVALID;
 	}
-	if (n_clusters && v.cluster_ptr[0] != 0) {
-		msg = "cluster_ptr does not start at 0";
-		return WHAMD_ERR_INVALID;
-	}
-	for (uint64_t c = 0; c < n_clusters; c++) {
-		if (v.cluster_ptr[c] > v.cluster_ptr[c + 1]) {
-			msg = "cluster_ptr decreases at cluster " + std::to_string(c);
-			return WHAMD_ERR_INVALID;
-		}
+	if (!check_offsets(v.cluster_ptr, n_clusters, "cluster_ptr", "cluster", msg)) return WHAMD_ERR_INVALID;
+	for (uint64_t c = 0; c < n_clusters; c++)
 		if (v.cluster_ptr[c + 1] - v.cluster_ptr[c] >= PT_MAX_RANK) {
 			msg = "cluster " + std::to_string(c) + " has 2^28 or more reads";
 			return WHAMD_ERR_UNSUPPORTED;
 		}
-	}
 	if (n_clusters && v.cluster_ptr[n_clusters] && !v.cluster_reads) {
 		msg = "null argument";
 		return WHAMD_ERR_INVALID;
@@ -298,49 +290,24 @@ void assemble(const ThreadProblem& p, const ThreadRows& rows, whamd_poly_thread_
 }
 
 whamd_status_t thread_inputs(const whamd_poly_thread_view* views, uint64_t n, int device, bool host, whamd_poly_thread_result** out) {
-	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
-	*out = nullptr;
-	const double t0 = now_ms();
-	std::vector<ThreadProblem> problems(n);
-	std::vector<ThreadRows> rows(n);
-	std::string msg;
-	for (uint64_t x = 0; x < n; x++) {
-		const whamd_status_t st = polythread_prepare(views[x], problems[x], msg);
-		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
-	}
-	const double t1 = now_ms();
-	CallTimes times;
-	if (host) {
-#ifdef WHAMD_DEBUG_BUILD
-		for (uint64_t x = 0; x < n; x++) polythread_host(problems[x], rows[x]);
-#endif
-	} else {
-		const whamd_status_t st = polythread_device(problems, device, rows, times, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	const double t2 = now_ms();
-	std::unique_ptr<whamd_poly_thread_result> r(new whamd_poly_thread_result());
-	r->problems.resize(n);
-	for (uint64_t x = 0; x < n; x++) {
-		if (rows[x].npc.empty()) {   // (nothing of the call touched the device: no rows anywhere)
-			rows[x].npc.assign(problems[x].m.n_positions, 0);
-			rows[x].n_sel.assign(problems[x].m.n_positions, 0);
-			rows[x].na = 4;
-		}
-		assemble(problems[x], rows[x], r->problems[x]);
-	}
-	const double t3 = now_ms();
-	for (uint64_t x = 0; x < n; x++) {
-		whamd_poly_thread_stats& s = r->problems[x].stats;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.fill_ms = t3 - t2;
-		s.total_ms = t3 - t0;
-	}
-	*out = r.release();
+	BatchClock clock;
+	const whamd_status_t st = run_batch<ThreadProblem, ThreadRows>(
+		views, n, host, out, polythread_prepare,
+		[](auto& problems, auto& rows) {
+			for (size_t x = 0; x < problems.size(); x++) polythread_host(problems[x], rows[x]);
+		},
+		[&](auto& problems, auto& rows, CallTimes& times, std::string& msg) { return polythread_device(problems, device, rows, times, msg); },
+		[](const ThreadProblem& p, ThreadRows& rows, whamd_poly_thread_result::Problem& o) {
+			if (rows.npc.empty()) {   // (nothing of the call touched the device: no rows anywhere)
+				rows.npc.assign(p.m.n_positions, 0);
+				rows.n_sel.assign(p.m.n_positions, 0);
+				rows.na = 4;
+			}
+			assemble(p, rows, o);
+		},
+		&clock);
+	if (st != WHAMD_OK) return st;
+	for (auto& p : (*out)->problems) p.stats.fill_ms = clock.t3 - clock.t2;
 	return WHAMD_OK;
 }
 
@@ -351,8 +318,8 @@ whamd_status_t select_clusters(uint64_t n_pos, const uint64_t* pc_ptr, const uin
 	if (!ploidy_ok(ploidy, msg)) return fail(WHAMD_ERR_INVALID, msg);
 	if (!pc_ptr || !cov_ptr_out) return fail(WHAMD_ERR_INVALID, "null argument");
 	if (n_pos >= 0xfffff000ull) return fail(WHAMD_ERR_UNSUPPORTED, "2^32 - 4096 or more positions");
-	if (pc_ptr[0] != 0) return fail(WHAMD_ERR_INVALID, "pc_ptr does not start at 0");
-	for (uint64_t x = 0; x < n_pos; x++)
+	if (pc_ptr[0] != 0) return fail(WHAMD_ERR_INVALID, not_from_zero("pc_ptr"));
+	for (uint64_t x = 0; x < n_pos; x++)   // (strict: not check_offsets)
 		if (pc_ptr[x] >= pc_ptr[x + 1]) return fail(WHAMD_ERR_INVALID, "position " + std::to_string(x) + " lists no cluster");
 	const uint64_t n_rows = pc_ptr[n_pos];
 	if (n_rows >= 0xfffff000ull) return fail(WHAMD_ERR_UNSUPPORTED, "2^32 - 4096 or more rows");
@@ -409,9 +376,7 @@ whamd_status_t haplotypes(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy
 	if (!n_pos) return WHAMD_OK;
 	if (!paths || !pc_ptr || !out) return fail(WHAMD_ERR_INVALID, "null argument");
 	if (n_pos >= 0xfffff000ull) return fail(WHAMD_ERR_UNSUPPORTED, "2^32 - 4096 or more positions");
-	if (pc_ptr[0] != 0) return fail(WHAMD_ERR_INVALID, "pc_ptr does not start at 0");
-	for (uint64_t x = 0; x < n_pos; x++)
-		if (pc_ptr[x] > pc_ptr[x + 1]) return fail(WHAMD_ERR_INVALID, "pc_ptr decreases at position " + std::to_string(x));
+	if (!check_offsets(pc_ptr, n_pos, "pc_ptr", "position", msg)) return fail(WHAMD_ERR_INVALID, msg);
 	if (pc_ptr[n_pos] >= 0xfffff000ull / ploidy) return fail(WHAMD_ERR_UNSUPPORTED, "too many rows for uint32 offsets");
 	if (pc_ptr[n_pos] && (!pc_cluster || !pc_cons)) return fail(WHAMD_ERR_INVALID, "null argument");
 	if (host) {
@@ -429,13 +394,6 @@ whamd_status_t haplotypes(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy
 	std::memcpy(out, got.data(), got.size());
 	return WHAMD_OK;
 }
-
-template <class T>
-void copy_out(T* dst, const std::vector<T>& src) {
-	if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
-}
-
-const whamd_poly_thread_result::Problem* problem_of(const whamd_poly_thread_result* r, uint64_t m) { return r && m < r->problems.size() ? &r->problems[m] : nullptr; }
 
 }  // namespace
 
@@ -464,9 +422,8 @@ uint64_t whamd_poly_thread_cov_count(const whamd_poly_thread_result* r, uint64_t
 
 whamd_status_t whamd_poly_thread_get_rows(const whamd_poly_thread_result* r, uint64_t m, uint64_t* pc_ptr_out, uint32_t* cluster_out, uint32_t* depth_out,
                                           uint32_t* first_out, int8_t* consensus_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
 	const auto* p = problem_of(r, m);
-	if (!p) return fail(WHAMD_ERR_INVALID, "problem index out of range");
+	if (!p) return no_problem(r);
 	copy_out(pc_ptr_out, p->pc_ptr);
 	copy_out(cluster_out, p->cluster);
 	copy_out(depth_out, p->depth);
@@ -477,9 +434,8 @@ whamd_status_t whamd_poly_thread_get_rows(const whamd_poly_thread_result* r, uin
 
 whamd_status_t whamd_poly_thread_get_cov(const whamd_poly_thread_result* r, uint64_t m, uint64_t* cov_ptr_out, uint32_t* cluster_out, uint8_t* readded_out,
                                          uint32_t* rank_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
 	const auto* p = problem_of(r, m);
-	if (!p) return fail(WHAMD_ERR_INVALID, "problem index out of range");
+	if (!p) return no_problem(r);
 	copy_out(cov_ptr_out, p->cov.ptr);
 	copy_out(cluster_out, p->cov.cluster);
 	copy_out(readded_out, p->cov.readded);
@@ -488,11 +444,7 @@ whamd_status_t whamd_poly_thread_get_cov(const whamd_poly_thread_result* r, uint
 }
 
 whamd_status_t whamd_poly_thread_get_stats(const whamd_poly_thread_result* r, uint64_t m, whamd_poly_thread_stats* stats_out) {
-	if (!r || !stats_out) return fail(WHAMD_ERR_INVALID, "null argument");
-	const auto* p = problem_of(r, m);
-	if (!p) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	*stats_out = p->stats;
-	return WHAMD_OK;
+	return get_stats_of(r, m, stats_out);
 }
 
 void whamd_poly_thread_destroy(whamd_poly_thread_result* r) { delete r; }

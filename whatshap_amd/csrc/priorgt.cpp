@@ -14,7 +14,7 @@
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -105,15 +105,7 @@ whamd_status_t whamd::priorgt_prepare(const whamd_prior_genotypes_view& v, Prior
 			      (v.positions[c] == v.positions[c - 1] ? " is a duplicate" : " comes after a larger one");
 			return WHAMD_ERR_INVALID;
 		}
-	if (n_reads && v.read_ptr[0] != 0) {
-		msg = "read_ptr does not start at 0";
-		return WHAMD_ERR_INVALID;
-	}
-	for (uint64_t r = 0; r < n_reads; r++)
-		if (v.read_ptr[r] > v.read_ptr[r + 1]) {
-			msg = "read_ptr decreases at read " + std::to_string(r);
-			return WHAMD_ERR_INVALID;
-		}
+	if (!check_offsets(v.read_ptr, n_reads, "read_ptr", "read", msg)) return WHAMD_ERR_INVALID;
 	const uint64_t n_entries = n_reads ? v.read_ptr[n_reads] : 0;
 	if (n_entries && (!v.entry_position || !v.entry_allele || !v.entry_quality)) {
 		msg = "null argument";
@@ -230,44 +222,18 @@ void assemble(const PriorProblem& p, PriorScores& sc, whamd_prior_genotypes_resu
 }
 
 whamd_status_t prior_genotypes(const whamd_prior_genotypes_view* views, uint64_t n, int device, bool host, whamd_prior_genotypes_result** out) {
-	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
-	*out = nullptr;
-	const double t0 = now_ms();
-	std::vector<PriorProblem> problems(n);
-	std::vector<PriorScores> scores(n);
-	std::string msg;
-	for (uint64_t x = 0; x < n; x++) {
-		const whamd_status_t st = priorgt_prepare(views[x], problems[x], msg);
-		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
-	}
-	const double t1 = now_ms();
-	CallTimes times;
-	if (host) {
-#ifdef WHAMD_DEBUG_BUILD
-		double table[3 * PG_CODES];
-		pg_factor_table(table);
-		for (uint64_t x = 0; x < n; x++)
-			if (problems[x].n_counted) priorgt_host(problems[x], table, scores[x]);
-#endif
-	} else {
-		const whamd_status_t st = priorgt_device(problems, device, scores, times, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	std::unique_ptr<whamd_prior_genotypes_result> r(new whamd_prior_genotypes_result());
-	r->problems.resize(n);
-	for (uint64_t x = 0; x < n; x++) assemble(problems[x], scores[x], r->problems[x]);
-	const double t2 = now_ms();
-	for (uint64_t x = 0; x < n; x++) {
-		whamd_prior_genotypes_stats& s = r->problems[x].stats;
-		s.launches = times.launches;
-		s.map_ms = t1 - t0;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
-	}
-	*out = r.release();
+	BatchClock clock;
+	const whamd_status_t st = run_batch<PriorProblem, PriorScores>(
+		views, n, host, out, priorgt_prepare,
+		[](auto& problems, auto& scores) {
+			double table[3 * PG_CODES];
+			pg_factor_table(table);
+			for (size_t x = 0; x < problems.size(); x++)
+				if (problems[x].n_counted) priorgt_host(problems[x], table, scores[x]);
+		},
+		[&](auto& problems, auto& scores, CallTimes& times, std::string& msg) { return priorgt_device(problems, device, scores, times, msg); }, assemble, &clock);
+	if (st != WHAMD_OK) return st;
+	for (auto& p : (*out)->problems) p.stats.map_ms = clock.t1 - clock.t0;   // (the mapping is the preparation)
 	return WHAMD_OK;
 }
 
@@ -285,9 +251,9 @@ uint64_t whamd_prior_genotypes_count(const whamd_prior_genotypes_result* r, uint
 
 whamd_status_t whamd_prior_genotypes_get(const whamd_prior_genotypes_result* r, uint64_t m, double* gl_out, int8_t* genotype_out, double* reg_out,
                                          int8_t* reg_genotype_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	const std::vector<PgOut>& o = r->problems[m].out;
+	const auto* p = problem_of(r, m);
+	if (!p) return no_problem(r);
+	const std::vector<PgOut>& o = p->out;
 	for (size_t c = 0; c < o.size(); c++) {
 		if (gl_out) std::memcpy(gl_out + 3 * c, o[c].gl, sizeof o[c].gl);
 		if (genotype_out) genotype_out[c] = (int8_t)o[c].genotype;
@@ -298,10 +264,7 @@ whamd_status_t whamd_prior_genotypes_get(const whamd_prior_genotypes_result* r, 
 }
 
 whamd_status_t whamd_prior_genotypes_get_stats(const whamd_prior_genotypes_result* r, uint64_t m, whamd_prior_genotypes_stats* stats_out) {
-	if (!r || !stats_out) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	*stats_out = r->problems[m].stats;
-	return WHAMD_OK;
+	return get_stats_of(r, m, stats_out);
 }
 
 void whamd_prior_genotypes_destroy(whamd_prior_genotypes_result* r) { delete r; }

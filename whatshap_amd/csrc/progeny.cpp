@@ -9,7 +9,7 @@
 #include <memory>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -343,7 +343,8 @@ struct whamd_progeny_scores {
 namespace {
 
 // Counts and times of a finished call into its stats.
-void fill_stats(whamd_progeny_scores& r, const CallTimes& times, double t0, double t1, double t2) {
+void fill_stats(whamd_progeny_scores& r, const CallTimes& times, BatchClock clock) {
+	clock.t2 = clock.t3 = now_ms();   // (nothing is assembled: the results are the scores)
 	for (size_t x = 0; x < r.problems.size(); x++) {
 		const ProgenyProblem& p = r.problems[x];
 		whamd_progeny_score_stats& s = r.stats[x];
@@ -352,19 +353,15 @@ void fill_stats(whamd_progeny_scores& r, const CallTimes& times, double t0, doub
 		s.n_inf = p.n_inf;
 		s.n_reused = p.n_reused;
 		s.n_sample_terms = (p.lo.size() - p.n_inf) * (uint64_t)p.n_samples;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
+		stamp_times(s, times, clock);
 	}
 }
 
 whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bool host, whamd_progeny_scores** out) {
 	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
 	*out = nullptr;
-	const double t0 = now_ms();
+	BatchClock clock;
+	clock.t0 = now_ms();
 	std::unique_ptr<whamd_progeny_scores> r(new whamd_progeny_scores());
 	r->problems.resize(n);
 	r->results.resize(n);
@@ -374,7 +371,7 @@ whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bo
 		const whamd_status_t st = progeny_prepare(views[x], r->problems[x], msg);
 		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
 	}
-	const double t1 = now_ms();
+	clock.t1 = now_ms();
 	CallTimes times;
 	if (host) {
 #ifdef WHAMD_DEBUG_BUILD
@@ -384,7 +381,7 @@ whamd_status_t score(const whamd_progeny_view* views, uint64_t n, int device, bo
 		const whamd_status_t st = progeny_score_device(r->problems, device, r->results, times, msg);
 		if (st != WHAMD_OK) return fail(st, msg);
 	}
-	fill_stats(*r, times, t0, t1, now_ms());
+	fill_stats(*r, times, clock);
 	*out = r.release();
 	return WHAMD_OK;
 }
@@ -420,7 +417,8 @@ whamd_status_t gl(const whamd_progeny_depths_view* views, uint64_t n, int device
 whamd_status_t score_depths(const whamd_progeny_depths_view* views, uint64_t n, int device, whamd_progeny_scores** out) {
 	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
 	*out = nullptr;
-	const double t0 = now_ms();
+	BatchClock clock;
+	clock.t0 = now_ms();
 	std::unique_ptr<whamd_progeny_scores> r(new whamd_progeny_scores());
 	r->problems.resize(n);
 	r->results.resize(n);
@@ -436,11 +434,11 @@ whamd_status_t score_depths(const whamd_progeny_depths_view* views, uint64_t n, 
 		st = progeny_prepare(pv, r->problems[x], msg, false);
 		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
 	}
-	const double t1 = now_ms();
+	clock.t1 = now_ms();
 	CallTimes times;
 	st = progeny_score_depths_device(ds, r->problems, device, r->results, times, msg);
 	if (st != WHAMD_OK) return fail(st, msg);
-	fill_stats(*r, times, t0, t1, now_ms());
+	fill_stats(*r, times, clock);
 	*out = r.release();
 	return WHAMD_OK;
 }

@@ -13,7 +13,7 @@
 #include <unordered_map>
 
 #include "../../include/whatshap_amd_debug.h"
-#include "api_guard.h"
+#include "batch_call.h"
 #include "debug_build.h"
 
 using namespace whamd;
@@ -39,15 +39,7 @@ whamd_status_t whamd::tagphase_prepare(const whamd_tagphase_view& v, TagphasePro
 		return WHAMD_ERR_UNSUPPORTED;
 	}
 	const uint64_t n_reads = v.n_reads, n_var = v.n_variants;
-	if (n_reads && v.read_ptr[0] != 0) {
-		msg = "read_ptr does not start at 0";
-		return WHAMD_ERR_INVALID;
-	}
-	for (uint64_t r = 0; r < n_reads; r++)
-		if (v.read_ptr[r] > v.read_ptr[r + 1]) {
-			msg = "read_ptr decreases at read " + std::to_string(r);
-			return WHAMD_ERR_INVALID;
-		}
+	if (!check_offsets(v.read_ptr, n_reads, "read_ptr", "read", msg)) return WHAMD_ERR_INVALID;
 	const uint64_t n_entries = n_reads ? v.read_ptr[n_reads] : 0;
 	if (n_entries && (!v.entry_variant || !v.entry_id || !v.entry_quality)) {
 		msg = "null argument";
@@ -253,47 +245,13 @@ void assemble(const TagphaseProblem& p, const TagphaseScores& sc, whamd_tagphase
 }
 
 whamd_status_t tagphase(const whamd_tagphase_view* views, uint64_t n, int device, bool host, whamd_tagphase_result** out) {
-	if (!out || (n && !views)) return fail(WHAMD_ERR_INVALID, "null argument");
-	*out = nullptr;
-	const double t0 = now_ms();
-	std::vector<TagphaseProblem> problems(n);
-	std::vector<TagphaseScores> scores(n);
-	std::string msg;
-	for (uint64_t x = 0; x < n; x++) {
-		const whamd_status_t st = tagphase_prepare(views[x], problems[x], msg);
-		if (st != WHAMD_OK) return fail(st, n > 1 ? "problem " + std::to_string(x) + ": " + msg : msg);
-	}
-	const double t1 = now_ms();
-	CallTimes times;
-	if (host) {
-#ifdef WHAMD_DEBUG_BUILD
-		for (uint64_t x = 0; x < n; x++)
-			if (problems[x].n_voting) tagphase_host(problems[x], scores[x]);
-#endif
-	} else {
-		const whamd_status_t st = tagphase_device(problems, device, scores, times, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	std::unique_ptr<whamd_tagphase_result> r(new whamd_tagphase_result());
-	r->problems.resize(n);
-	for (uint64_t x = 0; x < n; x++) assemble(problems[x], scores[x], r->problems[x]);
-	const double t2 = now_ms();
-	for (uint64_t x = 0; x < n; x++) {
-		whamd_tagphase_stats& s = r->problems[x].stats;
-		s.launches = times.launches;
-		s.host_ms = t1 - t0;
-		s.upload_ms = times.upload_ms;
-		s.kernel_ms = times.kernel_ms;
-		s.download_ms = times.download_ms;
-		s.total_ms = t2 - t0;
-	}
-	*out = r.release();
-	return WHAMD_OK;
-}
-
-template <class T>
-void copy_out(T* dst, const std::vector<T>& src) {
-	if (dst && !src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
+	return run_batch<TagphaseProblem, TagphaseScores>(
+		views, n, host, out, tagphase_prepare,
+		[](auto& problems, auto& scores) {
+			for (size_t x = 0; x < problems.size(); x++)
+				if (problems[x].n_voting) tagphase_host(problems[x], scores[x]);
+		},
+		[&](auto& problems, auto& scores, CallTimes& times, std::string& msg) { return tagphase_device(problems, device, scores, times, msg); }, assemble);
 }
 
 }  // namespace
@@ -311,18 +269,17 @@ uint64_t whamd_tagphase_count(const whamd_tagphase_result* r, uint64_t m) { retu
 whamd_status_t whamd_tagphase_get(const whamd_tagphase_result* r, uint64_t m, uint8_t* voted_out, uint64_t* first_out, uint32_t* n_phasesets_out,
                                   int64_t* best_ps_out, uint8_t* best_id_out, int64_t* score_out, int64_t* total_out, uint8_t* kept_out,
                                   uint8_t* zero_total_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	const whamd_tagphase_result::Problem& p = r->problems[m];
-	copy_out(voted_out, p.voted);
-	copy_out(first_out, p.first);
-	copy_out(n_phasesets_out, p.n_phasesets);
-	copy_out(best_ps_out, p.best_ps);
-	copy_out(best_id_out, p.best_id);
-	copy_out(score_out, p.score);
-	copy_out(total_out, p.total);
-	copy_out(kept_out, p.kept);
-	copy_out(zero_total_out, p.zero_total);
+	const auto* p = problem_of(r, m);
+	if (!p) return no_problem(r);
+	copy_out(voted_out, p->voted);
+	copy_out(first_out, p->first);
+	copy_out(n_phasesets_out, p->n_phasesets);
+	copy_out(best_ps_out, p->best_ps);
+	copy_out(best_id_out, p->best_id);
+	copy_out(score_out, p->score);
+	copy_out(total_out, p->total);
+	copy_out(kept_out, p->kept);
+	copy_out(zero_total_out, p->zero_total);
 	return WHAMD_OK;
 }
 
@@ -330,23 +287,19 @@ uint64_t whamd_tagphase_row_count(const whamd_tagphase_result* r, uint64_t m) { 
 
 whamd_status_t whamd_tagphase_get_table(const whamd_tagphase_result* r, uint64_t m, uint64_t* row_ptr_out, int64_t* ps_out, int64_t* sum0_out,
                                         int64_t* sum1_out, uint64_t* first_out) {
-	if (!r) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	const whamd_tagphase_result::Problem& p = r->problems[m];
-	if (p.row_ptr.empty()) return fail(WHAMD_ERR_INVALID, "the problem was not given want_table");
-	copy_out(row_ptr_out, p.row_ptr);
-	copy_out(ps_out, p.row_ps);
-	copy_out(sum0_out, p.row_sum0);
-	copy_out(sum1_out, p.row_sum1);
-	copy_out(first_out, p.row_first);
+	const auto* p = problem_of(r, m);
+	if (!p) return no_problem(r);
+	if (p->row_ptr.empty()) return fail(WHAMD_ERR_INVALID, "the problem was not given want_table");
+	copy_out(row_ptr_out, p->row_ptr);
+	copy_out(ps_out, p->row_ps);
+	copy_out(sum0_out, p->row_sum0);
+	copy_out(sum1_out, p->row_sum1);
+	copy_out(first_out, p->row_first);
 	return WHAMD_OK;
 }
 
 whamd_status_t whamd_tagphase_get_stats(const whamd_tagphase_result* r, uint64_t m, whamd_tagphase_stats* stats_out) {
-	if (!r || !stats_out) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (m >= r->problems.size()) return fail(WHAMD_ERR_INVALID, "problem index out of range");
-	*stats_out = r->problems[m].stats;
-	return WHAMD_OK;
+	return get_stats_of(r, m, stats_out);
 }
 
 void whamd_tagphase_destroy(whamd_tagphase_result* r) { delete r; }

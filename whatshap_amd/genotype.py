@@ -150,38 +150,20 @@ def prior_genotypes_batch(problems: Sequence[PriorProblem], device: int = 0, hos
     """Every problem (sample x chromosome) in one native call: one upload, ``_native.PRIOR_GENOTYPES_LAUNCHES`` launches whatever the
     problems (none when no entry counts), one download.  ``stats``, if given, receives one dict per problem (its counts; launches and
     times are those of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.PriorGenotypesView * max(n, 1))()
-    for k, p in enumerate(problems):
-        views[k] = p.view()
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_prior_genotypes_host(views, n, C.byref(h))
-    else:
-        st = L.whamd_prior_genotypes(views, n, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _native.raise_status(L, st)
     P = _native._ptr
-    try:
+    with _native.batch_handle(host, [p.view() for p in problems], "whamd_prior_genotypes", "whamd_debug_prior_genotypes_host",
+                              "whamd_prior_genotypes_destroy", device=device) as (L, h):
         out = []
-        for k in range(n):
+        for k in range(len(problems)):
             cnt = L.whamd_prior_genotypes_count(h, k)
             gl, reg = np.zeros((cnt, 3), dtype=np.float64), np.zeros((cnt, 3), dtype=np.float64)
             gt, reg_gt = np.zeros(cnt, dtype=np.int8), np.zeros(cnt, dtype=np.int8)
-            st = L.whamd_prior_genotypes_get(h, k, P(gl, C.c_double), P(gt, C.c_int8), P(reg, C.c_double), P(reg_gt, C.c_int8))
-            if st != _native.WHAMD_OK:
-                _native.raise_status(L, st)
-            ts = _native.PriorGenotypesStats()
-            st = L.whamd_prior_genotypes_get_stats(h, k, C.byref(ts))
-            if st != _native.WHAMD_OK:
-                _native.raise_status(L, st)
-            out.append(PriorResult(gl, gt, reg, reg_gt, ts.as_dict()))
+            _native.checked(L, L.whamd_prior_genotypes_get(h, k, P(gl, C.c_double), P(gt, C.c_int8), P(reg, C.c_double), P(reg_gt, C.c_int8)))
+            ts = _native.read_stats(L, "whamd_prior_genotypes_get_stats", _native.PriorGenotypesStats, h, k)
+            out.append(PriorResult(gl, gt, reg, reg_gt, ts))
             if stats is not None:
-                stats.append(ts.as_dict())
+                stats.append(dict(ts))
         return out
-    finally:
-        L.whamd_prior_genotypes_destroy(h)
 
 
 def int_to_diploid_biallelic_gt(numeric_repr: int) -> core.Genotype:

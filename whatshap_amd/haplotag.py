@@ -171,49 +171,29 @@ class HaplotagResult:
 def haplotag_batch(problems: Sequence[HaplotagProblem], device: int = 0, host: bool = False, stats: Optional[list] = None) -> List[HaplotagResult]:
     """Every problem (chromosome x sample) in one native call: one upload, at most three launches, one download for the whole batch.
     ``stats``, if given, receives one dict per problem (its counts; launches and times are those of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.HaplotagView * max(n, 1))()
-    for k, p in enumerate(problems):
-        views[k] = p.view()
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_haplotag_host(views, n, C.byref(h))
-    else:
-        st = L.whamd_haplotag(views, n, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _native.raise_status(L, st)
-    try:
+    with _native.batch_handle(host, [p.view() for p in problems], "whamd_haplotag", "whamd_debug_haplotag_host", "whamd_haplotag_destroy",
+                              device=device) as (L, h):
         out = []
-        for k in range(n):
+        for k in range(len(problems)):
             cnt = L.whamd_haplotag_count(h, k)
             hap = np.empty(cnt, dtype=np.int32)
             qual = np.empty(cnt, dtype=np.int64)
             ps = np.empty(cnt, dtype=np.int64)
             if cnt:
-                st = L.whamd_haplotag_get(h, k, _native._ptr(hap, C.c_int32), _native._ptr(qual, C.c_int64), _native._ptr(ps, C.c_int64))
-                if st != _native.WHAMD_OK:
-                    _native.raise_status(L, st)
+                _native.checked(L, L.whamd_haplotag_get(h, k, _native._ptr(hap, C.c_int32), _native._ptr(qual, C.c_int64), _native._ptr(ps, C.c_int64)))
             nbx = L.whamd_haplotag_bx_count(h, k)
             bx = np.empty(nbx, dtype=np.uint32)
             bx_start = np.empty(nbx, dtype=np.int64)
             bx_hap = np.empty(nbx, dtype=np.int32)
             bx_ps = np.empty(nbx, dtype=np.int64)
             if nbx:
-                st = L.whamd_haplotag_get_bx(h, k, _native._ptr(bx, C.c_uint32), _native._ptr(bx_start, C.c_int64), _native._ptr(bx_hap, C.c_int32),
-                                             _native._ptr(bx_ps, C.c_int64))
-                if st != _native.WHAMD_OK:
-                    _native.raise_status(L, st)
-            hs = _native.HaplotagStats()
-            st = L.whamd_haplotag_get_stats(h, k, C.byref(hs))
-            if st != _native.WHAMD_OK:
-                _native.raise_status(L, st)
-            out.append(HaplotagResult(hap, qual, ps, bx, bx_start, bx_hap, bx_ps, hs.as_dict()))
+                _native.checked(L, L.whamd_haplotag_get_bx(h, k, _native._ptr(bx, C.c_uint32), _native._ptr(bx_start, C.c_int64), _native._ptr(bx_hap, C.c_int32),
+                                                           _native._ptr(bx_ps, C.c_int64)))
+            hs = _native.read_stats(L, "whamd_haplotag_get_stats", _native.HaplotagStats, h, k)
+            out.append(HaplotagResult(hap, qual, ps, bx, bx_start, bx_hap, bx_ps, hs))
             if stats is not None:
-                stats.append(hs.as_dict())
+                stats.append(dict(hs))
         return out
-    finally:
-        L.whamd_haplotag_destroy(h)
 
 
 def prepare_haplotag_information(variant_table, shared_samples, phased_input_reader, regions, ignore_linked_read, linked_read_cutoff, ploidy,

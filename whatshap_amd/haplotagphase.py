@@ -141,49 +141,29 @@ def tagphase_batch(problems: Sequence[TagphaseProblem], device: int = 0, host: b
                    stats: Optional[list] = None) -> List[TagphaseResult]:
     """Every problem (chromosome x sample) in one native call: one upload, 7 launches (11 with ``want_table``) whatever the problems.
     ``stats``, if given, receives one dict per problem (its counts; launches and times are those of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.TagphaseView * max(n, 1))()
-    for k, p in enumerate(problems):
-        views[k] = p.view(want_table)
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_tagphase_host(views, n, C.byref(h))
-    else:
-        st = L.whamd_tagphase(views, n, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _native.raise_status(L, st)
     P = _native._ptr
-    try:
+    with _native.batch_handle(host, [p.view(want_table) for p in problems], "whamd_tagphase", "whamd_debug_tagphase_host", "whamd_tagphase_destroy",
+                              device=device) as (L, h):
         out = []
-        for k in range(n):
+        for k in range(len(problems)):
             cnt = L.whamd_tagphase_count(h, k)
             u8 = lambda: np.zeros(cnt, dtype=np.uint8)   # noqa: E731
             i64 = lambda: np.zeros(cnt, dtype=np.int64)   # noqa: E731
             voted, first, nps, best_ps, best_id, score, total, kept, zero = u8(), np.zeros(cnt, dtype=np.uint64), np.zeros(cnt, dtype=np.uint32), i64(), u8(), i64(), i64(), u8(), u8()
-            st = L.whamd_tagphase_get(h, k, P(voted, C.c_uint8), P(first, C.c_uint64), P(nps, C.c_uint32), P(best_ps, C.c_int64), P(best_id, C.c_uint8),
-                                      P(score, C.c_int64), P(total, C.c_int64), P(kept, C.c_uint8), P(zero, C.c_uint8))
-            if st != _native.WHAMD_OK:
-                _native.raise_status(L, st)
+            _native.checked(L, L.whamd_tagphase_get(h, k, P(voted, C.c_uint8), P(first, C.c_uint64), P(nps, C.c_uint32), P(best_ps, C.c_int64),
+                                                    P(best_id, C.c_uint8), P(score, C.c_int64), P(total, C.c_int64), P(kept, C.c_uint8), P(zero, C.c_uint8)))
             table = None
             if want_table:
                 rows = L.whamd_tagphase_row_count(h, k)
                 table = (np.zeros(cnt + 1, dtype=np.uint64), np.zeros(rows, dtype=np.int64), np.zeros(rows, dtype=np.int64), np.zeros(rows, dtype=np.int64),
                          np.zeros(rows, dtype=np.uint64))
-                st = L.whamd_tagphase_get_table(h, k, P(table[0], C.c_uint64), P(table[1], C.c_int64), P(table[2], C.c_int64), P(table[3], C.c_int64),
-                                                P(table[4], C.c_uint64))
-                if st != _native.WHAMD_OK:
-                    _native.raise_status(L, st)
-            ts = _native.TagphaseStats()
-            st = L.whamd_tagphase_get_stats(h, k, C.byref(ts))
-            if st != _native.WHAMD_OK:
-                _native.raise_status(L, st)
-            out.append(TagphaseResult((voted, first, nps, best_ps, best_id, score, total, kept, zero), table, ts.as_dict()))
+                _native.checked(L, L.whamd_tagphase_get_table(h, k, P(table[0], C.c_uint64), P(table[1], C.c_int64), P(table[2], C.c_int64),
+                                                              P(table[3], C.c_int64), P(table[4], C.c_uint64)))
+            ts = _native.read_stats(L, "whamd_tagphase_get_stats", _native.TagphaseStats, h, k)
+            out.append(TagphaseResult((voted, first, nps, best_ps, best_id, score, total, kept, zero), table, ts))
             if stats is not None:
-                stats.append(ts.as_dict())
+                stats.append(dict(ts))
         return out
-    finally:
-        L.whamd_tagphase_destroy(h)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's signatures

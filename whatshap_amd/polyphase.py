@@ -209,48 +209,24 @@ class TriangleSparseMatrix:
         return keys[o, 0].astype(np.uint32), keys[o, 1].astype(np.uint32), vals[o]
 
 
-def _raise(L, status: int):
-    msg = L.whamd_last_error().decode("utf-8", "replace")
-    if status == _native.WHAMD_ERR_INVALID:
-        raise ValueError(msg)
-    raise _native.SolverError(status, msg)
-
-
 def score_readsets_batch(matrices: Sequence[AlleleMatrix], minOverlap: int, ploidy: int, err: float = 0.0, device: int = 0, host: bool = False,
                          stats: Optional[list] = None) -> List[TriangleSparseMatrix]:
     """scoreReadset for every matrix, in one native call (one launch sequence for the whole batch).  ``stats``, if given, receives one
     dict per matrix (err used, counts, and the timings of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(matrices)
-    views = (_native.PolyMatrixView * max(n, 1))()
-    for k, am in enumerate(matrices):
-        views[k] = am.view()
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_poly_score_host(views, n, int(minOverlap), int(ploidy), float(err), C.byref(h))
-    else:
-        st = L.whamd_poly_score(views, n, int(minOverlap), int(ploidy), float(err), int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
-    try:
+    with _native.batch_handle(host, [am.view() for am in matrices], "whamd_poly_score", "whamd_debug_poly_score_host", "whamd_poly_score_destroy",
+                              int(minOverlap), int(ploidy), float(err), device=device) as (L, h):
         out = []
-        for k in range(n):
+        for k in range(len(matrices)):
             cnt = L.whamd_poly_score_count(h, k)
             i = np.empty(cnt, dtype=np.uint32)
             j = np.empty(cnt, dtype=np.uint32)
             s = np.empty(cnt, dtype=np.float32)
             if cnt:
-                st = L.whamd_poly_score_get(h, k, _native._ptr(i, C.c_uint32), _native._ptr(j, C.c_uint32), _native._ptr(s, C.c_float))
-                if st != _native.WHAMD_OK:
-                    _raise(L, st)
+                _native.checked(L, L.whamd_poly_score_get(h, k, _native._ptr(i, C.c_uint32), _native._ptr(j, C.c_uint32), _native._ptr(s, C.c_float)))
             out.append(TriangleSparseMatrix(i, j, s))
             if stats is not None:
-                ps = _native.PolyScoreStats()
-                L.whamd_poly_score_get_stats(h, k, C.byref(ps))
-                stats.append(ps.as_dict())
+                stats.append(_native.read_stats(L, "whamd_poly_score_get_stats", _native.PolyScoreStats, h, k))
         return out
-    finally:
-        L.whamd_poly_score_destroy(h)
 
 
 def scoreReadset(am: AlleleMatrix, minOverlap: int, ploidy: int, err: float = 0.0, device: int = 0, host: bool = False,
@@ -276,7 +252,5 @@ def estimate_allele_error_rate(am: AlleleMatrix, ploidy: int, device: int = 0, h
     L = _native.debug_lib() if host else _native.lib()
     v = am.view()
     out = C.c_double()
-    st = L.whamd_poly_estimate_error_rate(C.byref(v), int(ploidy), C.byref(out))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
+    _native.checked(L, L.whamd_poly_estimate_error_rate(C.byref(v), int(ploidy), C.byref(out)))
     return out.value

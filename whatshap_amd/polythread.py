@@ -128,44 +128,26 @@ def _switch_costs(n_entries: int, n_reads: int) -> Tuple[int, int]:
     return affine, 4 * affine
 
 
-def _call(L, st):
-    if st != _native.WHAMD_OK:
-        _native.raise_status(L, st)
-
-
 def threading_inputs_batch(problems: Sequence[ThreadingProblem], device: int = 0, host: bool = False, stats: Optional[list] = None) -> List[ThreadingInputs]:
     """Every problem (block) in one native call: one upload, ``_native.POLY_THREAD_LAUNCHES`` launches whatever the problems.  ``stats``,
     if given, receives one dict per problem (its counts; launches and times are those of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.PolyThreadView * max(n, 1))()
-    for k, p in enumerate(problems):
-        views[k] = p.view()
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_poly_thread_inputs_host(views, n, C.byref(h))
-    else:
-        st = L.whamd_poly_thread_inputs(views, n, int(device), C.byref(h))
-    _call(L, st)
     P = _native._ptr
-    try:
+    with _native.batch_handle(host, [p.view() for p in problems], "whamd_poly_thread_inputs", "whamd_debug_poly_thread_inputs_host",
+                              "whamd_poly_thread_destroy", device=device) as (L, h):
         out = []
         for k, p in enumerate(problems):
             n_pos, n_rows, n_cov = L.whamd_poly_thread_position_count(h, k), L.whamd_poly_thread_row_count(h, k), L.whamd_poly_thread_cov_count(h, k)
             rows = (np.zeros(n_pos + 1, dtype=np.uint64), np.zeros(n_rows, dtype=np.uint32), np.zeros((n_rows, p.n_alleles), dtype=np.uint32),
                     np.zeros((n_rows, p.n_alleles), dtype=np.uint32), np.zeros((n_rows, p.ploidy), dtype=np.int8))
-            _call(L, L.whamd_poly_thread_get_rows(h, k, P(rows[0], C.c_uint64), P(rows[1], C.c_uint32), P(rows[2], C.c_uint32), P(rows[3], C.c_uint32),
+            _native.checked(L, L.whamd_poly_thread_get_rows(h, k, P(rows[0], C.c_uint64), P(rows[1], C.c_uint32), P(rows[2], C.c_uint32), P(rows[3], C.c_uint32),
                                                   P(rows[4], C.c_int8)))
             cov = (np.zeros(n_pos + 1, dtype=np.uint64), np.zeros(n_cov, dtype=np.uint32), np.zeros(n_cov, dtype=np.uint8), np.zeros(n_cov, dtype=np.uint32))
-            _call(L, L.whamd_poly_thread_get_cov(h, k, P(cov[0], C.c_uint64), P(cov[1], C.c_uint32), P(cov[2], C.c_uint8), P(cov[3], C.c_uint32)))
-            ts = _native.PolyThreadStats()
-            _call(L, L.whamd_poly_thread_get_stats(h, k, C.byref(ts)))
-            out.append(ThreadingInputs(p.ploidy, p.n_alleles, rows, cov, _switch_costs(ts.n_entries, ts.n_reads), ts.as_dict()))
+            _native.checked(L, L.whamd_poly_thread_get_cov(h, k, P(cov[0], C.c_uint64), P(cov[1], C.c_uint32), P(cov[2], C.c_uint8), P(cov[3], C.c_uint32)))
+            ts = _native.read_stats(L, "whamd_poly_thread_get_stats", _native.PolyThreadStats, h, k)
+            out.append(ThreadingInputs(p.ploidy, p.n_alleles, rows, cov, _switch_costs(ts["n_entries"], ts["n_reads"]), ts))
             if stats is not None:
-                stats.append(ts.as_dict())
+                stats.append(dict(ts))
         return out
-    finally:
-        L.whamd_poly_thread_destroy(h)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's signatures
@@ -212,7 +194,7 @@ def select_clusters(allele_depths: List[Dict[int, Dict[int, int]]], ploidy: int,
     else:
         launches = C.c_uint32()
         st = L.whamd_poly_select_clusters(*args, int(device), *outs, C.byref(launches))
-    _call(L, st)
+    _native.checked(L, st)
     cptr, ccl, cre, crk = cov_ptr.tolist(), cov_cluster.tolist(), cov_readded.tolist(), cov_rank.tolist()
     cov_map = []
     for x in range(n_pos):
@@ -256,7 +238,7 @@ def compute_haplotypes(path, consensus_lists: List[Dict[int, List[int]]], ploidy
     else:
         launches = C.c_uint32()
         st = L.whamd_poly_haplotypes(*args, int(device), P(out, C.c_int8), C.byref(launches))
-    _call(L, st)
+    _native.checked(L, st)
     if (out == short).any():
         raise IndexError("list index out of range")
     return out.tolist()
@@ -275,7 +257,7 @@ def haplotypes_from_inputs(path, inputs: ThreadingInputs, *, device: int = 0, ho
     else:
         launches = C.c_uint32()
         st = L.whamd_poly_haplotypes(*args, int(device), P(out, C.c_int8), C.byref(launches))
-    _call(L, st)
+    _native.checked(L, st)
     return out
 
 

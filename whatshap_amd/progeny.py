@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native
-from .polyphase import TriangleSparseMatrix, _raise
+from .polyphase import TriangleSparseMatrix
 
 _KIND_SN, _KIND_S2, _KIND_DN = 0, 1, 2
 
@@ -99,8 +99,7 @@ class ProgenyGenotypeLikelihoods:
         out = C.c_double()
         st = L.whamd_debug_progeny_pair_score_host(_native._ptr(self._gl, C.c_float), self._n_positions, self._n_samples, self._ploidy, int(pos1),
                                                    int(pos2), kind, C.byref(out))
-        if st != _native.WHAMD_OK:
-            _raise(L, st)
+        _native.checked(L, st)
         return out.value
 
     # the single-pair getters: host arithmetic (the debug library's twin of the device's inner function)
@@ -163,46 +162,29 @@ class ProgenyProblem:
 
 
 def _read_scores(L, h, n: int, stats: Optional[list]) -> List[VariantScoring]:
-    """The results of a whamd_progeny_scores handle, which is destroyed."""
-    try:
-        out = []
-        for k in range(n):
-            cnt = L.whamd_progeny_score_count(h, k)
-            i = np.empty(cnt, dtype=np.uint32)
-            j = np.empty(cnt, dtype=np.uint32)
-            s32 = np.empty(cnt, dtype=np.float32)
-            s64 = np.empty(cnt, dtype=np.float64)
-            if cnt:
-                st = L.whamd_progeny_score_get(h, k, _native._ptr(i, C.c_uint32), _native._ptr(j, C.c_uint32), _native._ptr(s32, C.c_float),
-                                               _native._ptr(s64, C.c_double))
-                if st != _native.WHAMD_OK:
-                    _raise(L, st)
-            out.append(VariantScoring(i, j, s32, s64))
-            if stats is not None:
-                ps = _native.ProgenyScoreStats()
-                L.whamd_progeny_score_get_stats(h, k, C.byref(ps))
-                stats.append(ps.as_dict())
-        return out
-    finally:
-        L.whamd_progeny_score_destroy(h)
+    """The results of a whamd_progeny_scores handle."""
+    out = []
+    for k in range(n):
+        cnt = L.whamd_progeny_score_count(h, k)
+        i = np.empty(cnt, dtype=np.uint32)
+        j = np.empty(cnt, dtype=np.uint32)
+        s32 = np.empty(cnt, dtype=np.float32)
+        s64 = np.empty(cnt, dtype=np.float64)
+        if cnt:
+            _native.checked(L, L.whamd_progeny_score_get(h, k, _native._ptr(i, C.c_uint32), _native._ptr(j, C.c_uint32), _native._ptr(s32, C.c_float),
+                                                         _native._ptr(s64, C.c_double)))
+        out.append(VariantScoring(i, j, s32, s64))
+        if stats is not None:
+            stats.append(_native.read_stats(L, "whamd_progeny_score_get_stats", _native.ProgenyScoreStats, h, k))
+    return out
 
 
 def score_variants_batch(problems: Sequence[ProgenyProblem], device: int = 0, host: bool = False, stats: Optional[list] = None) -> List[VariantScoring]:
     """get_variant_scoring for every problem in one native call (one upload, one launch, one download for the whole batch).  ``stats``,
     if given, receives one dict per problem (counts, and the timings of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.ProgenyView * max(n, 1))()
-    for k, p in enumerate(problems):
-        views[k] = p.view()
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_progeny_score_host(views, n, C.byref(h))
-    else:
-        st = L.whamd_progeny_score(views, n, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
-    return _read_scores(L, h, n, stats)
+    with _native.batch_handle(host, [p.view() for p in problems], "whamd_progeny_score", "whamd_debug_progeny_score_host", "whamd_progeny_score_destroy",
+                              device=device) as (L, h):
+        return _read_scores(L, h, len(problems), stats)
 
 
 def get_variant_scoring(varinfo, off_gl: ProgenyGenotypeLikelihoods, phasing_param, device: int = 0, host: bool = False,
@@ -228,8 +210,7 @@ def score_entries_host(problem: ProgenyProblem, i, j) -> Tuple[np.ndarray, np.nd
     v = problem.view()
     st = L.whamd_debug_progeny_score_entries_host(C.byref(v), i.size, _native._ptr(i, C.c_uint32), _native._ptr(j, C.c_uint32),
                                                   _native._ptr(score, C.c_double), _native._ptr(stored, C.c_uint8))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
+    _native.checked(L, st)
     return stored.astype(bool), score
 
 
@@ -274,8 +255,7 @@ def most_likely_variant_types(priors, off_gl: ProgenyGenotypeLikelihoods, nodes=
         st = L.whamd_debug_progeny_variant_types_host(*args, *outs)
     else:
         st = L.whamd_progeny_variant_types(*args, int(device), *outs)
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
+    _native.checked(L, st)
     return list(zip(g0.tolist(), g1.tolist())), llh
 
 
@@ -393,8 +373,7 @@ def offspring_gl_batch(problems: Sequence[DepthProblem], device: int = 0, host: 
         st = L.whamd_debug_progeny_gl_host(views, n, out32, out64)
     else:
         st = L.whamd_progeny_gl(views, n, int(device), out32, out64)
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
+    _native.checked(L, st)
     if doubles is not None:
         doubles.extend(f64)
     return [ProgenyGenotypeLikelihoods.from_array(t) for t in tables]
@@ -405,15 +384,11 @@ def score_variants_from_depths(problems: Sequence[DepthProblem], device: int = 0
     one upload (depths and entry lists), two launches -- the likelihood kernel writes the packed planes the pair kernel reads -- and one
     download.  No likelihood table exists on the host.  The same entries and bits as :func:`score_variants_batch` on the downloaded
     tables.  ``stats`` as there."""
-    L = _native.lib()
     for p in problems:
         if p.node_variant is None or p.alt_count is None:
             raise ValueError("scoring needs node_variant, alt_count and co_alt_count")
-    h = C.c_void_p()
-    st = L.whamd_progeny_score_depths(_depth_views(problems), len(problems), int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
-    return _read_scores(L, h, len(problems), stats)
+    with _native.batch_handle(False, [p.view() for p in problems], "whamd_progeny_score_depths", None, "whamd_progeny_score_destroy", device=device) as (L, h):
+        return _read_scores(L, h, len(problems), stats)
 
 
 def _depth_rows(progeny_table, samples: Sequence[str], position_pairs, varinfo):

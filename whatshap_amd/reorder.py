@@ -94,32 +94,13 @@ class ReorderResult:
         self.assignments, self.threads, self.haplotypes, self.confidence = assignments, threads, haplotypes, confidence
 
 
-def _raise(L, status: int):
-    msg = L.whamd_last_error().decode("utf-8", "replace")
-    if status == _native.WHAMD_ERR_INVALID:
-        raise ValueError(msg)
-    raise _native.SolverError(status, msg)
-
-
 def link_likelihoods_batch(problems: Sequence[ReorderProblem], error_rate: float = 0.07, device: int = 0, host: bool = False,
                            stats: Optional[list] = None) -> List[ReorderResult]:
     """The reordering of every problem in one native call (one upload, at most two launches, one download for the whole batch).
     ``stats``, if given, receives one dict per problem (counts, and the launches and timings of the whole call)."""
-    L = _native.debug_lib() if host else _native.lib()
-    n = len(problems)
-    views = (_native.PolyReorderView * max(n, 1))()
-    for k, pr in enumerate(problems):
-        views[k] = pr.view()
-    log_match, log_err = math.log(1 - error_rate), math.log(error_rate)
-    h = C.c_void_p()
-    if host:
-        st = L.whamd_debug_poly_reorder_host(views, n, log_match, log_err, C.byref(h))
-    else:
-        st = L.whamd_poly_reorder(views, n, log_match, log_err, int(device), C.byref(h))
-    if st != _native.WHAMD_OK:
-        _raise(L, st)
     p = _native._ptr
-    try:
+    with _native.batch_handle(host, [pr.view() for pr in problems], "whamd_poly_reorder", "whamd_debug_poly_reorder_host", "whamd_poly_reorder_destroy",
+                              math.log(1 - error_rate), math.log(error_rate), device=device) as (L, h):
         out = []
         for k, pr in enumerate(problems):
             n_bp = L.whamd_poly_reorder_breakpoint_count(h, k)
@@ -137,16 +118,11 @@ def link_likelihoods_batch(problems: Sequence[ReorderProblem], error_rate: float
                        L.whamd_poly_reorder_get_windows(h, k, p(window_ptr, C.c_uint64), p(left_count, C.c_uint32), p(window, C.c_uint32)),
                        L.whamd_poly_reorder_get_phasing(h, k, p(assignments, C.c_uint32), p(threads, C.c_int32), p(haplotypes, C.c_int8),
                                                         p(confidence, C.c_double))):
-                if st != _native.WHAMD_OK:
-                    _raise(L, st)
+                _native.checked(L, st)
             out.append(ReorderResult(llh_ptr, llh, best, window_ptr, left_count, window, assignments, threads, haplotypes, confidence))
             if stats is not None:
-                ps = _native.PolyReorderStats()
-                L.whamd_poly_reorder_get_stats(h, k, C.byref(ps))
-                stats.append(ps.as_dict())
+                stats.append(_native.read_stats(L, "whamd_poly_reorder_get_stats", _native.PolyReorderStats, h, k))
         return out
-    finally:
-        L.whamd_poly_reorder_destroy(h)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's signatures
