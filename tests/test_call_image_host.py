@@ -1,5 +1,6 @@
-"""The image layout of the batch calls (whatshap_amd/csrc/call_image.h), on the host alone: a stand-alone C++ program built with the
-address and undefined-behaviour sanitizers lays pieces out, writes every piece to its full count and checks offsets, total and pointers.
+"""The image layout and the grid arithmetic of the batch calls (whatshap_amd/csrc/call_image.h), on the host alone: a stand-alone C++
+program built with the address and undefined-behaviour sanitizers lays pieces out, writes every piece to its full count and checks
+offsets, total and pointers, and checks grid_for at its edges.
 Nothing is loaded into Python."""
 import os
 import shutil
@@ -98,6 +99,26 @@ int main() {
 	CHECK(im.dev(last)[last.count - 1] == 0xcdcd);
 	std::free(im.stage);
 	std::free(im.base);
+
+	{   // a piece of a result image: what a typed fetch copies (p.bytes() to host(p)) lies inside the image, behind the piece before it
+		ImageLayout r;
+		const auto out = r.add<double>(33);
+		const auto counts = r.add<uint32_t>(33);
+		const auto n_rows = r.add<uint32_t>(1);
+		CHECK(out.bytes() == 264 && counts.offset == 512 && n_rows.offset == 768 && r.total == 1024);
+		CHECK(counts.offset >= out.end() && n_rows.offset >= counts.end() && n_rows.end() <= r.total);
+	}
+	{   // grid_for: the rounded-up quotient in 64 bits, capped
+		CHECK(grid_for(0, 256) == 0);
+		CHECK(grid_for(1, 256) == 1 && grid_for(256, 256) == 1 && grid_for(257, 256) == 2);
+		CHECK(grid_for(257, 256 / 8) == 9);                                // eight lanes per key
+		CHECK(grid_for(5, 4) == 2);                                        // one wave per item, four waves per workgroup
+		CHECK(grid_for(0xffffefffull, 256) == 0x00fffff0u);                // the largest count a scatter layer accepts
+		CHECK(grid_for(0x7fffffffull * 256, 256) == 0x7fffffffu);
+		CHECK(grid_for(1ull << 40, 256, 16384) == 16384);                  // a grid-stride kernel's cap
+		CHECK(grid_for(16384ull * 256, 256, 16384) == 16384 && grid_for(16384ull * 256 - 256, 256, 16384) == 16383);
+		CHECK(grid_for(~0ull - 255, 256) == 0xffffffffu);                  // (n + block - 1 does not wrap below 2^64 - block; the default cap)
+	}
 	std::printf("ok\n");
 	return 0;
 }

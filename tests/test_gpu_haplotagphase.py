@@ -128,6 +128,30 @@ def test_reads_at_a_workgroup_edge(n_entries, want_table):
     assert int(res.n_phasesets.max()) >= (2 if n_entries == 600 else 1)   # (the two long reads carry different phase sets)
 
 
+def three_reads_problem(seed, votes=True):
+    """Three reads of two entries each over four variants; without `votes` every variant is homozygous, so no entry votes."""
+    rng = np.random.default_rng(seed)
+    flags = rng.choice(np.array([0, tp.PHASED, tp.SNV, tp.PHASED | tp.SNV], dtype=np.uint8), size=4) | (0 if votes else tp.HOMOZYGOUS)
+    tags = rng.integers(0, 1 << 40, size=2, dtype=np.int64)
+    return tp.TagphaseProblem(flags.astype(np.uint8), np.array([0, 2, 4, 6], dtype=np.uint64), rng.integers(0, 4, size=6), rng.integers(0, 2, size=6),
+                              rng.integers(1, 61, size=6, dtype=np.int64), tags[[0, 1, 0]], np.array([0, 1, 1], dtype=np.int32), 60.0, False)
+
+
+def test_problems_with_a_table_without_one_and_without_a_vote_in_one_call():
+    """One call whose problems want a table, want none, have no voting entry, and want a table again: the rows of the two tables lie one
+    after the other in the call's rows, behind the rows of the problem that wants none.  Byte for byte the host twin's."""
+    problems = [three_reads_problem(1), three_reads_problem(2), three_reads_problem(3, votes=False), three_reads_problem(4)]
+    wants = [True, False, False, True]
+    dev = tp.tagphase_batch(problems, want_table=wants)
+    host = tp.tagphase_batch(problems, host=True, want_table=wants)
+    for d, h, want in zip(dev, host, wants):
+        for field in tp.TagphaseResult.FIELDS + (tp.TagphaseResult.TABLE_FIELDS if want else ()):
+            assert getattr(d, field).tobytes() == getattr(h, field).tobytes(), field
+        assert {k: d.stats[k] for k in COUNTS} == {k: h.stats[k] for k in COUNTS}
+        assert d.stats["launches"] == LAUNCHES_TABLE
+    assert dev[0].stats["table_rows"] > 0 and dev[3].stats["table_rows"] > 0 and dev[2].stats["n_voting"] == 0 and dev[1].stats["n_voting"] > 0
+
+
 def test_two_calls_on_one_input_give_identical_bytes():
     """The order inside a run is whatever the atomics gave; it must not show."""
     p = hc.array_problem(hc.heavy_tail_runs(3_000, seed=8, mean=20, tail=0.01, tail_max=9_000), seed=9, n_phasesets=5, quality=(1, 2))

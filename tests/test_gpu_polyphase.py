@@ -92,5 +92,6 @@ def test_edge_cases_return_without_launch():
     st = {}
     assert len(polyphase.scoreReadset(disjoint, 3, 3, 0.07, stats=st)) == 0
     assert st["n_candidates"] == 2 and st["n_overlapping"] == 0
+    assert st["launches"] == 2 and st["download_ms"] == 0.0   # pair kernel and scan; nothing kept, so no compaction, sort or download
     stats = []
     assert polyphase.score_readsets_batch([], 1, 2, 0.07, stats=stats) == []

@@ -200,6 +200,18 @@ def test_fused_is_deterministic():
     assert all(np.array_equal(bits32(x.array()), bits32(y.array())) for x, y in zip(a, b))
 
 
+def test_a_fused_call_without_samples_launches_the_pair_kernel_alone():
+    """No sample, so no cell and no plane: the likelihood kernel is not launched, and every entry's score is the sum over no samples."""
+    p = synthetic(12, 0, seed=51, types=(gc.SN,))
+    assert p.n_samples == 0 and p.n_nodes == 12
+    fused, stats, unfused = fused_and_unfused([p])
+    assert_same_scores(fused, unfused)
+    host = progeny.score_variants_batch([progeny.ProgenyProblem(progeny.offspring_gl_batch([p], host=True)[0], p.node_variant, p.alt_count, p.co_alt_count,
+                                                                p.scoring_window)], host=True)
+    assert_same_scores(fused, host)
+    assert len(fused[0]) == sum(max(12 - s, 0) for s in pc.strides_of(4)) == 20 and stats[0]["launches"] == 1 and stats[0]["n_inf"] == 0
+
+
 def test_a_batch_of_minus_infinity_entries_touches_no_device():
     p = synthetic(6, 9, seed=41, types=(gc.DN,), window=7)   # duplex variants only: the stored entries are the pairs within one variant
     stats: list = []

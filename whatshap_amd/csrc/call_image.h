@@ -1,7 +1,7 @@
-// call_image.h -- the image a batch call uploads in one copy, and the times it reports.  Host only (no HIP): the layout is tested on its own
-// (tests/test_call_image_host.py).  A call adds its pieces to an ImageLayout, Session::stage() (device_runtime.h) takes the pinned and the
-// device block of the layout's total, and the call fills image.host(piece) and hands image.dev(piece) to its kernels: the type and the
-// offset of a piece are written once.
+// call_image.h -- the image a batch call uploads in one copy, the grid of a launch and the times the call reports.  Host only (no HIP):
+// the arithmetic is tested on its own (tests/test_call_image_host.py).  A call adds its pieces to an ImageLayout, Session::stage()
+// (device_runtime.h) takes the pinned and the device block of the layout's total, and the call fills image.host(piece) and hands
+// image.dev(piece) to its kernels: the type and the offset of a piece are written once.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -41,6 +41,9 @@ struct Image {
 	template <class T>
 	T* dev_out(const Piece<T>& p) const { return reinterpret_cast<T*>(base + p.offset); }   // a piece the kernels write
 };
+
+// Workgroups of a launch over n items, `block` items per workgroup; a grid-stride kernel caps them.
+inline uint32_t grid_for(uint64_t n, uint32_t block, uint32_t cap = UINT32_MAX) { return (uint32_t)((n + block - 1) / block < cap ? (n + block - 1) / block : cap); }
 
 // What a call reports: ms between HIP events of its stream (Session::finish()), and the kernels it launched.
 struct CallTimes {

@@ -423,8 +423,7 @@ void device_release_caches() {
 
 // ---------------------------------------------------------------------------------------------- one call on one device
 whamd_status_t Session::open(int dev_index, int n_events, std::string& msg) {
-	const whamd_status_t st = open_device(dev_index, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(open_device(dev_index, msg));
 	device = dev_index;
 	HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
 	ev.reserve(n_events);
@@ -443,10 +442,17 @@ double ms_between(hipEvent_t a, hipEvent_t b) {
 	return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0;
 }
 }  // namespace
-whamd_status_t Session::stage(const ImageLayout& layout, Image& image, std::string& msg) {
+whamd_status_t Session::work(const ImageLayout& layout, Image& image, std::string& msg) {
 	image.total = layout.total;
-	const whamd_status_t st = pinned_block(layout.total, (void**)&image.stage, msg);
-	return st != WHAMD_OK ? st : device_block(layout.total, (void**)&image.base, msg);
+	return device_block(layout.total, (void**)&image.base, msg);
+}
+whamd_status_t Session::results(const ImageLayout& layout, Image& image, std::string& msg) {
+	image.total = layout.total;
+	return pinned_block(layout.total, (void**)&image.stage, msg);
+}
+whamd_status_t Session::zero(const Image& image, size_t bytes, std::string& msg) {
+	HIP_TRY(hipMemsetAsync(image.base, 0, bytes, stream));
+	return WHAMD_OK;
 }
 whamd_status_t Session::upload(const Image& image, size_t bytes, std::string& msg) {
 	if (timed) HIP_TRY(hipEventRecord(ev[UPLOAD_BEGIN], stream));

@@ -23,6 +23,13 @@
 		}                                                                                             \
 	} while (0)
 
+// A step that returns a whamd_status_t: a failure is returned from the enclosing function at once, so no step runs after it.
+#define WHAMD_TRY(expr)                                                                               \
+	do {                                                                                              \
+		const whamd_status_t st_ = (expr);                                                            \
+		if (st_ != WHAMD_OK) return st_;                                                              \
+	} while (0)
+
 namespace whamd {
 
 // Makes `device` current; the two messages of a call without a usable device are written here and nowhere else.
@@ -91,13 +98,20 @@ struct StageSession {
 
 // ---------------------------------------------------------------------------------------------- one call on one device
 // What a call holds on the device and in pinned memory; given back on every way out.
-// The steps of a batch call (one image up, kernels, results down), in this order; each sets `msg` and returns the status:
-//   stage(layout, image)  the image's pinned and device block (call_image.h); the call fills image.host(piece)
-//   upload(image)         the image, or its first `bytes`, to the device
-//   ... the call's launches on `stream` ...
+// The steps of a batch call (one image up, kernels, results down), in this order; each sets `msg` and returns the status, and the call
+// wraps each in WHAMD_TRY:
+//   stage(layout, image)      the image's pinned and device block (call_image.h); the call fills image.host(piece).  Also an image the
+//                             kernels write and that comes down whole (no upload)
+//   work(layout, image)       an image the kernels make and use: its device block only
+//   results(layout, image)    an image the fetched pieces come down into: its pinned block only
+//   upload(image)             the image, or its first `bytes`, to the device
+//   zero(image, bytes)        the front of a work image
+//   ... launch(s, times, msg, kernel, grid, block, lds, args...), counted in times.launches ...
+//   fetch_now(res, piece, src)  at most once, in the middle: a fetch the host waits for, because the value sizes what follows
 //   kernels_done()
-//   fetch(dst, src, n)    device to pinned host; as many as the call needs (before kernels_done(): part of the kernel time)
-//   finish(times)         waits for the stream; upload / kernel / download ms of `times`
+//   fetch(res, piece, src)    device to pinned host, one copy per piece; as many as the call needs (before kernels_done(): part of the
+//                             kernel time).  fetch(dst, src, n) for a part of a piece
+//   finish(times)             waits for the stream; upload / kernel / download ms of `times`
 // A session opened with four events records one around each phase; one opened with none records nothing and finish() leaves `times` alone.
 struct Session {
 	int device = -1;
@@ -117,11 +131,31 @@ struct Session {
 	void close();
 	whamd_status_t device_block(size_t bytes, void** out, std::string& msg);
 	whamd_status_t pinned_block(size_t bytes, void** out, std::string& msg);
-	whamd_status_t stage(const ImageLayout& layout, Image& image, std::string& msg);
+	whamd_status_t stage(const ImageLayout& layout, Image& image, std::string& msg) {
+		WHAMD_TRY(results(layout, image, msg));
+		return work(layout, image, msg);
+	}
+	// One device block of the layout's total: sets base and total, leaves stage null.  A layer that scatters lays its work image out as
+	// rs_add_zeroed() (run_scatter.h), its own zeroed pieces, rs_add_rest(), the rest: the zeroed pieces come first, and the layout's total
+	// after the last of them is the byte count for zero().
+	whamd_status_t work(const ImageLayout& layout, Image& image, std::string& msg);
+	whamd_status_t zero(const Image& image, size_t bytes, std::string& msg);   // the image's first `bytes`, on the stream
+	// One pinned block of the layout's total: sets stage and total.
+	whamd_status_t results(const ImageLayout& layout, Image& image, std::string& msg);
 	whamd_status_t upload(const Image& image, size_t bytes, std::string& msg);
 	whamd_status_t upload(const Image& image, std::string& msg) { return upload(image, image.total, msg); }
 	whamd_status_t kernels_done(std::string& msg);
 	whamd_status_t fetch(void* dst, const void* src, size_t bytes, std::string& msg);
+	template <class T>
+	whamd_status_t fetch(const Image& res, const Piece<T>& p, const T* src, std::string& msg) { return fetch(res.host(p), src, p.bytes(), msg); }
+	// fetch() and then a wait for the stream: the one wait in the middle of a call.  The fetched value sizes what follows (kept pairs,
+	// table rows), so the host needs it before it can take the blocks and launch the rest.
+	template <class T>
+	whamd_status_t fetch_now(const Image& res, const Piece<T>& p, const T* src, std::string& msg) {
+		WHAMD_TRY(fetch(res, p, src, msg));
+		HIP_TRY(hipStreamSynchronize(stream));
+		return WHAMD_OK;
+	}
 	// downloaded = false: nothing was fetched after kernels_done() -- no event is recorded for it and download_ms is exactly 0.
 	whamd_status_t finish(CallTimes& times, std::string& msg, bool downloaded = true);
 	// Not from the pool: hipMalloc -- after devpool_release() once more if the first fails -- and hipFree when the session ends.
@@ -129,5 +163,16 @@ struct Session {
 	hipError_t add_stream(hipStream_t* out);
 	hipError_t sync_event(hipEvent_t* out);   // hipEventDisableTiming: orders streams, records no time
 };
+
+#if defined(__HIPCC__)
+// One launch on the session's stream with `lds` bytes of dynamic LDS, checked and counted in times.launches.
+template <class... P>
+whamd_status_t launch(Session& s, CallTimes& times, std::string& msg, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, P... args) {
+	hipLaunchKernelGGL(kernel, grid, block, lds, s.stream, args...);
+	HIP_TRY(hipGetLastError());
+	++times.launches;
+	return WHAMD_OK;
+}
+#endif
 
 }  // namespace whamd

@@ -236,10 +236,10 @@ __global__ void __launch_bounds__(HT_BLOCK) haplotag_block_kernel(HtArgs a) {
 }
 
 template <int P>
-void launch_class(uint32_t cls, const HtArgs& a, hipStream_t stream) {
-	if (cls == 0) hipLaunchKernelGGL((haplotag_team_kernel<P, (int)HT_SEGMENT>), dim3((a.n_groups + HT_BLOCK / HT_SEGMENT - 1) / (HT_BLOCK / HT_SEGMENT)), dim3(HT_BLOCK), 0, stream, a);
-	else if (cls == 1) hipLaunchKernelGGL((haplotag_team_kernel<P, 64>), dim3((a.n_groups + NW - 1) / NW), dim3(HT_BLOCK), 0, stream, a);
-	else hipLaunchKernelGGL((haplotag_block_kernel<P>), dim3(a.n_groups), dim3(HT_BLOCK), 0, stream, a);
+whamd_status_t launch_class(Session& s, CallTimes& times, std::string& msg, uint32_t cls, const HtArgs& a) {
+	if (cls == 0) return launch(s, times, msg, haplotag_team_kernel<P, (int)HT_SEGMENT>, dim3(grid_for(a.n_groups, HT_BLOCK / HT_SEGMENT)), dim3(HT_BLOCK), 0, a);
+	if (cls == 1) return launch(s, times, msg, haplotag_team_kernel<P, 64>, dim3(grid_for(a.n_groups, NW)), dim3(HT_BLOCK), 0, a);
+	return launch(s, times, msg, haplotag_block_kernel<P>, dim3(a.n_groups), dim3(HT_BLOCK), 0, a);
 }
 
 }  // namespace
@@ -296,14 +296,13 @@ whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int
 	const auto p_ent = in.add<HtEntry>(total_ent);
 	const size_t total_out = total_rec * sizeof(HtOut);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im;
 	HtOut* dev_out = nullptr;
 	HtOut* res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(total_out, (void**)&dev_out, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(total_out, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.device_block(total_out, (void**)&dev_out, msg));
+	WHAMD_TRY(s.pinned_block(total_out, (void**)&res, msg));
 	for (size_t x = 0; x < ps.size(); x++)
 		if (var_base[x + 1] > var_base[x]) std::memcpy(im.host(p_var) + var_base[x], ps[x].variants.data(), ps[x].variants.size() * sizeof(HtVariant));
 	HtGroup* recs = im.host(p_rec);
@@ -321,21 +320,19 @@ whamd_status_t haplotag_score_device(const std::vector<HaplotagProblem>& ps, int
 			}
 		}
 	});
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.upload(im, msg));
 	for (uint32_t cls = 0; cls < 3; cls++) {
 		if (!n_rec[cls]) continue;
 		HtArgs a{im.dev(p_ent), im.dev(p_var), im.dev(p_rec) + rec_base[cls], dev_out + rec_base[cls], (uint32_t)n_rec[cls]};
 		const uint32_t k = max_ploidy[cls];
-		if (k <= 2) launch_class<2>(cls, a, s.stream);
-		else if (k <= 4) launch_class<4>(cls, a, s.stream);
-		else if (k <= 8) launch_class<8>(cls, a, s.stream);
-		else launch_class<16>(cls, a, s.stream);
-		HIP_TRY(hipGetLastError());
-		++times.launches;
+		if (k <= 2) WHAMD_TRY(launch_class<2>(s, times, msg, cls, a));
+		else if (k <= 4) WHAMD_TRY(launch_class<4>(s, times, msg, cls, a));
+		else if (k <= 8) WHAMD_TRY(launch_class<8>(s, times, msg, cls, a));
+		else WHAMD_TRY(launch_class<16>(s, times, msg, cls, a));
 	}
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, dev_out, total_out, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, dev_out, total_out, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	parallel_ranges(total_rec, host_threads(total_rec, 1 << 16), [&](uint64_t b, uint64_t e, uint32_t) {
 		for (uint64_t x = b; x < e; x++) out[slots[x].problem].out[slots[x].group] = res[x];
 	});

@@ -169,36 +169,30 @@ whamd_status_t compare_device(const std::vector<CompareJob>& jobs, int device, s
 	ImageLayout in;
 	const auto p_job = in.add<PcJob>(recs.size());
 	const auto p_all = in.add<uint8_t>(n_alleles);
-	ImageLayout res_layout;   // what comes back, in one block: the results, then the paths
+	ImageLayout res_layout;   // what the kernel writes and what comes back, in one copy: the results, then the paths
 	const auto p_out = res_layout.add<PcOut>(recs.size());
 	const auto p_path = res_layout.add<uint16_t>(n_path);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
-	Image im;
-	char* dev_res = nullptr;
-	char* res = nullptr;
+	WHAMD_TRY(s.open(device, 4, msg));
+	Image im, res;
 	uint16_t* dev_pred = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(res_layout.total, (void**)&dev_res, msg)) != WHAMD_OK) return st;
-	if (n_pred && (st = s.device_block(n_pred * sizeof(uint16_t), (void**)&dev_pred, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(res_layout.total, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.stage(res_layout, res, msg));
+	if (n_pred) WHAMD_TRY(s.device_block(n_pred * sizeof(uint16_t), (void**)&dev_pred, msg));
 	std::memcpy(im.host(p_job), recs.data(), recs.size() * sizeof(PcJob));
 	for (size_t y = 0; y < sent.size(); y++) {
 		const CompareJob& j = jobs[sent[y]];
 		std::memcpy(im.host(p_all) + recs[y].p0_begin, j.p0, j.n_pos * j.k);
 		std::memcpy(im.host(p_all) + recs[y].p1_begin, j.p1, j.n_pos * j.k);
 	}
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	PcArgs a{im.dev(p_job), im.dev(p_all), reinterpret_cast<PcOut*>(dev_res + p_out.offset), dev_pred, reinterpret_cast<uint16_t*>(dev_res + p_path.offset)};
-	hipLaunchKernelGGL(compare_kernel, dim3((uint32_t)recs.size()), dim3(PC_BLOCK), 0, s.stream, a);
-	HIP_TRY(hipGetLastError());
-	++times.launches;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, dev_res, res_layout.total, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
-	const PcOut* got = reinterpret_cast<const PcOut*>(res + p_out.offset);
-	const uint16_t* paths = reinterpret_cast<const uint16_t*>(res + p_path.offset);
+	WHAMD_TRY(s.upload(im, msg));
+	PcArgs a{im.dev(p_job), im.dev(p_all), res.dev_out(p_out), dev_pred, res.dev_out(p_path)};
+	WHAMD_TRY(launch(s, times, msg, compare_kernel, dim3((uint32_t)recs.size()), dim3(PC_BLOCK), 0, a));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res.stage, res.base, res.total, msg));
+	WHAMD_TRY(s.finish(times, msg));
+	const PcOut* got = res.host(p_out);
+	const uint16_t* paths = res.host(p_path);
 	for (size_t y = 0; y < sent.size(); y++) {
 		CompareResult& o = out[sent[y]];
 		o.out = got[y];

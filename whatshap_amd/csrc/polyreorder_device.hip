@@ -109,18 +109,15 @@ whamd_status_t reorder_score_device(const std::vector<ReorderProblem>& ps, doubl
 	const auto p_hap = in.add<int8_t>(total.hap);
 	const auto p_rpos = in.add<uint32_t>(total.row);
 	const auto p_rall = in.add<uint8_t>(total.row);
-	const size_t llh_bytes = total.llh * sizeof(double);
+	ImageLayout out_layout;   // what the kernels write and what comes back: the sums
+	const auto p_llh = out_layout.add<double>(total.llh);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
-	Image im;
+	WHAMD_TRY(s.open(device, 4, msg));
+	Image im, res;
 	double* dev_table = nullptr;
-	double* dev_llh = nullptr;
-	double* res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if (total.tab && (st = s.device_block(total.tab * sizeof(double), (void**)&dev_table, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(llh_bytes, (void**)&dev_llh, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(llh_bytes, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	if (total.tab) WHAMD_TRY(s.device_block(total.tab * sizeof(double), (void**)&dev_table, msg));
+	WHAMD_TRY(s.stage(out_layout, res, msg));
 	uint32_t tile_at = 0;
 	for (size_t x = 0; x < ps.size(); x++) {
 		const ReorderProblem& p = ps[x];
@@ -158,22 +155,16 @@ whamd_status_t reorder_score_device(const std::vector<ReorderProblem>& ps, doubl
 			}
 		}
 	}
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	PrArgs a{im.dev(p_bp), im.dev(p_item), im.dev(p_tile), im.dev(p_win), im.dev(p_hap), im.dev(p_rpos), im.dev(p_rall), dev_table, dev_llh, total.item,
+	WHAMD_TRY(s.upload(im, msg));
+	PrArgs a{im.dev(p_bp), im.dev(p_item), im.dev(p_tile), im.dev(p_win), im.dev(p_hap), im.dev(p_rpos), im.dev(p_rall), dev_table, res.dev_out(p_llh), total.item,
 	         log_match, log_err};
-	if (total.item) {
-		hipLaunchKernelGGL(reorder_table_kernel, dim3((uint32_t)((total.item + PR_BLOCK - 1) / PR_BLOCK)), dim3(PR_BLOCK), 0, s.stream, a);
-		HIP_TRY(hipGetLastError());
-		++times.launches;
-	}
-	hipLaunchKernelGGL(reorder_permute_kernel, dim3((uint32_t)n_tiles), dim3(PR_BLOCK), 0, s.stream, a);
-	HIP_TRY(hipGetLastError());
-	++times.launches;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, dev_llh, llh_bytes, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	if (total.item) WHAMD_TRY(launch(s, times, msg, reorder_table_kernel, dim3(grid_for(total.item, PR_BLOCK)), dim3(PR_BLOCK), 0, a));
+	WHAMD_TRY(launch(s, times, msg, reorder_permute_kernel, dim3((uint32_t)n_tiles), dim3(PR_BLOCK), 0, a));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, p_llh, res.dev(p_llh), msg));
+	WHAMD_TRY(s.finish(times, msg));
 	for (size_t x = 0; x < ps.size(); x++)
-		if (!out[x].llh.empty()) std::memcpy(out[x].llh.data(), res + base[x].llh, out[x].llh.size() * sizeof(double));
+		if (!out[x].llh.empty()) std::memcpy(out[x].llh.data(), res.host(p_llh) + base[x].llh, out[x].llh.size() * sizeof(double));
 	return WHAMD_OK;
 }
 

@@ -9,7 +9,7 @@
 //   3. poly_compact_kernel: kept pairs -> (key, score), key = max(id) * N + min(id) over global read ids: the triangular order per matrix.
 //   4. rocprim radix sort of (key, score) on the bits the keys use.
 // Only the sorted (key, score) pairs come back.  The upload is one image (call_image.h); the steps are Session's (device_runtime.h), with one
-// wait of this call's own after step 2: the number of kept pairs sizes steps 3 and 4.
+// its one wait (fetch_now) after step 2: the number of kept pairs sizes steps 3 and 4.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -163,11 +163,13 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	const auto p_na = in.add<uint32_t>(n_mats);
 	const auto p_terms = in.add<float>(n_terms);
 	const auto p_counts = in.add<unsigned long long>(3 * (size_t)n_mats);   // zeros; the pair kernel adds to them
+	ImageLayout tail_layout;   // what comes down in the middle of the call
+	const auto t_last = tail_layout.add<uint32_t>(2);   // keep and slot of the last pair
+	const auto t_counts = tail_layout.add<unsigned long long>(p_counts.count);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
 	std::vector<uint64_t> read_base(n_mats + 1, 0), entry_base(n_mats + 1, 0), term_base(n_mats + 1, 0), pair_base(n_mats + 1, 0);
 	for (uint32_t u = 0; u < n_mats; u++) {
 		const PolyMatrix& m = ms[up[u]];
@@ -207,15 +209,15 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	// pair buffers
 	float* score = nullptr;
 	uint32_t *keep = nullptr, *slot = nullptr;
-	if ((st = s.device_block(n_pairs * 4, (void**)&score, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(n_pairs * 4, (void**)&keep, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(n_pairs * 4, (void**)&slot, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.device_block(n_pairs * 4, (void**)&score, msg));
+	WHAMD_TRY(s.device_block(n_pairs * 4, (void**)&keep, msg));
+	WHAMD_TRY(s.device_block(n_pairs * 4, (void**)&slot, msg));
 	size_t scan_tmp = 0;
 	HIP_TRY(rocprim::exclusive_scan(nullptr, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
 	void* scan_buf = nullptr;
-	if ((st = s.device_block(scan_tmp, &scan_buf, msg)) != WHAMD_OK) return st;
-	uint32_t* tail = nullptr;   // pinned: keep and slot of the last pair, then the counts
-	if ((st = s.pinned_block(8 + p_counts.bytes(), (void**)&tail, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.device_block(scan_tmp, &scan_buf, msg));
+	Image tail;
+	WHAMD_TRY(s.results(tail_layout, tail, msg));
 
 	PairArgs pa{};
 	pa.n_pairs = n_pairs;
@@ -234,21 +236,18 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	pa.score = score;
 	pa.keep = keep;
 	pa.counts = im.dev_out(p_counts);
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pairs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
+	const dim3 blocks(grid_for(n_pairs, BLOCK, MAX_BLOCKS));
 
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	hipLaunchKernelGGL(poly_pair_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, pa);
-	HIP_TRY(hipGetLastError());
+	WHAMD_TRY(s.upload(im, msg));
+	WHAMD_TRY(launch(s, times, msg, poly_pair_kernel, blocks, dim3(BLOCK), 0, pa));
 	HIP_TRY(rocprim::exclusive_scan(scan_buf, scan_tmp, keep, slot, 0u, (size_t)n_pairs, rocprim::plus<uint32_t>(), s.stream));
-	// the number of kept pairs sizes what follows: three small results come down in the middle of the kernel phase, and the host waits for them
-	// (Session's steps have no such wait: it is this call's alone)
-	if ((st = s.fetch(tail, keep + (n_pairs - 1), 4, msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(tail + 1, slot + (n_pairs - 1), 4, msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(tail + 2, im.dev(p_counts), p_counts.bytes(), msg)) != WHAMD_OK) return st;
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	times.launches = 2;
-	const uint64_t n_kept = (uint64_t)tail[0] + tail[1];
-	const unsigned long long* counts = (const unsigned long long*)(tail + 2);
+	++times.launches;
+	// the number of kept pairs sizes what follows: three small results come down in the middle of the kernel phase
+	WHAMD_TRY(s.fetch(tail.host(t_last), keep + (n_pairs - 1), 4, msg));
+	WHAMD_TRY(s.fetch(tail.host(t_last) + 1, slot + (n_pairs - 1), 4, msg));
+	WHAMD_TRY(s.fetch_now(tail, t_counts, im.dev(p_counts), msg));
+	const uint64_t n_kept = (uint64_t)tail.host(t_last)[0] + tail.host(t_last)[1];
+	const unsigned long long* counts = tail.host(t_counts);
 	for (uint32_t u = 0; u < n_mats; u++) {
 		out[up[u]].n_overlapping = counts[3 * u];
 		out[up[u]].n_nan = counts[3 * u + 1];
@@ -257,31 +256,33 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 	if (n_kept) {
 		uint64_t *key = nullptr, *key2 = nullptr;
 		float *val = nullptr, *val2 = nullptr;
-		if ((st = s.device_block(n_kept * 8, (void**)&key, msg)) != WHAMD_OK) return st;
-		if ((st = s.device_block(n_kept * 8, (void**)&key2, msg)) != WHAMD_OK) return st;
-		if ((st = s.device_block(n_kept * 4, (void**)&val, msg)) != WHAMD_OK) return st;
-		if ((st = s.device_block(n_kept * 4, (void**)&val2, msg)) != WHAMD_OK) return st;
+		WHAMD_TRY(s.device_block(n_kept * 8, (void**)&key, msg));
+		WHAMD_TRY(s.device_block(n_kept * 8, (void**)&key2, msg));
+		WHAMD_TRY(s.device_block(n_kept * 4, (void**)&val, msg));
+		WHAMD_TRY(s.device_block(n_kept * 4, (void**)&val2, msg));
 		unsigned end_bit = 1;
 		const uint64_t max_key = (uint64_t)N * N;
 		while (end_bit < 64 && (max_key >> end_bit)) ++end_bit;
 		size_t sort_tmp = 0;
 		HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
 		void* sort_buf = nullptr;
-		if ((st = s.device_block(sort_tmp, &sort_buf, msg)) != WHAMD_OK) return st;
-		char* res = nullptr;
-		if ((st = s.pinned_block(n_kept * 12, (void**)&res, msg)) != WHAMD_OK) return st;
+		WHAMD_TRY(s.device_block(sort_tmp, &sort_buf, msg));
+		ImageLayout sorted;   // the second result image: sized by the wait
+		const auto r_key = sorted.add<uint64_t>(n_kept);
+		const auto r_val = sorted.add<float>(n_kept);
+		Image res;
+		WHAMD_TRY(s.results(sorted, res, msg));
 		CompactArgs ca{n_pairs, N, pa.pair_prefix, pa.order, score, keep, slot, key, val};
-		hipLaunchKernelGGL(poly_compact_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, ca);
-		HIP_TRY(hipGetLastError());
+		WHAMD_TRY(launch(s, times, msg, poly_compact_kernel, blocks, dim3(BLOCK), 0, ca));
 		HIP_TRY(rocprim::radix_sort_pairs(sort_buf, sort_tmp, key, key2, val, val2, (size_t)n_kept, 0u, end_bit, s.stream));
-		if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-		if ((st = s.fetch(res, key2, n_kept * 8, msg)) != WHAMD_OK) return st;
-		if ((st = s.fetch(res + n_kept * 8, val2, n_kept * 4, msg)) != WHAMD_OK) return st;
-		if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
-		times.launches = 4;
+		++times.launches;
+		WHAMD_TRY(s.kernels_done(msg));
+		WHAMD_TRY(s.fetch(res, r_key, key2, msg));
+		WHAMD_TRY(s.fetch(res, r_val, val2, msg));
+		WHAMD_TRY(s.finish(times, msg));
 		// per matrix: its keys form one contiguous range (global ids of matrix u are read_base[u] ..)
-		const uint64_t* keys = (const uint64_t*)res;
-		const float* vals = (const float*)(res + n_kept * 8);
+		const uint64_t* keys = res.host(r_key);
+		const float* vals = res.host(r_val);
 		std::vector<uint64_t> cut(n_mats + 1);
 		for (uint32_t u = 0; u <= n_mats; u++) cut[u] = (uint64_t)(std::lower_bound(keys, keys + n_kept, read_base[u] * N) - keys);
 		parallel_ranges(n_mats, std::min<uint32_t>(host_threads(n_kept, 1 << 16), n_mats), [&](uint64_t b, uint64_t e, uint32_t) {
@@ -299,8 +300,8 @@ whamd_status_t poly_score_device(const std::vector<PolyMatrix>& ms, uint32_t min
 			}
 		});
 	} else {   // nothing kept, nothing more to fetch
-		if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-		if ((st = s.finish(times, msg, false)) != WHAMD_OK) return st;
+		WHAMD_TRY(s.kernels_done(msg));
+		WHAMD_TRY(s.finish(times, msg, false));
 	}
 	return WHAMD_OK;
 }

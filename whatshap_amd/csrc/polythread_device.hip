@@ -220,16 +220,15 @@ __global__ void __launch_bounds__(RS_BLOCK) polythread_haplotypes_kernel(PtHaplo
 }
 
 template <int NA>
-whamd_status_t launch_clusters_and_rows(hipStream_t stream, CallTimes& times, std::string& msg, const PtArgs& a, bool rows, dim3 per_segment) {
-	whamd_status_t st;
+whamd_status_t launch_clusters_and_rows(Session& s, CallTimes& times, std::string& msg, const PtArgs& a, bool rows, dim3 per_segment) {
 	if (rows) {
-		if ((st = rs_launch(stream, times, msg, polythread_a_kernel<NA, true>, per_segment, a)) != WHAMD_OK) return st;
-		if ((st = rs_launch(stream, times, msg, polythread_b_kernel<NA, true>, dim3(RS_LIST_GRID), a)) != WHAMD_OK) return st;
-		return rs_launch(stream, times, msg, polythread_c_kernel<NA, true>, dim3(RS_LIST_GRID), a);
+		WHAMD_TRY(rs_launch(s, times, msg, polythread_a_kernel<NA, true>, per_segment, a));
+		WHAMD_TRY(rs_launch(s, times, msg, polythread_b_kernel<NA, true>, dim3(RS_LIST_GRID), a));
+		return rs_launch(s, times, msg, polythread_c_kernel<NA, true>, dim3(RS_LIST_GRID), a);
 	}
-	if ((st = rs_launch(stream, times, msg, polythread_a_kernel<NA, false>, per_segment, a)) != WHAMD_OK) return st;
-	if ((st = rs_launch(stream, times, msg, polythread_b_kernel<NA, false>, dim3(RS_LIST_GRID), a)) != WHAMD_OK) return st;
-	return rs_launch(stream, times, msg, polythread_c_kernel<NA, false>, dim3(RS_LIST_GRID), a);
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_a_kernel<NA, false>, per_segment, a));
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_b_kernel<NA, false>, dim3(RS_LIST_GRID), a));
+	return rs_launch(s, times, msg, polythread_c_kernel<NA, false>, dim3(RS_LIST_GRID), a);
 }
 
 }  // namespace
@@ -274,21 +273,18 @@ whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int devic
 	const auto w_placed = work.add<PtPlaced>(n_placed);
 	const auto w_n_sel = work.add<uint32_t>(n_keys);
 	const auto w_sel = work.add<uint32_t>(n_keys * sel_stride);
+	ImageLayout results;   // what comes back, beside the rows
+	const auto r_counts = results.add<uint32_t>(n_keys);
+	const auto r_npc = results.add<uint32_t>(n_keys);
+	const auto r_n_sel = results.add<uint32_t>(n_keys);
+	const auto r_sel = results.add<uint32_t>(n_keys * sel_stride);
+	const auto r_n_rows = results.add<uint32_t>(1);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
-	Image im, wk;
-	char* dev_work = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
-	wk.base = dev_work;
-	wk.total = work.total;
-	uint32_t *res_counts = nullptr, *res_npc = nullptr, *res_n_sel = nullptr, *res_sel = nullptr, *res_rows_n = nullptr;
-	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_counts, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_npc, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_keys * sizeof(uint32_t), (void**)&res_n_sel, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_keys * sel_stride * sizeof(uint32_t), (void**)&res_sel, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(sizeof(uint32_t), (void**)&res_rows_n, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
+	Image im, wk, res, rw;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.work(work, wk, msg));
+	WHAMD_TRY(s.results(results, res, msg));
 	// the image
 	for (size_t x = 0; x < ps.size(); x++) {
 		const ThreadProblem& p = ps[x];
@@ -306,8 +302,8 @@ whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int devic
 		}
 	}
 	im.host(p_rptr)[n_reads] = (uint32_t)n_entries;
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	HIP_TRY(hipMemsetAsync(dev_work, 0, zeroed, s.stream));
+	WHAMD_TRY(s.upload(im, msg));
+	WHAMD_TRY(s.zero(wk, zeroed, msg));
 	PtArgs a{};
 	a.reads = im.dev(p_reads);
 	a.read_ptr = im.dev(p_rptr);
@@ -327,17 +323,14 @@ whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int devic
 	a.n_pc = 0;
 	a.max_ploidy = max_ploidy;
 	const RunIndex& run = a.run;
-	const dim3 per_entry((uint32_t)((n_entries + RS_BLOCK - 1) / RS_BLOCK)), per_segment((uint32_t)((n_keys + RS_BLOCK / PT_SEGMENT - 1) / (RS_BLOCK / PT_SEGMENT)));
-	const dim3 per_key((uint32_t)((n_keys + RS_BLOCK - 1) / RS_BLOCK));
-	if ((st = rs_launch(s.stream, times, msg, polythread_count_kernel, per_entry, a)) != WHAMD_OK) return st;
-	if ((st = rs_scan(s.stream, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr)) != WHAMD_OK) return st;
-	if ((st = rs_launch(s.stream, times, msg, polythread_place_kernel, per_entry, a)) != WHAMD_OK) return st;
-	if ((st = launch_clusters_and_rows<4>(s.stream, times, msg, a, false, per_segment)) != WHAMD_OK) return st;
-	if ((st = rs_scan(s.stream, times, msg, a.npc, a.npc_local, a.npc_tile_sums, run.n_keys, nullptr, a.n_rows)) != WHAMD_OK) return st;
-	// the one wait in the middle of the call: the number of rows
-	if ((st = s.fetch(res_rows_n, a.n_rows, sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	HIP_TRY(hipStreamSynchronize(s.stream));
-	const uint64_t n_pc = *res_rows_n;
+	const dim3 per_entry(grid_for(n_entries, RS_BLOCK)), per_segment(grid_for(n_keys, RS_BLOCK / PT_SEGMENT)), per_key(grid_for(n_keys, RS_BLOCK));
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_count_kernel, per_entry, a));
+	WHAMD_TRY(rs_scan(s, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr));
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_place_kernel, per_entry, a));
+	WHAMD_TRY(launch_clusters_and_rows<4>(s, times, msg, a, false, per_segment));
+	WHAMD_TRY(rs_scan(s, times, msg, a.npc, a.npc_local, a.npc_tile_sums, run.n_keys, nullptr, a.n_rows));
+	WHAMD_TRY(s.fetch_now(res, r_n_rows, a.n_rows, msg));   // the number of rows
+	const uint64_t n_pc = *res.host(r_n_rows);
 	if (!n_pc || n_pc > n_placed) {
 		msg = "internal error: the rows and the counted entries disagree";
 		return WHAMD_ERR_DEVICE;
@@ -349,22 +342,15 @@ whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int devic
 	const auto r_depth = rows.add<uint32_t>(n_pc * na);
 	const auto r_first = rows.add<uint32_t>(n_pc * na);
 	const auto r_cons = rows.add<int8_t>(n_pc * max_ploidy);
-	char *dev_rows = nullptr, *res_rows = nullptr;
-	if ((st = s.device_block(rows.total, (void**)&dev_rows, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(rows.total, (void**)&res_rows, msg)) != WHAMD_OK) return st;
-	Image rw;
-	rw.base = dev_rows;
-	rw.stage = res_rows;
-	rw.total = rows.total;
+	WHAMD_TRY(s.stage(rows, rw, msg));   // the second result image: sized by the wait, written by the kernels, fetched whole
 	a.pc_cluster = rw.dev_out(r_cluster);
 	a.pc_total = rw.dev_out(r_total);
 	a.pc_depth = rw.dev_out(r_depth);
 	a.pc_first = rw.dev_out(r_first);
 	a.pc_cons = rw.dev_out(r_cons);
 	HIP_TRY(hipMemsetAsync(a.pc_cons, 0, n_pc * max_ploidy, s.stream));
-	if (na == 4) st = launch_clusters_and_rows<4>(s.stream, times, msg, a, true, per_segment);
-	else st = launch_clusters_and_rows<16>(s.stream, times, msg, a, true, per_segment);
-	if (st != WHAMD_OK) return st;
+	if (na == 4) WHAMD_TRY(launch_clusters_and_rows<4>(s, times, msg, a, true, per_segment));
+	else WHAMD_TRY(launch_clusters_and_rows<16>(s, times, msg, a, true, per_segment));
 	PtSelectArgs sa{};
 	sa.total = a.pc_total;
 	sa.begin = nullptr;
@@ -378,14 +364,15 @@ whamd_status_t polythread_device(const std::vector<ThreadProblem>& ps, int devic
 	sa.n_total = (uint32_t)n_pc;
 	sa.ploidy = 0;
 	sa.stride = sel_stride;
-	if ((st = rs_launch(s.stream, times, msg, polythread_select_kernel, per_key, sa)) != WHAMD_OK) return st;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_counts, run.counts, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_npc, a.npc, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_n_sel, a.n_sel, n_keys * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_sel, a.sel, n_keys * sel_stride * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_rows, dev_rows, rows.total, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_select_kernel, per_key, sa));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, r_counts, run.counts, msg));
+	WHAMD_TRY(s.fetch(res, r_npc, a.npc, msg));
+	WHAMD_TRY(s.fetch(res, r_n_sel, a.n_sel, msg));
+	WHAMD_TRY(s.fetch(res, r_sel, a.sel, msg));
+	WHAMD_TRY(s.fetch(rw.stage, rw.base, rw.total, msg));
+	WHAMD_TRY(s.finish(times, msg));
+	const uint32_t *res_counts = res.host(r_counts), *res_npc = res.host(r_npc), *res_n_sel = res.host(r_n_sel), *res_sel = res.host(r_sel);
 	// back to the problems
 	uint64_t row_at = 0;
 	for (size_t x = 0; x < ps.size(); x++) {
@@ -449,19 +436,14 @@ whamd_status_t polythread_select_device(const std::vector<uint32_t>& begin, cons
 	const auto w_n_sel = work.add<uint32_t>(n_keys);
 	const auto w_sel = work.add<uint32_t>(n_keys * stride);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im, wk;
-	char* dev_work = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(work.total, (void**)&wk.stage, msg)) != WHAMD_OK) return st;
-	wk.base = dev_work;
-	wk.total = work.total;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.stage(work, wk, msg));   // (written by the kernel, fetched whole)
 	std::memcpy(im.host(p_begin), begin.data(), n_keys * sizeof(uint32_t));
 	std::memcpy(im.host(p_count), count.data(), n_keys * sizeof(uint32_t));
 	if (!total.empty()) std::memcpy(im.host(p_total), total.data(), total.size() * sizeof(uint32_t));
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.upload(im, msg));
 	PtSelectArgs sa{};
 	sa.total = im.dev(p_total);
 	sa.begin = im.dev(p_begin);
@@ -473,10 +455,10 @@ whamd_status_t polythread_select_device(const std::vector<uint32_t>& begin, cons
 	sa.n_total = (uint32_t)total.size();
 	sa.ploidy = ploidy;
 	sa.stride = (uint32_t)stride;
-	if ((st = rs_launch(s.stream, times, msg, polythread_select_kernel, dim3((uint32_t)((n_keys + RS_BLOCK - 1) / RS_BLOCK)), sa)) != WHAMD_OK) return st;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(wk.stage, dev_work, work.total, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_select_kernel, dim3(grid_for(n_keys, RS_BLOCK)), sa));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(wk.stage, wk.base, wk.total, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	std::memcpy(n_sel.data(), wk.host(w_n_sel), n_keys * sizeof(uint32_t));
 	std::memcpy(sel.data(), wk.host(w_sel), n_keys * stride * sizeof(uint32_t));
 	for (uint64_t v = 0; v < n_keys; v++) {
@@ -502,25 +484,24 @@ whamd_status_t polythread_haplotypes_device(const uint32_t* paths, uint64_t n_po
 	const auto p_cluster = in.add<uint32_t>(n_rows);
 	const auto p_cons = in.add<int8_t>(n_rows * ploidy);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im;
 	int8_t *dev_out = nullptr, *res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(n_pos * ploidy, (void**)&dev_out, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_pos * ploidy, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.device_block(n_pos * ploidy, (void**)&dev_out, msg));
+	WHAMD_TRY(s.pinned_block(n_pos * ploidy, (void**)&res, msg));
 	std::memcpy(im.host(p_paths), paths, n_pos * ploidy * sizeof(uint32_t));
 	for (uint64_t x = 0; x <= n_pos; x++) im.host(p_begin)[x] = (uint32_t)pc_ptr[x];
 	if (n_rows) {
 		std::memcpy(im.host(p_cluster), pc_cluster, n_rows * sizeof(uint32_t));
 		std::memcpy(im.host(p_cons), pc_cons, n_rows * ploidy);
 	}
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.upload(im, msg));
 	PtHaplotypeArgs ha{im.dev(p_paths), im.dev(p_begin), im.dev(p_cluster), im.dev(p_cons), dev_out, (uint32_t)n_pos, ploidy};
-	if ((st = rs_launch(s.stream, times, msg, polythread_haplotypes_kernel, dim3((uint32_t)((n_pos + RS_BLOCK - 1) / RS_BLOCK)), ha)) != WHAMD_OK) return st;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, dev_out, n_pos * ploidy, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(rs_launch(s, times, msg, polythread_haplotypes_kernel, dim3(grid_for(n_pos, RS_BLOCK)), ha));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, dev_out, n_pos * ploidy, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	std::memcpy(out.data(), res, n_pos * ploidy);
 	return WHAMD_OK;
 }

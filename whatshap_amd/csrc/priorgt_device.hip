@@ -215,19 +215,15 @@ whamd_status_t priorgt_device(const std::vector<PriorProblem>& ps, int device, s
 	rs_add_rest(work, n_col, w_run);
 	const auto w_placed = work.add<uint32_t>(n_placed);
 	const auto w_out = work.add<PgOut>(n_col);
+	ImageLayout results;   // what comes back
+	const auto r_out = results.add<PgOut>(n_col);
+	const auto r_counts = results.add<uint32_t>(n_col);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
-	Image im, wk;
-	char* dev_work = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
-	wk.base = dev_work;
-	wk.total = work.total;
-	PgOut* res_out = nullptr;
-	uint32_t* res_counts = nullptr;
-	if ((st = s.pinned_block(n_col * sizeof(PgOut), (void**)&res_out, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_col * sizeof(uint32_t), (void**)&res_counts, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
+	Image im, wk, res;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.work(work, wk, msg));
+	WHAMD_TRY(s.results(results, res, msg));
 	// the image: a word per column, and per entry the column moved to its place in the call and the code as prepared
 	pg_factor_table(im.host(p_table));
 	for (size_t x = 0; x < ps.size(); x++) {
@@ -245,8 +241,8 @@ whamd_status_t priorgt_device(const std::vector<PriorProblem>& ps, int device, s
 			std::memcpy(ecode + b, p.code.data() + b, e - b);
 		});
 	}
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	HIP_TRY(hipMemsetAsync(dev_work, 0, zeroed, s.stream));
+	WHAMD_TRY(s.upload(im, msg));
+	WHAMD_TRY(s.zero(wk, zeroed, msg));
 	PgArgs a{};
 	a.col_slot = im.dev(p_slot);
 	a.params = im.dev(p_params);
@@ -259,20 +255,21 @@ whamd_status_t priorgt_device(const std::vector<PriorProblem>& ps, int device, s
 	a.out = wk.dev_out(w_out);
 	a.n_entries = (uint32_t)n_entries;
 	const RunIndex& run = a.run;
-	const dim3 per_entry((uint32_t)((n_entries + RS_BLOCK - 1) / RS_BLOCK)), per_segment((uint32_t)((n_col + RS_BLOCK / RS_SEGMENT - 1) / (RS_BLOCK / RS_SEGMENT))),
-	    per_column((uint32_t)((n_col + RS_BLOCK - 1) / RS_BLOCK));
-	const auto launch = [&](void (*kernel)(PgArgs), dim3 grid) { return rs_launch(s.stream, times, msg, kernel, grid, a); };
-	if ((st = launch(priorgt_count_kernel, per_entry)) != WHAMD_OK) return st;
-	if ((st = rs_scan(s.stream, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr)) != WHAMD_OK) return st;
-	if ((st = launch(priorgt_place_kernel, per_entry)) != WHAMD_OK) return st;
-	if ((st = launch(priorgt_order_a_kernel, per_segment)) != WHAMD_OK) return st;
-	if ((st = launch(priorgt_order_b_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
-	if ((st = launch(priorgt_order_c_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
-	if ((st = launch(priorgt_chain_kernel, per_column)) != WHAMD_OK) return st;
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_out, a.out, n_col * sizeof(PgOut), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_counts, run.counts,n_col * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	const dim3 per_entry(grid_for(n_entries, RS_BLOCK)), per_segment(grid_for(n_col, RS_BLOCK / RS_SEGMENT)), per_column(grid_for(n_col, RS_BLOCK));
+	const auto launch = [&](void (*kernel)(PgArgs), dim3 grid) { return rs_launch(s, times, msg, kernel, grid, a); };
+	WHAMD_TRY(launch(priorgt_count_kernel, per_entry));
+	WHAMD_TRY(rs_scan(s, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr));
+	WHAMD_TRY(launch(priorgt_place_kernel, per_entry));
+	WHAMD_TRY(launch(priorgt_order_a_kernel, per_segment));
+	WHAMD_TRY(launch(priorgt_order_b_kernel, dim3(RS_LIST_GRID)));
+	WHAMD_TRY(launch(priorgt_order_c_kernel, dim3(RS_LIST_GRID)));
+	WHAMD_TRY(launch(priorgt_chain_kernel, per_column));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, r_out, a.out, msg));
+	WHAMD_TRY(s.fetch(res, r_counts, run.counts, msg));
+	WHAMD_TRY(s.finish(times, msg));
+	const PgOut* res_out = res.host(r_out);
+	const uint32_t* res_counts = res.host(r_counts);
 	for (size_t x = 0; x < ps.size(); x++) {
 		if (!ps[x].n_counted) continue;
 		out[x].out.assign(res_out + col_base[x], res_out + col_base[x + 1]);

@@ -146,7 +146,7 @@ struct PairBatch {
 		pa.score = score;
 		return pa;
 	}
-	uint32_t blocks() const { return (uint32_t)std::min<uint64_t>((n_entries + BLOCK - 1) / BLOCK, MAX_BLOCKS); }
+	dim3 blocks() const { return dim3(grid_for(n_entries, BLOCK, MAX_BLOCKS)); }
 	void scatter(const double* res, std::vector<ProgenyResult>& out) const {
 		for (uint32_t u = 0; u < up.size(); u++) {
 			RawVec<double>& dst = out[up[u]].score;
@@ -285,7 +285,7 @@ struct DepthBatch {
 		ga.table_f64 = table_f64;
 		return ga;
 	}
-	uint32_t blocks() const { return (uint32_t)std::min<uint64_t>((n_cells + BLOCK - 1) / BLOCK, MAX_BLOCKS); }
+	dim3 blocks() const { return dim3(grid_for(n_cells, BLOCK, MAX_BLOCKS)); }
 };
 
 struct TypesKernelArgs {
@@ -325,14 +325,13 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 	b.add(in);
 	const auto p_table = in.add<float>(std::max<uint64_t>(b.n_floats, 1));
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im;
 	double* score = nullptr;
 	double* res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(b.n_entries * 8, (void**)&score, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(b.n_entries * 8, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.device_block(b.n_entries * 8, (void**)&score, msg));
+	WHAMD_TRY(s.pinned_block(b.n_entries * 8, (void**)&res, msg));
 	b.fill(im);
 	// the repack: a block of nodes at a time (its rows stay in the host cache while every plane takes its piece)
 	parallel_ranges(jobs.size(), host_threads(b.n_floats, 1 << 18), [&](uint64_t jb, uint64_t je, uint32_t) {
@@ -354,13 +353,11 @@ whamd_status_t progeny_score_device(const std::vector<ProgenyProblem>& ps, int d
 	});
 
 	const PairArgs pa = b.args(im, im.dev(p_table), score);
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	hipLaunchKernelGGL(progeny_pair_kernel, dim3(b.blocks()), dim3(BLOCK), 0, s.stream, pa);
-	HIP_TRY(hipGetLastError());
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, score, b.n_entries * 8, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
-	times.launches = 1;
+	WHAMD_TRY(s.upload(im, msg));
+	WHAMD_TRY(launch(s, times, msg, progeny_pair_kernel, b.blocks(), dim3(BLOCK), 0, pa));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, score, b.n_entries * 8, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	b.scatter(res, out);
 	return WHAMD_OK;
 }
@@ -380,25 +377,23 @@ whamd_status_t progeny_gl_device(const std::vector<ProgenyDepths>& ds, int devic
 	ImageLayout in;
 	b.add(in);
 	Session s;
-	whamd_status_t st = s.open(device, 0, msg);   // (no events: the call reports no times)
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 0, msg));   // (no events: the call reports no times)
 	Image im;
 	float *t32 = nullptr, *r32 = nullptr;
 	double *t64 = nullptr, *r64 = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if (want_f32 && (st = s.device_block(b.n_values * 4, (void**)&t32, msg)) != WHAMD_OK) return st;
-	if (want_f32 && (st = s.pinned_block(b.n_values * 4, (void**)&r32, msg)) != WHAMD_OK) return st;
-	if (want_f64 && (st = s.device_block(b.n_values * 8, (void**)&t64, msg)) != WHAMD_OK) return st;
-	if (want_f64 && (st = s.pinned_block(b.n_values * 8, (void**)&r64, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	if (want_f32) WHAMD_TRY(s.device_block(b.n_values * 4, (void**)&t32, msg));
+	if (want_f32) WHAMD_TRY(s.pinned_block(b.n_values * 4, (void**)&r32, msg));
+	if (want_f64) WHAMD_TRY(s.device_block(b.n_values * 8, (void**)&t64, msg));
+	if (want_f64) WHAMD_TRY(s.pinned_block(b.n_values * 8, (void**)&r64, msg));
 	b.fill(im, nullptr);
 	const GlArgs ga = b.args(im, nullptr, t32, t64);
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	hipLaunchKernelGGL(progeny_gl_kernel, dim3(b.blocks()), dim3(BLOCK), 0, s.stream, ga);
-	HIP_TRY(hipGetLastError());
+	WHAMD_TRY(s.upload(im, msg));
 	CallTimes unused;
-	if (want_f32 && (st = s.fetch(r32, t32, b.n_values * 4, msg)) != WHAMD_OK) return st;
-	if (want_f64 && (st = s.fetch(r64, t64, b.n_values * 8, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(unused, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(launch(s, unused, msg, progeny_gl_kernel, b.blocks(), dim3(BLOCK), 0, ga));
+	if (want_f32) WHAMD_TRY(s.fetch(r32, t32, b.n_values * 4, msg));
+	if (want_f64) WHAMD_TRY(s.fetch(r64, t64, b.n_values * 8, msg));
+	WHAMD_TRY(s.finish(unused, msg));
 	for (size_t x = 0; x < ds.size(); x++) {
 		const uint64_t n = b.value_base[x + 1] - b.value_base[x];
 		if (want_f32 && table_out[x]) progeny_copy(table_out[x], r32 + b.value_base[x], n * 4);
@@ -420,31 +415,25 @@ whamd_status_t progeny_score_depths_device(const std::vector<ProgenyDepths>& ds,
 	b.add(in);
 	d.add(in);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	Image im;
 	float* planes = nullptr;
 	double* score = nullptr;
 	double* res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(std::max<uint64_t>(b.n_floats, 1) * 4, (void**)&planes, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(b.n_entries * 8, (void**)&score, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(b.n_entries * 8, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.device_block(std::max<uint64_t>(b.n_floats, 1) * 4, (void**)&planes, msg));
+	WHAMD_TRY(s.device_block(b.n_entries * 8, (void**)&score, msg));
+	WHAMD_TRY(s.pinned_block(b.n_entries * 8, (void**)&res, msg));
 	b.fill(im);
 	d.fill(im, b.table_base.data());
 	const GlArgs ga = d.args(im, planes, nullptr, nullptr);
 	const PairArgs pa = b.args(im, planes, score);
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	if (d.n_cells) {   // (entries between nodes of a problem without samples read no plane)
-		hipLaunchKernelGGL(progeny_gl_kernel, dim3(d.blocks()), dim3(BLOCK), 0, s.stream, ga);
-		HIP_TRY(hipGetLastError());
-	}
-	hipLaunchKernelGGL(progeny_pair_kernel, dim3(b.blocks()), dim3(BLOCK), 0, s.stream, pa);
-	HIP_TRY(hipGetLastError());
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res, score, b.n_entries * 8, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
-	times.launches = d.n_cells ? 2 : 1;
+	WHAMD_TRY(s.upload(im, msg));
+	if (d.n_cells) WHAMD_TRY(launch(s, times, msg, progeny_gl_kernel, d.blocks(), dim3(BLOCK), 0, ga));   // (entries between nodes of a problem without samples read no plane)
+	WHAMD_TRY(launch(s, times, msg, progeny_pair_kernel, b.blocks(), dim3(BLOCK), 0, pa));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, score, b.n_entries * 8, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	b.scatter(res, out);
 	return WHAMD_OK;
 }
@@ -458,24 +447,21 @@ whamd_status_t progeny_types_device(const float* rows, uint64_t n, uint32_t n_sa
 	const auto p_prior = in.add<double>((size_t)n_types * k1);
 	const auto p_rows = in.add<float>(n * n_samples * k1);
 	Session s;
-	whamd_status_t st = s.open(device, 0, msg);   // (no events: the call reports no times)
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 0, msg));   // (no events: the call reports no times)
 	Image im;
 	double* out = nullptr;
 	double* res = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(n_lanes * 8, (void**)&out, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_lanes * 8, (void**)&res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.device_block(n_lanes * 8, (void**)&out, msg));
+	WHAMD_TRY(s.pinned_block(n_lanes * 8, (void**)&res, msg));
 	std::memcpy(im.host(p_prior), prior, p_prior.bytes());
 	std::memcpy(im.host(p_rows), rows, p_rows.bytes());
 	TypesKernelArgs ta{n_lanes, n_types, n_samples, k1, im.dev(p_rows), im.dev(p_prior), out};
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_lanes + BLOCK - 1) / BLOCK, MAX_BLOCKS);
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	hipLaunchKernelGGL(progeny_types_kernel, dim3(blocks), dim3(BLOCK), 0, s.stream, ta);
-	HIP_TRY(hipGetLastError());
+	WHAMD_TRY(s.upload(im, msg));
 	CallTimes unused;
-	if ((st = s.fetch(res, out, n_lanes * 8, msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(unused, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(launch(s, unused, msg, progeny_types_kernel, dim3(grid_for(n_lanes, BLOCK, MAX_BLOCKS)), dim3(BLOCK), 0, ta));
+	WHAMD_TRY(s.fetch(res, out, n_lanes * 8, msg));
+	WHAMD_TRY(s.finish(unused, msg));
 	std::memcpy(llh, res, n_lanes * 8);
 	return WHAMD_OK;
 }

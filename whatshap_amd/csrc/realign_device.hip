@@ -335,8 +335,7 @@ LongShape long_shape(bool affine, uint64_t n_long, uint32_t max_target) {
 
 whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele_out, int64_t* quality_out, CallTimes& times, std::string& msg) {
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
 	const bool affine = b.params.use_affine != 0;
 	// one image: jobs | query windows | long jobs | variants | allowed alleles | alt offsets | alt bytes | reference slice
 	ImageLayout in;
@@ -349,7 +348,7 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 	const auto p_altb = in.add<uint8_t>(b.n_alt_bytes);
 	const auto p_ref = in.add<uint8_t>(b.ref_len);
 	Image im;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
 	const uint32_t n_ranges = (uint32_t)b.range_jobs.size();
 	parallel_ranges(n_ranges + 1, host_threads(n_ranges + 1, 1), [&](uint64_t begin, uint64_t end, uint32_t) {
 		for (uint64_t r = begin; r < end; ++r) {
@@ -378,7 +377,7 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 	const auto p_allele = out.add<int32_t>(b.n_jobs);
 	const auto p_quality = out.add<int64_t>(affine ? b.n_jobs : 0);
 	Image res;
-	if ((st = s.stage(out, res, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(out, res, msg));
 	RealignArgs a{};
 	a.jobs = im.dev(p_jobs);
 	a.qbuf = im.dev(p_q);
@@ -396,7 +395,7 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 	RealignArgs shortj = a;
 	shortj.n_items = (uint32_t)b.n_jobs;
 	shortj.skip_long = b.n_long > 0;
-	const uint32_t short_blocks = (uint32_t)std::min<uint64_t>(affine ? (b.n_jobs + BLOCK / 64 - 1) / (BLOCK / 64) : (b.n_jobs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
+	const dim3 short_blocks(grid_for(b.n_jobs, affine ? BLOCK / 64 : BLOCK, MAX_BLOCKS));
 	RealignArgs longj = a;
 	const LongShape ls = long_shape(affine, b.n_long, b.max_target_long);
 	if (b.n_long) {
@@ -406,23 +405,18 @@ whamd_status_t realign_device(const RealignBatch& b, int device, int32_t* allele
 		longj.row_floats = ls.row_floats;
 		if (ls.scratch) {
 			void* c = nullptr;
-			if ((st = s.device_block(ls.scratch, &c, msg)) != WHAMD_OK) return st;
+			WHAMD_TRY(s.device_block(ls.scratch, &c, msg));
 			if (affine) longj.bnd = (float*)c;
 			else longj.carry = (uint64_t*)c;
 		}
 	}
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
-	else hipLaunchKernelGGL(realign_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortj);
-	HIP_TRY(hipGetLastError());
-	if (b.n_long) {
-		if (affine) hipLaunchKernelGGL(realign_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longj);
-		else hipLaunchKernelGGL(realign_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longj);
-		HIP_TRY(hipGetLastError());
-	}
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res.stage, res.base, p_quality.end(), msg)) != WHAMD_OK) return st;   // (to the last byte in use)
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.upload(im, msg));
+	const auto kernel = affine ? realign_affine_kernel : realign_unit_kernel;
+	WHAMD_TRY(launch(s, times, msg, kernel, short_blocks, dim3(BLOCK), 0, shortj));
+	if (b.n_long) WHAMD_TRY(launch(s, times, msg, kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, longj));
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res.stage, res.base, p_quality.end(), msg));   // (to the last byte in use)
+	WHAMD_TRY(s.finish(times, msg));
 	std::memcpy(allele_out, res.host(p_allele), p_allele.bytes());
 	if (affine) std::memcpy(quality_out, res.host(p_quality), p_quality.bytes());
 	return WHAMD_OK;
@@ -443,8 +437,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 		}
 	}
 	Session s;
-	whamd_status_t st = s.open(device, 0, msg);   // (no events: the call reports no times)
-	if (st != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 0, msg));   // (no events: the call reports no times)
 	const uint64_t nq = query_ptr[n_pairs], nt = target_ptr[n_pairs], n_long = long_pairs.size();
 	// one image: query offsets | target offsets | queries | targets | mismatch costs | long pairs | the distances (written by the kernels: not uploaded)
 	ImageLayout in;
@@ -456,7 +449,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 	const auto p_long = in.add<uint32_t>(n_long);
 	const auto p_out = in.add<int64_t>(n_pairs);
 	Image im;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.stage(in, im, msg));
 	std::memcpy(im.host(p_qp), query_ptr, p_qp.bytes());
 	std::memcpy(im.host(p_tp), target_ptr, p_tp.bytes());
 	if (nq) std::memcpy(im.host(p_q), query, nq);
@@ -475,7 +468,7 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 	PairArgs shortp = a;
 	shortp.n_items = (uint32_t)n_pairs;
 	shortp.skip_long = n_long > 0;
-	const uint32_t short_blocks = (uint32_t)std::min<uint64_t>(use_affine ? (n_pairs + BLOCK / 64 - 1) / (BLOCK / 64) : (n_pairs + BLOCK - 1) / BLOCK, MAX_BLOCKS);
+	const dim3 short_blocks(grid_for(n_pairs, use_affine ? BLOCK / 64 : BLOCK, MAX_BLOCKS));
 	PairArgs longp = a;
 	const LongShape ls = long_shape(use_affine != 0, n_long, max_t_long);
 	if (n_long) {
@@ -485,23 +478,18 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
 		longp.row_floats = ls.row_floats;
 		if (ls.scratch) {
 			void* c = nullptr;
-			if ((st = s.device_block(ls.scratch, &c, msg)) != WHAMD_OK) return st;
+			WHAMD_TRY(s.device_block(ls.scratch, &c, msg));
 			if (use_affine) longp.bnd = (float*)c;
 			else longp.carry = (uint64_t*)c;
 		}
 	}
-	if ((st = s.upload(im, p_out.offset, msg)) != WHAMD_OK) return st;
-	if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
-	else hipLaunchKernelGGL(distance_unit_kernel, dim3(short_blocks), dim3(BLOCK), 0, s.stream, shortp);
-	HIP_TRY(hipGetLastError());
-	if (n_long) {
-		if (use_affine) hipLaunchKernelGGL(distance_affine_kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, s.stream, longp);
-		else hipLaunchKernelGGL(distance_unit_kernel, dim3(ls.blocks), dim3(ls.block), 0, s.stream, longp);
-		HIP_TRY(hipGetLastError());
-	}
+	WHAMD_TRY(s.upload(im, p_out.offset, msg));
 	CallTimes unused;
-	if ((st = s.fetch(im.host(p_out), im.dev(p_out), p_out.bytes(), msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(unused, msg)) != WHAMD_OK) return st;
+	const auto kernel = use_affine ? distance_affine_kernel : distance_unit_kernel;
+	WHAMD_TRY(launch(s, unused, msg, kernel, short_blocks, dim3(BLOCK), 0, shortp));
+	if (n_long) WHAMD_TRY(launch(s, unused, msg, kernel, dim3(ls.blocks), dim3(ls.block), ls.lds, longp));
+	WHAMD_TRY(s.fetch(im.host(p_out), im.dev(p_out), p_out.bytes(), msg));
+	WHAMD_TRY(s.finish(unused, msg));
 	std::memcpy(distance_out, im.host(p_out), p_out.bytes());
 	return WHAMD_OK;
 }

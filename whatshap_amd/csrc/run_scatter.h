@@ -106,8 +106,9 @@ __device__ inline uint32_t block_exclusive(uint32_t mine, uint32_t* wave_total, 
 }
 
 // ---------------------------------------------------------------------------------------------- host
-// The index's pieces of a call's work layout.  The call zeroes the front of its work block: rs_add_zeroed() first, then the layer's own
-// zeroed pieces, then -- the layout's total is the number of bytes to zero -- rs_add_rest() and what else the layer makes.
+// The index's pieces of a call's work layout (Session::work()).  The call zeroes the front of its work image: rs_add_zeroed() first, then
+// the layer's own zeroed pieces, then -- the layout's total is the number of bytes for Session::zero() -- rs_add_rest() and what else the
+// layer makes.
 struct RunPieces {
 	Piece<uint32_t> counts, cursor, list_n, local, tile_sums, list_b, list_c;
 };
@@ -116,18 +117,15 @@ void rs_add_zeroed(ImageLayout& work, uint64_t n_keys, RunPieces& p);
 void rs_add_rest(ImageLayout& work, uint64_t n_keys, RunPieces& p);
 RunIndex rs_bind(const Image& work, const RunPieces& p, uint64_t n_keys, uint64_t n_placed, uint32_t a_max, uint32_t b_max);
 
-// One launch of RS_BLOCK threads per workgroup on `stream`, checked and counted in times.launches.
+// launch() (device_runtime.h) with RS_BLOCK threads per workgroup.
 template <class... P>
-whamd_status_t rs_launch(hipStream_t stream, CallTimes& times, std::string& msg, void (*kernel)(P...), dim3 grid, P... args) {
-	hipLaunchKernelGGL(kernel, grid, dim3(RS_BLOCK), 0, stream, args...);
-	HIP_TRY(hipGetLastError());
-	++times.launches;
-	return WHAMD_OK;
+whamd_status_t rs_launch(Session& s, CallTimes& times, std::string& msg, void (*kernel)(P...), dim3 grid, P... args) {
+	return launch(s, times, msg, kernel, grid, dim3(RS_BLOCK), 0, args...);
 }
 
 // The two scan launches: in[n] -> local[n], tile_sums[rs_tiles(n)].  With `lists`: the elements of more than its a_max / b_max are
 // appended to its list_b / list_c (lengths in its list_n).  With total_out: the sum of all goes there.
-whamd_status_t rs_scan(hipStream_t stream, CallTimes& times, std::string& msg, const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n,
+whamd_status_t rs_scan(Session& s, CallTimes& times, std::string& msg, const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n,
                        const RunIndex* lists, uint32_t* total_out);
 
 }  // namespace whamd

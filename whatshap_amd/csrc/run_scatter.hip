@@ -70,14 +70,13 @@ RunIndex rs_bind(const Image& work, const RunPieces& p, uint64_t n_keys, uint64_
 	                work.dev_out(p.list_c), (uint32_t)n_keys, (uint32_t)n_placed, a_max, b_max};
 }
 
-whamd_status_t rs_scan(hipStream_t stream, CallTimes& times, std::string& msg, const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n,
+whamd_status_t rs_scan(Session& s, CallTimes& times, std::string& msg, const uint32_t* in, uint32_t* local, uint32_t* tile_sums, uint32_t n,
                        const RunIndex* lists, uint32_t* total_out) {
 	const uint32_t n_tiles = rs_tiles(n);
 	const RunIndex none{};
 	const RunIndex& l = lists ? *lists : none;
-	const whamd_status_t st = rs_launch(stream, times, msg, run_scan_tiles_kernel, dim3(n_tiles), in, local, tile_sums, n, l.list_n, l.list_b, l.list_c, l.a_max, l.b_max);
-	if (st != WHAMD_OK) return st;
-	return rs_launch(stream, times, msg, run_scan_sums_kernel, dim3(1), tile_sums, n_tiles, total_out);
+	WHAMD_TRY(rs_launch(s, times, msg, run_scan_tiles_kernel, dim3(n_tiles), in, local, tile_sums, n, l.list_n, l.list_b, l.list_c, l.a_max, l.b_max));
+	return rs_launch(s, times, msg, run_scan_sums_kernel, dim3(1), tile_sums, n_tiles, total_out);
 }
 
 }  // namespace whamd

@@ -351,21 +351,16 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 	const auto w_nps_tiles = work.add<uint32_t>(want_table ? rs_tiles(n_var) : 0);
 	const auto w_placed = work.add<TpPlaced>(n_placed);
 	const auto w_out = work.add<TpOut>(n_var);
+	ImageLayout results;   // what comes back
+	const auto r_out = results.add<TpOut>(n_var);
+	const auto r_counts = results.add<uint32_t>(n_var);
+	const auto r_n_rows = results.add<uint32_t>(1);
 	Session s;
-	whamd_status_t st = s.open(device, 4, msg);
-	if (st != WHAMD_OK) return st;
-	Image im, wk;
-	char* dev_work = nullptr;
-	if ((st = s.stage(in, im, msg)) != WHAMD_OK) return st;
-	if ((st = s.device_block(work.total, (void**)&dev_work, msg)) != WHAMD_OK) return st;
-	wk.base = dev_work;
-	wk.total = work.total;
-	TpOut* res_out = nullptr;
-	uint32_t* res_counts = nullptr;
-	uint32_t* res_rows_n = nullptr;
-	if ((st = s.pinned_block(n_var * sizeof(TpOut), (void**)&res_out, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(n_var * sizeof(uint32_t), (void**)&res_counts, msg)) != WHAMD_OK) return st;
-	if ((st = s.pinned_block(sizeof(uint32_t), (void**)&res_rows_n, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.open(device, 4, msg));
+	Image im, wk, res, rows;
+	WHAMD_TRY(s.stage(in, im, msg));
+	WHAMD_TRY(s.work(work, wk, msg));
+	WHAMD_TRY(s.results(results, res, msg));
 	// the image: per variant and per read a few words; the entry arrays are copied as they are
 	for (size_t x = 0; x < ps.size(); x++) {
 		const TagphaseProblem& p = ps[x];
@@ -390,8 +385,8 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 		});
 	}
 	im.host(p_rptr)[n_reads] = (uint32_t)n_entries;
-	if ((st = s.upload(im, msg)) != WHAMD_OK) return st;
-	HIP_TRY(hipMemsetAsync(dev_work, 0, zeroed, s.stream));
+	WHAMD_TRY(s.upload(im, msg));
+	WHAMD_TRY(s.zero(wk, zeroed, msg));
 	TpArgs a{};
 	a.vinfo = im.dev(p_vinfo);
 	a.gap = im.dev(p_gap);
@@ -411,37 +406,40 @@ whamd_status_t tagphase_device(const std::vector<TagphaseProblem>& ps, int devic
 	a.n_reads = (uint32_t)n_reads;
 	a.n_entries = (uint32_t)n_entries;
 	const RunIndex& run = a.run;
-	const dim3 per_entry((uint32_t)((n_entries + RS_BLOCK - 1) / RS_BLOCK)), per_segment((uint32_t)((n_var + RS_BLOCK / TP_SEGMENT - 1) / (RS_BLOCK / TP_SEGMENT)));
-	const auto launch = [&](void (*kernel)(TpArgs), dim3 grid) { return rs_launch(s.stream, times, msg, kernel, grid, a); };
-	if ((st = launch(tagphase_count_kernel, per_entry)) != WHAMD_OK) return st;
-	if ((st = rs_scan(s.stream, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr)) != WHAMD_OK) return st;
-	if ((st = launch(tagphase_place_kernel, per_entry)) != WHAMD_OK) return st;
-	if ((st = launch(tagphase_reduce_a_kernel, per_segment)) != WHAMD_OK) return st;
-	if ((st = launch(tagphase_reduce_b_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
-	if ((st = launch(tagphase_reduce_c_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
-	TpRow* res_rows = nullptr;
+	const dim3 per_entry(grid_for(n_entries, RS_BLOCK)), per_segment(grid_for(n_var, RS_BLOCK / TP_SEGMENT));
+	const auto launch = [&](void (*kernel)(TpArgs), dim3 grid) { return rs_launch(s, times, msg, kernel, grid, a); };
+	WHAMD_TRY(launch(tagphase_count_kernel, per_entry));
+	WHAMD_TRY(rs_scan(s, times, msg, run.counts, run.local, run.tile_sums, run.n_keys, &run, nullptr));
+	WHAMD_TRY(launch(tagphase_place_kernel, per_entry));
+	WHAMD_TRY(launch(tagphase_reduce_a_kernel, per_segment));
+	WHAMD_TRY(launch(tagphase_reduce_b_kernel, dim3(RS_LIST_GRID)));
+	WHAMD_TRY(launch(tagphase_reduce_c_kernel, dim3(RS_LIST_GRID)));
+	Piece<TpRow> r_rows;
 	uint64_t n_rows = 0;
 	if (want_table) {
-		if ((st = rs_scan(s.stream, times, msg, a.nps, a.nps_local, a.nps_tile_sums, run.n_keys, nullptr, a.n_rows)) != WHAMD_OK) return st;
-		// the one wait in the middle of the call: the table's size
-		if ((st = s.fetch(res_rows_n, a.n_rows, sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-		HIP_TRY(hipStreamSynchronize(s.stream));
-		n_rows = *res_rows_n;
+		WHAMD_TRY(rs_scan(s, times, msg, a.nps, a.nps_local, a.nps_tile_sums, run.n_keys, nullptr, a.n_rows));
+		WHAMD_TRY(s.fetch_now(res, r_n_rows, a.n_rows, msg));   // the table's size
+		n_rows = *res.host(r_n_rows);
 		if (n_rows > n_placed) {
 			msg = "internal error: more table rows than voting entries";
 			return WHAMD_ERR_DEVICE;
 		}
-		if ((st = s.device_block(n_rows * sizeof(TpRow), (void**)&a.rows, msg)) != WHAMD_OK) return st;
-		if ((st = s.pinned_block(n_rows * sizeof(TpRow), (void**)&res_rows, msg)) != WHAMD_OK) return st;
-		if ((st = launch(tagphase_rows_a_kernel, per_segment)) != WHAMD_OK) return st;
-		if ((st = launch(tagphase_rows_list_kernel, dim3(RS_LIST_GRID))) != WHAMD_OK) return st;
+		ImageLayout table;   // the second result image: sized by the wait
+		r_rows = table.add<TpRow>(n_rows);
+		WHAMD_TRY(s.stage(table, rows, msg));
+		a.rows = rows.dev_out(r_rows);
+		WHAMD_TRY(launch(tagphase_rows_a_kernel, per_segment));
+		WHAMD_TRY(launch(tagphase_rows_list_kernel, dim3(RS_LIST_GRID)));
 	}
-	if ((st = s.kernels_done(msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_out, a.out, n_var * sizeof(TpOut), msg)) != WHAMD_OK) return st;
-	if ((st = s.fetch(res_counts, run.counts,n_var * sizeof(uint32_t), msg)) != WHAMD_OK) return st;
-	if (n_rows && (st = s.fetch(res_rows, a.rows, n_rows * sizeof(TpRow), msg)) != WHAMD_OK) return st;
-	if ((st = s.finish(times, msg)) != WHAMD_OK) return st;
+	WHAMD_TRY(s.kernels_done(msg));
+	WHAMD_TRY(s.fetch(res, r_out, a.out, msg));
+	WHAMD_TRY(s.fetch(res, r_counts, run.counts, msg));
+	if (n_rows) WHAMD_TRY(s.fetch(rows, r_rows, a.rows, msg));
+	WHAMD_TRY(s.finish(times, msg));
 	// back to the problems: entry indices become local to each
+	const TpOut* res_out = res.host(r_out);
+	const uint32_t* res_counts = res.host(r_counts);
+	const TpRow* res_rows = rows.host(r_rows);   // (null without a table)
 	uint64_t row_at = 0;
 	for (size_t x = 0; x < ps.size(); x++) {
 		const TagphaseProblem& p = ps[x];

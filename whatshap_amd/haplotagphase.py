@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -137,12 +137,14 @@ class TagphaseResult:
         return voted[np.argsort(self.first[voted], kind="stable")]
 
 
-def tagphase_batch(problems: Sequence[TagphaseProblem], device: int = 0, host: bool = False, want_table: bool = False,
+def tagphase_batch(problems: Sequence[TagphaseProblem], device: int = 0, host: bool = False, want_table: Union[bool, Sequence[bool]] = False,
                    stats: Optional[list] = None) -> List[TagphaseResult]:
     """Every problem (chromosome x sample) in one native call: one upload, 7 launches (11 with ``want_table``) whatever the problems.
+    ``want_table`` is one flag for all problems or one per problem.
     ``stats``, if given, receives one dict per problem (its counts; launches and times are those of the whole call)."""
     P = _native._ptr
-    with _native.batch_handle(host, [p.view(want_table) for p in problems], "whamd_tagphase", "whamd_debug_tagphase_host", "whamd_tagphase_destroy",
+    wants = [want_table] * len(problems) if isinstance(want_table, bool) else list(want_table)
+    with _native.batch_handle(host, [p.view(w) for p, w in zip(problems, wants)], "whamd_tagphase", "whamd_debug_tagphase_host", "whamd_tagphase_destroy",
                               device=device) as (L, h):
         out = []
         for k in range(len(problems)):
@@ -153,7 +155,7 @@ def tagphase_batch(problems: Sequence[TagphaseProblem], device: int = 0, host: b
             _native.checked(L, L.whamd_tagphase_get(h, k, P(voted, C.c_uint8), P(first, C.c_uint64), P(nps, C.c_uint32), P(best_ps, C.c_int64),
                                                     P(best_id, C.c_uint8), P(score, C.c_int64), P(total, C.c_int64), P(kept, C.c_uint8), P(zero, C.c_uint8)))
             table = None
-            if want_table:
+            if wants[k]:
                 rows = L.whamd_tagphase_row_count(h, k)
                 table = (np.zeros(cnt + 1, dtype=np.uint64), np.zeros(rows, dtype=np.int64), np.zeros(rows, dtype=np.int64), np.zeros(rows, dtype=np.int64),
                          np.zeros(rows, dtype=np.uint64))
