@@ -65,6 +65,26 @@ whamd_status_t whamd_debug_edit_distance_host(uint64_t n_pairs, const uint64_t* 
                                               const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start,
                                               int32_t gap_extend, int64_t* distance_out);
 
+/* THE LAUNCH SHAPE of realign's long jobs (csrc/realign_shape.h, DESIGN.md: the table of shapes): what the second launch of
+ * whamd_realign_detect / whamd_edit_distance_batch -- the one over the jobs whose query is longer than 64 -- looks like for n_long such jobs
+ * whose longest allele window (target) is max_target bytes.  Host code, no device needed.  blocks = 0: no second launch.  lds_bytes: dynamic
+ * LDS per workgroup (affine strip boundary rows in LDS); scratch_bytes: global scratch (unit carry rows of carry_words words per lane, or
+ * affine rows of row_floats floats per wave when global_rows = 1). */
+typedef struct whamd_debug_realign_shape {
+	uint32_t blocks, block;
+	uint64_t lds_bytes, scratch_bytes;
+	uint32_t carry_words, row_floats;
+	int32_t global_rows, reserved;
+} whamd_debug_realign_shape;
+whamd_status_t whamd_debug_realign_long_shape(int use_affine, uint64_t n_long, uint32_t max_target, whamd_debug_realign_shape* out);
+/* What the shape of a call is made from: the host walk of whamd_realign_detect on the same views (jobs, long jobs, the longest allele window
+ * of a long job), and the same two counts for the pairs of a whamd_edit_distance_batch.  Any out pointer may be NULL. */
+whamd_status_t whamd_debug_realign_walk_counts(const whamd_realign_alignments_view* alignments, const whamd_realign_variants_view* variants,
+                                               const whamd_realign_reference_view* reference, const whamd_realign_params* params,
+                                               uint64_t* n_jobs_out, uint64_t* n_long_out, uint32_t* max_target_long_out);
+whamd_status_t whamd_debug_edit_distance_long_counts(uint64_t n_pairs, const uint64_t* query_ptr, const uint64_t* target_ptr, uint64_t* n_long_out,
+                                                     uint32_t* max_target_long_out);
+
 /* HOST-ONLY DIAGNOSTIC of polyphase read scoring (csrc/polyscore.cpp): the same matrices, term tables and windows as whamd_poly_score,
  * then the pair loop on one CPU thread with the device's arithmetic -- the device's bit-exact reference and what the CPU test-suite
  * compares with the recorded reference; never what the product calls.  Read with the whamd_poly_score_* getters of the debug library. */

@@ -10,7 +10,11 @@ whatshap.vcf / whatshap.bam and whatshap.core (none of which ReadSetReader.reali
   (b) "groups": detect_alleles_by_alignment over synthetic references, variants (SNV, indels up to 30 bp, MNV, multi-allelic, symbolic,
                 two at one position) and alignments with every CIGAR operation, overhang 3 / 10 / 25, both cost models, restricted
                 genotypes; every read's yields, or the exception the reference raised for it ("errors").
-Usage: python tests/golden/make_realign_golden.py [/path/to/reference]
+and, to tests/golden/realign_edge_cases.json.gz:
+  (c) edit_distance / edit_distance_affine_gap of every pair of tests/realign_cases.py edge_pairs() (query words 63 | 64 | 65 and
+      127 | 128 | 129, the same for the target's carry words, targets at 1364 | 1365 and 5460 | 5461, gaps beyond 2^24): the results
+      in the generator's order and a hash of the generated inputs, no sequences.
+Usage: python tests/golden/make_realign_golden.py [--edge-only] [/path/to/reference]     (--edge-only: (c) alone)
 """
 import gzip
 import importlib.util
@@ -26,6 +30,7 @@ import types
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "realign_cases.json.gz")
+OUT_EDGE = os.path.join(HERE, "realign_edge_cases.json.gz")
 
 
 def build_reference(ref_root, tmp):
@@ -243,13 +248,33 @@ def make_error_groups(variants_mod):
     return cases
 
 
+def write_edge(align):
+    """tests/golden/realign_edge_cases.json.gz: both distances of the reference for every pair of realign_cases.edge_pairs() -- the results
+    and a hash of the generated inputs, no sequences."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import realign_cases
+
+    pairs = realign_cases.edge_pairs()
+    data = {"sha256": realign_cases.edge_hash(pairs), "n": len(pairs),
+            "unit": [align.edit_distance(p["q"], p["t"]) for p in pairs],
+            "affine": [align.edit_distance_affine_gap(p["q"], p["t"], p["costs"], p["gap"][0], p["gap"][1]) for p in pairs]}
+    with open(OUT_EDGE, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as f:   # (no time stamp: the same bytes on every run)
+        f.write(json.dumps(data, separators=(",", ":")).encode())
+    print(f"{OUT_EDGE}: {len(pairs)} pairs, {os.path.getsize(OUT_EDGE)} bytes")
+
+
 def main():
-    ref_root = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("WHATSHAP_REFERENCE", "/root/reference")
+    args = [a for a in sys.argv[1:] if a != "--edge-only"]
+    edge_only = len(args) != len(sys.argv) - 1   # --edge-only: leave realign_cases.json.gz as it is
+    ref_root = args[0] if args else os.environ.get("WHATSHAP_REFERENCE", "/root/reference")
     if not os.path.isdir(os.path.join(ref_root, "whatshap")):
         sys.exit(f"no reference tree at {ref_root}")
     tmp = tempfile.mkdtemp(prefix="realign_ref_")
     try:
         align, variants_mod = build_reference(ref_root, tmp)
+        write_edge(align)
+        if edge_only:
+            return
         rng = random.Random(20261015)
         pairs = make_pairs(rng, align)
         groups = []

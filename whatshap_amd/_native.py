@@ -154,6 +154,12 @@ class RealignStats(Record):
         (name, C.c_double) for name in ("host_walk_ms", "upload_ms", "kernel_ms", "download_ms", "host_finish_ms", "total_ms")]
 
 
+class DebugRealignShape(Record):
+    """whamd_debug_realign_shape (include/whatshap_amd_debug.h): the launch of realign's long jobs."""
+    _fields_ = [("blocks", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64), ("carry_words", C.c_uint32),
+                ("row_floats", C.c_uint32), ("global_rows", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PolyMatrixView(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("position", C.POINTER(C.c_int64)), ("allele", C.POINTER(C.c_int8))]
 
@@ -413,6 +419,13 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_edit_distance_host.restype = C.c_int
     L.whamd_debug_edit_distance_host.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
                                                  C.c_int, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    L.whamd_debug_realign_long_shape.restype = C.c_int
+    L.whamd_debug_realign_long_shape.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(DebugRealignShape)]
+    L.whamd_debug_realign_walk_counts.restype = C.c_int
+    L.whamd_debug_realign_walk_counts.argtypes = [C.POINTER(RealignAlignmentsView), C.POINTER(RealignVariantsView), C.POINTER(RealignReferenceView),
+                                                  C.POINTER(RealignParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    L.whamd_debug_edit_distance_long_counts.restype = C.c_int
+    L.whamd_debug_edit_distance_long_counts.argtypes = [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.whamd_debug_poly_score_host.restype = C.c_int
     L.whamd_debug_poly_score_host.argtypes = [C.POINTER(PolyMatrixView), C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_void_p)]
     L.whamd_debug_progeny_score_host.restype = C.c_int

@@ -9,8 +9,10 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/whatshap_amd_debug.h"
 #include "api_guard.h"
 #include "debug_build.h"
+#include "realign_shape.h"
 
 using namespace whamd;
 
@@ -506,6 +508,50 @@ whamd_status_t whamd_debug_edit_distance_host(uint64_t n_pairs, const uint64_t* 
 			auto ca = [&](uint32_t i) { return c[i]; };
 			distance_out[p] = use_affine ? host_affine(qa, m, ta, n, ca, gap_start, gap_extend) : host_edit_distance(qa, m, ta, n);
 		}
+		return WHAMD_OK;
+	});
+}
+
+whamd_status_t whamd_debug_realign_long_shape(int use_affine, uint64_t n_long, uint32_t max_target, whamd_debug_realign_shape* out) {
+	return guarded([&]() -> whamd_status_t {
+		if (!out) return fail(WHAMD_ERR_INVALID, "null argument");
+		const LongShape s = long_shape(use_affine != 0, n_long, max_target);
+		out->blocks = s.blocks;
+		out->block = s.block;
+		out->lds_bytes = s.lds;
+		out->scratch_bytes = s.scratch;
+		out->carry_words = s.carry_words;
+		out->row_floats = s.row_floats;
+		out->global_rows = s.global_rows ? 1 : 0;
+		out->reserved = 0;
+		return WHAMD_OK;
+	});
+}
+
+whamd_status_t whamd_debug_realign_walk_counts(const whamd_realign_alignments_view* alignments, const whamd_realign_variants_view* variants,
+                                               const whamd_realign_reference_view* reference, const whamd_realign_params* params,
+                                               uint64_t* n_jobs_out, uint64_t* n_long_out, uint32_t* max_target_long_out) {
+	return guarded([&]() -> whamd_status_t {
+		if (!alignments || !variants || !reference || !params) return fail(WHAMD_ERR_INVALID, "null argument");
+		RealignBatch b;
+		std::string msg;
+		const whamd_status_t st = realign_walk(*alignments, *variants, *reference, *params, b, msg);
+		if (st != WHAMD_OK) return fail(st, msg);
+		if (n_jobs_out) *n_jobs_out = b.n_jobs;
+		if (n_long_out) *n_long_out = b.n_long;
+		if (max_target_long_out) *max_target_long_out = b.max_target_long;
+		return WHAMD_OK;
+	});
+}
+
+whamd_status_t whamd_debug_edit_distance_long_counts(uint64_t n_pairs, const uint64_t* query_ptr, const uint64_t* target_ptr, uint64_t* n_long_out,
+                                                     uint32_t* max_target_long_out) {
+	return guarded([&]() -> whamd_status_t {
+		if (n_pairs && (!query_ptr || !target_ptr)) return fail(WHAMD_ERR_INVALID, "null argument");
+		std::vector<uint32_t> long_pairs;
+		const uint32_t max_t = n_pairs ? long_pairs_of(n_pairs, query_ptr, target_ptr, long_pairs) : 0;
+		if (n_long_out) *n_long_out = long_pairs.size();
+		if (max_target_long_out) *max_target_long_out = max_t;
 		return WHAMD_OK;
 	});
 }

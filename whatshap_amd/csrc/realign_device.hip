@@ -13,7 +13,9 @@
 //                 first lane of the next one, in LDS when it fits (targets up to 5 460 bytes), else in a global scratch row of the wave.
 //   long jobs     only jobs whose query is longer than 64 need a scratch row (Myers carry, Gotoh strip boundary).  They run in a launch of
 //                 their own, whose rows are sized by their longest allele window and whose grid is capped by the scratch budget; the
-//                 launch over all other jobs needs no scratch at all.
+//                 launch over all other jobs needs no scratch at all.  The shape of that launch is long_shape() of realign_shape.h: affine,
+//                 four waves per workgroup with one LDS row each while the longest window is at most 1 364 bytes, one wave with one LDS
+//                 row up to 5 460 (65 532 bytes), one wave with a global row beyond; unit, 64 lanes with 2 ceil(window / 64) carry words each.
 //   decision      realign (variants.py:866-891): distances of the allowed alleles in index order, stable order by distance, the first
 //                 allele iff it is alone or strictly best; quality 30 (unit) or d0 - d1 / d0 (affine).
 // Only the per-job result (allele or -1, and the quality in affine mode) goes back to the host.
@@ -27,6 +29,7 @@
 
 #include "device_runtime.h"
 #include "realign.h"
+#include "realign_shape.h"
 
 namespace whamd {
 namespace {
@@ -295,41 +298,7 @@ __global__ void __launch_bounds__(256) distance_affine_kernel(PairArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- host driver
-constexpr uint32_t BLOCK = 256, MAX_BLOCKS = 8192, MAX_LONG_BLOCKS = 1024;
-constexpr size_t LDS_LIMIT = 64 << 10;
-constexpr size_t SCRATCH_BUDGET = (size_t)512 << 20;   // scratch rows of the long-job launch: the grid shrinks to stay within this (at least one block)
-
-// Launch shape of the jobs with a query longer than 64 whose longest allele window is `max_target` bytes.
-struct LongShape {
-	uint32_t blocks = 0, block = 64;
-	size_t lds = 0;           // dynamic LDS per block (affine rows in LDS)
-	size_t scratch = 0;       // bytes of global scratch (unit carry rows, or affine rows that do not fit in LDS)
-	uint32_t carry_words = 0, row_floats = 0;
-	bool global_rows = false;
-};
-LongShape long_shape(bool affine, uint64_t n_long, uint32_t max_target) {
-	LongShape s;
-	if (n_long == 0) return s;   // no second launch
-	if (affine) {
-		s.row_floats = 3 * (max_target + 1);
-		const size_t row = (size_t)s.row_floats * 4;
-		s.block = row * 4 <= LDS_LIMIT ? 256 : 64;
-		s.global_rows = row > LDS_LIMIT;
-		const uint64_t waves = s.block / 64;
-		uint64_t blocks = std::min<uint64_t>((n_long + waves - 1) / waves, MAX_LONG_BLOCKS);
-		if (s.global_rows) blocks = std::max<uint64_t>(1, std::min<uint64_t>(blocks, SCRATCH_BUDGET / row));
-		s.blocks = (uint32_t)blocks;
-		s.lds = s.global_rows ? 0 : row * waves;
-		s.scratch = s.global_rows ? row * blocks : 0;
-	} else {
-		s.carry_words = 2 * ((std::max(max_target, 1u) + 63) / 64);
-		const size_t per_block = (size_t)s.block * s.carry_words * 8;
-		s.blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((n_long + s.block - 1) / s.block, MAX_LONG_BLOCKS),
-		                                                              SCRATCH_BUDGET / per_block));
-		s.scratch = per_block * s.blocks;
-	}
-	return s;
-}
+constexpr uint32_t BLOCK = 256, MAX_BLOCKS = 8192;   // (the long jobs' launch: realign_shape.h)
 
 }  // namespace
 
@@ -426,16 +395,12 @@ whamd_status_t edit_distance_device(uint64_t n_pairs, const uint64_t* query_ptr,
                                     const uint8_t* target, int use_affine, const float* mismatch_cost, int32_t gap_start, int32_t gap_extend,
                                     int device, int64_t* distance_out, std::string& msg) {
 	if (n_pairs >= UINT32_MAX) { msg = "too many pairs for one call"; return WHAMD_ERR_INVALID; }
-	uint32_t max_t_long = 0;
-	std::vector<uint32_t> long_pairs;
 	for (uint64_t p = 0; p < n_pairs; ++p) {
 		if (query_ptr[p + 1] < query_ptr[p] || target_ptr[p + 1] < target_ptr[p]) { msg = "query_ptr / target_ptr must not decrease"; return WHAMD_ERR_INVALID; }
 		if (target_ptr[p + 1] - target_ptr[p] >= UINT32_MAX || query_ptr[p + 1] - query_ptr[p] >= UINT32_MAX) { msg = "sequence too long"; return WHAMD_ERR_INVALID; }
-		if (query_ptr[p + 1] - query_ptr[p] > 64) {
-			long_pairs.push_back((uint32_t)p);
-			max_t_long = (uint32_t)std::max<uint64_t>(max_t_long, target_ptr[p + 1] - target_ptr[p]);
-		}
 	}
+	std::vector<uint32_t> long_pairs;
+	const uint32_t max_t_long = long_pairs_of(n_pairs, query_ptr, target_ptr, long_pairs);
 	Session s;
 	WHAMD_TRY(s.open(device, 0, msg));   // (no events: the call reports no times)
 	const uint64_t nq = query_ptr[n_pairs], nt = target_ptr[n_pairs], n_long = long_pairs.size();

@@ -200,6 +200,43 @@ def _distance_call(queries, targets, costs, gap_start, gap_extend, device, host)
     return out[:n]
 
 
+def debug_long_shape(use_affine: bool, n_long: int, max_target: int) -> dict:
+    """TEST INFRASTRUCTURE (debug library, no device): the launch shape of n_long jobs with a query longer than 64 whose longest allele
+    window is max_target bytes -- blocks (0: no second launch), block, lds_bytes, scratch_bytes, carry_words, row_floats, global_rows."""
+    L = _native.debug_lib()
+    shape = _native.DebugRealignShape()
+    _native._check(L.whamd_debug_realign_long_shape(C.c_int(1 if use_affine else 0), C.c_uint64(int(n_long)), C.c_uint32(int(max_target)), C.byref(shape)), L)
+    return shape.as_dict()
+
+
+def debug_walk_counts(variants, alignments, reference, restricted_genotypes=None, overhang: int = 10, use_affine: bool = False, gap_start=None,
+                      gap_extend=None, default_mismatch=None, first_variant=None) -> dict:
+    """TEST INFRASTRUCTURE (debug library, no device): what detect_alleles_batch's host walk counts on these inputs -- n_jobs, n_long (jobs
+    with a query longer than 64) and max_target_long (their longest allele window), which decide the second launch."""
+    L = _native.debug_lib()
+    var = _Variants(variants, restricted_genotypes)
+    al = _Alignments(alignments, first_variant)
+    ref = reference if isinstance(reference, _Reference) else _Reference(reference)
+    params = _params(overhang, use_affine, gap_start, gap_extend, default_mismatch)
+    n_jobs, n_long, max_t = C.c_uint64(), C.c_uint64(), C.c_uint32()
+    st = L.whamd_debug_realign_walk_counts(C.byref(al.view), C.byref(var.view), C.byref(ref.view), C.byref(params), C.byref(n_jobs), C.byref(n_long),
+                                           C.byref(max_t))
+    if st != _native.WHAMD_OK:
+        _raise(L, st)
+    return {"n_jobs": n_jobs.value, "n_long": n_long.value, "max_target_long": max_t.value}
+
+
+def debug_pair_counts(pairs) -> dict:
+    """TEST INFRASTRUCTURE (debug library, no device): n_long and max_target_long of an edit_distance*_batch over these (query, target, ...)."""
+    pairs = list(pairs)
+    L = _native.debug_lib()
+    qptr, _, tptr, _ = _pairs_arrays([p[0] for p in pairs], [p[1] for p in pairs])
+    n_long, max_t = C.c_uint64(), C.c_uint32()
+    _native._check(L.whamd_debug_edit_distance_long_counts(C.c_uint64(len(pairs)), _native._ptr(qptr, C.c_uint64), _native._ptr(tptr, C.c_uint64),
+                                                           C.byref(n_long), C.byref(max_t)), L)
+    return {"n_long": n_long.value, "max_target_long": max_t.value}
+
+
 def edit_distance_batch(pairs, device: int = 0, host: bool = False) -> np.ndarray:
     """edit_distance(s, t) for many (s, t) pairs in one device call."""
     pairs = list(pairs)
