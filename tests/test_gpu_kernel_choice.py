@@ -375,10 +375,16 @@ def test_batched_runs_of_many_components(symmetry):
 def test_lds_resident_runs(symmetry):
     """Path "resident": resident_segment<false, SYM> of a single individual; resident_segment_ped<false> of a short trio and <false, true> of one long
     enough for the chunked backtrace."""
+    def largest_run_lds():   # what the launches of the table solved last asked for, against what the plan check approved (res_segment_lds_bytes on both sides)
+        return max(r["lds"] for r in LAST_LEDGER if r["site"] == "run")
+
     names, _ = solve_and_check(single(120, 13, 90), ("resident single", 120), path="resident", symmetry=symmetry)   # (two workgroups per run)
     assert f"resident_segment<false, {_b(symmetry)}>" in names, names
-    short, _ = solve_and_check(synthetic_block(n_variants=120, coverage=8, seed=91, trio=True), ("resident trio", 120), path="resident", symmetry=symmetry)
+    assert largest_run_lds() == _native.plan_summary(single(120, 13, 90), "resident")["max_lds_bytes"]
+    trio = synthetic_block(n_variants=120, coverage=8, seed=91, trio=True)
+    short, _ = solve_and_check(trio, ("resident trio", 120), path="resident", symmetry=symmetry)
     assert "resident_segment_ped<false>" in short, short
+    assert largest_run_lds() == _native.plan_summary(trio, "resident")["max_lds_bytes"]
     long, stats = solve_and_check(synthetic_block(n_variants=2000, coverage=8, seed=92, trio=True), ("resident trio", 2000), path="resident", symmetry=symmetry)
     assert "resident_segment_ped<false, true>" in long and stats["bt_chunks"] > 0, (long, stats)
     TESTS_RUN.add(f"test_lds_resident_runs[{symmetry}]")

@@ -8,15 +8,13 @@
 #include <stdexcept>
 #include <string>
 
-#include "api_guard.h"
+#include "c_api.h"
 #include "debug_build.h"
 #ifdef WHAMD_DEBUG_BUILD
 #include "../../include/whatshap_amd_debug.h"
 #endif
 #include "device_runtime.h"
-#include "device_table.h"
 #include "genotype.h"
-#include "genotype_plan.h"
 #include "heuristic.h"
 #include "host_parallel.h"
 #include "problem.h"
@@ -26,17 +24,6 @@
 #include <vector>
 
 using namespace whamd;
-
-struct whamd_dptable {
-	Problem problem;
-	Solution solution;
-	DeviceTable device;
-	whamd_solve_stats stats{};
-	int device_index = 0;
-	bool uploaded = false;
-	bool solved = false;
-	bool in_flight = false;
-};
 
 namespace {
 
@@ -84,9 +71,8 @@ whamd_status_t create_table(const whamd_readset_view* readset, const uint32_t* r
 		if (!keys[i] || !values[i]) return fail(WHAMD_ERR_INVALID, "null option");
 		if (std::string(keys[i]) == "host_threads") whamd::host_threads_override() = (uint32_t)std::max(0, std::atoi(values[i]));
 	}
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0,
-	                                  positions, n_positions, t->problem, msg, /*columns_only=*/false, /*lazy_fact_terms=*/true);
-	if (st != WHAMD_OK) return fail(st, msg);
+	whamd_status_t st = ProblemInputs{readset, recombcost, n_recombcost, pedigree, distrust_genotypes, positions, n_positions}.build(t->problem, /*columns_only=*/false, /*lazy_fact_terms=*/true);
+	if (st != WHAMD_OK) return st;
 	const double t1 = now_ms();
 	t->device_index = device;
 	t->device.set_thread_budget(whamd::host_threads_override() != 0);   // (a caller that caps a create's threads runs many tables: no preview)
@@ -485,6 +471,7 @@ whamd_status_t whamd_dptable_set_option(whamd_dptable* t, const char* key, const
 	return apply_option(t, key, value);
 }
 
+// The planner the table would take for `path`, and that planner's own check of what it planned (slot_plan.cpp, resident_plan.cpp).
 whamd_status_t whamd_plan_summarize(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
                                     const whamd_pedigree_view* pedigree, int distrust_genotypes,
                                     const uint32_t* positions, size_t n_positions, const char* path,
@@ -492,422 +479,30 @@ whamd_status_t whamd_plan_summarize(const whamd_readset_view* readset, const uin
 	return guarded([&]() -> whamd_status_t {
 	if (!out) return fail(WHAMD_ERR_INVALID, "out is NULL");
 	Problem p;
-	std::string msg;
 	const double tb0 = now_ms();
 	const std::string mode(path ? path : "auto");
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions,
-	                                  n_positions, p, msg, /*columns_only=*/mode == "genotype_slots");
-	if (st != WHAMD_OK) return fail(st, msg);
+	if (whamd_status_t st = ProblemInputs{readset, recombcost, n_recombcost, pedigree, distrust_genotypes, positions, n_positions}.build(p, /*columns_only=*/mode == "genotype_slots")) return st;
 	SlotPlan sp;
 	if (mode == "genotype_slots") {
-		// the run plan of the genotyping path (genotype_slots.hip): every column must lie in a run, or the per-column kernels take over
-		whamd_plan_summary s{};
-		s.n_columns = p.n_cols;
-		s.max_coverage = p.max_k;
-		if (plan_forward_slots(p, 0, 0, sp, 0, /*genotype_mode=*/true)) {
-			s.n_steps = sp.steps.size();
-			s.n_runs = sp.runs.size();
-			bool ok = true;
-			uint32_t expect = 0;
-			for (const Step& step : sp.steps) {
-				if (step.kind != 2) {
-					if (debug_env("WHAMD_DEBUG_PLAN")) fprintf(stderr, "[plan] genotype: column %u outside runs (k=%u b=%u f=%u, next k=%u)\n", step.index, p.k[step.index], p.b[step.index], p.f[step.index], step.index + 1 < p.n_cols ? p.k[step.index + 1] : 0);
-					ok = ok && step.index == expect; expect = step.index + 1; continue;
-				}
-				const SlotRun& run = sp.runs[step.index];
-				ok = ok && run.c0 == expect && run.lr == 0 && !run.half && run.ncols >= 1 && run.ncols <= (uint32_t)PSLOT_MAXCOLS;
-				expect = run.c0 + run.ncols;
-				s.n_resident_columns += run.ncols;
-				s.max_run_columns = std::max<uint64_t>(s.max_run_columns, run.ncols);
-				s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << run.g);
-				uint32_t starts = 0, ends = 0;
-				for (uint32_t i = 0; i < run.ncols; ++i) {
-					const PedSlotRow& pr = sp.prows[run.c0 + i];
-					const uint32_t c = run.c0 + i;
-					ok = ok && pr.pad[0] == (uint32_t)p.k[c] - (i == 0 ? p.b[run.c0] : p.b[c]) && pr.pad[1] == starts;
-					ok = ok && pr.n_end == (c + 1 == p.n_cols ? 0u : (uint32_t)p.k[c] - p.f[c]) && sp.bt_cols[c].kf == ends;
-					starts += pr.pad[0];
-					ends += pr.n_end;
-				}
-			}
-			ok = ok && expect == p.n_cols;
-			s.invariants_ok = ok ? 1 : 0;
-		}
-		*out = s;
+		*out = whamd_plan_summary{};   // (a table outside the run path: its size and nothing else, invariants_ok 0)
+		out->n_columns = p.n_cols;
+		out->max_coverage = p.max_k;
+		if (plan_forward_slots(p, 0, 0, sp, 0, /*genotype_mode=*/true)) check_genotype_slot_plan(p, sp, *out);
 		return WHAMD_OK;
 	}
 	const double tp0 = now_ms();
 	const bool slots_ok = (mode == "auto" || mode == "slots") && plan_forward_slots(p, 11, 1, sp);
 	if (getenv("WHAMD_DEBUG_TIMING")) fprintf(stderr, "[whamd timing] plan_summarize: build_problem %.1f ms, plan_forward_slots %.1f ms\n", tp0 - tb0, now_ms() - tp0);
 	if (slots_ok) {
-		// slot runs (slots.h): every column in exactly one step, runs within their limits, slots consistent
-		whamd_plan_summary s{};
-		s.n_columns = p.n_cols;
-		s.n_steps = sp.steps.size();
-		s.n_runs = sp.runs.size();
-		s.max_coverage = p.max_k;
-		s.n_components = sp.component_first_step.size();
-		bool ok = true;
-		uint32_t expect = 0;
-		size_t kc = 0;
-		for (size_t si = 0; si < sp.steps.size(); ++si) {
-			const Step& step = sp.steps[si];
-			const uint32_t c0 = step.kind == 2 ? sp.runs[step.index].c0 : step.index;
-			if (!sp.ped && (si == 0 || p.b[c0] == 0)) { ok = ok && kc < sp.component_first_step.size() && sp.component_first_step[kc] == si; ++kc; }
-			ok = ok && c0 == expect;
-			if (step.kind == 0) { expect = c0 + 1; ok = ok && sp.col_to_row[c0] < 0; continue; }
-			const SlotRun& run = sp.runs[step.index];
-			expect = c0 + run.ncols;
-			ok = ok && step.kind == 2 && run.ncols >= 2 && run.ncols <= (uint32_t)(sp.ped ? PSLOT_MAXCOLS : SLOT_MAXCOLS) && run.g <= (uint32_t)SLOT_GMAX;
-			if (sp.ped) {
-				const PedSlotExtra& ex = sp.pextra[step.index];
-				ok = ok && sp.pextra.size() == sp.runs.size() && run.lr == 0 && !run.half && (1u << ex.tb) == p.T && run.L == 6u - ex.tb + run.lw;
-				ok = ok && (ex.nf == 2 || ex.nf == 4 || ((ex.nf == 16 || ex.nf == (uint32_t)PSLOT_FACT) && ex.tb == 2) || (ex.nf == (uint32_t)PSLOT_FACT4 && ex.tb == 4)) && ex.fwn == run.ncols * pslot_ta(ex.nf, p.T) * pslot_na(ex.nf) && ex.fwn <= (uint32_t)PSLOT_FORMWORDS && ex.rec_words == ((run.ncols + 3) / 4) * run.threads;
-				ok = ok && run.lw <= (uint32_t)SLOT_LWMAX && run.threads == (64u << run.lw);
-			} else
-			ok = ok && run.lr >= 1 && run.lr <= (uint32_t)SLOT_LR && run.L == run.lr + (uint32_t)SLOT_LANE + run.lw && run.lw <= (uint32_t)SLOT_LWMAX && run.threads == (64u << run.lw);
-			ok = ok && run.L + run.g <= (uint32_t)SLOT_MAXSLOTS && run.n_ends <= (uint32_t)SLOT_MAXENDS_RUN && (!run.half || run.g >= 1);
-			uint32_t ends = 0;
-			for (uint32_t i = 0; i < run.ncols && ok; ++i) {
-				const uint32_t c = c0 + i;
-				if (c + 1 >= p.n_cols) { ok = false; break; }   // the last column never runs inside a run
-				ok = ok && sp.col_to_row[c] == (int32_t)(run.row_off + i) && (i == 0 || p.b[c] != 0);
-				const uint32_t row_n_end = sp.ped ? sp.prows[run.row_off + i].n_end : sp.rows[run.row_off + i].n_end;
-				const SlotBtCol& bc = sp.bt_cols[run.row_off + i];
-				ok = ok && bc.k == p.k[c] && bc.kf == ends && row_n_end == (uint32_t)p.k[c] - p.f[c] && row_n_end <= (uint32_t)(sp.ped ? PSLOT_MAXEND : SLOT_MAXEND);
-				if (sp.ped && sp.pextra[step.index].nf == (uint32_t)PSLOT_FACT) ok = ok && p.fterm_kind == 1 && p.fterms.size() == (size_t)p.n_cols * p.T * 16;
-				else if (sp.ped && sp.pextra[step.index].nf == (uint32_t)PSLOT_FACT4) ok = ok && p.fterm_kind == 2 && p.fterms.size() == (size_t)p.n_cols * PSLOT_FSTRIDE4;
-				else if (sp.ped) for (uint32_t t = 0; t < p.T; ++t) ok = ok && p.term_end(c, t) - p.term_begin(c, t) <= sp.pextra[step.index].nf;
-				uint32_t used = 0;
-				for (uint32_t j = 0; j < bc.k; ++j) {   // distinct slots, ending reads local
-					ok = ok && bc.slot[j] < run.L + run.g && !((used >> bc.slot[j]) & 1u);
-					used |= 1u << bc.slot[j];
-					if (!((p.fwd_mask[c] >> j) & 1u)) ok = ok && bc.slot[j] < run.L;
-				}
-				for (uint32_t q = 0; q < row_n_end; ++q) {
-					const uint32_t es = sp.ped ? (uint32_t)(q < 3u ? bc.slot[25 + q] : bc.pad[1]) : (sp.rows[run.row_off + i].end[q].info & 255u);
-					ok = ok && sp.end_slots[sp.end_off[step.index] + ends + q] == es;
-				}
-				ends += row_n_end;
-			}
-			ok = ok && ends == run.n_ends;
-			s.max_run_columns = std::max<uint64_t>(s.max_run_columns, run.ncols);
-			s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << (run.g - run.half));
-			if (sp.ped) {
-				const PedSlotExtra& ex = sp.pextra[step.index];
-				s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, pedslot_lds_bytes(run.threads, run.ncols, ex));
-				if (pslot_is_fact(ex.nf)) s.n_fact_runs++;
-				s.backtrace_bytes += ((uint64_t)ex.rec_words * 4) << run.g;
-			} else {
-				s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, slot_run_lds_bytes(run.threads, run.lr, run.ncols));
-				s.backtrace_bytes += (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half));
-			}
-			if (run.half) s.n_halved_runs++;
-			if (run.yflags & 1u) s.n_yform_runs++;
-			s.n_resident_columns += run.ncols;
-			s.n_vectorised_columns += run.ncols;
-		}
-		ok = ok && expect == p.n_cols && kc == sp.component_first_step.size();
-		s.invariants_ok = ok ? 1 : 0;
-		*out = s;
+		check_slot_plan(p, sp, *out);
 		return WHAMD_OK;
 	}
 	ResidentPlan plan;
 	plan_forward(p, mode == "auto" || mode == "resident", 11, true, plan);
-	whamd_plan_summary s{};
-	s.n_columns = p.n_cols;
-	s.n_steps = plan.steps.size();
-	s.n_runs = plan.segments.size();
-	s.max_coverage = p.max_k;
-	s.n_components = plan.component_first_step.size();
-	bool ok = true;
-	// components: boundaries are exactly the steps whose first column no read enters, and no run spans one
-	if (!plan.component_first_step.empty()) {
-		size_t k = 0;
-		for (size_t si = 0; si < plan.steps.size(); ++si) {
-			const Step& step = plan.steps[si];
-			const uint32_t c0 = step.kind == 1 ? plan.segments[step.index].c0 : step.index;
-			const bool boundary = si == 0 || p.b[c0] == 0;
-			if (boundary) { ok = ok && k < plan.component_first_step.size() && plan.component_first_step[k] == si; ++k; }
-			if (step.kind == 1)
-				for (uint32_t i = 1; i < plan.segments[step.index].ncols; ++i) ok = ok && p.b[c0 + i] != 0;
-		}
-		ok = ok && k == plan.component_first_step.size();
-	}
-	std::vector<uint8_t> seen(p.n_cols, 0);
-	uint32_t expect = 0;
-	for (const Step& step : plan.steps) {
-		if (step.kind == 0) {
-			ok = ok && step.index == expect && step.index < p.n_cols;
-			if (step.index < p.n_cols) seen[step.index]++;
-			expect = step.index + 1;
-			continue;
-		}
-		const ResSegment& sg = plan.segments[step.index];
-		ok = ok && sg.c0 == expect && sg.ncols >= 2 && sg.ncols <= (uint32_t)RES_MAXCOLS && sg.g <= (uint32_t)RES_GMAX;
-		expect = sg.c0 + sg.ncols;
-		uint64_t stage = 0;
-		for (uint32_t i = 0; i < sg.ncols; ++i) {
-			const uint32_t c = sg.c0 + i;
-			if (c >= p.n_cols) { ok = false; break; }
-			seen[c]++;
-			const ResColumn& rc = plan.columns[sg.col_off + i];
-			ok = ok && plan.col_to_res[c] == (int32_t)(sg.col_off + i);
-			ok = ok && rc.Lb == p.b[c] - sg.g && rc.Lf == p.f[c] - sg.g && rc.ebits == (uint32_t)p.k[c] - p.f[c];
-			const uint32_t lmax = sg.kind == 1 ? (uint32_t)PED_LMAX : (uint32_t)RES_LMAX;
-			ok = ok && rc.Lb <= lmax && rc.Lf <= lmax && rc.ebits <= (uint32_t)RES_EMAX;
-			ok = ok && rc.stage_off == stage;
-			stage += sg.kind == 1 ? (uint64_t)rc.nwords : (uint64_t)rc.ebits * rc.nwords;
-			if (rc.mode == RES_MODE_FOLDED) { s.n_folded_columns++; ok = ok && i + 1 < sg.ncols && rc.ebits == 0; }
-			if (rc.mode != RES_MODE_GENERIC) s.n_vectorised_columns++;
-			if (rc.nfold) ok = ok && rc.nfold <= RES_MAXFOLD && i >= rc.nfold;
-			ok = ok && c + 1 < p.n_cols;  // the last column never runs resident
-		}
-		ok = ok && stage == sg.stage_words;
-		const uint64_t lds = sg.kind == 1
-			? (((uint64_t)sg.ncols * (PED_LDSWORDS + PED_TABLE) + (uint64_t)sg.n_terms * 2 + 3) & ~3ull) * 4 + 2 * (16ull << sg.max_l) + (uint64_t)sg.stage_words * 8
-			: (uint64_t)sg.ncols * (64 + RES_TABLE) * 4 + 2 * (4ull << sg.max_l) + (uint64_t)sg.stage_words * 8;
-		ok = ok && lds <= 160 * 1024;
-		s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, lds);
-		s.max_run_columns = std::max<uint64_t>(s.max_run_columns, sg.ncols);
-		s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << (sg.g - sg.half));  // launched workgroups
-		if (sg.half) s.n_halved_runs++;
-		s.n_resident_columns += sg.ncols;
-		s.backtrace_bytes += (uint64_t)sg.stage_words * (1ull << sg.g) * 8;
-	}
-	ok = ok && expect == p.n_cols;
-	for (uint32_t c = 0; c < p.n_cols; ++c) ok = ok && seen[c] == 1;
-	s.invariants_ok = ok ? 1 : 0;
-	*out = s;
+	check_resident_plan(p, plan, *out);
 	return WHAMD_OK;
 	});
 }
-
-#ifdef WHAMD_DEBUG_BUILD   // libwhatshap_amd_debug.so only (include/whatshap_amd_debug.h): test infrastructure
-whamd_status_t whamd_debug_emulate_slot_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                            const whamd_pedigree_view* pedigree, int distrust_genotypes, const uint32_t* positions,
-                                            size_t n_positions, int slot_l, int symmetry, uint32_t* index_out, uint32_t* score_out,
-                                            uint64_t* n_run_columns_out) {
-	return guarded([&]() -> whamd_status_t {
-	const int lr = slot_l >= 200 ? 1 : slot_l >= 100 ? 3 : 2;   // slot_l + 100: 8 cells per thread, + 200: 2 cells per thread
-	if (slot_l >= 100) slot_l -= slot_l >= 200 ? 200 : 100;
-	Problem p;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions,
-	                                  n_positions, p, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	SlotPlan sp;
-	if (p.T != 1 || !plan_forward_slots(p, slot_l, symmetry, sp, lr)) return fail(WHAMD_ERR_UNSUPPORTED, "slot runs apply to a single individual only");
-	std::vector<uint32_t> path;
-	uint32_t score = 0;
-	if (!emulate_slot_plan(p, sp, path, score, msg)) return fail(WHAMD_ERR_INVALID, "slot plan inconsistent: " + msg);
-	if (index_out && !path.empty()) std::memcpy(index_out, path.data(), path.size() * sizeof(uint32_t));
-	if (score_out) *score_out = score;
-	if (n_run_columns_out) *n_run_columns_out = sp.n_run_columns;
-	return WHAMD_OK;
-	});
-}
-
-whamd_status_t whamd_debug_emulate_pedslot_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                               const whamd_pedigree_view* pedigree, int distrust_genotypes, const uint32_t* positions,
-                                               size_t n_positions, int slot_l, uint32_t* index_out, uint32_t* transmission_out,
-                                               uint32_t* score_out, uint64_t* n_run_columns_out) {
-	return guarded([&]() -> whamd_status_t {
-	Problem p;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions,
-	                                  n_positions, p, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	SlotPlan sp;
-	if (p.T == 1 || !plan_forward_slots(p, slot_l > 0 ? -slot_l : 0, 0, sp) || !sp.ped)
-		return fail(WHAMD_ERR_UNSUPPORTED, "pedigree slot runs apply to tables with one or two trios whose columns need at most 4 cost forms per transmission value");
-	std::vector<uint32_t> path, trans;
-	uint32_t score = 0;
-	if (!emulate_pedslot_plan(p, sp, path, trans, score, msg)) return fail(WHAMD_ERR_INVALID, "pedigree slot plan inconsistent: " + msg);
-	if (index_out && !path.empty()) std::memcpy(index_out, path.data(), path.size() * sizeof(uint32_t));
-	if (transmission_out && !trans.empty()) std::memcpy(transmission_out, trans.data(), trans.size() * sizeof(uint32_t));
-	if (score_out) *score_out = score;
-	if (n_run_columns_out) *n_run_columns_out = sp.n_run_columns;
-	return WHAMD_OK;
-	});
-}
-whamd_status_t whamd_debug_lazy_terms_check(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                            const whamd_pedigree_view* pedigree, int distrust_genotypes, const uint32_t* positions, size_t n_positions,
-                                            const uint8_t* need_in, int rounds, int* lazy_out, uint64_t* differences_out, uint64_t* built_before_out,
-                                            uint64_t* built_after_out) {
-	return guarded([&]() -> whamd_status_t {
-	Problem eager, lazy;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, eager, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, lazy, msg, false, /*lazy_fact_terms=*/true);
-	if (st != WHAMD_OK) return fail(st, msg);
-	if (lazy_out) *lazy_out = lazy.lazy_terms ? 1 : 0;
-	const uint32_t n = eager.n_cols;
-	uint64_t before = 0, after = 0, diff = 0;
-	for (uint32_t c = 0; c < n; ++c) before += lazy.term_end(c, lazy.T - 1) > lazy.term_begin(c, 0);
-	std::vector<uint8_t> need(n, 1);
-	if (need_in) for (uint32_t c = 0; c < n; ++c) need[c] = need_in[c] != 0;
-	rounds = std::max(1, rounds);
-	for (int r = 0; r < rounds; ++r) {
-		std::vector<uint8_t> part(n, 0);
-		for (uint32_t c = 0; c < n; ++c) part[c] = need[c] && (int)(c % (uint32_t)rounds) == r;
-		st = fill_lazy_terms(lazy, part, msg);
-		if (st != WHAMD_OK) return fail(st, msg);
-	}
-	for (uint32_t c = 0; c < n; ++c) {
-		after += lazy.term_end(c, lazy.T - 1) > lazy.term_begin(c, 0);
-		if (!need[c]) continue;
-		bool same = true;
-		for (uint32_t t = 0; t < eager.T && same; ++t) {
-			const uint64_t a0 = eager.term_begin(c, t), a1 = eager.term_end(c, t), b0 = lazy.term_begin(c, t), b1 = lazy.term_end(c, t);
-			same = a1 - a0 == b1 - b0;
-			for (uint64_t i = 0; same && i < a1 - a0; ++i)
-				same = eager.terms[a0 + i].c == lazy.terms[b0 + i].c && eager.terms[a0 + i].plus == lazy.terms[b0 + i].plus && eager.terms[a0 + i].minus == lazy.terms[b0 + i].minus;
-		}
-		diff += !same;
-	}
-	// what does not depend on the route: the factorised line itself and the problem's shape
-	if (eager.fterm_kind != lazy.fterm_kind || eager.fterms.size() != lazy.fterms.size()) diff += n;
-	else for (size_t i = 0; i < eager.fterms.size(); ++i) if (eager.fterms[i].c != lazy.fterms[i].c || eager.fterms[i].plus != lazy.fterms[i].plus || eager.fterms[i].minus != lazy.fterms[i].minus) { ++diff; break; }
-	if (lazy.value_bound < eager.value_bound) diff += n;   // (the lazy bound may only be LARGER: it is what rules 32-bit wrap-around out)
-	if (differences_out) *differences_out = diff;
-	if (built_before_out) *built_before_out = before;
-	if (built_after_out) *built_after_out = after;
-	return WHAMD_OK;
-	});
-}
-
-size_t whamd_debug_solve_kernels(whamd_debug_kernel* out, size_t capacity) { return DeviceTable::debug_solve_kernels(out, capacity); }
-
-whamd_status_t whamd_debug_dptable_launches(const whamd_dptable* table, whamd_debug_launch* out, size_t capacity, size_t* n_out) {
-	if (!table || !n_out) return fail(WHAMD_ERR_INVALID, "null argument");
-	if (!table->solved) return fail(WHAMD_ERR_INVALID, "the table has not been solved: its ledger is read after whamd_dptable_wait");
-	*n_out = table->device.debug_launches(out, capacity);
-	return WHAMD_OK;
-}
-
-whamd_status_t whamd_debug_dptable_preview(const whamd_dptable* table, whamd_debug_preview* out) {
-	if (!table || !out) return fail(WHAMD_ERR_INVALID, "null argument");
-	table->device.debug_preview(out);
-	return WHAMD_OK;
-}
-
-whamd_status_t whamd_debug_preview_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                        const whamd_pedigree_view* pedigree, int distrust_genotypes,
-                                        const uint32_t* positions, size_t n_positions, uint32_t pieces, whamd_debug_preview_plan_result* out,
-                                        uint64_t* rec_predicted, uint64_t* rec_laid_out, uint32_t* spec_predicted, uint32_t* spec_laid_out, size_t capacity) {
-	return guarded([&]() -> whamd_status_t {
-	if (!out) return fail(WHAMD_ERR_INVALID, "out is NULL");
-	Problem p;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, p, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	st = DeviceTable::debug_preview_plan(p, pieces, out, rec_predicted, rec_laid_out, spec_predicted, spec_laid_out, capacity, msg);
-	return st == WHAMD_OK ? WHAMD_OK : fail(st, msg);
-	});
-}
-
-whamd_status_t whamd_debug_head_first_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                           const whamd_pedigree_view* pedigree, int distrust_genotypes,
-                                           const uint32_t* positions, size_t n_positions, uint32_t head_pieces, whamd_debug_head_plan_result* out) {
-	return guarded([&]() -> whamd_status_t {
-	if (!out) return fail(WHAMD_ERR_INVALID, "out is NULL");
-	Problem p;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, distrust_genotypes != 0, positions, n_positions, p, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	if (p.T != 1) return fail(WHAMD_ERR_UNSUPPORTED, "the head hook applies to a single individual only");
-	*out = whamd_debug_head_plan_result{};
-	auto mix = [](uint64_t& h, const void* data, size_t bytes) {   // FNV-1a
-		const unsigned char* b = static_cast<const unsigned char*>(data);
-		for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
-	};
-	// the part of the plan that belongs to the runs [0, n_runs): what a launch of one of them reads, and what its backtrace reads
-	auto runs_digest = [&mix](const SlotPlan& sp, size_t n_runs) {
-		uint64_t h = 1469598103934665603ull;
-		for (size_t ri = 0; ri < n_runs; ++ri) {
-			const SlotRun& run = sp.runs[ri];
-			mix(h, &run, sizeof run);
-			mix(h, sp.rows.data() + run.row_off, (size_t)run.ncols * sizeof(SlotRow));
-			mix(h, sp.bt_cols.data() + run.row_off, (size_t)run.ncols * sizeof(SlotBtCol));
-			mix(h, sp.ctrl.data() + run.ctrl_off, (size_t)SLOT_CTRL_WORDS * 4);
-			mix(h, sp.end_slots.data() + sp.end_off[ri], run.n_ends);
-		}
-		return h;
-	};
-	SlotPlan sp;
-	SlotPlanHead head;
-	const uint32_t n_pieces = slot_plan_pieces(p.n_cols);
-	head.col_limit = slot_plan_piece_begin(p.n_cols, std::min(head_pieces, n_pieces));
-	uint32_t calls = 0, head_steps = 0;
-	uint64_t in_hook = 0;
-	head.at_head = [&](uint32_t n_head) {
-		++calls;
-		head_steps = n_head;
-		in_hook = runs_digest(sp, n_head);
-	};
-	if (!plan_forward_slots(p, 11, 1, sp, 2, false, head_pieces ? &head : nullptr)) return fail(WHAMD_ERR_UNSUPPORTED, "the table is not eligible for slot runs");
-	out->n_pieces = n_pieces;
-	out->head_steps = head_steps;
-	out->n_steps = (uint32_t)sp.steps.size();
-	out->hook_calls = calls;
-	out->head_digest_in_hook = in_hook;
-	out->head_digest = runs_digest(sp, head_steps);
-	out->n_runs = (uint32_t)sp.runs.size();
-	out->n_components = (uint32_t)sp.component_first_step.size();
-	uint64_t h = runs_digest(sp, sp.runs.size());
-	mix(h, sp.steps.data(), sp.steps.size() * sizeof(Step));
-	mix(h, sp.end_off.data(), sp.end_off.size() * 4);
-	mix(h, sp.start_slots.data(), sp.start_slots.size());
-	mix(h, sp.start_off.data(), sp.start_off.size() * 4);
-	mix(h, sp.f_exit.data(), sp.f_exit.size() * 4);
-	for (const std::vector<uint8_t>& e : sp.exit_slot) mix(h, e.data(), e.size());
-	mix(h, sp.col_to_row.data(), sp.col_to_row.size() * 4);
-	mix(h, sp.component_first_step.data(), sp.component_first_step.size() * 4);
-	mix(h, &sp.n_run_columns, sizeof sp.n_run_columns);
-	out->digest = h;
-	out->edge_yflags[0] = out->edge_yflags[1] = 0xFFFFFFFFu;
-	if (head_steps) {
-		out->edge_yflags[0] = sp.runs[head_steps - 1].yflags;
-		if (head_steps < sp.steps.size() && sp.steps[head_steps].kind == 2) out->edge_yflags[1] = sp.runs[sp.steps[head_steps].index].yflags;
-	}
-	return WHAMD_OK;
-	});
-}
-
-whamd_status_t whamd_debug_genotype_run_plan(const whamd_readset_view* readset, const uint32_t* recombcost, size_t n_recombcost,
-                                             const whamd_pedigree_view* pedigree, const uint32_t* positions, size_t n_positions,
-                                             whamd_debug_genotype_run* out, size_t capacity, size_t* n_out, double* min_total_out) {
-	return guarded([&]() -> whamd_status_t {
-	if (!n_out) return fail(WHAMD_ERR_INVALID, "n_out is NULL");
-	Problem p;
-	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, false, positions, n_positions, p, msg, /*columns_only=*/true);
-	if (st != WHAMD_OK) return fail(st, msg);
-	GenotypeModel model;
-	st = build_genotype_model(p, model, msg);
-	if (st != WHAMD_OK) return fail(st, msg);
-	GenoRunPlan pl;
-	if (!geno_plan_runs(p, model, 0, pl)) return fail(WHAMD_ERR_UNSUPPORTED, "the table is not eligible for the genotyper's run path");
-	*n_out = pl.runs.size();
-	if (min_total_out) *min_total_out = GS_MIN_TOTAL;
-	for (size_t ri = 0; out && ri < pl.runs.size() && ri < capacity; ++ri) {
-		const GsRun& r = pl.runs[ri];
-		whamd_debug_genotype_run o{};
-		o.c0 = r.c0; o.ncols = r.ncols;
-		o.rescale_f = r.n_part_in_f ? 1u : 0u; o.rescale_b = r.n_part_in_b ? 1u : 0u;
-		o.emit_f = r.emit_f; o.emit_b = r.emit_b;
-		o.n_part_out = 1u << r.g;
-		o.part_out_f = r.part_out_f; o.part_out_b = r.part_out_b;
-		o.part_in_f = r.part_in_f; o.n_part_in_f = r.n_part_in_f;
-		o.part_in_b = r.part_in_b; o.n_part_in_b = r.n_part_in_b;
-		out[ri] = o;
-	}
-	return WHAMD_OK;
-	});
-}
-#endif   // WHAMD_DEBUG_BUILD
 
 }  // extern "C"
 
@@ -1120,8 +715,8 @@ whamd_status_t whamd_genotype_likelihoods(const whamd_readset_view* readset, con
 	const double t0 = now_ms();
 	Problem p;
 	std::string msg;
-	whamd_status_t st = build_problem(readset, recombcost, n_recombcost, pedigree, false, positions, n_positions, p, msg, /*columns_only=*/true);
-	if (st != WHAMD_OK) return fail(st, msg);
+	whamd_status_t st = ProblemInputs{readset, recombcost, n_recombcost, pedigree, 0, positions, n_positions}.build(p, /*columns_only=*/true);
+	if (st != WHAMD_OK) return st;
 	const size_t need = (size_t)p.n_ind * p.n_cols * 3;
 	if (need && (!gl_out || gl_capacity < need)) return fail(WHAMD_ERR_INVALID, "gl_out holds fewer than individuals * columns * 3 values");
 	GenotypeModel model;

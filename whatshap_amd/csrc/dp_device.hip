@@ -927,7 +927,7 @@ static whamd_status_t opt_in_large_lds(int device, std::string& msg) {
 	if (device < 64 && ((attr_done >> device) & 1ull)) return WHAMD_OK;
 	size_t count = 0;
 	const void* const* kernels = large_lds_kernels(count);
-	for (size_t i = 0; i < count; ++i) HIP_TRY(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+	for (size_t i = 0; i < count; ++i) HIP_TRY(hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)CU_LDS_BYTES));
 	if (device < 64) attr_done |= 1ull << device;
 	return WHAMD_OK;
 }
@@ -1298,14 +1298,12 @@ void DeviceTable::Impl::launch_run(const ResBatchEntry& e, uint64_t& launches) {
 		return f;
 	};
 #endif
+	const size_t lds = res_segment_lds_bytes(sg);
 	if (sg.kind == 1) {
-		const size_t words = ((size_t)sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)sg.n_terms * 2 + 3) & ~(size_t)3;
-		const size_t lds_ped = words * 4 + 2 * ((size_t)16 << sg.max_l) + (size_t)sg.stage_words * 8;
 		const PedSegmentFn kernel = ped_segment_kernel(stamps, sg.in_mirror_bit && m.tp.use_chunks);
-		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, m.dev.dp, sg, e.prev, e.cur);
-		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << sg.g), dim3(sg.threads), lds_ped, rs, true, segment_facts(sg.in_mirror_bit && m.tp.use_chunks, false));
+		hipLaunchKernelGGL(kernel, dim3(1u << sg.g), dim3(sg.threads), lds, rs, m.dev.dp, sg, e.prev, e.cur);
+		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << sg.g), dim3(sg.threads), lds, rs, true, segment_facts(sg.in_mirror_bit && m.tp.use_chunks, false));
 	} else {
-		const size_t lds = (size_t)sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << sg.max_l) + (size_t)sg.stage_words * 8;
 		const SegmentFn kernel = segment_kernel(stamps, sg.half || sg.in_half || sg.mirror_out);
 		hipLaunchKernelGGL(kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, m.dev.dp, sg, e.prev, e.cur, e.score_out);
 		WHAMD_NOTE(m, WHAMD_LAUNCH_RUN, (const void*)kernel, dim3(1u << (sg.g - sg.half)), dim3(sg.threads), lds, rs, true, segment_facts(false, sg.half || sg.in_half || sg.mirror_out));

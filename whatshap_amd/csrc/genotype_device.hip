@@ -701,7 +701,7 @@ struct ColumnCall : GenotypeCall {
 		HIP_TRY(alloc((void**)&d_tables, (size_t)n * G.table_stride * sizeof(double)));
 		G.tables = d_tables;
 		table_bytes = (size_t)G.table_stride * sizeof(double);   // the step kernels copy their column's tables into LDS
-		if (table_bytes + sizeof(GenoShared) > 160 * 1024) {   // (a quartet beyond coverage ~35: never reached below the 25-read limit, but never a bare launch failure)
+		if (table_bytes + sizeof(GenoShared) > CU_LDS_BYTES) {   // (a quartet beyond coverage ~35: never reached below the 25-read limit, but never a bare launch failure)
 			msg = "lookup tables of " + std::to_string(table_bytes >> 10) + " KiB per column do not fit in LDS";
 			return WHAMD_ERR_UNSUPPORTED;
 		}
@@ -733,7 +733,7 @@ struct ColumnCall : GenotypeCall {
 	whamd_status_t launch_tables() {
 		kn = geno_column_kernels(T);
 		if (table_bytes + sizeof(GenoShared) > 64 * 1024) {
-			const int lds = 160 * 1024 - (int)sizeof(GenoShared);
+			const int lds = (int)CU_LDS_BYTES - (int)sizeof(GenoShared);
 			for (BackwardFn fn : GENO_BACKWARD) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
 			for (const auto& of_t : GENO_FORWARD)
 				for (ForwardFn fn : of_t) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));

@@ -99,9 +99,9 @@ inline size_t run_lds_bytes(uint32_t threads, uint32_t ncols, uint32_t T, uint32
 	const size_t waves = threads >> 6;
 	return ((size_t)2 * threads + waves * ncols * T * E + (size_t)ncols * T * A + ((ncols + 1) & ~1u) + 16) * 8 + (size_t)ncols * sizeof(GsCol);
 }
-// What a run kernel may take of the 160 KiB: the planner (slot_plan.cpp, genotype_mode) ends a run before it needs more -- a quartet's run of 32
+// What a run kernel may take of the 160 KiB (CU_LDS_BYTES): the planner (slot_plan.cpp, genotype_mode) ends a run before it needs more -- a quartet's run of 32
 // columns and four waves would need 197 KiB, it gets 24 columns --, geno_plan_windows refuses a plan that needs more all the same.
-constexpr size_t GS_MAX_LDS = 150 * 1024;
+constexpr size_t GS_MAX_LDS = RUN_LDS_BUDGET;
 
 // ---------------------------------------------------------------------------------------------- run path: windows
 // Runs [r0, r1) = columns [c0, c1); `words` doubles in each of the two column stores.

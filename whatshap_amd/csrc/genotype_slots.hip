@@ -687,7 +687,7 @@ struct RunCall : GenotypeCall {
 	// the kernels of this T; the run kernels take up to 160 KiB of LDS
 	whamd_status_t launch_tables() {
 		kn = geno_run_kernels(tb);
-		for (RunFn fn : {kn.fwd, kn.bwd}) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+		for (RunFn fn : {kn.fwd, kn.bwd}) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CU_LDS_BYTES));
 		return WHAMD_OK;
 	}
 

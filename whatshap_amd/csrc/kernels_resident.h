@@ -272,9 +272,10 @@ __device__ __forceinline__ void resident_segment_body(const DevProblem& P, const
 	const uint32_t tid = threadIdx.x, NT = blockDim.x;
 	const unsigned long long rt_begin = DBG ? wall_clock64() : 0ull;
 	unsigned long long t_args = 0, t_first = 0;
-	uint32_t* ldsc = smem;                                             // ncols * 64 words: column descriptors
-	int32_t* tab = reinterpret_cast<int32_t*>(smem + sg.ncols * 64);   // ncols * 256 words: lookup tables
-	uint32_t* bufP = smem + sg.ncols * (64 + RES_TABLE);
+	// (the areas in order: res_run_lds_bytes, resident.h)
+	uint32_t* ldsc = smem;                                                       // ncols * RES_LDSWORDS words: column descriptors
+	int32_t* tab = reinterpret_cast<int32_t*>(smem + sg.ncols * RES_LDSWORDS);   // ncols * RES_TABLE words: lookup tables
+	uint32_t* bufP = smem + res_slice_word(sg.ncols);
 	uint32_t* bufQ = bufP + (1u << sg.max_l);
 	uint8_t* stage = reinterpret_cast<uint8_t*>(bufQ + (1u << sg.max_l));  // backtrace record of the run (stage_words * 8 bytes)
 	// per-column scalars that depend on the workgroup index, straight from the global descriptors: 16 lanes per column

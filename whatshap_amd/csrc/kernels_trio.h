@@ -155,7 +155,7 @@ __global__ __launch_bounds__(1024) void resident_segment_ped(DevProblem P, ResSe
 	uint32_t* ldsc = smem;                                                           // ncols * PED_LDSWORDS
 	int32_t* tab = reinterpret_cast<int32_t*>(ldsc + sg.ncols * PED_LDSWORDS);       // ncols * PED_TABLE words
 	uint2* terms = reinterpret_cast<uint2*>(tab + sg.ncols * PED_TABLE);             // n_terms * 2 words
-	uint4* bufP = reinterpret_cast<uint4*>(smem + ((sg.ncols * (PED_LDSWORDS + PED_TABLE) + sg.n_terms * 2 + 3) & ~3u));
+	uint4* bufP = reinterpret_cast<uint4*>(smem + ped_slice_word(sg.ncols, sg.n_terms));   // (the areas in order: ped_run_lds_bytes, resident.h)
 	uint4* bufQ = bufP + (1u << sg.max_l);
 	uint32_t* stage = reinterpret_cast<uint32_t*>(bufQ + (1u << sg.max_l));
 	// per-column scalars that depend on the workgroup index, straight from the global descriptors: 64 lanes per column

@@ -17,6 +17,11 @@
 
 namespace whamd {
 
+// LDS of one gfx950 compute unit: the most dynamic LDS a launch may ask for (every run kernel's hipFuncAttributeMaxDynamicSharedMemorySize).
+constexpr size_t CU_LDS_BYTES = 160 * 1024;
+// What the planners let one run take of it (resident runs here, the genotyper's runs as GS_MAX_LDS): a margin of 10 KB, reason not recorded.
+constexpr size_t RUN_LDS_BUDGET = 150 * 1024;
+
 constexpr int RES_EMAX = 3;        // reads that may end in one resident column
 constexpr int RES_LMAX = 13;       // log2 of the largest LDS slice (entries)
 constexpr int RES_GMAX = 10;       // log2 of the largest grid (workgroups) of one run (coverage 23 = 10 grid + 13 local bits)
@@ -135,6 +140,35 @@ struct ResSegment {
 	uint32_t in_fullmask, out_fullmask;  // all index bits of the entering / exit slice
 };
 
+// Dynamic LDS of a resident run, in the order the kernels carve it out of `smem` (resident_segment_body, resident_segment_ped):
+//   single individual: descriptors [ncols][RES_LDSWORDS] | lookup tables [ncols][RES_TABLE] | slice P, slice Q [2^max_l] u32 each |
+//                      backtrace record [stage_words] u64
+//   trio:              descriptors [ncols][PED_LDSWORDS] | lookup tables [ncols][PED_TABLE] | term pool [n_terms] PedTerm, padded to 16 bytes |
+//                      slice P, slice Q [2^max_l] entries of T = 4 values (16 bytes) each | backtrace record [stage_words] u64
+// res_slice_word / ped_slice_word: the word of `smem` at which slice P begins (the kernels and the sizes below share them; U = uint32_t in a kernel,
+// uint64_t for the planner's running totals).
+template <class U> constexpr U res_slice_word(U ncols) { return ncols * (RES_LDSWORDS + RES_TABLE); }
+template <class U> constexpr U ped_slice_word(U ncols, U n_terms) { return (ncols * (PED_LDSWORDS + PED_TABLE) + n_terms * 2 + 3) & ~(U)3; }
+constexpr uint64_t res_run_lds_bytes(uint64_t ncols, uint32_t max_l, uint64_t stage_words) {
+	return res_slice_word(ncols) * 4 + 2 * (4ull << max_l) + stage_words * 8;
+}
+constexpr uint64_t ped_run_lds_bytes(uint64_t ncols, uint64_t n_terms, uint32_t max_l, uint64_t stage_words) {
+	return ped_slice_word(ncols, n_terms) * 4 + 2 * (16ull << max_l) + stage_words * 8;
+}
+inline uint64_t res_segment_lds_bytes(const ResSegment& sg) {
+	return sg.kind == 1 ? ped_run_lds_bytes(sg.ncols, sg.n_terms, sg.max_l, sg.stage_words) : res_run_lds_bytes(sg.ncols, sg.max_l, sg.stage_words);
+}
+// What plan_forward holds against RUN_LDS_BUDGET while it extends a trio run by a column (a single-individual run: res_run_lds_bytes itself): the term
+// pool without its padding, plus 16 bytes that bound the padding.  Descriptors and tables are a multiple of 4 words and a term is 2 words, so
+// ped_run_lds_bytes is this sum - 16 for an even n_terms and - 8 for an odd one: a run that passes needs at most RUN_LDS_BUDGET - 8 bytes.  The test
+// cannot be restated on ped_run_lds_bytes -- 153 584 unpadded bytes with an odd n_terms pass, 153 592 with an even one do not, and both need
+// 153 592 -- so the sum stays what it was, term for term, and a run ends at the column at which it always ended.
+constexpr uint64_t ped_run_lds_bound(uint64_t ncols, uint64_t n_terms, uint32_t max_l, uint64_t stage_words) {
+	return ncols * (PED_LDSWORDS + PED_TABLE) * 4 + n_terms * 8 + 2 * (16ull << max_l) + stage_words * 8 + 16;
+}
+static_assert(ped_run_lds_bound(3, 6, 5, 7) == ped_run_lds_bytes(3, 6, 5, 7) + 16 && ped_run_lds_bound(3, 7, 5, 7) == ped_run_lds_bytes(3, 7, 5, 7) + 8,
+              "the planner's bound against the size a trio run is launched with");
+
 // One run of a batched launch (resident_batch): the segment and the buffers of its job's lane.
 struct ResBatchEntry {
 	ResSegment sg;
@@ -229,5 +263,8 @@ struct ResidentPlan {
 // Plans the whole forward pass.  `resident` false -> every step is a per-column step.
 // use_symmetry: 0 never halve runs, 1 halve full-chip runs (>= 2^8 workgroups), 2 halve every run with a grid read (tests)
 void plan_forward(const Problem& p, bool resident, int l_pref, bool fold, ResidentPlan& plan, int use_symmetry = 1);
+// The plan check behind whamd_plan_summarize (resident_plan.cpp): fills the summary from the plan and returns what it stores as invariants_ok.  It
+// expects the arrays of the plan to have the sizes the planner gives them (an index out of range is not what it looks for).
+bool check_resident_plan(const Problem& p, const ResidentPlan& plan, whamd_plan_summary& summary);
 
 }  // namespace whamd

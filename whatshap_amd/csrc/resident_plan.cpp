@@ -140,15 +140,13 @@ void plan_forward(const Problem& p, bool resident, int l_pref, bool fold, Reside
 				run_max_l = std::max(run_max_l, std::max(Lb, Lf));
 				run_stage += ((1ull << Lf) + 1) / 2;  // one u32 per projection entry
 				run_terms += p.term_end(c1, p.T - 1) - p.term_begin(c1, 0);
-				const uint64_t lds_bytes = (uint64_t)(c1 - c + 1) * (PED_LDSWORDS + PED_TABLE) * 4 + run_terms * 8 + 2 * (16ull << run_max_l) + run_stage * 8 + 16;
-				if (lds_bytes > 150 * 1024) break;
+				if (ped_run_lds_bound(c1 - c + 1, run_terms, run_max_l, run_stage) > RUN_LDS_BUDGET) break;
 				if (ped_abs[c1] >= (1u << 23)) break;  // L_s must fit the 24-bit multiply-add of the term evaluation
 			} else {
 				if (Lb > (uint32_t)RES_LMAX || Lf > (uint32_t)RES_LMAX || Lk > 14) break;
 				run_max_l = std::max(run_max_l, std::max(Lb, Lf));
 				run_stage += (uint64_t)(kc - p.f[c1]) * std::max<uint32_t>(4, (1u << Lf) / 32);
-				const uint64_t lds_bytes = (uint64_t)(c1 - c + 1) * (64 + RES_TABLE) * 4 + 2 * (4ull << run_max_l) + run_stage * 8;
-				if (lds_bytes > 150 * 1024) break;
+				if (res_run_lds_bytes(c1 - c + 1, run_max_l, run_stage) > RUN_LDS_BUDGET) break;
 			}
 			++c1;
 		}
@@ -509,6 +507,73 @@ void plan_forward(const Problem& p, bool resident, int l_pref, bool fold, Reside
 		B.in_mirror_bit = bit;
 		B.in_fullmask = A.out_fullmask;
 	}
+}
+
+// The plan check behind whamd_plan_summarize (tests/test_plan_checks_host.py corrupts a plan field by field and expects `false`).
+bool check_resident_plan(const Problem& p, const ResidentPlan& plan, whamd_plan_summary& s) {
+	s = whamd_plan_summary{};
+	s.n_columns = p.n_cols;
+	s.n_steps = plan.steps.size();
+	s.n_runs = plan.segments.size();
+	s.max_coverage = p.max_k;
+	s.n_components = plan.component_first_step.size();
+	bool ok = true;
+	// components: boundaries are exactly the steps whose first column no read enters, and no run spans one
+	if (!plan.component_first_step.empty()) {
+		size_t k = 0;
+		for (size_t si = 0; si < plan.steps.size(); ++si) {
+			const Step& step = plan.steps[si];
+			const uint32_t c0 = step.kind == 1 ? plan.segments[step.index].c0 : step.index;
+			const bool boundary = si == 0 || p.b[c0] == 0;
+			if (boundary) { ok = ok && k < plan.component_first_step.size() && plan.component_first_step[k] == si; ++k; }
+			if (step.kind == 1)
+				for (uint32_t i = 1; i < plan.segments[step.index].ncols; ++i) ok = ok && p.b[c0 + i] != 0;
+		}
+		ok = ok && k == plan.component_first_step.size();
+	}
+	std::vector<uint8_t> seen(p.n_cols, 0);
+	uint32_t expect = 0;
+	for (const Step& step : plan.steps) {
+		if (step.kind == 0) {
+			ok = ok && step.index == expect && step.index < p.n_cols;
+			if (step.index < p.n_cols) seen[step.index]++;
+			expect = step.index + 1;
+			continue;
+		}
+		const ResSegment& sg = plan.segments[step.index];
+		ok = ok && sg.c0 == expect && sg.ncols >= 2 && sg.ncols <= (uint32_t)RES_MAXCOLS && sg.g <= (uint32_t)RES_GMAX;
+		expect = sg.c0 + sg.ncols;
+		uint64_t stage = 0;
+		for (uint32_t i = 0; i < sg.ncols; ++i) {
+			const uint32_t c = sg.c0 + i;
+			if (c >= p.n_cols) { ok = false; break; }
+			seen[c]++;
+			const ResColumn& rc = plan.columns[sg.col_off + i];
+			ok = ok && plan.col_to_res[c] == (int32_t)(sg.col_off + i);
+			ok = ok && rc.Lb == p.b[c] - sg.g && rc.Lf == p.f[c] - sg.g && rc.ebits == (uint32_t)p.k[c] - p.f[c];
+			const uint32_t lmax = sg.kind == 1 ? (uint32_t)PED_LMAX : (uint32_t)RES_LMAX;
+			ok = ok && rc.Lb <= lmax && rc.Lf <= lmax && rc.ebits <= (uint32_t)RES_EMAX;
+			ok = ok && rc.stage_off == stage;
+			stage += sg.kind == 1 ? (uint64_t)rc.nwords : (uint64_t)rc.ebits * rc.nwords;
+			if (rc.mode == RES_MODE_FOLDED) { s.n_folded_columns++; ok = ok && i + 1 < sg.ncols && rc.ebits == 0; }
+			if (rc.mode != RES_MODE_GENERIC) s.n_vectorised_columns++;
+			if (rc.nfold) ok = ok && rc.nfold <= RES_MAXFOLD && i >= rc.nfold;
+			ok = ok && c + 1 < p.n_cols;  // the last column never runs resident
+		}
+		ok = ok && stage == sg.stage_words;
+		const uint64_t lds = res_segment_lds_bytes(sg);
+		ok = ok && lds <= CU_LDS_BYTES;
+		s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, lds);
+		s.max_run_columns = std::max<uint64_t>(s.max_run_columns, sg.ncols);
+		s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << (sg.g - sg.half));  // launched workgroups
+		if (sg.half) s.n_halved_runs++;
+		s.n_resident_columns += sg.ncols;
+		s.backtrace_bytes += (uint64_t)sg.stage_words * (1ull << sg.g) * 8;
+	}
+	ok = ok && expect == p.n_cols;
+	for (uint32_t c = 0; c < p.n_cols; ++c) ok = ok && seen[c] == 1;
+	s.invariants_ok = ok ? 1 : 0;
+	return ok;
 }
 
 }  // namespace whamd

@@ -716,4 +716,150 @@ bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan
 	return true;
 }
 
+// ---- the plan checks (whamd_plan_summarize; tests/test_plan_checks_host.py corrupts a plan field by field and expects `false`)
+
+// slot runs (slots.h): every column in exactly one step, runs within their limits, slots consistent
+bool check_slot_plan(const Problem& p, const SlotPlan& sp, whamd_plan_summary& s) {
+	s = whamd_plan_summary{};
+	s.n_columns = p.n_cols;
+	s.n_steps = sp.steps.size();
+	s.n_runs = sp.runs.size();
+	s.max_coverage = p.max_k;
+	s.n_components = sp.component_first_step.size();
+	bool ok = true;
+	uint32_t expect = 0;
+	size_t kc = 0;
+	for (size_t si = 0; si < sp.steps.size(); ++si) {
+		const Step& step = sp.steps[si];
+		const uint32_t c0 = step.kind == 2 ? sp.runs[step.index].c0 : step.index;
+		if (!sp.ped && (si == 0 || p.b[c0] == 0)) { ok = ok && kc < sp.component_first_step.size() && sp.component_first_step[kc] == si; ++kc; }
+		ok = ok && c0 == expect;
+		if (step.kind == 0) { expect = c0 + 1; ok = ok && sp.col_to_row[c0] < 0; continue; }
+		const SlotRun& run = sp.runs[step.index];
+		expect = c0 + run.ncols;
+		ok = ok && step.kind == 2 && run.ncols >= 2 && run.ncols <= (uint32_t)(sp.ped ? PSLOT_MAXCOLS : SLOT_MAXCOLS) && run.g <= (uint32_t)SLOT_GMAX;
+		if (sp.ped) {
+			const PedSlotExtra& ex = sp.pextra[step.index];
+			ok = ok && sp.pextra.size() == sp.runs.size() && run.lr == 0 && !run.half && (1u << ex.tb) == p.T && run.L == 6u - ex.tb + run.lw;
+			ok = ok && (ex.nf == 2 || ex.nf == 4 || ((ex.nf == 16 || ex.nf == (uint32_t)PSLOT_FACT) && ex.tb == 2) || (ex.nf == (uint32_t)PSLOT_FACT4 && ex.tb == 4)) && ex.fwn == run.ncols * pslot_ta(ex.nf, p.T) * pslot_na(ex.nf) && ex.fwn <= (uint32_t)PSLOT_FORMWORDS && ex.rec_words == ((run.ncols + 3) / 4) * run.threads;
+			ok = ok && run.lw <= (uint32_t)SLOT_LWMAX && run.threads == (64u << run.lw);
+		} else
+		ok = ok && run.lr >= 1 && run.lr <= (uint32_t)SLOT_LR && run.L == run.lr + (uint32_t)SLOT_LANE + run.lw && run.lw <= (uint32_t)SLOT_LWMAX && run.threads == (64u << run.lw);
+		ok = ok && run.L + run.g <= (uint32_t)SLOT_MAXSLOTS && run.n_ends <= (uint32_t)SLOT_MAXENDS_RUN && (!run.half || run.g >= 1);
+		uint32_t ends = 0;
+		for (uint32_t i = 0; i < run.ncols && ok; ++i) {
+			const uint32_t c = c0 + i;
+			if (c + 1 >= p.n_cols) { ok = false; break; }   // the last column never runs inside a run
+			ok = ok && sp.col_to_row[c] == (int32_t)(run.row_off + i) && (i == 0 || p.b[c] != 0);
+			const uint32_t row_n_end = sp.ped ? sp.prows[run.row_off + i].n_end : sp.rows[run.row_off + i].n_end;
+			const SlotBtCol& bc = sp.bt_cols[run.row_off + i];
+			ok = ok && bc.k == p.k[c] && bc.kf == ends && row_n_end == (uint32_t)p.k[c] - p.f[c] && row_n_end <= (uint32_t)(sp.ped ? PSLOT_MAXEND : SLOT_MAXEND);
+			if (sp.ped && sp.pextra[step.index].nf == (uint32_t)PSLOT_FACT) ok = ok && p.fterm_kind == 1 && p.fterms.size() == (size_t)p.n_cols * p.T * 16;
+			else if (sp.ped && sp.pextra[step.index].nf == (uint32_t)PSLOT_FACT4) ok = ok && p.fterm_kind == 2 && p.fterms.size() == (size_t)p.n_cols * PSLOT_FSTRIDE4;
+			else if (sp.ped) for (uint32_t t = 0; t < p.T; ++t) ok = ok && p.term_end(c, t) - p.term_begin(c, t) <= sp.pextra[step.index].nf;
+			uint32_t used = 0;
+			for (uint32_t j = 0; j < bc.k; ++j) {   // distinct slots, ending reads local
+				ok = ok && bc.slot[j] < run.L + run.g && !((used >> bc.slot[j]) & 1u);
+				used |= 1u << bc.slot[j];
+				if (!((p.fwd_mask[c] >> j) & 1u)) ok = ok && bc.slot[j] < run.L;
+			}
+			for (uint32_t q = 0; q < row_n_end; ++q) {
+				const uint32_t es = sp.ped ? (uint32_t)(q < 3u ? bc.slot[25 + q] : bc.pad[1]) : (sp.rows[run.row_off + i].end[q].info & 255u);
+				ok = ok && sp.end_slots[sp.end_off[step.index] + ends + q] == es;
+			}
+			ends += row_n_end;
+		}
+		ok = ok && ends == run.n_ends;
+		s.max_run_columns = std::max<uint64_t>(s.max_run_columns, run.ncols);
+		s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << (run.g - run.half));
+		if (sp.ped) {
+			const PedSlotExtra& ex = sp.pextra[step.index];
+			s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, pedslot_lds_bytes(run.threads, run.ncols, ex));
+			if (pslot_is_fact(ex.nf)) s.n_fact_runs++;
+			s.backtrace_bytes += ((uint64_t)ex.rec_words * 4) << run.g;
+		} else {
+			s.max_lds_bytes = std::max<uint64_t>(s.max_lds_bytes, slot_run_lds_bytes(run.threads, run.lr, run.ncols));
+			s.backtrace_bytes += (uint64_t)run.n_ends * run.threads * (1ull << (run.g - run.half));
+		}
+		if (run.half) s.n_halved_runs++;
+		if (run.yflags & 1u) s.n_yform_runs++;
+		s.n_resident_columns += run.ncols;
+		s.n_vectorised_columns += run.ncols;
+	}
+	ok = ok && expect == p.n_cols && kc == sp.component_first_step.size();
+	s.invariants_ok = ok ? 1 : 0;
+	return ok;
+}
+
+// the run plan of the genotyping path (genotype_slots.hip): every column must lie in a run, or the per-column kernels take over
+bool check_genotype_slot_plan(const Problem& p, const SlotPlan& sp, whamd_plan_summary& s) {
+	s = whamd_plan_summary{};
+	s.n_columns = p.n_cols;
+	s.max_coverage = p.max_k;
+	s.n_steps = sp.steps.size();
+	s.n_runs = sp.runs.size();
+	bool ok = true;
+	uint32_t expect = 0;
+	for (const Step& step : sp.steps) {
+		if (step.kind != 2) {
+			if (debug_env("WHAMD_DEBUG_PLAN")) fprintf(stderr, "[plan] genotype: column %u outside runs (k=%u b=%u f=%u, next k=%u)\n", step.index, p.k[step.index], p.b[step.index], p.f[step.index], step.index + 1 < p.n_cols ? p.k[step.index + 1] : 0);
+			ok = ok && step.index == expect; expect = step.index + 1; continue;
+		}
+		const SlotRun& run = sp.runs[step.index];
+		ok = ok && run.c0 == expect && run.lr == 0 && !run.half && run.ncols >= 1 && run.ncols <= (uint32_t)PSLOT_MAXCOLS;
+		expect = run.c0 + run.ncols;
+		s.n_resident_columns += run.ncols;
+		s.max_run_columns = std::max<uint64_t>(s.max_run_columns, run.ncols);
+		s.max_workgroups = std::max<uint64_t>(s.max_workgroups, 1ull << run.g);
+		uint32_t starts = 0, ends = 0;
+		for (uint32_t i = 0; i < run.ncols; ++i) {
+			const PedSlotRow& pr = sp.prows[run.c0 + i];
+			const uint32_t c = run.c0 + i;
+			ok = ok && pr.pad[0] == (uint32_t)p.k[c] - (i == 0 ? p.b[run.c0] : p.b[c]) && pr.pad[1] == starts;
+			ok = ok && pr.n_end == (c + 1 == p.n_cols ? 0u : (uint32_t)p.k[c] - p.f[c]) && sp.bt_cols[c].kf == ends;
+			starts += pr.pad[0];
+			ends += pr.n_end;
+		}
+	}
+	ok = ok && expect == p.n_cols;
+	s.invariants_ok = ok ? 1 : 0;
+	return ok;
+}
+
+#ifdef WHAMD_DEBUG_BUILD   // (whamd_debug_head_first_plan)
+namespace {
+void fnv1a(uint64_t& h, const void* data, size_t bytes) {
+	const unsigned char* b = static_cast<const unsigned char*>(data);
+	for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+}
+}  // namespace
+
+uint64_t slot_plan_runs_digest(const SlotPlan& sp, size_t n_runs) {
+	uint64_t h = 1469598103934665603ull;
+	for (size_t ri = 0; ri < n_runs; ++ri) {
+		const SlotRun& run = sp.runs[ri];
+		fnv1a(h, &run, sizeof run);
+		fnv1a(h, sp.rows.data() + run.row_off, (size_t)run.ncols * sizeof(SlotRow));
+		fnv1a(h, sp.bt_cols.data() + run.row_off, (size_t)run.ncols * sizeof(SlotBtCol));
+		fnv1a(h, sp.ctrl.data() + run.ctrl_off, (size_t)SLOT_CTRL_WORDS * 4);
+		fnv1a(h, sp.end_slots.data() + sp.end_off[ri], run.n_ends);
+	}
+	return h;
+}
+
+uint64_t slot_plan_digest(const SlotPlan& sp) {
+	uint64_t h = slot_plan_runs_digest(sp, sp.runs.size());
+	fnv1a(h, sp.steps.data(), sp.steps.size() * sizeof(Step));
+	fnv1a(h, sp.end_off.data(), sp.end_off.size() * 4);
+	fnv1a(h, sp.start_slots.data(), sp.start_slots.size());
+	fnv1a(h, sp.start_off.data(), sp.start_off.size() * 4);
+	fnv1a(h, sp.f_exit.data(), sp.f_exit.size() * 4);
+	for (const std::vector<uint8_t>& e : sp.exit_slot) fnv1a(h, e.data(), e.size());
+	fnv1a(h, sp.col_to_row.data(), sp.col_to_row.size() * 4);
+	fnv1a(h, sp.component_first_step.data(), sp.component_first_step.size() * 4);
+	fnv1a(h, &sp.n_run_columns, sizeof sp.n_run_columns);
+	return h;
+}
+#endif
+
 }  // namespace whamd

@@ -324,6 +324,16 @@ struct SlotPlanHead {
 	std::function<void(uint32_t)> at_head;
 };
 bool plan_forward_slots(const Problem& p, int l_pref, int use_symmetry, SlotPlan& plan, int lr = 2, bool genotype_mode = false, const SlotPlanHead* head = nullptr);
+// The plan checks behind whamd_plan_summarize (slot_plan.cpp): each fills the summary from the plan and returns what it stores as invariants_ok.
+// check_slot_plan: single-individual and pedigree plans; check_genotype_slot_plan: plans made with genotype_mode.  They expect the arrays of the
+// plan to have the sizes the planner gives them (an index out of range is not what they look for).
+bool check_slot_plan(const Problem& p, const SlotPlan& plan, whamd_plan_summary& summary);
+bool check_genotype_slot_plan(const Problem& p, const SlotPlan& plan, whamd_plan_summary& summary);
+#ifdef WHAMD_DEBUG_BUILD
+// FNV-1a of what the runs [0, n_runs) and their backtrace read of the plan, and of the whole plan (whamd_debug_head_first_plan).
+uint64_t slot_plan_runs_digest(const SlotPlan& plan, size_t n_runs);
+uint64_t slot_plan_digest(const SlotPlan& plan);
+#endif
 // Milliseconds of the steady clock, for the WHAMD_DEBUG_TIMING lines of different files that are read against each other ("t = ...").
 inline double timing_stamp_ms() { return std::fmod(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), 1e6); }
 

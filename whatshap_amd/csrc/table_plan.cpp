@@ -538,10 +538,7 @@ whamd_status_t make_schedule(const TableBuild& b, const DevProblem& dp, uint32_t
 				e.prev = lane.d_pr[c.flip];
 				e.cur = lane.d_pr[c.flip ^ 1];
 				e.score_out = (last && !job.final) ? d_job_scores + job_id : nullptr;
-				const size_t lds = e.sg.kind == 1
-					? ((((size_t)e.sg.ncols * (PED_LDSWORDS + PED_TABLE) + (size_t)e.sg.n_terms * 2 + 3) & ~(size_t)3) * 4 + 2 * ((size_t)16 << e.sg.max_l) + (size_t)e.sg.stage_words * 8)
-					: ((size_t)e.sg.ncols * (64 + RES_TABLE) * 4 + 2 * ((size_t)4 << e.sg.max_l) + (size_t)e.sg.stage_words * 8);
-				ss.lds = std::max(ss.lds, lds);
+				ss.lds = std::max<size_t>(ss.lds, res_segment_lds_bytes(e.sg));
 				ss.grid_x = std::max(ss.grid_x, 1u << (e.sg.g - e.sg.half));
 				ss.threads = std::max(ss.threads, e.sg.threads);
 				ss.sym = ss.sym || e.sg.half || e.sg.in_half || e.sg.mirror_out;
