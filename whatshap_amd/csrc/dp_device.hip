@@ -316,6 +316,7 @@ struct DeviceTable::Impl {
 	whamd_status_t submit_singles(const Problem& p, const SuperStep& ss, uint64_t& launches, std::string& msg);
 	whamd_status_t submit_tail(const Problem& p, std::string& msg, hipStream_t tail_stream = nullptr, bool walked_by_group = false);
 	whamd_status_t report_slot_stamps(std::string& msg) const;
+	whamd_status_t report_slot_wave_stamps(std::string& msg) const;
 	whamd_status_t report_resident_stamps(std::string& msg) const;
 
 	// The preview (DESIGN.md 6.1 "preview"): the leading slot runs of a lone table's forward pass, launched on `stream` from INSIDE the create -- from arrays of
@@ -866,8 +867,11 @@ whamd_status_t DeviceTable::Impl::arm_debug_stamps(TableUploader& up, std::strin
 		m.dev.dp.dbg_wg_off = (uint32_t)((m.tp.plan.segments.size() + 1) * 8);
 		m.dev.dp.dbg_flags = (uint32_t)atoi(debug_env("WHAMD_DEBUG_STAMPS"));
 	}
+	bool wave_stamps = false;
 	if (debug_env("WHAMD_SLOT_STAMPS") && m.tp.use_slots) {   // in-kernel cycle stamps of workgroup 0 / wave 0 of every slot run
-		const size_t dbg_bytes = (m.tp.splan.runs.size() + 1) * 48 * 8 + 4 * 512 * 16 + 128;   // + the backtrace kernel's own stamps
+		wave_stamps = atoi(debug_env("WHAMD_SLOT_STAMPS")) >= 2;   // (= 2: every wave of three workgroups of every X run, behind the other stamps)
+		const size_t dbg_bytes = (m.tp.splan.runs.size() + 1) * 48 * 8 + 4 * 512 * 16 + 128 +   // + the backtrace kernel's own stamps
+		                         (wave_stamps ? (m.tp.splan.runs.size() + 1) * SLOT_WAVE_STAMP_WGS * SLOT_WAVE_STAMP_WORDS * 8 : 0);
 		HIP_TRY(up.alloc((void**)&m.dev.dp.dbg, dbg_bytes));
 		HIP_TRY(hipMemset(m.dev.dp.dbg, 0, dbg_bytes));
 		m.dev.dp.dbg_wg_off = (uint32_t)((m.tp.splan.runs.size() + 1) * 48);
@@ -875,6 +879,7 @@ whamd_status_t DeviceTable::Impl::arm_debug_stamps(TableUploader& up, std::strin
 	}
 	if (const char* skip = debug_env("WHAMD_SLOT_SKIP")) m.dev.dp.dbg_flags = (uint32_t)atoi(skip);  // timing experiments (results invalid): 1 no exit
 	                                                                                          // stores, 2 no records, 4 one column per run, 8 no ending reads, 16 no cost update
+	if (wave_stamps) m.dev.dp.dbg_flags |= 256u;   // (the X runs keep per-wave stamps INSTEAD of wave 0's column stamps)
 	return WHAMD_OK;
 }
 
@@ -1846,6 +1851,7 @@ void DeviceTable::read_timing(whamd_solve_stats& st) {
 // The in-kernel cycle stamps of the slot runs (WHAMD_SLOT_STAMPS, debug library): full-length runs, wave 0 of workgroup 0.
 whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
 	const Impl& m = *this;
+	if (m.dev.dp.dbg_flags & 256u) return m.report_slot_wave_stamps(msg);
 	std::vector<unsigned long long> d(m.tp.splan.runs.size() * 48);
 	HIP_TRY(hipMemcpy(d.data(), m.dev.dp.dbg, d.size() * 8, hipMemcpyDeviceToHost));
 	double a[6] = {0, 0, 0, 0, 0, 0};
@@ -1862,6 +1868,72 @@ whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
 	if (cnt) {
 		fprintf(stderr, "[whamd slot stamps] cycles after the loop start at which column c had its cost added:");
 		for (int k = 0; k < 22; ++k) fprintf(stderr, " %.0f", percol[k] / cnt);
+		fprintf(stderr, "\n");
+	}
+	return WHAMD_OK;
+}
+
+// The per-wave stamps of the X runs (WHAMD_SLOT_STAMPS=2, debug library): full-length runs of eight waves, workgroups 0, 3 and 6 (three XCDs).  Every stamp
+// as cycles after the EARLIEST wave start of its workgroup, averaged per wave; its spread over the eight waves; which wave is last; and the entering
+// cells' own latency by the order in which the waves issued their request (a queue in front of a late request shows as latency growing with the rank).
+whamd_status_t DeviceTable::Impl::report_slot_wave_stamps(std::string& msg) const {
+	const Impl& m = *this;
+	constexpr int NW = 8, NS = 8;
+	static const char* const names[NS] = {"wave start", "entering cells requested", "last prologue request", "entering cells landed", "all landed, loop starts",
+	                                      "first wave-slot ending reached", "first wave-slot ending left", "loop end"};
+	static const int word[NS] = {0, 1, 2, 3, 7, 4, 5, 6};   // (the order of slot_runx_exit's words -> the order of the events)
+	const size_t nruns = m.tp.splan.runs.size(), per_run = (size_t)SLOT_WAVE_STAMP_WGS * SLOT_WAVE_STAMP_WORDS;
+	std::vector<unsigned long long> d(nruns * per_run);
+	HIP_TRY(hipMemcpy(d.data(), m.dev.dp.dbg + m.dev.dp.dbg_wg_off + SLOT_WAVE_STAMP_OFF, d.size() * 8, hipMemcpyDeviceToHost));
+	for (uint32_t sel = 0; sel < SLOT_WAVE_STAMP_WGS; ++sel) {
+		double mean[NS][NW] = {}, spread[NS] = {}, spread_max[NS] = {}, lat_rank[NW] = {}, req_rank[NW] = {}, land_rank[NW] = {};
+		size_t last[2][NW] = {}, cnt = 0;
+		for (size_t i = 0; i < nruns; ++i) {
+			const unsigned long long* r = d.data() + i * per_run + sel * SLOT_WAVE_STAMP_WORDS;
+			bool full = m.tp.splan.runs[i].ncols == 22;
+			for (int v = 0; v < NW; ++v) full = full && r[v * 8 + 6] != 0 && r[v * 8 + 4] != 0;   // (a run of eight waves with a wave-slot ending)
+			if (!full) continue;
+			unsigned long long s0 = r[0];
+			for (int v = 1; v < NW; ++v) s0 = std::min(s0, r[v * 8]);
+			double at[NS][NW];
+			for (int k = 0; k < NS; ++k) {
+				double lo = 1e300, hi = 0;
+				int hi_at = 0;
+				for (int v = 0; v < NW; ++v) {
+					at[k][v] = (double)(r[v * 8] - s0) + (k ? (double)r[v * 8 + word[k]] : 0.0);
+					mean[k][v] += at[k][v];
+					lo = std::min(lo, at[k][v]);
+					if (at[k][v] > hi) { hi = at[k][v]; hi_at = v; }
+				}
+				spread[k] += hi - lo;
+				spread_max[k] = std::max(spread_max[k], hi - lo);
+				if (k == 3) last[0][hi_at]++;
+				if (k == 5) last[1][hi_at]++;
+			}
+			int order[NW];
+			for (int v = 0; v < NW; ++v) order[v] = v;
+			std::sort(order, order + NW, [&](int a, int b) { return at[1][a] < at[1][b]; });
+			for (int q = 0; q < NW; ++q) { req_rank[q] += at[1][order[q]]; land_rank[q] += at[3][order[q]]; lat_rank[q] += at[3][order[q]] - at[1][order[q]]; }
+			++cnt;
+		}
+		if (!cnt) continue;
+		fprintf(stderr, "[whamd slot wave stamps] workgroup %u: %zu runs of 22 columns, shader cycles after the workgroup's earliest wave start; waves 0 .. 7 | mean spread, largest spread\n", 3 * sel, cnt);
+		for (int k = 0; k < NS; ++k) {
+			fprintf(stderr, "[whamd slot wave stamps]   %-31s", names[k]);
+			for (int v = 0; v < NW; ++v) fprintf(stderr, " %6.0f", mean[k][v] / cnt);
+			fprintf(stderr, " | %6.0f %6.0f\n", spread[k] / cnt, spread_max[k]);
+		}
+		for (int h = 0; h < 2; ++h) {
+			fprintf(stderr, "[whamd slot wave stamps]   runs in which wave v is the last %-14s", h ? "at the ending:" : "to have cells:");
+			for (int v = 0; v < NW; ++v) fprintf(stderr, " %6zu", last[h][v]);
+			fprintf(stderr, "\n");
+		}
+		fprintf(stderr, "[whamd slot wave stamps]   by the order of the waves' requests -- requested:     ");
+		for (int q = 0; q < NW; ++q) fprintf(stderr, " %6.0f", req_rank[q] / cnt);
+		fprintf(stderr, "\n[whamd slot wave stamps]                                           landed:        ");
+		for (int q = 0; q < NW; ++q) fprintf(stderr, " %6.0f", land_rank[q] / cnt);
+		fprintf(stderr, "\n[whamd slot wave stamps]                                           latency:       ");
+		for (int q = 0; q < NW; ++q) fprintf(stderr, " %6.0f", lat_rank[q] / cnt);
 		fprintf(stderr, "\n");
 	}
 	return WHAMD_OK;

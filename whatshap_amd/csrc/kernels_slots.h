@@ -622,7 +622,15 @@ __device__ __forceinline__ uint32_t slot_touch_lines(const void* base) {   // li
 }
 __device__ __forceinline__ void slot_touch_done(uint32_t junk) { asm volatile("" ::"s"(junk)); }
 
-struct SlotxStamps { unsigned long long t_start, t_issued, t_loaded, t_loop; };
+struct SlotxStamps {
+	unsigned long long t_start, t_issued, t_loaded, t_loop;
+	// per-wave stamps (WHAMD_SLOT_STAMPS=2: dbg_flags bit 8), low words of the cycle counter: the entering cells' load issued / landed, the run's first
+	// wave-slot ending reached / left
+	uint32_t w_enter = 0, w_landed = 0, w_end_in = 0, w_end_out = 0;
+};
+// Per-wave stamps: every wave of workgroups 0, 3 and 6 (three XCDs) keeps eight words per run behind the other stamps of P.dbg (report_slot_wave_stamps).
+constexpr uint32_t SLOT_WAVE_STAMP_WGS = 3, SLOT_WAVE_STAMP_WORDS = 8 * 8, SLOT_WAVE_STAMP_OFF = 4 * 512 * 2 + 16;
+__device__ __forceinline__ bool slot_wave_stamps_on(const DevProblem& P) { return P.dbg && (P.dbg_flags & 256u); }
 template <int LR, int XC, bool DBG>
 __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[1 << LR],
                                                SlotxStamps& stamps, const void* warm = nullptr) {
@@ -634,6 +642,13 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	const unsigned long long t_start = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t wave = uni(tid >> 6);
+	// A workgroup of eight waves is two waves per SIMD, and at equal priority the older wave of a SIMD wins the issue arbitration: waves 4 .. 7 -- dispatched
+	// second -- asked for their entering cells 550 cycles after waves 0 .. 3 and reached the run's first wave-slot ending 1 200 cycles after them, where the older
+	// half then stood and waited (per-wave stamps, profiles/late_wave/stamps.md: the launch is as long as its slowest wave).  The younger half runs the PROLOGUE at
+	// priority 1 -- its request for the entering cells, the longest latency of the launch, goes out first -- and everybody the loop at priority 0 again (the
+	// priority kept through the loop only swaps the two halves' roles: measured, profiles/late_wave/experiments_not_kept.md).  One workgroup per CU only: where
+	// several share a CU (STREAM) they fill each other's waits.  The condition is a scalar: s_setprio ignores EXEC.
+	if (!STREAM && wave >= 4u) __builtin_amdgcn_s_setprio(1);
 	const uint32_t L = run.L;
 	const uint32_t lthr = tid << LR;
 	const uint32_t Pthr = (w << L) | lthr;
@@ -668,6 +683,10 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	uint32_t Draw[R];
 	bool flip;
 	slot_enter_cells<LR, DBG>(P, run, prev, Pthr, Draw, flip);
+	const bool wstamps = DBG && slot_wave_stamps_on(P);
+	if (DBG && wstamps) asm volatile("" ::: "memory");   // (the stamp behind the entering cells' requests and in front of every other one)
+	stamps.w_enter = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
+	if (DBG && wstamps) asm volatile("" ::: "memory");
 	const uint32_t par_l = tab[run.tab_par + tid];
 	const uint32_t* __restrict__ sl_src = tab + run.tab_sl + lane;   // the lane part of column c: sl_src[64 c] (one coalesced 256-byte request per wave and column)
 	const uint32_t* __restrict__ g_row = tab + run.tab_g + w * ncp;  // the workgroup's and the wave's part: rows of the tables G and W
@@ -688,6 +707,8 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		touch_g = slot_touch_lines<2>(g_row);
 		touch_w = slot_touch_lines<2>(w_row);
 		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
+		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");   // (vector loads return in order: par_l and four lane parts are behind the entering cells)
+		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
 	} else {
 		// lane c of every wave fetches the workgroup + wave part of column c, the thread the lane part of every column (columns behind the run's last
 		// read zeros, further ones the tables that follow -- never used)
@@ -702,6 +723,8 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		if (XC > 24) touch_kr2 = slot_touch_lines<2>(kr_tab + 128);   // (lines 9, 10 of a 32-column run)
 		touch_cw = slot_touch_lines<2>(cw_tab);   // (... and the control words': sixteen columns per line)
 		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
+		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XC + 3) : "memory");   // (... par_l, a_g, a_w and XC lane parts are)
+		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
 		// X0 of column c = 2 A(thread's cell 0) + bias = lane part + (workgroup + wave part, held by lane c): kept in the thread's OWN 16 bytes per trip of
 		// an LDS area (nobody else reads them: no barrier) -- a register per column would need the column loop unrolled over the whole run
 		const uint32_t Avec = lane < ncols ? a_g + a_w : 0u;   // (columns behind the run's last: zero)
@@ -726,6 +749,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	if (warm) asm volatile("" ::"v"(warm_junk), "v"(D[0]));   // (the entering cells are here, so the request issued before them is too)
 	if (DBG && P.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	const unsigned long long t_loaded = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
+	if (!STREAM) __builtin_amdgcn_s_setprio(0);   // (the prologue's priority of the younger half ends here)
 
 	const uint32_t lds0 = (uint32_t)(unsigned long long)smem;   // LDS byte offset of the exchange buffers
 	const uint32_t lane4 = lane << 2, tid16 = lds0 + (tid << 4);   // (tid16: this thread's 16 bytes of exchange buffer 0)
@@ -749,10 +773,16 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		D[1] = slot_y_sad_s(x, k1, D[1]);
 		D[2] = slot_y_sad_s(x, k2, D[2]);
 		D[3] = slot_y_sad_s(x, k3, D[3]);
-		if (DBG && P.dbg && w == 0 && tid == 0 && ci < 32u) P.dbg[(size_t)run.pad * 48 + 8 + ci] = __builtin_readcyclecounter() - t_loaded;
+		if (DBG && P.dbg && !wstamps && w == 0 && tid == 0 && ci < 32u) P.dbg[(size_t)run.pad * 48 + 8 + ci] = __builtin_readcyclecounter() - t_loaded;
 		if (ctrl & 3u) {   // reads ending here: the first two are described in the control word, a third and later ones in the row (scalar loads, requested
 			              // before the second ending read is evaluated)
-			ending(ctrl);
+			if (DBG && wstamps && !stamps.w_end_in && ((ctrl >> 2) & 31u) >= 8u) {   // (per-wave stamps: the run's first wave-slot ending, where it is a column's first)
+				stamps.w_end_in = (uint32_t)__builtin_readcyclecounter() | 1u;
+				ending(ctrl);
+				stamps.w_end_out = (uint32_t)__builtin_readcyclecounter() + (D[0] & 0u);
+			} else {
+				ending(ctrl);
+			}
 			if (ctrl & 2u) {
 				const unsigned long long row = (unsigned long long)(rows + ci);
 				uint32_t n_end = 2u, info = 0u;
@@ -1079,6 +1109,14 @@ __device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRu
 		unsigned long long* d = P.dbg + (size_t)run.pad * 48;
 		d[0] = stamps.t_issued - stamps.t_start; d[1] = stamps.t_loaded - stamps.t_start; d[2] = stamps.t_loop - stamps.t_loaded; d[3] = __builtin_readcyclecounter() - stamps.t_loop;
 		d[4] = run.ncols; d[5] = 1;
+	}
+	if (DBG && slot_wave_stamps_on(P) && lane == 0 && w < 3u * SLOT_WAVE_STAMP_WGS && w % 3u == 0u) {   // lane 0 of every wave of workgroups 0, 3, 6: its own eight words
+		unsigned long long* d = P.dbg + P.dbg_wg_off + SLOT_WAVE_STAMP_OFF + ((size_t)run.pad * SLOT_WAVE_STAMP_WGS + w / 3u) * SLOT_WAVE_STAMP_WORDS + wave * 8u;
+		const uint32_t t0 = (uint32_t)stamps.t_start;
+		d[0] = stamps.t_start;   // (absolute: the waves of a workgroup are compared on the host; everything else relative to the wave's own start)
+		d[1] = stamps.w_enter - t0; d[2] = (uint32_t)stamps.t_issued - t0; d[3] = stamps.w_landed - t0;
+		d[4] = stamps.w_end_in ? (stamps.w_end_in - t0) : 0u; d[5] = stamps.w_end_in ? (stamps.w_end_out - t0) : 0u; d[6] = (uint32_t)stamps.t_loop - t0;
+		d[7] = (uint32_t)stamps.t_loaded - t0;   // (every prologue request landed, cells in Y form: the loop starts)
 	}
 }
 template <int LR, int XC, bool DBG, bool SPEC>
