@@ -487,7 +487,7 @@ whamd_status_t whamd_edit_distance_batch(uint64_t n_pairs, const uint64_t* query
  * the matrix, the likelihoods (readscoring.cpp:123-191), the allele-pair tables (:193-225) and one float term per (position, allele,
  * allele) are computed on the host (csrc/polyscore.cpp); the pair loop runs on the device (csrc/polyscore_device.hip) and its results
  * are bit-identical to the host restatement of the debug library.  The reference sums the genotypes of a position in the iteration order
- * of an unordered_map; this library sums them in increasing genotype index, which can move a term by one float ulp.
+ * of an unordered_map; this library sums them in that order as GNU libstdc++ gives it (hash_order, csrc/polyscore.cpp).
  * A matrix is a CSR list of reads: read r lists (position, allele) entries read_ptr[r] .. read_ptr[r+1]-1, positions in genome
  * coordinates as Read::getPosition gives them, as AlleleMatrix(ReadSet*) takes them (:59-91): the first and last LISTED entry are the
  * read's first / last position, a position listed twice keeps the allele listed last and counts twice in the depths.  An empty read

@@ -1,20 +1,29 @@
 """GPU: polyphase read scoring on the device.  Against every recorded result of the reference (tests/golden/make_polyphase_golden.py),
 bit-identical to the host pair loop of the debug library on large random blocks (50 000 long-read-like reads with windows of hundreds
 of partners and anchors spanning 20 000 variants), a batch of 500 blocks against the same blocks one by one, and the calls that need
-no device work."""
+no device work.  The second recording (NaN scores, ploidy up to 15, 16 alleles, far-apart positions, long shared stretches) the same
+way; and what the kernels do at their edges, device against host pair loop on the arrays and on every count: candidate counts around
+the wave and block size with the last pair kept or not, batches whose waves hold dozens of matrices (the per-lane counting), more than
+65 536 reads in one call (sort keys of more than 32 bits), 16 alleles and ploidy 15 at size."""
 import numpy as np
 import pytest
 
-from polyphase_cases import expected, load, matrix, random_block, ulp_distance
+from polyphase_cases import EDGE_KINDS, expected, load, load_edge, matrix, pair_count_matrix, random_block, ulp_distance
 from whatshap_amd import polyphase
 
 pytestmark = pytest.mark.gpu
 
 CASES = load()
+EDGE = load_edge()
+COUNTS = ("err", "n_candidates", "n_overlapping", "n_entries", "n_nan", "n_pair_positions")
 
 
 def same(a, b):
     return all(np.array_equal(x, y) for x, y in zip(a.arrays(), b.arrays()))
+
+
+def same_counts(a, b):
+    return all(a[k] == b[k] for k in COUNTS)
 
 
 def check(case, got, stats):
@@ -47,6 +56,141 @@ def test_device_equals_reference_as_batches():
             check(case, g, st)
 
 
+@pytest.mark.parametrize("kind", EDGE_KINDS)
+def test_device_equals_edge_recording_and_host(kind):
+    """Case by case and as batches by (minOverlap, ploidy, err): against the recording, and identical to the host loop."""
+    cases = [c for c in EDGE if c["kind"] == kind]
+    ms = [matrix(c) for c in cases]
+    one = []
+    for case, m in zip(cases, ms):
+        st, host_st = {}, {}
+        got = polyphase.scoreReadset(m, case["min_overlap"], case["ploidy"], case["err"], stats=st)
+        host = polyphase.scoreReadset(m, case["min_overlap"], case["ploidy"], case["err"], host=True, stats=host_st)
+        assert same(got, host) and same_counts(st, host_st)
+        one.append((got, st))
+    groups = {}
+    for k, case in enumerate(cases):
+        groups.setdefault((case["min_overlap"], case["ploidy"], case["err"]), []).append(k)
+    batched = [None] * len(cases)
+    for (mo, ploidy, err), ks in groups.items():
+        stats = []
+        got = polyphase.score_readsets_batch([ms[k] for k in ks], mo, ploidy, err, stats=stats)
+        for k, g, st in zip(ks, got, stats):
+            assert same(g, one[k][0]) and same_counts(st, one[k][1])
+            batched[k] = (g, st)
+    for case, (got, st), (g, bst) in zip(cases, one, batched):
+        check(case, got, st)
+        check(case, g, bst)
+    if kind == "nan":
+        assert all(st["n_nan"] > 0 for _, st in one) and any(st["n_entries"] > 0 for _, st in one)
+
+
+@pytest.mark.parametrize("last_stored", [True, False])
+@pytest.mark.parametrize("n_pairs", [1, 63, 64, 65, 255, 256, 257])
+def test_pair_count_edges(n_pairs, last_stored):
+    """A last wave of 1, 63, 64 lanes, one block and one lane more or less, the last pair kept or not (n_kept = keep[last] + slot[last])."""
+    am, shared = pair_count_matrix([True] * (n_pairs - 1) + [last_stored])
+    st, host_st = {}, {}
+    got = polyphase.scoreReadset(am, 2, 2, 0.07, stats=st)
+    host = polyphase.scoreReadset(am, 2, 2, 0.07, host=True, stats=host_st)
+    n_stored = n_pairs - 1 + last_stored
+    assert st["n_candidates"] == n_pairs and st["n_overlapping"] == st["n_entries"] == n_stored
+    assert st["n_nan"] == 0 and st["n_pair_positions"] == shared
+    i, j, _ = got.arrays()
+    assert i.tolist() == list(range(1, n_stored + 1)) and not j.any()
+    assert same(got, host) and same_counts(st, host_st)
+
+
+@pytest.mark.parametrize("which", [0, 2, 4])
+def test_exactly_one_stored_pair(which):
+    am, shared = pair_count_matrix([q == which for q in range(5)])
+    st, host_st = {}, {}
+    got = polyphase.scoreReadset(am, 2, 2, 0.07, stats=st)
+    host = polyphase.scoreReadset(am, 2, 2, 0.07, host=True, stats=host_st)
+    assert st["n_candidates"] == 5 and st["n_overlapping"] == st["n_entries"] == 1 and st["n_pair_positions"] == shared == 6
+    assert got.getEntries() == [(which + 1, 0)]
+    assert same(got, host) and same_counts(st, host_st)
+
+
+def test_waves_that_span_matrices():
+    """Several hundred matrices of 1 - 5 candidate pairs (one wave holds dozens of them: every count then comes from the per-lane
+    atomics), one of a few thousand pairs in between (uniform waves again), matrices without candidates first, in the middle and last
+    (the mapping from uploaded to given matrices), at an err whose square overflows, so that NaN and stored pairs lie side by side."""
+    mo, ploidy, err = 1, 6, 3e153
+    drawn = [polyphase.AlleleMatrix.from_csr(*random_block(5000 + b, 2 + b % 3, 6, ploidy=6, n_alleles=3, min_len=2, max_len=4)) for b in range(450)]
+    stats = []
+    polyphase.score_readsets_batch(drawn, mo, ploidy, err, host=True, stats=stats)
+    small = [m for m, st in zip(drawn, stats) if 1 <= st["n_candidates"] <= 5]
+    assert len(small) >= 300
+    big = polyphase.AlleleMatrix.from_csr(*random_block(77, 300, 200, ploidy=6, n_alleles=3, min_len=5, max_len=20))
+    disjoint = polyphase.AlleleMatrix.from_csr([0, 2, 4, 6], [10, 11, 20, 21, 30, 31], [0, 1, 1, 0, 0, 1])
+    single = polyphase.AlleleMatrix.from_csr([0, 3], [10, 20, 30], [0, 1, 2])
+    blocks = [polyphase.AlleleMatrix()] + small[:150] + [big] + small[150:250] + [disjoint] + small[250:] + [single]
+    dev_st, host_st = [], []
+    dev = polyphase.score_readsets_batch(blocks, mo, ploidy, err, stats=dev_st)
+    host = polyphase.score_readsets_batch(blocks, mo, ploidy, err, host=True, stats=host_st)
+    assert [k for k, st in enumerate(host_st) if st["n_candidates"] == 0] == [0, 252, len(blocks) - 1]
+    assert 2000 <= host_st[151]["n_candidates"] <= 9000
+    assert sum(1 for st in host_st if st["n_nan"] > 0 and st["n_candidates"] <= 5) >= 10
+    assert sum(1 for st in host_st if st["n_entries"] > 0 and st["n_candidates"] <= 5) >= 100
+    assert sum(st["n_pair_positions"] for st in host_st) > sum(st["n_overlapping"] for st in host_st) > 0
+    assert dev_st[0]["launches"] == 4
+    for m, d, h, dst, hst in zip(blocks, dev, host, dev_st, host_st):
+        one_st = {}
+        one = polyphase.scoreReadset(m, mo, ploidy, err, stats=one_st)
+        assert same(d, h) and same(d, one)
+        assert same_counts(dst, hst) and same_counts(dst, one_st)
+
+
+def largest_key(i, j, read_base, n):
+    return (read_base + int(i[-1])) * n + read_base + int(j[-1])
+
+
+def test_one_matrix_of_more_than_65536_reads():
+    """Sort keys max(id) * N + min(id) of 33 bits: compaction, the radix sort's end bit and the host's key / N, key % N."""
+    n = 70_000
+    am = polyphase.AlleleMatrix.from_csr(*random_block(11, n, 28_000, ploidy=4, n_alleles=2, min_len=2, max_len=6))
+    st, host_st = {}, {}
+    got = polyphase.scoreReadset(am, 1, 4, 0.07, stats=st)
+    host = polyphase.scoreReadset(am, 1, 4, 0.07, host=True, stats=host_st)
+    i, j, _ = got.arrays()
+    assert largest_key(i, j, 0, n) >= 2**32 and i[-1] >= n - 5     # entries among the last reads
+    assert (i.astype(np.uint64) * n + j >= 2**32).sum() > 10_000
+    assert 5 * n < st["n_candidates"] < 20 * n                       # windows of about ten partners
+    assert same(got, host) and same_counts(st, host_st)
+
+
+def test_batch_of_more_than_65536_reads():
+    """The same with the reads spread over 1 200 blocks: global ids read_base + i, and the cut of the sorted keys at read_base * N."""
+    blocks = [polyphase.AlleleMatrix.from_csr(*random_block(9000 + b, 56, 80, ploidy=4, n_alleles=2, min_len=2, max_len=8)) for b in range(1200)]
+    dev_st, host_st = [], []
+    dev = polyphase.score_readsets_batch(blocks, 1, 4, 0.07, stats=dev_st)
+    host = polyphase.score_readsets_batch(blocks, 1, 4, 0.07, host=True, stats=host_st)
+    assert all(st["n_candidates"] > 0 for st in host_st)             # every block is uploaded: read_base is the sum of the sizes before
+    n = sum(len(b) for b in blocks)
+    assert n > 65_536
+    i, j, _ = dev[-1].arrays()
+    assert largest_key(i, j, n - len(blocks[-1]), n) >= 2**32 and i[-1] >= len(blocks[-1]) - 5
+    assert sum(1 for b in range(1200) if len(dev[b]) and largest_key(*dev[b].arrays()[:2], 56 * b, n) >= 2**32) > 50
+    assert dev_st[0]["launches"] == 4
+    for d, h, dst, hst in zip(dev, host, dev_st, host_st):
+        assert same(d, h) and same_counts(dst, hst)
+    for b in list(range(0, 1200, 100)) + [1199]:
+        one_st = {}
+        assert same(dev[b], polyphase.scoreReadset(blocks[b], 1, 4, 0.07, stats=one_st)) and same_counts(dev_st[b], one_st)
+
+
+@pytest.mark.parametrize("ploidy,n_alleles", [(2, 16), (15, 2)])
+def test_sixteen_alleles_and_ploidy_15_at_size(ploidy, n_alleles):
+    am = polyphase.AlleleMatrix.from_csr(*random_block(21, 3000, 2500, ploidy=ploidy, n_alleles=n_alleles, min_len=10, max_len=60))
+    assert am.getMaxNumAllele() == n_alleles
+    st, host_st = {}, {}
+    got = polyphase.scoreReadset(am, 2, ploidy, 0.07, stats=st)
+    host = polyphase.scoreReadset(am, 2, ploidy, 0.07, host=True, stats=host_st)
+    assert st["n_candidates"] > 100_000 and st["n_entries"] > 50_000
+    assert same(got, host) and same_counts(st, host_st)
+
+
 # (three alleles at ploidy 6 with err = 0 would test little: the reference's estimate is then 0.0 -- every depth sum is NaN or -inf,
 # none beats the initial -inf -- and every term is 0 or NaN)
 @pytest.mark.parametrize("seed,ploidy,n_alleles,min_overlap,err", [(1, 4, 2, 2, 0.07), (2, 6, 2, 1, 0.0), (3, 3, 3, 1, 0.07)])
@@ -60,7 +204,7 @@ def test_device_bit_identical_to_host_on_large_block(seed, ploidy, n_alleles, mi
     assert dev_st["n_candidates"] > 50_000 * 100          # windows of hundreds
     assert dev_st["n_entries"] > 1_000_000
     assert same(dev, host)
-    for k in ("err", "n_candidates", "n_overlapping", "n_entries", "n_nan", "n_pair_positions"):
+    for k in COUNTS:
         assert dev_st[k] == host_st[k], k
     assert dev_st["launches"] > 0
 
@@ -77,7 +221,7 @@ def test_batch_of_500_blocks_equals_one_by_one():
         one_st = {}
         one = polyphase.scoreReadset(m, 2, 4, 0.0, stats=one_st)
         assert same(b, one)
-        assert st["n_entries"] == one_st["n_entries"] and st["err"] == one_st["err"]
+        assert same_counts(st, one_st)
 
 
 def test_edge_cases_return_without_launch():

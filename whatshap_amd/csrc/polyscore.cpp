@@ -88,11 +88,13 @@ double log_multinom_pmf(const std::vector<uint32_t>& n, const std::vector<double
 struct GenotypeTable {
 	uint32_t ploidy = 0, n_alleles = 0;
 	std::vector<std::vector<uint32_t>> alleles;   // [C(ploidy + n_alleles - 1, n_alleles - 1)]
+	std::vector<uint64_t> code;                   // Genotype::get_code(): allele i in bits 4 i .. 4 i + 3, the ploidy in bits 60 .. 63
 	void build(uint32_t p, uint32_t a) {
 		ploidy = p;
 		n_alleles = a;
 		const int n = a ? binomial_coefficient((int)(p + a - 1), (int)a - 1) : 0;
 		alleles.assign(n, {});
+		code.assign(n, 0);
 		if (!n) return;
 		std::vector<uint32_t> cur(p, 0);   // ascending
 		// every multiset of size p over [0, a): index = sum_i C(cur[i] + i, i + 1)
@@ -101,6 +103,8 @@ struct GenotypeTable {
 				uint64_t index = 0;
 				for (uint32_t i = 0; i < p; i++) index += (uint64_t)binomial_coefficient((int)(cur[i] + i), (int)(i + 1));
 				alleles[index].assign(cur.rbegin(), cur.rend());
+				code[index] = (uint64_t)p << 60;
+				for (uint32_t i = 0; i < p; i++) code[index] |= (uint64_t)alleles[index][i] << (4 * i);
 				return;
 			}
 			for (uint32_t x = from; x < a; x++) {
@@ -112,10 +116,63 @@ struct GenotypeTable {
 	}
 };
 
-// computeGenotypeLikelihoods (readscoring.cpp:123-191): (genotype index, likelihood) of the reachable genotypes, in increasing index.
-// Quirks kept: one present allele -> 1, then exp(1 - 0) / (1 + e) after normalisation; two present alleles -> fracAlt = index / ploidy
-// (the enumeration index, not the alt count); any exp that overflows (or is NaN) -> every depth halved, all of it again.  The reference
-// normalises in its unordered_map's order; the sum here runs in increasing index.
+// The order in which the reference walks the genotypes of one position: that of its std::unordered_map<Genotype, double>, filled in
+// increasing index and hashed by the genotype's code.  The sums over a position's genotypes (the normalising weight here, same / diff in
+// poly_prepare) run in it, and it decides more than a last bit: where same / diff is 1 but for rounding (two different alleles at a
+// position with six alleles present and err = 0.2), the term is 0.0 in one order and 1e-16 in another, and a pair whose terms are all
+// 0.0 is not stored.  Restated for GNU libstdc++, which the reference is built with on Linux: buckets are code % count, the count grows
+// 1 -> 13 -> 29 -> ... whenever the elements would outnumber it, a node enters at the front of its bucket's stretch of the one list, or
+// at the list's head when the bucket is empty, and a growth re-enters every node that way in list order.
+void hash_order(const std::vector<uint64_t>& code, std::vector<std::pair<uint32_t, double>>& gl) {
+	static const uint32_t COUNTS[] = {13, 29, 59, 127, 257, 541, 1109, 2357, 5087, 10273, 20753, 42043, 85229, 172933, 351061, 712697, 1447153};
+	const uint32_t n = (uint32_t)gl.size();
+	if (n < 2 || n > COUNTS[sizeof(COUNTS) / sizeof(COUNTS[0]) - 1]) return;   // (more genotypes than any real call has: index order)
+	constexpr int32_t NONE = -1, EMPTY = -2, HEAD = -1;   // a bucket holds the node before its first one (HEAD: the list's head)
+	std::vector<int32_t> next(n, NONE), before;
+	int32_t head = NONE;
+	uint32_t n_buckets = 1, grown = 0;
+	before.assign(1, EMPTY);
+	auto key = [&](int32_t node) { return code[gl[node].first]; };
+	auto enter = [&](int32_t node, uint32_t& head_bucket, bool rehash) {
+		const uint32_t b = (uint32_t)(key(node) % n_buckets);
+		if (before[b] != EMPTY) {
+			int32_t& after = before[b] == HEAD ? head : next[before[b]];
+			next[node] = after;
+			after = node;
+			return;
+		}
+		next[node] = head;
+		head = node;
+		before[b] = HEAD;
+		if (next[node] != NONE) before[rehash ? head_bucket : (uint32_t)(key(next[node]) % n_buckets)] = node;
+		head_bucket = b;
+	};
+	for (uint32_t k = 0; k < n; k++) {
+		if (k + 1 > n_buckets || k == 0) {   // (the first element already finds one bucket too few: libstdc++ starts at 13)
+			n_buckets = COUNTS[grown++];
+			before.assign(n_buckets, EMPTY);
+			int32_t node = head;
+			head = NONE;
+			uint32_t head_bucket = 0;
+			while (node != NONE) {
+				const int32_t following = next[node];
+				enter(node, head_bucket, true);
+				node = following;
+			}
+		}
+		uint32_t unused = 0;
+		enter((int32_t)k, unused, false);
+	}
+	std::vector<std::pair<uint32_t, double>> walked;
+	walked.reserve(n);
+	for (int32_t node = head; node != NONE; node = next[node]) walked.push_back(gl[node]);
+	gl.swap(walked);
+}
+
+// computeGenotypeLikelihoods (readscoring.cpp:123-191): (genotype index, likelihood) of the reachable genotypes, in the reference's
+// order (hash_order).  Quirks kept: one present allele -> 1, then exp(1 - 0) / (1 + e) after normalisation; two present alleles ->
+// fracAlt = index / ploidy (the enumeration index, not the alt count); any exp that overflows (or is NaN) -> every depth halved, all of
+// it again.
 void genotype_likelihoods(const GenotypeTable& gt, const uint32_t* depth_in, double err, std::vector<std::pair<uint32_t, double>>& gl) {
 	const uint32_t n_alleles = gt.n_alleles, ploidy = gt.ploidy;
 	std::vector<uint32_t> depth(depth_in, depth_in + n_alleles);
@@ -155,6 +212,7 @@ void genotype_likelihoods(const GenotypeTable& gt, const uint32_t* depth_in, dou
 				gl.emplace_back(index, l);
 			}
 		}
+		hash_order(gt.code, gl);
 		bool overflow = false;
 		for (auto& e : gl) {
 			const double l = std::exp(e.second - lowest);
@@ -344,7 +402,7 @@ void whamd::poly_prepare(PolyMatrix& m, uint32_t min_overlap, uint32_t ploidy, d
 		for (const auto& x : gl) have[x.first] = 1;
 	for (size_t g = 0; g < G; g++)
 		if (have[g]) allele_pair_likelihoods(gt.alleles[g], A, err, apls.data() + g * AA, apld.data() + g * AA);
-	// computeLogScoreSinglePos (readscoring.cpp:255-279) for every (position, a1, a2), genotypes in increasing index
+	// computeLogScoreSinglePos (readscoring.cpp:255-279) for every (position, a1, a2), genotypes in the order of genotype_likelihoods
 	m.terms.assign((size_t)P * AA, 0.0f);
 	parallel_ranges(P, n_threads, [&](uint64_t b, uint64_t e, uint32_t) {
 		for (uint64_t p = b; p < e; p++) {

@@ -3,8 +3,8 @@
 
 The matrices, genotype likelihoods and the per-position term tables are computed on the host inside the native library, the pair loop on
 the device; ``host=True`` runs the pair loop of the debug library on the host instead (test infrastructure, bit-identical to the device).
-Scores equal the reference's except where its unordered_map order of summing genotypes moves a term by one float ulp; the stored set,
-NaN count and estimated error rate are the same.  There is no CPU fallback: without a device the native library raises.
+A position's genotypes are summed in the order of the reference's unordered_map (as GNU libstdc++ iterates it; csrc/polyscore.cpp): the
+stored set, scores, NaN count and estimated error rate equal the reference's on every recorded case.  There is no CPU fallback: without a device the native library raises.
 """
 
 from __future__ import annotations
