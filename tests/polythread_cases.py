@@ -1,7 +1,8 @@
 """Seeded cases for the polyphase threading inputs (whatshap_amd/polythread.py): the smallest shapes at which each piece of
 get_allele_depths, select_clusters and compute_haplotypes can go wrong, a few dozen random blocks, and the larger shapes that are only
 compared between the device and the host twin.  tests/golden/make_polythread_golden.py records what the reference returns for
-``all_cases()`` and ``select_cases()``; the tests read the recorded data.
+``all_cases()`` and ``select_cases()``; the tests read the recorded data.  Further down: a plain restatement of the rules (numpy and
+Python, nothing of the library), the shapes built from run lengths, and the checks the host and the GPU tests share.
 
 A case: ``reads`` (rows of (local position, allele), as listed), ``n_pos``, ``clustering`` (lists of read ids, each in its own order),
 ``ploidy``, ``max_gap``.  A select case: ``depths`` per position as [[cluster, [[allele, count], ...]], ...] in dict order."""
@@ -305,6 +306,329 @@ def edge_reads_arrays(n_entries=600, n_clusters=5):
     cluster_of = rng.integers(0, n_clusters, size=len(read_ptr) - 1)
     clustering = [rng.permutation(np.flatnonzero(cluster_of == c)).astype(np.uint32) for c in range(n_clusters)]
     return read_ptr, 100 + 7 * local, alle, clustering
+
+
+# ---------------------------------------------------------------------------------------------- a plain restatement
+# numpy and Python only, nothing of the library: the rules as DESIGN.md (section 20) and csrc/polythread.h state them.  The host tests
+# hold it to every recorded case first; then it is the reference at sizes the fixture cannot hold, where the device and the host twin
+# share pt_consensus, pt_select and pt_haplotype_position and a fault in those would pass a comparison of the two.
+NO_READ = 0xFFFFFFFF
+
+
+class Restated:
+    """The rows of one problem: ``n_pos``, ``ptr`` [n_pos + 1], per row ``cluster`` (ascending within a position), ``depth`` and ``first``
+    [rows][n_alleles], ``total``."""
+
+    def __init__(self, n_pos, ptr, cluster, depth, first):
+        self.n_pos, self.ptr, self.cluster, self.depth, self.first, self.total = n_pos, ptr, cluster, depth, first, depth.sum(axis=1)
+
+
+def restate_rows(read_ptr, positions, alleles, clustering, n_alleles):
+    """Per local position (the rank of the global one among all listed) and cluster with a read there, in ascending cluster id: how many
+    of the cluster's reads show each allele, and the smallest rank, in the cluster's list, of a read that shows it (NO_READ: none).  A
+    read that lists a position twice shows the allele listed last; a read in no cluster counts nowhere."""
+    read_ptr = np.asarray(read_ptr).astype(np.int64)
+    positions, alleles = np.asarray(positions, dtype=np.int64), np.asarray(alleles, dtype=np.int64)
+    n_reads = len(read_ptr) - 1
+    read_of = np.repeat(np.arange(n_reads, dtype=np.int64), np.diff(read_ptr))
+    local = np.unique(positions, return_inverse=True)[1].reshape(-1)
+    n_pos = int(local.max()) + 1 if local.size else 0
+    slot = read_of * n_pos + local
+    last = slot.size - 1 - np.unique(slot[::-1], return_index=True)[1]   # of the entries of one (read, position), the last listed
+    read_of, local, alleles = read_of[last], local[last], alleles[last]
+    cluster_of, rank_of = np.full(n_reads, -1, dtype=np.int64), np.zeros(n_reads, dtype=np.int64)
+    for c, members in enumerate(clustering):
+        members = np.asarray(members, dtype=np.int64).reshape(-1)
+        cluster_of[members] = c
+        rank_of[members] = np.arange(members.size)
+    counted = cluster_of[read_of] >= 0
+    local, alleles, cluster, rank = local[counted], alleles[counted], cluster_of[read_of[counted]], rank_of[read_of[counted]]
+    n_clusters = max(1, len(clustering))
+    pair, row_of = np.unique(local * n_clusters + cluster, return_inverse=True)
+    row_of = row_of.reshape(-1)
+    depth = np.zeros((pair.size, n_alleles), dtype=np.int64)
+    first = np.full((pair.size, n_alleles), NO_READ, dtype=np.int64)
+    np.add.at(depth, (row_of, alleles), 1)
+    np.minimum.at(first, (row_of, alleles), rank)
+    ptr = np.zeros(n_pos + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pair // n_clusters, minlength=n_pos), out=ptr[1:])
+    return Restated(n_pos, ptr, pair % n_clusters, depth, first)
+
+
+def restate_consensus(depth, first, ploidy):
+    """One row's consensus list: ``ploidy`` picks, each the allele of largest depth / (1 + times picked) as a Python float; equal
+    quotients go to the allele a read of the list showed first; an allele no read shows is never picked."""
+    times = [0] * len(depth)
+    picks = []
+    for _ in range(ploidy):
+        best = None
+        for a, n in enumerate(depth):
+            if n == 0:
+                continue
+            q = n / (1 + times[a])
+            if best is None or q > best_q or (q == best_q and first[a] < first[best]):
+                best, best_q = a, q
+        picks.append(best)
+        times[best] += 1
+    return picks
+
+
+def restate_consensus_rows(depth, first, ploidy):
+    """restate_consensus for every row.  A row with one allele shown can pick no other, whatever the quotients: those are filled in
+    at once, so that half a million rows of one entry do not each take a Python loop."""
+    out = np.zeros((len(depth), ploidy), dtype=np.int64)
+    one = (depth > 0).sum(axis=1) == 1
+    out[one] = np.argmax(depth[one] > 0, axis=1)[:, None]
+    for row in np.flatnonzero(~one).tolist():
+        out[row] = restate_consensus(depth[row].tolist(), first[row].tolist(), ploidy)
+    return out
+
+
+def restate_selection(totals, ploidy):
+    """A position's own selection among its rows of total depth ``totals`` (Python ints, in row order): rows by descending total, equal
+    ones in row order; the first always, then up to min(n, ploidy + 2) in all, ending at the first whose share of the sum is below
+    1.0 / (8.0 * ploidy) in Python floats.  The chosen row indices in that order."""
+    order = sorted(range(len(totals)), key=lambda k: -totals[k])   # (stable)
+    everything = sum(totals)
+    chosen = order[:1]
+    for k in order[1:min(len(totals), ploidy + 2)]:
+        if totals[k] / everything < 1.0 / (8.0 * ploidy):
+            break
+        chosen.append(k)
+    return chosen
+
+
+def restate_selections(ptr, total, ploidy):
+    """restate_selection at every position: (sel_ptr [n_pos + 1], the chosen rows as indices into the rows of the problem).  A position
+    of one row selects it -- the first is always taken --, which is filled in at once."""
+    ptr = np.asarray(ptr, dtype=np.int64)
+    n_rows_of = np.diff(ptr)
+    chosen = {x: restate_selection(total[ptr[x]:ptr[x + 1]].tolist(), ploidy) for x in np.flatnonzero(n_rows_of != 1).tolist()}
+    count = (n_rows_of == 1).astype(np.int64)
+    for x, rows in chosen.items():
+        count[x] = len(rows)
+    sel_ptr = np.zeros(len(ptr), dtype=np.int64)
+    np.cumsum(count, out=sel_ptr[1:])
+    sel_row = np.zeros(int(sel_ptr[-1]), dtype=np.int64)
+    single = np.flatnonzero(n_rows_of == 1)
+    sel_row[sel_ptr[single]] = ptr[single]
+    for x, rows in chosen.items():
+        sel_row[sel_ptr[x]:sel_ptr[x + 1]] = ptr[x] + np.asarray(rows, dtype=np.int64)
+    return sel_ptr, sel_row
+
+
+def restate_haplotypes(paths, ptr, cluster, consensus, ploidy):
+    """out[i][x]: the pick, of the consensus list of cluster paths[x][i] among the rows of position x, whose number is how many earlier
+    slots of x name the same cluster; -1 where that cluster has no row at x."""
+    ptr, cluster, consensus = np.asarray(ptr).tolist(), np.asarray(cluster).tolist(), np.asarray(consensus).tolist()
+    out = np.full((ploidy, len(ptr) - 1), -1, dtype=np.int64)
+    for x, slots in enumerate(np.asarray(paths).tolist()):
+        row_of = {cluster[row]: row for row in range(ptr[x], ptr[x + 1])}
+        seen = {}
+        for i, cid in enumerate(slots[:ploidy]):
+            nth = seen.get(cid, 0)
+            seen[cid] = nth + 1
+            if cid in row_of:
+                out[i][x] = consensus[row_of[cid]][nth]
+    return out
+
+
+def own_selection(res):
+    """What each position selected from its own depths, in the order of selecting, out of a result's lists: the entries that were not
+    re-added, by ``cov_rank`` (the original selection keeps its places in front of what the gap filling appends).  (sel_ptr, cluster ids)."""
+    n_pos = len(res.cov_ptr) - 1
+    position = np.repeat(np.arange(n_pos, dtype=np.int64), np.diff(res.cov_ptr.astype(np.int64)))
+    own = np.flatnonzero(res.cov_readded == 0)
+    own = own[np.lexsort((res.cov_rank[own], position[own]))]
+    sel_ptr = np.zeros(n_pos + 1, dtype=np.int64)
+    np.cumsum(np.bincount(position[own], minlength=n_pos), out=sel_ptr[1:])
+    return sel_ptr, res.cov_cluster[own].astype(np.int64)
+
+
+def check_against_restatement(res, arrays, ploidy):
+    """One problem's result arrays (device or host twin) against the restatement of its input: rows, depths (zero in a re-added
+    cluster's row, which is what the gap filling leaves), first, consensus lists and every position's own selection.  Returns the
+    restated rows."""
+    read_ptr, positions, alleles, clustering = arrays
+    want = restate_rows(read_ptr, positions, alleles, clustering, res.n_alleles)
+    assert want.n_pos == len(res.pc_ptr) - 1
+    assert np.array_equal(res.pc_ptr, want.ptr) and np.array_equal(res.pc_cluster, want.cluster)
+    assert np.array_equal(res.pc_first, want.first)
+    n_ids = len(clustering) + 1
+    cov_position = np.repeat(np.arange(want.n_pos, dtype=np.int64), np.diff(res.cov_ptr.astype(np.int64)))
+    readded = (cov_position * n_ids + res.cov_cluster)[res.cov_readded != 0]
+    row_position = np.repeat(np.arange(want.n_pos, dtype=np.int64), np.diff(want.ptr))
+    emptied = np.isin(row_position * n_ids + want.cluster, readded)
+    assert np.array_equal(res.pc_depth, np.where(emptied[:, None], 0, want.depth))
+    assert np.array_equal(res.pc_consensus, restate_consensus_rows(want.depth, want.first, ploidy))
+    sel_ptr, sel_row = restate_selections(want.ptr, want.total, ploidy)
+    got_ptr, got_cluster = own_selection(res)
+    assert np.array_equal(got_ptr, sel_ptr) and np.array_equal(got_cluster, want.cluster[sel_row])
+    return want
+
+
+# ---------------------------------------------------------------------------------------------- shapes built from run lengths
+def runs_problem(runs, clusters_per_run, ploidy, n_alleles, seed, max_gap=0):
+    """One single-entry read per counted entry: position x has runs[x] entries, entry k of the run in cluster k mod clusters_per_run[x].
+    Random alleles; the reads in shuffled order (the read-major entries are not sorted by position), every cluster's list shuffled.
+    Returns (arrays, ploidy, max_gap) as small_blocks() does."""
+    rng = np.random.default_rng(seed)
+    runs, per_run = np.asarray(runs, dtype=np.int64), np.asarray(clusters_per_run, dtype=np.int64)
+    assert runs.shape == per_run.shape and (runs >= 1).all() and (per_run >= 1).all()
+    n = int(runs.sum())
+    begin = np.cumsum(runs) - runs
+    position = np.repeat(np.arange(runs.size, dtype=np.int64), runs)
+    cluster = (np.arange(n, dtype=np.int64) - np.repeat(begin, runs)) % np.repeat(per_run, runs)
+    entry_of_read = rng.permutation(n)
+    position, cluster = position[entry_of_read], cluster[entry_of_read]
+    alleles = rng.integers(0, n_alleles, size=n)
+    members = rng.permutation(n)
+    members = members[np.argsort(cluster[members], kind="stable")]
+    ends = np.cumsum(np.bincount(cluster, minlength=int(per_run.max())))
+    clustering = [m.astype(np.uint32) for m in np.split(members, ends[:-1])]
+    return (np.arange(n + 1, dtype=np.uint64), 100 + 7 * position, alleles, clustering), ploidy, max_gap
+
+
+# Run lengths on both sides of everything that changes a team's path (read from the headers by the tests): the segment's eight lanes,
+# the wave, the workgroup, the class bounds; 128 is two waves' worth.
+def header_constants():
+    """The constants the run lengths below are built around, as the headers of today have them."""
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "whatshap_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, name)).read() for name in ("run_scatter.h", "run_teams.h", "polythread.h"))
+    out = {name: int(re.search(r"constexpr uint32_t %s = (\d+);" % name, text).group(1))
+           for name in ("RS_SEGMENT", "RS_BLOCK", "RS_SCAN_TILE", "PT_CLASS_A_MAX", "PT_CLASS_B_MAX")}
+    out["WAVE"] = int(re.search(r"constexpr int RT_WAVES = \(int\)RS_BLOCK / (\d+);", text).group(1))
+    return out
+
+
+def boundary_runs(k=None):
+    k = k or header_constants()
+    segment, wave, block, a_max, b_max = k["RS_SEGMENT"], k["WAVE"], k["RS_BLOCK"], k["PT_CLASS_A_MAX"], k["PT_CLASS_B_MAX"]
+    return tuple(sorted({1, 2, 127, 128, 129} | {c + d for c in (segment, wave, block, a_max, b_max) for d in (-1, 0, 1)}))
+
+
+def boundary_problem(runs, k, ploidy, n_alleles):
+    return runs_problem(runs, [min(k, r) for r in runs], ploidy, n_alleles, seed=900 + 16 * k + n_alleles)
+
+
+def classes_of(runs, a_max, b_max):
+    runs = np.asarray(runs)
+    return int((runs <= a_max).sum()), int(((runs > a_max) & (runs <= b_max)).sum()), int((runs > b_max).sum())
+
+
+CARRY_TILES = 257   # one more than the single workgroup of the second scan launch takes per pass
+CARRY_KEYS = {0: (3, 2), 2047: (1, 1), 2048: (2, 2), 2049: (5, 3), 524_287: (7, 4), 524_288: (6, 3), 2048 * 255 + 100: (65, 9), 2048 * 255 + 1000: (4097, 5)}
+
+
+def carry_problem(scan_tile=2048):
+    """(CARRY_TILES - 1) scan tiles and one position: runs of one entry, but for CARRY_KEYS (position: run, clusters) -- the class b and
+    the class c run in the last full tile, behind the carry, and more than one row on both sides of the last tile's edge."""
+    n_pos = scan_tile * (CARRY_TILES - 1) + 1
+    runs, per_run = np.ones(n_pos, dtype=np.int64), np.ones(n_pos, dtype=np.int64)
+    for x, (run, clusters) in CARRY_KEYS.items():
+        runs[x], per_run[x] = run, clusters
+    return runs_problem(runs, per_run, 2, 3, seed=257)
+
+
+def tie_cases(alleles=(0, 1), n_alleles=2):
+    """A position of 4 500 entries (one workgroup) and one of 300 (one wave), one cluster, two alleles of depths 2 : 1, ploidy 4: the
+    second pick ties 3000 / 2 against 1500 / 1 (200 / 2 against 100 / 1) and goes to the allele shown first.  Two cases: the cluster's
+    list as made (a read of the first allele of the pair in front) and reversed (one of the second)."""
+    def row(deep, shallow):
+        depth = [0] * n_alleles
+        depth[alleles[0]], depth[alleles[1]] = deep, shallow
+        return {0: depth}
+
+    table = [row(3000, 1500), row(200, 100)]
+    return [from_depths(f"tie_alleles_{alleles[0]}_{alleles[1]}_first_{alleles[0]}", table, 4, 0),
+            from_depths(f"tie_alleles_{alleles[0]}_{alleles[1]}_first_{alleles[1]}", table, 4, 0, reverse=(0,))]
+
+
+def arrays_of(c):
+    """A case as (read_ptr, positions, alleles, clustering)."""
+    return (*csr_of(c), c["clustering"])
+
+
+def check_ties(results, cases, alleles):
+    """Both orders of tie_cases against the restatement, and the two consensus lists differ as the rule says."""
+    for res, c in zip(results, cases):
+        check_against_restatement(res, arrays_of(c), c["ploidy"])
+    a, b = alleles
+    for x in (0, 1):
+        assert results[0].pc_consensus[x].tolist() == [a, a, b, a] and results[1].pc_consensus[x].tolist() == [a, b, a, a]
+
+
+# ---------------------------------------------------------------------------------------------- the selection's threshold, met exactly
+THRESHOLD_M = (1, 2, 3, 7, 11, 1_000_003, 33_554_431)
+
+
+def threshold_triples():
+    """(ploidy, m, d, large): two clusters of depths large = 8 * ploidy * m + d - m and m, so m / (large + m) is 1 / (8 * ploidy)
+    exactly at d = 0 (kept: not below), just below at d = +1 (dropped) and just above at d = -1 (kept)."""
+    out = []
+    for ploidy in range(1, 17):
+        for m in THRESHOLD_M:
+            for d in (0, 1, -1):
+                large = 8 * ploidy * m + d - m
+                if large + m >= 1 << 32 or large <= m:
+                    continue
+                out.append((ploidy, m, d, large))
+    return out
+
+
+def check_exact_thresholds(select):
+    """``select(depth dicts, ploidy)``: select_clusters without gap filling.  Every triple of every ploidy goes into every call as a
+    position of its own (336 positions: the stand-alone select launch takes a second workgroup), once per ploidy of the call; what is
+    expected is the Python-float expression itself, and for the call's own triples kept, dropped, kept.  A few go singly."""
+    triples = threshold_triples()
+    assert len(triples) == 336
+    for ploidy in range(1, 17):
+        got = select([{0: {0: large}, 1: {1: m}} for _, m, _, large in triples], ploidy)
+        want = [[0] if m / (large + m) < 1.0 / (8.0 * ploidy) else [0, 1] for _, m, _, large in triples]
+        assert got == want, ploidy
+        own = [(d, len(g) == 2) for (p, _, d, _), g in zip(triples, got) if p == ploidy]
+        assert len(own) == 3 * len(THRESHOLD_M) and all(kept == (d != 1) for d, kept in own), ploidy
+    for ploidy, m, d, large in triples[4::37]:
+        assert select([{0: {0: large}, 1: {1: m}}], ploidy) == [[0, 1] if d != 1 else [0]], (ploidy, m, d)
+
+
+# ---------------------------------------------------------------------------------------------- paths for compute_haplotypes
+HAPLOTYPE_POSITIONS = (255, 256, 257, 2049)   # one thread per position, 256 per workgroup: one workgroup, its edge, two, nine
+
+
+def haplotype_blocks(ploidy):
+    return [(array_problem(700 + 20 * k + ploidy, n_pos, max(12, 3 * ploidy), ploidy, 4, 9, 3), ploidy, 10) for k, n_pos in enumerate(HAPLOTYPE_POSITIONS)]
+
+
+def seeded_paths(res, n_ids, seed):
+    """[n_pos][ploidy]: every slot a cluster of the position's rows; at one position in four the second slot repeats the first; about
+    one slot in twenty names any id up to n_ids instead, which mostly has no row there."""
+    rng = np.random.default_rng(seed)
+    ptr = res.pc_ptr.astype(np.int64)
+    n_pos = len(ptr) - 1
+    rows = ptr[:-1, None] + (rng.random((n_pos, res.ploidy)) * np.diff(ptr)[:, None]).astype(np.int64)
+    paths = res.pc_cluster[rows].astype(np.int64)
+    if res.ploidy > 1:
+        again = rng.random(n_pos) < 0.25
+        paths[again, 1] = paths[again, 0]
+    elsewhere = rng.random(paths.shape) < 0.05
+    return np.where(elsewhere, rng.integers(0, n_ids + 1, size=paths.shape), paths)
+
+
+def check_haplotypes(results, blocks, run):
+    """``run(paths, result)`` -> int8 [ploidy][n_pos] against the restatement on seeded paths; -1 occurs, and some position hands two
+    slots of one cluster different picks."""
+    for k, (res, (arrays, ploidy, _)) in enumerate(zip(results, blocks)):
+        paths = seeded_paths(res, len(arrays[3]), 40 + k)
+        got = run(paths, res)
+        assert got.shape == (ploidy, len(res.pc_ptr) - 1)
+        assert np.array_equal(got, restate_haplotypes(paths, res.pc_ptr, res.pc_cluster, res.pc_consensus, ploidy)), k
+        assert (got == -1).any()
+        if ploidy > 1:
+            assert ((paths[:, 0] == paths[:, 1]) & (got[0] != got[1]) & (got[0] >= 0)).any()
 
 
 # ---------------------------------------------------------------------------------------------- what both test files share

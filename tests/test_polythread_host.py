@@ -1,6 +1,7 @@
 """CPU: the host twin of the polyphase threading inputs (debug library, one thread; the kernels call the same consensus, selection and
 haplotype functions) against everything the reference recorded in tests/golden/polythread_cases.json.gz -- arrays, dict forms, insertion
-orders, the mutation select_clusters leaves --, the refusals, and the reference-signature functions."""
+orders, the mutation select_clusters leaves --, the refusals, and the reference-signature functions.  polythread_cases' plain
+restatement is held to the same record, and the twin to the restatement on the shapes the GPU tests run."""
 import copy
 
 import numpy as np
@@ -184,6 +185,112 @@ def test_larger_ploidy_and_allele_counts_up_to_the_bounds():
                 picks.append(best_al)
                 cnts[best_al] = cnts.get(best_al, 0) + 1
             assert cons[x][cid] == picks
+
+
+# ---------------------------------------------------------------------------------------------- the plain restatement
+def recorded_rows(rec, n_alleles):
+    """(ptr, cluster, depth rows, allele orders, consensus lists) of a recorded case, before select_clusters' side effect."""
+    ptr, cluster, depth, order, cons = [0], [], [], [], []
+    for before, lists in zip(rec["ad"], rec["cons_lists"]):
+        lists = dict((cid, picks) for cid, picks in lists)
+        for cid, alleles in sorted(before):
+            row = [0] * n_alleles
+            for a, n in alleles:
+                row[a] = n
+            cluster.append(cid)
+            depth.append(row)
+            order.append([a for a, _ in alleles])
+            cons.append(lists[cid])
+        ptr.append(len(cluster))
+    return ptr, cluster, depth, order, cons
+
+
+def test_the_restatement_equals_every_recorded_case():
+    """polythread_cases' numpy / Python restatement, which shares nothing with the library, against the reference's record: rows,
+    depths before the side effect, insertion orders, consensus lists, each position's own selection and the haplotypes."""
+    for rec in CASES + [GOLDEN["uncovered"]]:
+        n_alleles = max([a for r in rec["reads"] for _, a in r], default=0) + 1
+        rows = pc.restate_rows(*pc.csr_of(rec), rec["clustering"], n_alleles)
+        ptr, cluster, depth, order, cons = recorded_rows(rec, n_alleles)
+        assert rows.n_pos == rec["n_pos"] and rows.ptr.tolist() == ptr and rows.cluster.tolist() == cluster, rec["name"]
+        assert rows.depth.tolist() == depth and rows.total.tolist() == [sum(row) for row in depth], rec["name"]
+        for first, shown, alleles in zip(rows.first.tolist(), depth, order):
+            assert [first[a] == pc.NO_READ for a in range(n_alleles)] == [n == 0 for n in shown], rec["name"]
+            assert sorted((a for a in range(n_alleles) if shown[a]), key=lambda a: first[a]) == alleles, rec["name"]
+        assert [pc.restate_consensus(d, f, rec["ploidy"]) for d, f in zip(rows.depth.tolist(), rows.first.tolist())] == cons, rec["name"]
+        consensus = pc.restate_consensus_rows(rows.depth, rows.first, rec["ploidy"])
+        assert consensus.tolist() == cons, rec["name"]
+        if "cov_map" not in rec:   # (the refused case: the reference's select_clusters raises)
+            continue
+        sel_ptr, sel_row = pc.restate_selections(rows.ptr, rows.total, rec["ploidy"])
+        for x, (before, after, listed) in enumerate(zip(rec["ad"], rec["ad_after"], rec["cov_map"])):
+            own = rows.cluster[sel_row[sel_ptr[x]:sel_ptr[x + 1]]].tolist()
+            assert sel_row[sel_ptr[x]:sel_ptr[x + 1]].tolist() == [ptr[x] + k for k in pc.restate_selection(rows.total[ptr[x]:ptr[x + 1]].tolist(), rec["ploidy"])]
+            # the recorded list is the own selection and what the gap filling re-added, which the record shows as an emptied or a new dict
+            before = dict((cid, v) for cid, v in before)
+            readded = {cid for cid, v in after if not v and before.get(cid) != v}
+            assert sorted(own) == [cid for cid in listed if cid not in readded], (rec["name"], x)
+            if rec["max_gap"] == 0 or x in (0, rec["n_pos"] - 1):   # (no gap filling there: the list is the own selection)
+                assert sorted(own) == listed, (rec["name"], x)
+        for paths, want in zip(rec["paths"], rec["haplotypes"]):
+            assert pc.restate_haplotypes(paths, rows.ptr, rows.cluster, consensus, rec["ploidy"]).tolist() == want, rec["name"]
+    assert pc.restate_haplotypes([[0, 0, 7]], [0, 1], [0], [[1, 0, 1]], 3).tolist() == [[1], [0], [-1]]
+    assert sum(rec["max_gap"] == 0 for rec in CASES) >= 1
+
+
+def test_the_restated_selection_equals_the_recorded_dict_level_cases():
+    """GOLDEN["select"]: clusters in dict order, equal depths, empty inner dicts."""
+    for rec in GOLDEN["select"]:
+        n_pos = len(rec["depths"])
+        for x, (before, after, listed) in enumerate(zip(rec["depths"], rec["ad_after"], rec["cov_map"])):
+            own = [before[k][0] for k in pc.restate_selection([sum(n for _, n in alleles) for _, alleles in before], rec["ploidy"])]
+            known = dict((cid, v) for cid, v in before)
+            readded = {cid for cid, v in after if not v and known.get(cid) != v}
+            assert sorted(own) == [cid for cid in listed if cid not in readded], (rec["name"], x)
+            if x in (0, n_pos - 1):
+                assert sorted(own) == listed, (rec["name"], x)
+
+
+def host_and_restatement(blocks):
+    """The host twin on (arrays, ploidy, max_gap) blocks, every result against the restatement of its input."""
+    got = pt.threading_inputs_batch([pc.problem_of_arrays(*b) for b in blocks], host=True)
+    return got, [pc.check_against_restatement(g, arrays, ploidy) for g, (arrays, ploidy, _) in zip(got, blocks)]
+
+
+def test_host_twin_equals_the_restatement_on_the_recorded_cases(host_results):
+    for res, rec in zip(host_results, CASES):
+        pc.check_against_restatement(res, pc.arrays_of(rec), rec["ploidy"])
+
+
+@pytest.mark.parametrize("n_alleles, ploidy", [(3, 3), (16, 16)])
+def test_host_twin_equals_the_restatement_at_every_class_boundary(n_alleles, ploidy):
+    runs = pc.boundary_runs()
+    got, want = host_and_restatement([pc.boundary_problem(runs, k, ploidy, n_alleles) for k in (1, 3, 9)])
+    assert [len(w.cluster) for w in want] == [17, 48, 135] == [g.stats["n_rows"] for g in got]
+    assert all(g.n_alleles == n_alleles for g in got)
+
+
+def test_host_twin_equals_the_restatement_across_257_scan_tiles_and_with_a_cluster_per_entry():
+    got, want = host_and_restatement([pc.carry_problem(), pc.runs_problem((4097, 65, 1), (4097, 65, 1), 2, 2, seed=4163)])
+    assert got[0].stats["n_rows"] == len(want[0].cluster) == 524_310 and got[0].stats["n_positions"] == 2048 * 256 + 1
+    assert len(want[1].cluster) == 4163 and (want[1].total == 1).all()
+
+
+def test_consensus_ties_at_depth_go_to_the_allele_shown_first():
+    for alleles, n_alleles in (((0, 1), 2), ((14, 15), 16)):
+        cases = pc.tie_cases(alleles, n_alleles)
+        pc.check_ties(pt.threading_inputs_batch([pc.problem_of(c) for c in cases], host=True), cases, alleles)
+
+
+def test_selection_at_the_exact_threshold():
+    pc.check_exact_thresholds(lambda depths, ploidy: pt.select_clusters(depths, ploidy, 0, host=True))
+
+
+@pytest.mark.parametrize("ploidy", [2, 6, 16])
+def test_haplotypes_on_seeded_paths_equal_the_restatement(ploidy):
+    blocks = pc.haplotype_blocks(ploidy)
+    got, _ = host_and_restatement(blocks)
+    pc.check_haplotypes(got, blocks, lambda paths, res: pt.haplotypes_from_inputs(paths, res, host=True))
 
 
 def test_without_a_device_the_native_call_raises():
