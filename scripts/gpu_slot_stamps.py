@@ -2,7 +2,8 @@
 
     gpu_slot_stamps.py [COLUMNS [VARIANTS]]   wave 0 of workgroup 0: prologue, every column, exit
     gpu_slot_stamps.py COLUMNS waves          WHAMD_SLOT_STAMPS=2: every wave of workgroups 0, 3 and 6 (three XCDs) of every X run -- wave start, entering
-                                              cells requested / landed, last prologue request, first wave-slot ending reached / left, loop end; per stamp
+                                              cells requested / landed, last prologue request, loop start (every vector request landed) and the
+                                              prologue's scalar requests landed too, first wave-slot ending reached / left, loop end; per stamp
                                               its spread over the eight waves, which wave is last, the cells' latency by the order of the requests
 """
 import os, sys

@@ -1878,10 +1878,11 @@ whamd_status_t DeviceTable::Impl::report_slot_stamps(std::string& msg) const {
 // cells' own latency by the order in which the waves issued their request (a queue in front of a late request shows as latency growing with the rank).
 whamd_status_t DeviceTable::Impl::report_slot_wave_stamps(std::string& msg) const {
 	const Impl& m = *this;
-	constexpr int NW = 8, NS = 8;
+	constexpr int NW = 8, NS = 9;
 	static const char* const names[NS] = {"wave start", "entering cells requested", "last prologue request", "entering cells landed", "all landed, loop starts",
-	                                      "first wave-slot ending reached", "first wave-slot ending left", "loop end"};
-	static const int word[NS] = {0, 1, 2, 3, 7, 4, 5, 6};   // (the order of slot_runx_exit's words -> the order of the events)
+	                                      "scalar tables landed too", "first wave-slot ending reached", "first wave-slot ending left", "loop end"};
+	static const int word[NS] = {0, 1, 2, 3, 7, 8, 4, 5, 6};   // (the order of slot_runx_exit's words -> the order of the events; 8: the high half of word 7)
+	auto stamp = [](const unsigned long long* wave_words, int k) { return k == 8 ? wave_words[7] >> 32 : (k == 7 ? wave_words[7] & 0xFFFFFFFFull : wave_words[k]); };
 	const size_t nruns = m.tp.splan.runs.size(), per_run = (size_t)SLOT_WAVE_STAMP_WGS * SLOT_WAVE_STAMP_WORDS;
 	std::vector<unsigned long long> d(nruns * per_run);
 	HIP_TRY(hipMemcpy(d.data(), m.dev.dp.dbg + m.dev.dp.dbg_wg_off + SLOT_WAVE_STAMP_OFF, d.size() * 8, hipMemcpyDeviceToHost));
@@ -1900,7 +1901,7 @@ whamd_status_t DeviceTable::Impl::report_slot_wave_stamps(std::string& msg) cons
 				double lo = 1e300, hi = 0;
 				int hi_at = 0;
 				for (int v = 0; v < NW; ++v) {
-					at[k][v] = (double)(r[v * 8] - s0) + (k ? (double)r[v * 8 + word[k]] : 0.0);
+					at[k][v] = (double)(r[v * 8] - s0) + (k ? (double)stamp(r + v * 8, word[k]) : 0.0);
 					mean[k][v] += at[k][v];
 					lo = std::min(lo, at[k][v]);
 					if (at[k][v] > hi) { hi = at[k][v]; hi_at = v; }
@@ -1908,7 +1909,7 @@ whamd_status_t DeviceTable::Impl::report_slot_wave_stamps(std::string& msg) cons
 				spread[k] += hi - lo;
 				spread_max[k] = std::max(spread_max[k], hi - lo);
 				if (k == 3) last[0][hi_at]++;
-				if (k == 5) last[1][hi_at]++;
+				if (k == 6) last[1][hi_at]++;
 			}
 			int order[NW];
 			for (int v = 0; v < NW; ++v) order[v] = v;

@@ -627,6 +627,7 @@ struct SlotxStamps {
 	// per-wave stamps (WHAMD_SLOT_STAMPS=2: dbg_flags bit 8), low words of the cycle counter: the entering cells' load issued / landed, the run's first
 	// wave-slot ending reached / left
 	uint32_t w_enter = 0, w_landed = 0, w_end_in = 0, w_end_out = 0;
+	uint32_t w_scalars = 0;   // (behind t_loaded: the prologue's scalar requests -- Kr and control words, tie parities, line touches -- have landed too)
 };
 // Per-wave stamps: every wave of workgroups 0, 3 and 6 (three XCDs) keeps eight words per run behind the other stamps of P.dbg (report_slot_wave_stamps).
 constexpr uint32_t SLOT_WAVE_STAMP_WGS = 3, SLOT_WAVE_STAMP_WORDS = 8 * 8, SLOT_WAVE_STAMP_OFF = 4 * 512 * 2 + 16;
@@ -648,7 +649,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	// priority 1 -- its request for the entering cells, the longest latency of the launch, goes out first -- and everybody the loop at priority 0 again (the
 	// priority kept through the loop only swaps the two halves' roles: measured, profiles/late_wave/experiments_not_kept.md).  One workgroup per CU only: where
 	// several share a CU (STREAM) they fill each other's waits.  The condition is a scalar: s_setprio ignores EXEC.
-	if (!STREAM && wave >= 4u) __builtin_amdgcn_s_setprio(1);
+	// (!STREAM: the kernel's head -- slot_runx_arguments -- has raised the priority of waves 4 .. 7 while the kernel arguments travelled)
 	const uint32_t L = run.L;
 	const uint32_t lthr = tid << LR;
 	const uint32_t Pthr = (w << L) | lthr;
@@ -657,19 +658,35 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	const uint32_t* __restrict__ tab = P.slot_tab;
 	// ---- prologue: one batch of loads.  Wave-uniform data through the scalar cache: the control words and the Kr words of the first trip, the
 	// workgroup's half of the tie parities.
-	const uint32_t* __restrict__ kr_tab = tab + run.tab_kr;
-	const uint32_t* __restrict__ cw_tab = kr_tab + ((ncols + (uint32_t)SLOT_XPAD) << LR);   // one control word per column, behind the Kr words (slot_tables)
+	const uint32_t* __restrict__ kr_tab;
+	const uint32_t* __restrict__ cw_tab;   // one control word per column, behind the Kr words (slot_tables)
 	typedef uint32_t slot_u32x4c __attribute__((ext_vector_type(4)));
 	typedef const __attribute__((address_space(4))) slot_u32x4c* slot_cptr4c;
-	slot_u32x16 krA = *(slot_cptr16)(unsigned long long)kr_tab, krB;
-	slot_u32x4c cwA = *(slot_cptr4c)(unsigned long long)cw_tab, cwB;
-	const uint32_t par_w = *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)(tab + run.tab_par + threads + w);
+	slot_u32x16 krA, krB;
+	slot_u32x4c cwA, cwB;
+	uint32_t par_w;
 	// The Kr words of a trip are one 64-byte line, requested a trip ahead -- a MISS of the scalar cache every trip, and scalar loads share their counter with LDS
 	// operations: an ending read in the first columns of a trip waited for it with its own `s_waitcnt lgkmcnt(0)` (stamps: 500 - 600 cycles there against 400 in a
 	// trip's last column).  The lines of the whole run are touched here, under the prologue's long waits, so that the loop's requests HIT (72 cycles).  One word of
 	// each line into a register that stays reserved until the first wait for scalar data below (the loads return in any order; the compiler must not reuse the
 	// registers before they have).  Lines behind a short run's last belong to the tables that follow (slot_tables leaves room behind the last run).
 	uint32_t touch_kr = 0, touch_kr2 = 0, touch_cw = 0, touch_g = 0, touch_w = 0;
+	// Where these scalar requests stand.  Streamed operands: in front of the entering cells, as they were.  LDS operand lines (one workgroup per CU): BEHIND every
+	// vector request of the prologue, touches included.  They are cold misses, but they are not what the loop's head waits for: a stamp behind that wait found the
+	// waves 41 - 49 cycles in it (profiles/xrun_one_wait/stamps.md), and in front of the lane parts' loads they only delayed those.
+	auto request_tables = [&]() {
+		kr_tab = tab + run.tab_kr;
+		cw_tab = kr_tab + ((ncols + (uint32_t)SLOT_XPAD) << LR);
+		krA = *(slot_cptr16)(unsigned long long)kr_tab;
+		cwA = *(slot_cptr4c)(unsigned long long)cw_tab;
+		par_w = *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)(tab + run.tab_par + threads + w);
+		if (!STREAM) {
+			touch_kr = slot_touch_lines<(XC <= 8 ? 4 : 8)>(kr_tab);   // (XC / 4 + 2 lines of Kr words; a short run's touches reach into the tables behind it: harmless)
+			if (XC > 24) touch_kr2 = slot_touch_lines<2>(kr_tab + 128);   // (lines 9, 10 of a 32-column run)
+			touch_cw = slot_touch_lines<2>(cw_tab);   // (... and the control words': sixteen columns per line)
+		}
+	};
+	if (STREAM) request_tables();
 	// the entering cells first (they come from the other XCDs' stores: the longest latency of the prologue) ...
 	// Shared launches read their run descriptor from memory (SlotBatchEntry) BEFORE anything else can be requested: a miss all the way to HBM per launch.
 	// The entry of the table's next step lies behind this one; its lines are requested here, just before the entering cells (which miss to HBM anyway) --
@@ -683,6 +700,8 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	uint32_t Draw[R];
 	bool flip;
 	slot_enter_cells<LR, DBG>(P, run, prev, Pthr, Draw, flip);
+	unsigned long long fmask = __builtin_amdgcn_ballot_w64(flip);   // (the lanes whose cells arrive reversed: formed HERE, under the loads' latency -- the empty
+	asm volatile("" : "+s"(fmask));                                  //  statement keeps the compiler from forming the mask again in front of its use)
 	const bool wstamps = DBG && slot_wave_stamps_on(P);
 	if (DBG && wstamps) asm volatile("" ::: "memory");   // (the stamp behind the entering cells' requests and in front of every other one)
 	stamps.w_enter = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
@@ -717,11 +736,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		uint32_t X[XC > 0 ? XC : 4];
 #pragma unroll
 		for (int c = 0; c < XC; ++c) X[c] = sl_src[64 * c];
-		// (issued HERE, behind every request of the prologue: in front of the entering cells' loads the scalar waits of their index arithmetic would have
-		// waited for these misses first)
-		touch_kr = slot_touch_lines<(XC <= 8 ? 4 : 8)>(kr_tab);   // (XC / 4 + 2 lines of Kr words; a short run's touches reach into the tables behind it: harmless)
-		if (XC > 24) touch_kr2 = slot_touch_lines<2>(kr_tab + 128);   // (lines 9, 10 of a 32-column run)
-		touch_cw = slot_touch_lines<2>(cw_tab);   // (... and the control words': sixteen columns per line)
+		request_tables();
 		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
 		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XC + 3) : "memory");   // (... par_l, a_g, a_w and XC lane parts are)
 		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
@@ -739,9 +754,17 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	}
 	uint32_t par = par_l ^ par_w;   // bit 0: the next ending read
 	uint8_t* __restrict__ rec = P.bt + (((unsigned long long)run.rec_hi << 32) | run.rec_lo) + (size_t)w * run.n_ends * threads;   // (wave-uniform; the thread adds tid)
-	// D: Y = B - 2 D
-#pragma unroll
-	for (int r = 0; r < R; ++r) D[r] = flip ? Draw[R - 1 - r] : Draw[r];
+	// D: Y = B - 2 D.  The mirrored group of a halved run arrives in reverse order: FOUR selects under one lane mask (written as `flip ? Draw[R - 1 - r] : Draw[r]`
+	// the compiler selects the INDEX and extracts dynamically: 12 compares, 16 selects and their hazard waits behind the cells' landing, on every wave).
+	// (ONE statement, and two wait states in front: a lane mask that a VALU compare wrote may not be read by the next VALU instruction, and the compiler does not
+	//  look for that inside an asm statement)
+	asm("s_nop 1\n\t"
+	    "v_cndmask_b32_e64 %0, %4, %7, %8\n\t"
+	    "v_cndmask_b32_e64 %1, %5, %6, %8\n\t"
+	    "v_cndmask_b32_e64 %2, %6, %5, %8\n\t"
+	    "v_cndmask_b32_e64 %3, %7, %4, %8"
+	    : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+	    : "v"(Draw[0]), "v"(Draw[1]), "v"(Draw[2]), "v"(Draw[3]), "s"(fmask));
 	if (!(run.yflags & 2u)) {   // the entering column is in D form
 #pragma unroll
 		for (int r = 0; r < R; ++r) D[r] = run.base_in - 2u * D[r];
@@ -749,6 +772,9 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	if (warm) asm volatile("" ::"v"(warm_junk), "v"(D[0]));   // (the entering cells are here, so the request issued before them is too)
 	if (DBG && P.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	const unsigned long long t_loaded = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
+	if (DBG && wstamps) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (what the wait at the loop's head would sit out: t_loaded is where a wave reaches it)
+	stamps.w_scalars = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
+	if (DBG && wstamps) asm volatile("" ::: "memory");
 	if (!STREAM) __builtin_amdgcn_s_setprio(0);   // (the prologue's priority of the younger half ends here)
 
 	const uint32_t lds0 = (uint32_t)(unsigned long long)smem;   // LDS byte offset of the exchange buffers
@@ -1116,7 +1142,8 @@ __device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRu
 		d[0] = stamps.t_start;   // (absolute: the waves of a workgroup are compared on the host; everything else relative to the wave's own start)
 		d[1] = stamps.w_enter - t0; d[2] = (uint32_t)stamps.t_issued - t0; d[3] = stamps.w_landed - t0;
 		d[4] = stamps.w_end_in ? (stamps.w_end_in - t0) : 0u; d[5] = stamps.w_end_in ? (stamps.w_end_out - t0) : 0u; d[6] = (uint32_t)stamps.t_loop - t0;
-		d[7] = (uint32_t)stamps.t_loaded - t0;   // (every prologue request landed, cells in Y form: the loop starts)
+		// (every vector request of the prologue landed, cells in Y form: the loop starts; high half: its scalar requests landed too -- zero where not stamped)
+		d[7] = (unsigned long long)((uint32_t)stamps.t_loaded - t0) | ((unsigned long long)(stamps.w_scalars ? stamps.w_scalars - t0 : 0u) << 32);
 	}
 }
 template <int LR, int XC, bool DBG, bool SPEC>
@@ -1189,6 +1216,74 @@ __global__ __launch_bounds__(256) void slot_tables(DevProblem P, const SlotRun* 
 	}
 }
 
+// The kernel arguments of an X run with LDS operand lines (XC > 0: one workgroup per CU), fetched by hand.  Left to the compiler, the by-value arguments came
+// in four dependent round trips before the entering cells could be requested -- `pack` alone, a batch with the first line touches, a batch with the entry's
+// words and the other touches, `prev` inside its branch -- and three more at the loop's head (`cur` / `score_out`, P.bt, P.slot_rows): a scalar-cache hit is
+// 72 cycles at least, the first touch of the argument segment 565.  Here EVERY word the prologue, the loop's head and the exit use is
+// requested in one group with one wait behind it -- the group touches every line that is used, so touch_kernel_arguments has nothing left to do -- and the
+// younger half of the workgroup raises its priority (slot_runx_core) while the group travels.  The loads and their wait are ONE statement: the compiler
+// cannot see a load inside an asm statement and would hand out a destination before the data is there.
+// Not fetched: `in_pos` (the general entry layout keeps a load of its own, slot_enter_cells) and what only the debug library reads.
+struct SlotRunxArgs {
+	DevProblem P;
+	SlotRun run;
+	const uint32_t* prev;
+	uint32_t* cur;
+	uint32_t* score_out;
+	uint32_t pack;
+};
+__device__ __forceinline__ void slot_runx_arguments(SlotRunxArgs& a) {
+	typedef const __attribute__((address_space(4))) void* karg_ptr;
+	const karg_ptr ka = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+	const uint32_t tid0 = uni(threadIdx.x);
+	constexpr uint32_t RUN = sizeof(DevProblem), TAIL = sizeof(DevProblem) + sizeof(SlotRun);
+	static_assert(offsetof(SlotRun, in_fullmask) == 64 && offsetof(SlotRun, spec_id) == 80 && offsetof(SlotRun, out_pos) == 128 && offsetof(SlotRun, tab_g) == 160 &&
+	              sizeof(SlotRun) == 192 && sizeof(DevProblem) % 8 == 0, "the word groups below");
+	unsigned long long bt, rows, tab, keys, prev, cur, score;
+	uint32_t stride, pack;
+	slot_u32x16 r0;       // c0 .. in_mirror_pos
+	slot_u32x4 r16, r20;  // in_fullmask .. out_fullmask; spec_id .. pad
+	slot_u32x8 r32, r40;  // out_pos; tab_g .. tab_par
+	asm volatile(
+	    "s_load_dwordx16 %[r0], %[ka], %[o_run]\n\t"
+	    "s_load_dwordx2 %[prev], %[ka], %[o_tail]\n\t"
+	    "s_load_dwordx2 %[tab], %[ka], %[o_tab]\n\t"
+	    "s_load_dwordx8 %[r40], %[ka], %[o_run] + 160\n\t"
+	    "s_load_dwordx4 %[r16], %[ka], %[o_run] + 64\n\t"
+	    "s_load_dword %[pack], %[ka], %[o_tail] + 24\n\t"
+	    "s_load_dwordx4 %[r20], %[ka], %[o_run] + 80\n\t"
+	    "s_load_dwordx8 %[r32], %[ka], %[o_run] + 128\n\t"
+	    "s_load_dwordx2 %[cur], %[ka], %[o_tail] + 8\n\t"
+	    "s_load_dwordx2 %[score], %[ka], %[o_tail] + 16\n\t"
+	    "s_load_dwordx2 %[bt], %[ka], %[o_bt]\n\t"
+	    "s_load_dwordx2 %[rows], %[ka], %[o_rows]\n\t"
+	    "s_load_dwordx2 %[keys], %[ka], %[o_keys]\n\t"
+	    "s_load_dword %[stride], %[ka], %[o_stride]\n\t"
+	    "s_cmpk_lt_u32 %[tid0], 0x100\n\t"     // (waves 4 .. 7, the second-dispatched wave of every SIMD: the prologue at priority 1 -- slot_runx_core;
+	    "s_cbranch_scc1 .Lxa%=\n\t"            //  a scalar guard, s_setprio ignores EXEC)
+	    "s_setprio 1\n"
+	    ".Lxa%=:\n\t"
+	    "s_waitcnt lgkmcnt(0)"
+	    : [r0] "=&s"(r0), [r16] "=&s"(r16), [r20] "=&s"(r20), [r32] "=&s"(r32), [r40] "=&s"(r40), [bt] "=&s"(bt), [rows] "=&s"(rows), [tab] "=&s"(tab), [keys] "=&s"(keys),
+	      [stride] "=&s"(stride), [prev] "=&s"(prev), [cur] "=&s"(cur), [score] "=&s"(score), [pack] "=&s"(pack)
+	    : [ka] "s"(ka), [tid0] "s"(tid0), [o_run] "n"(RUN), [o_tail] "n"(TAIL), [o_bt] "n"(offsetof(DevProblem, bt)), [o_rows] "n"(offsetof(DevProblem, slot_rows)),
+	      [o_tab] "n"(offsetof(DevProblem, slot_tab)), [o_keys] "n"(offsetof(DevProblem, spec_keys)), [o_stride] "n"(offsetof(DevProblem, spec_stride))
+	    : "memory", "scc");
+	a.P = DevProblem{};
+	// (pointers made from integers are generic -- flat loads and stores, which count as LDS operations too: say that they are global, as kernel arguments are)
+	auto global = [](unsigned long long v, auto* type) { return (decltype(type))(__attribute__((address_space(1))) void*)v; };
+	a.P.bt = global(bt, (uint8_t*)nullptr); a.P.slot_rows = global(rows, (const SlotRow*)nullptr); a.P.slot_tab = global(tab, (const uint32_t*)nullptr);
+	a.P.spec_keys = global(keys, (unsigned long long*)nullptr); a.P.spec_stride = stride;
+	uint32_t* rw = reinterpret_cast<uint32_t*>(&a.run);
+#pragma unroll
+	for (int i = 0; i < 16; ++i) rw[i] = r0[i];
+#pragma unroll
+	for (int i = 0; i < 4; ++i) { rw[16 + i] = r16[i]; rw[20 + i] = r20[i]; }
+#pragma unroll
+	for (int i = 0; i < 8; ++i) { rw[32 + i] = r32[i]; rw[40 + i] = r40[i]; }
+	a.prev = global(prev, (const uint32_t*)nullptr); a.cur = global(cur, (uint32_t*)nullptr); a.score_out = global(score, (uint32_t*)nullptr); a.pack = pack;
+}
+
 // DBG: timing experiments (WHAMD_SLOT_SKIP switches parts off -- results invalid) and in-kernel cycle stamps (WHAMD_SLOT_STAMPS);
 // the production instantiation carries none of it (a single wave issues one VALU instruction per ~8 cycles -- measured,
 // scripts/micro/issue_rate.hip -- so every instruction on the column chain counts).
@@ -1201,9 +1296,19 @@ __global__ __launch_bounds__(256) void slot_tables(DevProblem P, const SlotRun* 
 template <int LR, int XC, bool DBG, bool SPEC>
 __global__ __launch_bounds__(512) void slot_runx(DevProblem P, SlotRun run, const uint32_t* __restrict__ prev, uint32_t* __restrict__ cur, uint32_t* __restrict__ score_out,
                                                  uint32_t pack) {
-	if (pack && (blockIdx.x & 7u)) return;
-	touch_kernel_arguments<sizeof(DevProblem) + sizeof(SlotRun) + 28>();
-	slot_runx_body<LR, XC, DBG, SPEC>(P, run, prev, cur, pack ? blockIdx.x >> 3 : blockIdx.x, score_out);
+	if constexpr (XC == 0) {   // (streamed operands: several workgroups per CU fill each other's waits -- the compiler's own argument loads, as they were)
+		if (pack && (blockIdx.x & 7u)) return;
+		touch_kernel_arguments<sizeof(DevProblem) + sizeof(SlotRun) + 28>();
+		slot_runx_body<LR, XC, DBG, SPEC>(P, run, prev, cur, pack ? blockIdx.x >> 3 : blockIdx.x, score_out);
+	} else {
+		SlotRunxArgs a;
+		slot_runx_arguments(a);
+#pragma unroll
+		for (int i = 0; i < 8; ++i) a.run.in_pos[i] = run.in_pos[i];   // (used by the general entry layout alone: loaded there)
+		if (DBG) { a.P.dbg = P.dbg; a.P.dbg_wg_off = P.dbg_wg_off; a.P.dbg_flags = P.dbg_flags; }
+		if (a.pack && (blockIdx.x & 7u)) return;
+		slot_runx_body<LR, XC, DBG, SPEC>(a.P, a.run, a.prev, a.cur, a.pack ? blockIdx.x >> 3 : blockIdx.x, a.score_out);
+	}
 }
 
 template <int LR, bool DBG, bool SPEC, bool YF = false>
