@@ -144,27 +144,54 @@ __device__ __forceinline__ void slot_enter_cells(const DevProblem& P, const Slot
 
 // ---- exit of a run: scatter into the next step's order (cells whose free-slot bits are zero hold the representatives), the seed of the
 // speculative backtrace (SPEC), Y form back to D form where the next step is not a Y-form run.
-template <int LR, bool DBG, bool SPEC, bool YF>
+// Two parts.  WHERE the thread's cells go: one word per thread, the exit index of its cell 0 gathered bit by bit from the position table, or SLOT_EXIT_NONE where
+// the thread does not write at all (a set bit in a free local slot); nothing in it depends on the cells.  The STORE takes that word and the store form, a
+// scalar fact of the run -- occupied reg slots | position of reg slot 0's read << 2 | of reg slot 1's << 7: the 16-byte fast path or cell by cell -- and holds no
+// gather.  Behind the column loop the two run back to back (SLOT_EXIT_BOTH); an X run with LDS operand lines forms the first under its prologue's wait
+// (slot_exit_where in slot_runx_core) and keeps the second behind the loop (slot_exit_store).  ONE body with the part as a template parameter, not two
+// functions called in turn: the callers that run both parts keep their device code byte for byte (a callee is simplified on its own before it is inlined,
+// which reorders operands and branches of every caller).
+constexpr uint32_t SLOT_EXIT_NONE = 0xFFFFFFFFu;   // (an exit index has at most SLOT_MAXSLOTS bits)
+struct SlotExitWhere { uint32_t base, form; };
+enum SlotExitPart { SLOT_EXIT_BOTH, SLOT_EXIT_WHERE, SLOT_EXIT_STORE };
+template <int LR, bool DBG, bool SPEC, bool YF, SlotExitPart PART = SLOT_EXIT_BOTH>
 __device__ __forceinline__ void slot_exit_cells(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t (&D)[1 << LR], const uint32_t w,
                                                 const uint32_t tid, const uint32_t lane, const uint32_t wave, const uint32_t L, const uint32_t lthr, const uint32_t Pthr,
-                                                const uint32_t threads) {
+                                                const uint32_t threads, SlotExitWhere* where = nullptr) {
 	constexpr int R = 1 << LR;
+	static_assert(PART == SLOT_EXIT_BOTH || LR == 2, "the store form holds the positions of two reg slots' reads");
 	const bool y_out = YF && (run.yflags & 4u);   // the next step is a Y-form run too: the column stays as it is
-	if (YF && !y_out) {
+	if (PART != SLOT_EXIT_WHERE && YF && !y_out) {
 #pragma unroll
 		for (int r = 0; r < R; ++r) D[r] = (run.base_out - D[r]) >> 1;   // D = (B - Y) / 2, exactly
 	}
 	const uint32_t key_flip = y_out ? 0xFFFFFFFFu : 0u;   // seeds of the speculative backtrace order by D: the largest Y is the smallest D
 	{
-		const uint32_t occ = run.out_occ;
-		const uint32_t localmask = (1u << L) - 1u;
-		const bool thread_writes = ((lthr & ~(uint32_t)(R - 1)) & ~occ & localmask) == 0u;
-		uint32_t pos[SLOT_MAXSLOTS];
+		uint32_t occ, base, pos[SLOT_MAXSLOTS];
+		bool thread_writes;
+		if constexpr (PART != SLOT_EXIT_STORE) {
+			occ = run.out_occ;
+			const uint32_t localmask = (1u << L) - 1u;
+			thread_writes = ((lthr & ~(uint32_t)(R - 1)) & ~occ & localmask) == 0u;
 #pragma unroll
-		for (int s = 0; s < SLOT_MAXSLOTS; ++s) pos[s] = slot_pos_dev(run.out_pos, s);
-		uint32_t base = 0;
+			for (int s = 0; s < SLOT_MAXSLOTS; ++s) pos[s] = slot_pos_dev(run.out_pos, s);
+			base = 0;
 #pragma unroll
-		for (int s = LR; s < SLOT_MAXSLOTS; ++s) base |= ((Pthr & occ) >> s & 1u) << pos[s];
+			for (int s = LR; s < SLOT_MAXSLOTS; ++s) base |= ((Pthr & occ) >> s & 1u) << pos[s];
+		}
+		if constexpr (PART == SLOT_EXIT_WHERE) {
+			where->base = thread_writes ? base : SLOT_EXIT_NONE;
+			where->form = (occ & (uint32_t)(R - 1)) | (pos[0] << 2) | (pos[1] << 7);
+			return;
+		}
+		if constexpr (PART == SLOT_EXIT_STORE) {
+			base = where->base;
+			thread_writes = base != SLOT_EXIT_NONE;
+			const uint32_t form = uni(where->form);   // (a scalar that went through an empty asm statement: say that it is one, or the store form is tested lane by lane)
+			occ = form & (uint32_t)(R - 1);
+			pos[0] = (form >> 2) & 31u;
+			pos[1] = (form >> 7) & 31u;
+		}
 		const uint32_t mirror_x = run.mirror_out ? run.out_fullmask : 0u;
 		unsigned long long best_key = ~0ull;   // (value, exit index) of the smallest cell this thread stores (run.spec_id)
 		if (R == 2 && (occ & 1u) && pos[0] == 0u) {
@@ -232,6 +259,17 @@ __device__ __forceinline__ void slot_exit_cells(const DevProblem& P, const SlotR
 			if (lane == 0) P.spec_keys[(size_t)(run.spec_id - 1u) * P.spec_stride + w * (threads >> 6) + wave] = best_key;
 		}
 	}
+}
+
+template <int LR>
+__device__ __forceinline__ void slot_exit_where(const SlotRun& run, const uint32_t L, const uint32_t lthr, const uint32_t Pthr, SlotExitWhere& where) {
+	uint32_t none[1 << LR];   // (this part touches neither the cells nor memory)
+	slot_exit_cells<LR, false, false, false, SLOT_EXIT_WHERE>(DevProblem{}, run, nullptr, none, 0u, 0u, 0u, 0u, L, lthr, Pthr, 0u, &where);
+}
+template <int LR, bool DBG, bool SPEC, bool YF>
+__device__ __forceinline__ void slot_exit_store(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t (&D)[1 << LR], const uint32_t w,
+                                                const uint32_t lane, const uint32_t wave, const uint32_t threads, SlotExitWhere& where) {
+	slot_exit_cells<LR, DBG, SPEC, YF, SLOT_EXIT_STORE>(P, run, cur, D, w, 0u, lane, wave, 0u, 0u, 0u, threads, &where);
 }
 
 template <int LR, bool DBG, bool SPEC, bool YF = false>
@@ -634,7 +672,7 @@ constexpr uint32_t SLOT_WAVE_STAMP_WGS = 3, SLOT_WAVE_STAMP_WORDS = 8 * 8, SLOT_
 __device__ __forceinline__ bool slot_wave_stamps_on(const DevProblem& P) { return P.dbg && (P.dbg_flags & 256u); }
 template <int LR, int XC, bool DBG>
 __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[1 << LR],
-                                               SlotxStamps& stamps, const void* warm = nullptr) {
+                                               SlotxStamps& stamps, const void* warm = nullptr, SlotExitWhere* where = nullptr) {
 	static_assert(LR == 2, "X runs: four cells per thread (the masks, the decisions and the exchange are written for four)");
 	static_assert(XC % 4 == 0 && XC <= SLOT_XCOLS, "whole trips of four columns");
 	constexpr bool STREAM = XC == 0;   // the operands of a trip are formed a trip ahead from the tables (no LDS lines: several workgroups per CU -- shared launches)
@@ -738,6 +776,16 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		for (int c = 0; c < XC; ++c) X[c] = sl_src[64 * c];
 		request_tables();
 		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
+		// The exit addresses, HERE: behind the prologue's last request and in front of the first instruction that consumes a loaded word -- a wave sat 300 - 700
+		// cycles between the two (profiles/xrun_one_wait/stamps.md), and behind the loop the same gather is 775 - 850 cycles of every launch that nothing covers.
+		// One VGPR and one SGPR travel through the loop instead of out_occ, L and the eight words of out_pos.  (The scheduling barriers and the empty statement
+		// hold the place: left alone, the compiler sinks the gather behind the loop again, where its only consumer is.)
+		{
+			__builtin_amdgcn_sched_barrier(0);
+			slot_exit_where<LR>(run, L, lthr, Pthr, *where);
+			asm volatile("" : "+v"(where->base), "+s"(where->form));
+			__builtin_amdgcn_sched_barrier(0);
+		}
 		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XC + 3) : "memory");   // (... par_l, a_g, a_w and XC lane parts are)
 		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
 		// X0 of column c = 2 A(thread's cell 0) + bias = lane part + (workgroup + wave part, held by lane c): kept in the thread's OWN 16 bytes per trip of
@@ -1123,13 +1171,18 @@ __device__ __forceinline__ void slot_runx8_core(const DevProblem& P, const SlotR
 	stamps.t_loop = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
 }
 
-template <int LR, bool DBG, bool SPEC>
+template <int LR, bool DBG, bool SPEC, bool EARLY = false>
 __device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t* score_out, const uint32_t w, uint32_t (&D)[1 << LR],
-                                               const SlotxStamps& stamps) {
+                                               const SlotxStamps& stamps, SlotExitWhere* where = nullptr) {
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t wave = uni(tid >> 6);
-	const uint32_t L = run.L, lthr = tid << LR;
-	slot_exit_cells<LR, DBG, SPEC, true>(P, run, cur, D, w, tid, lane, wave, L, lthr, (w << L) | lthr, run.threads);
+	if constexpr (EARLY) {   // (formed in the prologue, slot_runx_core: the store alone is left)
+		static_assert(LR == 2, "two reg slots' positions in the store form");
+		slot_exit_store<LR, DBG, SPEC, true>(P, run, cur, D, w, lane, wave, run.threads, *where);
+	} else {
+		const uint32_t L = run.L, lthr = tid << LR;
+		slot_exit_cells<LR, DBG, SPEC, true>(P, run, cur, D, w, tid, lane, wave, L, lthr, (w << L) | lthr, run.threads);
+	}
 	if (score_out && w == 0 && tid == 0) *score_out = D[0];
 	if (DBG && P.dbg && w == 0 && tid == 0) {
 		unsigned long long* d = P.dbg + (size_t)run.pad * 48;
@@ -1151,8 +1204,14 @@ __device__ __forceinline__ void slot_runx_body(const DevProblem& P, const SlotRu
                                                uint32_t* score_out) {
 	uint32_t D[1 << LR];
 	SlotxStamps stamps;
-	slot_runx_core<LR, XC, DBG>(P, run, prev, w, D, stamps);
-	slot_runx_exit<LR, DBG, SPEC>(P, run, cur, score_out, w, D, stamps);
+	if constexpr (XC > 0) {   // (one workgroup per CU: the exit addresses are formed under the prologue's wait)
+		SlotExitWhere where;
+		slot_runx_core<LR, XC, DBG>(P, run, prev, w, D, stamps, nullptr, &where);
+		slot_runx_exit<LR, DBG, SPEC, true>(P, run, cur, score_out, w, D, stamps, &where);
+	} else {
+		slot_runx_core<LR, XC, DBG>(P, run, prev, w, D, stamps);
+		slot_runx_exit<LR, DBG, SPEC>(P, run, cur, score_out, w, D, stamps);
+	}
 }
 
 // The per-run tables of the prologue (SlotRun::tab_g / tab_w / tab_sl), once per table at create time: blockIdx.y = run.
