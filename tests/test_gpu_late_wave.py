@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the users of the X runs' prologue (kernels_slots.h slot_runx_core, slot_runx8_core) against the oracle, through the product library
+"""GPU (-m gpu): the users of the X runs' prologue (kernels_slots.h slot_runx_lds_core, slot_runx_stream_core) against the oracle, through the product library
 and through the debug library with no debug switch set.  The order of the prologue's memory requests must not change a result:
 
 * coverage 20, 96 columns: the ramp and two full-width unpacked runs of 22 columns -- 256 workgroups of eight waves, `slot_runx<2, 24>` -- with

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every way out of an X run (kernels_slots.h slot_exit_cells and its parts, slot_runx_core, slot_runx_exit), each against the oracle in full
+"""GPU (-m gpu): every way out of an X run (kernels_slots.h slot_exit_cells and its parts, slot_runx_lds_core, slot_runx_stream_core, slot_runx_exit / slot_runx_exit_early), each against the oracle in full
 -- cost, index path, partitioning, superreads -- with the debug library's launch ledger asserting that the intended kernel ran
 (tests/test_gpu_kernel_choice.py: solve_and_check / solve_many_and_check and the rule the ledger is held to).
 

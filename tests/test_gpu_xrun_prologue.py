@@ -1,4 +1,4 @@
-"""GPU (-m gpu): every way into and out of an X run's prologue (kernels_slots.h slot_runx_arguments / slot_runx_core / slot_enter_cells), each against the
+"""GPU (-m gpu): every way into and out of an X run's prologue (kernels_slots.h slot_runx_arguments / slot_runx_lds_core / slot_runx_stream_core / slot_enter_cells), each against the
 oracle in full -- cost, index path, partitioning, superreads -- with the debug library's launch ledger asserting that the intended kernel ran
 (tests/test_gpu_kernel_choice.py: solve_and_check / solve_many_and_check and the rule the ledger is held to).
 
@@ -7,6 +7,7 @@ result in exactly one of the cases below -- `pack` (narrow runs on one XCD), the
 previous column, the D-form entry, the general entry layout with its own load of `in_pos`, the exit's words (`out_pos`, `cur`, `score_out`), the record
 pointer (`P.bt`), the rows of a third ending read (`P.slot_rows`), the speculative seed (`P.spec_keys`).
 """
+import numpy as np
 import pytest
 
 from test_gpu_kernel_choice import LAST_LEDGER, components, solve_and_check, solve_many_and_check
@@ -82,9 +83,30 @@ def test_a_run_that_ends_a_backtrace_chunk():
 
 
 def test_the_same_problems_sharing_their_launches():
-    """`slot_groupx<2>` (streamed operands through the shared core: the flip as four selects, the entry read from memory)."""
+    """`slot_groupx<2>` (streamed operands, slot_runx_stream_core<2>: the flip as four selects, the entry read from memory)."""
     members = [(("xrun prologue", c), flagship_like(c), {"shared_launches": 1}) for c in (12, 13, 17, 18)]
     names, stats = solve_many_and_check(members)
     assert all(s["group_tables"] > 1 for s in stats), stats
     assert all("slot_groupx<2, false>" in n for n in names[:3]), names
-    assert "slot_groupx<3, false>" in names[3], names   # (a wide table that shares its launches holds eight cells per thread: slot_runx8_core, untouched)
+    assert "slot_groupx<3, false>" in names[3], names   # (a wide table that shares its launches holds eight cells per thread: slot_runx_stream_core<3>)
+
+
+def ending_reads_per_column(p):
+    """How many reads end in each column, from the problem's arrays (the last entry of a read is its last column; positions are 1000 * (column + 1))."""
+    last = np.asarray(p.var_position)[np.asarray(p.read_ptr[1:], dtype=np.int64) - 1] // 1000 - 1
+    return np.bincount(last, minlength=p.n_variants)
+
+
+def test_third_and_later_ending_reads_sharing_their_launches():
+    """The walk over a column's ending reads is one text for four and for eight cells per thread (slotx_later_endings, slot_runx_stream_core<2 | 3>): the
+    third and later ones come from the row, and their decode differs between the two by the width of the qmask alone -- wrong only in a column where three
+    or more reads end.  Irregular tables (seeds chosen on the host so that each has such columns), two narrow and two wide, sharing their launches."""
+    shapes = [(120, 16, 7), (120, 16, 5), (150, 18, 7), (200, 18, 9)]   # (columns, coverage, seed)
+    members = [(("xrun irregular shared",) + s, irregular_block(s[0], s[1], seed=s[2]), {"shared_launches": 1}) for s in shapes]
+    for key, p, _ in members:
+        ends = ending_reads_per_column(p)
+        assert (ends[:-1] >= 3).any(), (key, ends.max())   # (a column before the table's last: the last one ends every read that is left)
+    names, stats = solve_many_and_check(members)
+    assert all(s["group_tables"] > 1 for s in stats), stats
+    assert all("slot_groupx<2, false>" in n for n in names[:2]), names
+    assert all("slot_groupx<3, false>" in n for n in names[2:]), names

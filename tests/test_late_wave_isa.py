@@ -1,5 +1,5 @@
 """No GPU needed: the prologue of an X run as it is meant to be issued, pinned on the cross-compiled assembly of `slot_runx<2, 24, false, false>`
-(kernels_slots.h slot_runx_core, DESIGN.md 4.1b, profiles/late_wave/stamps.md).
+(kernels_slots.h slot_runx_lds_core, DESIGN.md 4.1b, profiles/late_wave/stamps.md).
 
 The waves that are late at a run's first wave-slot ending are waves 4 .. 7, the second-dispatched wave of every SIMD, which lose the issue arbitration to
 the older wave at equal priority.  The remedy that was kept: the younger half runs the prologue at priority 1, everybody the column loop at priority 0.

@@ -1,5 +1,5 @@
 """No GPU needed: the exit of an X run, pinned on the cross-compiled assembly of `slot_runx<2, XC, false, SPEC>` for XC = 8, 16, 24, 32
-(kernels_slots.h slot_exit_cells and its parts, slot_runx_core, DESIGN.md 4.1b "the exit", profiles/xrun_exit/).
+(kernels_slots.h slot_exit_cells and its parts, slot_runx_lds_core, DESIGN.md 4.1b "the exit", profiles/xrun_exit/).
 
 A launch is a link of a chain of dependent launches, so what a kernel does behind its column loop is covered by no other wave.  The exit used to form
 the thread's exit index there, bit by bit from the position table: 24 `v_bfe_u32`, 23 `v_lshl_or_b32` and the scalar shifts that unpack `out_pos`, about 110

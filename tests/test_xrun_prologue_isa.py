@@ -1,5 +1,5 @@
 """No GPU needed: the request order of an X run's prologue, pinned on the cross-compiled assembly of `slot_runx<2, XC, false, SPEC>` for XC = 8, 16, 24, 32
-(kernels_slots.h slot_runx_arguments / slot_runx_core, DESIGN.md 4.1b "the prologue's request order", profiles/xrun_one_wait/).
+(kernels_slots.h slot_runx_arguments / slot_runx_lds_core, DESIGN.md 4.1b "the prologue's request order", profiles/xrun_one_wait/).
 
 A launch of 22 columns spent its first third before the first column, and the column loop cannot hide that part.  What the prologue is meant to be:
 

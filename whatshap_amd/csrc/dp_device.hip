@@ -808,7 +808,7 @@ whamd_status_t DeviceTable::Impl::make_lanes(const TableBuild& b, TableUploader&
 whamd_status_t DeviceTable::Impl::upload_entries(TableUploader& up, std::string& msg) {
 	Impl& m = *this;
 	HIP_TRY(up.up((void**)&m.dev.d_entries, m.tp.entries.data(), m.tp.entries.size() * sizeof(ResBatchEntry)));
-	m.tp.slot_entries.resize(m.tp.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_core)
+	m.tp.slot_entries.resize(m.tp.slot_entries.size() + 2);   // (two unused entries behind the last: a group launch warms 512 bytes behind its own entry, slot_runx_stream_core)
 	HIP_TRY(up.up((void**)&m.dev.d_slot_entries, m.tp.slot_entries.data(), m.tp.slot_entries.size() * sizeof(SlotBatchEntry)));
 	m.tp.slot_entries.resize(m.tp.slot_entries.size() - 2);
 	std::vector<BtJob> btjobs;

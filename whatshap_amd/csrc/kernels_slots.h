@@ -148,7 +148,7 @@ __device__ __forceinline__ void slot_enter_cells(const DevProblem& P, const Slot
 // the thread does not write at all (a set bit in a free local slot); nothing in it depends on the cells.  The STORE takes that word and the store form, a
 // scalar fact of the run -- occupied reg slots | position of reg slot 0's read << 2 | of reg slot 1's << 7: the 16-byte fast path or cell by cell -- and holds no
 // gather.  Behind the column loop the two run back to back (SLOT_EXIT_BOTH); an X run with LDS operand lines forms the first under its prologue's wait
-// (slot_exit_where in slot_runx_core) and keeps the second behind the loop (slot_exit_store).  ONE body with the part as a template parameter, not two
+// (slot_exit_where in slot_runx_lds_core) and keeps the second behind the loop (slot_exit_store).  ONE body with the part as a template parameter, not two
 // functions called in turn: the callers that run both parts keep their device code byte for byte (a callee is simplified on its own before it is inlined,
 // which reorders operands and branches of every caller).
 constexpr uint32_t SLOT_EXIT_NONE = 0xFFFFFFFFu;   // (an exit index has at most SLOT_MAXSLOTS bits)
@@ -268,8 +268,9 @@ __device__ __forceinline__ void slot_exit_where(const SlotRun& run, const uint32
 }
 template <int LR, bool DBG, bool SPEC, bool YF>
 __device__ __forceinline__ void slot_exit_store(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t (&D)[1 << LR], const uint32_t w,
-                                                const uint32_t lane, const uint32_t wave, const uint32_t threads, SlotExitWhere& where) {
-	slot_exit_cells<LR, DBG, SPEC, YF, SLOT_EXIT_STORE>(P, run, cur, D, w, 0u, lane, wave, 0u, 0u, 0u, threads, &where);
+                                                const uint32_t lane, const uint32_t wave, const uint32_t threads, const SlotExitWhere& where) {
+	SlotExitWhere at{where.base, where.form};   // (the one body takes the words through a pointer it may write through: the other part does)
+	slot_exit_cells<LR, DBG, SPEC, YF, SLOT_EXIT_STORE>(P, run, cur, D, w, 0u, lane, wave, 0u, 0u, 0u, threads, &at);
 }
 
 template <int LR, bool DBG, bool SPEC, bool YF = false>
@@ -660,6 +661,22 @@ __device__ __forceinline__ uint32_t slot_touch_lines(const void* base) {   // li
 }
 __device__ __forceinline__ void slot_touch_done(uint32_t junk) { asm volatile("" ::"s"(junk)); }
 
+// Shared launches read their run descriptor from memory before anything else can be requested -- a miss all the way to HBM per launch.  The entry of a
+// table's next step lies behind the current one (the schedule's entries are consecutive): the kernel requests its lines with ONE vector load at its very
+// start -- into this XCD's L2, where the next launch's workgroup (x, y) finds them (measured: 24 coverage-15 tables 11.1 -> 10.5 us per launch).  The
+// destination register must stay reserved until the load has landed (the compiler cannot see a load inside an asm statement): slot_warm_done() at the
+// kernel's end -- vector loads return in order, and the body has consumed later ones by then -- or, with `later`, as soon as a word of a vector load that
+// was requested behind this one is used.
+__device__ __forceinline__ uint32_t slot_warm_entry(const SlotBatchEntry* next) {
+	uint32_t junk;
+	const unsigned long long line = (unsigned long long)next + ((threadIdx.x & 7u) << 6);
+	asm volatile("global_load_dword %0, %1, off" : "=v"(junk) : "v"(line) : "memory");
+	return junk;
+}
+__device__ __forceinline__ uint32_t slot_warm_next(const SlotBatchEntry* ep) { return slot_warm_entry(ep + 1); }
+__device__ __forceinline__ void slot_warm_done(uint32_t junk) { asm volatile("" ::"v"(junk)); }
+__device__ __forceinline__ void slot_warm_done(uint32_t junk, uint32_t later) { asm volatile("" ::"v"(junk), "v"(later)); }
+
 struct SlotxStamps {
 	unsigned long long t_start, t_issued, t_loaded, t_loop;
 	// per-wave stamps (WHAMD_SLOT_STAMPS=2: dbg_flags bit 8), low words of the cycle counter: the entering cells' load issued / landed, the run's first
@@ -670,13 +687,40 @@ struct SlotxStamps {
 // Per-wave stamps: every wave of workgroups 0, 3 and 6 (three XCDs) keeps eight words per run behind the other stamps of P.dbg (report_slot_wave_stamps).
 constexpr uint32_t SLOT_WAVE_STAMP_WGS = 3, SLOT_WAVE_STAMP_WORDS = 8 * 8, SLOT_WAVE_STAMP_OFF = 4 * 512 * 2 + 16;
 __device__ __forceinline__ bool slot_wave_stamps_on(const DevProblem& P) { return P.dbg && (P.dbg_flags & 256u); }
-template <int LR, int XC, bool DBG>
-__device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[1 << LR],
-                                               SlotxStamps& stamps, const void* warm = nullptr, SlotExitWhere* where = nullptr) {
-	static_assert(LR == 2, "X runs: four cells per thread (the masks, the decisions and the exchange are written for four)");
-	static_assert(XC % 4 == 0 && XC <= SLOT_XCOLS, "whole trips of four columns");
-	constexpr bool STREAM = XC == 0;   // the operands of a trip are formed a trip ahead from the tables (no LDS lines: several workgroups per CU -- shared launches)
-	constexpr int R = 1 << LR;
+
+// The info word of an ending read (slot | qmask << 8 | exchange buffer << 16) as the control field the ending blocks take: n_end's two bits left free |
+// slot << 2 | qmask << 7 | exchange buffer << 15.  QMASK: the bits of a qmask that are kept -- one per cell of a thread.
+template <uint32_t QMASK>
+__device__ __forceinline__ constexpr uint32_t slot_end_field(uint32_t info) {
+	return ((info & 31u) << 2) | (((info >> 8) & QMASK) << 7) | (((info >> 16) & 1u) << 15);
+}
+// The reads that end in a column of an X run behind its first, R cells per thread: the second is described in the high half of the control word, a third and
+// later ones in the row (scalar loads, requested before the second ending read is evaluated).  `ending` takes a control field.
+template <int R, class Ending>
+__device__ __forceinline__ void slotx_later_endings(const Ending& ending, const uint32_t ctrl, const SlotRow* __restrict__ row_of_column) {
+	if (ctrl & 2u) {
+		const unsigned long long row = (unsigned long long)row_of_column;
+		uint32_t n_end = 2u, info = 0u;
+		if (ctrl & 1u) {   // (a count of 3 says "three or more")
+			n_end = *(const __attribute__((address_space(4))) uint32_t*)(row + 44);
+			info = *(const __attribute__((address_space(4))) uint32_t*)(row + 64);
+		}
+		ending(ctrl >> 16);
+		for (uint32_t e = 2; e < n_end; ++e) {
+			const uint32_t field = slot_end_field<(1u << R) - 1u>(info);
+			if (e + 1u < n_end) info = *(const __attribute__((address_space(4))) uint32_t*)(row + 56 + 8 * e);     // (the next one's, a read ahead)
+			ending(field);
+		}
+	}
+}
+
+// ---- LDS operand lines: one workgroup per CU, a launch of its own (slot_runx<2, 8 | 16 | 24 | 32>).  Prologue + column loop; leaves the thread's four cells in D
+// and where they go in `where`.
+template <int XC, bool DBG>
+__device__ __forceinline__ void slot_runx_lds_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[4],
+                                                   SlotxStamps& stamps, SlotExitWhere& where) {
+	static_assert(XC > 0 && XC % 4 == 0 && XC <= SLOT_XCOLS, "whole trips of four columns, their operands in LDS lines");
+	constexpr int LR = 2, R = 4;   // four cells per thread (the masks, the decisions and the exchange are written for four)
 	extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // wave-slot exchange 2 x [threads][R] | X0 [trip][thread][4 columns] (slotx_lds_bytes)
 	const unsigned long long t_start = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -686,55 +730,15 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	// half then stood and waited (per-wave stamps, profiles/late_wave/stamps.md: the launch is as long as its slowest wave).  The younger half runs the PROLOGUE at
 	// priority 1 -- its request for the entering cells, the longest latency of the launch, goes out first -- and everybody the loop at priority 0 again (the
 	// priority kept through the loop only swaps the two halves' roles: measured, profiles/late_wave/experiments_not_kept.md).  One workgroup per CU only: where
-	// several share a CU (STREAM) they fill each other's waits.  The condition is a scalar: s_setprio ignores EXEC.
-	// (!STREAM: the kernel's head -- slot_runx_arguments -- has raised the priority of waves 4 .. 7 while the kernel arguments travelled)
+	// several share a CU (slot_runx_stream_core) they fill each other's waits.  The condition is a scalar: s_setprio ignores EXEC.
+	// (the kernel's head -- slot_runx_arguments -- has raised the priority of waves 4 .. 7 while the kernel arguments travelled)
 	const uint32_t L = run.L;
 	const uint32_t lthr = tid << LR;
 	const uint32_t Pthr = (w << L) | lthr;
 	const uint32_t ncols = run.ncols, threads = run.threads;
 	const uint32_t ncp = (ncols + 7u) & ~7u;   // row length of the tables G, W and SL of an X run: padded with zeros to a pair of trips (slot_tables)
 	const uint32_t* __restrict__ tab = P.slot_tab;
-	// ---- prologue: one batch of loads.  Wave-uniform data through the scalar cache: the control words and the Kr words of the first trip, the
-	// workgroup's half of the tie parities.
-	const uint32_t* __restrict__ kr_tab;
-	const uint32_t* __restrict__ cw_tab;   // one control word per column, behind the Kr words (slot_tables)
-	typedef uint32_t slot_u32x4c __attribute__((ext_vector_type(4)));
-	typedef const __attribute__((address_space(4))) slot_u32x4c* slot_cptr4c;
-	slot_u32x16 krA, krB;
-	slot_u32x4c cwA, cwB;
-	uint32_t par_w;
-	// The Kr words of a trip are one 64-byte line, requested a trip ahead -- a MISS of the scalar cache every trip, and scalar loads share their counter with LDS
-	// operations: an ending read in the first columns of a trip waited for it with its own `s_waitcnt lgkmcnt(0)` (stamps: 500 - 600 cycles there against 400 in a
-	// trip's last column).  The lines of the whole run are touched here, under the prologue's long waits, so that the loop's requests HIT (72 cycles).  One word of
-	// each line into a register that stays reserved until the first wait for scalar data below (the loads return in any order; the compiler must not reuse the
-	// registers before they have).  Lines behind a short run's last belong to the tables that follow (slot_tables leaves room behind the last run).
-	uint32_t touch_kr = 0, touch_kr2 = 0, touch_cw = 0, touch_g = 0, touch_w = 0;
-	// Where these scalar requests stand.  Streamed operands: in front of the entering cells, as they were.  LDS operand lines (one workgroup per CU): BEHIND every
-	// vector request of the prologue, touches included.  They are cold misses, but they are not what the loop's head waits for: a stamp behind that wait found the
-	// waves 41 - 49 cycles in it (profiles/xrun_one_wait/stamps.md), and in front of the lane parts' loads they only delayed those.
-	auto request_tables = [&]() {
-		kr_tab = tab + run.tab_kr;
-		cw_tab = kr_tab + ((ncols + (uint32_t)SLOT_XPAD) << LR);
-		krA = *(slot_cptr16)(unsigned long long)kr_tab;
-		cwA = *(slot_cptr4c)(unsigned long long)cw_tab;
-		par_w = *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)(tab + run.tab_par + threads + w);
-		if (!STREAM) {
-			touch_kr = slot_touch_lines<(XC <= 8 ? 4 : 8)>(kr_tab);   // (XC / 4 + 2 lines of Kr words; a short run's touches reach into the tables behind it: harmless)
-			if (XC > 24) touch_kr2 = slot_touch_lines<2>(kr_tab + 128);   // (lines 9, 10 of a 32-column run)
-			touch_cw = slot_touch_lines<2>(cw_tab);   // (... and the control words': sixteen columns per line)
-		}
-	};
-	if (STREAM) request_tables();
-	// the entering cells first (they come from the other XCDs' stores: the longest latency of the prologue) ...
-	// Shared launches read their run descriptor from memory (SlotBatchEntry) BEFORE anything else can be requested: a miss all the way to HBM per launch.
-	// The entry of the table's next step lies behind this one; its lines are requested here, just before the entering cells (which miss to HBM anyway) --
-	// into this XCD's L2, where the next launch's workgroup (x, y) finds them.  The destination register stays reserved until the entering cells are used
-	// below: vector loads return in order, so by then this request has landed (the compiler cannot see a load inside an asm statement).
-	uint32_t warm_junk = 0;
-	if (warm) {
-		const unsigned long long line = (unsigned long long)warm + ((lane & 7u) << 6);
-		asm volatile("global_load_dword %0, %1, off" : "=v"(warm_junk) : "v"(line) : "memory");
-	}
+	// ---- prologue: one batch of loads, the entering cells first (they come from the other XCDs' stores: the longest latency of the prologue) ...
 	uint32_t Draw[R];
 	bool flip;
 	slot_enter_cells<LR, DBG>(P, run, prev, Pthr, Draw, flip);
@@ -748,57 +752,62 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	const uint32_t* __restrict__ sl_src = tab + run.tab_sl + lane;   // the lane part of column c: sl_src[64 c] (one coalesced 256-byte request per wave and column)
 	const uint32_t* __restrict__ g_row = tab + run.tab_g + w * ncp;  // the workgroup's and the wave's part: rows of the tables G and W
 	const uint32_t* __restrict__ w_row = tab + run.tab_w + wave * ncp;
-	typedef uint32_t slot_u32x4s __attribute__((ext_vector_type(4)));
-	typedef const __attribute__((address_space(4))) slot_u32x4s* slot_cptr4;
-	slot_u32x4s gA, gB, wA, wB;
-	uint32_t slA[4], slB[4];
-	unsigned long long t_issued = 0ull;
-	if (STREAM) {
-		gA = *(slot_cptr4)(unsigned long long)g_row;
-		wA = *(slot_cptr4)(unsigned long long)w_row;
+	// lane c of every wave fetches the workgroup + wave part of column c, the thread the lane part of every column (columns behind the run's last
+	// read zeros, further ones the tables that follow -- never used)
+	const uint32_t cl = lane < ncols ? lane : 0u;
+	const uint32_t a_g = g_row[cl], a_w = w_row[cl];
+	uint32_t X[XC];
 #pragma unroll
-		for (int k = 0; k < 4; ++k) slA[k] = sl_src[64 * k];
-		// (shared launches: the scalar lines of the whole run -- Kr and control words, the workgroup's and the wave's row of G / W -- touched behind the prologue's requests)
-		touch_kr = slot_touch_lines<8>(kr_tab);
-		touch_cw = slot_touch_lines<2>(cw_tab);
-		touch_g = slot_touch_lines<2>(g_row);
-		touch_w = slot_touch_lines<2>(w_row);
-		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
-		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");   // (vector loads return in order: par_l and four lane parts are behind the entering cells)
-		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
-	} else {
-		// lane c of every wave fetches the workgroup + wave part of column c, the thread the lane part of every column (columns behind the run's last
-		// read zeros, further ones the tables that follow -- never used)
-		const uint32_t cl = lane < ncols ? lane : 0u;
-		const uint32_t a_g = g_row[cl], a_w = w_row[cl];
-		uint32_t X[XC > 0 ? XC : 4];
+	for (int c = 0; c < XC; ++c) X[c] = sl_src[64 * c];
+	// Wave-uniform data through the scalar cache, BEHIND every vector request of the prologue: the control words and the Kr words of the first trip, the
+	// workgroup's half of the tie parities, the line touches.  They are cold misses, but they are not what the loop's head waits for: a stamp behind that wait
+	// found the waves 41 - 49 cycles in it (profiles/xrun_one_wait/stamps.md), and in front of the lane parts' loads they only delayed those.
+	// (Written as a lambda that is called where it stands: what a lambda captures becomes a register after everything else has, and with plain statements the
+	//  loop's scalars come out under other register numbers -- this path's device code is held instruction for instruction, scripts/isa_diff.py.)
+	const uint32_t* __restrict__ kr_tab;
+	const uint32_t* __restrict__ cw_tab;   // one control word per column, behind the Kr words (slot_tables)
+	typedef const __attribute__((address_space(4))) slot_u32x4* slot_cptr4;
+	slot_u32x16 krA, krB;
+	slot_u32x4 cwA, cwB;
+	uint32_t par_w, touch_kr = 0, touch_kr2 = 0, touch_cw = 0;
+	// The Kr words of a trip are one 64-byte line, requested a trip ahead -- a MISS of the scalar cache every trip, and scalar loads share their counter with LDS
+	// operations: an ending read in the first columns of a trip waited for it with its own `s_waitcnt lgkmcnt(0)` (stamps: 500 - 600 cycles there against 400 in a
+	// trip's last column).  The lines of the whole run are touched here, under the prologue's long waits, so that the loop's requests HIT (72 cycles).  One word of
+	// each line into a register that stays reserved until the first wait for scalar data below (the loads return in any order; the compiler must not reuse the
+	// registers before they have).  Lines behind a short run's last belong to the tables that follow (slot_tables leaves room behind the last run).
+	[&]() {
+		kr_tab = tab + run.tab_kr;
+		cw_tab = kr_tab + ((ncols + (uint32_t)SLOT_XPAD) << LR);
+		krA = *(slot_cptr16)(unsigned long long)kr_tab;
+		cwA = *(slot_cptr4)(unsigned long long)cw_tab;
+		par_w = *(const __attribute__((address_space(4))) uint32_t*)(unsigned long long)(tab + run.tab_par + threads + w);
+		touch_kr = slot_touch_lines<(XC <= 8 ? 4 : 8)>(kr_tab);   // (XC / 4 + 2 lines of Kr words; a short run's touches reach into the tables behind it: harmless)
+		if (XC > 24) touch_kr2 = slot_touch_lines<2>(kr_tab + 128);   // (lines 9, 10 of a 32-column run)
+		touch_cw = slot_touch_lines<2>(cw_tab);   // (... and the control words': sixteen columns per line)
+	}();
+	const unsigned long long t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
+	// The exit addresses, HERE: behind the prologue's last request and in front of the first instruction that consumes a loaded word -- a wave sat 300 - 700
+	// cycles between the two (profiles/xrun_one_wait/stamps.md), and behind the loop the same gather is 775 - 850 cycles of every launch that nothing covers.
+	// One VGPR and one SGPR travel through the loop instead of out_occ, L and the eight words of out_pos.  (The scheduling barriers and the empty statement
+	// hold the place: left alone, the compiler sinks the gather behind the loop again, where its only consumer is.)
+	{
+		__builtin_amdgcn_sched_barrier(0);
+		slot_exit_where<LR>(run, L, lthr, Pthr, where);
+		asm volatile("" : "+v"(where.base), "+s"(where.form));
+		__builtin_amdgcn_sched_barrier(0);
+	}
+	if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XC + 3) : "memory");   // (vector loads return in order: par_l, a_g, a_w and XC lane parts are behind the entering cells)
+	stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
+	// X0 of column c = 2 A(thread's cell 0) + bias = lane part + (workgroup + wave part, held by lane c): kept in the thread's OWN 16 bytes per trip of
+	// an LDS area (nobody else reads them: no barrier) -- a register per column would need the column loop unrolled over the whole run
+	const uint32_t Avec = lane < ncols ? a_g + a_w : 0u;   // (columns behind the run's last: zero)
+	uint4* __restrict__ xs = reinterpret_cast<uint4*>(smem + 2u * threads * R) + tid;   // + trip * threads  (behind the two exchange buffers)
 #pragma unroll
-		for (int c = 0; c < XC; ++c) X[c] = sl_src[64 * c];
-		request_tables();
-		t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
-		// The exit addresses, HERE: behind the prologue's last request and in front of the first instruction that consumes a loaded word -- a wave sat 300 - 700
-		// cycles between the two (profiles/xrun_one_wait/stamps.md), and behind the loop the same gather is 775 - 850 cycles of every launch that nothing covers.
-		// One VGPR and one SGPR travel through the loop instead of out_occ, L and the eight words of out_pos.  (The scheduling barriers and the empty statement
-		// hold the place: left alone, the compiler sinks the gather behind the loop again, where its only consumer is.)
-		{
-			__builtin_amdgcn_sched_barrier(0);
-			slot_exit_where<LR>(run, L, lthr, Pthr, *where);
-			asm volatile("" : "+v"(where->base), "+s"(where->form));
-			__builtin_amdgcn_sched_barrier(0);
-		}
-		if (DBG && wstamps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XC + 3) : "memory");   // (... par_l, a_g, a_w and XC lane parts are)
-		stamps.w_landed = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
-		// X0 of column c = 2 A(thread's cell 0) + bias = lane part + (workgroup + wave part, held by lane c): kept in the thread's OWN 16 bytes per trip of
-		// an LDS area (nobody else reads them: no barrier) -- a register per column would need the column loop unrolled over the whole run
-		const uint32_t Avec = lane < ncols ? a_g + a_w : 0u;   // (columns behind the run's last: zero)
-		uint4* __restrict__ xs = reinterpret_cast<uint4*>(smem + 2u * threads * R) + tid;   // + trip * threads  (behind the two exchange buffers)
+	for (int t4 = 0; t4 < XC / 4; ++t4) {
+		uint32_t x[4];
 #pragma unroll
-		for (int t4 = 0; t4 < XC / 4; ++t4) {
-			uint32_t x[4];
-#pragma unroll
-			for (int k = 0; k < 4; ++k) x[k] = X[4 * t4 + k] + (uint32_t)__builtin_amdgcn_readlane((int)Avec, 4 * t4 + k);
-			xs[(uint32_t)t4 * threads] = make_uint4(x[0], x[1], x[2], x[3]);
-		}
+		for (int k = 0; k < 4; ++k) x[k] = X[4 * t4 + k] + (uint32_t)__builtin_amdgcn_readlane((int)Avec, 4 * t4 + k);
+		xs[(uint32_t)t4 * threads] = make_uint4(x[0], x[1], x[2], x[3]);
 	}
 	uint32_t par = par_l ^ par_w;   // bit 0: the next ending read
 	uint8_t* __restrict__ rec = P.bt + (((unsigned long long)run.rec_hi << 32) | run.rec_lo) + (size_t)w * run.n_ends * threads;   // (wave-uniform; the thread adds tid)
@@ -817,13 +826,12 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 #pragma unroll
 		for (int r = 0; r < R; ++r) D[r] = run.base_in - 2u * D[r];
 	}
-	if (warm) asm volatile("" ::"v"(warm_junk), "v"(D[0]));   // (the entering cells are here, so the request issued before them is too)
 	if (DBG && P.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	const unsigned long long t_loaded = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
 	if (DBG && wstamps) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (what the wait at the loop's head would sit out: t_loaded is where a wave reaches it)
 	stamps.w_scalars = (DBG && wstamps) ? (uint32_t)__builtin_readcyclecounter() : 0u;
 	if (DBG && wstamps) asm volatile("" ::: "memory");
-	if (!STREAM) __builtin_amdgcn_s_setprio(0);   // (the prologue's priority of the younger half ends here)
+	__builtin_amdgcn_s_setprio(0);   // (the prologue's priority of the younger half ends here)
 
 	const uint32_t lds0 = (uint32_t)(unsigned long long)smem;   // LDS byte offset of the exchange buffers
 	const uint32_t lane4 = lane << 2, tid16 = lds0 + (tid << 4);   // (tid16: this thread's 16 bytes of exchange buffer 0)
@@ -848,8 +856,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		D[2] = slot_y_sad_s(x, k2, D[2]);
 		D[3] = slot_y_sad_s(x, k3, D[3]);
 		if (DBG && P.dbg && !wstamps && w == 0 && tid == 0 && ci < 32u) P.dbg[(size_t)run.pad * 48 + 8 + ci] = __builtin_readcyclecounter() - t_loaded;
-		if (ctrl & 3u) {   // reads ending here: the first two are described in the control word, a third and later ones in the row (scalar loads, requested
-			              // before the second ending read is evaluated)
+		if (ctrl & 3u) {   // reads ending here: the first is described in the control word's low half
 			if (DBG && wstamps && !stamps.w_end_in && ((ctrl >> 2) & 31u) >= 8u) {   // (per-wave stamps: the run's first wave-slot ending, where it is a column's first)
 				stamps.w_end_in = (uint32_t)__builtin_readcyclecounter() | 1u;
 				ending(ctrl);
@@ -857,20 +864,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 			} else {
 				ending(ctrl);
 			}
-			if (ctrl & 2u) {
-				const unsigned long long row = (unsigned long long)(rows + ci);
-				uint32_t n_end = 2u, info = 0u;
-				if (ctrl & 1u) {   // (a count of 3 says "three or more")
-					n_end = *(const __attribute__((address_space(4))) uint32_t*)(row + 44);
-					info = *(const __attribute__((address_space(4))) uint32_t*)(row + 64);
-				}
-				ending(ctrl >> 16);
-				for (uint32_t e = 2; e < n_end; ++e) {
-					const uint32_t field = ((info & 31u) << 2) | (((info >> 8) & 15u) << 7) | (((info >> 16) & 1u) << 15);   // info: slot | qmask << 8 | exchange buffer << 16
-					if (e + 1u < n_end) info = *(const __attribute__((address_space(4))) uint32_t*)(row + 56 + 8 * e);     // (the next one's, a read ahead)
-					ending(field);
-				}
-			}
+			slotx_later_endings<R>(ending, ctrl, rows + ci);
 		}
 		++ci;
 	};
@@ -882,42 +876,6 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	// exit edge: five VALU -> SGPR copies per column): the columns behind the run's last -- up to seven, to a whole pair of trips -- are HARMLESS,
 	// their operands and Kr words are zero (slot_tables pads the lane parts and the Kr table, lanes >= ncols of Avec are zero: |0 - 0| = 0) and no
 	// read ends in them (the control words behind the run are zero).
-	if (STREAM) {
-		{   // (the first wait for scalar data: the touches of the prologue have returned, their registers are free)
-			asm volatile("" ::"s"(krA[0]), "s"(cwA[0]), "s"(gA[0]), "s"(wA[0]));
-			slot_touch_done(touch_kr); slot_touch_done(touch_cw); slot_touch_done(touch_g); slot_touch_done(touch_w);
-		}
-		// the operands of a trip: lane part (four coalesced loads, a trip ahead) + the workgroup's and the wave's part (two scalar-cache loads of four words)
-		for (uint32_t pairs = (ncols + 7u) >> 3; pairs; --pairs) {
-			asm volatile("" ::"s"(krA[0]), "s"(cwA[0]), "s"(gA[0]), "s"(wA[0]));
-			krB = *(slot_cptr16)(unsigned long long)(kr_tab + 16u);
-			cwB = *(slot_cptr4c)(unsigned long long)(cw_tab + 4u);
-			gB = *(slot_cptr4)(unsigned long long)(g_row + 4u);
-			wB = *(slot_cptr4)(unsigned long long)(w_row + 4u);
-#pragma unroll
-			for (int k = 0; k < 4; ++k) slB[k] = sl_src[64 * (4 + k)];
-			column(slA[0] + (gA[0] + wA[0]), krA[0], krA[1], krA[2], krA[3], cwA[0]);
-			column(slA[1] + (gA[1] + wA[1]), krA[4], krA[5], krA[6], krA[7], cwA[1]);
-			column(slA[2] + (gA[2] + wA[2]), krA[8], krA[9], krA[10], krA[11], cwA[2]);
-			column(slA[3] + (gA[3] + wA[3]), krA[12], krA[13], krA[14], krA[15], cwA[3]);
-			asm volatile("" ::"s"(krB[0]), "s"(cwB[0]), "s"(gB[0]), "s"(wB[0]));
-			kr_tab += 32u;
-			cw_tab += 8u;
-			g_row += 8u;
-			w_row += 8u;
-			sl_src += 512u;
-			krA = *(slot_cptr16)(unsigned long long)kr_tab;
-			cwA = *(slot_cptr4c)(unsigned long long)cw_tab;
-			gA = *(slot_cptr4)(unsigned long long)g_row;
-			wA = *(slot_cptr4)(unsigned long long)w_row;
-#pragma unroll
-			for (int k = 0; k < 4; ++k) slA[k] = sl_src[64 * k];
-			column(slB[0] + (gB[0] + wB[0]), krB[0], krB[1], krB[2], krB[3], cwB[0]);
-			column(slB[1] + (gB[1] + wB[1]), krB[4], krB[5], krB[6], krB[7], cwB[1]);
-			column(slB[2] + (gB[2] + wB[2]), krB[8], krB[9], krB[10], krB[11], cwB[2]);
-			column(slB[3] + (gB[3] + wB[3]), krB[12], krB[13], krB[14], krB[15], cwB[3]);
-		}
-	} else {
 	const uint32_t xstride = threads * 16u;
 	uint32_t xaddr = 2u * xstride + tid16;   // LDS byte address of the thread's line of trip 0 (behind the two exchange buffers)
 	typedef __attribute__((address_space(3))) const slot_u32x4* lds_line;
@@ -929,7 +887,7 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	for (uint32_t pairs = (ncols + 7u) >> 3; pairs; --pairs) {
 		asm volatile("" ::"s"(krA[0]), "s"(cwA[0]), "v"(xA.x));
 		krB = *(slot_cptr16)(unsigned long long)(kr_tab + 16u);
-		cwB = *(slot_cptr4c)(unsigned long long)(cw_tab + 4u);
+		cwB = *(slot_cptr4)(unsigned long long)(cw_tab + 4u);
 		xB = *(lds_line)(size_t)(xaddr + xstride);
 		column(xA.x, krA[0], krA[1], krA[2], krA[3], cwA[0]);
 		column(xA.y, krA[4], krA[5], krA[6], krA[7], cwA[1]);
@@ -940,13 +898,12 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 		cw_tab += 8u;
 		xaddr += 2u * xstride;
 		krA = *(slot_cptr16)(unsigned long long)kr_tab;
-		cwA = *(slot_cptr4c)(unsigned long long)cw_tab;
+		cwA = *(slot_cptr4)(unsigned long long)cw_tab;
 		xA = *(lds_line)(size_t)xaddr;
 		column(xB.x, krB[0], krB[1], krB[2], krB[3], cwB[0]);
 		column(xB.y, krB[4], krB[5], krB[6], krB[7], cwB[1]);
 		column(xB.z, krB[8], krB[9], krB[10], krB[11], cwB[2]);
 		column(xB.w, krB[12], krB[13], krB[14], krB[15], cwB[3]);
-	}
 	}
 	stamps.t_start = t_start; stamps.t_issued = t_issued; stamps.t_loaded = t_loaded;
 	stamps.t_loop = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
@@ -1049,91 +1006,117 @@ __device__ __forceinline__ void slot_runx_core(const DevProblem& P, const SlotRu
 	"global_store_byte %[ro], %[tk], %[rb]\n\t"                                                                        \
 	"v_add_u32_e32 %[ro], %[thr], %[ro]"
 
-template <bool DBG>
-__device__ __forceinline__ void slot_runx8_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[8],
-                                                SlotxStamps& stamps, const void* warm = nullptr) {
-	constexpr int LR = 3, R = 8;
-	extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // wave-slot exchange 2 x [threads][8]
-	const unsigned long long t_start = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
+// ---- Streamed operands: several workgroups per CU -- shared launches (slot_groupx<2 | 3>) and the runs that keep no LDS lines (slot_runx<2, 0>) -- fill each
+// other's waits.  R = 4 or 8 cells per thread; the operands of a trip are formed a trip ahead from the tables.  A trip is ONE 64-byte line of Kr words: CPT = 16 / R
+// columns.  Prologue + column loop; leaves the thread's cells in D.  No stamps: the debug library has no streamed kernel of its own.
+// `warm`: the entry behind a shared launch's own, requested into this XCD's L2 (slot_warm_entry), or null.  It goes out just before the entering cells
+// (which miss to HBM anyway); vector loads return in order, so the request has landed when the entering cells are used.
+template <int LR>
+__device__ __forceinline__ void slot_runx_stream_core(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, const uint32_t w, uint32_t (&D)[1 << LR],
+                                                      const SlotBatchEntry* warm = nullptr) {
+	static_assert(LR == 2 || LR == 3, "the ending blocks are written for four and for eight cells per thread");
+	constexpr int R = 1 << LR, CPT = 16 / R;
+	typedef uint32_t trip_words __attribute__((ext_vector_type(CPT)));   // one word per column of a trip
+	typedef const __attribute__((address_space(4))) trip_words* trip_cptr;
+	typedef const __attribute__((address_space(4))) uint32_t* slot_cptr1;
+	extern __shared__ __attribute__((aligned(16))) uint32_t smem[];   // wave-slot exchange 2 x [threads][R]
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t wave = uni(tid >> 6);
 	const uint32_t L = run.L;
 	const uint32_t Pthr = (w << L) | (tid << LR);
 	const uint32_t ncols = run.ncols, threads = run.threads;
-	const uint32_t ncp = (ncols + 7u) & ~7u;
+	const uint32_t ncp = (ncols + 7u) & ~7u;   // row length of the tables G, W and SL of an X run: padded with zeros to a pair of trips of four (slot_tables)
 	const uint32_t* __restrict__ tab = P.slot_tab;
-	const uint32_t* __restrict__ kr_tab = tab + run.tab_kr;               // [column][8]: sixteen words = two columns
+	// ---- prologue: one batch of loads.  Wave-uniform data through the scalar cache, in front of the entering cells: the control words and the Kr words of the
+	// first trip, the workgroup's half of the tie parities.
+	const uint32_t* __restrict__ kr_tab = tab + run.tab_kr;               // [column][R]
 	const uint32_t* __restrict__ cw_tab = kr_tab + ((ncols + (uint32_t)SLOT_XPAD) << LR);   // one control word per column, behind the Kr words (slot_tables)
-	typedef const __attribute__((address_space(4))) uint32_t* slot_cptr1;
 	slot_u32x16 krA = *(slot_cptr16)(unsigned long long)kr_tab, krB;
-	slot_u32x2 cwA = *(slot_cptr2)(unsigned long long)cw_tab, cwB;
+	trip_words cwA = *(trip_cptr)(unsigned long long)cw_tab, cwB;
 	const uint32_t par_w = *(slot_cptr1)(unsigned long long)(tab + run.tab_par + threads + w);
 	uint32_t warm_junk = 0;
-	if (warm) {   // (the next step's entry into this XCD's L2: see slot_runx_core)
-		const unsigned long long line = (unsigned long long)warm + ((lane & 7u) << 6);
-		asm volatile("global_load_dword %0, %1, off" : "=v"(warm_junk) : "v"(line) : "memory");
-	}
+	if (warm) warm_junk = slot_warm_entry(warm);
 	uint32_t Draw[R];
 	bool flip;
-	slot_enter_cells<LR, DBG>(P, run, prev, Pthr, Draw, flip);
+	slot_enter_cells<LR, false>(P, run, prev, Pthr, Draw, flip);
+	[[maybe_unused]] unsigned long long fmask = 0;
+	if constexpr (LR == 2) {
+		fmask = __builtin_amdgcn_ballot_w64(flip);   // (the lanes whose cells arrive reversed: formed HERE, under the loads' latency -- the empty
+		asm volatile("" : "+s"(fmask));               //  statement keeps the compiler from forming the mask again in front of its use)
+	}
 	const uint32_t par_l = tab[run.tab_par + tid];
-	const uint32_t* __restrict__ sl_src = tab + run.tab_sl + lane;
-	const uint32_t* __restrict__ g_row = tab + run.tab_g + w * ncp;
+	// the operands of a trip: lane part (CPT coalesced loads, a trip ahead) + the workgroup's and the wave's part (two scalar-cache loads of CPT words)
+	const uint32_t* __restrict__ sl_src = tab + run.tab_sl + lane;   // the lane part of column c: sl_src[64 c] (one coalesced 256-byte request per wave and column)
+	const uint32_t* __restrict__ g_row = tab + run.tab_g + w * ncp;  // the workgroup's and the wave's part: rows of the tables G and W
 	const uint32_t* __restrict__ w_row = tab + run.tab_w + wave * ncp;
-	slot_u32x2 gA = *(slot_cptr2)(unsigned long long)g_row, gB;
-	slot_u32x2 wA = *(slot_cptr2)(unsigned long long)w_row, wB;
-	uint32_t slA[2] = {sl_src[0], sl_src[64]}, slB[2];
-	// (the scalar lines of the whole run touched behind the prologue's requests, as in slot_runx_core: a trip of TWO columns is one line of Kr words)
-	const uint32_t touch_kr = slot_touch_lines<16>(kr_tab), touch_cw = slot_touch_lines<2>(cw_tab), touch_g = slot_touch_lines<2>(g_row), touch_w = slot_touch_lines<2>(w_row);
-	const unsigned long long t_issued = (DBG && P.dbg) ? __builtin_readcyclecounter() : 0ull;
-	uint32_t par = par_l ^ par_w;
-	uint8_t* __restrict__ rec = P.bt + (((unsigned long long)run.rec_hi << 32) | run.rec_lo) + (size_t)w * run.n_ends * threads;
+	trip_words gA = *(trip_cptr)(unsigned long long)g_row, gB;
+	trip_words wA = *(trip_cptr)(unsigned long long)w_row, wB;
+	uint32_t slA[CPT], slB[CPT];
 #pragma unroll
-	for (int r = 0; r < R; ++r) D[r] = flip ? Draw[R - 1 - r] : Draw[r];
-	if (!(run.yflags & 2u)) {
+	for (int k = 0; k < CPT; ++k) slA[k] = sl_src[64 * k];
+	// The Kr words of a trip are requested a trip ahead -- a MISS of the scalar cache every trip, and scalar loads share their counter with LDS operations: an
+	// ending read in the first columns of a trip waited for it with its own `s_waitcnt lgkmcnt(0)`.  The scalar lines of the whole run -- Kr and control words,
+	// the workgroup's and the wave's row of G / W -- are touched here, behind the prologue's requests, so that the loop's requests HIT (72 cycles).  One word of
+	// each line into a register that stays reserved until the first wait for scalar data below.  Lines behind a short run's last belong to the tables that follow.
+	const uint32_t touch_kr = slot_touch_lines<(2 << LR)>(kr_tab), touch_cw = slot_touch_lines<2>(cw_tab), touch_g = slot_touch_lines<2>(g_row), touch_w = slot_touch_lines<2>(w_row);
+	uint32_t par = par_l ^ par_w;   // bit 0: the next ending read
+	uint8_t* __restrict__ rec = P.bt + (((unsigned long long)run.rec_hi << 32) | run.rec_lo) + (size_t)w * run.n_ends * threads;   // (wave-uniform; the thread adds tid)
+	// D: Y = B - 2 D.  The mirrored group of a halved run arrives in reverse order.
+	if constexpr (LR == 2) {
+		// FOUR selects under one lane mask (written as `flip ? Draw[R - 1 - r] : Draw[r]` the compiler selects the INDEX and extracts dynamically: 12 compares,
+		// 16 selects and their hazard waits behind the cells' landing, on every wave).  ONE statement, and two wait states in front: a lane mask that a VALU
+		// compare wrote may not be read by the next VALU instruction, and the compiler does not look for that inside an asm statement.
+		asm("s_nop 1\n\t"
+		    "v_cndmask_b32_e64 %0, %4, %7, %8\n\t"
+		    "v_cndmask_b32_e64 %1, %5, %6, %8\n\t"
+		    "v_cndmask_b32_e64 %2, %6, %5, %8\n\t"
+		    "v_cndmask_b32_e64 %3, %7, %4, %8"
+		    : "=&v"(D[0]), "=&v"(D[1]), "=&v"(D[2]), "=&v"(D[3])
+		    : "v"(Draw[0]), "v"(Draw[1]), "v"(Draw[2]), "v"(Draw[3]), "s"(fmask));
+	} else {
+#pragma unroll
+		for (int r = 0; r < R; ++r) D[r] = flip ? Draw[R - 1 - r] : Draw[r];
+	}
+	if (!(run.yflags & 2u)) {   // the entering column is in D form
 #pragma unroll
 		for (int r = 0; r < R; ++r) D[r] = run.base_in - 2u * D[r];
 	}
-	if (warm) asm volatile("" ::"v"(warm_junk), "v"(D[0]));
-	if (DBG && P.dbg) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	const unsigned long long t_loaded = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
+	if (warm) slot_warm_done(warm_junk, D[0]);
 
-	const uint32_t lds0 = (uint32_t)(unsigned long long)smem;
-	const uint32_t lane4 = lane << 2, tid32 = lds0 + (tid << 5);
-	const uint32_t xbytes = threads * R * 4u;
-	uint32_t rec_off = tid;
+	const uint32_t lds0 = (uint32_t)(unsigned long long)smem;   // LDS byte offset of the exchange buffers
+	const uint32_t lane4 = lane << 2, tidx = lds0 + (tid << (LR + 2));   // (tidx: this thread's bytes of exchange buffer 0)
+	const uint32_t xbytes = threads * R * 4u;                   // one exchange buffer
+	uint32_t rec_off = tid;                                     // this thread's byte of the current ending read, relative to rec
 	const SlotRow* __restrict__ rows = P.slot_rows + run.row_off;
+	// one ending read (its control field is a scalar): SLOTX_ENDING_ASM / SLOTX8_ENDING_ASM
 	auto ending = [&](const uint32_t field) {
-		unsigned long long q1, q2, q3, q4, q5, q6, q7, qt, qn;
+		unsigned long long q1, q2, q3, qt, qn;
 		uint32_t t, sa, sl, takes;
-		asm volatile(SLOTX8_ENDING_ASM
-		             : [d0] "+v"(D[0]), [d1] "+v"(D[1]), [d2] "+v"(D[2]), [d3] "+v"(D[3]), [d4] "+v"(D[4]), [d5] "+v"(D[5]), [d6] "+v"(D[6]), [d7] "+v"(D[7]), [par] "+v"(par),
-		               [ro] "+v"(rec_off), [tk] "=&v"(takes), [t] "=&v"(t), [sa] "=&s"(sa), [sl] "=&s"(sl), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3), [q4] "=&s"(q4),
-		               [q5] "=&s"(q5), [q6] "=&s"(q6), [q7] "=&s"(q7), [qt] "=&s"(qt), [qn] "=&s"(qn)
-		             : [cw] "s"(field), [xby] "s"(xbytes), [thr] "s"(threads), [rb] "s"(rec), [l4] "v"(lane4), [t32] "v"(tid32)
-		             : "memory", "scc", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+		if constexpr (LR == 2) {
+			uint32_t a;
+			asm volatile(SLOTX_ENDING_ASM
+			             : [d0] "+v"(D[0]), [d1] "+v"(D[1]), [d2] "+v"(D[2]), [d3] "+v"(D[3]), [par] "+v"(par), [ro] "+v"(rec_off), [tk] "=&v"(takes), [t] "=&v"(t), [a] "=&v"(a),
+			               [sa] "=&s"(sa), [sl] "=&s"(sl), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3), [qt] "=&s"(qt), [qn] "=&s"(qn)
+			             : [cw] "s"(field), [xby] "s"(xbytes), [thr] "s"(threads), [rb] "s"(rec), [l4] "v"(lane4), [t16] "v"(tidx)
+			             : "memory", "scc", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+		} else {
+			unsigned long long q4, q5, q6, q7;
+			asm volatile(SLOTX8_ENDING_ASM
+			             : [d0] "+v"(D[0]), [d1] "+v"(D[1]), [d2] "+v"(D[2]), [d3] "+v"(D[3]), [d4] "+v"(D[4]), [d5] "+v"(D[5]), [d6] "+v"(D[6]), [d7] "+v"(D[7]), [par] "+v"(par),
+			               [ro] "+v"(rec_off), [tk] "=&v"(takes), [t] "=&v"(t), [sa] "=&s"(sa), [sl] "=&s"(sl), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3), [q4] "=&s"(q4),
+			               [q5] "=&s"(q5), [q6] "=&s"(q6), [q7] "=&s"(q7), [qt] "=&s"(qt), [qn] "=&s"(qn)
+			             : [cw] "s"(field), [xby] "s"(xbytes), [thr] "s"(threads), [rb] "s"(rec), [l4] "v"(lane4), [t32] "v"(tidx)
+			             : "memory", "scc", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63");
+		}
 	};
+	// column k of the current trip: its operand x, its R Kr words, its control word
 	uint32_t ci = 0;
-	auto column = [&](const uint32_t x, const slot_u32x16& kr, const int half, const uint32_t ctrl) {
+	auto column = [&](const uint32_t x, const slot_u32x16& kr, const int k, const uint32_t ctrl) {
 #pragma unroll
-		for (int r = 0; r < R; ++r) D[r] = slot_y_sad_s(x, kr[half * 8 + r], D[r]);
-		if (DBG && P.dbg && w == 0 && tid == 0 && ci < 32u) P.dbg[(size_t)run.pad * 48 + 8 + ci] = __builtin_readcyclecounter() - t_loaded;
-		if (ctrl & 3u) {   // (the first two ending reads in the control word, later ones in the row: as in slot_runx_core)
+		for (int r = 0; r < R; ++r) D[r] = slot_y_sad_s(x, kr[k * R + r], D[r]);
+		if (ctrl & 3u) {   // reads ending here: the first is described in the control word's low half
 			ending(ctrl);
-			if (ctrl & 2u) {
-				const unsigned long long row = (unsigned long long)(rows + ci);
-				uint32_t n_end = 2u, info = 0u;
-				if (ctrl & 1u) {
-					n_end = *(slot_cptr1)(row + 44);
-					info = *(slot_cptr1)(row + 64);
-				}
-				ending(ctrl >> 16);
-				for (uint32_t e = 2; e < n_end; ++e) {
-					const uint32_t field = ((info & 31u) << 2) | (((info >> 8) & 255u) << 7) | (((info >> 16) & 1u) << 15);
-					if (e + 1u < n_end) info = *(slot_cptr1)(row + 56 + 8 * e);
-					ending(field);
-				}
-			}
+			slotx_later_endings<R>(ending, ctrl, rows + ci);
 		}
 		++ci;
 	};
@@ -1141,48 +1124,55 @@ __device__ __forceinline__ void slot_runx8_core(const DevProblem& P, const SlotR
 		asm volatile("" ::"s"(krA[0]), "s"(cwA[0]), "s"(gA[0]), "s"(wA[0]));
 		slot_touch_done(touch_kr); slot_touch_done(touch_cw); slot_touch_done(touch_g); slot_touch_done(touch_w);
 	}
-	// two trips (of two columns) per loop iteration; the columns behind the run's last are harmless (zeros), as in slot_runx_core
-	for (uint32_t quads = (ncols + 3u) >> 2; quads; --quads) {
+	// Two trips per loop iteration (no register copies): while trip t is evaluated from set A, the operands, Kr words and control words of trip t + 1 travel
+	// into set B, and the other way round.  Scalar loads return out of order, so a wait for set A would also wait for the requests of set B issued before it: the
+	// empty statements below USE set A first -- the compiler's wait lands in front of them, before the next requests go out.
+	// A counted loop without a way out in the middle (a `break` per column made the compiler merge the loop's scalars with undefined values on the exit edge:
+	// five VALU -> SGPR copies per column): the columns behind the run's last, to a whole pair of trips, are HARMLESS -- their operands and Kr words are zero
+	// (slot_tables pads the tables: |0 - 0| = 0) and no read ends in them (the control words behind the run are zero).
+	for (uint32_t pairs = (ncols + 2u * CPT - 1u) / (2u * CPT); pairs; --pairs) {
 		asm volatile("" ::"s"(krA[0]), "s"(cwA[0]), "s"(gA[0]), "s"(wA[0]));
 		krB = *(slot_cptr16)(unsigned long long)(kr_tab + 16u);
-		cwB = *(slot_cptr2)(unsigned long long)(cw_tab + 2u);
-		gB = *(slot_cptr2)(unsigned long long)(g_row + 2u);
-		wB = *(slot_cptr2)(unsigned long long)(w_row + 2u);
-		slB[0] = sl_src[128];
-		slB[1] = sl_src[192];
-		column(slA[0] + (gA[0] + wA[0]), krA, 0, cwA[0]);
-		column(slA[1] + (gA[1] + wA[1]), krA, 1, cwA[1]);
+		cwB = *(trip_cptr)(unsigned long long)(cw_tab + CPT);
+		gB = *(trip_cptr)(unsigned long long)(g_row + CPT);
+		wB = *(trip_cptr)(unsigned long long)(w_row + CPT);
+#pragma unroll
+		for (int k = 0; k < CPT; ++k) slB[k] = sl_src[64 * (CPT + k)];
+#pragma unroll
+		for (int k = 0; k < CPT; ++k) column(slA[k] + (gA[k] + wA[k]), krA, k, cwA[k]);
 		asm volatile("" ::"s"(krB[0]), "s"(cwB[0]), "s"(gB[0]), "s"(wB[0]));
 		kr_tab += 32u;
-		cw_tab += 4u;
-		g_row += 4u;
-		w_row += 4u;
-		sl_src += 256u;
+		cw_tab += 2 * CPT;
+		g_row += 2 * CPT;
+		w_row += 2 * CPT;
+		sl_src += 128 * CPT;
 		krA = *(slot_cptr16)(unsigned long long)kr_tab;
-		cwA = *(slot_cptr2)(unsigned long long)cw_tab;
-		gA = *(slot_cptr2)(unsigned long long)g_row;
-		wA = *(slot_cptr2)(unsigned long long)w_row;
-		slA[0] = sl_src[0];
-		slA[1] = sl_src[64];
-		column(slB[0] + (gB[0] + wB[0]), krB, 0, cwB[0]);
-		column(slB[1] + (gB[1] + wB[1]), krB, 1, cwB[1]);
+		cwA = *(trip_cptr)(unsigned long long)cw_tab;
+		gA = *(trip_cptr)(unsigned long long)g_row;
+		wA = *(trip_cptr)(unsigned long long)w_row;
+#pragma unroll
+		for (int k = 0; k < CPT; ++k) slA[k] = sl_src[64 * k];
+#pragma unroll
+		for (int k = 0; k < CPT; ++k) column(slB[k] + (gB[k] + wB[k]), krB, k, cwB[k]);
 	}
-	stamps.t_start = t_start; stamps.t_issued = t_issued; stamps.t_loaded = t_loaded;
-	stamps.t_loop = (DBG && P.dbg) ? __builtin_readcyclecounter() + (D[0] & 0u) : 0ull;
 }
 
-template <int LR, bool DBG, bool SPEC, bool EARLY = false>
-__device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t* score_out, const uint32_t w, uint32_t (&D)[1 << LR],
-                                               const SlotxStamps& stamps, SlotExitWhere* where = nullptr) {
+// The exit of an X run behind its column loop.  Streamed operands: both parts (the descriptor of a shared launch is fetched again for it).
+template <int LR, bool SPEC>
+__device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t* score_out, const uint32_t w, uint32_t (&D)[1 << LR]) {
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t wave = uni(tid >> 6);
-	if constexpr (EARLY) {   // (formed in the prologue, slot_runx_core: the store alone is left)
-		static_assert(LR == 2, "two reg slots' positions in the store form");
-		slot_exit_store<LR, DBG, SPEC, true>(P, run, cur, D, w, lane, wave, run.threads, *where);
-	} else {
-		const uint32_t L = run.L, lthr = tid << LR;
-		slot_exit_cells<LR, DBG, SPEC, true>(P, run, cur, D, w, tid, lane, wave, L, lthr, (w << L) | lthr, run.threads);
-	}
+	const uint32_t L = run.L, lthr = tid << LR;
+	slot_exit_cells<LR, false, SPEC, true>(P, run, cur, D, w, tid, lane, wave, L, lthr, (w << L) | lthr, run.threads);
+	if (score_out && w == 0 && tid == 0) *score_out = D[0];
+}
+// LDS operand lines: `where` was formed in the prologue (slot_runx_lds_core), the store alone is left; the debug library's stamps.
+template <bool DBG, bool SPEC>
+__device__ __forceinline__ void slot_runx_exit_early(const DevProblem& P, const SlotRun& run, uint32_t* __restrict__ cur, uint32_t* score_out, const uint32_t w, uint32_t (&D)[4],
+                                                     const SlotxStamps& stamps, const SlotExitWhere& where) {
+	const uint32_t tid = threadIdx.x, lane = tid & 63u;
+	const uint32_t wave = uni(tid >> 6);
+	slot_exit_store<2, DBG, SPEC, true>(P, run, cur, D, w, lane, wave, run.threads, where);
 	if (score_out && w == 0 && tid == 0) *score_out = D[0];
 	if (DBG && P.dbg && w == 0 && tid == 0) {
 		unsigned long long* d = P.dbg + (size_t)run.pad * 48;
@@ -1202,15 +1192,17 @@ __device__ __forceinline__ void slot_runx_exit(const DevProblem& P, const SlotRu
 template <int LR, int XC, bool DBG, bool SPEC>
 __device__ __forceinline__ void slot_runx_body(const DevProblem& P, const SlotRun& run, const uint32_t* __restrict__ prev, uint32_t* __restrict__ cur, const uint32_t w,
                                                uint32_t* score_out) {
+	static_assert(LR == 2, "a launch of its own: four cells per thread");
 	uint32_t D[1 << LR];
-	SlotxStamps stamps;
 	if constexpr (XC > 0) {   // (one workgroup per CU: the exit addresses are formed under the prologue's wait)
+		SlotxStamps stamps;
 		SlotExitWhere where;
-		slot_runx_core<LR, XC, DBG>(P, run, prev, w, D, stamps, nullptr, &where);
-		slot_runx_exit<LR, DBG, SPEC, true>(P, run, cur, score_out, w, D, stamps, &where);
+		slot_runx_lds_core<XC, DBG>(P, run, prev, w, D, stamps, where);
+		slot_runx_exit_early<DBG, SPEC>(P, run, cur, score_out, w, D, stamps, where);
 	} else {
-		slot_runx_core<LR, XC, DBG>(P, run, prev, w, D, stamps);
-		slot_runx_exit<LR, DBG, SPEC>(P, run, cur, score_out, w, D, stamps);
+		static_assert(!DBG, "streamed operands have no form with stamps");
+		slot_runx_stream_core<LR>(P, run, prev, w, D);
+		slot_runx_exit<LR, SPEC>(P, run, cur, score_out, w, D);
 	}
 }
 
@@ -1245,9 +1237,8 @@ __global__ __launch_bounds__(256) void slot_tables(DevProblem P, const SlotRun* 
 			uint32_t word = 0;
 			if (c < ncols) {
 				const SlotRow& row = rows[c];
-				auto field = [](uint32_t info) { return ((info & 31u) << 2) | (((info >> 8) & 255u) << 7) | (((info >> 16) & 1u) << 15); };
-				if (row.n_end) word = (row.n_end < 3u ? row.n_end : 3u) | field(row.end[0].info);
-				if (row.n_end > 1u) word |= field(row.end[1].info) << 16;
+				if (row.n_end) word = (row.n_end < 3u ? row.n_end : 3u) | slot_end_field<255u>(row.end[0].info);
+				if (row.n_end > 1u) word |= slot_end_field<255u>(row.end[1].info) << 16;
 			}
 			tab[run.tab_kr + n_krw + c] = word;
 		} else if (i >= n_g + n_w + n_sl) {
@@ -1280,7 +1271,7 @@ __global__ __launch_bounds__(256) void slot_tables(DevProblem P, const SlotRun* 
 // words and the other touches, `prev` inside its branch -- and three more at the loop's head (`cur` / `score_out`, P.bt, P.slot_rows): a scalar-cache hit is
 // 72 cycles at least, the first touch of the argument segment 565.  Here EVERY word the prologue, the loop's head and the exit use is
 // requested in one group with one wait behind it -- the group touches every line that is used, so touch_kernel_arguments has nothing left to do -- and the
-// younger half of the workgroup raises its priority (slot_runx_core) while the group travels.  The loads and their wait are ONE statement: the compiler
+// younger half of the workgroup raises its priority (slot_runx_lds_core) while the group travels.  The loads and their wait are ONE statement: the compiler
 // cannot see a load inside an asm statement and would hand out a destination before the data is there.
 // Not fetched: `in_pos` (the general entry layout keeps a load of its own, slot_enter_cells) and what only the debug library reads.
 struct SlotRunxArgs {
@@ -1318,7 +1309,7 @@ __device__ __forceinline__ void slot_runx_arguments(SlotRunxArgs& a) {
 	    "s_load_dwordx2 %[rows], %[ka], %[o_rows]\n\t"
 	    "s_load_dwordx2 %[keys], %[ka], %[o_keys]\n\t"
 	    "s_load_dword %[stride], %[ka], %[o_stride]\n\t"
-	    "s_cmpk_lt_u32 %[tid0], 0x100\n\t"     // (waves 4 .. 7, the second-dispatched wave of every SIMD: the prologue at priority 1 -- slot_runx_core;
+	    "s_cmpk_lt_u32 %[tid0], 0x100\n\t"     // (waves 4 .. 7, the second-dispatched wave of every SIMD: the prologue at priority 1 -- slot_runx_lds_core;
 	    "s_cbranch_scc1 .Lxa%=\n\t"            //  a scalar guard, s_setprio ignores EXEC)
 	    "s_setprio 1\n"
 	    ".Lxa%=:\n\t"
@@ -1420,19 +1411,6 @@ __device__ __forceinline__ DevProblem slot_entry_problem(const SlotBatchEntry& e
 	return P;
 }
 
-// Shared launches read their run descriptor from memory before anything else can be requested -- a miss all the way to HBM per launch.  The entry of a
-// table's next step lies behind the current one (the schedule's entries are consecutive): the kernel requests its lines with ONE vector load at its very
-// start -- into this XCD's L2, where the next launch's workgroup (x, y) finds them (measured: 24 coverage-15 tables 11.1 -> 10.5 us per launch).  The
-// destination register must stay reserved until the load has landed (the compiler cannot see a load inside an asm statement): slot_warm_done() at the
-// kernel's end -- vector loads return in order, and the body has consumed later ones by then.
-__device__ __forceinline__ uint32_t slot_warm_next(const SlotBatchEntry* ep) {
-	uint32_t junk;
-	const unsigned long long line = (unsigned long long)(ep + 1) + ((threadIdx.x & 7u) << 6);
-	asm volatile("global_load_dword %0, %1, off" : "=v"(junk) : "v"(line) : "memory");
-	return junk;
-}
-__device__ __forceinline__ void slot_warm_done(uint32_t junk) { asm volatile("" ::"v"(junk)); }
-
 // Which table and which workgroup of its run a workgroup of a group launch is.  Workgroups go to the XCDs round robin in their linear order (x fastest):
 // with the TABLE as x -- `args.pad` != 0, the table dimension padded to a multiple of eight -- every workgroup of a table runs on ONE XCD, and the column a run
 // hands to the next stays in that XCD's L2 instead of crossing to another one (scripts/micro/r5_boundary.hip: 2.26 us instead of 2.89 per dependent launch).
@@ -1449,27 +1427,24 @@ __device__ __forceinline__ SlotGroupWho slot_group_who(const SlotGroupArgs& args
 // The X runs of several tables in one launch (the counterpart of slot_group below for runs that take the X kernel; the group's other runs go out as
 // a slot_group launch of their own).  The entry is read TWICE: the prologue's and the loop's half before the loop, the exit's half -- exchange layout,
 // masks, the speculative seed's slot -- after it (scalar-cache hits), so the loop's scalar budget is the loop's alone.
+// (DBG is part of the kernel's name and nothing else: the streamed core has no debug form.)
 template <int LR = 2, bool DBG = false>
 __global__ __launch_bounds__(512, 4) void slot_groupx(SlotGroupArgs args) {
 	const SlotGroupWho who = slot_group_who(args);
 	if (who.none) return;
 	const SlotBatchEntry* ep = args.entry[who.table];
 	uint32_t D[1 << LR];
-	SlotxStamps stamps;
 	{
 		const SlotBatchEntry e = slot_scalar_copy(ep);
 		if (who.w >= (1u << (e.run.g - e.run.half)) || threadIdx.x >= e.run.threads) return;
-		DevProblem P = slot_entry_problem(e, false);
-		if (DBG) P.dbg_flags = e.pad2;
-		const void* warm = (e.pad2 & 0x10000u) ? nullptr : (const void*)(ep + 1);   // (pad2 bit 16: timing experiment, debug library)
-		if constexpr (LR == 3) slot_runx8_core<DBG>(P, e.run, e.prev, who.w, D, stamps, warm);
-		else slot_runx_core<2, 0, DBG>(P, e.run, e.prev, who.w, D, stamps, warm);
+		const DevProblem P = slot_entry_problem(e, false);
+		slot_runx_stream_core<LR>(P, e.run, e.prev, who.w, D, (e.pad2 & 0x10000u) ? nullptr : ep + 1);   // (pad2 bit 16: timing experiment, debug library)
 	}
 	asm volatile("" : "+s"(ep));   // (opaque: what follows is fetched again, not kept in registers through the loop)
 	const SlotBatchEntry e = slot_scalar_copy(ep);
-	DevProblem P = slot_entry_problem(e, false);
-	if (e.run.spec_id) slot_runx_exit<LR, DBG, true>(P, e.run, e.cur, e.score_out, who.w, D, stamps);
-	else slot_runx_exit<LR, DBG, false>(P, e.run, e.cur, e.score_out, who.w, D, stamps);
+	const DevProblem P = slot_entry_problem(e, false);
+	if (e.run.spec_id) slot_runx_exit<LR, true>(P, e.run, e.cur, e.score_out, who.w, D);
+	else slot_runx_exit<LR, false>(P, e.run, e.cur, e.score_out, who.w, D);
 }
 
 // One launch = the next run of SEVERAL TABLES (whamd_dptable_enqueue_many: independent tables advance in lockstep on one stream):
