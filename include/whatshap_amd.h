@@ -1118,6 +1118,84 @@ whamd_status_t whamd_poly_select_clusters(uint64_t n_pos, const uint64_t* pc_ptr
 whamd_status_t whamd_poly_haplotypes(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
                                      const int8_t* pc_consensus, int device, int8_t* haplotypes_out, uint32_t* launches_out);
 
+/* ---- Read merging (ReadMerger.merge of whatshap/merge.py; `whatshap phase --merge-reads`, cli/phase.py:517-534) ---------------------------
+ * The step in front of the read selection.  One problem is one read set: the reads, IN THE ORDER GIVEN, as CSR of (position, allele,
+ * quality); the two integer thresholds, which the caller computes with the reference's own expression, 1 + int(log(threshold, (1 - e) /
+ * (e / 3))); and max_error_rate.  Read i has begin_i (the position of its first entry), len_i entries and end_i = begin_i + len_i -- a
+ * position plus a count, as there.
+ * Pairs: j < i are compared iff end_j > max(begin_{j+1} .. begin_i).  hang = begin_i - begin_j; start = hang if hang >= 0, else
+ * max(len_j + hang, 0); L = min(len_j - start, len_i); mismatch = the t < L with allele_j[start + t] != allele_i[t] -- a shift by list
+ * index, as there; match = L - mismatch.  Blue edge: L >= thr_neg_diff and (double)min(match, mismatch) / (double)L <= max_error_rate
+ * and match - mismatch >= thr_diff.  A blue edge is also a not-blue edge iff mismatch - match >= thr_neg_diff.
+ * Components of the blue graph, the smallest id their representative.  A component of more than one read is one superread at its
+ * representative: per position of any member sum[a] = the members' qualities with allele a (int64), positions ascending, allele 0 if
+ * sum0 >= sum1 else 1, quality |sum1 - sum0|.  The reference cuts components apart when not-blue edges exist (n_not_blue > 0): the
+ * caller does that from the edge list and calls again with `representative` given, which skips pairs and components.
+ * Device (csrc/readmerge_device.hip): the pairs -- flags and mismatches, scan, the edge list in ascending (j, i) -- and the sums
+ * (integer atomics per (superread, position, allele), then allele and quality): WHAMD_READMERGE_LAUNCHES launches for a call with a pair
+ * and a superread, whatever the problems; 4 of them are the pairs', 5 the superreads', and a stage without work launches nothing.  Union-find
+ * and the superreads' sorted positions are host work inside the call.
+ * Errors, all with nothing launched.  WHAMD_ERR_INVALID: a read without entries, an allele outside {0, 1}, a null array, read_ptr that
+ * decreases or does not start at 0, a given representative that is not the smallest id of its component.  WHAMD_ERR_UNSUPPORTED: a
+ * position of magnitude 2^62 or more; |quality| of a problem summing beyond 2^63 - 1; 2^32 - 4096 or more reads, entries or pairs in
+ * one call.  Never an approximate answer. */
+#define WHAMD_READMERGE_LAUNCHES 9u
+
+typedef struct whamd_readmerge_view {
+	uint64_t n_reads;
+	const uint64_t* read_ptr;           /* [n_reads + 1] into the entry arrays */
+	const int64_t* entry_position;      /* [n_entries] */
+	const uint8_t* entry_allele;        /* [n_entries] 0 / 1 */
+	const int64_t* entry_quality;       /* [n_entries] */
+	const uint32_t* representative;     /* NULL, or [n_reads]: the components are given */
+	int64_t thr_diff;
+	int64_t thr_neg_diff;
+	double max_error_rate;
+	uint32_t want_edges;                /* 0 / 1: keep the edge list */
+	uint32_t reserved;
+} whamd_readmerge_view;
+
+typedef struct whamd_readmerge_stats {
+	uint64_t n_reads;
+	uint64_t n_entries;
+	uint64_t n_pairs;                   /* pairs compared */
+	uint64_t n_blue;
+	uint64_t n_not_blue;
+	uint64_t n_merged_components;       /* components of more than one read */
+	uint64_t n_merged_entries;          /* entries of their reads */
+	uint64_t n_super_entries;           /* entries of the superreads */
+	uint32_t launches;                  /* kernel launches of the whole call: 0, 4, 5 or WHAMD_READMERGE_LAUNCHES */
+	double host_ms;                     /* wall, whole call: validation, packing, partner ranges */
+	double upload_ms;                   /* HIP events, whole call (both stages) */
+	double kernel_ms;                   /* HIP events, whole call (both stages) */
+	double pair_kernel_ms;              /* of it: the pairs' four launches, the wait for the edge count included */
+	double download_ms;                 /* HIP events, whole call */
+	double components_ms;               /* wall, whole call: union-find, the superreads' positions and slots */
+	double total_ms;                    /* wall, whole call */
+} whamd_readmerge_stats;
+
+typedef struct whamd_readmerge_result whamd_readmerge_result; /* opaque: the result of one whamd_readmerge call */
+
+/* One call for a batch of problems (read sets): a constant number of launches. */
+whamd_status_t whamd_readmerge(const whamd_readmerge_view* problems, uint64_t n_problems, int device, whamd_readmerge_result** out);
+uint64_t whamd_readmerge_problem_count(const whamd_readmerge_result* r);
+/* Reads, superread entries and (want_edges) edges of problem m. */
+uint64_t whamd_readmerge_count(const whamd_readmerge_result* r, uint64_t m);
+uint64_t whamd_readmerge_super_count(const whamd_readmerge_result* r, uint64_t m);
+uint64_t whamd_readmerge_edge_count(const whamd_readmerge_result* r, uint64_t m);
+/* Per read of problem m: its representative and the number of reads in its component; super_ptr_out [reads + 1]: read k owns the
+ * superread entries super_ptr[k] .. super_ptr[k+1]-1 (none unless it represents more than one read); per entry the position
+ * (ascending within a superread), allele, quality and the two sums.  NULL skips. */
+whamd_status_t whamd_readmerge_get(const whamd_readmerge_result* r, uint64_t m, uint32_t* representative_out, uint32_t* component_size_out,
+                                   uint64_t* super_ptr_out, int64_t* position_out, uint8_t* allele_out, int64_t* quality_out, int64_t* sum0_out,
+                                   int64_t* sum1_out);
+/* The blue edges of problem m (want_edges) in ascending (j, i): byte for byte the same from call to call.  NULL skips. */
+whamd_status_t whamd_readmerge_get_edges(const whamd_readmerge_result* r, uint64_t m, uint32_t* j_out, uint32_t* i_out, uint32_t* match_out,
+                                         uint32_t* mismatch_out, uint8_t* not_blue_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_readmerge_get_stats(const whamd_readmerge_result* r, uint64_t m, whamd_readmerge_stats* stats_out);
+void whamd_readmerge_destroy(whamd_readmerge_result* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,12 @@ whamd_status_t whamd_debug_tagphase_host(const whamd_tagphase_view* problems, ui
  * debug library. */
 whamd_status_t whamd_debug_prior_genotypes_host(const whamd_prior_genotypes_view* problems, uint64_t n_problems, whamd_prior_genotypes_result** out);
 
+/* HOST-ONLY DIAGNOSTICS of the read merging (csrc/readmerge.cpp): the same validation, packing and partner ranges as whamd_readmerge,
+ * then every pair and every sum in plain loops on one CPU thread with the functions the kernels call (csrc/readmerge.h) -- what the CPU
+ * test-suite holds to the recorded reference, the same bytes as the device; never what the product calls.  Launches nothing.  Read with
+ * the whamd_readmerge_* getters of the debug library. */
+whamd_status_t whamd_debug_readmerge_host(const whamd_readmerge_view* problems, uint64_t n_problems, whamd_readmerge_result** out);
+
 /* THE LAUNCH LEDGER (csrc/dp_device.hip): which kernel instantiation every launch of a solve took, so that a test can hold the
  * choice itself -- not only the result -- against the rules of DESIGN.md 6.2 and slots.h.  Host code of the debug library only.
  *

@@ -268,6 +268,19 @@ class PolyThreadStats(Record):
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "fill_ms", "total_ms")]
 
 
+class ReadmergeView(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("entry_position", C.POINTER(C.c_int64)), ("entry_allele", C.POINTER(C.c_uint8)),
+                ("entry_quality", C.POINTER(C.c_int64)), ("representative", C.POINTER(C.c_uint32)), ("thr_diff", C.c_int64), ("thr_neg_diff", C.c_int64),
+                ("max_error_rate", C.c_double), ("want_edges", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ReadmergeStats(Record):
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_entries", "n_pairs", "n_blue", "n_not_blue", "n_merged_components", "n_merged_entries",
+                                                "n_super_entries")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "pair_kernel_ms", "download_ms", "components_ms", "total_ms")]
+
+
+READMERGE_LAUNCHES = 9          # WHAMD_READMERGE_LAUNCHES of include/whatshap_amd.h
 POLY_THREAD_LAUNCHES = 13       # WHAMD_POLY_THREAD_LAUNCHES of include/whatshap_amd.h
 POLY_THREAD_MAX_PLOIDY = 16     # WHAMD_POLY_THREAD_MAX_PLOIDY
 POLY_THREAD_MAX_ALLELES = 16    # WHAMD_POLY_THREAD_MAX_ALLELES
@@ -459,6 +472,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_poly_haplotypes_host.restype = C.c_int
     L.whamd_debug_poly_haplotypes_host.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8),
                                                    C.POINTER(C.c_int8)]
+    L.whamd_debug_readmerge_host.restype = C.c_int
+    L.whamd_debug_readmerge_host.argtypes = [C.POINTER(ReadmergeView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
     L.whamd_debug_solve_kernels.argtypes = [C.POINTER(DebugKernel), C.c_size_t]
     L.whamd_debug_dptable_launches.restype = C.c_int
@@ -710,6 +725,23 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_poly_haplotypes.restype = C.c_int
     L.whamd_poly_haplotypes.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8), C.c_int,
                                         C.POINTER(C.c_int8), C.POINTER(C.c_uint32)]
+    L.whamd_readmerge.restype = C.c_int
+    L.whamd_readmerge.argtypes = [C.POINTER(ReadmergeView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_readmerge_problem_count.restype = C.c_uint64
+    L.whamd_readmerge_problem_count.argtypes = [C.c_void_p]
+    for name in ("whamd_readmerge_count", "whamd_readmerge_super_count", "whamd_readmerge_edge_count"):
+        getattr(L, name).restype = C.c_uint64
+        getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_readmerge_get.restype = C.c_int
+    L.whamd_readmerge_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.whamd_readmerge_get_edges.restype = C.c_int
+    L.whamd_readmerge_get_edges.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint8)]
+    L.whamd_readmerge_get_stats.restype = C.c_int
+    L.whamd_readmerge_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ReadmergeStats)]
+    L.whamd_readmerge_destroy.restype = None
+    L.whamd_readmerge_destroy.argtypes = [C.c_void_p]
     if L.whamd_abi_version() != ABI_VERSION:
         raise ImportError(f"{path} has ABI version {L.whamd_abi_version()}, this binding was written for {ABI_VERSION} (stale library? run make)")
     return L
@@ -748,6 +780,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_thread_inputs", "whamd_poly_thread_problem_count", "whamd_poly_thread_position_count", "whamd_poly_thread_row_count",
     "whamd_poly_thread_cov_count", "whamd_poly_thread_get_rows", "whamd_poly_thread_get_cov", "whamd_poly_thread_get_stats", "whamd_poly_thread_destroy",
     "whamd_poly_select_clusters", "whamd_poly_haplotypes",
+    "whamd_readmerge", "whamd_readmerge_problem_count", "whamd_readmerge_count", "whamd_readmerge_super_count", "whamd_readmerge_edge_count",
+    "whamd_readmerge_get", "whamd_readmerge_get_edges", "whamd_readmerge_get_stats", "whamd_readmerge_destroy",
 ]
 
 

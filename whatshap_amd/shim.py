@@ -358,6 +358,41 @@ def compute_genotypes_factory(reference_core=None, device: int = 0):
     return compute_genotypes
 
 
+def read_merger_class(read_class=None, readset_class=None, device: int = 0):
+    """A class with the constructor and ``merge`` of the reference's ``ReadMerger`` (whatshap/merge.py:20-39) whose merging runs on the
+    device (``whatshap_amd.readmerge``).  With the reference's ``Read`` and ``ReadSet`` handed in, the merged reads come back as its own
+    objects, built as merge.py:185-200 builds them.  No fallback: a refusal raises."""
+    from . import readmerge as _readmerge
+
+    class ReadMerger(_readmerge.ReadMerger):
+        def __init__(self, error_rate, max_error_rate, positive_threshold, negative_threshold):
+            super().__init__(error_rate, max_error_rate, positive_threshold, negative_threshold, device=device)
+
+        def merge(self, readset):
+            _counters["read_merges"] = _counters.get("read_merges", 0) + 1
+            problem, result = self.merged(readset)
+            if read_class is None or readset_class is None:
+                return _readmerge.to_readset(result.merged_reads(problem))
+            return _readmerge.to_readset(result.merged_reads(problem), read_class, readset_class)
+
+    return ReadMerger
+
+
+def install_read_merger(phase_module, device: int = 0):
+    """Rebinds ``ReadMerger`` in ``phase_module`` (normally ``whatshap.cli.phase``, which binds it at ``:63`` and constructs it at
+    ``:374`` when ``--merge-reads`` is given): ``read_merger.merge(readset)`` (``:517-534``), the step in front of ``select_reads``,
+    then runs on the device.  The merged reads go back as the ``ReadSet`` ``phase_module`` imported (``:35``) of the ``Read``s of the
+    module that class comes from (``whatshap.core``).  ``DoNothingReadMerger`` stays.  Returns the previous binding: ``.bindings`` and
+    ``.restore()``."""
+    import sys
+
+    previous = _PreviousBindings(phase_module, {"ReadMerger": phase_module.ReadMerger})
+    readset_class = getattr(phase_module, "ReadSet", None)
+    read_class = getattr(phase_module, "Read", None) or getattr(sys.modules.get(getattr(readset_class, "__module__", None)), "Read", None)
+    phase_module.ReadMerger = read_merger_class(read_class, readset_class, device)
+    return previous
+
+
 def install_genotype_priors(genotype_module, reference_core=None, device: int = 0):
     """Rebinds ``compute_genotypes`` in ``genotype_module`` (normally ``whatshap.cli.genotype``, which binds it at import and calls it
     at ``:243`` for every sample and chromosome): the priors of ``whatshap genotype`` then come from the device, bit for bit the
