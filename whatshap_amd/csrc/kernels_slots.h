@@ -570,6 +570,12 @@ typedef uint32_t slot_u32x4 __attribute__((ext_vector_type(4)));
 // The block reads the ending read's 16-bit control field (n_end | slot << 2 | qmask << 7 | exchange buffer << 15) from a scalar register; the thread's tie
 // parities move down one bit per ending read; the record byte is stored from inside (offset register advanced by the workgroup's size).  Two exchange
 // buffers: the barrier of the next exchange also protects this one's reads.
+// The record store is NON-TEMPORAL.  Nothing reads the record before the backtrace, a whole forward pass later, yet a plain store leaves its lines dirty in the
+// L2 until the launch ends: 1.4 of the 3.4 MB a headline launch hands to the flush that stands between two dependent launches (the rest is the exit column,
+// which the next launch needs).  A wave's record store is one whole 64-byte piece, a byte from each lane, so no memory transaction is split.  Measured on the
+// flagship's chain, four libraries alternating in one visit, identical solutions (profiles/record_pairs/policy_ab.md): plain 7.72 us per launch, `sc1` and
+// `sc0 sc1` 7.62, `nt` 7.44 -- 70.2 -> 67.7 ms of forward pass, each figure within 0.02 us over three rounds.
+#define SLOTX_REC_POLICY " nt"
 #define SLOTX_ENDING_ASM                                                                                               \
 	"s_bfe_u32 %[sl], %[cw], 0x50002\n\t"          /* slot of the ending read: bits 2 .. 6 of its control field */     \
 	"s_cmp_lt_u32 %[sl], 8\n\t"                                                                                        \
@@ -637,7 +643,7 @@ typedef uint32_t slot_u32x4 __attribute__((ext_vector_type(4)));
 	"v_max_u32_e32 %[d1], %[d1], v61\n\t"                                                                              \
 	"v_addc_co_u32_e64 %[tk], %[qn], %[tk], %[tk], %[qt]\n\t"                                                          \
 	"v_max_u32_e32 %[d0], %[d0], v60\n\t"                                                                              \
-	"global_store_byte %[ro], %[tk], %[rb]\n\t"    /* the record byte of this thread and ending read: fire and forget */ \
+	"global_store_byte %[ro], %[tk], %[rb]" SLOTX_REC_POLICY "\n\t"    /* the record byte of this thread and ending read: fire and forget */ \
 	"v_add_u32_e32 %[ro], %[thr], %[ro]"
 
 // (prologue + column loop of an X run: leaves the thread's four cells in D; the exit -- slot_runx_exit -- is a call of its own so that a kernel whose run
@@ -1003,7 +1009,7 @@ __device__ __forceinline__ void slot_runx_lds_core(const DevProblem& P, const Sl
 	"v_max_u32_e32 %[d1], %[d1], v57\n\t"                                                                              \
 	"v_addc_co_u32_e64 %[tk], %[qn], %[tk], %[tk], %[qt]\n\t"                                                          \
 	"v_max_u32_e32 %[d0], %[d0], v56\n\t"                                                                              \
-	"global_store_byte %[ro], %[tk], %[rb]\n\t"                                                                        \
+	"global_store_byte %[ro], %[tk], %[rb]" SLOTX_REC_POLICY "\n\t"                                                      \
 	"v_add_u32_e32 %[ro], %[thr], %[ro]"
 
 // ---- Streamed operands: several workgroups per CU -- shared launches (slot_groupx<2 | 3>) and the runs that keep no LDS lines (slot_runx<2, 0>) -- fill each
