@@ -38,7 +38,7 @@ extern "C" {
 
 /* 2: whamd_plan_summary grew (n_yform_runs, n_fact_runs), whamd_solve_stats.group_tables / host_flatten_ms: a caller built against
  * version 1 must not be handed the larger structs -- bindings compare whamd_abi_version() with the header they were built from. */
-#define WHAMD_ABI_VERSION 3
+#define WHAMD_ABI_VERSION 4
 
 /* allele codes, identical to Entry::allele_t (src/entry.h:8) */
 #define WHAMD_ALLELE_REF 0
@@ -1117,6 +1117,82 @@ whamd_status_t whamd_poly_select_clusters(uint64_t n_pos, const uint64_t* pc_ptr
  * where the cluster has no row at p. */
 whamd_status_t whamd_poly_haplotypes(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
                                      const int8_t* pc_consensus, int device, int8_t* haplotypes_out, uint32_t* launches_out);
+
+/* ---- Polyphase threading DP (HaploThreader::computePaths of src/polyphase/haplothreader.cpp, as compute_threading_path calls it) ---------
+ * What lies between whamd_poly_select_clusters and whamd_poly_haplotypes.  One problem: the lists (cov_map) as CSR, any order within a
+ * position; per (position, cluster) row the total depth -- every listed cluster needs a row at its position, a re-added cluster one of
+ * depth 0 --; ploidy, the two switch costs, max_cluster_gap, block_starts (sections [block_starts[i], block_starts[i+1]), the last to the
+ * end; empty ones are skipped), row_limit (0 only).  The sections of all problems of a call are the jobs.
+ * Per column the tuples (multisets of `ploidy` clusters of the position's list) in the reference's enumeration order; coverage cost as
+ * getCoverageCost (double sum, float once), tuples above 30 + the column's smallest left out; score(t) = min over the column before of
+ * score(p) + cost(k) (float; cost(0) adds nothing), + coverage cost(t); cost(k) = float(switch_cost k + affine_switch_cost (k > 0)), k =
+ * ploidy - |p and t|.  Among equal sums the equivalent tuple, then the lower predecessor score, then the lower rank (place among the
+ * column's surviving tuples); the end of a section is its lowest score, then the lowest rank.  `ambiguous` of a section counts the
+ * decisions along the returned path that only the rank made, plus one if the end's score is not unique: where it is 0 the path is the
+ * reference's, slot order included; otherwise it is an optimal path.
+ * Device (csrc/polythreader_device.hip): count, scan (2), columns (one workgroup per section), backtrace:
+ * WHAMD_POLY_THREADER_LAUNCHES launches per call whatever the problems; smoothed coverages and log terms are host work inside the call.
+ * Errors, all with nothing launched unless said.  WHAMD_ERR_INVALID: a ploidy outside WHAMD_POLY_THREADER_MIN_PLOIDY ..
+ * WHAMD_POLY_THREADER_MAX_PLOIDY, row_limit other than 0, switch costs that are negative, NaN, not multiples of 2^-20 below 2^20 or for
+ * which some cost(k) is not exact in float, an empty list, a cluster listed twice at a position, a listed cluster without a depth row
+ * ("has no depth row"), block_starts that is empty, does not begin with 0 or decreases, a null array, offsets that decrease or do not
+ * start at 0.  WHAMD_ERR_UNSUPPORTED: more than WHAMD_POLY_THREADER_MAX_CLUSTERS clusters at a position, smoothed coverages of a
+ * position summing beyond int32, 2^32 - 4096 or more positions or tuples in one call, a backtrace store the device cannot hold (after
+ * the first three launches).  Never a truncated or approximate answer. */
+#define WHAMD_POLY_THREADER_MIN_PLOIDY 2u
+#define WHAMD_POLY_THREADER_MAX_PLOIDY 6u
+#define WHAMD_POLY_THREADER_MAX_CLUSTERS 8u
+#define WHAMD_POLY_THREADER_LAUNCHES 5u
+#define WHAMD_POLY_THREADER_WANT_COSTS 1u
+
+typedef struct whamd_poly_threader_view {
+	uint64_t n_positions;
+	const uint64_t* cov_ptr;            /* [n_positions + 1] */
+	const uint32_t* cov_cluster;        /* [cov_ptr[n_positions]] cluster ids */
+	const uint64_t* pc_ptr;             /* [n_positions + 1] the depth rows */
+	const uint32_t* pc_cluster;
+	const uint32_t* pc_total;           /* per row: depth over all alleles */
+	uint64_t n_block_starts;
+	const uint64_t* block_starts;
+	double switch_cost;
+	double affine_switch_cost;
+	uint32_t ploidy;
+	uint32_t max_cluster_gap;
+	uint32_t row_limit;                 /* 0 */
+	uint32_t flags;                     /* WHAMD_POLY_THREADER_WANT_COSTS: keep the coverage cost of every tuple */
+} whamd_poly_threader_view;
+
+typedef struct whamd_poly_threader_stats {
+	uint64_t n_positions;
+	uint64_t n_sections;
+	uint64_t n_tuples;                  /* of all columns */
+	uint64_t n_entries;                 /* of them: within 30 of their column's smallest coverage cost (backtrace records) */
+	uint32_t launches;                  /* kernel launches of the whole call: 0 or WHAMD_POLY_THREADER_LAUNCHES */
+	double host_ms;                     /* wall, whole call: validation, smoothed coverages, log terms */
+	double upload_ms;                   /* HIP events, whole call */
+	double kernel_ms;                   /* HIP events, whole call */
+	double download_ms;                 /* HIP events, whole call */
+	double total_ms;                    /* wall, whole call */
+} whamd_poly_threader_stats;
+
+typedef struct whamd_poly_threader_result whamd_poly_threader_result; /* opaque: the result of one whamd_poly_threader call */
+
+/* One call for a batch of problems: one upload, a constant number of launches. */
+whamd_status_t whamd_poly_threader(const whamd_poly_threader_view* problems, uint64_t n_problems, int device, whamd_poly_threader_result** out);
+uint64_t whamd_poly_threader_problem_count(const whamd_poly_threader_result* r);
+/* Positions, (non-empty) sections, list entries and kept tuple costs of problem m. */
+uint64_t whamd_poly_threader_position_count(const whamd_poly_threader_result* r, uint64_t m);
+uint64_t whamd_poly_threader_section_count(const whamd_poly_threader_result* r, uint64_t m);
+uint64_t whamd_poly_threader_cov_count(const whamd_poly_threader_result* r, uint64_t m);
+uint64_t whamd_poly_threader_cost_count(const whamd_poly_threader_result* r, uint64_t m);
+/* Problem m: paths_out [positions][ploidy] cluster ids in slot order; path_cost_out [positions] the coverage cost of the path's tuple;
+ * smoothed_out per list entry (computeCoverage); per section its first position, its score (the optimum) and `ambiguous`;
+ * all_costs_out (WANT_COSTS) the coverage cost of every tuple, positions in order, tuples in enumeration order.  NULL skips. */
+whamd_status_t whamd_poly_threader_get(const whamd_poly_threader_result* r, uint64_t m, uint32_t* paths_out, float* path_cost_out, uint32_t* smoothed_out,
+                                       uint64_t* section_first_out, float* score_out, uint32_t* ambiguous_out, float* all_costs_out);
+/* Counts of problem m; launches and times are those of the whole call. */
+whamd_status_t whamd_poly_threader_get_stats(const whamd_poly_threader_result* r, uint64_t m, whamd_poly_threader_stats* stats_out);
+void whamd_poly_threader_destroy(whamd_poly_threader_result* r);
 
 /* ---- Read merging (ReadMerger.merge of whatshap/merge.py; `whatshap phase --merge-reads`, cli/phase.py:517-534) ---------------------------
  * The step in front of the read selection.  One problem is one read set: the reads, IN THE ORDER GIVEN, as CSR of (position, allele,

@@ -268,6 +268,10 @@ whamd_status_t whamd_debug_poly_select_clusters_host(uint64_t n_pos, const uint6
 whamd_status_t whamd_debug_poly_haplotypes_host(const uint32_t* paths, uint64_t n_pos, uint32_t ploidy, const uint64_t* pc_ptr, const uint32_t* pc_cluster,
                                                 const int8_t* pc_consensus, int8_t* haplotypes_out);
 
+/* HOST-ONLY twin of the polyphase threading DP (csrc/polythreader.cpp): the same validation and host work, then the plain walk over all
+ * pairs of tuples of neighbouring columns on one host thread; bit-identical to the device: scores, paths, ambiguous. */
+whamd_status_t whamd_debug_poly_threader_host(const whamd_poly_threader_view* problems, uint64_t n_problems, whamd_poly_threader_result** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libwhatshap_amd.so")
 DEBUG_LIB_PATH = os.path.join(_HERE, "libwhatshap_amd_debug.so")   # test infrastructure (debug_lib)
-ABI_VERSION = 3   # WHAMD_ABI_VERSION of include/whatshap_amd.h this file mirrors (struct layouts below)
+ABI_VERSION = 4   # WHAMD_ABI_VERSION of include/whatshap_amd.h this file mirrors (struct layouts below)
 
 WHAMD_OK = 0
 WHAMD_ERR_INVALID = 1
@@ -268,6 +268,18 @@ class PolyThreadStats(Record):
         (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "fill_ms", "total_ms")]
 
 
+class PolyThreaderView(C.Structure):
+    _fields_ = [("n_positions", C.c_uint64), ("cov_ptr", C.POINTER(C.c_uint64)), ("cov_cluster", C.POINTER(C.c_uint32)), ("pc_ptr", C.POINTER(C.c_uint64)),
+                ("pc_cluster", C.POINTER(C.c_uint32)), ("pc_total", C.POINTER(C.c_uint32)), ("n_block_starts", C.c_uint64), ("block_starts", C.POINTER(C.c_uint64)),
+                ("switch_cost", C.c_double), ("affine_switch_cost", C.c_double), ("ploidy", C.c_uint32), ("max_cluster_gap", C.c_uint32),
+                ("row_limit", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PolyThreaderStats(Record):
+    _fields_ = [(name, C.c_uint64) for name in ("n_positions", "n_sections", "n_tuples", "n_entries")] + [("launches", C.c_uint32)] + [
+        (name, C.c_double) for name in ("host_ms", "upload_ms", "kernel_ms", "download_ms", "total_ms")]
+
+
 class ReadmergeView(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("read_ptr", C.POINTER(C.c_uint64)), ("entry_position", C.POINTER(C.c_int64)), ("entry_allele", C.POINTER(C.c_uint8)),
                 ("entry_quality", C.POINTER(C.c_int64)), ("representative", C.POINTER(C.c_uint32)), ("thr_diff", C.c_int64), ("thr_neg_diff", C.c_int64),
@@ -285,6 +297,11 @@ POLY_THREAD_LAUNCHES = 13       # WHAMD_POLY_THREAD_LAUNCHES of include/whatshap
 POLY_THREAD_MAX_PLOIDY = 16     # WHAMD_POLY_THREAD_MAX_PLOIDY
 POLY_THREAD_MAX_ALLELES = 16    # WHAMD_POLY_THREAD_MAX_ALLELES
 POLY_THREAD_DEPTHS_ONLY = 1     # WHAMD_POLY_THREAD_DEPTHS_ONLY
+POLY_THREADER_LAUNCHES = 5      # WHAMD_POLY_THREADER_LAUNCHES
+POLY_THREADER_MIN_PLOIDY = 2    # WHAMD_POLY_THREADER_MIN_PLOIDY
+POLY_THREADER_MAX_PLOIDY = 6    # WHAMD_POLY_THREADER_MAX_PLOIDY
+POLY_THREADER_MAX_CLUSTERS = 8  # WHAMD_POLY_THREADER_MAX_CLUSTERS
+POLY_THREADER_WANT_COSTS = 1    # WHAMD_POLY_THREADER_WANT_COSTS
 
 
 def _ptr(arr: Optional[np.ndarray], ctype):
@@ -472,6 +489,8 @@ def debug_lib() -> C.CDLL:
     L.whamd_debug_poly_haplotypes_host.restype = C.c_int
     L.whamd_debug_poly_haplotypes_host.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8),
                                                    C.POINTER(C.c_int8)]
+    L.whamd_debug_poly_threader_host.restype = C.c_int
+    L.whamd_debug_poly_threader_host.argtypes = [C.POINTER(PolyThreaderView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_readmerge_host.restype = C.c_int
     L.whamd_debug_readmerge_host.argtypes = [C.POINTER(ReadmergeView), C.c_uint64, C.POINTER(C.c_void_p)]
     L.whamd_debug_solve_kernels.restype = C.c_size_t
@@ -725,6 +744,20 @@ def _bind(L: C.CDLL, path: str) -> C.CDLL:
     L.whamd_poly_haplotypes.restype = C.c_int
     L.whamd_poly_haplotypes.argtypes = [C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int8), C.c_int,
                                         C.POINTER(C.c_int8), C.POINTER(C.c_uint32)]
+    L.whamd_poly_threader.restype = C.c_int
+    L.whamd_poly_threader.argtypes = [C.POINTER(PolyThreaderView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+    L.whamd_poly_threader_problem_count.restype = C.c_uint64
+    L.whamd_poly_threader_problem_count.argtypes = [C.c_void_p]
+    for name in ("whamd_poly_threader_position_count", "whamd_poly_threader_section_count", "whamd_poly_threader_cov_count", "whamd_poly_threader_cost_count"):
+        getattr(L, name).restype = C.c_uint64
+        getattr(L, name).argtypes = [C.c_void_p, C.c_uint64]
+    L.whamd_poly_threader_get.restype = C.c_int
+    L.whamd_poly_threader_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    L.whamd_poly_threader_get_stats.restype = C.c_int
+    L.whamd_poly_threader_get_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PolyThreaderStats)]
+    L.whamd_poly_threader_destroy.restype = None
+    L.whamd_poly_threader_destroy.argtypes = [C.c_void_p]
     L.whamd_readmerge.restype = C.c_int
     L.whamd_readmerge.argtypes = [C.POINTER(ReadmergeView), C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
     L.whamd_readmerge_problem_count.restype = C.c_uint64
@@ -780,6 +813,8 @@ EXPORTED_SYMBOLS = [
     "whamd_poly_thread_inputs", "whamd_poly_thread_problem_count", "whamd_poly_thread_position_count", "whamd_poly_thread_row_count",
     "whamd_poly_thread_cov_count", "whamd_poly_thread_get_rows", "whamd_poly_thread_get_cov", "whamd_poly_thread_get_stats", "whamd_poly_thread_destroy",
     "whamd_poly_select_clusters", "whamd_poly_haplotypes",
+    "whamd_poly_threader", "whamd_poly_threader_problem_count", "whamd_poly_threader_position_count", "whamd_poly_threader_section_count",
+    "whamd_poly_threader_cov_count", "whamd_poly_threader_cost_count", "whamd_poly_threader_get", "whamd_poly_threader_get_stats", "whamd_poly_threader_destroy",
     "whamd_readmerge", "whamd_readmerge_problem_count", "whamd_readmerge_count", "whamd_readmerge_super_count", "whamd_readmerge_edge_count",
     "whamd_readmerge_get", "whamd_readmerge_get_edges", "whamd_readmerge_get_stats", "whamd_readmerge_destroy",
 ]

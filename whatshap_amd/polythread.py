@@ -6,8 +6,13 @@ Per (position, cluster) the native library leaves the depth of every allele, the
 it (the reference's dict insertion order) and the consensus list; per position the clusters the threader may use, gap filling included.
 The transposition, the depths, the consensus lists and the selection run on the device; the sequential gap filling runs on the host
 inside the native call.  ``host=True`` takes the one-thread twin of the debug library instead (test infrastructure, the same bytes).
-``HaploThreader`` and ``force_genotypes`` are not here: a caller runs the reference's threader between :func:`select_clusters` and
-:func:`compute_haplotypes`, on what :func:`threading_inputs` returns.  There is no CPU fallback: without a device the native call raises.
+The threader itself, ``HaploThreader.computePaths`` as ``compute_threading_path`` calls it (lines 85-109), is here too:
+:func:`thread_batch` runs the DP over the tuples of every column on the device, one workgroup per section, any number of problems in one
+call; :func:`compute_threading_path` has the reference's signature and :func:`run_threading` chains inputs, threader and haplotypes
+without leaving arrays.  The optimum is the reference's bit for bit; the path is the reference's wherever ``ambiguous`` is 0, and an
+optimal one where the reference's own choice hangs on the iteration order of a hash map.  ``force_genotypes`` is not
+here: it stays the reference's function (it needs scipy), handed to :func:`run_threading` by the caller.  There is no CPU fallback:
+without a device the native call raises.
 """
 
 from __future__ import annotations
@@ -275,3 +280,162 @@ def threading_inputs(allele_matrix: AlleleMatrix, clustering, ploidy: int, max_c
         raise
     ad, cl = res._dicts()
     return {"cov_map": res.cov_map(), "allele_depths": ad, "cons_lists": cl, "switch_cost": res.switch_cost, "affine_switch_cost": res.affine_switch_cost}
+
+
+# ---------------------------------------------------------------------------------------------- the threader
+class ThreaderProblem:
+    """One problem of :func:`thread_batch` at array level: ``cov_ptr`` / ``cov_cluster`` (cov_map as CSR, any order within a position),
+    ``pc_ptr`` / ``pc_cluster`` / ``pc_total`` (per (position, cluster) row the depth over all alleles; every listed cluster needs a row),
+    ``ploidy`` (2 .. 6), the costs, ``max_cluster_gap``, ``block_starts`` and ``row_limit`` (0)."""
+
+    def __init__(self, cov_ptr, cov_cluster, pc_ptr, pc_cluster, pc_total, ploidy: int, switch_cost: float = 32.0, affine_switch_cost: float = 8.0,
+                 max_cluster_gap: int = 10, block_starts=(0,), row_limit: int = 0, want_costs: bool = False):
+        self.cov_ptr = np.ascontiguousarray(cov_ptr, dtype=np.uint64)
+        self.cov_cluster = np.ascontiguousarray(cov_cluster, dtype=np.uint32)
+        self.pc_ptr = np.ascontiguousarray(pc_ptr, dtype=np.uint64)
+        self.pc_cluster = np.ascontiguousarray(pc_cluster, dtype=np.uint32)
+        self.pc_total = np.ascontiguousarray(pc_total, dtype=np.uint32)
+        if len(self.cov_ptr) != len(self.pc_ptr) or len(self.cov_ptr) < 1:
+            raise ValueError("cov_ptr and pc_ptr must both hold positions + 1 offsets")
+        if len(self.cov_cluster) != int(self.cov_ptr[-1]) or len(self.pc_cluster) != int(self.pc_ptr[-1]) or len(self.pc_total) != len(self.pc_cluster):
+            raise ValueError("an array is not as long as its offsets say")
+        self.ploidy = int(ploidy)
+        if not 0 <= self.ploidy < 1 << 32:
+            raise ValueError(f"ploidy {ploidy} outside {_native.POLY_THREADER_MIN_PLOIDY} .. {_native.POLY_THREADER_MAX_PLOIDY}")
+        self.switch_cost, self.affine_switch_cost = float(switch_cost), float(affine_switch_cost)
+        if max_cluster_gap < 0:
+            raise ValueError("max_cluster_gap is negative")
+        self.max_cluster_gap = min(int(max_cluster_gap), 0xFFFFFFFF)
+        self.block_starts = np.ascontiguousarray(block_starts, dtype=np.uint64)
+        if not 0 <= int(row_limit) < 1 << 32:
+            raise ValueError(f"row_limit {row_limit}: only 0 (no limit) is supported")
+        self.row_limit = int(row_limit)
+        self.want_costs = bool(want_costs)
+
+    @classmethod
+    def from_inputs(cls, inputs: ThreadingInputs, switch_cost=None, affine_switch_cost=None, max_cluster_gap: int = 10, block_starts=(0,), **kw):
+        """From :class:`ThreadingInputs` directly.  A re-added cluster without a row at its position gets one of depth 0 (the reference
+        appends an empty dict there); the costs default to those of run_threading."""
+        n_pos = len(inputs.pc_ptr) - 1
+        total = inputs.pc_depth.sum(axis=1, dtype=np.uint64) if inputs.pc_depth.size else np.zeros(len(inputs.pc_cluster), dtype=np.uint64)
+        if total.size and total.max() > 0xFFFFFFFF:
+            raise ValueError("a depth outside uint32 (out of range)")
+        pc_ptr, pc_cluster, pc_total = inputs.pc_ptr, inputs.pc_cluster, total
+        readded = np.flatnonzero(inputs.cov_readded)
+        if readded.size:
+            pos_of = np.searchsorted(inputs.cov_ptr, readded, side="right") - 1
+            row_pos = np.repeat(np.arange(n_pos), np.diff(inputs.pc_ptr).astype(np.int64))
+            have = set(zip(row_pos.tolist(), inputs.pc_cluster.tolist()))
+            extra = [(int(x), int(inputs.cov_cluster[k])) for x, k in zip(pos_of.tolist(), readded.tolist()) if (int(x), int(inputs.cov_cluster[k])) not in have]
+            if extra:
+                all_pos = np.concatenate([row_pos, np.asarray([e[0] for e in extra], dtype=np.int64)])
+                order = np.argsort(all_pos, kind="stable")
+                pc_cluster = np.concatenate([inputs.pc_cluster, np.asarray([e[1] for e in extra], dtype=np.uint32)])[order]
+                pc_total = np.concatenate([total, np.zeros(len(extra), dtype=np.uint64)])[order]
+                pc_ptr = np.zeros(n_pos + 1, dtype=np.uint64)
+                np.cumsum(np.bincount(all_pos, minlength=n_pos), out=pc_ptr[1:])
+        return cls(inputs.cov_ptr, inputs.cov_cluster, pc_ptr, pc_cluster, pc_total, inputs.ploidy,
+                   inputs.switch_cost if switch_cost is None else switch_cost, inputs.affine_switch_cost if affine_switch_cost is None else affine_switch_cost,
+                   max_cluster_gap, block_starts, **kw)
+
+    def view(self) -> _native.PolyThreaderView:
+        P = _native._ptr
+        return _native.PolyThreaderView(len(self.cov_ptr) - 1, P(self.cov_ptr, C.c_uint64), P(self.cov_cluster, C.c_uint32), P(self.pc_ptr, C.c_uint64),
+                                        P(self.pc_cluster, C.c_uint32), P(self.pc_total, C.c_uint32), len(self.block_starts), P(self.block_starts, C.c_uint64),
+                                        self.switch_cost, self.affine_switch_cost, self.ploidy, self.max_cluster_gap, self.row_limit,
+                                        _native.POLY_THREADER_WANT_COSTS if self.want_costs else 0)
+
+
+class ThreadingResult:
+    """One problem of :func:`thread_batch`: ``paths`` uint32 [n_pos][ploidy] (cluster ids in slot order), per section ``section_first``,
+    ``score`` (float32: the optimum, the reference's bit for bit) and ``ambiguous`` (0: the path is the reference's); ``path_cost``
+    float32 [n_pos] (the coverage cost of the path's tuple), ``smoothed`` (computeCoverage, per cov_map entry), ``all_costs``
+    (``want_costs``: of every tuple, in enumeration order); ``stats``."""
+
+    ARRAYS = ("paths", "path_cost", "smoothed", "section_first", "score", "ambiguous", "all_costs")
+
+    def __init__(self, arrays, stats):
+        self.paths, self.path_cost, self.smoothed, self.section_first, self.score, self.ambiguous, self.all_costs = arrays
+        self.stats = stats
+
+    def tobytes(self) -> bytes:
+        return b"".join(getattr(self, name).tobytes() for name in self.ARRAYS)
+
+
+def thread_batch(problems: Sequence[ThreaderProblem], device: int = 0, host: bool = False) -> List[ThreadingResult]:
+    """Every problem in one native call: one upload, ``_native.POLY_THREADER_LAUNCHES`` launches whatever the problems; the sections of
+    all problems are the jobs.  ``IndexError`` for a cov_map cluster without a depth row, as the reference's ``.at()`` gives."""
+    P = _native._ptr
+    try:
+        handle = _native.batch_handle(host, [p.view() for p in problems], "whamd_poly_threader", "whamd_debug_poly_threader_host", "whamd_poly_threader_destroy",
+                                      device=device)
+        with handle as (L, h):
+            out = []
+            for k, p in enumerate(problems):
+                n_pos, n_sec = L.whamd_poly_threader_position_count(h, k), L.whamd_poly_threader_section_count(h, k)
+                n_cov, n_costs = L.whamd_poly_threader_cov_count(h, k), L.whamd_poly_threader_cost_count(h, k)
+                arrays = (np.zeros((n_pos, p.ploidy), dtype=np.uint32), np.zeros(n_pos, dtype=np.float32), np.zeros(n_cov, dtype=np.uint32),
+                          np.zeros(n_sec, dtype=np.uint64), np.zeros(n_sec, dtype=np.float32), np.zeros(n_sec, dtype=np.uint32), np.zeros(n_costs, dtype=np.float32))
+                _native.checked(L, L.whamd_poly_threader_get(h, k, P(arrays[0], C.c_uint32), P(arrays[1], C.c_float), P(arrays[2], C.c_uint32),
+                                                             P(arrays[3], C.c_uint64), P(arrays[4], C.c_float), P(arrays[5], C.c_uint32), P(arrays[6], C.c_float)))
+                out.append(ThreadingResult(arrays, _native.read_stats(L, "whamd_poly_threader_get_stats", _native.PolyThreaderStats, h, k)))
+            return out
+    except ValueError as e:
+        if "has no depth row" in str(e):
+            raise IndexError(str(e)) from e
+        raise
+
+
+def _threader_problem_from_dicts(cov_map, allele_depths, ploidy, switch_cost, affine_switch_cost, max_cluster_gap, **kw) -> ThreaderProblem:
+    n_pos = len(cov_map)
+    if len(allele_depths) != n_pos:
+        raise ValueError("cov_map and allele_depths differ in length")
+    cov_ptr, pc_ptr = np.zeros(n_pos + 1, dtype=np.uint64), np.zeros(n_pos + 1, dtype=np.uint64)
+    cov, cluster, total = [], [], []
+    for x in range(n_pos):
+        cov.extend(cov_map[x])
+        cov_ptr[x + 1] = len(cov)
+        for cid, depths in allele_depths[x].items():
+            cluster.append(cid)
+            total.append(sum(depths.values()))
+        pc_ptr[x + 1] = len(cluster)
+    for name, values in (("cluster id", cov), ("cluster id", cluster), ("depth", total)):
+        if values and (min(values) < 0 or max(values) > 0xFFFFFFFF):
+            raise ValueError(f"a {name} outside uint32 (out of range)")
+    return ThreaderProblem(cov_ptr, cov, pc_ptr, cluster, total, ploidy, switch_cost, affine_switch_cost, max_cluster_gap, **kw)
+
+
+def compute_threading_path(cov_map: List[List[int]], allele_depths: List[Dict[int, Dict[int, int]]], ploidy: int, switch_cost: float = 32.0,
+                           affine_switch_cost: float = 8.0, max_cluster_gap: int = 10, *, device: int = 0, host: bool = False) -> List[List[int]]:
+    """compute_threading_path (threading.py:85-109): the threading of ``ploidy`` haplotypes through the clusters, one list of cluster
+    ids per position.  ``ValueError`` for what the reference would run with a row limit (ploidy above 6) and for switch costs whose
+    ``cost(k)`` is not exact in float."""
+    if not len(cov_map):
+        return []
+    problem = _threader_problem_from_dicts(cov_map, allele_depths, ploidy, switch_cost, affine_switch_cost, max_cluster_gap)
+    return thread_batch([problem], device=device, host=host)[0].paths.tolist()
+
+
+def run_threading(allele_matrix: AlleleMatrix, clustering, ploidy: int, genotypes, distrust_genotypes: bool = False, max_cluster_gap: int = 10,
+                  error_rate: float = 0.05, *, force_genotypes=None, device: int = 0, host: bool = False):
+    """run_threading (threading.py:24-75): ``(paths, haplotypes)``, lists as there.  Inputs, threader and haplotypes stay arrays in
+    between.  ``force_genotypes`` is the reference's function (``whatshap.polyphase.threading.force_genotypes``), called as there unless
+    ``distrust_genotypes``; without it and with ``distrust_genotypes=False`` this raises instead of skipping the step."""
+    if not distrust_genotypes and force_genotypes is None:
+        raise ValueError("distrust_genotypes is False: pass force_genotypes (the reference's function); the step is never skipped silently")
+    try:
+        inputs = threading_inputs_batch([ThreadingProblem(allele_matrix, clustering, ploidy, max_cluster_gap)], device=device, host=host)[0]
+    except ValueError as e:
+        if "has no counted entry" in str(e):
+            raise IndexError("list index out of range") from e
+        raise
+    n_pos = len(inputs.pc_ptr) - 1
+    if not n_pos:
+        return [], [[] for _ in range(int(ploidy))]
+    result = thread_batch([ThreaderProblem.from_inputs(inputs, max_cluster_gap=max_cluster_gap)], device=device, host=host)[0]
+    assert len(result.paths) == n_pos
+    paths = result.paths.tolist()
+    haplotypes = haplotypes_from_inputs(result.paths, inputs, device=device, host=host).tolist()
+    if not distrust_genotypes:
+        haplotypes = force_genotypes(paths, haplotypes, genotypes, inputs.cov_map(), inputs.allele_depths(), error_rate)
+    return paths, haplotypes

@@ -393,6 +393,22 @@ def install_read_merger(phase_module, device: int = 0):
     return previous
 
 
+def install_threading(threading_module, device: int = 0):
+    """Rebinds ``compute_threading_path`` in ``threading_module`` (normally ``whatshap.polyphase.threading``, whose ``run_threading``
+    calls it at ``:56`` between ``select_clusters`` and ``compute_haplotypes``): the DP of ``HaploThreader`` then runs on the device.
+    The rest of the module -- ``get_allele_depths``, ``select_clusters``, ``compute_haplotypes``, ``force_genotypes`` -- is left alone.
+    Returns the previous binding: ``.bindings`` and ``.restore()``."""
+    from . import polythread
+
+    previous = _PreviousBindings(threading_module, {"compute_threading_path": threading_module.compute_threading_path})
+
+    def compute_threading_path(cov_map, allele_depths, ploidy, switch_cost=32.0, affine_switch_cost=8.0, max_cluster_gap=10):
+        return polythread.compute_threading_path(cov_map, allele_depths, ploidy, switch_cost, affine_switch_cost, max_cluster_gap, device=device)
+
+    threading_module.compute_threading_path = compute_threading_path
+    return previous
+
+
 def install_genotype_priors(genotype_module, reference_core=None, device: int = 0):
     """Rebinds ``compute_genotypes`` in ``genotype_module`` (normally ``whatshap.cli.genotype``, which binds it at import and calls it
     at ``:243`` for every sample and chromosome): the priors of ``whatshap genotype`` then come from the device, bit for bit the
